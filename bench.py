@@ -38,7 +38,9 @@ FLOP model, stated both ways: `frac` counts 60 flop per triangle test (SURVEY 8d
 scene at 250.7 tests and 4.65 bounces per sample, docs/dmt-mk_roofline_point.txt:2-6), i.e. shading + sampler flops this
 build did not count itself; `frac_tests_only` counts the triangle tests and node visits alone.
 A `secondary` array (N = 1, default workload only) carries BASELINE config 4 (1 M random triangles, BVH kernel) timed
-for a few steps after the headline's timed region, so that the driver's record holds a number for it as well.
+for the same --steps / --warmup after the headline's timed region, so that the driver's record holds a number for it as well.
+`--dump-outputs DIR` writes the headline's film after its last timed step (dump_outputs below), so that two builds can be
+compared output for output: scene, camera and sample sequence depend on the arguments alone.
 """
 import argparse
 import json
@@ -279,10 +281,37 @@ def oracle_band(O, width, height, spp, max_depth, want_rows, threads, film_mean)
     return parity, stats
 
 
+DUMP_LIMIT_BYTES = 64_000_000       # --dump-outputs: at most 64 MB in all
+DUMP_SAMPLE_SEED = 0x5EED1234
+
+
+def dump_outputs(out_dir, film_mean, film_m2, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the film (mean and M2, each
+    [H, W, 4] float32; M2's channel 3 is the sample count N) -- as out_dir/mean.npy and out_dir/m2.npy.  A film above
+    `limit` bytes in all is cut to a fixed, seeded sample of pixels (the same pixels on every run): mean.npy and m2.npy
+    are then [n, 4], and pixel_index.npy (float64) holds each row's flat index y * W + x.  Returns the files written."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    mean = np.ascontiguousarray(film_mean, dtype=np.float32)
+    m2 = np.ascontiguousarray(film_m2, dtype=np.float32)
+    arrays = {"mean": mean, "m2": m2}
+    if mean.nbytes + m2.nbytes > limit:
+        pixels = mean.shape[0] * mean.shape[1]
+        n = (limit - 4096) // (2 * 4 * 4 + 8)          # mean + M2 rows + one float64 index per pixel; 4 KiB for .npy headers
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(pixels, size=n, replace=False))
+        arrays = {"mean": mean.reshape(-1, 4)[idx], "m2": m2.reshape(-1, 4)[idx], "pixel_index": idx.astype(np.float64)}
+    files = []
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+        files.append(out / f"{name}.npy")
+    return files
+
+
 SECONDARY_WORKLOAD = "random1M_1024x1024_512spp_8bounces"
 
 
-def run_secondary(pkg, dev_index, stream_ptr, steps=2, warmup=1):
+def run_secondary(pkg, dev_index, stream_ptr, steps, warmup):
     """BASELINE config 4 after the headline's timed region (N = 1): scene + BVH build + upload untimed, then `steps`
     full passes (one launch each) between stream synchronisations.  Returns the `secondary` entry."""
     import numpy as np
@@ -339,7 +368,12 @@ def main():
     ap.add_argument("--parity-rows", type=int, default=0,
                     help="Cornell workloads without the cpu_baseline leg (N > 1, --no-cpu-baseline): check this many rows of the combined film "
                          "against the CPU oracle on rank 0 (untimed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film of the last timed step (rank 0) as DIR/mean.npy and DIR/m2.npy, float32, at most 64 MB "
+                         "in all (a larger film: a fixed, seeded sample of pixels plus DIR/pixel_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -451,6 +485,8 @@ def main():
     if rank == 0:
         film_mean = mean.cpu().numpy()
         film_m2 = m2.cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, film_mean, film_m2)
         counts_ok = bool((film_m2[..., 3] == spp).all()) and bool(np.isfinite(film_mean).all())
         info = r.kernel_info()
 
@@ -530,7 +566,7 @@ def main():
         secondary = None
         if world == 1 and args.workload == DEFAULT_WORKLOAD and not args.no_secondary:
             try:
-                secondary = [run_secondary(pkg, dev_index, stream.cuda_stream)]
+                secondary = [run_secondary(pkg, dev_index, stream.cuda_stream, args.steps, args.warmup)]
             except Exception as e:   # the headline line is printed regardless; the failure is part of the record
                 secondary = [{"workload": SECONDARY_WORKLOAD, "error": f"{type(e).__name__}: {e}"}]
         scene_text = {

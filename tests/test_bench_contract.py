@@ -116,3 +116,52 @@ def test_issue_view_uses_the_cycles_of_its_own_pass():
     assert abs(iv["raw"] - 1.0405) < 2e-3 and iv["valu_busy"] == 1.0 and abs(iv["clock_ghz"] - 2.3685) < 2e-3
     assert abs(iv["valu_insts_x4_per_simd_cycle"] - 1.0036) < 2e-3
     assert abs(r["valu_view"]["frac"] - 0.27) < 0.01 and abs(r["valu_view"]["frac_tests_only"] - 0.228) < 0.01
+
+
+def test_dump_outputs_writes_the_film(tmp_path):
+    """--dump-outputs: a film within the 64 MB limit is written whole, float32, as the caller receives it."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(1)
+    mean = rng.random((24, 40, 4), dtype=np.float32)
+    m2 = rng.random((24, 40, 4), dtype=np.float32)
+    files = b.dump_outputs(tmp_path / "d", mean, m2)
+    assert sorted(f.name for f in files) == ["m2.npy", "mean.npy"]
+    for name, want in (("mean", mean), ("m2", m2)):
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, want)
+
+
+def test_dump_outputs_samples_a_large_film_the_same_way_every_time(tmp_path):
+    """A film above the limit is cut to a fixed, seeded pixel sample: under the limit, identical from call to call, and
+    every row is the film's value at its stated pixel."""
+    import numpy as np
+    b = _bench()
+    h, w = 64, 96
+    mean = np.arange(h * w * 4, dtype=np.float32).reshape(h, w, 4)
+    m2 = -mean
+    limit = 40_000
+    written = []
+    for run in ("a", "b"):
+        files = b.dump_outputs(tmp_path / run, mean, m2, limit=limit)
+        assert sum(f.stat().st_size for f in files) <= limit
+        written.append({f.name: np.load(f) for f in files})
+    assert sorted(written[0]) == ["m2.npy", "mean.npy", "pixel_index.npy"]
+    for k in written[0]:
+        assert np.array_equal(written[0][k], written[1][k]), k
+    idx = written[0]["pixel_index.npy"]
+    assert idx.dtype == np.float64 and len(idx) > 100 and len(np.unique(idx)) == len(idx)
+    assert 0 <= idx.min() and idx.max() < h * w
+    flat = idx.astype(np.int64)
+    assert np.array_equal(written[0]["mean.npy"], mean.reshape(-1, 4)[flat])
+    assert np.array_equal(written[0]["m2.npy"], m2.reshape(-1, 4)[flat])
+
+
+def test_bench_rejects_a_step_count_below_one():
+    """--steps K sets the number of timed steps; K = 0 would time nothing, so it is an argument error (before any GPU work)."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr
+    src = (ROOT / "bench.py").read_text()
+    assert "for i in range(args.steps):" in src and "--dump-outputs" in src

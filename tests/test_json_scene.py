@@ -239,10 +239,8 @@ def test_fbx_reader_rejects_garbage(pkg, tmp_path):
 
 
 def test_fbx_reader_on_the_reference_asset(pkg):
-    """scenes/sphere.fbx of the reference (BASELINE config 3): present in the build container only."""
-    asset = Path("/root/reference/scenes/sphere.fbx")
-    if not asset.exists():
-        pytest.skip("reference assets are not on this machine")
+    """scenes/sphere.fbx of the reference (BASELINE config 3), byte for byte (data fixture under tests/golden/c3/)."""
+    asset = GOLDEN / "c3" / "sphere.fbx"
     t = pkg.host_scene.read_fbx(asset)
     assert t.shape == (480, 3, 3)                         # 1440 polygon-vertex indices, all triangles
     r = np.linalg.norm(t.reshape(-1, 3), axis=1)
