@@ -267,7 +267,7 @@ DMT_DEV void trav_leaf(BvhView const& bv, Traversal& tv, f3 o, f3 d, TraversalCo
   trav_leaf_ref<STATS>(bv, tv, o, d, tv.cur, tc);
   tv.cur = tv.tlim < 0.f ? kBvhEmpty : tv.stack.pop(bv);  // (a closest-hit limit is never negative)
 }
-// ---- whole traversals of one ray per lane (test kernels, lane_step<BVH>): the same step functions in a loop ----
+// ---- whole traversals of one ray per lane (test kernels, lane_step with kFeatBvh): the same step functions in a loop ----
 template <bool STATS>
 DMT_DEV void trav_run(BvhView const& bv, Traversal& tv, f3 o, f3 d, TraversalCounters* tc) {
   for (;;) {

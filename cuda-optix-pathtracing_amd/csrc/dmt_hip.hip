@@ -345,11 +345,25 @@ DMT_DEV f3 apply_material_textures(KArgs k, Rec32& rec, uint32_t matId, int tri,
 
 DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, int& bestTri, float& bu, float& bv, bool& occluded);
 
-template <bool ENV = false, bool AREA = false, int TEX = false, int LTREE = false, bool BVH = false>
+// Optional parts of the path-tracing code, one bit each: the template argument F of path_shade, lane_finish, lane_step,
+// megakernel_body(_bvh) and wf_shade_body.  featuresOf (host) computes a context's mask; DMT_MEGAKERNELS and
+// DMT_WF_SHADE_KERNELS list the masks that have a kernel.
+constexpr uint32_t kFeatBvh = 1u << 0;           // BVH traversal instead of the brute-force triangle pass
+constexpr uint32_t kFeatStats = 1u << 1;         // per-lane work counters (dmt_render_stats; never on the timed path)
+constexpr uint32_t kFeatEnv = 1u << 2;           // A18 env-map light
+constexpr uint32_t kFeatArea = 1u << 3;          // SURVEY 8f-3 emissive triangles
+constexpr uint32_t kFeatTex = 1u << 4;           // SURVEY 8f-1 image textures
+constexpr uint32_t kFeatBlend = 1u << 5;         // image textures + fractional "metallic" (BS_GGX_BLEND record pairs)
+constexpr uint32_t kFeatLightTree = 1u << 6;     // SURVEY 8f-4 light tree (light_tree.hpp)
+constexpr uint32_t kFeatLightTreeRef = 1u << 7;  // the reference-semantics light tree (light_tree_ref.hpp)
+
+template <uint32_t F>
 DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv) {
+  static_assert(!((F & kFeatLightTree) && (F & kFeatLightTreeRef)), "one light tree at a time");
+  static_assert(!((F & kFeatTex) && (F & kFeatBlend)), "kFeatBlend carries the texture code itself");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
-  if constexpr (ENV) {
+  if constexpr (F & kFeatEnv) {
     if (bestTri < 0) {  // A18: the env map seen by a path ray, MIS against NEE (core-render.cpp:154-163)
       EnvView const env = load_env(k);
       float pdfLight = 0.f;
@@ -374,7 +388,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   f3 const rd = ray_dir(st);
   Hit const hit = hit_finish(sc.post[bestTri], bu, bv, rd);
   uint32_t nAll = sc.lightCount;  // lights the NEE chooses among
-  if constexpr (AREA) {
+  if constexpr (F & kFeatArea) {
     KArgs const ka = kargs(k);
     nAll += ka->areaCount;
     uint32_t const ai = ka->areaOf[bestTri];
@@ -386,7 +400,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
         if (st.depth == 0 || st.lastSpecular) {
           st.L = st.L + st.beta * Le;
         } else {
-          float const a = st.lastPdf, b = pl * (ENV ? 0.5f : 1.f) / float(nAll);
+          float const a = st.lastPdf, b = pl * ((F & kFeatEnv) ? 0.5f : 1.f) / float(nAll);
           st.L = st.L + st.beta * Le * ((a * a) / (a * a + b * b));
         }
       }
@@ -399,11 +413,11 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   Rec32 rec = sc.bsdfs[hit.matId];
   f3 ns = hit.normal;  // shading normal: the geometric one unless a normal map says otherwise
   // fractional "metallic" (BS_GGX_BLEND, JSON scenes): both lobes of the material are prepared, evaluated and sampled and the
-  // results blended as the reference's CPU renderer does (core-material.cpp:275-286, :383-394).  TEX instantiations only.
+  // results blended as the reference's CPU renderer does (core-material.cpp:275-286, :383-394).  kFeatBlend instantiations only.
   Rec32 rec2{};
   float mix = 0.f;
   bool blend = false;
-  if constexpr (TEX >= 2) {
+  if constexpr (F & kFeatBlend) {
     if (hi16(rec.w[1]) == BS_GGX_BLEND) {
       mix = blend_metallic(k, rec, hit.matId, bestTri, bu, bv);
       rec.w[1] = (rec.w[1] & 0x0000FFFFu) | (uint32_t(BS_GGX_DIEL) << 16);
@@ -412,8 +426,8 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
       else blend = mix > 0.f;      // :272  metallic <= 0: the dielectric alone
     }
   }
-  if constexpr (TEX) {
-    if (TEX < 2 || kargs(k)->matTex != nullptr) {
+  if constexpr (F & (kFeatTex | kFeatBlend)) {
+    if (!(F & kFeatBlend) || kargs(k)->matTex != nullptr) {
       ns = apply_material_textures(k, rec, hit.matId, bestTri, bu, bv, hit.normal);
       if (blend) (void)apply_material_textures(k, rec2, hit.matId + 1u, bestTri, bu, bv, hit.normal);  // same roughness map
     }
@@ -430,7 +444,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
 #endif
   Bsdf const b = bsdf_prepare(rec, ns, wo);  // :165-166
   Bsdf b2{};
-  if constexpr (TEX >= 2) {
+  if constexpr (F & kFeatBlend) {
     if (blend) b2 = bsdf_prepare(rec2, ns, wo);
   }
   // f * weight and pdf of the material towards wi.  Blend: f = lerp(fD, fC, metallic), the RGB overload (a, b, t) of
@@ -440,7 +454,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   auto blend_pdf = [&](float pdfD, float pdfC) { return (1.f - pdfD) * pdfC + pdfD * mix; };
   auto eval_material = [&](f3 wi, float& pdf) {
     f3 f = eval_bsdf(b, wo, wi, ns, hit.normal, pdf) * b.weight;
-    if constexpr (TEX >= 2) {
+    if constexpr (F & kFeatBlend) {
       if (blend) {
         float pdfC = 0.f;
         f3 const fC = eval_bsdf(b2, wo, wi, ns, hit.normal, pdfC) * b2.weight;
@@ -456,7 +470,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   float uLight = st.rng.get1D();
   f2 const uLight2 = st.rng.get2D();
   bool envNee = false;
-  if constexpr (ENV) {  // A18: env map with probability 1/2, the light list otherwise (core-render.cpp:290-299)
+  if constexpr (F & kFeatEnv) {  // A18: env map with probability 1/2, the light list otherwise (core-render.cpp:290-299)
     envNee = uLight < 0.5f;
     uLight = envNee ? uLight : (uLight - 0.5f) * 2.f;
     if (envNee) {
@@ -476,7 +490,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
     }
   }
   bool areaNee = false;
-  if constexpr (AREA) {
+  if constexpr (F & kFeatArea) {
     uint32_t const li = pick_index(uLight, nAll);
     areaNee = !envNee && li >= sc.lightCount;
     if (areaNee) {
@@ -488,7 +502,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
         f3 const f = eval_material(as.wi, bsdfPdf);
         if (!is_zero(f)) {
           f3 const Le = mk3(ka->areaLe[3 * ai], ka->areaLe[3 * ai + 1], ka->areaLe[3 * ai + 2]);
-          float const a = as.pdf * (ENV ? 0.5f : 1.f) / float(nAll), bb = bsdfPdf;
+          float const a = as.pdf * ((F & kFeatEnv) ? 0.5f : 1.f) / float(nAll), bb = bsdfPdf;
           put_C(st.beta * (Le * f * (((a * a) / (a * a + bb * bb)) / a)));
           set_shadow_ray(st, offset_ray_origin(hit.pos, hit.error, hit.normal, as.wi), as.wi);
           st.smax = as.dist * 0.999f;
@@ -498,7 +512,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
     }
   }
   bool treeNee = false;
-  if constexpr (LTREE == 2) {
+  if constexpr (F & kFeatLightTreeRef) {
     // The reference's light tree with its own semantics (light_tree_ref.hpp): a cut of up to FOUR tree nodes, one light drawn
     // below each, one shadow ray per light (core-render.cpp:296-370).  This loop carries one pending shadow ray per lane, so
     // all but the LAST contributing light are tested for visibility right here (a whole any-hit traversal per ray; the
@@ -507,7 +521,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
     treeNee = !envNee && sc.lightCount > 1;
     if (treeNee) {
       LightTreeRefSelection const sel = ltr_select(kargs(k)->lightTreeRef, hit.pos.x, hit.pos.y, hit.pos.z, hit.normal.x, hit.normal.y,
-                                                   hit.normal.z, uLight, ENV ? 0.5f : 1.f);
+                                                   hit.normal.z, uLight, (F & kFeatEnv) ? 0.5f : 1.f);
       bool pending = false;
       f3 pendC = mk3(0, 0, 0), pendO = mk3(0, 0, 0), pendD = mk3(0, 0, 0);
       float pendMax = 0.f;
@@ -529,7 +543,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
         }
         if (pending) {  // an earlier light is waiting: resolve it now, keep this one pending
           bool occ;
-          if constexpr (BVH) {
+          if constexpr (F & kFeatBvh) {
             occ = bvh_any(load_bvh(k), true, pendO, pendD, pendMax, blockIdx.x * blockDim.x + threadIdx.x);
           } else {
             PathState tmp = st;
@@ -556,15 +570,15 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
     uint32_t li = 0;
     float pmf = 0.f;
     bool picked = true;
-    if constexpr (LTREE == 1) {  // importance-driven choice (light_tree.hpp) instead of the uniform pick
+    if constexpr (F & kFeatLightTree) {  // importance-driven choice (light_tree.hpp) instead of the uniform pick
       float treePmf = 0.f;
       int const sel = lt_select(kargs(k)->lightTree, hit.pos.x, hit.pos.y, hit.pos.z, hit.normal.x, hit.normal.y, hit.normal.z, uLight, treePmf);
       picked = sel >= 0;
       li = picked ? uint32_t(sel) : 0u;
-      pmf = (ENV ? 0.5f : 1.f) * treePmf;
+      pmf = ((F & kFeatEnv) ? 0.5f : 1.f) * treePmf;
     } else {
-      li = pick_index(uLight, AREA ? nAll : sc.lightCount);
-      pmf = (ENV ? 0.5f : 1.f) / float(AREA ? nAll : sc.lightCount);
+      li = pick_index(uLight, (F & kFeatArea) ? nAll : sc.lightCount);
+      pmf = ((F & kFeatEnv) ? 0.5f : 1.f) / float((F & kFeatArea) ? nAll : sc.lightCount);
     }
     Rec32 const light = sc.lights[li];
     LightSample const ls = sample_light(light, hit.pos, uLight2, st.lastT, hit.normal);
@@ -593,7 +607,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   f2 const u2 = st.rng.get2D();
   float const uc = st.rng.get1D();
   BsdfSample bs = sample_bsdf(b, wo, ns, hit.normal, u2, uc);
-  if constexpr (TEX >= 2) {
+  if constexpr (F & kFeatBlend) {
     if (blend) {  // core-material.cpp:275-286: both lobes sampled with the same numbers; direction and flags of the conductor's
       BsdfSample sC = sample_bsdf(b2, wo, ns, hit.normal, u2, uc);
       sC.f = bs.f * (1.f - mix) + sC.f * mix;
@@ -605,7 +619,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   sect_mark(8);
   if (!bs.valid()) return true;
   st.lastT = bs.refract;
-  if constexpr (ENV || AREA) st.lastPdf = bs.pdf, st.lastSpecular = bs.delta;
+  if constexpr (F & (kFeatEnv | kFeatArea)) st.lastPdf = bs.pdf, st.lastSpecular = bs.delta;
   set_ray(st, offset_ray_origin(hit.pos, hit.error, hit.normal, bs.wi), bs.wi);
   st.beta = st.beta * (bs.f * fabsf(dot(bs.wi, hit.normal)) / bs.pdf);
   float const rrBeta = max3(st.beta * bs.eta);
@@ -704,28 +718,28 @@ DMT_DEV void trace_pair_bvh(KArgs k, PathState const& st, bool doC, bool doS, ui
 
 // One "ray pass" of a lane: trace (closest + pending shadow), resolve the shadow ray, shade.
 // sink(L, sidx) is called once per completed sample with the index the sample was started with.
-template <bool ENV = false, bool AREA = false, int TEX = false, int LTREE = false, bool BVH = false, class Sink>
+template <uint32_t F, class Sink>
 DMT_DEV void lane_finish(KArgs k, PathState& st, bool doC, bool doS, int bestTri, float bu, float bv, bool occluded,
                          Sink&& sink);
 
-template <bool BVH, bool STATS = false, bool ENV = false, bool AREA = false, int TEX = false, int LTREE = false, class Sink>
+template <uint32_t F, class Sink>
 DMT_DEV void lane_step(KArgs k, uint32_t gtid, PathState& st, Sink&& sink, LaneStats* ls = nullptr) {
   bool const doC = st.active;
   bool const doS = st.hasShadow;
   int bestTri;
   float bu, bv;
   bool occluded;
-  if constexpr (BVH)
-    trace_pair_bvh<STATS>(k, st, doC, doS, gtid, bestTri, bu, bv, occluded, ls);
+  if constexpr (F & kFeatBvh)
+    trace_pair_bvh<(F & kFeatStats) != 0>(k, st, doC, doS, gtid, bestTri, bu, bv, occluded, ls);
   else
     trace_pair_brute(k, st, doC, doS, bestTri, bu, bv, occluded);
   sect_mark(2);
-  if constexpr (STATS) ls->bounces += (doC && bestTri >= 0 && st.depth < kargs(k)->maxDepth) ? 1u : 0u;
-  lane_finish<ENV, AREA, TEX, LTREE, BVH>(k, st, doC, doS, bestTri, bu, bv, occluded, sink);
+  if constexpr (F & kFeatStats) ls->bounces += (doC && bestTri >= 0 && st.depth < kargs(k)->maxDepth) ? 1u : 0u;
+  lane_finish<F & ~kFeatStats>(k, st, doC, doS, bestTri, bu, bv, occluded, sink);
 }
 
 // Second half of a ray pass: resolve the shadow ray (in the reference's accumulation order), then shade.
-template <bool ENV, bool AREA, int TEX, int LTREE, bool BVH, class Sink>
+template <uint32_t F, class Sink>
 DMT_DEV void lane_finish(KArgs k, PathState& st, bool doC, bool doS, int bestTri, float bu, float bv, bool occluded,
                          Sink&& sink) {
   if (doS) {
@@ -741,7 +755,7 @@ DMT_DEV void lane_finish(KArgs k, PathState& st, bool doC, bool doS, int bestTri
   }
   sect_mark(3);
   if (doC) {
-    if (path_shade<ENV, AREA, TEX, LTREE, BVH>(k, st, bestTri, bu, bv)) {
+    if (path_shade<F>(k, st, bestTri, bu, bv)) {
       st.active = false;
       if (st.hasShadow) {  // last NEE still untraced: park the sample, the lane may start the next
         put_Lfin(st.L);
@@ -1215,8 +1229,10 @@ DMT_DEV void flush_stats(KArgs Pk, LaneStats const& ls) {
   }
 }
 
-template <bool BVH, bool STATS = false, bool ENV = false, bool AREA = false, int TEX = false, int LTREE = false>
+template <uint32_t F>
 DMT_DEV void megakernel_body() {
+  static_assert(!(F & kFeatBvh), "BVH kernels run megakernel_body_bvh");
+  constexpr bool STATS = (F & kFeatStats) != 0;
   KArgs const Pk = kargs_base();
   LaneStats ls;
   int const lane = int(threadIdx.x) & 63;
@@ -1250,7 +1266,7 @@ DMT_DEV void megakernel_body() {
         }
       }
       sect_mark(1);
-      lane_step<BVH, STATS, ENV, AREA, TEX, LTREE>(Pk, gtid, st, sink, STATS ? &ls : nullptr);
+      lane_step<F>(Pk, gtid, st, sink, STATS ? &ls : nullptr);
     }
   }
 #if DMT_SECTION_TIMING
@@ -1275,8 +1291,10 @@ DMT_DEV void megakernel_body() {
 #ifndef DMT_BVH_DUMMY_LDS
 #define DMT_BVH_DUMMY_LDS 0  // occupancy experiments: extra LDS bytes per block (fewer resident blocks per CU)
 #endif
-template <bool STATS = false, bool ENV = false, bool AREA = false, int TEX = false, int LTREE = false>
+template <uint32_t F>
 DMT_DEV void megakernel_body_bvh() {
+  static_assert((F & kFeatBvh) != 0, "brute-force kernels run megakernel_body");
+  constexpr bool STATS = (F & kFeatStats) != 0;
   KArgs const Pk = kargs_base();
 #if DMT_BVH_DUMMY_LDS > 0
   __shared__ volatile char s_dummy[DMT_BVH_DUMMY_LDS];
@@ -1392,7 +1410,7 @@ DMT_DEV void megakernel_body_bvh() {
       if constexpr (STATS) ++ls.itShade, ls.lanesShade += tv.phase == TR_DONE ? 1u : 0u;
       if (tv.phase == TR_DONE) {
         if constexpr (STATS) ls.bounces += (st.active && tv.bestTri >= 0 && st.depth < kargs(Pk)->maxDepth) ? 1u : 0u;
-        lane_finish<ENV, AREA, TEX, LTREE, true>(Pk, st, st.active, st.hasShadow, tv.bestTri, tv.bu, tv.bv, st.smax < 0.f, sink);
+        lane_finish<F & ~kFeatStats>(Pk, st, st.active, st.hasShadow, tv.bestTri, tv.bu, tv.bv, st.smax < 0.f, sink);
         tv.phase = TR_IDLE;
       }
     }
@@ -1400,53 +1418,55 @@ DMT_DEV void megakernel_body_bvh() {
   flush_stats<STATS>(Pk, ls);
 }
 
-// brute force: the reference's semantics, every triangle tested (small scenes, parity mode)
-__global__ void __launch_bounds__(256, DMT_MIN_WAVES_PER_SIMD) k_megakernel(RenderParams P) { megakernel_body<false>(); }
-// BVH traversal (large scenes); 16 KB more LDS per block for the traversal stacks
-__global__ void __launch_bounds__(256, DMT_MIN_WAVES_PER_SIMD_BVH) k_megakernel_bvh(RenderParams P) { megakernel_body_bvh<false>(); }
-// same kernel with per-lane work counters (node visits, triangle tests, rays, bounces): feeds the
-// algorithmic-bytes model of the BVH path; never on the timed path
-__global__ void __launch_bounds__(256, 2) k_megakernel_bvh_stats(RenderParams P) { megakernel_body_bvh<true>(); }
-// A18: the same two kernels with the env-map light compiled in (dmt_upload_envmap selects them).  Separate
-// instantiations, so that the register allocation of the default kernels is not touched.
-__global__ void __launch_bounds__(256, 4) k_megakernel_env(RenderParams P) { megakernel_body<false, false, true>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_bvh_env(RenderParams P) { megakernel_body_bvh<false, true>(); }
-__global__ void __launch_bounds__(256, 2) k_megakernel_bvh_stats_env(RenderParams P) { megakernel_body_bvh<true, true>(); }
-// emissive triangles compiled in (dmt_upload_area_lights selects them)
-__global__ void __launch_bounds__(256, 4) k_megakernel_area(RenderParams P) { megakernel_body<false, false, false, true>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_bvh_area(RenderParams P) { megakernel_body_bvh<false, false, true>(); }
-// image textures compiled in (dmt_upload_textures selects them); with or without the env map
-__global__ void __launch_bounds__(256, 4) k_megakernel_tex(RenderParams P) { megakernel_body<false, false, false, false, true>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_bvh_tex(RenderParams P) { megakernel_body_bvh<false, false, false, true>(); }
-__global__ void __launch_bounds__(256, 4) k_megakernel_env_tex(RenderParams P) { megakernel_body<false, false, true, false, true>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_bvh_env_tex(RenderParams P) { megakernel_body_bvh<false, true, false, true>(); }
-// SURVEY 8f-1 fractional / textured "metallic": the texture kernels plus the two-lobe blend (a second prepared BSDF per lane:
-// one wave per SIMD fewer than the texture kernels, whose register allocation stays untouched)
-__global__ void __launch_bounds__(256, 3) k_megakernel_blend(RenderParams P) { megakernel_body<false, false, false, false, 2>(); }
-__global__ void __launch_bounds__(256, 2) k_megakernel_bvh_blend(RenderParams P) { megakernel_body_bvh<false, false, false, 2>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_env_blend(RenderParams P) { megakernel_body<false, false, true, false, 2>(); }
-__global__ void __launch_bounds__(256, 2) k_megakernel_bvh_env_blend(RenderParams P) { megakernel_body_bvh<false, true, false, 2>(); }
-// light tree compiled in (dmt_set_light_sampling(DMT_LIGHTS_TREE) selects them); with or without the env map
-__global__ void __launch_bounds__(256, 4) k_megakernel_ltree(RenderParams P) { megakernel_body<false, false, false, false, false, true>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_bvh_ltree(RenderParams P) { megakernel_body_bvh<false, false, false, false, true>(); }
-__global__ void __launch_bounds__(256, 4) k_megakernel_env_ltree(RenderParams P) { megakernel_body<false, false, true, false, false, true>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_bvh_env_ltree(RenderParams P) { megakernel_body_bvh<false, true, false, false, true>(); }
-// both optional light kinds at once
-// the reference-semantics light tree (light_tree_ref.hpp): cuts of up to four lights per bounce
-__global__ void __launch_bounds__(256, 3) k_megakernel_ltree2(RenderParams P) { megakernel_body<false, false, false, false, false, 2>(); }
-__global__ void __launch_bounds__(256, 2) k_megakernel_bvh_ltree2(RenderParams P) { megakernel_body_bvh<false, false, false, false, 2>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_env_ltree2(RenderParams P) { megakernel_body<false, false, true, false, false, 2>(); }
-__global__ void __launch_bounds__(256, 2) k_megakernel_bvh_env_ltree2(RenderParams P) { megakernel_body_bvh<false, true, false, false, 2>(); }
-__global__ void __launch_bounds__(256, 4) k_megakernel_env_area(RenderParams P) { megakernel_body<false, false, true, true>(); }
-__global__ void __launch_bounds__(256, 3) k_megakernel_bvh_env_area(RenderParams P) { megakernel_body_bvh<false, true, true>(); }
+// The megakernels, one per feature mask a launch can need: (name suffix, mask, minimum waves per SIMD, body).  The kernel
+// calls its body directly (one more inlined level in between changes the generated code).  Separate kernels, so that one
+// combination's register allocation never touches another's.  No suffix: brute force, the reference's semantics; _bvh: 16 KB
+// more LDS per block for the traversal stacks; _blend: a second prepared BSDF per lane, one wave per SIMD fewer than _tex.
+#define DMT_MEGAKERNELS(X)                                                          \
+  X(, 0, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                                   \
+  X(_bvh, kFeatBvh, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh)                \
+  X(_env, kFeatEnv, 4, megakernel_body)                                             \
+  X(_bvh_env, kFeatBvh | kFeatEnv, 3, megakernel_body_bvh)                          \
+  X(_area, kFeatArea, 4, megakernel_body)                                           \
+  X(_bvh_area, kFeatBvh | kFeatArea, 3, megakernel_body_bvh)                        \
+  X(_env_area, kFeatEnv | kFeatArea, 4, megakernel_body)                            \
+  X(_bvh_env_area, kFeatBvh | kFeatEnv | kFeatArea, 3, megakernel_body_bvh)         \
+  X(_tex, kFeatTex, 4, megakernel_body)                                             \
+  X(_bvh_tex, kFeatBvh | kFeatTex, 3, megakernel_body_bvh)                          \
+  X(_env_tex, kFeatEnv | kFeatTex, 4, megakernel_body)                              \
+  X(_bvh_env_tex, kFeatBvh | kFeatEnv | kFeatTex, 3, megakernel_body_bvh)           \
+  X(_blend, kFeatBlend, 3, megakernel_body)                                         \
+  X(_bvh_blend, kFeatBvh | kFeatBlend, 2, megakernel_body_bvh)                      \
+  X(_env_blend, kFeatEnv | kFeatBlend, 3, megakernel_body)                          \
+  X(_bvh_env_blend, kFeatBvh | kFeatEnv | kFeatBlend, 2, megakernel_body_bvh)       \
+  X(_ltree, kFeatLightTree, 4, megakernel_body)                                     \
+  X(_bvh_ltree, kFeatBvh | kFeatLightTree, 3, megakernel_body_bvh)                  \
+  X(_env_ltree, kFeatEnv | kFeatLightTree, 4, megakernel_body)                      \
+  X(_bvh_env_ltree, kFeatBvh | kFeatEnv | kFeatLightTree, 3, megakernel_body_bvh)   \
+  X(_ltree2, kFeatLightTreeRef, 3, megakernel_body)                                 \
+  X(_bvh_ltree2, kFeatBvh | kFeatLightTreeRef, 2, megakernel_body_bvh)              \
+  X(_env_ltree2, kFeatEnv | kFeatLightTreeRef, 3, megakernel_body)                  \
+  X(_bvh_env_ltree2, kFeatBvh | kFeatEnv | kFeatLightTreeRef, 2, megakernel_body_bvh)
+// the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
+// algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
+#define DMT_STATS_MEGAKERNELS(X)                                                    \
+  X(_bvh_stats, kFeatBvh | kFeatStats, 2, megakernel_body_bvh)                      \
+  X(_bvh_stats_env, kFeatBvh | kFeatStats | kFeatEnv, 2, megakernel_body_bvh)
+
+#define DMT_DEFINE_MEGAKERNEL(suffix, mask, waves, body) \
+  __global__ void __launch_bounds__(256, waves) k_megakernel##suffix(RenderParams P) { body<mask>(); }
+DMT_MEGAKERNELS(DMT_DEFINE_MEGAKERNEL)
+DMT_STATS_MEGAKERNELS(DMT_DEFINE_MEGAKERNEL)
 
 #include "wavefront.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // device unit-test kernels
 // ---------------------------------------------------------------------------------------------
-__global__ void k_test_trace(RenderParams P, bool useBvh, int n, int32_t const* pxs, int32_t const* pys,
-                             int32_t const* ss, float* L3) {
+// dmt_test_trace_samples: the radiance of single samples, shaded by the body of the megakernel row `F` (one instantiation
+// per row of DMT_MEGAKERNELS; the BVH rows trace each ray to completion instead of stepping the wave's traversal)
+template <uint32_t F>
+__global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t const* pys, int32_t const* ss, float* L3) {
   KArgs const k = kargs_base();
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
   PathState st{};
@@ -1456,52 +1476,7 @@ __global__ void k_test_trace(RenderParams P, bool useBvh, int n, int32_t const* 
   }
   auto store = [&](f3 L, uint32_t) { L3[3 * i] = L.x, L3[3 * i + 1] = L.y, L3[3 * i + 2] = L.z; };
   uint32_t const gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  for (;;) {
-    if (!__any(st.active || st.hasShadow)) break;
-    bool const useEnv = kargs(k)->env.w > 0;
-    if (kargs(k)->lightTree != nullptr) {
-      if (useEnv) {
-        if (useBvh)
-          lane_step<true, false, true, false, false, true>(k, gtid, st, store);
-        else
-          lane_step<false, false, true, false, false, true>(k, gtid, st, store);
-      } else if (useBvh) {
-        lane_step<true, false, false, false, false, true>(k, gtid, st, store);
-      } else {
-        lane_step<false, false, false, false, false, true>(k, gtid, st, store);
-      }
-    } else if (kargs(k)->matTex != nullptr) {
-      if (useEnv) {
-        if (useBvh)
-          lane_step<true, false, true, false, true>(k, gtid, st, store);
-        else
-          lane_step<false, false, true, false, true>(k, gtid, st, store);
-      } else if (useBvh) {
-        lane_step<true, false, false, false, true>(k, gtid, st, store);
-      } else {
-        lane_step<false, false, false, false, true>(k, gtid, st, store);
-      }
-    } else if (kargs(k)->areaCount > 0 && useEnv) {
-      if (useBvh)
-        lane_step<true, false, true, true>(k, gtid, st, store);
-      else
-        lane_step<false, false, true, true>(k, gtid, st, store);
-    } else if (kargs(k)->areaCount > 0) {
-      if (useBvh)
-        lane_step<true, false, false, true>(k, gtid, st, store);
-      else
-        lane_step<false, false, false, true>(k, gtid, st, store);
-    } else if (useEnv) {
-      if (useBvh)
-        lane_step<true, false, true>(k, gtid, st, store);
-      else
-        lane_step<false, false, true>(k, gtid, st, store);
-    } else if (useBvh) {
-      lane_step<true>(k, gtid, st, store);
-    } else {
-      lane_step<false>(k, gtid, st, store);
-    }
-  }
+  while (__any(st.active || st.hasShadow)) lane_step<F>(k, gtid, st, store);
 }
 
 // A18 probes: env-map sampling (u2 -> wi, pdf, uv, Le by uv) and evaluation by direction (wi -> Le, pdf)
@@ -1553,7 +1528,7 @@ __global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float*
         r[4] = st.beta.x, r[5] = st.beta.y, r[6] = st.beta.z, r[7] = st.L.x, r[8] = st.L.y, r[9] = st.L.z;
         r[10] = float(st.depth), r[11] = float(st.rng.dim);
       }
-      ended = path_shade(k, st, bestTri, bu, bv);
+      ended = path_shade<0>(k, st, bestTri, bu, bv);
       if (ended) st.active = false;
     }
     if (ended && !st.hasShadow) break;
@@ -1731,7 +1706,7 @@ struct dmt_ctx {
   uint32_t* d_matTex = nullptr;
   float* d_triUv = nullptr;
   uint32_t texCount = 0, matTexCount = 0;
-  bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_tex kernels carry that code
+  bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_blend kernels carry that code
   size_t triUvCount = 0;
   // wavefront form of the BVH path (wavefront.hpp)
   int bvhStrategy = 0;             // 0 = automatic (by launch size), 1 = megakernel, 2 = wavefront
@@ -1878,14 +1853,42 @@ SamplerParams computeSamplerParams(int width, int height) {
   return p;
 }
 
-// the light tree applies to plain point / spot light lists; textured or emissive-triangle scenes keep the uniform pick
-bool useLightTreeRef(dmt_ctx const* c) {
-  return !c->lightTreeTooDeep && c->lightSampling == DMT_LIGHTS_TREE_REFERENCE && c->lightCount > 1 && c->lightsTreeable && c->areaCount == 0 && c->texCount == 0 && !c->hasBlend;
-}
-bool useLightTree(dmt_ctx const* c) {
-  return !c->lightTreeTooDeep && c->lightSampling == DMT_LIGHTS_TREE && c->lightCount > 1 && c->lightsTreeable && c->areaCount == 0 && c->texCount == 0 && !c->hasBlend;
+// The feature mask (kFeat*) of what a launch of this context needs.  The light tree applies to plain point / spot light
+// lists; textured or emissive-triangle scenes keep the uniform pick.  A light tree not built yet counts as applying:
+// resolveFeatures builds it first.
+uint32_t featuresOf(dmt_ctx const* c) {
+  bool const treeable = !c->lightTreeTooDeep && c->lightCount > 1 && c->lightsTreeable && c->areaCount == 0 && c->texCount == 0 && !c->hasBlend;
+  uint32_t F = 0;
+  if (c->accel == DMT_ACCEL_BVH) F |= kFeatBvh;
+  if (c->env.w > 0) F |= kFeatEnv;
+  if (c->areaCount > 0) F |= kFeatArea;
+  if (c->hasBlend) F |= kFeatBlend;  // the blend kernels carry the texture code too
+  else if (c->texCount > 0) F |= kFeatTex;
+  if (treeable && c->lightSampling == DMT_LIGHTS_TREE) F |= kFeatLightTree;
+  if (treeable && c->lightSampling == DMT_LIGHTS_TREE_REFERENCE) F |= kFeatLightTreeRef;
+  return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
+// featuresOf once the light tree it asks for is built: a tree deeper than the walk's guard switches the context back to the
+// uniform pick (lightTreeTooDeep), which changes the kernel, its occupancy and the launch shape
+int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
+  if ((featuresOf(ctx) & (kFeatLightTree | kFeatLightTreeRef)) && !ctx->lightTreeValid) {
+    if (int const rc = ensureLightTree(ctx)) return rc;
+  }
+  *mask = featuresOf(ctx);
+  return DMT_OK;
+}
+// the combinations dmt_render refuses (mask | kFeatStats for dmt_render_stats / dmt_render_profile)
+int checkFeatures(dmt_ctx* ctx, uint32_t F) {
+  if ((F & kFeatStats) && (F & (kFeatTex | kFeatBlend | kFeatArea | kFeatLightTree | kFeatLightTreeRef)))
+    return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: the counting kernels exist for the plain and env-map BVH kernels only; "
+                                    "with textures, blended materials, emissive triangles or a light tree they would describe a different kernel");
+  if ((F & kFeatBlend) && (F & kFeatArea)) return fail(ctx, DMT_ERR_STATE, "dmt_render: fractional-metallic materials together with emissive triangles are not supported");
+  if ((F & kFeatTex) && (F & kFeatArea)) return fail(ctx, DMT_ERR_STATE, "dmt_render: image textures together with emissive triangles are not supported");
+  if (ctx->texCount > 0 && (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount))
+    return fail(ctx, DMT_ERR_STATE, "dmt_render: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
+  return DMT_OK;
+}
 
 SceneView sceneView(dmt_ctx const* c) {
   SceneView s;
@@ -1931,26 +1934,38 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.env = c->env;
   P.areaOf = c->d_areaOf, P.areaTri = c->d_areaTri, P.areaLe = c->d_areaLe, P.areaCount = c->areaCount;
   if (c->texCount > 0) P.texRgba = c->d_texRgba, P.texDesc = c->d_texDesc, P.matTex = c->d_matTex, P.triUv = c->d_triUv;
-  if (useLightTree(c) && c->lightTreeValid) P.lightTree = c->d_lightTree;
-  if (useLightTreeRef(c) && c->lightTreeValid) P.lightTreeRef = c->d_lightTreeRef;
+  uint32_t const F = featuresOf(c);
+  if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree;
+  if ((F & kFeatLightTreeRef) && c->lightTreeValid) P.lightTreeRef = c->d_lightTreeRef;
   return P;
 }
 
-// which megakernel a launch of this context runs: accelerator x optional light kinds x textures
-typedef void (*MegakernelFn)(RenderParams);
-MegakernelFn megakernelOf(dmt_ctx const* c) {
-  bool const bvh = c->accel == DMT_ACCEL_BVH, env = c->env.w > 0, area = c->areaCount > 0, tex = c->texCount > 0;
-  if (c->hasBlend) return bvh ? (env ? k_megakernel_bvh_env_blend : k_megakernel_bvh_blend) : (env ? k_megakernel_env_blend : k_megakernel_blend);
-  if (tex) return bvh ? (env ? k_megakernel_bvh_env_tex : k_megakernel_bvh_tex) : (env ? k_megakernel_env_tex : k_megakernel_tex);
-  if (useLightTreeRef(c)) return bvh ? (env ? k_megakernel_bvh_env_ltree2 : k_megakernel_bvh_ltree2) : (env ? k_megakernel_env_ltree2 : k_megakernel_ltree2);
-  if (useLightTree(c)) return bvh ? (env ? k_megakernel_bvh_env_ltree : k_megakernel_bvh_ltree) : (env ? k_megakernel_env_ltree : k_megakernel_ltree);
-  if (area && env) return bvh ? k_megakernel_bvh_env_area : k_megakernel_env_area;
-  if (area) return bvh ? k_megakernel_bvh_area : k_megakernel_area;
-  if (env) return bvh ? k_megakernel_bvh_env : k_megakernel_env;
-  return bvh ? k_megakernel_bvh : k_megakernel;
+// kernel tables: {mask, kernel} per row of the device-side lists; a mask without a row has no kernel (nullptr)
+template <class Fn>
+struct KernelRow { uint32_t mask; Fn fn; };
+template <class Fn, size_t N>
+Fn kernelOf(KernelRow<Fn> const (&rows)[N], uint32_t mask) {
+  for (KernelRow<Fn> const& r : rows) if (r.mask == mask) return r.fn;
+  return nullptr;
 }
-int blocksPerCuOf(dmt_ctx* c) {
-  void const* const fn = reinterpret_cast<void const*>(megakernelOf(c));
+int noKernel(dmt_ctx* ctx, char const* what, uint32_t mask) {
+  ctx->err = std::string(what) + ": no kernel is compiled for this combination of scene features (mask " + std::to_string(mask) + ")";
+  return DMT_ERR_STATE;
+}
+typedef void (*MegakernelFn)(RenderParams);
+typedef void (*WfKernelFn)(RenderParams, WfParams);
+typedef void (*TestTraceFn)(RenderParams, int, int32_t const*, int32_t const*, int32_t const*, float*);
+#define DMT_MEGAKERNEL_ROW(suffix, mask, waves, body) {mask, k_megakernel##suffix},
+#define DMT_WF_SHADE_ROW(suffix, mask, waves) {mask, k_wf_shade##suffix},
+#define DMT_TEST_TRACE_ROW(suffix, mask, waves, body) {mask, k_test_trace<mask>},
+KernelRow<MegakernelFn> const kMegakernels[] = {DMT_MEGAKERNELS(DMT_MEGAKERNEL_ROW) DMT_STATS_MEGAKERNELS(DMT_MEGAKERNEL_ROW)};
+KernelRow<WfKernelFn> const kWfShadeKernels[] = {DMT_WF_SHADE_KERNELS(DMT_WF_SHADE_ROW)};
+KernelRow<TestTraceFn> const kTestTraceKernels[] = {DMT_MEGAKERNELS(DMT_TEST_TRACE_ROW)};
+
+MegakernelFn megakernelOf(uint32_t mask) { return kernelOf(kMegakernels, mask); }
+// resident 256-thread blocks per CU of a kernel (cached per context)
+int blocksPerCuOf(dmt_ctx* c, MegakernelFn kernel) {
+  void const* const fn = reinterpret_cast<void const*>(kernel);
   for (auto const& e : c->occupancy)
     if (e.first == fn) return e.second;
   int n = 0;
@@ -2500,8 +2515,9 @@ int dmt_download_film(dmt_ctx* ctx, float* mean4, float* m24) {
 
 // Wavefront form of a BVH launch (wavefront.hpp): passes over (owned tiles, sample range), each pass a fixed sequence of
 // kernels on the context's stream.  `ownedTiles` = tiles this rank renders; P carries region / partition / film.
-static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, uint32_t sample_offset, uint32_t spp, bool useEnv,
-                           bool useArea, uint64_t* stats, int nstats) {
+// `shade` = the k_wf_shade* row of the launch's mask.
+static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, uint32_t sample_offset, uint32_t spp, WfKernelFn shade,
+                           uint64_t* stats, int nstats) {
   uint32_t const iters = uint32_t(ctx->maxDepth) + 2u;  // closest rays at depth 0..maxDepth, + one trailing shadow ray
   size_t const target = ctx->wfTargetPaths < 4096 ? 4096 : ctx->wfTargetPaths;
   uint32_t const tilesPerPass = uint32_t(std::min<size_t>(ownedTiles, std::max<size_t>(1, target / 64)));
@@ -2525,6 +2541,7 @@ static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, ui
   if (ctx->wfBlocksTrace == 0) {
     int a = 0, b = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, reinterpret_cast<void const*>(k_wf_trace), 256, 0);
+    // one shade grid for every variant: sized by the one with the most registers
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, reinterpret_cast<void const*>(k_wf_shade_env_area), 256, 0);
     ctx->wfBlocksTrace = a > 0 ? a : 1, ctx->wfBlocksShade = b > 0 ? b : 1;
   }
@@ -2539,6 +2556,7 @@ static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, ui
     HIP_TRY(ctx, hipMemsetAsync(dstats, 0, 16 * sizeof(unsigned long long), ctx->stream));
     P.stats = dstats;
   }
+  WfKernelFn const trace = stats ? k_wf_trace_stats : k_wf_trace;
   WfParams W{};
   W.state = ctx->d_wfState;
   W.queue[0] = ctx->d_wfQueue, W.queue[1] = ctx->d_wfQueue + slotsMax;
@@ -2557,23 +2575,8 @@ static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, ui
         // a persistent grid no larger than the pass: small passes do not pay for 2 048 idle blocks per launch
         uint32_t const tb = std::min<uint32_t>(traceBlocks, (W.slots + 255u) / 256u);
         uint32_t const sb = std::min<uint32_t>(shadeBlocks, (W.slots + 255u) / 256u);
-        if (stats) {
-          hipLaunchKernelGGL(k_wf_trace_stats, dim3(tb), dim3(256), 0, ctx->stream, P, W);
-          if (useEnv)
-            hipLaunchKernelGGL(k_wf_shade_stats_env, dim3(sb), dim3(256), 0, ctx->stream, P, W);
-          else
-            hipLaunchKernelGGL(k_wf_shade_stats, dim3(sb), dim3(256), 0, ctx->stream, P, W);
-          continue;
-        }
-        hipLaunchKernelGGL(k_wf_trace, dim3(tb), dim3(256), 0, ctx->stream, P, W);
-        if (useEnv && useArea)
-          hipLaunchKernelGGL(k_wf_shade_env_area, dim3(sb), dim3(256), 0, ctx->stream, P, W);
-        else if (useArea)
-          hipLaunchKernelGGL(k_wf_shade_area, dim3(sb), dim3(256), 0, ctx->stream, P, W);
-        else if (useEnv)
-          hipLaunchKernelGGL(k_wf_shade_env, dim3(sb), dim3(256), 0, ctx->stream, P, W);
-        else
-          hipLaunchKernelGGL(k_wf_shade, dim3(sb), dim3(256), 0, ctx->stream, P, W);
+        hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, ctx->stream, P, W);
+        hipLaunchKernelGGL(shade, dim3(sb), dim3(256), 0, ctx->stream, P, W);
       }
       if (!stats) hipLaunchKernelGGL(k_wf_fold, dim3((W.pixelSlots + 255u) / 256u), dim3(256), 0, ctx->stream, P, W);
       HIP_TRY(ctx, hipGetLastError());
@@ -2618,19 +2621,13 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   if (y1 > ctx->filmH) y1 = ctx->filmH;
   if (spp == 0 || x1 <= x0 || y1 <= y0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // the light tree is built before anything asks which kernel will run: a tree deeper than the walk's guard switches the
-  // context back to the uniform pick (lightTreeTooDeep), which changes the kernel, its occupancy and the launch shape
-  if ((useLightTree(ctx) || useLightTreeRef(ctx)) && !ctx->lightTreeValid) {
-    if (int const rcT = ensureLightTree(ctx)) return rcT;
-  }
-  if (stats6 && (ctx->texCount > 0 || ctx->hasBlend || ctx->areaCount > 0 || useLightTree(ctx) || useLightTreeRef(ctx)))
-    return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: the counting kernels exist for the plain and env-map BVH kernels only; "
-                                    "with textures, blended materials, emissive triangles or a light tree they would describe a different kernel");
+  uint32_t F = 0;
+  if (int const rc = resolveFeatures(ctx, &F)) return rc;
+  if (int const rc = checkFeatures(ctx, stats6 ? F | kFeatStats : F)) return rc;
+  MegakernelFn const kernel = megakernelOf(F);
+  if (!kernel) return noKernel(ctx, "dmt_render", F);
 
-  RenderParams P{};
-  P.scene = sceneView(ctx);
-  P.cam = ctx->xf;
-  P.sp = ctx->sp;
+  RenderParams P = baseParams(ctx, 0);
   P.mean = ctx->d_mean, P.m2 = ctx->d_m2, P.counter = ctx->d_counter;
   P.width = ctx->filmW, P.height = ctx->filmH;
   P.x0 = x0, P.y0 = y0, P.x1 = x1, P.y1 = y1;
@@ -2641,15 +2638,16 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   P.rank = ctx->rank, P.world = ctx->world;
   P.numItems = tiles > uint32_t(ctx->rank) ? (tiles - uint32_t(ctx->rank) + uint32_t(ctx->world) - 1) / uint32_t(ctx->world) : 0;
   P.sampleOffset = sample_offset, P.spp = spp;
-  P.maxDepth = ctx->maxDepth;
-  P.shadeThreshold = bvhShadeThreshold(ctx);
   if (P.numItems == 0) return DMT_OK;
   uint32_t const ownedTiles = P.numItems;
   // BVH launches run as the megakernel unless the wavefront form (wavefront.hpp) is asked for: on the measured scenes
   // the megakernel is faster (1 M triangles: 489 vs 378 Msamples/s), so "automatic" means megakernel
-  bool const wavefront = ctx->accel == DMT_ACCEL_BVH && ctx->bvhStrategy == 2 && ctx->texCount == 0 && !ctx->hasBlend && !useLightTree(ctx) && !useLightTreeRef(ctx);  // textures / blends / light tree: megakernels only
+  // (BVH masks without textures, blends or a light tree have a k_wf_shade* row)
+  WfKernelFn const wfShade = kernelOf(kWfShadeKernels, stats6 ? F | kFeatStats : F);
+  bool const wavefront = ctx->bvhStrategy == 2 && wfShade != nullptr;
+  int const blocksPerCu = blocksPerCuOf(ctx, kernel);
   {  // fewer owned tiles than ~4 per resident wave: schedule row bands of the tiles instead of whole tiles
-    uint32_t const waves = uint32_t(ctx->cuCount) * uint32_t(blocksPerCuOf(ctx)) * 4u;
+    uint32_t const waves = uint32_t(ctx->cuCount) * uint32_t(blocksPerCu) * 4u;
     P.subShift = ctx->subShift >= 0 ? uint32_t(ctx->subShift) : 0u;
     if (ctx->subShift < 0)
       while (P.subShift < 2u && (uint64_t(P.numItems) << P.subShift) < 4ull * waves) ++P.subShift;
@@ -2667,26 +2665,7 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
 
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   uint32_t const wavesWanted = P.numItems * P.numChunks < P.numItems ? P.numItems : P.numItems * P.numChunks;
-  uint32_t blocks = uint32_t(ctx->cuCount) * uint32_t(blocksPerCuOf(ctx));
-  bool const useEnv = ctx->env.w > 0;
-  bool const useArea = ctx->areaCount > 0;
-  P.env = ctx->env;
-  P.areaOf = ctx->d_areaOf, P.areaTri = ctx->d_areaTri, P.areaLe = ctx->d_areaLe, P.areaCount = ctx->areaCount;
-  if (ctx->hasBlend && useArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: fractional-metallic materials together with emissive triangles are not supported");
-  if (ctx->texCount > 0) {
-    if (useArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: image textures together with emissive triangles are not supported");
-    if (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount)
-      return fail(ctx, DMT_ERR_STATE, "dmt_render: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
-    P.texRgba = ctx->d_texRgba, P.texDesc = ctx->d_texDesc, P.matTex = ctx->d_matTex, P.triUv = ctx->d_triUv;
-  }
-  if (useLightTree(ctx)) {
-    if (int const rcT = ensureLightTree(ctx)) return rcT;
-    P.lightTree = ctx->d_lightTree;
-  }
-  if (useLightTreeRef(ctx)) {
-    if (int const rcT = ensureLightTree(ctx)) return rcT;
-    P.lightTreeRef = ctx->d_lightTreeRef;
-  }
+  uint32_t blocks = uint32_t(ctx->cuCount) * uint32_t(blocksPerCu);
   uint32_t const blocksNeeded = (wavesWanted + 3) / 4;
   if (blocks > blocksNeeded) blocks = blocksNeeded;
   if (blocks == 0) blocks = 1;
@@ -2723,14 +2702,14 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
   HIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream));
   uint64_t const launchFolds = uint64_t(P.numItems) * P.numChunks;  // every item is folded exactly once (checkErrorFlag)
-  if (useBvh && wavefront) {
+  if (wavefront) {
     if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render: BVH not built");
-    int const rcW = launchWavefront(ctx, P, ownedTiles, sample_offset, spp, useEnv, useArea, stats6, nstats);
+    int const rcW = launchWavefront(ctx, P, ownedTiles, sample_offset, spp, wfShade, stats6, nstats);
     if (rcW) return rcW;
     if (stats6) return DMT_OK;
   } else if (useBvh) {
     if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render: BVH not built");
-    int const rcO = ensureOverflow(ctx, size_t(ctx->cuCount) * size_t(std::max(blocksPerCuOf(ctx), ctx->blocksPerCUBvh)) * 256);
+    int const rcO = ensureOverflow(ctx, size_t(ctx->cuCount) * size_t(std::max(blocksPerCu, ctx->blocksPerCUBvh)) * 256);
     if (rcO) return rcO;
     P.bvh = bvhView(ctx, size_t(blocks) * 256);
     if (stats6) {
@@ -2738,10 +2717,7 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
       HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dstats), 16 * sizeof(unsigned long long)));
       HIP_TRY(ctx, hipMemsetAsync(dstats, 0, 16 * sizeof(unsigned long long), ctx->stream));
       P.stats = dstats;
-      if (useEnv)
-        hipLaunchKernelGGL(k_megakernel_bvh_stats_env, dim3(blocks), dim3(256), 0, ctx->stream, P);
-      else
-        hipLaunchKernelGGL(k_megakernel_bvh_stats, dim3(blocks), dim3(256), 0, ctx->stream, P);
+      hipLaunchKernelGGL(megakernelOf(F | kFeatStats), dim3(blocks), dim3(256), 0, ctx->stream, P);
       hipError_t e = hipGetLastError();
       if (e == hipSuccess) ctx->expectedFolds += launchFolds;
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -2750,12 +2726,12 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
       HIP_TRY(ctx, e);
       return DMT_OK;
     }
-    hipLaunchKernelGGL(megakernelOf(ctx), dim3(blocks), dim3(256), 0, ctx->stream, P);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, ctx->stream, P);
   } else {
-    hipLaunchKernelGGL(megakernelOf(ctx), dim3(blocks), dim3(256), 0, ctx->stream, P);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, ctx->stream, P);
   }
   HIP_TRY(ctx, hipGetLastError());
-  if (!(useBvh && wavefront)) ctx->expectedFolds += launchFolds;
+  if (!wavefront) ctx->expectedFolds += launchFolds;
   HIP_TRY(ctx, hipEventRecord(ev.second, ctx->stream));
   ++ctx->eventsUsed;
   return DMT_OK;
@@ -3053,14 +3029,16 @@ int dmt_kernel_time(dmt_ctx* ctx, double* total_ms, uint64_t* launches, int rese
 
 int dmt_kernel_info(dmt_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* blocks_per_cu, int* cu_count) {
   if (!ctx) return DMT_ERR_INVALID;
+  uint32_t F = 0;  // facts of the kernel dmt_render would launch now
+  if (int const rc = resolveFeatures(ctx, &F)) return rc;
+  MegakernelFn const kernel = megakernelOf(F);
+  if (!kernel) return noKernel(ctx, "dmt_kernel_info", F);
   hipFuncAttributes attr{};
-  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;  // facts of the kernel dmt_render would launch now
-  HIP_TRY(ctx, hipFuncGetAttributes(&attr, useBvh ? reinterpret_cast<void const*>(k_megakernel_bvh)
-                                                  : reinterpret_cast<void const*>(k_megakernel)));
+  HIP_TRY(ctx, hipFuncGetAttributes(&attr, reinterpret_cast<void const*>(kernel)));
   if (vgprs) *vgprs = attr.numRegs;
   if (sgprs) *sgprs = 0;
   if (lds_bytes) *lds_bytes = int(attr.sharedSizeBytes);
-  if (blocks_per_cu) *blocks_per_cu = blocksPerCuOf(ctx);
+  if (blocks_per_cu) *blocks_per_cu = blocksPerCuOf(ctx, kernel);
   if (cu_count) *cu_count = ctx->cuCount;
   return DMT_OK;
 }
@@ -3225,15 +3203,17 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
   int32_t* dss = S.up(ss, size_t(n));
   float* dL = S.up<float>(nullptr, 3 * size_t(n));
   SCRATCH_CHECK(ctx, dpx && dpy && dss && dL);
-  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
+  uint32_t F = 0;  // the shading body dmt_render would run
+  if (int const rc = resolveFeatures(ctx, &F)) return rc;
+  TestTraceFn const kernel = kernelOf(kTestTraceKernels, F);
+  if (!kernel) return noKernel(ctx, "dmt_test_trace_samples", F);
   size_t const threads = size_t((n + 63) / 64) * 64;
-  if (useBvh) {
+  if (F & kFeatBvh) {
     if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_samples: BVH not built");
     int const rcO = ensureOverflow(ctx, threads);
     if (rcO) return rcO;
   }
-  hipLaunchKernelGGL(k_test_trace, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, baseParams(ctx, threads), useBvh, n,
-                     dpx, dpy, dss, dL);
+  hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, baseParams(ctx, threads), n, dpx, dpy, dss, dL);
   int rc = finishTest(ctx);
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpy(L3, dL, size_t(n) * 12, hipMemcpyDeviceToHost));

@@ -223,8 +223,10 @@ __global__ void __launch_bounds__(256, DMT_WF_TRACE_WAVES) k_wf_trace(RenderPara
 __global__ void __launch_bounds__(256, 4) k_wf_trace_stats(RenderParams P, WfParams W) { wf_trace_body<true>(W); }
 
 // ---- shade ------------------------------------------------------------------------------------------------
-template <bool ENV, bool AREA, bool STATS>
+template <uint32_t F>
 DMT_DEV void wf_shade_body(WfParams const& W) {
+  static_assert(!(F & (kFeatTex | kFeatBlend | kFeatLightTree | kFeatLightTreeRef)), "megakernels only");
+  constexpr bool STATS = (F & kFeatStats) != 0;
   KArgs const Pk = kargs_base();
   int const lane = int(threadIdx.x) & 63;
   uint32_t const count = W.counts[W.it];
@@ -266,13 +268,13 @@ DMT_DEV void wf_shade_body(WfParams const& W) {
         st.active = true, st.hasShadow = false;
         int const tri = reinterpret_cast<int32_t const*>(wf_plane(W, WF_HIT_TRI))[path];
         if constexpr (STATS) ls.bounces += (tri >= 0 && st.depth < kargs(Pk)->maxDepth) ? 1u : 0u;
-        bool const ended = path_shade<ENV, AREA>(Pk, st, tri, wf_plane(W, WF_HIT_U)[path], wf_plane(W, WF_HIT_V)[path]);
+        bool const ended = path_shade<F & ~(kFeatBvh | kFeatStats)>(Pk, st, tri, wf_plane(W, WF_HIT_U)[path], wf_plane(W, WF_HIT_V)[path]);
         changedL = true;
         if (!ended) {
           wf_plane(W, WF_OX)[path] = st.rp.ox.x, wf_plane(W, WF_OY)[path] = st.rp.oy.x, wf_plane(W, WF_OZ)[path] = st.rp.oz.x;
           wf_plane(W, WF_DX)[path] = st.rp.dx.x, wf_plane(W, WF_DY)[path] = st.rp.dy.x, wf_plane(W, WF_DZ)[path] = st.rp.dz.x;
           wf_plane(W, WF_BX)[path] = st.beta.x, wf_plane(W, WF_BY)[path] = st.beta.y, wf_plane(W, WF_BZ)[path] = st.beta.z;
-          if constexpr (ENV || AREA) wf_plane(W, WF_LASTPDF)[path] = st.lastPdf;
+          if constexpr (F & (kFeatEnv | kFeatArea)) wf_plane(W, WF_LASTPDF)[path] = st.lastPdf;
         }
         if (st.hasShadow) {
           wf_plane(W, WF_SOX)[path] = st.rp.ox.y, wf_plane(W, WF_SOY)[path] = st.rp.oy.y, wf_plane(W, WF_SOZ)[path] = st.rp.oz.y;
@@ -292,12 +294,17 @@ DMT_DEV void wf_shade_body(WfParams const& W) {
   }
   flush_stats<STATS>(Pk, ls);
 }
-__global__ void __launch_bounds__(256, 4) k_wf_shade(RenderParams P, WfParams W) { wf_shade_body<false, false, false>(W); }
-__global__ void __launch_bounds__(256, 4) k_wf_shade_env(RenderParams P, WfParams W) { wf_shade_body<true, false, false>(W); }
-__global__ void __launch_bounds__(256, 4) k_wf_shade_area(RenderParams P, WfParams W) { wf_shade_body<false, true, false>(W); }
-__global__ void __launch_bounds__(256, 4) k_wf_shade_env_area(RenderParams P, WfParams W) { wf_shade_body<true, true, false>(W); }
-__global__ void __launch_bounds__(256, 2) k_wf_shade_stats(RenderParams P, WfParams W) { wf_shade_body<false, false, true>(W); }
-__global__ void __launch_bounds__(256, 2) k_wf_shade_stats_env(RenderParams P, WfParams W) { wf_shade_body<true, false, true>(W); }
+// (name suffix, mask, minimum waves per SIMD) of the shade kernels, as DMT_MEGAKERNELS; launchWavefront picks the row
+#define DMT_WF_SHADE_KERNELS(X)                              \
+  X(, kFeatBvh, 4)                                           \
+  X(_env, kFeatBvh | kFeatEnv, 4)                            \
+  X(_area, kFeatBvh | kFeatArea, 4)                          \
+  X(_env_area, kFeatBvh | kFeatEnv | kFeatArea, 4)           \
+  X(_stats, kFeatBvh | kFeatStats, 2)                        \
+  X(_stats_env, kFeatBvh | kFeatStats | kFeatEnv, 2)
+#define DMT_DEFINE_WF_SHADE(suffix, mask, waves) \
+  __global__ void __launch_bounds__(256, waves) k_wf_shade##suffix(RenderParams P, WfParams W) { wf_shade_body<mask>(W); }
+DMT_WF_SHADE_KERNELS(DMT_DEFINE_WF_SHADE)
 
 // ---- fold -------------------------------------------------------------------------------------------------
 // One lane per pixel: running (mean, M2, N) of the film + the pass's n radiances in sample order
