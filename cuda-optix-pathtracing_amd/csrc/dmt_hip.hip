@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -681,7 +682,7 @@ DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, 
   uint32_t const last = n ? n - 1 : 0;
   DMT_TRI_DECL(a);
   DMT_TRI_DECL(b);
-  DMT_TRI_LOAD(a, 0);  // the array always holds >= 1 record (devAlloc)
+  DMT_TRI_LOAD(a, 0);  // the array always holds >= 1 record (DevBuf::assign)
   for (uint32_t i = 0; i < n;) {
     uint32_t const ib = i + 1 < last ? i + 1 : last;
     DMT_TRI_LOAD(b, ib);
@@ -1664,27 +1665,66 @@ __global__ void k_test_closest(RenderParams P, bool useBvh, int n, float const* 
 // =============================================================================================
 // host side of the C ABI
 // =============================================================================================
+// Owner of one device array of T: hipFree on destruction, movable, not copyable.  Every device allocation of the
+// host side goes through this type.
+template <class T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) reset(), p_ = o.p_, n_ = o.n_, o.p_ = nullptr, o.n_ = 0;
+    return *this;
+  }
+  DevBuf(DevBuf const&) = delete;
+  DevBuf& operator=(DevBuf const&) = delete;
+  ~DevBuf() { reset(); }
+  T* get() const { return p_; }
+  size_t size() const { return n_; }  // elements allocated
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr, n_ = 0;
+  }
+  // room for at least n elements, contents not kept.  The old array is freed before the new one is allocated, so a
+  // large scratch buffer never exists twice; on failure the buffer is empty.
+  hipError_t reserve(size_t n) {
+    if (n_ >= n) return hipSuccess;
+    reset();
+    hipError_t const e = hipMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T));
+    if (e != hipSuccess) p_ = nullptr;
+    else n_ = n;
+    return e;
+  }
+  // max(n, 1) elements holding the n elements of T at `host`
+  hipError_t assign(void const* host, size_t n) {
+    hipError_t e = reserve(n ? n : 1);
+    if (e == hipSuccess && n) e = hipMemcpy(p_, host, n * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
+
 struct dmt_ctx {
   int device = 0;
   hipStream_t ownStream = nullptr;
   hipStream_t stream = nullptr;
   std::string err;
   // scene
-  TriIsect* d_tris = nullptr;
-  TriPost* d_post = nullptr;
-  Rec32* d_bsdfs = nullptr;
-  Rec32* d_lights = nullptr;
-  Rec32* d_inf = nullptr;
+  DevBuf<TriIsect> d_tris;
+  DevBuf<TriPost> d_post;
+  DevBuf<Rec32> d_bsdfs, d_lights, d_inf;
   uint32_t triCount = 0, bsdfCount = 0, lightCount = 0, infCount = 0;
   uint32_t maxMatId = 0;
   // BVH (built on demand for DMT_ACCEL_BVH)
   std::vector<float> h_xs, h_ys, h_zs;  // host copy of the soup (the builder's input)
   std::vector<uint32_t> h_mat;
-  Bvh4Node* d_bvhNodes = nullptr;
+  DevBuf<Bvh4Node> d_bvhNodes;
   int shadeThresholdEnv = 0;  // DMT_BVH_SHADE_THRESHOLD from the environment, 0 = choose by tree size
-  TriPair* d_trisBvh = nullptr;   // leaf storage of the BVH
-  uint32_t* d_overflow = nullptr;
-  size_t overflowThreads = 0;
+  DevBuf<TriPair> d_trisBvh;   // leaf storage of the BVH
+  DevBuf<uint32_t> d_overflow;  // kBvhOverflowStack words per thread
   bool haveBvh = false;
   int bvhDepth = 0;
   uint32_t bvhNodeCount = 0, bvhPairCount = 0;
@@ -1692,35 +1732,34 @@ struct dmt_ctx {
   // light tree (light_tree.hpp): built from the uploaded lights when dmt_set_light_sampling asks for it
   int lightSampling = DMT_LIGHTS_UNIFORM;
   std::vector<uint8_t> h_lights;  // host copy of the packed light records
-  LightTreeNode* d_lightTree = nullptr;
-  LightTreeRefNode* d_lightTreeRef = nullptr;  // DMT_LIGHTS_TREE_REFERENCE
+  DevBuf<LightTreeNode> d_lightTree;
+  DevBuf<LightTreeRefNode> d_lightTreeRef;  // DMT_LIGHTS_TREE_REFERENCE
   uint32_t lightTreeNodes = 0;
   int lightTreeDepth = 0;
   bool lightTreeValid = false;
   bool lightTreeTooDeep = false;   // the last build exceeded the walk's depth guard: the uniform pick is used instead (dmt_last_error says so)
   bool lightsTreeable = false;     // every record of the light list is a point or spot light
   std::vector<std::pair<void const*, int>> occupancy;  // megakernel variant -> resident 256-thread blocks per CU
-  // SURVEY 8f-1 image textures (one allocation each)
-  uint32_t* d_texRgba = nullptr;
-  int32_t* d_texDesc = nullptr;
-  uint32_t* d_matTex = nullptr;
-  float* d_triUv = nullptr;
+  // SURVEY 8f-1 image textures
+  DevBuf<uint32_t> d_texRgba;
+  DevBuf<int32_t> d_texDesc;  // 3 words per texture
+  DevBuf<uint32_t> d_matTex;  // 4 words per BSDF
+  DevBuf<float> d_triUv;      // 6 floats per triangle
   uint32_t texCount = 0, matTexCount = 0;
   bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_blend kernels carry that code
   size_t triUvCount = 0;
   // wavefront form of the BVH path (wavefront.hpp)
   int bvhStrategy = 0;             // 0 = automatic (by launch size), 1 = megakernel, 2 = wavefront
   size_t wfTargetPaths = size_t(1) << 22;  // path slots per pass
-  float* d_wfState = nullptr;
-  uint32_t* d_wfQueue = nullptr;   // two queues
-  uint32_t* d_wfCounts = nullptr;  // counts + cursors
-  size_t wfSlotsCap = 0, wfCountsCap = 0;
+  DevBuf<float> d_wfState;
+  DevBuf<uint32_t> d_wfQueue;   // two queues
+  DevBuf<uint32_t> d_wfCounts;  // counts + cursors
   int wfBlocksTrace = 0, wfBlocksShade = 0;
-  float* d_env = nullptr;  // A18: one allocation holding the five tables and the image
+  DevBuf<float> d_env;     // A18: one allocation holding the five tables and the image
   EnvView env{};           // env.w == 0: no env map
-  uint32_t* d_areaOf = nullptr;   // per-triangle area-light index
-  uint32_t* d_areaTri = nullptr;
-  float* d_areaLe = nullptr;
+  DevBuf<uint32_t> d_areaOf;  // per-triangle area-light index
+  DevBuf<uint32_t> d_areaTri;
+  DevBuf<float> d_areaLe;
   uint32_t areaCount = 0;
   std::vector<uint32_t> h_areaTri;  // kept to rebuild areaOf when triangles are re-uploaded
   std::vector<float> h_areaLe;
@@ -1729,18 +1768,17 @@ struct dmt_ctx {
   dmt_camera cam{};
   CameraXf xf{};
   SamplerParams sp{};
-  // film
+  // film: the context's own, or the caller's after dmt_film_bind (which frees the own one)
+  DevBuf<float4> ownMean, ownM2;
   float4* d_mean = nullptr;
   float4* d_m2 = nullptr;
-  bool ownFilm = false;
   int filmW = 0, filmH = 0;
-  uint32_t* d_counter = nullptr;   // work counter
-  uint32_t* d_sched = nullptr;     // [waves * kSlabsPerWave] slab-busy marks, then [numChunks][numItems] hand-over words; zeroed per launch
-  unsigned long long* d_schedDiag = nullptr;  // kSchedDiagWords counters over all launches (dmt_sched_diag)
-  unsigned long long expectedFolds = 0;       // work items launched so far: what d_schedDiag[0] must read once the stream has drained
-  float* d_stage = nullptr;        // staging slabs of finished samples, [wave][kSlabsPerWave][chunkSpp][64] float3
-  size_t stageFloats = 0;
-  size_t schedCap = 0;
+  DevBuf<uint32_t> d_counter;   // work counter
+  DevBuf<uint32_t> d_sched;     // [waves * kSlabsPerWave] slab-busy marks, then [numChunks][numItems] hand-over words; zeroed per launch
+  DevBuf<unsigned long long> d_schedDiag;  // kSchedDiagWords counters over all launches (dmt_sched_diag)
+  unsigned long long expectedFolds = 0;    // work items launched so far: what d_schedDiag[0] must read once the stream has drained
+  DevBuf<unsigned long long> d_stats;      // 16 device counters of dmt_render_stats / dmt_render_profile
+  DevBuf<float> d_stage;        // staging slabs of finished samples, [wave][kSlabsPerWave][chunkSpp][64] float3
   uint32_t chunkSpp = 0;           // samples per work item, 0 = automatic
   int subShift = -1;               // row bands per tile (log2); -1 = choose per launch
   int maxDepth = 32;
@@ -1892,8 +1930,8 @@ int checkFeatures(dmt_ctx* ctx, uint32_t F) {
 
 SceneView sceneView(dmt_ctx const* c) {
   SceneView s;
-  s.tris = c->d_tris, s.post = c->d_post, s.bsdfs = c->d_bsdfs, s.lights = c->d_lights;
-  s.infLights = c->d_inf;
+  s.tris = c->d_tris.get(), s.post = c->d_post.get(), s.bsdfs = c->d_bsdfs.get(), s.lights = c->d_lights.get();
+  s.infLights = c->d_inf.get();
   s.triCount = c->triCount, s.bsdfCount = c->bsdfCount, s.lightCount = c->lightCount;
   s.infLightCount = c->infCount;
   return s;
@@ -1901,7 +1939,7 @@ SceneView sceneView(dmt_ctx const* c) {
 
 BvhView bvhView(dmt_ctx const* c, size_t threads) {
   BvhView b;
-  b.nodes = c->d_bvhNodes, b.pairs = c->d_trisBvh, b.overflow = c->d_overflow;
+  b.nodes = c->d_bvhNodes.get(), b.pairs = c->d_trisBvh.get(), b.overflow = c->d_overflow.get();
   b.overflowStride = uint32_t(threads);
   return b;
 }
@@ -1932,11 +1970,12 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = bvhShadeThreshold(c);
   P.env = c->env;
-  P.areaOf = c->d_areaOf, P.areaTri = c->d_areaTri, P.areaLe = c->d_areaLe, P.areaCount = c->areaCount;
-  if (c->texCount > 0) P.texRgba = c->d_texRgba, P.texDesc = c->d_texDesc, P.matTex = c->d_matTex, P.triUv = c->d_triUv;
+  P.areaOf = c->d_areaOf.get(), P.areaTri = c->d_areaTri.get(), P.areaLe = c->d_areaLe.get(), P.areaCount = c->areaCount;
+  if (c->texCount > 0)
+    P.texRgba = c->d_texRgba.get(), P.texDesc = c->d_texDesc.get(), P.matTex = c->d_matTex.get(), P.triUv = c->d_triUv.get();
   uint32_t const F = featuresOf(c);
-  if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree;
-  if ((F & kFeatLightTreeRef) && c->lightTreeValid) P.lightTreeRef = c->d_lightTreeRef;
+  if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree.get();
+  if ((F & kFeatLightTreeRef) && c->lightTreeValid) P.lightTreeRef = c->d_lightTreeRef.get();
   return P;
 }
 
@@ -1974,25 +2013,8 @@ int blocksPerCuOf(dmt_ctx* c, MegakernelFn kernel) {
   return n;
 }
 
-template <class T>
-int devAlloc(dmt_ctx* ctx, T** p, size_t n) {
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (n == 0) n = 1;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  return DMT_OK;
-}
-
-int ensureOverflow(dmt_ctx* ctx, size_t threads) {
-  if (threads <= ctx->overflowThreads && ctx->d_overflow) return DMT_OK;
-  if (ctx->d_overflow) (void)hipFree(ctx->d_overflow);
-  ctx->d_overflow = nullptr, ctx->overflowThreads = 0;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_overflow), threads * size_t(kBvhOverflowStack) * sizeof(uint32_t)));
-  ctx->overflowThreads = threads;
-  return DMT_OK;
-}
+// BVH traversal-stack overflow area for `threads` threads
+hipError_t reserveOverflow(dmt_ctx* ctx, size_t threads) { return ctx->d_overflow.reserve(threads * size_t(kBvhOverflowStack)); }
 
 // (re)build the 4-wide BVH of the uploaded soup and upload nodes + triangle pairs
 int buildBvh(dmt_ctx* ctx) {
@@ -2022,13 +2044,11 @@ int buildBvh(dmt_ctx* ctx) {
       P.orig[half] = i;
     }
   for (size_t p = npairs; p < pairs.size(); ++p) pairs[p] = pairs[npairs - 1];
-  int rc = devAlloc(ctx, &ctx->d_bvhNodes, r.nodes.size());
-  if (rc) return rc;
-  rc = devAlloc(ctx, &ctx->d_trisBvh, pairs.size());
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(ctx->d_bvhNodes, r.nodes.data(), r.nodes.size() * sizeof(Bvh4Node), hipMemcpyHostToDevice));
-  if (!pairs.empty())
-    HIP_TRY(ctx, hipMemcpy(ctx->d_trisBvh, pairs.data(), pairs.size() * sizeof(TriPair), hipMemcpyHostToDevice));
+  DevBuf<Bvh4Node> nodes;
+  DevBuf<TriPair> leaves;
+  HIP_TRY(ctx, nodes.assign(r.nodes.data(), r.nodes.size()));
+  HIP_TRY(ctx, leaves.assign(pairs.data(), pairs.size()));
+  ctx->d_bvhNodes = std::move(nodes), ctx->d_trisBvh = std::move(leaves);
   ctx->bvhDepth = r.depth;
   ctx->bvhNodeCount = uint32_t(r.nodes.size());
   ctx->bvhPairCount = uint32_t(npairs);
@@ -2072,9 +2092,7 @@ int ensureLightTree(dmt_ctx* ctx) {
       ctx->lightTreeTooDeep = true;
       return DMT_OK;
     }
-    int const rcR = devAlloc(ctx, &ctx->d_lightTreeRef, nodes.size());
-    if (rcR) return rcR;
-    if (!nodes.empty()) HIP_TRY(ctx, hipMemcpy(ctx->d_lightTreeRef, nodes.data(), nodes.size() * sizeof(LightTreeRefNode), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, ctx->d_lightTreeRef.assign(nodes.data(), nodes.size()));
     ctx->lightTreeNodes = uint32_t(nodes.size());
     ctx->lightTreeValid = true;
     return DMT_OK;
@@ -2091,40 +2109,18 @@ int ensureLightTree(dmt_ctx* ctx) {
     ctx->lightTreeTooDeep = true;
     return DMT_OK;
   }
-  int const rc = devAlloc(ctx, &ctx->d_lightTree, nodes.size());
-  if (rc) return rc;
-  if (!nodes.empty()) HIP_TRY(ctx, hipMemcpy(ctx->d_lightTree, nodes.data(), nodes.size() * sizeof(LightTreeNode), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, ctx->d_lightTree.assign(nodes.data(), nodes.size()));
   ctx->lightTreeNodes = uint32_t(nodes.size());
   ctx->lightTreeValid = true;
   return DMT_OK;
 }
-
-// scratch buffers for the test entry points
-struct Scratch {
-  dmt_ctx* ctx;
-  std::vector<void*> ptrs;
-  explicit Scratch(dmt_ctx* c) : ctx(c) {}
-  ~Scratch() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  T* up(T const* host, size_t n) {  // upload (or allocate when host == nullptr)
-    void* d = nullptr;
-    if (hipMalloc(&d, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-    ptrs.push_back(d);
-    if (host && n && hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return static_cast<T*>(d);
-  }
-};
-#define SCRATCH_CHECK(ctx, p) \
-  if (!(p)) return fail(ctx, DMT_ERR_HIP, "scratch allocation / upload failed")
 
 // After the stream has drained: every work item of every past launch must have been folded into the film exactly once
 // (item_complete / fold_chain count their folds).  Anything else means the hand-over protocol lost or duplicated a sample
 // chunk and the film is not the ordered fold the contract promises.
 int checkErrorFlag(dmt_ctx* ctx) {
   unsigned long long folds = 0;
-  HIP_TRY(ctx, hipMemcpy(&folds, ctx->d_schedDiag, sizeof(folds), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(&folds, ctx->d_schedDiag.get(), sizeof(folds), hipMemcpyDeviceToHost));
   if (folds != ctx->expectedFolds) {
     char msg[200];
     snprintf(msg, sizeof(msg), "in-launch ordering: %llu sample chunks were folded into the film, %llu were launched: the film is invalid",
@@ -2159,17 +2155,17 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
     g_createError = "device ordinal out of range";
     return DMT_ERR_INVALID;
   }
-  dmt_ctx* ctx = new (std::nothrow) dmt_ctx();
+  std::unique_ptr<dmt_ctx> ctx(new (std::nothrow) dmt_ctx());
   if (!ctx) return DMT_ERR_INVALID;
   ctx->device = device_ordinal;
   hipError_t e = hipSetDevice(device_ordinal);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->ownStream, hipStreamNonBlocking);
   hipDeviceProp_t prop{};
   if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device_ordinal);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_counter), 2 * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemset(ctx->d_counter, 0, 2 * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_schedDiag), kSchedDiagWords * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(ctx->d_schedDiag, 0, kSchedDiagWords * sizeof(unsigned long long));
+  if (e == hipSuccess) e = ctx->d_counter.reserve(2);
+  if (e == hipSuccess) e = hipMemset(ctx->d_counter.get(), 0, 2 * sizeof(uint32_t));
+  if (e == hipSuccess) e = ctx->d_schedDiag.reserve(kSchedDiagWords);
+  if (e == hipSuccess) e = hipMemset(ctx->d_schedDiag.get(), 0, kSchedDiagWords * sizeof(unsigned long long));
   int bpc = 0;
   if (e == hipSuccess)
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, reinterpret_cast<void const*>(k_megakernel), 256, 0);
@@ -2179,7 +2175,6 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
   if (e != hipSuccess) {
     g_createError = std::string("dmt_ctx_create: ") + hipGetErrorString(e);
     if (ctx->ownStream) (void)hipStreamDestroy(ctx->ownStream);
-    delete ctx;
     return DMT_ERR_HIP;
   }
   ctx->stream = ctx->ownStream;
@@ -2202,7 +2197,7 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
     int const v = std::atoi(e2);
     ctx->subShift = v < 0 ? -1 : (v > 2 ? 2 : v);
   }
-  *out = ctx;
+  *out = ctx.release();
   return DMT_OK;
 }
 
@@ -2214,37 +2209,8 @@ int dmt_ctx_destroy(dmt_ctx* ctx) {
     (void)hipEventDestroy(ev.first);
     (void)hipEventDestroy(ev.second);
   }
-  (void)hipFree(ctx->d_tris);
-  (void)hipFree(ctx->d_post);
-  (void)hipFree(ctx->d_bsdfs);
-  (void)hipFree(ctx->d_lights);
-  (void)hipFree(ctx->d_inf);
-  (void)hipFree(ctx->d_counter);
-  (void)hipFree(ctx->d_sched);
-  (void)hipFree(ctx->d_schedDiag);
-  (void)hipFree(ctx->d_stage);
-  (void)hipFree(ctx->d_env);
-  (void)hipFree(ctx->d_areaOf);
-  (void)hipFree(ctx->d_areaTri);
-  (void)hipFree(ctx->d_areaLe);
-  (void)hipFree(ctx->d_bvhNodes);
-  (void)hipFree(ctx->d_trisBvh);
-  (void)hipFree(ctx->d_overflow);
-  (void)hipFree(ctx->d_lightTree);
-  (void)hipFree(ctx->d_lightTreeRef);
-  (void)hipFree(ctx->d_texRgba);
-  (void)hipFree(ctx->d_texDesc);
-  (void)hipFree(ctx->d_matTex);
-  (void)hipFree(ctx->d_triUv);
-  (void)hipFree(ctx->d_wfState);
-  (void)hipFree(ctx->d_wfQueue);
-  (void)hipFree(ctx->d_wfCounts);
-  if (ctx->ownFilm) {
-    (void)hipFree(ctx->d_mean);
-    (void)hipFree(ctx->d_m2);
-  }
   if (ctx->ownStream) (void)hipStreamDestroy(ctx->ownStream);
-  delete ctx;
+  delete ctx;  // the device buffers free themselves
   return DMT_OK;
 }
 
@@ -2279,14 +2245,11 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
     q.nx = n.x, q.ny = n.y, q.nz = n.z;
     q.matId = mat_id[i], q.pad0 = q.pad1 = q.pad2 = 0;
   }
-  int rc = devAlloc(ctx, &ctx->d_tris, count);
-  if (rc) return rc;
-  rc = devAlloc(ctx, &ctx->d_post, count);
-  if (rc) return rc;
-  if (count) {
-    HIP_TRY(ctx, hipMemcpy(ctx->d_tris, a.data(), count * sizeof(TriIsect), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_post, b.data(), count * sizeof(TriPost), hipMemcpyHostToDevice));
-  }
+  DevBuf<TriIsect> tris;
+  DevBuf<TriPost> post;
+  HIP_TRY(ctx, tris.assign(a.data(), count));
+  HIP_TRY(ctx, post.assign(b.data(), count));
+  ctx->d_tris = std::move(tris), ctx->d_post = std::move(post);
   ctx->triCount = uint32_t(count);
   ctx->maxMatId = maxMat;
   ctx->haveTris = true;
@@ -2303,11 +2266,10 @@ int dmt_upload_bsdfs(dmt_ctx* ctx, const void* bsdf32, uint32_t count) {
   if (!ctx) return DMT_ERR_INVALID;
   if (count && !bsdf32) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_bsdfs: null array");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = devAlloc(ctx, &ctx->d_bsdfs, count);
-  if (rc) return rc;
-  if (count) HIP_TRY(ctx, hipMemcpy(ctx->d_bsdfs, bsdf32, size_t(count) * 32, hipMemcpyHostToDevice));
+  DevBuf<Rec32> bsdfs;
+  HIP_TRY(ctx, bsdfs.assign(bsdf32, count));
   // fractional-metallic materials (BS_GGX_BLEND: this record + the conductor record after it) run on the *_tex kernels
-  ctx->hasBlend = false;
+  bool blend = false;
   for (uint32_t i = 0; i < count; ++i) {
     uint32_t w1;
     memcpy(&w1, static_cast<unsigned char const*>(bsdf32) + 32 * size_t(i) + 4, 4);
@@ -2316,9 +2278,11 @@ int dmt_upload_bsdfs(dmt_ctx* ctx, const void* bsdf32, uint32_t count) {
       if (i + 1 < count) memcpy(&w1next, static_cast<unsigned char const*>(bsdf32) + 32 * size_t(i + 1) + 4, 4);
       if (i + 1 >= count || (w1next >> 16) != BS_GGX_COND)
         return fail(ctx, DMT_ERR_INVALID, "dmt_upload_bsdfs: a blend record (type 4) must be followed by its GGX conductor record");
-      ctx->hasBlend = true;
+      blend = true;
     }
   }
+  ctx->d_bsdfs = std::move(bsdfs);
+  ctx->hasBlend = blend;
   ctx->bsdfCount = count;
   ctx->haveBsdfs = true;
   return DMT_OK;
@@ -2330,13 +2294,10 @@ int dmt_upload_lights(dmt_ctx* ctx, const void* lights32, uint32_t count, const 
   if ((count && !lights32) || (infinite_count && !infinite32))
     return fail(ctx, DMT_ERR_INVALID, "dmt_upload_lights: null array");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = devAlloc(ctx, &ctx->d_lights, count);
-  if (rc) return rc;
-  rc = devAlloc(ctx, &ctx->d_inf, infinite_count);
-  if (rc) return rc;
-  if (count) HIP_TRY(ctx, hipMemcpy(ctx->d_lights, lights32, size_t(count) * 32, hipMemcpyHostToDevice));
-  if (infinite_count)
-    HIP_TRY(ctx, hipMemcpy(ctx->d_inf, infinite32, size_t(infinite_count) * 32, hipMemcpyHostToDevice));
+  DevBuf<Rec32> lights, inf;
+  HIP_TRY(ctx, lights.assign(lights32, count));
+  HIP_TRY(ctx, inf.assign(infinite32, infinite_count));
+  ctx->d_lights = std::move(lights), ctx->d_inf = std::move(inf);
   ctx->lightCount = count;
   ctx->infCount = infinite_count;
   ctx->haveLights = true;
@@ -2357,6 +2318,17 @@ int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam) {
   if (!cam || cam->width <= 0 || cam->height <= 0 || cam->width > 65536 || cam->height > 65536)
     return fail(ctx, DMT_ERR_INVALID, "dmt_set_camera: bad camera / resolution");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (cam->width != ctx->filmW || cam->height != ctx->filmH) {  // a new film, zeroed
+    size_t const pixels = size_t(cam->width) * size_t(cam->height);
+    DevBuf<float4> mean, m2;
+    HIP_TRY(ctx, mean.reserve(pixels));
+    HIP_TRY(ctx, m2.reserve(pixels));
+    HIP_TRY(ctx, hipMemsetAsync(mean.get(), 0, pixels * sizeof(float4), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(m2.get(), 0, pixels * sizeof(float4), ctx->stream));
+    ctx->ownMean = std::move(mean), ctx->ownM2 = std::move(m2);
+    ctx->d_mean = ctx->ownMean.get(), ctx->d_m2 = ctx->ownM2.get();
+    ctx->filmW = cam->width, ctx->filmH = cam->height;
+  }
   ctx->cam = *cam;
   float m[16];
   cameraFromRaster(cam->focal_length, cam->sensor_size, uint32_t(cam->width), uint32_t(cam->height), m);
@@ -2364,21 +2336,6 @@ int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam) {
   worldFromCamera(cam->dir, cam->pos, m);
   memcpy(ctx->xf.rfc, m, sizeof(m));
   ctx->sp = computeSamplerParams(cam->width, cam->height);
-  if (cam->width != ctx->filmW || cam->height != ctx->filmH) {
-    if (ctx->ownFilm) {
-      (void)hipFree(ctx->d_mean);
-      (void)hipFree(ctx->d_m2);
-    }
-    ctx->d_mean = ctx->d_m2 = nullptr;
-    ctx->ownFilm = false;
-    size_t const bytes = size_t(cam->width) * size_t(cam->height) * sizeof(float4);
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_mean), bytes));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_m2), bytes));
-    ctx->ownFilm = true;
-    ctx->filmW = cam->width, ctx->filmH = cam->height;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_mean, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_m2, 0, bytes, ctx->stream));
-  }
   ctx->haveCamera = true;
   return DMT_OK;
 }
@@ -2485,11 +2442,7 @@ int dmt_film_bind(dmt_ctx* ctx, void* d_mean, void* d_m2) {
   if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_film_bind: call dmt_set_camera first");
   if (!d_mean || !d_m2) return fail(ctx, DMT_ERR_INVALID, "dmt_film_bind: null buffer");
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->ownFilm) {
-    (void)hipFree(ctx->d_mean);
-    (void)hipFree(ctx->d_m2);
-    ctx->ownFilm = false;
-  }
+  ctx->ownMean.reset(), ctx->ownM2.reset();
   ctx->d_mean = static_cast<float4*>(d_mean);
   ctx->d_m2 = static_cast<float4*>(d_m2);
   return DMT_OK;
@@ -2524,20 +2477,10 @@ static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, ui
   uint32_t n = uint32_t(std::max<size_t>(1, target / (size_t(tilesPerPass) * 64)));
   if (n > spp) n = spp;
   size_t const slotsMax = size_t(tilesPerPass) * 64 * n;
-  if (slotsMax > ctx->wfSlotsCap) {
-    (void)hipFree(ctx->d_wfState), (void)hipFree(ctx->d_wfQueue);
-    ctx->d_wfState = nullptr, ctx->d_wfQueue = nullptr, ctx->wfSlotsCap = 0;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_wfState), size_t(WF_PLANES) * slotsMax * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_wfQueue), 2 * slotsMax * sizeof(uint32_t)));
-    ctx->wfSlotsCap = slotsMax;
-  }
+  HIP_TRY(ctx, ctx->d_wfState.reserve(size_t(WF_PLANES) * slotsMax));
+  HIP_TRY(ctx, ctx->d_wfQueue.reserve(2 * slotsMax));
   size_t const nCounts = 2 * (size_t(iters) + 2);
-  if (nCounts > ctx->wfCountsCap) {
-    (void)hipFree(ctx->d_wfCounts);
-    ctx->d_wfCounts = nullptr, ctx->wfCountsCap = 0;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_wfCounts), nCounts * sizeof(uint32_t)));
-    ctx->wfCountsCap = nCounts;
-  }
+  HIP_TRY(ctx, ctx->d_wfCounts.reserve(nCounts));
   if (ctx->wfBlocksTrace == 0) {
     int a = 0, b = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, reinterpret_cast<void const*>(k_wf_trace), 256, 0);
@@ -2547,26 +2490,24 @@ static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, ui
   }
   uint32_t const traceBlocks = uint32_t(ctx->cuCount) * uint32_t(stats ? 4 : ctx->wfBlocksTrace);
   uint32_t const shadeBlocks = uint32_t(ctx->cuCount) * uint32_t(stats ? 2 : ctx->wfBlocksShade);
-  int const rcO = ensureOverflow(ctx, size_t(traceBlocks) * 256);
-  if (rcO) return rcO;
+  HIP_TRY(ctx, reserveOverflow(ctx, size_t(traceBlocks) * 256));
   P.bvh = bvhView(ctx, size_t(traceBlocks) * 256);
-  unsigned long long* dstats = nullptr;
   if (stats) {
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dstats), 16 * sizeof(unsigned long long)));
-    HIP_TRY(ctx, hipMemsetAsync(dstats, 0, 16 * sizeof(unsigned long long), ctx->stream));
-    P.stats = dstats;
+    HIP_TRY(ctx, ctx->d_stats.reserve(16));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats.get(), 0, 16 * sizeof(unsigned long long), ctx->stream));
+    P.stats = ctx->d_stats.get();
   }
   WfKernelFn const trace = stats ? k_wf_trace_stats : k_wf_trace;
   WfParams W{};
-  W.state = ctx->d_wfState;
-  W.queue[0] = ctx->d_wfQueue, W.queue[1] = ctx->d_wfQueue + slotsMax;
-  W.counts = ctx->d_wfCounts, W.cursors = ctx->d_wfCounts + (iters + 2);
+  W.state = ctx->d_wfState.get();
+  W.queue[0] = ctx->d_wfQueue.get(), W.queue[1] = ctx->d_wfQueue.get() + slotsMax;
+  W.counts = ctx->d_wfCounts.get(), W.cursors = ctx->d_wfCounts.get() + (iters + 2);
   for (uint32_t tile0 = 0; tile0 < ownedTiles; tile0 += tilesPerPass) {
     uint32_t const tiles = std::min(tilesPerPass, ownedTiles - tile0);
     for (uint32_t s = 0; s < spp; s += n) {
       W.tile0 = tile0, W.pixelSlots = tiles * 64u, W.s0 = sample_offset + s, W.n = std::min(n, spp - s);
       W.slots = W.pixelSlots * W.n;
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_wfCounts, 0, nCounts * sizeof(uint32_t), ctx->stream));
+      HIP_TRY(ctx, hipMemsetAsync(ctx->d_wfCounts.get(), 0, nCounts * sizeof(uint32_t), ctx->stream));
       uint32_t const genBlocks = std::min<uint32_t>((W.slots + 255u) / 256u, uint32_t(ctx->cuCount) * 8u);
       W.it = 0;
       hipLaunchKernelGGL(k_wf_generate, dim3(genBlocks), dim3(256), 0, ctx->stream, P, W);
@@ -2583,11 +2524,9 @@ static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, ui
     }
   }
   if (stats) {
-    hipError_t e = hipStreamSynchronize(ctx->stream);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<unsigned long long> h(16, 0);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), dstats, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(dstats);
-    HIP_TRY(ctx, e);
+    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->d_stats.get(), 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     {  // samples = pixels of the owned tiles inside the region x spp (the kernels count rays, visits and bounces)
       uint64_t pixels = 0;
       for (uint32_t item = 0; item < ownedTiles; ++item) {
@@ -2628,7 +2567,7 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   if (!kernel) return noKernel(ctx, "dmt_render", F);
 
   RenderParams P = baseParams(ctx, 0);
-  P.mean = ctx->d_mean, P.m2 = ctx->d_m2, P.counter = ctx->d_counter;
+  P.mean = ctx->d_mean, P.m2 = ctx->d_m2, P.counter = ctx->d_counter.get();
   P.width = ctx->filmW, P.height = ctx->filmH;
   P.x0 = x0, P.y0 = y0, P.x1 = x1, P.y1 = y1;
   P.tx0 = x0 / 8, P.ty0 = y0 / 8;
@@ -2661,7 +2600,7 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   P.numChunks = (spp + P.chunkSpp - 1) / P.chunkSpp;
   if (uint64_t(P.numItems) * P.numChunks > 0x7FFFFFFFull)
     return fail(ctx, DMT_ERR_INVALID, "dmt_render: too many work items (tiles x sample chunks); raise dmt_set_chunk or split the pass");
-  P.schedDiag = ctx->d_schedDiag;
+  P.schedDiag = ctx->d_schedDiag.get();
 
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   uint32_t const wavesWanted = P.numItems * P.numChunks < P.numItems ? P.numItems : P.numItems * P.numChunks;
@@ -2679,27 +2618,17 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   auto& ev = ctx->events[ctx->eventsUsed];
   {  // staging slabs of finished samples, kSlabsPerWave per wave of the launch
     size_t const floats = size_t(blocks) * 4u * size_t(kSlabsPerWave) * size_t(P.chunkSpp) * 192u;
-    if (floats > ctx->stageFloats) {
-      if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-      ctx->d_stage = nullptr, ctx->stageFloats = 0;
-      HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_stage), floats * sizeof(float)));
-      ctx->stageFloats = floats;
-    }
-    P.stage = ctx->d_stage;
+    HIP_TRY(ctx, ctx->d_stage.reserve(floats));
+    P.stage = ctx->d_stage.get();
   }
   {  // slab-busy marks + one hand-over word per (chunk, tile item), all zero at launch
     size_t const busyWords = size_t(blocks) * 4u * size_t(kSlabsPerWave);
     size_t const linkWords = P.numChunks > 1 ? size_t(P.numItems) * size_t(P.numChunks) : 0;
-    if (busyWords + linkWords > ctx->schedCap) {
-      if (ctx->d_sched) (void)hipFree(ctx->d_sched);
-      ctx->d_sched = nullptr, ctx->schedCap = 0;
-      HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_sched), (busyWords + linkWords) * sizeof(uint32_t)));
-      ctx->schedCap = busyWords + linkWords;
-    }
-    P.slabBusy = ctx->d_sched, P.link = ctx->d_sched + busyWords;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_sched, 0, (busyWords + linkWords) * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, ctx->d_sched.reserve(busyWords + linkWords));
+    P.slabBusy = ctx->d_sched.get(), P.link = ctx->d_sched.get() + busyWords;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_sched.get(), 0, (busyWords + linkWords) * sizeof(uint32_t), ctx->stream));
   }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_counter, 0, sizeof(uint32_t), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_counter.get(), 0, sizeof(uint32_t), ctx->stream));
   HIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream));
   uint64_t const launchFolds = uint64_t(P.numItems) * P.numChunks;  // every item is folded exactly once (checkErrorFlag)
   if (wavefront) {
@@ -2709,21 +2638,17 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
     if (stats6) return DMT_OK;
   } else if (useBvh) {
     if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render: BVH not built");
-    int const rcO = ensureOverflow(ctx, size_t(ctx->cuCount) * size_t(std::max(blocksPerCu, ctx->blocksPerCUBvh)) * 256);
-    if (rcO) return rcO;
+    HIP_TRY(ctx, reserveOverflow(ctx, size_t(ctx->cuCount) * size_t(std::max(blocksPerCu, ctx->blocksPerCUBvh)) * 256));
     P.bvh = bvhView(ctx, size_t(blocks) * 256);
     if (stats6) {
-      unsigned long long* dstats = nullptr;
-      HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dstats), 16 * sizeof(unsigned long long)));
-      HIP_TRY(ctx, hipMemsetAsync(dstats, 0, 16 * sizeof(unsigned long long), ctx->stream));
-      P.stats = dstats;
+      HIP_TRY(ctx, ctx->d_stats.reserve(16));
+      HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats.get(), 0, 16 * sizeof(unsigned long long), ctx->stream));
+      P.stats = ctx->d_stats.get();
       hipLaunchKernelGGL(megakernelOf(F | kFeatStats), dim3(blocks), dim3(256), 0, ctx->stream, P);
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess) ctx->expectedFolds += launchFolds;
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e == hipSuccess) e = hipMemcpy(stats6, dstats, size_t(nstats) * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-      (void)hipFree(dstats);
-      HIP_TRY(ctx, e);
+      HIP_TRY(ctx, hipGetLastError());
+      ctx->expectedFolds += launchFolds;
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      HIP_TRY(ctx, hipMemcpy(stats6, ctx->d_stats.get(), size_t(nstats) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
       return DMT_OK;
     }
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, ctx->stream, P);
@@ -2841,12 +2766,12 @@ int dmt_sched_diag(dmt_ctx* ctx, uint64_t* out8, int reset) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   unsigned long long d[kSchedDiagWords] = {};
-  HIP_TRY(ctx, hipMemcpy(d, ctx->d_schedDiag, sizeof(d), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(d, ctx->d_schedDiag.get(), sizeof(d), hipMemcpyDeviceToHost));
   for (int i = 0; i < 8; ++i) out8[i] = i < kSchedDiagWords ? d[i] : 0;
   out8[6] = ctx->expectedFolds;
   out8[7] = uint64_t(kSlabsPerWave);
   if (reset) {
-    HIP_TRY(ctx, hipMemset(ctx->d_schedDiag, 0, sizeof(d)));
+    HIP_TRY(ctx, hipMemset(ctx->d_schedDiag.get(), 0, sizeof(d)));
     ctx->expectedFolds = 0;
   }
   return DMT_OK;
@@ -2854,8 +2779,7 @@ int dmt_sched_diag(dmt_ctx* ctx, uint64_t* out8, int reset) {
 
 // (re)builds the per-triangle lookup from the host copy of the area-light list
 static int rebuildAreaLights(dmt_ctx* ctx) {
-  (void)hipFree(ctx->d_areaOf), (void)hipFree(ctx->d_areaTri), (void)hipFree(ctx->d_areaLe);
-  ctx->d_areaOf = nullptr, ctx->d_areaTri = nullptr, ctx->d_areaLe = nullptr, ctx->areaCount = 0;
+  ctx->d_areaOf.reset(), ctx->d_areaTri.reset(), ctx->d_areaLe.reset(), ctx->areaCount = 0;
   uint32_t const n = uint32_t(ctx->h_areaTri.size());
   if (n == 0 || !ctx->haveTris) return DMT_OK;
   std::vector<uint32_t> of(ctx->triCount, 0xFFFFFFFFu);
@@ -2863,12 +2787,12 @@ static int rebuildAreaLights(dmt_ctx* ctx) {
     if (ctx->h_areaTri[k] >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "area light refers to a triangle outside the uploaded soup");
     of[ctx->h_areaTri[k]] = k;
   }
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_areaOf), of.size() * 4));
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_areaTri), size_t(n) * 4));
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_areaLe), size_t(n) * 12));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_areaOf, of.data(), of.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_areaTri, ctx->h_areaTri.data(), size_t(n) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_areaLe, ctx->h_areaLe.data(), size_t(n) * 12, hipMemcpyHostToDevice));
+  DevBuf<uint32_t> areaOf, areaTri;
+  DevBuf<float> areaLe;
+  HIP_TRY(ctx, areaOf.assign(of.data(), of.size()));
+  HIP_TRY(ctx, areaTri.assign(ctx->h_areaTri.data(), n));
+  HIP_TRY(ctx, areaLe.assign(ctx->h_areaLe.data(), 3 * size_t(n)));
+  ctx->d_areaOf = std::move(areaOf), ctx->d_areaTri = std::move(areaTri), ctx->d_areaLe = std::move(areaLe);
   ctx->areaCount = n;
   return DMT_OK;
 }
@@ -2887,8 +2811,7 @@ int dmt_upload_textures(dmt_ctx* ctx, const uint8_t* rgba8, uint64_t texel_count
   if (!ctx) return DMT_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  (void)hipFree(ctx->d_texRgba), (void)hipFree(ctx->d_texDesc), (void)hipFree(ctx->d_matTex), (void)hipFree(ctx->d_triUv);
-  ctx->d_texRgba = nullptr, ctx->d_texDesc = nullptr, ctx->d_matTex = nullptr, ctx->d_triUv = nullptr;
+  ctx->d_texRgba.reset(), ctx->d_texDesc.reset(), ctx->d_matTex.reset(), ctx->d_triUv.reset();
   ctx->texCount = 0, ctx->matTexCount = 0, ctx->triUvCount = 0;
   if (texture_count == 0) return DMT_OK;  // cleared
   if (!rgba8 || !desc3 || !mat_tex4 || !tri_uv6 || texel_count == 0 || bsdf_count == 0 || triangle_count == 0)
@@ -2903,14 +2826,15 @@ int dmt_upload_textures(dmt_ctx* ctx, const uint8_t* rgba8, uint64_t texel_count
       uint32_t const t = mat_tex4[4 * size_t(b) + size_t(j)];
       if (t != 0xFFFFFFFFu && t >= texture_count) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_textures: material refers to a texture that does not exist");
     }
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_texRgba), size_t(texel_count) * 4));
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_texDesc), size_t(texture_count) * 12));
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_matTex), size_t(bsdf_count) * 16));
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_triUv), size_t(triangle_count) * 24));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_texRgba, rgba8, size_t(texel_count) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_texDesc, desc3, size_t(texture_count) * 12, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_matTex, mat_tex4, size_t(bsdf_count) * 16, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_triUv, tri_uv6, size_t(triangle_count) * 24, hipMemcpyHostToDevice));
+  DevBuf<uint32_t> texRgba, matTex;
+  DevBuf<int32_t> texDesc;
+  DevBuf<float> triUv;
+  HIP_TRY(ctx, texRgba.assign(rgba8, size_t(texel_count)));
+  HIP_TRY(ctx, texDesc.assign(desc3, 3 * size_t(texture_count)));
+  HIP_TRY(ctx, matTex.assign(mat_tex4, 4 * size_t(bsdf_count)));
+  HIP_TRY(ctx, triUv.assign(tri_uv6, 6 * size_t(triangle_count)));
+  ctx->d_texRgba = std::move(texRgba), ctx->d_texDesc = std::move(texDesc), ctx->d_matTex = std::move(matTex);
+  ctx->d_triUv = std::move(triUv);
   ctx->texCount = texture_count, ctx->matTexCount = bsdf_count, ctx->triUvCount = size_t(triangle_count);
   return DMT_OK;
 }
@@ -2932,8 +2856,7 @@ int dmt_clear_envmap(dmt_ctx* ctx) {
   if (!ctx) return DMT_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->d_env) (void)hipFree(ctx->d_env);
-  ctx->d_env = nullptr;
+  ctx->d_env.reset();
   ctx->env = EnvView{};
   return DMT_OK;
 }
@@ -2947,27 +2870,27 @@ int dmt_upload_envmap(dmt_ctx* ctx, const float* rgb, int width, int height, con
                               quat_xyzw[3] * quat_xyzw[3]);
   if (!(len > 0.f)) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_envmap: zero quaternion");
   (void)scale;  // stored by the reference and never applied (core-light.cpp:115, :444-452)
-  int rc = dmt_clear_envmap(ctx);
-  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   envmap::Tables const t = envmap::build(rgb, width, height);
   size_t const wh = size_t(width) * size_t(height), h = size_t(height);
-  size_t const total = 2 * wh + 3 * h + 3 * wh;
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_env), total * sizeof(float)));
-  float* p = ctx->d_env;
+  DevBuf<float> buf;
+  HIP_TRY(ctx, buf.reserve(2 * wh + 3 * h + 3 * wh));
+  float* p = buf.get();
   EnvView e{};
+  hipError_t err = hipSuccess;
   auto put = [&](float const* src, size_t n) -> float const* {
     float* dst = p;
     p += n;
-    return hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? dst : nullptr;
+    if (err == hipSuccess) err = hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice);
+    return dst;
   };
   e.func = put(t.func.data(), wh), e.cdf = put(t.cdf.data(), wh), e.rowInt = put(t.rowInt.data(), h);
   e.mFunc = put(t.mFunc.data(), h), e.mCdf = put(t.mCdf.data(), h), e.rgb = put(rgb, 3 * wh);
-  if (!e.func || !e.cdf || !e.rowInt || !e.mFunc || !e.mCdf || !e.rgb) {
-    (void)dmt_clear_envmap(ctx);
-    return fail(ctx, DMT_ERR_HIP, "dmt_upload_envmap: copy failed");
-  }
+  if (err != hipSuccess) return fail(ctx, DMT_ERR_HIP, "dmt_upload_envmap: copy failed");
   e.mInt = t.mInt, e.w = width, e.h = height;
   e.qx = quat_xyzw[0] / len, e.qy = quat_xyzw[1] / len, e.qz = quat_xyzw[2] / len, e.qw = quat_xyzw[3] / len;
+  ctx->d_env = std::move(buf);
   ctx->env = e;
   return DMT_OK;
 }
@@ -2978,28 +2901,27 @@ int dmt_test_envmap(dmt_ctx* ctx, int n, const float* u2, const float* wi_in3, f
   if (ctx->env.w <= 0) return fail(ctx, DMT_ERR_STATE, "dmt_test_envmap: no env map uploaded");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   size_t const N = size_t(n);
-  float* d = nullptr;  // u2(2) wiIn(3) wi(3) pdf(1) uv(2) Le(3) ok(1) LeDir(3) pdfDir(1) = 19 words per case
-  HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&d), N * 19 * sizeof(float)));
-  float *du = d, *dwin = d + 2 * N, *dwi = d + 5 * N, *dpdf = d + 8 * N, *duv = d + 9 * N, *dLe = d + 11 * N;
-  int32_t* dok = reinterpret_cast<int32_t*>(d + 14 * N);
-  float *dLd = d + 15 * N, *dpd = d + 18 * N;
-  hipError_t e = hipMemcpy(du, u2, N * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dwin, wi_in3, N * 12, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_test_envmap, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, ctx->env, n, du, dwin, dwi, dpdf, duv,
-                       dLe, dok, dLd, dpd);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(wi3, dwi, N * 12, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(pdf, dpdf, N * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(uv2, duv, N * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(Le3, dLe, N * 12, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(ok, dok, N * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(Le_dir3, dLd, N * 12, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(pdf_dir, dpd, N * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  HIP_TRY(ctx, e);
+  DevBuf<float> du, dwin, dwi, dpdf, duv, dLe, dLd, dpd;
+  DevBuf<int32_t> dok;
+  HIP_TRY(ctx, du.assign(u2, 2 * N));
+  HIP_TRY(ctx, dwin.assign(wi_in3, 3 * N));
+  HIP_TRY(ctx, dwi.reserve(3 * N));
+  HIP_TRY(ctx, dpdf.reserve(N));
+  HIP_TRY(ctx, duv.reserve(2 * N));
+  HIP_TRY(ctx, dLe.reserve(3 * N));
+  HIP_TRY(ctx, dok.reserve(N));
+  HIP_TRY(ctx, dLd.reserve(3 * N));
+  HIP_TRY(ctx, dpd.reserve(N));
+  hipLaunchKernelGGL(k_test_envmap, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, ctx->env, n, du.get(), dwin.get(), dwi.get(),
+                     dpdf.get(), duv.get(), dLe.get(), dok.get(), dLd.get(), dpd.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(wi3, dwi.get(), N * 12, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(pdf, dpdf.get(), N * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(uv2, duv.get(), N * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(Le3, dLe.get(), N * 12, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(ok, dok.get(), N * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(Le_dir3, dLd.get(), N * 12, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(pdf_dir, dpd.get(), N * 4, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3050,26 +2972,25 @@ int dmt_test_triangle_intersect(dmt_ctx* ctx, const float* xs, const float* ys, 
   if (!ctx || !xs || !ys || !zs || !o3 || !d3 || !hit) return DMT_ERR_INVALID;
   if (count == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  float* dx = S.up(xs, 4 * count);
-  float* dy = S.up(ys, 4 * count);
-  float* dz = S.up(zs, 4 * count);
-  int32_t* dh = S.up<int32_t>(nullptr, count);
-  float* dt = S.up<float>(nullptr, count);
-  float* dp = S.up<float>(nullptr, 3 * count);
-  float* dn = S.up<float>(nullptr, 3 * count);
-  float* de = S.up<float>(nullptr, 3 * count);
-  SCRATCH_CHECK(ctx, dx && dy && dz && dh && dt && dp && dn && de);
+  DevBuf<float> dx, dy, dz, dt, dp, dn, de;
+  DevBuf<int32_t> dh;
+  HIP_TRY(ctx, dx.assign(xs, 4 * count));
+  HIP_TRY(ctx, dy.assign(ys, 4 * count));
+  HIP_TRY(ctx, dz.assign(zs, 4 * count));
+  HIP_TRY(ctx, dh.reserve(count));
+  HIP_TRY(ctx, dt.reserve(count));
+  HIP_TRY(ctx, dp.reserve(3 * count));
+  HIP_TRY(ctx, dn.reserve(3 * count));
+  HIP_TRY(ctx, de.reserve(3 * count));
   uint32_t const n = uint32_t(count);
-  hipLaunchKernelGGL(k_test_tri, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dx, dy, dz, n,
-                     f3{o3[0], o3[1], o3[2]}, f3{d3[0], d3[1], d3[2]}, dh, dt, dp, dn, de);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(hit, dh, count * 4, hipMemcpyDeviceToHost));
-  if (t) HIP_TRY(ctx, hipMemcpy(t, dt, count * 4, hipMemcpyDeviceToHost));
-  if (pos3) HIP_TRY(ctx, hipMemcpy(pos3, dp, count * 12, hipMemcpyDeviceToHost));
-  if (nrm3) HIP_TRY(ctx, hipMemcpy(nrm3, dn, count * 12, hipMemcpyDeviceToHost));
-  if (err3) HIP_TRY(ctx, hipMemcpy(err3, de, count * 12, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(k_test_tri, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dx.get(), dy.get(), dz.get(), n,
+                     f3{o3[0], o3[1], o3[2]}, f3{d3[0], d3[1], d3[2]}, dh.get(), dt.get(), dp.get(), dn.get(), de.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(hit, dh.get(), count * 4, hipMemcpyDeviceToHost));
+  if (t) HIP_TRY(ctx, hipMemcpy(t, dt.get(), count * 4, hipMemcpyDeviceToHost));
+  if (pos3) HIP_TRY(ctx, hipMemcpy(pos3, dp.get(), count * 12, hipMemcpyDeviceToHost));
+  if (nrm3) HIP_TRY(ctx, hipMemcpy(nrm3, dn.get(), count * 12, hipMemcpyDeviceToHost));
+  if (err3) HIP_TRY(ctx, hipMemcpy(err3, de.get(), count * 12, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3079,21 +3000,20 @@ int dmt_test_sampler(dmt_ctx* ctx, int width, int height, int n, const int32_t* 
     return DMT_ERR_INVALID;
   if (n == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  int32_t* dpx = S.up(pxs, size_t(n));
-  int32_t* dpy = S.up(pys, size_t(n));
-  int32_t* dss = S.up(ss, size_t(n));
-  int32_t* dh = S.up<int32_t>(nullptr, size_t(n));
-  float* dp2 = S.up<float>(nullptr, 2 * size_t(n));
-  float* dd = S.up<float>(nullptr, size_t(n) * size_t(ndims));
-  SCRATCH_CHECK(ctx, dpx && dpy && dss && dh && dp2 && dd);
+  DevBuf<int32_t> dpx, dpy, dss, dh;
+  DevBuf<float> dp2, dd;
+  HIP_TRY(ctx, dpx.assign(pxs, size_t(n)));
+  HIP_TRY(ctx, dpy.assign(pys, size_t(n)));
+  HIP_TRY(ctx, dss.assign(ss, size_t(n)));
+  HIP_TRY(ctx, dh.reserve(size_t(n)));
+  HIP_TRY(ctx, dp2.reserve(2 * size_t(n)));
+  HIP_TRY(ctx, dd.reserve(size_t(n) * size_t(ndims)));
   hipLaunchKernelGGL(k_test_sampler, dim3((n + 63) / 64), dim3(64), 0, ctx->stream,
-                     computeSamplerParams(width, height), n, dpx, dpy, dss, ndims, dh, dp2, dd);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(halton_index, dh, size_t(n) * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(pixel2d_out, dp2, size_t(n) * 8, hipMemcpyDeviceToHost));
-  if (ndims) HIP_TRY(ctx, hipMemcpy(dims, dd, size_t(n) * size_t(ndims) * 4, hipMemcpyDeviceToHost));
+                     computeSamplerParams(width, height), n, dpx.get(), dpy.get(), dss.get(), ndims, dh.get(), dp2.get(), dd.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(halton_index, dh.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(pixel2d_out, dp2.get(), size_t(n) * 8, hipMemcpyDeviceToHost));
+  if (ndims) HIP_TRY(ctx, hipMemcpy(dims, dd.get(), size_t(n) * size_t(ndims) * 4, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3103,19 +3023,18 @@ int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t*
   if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_camera_rays: set the camera first");
   if (n == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  int32_t* dpx = S.up(pxs, size_t(n));
-  int32_t* dpy = S.up(pys, size_t(n));
-  int32_t* dss = S.up(ss, size_t(n));
-  float* dO = S.up<float>(nullptr, 3 * size_t(n));
-  float* dD = S.up<float>(nullptr, 3 * size_t(n));
-  SCRATCH_CHECK(ctx, dpx && dpy && dss && dO && dD);
-  hipLaunchKernelGGL(k_test_camera, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, n, dpx,
-                     dpy, dss, dO, dD);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(o3, dO, size_t(n) * 12, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(d3, dD, size_t(n) * 12, hipMemcpyDeviceToHost));
+  DevBuf<int32_t> dpx, dpy, dss;
+  DevBuf<float> dO, dD;
+  HIP_TRY(ctx, dpx.assign(pxs, size_t(n)));
+  HIP_TRY(ctx, dpy.assign(pys, size_t(n)));
+  HIP_TRY(ctx, dss.assign(ss, size_t(n)));
+  HIP_TRY(ctx, dO.reserve(3 * size_t(n)));
+  HIP_TRY(ctx, dD.reserve(3 * size_t(n)));
+  hipLaunchKernelGGL(k_test_camera, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, n, dpx.get(),
+                     dpy.get(), dss.get(), dO.get(), dD.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(o3, dO.get(), size_t(n) * 12, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(d3, dD.get(), size_t(n) * 12, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3126,25 +3045,23 @@ int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, con
     return DMT_ERR_INVALID;
   if (n == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  float* dns = S.up(ns3, 3 * size_t(n));
-  float* dwo = S.up(wo3, 3 * size_t(n));
-  float* du2 = S.up(u2, 2 * size_t(n));
-  float* duc = S.up(uc, size_t(n));
-  float* dwi = S.up(wi_eval3, 3 * size_t(n));
-  float* dp = S.up<float>(nullptr, 12 * size_t(n));
-  float* ds = S.up<float>(nullptr, 10 * size_t(n));
-  float* de = S.up<float>(nullptr, 4 * size_t(n));
-  SCRATCH_CHECK(ctx, dns && dwo && du2 && duc && dwi && dp && ds && de);
+  DevBuf<float> dns, dwo, du2, duc, dwi, dp, ds, de;
+  HIP_TRY(ctx, dns.assign(ns3, 3 * size_t(n)));
+  HIP_TRY(ctx, dwo.assign(wo3, 3 * size_t(n)));
+  HIP_TRY(ctx, du2.assign(u2, 2 * size_t(n)));
+  HIP_TRY(ctx, duc.assign(uc, size_t(n)));
+  HIP_TRY(ctx, dwi.assign(wi_eval3, 3 * size_t(n)));
+  HIP_TRY(ctx, dp.reserve(12 * size_t(n)));
+  HIP_TRY(ctx, ds.reserve(10 * size_t(n)));
+  HIP_TRY(ctx, de.reserve(4 * size_t(n)));
   Rec32 rec;
   memcpy(&rec, bsdf32, 32);
-  hipLaunchKernelGGL(k_test_bsdf, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, rec, n, dns, dwo, du2, duc,
-                     dwi, dp, ds, de);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(prepared12, dp, size_t(n) * 48, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(sample10, ds, size_t(n) * 40, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(eval4, de, size_t(n) * 16, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(k_test_bsdf, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, rec, n, dns.get(), dwo.get(), du2.get(), duc.get(),
+                     dwi.get(), dp.get(), ds.get(), de.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(prepared12, dp.get(), size_t(n) * 48, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(sample10, ds.get(), size_t(n) * 40, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(eval4, de.get(), size_t(n) * 16, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3153,19 +3070,19 @@ int dmt_test_light(dmt_ctx* ctx, const void* light32, int n, const float* pos3, 
   if (!ctx || n < 0 || !light32 || !pos3 || !nrm3 || !u2 || !had_transmission || !out14) return DMT_ERR_INVALID;
   if (n == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  float* dp = S.up(pos3, 3 * size_t(n));
-  float* dn = S.up(nrm3, 3 * size_t(n));
-  float* du = S.up(u2, 2 * size_t(n));
-  int32_t* dh = S.up(had_transmission, size_t(n));
-  float* dout = S.up<float>(nullptr, 14 * size_t(n));
-  SCRATCH_CHECK(ctx, dp && dn && du && dh && dout);
+  DevBuf<float> dp, dn, du, dout;
+  DevBuf<int32_t> dh;
+  HIP_TRY(ctx, dp.assign(pos3, 3 * size_t(n)));
+  HIP_TRY(ctx, dn.assign(nrm3, 3 * size_t(n)));
+  HIP_TRY(ctx, du.assign(u2, 2 * size_t(n)));
+  HIP_TRY(ctx, dh.assign(had_transmission, size_t(n)));
+  HIP_TRY(ctx, dout.reserve(14 * size_t(n)));
   Rec32 rec;
   memcpy(&rec, light32, 32);
-  hipLaunchKernelGGL(k_test_light, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, rec, n, dp, dn, du, dh, dout);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(out14, dout, size_t(n) * 56, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(k_test_light, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, rec, n, dp.get(), dn.get(), du.get(), dh.get(),
+                     dout.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(out14, dout.get(), size_t(n) * 56, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3173,18 +3090,16 @@ int dmt_test_half(dmt_ctx* ctx, int n, const float* f_in, uint16_t* h_out, const
   if (!ctx || n < 0) return DMT_ERR_INVALID;
   if (n == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  float* dfi = f_in ? S.up(f_in, size_t(n)) : nullptr;
-  uint16_t* dho = h_out ? S.up<uint16_t>(nullptr, size_t(n)) : nullptr;
-  uint16_t* dhi = h_in ? S.up(h_in, size_t(n)) : nullptr;
-  float* dfo = f_out ? S.up<float>(nullptr, size_t(n)) : nullptr;
-  if ((f_in && !dfi) || (h_out && !dho) || (h_in && !dhi) || (f_out && !dfo))
-    return fail(ctx, DMT_ERR_HIP, "scratch allocation / upload failed");
-  hipLaunchKernelGGL(k_test_half, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, dfi, dho, dhi, dfo);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  if (h_out && f_in) HIP_TRY(ctx, hipMemcpy(h_out, dho, size_t(n) * 2, hipMemcpyDeviceToHost));
-  if (f_out && h_in) HIP_TRY(ctx, hipMemcpy(f_out, dfo, size_t(n) * 4, hipMemcpyDeviceToHost));
+  DevBuf<float> dfi, dfo;  // the buffers of absent arrays stay empty (null)
+  DevBuf<uint16_t> dho, dhi;
+  if (f_in) HIP_TRY(ctx, dfi.assign(f_in, size_t(n)));
+  if (h_out) HIP_TRY(ctx, dho.reserve(size_t(n)));
+  if (h_in) HIP_TRY(ctx, dhi.assign(h_in, size_t(n)));
+  if (f_out) HIP_TRY(ctx, dfo.reserve(size_t(n)));
+  hipLaunchKernelGGL(k_test_half, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, dfi.get(), dho.get(), dhi.get(), dfo.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  if (h_out && f_in) HIP_TRY(ctx, hipMemcpy(h_out, dho.get(), size_t(n) * 2, hipMemcpyDeviceToHost));
+  if (f_out && h_in) HIP_TRY(ctx, hipMemcpy(f_out, dfo.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3197,12 +3112,12 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
     return fail(ctx, DMT_ERR_INVALID, "dmt_test_trace_samples: material index outside the BSDF array");
   if (n == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  int32_t* dpx = S.up(pxs, size_t(n));
-  int32_t* dpy = S.up(pys, size_t(n));
-  int32_t* dss = S.up(ss, size_t(n));
-  float* dL = S.up<float>(nullptr, 3 * size_t(n));
-  SCRATCH_CHECK(ctx, dpx && dpy && dss && dL);
+  DevBuf<int32_t> dpx, dpy, dss;
+  DevBuf<float> dL;
+  HIP_TRY(ctx, dpx.assign(pxs, size_t(n)));
+  HIP_TRY(ctx, dpy.assign(pys, size_t(n)));
+  HIP_TRY(ctx, dss.assign(ss, size_t(n)));
+  HIP_TRY(ctx, dL.reserve(3 * size_t(n)));
   uint32_t F = 0;  // the shading body dmt_render would run
   if (int const rc = resolveFeatures(ctx, &F)) return rc;
   TestTraceFn const kernel = kernelOf(kTestTraceKernels, F);
@@ -3210,13 +3125,12 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
   size_t const threads = size_t((n + 63) / 64) * 64;
   if (F & kFeatBvh) {
     if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_samples: BVH not built");
-    int const rcO = ensureOverflow(ctx, threads);
-    if (rcO) return rcO;
+    HIP_TRY(ctx, reserveOverflow(ctx, threads));
   }
-  hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, baseParams(ctx, threads), n, dpx, dpy, dss, dL);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(L3, dL, size_t(n) * 12, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, baseParams(ctx, threads), n, dpx.get(), dpy.get(),
+                     dss.get(), dL.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(L3, dL.get(), size_t(n) * 12, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3227,18 +3141,17 @@ int dmt_test_trace_log(dmt_ctx* ctx, int px, int py, int s, float* rec12, int ca
   if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
     return fail(ctx, DMT_ERR_INVALID, "dmt_test_trace_log: material index outside the BSDF array");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  float* dr = S.up<float>(nullptr, 12 * size_t(cap));
-  int* dn = S.up<int>(nullptr, 1);
-  float* dL = S.up<float>(nullptr, 3);
-  SCRATCH_CHECK(ctx, dr && dn && dL);
-  hipLaunchKernelGGL(k_test_trace_log, dim3(1), dim3(64), 0, ctx->stream, baseParams(ctx, 64), px, py, s, dr, cap, dn,
-                     dL);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(rec12, dr, size_t(cap) * 48, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(n_out, dn, 4, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(L3, dL, 12, hipMemcpyDeviceToHost));
+  DevBuf<float> dr, dL;
+  DevBuf<int> dn;
+  HIP_TRY(ctx, dr.reserve(12 * size_t(cap)));
+  HIP_TRY(ctx, dn.reserve(1));
+  HIP_TRY(ctx, dL.reserve(3));
+  hipLaunchKernelGGL(k_test_trace_log, dim3(1), dim3(64), 0, ctx->stream, baseParams(ctx, 64), px, py, s, dr.get(), cap, dn.get(),
+                     dL.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(rec12, dr.get(), size_t(cap) * 48, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(n_out, dn.get(), 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(L3, dL.get(), 12, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -3247,25 +3160,23 @@ int dmt_test_closest_hit(dmt_ctx* ctx, int nrays, const float* o3, const float* 
   if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit: upload triangles first");
   if (nrays == 0) return DMT_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Scratch S(ctx);
-  float* dO = S.up(o3, 3 * size_t(nrays));
-  float* dD = S.up(d3, 3 * size_t(nrays));
-  int32_t* di = S.up<int32_t>(nullptr, size_t(nrays));
-  float* dt = S.up<float>(nullptr, size_t(nrays));
-  SCRATCH_CHECK(ctx, dO && dD && di && dt);
+  DevBuf<float> dO, dD, dt;
+  DevBuf<int32_t> di;
+  HIP_TRY(ctx, dO.assign(o3, 3 * size_t(nrays)));
+  HIP_TRY(ctx, dD.assign(d3, 3 * size_t(nrays)));
+  HIP_TRY(ctx, di.reserve(size_t(nrays)));
+  HIP_TRY(ctx, dt.reserve(size_t(nrays)));
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   size_t const threads = size_t((nrays + 63) / 64) * 64;
   if (useBvh) {
     if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit: BVH not built");
-    int const rcO = ensureOverflow(ctx, threads);
-    if (rcO) return rcO;
+    HIP_TRY(ctx, reserveOverflow(ctx, threads));
   }
   hipLaunchKernelGGL(k_test_closest, dim3((nrays + 63) / 64), dim3(64), 0, ctx->stream, baseParams(ctx, threads),
-                     useBvh, nrays, dO, dD, di, dt);
-  int rc = finishTest(ctx);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(tri_index, di, size_t(nrays) * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(t, dt, size_t(nrays) * 4, hipMemcpyDeviceToHost));
+                     useBvh, nrays, dO.get(), dD.get(), di.get(), dt.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(tri_index, di.get(), size_t(nrays) * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(t, dt.get(), size_t(nrays) * 4, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
