@@ -18,6 +18,7 @@
 //     32-byte write per pixel per pass.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -38,8 +39,28 @@ using namespace dmt;
 
 namespace {
 
+// Culled clusters of the brute-force pass (planBruteCull on the host, brute_clusters on the device).  A cluster is a run of
+// consecutive triangles of one material -- one mesh of the scene front-ends -- that is small next to the scene; the pass tests
+// its triangles only for the rays that touch its bounding sphere, compacted over the wave's lanes.  Everything else stays in
+// the "always" list, which the packed SGPR loop tests for every ray as before.
+constexpr uint32_t kCullMaxClusters = 4;
+constexpr uint32_t kCullMaxTris = 32;   // LDS copy of the culled triangles, 36 B each (see the LDS budget in DESIGN.md 4.1)
+struct CullCluster {                    // 32 B
+  float cx, cy, cz, r2;                 // bounding sphere: centre and squared inflated radius
+  uint32_t first, count;                // original triangle indices [first, first + count)
+  uint32_t slot, magic;                 // first slot of its triangles in the LDS copy; ceil(2^32 / count)
+};
+struct CullView {
+  TriIsect const* always;         // the triangles every ray is tested against; == scene.tris when clusterCount == 0
+  uint32_t const* alwaysIdx;      // [alwaysCount] original index of always[i] (clusterCount > 0 only)
+  CullCluster const* clusters;    // [kCullMaxClusters]
+  float const* tri9;              // [9][kCullMaxTris] p0, e0, e1 of the culled triangles, field-major
+  uint32_t alwaysCount, clusterCount;
+};
+
 struct RenderParams {
   SceneView scene;
+  CullView cull;
   BvhView bvh;
   CameraXf cam;
   SamplerParams sp;
@@ -344,6 +365,7 @@ DMT_DEV f3 apply_material_textures(KArgs k, Rec32& rec, uint32_t matId, int tri,
   return (l2 > 0.f && l2 < kInf) ? ns / sqrtf(l2) : ng;
 }
 
+template <bool CULL = true>
 DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, int& bestTri, float& bu, float& bv, bool& occluded);
 
 // Optional parts of the path-tracing code, one bit each: the template argument F of path_shade, lane_finish, lane_step,
@@ -552,7 +574,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
             tmp.smax = pendMax;
             int bt;
             float tu, tvv;
-            trace_pair_brute(k, tmp, false, true, bt, tu, tvv, occ);
+            trace_pair_brute<false>(k, tmp, false, true, bt, tu, tvv, occ);  // divergent here: the plain loop over every triangle
           }
           if (!occ) st.L = st.L + pendC;
         }
@@ -673,12 +695,139 @@ struct BruteHit {
     if (doS && v2 && m.t.y < st.smax) h.occluded = true; /* :210-211 */                                        \
   } while (0)
 
+// LDS of the culled clusters: the block's copy of their triangles and cluster records (cull_stage), and per wave the
+// bound hits of each cluster and the per-lane results of the compacted tests (brute_clusters).  5 632 B per block.
+__shared__ float s_cullTri[9 * kCullMaxTris];                               // [field][slot]
+__shared__ CullCluster s_cullCl[kCullMaxClusters];
+__shared__ unsigned long long s_cullKey[kLdsThreads];                       // closest ray: min of (t bits << 32 | original index)
+__shared__ uint8_t s_cullOcc[kLdsThreads];                                  // shadow ray: some culled triangle occludes it
+__shared__ uint8_t s_cullOwner[kLdsThreads / 64][kCullMaxClusters][128];   // per cluster: lane | 64 * shadow of every bound hit
+constexpr float kCullTSlack = 1.0f + 1.0f / 256;  // the bound test's segment ends this much beyond smax / the best t so far
+constexpr float kCullRel = 1.0f / 16384;          // ... and its radius grows by this fraction of the squared ray extent
+
+// Every thread of a block that traces with trace_pair_brute<true> runs this once before its first trace (the kernels
+// whose body can call it: brute-force megakernels, k_test_trace, k_test_closest).  Any block size up to kLdsThreads.
+DMT_DEV void cull_stage(KArgs k) {
+  k = kargs(k);
+  if (k->cull.clusterCount == 0) return;  // uniform: nobody waits at the barrier
+  float const* const t9 = k->cull.tri9;
+  for (uint32_t i = threadIdx.x; i < 9 * kCullMaxTris; i += blockDim.x) s_cullTri[i] = t9[i];
+  uint32_t const* const cl = reinterpret_cast<uint32_t const*>(k->cull.clusters);
+  for (uint32_t i = threadIdx.x; i < kCullMaxClusters * 8; i += blockDim.x) reinterpret_cast<uint32_t*>(s_cullCl)[i] = cl[i];
+  __syncthreads();
+}
+
+// The culled clusters for the lane's ray pair, after the packed loop has run over the always list (h holds its result,
+// with the always list's position in h.tri).  For each cluster a packed segment-sphere test of both rays: [0, smax] for
+// the shadow ray, [0, best t so far] for the closest ray, both with slack.  Then the (ray, triangle) tests of the rays that
+// touched a bound are spread over the wave's active lanes, nAct per pass; a lane decodes (cluster, owner lane, kind,
+// triangle), fetches the owner's ray with ds_bpermute and runs the scalar mt_core9 + mt_valid, which are bit-identical to
+// the packed loop's halves.  Closest hits meet in a ds_min_u64 of (t bits, original index) per owner, shadow hits in an
+// OR.  The merge takes the lexicographic minimum with the loop's result: the same (tri, u, v, occluded) as one loop over
+// every triangle in index order with a strict < (valid t > 1e-4, so float bits order like the floats).
+DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, BruteHit& h) {
+  k = kargs(k);
+  uint32_t const nc = k->cull.clusterCount;
+  if (h.tri >= 0) h.tri = int(k->cull.alwaysIdx[h.tri]);
+  uint32_t const lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  unsigned long long const act = __ballot(1);
+  uint32_t const nAct = uint32_t(__popcll(act));
+  uint32_t const rank = __builtin_amdgcn_mbcnt_hi(uint32_t(act >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(act), 0u));
+  s_cullKey[threadIdx.x] = ~0ull;
+  s_cullOcc[threadIdx.x] = 0;
+  float const tmaxC = h.bt * kCullTSlack, tmaxS = st.smax * kCullTSlack;
+  uint32_t pre[kCullMaxClusters + 1];  // first task of each cluster (uniform)
+  pre[0] = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < kCullMaxClusters; ++c) {
+    uint32_t tasks = 0;
+    if (c < nc) {
+      CullCluster const cl = s_cullCl[c];
+      v2f const wx = cl.cx - st.rp.ox, wy = cl.cy - st.rp.oy, wz = cl.cz - st.rp.oz;
+      v2f const dd = st.rp.dx * st.rp.dx + st.rp.dy * st.rp.dy + st.rp.dz * st.rp.dz;
+      v2f const ww = wx * wx + wy * wy + wz * wz;
+      v2f tc = (wx * st.rp.dx + wy * st.rp.dy + wz * st.rp.dz) * rcp_(dd);
+      tc.x = fminf(fmaxf(tc.x, 0.f), tmaxC);
+      tc.y = fminf(fmaxf(tc.y, 0.f), tmaxS);
+      v2f const ex = wx - tc * st.rp.dx, ey = wy - tc * st.rp.dy, ez = wz - tc * st.rp.dz;
+      v2f const ee = ex * ex + ey * ey + ez * ez;
+      v2f const lim = cl.r2 + kCullRel * (ww + tc * tc * dd);
+      bool const hitC = doC && ee.x <= lim.x, hitS = doS && ee.y <= lim.y;
+      unsigned long long const mC = __ballot(hitC), mS = __ballot(hitS);
+      uint32_t const nC = uint32_t(__popcll(mC));
+      if (hitC) s_cullOwner[w][c][__builtin_amdgcn_mbcnt_hi(uint32_t(mC >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mC), 0u))] = uint8_t(lane);
+      if (hitS)
+        s_cullOwner[w][c][nC + __builtin_amdgcn_mbcnt_hi(uint32_t(mS >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mS), 0u))] =
+            uint8_t(lane | 64u);
+      tasks = (nC + uint32_t(__popcll(mS))) * cl.count;
+    }
+    pre[c + 1] = pre[c] + tasks;
+  }
+  uint32_t const total = pre[kCullMaxClusters];
+  asm volatile("" ::: "memory");  // one wave's LDS operations complete in order: only the compiler must not reorder them
+  for (uint32_t base = 0; base < total; base += nAct) {
+    uint32_t const g = min(base + rank, total - 1u);
+    uint32_t c = 0, first = 0;
+#pragma unroll
+    for (uint32_t q = 1; q < kCullMaxClusters; ++q)
+      if (g >= pre[q]) c = q, first = pre[q];
+    CullCluster const cl = s_cullCl[c];
+    uint32_t const local = g - first;
+    uint32_t const e = __umulhi(local, cl.magic);  // local / count, exact for local < 2^32 / count^2
+    uint32_t const j = local - e * cl.count;
+    uint32_t const own = s_cullOwner[w][c][e];
+    bool const shadow = own >= 64u;
+    int const src = int(own & 63u) << 2;
+    auto pull = [&](v2f v) {
+      float const a = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v.x)));
+      float const b = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v.y)));
+      return shadow ? b : a;
+    };
+    float const ox = pull(st.rp.ox), oy = pull(st.rp.oy), oz = pull(st.rp.oz);
+    float const dx = pull(st.rp.dx), dy = pull(st.rp.dy), dz = pull(st.rp.dz);
+    float const smax = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(st.smax)));
+    float const* const T = s_cullTri + cl.slot + j;
+    float det, t, u, v;
+    mt_core9<float>(T[0 * kCullMaxTris], T[1 * kCullMaxTris], T[2 * kCullMaxTris], T[3 * kCullMaxTris], T[4 * kCullMaxTris],
+                    T[5 * kCullMaxTris], T[6 * kCullMaxTris], T[7 * kCullMaxTris], T[8 * kCullMaxTris], ox, oy, oz, dx, dy, dz,
+                    det, t, u, v);
+    if (base + rank < total && mt_valid(det, t, u, v)) {
+      uint32_t const slot = w * 64u + (own & 63u);
+      if (shadow) {
+        if (t < smax) s_cullOcc[slot] = 1;
+      } else if (t < kInf) {
+        atomicMin(&s_cullKey[slot], (static_cast<unsigned long long>(__float_as_uint(t)) << 32) | (cl.first + j));
+      }
+    }
+  }
+  asm volatile("" ::: "memory");
+  if (doC) {
+    unsigned long long const kc = s_cullKey[threadIdx.x];
+    if (kc < ((static_cast<unsigned long long>(__float_as_uint(h.bt)) << 32) | uint32_t(h.tri))) {
+      uint32_t const orig = uint32_t(kc);
+      uint32_t slot = 0;
+#pragma unroll
+      for (uint32_t c = 0; c < kCullMaxClusters; ++c)
+        if (c < nc && orig - s_cullCl[c].first < s_cullCl[c].count) slot = s_cullCl[c].slot + (orig - s_cullCl[c].first);
+      float const* const T = s_cullTri + slot;
+      float det, t, u, v;  // the winner's u, v: the scalar form of the test again, on the lane's own ray
+      mt_core9<float>(T[0 * kCullMaxTris], T[1 * kCullMaxTris], T[2 * kCullMaxTris], T[3 * kCullMaxTris], T[4 * kCullMaxTris],
+                      T[5 * kCullMaxTris], T[6 * kCullMaxTris], T[7 * kCullMaxTris], T[8 * kCullMaxTris], st.rp.ox.x, st.rp.oy.x,
+                      st.rp.oz.x, st.rp.dx.x, st.rp.dy.x, st.rp.dz.x, det, t, u, v);
+      h.bt = __uint_as_float(uint32_t(kc >> 32)), h.tri = int(orig), h.bu = u, h.bv = v;
+    }
+  }
+  if (doS && s_cullOcc[threadIdx.x]) h.occluded = true;
+}
+
+// CULL = false: the plain loop over every triangle (callers in divergent code or outside a staged block).
+template <bool CULL>
 DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, int& bestTri, float& bu,
                               float& bv, bool& occluded) {
   BruteHit h{kInf, 0.f, 0.f, -1, false};
   k = kargs(k);
-  auto const* tris = to_const_as(k->scene.tris);
-  uint32_t const n = k->scene.triCount;
+  auto const* tris = to_const_as(CULL ? k->cull.always : k->scene.tris);
+  uint32_t const n = CULL ? k->cull.alwaysCount : k->scene.triCount;
   uint32_t const last = n ? n - 1 : 0;
   DMT_TRI_DECL(a);
   DMT_TRI_DECL(b);
@@ -694,6 +843,9 @@ DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, 
     __builtin_amdgcn_sched_barrier(0);
     DMT_TRI_TEST(b, i);
     ++i;
+  }
+  if constexpr (CULL) {
+    if (kargs(k)->cull.clusterCount != 0) brute_clusters(k, st, doC, doS, h);
   }
   bestTri = h.tri, bu = h.bu, bv = h.bv, occluded = h.occluded;
 }
@@ -1242,6 +1394,7 @@ DMT_DEV void megakernel_body() {
   LaneSched Ls;
   PathState st{};
   auto sink = [&](f3 L, uint32_t sidx) { stage_sample(Pk, sidx, L); };
+  cull_stage(Pk);
 #if DMT_SECTION_TIMING
   if (lane < 16) s_sectAcc[threadIdx.x >> 6][lane] = 0;
   sect_mark(15);
@@ -1469,6 +1622,7 @@ DMT_STATS_MEGAKERNELS(DMT_DEFINE_MEGAKERNEL)
 template <uint32_t F>
 __global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t const* pys, int32_t const* ss, float* L3) {
   KArgs const k = kargs_base();
+  if constexpr (!(F & kFeatBvh)) cull_stage(k);
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
   PathState st{};
   if (i < n) {
@@ -1514,7 +1668,7 @@ __global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float*
     int bestTri;
     float bu, bv;
     bool occluded;
-    trace_pair_brute(k, st, doC, doS, bestTri, bu, bv, occluded);
+    trace_pair_brute<false>(k, st, doC, doS, bestTri, bu, bv, occluded);  // one thread: the plain loop
     if (doS) {
       if (!occluded) st.L = st.L + get_C();
       st.hasShadow = false;
@@ -1640,6 +1794,7 @@ __global__ void k_test_half(int n, float const* fin, uint16_t* hout, uint16_t co
 __global__ void k_test_closest(RenderParams P, bool useBvh, int n, float const* o3, float const* d3, int32_t* tri,
                                float* tOut) {
   KArgs const k = kargs_base();
+  if (!useBvh) cull_stage(k);
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
   bool const alive = i < n;
   PathState st{};
@@ -1718,6 +1873,13 @@ struct dmt_ctx {
   DevBuf<Rec32> d_bsdfs, d_lights, d_inf;
   uint32_t triCount = 0, bsdfCount = 0, lightCount = 0, infCount = 0;
   uint32_t maxMatId = 0;
+  // the brute-force pass's culled clusters (planBruteCull); none: the pass tests d_tris for every ray
+  bool bruteCull = true;  // DMT_BRUTE_CULL=0 in the environment at context creation: no clusters (A/B runs, tests)
+  DevBuf<TriIsect> d_cullAlways;
+  DevBuf<uint32_t> d_cullIdx;
+  DevBuf<CullCluster> d_cullClusters;
+  DevBuf<float> d_cullTri9;
+  uint32_t cullAlwaysCount = 0, cullClusterCount = 0;
   // BVH (built on demand for DMT_ACCEL_BVH)
   std::vector<float> h_xs, h_ys, h_zs;  // host copy of the soup (the builder's input)
   std::vector<uint32_t> h_mat;
@@ -1845,6 +2007,58 @@ H3 hnormalize(H3 a) {
   float const inv = 1.0f / sqrtf(a.x * a.x + a.y * a.y + a.z * a.z);
   return {a.x * inv, a.y * inv, a.z * inv};
 }
+
+// ---- the brute-force pass's culled clusters ----
+// A candidate is a maximal run of consecutive triangles with one material id (one mesh of the scene front-ends) of at least
+// kCullMinTris triangles.  Its bound is the sphere around the centre of its vertex box through the farthest vertex, inflated
+// by 1/1024 of the radius plus 1e-6 of (|centre|_max + radius): far more than mt_valid's 1e-7 barycentric slack (1e-7 of an
+// edge), the float rounding of the centre and of e0 / e1, and the squared radius is rounded up.  It is culled when that
+// radius is at most kCullMaxRadiusFrac of the scene's bounding-box diagonal; in index order while at most kCullMaxClusters
+// clusters and kCullMaxTris triangles (the LDS copy) are taken.  The device test adds a relative margin of its own
+// (kCullRel) for the rounding of the segment-sphere test and of the Moeller-Trumbore hit point.
+constexpr uint32_t kCullMinTris = 4;
+constexpr double kCullMaxRadiusFrac = 0.125;
+std::vector<CullCluster> planBruteCull(float const* xs, float const* ys, float const* zs, uint32_t const* mat, uint32_t n, bool enable,
+                                       std::vector<float>* radii) {
+  std::vector<CullCluster> out;
+  if (!enable || n == 0) return out;
+  auto vtx = [&](uint32_t t, int k, int a) { return double((a == 0 ? xs : a == 1 ? ys : zs)[4 * size_t(t) + k]); };
+  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  for (uint32_t t = 0; t < n; ++t)
+    for (int k = 0; k < 3; ++k)
+      for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], vtx(t, k, a)), hi[a] = std::fmax(hi[a], vtx(t, k, a));
+  double const diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+  if (!std::isfinite(diag)) return out;
+  uint32_t culled = 0;
+  for (uint32_t first = 0, end = 0; first < n && out.size() < kCullMaxClusters; first = end) {
+    for (end = first + 1; end < n && mat[end] == mat[first];) ++end;
+    uint32_t const count = end - first;
+    if (count < kCullMinTris || culled + count > kCullMaxTris) continue;
+    double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (uint32_t t = first; t < end; ++t)
+      for (int k = 0; k < 3; ++k)
+        for (int a = 0; a < 3; ++a) blo[a] = std::fmin(blo[a], vtx(t, k, a)), bhi[a] = std::fmax(bhi[a], vtx(t, k, a));
+    float const c[3] = {float(0.5 * (blo[0] + bhi[0])), float(0.5 * (blo[1] + bhi[1])), float(0.5 * (blo[2] + bhi[2]))};
+    double r2 = 0.0;
+    for (uint32_t t = first; t < end; ++t)
+      for (int k = 0; k < 3; ++k) {
+        double const dx = vtx(t, k, 0) - c[0], dy = vtx(t, k, 1) - c[1], dz = vtx(t, k, 2) - c[2];
+        r2 = std::fmax(r2, dx * dx + dy * dy + dz * dz);
+      }
+    double const cmax = std::fmax(std::fabs(double(c[0])), std::fmax(std::fabs(double(c[1])), std::fabs(double(c[2]))));
+    double const r = std::sqrt(r2) * (1.0 + 1.0 / 1024) + 1e-6 * (cmax + std::sqrt(r2));
+    if (!(r <= kCullMaxRadiusFrac * diag)) continue;
+    CullCluster cl{};
+    cl.cx = c[0], cl.cy = c[1], cl.cz = c[2];
+    cl.r2 = std::nextafter(float(r * r), HUGE_VALF);
+    cl.first = first, cl.count = count, cl.slot = culled;
+    cl.magic = uint32_t(((uint64_t(1) << 32) + count - 1) / count);
+    out.push_back(cl);
+    if (radii) radii->push_back(float(r));
+    culled += count;
+  }
+  return out;
+}
 void worldFromCamera(float const dir[3], float const pos[3], float m[16]) {
   H3 const fwd = hnormalize({dir[0], dir[1], dir[2]});
   H3 const right = hnormalize(hcross(fwd, {0, 0, 1}));
@@ -1964,6 +2178,12 @@ int bvhShadeThreshold(dmt_ctx const* c) {
 RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   RenderParams P{};
   P.scene = sceneView(c);
+  if (c->cullClusterCount > 0) {
+    P.cull.always = c->d_cullAlways.get(), P.cull.alwaysIdx = c->d_cullIdx.get(), P.cull.clusters = c->d_cullClusters.get();
+    P.cull.tri9 = c->d_cullTri9.get(), P.cull.alwaysCount = c->cullAlwaysCount, P.cull.clusterCount = c->cullClusterCount;
+  } else {
+    P.cull.always = c->d_tris.get(), P.cull.alwaysCount = c->triCount;
+  }
   P.bvh = bvhView(c, threads);
   P.cam = c->xf;
   P.sp = c->sp;
@@ -2193,6 +2413,7 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
     long long const v = std::atoll(e4);
     if (v >= 4096) ctx->wfTargetPaths = size_t(v);
   }
+  if (char const* e6 = std::getenv("DMT_BRUTE_CULL")) ctx->bruteCull = std::atoi(e6) != 0;  // A/B runs and tests
   if (char const* e2 = std::getenv("DMT_SUB_SHIFT")) {  // scheduling experiments only: results do not depend on it
     int const v = std::atoi(e2);
     ctx->subShift = v < 0 ? -1 : (v > 2 ? 2 : v);
@@ -2249,7 +2470,38 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   DevBuf<TriPost> post;
   HIP_TRY(ctx, tris.assign(a.data(), count));
   HIP_TRY(ctx, post.assign(b.data(), count));
+  std::vector<CullCluster> const clusters = planBruteCull(xs, ys, zs, mat_id, uint32_t(count), ctx->bruteCull, nullptr);
+  DevBuf<TriIsect> cullAlways;
+  DevBuf<uint32_t> cullIdx;
+  DevBuf<CullCluster> cullClusters;
+  DevBuf<float> cullTri9;
+  uint32_t alwaysCount = uint32_t(count);
+  if (!clusters.empty()) {
+    std::vector<uint8_t> culled(count, 0);
+    std::vector<float> tri9(9 * kCullMaxTris, 0.f);
+    for (CullCluster const& cl : clusters)
+      for (uint32_t j = 0; j < cl.count; ++j) {
+        TriIsect const& t = a[cl.first + j];
+        float const f[9] = {t.p0x, t.p0y, t.p0z, t.e0x, t.e0y, t.e0z, t.e1x, t.e1y, t.e1z};
+        for (int q = 0; q < 9; ++q) tri9[q * kCullMaxTris + cl.slot + j] = f[q];
+        culled[cl.first + j] = 1;
+      }
+    std::vector<TriIsect> always;
+    std::vector<uint32_t> idx;
+    for (size_t i = 0; i < count; ++i)
+      if (!culled[i]) always.push_back(a[i]), idx.push_back(uint32_t(i));
+    std::vector<CullCluster> table(kCullMaxClusters, CullCluster{});
+    std::copy(clusters.begin(), clusters.end(), table.begin());
+    alwaysCount = uint32_t(always.size());
+    HIP_TRY(ctx, cullAlways.assign(always.data(), always.size()));
+    HIP_TRY(ctx, cullIdx.assign(idx.data(), idx.size()));
+    HIP_TRY(ctx, cullClusters.assign(table.data(), table.size()));
+    HIP_TRY(ctx, cullTri9.assign(tri9.data(), tri9.size()));
+  }
   ctx->d_tris = std::move(tris), ctx->d_post = std::move(post);
+  ctx->d_cullAlways = std::move(cullAlways), ctx->d_cullIdx = std::move(cullIdx);
+  ctx->d_cullClusters = std::move(cullClusters), ctx->d_cullTri9 = std::move(cullTri9);
+  ctx->cullAlwaysCount = alwaysCount, ctx->cullClusterCount = uint32_t(clusters.size());
   ctx->triCount = uint32_t(count);
   ctx->maxMatId = maxMat;
   ctx->haveTris = true;
@@ -2677,6 +2929,20 @@ extern "C" int dmt_diag_section_cycles(unsigned long long* out16, int reset) {
 // Host-only: build the BVH of a soup and check its invariants (every triangle in exactly one leaf, every DECODED
 // (quantised) child box encloses all vertices below it and lies inside its parent's decoded box up to one quantisation
 // step, inner children first with consecutive indices, depth within the traversal-stack bound).
+int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                        uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_sphere) {
+  if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
+  std::vector<float> radii;
+  std::vector<CullCluster> const cl = planBruteCull(xs, ys, zs, mat_id, uint32_t(count), enable != 0, &radii);
+  *cluster_count = uint32_t(cl.size());
+  for (size_t k = 0; k < cl.size(); ++k) {
+    if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
+    if (cluster_sphere) cluster_sphere[4 * k] = cl[k].cx, cluster_sphere[4 * k + 1] = cl[k].cy, cluster_sphere[4 * k + 2] = cl[k].cz,
+                        cluster_sphere[4 * k + 3] = radii[k];
+  }
+  return DMT_OK;
+}
+
 int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t count, int* node_count, int* depth,
                      int* max_leaf) {
   if ((count && (!xs || !ys || !zs)) || count > 0x0FFFFFFFu) return DMT_ERR_INVALID;

@@ -206,6 +206,13 @@ int dmt_kernel_info(dmt_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* b
 int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t count, int* node_count,
                      int* depth, int* max_leaf);
 
+/* host-only (no GPU needed): how the brute-force pass splits a soup.  Up to 4 culled clusters, runs of
+ * >= 4 consecutive triangles of one material whose bounding sphere is small next to the scene; every other triangle is
+ * tested for every ray.  Cluster k: cluster_first_count[2k], [2k + 1] = first original index, triangle count;
+ * cluster_sphere[4k .. 4k + 3] = centre and inflated radius.  enable = 0 gives no cluster (what DMT_BRUTE_CULL=0 does). */
+int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count,
+                        int enable, uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_sphere);
+
 /* ---- device unit-test entry points (GPU twins of the reference's T/tests kernels) ---------- */
 int dmt_test_triangle_intersect(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs,
                                 size_t count, const float* o3, const float* d3, int32_t* hit,
