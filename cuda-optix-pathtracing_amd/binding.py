@@ -54,7 +54,7 @@ EXPORTED_SYMBOLS = [
     "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
-    "dmt_render", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_test_triangle_intersect",
+    "dmt_render", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_test_triangle_intersect",
     "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_light", "dmt_test_half",
     "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
 ]
@@ -124,6 +124,20 @@ def brute_cull_plan(xs, ys, zs, mat_id, enable=True):
         raise DmtError(f"dmt_brute_cull_plan failed ({rc})")
     return [(int(fc[2 * k]), int(fc[2 * k + 1]), tuple(float(x) for x in sph[4 * k:4 * k + 3]), float(sph[4 * k + 3]))
             for k in range(nc.value)]
+
+
+def brute_cull_box_plan(xs, ys, zs, mat_id, enable=True):
+    """Host-only: the box clusters of the brute-force pass, a list of (first, count, (lox, loy, loz), (hix, hiy, hiz))."""
+    lib = load_library()
+    xs, ys, zs = _f32(xs), _f32(ys), _f32(zs)
+    mat = np.ascontiguousarray(mat_id, np.uint32)
+    n = xs.size // 4
+    nc, fc, box = C.c_uint32(), np.zeros(24, np.uint32), np.zeros(72, np.float32)
+    rc = lib.dmt_brute_cull_box_plan(_p(xs), _p(ys), _p(zs), _p(mat), C.c_size_t(n), int(bool(enable)), C.byref(nc), _p(fc), _p(box))
+    if rc != 0:
+        raise DmtError(f"dmt_brute_cull_box_plan failed ({rc})")
+    return [(int(fc[2 * k]), int(fc[2 * k + 1]), tuple(float(x) for x in box[6 * k:6 * k + 3]),
+             tuple(float(x) for x in box[6 * k + 3:6 * k + 6])) for k in range(nc.value)]
 
 
 def envmap_tables(rgb):

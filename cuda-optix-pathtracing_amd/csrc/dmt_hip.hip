@@ -39,16 +39,25 @@ using namespace dmt;
 
 namespace {
 
-// Culled clusters of the brute-force pass (planBruteCull on the host, brute_clusters on the device).  A cluster is a run of
-// consecutive triangles of one material -- one mesh of the scene front-ends -- that is small next to the scene; the pass tests
-// its triangles only for the rays that touch its bounding sphere, compacted over the wave's lanes.  Everything else stays in
-// the "always" list, which the packed SGPR loop tests for every ray as before.
-constexpr uint32_t kCullMaxClusters = 4;
-constexpr uint32_t kCullMaxTris = 32;   // LDS copy of the culled triangles, 36 B each (see the LDS budget in DESIGN.md 4.1)
-struct CullCluster {                    // 32 B
-  float cx, cy, cz, r2;                 // bounding sphere: centre and squared inflated radius
-  uint32_t first, count;                // original triangle indices [first, first + count)
-  uint32_t slot, magic;                 // first slot of its triangles in the LDS copy; ceil(2^32 / count)
+// Culled clusters of the brute-force pass (planBruteCull / planBruteCullBox on the host, brute_clusters on the device).  A
+// cluster is a run of consecutive triangles of one material -- one mesh of the scene front-ends -- with a cheap bound: a small
+// sphere (compact meshes) or a thin box (flat meshes such as walls); the pass tests its triangles only for the rays that touch
+// the bound, compacted over the wave's lanes.  Everything else stays in the "always" list, which the packed SGPR loop tests
+// for every ray as before.
+constexpr uint32_t kCullMaxClusters = 12;  // sphere clusters first, then box clusters; the device takes them kCullGroup at a time
+constexpr uint32_t kCullGroup = 4;
+constexpr uint32_t kCullMaxTris = 44;      // LDS copy of the culled triangles, 36 B each (see the LDS budget in DESIGN.md 4.1)
+constexpr uint32_t kCullSlotBits = 6;      // a closest-hit key holds (original index << 6 | LDS slot): kCullMaxTris <= 64
+constexpr uint32_t kCullMaxIndex = 1u << (32 - kCullSlotBits);  // no culling for soups of more triangles
+struct CullCluster {                       // 48 B, read by scalar loads in the bound tests
+  float b[6];                              // sphere: centre xyz and squared inflated radius; box: inflated lo xyz, hi xyz
+  uint32_t box;                            // 0: sphere bound, 1: box bound
+  uint32_t first, count;                   // original triangle indices [first, first + count)
+  uint32_t slot, magic;                    // first slot of its triangles in the LDS copy; ceil(2^32 / count)
+  uint32_t pad;
+};
+struct CullRec {                           // 12 B, the block's LDS copy of what a compacted task needs
+  uint32_t first, countSlot, magic;        // countSlot = count | slot << 16
 };
 struct CullView {
   TriIsect const* always;         // the triangles every ray is tested against; == scene.tris when clusterCount == 0
@@ -695,15 +704,26 @@ struct BruteHit {
     if (doS && v2 && m.t.y < st.smax) h.occluded = true; /* :210-211 */                                        \
   } while (0)
 
-// LDS of the culled clusters: the block's copy of their triangles and cluster records (cull_stage), and per wave the
-// bound hits of each cluster and the per-lane results of the compacted tests (brute_clusters).  5 632 B per block.
-__shared__ float s_cullTri[9 * kCullMaxTris];                               // [field][slot]
-__shared__ CullCluster s_cullCl[kCullMaxClusters];
-__shared__ unsigned long long s_cullKey[kLdsThreads];                       // closest ray: min of (t bits << 32 | original index)
-__shared__ uint8_t s_cullOcc[kLdsThreads];                                  // shadow ray: some culled triangle occludes it
-__shared__ uint8_t s_cullOwner[kLdsThreads / 64][kCullMaxClusters][128];   // per cluster: lane | 64 * shadow of every bound hit
+// LDS of the culled clusters: the block's copy of their triangles and task records (cull_stage), and per wave the bound
+// hits of one group of kCullGroup clusters and the per-lane results of the compacted tests (brute_clusters).  5 856 B per block.
+__shared__ float s_cullTri[9 * kCullMaxTris];                         // [field][slot]
+__shared__ CullRec s_cullRec[kCullMaxClusters];
+__shared__ unsigned long long s_cullKey[kLdsThreads];                 // closest ray: min of (t bits << 32 | original index << 6 | slot)
+__shared__ unsigned long long s_cullOcc[kLdsThreads / 64];            // shadow rays: bit `lane` = some culled triangle occludes it
+__shared__ uint8_t s_cullOwner[kLdsThreads / 64][kCullGroup][128];   // per cluster of the group: lane | 64 * shadow of every bound hit
 constexpr float kCullTSlack = 1.0f + 1.0f / 256;  // the bound test's segment ends this much beyond smax / the best t so far
-constexpr float kCullRel = 1.0f / 16384;          // ... and its radius grows by this fraction of the squared ray extent
+constexpr float kCullRel = 1.0f / 16384;          // ... and a sphere's radius grows by this fraction of the squared ray extent
+constexpr float kCullTLo = 1e-4f * (1.0f - 1.0f / 256);  // box bounds: the segment starts this far below mt_valid's t > 1e-4
+
+#ifndef DMT_CULL_COUNTS
+#define DMT_CULL_COUNTS 0
+#endif
+#if DMT_CULL_COUNTS
+// Diagnostic build only (make variant DEFS=-DDMT_CULL_COUNTS=1): the work of brute_clusters summed over all waves, read back
+// with dmt_diag_cull_counts (tools/diag_cull_counts.py).  [0] calls per wave, [1] / [2] closest / shadow rays, [3] task passes,
+// [4 + kind] bound hits of closest rays, [6 + kind] of shadow rays, [8 + kind] compacted tasks; kind 0 = sphere, 1 = box.
+__device__ unsigned long long g_cullCount[16];
+#endif
 
 // Every thread of a block that traces with trace_pair_brute<true> runs this once before its first trace (the kernels
 // whose body can call it: brute-force megakernels, k_test_trace, k_test_closest).  Any block size up to kLdsThreads.
@@ -712,112 +732,160 @@ DMT_DEV void cull_stage(KArgs k) {
   if (k->cull.clusterCount == 0) return;  // uniform: nobody waits at the barrier
   float const* const t9 = k->cull.tri9;
   for (uint32_t i = threadIdx.x; i < 9 * kCullMaxTris; i += blockDim.x) s_cullTri[i] = t9[i];
-  uint32_t const* const cl = reinterpret_cast<uint32_t const*>(k->cull.clusters);
-  for (uint32_t i = threadIdx.x; i < kCullMaxClusters * 8; i += blockDim.x) reinterpret_cast<uint32_t*>(s_cullCl)[i] = cl[i];
+  CullCluster const* const cl = k->cull.clusters;
+  for (uint32_t i = threadIdx.x; i < kCullMaxClusters; i += blockDim.x)
+    s_cullRec[i] = CullRec{cl[i].first, cl[i].count | cl[i].slot << 16, cl[i].magic};
   __syncthreads();
 }
 
+// 1 / d for the slab test, with |d| raised to FLT_MIN first: the reciprocal is finite, so (plane - o) * inv is never
+// 0 * inf = NaN.  A zero component becomes a tiny one of the same sign: the ray leans into the slab it lies in, and an
+// origin on a face gives t = 0 on that face -- a hit, never a miss.  (1 / FLT_MIN = 2^126 is a normal float.)
+DMT_DEV float slab_rcp(float d) { return rcp_(copysignf(fmaxf(fabsf(d), 0x1p-126f), d)); }
+
 // The culled clusters for the lane's ray pair, after the packed loop has run over the always list (h holds its result,
-// with the always list's position in h.tri).  For each cluster a packed segment-sphere test of both rays: [0, smax] for
-// the shadow ray, [0, best t so far] for the closest ray, both with slack.  Then the (ray, triangle) tests of the rays that
-// touched a bound are spread over the wave's active lanes, nAct per pass; a lane decodes (cluster, owner lane, kind,
-// triangle), fetches the owner's ray with ds_bpermute and runs the scalar mt_core9 + mt_valid, which are bit-identical to
-// the packed loop's halves.  Closest hits meet in a ds_min_u64 of (t bits, original index) per owner, shadow hits in an
-// OR.  The merge takes the lexicographic minimum with the loop's result: the same (tri, u, v, occluded) as one loop over
-// every triangle in index order with a strict < (valid t > 1e-4, so float bits order like the floats).
+// with the always list's position in h.tri).  The clusters are taken kCullGroup at a time, which bounds the owner lists.  For
+// each cluster of a group a packed bound test of both rays, over [0 or kCullTLo, smax] for the shadow ray and up to the best
+// t so far for the closest ray, with slack: segment-sphere for sphere bounds, slabs for box bounds.  Then the (ray, triangle)
+// tests of the rays that touched a bound are spread over the wave's active lanes, nAct per pass; a lane decodes (cluster,
+// owner lane, kind, triangle), fetches the owner's ray with ds_bpermute and runs the scalar mt_core9 + mt_valid, which are
+// bit-identical to the packed loop's halves.  Closest hits meet in a ds_min_u64 of (t bits, original index, slot) per owner,
+// shadow hits in an OR.  After a group the closest ray's segment shrinks to the best culled hit so far.  The merge takes the
+// lexicographic minimum with the loop's result: the same (tri, u, v, occluded) as one loop over every triangle in index order
+// with a strict < (valid t > 1e-4, so float bits order like the floats; no two triangles share an original index).
 DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, BruteHit& h) {
   k = kargs(k);
   uint32_t const nc = k->cull.clusterCount;
+  auto const* const cls = to_const_as(k->cull.clusters);
   if (h.tri >= 0) h.tri = int(k->cull.alwaysIdx[h.tri]);
   uint32_t const lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
   unsigned long long const act = __ballot(1);
   uint32_t const nAct = uint32_t(__popcll(act));
   uint32_t const rank = __builtin_amdgcn_mbcnt_hi(uint32_t(act >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(act), 0u));
   s_cullKey[threadIdx.x] = ~0ull;
-  s_cullOcc[threadIdx.x] = 0;
-  float const tmaxC = h.bt * kCullTSlack, tmaxS = st.smax * kCullTSlack;
-  uint32_t pre[kCullMaxClusters + 1];  // first task of each cluster (uniform)
-  pre[0] = 0;
+  s_cullOcc[w] = 0;
+  float tmaxC = h.bt * kCullTSlack;
+  float const tmaxS = st.smax * kCullTSlack;
+  v2f const ix = {slab_rcp(st.rp.dx.x), slab_rcp(st.rp.dx.y)};
+  v2f const iy = {slab_rcp(st.rp.dy.x), slab_rcp(st.rp.dy.y)};
+  v2f const iz = {slab_rcp(st.rp.dz.x), slab_rcp(st.rp.dz.y)};
+#if DMT_CULL_COUNTS
+  unsigned long long cnt[16] = {};
+  cnt[0] = 1, cnt[1] = __popcll(__ballot(doC)), cnt[2] = __popcll(__ballot(doS));
+#endif
+  for (uint32_t c0 = 0; c0 < nc; c0 += kCullGroup) {
+    uint32_t pre[kCullGroup + 1];  // first task of each cluster of the group (uniform)
+    pre[0] = 0;
 #pragma unroll
-  for (uint32_t c = 0; c < kCullMaxClusters; ++c) {
-    uint32_t tasks = 0;
-    if (c < nc) {
-      CullCluster const cl = s_cullCl[c];
-      v2f const wx = cl.cx - st.rp.ox, wy = cl.cy - st.rp.oy, wz = cl.cz - st.rp.oz;
-      v2f const dd = st.rp.dx * st.rp.dx + st.rp.dy * st.rp.dy + st.rp.dz * st.rp.dz;
-      v2f const ww = wx * wx + wy * wy + wz * wz;
-      v2f tc = (wx * st.rp.dx + wy * st.rp.dy + wz * st.rp.dz) * rcp_(dd);
-      tc.x = fminf(fmaxf(tc.x, 0.f), tmaxC);
-      tc.y = fminf(fmaxf(tc.y, 0.f), tmaxS);
-      v2f const ex = wx - tc * st.rp.dx, ey = wy - tc * st.rp.dy, ez = wz - tc * st.rp.dz;
-      v2f const ee = ex * ex + ey * ey + ez * ez;
-      v2f const lim = cl.r2 + kCullRel * (ww + tc * tc * dd);
-      bool const hitC = doC && ee.x <= lim.x, hitS = doS && ee.y <= lim.y;
-      unsigned long long const mC = __ballot(hitC), mS = __ballot(hitS);
-      uint32_t const nC = uint32_t(__popcll(mC));
-      if (hitC) s_cullOwner[w][c][__builtin_amdgcn_mbcnt_hi(uint32_t(mC >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mC), 0u))] = uint8_t(lane);
-      if (hitS)
-        s_cullOwner[w][c][nC + __builtin_amdgcn_mbcnt_hi(uint32_t(mS >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mS), 0u))] =
-            uint8_t(lane | 64u);
-      tasks = (nC + uint32_t(__popcll(mS))) * cl.count;
+    for (uint32_t q = 0; q < kCullGroup; ++q) {
+      uint32_t tasks = 0;
+      if (c0 + q < nc) {
+        auto const& r = cls[c0 + q];  // scalar loads: c0 + q is uniform
+        CullCluster cl;
+        for (int i = 0; i < 6; ++i) cl.b[i] = r.b[i];
+        cl.box = r.box, cl.count = r.count;
+        bool hitC, hitS;
+        if (cl.box) {
+          // slabs: per axis the t of the two faces, near = max over the axes' entries and the segment start, far = min over
+          // the exits and the segment end.  Each t is within a few ulps (relative) of the exact one, near > 0, so
+          // near <= far * kCullTSlack keeps every segment that meets the box.
+          v2f const x0 = (cl.b[0] - st.rp.ox) * ix, x1 = (cl.b[3] - st.rp.ox) * ix;
+          v2f const y0 = (cl.b[1] - st.rp.oy) * iy, y1 = (cl.b[4] - st.rp.oy) * iy;
+          v2f const z0 = (cl.b[2] - st.rp.oz) * iz, z1 = (cl.b[5] - st.rp.oz) * iz;
+          float const nC = fmaxf(fmaxf(fminf(x0.x, x1.x), fminf(y0.x, y1.x)), fmaxf(fminf(z0.x, z1.x), kCullTLo));
+          float const fC = fminf(fminf(fmaxf(x0.x, x1.x), fmaxf(y0.x, y1.x)), fminf(fmaxf(z0.x, z1.x), tmaxC));
+          float const nS = fmaxf(fmaxf(fminf(x0.y, x1.y), fminf(y0.y, y1.y)), fmaxf(fminf(z0.y, z1.y), kCullTLo));
+          float const fS = fminf(fminf(fmaxf(x0.y, x1.y), fmaxf(y0.y, y1.y)), fminf(fmaxf(z0.y, z1.y), tmaxS));
+          hitC = doC && nC <= fC * kCullTSlack, hitS = doS && nS <= fS * kCullTSlack;
+        } else {
+          v2f const wx = cl.b[0] - st.rp.ox, wy = cl.b[1] - st.rp.oy, wz = cl.b[2] - st.rp.oz;
+          v2f const dd = st.rp.dx * st.rp.dx + st.rp.dy * st.rp.dy + st.rp.dz * st.rp.dz;
+          v2f const ww = wx * wx + wy * wy + wz * wz;
+          v2f tc = (wx * st.rp.dx + wy * st.rp.dy + wz * st.rp.dz) * rcp_(dd);
+          tc.x = fminf(fmaxf(tc.x, 0.f), tmaxC);
+          tc.y = fminf(fmaxf(tc.y, 0.f), tmaxS);
+          v2f const ex = wx - tc * st.rp.dx, ey = wy - tc * st.rp.dy, ez = wz - tc * st.rp.dz;
+          v2f const ee = ex * ex + ey * ey + ez * ez;
+          v2f const lim = cl.b[3] + kCullRel * (ww + tc * tc * dd);
+          hitC = doC && ee.x <= lim.x, hitS = doS && ee.y <= lim.y;
+        }
+        unsigned long long const mC = __ballot(hitC), mS = __ballot(hitS);
+        uint32_t const nC = uint32_t(__popcll(mC)), nS = uint32_t(__popcll(mS));
+        if (hitC) s_cullOwner[w][q][__builtin_amdgcn_mbcnt_hi(uint32_t(mC >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mC), 0u))] = uint8_t(lane);
+        if (hitS)
+          s_cullOwner[w][q][nC + __builtin_amdgcn_mbcnt_hi(uint32_t(mS >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mS), 0u))] =
+              uint8_t(lane | 64u);
+        tasks = (nC + nS) * cl.count;
+#if DMT_CULL_COUNTS
+        if (cl.box) cnt[5] += nC, cnt[7] += nS, cnt[9] += tasks;
+        else cnt[4] += nC, cnt[6] += nS, cnt[8] += tasks;
+#endif
+      }
+      pre[q + 1] = pre[q] + tasks;
     }
-    pre[c + 1] = pre[c] + tasks;
-  }
-  uint32_t const total = pre[kCullMaxClusters];
-  asm volatile("" ::: "memory");  // one wave's LDS operations complete in order: only the compiler must not reorder them
-  for (uint32_t base = 0; base < total; base += nAct) {
-    uint32_t const g = min(base + rank, total - 1u);
-    uint32_t c = 0, first = 0;
+    uint32_t const total = pre[kCullGroup];
+#if DMT_CULL_COUNTS
+    cnt[3] += (total + nAct - 1) / nAct;
+#endif
+    asm volatile("" ::: "memory");  // one wave's LDS operations complete in order: only the compiler must not reorder them
+    for (uint32_t base = 0; base < total; base += nAct) {
+      uint32_t const g = min(base + rank, total - 1u);
+      uint32_t q = 0, first = 0;
 #pragma unroll
-    for (uint32_t q = 1; q < kCullMaxClusters; ++q)
-      if (g >= pre[q]) c = q, first = pre[q];
-    CullCluster const cl = s_cullCl[c];
-    uint32_t const local = g - first;
-    uint32_t const e = __umulhi(local, cl.magic);  // local / count, exact for local < 2^32 / count^2
-    uint32_t const j = local - e * cl.count;
-    uint32_t const own = s_cullOwner[w][c][e];
-    bool const shadow = own >= 64u;
-    int const src = int(own & 63u) << 2;
-    auto pull = [&](v2f v) {
-      float const a = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v.x)));
-      float const b = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v.y)));
-      return shadow ? b : a;
-    };
-    float const ox = pull(st.rp.ox), oy = pull(st.rp.oy), oz = pull(st.rp.oz);
-    float const dx = pull(st.rp.dx), dy = pull(st.rp.dy), dz = pull(st.rp.dz);
-    float const smax = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(st.smax)));
-    float const* const T = s_cullTri + cl.slot + j;
-    float det, t, u, v;
-    mt_core9<float>(T[0 * kCullMaxTris], T[1 * kCullMaxTris], T[2 * kCullMaxTris], T[3 * kCullMaxTris], T[4 * kCullMaxTris],
-                    T[5 * kCullMaxTris], T[6 * kCullMaxTris], T[7 * kCullMaxTris], T[8 * kCullMaxTris], ox, oy, oz, dx, dy, dz,
-                    det, t, u, v);
-    if (base + rank < total && mt_valid(det, t, u, v)) {
-      uint32_t const slot = w * 64u + (own & 63u);
-      if (shadow) {
-        if (t < smax) s_cullOcc[slot] = 1;
-      } else if (t < kInf) {
-        atomicMin(&s_cullKey[slot], (static_cast<unsigned long long>(__float_as_uint(t)) << 32) | (cl.first + j));
+      for (uint32_t p = 1; p < kCullGroup; ++p)
+        if (g >= pre[p]) q = p, first = pre[p];
+      CullRec const rec = s_cullRec[c0 + q];
+      uint32_t const count = rec.countSlot & 0xFFFFu, slot0 = rec.countSlot >> 16;
+      uint32_t const local = g - first;
+      uint32_t const e = __umulhi(local, rec.magic);  // local / count, exact for local < 2^32 / count^2
+      uint32_t const j = local - e * count;
+      uint32_t const own = s_cullOwner[w][q][e];
+      bool const shadow = own >= 64u;
+      int const src = int(own & 63u) << 2;
+      auto pull = [&](v2f v) {
+        float const a = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v.x)));
+        float const b = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v.y)));
+        return shadow ? b : a;
+      };
+      float const ox = pull(st.rp.ox), oy = pull(st.rp.oy), oz = pull(st.rp.oz);
+      float const dx = pull(st.rp.dx), dy = pull(st.rp.dy), dz = pull(st.rp.dz);
+      float const smax = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(st.smax)));
+      float const* const T = s_cullTri + slot0 + j;
+      float det, t, u, v;
+      mt_core9<float>(T[0 * kCullMaxTris], T[1 * kCullMaxTris], T[2 * kCullMaxTris], T[3 * kCullMaxTris], T[4 * kCullMaxTris],
+                      T[5 * kCullMaxTris], T[6 * kCullMaxTris], T[7 * kCullMaxTris], T[8 * kCullMaxTris], ox, oy, oz, dx, dy, dz,
+                      det, t, u, v);
+      if (base + rank < total && mt_valid(det, t, u, v)) {
+        if (shadow) {
+          if (t < smax) atomicOr(&s_cullOcc[w], 1ull << (own & 63u));
+        } else if (t < kInf) {
+          atomicMin(&s_cullKey[w * 64u + own],
+                    (static_cast<unsigned long long>(__float_as_uint(t)) << 32) | ((rec.first + j) << kCullSlotBits) | (slot0 + j));
+        }
       }
     }
+    asm volatile("" ::: "memory");
+    if (c0 + kCullGroup < nc) {  // the next group's closest segment ends at the best culled hit so far
+      unsigned long long const kc = s_cullKey[threadIdx.x];
+      if (kc != ~0ull) tmaxC = fminf(tmaxC, __uint_as_float(uint32_t(kc >> 32)) * kCullTSlack);
+    }
   }
-  asm volatile("" ::: "memory");
+#if DMT_CULL_COUNTS
+  if (rank == 0)
+    for (int i = 0; i < 10; ++i) atomicAdd(&g_cullCount[i], cnt[i]);
+#endif
   if (doC) {
     unsigned long long const kc = s_cullKey[threadIdx.x];
-    if (kc < ((static_cast<unsigned long long>(__float_as_uint(h.bt)) << 32) | uint32_t(h.tri))) {
-      uint32_t const orig = uint32_t(kc);
-      uint32_t slot = 0;
-#pragma unroll
-      for (uint32_t c = 0; c < kCullMaxClusters; ++c)
-        if (c < nc && orig - s_cullCl[c].first < s_cullCl[c].count) slot = s_cullCl[c].slot + (orig - s_cullCl[c].first);
-      float const* const T = s_cullTri + slot;
+    if (kc < ((static_cast<unsigned long long>(__float_as_uint(h.bt)) << 32) | (uint32_t(h.tri) << kCullSlotBits))) {
+      float const* const T = s_cullTri + (uint32_t(kc) & ((1u << kCullSlotBits) - 1u));
       float det, t, u, v;  // the winner's u, v: the scalar form of the test again, on the lane's own ray
       mt_core9<float>(T[0 * kCullMaxTris], T[1 * kCullMaxTris], T[2 * kCullMaxTris], T[3 * kCullMaxTris], T[4 * kCullMaxTris],
                       T[5 * kCullMaxTris], T[6 * kCullMaxTris], T[7 * kCullMaxTris], T[8 * kCullMaxTris], st.rp.ox.x, st.rp.oy.x,
                       st.rp.oz.x, st.rp.dx.x, st.rp.dy.x, st.rp.dz.x, det, t, u, v);
-      h.bt = __uint_as_float(uint32_t(kc >> 32)), h.tri = int(orig), h.bu = u, h.bv = v;
+      h.bt = __uint_as_float(uint32_t(kc >> 32)), h.tri = int(uint32_t(kc) >> kCullSlotBits), h.bu = u, h.bv = v;
     }
   }
-  if (doS && s_cullOcc[threadIdx.x]) h.occluded = true;
+  if (doS && ((s_cullOcc[w] >> lane) & 1ull)) h.occluded = true;
 }
 
 // CULL = false: the plain loop over every triangle (callers in divergent code or outside a staged block).
@@ -1873,8 +1941,8 @@ struct dmt_ctx {
   DevBuf<Rec32> d_bsdfs, d_lights, d_inf;
   uint32_t triCount = 0, bsdfCount = 0, lightCount = 0, infCount = 0;
   uint32_t maxMatId = 0;
-  // the brute-force pass's culled clusters (planBruteCull); none: the pass tests d_tris for every ray
-  bool bruteCull = true;  // DMT_BRUTE_CULL=0 in the environment at context creation: no clusters (A/B runs, tests)
+  // the brute-force pass's culled clusters (planBruteCull, planBruteCullBox); none: the pass tests d_tris for every ray
+  int bruteCull = 2;  // DMT_BRUTE_CULL at context creation (A/B runs, tests): 0 no clusters, 1 sphere clusters only, unset both
   DevBuf<TriIsect> d_cullAlways;
   DevBuf<uint32_t> d_cullIdx;
   DevBuf<CullCluster> d_cullClusters;
@@ -2013,11 +2081,12 @@ H3 hnormalize(H3 a) {
 // kCullMinTris triangles.  Its bound is the sphere around the centre of its vertex box through the farthest vertex, inflated
 // by 1/1024 of the radius plus 1e-6 of (|centre|_max + radius): far more than mt_valid's 1e-7 barycentric slack (1e-7 of an
 // edge), the float rounding of the centre and of e0 / e1, and the squared radius is rounded up.  It is culled when that
-// radius is at most kCullMaxRadiusFrac of the scene's bounding-box diagonal; in index order while at most kCullMaxClusters
-// clusters and kCullMaxTris triangles (the LDS copy) are taken.  The device test adds a relative margin of its own
+// radius is at most kCullMaxRadiusFrac of the scene's bounding-box diagonal; in index order while at most kCullMaxSphereClusters
+// clusters and kCullMaxSphereTris triangles are taken.  The device test adds a relative margin of its own
 // (kCullRel) for the rounding of the segment-sphere test and of the Moeller-Trumbore hit point.
 constexpr uint32_t kCullMinTris = 4;
 constexpr double kCullMaxRadiusFrac = 0.125;
+constexpr uint32_t kCullMaxSphereClusters = 4, kCullMaxSphereTris = 32;
 std::vector<CullCluster> planBruteCull(float const* xs, float const* ys, float const* zs, uint32_t const* mat, uint32_t n, bool enable,
                                        std::vector<float>* radii) {
   std::vector<CullCluster> out;
@@ -2030,10 +2099,10 @@ std::vector<CullCluster> planBruteCull(float const* xs, float const* ys, float c
   double const diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
   if (!std::isfinite(diag)) return out;
   uint32_t culled = 0;
-  for (uint32_t first = 0, end = 0; first < n && out.size() < kCullMaxClusters; first = end) {
+  for (uint32_t first = 0, end = 0; first < n && out.size() < kCullMaxSphereClusters; first = end) {
     for (end = first + 1; end < n && mat[end] == mat[first];) ++end;
     uint32_t const count = end - first;
-    if (count < kCullMinTris || culled + count > kCullMaxTris) continue;
+    if (count < kCullMinTris || culled + count > kCullMaxSphereTris) continue;
     double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
     for (uint32_t t = first; t < end; ++t)
       for (int k = 0; k < 3; ++k)
@@ -2049,12 +2118,78 @@ std::vector<CullCluster> planBruteCull(float const* xs, float const* ys, float c
     double const r = std::sqrt(r2) * (1.0 + 1.0 / 1024) + 1e-6 * (cmax + std::sqrt(r2));
     if (!(r <= kCullMaxRadiusFrac * diag)) continue;
     CullCluster cl{};
-    cl.cx = c[0], cl.cy = c[1], cl.cz = c[2];
-    cl.r2 = std::nextafter(float(r * r), HUGE_VALF);
+    cl.b[0] = c[0], cl.b[1] = c[1], cl.b[2] = c[2];
+    cl.b[3] = std::nextafter(float(r * r), HUGE_VALF);
     cl.first = first, cl.count = count, cl.slot = culled;
     cl.magic = uint32_t(((uint64_t(1) << 32) + count - 1) / count);
     out.push_back(cl);
     if (radii) radii->push_back(float(r));
+    culled += count;
+  }
+  return out;
+}
+// Box clusters: a maximal one-material run of at least kCullBoxMinTris triangles that planBruteCull did not take -- the sphere
+// rule rejects flat meshes such as walls, whose sphere holds most of the scene.  Its bound is its vertex box with every face
+// moved out by m = 2^-19 (extent + |coordinate|_max of the box), then rounded outward to float.  m covers, with a margin of
+// about 8:
+//  * mt_valid's slack: it accepts u, v >= -1e-7 and u + v <= 1 + 1e-7, i.e. points up to 1e-7 (|e0| + |e1|) <= 3.5e-7 extent
+//    outside the triangle;
+//  * e0 / e1 are stored as floats: the tested triangle's vertices are up to 2^-24 |e| <= 1.1e-7 extent off the soup's;
+//  * the rounding of the Moeller-Trumbore arithmetic across the ray: a few ulps of the coordinates, 2^-22 |coordinate|_max.
+// Along the ray the device allows for its own rounding: the segment runs from kCullTLo = (1 - 2^-8) 1e-4 to the end t
+// times kCullTSlack = 1 + 2^-8, and the slab test keeps near <= far * kCullTSlack; every t it or mt_core9 computes is
+// within a few ulps of the exact one (relative), far below 2^-8.  An axis-aligned wall has zero thickness and 2m after
+// inflation; m stays well below kCullTLo, so a ray that leaves a wall at more than ~m / 1e-4 radians to its plane (Cornell:
+// 0.057) is not handed that wall again.
+// A run becomes a cluster when its box (before inflation) has a surface area of at most kCullBoxMaxAreaFrac of the scene
+// box's: a random line that meets the scene box meets a convex body inside it with probability S_body / S_scene (Cauchy),
+// and a compacted test costs about 2.7 packed ones.  Cornell's walls are exactly 1/3.  Clusters are taken in
+// index order while the total stays within kCullMaxClusters clusters and kCullMaxTris triangles (the LDS copy).
+constexpr uint32_t kCullBoxMinTris = 2;  // the task decode needs count >= 2; a lone triangle costs about one bound test anyway
+constexpr double kCullBoxMaxAreaFrac = 0.35;
+std::vector<CullCluster> planBruteCullBox(float const* xs, float const* ys, float const* zs, uint32_t const* mat, uint32_t n,
+                                          std::vector<CullCluster> const& spheres) {
+  std::vector<CullCluster> out;
+  if (n == 0) return out;
+  auto vtx = [&](uint32_t t, int k, int a) { return double((a == 0 ? xs : a == 1 ? ys : zs)[4 * size_t(t) + k]); };
+  auto area = [](double const lo[3], double const hi[3]) {
+    double const x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
+    return 2.0 * (x * y + y * z + z * x);
+  };
+  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  for (uint32_t t = 0; t < n; ++t)
+    for (int k = 0; k < 3; ++k)
+      for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], vtx(t, k, a)), hi[a] = std::fmax(hi[a], vtx(t, k, a));
+  double const sceneArea = area(lo, hi);
+  if (!std::isfinite(sceneArea) || !(sceneArea > 0.0)) return out;
+  uint32_t culled = 0;
+  for (CullCluster const& c : spheres) culled += c.count;
+  size_t const taken = spheres.size();
+  for (uint32_t first = 0, end = 0; first < n && taken + out.size() < kCullMaxClusters; first = end) {
+    for (end = first + 1; end < n && mat[end] == mat[first];) ++end;
+    uint32_t const count = end - first;
+    if (count < kCullBoxMinTris || culled + count > kCullMaxTris) continue;
+    if (std::any_of(spheres.begin(), spheres.end(), [&](CullCluster const& c) { return c.first == first; })) continue;
+    double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (uint32_t t = first; t < end; ++t)
+      for (int k = 0; k < 3; ++k)
+        for (int a = 0; a < 3; ++a) blo[a] = std::fmin(blo[a], vtx(t, k, a)), bhi[a] = std::fmax(bhi[a], vtx(t, k, a));
+    if (!(area(blo, bhi) <= kCullBoxMaxAreaFrac * sceneArea)) continue;
+    double ext = 0.0, cmax = 0.0;
+    for (int a = 0; a < 3; ++a)
+      ext = std::fmax(ext, bhi[a] - blo[a]), cmax = std::fmax(cmax, std::fmax(std::fabs(blo[a]), std::fabs(bhi[a])));
+    double const m = 0x1p-19 * (ext + cmax);
+    CullCluster cl{};
+    for (int a = 0; a < 3; ++a) {
+      float l = float(blo[a] - m), h = float(bhi[a] + m);
+      if (double(l) > blo[a] - m) l = std::nextafter(l, -HUGE_VALF);
+      if (double(h) < bhi[a] + m) h = std::nextafter(h, HUGE_VALF);
+      cl.b[a] = l, cl.b[3 + a] = h;
+    }
+    cl.box = 1;
+    cl.first = first, cl.count = count, cl.slot = culled;
+    cl.magic = uint32_t(((uint64_t(1) << 32) + count - 1) / count);
+    out.push_back(cl);
     culled += count;
   }
   return out;
@@ -2413,7 +2548,10 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
     long long const v = std::atoll(e4);
     if (v >= 4096) ctx->wfTargetPaths = size_t(v);
   }
-  if (char const* e6 = std::getenv("DMT_BRUTE_CULL")) ctx->bruteCull = std::atoi(e6) != 0;  // A/B runs and tests
+  if (char const* e6 = std::getenv("DMT_BRUTE_CULL")) {  // A/B runs and tests
+    int const v = std::atoi(e6);
+    ctx->bruteCull = v == 0 ? 0 : v == 1 ? 1 : 2;
+  }
   if (char const* e2 = std::getenv("DMT_SUB_SHIFT")) {  // scheduling experiments only: results do not depend on it
     int const v = std::atoi(e2);
     ctx->subShift = v < 0 ? -1 : (v > 2 ? 2 : v);
@@ -2470,7 +2608,13 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   DevBuf<TriPost> post;
   HIP_TRY(ctx, tris.assign(a.data(), count));
   HIP_TRY(ctx, post.assign(b.data(), count));
-  std::vector<CullCluster> const clusters = planBruteCull(xs, ys, zs, mat_id, uint32_t(count), ctx->bruteCull, nullptr);
+  // a closest-hit key holds the original index in 26 bits: no culling for larger soups
+  std::vector<CullCluster> clusters =
+      planBruteCull(xs, ys, zs, mat_id, uint32_t(count), ctx->bruteCull >= 1 && count < kCullMaxIndex, nullptr);
+  if (ctx->bruteCull >= 2 && count < kCullMaxIndex) {
+    std::vector<CullCluster> const boxes = planBruteCullBox(xs, ys, zs, mat_id, uint32_t(count), clusters);
+    clusters.insert(clusters.end(), boxes.begin(), boxes.end());
+  }
   DevBuf<TriIsect> cullAlways;
   DevBuf<uint32_t> cullIdx;
   DevBuf<CullCluster> cullClusters;
@@ -2914,6 +3058,17 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   return DMT_OK;
 }
 
+#if DMT_CULL_COUNTS
+extern "C" int dmt_diag_cull_counts(unsigned long long* out16, int reset) {
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_cullCount), 16 * sizeof(unsigned long long));
+  if (e == hipSuccess && reset) {
+    unsigned long long z[16] = {};
+    e = hipMemcpyToSymbol(HIP_SYMBOL(g_cullCount), z, sizeof(z));
+  }
+  return e == hipSuccess ? 0 : -1;
+}
+#endif
 #if DMT_SECTION_TIMING
 extern "C" int dmt_diag_section_cycles(unsigned long long* out16, int reset) {
   hipError_t e = hipDeviceSynchronize();
@@ -2937,8 +3092,25 @@ int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const
   *cluster_count = uint32_t(cl.size());
   for (size_t k = 0; k < cl.size(); ++k) {
     if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
-    if (cluster_sphere) cluster_sphere[4 * k] = cl[k].cx, cluster_sphere[4 * k + 1] = cl[k].cy, cluster_sphere[4 * k + 2] = cl[k].cz,
+    if (cluster_sphere) cluster_sphere[4 * k] = cl[k].b[0], cluster_sphere[4 * k + 1] = cl[k].b[1], cluster_sphere[4 * k + 2] = cl[k].b[2],
                         cluster_sphere[4 * k + 3] = radii[k];
+  }
+  return DMT_OK;
+}
+
+int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                            uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box) {
+  if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
+  std::vector<CullCluster> cl;
+  if (enable && count < kCullMaxIndex) {
+    std::vector<CullCluster> const spheres = planBruteCull(xs, ys, zs, mat_id, uint32_t(count), true, nullptr);
+    cl = planBruteCullBox(xs, ys, zs, mat_id, uint32_t(count), spheres);
+  }
+  *cluster_count = uint32_t(cl.size());
+  for (size_t k = 0; k < cl.size(); ++k) {
+    if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
+    if (cluster_box)
+      for (int a = 0; a < 6; ++a) cluster_box[6 * k + size_t(a)] = cl[k].b[a];
   }
   return DMT_OK;
 }

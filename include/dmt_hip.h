@@ -213,6 +213,13 @@ int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t c
 int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count,
                         int enable, uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_sphere);
 
+/* host-only: the box clusters the brute-force pass adds after those of dmt_brute_cull_plan (flat meshes such as walls).  Up
+ * to 12 minus the sphere clusters: runs of >= 2 consecutive triangles of one material that the sphere rule rejects and
+ * whose box has at most 0.35 of the scene box's surface area.  Cluster k: cluster_first_count[2k], [2k + 1] as above;
+ * cluster_box[6k .. 6k + 5] = inflated box lo xyz, hi xyz.  enable = 0 gives none (DMT_BRUTE_CULL=0 or 1). */
+int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count,
+                            int enable, uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box);
+
 /* ---- device unit-test entry points (GPU twins of the reference's T/tests kernels) ---------- */
 int dmt_test_triangle_intersect(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs,
                                 size_t count, const float* o3, const float* d3, int32_t* hit,
