@@ -13,9 +13,13 @@ The frame is partitioned by interleaved 8x8 tiles (tile j -> rank j mod N), tota
 "scaling": "strong".  Scene and film are resident in HBM before the timed region.
 
 PyTorch is plumbing here (device buffers for the film, streams, torch.distributed); every sample is
-traced by csrc/libdmt_hip.so through the C ABI.  The CPU oracle is used ONLY in the cpu_baseline
-leg (rank 0, N == 1), where it is the thing timed on the host cores and, as a by-product, supplies
-the per-sample work counters for the flop / byte models and a band to check the GPU film against.
+traced by csrc/libdmt_hip.so through the C ABI.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, a check of the
+film's sample counts, and the JSON line (its `roofline` from committed counters and the live kernel time, no run of its
+own).  `--full` adds what takes runs of its own: the cpu_baseline leg (rank 0, N == 1), where the CPU oracle is the thing
+timed on the host cores and, as a by-product, supplies the per-sample work counters for the flop / byte models and a band
+to check the GPU film against; the counting pass of the BVH workloads; and the `secondary` record below.
 
 Roofline record (`roofline`): the bound that limits each workload's kernel, as a fraction <= 1.
   * Cornell workloads (26 triangles, k_megakernel): the scene lives in SGPRs / the scalar cache and the only compulsory
@@ -37,8 +41,8 @@ FLOP model, stated both ways: `frac` counts 60 flop per triangle test (SURVEY 8d
 + 620 per bounce, where the 620 is a FILLER backed out of the authors' own nvprof total (17.9 kFLOP per sample on the same
 scene at 250.7 tests and 4.65 bounces per sample, docs/dmt-mk_roofline_point.txt:2-6), i.e. shading + sampler flops this
 build did not count itself; `frac_tests_only` counts the triangle tests and node visits alone.
-A `secondary` array (N = 1, default workload only) carries BASELINE config 4 (1 M random triangles, BVH kernel) timed
-for the same --steps / --warmup after the headline's timed region, so that the driver's record holds a number for it as well.
+A `secondary` array (--full, N = 1, default workload only) carries BASELINE config 4 (1 M random triangles, BVH kernel)
+timed for the same --steps / --warmup after the headline's timed region, so that the record holds a number for it as well.
 `--dump-outputs DIR` writes the headline's film after its last timed step (dump_outputs below), so that two builds can be
 compared output for output: scene, camera and sample sequence depend on the arguments alone.
 """
@@ -90,7 +94,7 @@ C1_WORKLOAD = "cornell_512x512_64spp_4bounces"
 
 # Per-sample work counters of the Cornell workloads, counted by the CPU restatement on rows spread evenly over
 # the frame (same procedure as the cpu_baseline leg below, which recounts them live when it runs).
-# Used for the flop / byte models when the cpu_baseline leg is skipped (N > 1, --no-cpu-baseline).
+# Used for the flop / byte models when the cpu_baseline leg is skipped (no --full, N > 1, --no-cpu-baseline).
 WORKLOAD_STATS = {
     "cornell_1024x1024_1024spp_8bounces": {"samples": 1.0, "closest_rays": 3.6101, "shadow_rays": 3.1595,
                                            "tri_tests": 173.8335, "bounces": 3.1595, "hits": 3.1595},
@@ -352,28 +356,37 @@ def run_secondary(pkg, dev_index, stream_ptr, steps, warmup):
             "roofline": roofline, "fold_handover": sched}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
     ap.add_argument("--kspp", type=int, default=0, help="samples per pixel per kernel launch (0 = all spp in one launch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the BASELINE config 4 record appended to the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline with its parity band "
+                         "against the CPU oracle (N = 1), the BVH workloads' counting pass, and the `secondary` BASELINE config 4 "
+                         "record (N = 1, default workload)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity band")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the BASELINE config 4 record of the default workload")
     ap.add_argument("--cornell-bvh", action="store_true",
                     help="experiment (VERDICT r2 item 9): run a Cornell workload through the BVH kernel instead of the brute-force loop "
                          "(films are bit-identical); the roofline record then still describes the brute-force model")
-    ap.add_argument("--cpu-band-rows", type=int, default=16)
+    ap.add_argument("--cpu-band-rows", type=int, default=16, help="with --full: rows of the CPU oracle's parity band")
     ap.add_argument("--parity-rows", type=int, default=0,
-                    help="Cornell workloads without the cpu_baseline leg (N > 1, --no-cpu-baseline): check this many rows of the combined film "
-                         "against the CPU oracle on rank 0 (untimed)")
+                    help="Cornell workloads without the cpu_baseline leg (no --full, N > 1, --no-cpu-baseline): check this many rows of the "
+                         "combined film against the CPU oracle on rank 0 (untimed)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the film of the last timed step (rank 0) as DIR/mean.npy and DIR/m2.npy, float32, at most 64 MB "
                          "in all (a larger film: a fixed, seeded sample of pixels plus DIR/pixel_index.npy)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     import numpy as np
     import torch
@@ -493,7 +506,7 @@ def main():
         cpu_baseline = None
         parity = None
         stats = None
-        if use_bvh:
+        if use_bvh and args.full:
             # BVH path: node visits / triangle tests come from the counting build of the same kernel
             # (1 spp over the whole frame; the film is rebuilt by nothing afterwards -- timing is done)
             r.set_partition(0, 1)
@@ -531,7 +544,7 @@ def main():
                 if ospp == spp:
                     d = film_mean[y:y + nrows, x0:x0 + npx, :3].astype(np.float64) - omean[y:y + nrows, x0:x0 + npx, :3]
                     parity = {"rmse_vs_cpu_rows": float(np.sqrt((d ** 2).mean(axis=2)).mean()), "tolerance": 1e-3}
-        elif not args.no_cpu_baseline and world == 1:
+        elif not use_bvh and args.full and not args.no_cpu_baseline and world == 1:
             O = graft.load_oracle()          # cpu_baseline leg: the oracle is the thing timed
             # the 1-GPU box exposes 256 logical CPUs but the job's CPU share is 16 cores
             threads = int(os.environ.get("DMT_CPU_THREADS", min(os.cpu_count() or 1, 16)))
@@ -550,8 +563,8 @@ def main():
             }
             # (2) untimed: rows of THIS workload's frame -> work counters for the models + a parity band for the GPU film
             parity, stats = oracle_band(O, width, height, spp, max_depth, args.cpu_band_rows, threads, film_mean)
-        elif args.parity_rows > 0:
-            # no cpu_baseline leg (N > 1 or --no-cpu-baseline), but the combined film is still checked against the CPU oracle on a few rows
+        elif not use_bvh and args.parity_rows > 0:
+            # no cpu_baseline leg (no --full, N > 1 or --no-cpu-baseline), but the combined film is still checked against the CPU oracle on a few rows
             O = graft.load_oracle()
             threads = int(os.environ.get("DMT_CPU_THREADS", min(os.cpu_count() or 1, 16)))
             parity, stats = oracle_band(O, width, height, spp, max_depth, args.parity_rows, threads, film_mean)
@@ -564,7 +577,7 @@ def main():
             roofline["launches"] = int(launches)
 
         secondary = None
-        if world == 1 and args.workload == DEFAULT_WORKLOAD and not args.no_secondary:
+        if args.full and world == 1 and args.workload == DEFAULT_WORKLOAD and not args.no_secondary:
             try:
                 secondary = [run_secondary(pkg, dev_index, stream.cuda_stream, args.steps, args.warmup)]
             except Exception as e:   # the headline line is printed regardless; the failure is part of the record
@@ -594,6 +607,7 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu_baseline, "parity": parity,
             "per_rank": per_rank,
             "secondary": secondary,
+            "full": args.full,       # cpu_baseline, the BVH counting pass and secondary run only with --full
             "fold_handover": sched,   # in-launch ordered fold without waiting: chunks handed to another wave, stalls, early exits
         }
         print(json.dumps(out), flush=True)

@@ -165,3 +165,12 @@ def test_bench_rejects_a_step_count_below_one():
     assert p.returncode == 2 and "--steps" in p.stderr
     src = (ROOT / "bench.py").read_text()
     assert "for i in range(args.steps):" in src and "--dump-outputs" in src
+
+
+def test_full_is_opt_in():
+    """A plain `--gpus 1 --steps K --warmup W` run measures the headline alone; the CPU baseline, the BVH counting pass
+    and the `secondary` record need --full."""
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 5, 2)
+    assert b.parse_args(["--full"]).full is True

@@ -7,7 +7,7 @@ out=gpurun_out/profiles_$tag
 mkdir -p "$out"
 for w in "$@"; do
   echo "== $w $(date +%T)" >> "$out/progress.log"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_$w" -- python3 bench.py --steps 3 --warmup 1 --workload "$w" > "$out/bench_under_rocprof_$w.log" 2>&1 || echo "trace $w failed" >> "$out/progress.log"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_$w" -- python3 bench.py --full --steps 3 --warmup 1 --workload "$w" > "$out/bench_under_rocprof_$w.log" 2>&1 || echo "trace $w failed" >> "$out/progress.log"
   f=$(find "$out/trace_$w" -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp "$f" "$out/kernel_stats_$w.csv"
   grep '^{' "$out/bench_under_rocprof_$w.log" > "$out/bench_under_rocprof_$w.json"
