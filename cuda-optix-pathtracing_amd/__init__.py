@@ -15,6 +15,11 @@ from .binding import (  # noqa: F401
     light_tree_pmfs,
     light_tree_ref_select,
     envmap_tables,
+    texture_mip_chain,
+    texture_footprint,
+    mip_level_count,
+    TEXFILTER_LEVEL0,
+    TEXFILTER_REFERENCE,
     build_library,
     library_path,
     load_library,

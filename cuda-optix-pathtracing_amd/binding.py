@@ -57,7 +57,53 @@ EXPORTED_SYMBOLS = [
     "dmt_render", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_test_triangle_intersect",
     "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_light", "dmt_test_half",
     "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
+    "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
 ]
+
+# dmt_set_texture_filter modes (include/dmt_hip.h)
+TEXFILTER_LEVEL0 = 0
+TEXFILTER_REFERENCE = 1
+
+
+def mip_level_count(width, height):
+    """The reference's MIP level count: halve both sides until both reach 0 (core-texture.cu:360-366)."""
+    n, w, h = 0, int(width), int(height)
+    while w > 0 or h > 0:
+        n, w, h = n + 1, w >> 1, h >> 1
+    return n
+
+
+def texture_mip_chain(rgba8):
+    """Host only: MIP levels 1.. of one texture (h x w x 4 uint8) as dmt_upload_textures builds them.  Returns
+    (levels, [level 1 array, level 2 array, ...]), each level (max(1, h >> l), max(1, w >> l), 4) uint8."""
+    lib = load_library()
+    img = np.ascontiguousarray(rgba8, np.uint8)
+    h, w = img.shape[:2]
+    levels = mip_level_count(w, h)
+    sizes = [(max(1, h >> l), max(1, w >> l)) for l in range(1, levels)]
+    total = sum(a * b for a, b in sizes)
+    out = np.zeros(max(total, 1) * 4, np.uint8)
+    n = C.c_int()
+    rc = lib.dmt_texture_mip_chain(_p(img), int(w), int(h), _p(out), C.c_uint64(total), C.byref(n))
+    if rc != 0:
+        raise DmtError(f"dmt_texture_mip_chain failed ({rc})")
+    chain, off = [], 0
+    for a, b in sizes:
+        chain.append(out[4 * off:4 * (off + a * b)].reshape(a, b, 4))
+        off += a * b
+    return n.value, chain
+
+
+def texture_footprint(camera44):
+    """Host only: the camera's footprint for the first-hit texture filter -- dict(cfr = camera-from-render 3x4, min_dx,
+    min_dy, spp_scale)."""
+    lib = load_library()
+    cam = np.ascontiguousarray(camera44, np.uint8).reshape(44)
+    out = np.zeros(19, np.float32)
+    rc = lib.dmt_texture_footprint(_p(cam), _p(out))
+    if rc != 0:
+        raise DmtError(f"dmt_texture_footprint failed ({rc})")
+    return dict(cfr=out[:12].reshape(3, 4).copy(), min_dx=out[12:15].copy(), min_dy=out[15:18].copy(), spp_scale=np.float32(out[18]))
 
 
 def _p(a):
@@ -285,6 +331,10 @@ class Renderer:
         """0 = uniform pick (reference, parity mode), 1 = light tree (csrc/light_tree.hpp)."""
         self._check(self._lib.dmt_set_light_sampling(self._ctx, int(mode)), "dmt_set_light_sampling")
 
+    def set_texture_filter(self, mode):
+        """TEXFILTER_LEVEL0 (default: level-0 bilinear lookups) or TEXFILTER_REFERENCE (first-hit MIP / EWA filtering)."""
+        self._check(self._lib.dmt_set_texture_filter(self._ctx, int(mode)), "dmt_set_texture_filter")
+
     def set_bvh_strategy(self, strategy, paths_per_pass=0):
         """0 = automatic, 1 = megakernel, 2 = device-side wavefront (films are bit-identical)."""
         self._check(self._lib.dmt_set_bvh_strategy(self._ctx, int(strategy), C.c_uint64(int(paths_per_pass))), "dmt_set_bvh_strategy")
@@ -441,6 +491,22 @@ class Renderer:
         self._check(self._lib.dmt_test_trace_samples(self._ctx, n, _p(pxs), _p(pys), _p(ss), _p(out)),
                     "dmt_test_trace_samples")
         return out
+
+    def test_texture_filter(self, tri, bu, bv, tex, depth=0):
+        """Filtered lookups of texture `tex` at (tri, bu, bv) by the filtering kernels' device code, as at a hit of depth
+        `depth` (0 = the camera ray's).  Returns (rgb (n, 3), branch (n,), lod (n,))."""
+        tri, tex = _i32(tri), _i32(tex)
+        bu, bv = _f32(bu), _f32(bv)
+        n = tri.shape[0]
+        tex = np.ascontiguousarray(np.broadcast_to(tex, (n,)), np.int32)
+        depth = np.ascontiguousarray(np.broadcast_to(_i32(depth), (n,)), np.int32)
+        assert bu.shape[0] == n and bv.shape[0] == n
+        rgb = np.zeros((n, 3), np.float32)
+        branch = np.zeros(n, np.int32)
+        lod = np.zeros(n, np.float32)
+        self._check(self._lib.dmt_test_texture_filter(self._ctx, n, _p(tri), _p(bu), _p(bv), _p(tex), _p(depth), _p(rgb),
+                                                      _p(branch), _p(lod)), "dmt_test_texture_filter")
+        return rgb, branch, lod
 
     def test_trace_log(self, px, py, s, cap=64):
         rec = np.zeros((cap, 12), np.float32)

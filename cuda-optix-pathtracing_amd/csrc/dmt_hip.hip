@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <new>
 #include <string>
@@ -105,6 +106,13 @@ struct RenderParams {
   LightTreeNode const* lightTree;  // light BVH over `lights` (light_tree.hpp); read by the *_ltree kernels only
   LightTreeRefNode const* lightTreeRef;  // the reference-semantics tree (light_tree_ref.hpp); read by the *_ltree2 kernels only
   unsigned long long* stats;  // stats build only: samples, closest rays, shadow rays, node visits, triangle tests, bounces
+  // first-hit texture filtering (DMT_TEXFILTER_REFERENCE); read by the *_texf kernels only.  Camera footprint as
+  // dmt_texture_footprint returns it, and the MIP levels above 0 of every texture (layout: buildMipChain)
+  float texCfr[12];           // camera-from-render, row-major 3x4
+  float texMinDx[3], texMinDy[3];  // smallest direction differentials, in the frame of the camera ray
+  float texSppScale;          // max(1/8, 1/sqrt(frame spp))
+  uint32_t const* texMip;     // RGBA8 texels of levels 1.. of every texture, back to back
+  int32_t const* texMipDesc;  // [texture] {levels, first texel of level 1 in texMip}
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -315,9 +323,325 @@ DMT_DEV f3 tex_bilinear(KArgs k, int32_t tex, float s, float t, bool isNormal) {
   if (isNormal) c.x = c.x * 2.f - 1.f, c.y = c.y * 2.f - 1.f;
   return c;
 }
+// ---- first-hit texture filtering (DMT_TEXFILTER_REFERENCE, *_texf kernels).  The reference's CPU renderer
+// filters every image-texture lookup at the camera ray's first hit by the pixel's footprint and looks up MIP level 0 at
+// every later hit (core-render.cpp:264-268).  Restated here, with the reference's lines:
+//   footprint   approximate_dp_dxy (core-texture.cu:55-87) with the frame's smallest camera differentials
+//               (minDifferentialsFromCamera, core-render.cpp:928-980; host side, dmt_texture_footprint);
+//               dpdu / dpdv (core-render.cpp:209-226); duv_From_dp_dxy, the #else branch (core-texture.cu:123-258);
+//               zeroed when |cross(dpdx, dpdy)| < 1e-6 (core-render.cpp:264-268)
+//   lookup      sampleMippedTexture (core-material.cpp:83-175): isotropic trilinear when no derivative is near zero (the
+//               condition the reference names validDiffs, inverted, kept as written), else two EWA lookups (EWAFormula,
+//               core-texture.cu:664-748) at the level of the UNclamped minor axis (computeTextureLOD_from_dudv, :595-662)
+// Where the reference is undefined:
+//   [fix 1] levels where one axis has reached 0 get resolution max(1, ...) (buildMipChain);
+//   [fix 2] the second lookup of a pair past the last level reads the last level;
+//   [fix 3] EWA with a zero-length shorter axis takes the isotropic branch (the clamp would compute 0 * inf);
+//   [fix 4] an EWA lookup tests at most kEwaMaxTexels texel positions: while the ellipse's box at the reference's level
+//           holds more, the level is raised (each level quarters the box); a box still too large at the last level, or
+//           at the second level of the pair, takes the single-texel fallback of EWAFormula;
+//   [fix 5] a triangle whose UV determinant is exactly 0 gets zero differentials.
+// With zero differentials the lookup is tex_bilinear itself: the reference's lerp returns its first argument at t <= 0.
+// The differentials and the EWA level are evaluated in double (see tex_footprint, ewa_lod_minor); the lookups in float.
+#include "../../include/dmt_ewa_lut.inc"
+__constant__ float kEwaLut[DMT_EWA_LUT_SIZE] = {DMT_EWA_LUT_VALUES};
+constexpr float kEwaMaxTexels = 1024.f;  // [fix 4] texel positions per EWA lookup
+constexpr float kMaxAnisotropy = 8.f;    // core-texture.h:210
+
+struct TexDiff {  // d(u, v) / d(x, y) of the hit; all zero: the level-0 bilinear lookup
+  float dudx, dudy, dvdx, dvdy;
+};
+struct TexProbe {  // what dmt_test_texture_filter reports: 0 level 0, 1 trilinear, 2 EWA, 3 EWA at a level raised by [fix 4]
+  int branch;
+  float lod;
+};
+struct TexLevel {
+  uint32_t const* rgba;
+  int32_t first, w, h;
+};
+DMT_DEV TexLevel tex_level(KArgs k, int32_t tex, int l) {
+  KArgs const ka = kargs(k);
+  int32_t const* const d = ka->texDesc + 3 * tex;
+  TexLevel L;
+  L.w = d[1], L.h = d[2];
+  if (l == 0) {
+    L.rgba = ka->texRgba, L.first = d[0];
+    return L;
+  }
+  int32_t first = ka->texMipDesc[2 * tex + 1];
+  for (int i = 1; i < l; ++i) first += max(1, L.w >> i) * max(1, L.h >> i);
+  L.rgba = ka->texMip, L.first = first, L.w = max(1, L.w >> l), L.h = max(1, L.h >> l);
+  return L;
+}
+DMT_DEV f3 lerp_rgb(f3 a, f3 b, float t) { return t <= 0.f ? a : (t >= 1.f ? b : (1.f - t) * a + t * b); }  // cudautils-color.cuh:112-114
+// sampleBilinearTexel (core-material.cpp:20-56) on one level
+DMT_DEV f3 tex_bilinear_level(TexLevel const& L, float s, float t, bool isNormal) {
+  float const x = s * float(L.w) - 0.5f, y = t * float(L.h) - 0.5f;
+  float const fx = floorf(x), fy = floorf(y);
+  int const x0 = int(fx), y0 = int(fy);
+  float const tx = x - fx, ty = y - fy;
+  f3 const c00 = tex_texel(L.rgba, L.first, L.w, L.h, x0, y0), c10 = tex_texel(L.rgba, L.first, L.w, L.h, x0 + 1, y0);
+  f3 const c01 = tex_texel(L.rgba, L.first, L.w, L.h, x0, y0 + 1), c11 = tex_texel(L.rgba, L.first, L.w, L.h, x0 + 1, y0 + 1);
+  f3 c = lerp_rgb(lerp_rgb(c00, c10, tx), lerp_rgb(c01, c11, tx), ty);
+  if (isNormal) c.x = c.x * 2.f - 1.f, c.y = c.y * 2.f - 1.f;
+  return c;
+}
+// EWAFormula's ellipse and box at one level (core-texture.cu:664-712)
+struct EwaBox {
+  float A, B, C;
+  int sx, sy;
+  float s0, s1, t0, t1;
+  float count;  // texel positions in the box (the loop never runs when it exceeds kEwaMaxTexels or is not a number)
+};
+DMT_DEV EwaBox ewa_box(int w, int h, float s, float t, f2 d0, f2 d1) {
+#pragma clang fp contract(off)
+  EwaBox b;
+  float const d0x = d0.x * float(w), d0y = d0.y * float(h), d1x = d1.x * float(w), d1y = d1.y * float(h);
+  b.sx = int(s * float(w) - 0.5f), b.sy = int(t * float(h) - 0.5f);  // truncated, not floored (as written)
+  float A = d0y * d0y + d1y * d1y + 1.f;
+  float B = -2.f * (d0x * d0y + d1x * d1y);
+  float C = d0x * d0x + d1x * d1x + 1.f;
+  float const invF = 1.f / (A * C - 0.25f * B * B);
+  A *= invF, B *= invF, C *= invF;
+  float const invDet = 1.f / (A * C - 0.25f * B * B);
+  float const uR = safe_sqrt(C * invDet), vR = safe_sqrt(A * invDet);
+  b.A = A, b.B = B, b.C = C;
+  b.s0 = ceilf(float(b.sx) - uR), b.s1 = floorf(float(b.sx) + uR);
+  b.t0 = ceilf(float(b.sy) - vR), b.t1 = floorf(float(b.sy) + vR);
+  b.count = (b.s1 - b.s0 + 1.f) * (b.t1 - b.t0 + 1.f);
+  return b;
+}
+DMT_DEV f3 ewa_texel(TexLevel const& L, int s, int t, bool isNormal) {
+  f3 c = tex_texel(L.rgba, L.first, L.w, L.h, s, t);
+  if (isNormal) c.x = c.x * 2.f - 1.f, c.y = c.y * 2.f - 1.f;  // remapNormal per texel (core-texture.h:233-240)
+  return c;
+}
+DMT_DEV f3 ewa_lookup(TexLevel const& L, float s, float t, f2 d0, f2 d1, bool isNormal) {
+#pragma clang fp contract(off)
+  EwaBox const b = ewa_box(L.w, L.h, s, t, d0, d1);
+  f3 sum = mk3(0.f, 0.f, 0.f);
+  float sumW = 0.f;
+  if (b.count <= kEwaMaxTexels) {  // [fix 4]; false for NaN
+    int const s0 = int(b.s0), s1 = int(b.s1), t0 = int(b.t0), t1 = int(b.t1);
+    for (int ti = t0; ti <= t1; ++ti) {
+      float const tt = float(ti) - float(b.sy);
+      for (int si = s0; si <= s1; ++si) {
+        float const ss = float(si) - float(b.sx);
+        float const r2 = b.A * ss * ss + b.B * ss * tt + b.C * tt * tt;
+        if (r2 < 1.f) {
+          float const w = kEwaLut[int(fminf(r2 * float(DMT_EWA_LUT_SIZE), float(DMT_EWA_LUT_SIZE - 1)))];
+          sum = sum + ewa_texel(L, si, ti, isNormal) * w;
+          sumW += w;
+        }
+      }
+    }
+  }
+  if (!(sumW > 0.f)) return ewa_texel(L, b.sx, b.sy, isNormal);  // floor(sx + 0.5) of an int
+  return mk3(sum.x / sumW, sum.y / sumW, sum.z / sumW);
+}
+// computeTextureLOD_from_dudv's lod_minor (core-texture.cu:595-662), in double: the smaller eigenvalue is a difference of
+// two nearly equal numbers when the footprint is long and thin, where float would leave little of it
+DMT_DEV float ewa_lod_minor(TexDiff const& d, int w, int h) {
+  double const a0 = double(d.dudx) * w, a1 = double(d.dvdx) * h, b0 = double(d.dudy) * w, b1 = double(d.dvdy) * h;
+  double const E = a0 * a0 + a1 * a1, F = b0 * b0 + b1 * b1, G = a0 * b0 + a1 * b1;
+  double const eps = 1e-12;
+  double const trace = E + F;
+  double det = E * F - G * G;
+  if (det < 0.0 && det > -eps) det = 0.0;
+  if (trace <= eps) return 0.f;
+  double discr = trace * trace - 4.0 * det;
+  if (discr < 0.0) discr = 0.0;
+  double l2 = 0.5 * (trace - sqrt(discr));
+  if (l2 < 0.0 && l2 > -eps) l2 = 0.0;
+  double const sigma = l2 > 0.0 ? sqrt(l2) : 0.0;
+  return sigma > 0.0 ? float(fmax(0.0, log2(sigma))) : 0.f;
+}
+// sampleMippedTexture (core-material.cpp:83-175) with [fix 2-4]
+template <bool PROBE>
+DMT_DEV f3 tex_filtered(KArgs k, int32_t tex, float s, float t, bool isNormal, TexDiff const& d, TexProbe* pr) {
+#pragma clang fp contract(off)
+  if (d.dudx == 0.f && d.dudy == 0.f && d.dvdx == 0.f && d.dvdy == 0.f) {
+    if constexpr (PROBE) pr->branch = 0, pr->lod = 0.f;
+    return tex_bilinear(k, tex, s, t, isNormal);
+  }
+  KArgs const ka = kargs(k);
+  int32_t const* const desc = ka->texDesc + 3 * tex;
+  int const w = desc[1], h = desc[2];
+  int const levels = ka->texMipDesc[2 * tex];
+  f2 const dx = mk2(d.dudx, d.dvdx), dy = mk2(d.dudy, d.dvdy);
+  bool const dxLonger = dot(dx, dx) > dot(dy, dy);
+  f2 const d0 = dxLonger ? dx : dy;
+  f2 d1 = dxLonger ? dy : dx;
+  float const shorterLen = sqrtf(dot(d1, d1)), longerLen = sqrtf(dot(d0, d0));
+  auto nearZero = [](float x) { return fabsf(x) < __FLT_EPSILON__; };
+  bool const someNearZero = nearZero(d.dudx) || nearZero(d.dudy) || nearZero(d.dvdx) || nearZero(d.dvdy);
+  if (!someNearZero || shorterLen == 0.f) {  // isotropic trilinear ([fix 3]: also for a zero-length shorter axis)
+    float const dud = fmaxf(fabsf(d.dudx), fabsf(d.dudy)), dvd = fmaxf(fabsf(d.dvdx), fabsf(d.dvdy));
+    float const rho = fmaxf(dud * float(w), dvd * float(h));
+    float const lod = fmaxf(log2f(fmaxf(rho, 1e-8f)), 0.f);
+    int const ilod = min(max(int(floorf(lod)), 0), levels - 1);
+    float const tl = lod - float(ilod);
+    if constexpr (PROBE) pr->branch = 1, pr->lod = lod;
+    f3 const c0 = tex_bilinear_level(tex_level(k, tex, ilod), s, t, isNormal);
+    f3 const c1 = tex_bilinear_level(tex_level(k, tex, min(ilod + 1, levels - 1)), s, t, isNormal);  // [fix 2]
+    return lerp_rgb(c0, c1, tl);
+  }
+  if (float const den = shorterLen * kMaxAnisotropy; den < longerLen) {
+    float const scale = longerLen / den;
+    d1.x *= scale, d1.y *= scale;
+  }
+  float const lambda = ewa_lod_minor(d, w, h);
+  int ilod = min(max(int(floorf(lambda)), 0), levels - 1);
+  float const tl = lambda - float(ilod);
+  TexLevel L0 = tex_level(k, tex, ilod);
+  bool raised = false;
+  while (ilod < levels - 1 && !(ewa_box(L0.w, L0.h, s, t, d0, d1).count <= kEwaMaxTexels)) {  // [fix 4]
+    ++ilod, raised = true;
+    L0 = tex_level(k, tex, ilod);
+  }
+  if constexpr (PROBE) pr->branch = raised ? 3 : 2, pr->lod = float(ilod) + tl;
+  f3 const c0 = ewa_lookup(L0, s, t, d0, d1, isNormal);
+  f3 const c1 = ewa_lookup(tex_level(k, tex, min(ilod + 1, levels - 1)), s, t, d0, d1, isNormal);  // [fix 2]
+  return lerp_rgb(c0, c1, tl);
+}
+// one texture lookup of a material: level-0 bilinear, or (FILT) filtered by the hit's UV differentials
+template <bool FILT>
+DMT_DEV f3 tex_lookup(KArgs k, int32_t tex, float s, float t, bool isNormal, TexDiff const& d) {
+  if constexpr (FILT) return tex_filtered<false>(k, tex, s, t, isNormal, d, nullptr);
+  else return tex_bilinear(k, tex, s, t, isNormal);
+}
+// The footprint of one hit, evaluated in double (once per camera-ray hit; the result is rounded to float): a derivative that
+// should vanish -- a UV axis orthogonal to dpdx or dpdy -- then stays far below the FLT_EPSILON test that picks the EWA branch.
+struct d3 {
+  double x, y, z;
+};
+DMT_DEV d3 md3(double x, double y, double z) { return d3{x, y, z}; }
+DMT_DEV d3 operator+(d3 a, d3 b) { return md3(a.x + b.x, a.y + b.y, a.z + b.z); }
+DMT_DEV d3 operator-(d3 a, d3 b) { return md3(a.x - b.x, a.y - b.y, a.z - b.z); }
+DMT_DEV d3 operator*(d3 a, double s) { return md3(a.x * s, a.y * s, a.z * s); }
+DMT_DEV double dotd(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+DMT_DEV d3 crossd(d3 a, d3 b) { return md3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+DMT_DEV double lend(d3 a) { return sqrt(dotd(a, a)); }
+DMT_DEV d3 normd(d3 a) {
+  double const l = lend(a);
+  return md3(a.x / l, a.y / l, a.z / l);
+}
+DMT_DEV d3 mul3(double const m[9], d3 v) {  // column-major
+  return md3(m[0] * v.x + m[3] * v.y + m[6] * v.z, m[1] * v.x + m[4] * v.y + m[7] * v.z, m[2] * v.x + m[5] * v.y + m[8] * v.z);
+}
+DMT_DEV d3 mul3T(double const m[9], d3 v) {  // transpose(m) v
+  return md3(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z, m[6] * v.x + m[7] * v.y + m[8] * v.z);
+}
+DMT_DEV void inv3(double const m[9], double r[9]) {  // Transform's mInv = inverse(m)
+  double const c0 = m[4] * m[8] - m[7] * m[5], c1 = m[7] * m[2] - m[1] * m[8], c2 = m[1] * m[5] - m[4] * m[2];
+  double const inv = 1.0 / (m[0] * c0 + m[3] * c1 + m[6] * c2);
+  r[0] = c0 * inv, r[1] = c1 * inv, r[2] = c2 * inv;
+  r[3] = (m[6] * m[5] - m[3] * m[8]) * inv, r[4] = (m[0] * m[8] - m[6] * m[2]) * inv, r[5] = (m[3] * m[2] - m[0] * m[5]) * inv;
+  r[6] = (m[3] * m[7] - m[6] * m[4]) * inv, r[7] = (m[6] * m[1] - m[0] * m[7]) * inv, r[8] = (m[0] * m[4] - m[3] * m[1]) * inv;
+}
+// the UV differentials of a camera ray's hit at p on triangle `tri` with geometric normal ng (any orientation)
+DMT_DEV TexDiff tex_footprint(KArgs k, int tri, f3 pf, f3 ngf) {
+#pragma clang fp contract(off)
+  KArgs const ka = kargs(k);
+  TexDiff r{0.f, 0.f, 0.f, 0.f};
+  // approximate_dp_dxy (core-texture.cu:55-87): tangent plane in camera space, rotated so that the hit lies down +z
+  auto const& c = ka->texCfr;
+  d3 const p = md3(pf.x, pf.y, pf.z), ng = md3(ngf.x, ngf.y, ngf.z);
+  d3 const pC = md3(c[0] * p.x + c[1] * p.y + c[2] * p.z + c[3], c[4] * p.x + c[5] * p.y + c[6] * p.z + c[7],
+                    c[8] * p.x + c[9] * p.y + c[10] * p.z + c[11]);
+  double rfc[9];  // cameraFromRender's inverse: the renderFromCamera rotation
+  for (int i = 0; i < 3; ++i) rfc[i] = ka->cam.rfc[i], rfc[3 + i] = ka->cam.rfc[4 + i], rfc[6 + i] = ka->cam.rfc[8 + i];
+  d3 const from = normd(pC);
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // Transform::rotateFromTo(from, +z), cudautils-transform.cu:87-147
+  double const cosT = from.z;
+  if (cosT > 1.0 - 1e-6) {
+    // case 1: already aligned
+  } else if (cosT < -1.0 + 1e-6) {  // case 2: opposite (its literal is read column by column, as Matrix4f stores it)
+    d3 o = md3(1, 0, 0);
+    if (fabs(dotd(from, o)) > 0.99) o = md3(0, 1, 0);
+    d3 const a = normd(crossd(from, o));
+    double const x = a.x, y = a.y, z = a.z, cc = -1.0, tt = 1.0 - cc;
+    double const lit[9] = {tt * x * x + cc, tt * x * y - z, tt * z * x + y, tt * x * y + z, tt * y * y + cc, tt * y * z - x,
+                           tt * z * x - y, tt * y * z + x, tt * z * z + cc};
+    for (int i = 0; i < 9; ++i) R[i] = lit[i];
+  } else {  // Rodrigues: I + [v]x + [v]x^2 (1 - c) / s^2, v = from x z
+    double const x = from.y, y = -from.x, z = 0.0;
+    double const s = sqrt(x * x + y * y + z * z);
+    double const kk = (1.0 - cosT) / (s * s);
+    double const vx[9] = {0, -z, y, z, 0, -x, -y, x, 0};
+    double const vx2[9] = {-y * y - z * z, x * y, x * z, x * y, -x * x - z * z, y * z, x * z, y * z, -x * x - y * y};
+    int const at[9] = {0, 3, 6, 1, 4, 7, 2, 5, 8};  // row-major entry i -> column-major slot
+    for (int i = 0; i < 9; ++i) R[at[i]] += vx[i] + vx2[i] * kk;
+  }
+  double Ri[9];
+  inv3(R, Ri);
+  d3 const pD = mul3(R, pC);
+  d3 const nD = mul3T(Ri, mul3T(rfc, ng));  // normals: transpose of the inverse
+  double const dd = nD.z * pD.z;
+  d3 const xd = normd(md3(ka->texMinDx[0], ka->texMinDx[1], 1.0 + double(ka->texMinDx[2])));
+  d3 const yd = normd(md3(ka->texMinDy[0], ka->texMinDy[1], 1.0 + double(ka->texMinDy[2])));
+  double const tx = -(0.0 - dd) / dotd(nD, xd), ty = -(0.0 - dd) / dotd(nD, yd);  // the origin differentials are 0 (pinhole)
+  double const sc = ka->texSppScale;
+  d3 const dpdx = mul3(rfc, mul3(Ri, xd * tx - pD)) * sc, dpdy = mul3(rfc, mul3(Ri, yd * ty - pD)) * sc;
+  if (!(lend(crossd(dpdx, dpdy)) >= 1e-6)) return r;  // core-render.cpp:264-268
+  // dpdu / dpdv (core-render.cpp:209-226)
+  TriPost const P = load_scene(k).post[tri];
+  float const* const uv = ka->triUv + 6 * size_t(tri);
+  d3 const p0 = md3(P.p0x, P.p0y, P.p0z), dp1 = md3(P.p1x, P.p1y, P.p1z) - p0, dp2 = md3(P.p2x, P.p2y, P.p2z) - p0;
+  double const du1 = double(uv[2]) - uv[0], dv1 = double(uv[3]) - uv[1], du2 = double(uv[4]) - uv[0], dv2 = double(uv[5]) - uv[1];
+  double const detUv = du1 * dv2 - dv1 * du2;
+  if (detUv == 0.0) return r;  // [fix 5]
+  double const invUv = 1.0 / detUv;
+  d3 const dpdu = (dp1 * dv2 - dp2 * dv1) * invUv, dpdv = (dp2 * du1 - dp1 * du2) * invUv;
+  // duv_From_dp_dxy (core-texture.cu:123-258, the #else branch)
+  d3 rdpdy = dpdy;
+  if (lend(dpdx - dpdy) < 1e-12 * fmax(1.0, lend(dpdx))) {
+    d3 n = crossd(dpdu, dpdv);
+    double nl = lend(n);
+    if (nl < 1e-12) {
+      n = crossd(dpdu, dpdx), nl = lend(n);
+      if (nl < 1e-12) n = crossd(dpdv, dpdx), nl = lend(n);
+    }
+    if (nl < 1e-12) n = md3(0, 0, 1);
+    rdpdy = dpdy + normd(n) * (1e-6 * fmax(1.0, lend(dpdx)));
+  }
+  double const a00 = dotd(dpdu, dpdu), a01 = dotd(dpdu, dpdv), a11 = dotd(dpdv, dpdv);
+  double const b0x = dotd(dpdu, dpdx), b1x = dotd(dpdv, dpdx), b0y = dotd(dpdu, rdpdy), b1y = dotd(dpdv, rdpdy);
+  double const det = a00 * a11 - a01 * a01;
+  if (fabs(det) < 1e-8) return r;
+  double dudx, dvdx, dudy, dvdy;
+  if (!__builtin_isinf(det) && fabs(det) > 1e-12) {
+    double const inv = 1.0 / det;
+    dudx = (a11 * b0x - a01 * b1x) * inv, dvdx = (a00 * b1x - a01 * b0x) * inv;
+    dudy = (a11 * b0y - a01 * b1y) * inv, dvdy = (a00 * b1y - a01 * b0y) * inv;
+  } else {
+    double const lambda = 1e-6 * fmax(1.0, fmax(a00, a11));
+    double const r00 = a00 + lambda, r11 = a11 + lambda, r01 = a01;
+    double const rdet = r00 * r11 - r01 * r01;
+    if (!__builtin_isinf(rdet) && fabs(rdet) > 0.0) {
+      double const inv = 1.0 / rdet;
+      dudx = (r11 * b0x - r01 * b1x) * inv, dvdx = (r00 * b1x - r01 * b0x) * inv;
+      dudy = (r11 * b0y - r01 * b1y) * inv, dvdy = (r00 * b1y - r01 * b0y) * inv;
+    } else {  // geometric gradients
+      d3 n = crossd(dpdu, dpdv);
+      double nl = lend(n);
+      if (nl < 1e-12) {
+        n = crossd(dpdu, dpdx), nl = lend(n);
+        if (nl < 1e-12) n = crossd(dpdv, dpdx), nl = lend(n);
+      }
+      n = nl < 1e-12 ? md3(0, 0, 1) : normd(n);
+      d3 const gu = normd(crossd(n, dpdv)), gv = normd(crossd(dpdu, n));
+      dudx = dotd(gu, dpdx), dvdx = dotd(gv, dpdx), dudy = dotd(gu, rdpdy), dvdy = dotd(gv, rdpdy);
+    }
+  }
+  auto clampd = [](double v) { return __builtin_isinf(v) ? 0.f : float(fmin(fmax(v, -1e8), 1e8)); };
+  r.dudx = clampd(dudx), r.dvdx = clampd(dvdx), r.dudy = clampd(dudy), r.dvdy = clampd(dvdy);
+  return r;
+}
 // metallic fraction of a BS_GGX_BLEND material at the hit: the record's constant, or the material's 1-channel metallic map
 // (core-material.cpp:209-216), whose index sits in the first texture slot of the pair's SECOND row
-DMT_DEV float blend_metallic(KArgs k, Rec32 const& rec, uint32_t matId, int tri, float bu, float bv) {
+template <bool FILT = false>
+DMT_DEV float blend_metallic(KArgs k, Rec32 const& rec, uint32_t matId, int tri, float bu, float bv, TexDiff const& td = TexDiff{}) {
   KArgs const ka = kargs(k);
   float m = h2f(lo16(rec.w[0]));
   if (ka->matTex != nullptr) {
@@ -325,13 +649,14 @@ DMT_DEV float blend_metallic(KArgs k, Rec32 const& rec, uint32_t matId, int tri,
     if (texM >= 0) {
       float const* const uv = ka->triUv + 6 * size_t(tri);
       float const w0 = 1.f - bu - bv;
-      m = tex_bilinear(k, texM, w0 * uv[0] + bu * uv[2] + bv * uv[4], w0 * uv[1] + bu * uv[3] + bv * uv[5], false).x;
+      m = tex_lookup<FILT>(k, texM, w0 * uv[0] + bu * uv[2] + bv * uv[4], w0 * uv[1] + bu * uv[3] + bv * uv[5], false, td).x;
     }
   }
   return m;
 }
 // patches `rec` from the material's textures at the hit and returns the shading normal (ng when there is no normal map)
-DMT_DEV f3 apply_material_textures(KArgs k, Rec32& rec, uint32_t matId, int tri, float bu, float bv, f3 ng) {
+template <bool FILT = false>
+DMT_DEV f3 apply_material_textures(KArgs k, Rec32& rec, uint32_t matId, int tri, float bu, float bv, f3 ng, TexDiff const& td = TexDiff{}) {
   KArgs const ka = kargs(k);
   uint32_t const* const m = ka->matTex + 4 * matId;
   int32_t const texD = int32_t(m[0]), texR = int32_t(m[1]), texN = int32_t(m[2]);
@@ -342,12 +667,12 @@ DMT_DEV f3 apply_material_textures(KArgs k, Rec32& rec, uint32_t matId, int tri,
   float const s = w0 * uv[0] + bu * uv[2] + bv * uv[4], t = w0 * uv[1] + bu * uv[3] + bv * uv[5];
   uint32_t const type = hi16(rec.w[1]);
   if (texD >= 0 && type == BS_OREN) {
-    f3 const c = tex_bilinear(k, texD, s, t, false);
+    f3 const c = tex_lookup<FILT>(k, texD, s, t, false, td);
     rec.w[0] = f2h(fmaxf(0.f, fminf(c.x, 1.f))) | (f2h(fmaxf(0.f, fminf(c.y, 1.f))) << 16);
     rec.w[1] = (rec.w[1] & 0xFFFF0000u) | f2h(fmaxf(0.f, fminf(c.z, 1.f)));
   }
   if (texR >= 0) {
-    float const rough = fmaxf(0.f, fminf(tex_bilinear(k, texR, s, t, false).x, 1.f));
+    float const rough = fmaxf(0.f, fminf(tex_lookup<FILT>(k, texR, s, t, false, td).x, 1.f));
     if (type == BS_OREN) {  // makeOrenNayar, CC/private/bsdf.cu:817-844: terms derived from the STORED halves
       float const kk = (kPi / 2.f) - 2.f / 3.f;
       uint32_t const hr = f2h(fmaxf(0.f, fminf(rough, kPi / 2.f)));
@@ -364,7 +689,7 @@ DMT_DEV f3 apply_material_textures(KArgs k, Rec32& rec, uint32_t matId, int tri,
     }
   }
   if (texN < 0) return ng;
-  f3 n = tex_bilinear(k, texN, s, t, true);
+  f3 n = tex_lookup<FILT>(k, texN, s, t, true, td);
   auto quant = [](float v) { return float(int(v * 1023.f + 0.5f)) / 1023.f; };
   n = normalize(mk3(quant(n.x), quant(n.y), quant(n.z)));
   f3 tx, ty;
@@ -388,11 +713,13 @@ constexpr uint32_t kFeatTex = 1u << 4;           // SURVEY 8f-1 image textures
 constexpr uint32_t kFeatBlend = 1u << 5;         // image textures + fractional "metallic" (BS_GGX_BLEND record pairs)
 constexpr uint32_t kFeatLightTree = 1u << 6;     // SURVEY 8f-4 light tree (light_tree.hpp)
 constexpr uint32_t kFeatLightTreeRef = 1u << 7;  // the reference-semantics light tree (light_tree_ref.hpp)
+constexpr uint32_t kFeatTexFilter = 1u << 8;     // first-hit MIP / EWA texture filtering; with kFeatTex or kFeatBlend only
 
 template <uint32_t F>
 DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv) {
   static_assert(!((F & kFeatLightTree) && (F & kFeatLightTreeRef)), "one light tree at a time");
   static_assert(!((F & kFeatTex) && (F & kFeatBlend)), "kFeatBlend carries the texture code itself");
+  static_assert(!(F & kFeatTexFilter) || (F & (kFeatTex | kFeatBlend)), "the texture filter needs the texture code");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
   if constexpr (F & kFeatEnv) {
@@ -449,9 +776,14 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   Rec32 rec2{};
   float mix = 0.f;
   bool blend = false;
+  constexpr bool FILT = (F & kFeatTexFilter) != 0;
+  TexDiff td{0.f, 0.f, 0.f, 0.f};  // UV differentials of the camera ray's hit; zero at every later hit (core-render.cpp:264-268)
+  if constexpr (FILT) {
+    if (st.depth == 0) td = tex_footprint(k, bestTri, hit.pos, hit.normal);
+  }
   if constexpr (F & kFeatBlend) {
     if (hi16(rec.w[1]) == BS_GGX_BLEND) {
-      mix = blend_metallic(k, rec, hit.matId, bestTri, bu, bv);
+      mix = blend_metallic<FILT>(k, rec, hit.matId, bestTri, bu, bv, td);
       rec.w[1] = (rec.w[1] & 0x0000FFFFu) | (uint32_t(BS_GGX_DIEL) << 16);
       rec2 = sc.bsdfs[hit.matId + 1u];
       if (mix >= 1.f) rec = rec2;  // :273  the conductor alone
@@ -460,8 +792,8 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   }
   if constexpr (F & (kFeatTex | kFeatBlend)) {
     if (!(F & kFeatBlend) || kargs(k)->matTex != nullptr) {
-      ns = apply_material_textures(k, rec, hit.matId, bestTri, bu, bv, hit.normal);
-      if (blend) (void)apply_material_textures(k, rec2, hit.matId + 1u, bestTri, bu, bv, hit.normal);  // same roughness map
+      ns = apply_material_textures<FILT>(k, rec, hit.matId, bestTri, bu, bv, hit.normal, td);
+      if (blend) (void)apply_material_textures<FILT>(k, rec2, hit.matId + 1u, bestTri, bu, bv, hit.normal, td);  // same roughness map
     }
   }
 #if DMT_SECTION_TIMING
@@ -1668,7 +2000,15 @@ DMT_DEV void megakernel_body_bvh() {
   X(_ltree2, kFeatLightTreeRef, 3, megakernel_body)                                 \
   X(_bvh_ltree2, kFeatBvh | kFeatLightTreeRef, 2, megakernel_body_bvh)              \
   X(_env_ltree2, kFeatEnv | kFeatLightTreeRef, 3, megakernel_body)                  \
-  X(_bvh_env_ltree2, kFeatBvh | kFeatEnv | kFeatLightTreeRef, 2, megakernel_body_bvh)
+  X(_bvh_env_ltree2, kFeatBvh | kFeatEnv | kFeatLightTreeRef, 2, megakernel_body_bvh)   \
+  X(_texf, kFeatTex | kFeatTexFilter, 2, megakernel_body)                           \
+  X(_bvh_texf, kFeatBvh | kFeatTex | kFeatTexFilter, 2, megakernel_body_bvh)        \
+  X(_env_texf, kFeatEnv | kFeatTex | kFeatTexFilter, 2, megakernel_body)            \
+  X(_bvh_env_texf, kFeatBvh | kFeatEnv | kFeatTex | kFeatTexFilter, 2, megakernel_body_bvh) \
+  X(_blendf, kFeatBlend | kFeatTexFilter, 2, megakernel_body)                       \
+  X(_bvh_blendf, kFeatBvh | kFeatBlend | kFeatTexFilter, 2, megakernel_body_bvh)    \
+  X(_env_blendf, kFeatEnv | kFeatBlend | kFeatTexFilter, 2, megakernel_body)        \
+  X(_bvh_env_blendf, kFeatBvh | kFeatEnv | kFeatBlend | kFeatTexFilter, 2, megakernel_body_bvh)
 // the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
 // algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
 #define DMT_STATS_MEGAKERNELS(X)                                                    \
@@ -1700,6 +2040,27 @@ __global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t 
   auto store = [&](f3 L, uint32_t) { L3[3 * i] = L.x, L3[3 * i + 1] = L.y, L3[3 * i + 2] = L.z; };
   uint32_t const gtid = blockIdx.x * blockDim.x + threadIdx.x;
   while (__any(st.active || st.hasShadow)) lane_step<F>(k, gtid, st, store);
+}
+
+// first-hit texture filter probes: the lookup of texture `tex` at (tri, bu, bv) by the *_texf kernels' device code, as at a
+// hit of depth `depth` (0: the camera ray's, filtered; otherwise level 0)
+__global__ void k_test_texfilter(RenderParams P, int n, int32_t const* tri, float const* bu, float const* bv, int32_t const* tex,
+                                 int32_t const* depth, float* rgb3, int32_t* branch, float* lod) {
+#pragma clang fp contract(off)  // (s, t) rounded as a plain float restatement rounds them
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  TriPost const T = load_scene(k).post[tri[i]];
+  Hit const hit = hit_finish(T, bu[i], bv[i], mk3(0.f, 0.f, 1.f));
+  TexDiff td{0.f, 0.f, 0.f, 0.f};
+  if (depth[i] == 0) td = tex_footprint(k, tri[i], hit.pos, hit.normal);
+  float const* const uv = kargs(k)->triUv + 6 * size_t(tri[i]);
+  float const w0 = 1.f - bu[i] - bv[i];
+  float const s = w0 * uv[0] + bu[i] * uv[2] + bv[i] * uv[4], t = w0 * uv[1] + bu[i] * uv[3] + bv[i] * uv[5];
+  TexProbe pr{0, 0.f};
+  f3 const c = tex_filtered<true>(k, tex[i], s, t, false, td, &pr);
+  rgb3[3 * i] = c.x, rgb3[3 * i + 1] = c.y, rgb3[3 * i + 2] = c.z;
+  branch[i] = pr.branch, lod[i] = pr.lod;
 }
 
 // A18 probes: env-map sampling (u2 -> wi, pdf, uv, Le by uv) and evaluation by direction (wi -> Le, pdf)
@@ -1976,6 +2337,10 @@ struct dmt_ctx {
   DevBuf<uint32_t> d_matTex;  // 4 words per BSDF
   DevBuf<float> d_triUv;      // 6 floats per triangle
   uint32_t texCount = 0, matTexCount = 0;
+  DevBuf<uint32_t> d_texMip;      // MIP levels 1.. of every texture (buildMipChain)
+  DevBuf<int32_t> d_texMipDesc;   // 2 words per texture: {levels, first texel of level 1}
+  int texFilter = DMT_TEXFILTER_LEVEL0;
+  float texFoot[19] = {};         // dmt_texture_footprint of the current camera
   bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_blend kernels carry that code
   size_t triUvCount = 0;
   // wavefront form of the BVH path (wavefront.hpp)
@@ -2240,6 +2605,100 @@ SamplerParams computeSamplerParams(int width, int height) {
   return p;
 }
 
+// MIP chain of one RGBA8 texture (makeRGBMipmappedTexture, core-texture.cu:340-540): the reference's level count
+// (`while (w > 0 || h > 0)`), level l of resolution (max(1, w >> l), max(1, h >> l)), each texel the 2x2 box average of the
+// level above in float, stored as a byte by truncation (toByte).  Levels 1.. are appended to `out` row by row; returns the
+// level count.  [fix 1] a level where one axis has reached 0 averages the parent texels that exist (1x2 or 2x1); the
+// reference stores zeros there.  Textures of other than power-of-two sides (which the reference refuses) follow the same
+// rule, so the last odd row or column of a level takes no part in the next, as the reference's indexing would have it.
+int buildMipChain(uint8_t const* rgba, int w, int h, std::vector<uint32_t>& out) {
+  int levels = 0;
+  for (int a = w, b = h; a > 0 || b > 0; a >>= 1, b >>= 1) ++levels;
+  out.clear();
+  std::vector<uint8_t> prev(rgba, rgba + 4 * size_t(w) * size_t(h)), cur;
+  int pw = w, ph = h;
+  for (int l = 1; l < levels; ++l) {
+    int const cw = std::max(1, w >> l), ch = std::max(1, h >> l);
+    cur.assign(4 * size_t(cw) * size_t(ch), 0);
+    for (int v = 0; v < ch; ++v)
+      for (int u = 0; u < cw; ++u) {
+        bool const x1 = 2 * u + 1 < pw, y1 = 2 * v + 1 < ph;
+        float const scale = (x1 && y1) ? 0.25f : (x1 || y1) ? 0.5f : 1.f;
+        uint32_t word = 0;
+        for (int c = 0; c < 4; ++c) {
+          auto at = [&](int x, int y) { return float(prev[4 * (size_t(y) * size_t(pw) + size_t(x)) + size_t(c)]) / 255.f; };
+          float sum = at(2 * u, 2 * v);  // c00 + c10 + c01 + c11, left to right
+          if (x1) sum += at(2 * u + 1, 2 * v);
+          if (y1) sum += at(2 * u, 2 * v + 1);
+          if (x1 && y1) sum += at(2 * u + 1, 2 * v + 1);
+          float const t = scale * sum * 255.f;
+          uint8_t const byte = uint8_t(std::min(std::max(t, 0.f), 255.f));
+          cur[4 * (size_t(v) * size_t(cw) + size_t(u)) + size_t(c)] = byte;
+          word |= uint32_t(byte) << (8 * c);
+        }
+        out.push_back(word);
+      }
+    prev.swap(cur);
+    pw = cw, ph = ch;
+  }
+  return levels;
+}
+
+// The camera's footprint for the first-hit texture filter (minDifferentialsFromCamera, core-render.cpp:928-980), once per
+// camera: 512 rays along the film diagonal, pFilm = i / 511 * resolution; for each, the x / y neighbour directions
+// (camera-space direction + one raster step) in Frame::fromZ(ray.d) (gramSchmidt, cudautils-vecmath.cu:960-969); the
+// smallest of each by squared length is kept (strict <, so the first of equals).  The origin differentials of a pinhole
+// camera are 0.  The scale is max(1/8, 1/sqrt(spp)) of the frame's spp (dmt_camera.spp; < 1 counts as 1).  Evaluated in
+// double from the float matrices of dmt_set_camera; out = camera-from-render as a row-major 3x4, min dx[3], min dy[3], scale.
+void textureFootprint(dmt_camera const& cam, float out[19]) {
+  float cf[16], rf[16];
+  cameraFromRaster(cam.focal_length, cam.sensor_size, uint32_t(cam.width), uint32_t(cam.height), cf);
+  worldFromCamera(cam.dir, cam.pos, rf);
+  struct D3 { double x, y, z; };
+  auto add = [](D3 a, D3 b) { return D3{a.x + b.x, a.y + b.y, a.z + b.z}; };
+  auto sub = [](D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; };
+  auto dotd = [](D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; };
+  auto crossd = [](D3 a, D3 b) { return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; };
+  auto norm = [&](D3 a) { double const l = std::sqrt(dotd(a, a)); return D3{a.x / l, a.y / l, a.z / l}; };
+  auto point = [](float const* m, D3 p) {  // affine, column-major
+    return D3{m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12], m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
+              m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14]};
+  };
+  auto dir = [](float const* m, D3 v) {
+    return D3{m[0] * v.x + m[4] * v.y + m[8] * v.z, m[1] * v.x + m[5] * v.y + m[9] * v.z, m[2] * v.x + m[6] * v.y + m[10] * v.z};
+  };
+  auto dirT = [](float const* m, D3 v) {  // the inverse of the rotation: its transpose
+    return D3{m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z};
+  };
+  D3 const pos{rf[12], rf[13], rf[14]};
+  D3 const tr = dirT(rf, pos);
+  for (int r = 0; r < 3; ++r) {
+    out[4 * r + 0] = rf[4 * r + 0], out[4 * r + 1] = rf[4 * r + 1], out[4 * r + 2] = rf[4 * r + 2];
+    out[4 * r + 3] = float(-(r == 0 ? tr.x : r == 1 ? tr.y : tr.z));
+  }
+  D3 const dxCam = sub(point(cf, D3{1, 0, 0}), point(cf, D3{0, 0, 0}));
+  D3 const dyCam = sub(point(cf, D3{0, 1, 0}), point(cf, D3{0, 0, 0}));
+  double const inf = std::numeric_limits<double>::infinity();
+  D3 minX{inf, inf, inf}, minY{inf, inf, inf};
+  for (int i = 0; i < 512; ++i) {
+    double const f = double(i) / 511.0;
+    D3 const pCam = point(cf, D3{f * cam.width, f * cam.height, 0});
+    D3 const d = norm(dir(rf, norm(pCam)));
+    D3 const rx = norm(dir(rf, add(dirT(rf, d), dxCam)));
+    D3 const ry = norm(dir(rf, add(dirT(rf, d), dyCam)));
+    D3 const gx = (d.x != d.y || d.x != d.z) ? D3{d.z - d.y, d.x - d.z, d.y - d.x} : D3{d.z - d.y, d.x + d.z, -d.y - d.x};
+    D3 const fx = norm(gx), fy = crossd(d, fx);
+    auto local = [&](D3 v) { return D3{dotd(v, fx), dotd(v, fy), dotd(v, d)}; };
+    D3 const df = norm(local(d)), dxf = norm(local(rx)), dyf = norm(local(ry));
+    D3 const ex = sub(dxf, df), ey = sub(dyf, df);
+    if (dotd(ex, ex) < dotd(minX, minX)) minX = ex;
+    if (dotd(ey, ey) < dotd(minY, minY)) minY = ey;
+  }
+  out[12] = float(minX.x), out[13] = float(minX.y), out[14] = float(minX.z);
+  out[15] = float(minY.x), out[16] = float(minY.y), out[17] = float(minY.z);
+  out[18] = float(std::max(0.125, 1.0 / std::sqrt(double(std::max(cam.spp, 1)))));
+}
+
 // The feature mask (kFeat*) of what a launch of this context needs.  The light tree applies to plain point / spot light
 // lists; textured or emissive-triangle scenes keep the uniform pick.  A light tree not built yet counts as applying:
 // resolveFeatures builds it first.
@@ -2253,6 +2712,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   else if (c->texCount > 0) F |= kFeatTex;
   if (treeable && c->lightSampling == DMT_LIGHTS_TREE) F |= kFeatLightTree;
   if (treeable && c->lightSampling == DMT_LIGHTS_TREE_REFERENCE) F |= kFeatLightTreeRef;
+  if (c->texFilter == DMT_TEXFILTER_REFERENCE && (F & (kFeatTex | kFeatBlend))) F |= kFeatTexFilter;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2326,8 +2786,14 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.shadeThreshold = bvhShadeThreshold(c);
   P.env = c->env;
   P.areaOf = c->d_areaOf.get(), P.areaTri = c->d_areaTri.get(), P.areaLe = c->d_areaLe.get(), P.areaCount = c->areaCount;
-  if (c->texCount > 0)
+  if (c->texCount > 0) {
     P.texRgba = c->d_texRgba.get(), P.texDesc = c->d_texDesc.get(), P.matTex = c->d_matTex.get(), P.triUv = c->d_triUv.get();
+    P.texMip = c->d_texMip.get(), P.texMipDesc = c->d_texMipDesc.get();
+    memcpy(P.texCfr, c->texFoot, 12 * sizeof(float));
+    memcpy(P.texMinDx, c->texFoot + 12, 3 * sizeof(float));
+    memcpy(P.texMinDy, c->texFoot + 15, 3 * sizeof(float));
+    P.texSppScale = c->texFoot[18];
+  }
   uint32_t const F = featuresOf(c);
   if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree.get();
   if ((F & kFeatLightTreeRef) && c->lightTreeValid) P.lightTreeRef = c->d_lightTreeRef.get();
@@ -2732,6 +3198,7 @@ int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam) {
   worldFromCamera(cam->dir, cam->pos, m);
   memcpy(ctx->xf.rfc, m, sizeof(m));
   ctx->sp = computeSamplerParams(cam->width, cam->height);
+  textureFootprint(*cam, ctx->texFoot);
   ctx->haveCamera = true;
   return DMT_OK;
 }
@@ -3250,6 +3717,7 @@ int dmt_upload_textures(dmt_ctx* ctx, const uint8_t* rgba8, uint64_t texel_count
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->d_texRgba.reset(), ctx->d_texDesc.reset(), ctx->d_matTex.reset(), ctx->d_triUv.reset();
+  ctx->d_texMip.reset(), ctx->d_texMipDesc.reset();
   ctx->texCount = 0, ctx->matTexCount = 0, ctx->triUvCount = 0;
   if (texture_count == 0) return DMT_OK;  // cleared
   if (!rgba8 || !desc3 || !mat_tex4 || !tri_uv6 || texel_count == 0 || bsdf_count == 0 || triangle_count == 0)
@@ -3264,15 +3732,27 @@ int dmt_upload_textures(dmt_ctx* ctx, const uint8_t* rgba8, uint64_t texel_count
       uint32_t const t = mat_tex4[4 * size_t(b) + size_t(j)];
       if (t != 0xFFFFFFFFu && t >= texture_count) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_textures: material refers to a texture that does not exist");
     }
-  DevBuf<uint32_t> texRgba, matTex;
-  DevBuf<int32_t> texDesc;
+  std::vector<uint32_t> mip;  // levels 1.. of every texture, back to back (upload-time host work)
+  std::vector<int32_t> mipDesc(2 * size_t(texture_count));
+  for (uint32_t k = 0; k < texture_count; ++k) {
+    std::vector<uint32_t> chain;
+    mipDesc[2 * k] = buildMipChain(rgba8 + 4 * size_t(desc3[3 * k]), desc3[3 * k + 1], desc3[3 * k + 2], chain);
+    if (mip.size() + chain.size() > size_t(INT32_MAX)) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_textures: MIP chains too large");
+    mipDesc[2 * k + 1] = int32_t(mip.size());
+    mip.insert(mip.end(), chain.begin(), chain.end());
+  }
+  DevBuf<uint32_t> texRgba, matTex, texMip;
+  DevBuf<int32_t> texDesc, texMipDesc;
   DevBuf<float> triUv;
+  HIP_TRY(ctx, texMip.assign(mip.data(), mip.size()));
+  HIP_TRY(ctx, texMipDesc.assign(mipDesc.data(), mipDesc.size()));
   HIP_TRY(ctx, texRgba.assign(rgba8, size_t(texel_count)));
   HIP_TRY(ctx, texDesc.assign(desc3, 3 * size_t(texture_count)));
   HIP_TRY(ctx, matTex.assign(mat_tex4, 4 * size_t(bsdf_count)));
   HIP_TRY(ctx, triUv.assign(tri_uv6, 6 * size_t(triangle_count)));
   ctx->d_texRgba = std::move(texRgba), ctx->d_texDesc = std::move(texDesc), ctx->d_matTex = std::move(matTex);
   ctx->d_triUv = std::move(triUv);
+  ctx->d_texMip = std::move(texMip), ctx->d_texMipDesc = std::move(texMipDesc);
   ctx->texCount = texture_count, ctx->matTexCount = bsdf_count, ctx->triUvCount = size_t(triangle_count);
   return DMT_OK;
 }
@@ -3569,6 +4049,57 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
                      dss.get(), dL.get());
   if (int const rc = finishTest(ctx)) return rc;
   HIP_TRY(ctx, hipMemcpy(L3, dL.get(), size_t(n) * 12, hipMemcpyDeviceToHost));
+  return DMT_OK;
+}
+
+int dmt_set_texture_filter(dmt_ctx* ctx, int mode) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (mode != DMT_TEXFILTER_LEVEL0 && mode != DMT_TEXFILTER_REFERENCE) return fail(ctx, DMT_ERR_INVALID, "dmt_set_texture_filter: unknown mode");
+  ctx->texFilter = mode;
+  return DMT_OK;
+}
+
+int dmt_texture_mip_chain(const uint8_t* rgba8, int width, int height, uint8_t* out, uint64_t out_texels, int* levels) {
+  if (!rgba8 || width <= 0 || height <= 0 || width > 65536 || height > 65536 || !levels) return DMT_ERR_INVALID;
+  std::vector<uint32_t> chain;
+  *levels = buildMipChain(rgba8, width, height, chain);
+  if (out_texels < chain.size() || (!out && !chain.empty())) return DMT_ERR_INVALID;
+  if (!chain.empty()) memcpy(out, chain.data(), 4 * chain.size());
+  return DMT_OK;
+}
+
+int dmt_texture_footprint(const dmt_camera* cam, float* out) {
+  if (!cam || !out || cam->width <= 0 || cam->height <= 0) return DMT_ERR_INVALID;
+  textureFootprint(*cam, out);
+  return DMT_OK;
+}
+
+int dmt_test_texture_filter(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const int32_t* tex,
+                            const int32_t* depth, float* rgb3, int32_t* branch, float* lod) {
+  if (!ctx || n < 0 || !tri || !bu || !bv || !tex || !depth || !rgb3 || !branch || !lod) return DMT_ERR_INVALID;
+  if (!(ctx->haveTris && ctx->haveCamera) || ctx->texCount == 0 || ctx->triUvCount != ctx->triCount)
+    return fail(ctx, DMT_ERR_STATE, "dmt_test_texture_filter: triangles, camera and textures (with one UV triple per triangle) first");
+  for (int i = 0; i < n; ++i)
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount || tex[i] < 0 || uint32_t(tex[i]) >= ctx->texCount)
+      return fail(ctx, DMT_ERR_INVALID, "dmt_test_texture_filter: triangle or texture index out of range");
+  if (n == 0) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevBuf<int32_t> dTri, dTex, dDepth, dBranch;
+  DevBuf<float> dBu, dBv, dRgb, dLod;
+  HIP_TRY(ctx, dTri.assign(tri, size_t(n)));
+  HIP_TRY(ctx, dTex.assign(tex, size_t(n)));
+  HIP_TRY(ctx, dDepth.assign(depth, size_t(n)));
+  HIP_TRY(ctx, dBu.assign(bu, size_t(n)));
+  HIP_TRY(ctx, dBv.assign(bv, size_t(n)));
+  HIP_TRY(ctx, dRgb.reserve(3 * size_t(n)));
+  HIP_TRY(ctx, dBranch.reserve(size_t(n)));
+  HIP_TRY(ctx, dLod.reserve(size_t(n)));
+  hipLaunchKernelGGL(k_test_texfilter, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, baseParams(ctx, size_t((n + 63) / 64) * 64), n,
+                     dTri.get(), dBu.get(), dBv.get(), dTex.get(), dDepth.get(), dRgb.get(), dBranch.get(), dLod.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(rgb3, dRgb.get(), 12 * size_t(n), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(branch, dBranch.get(), 4 * size_t(n), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(lod, dLod.get(), 4 * size_t(n), hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 

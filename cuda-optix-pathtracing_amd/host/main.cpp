@@ -4,7 +4,7 @@
 //   * dmt-tracer (cli/CLIManager.cpp:11-36): --device|-d cpu|gpu, --scene|-s <file>, --out|-o <path>, --time|-t,
 //       --help|-h.  `--device cpu` is refused: this build has no CPU renderer (the CPU restatement used by the tests is test
 //       infrastructure and is never linked into the product).
-// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --light-tree, --light-tree-reference, and --gpus <N>: N contexts, one per GPU
+// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --light-tree, --light-tree-reference, --texture-filter, and --gpus <N>: N contexts, one per GPU
 // (ordinals 0..N-1), each rendering the interleaved 8x8 tiles j mod N == rank (dmt_set_partition) concurrently; the N
 // films are disjoint and summed on the host (x + 0: an exact gather).  bench.py's N-process RCCL path is the scalable
 // form of the same partition; --gpus is the single-process form for the CLI.
@@ -35,6 +35,7 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   std::string scenePath;  // --scene <file.json>: the reference's JSON scene description instead of cornellBox()
   bool bvh = false;       // --bvh: traverse the 4-wide BVH instead of testing every triangle
   bool lightTree = false; // --light-tree: importance-driven light choice (csrc/light_tree.hpp) instead of the uniform pick
+  bool textureFilter = false; // --texture-filter: first-hit MIP / EWA filtering of image textures (DMT_TEXFILTER_REFERENCE)
   bool lightTreeRef = false; // --light-tree-reference: the reference's tree semantics, up to four lights per bounce (csrc/light_tree_ref.hpp)
   bool widthSet = false, heightSet = false, sppSet = false, depthSet = false;
 
@@ -75,7 +76,9 @@ void printHelp() {
       "                       its resolution, samples and max-depth apply unless given on the command line\n"
       "  --bvh             -- BVH traversal instead of the brute-force triangle loop\n"
       "  --light-tree      -- pick the NEE light through a light BVH (flux x cosine / distance^2) instead of uniformly\n"
-      "  --light-tree-reference -- the reference's light tree semantics: cones, adaptive cuts, up to four lights per bounce");
+      "  --light-tree-reference -- the reference's light tree semantics: cones, adaptive cuts, up to four lights per bounce\n"
+      "  --texture-filter  -- filter image textures at the camera ray's first hit (MIP levels / EWA by the pixel footprint)\n"
+      "                       instead of the level-0 bilinear lookup");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -90,6 +93,7 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--bvh") c.bvh = true;
     else if (a == "--light-tree") c.lightTree = true;
     else if (a == "--light-tree-reference") c.lightTreeRef = true;
+    else if (a == "--texture-filter") c.textureFilter = true;
     else if (a == "--kspp" && more) c.kspp = std::atoi(argv[++i]);
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
@@ -174,6 +178,7 @@ int main(int argc, char** argv) {
   bool const verbose = cfg.logLevel == "verbose";
   dmt_host::Scene scene = cfg.scenePath.empty() ? dmt_host::cornellBox() : std::move(json.scene);
   scene.camera.width = cfg.width, scene.camera.height = cfg.height, scene.camera.spp = cfg.kspp;
+  if (cfg.textureFilter) scene.camera.spp = cfg.spp;  // the filter's footprint scale follows the frame's samples per pixel
   double const loadMs = msSince(tLoad);
 
   // one context per GPU; DMT_CLI_SHARE_DEVICE=1 (tests on a one-GPU box) maps all ranks onto --gpu-ordinal
@@ -190,6 +195,7 @@ int main(int argc, char** argv) {
     if (dmt_set_partition(ctx, r, cfg.gpus) != DMT_OK) return fail(ctx, "dmt_set_partition");
     if (cfg.lightTree && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
     if (cfg.lightTreeRef && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
+    if (cfg.textureFilter && dmt_set_texture_filter(ctx, DMT_TEXFILTER_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_texture_filter");
   }
   double const uploadMs = msSince(tUpload);
 

@@ -145,6 +145,27 @@ int dmt_clear_envmap(dmt_ctx* ctx);
  * BSDFs (the counts must match at render time); texture_count == 0 clears.  Not combinable with emissive triangles. */
 int dmt_upload_textures(dmt_ctx* ctx, const uint8_t* rgba8, uint64_t texel_count, const int32_t* desc3, uint32_t texture_count,
                         const uint32_t* mat_tex4, uint32_t bsdf_count, const float* tri_uv6, uint64_t triangle_count);
+/* First-hit texture filtering (the reference's CPU renderer, src/core/private/core-material.cpp:83-175): at the camera
+ * ray's hit every texture lookup is filtered by the pixel's footprint -- isotropic trilinear, or two EWA lookups -- over a
+ * 2x2-box MIP chain that dmt_upload_textures builds; every later hit keeps the level-0 bilinear lookup.  Mode
+ * DMT_TEXFILTER_LEVEL0 (the default) is the level-0 lookup everywhere; DMT_TEXFILTER_REFERENCE selects the filtering
+ * kernels when textures are uploaded.  The footprint uses the camera's spp field (the frame's samples per pixel). */
+enum {
+  DMT_TEXFILTER_LEVEL0 = 0,
+  DMT_TEXFILTER_REFERENCE = 1,
+};
+int dmt_set_texture_filter(dmt_ctx* ctx, int mode);
+/* host only: MIP levels 1.. of one RGBA8 texture (width x height texels, 4 bytes each), back to back and row major, into
+ * `out` (capacity out_texels texels); *levels = the level count including level 0 */
+int dmt_texture_mip_chain(const uint8_t* rgba8, int width, int height, uint8_t* out, uint64_t out_texels, int* levels);
+/* host only: the camera's footprint, 19 floats: camera-from-render as a row-major 3x4, the smallest x and y direction
+ * differentials (3 + 3), the spp scale max(1/8, 1/sqrt(spp)) */
+int dmt_texture_footprint(const dmt_camera* cam, float* out);
+/* device probes of the filtered lookup of texture tex[i] at triangle tri[i], barycentrics (bu[i], bv[i]) of the uploaded
+ * scene, as at a hit of depth depth[i] (0 = the camera ray's hit): rgb3, branch (0 level 0, 1 trilinear, 2 EWA, 3 EWA at a
+ * level raised to bound its work) and the level used (integer part) with its interpolation weight (fraction) */
+int dmt_test_texture_filter(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const int32_t* tex,
+                            const int32_t* depth, float* rgb3, int32_t* branch, float* lod);
 /* host only (no GPU needed): the sampling tables dmt_upload_envmap builds; func/cdf: height*width floats each,
  * row_integral / marginal_func / marginal_cdf: height floats each */
 int dmt_envmap_tables(const float* rgb, int width, int height, float* func, float* cdf, float* row_integral,
