@@ -54,7 +54,7 @@ EXPORTED_SYMBOLS = [
     "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
-    "dmt_render", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_test_triangle_intersect",
+    "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_test_triangle_intersect",
     "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_light", "dmt_test_half",
     "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
     "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
@@ -371,6 +371,17 @@ class Renderer:
         x0, y0, x1, y1 = region if region is not None else (0, 0, self.width, self.height)
         self._check(self._lib.dmt_render(self._ctx, C.c_uint32(sample_offset), C.c_uint32(spp), int(x0), int(y0),
                                          int(x1), int(y1)), "dmt_render")
+
+    def render_adaptive(self, threshold, max_spp, step_spp, min_spp=0, region=None):
+        """Adaptive sampling (dmt_render_adaptive): rounds of step_spp samples from sample 0 until each pixel of the region
+        has max_spp samples, or at least min_spp and a relative standard error of its mean <= threshold.  Synchronous.
+        Returns (rounds launched, path samples traced).  Call film_clear() first for a fresh image."""
+        x0, y0, x1, y1 = region if region is not None else (0, 0, self.width, self.height)
+        rounds, samples = C.c_uint32(0), C.c_uint64(0)
+        self._check(self._lib.dmt_render_adaptive(self._ctx, C.c_uint32(min_spp), C.c_uint32(max_spp), C.c_uint32(step_spp),
+                                                  C.c_float(threshold), int(x0), int(y0), int(x1), int(y1), C.byref(rounds),
+                                                  C.byref(samples)), "dmt_render_adaptive")
+        return int(rounds.value), int(samples.value)
 
     def render_stats(self, spp, sample_offset=0, region=None):
         x0, y0, x1, y1 = region if region is not None else (0, 0, self.width, self.height)

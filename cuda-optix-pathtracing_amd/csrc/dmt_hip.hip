@@ -89,6 +89,10 @@ struct RenderParams {
   float* stage;            // staging slabs of finished samples: [wave][kSlabsPerWave][chunkSpp][64] float3
   uint32_t* link;          // [numChunks][numItems] hand-over word of (chunk, tile): 0, kFoldReady or slab + 1 (item_complete)
   uint32_t* slabBusy;      // [wave][kSlabsPerWave] 1 while a handed-over slab waits for its folder
+  // adaptive sampling (dmt_render_adaptive; both null otherwise): the launch's tiles are tileList[0 .. numItems >> subShift),
+  // region tile indices (rank + k * world), and a lane renders its pixel only if the pixel's bit of tileMask[tile] is set
+  uint32_t const* tileList;
+  unsigned long long const* tileMask;
   unsigned long long* schedDiag;  // kSchedDiagWords counters, accumulated over launches (dmt_sched_diag)
   int maxDepth;
   int shadeThreshold;         // BVH megakernel: shade when this many lanes of the wave have finished their rays (bvhShadeThreshold)
@@ -1479,20 +1483,34 @@ struct LaneSched {
 };
 
 // pixel origin and row count of a tile item (an owned tile is scheduled as 1 << subShift bands of 8 >> subShift
-// rows: more, smaller items when this GPU has fewer tiles than resident waves; lanes beyond the band are "outside")
+// rows: more, smaller items when this GPU has fewer tiles than resident waves; lanes beyond the band are "outside").
+// Adaptive launches (tileList set; wave-uniform) take the tile from the list and keep only the lanes whose pixel bit is
+// set in the tile's mask word: pixel (x, y) of the tile is bit y * 8 + x, so lane i of band b is bit b * rows * 8 + i.
+// The two pointers are read from the kernel arguments here, not kept in TileArgs (SGPRs held across the hot loop).
 struct ItemGeom {
   int px0, py0;
   uint32_t rows;
+  unsigned long long live;  // bit i: lane i's pixel is traced (all ones without a tile list)
 };
 DMT_DEV ItemGeom item_geom(TileArgs const& T, uint32_t item) {
   uint32_t const band = item & ((1u << T.subShift) - 1u);
   uint32_t const rows = 8u >> T.subShift;
-  uint32_t const j = uint32_t(T.rank) + (item >> T.subShift) * uint32_t(T.world);
-  return {(T.tx0 + int(j % uint32_t(T.rtx))) * 8, (T.ty0 + int(j / uint32_t(T.rtx))) * 8 + int(band * rows), rows};
+  uint32_t j;
+  unsigned long long live = ~0ull;
+  KArgs const k = kargs(kargs_base());
+  if (uint32_t const* const list = k->tileList) {
+    j = list[item >> T.subShift];
+    live = kargs(k)->tileMask[j] >> (band * rows * 8u);
+  } else {
+    j = uint32_t(T.rank) + (item >> T.subShift) * uint32_t(T.world);
+  }
+  return {(T.tx0 + int(j % uint32_t(T.rtx))) * 8, (T.ty0 + int(j / uint32_t(T.rtx))) * 8 + int(band * rows), rows, live};
 }
 DMT_DEV bool item_lane_inside(TileArgs const& T, ItemGeom const& g, int lane) {
   int const px = g.px0 + (lane & 7), py = g.py0 + (lane >> 3);
-  return uint32_t(lane >> 3) < g.rows && px >= T.x0 && px < T.x1 && py >= T.y0 && py < T.y1;
+  // (g.live is wave-uniform and bit i belongs to lane i: it IS the lane mask -- no per-lane shift, no VGPRs)
+  return uint32_t(lane >> 3) < g.rows && px >= T.x0 && px < T.x1 && py >= T.y0 && py < T.y1 &&
+         __builtin_amdgcn_inverse_ballot_w64(g.live);
 }
 DMT_DEV uint32_t chunk_samples(TileArgs const& T, uint32_t chunk) {
   uint32_t const s0 = chunk * T.chunkSpp;
@@ -2020,6 +2038,54 @@ DMT_DEV void megakernel_body_bvh() {
 DMT_MEGAKERNELS(DMT_DEFINE_MEGAKERNEL)
 DMT_STATS_MEGAKERNELS(DMT_DEFINE_MEGAKERNEL)
 
+// ---- adaptive sampling (dmt_render_adaptive) --------------------------------------------------------
+// Stopping rule, fp32: a pixel with N = M2.w samples has the relative standard error of its mean
+//   err = sqrt((M2.x + M2.y + M2.z) / (N (N - 1))) / max(mean.x + mean.y + mean.z, 1e-3)     (+inf for N < 2)
+// and takes part in the round that starts at sample `offset` iff
+//   N == offset && N < maxSpp && (N < minSpp || err > threshold).
+// N == offset: a pixel is traced only while it holds exactly samples [0, offset), so it drops out for good and a film
+// that was not cleared is never counted twice; its film then equals a uniform film of N samples bit for bit.
+DMT_DEV bool adaptive_active(float4 m, float4 v, uint32_t offset, uint32_t minSpp, uint32_t maxSpp, float threshold) {
+  float const N = v.w;
+  if (N != float(offset) || !(N < float(maxSpp))) return false;
+  if (N < float(minSpp) || N < 2.f) return true;
+  float const err = sqrtf((v.x + v.y + v.z) / (N * (N - 1.f))) / fmaxf(m.x + m.y + m.z, 1e-3f);
+  return err > threshold;
+}
+struct AdaptiveArgs {
+  float4 const* mean;
+  float4 const* m2;
+  unsigned long long* mask;  // [region tile] the tile's active pixels, bit y * 8 + x
+  uint32_t* list;            // [k < counters[0]] region tiles with at least one active pixel, in no particular order
+  uint32_t* counters;        // {listed tiles, active pixels}, zero at launch
+  int width, x0, y0, x1, y1, tx0, ty0, rtx;
+  uint32_t owned;            // tiles of the region this partition owns
+  int rank, world;
+  uint32_t offset, minSpp, maxSpp;
+  float threshold;
+};
+// one wave per owned tile (region tile j = rank + w * world, as item_geom), lane = pixel
+__global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
+  uint32_t const w = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (w >= A.owned) return;  // whole waves
+  int const lane = int(threadIdx.x) & 63;
+  uint32_t const j = uint32_t(A.rank) + w * uint32_t(A.world);
+  int const px = (A.tx0 + int(j % uint32_t(A.rtx))) * 8 + (lane & 7), py = (A.ty0 + int(j / uint32_t(A.rtx))) * 8 + (lane >> 3);
+  bool active = false;
+  if (px >= A.x0 && px < A.x1 && py >= A.y0 && py < A.y1) {
+    size_t const pidx = size_t(px) + size_t(py) * size_t(A.width);
+    active = adaptive_active(film_load(A.mean + pidx), film_load(A.m2 + pidx), A.offset, A.minSpp, A.maxSpp, A.threshold);
+  }
+  unsigned long long const word = __ballot(active);
+  if (lane == 0) {
+    A.mask[j] = word;
+    if (word != 0ull) {
+      A.list[atomicAdd(&A.counters[0], 1u)] = j;
+      atomicAdd(&A.counters[1], uint32_t(__popcll(word)));
+    }
+  }
+}
+
 #include "wavefront.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -2374,6 +2440,10 @@ struct dmt_ctx {
   unsigned long long expectedFolds = 0;    // work items launched so far: what d_schedDiag[0] must read once the stream has drained
   DevBuf<unsigned long long> d_stats;      // 16 device counters of dmt_render_stats / dmt_render_profile
   DevBuf<float> d_stage;        // staging slabs of finished samples, [wave][kSlabsPerWave][chunkSpp][64] float3
+  // dmt_render_adaptive: per tile of the film's tile grid a mask word, the list of tiles with active pixels, two counters
+  DevBuf<unsigned long long> d_adMask;
+  DevBuf<uint32_t> d_adList;
+  DevBuf<uint32_t> d_adCount;
   uint32_t chunkSpp = 0;           // samples per work item, 0 = automatic
   int subShift = -1;               // row bands per tile (log2); -1 = choose per launch
   int maxDepth = 32;
@@ -3405,7 +3475,14 @@ static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, ui
   return DMT_OK;
 }
 
-static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats) {
+// the tiles of an adaptive round (dmt_render_adaptive): `count` region tiles in `list`, their pixel masks in `mask`
+struct TileSelection {
+  uint32_t const* list;
+  unsigned long long const* mask;
+  uint32_t count;
+};
+static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats,
+                      TileSelection const* sel = nullptr) {
   if (!ctx) return DMT_ERR_INVALID;
   if (stats6) memset(stats6, 0, size_t(nstats) * sizeof(uint64_t));
   if (!(ctx->haveTris && ctx->haveBsdfs && ctx->haveLights && ctx->haveCamera))
@@ -3442,11 +3519,12 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   P.sampleOffset = sample_offset, P.spp = spp;
   if (P.numItems == 0) return DMT_OK;
   uint32_t const ownedTiles = P.numItems;
+  if (sel) P.numItems = sel->count, P.tileList = sel->list, P.tileMask = sel->mask;  // (count > 0: checked by the caller)
   // BVH launches run as the megakernel unless the wavefront form (wavefront.hpp) is asked for: on the measured scenes
   // the megakernel is faster (1 M triangles: 489 vs 378 Msamples/s), so "automatic" means megakernel
   // (BVH masks without textures, blends or a light tree have a k_wf_shade* row)
   WfKernelFn const wfShade = kernelOf(kWfShadeKernels, stats6 ? F | kFeatStats : F);
-  bool const wavefront = ctx->bvhStrategy == 2 && wfShade != nullptr;
+  bool const wavefront = ctx->bvhStrategy == 2 && wfShade != nullptr && !sel;  // (adaptive rounds: always the megakernel)
   int const blocksPerCu = blocksPerCuOf(ctx, kernel);
   {  // fewer owned tiles than ~4 per resident wave: schedule row bands of the tiles instead of whole tiles
     uint32_t const waves = uint32_t(ctx->cuCount) * uint32_t(blocksPerCu) * 4u;
@@ -3639,10 +3717,63 @@ int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t c
   return ok && maxLeaf <= kBvhMaxLeafTris ? DMT_OK : DMT_ERR_STATE;
 }
 
-static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats);
+static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats,
+                      TileSelection const* sel);
 
 int dmt_render(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1) {
   return renderImpl(ctx, sample_offset, spp, x0, y0, x1, y1, nullptr, 0);
+}
+
+// Adaptive sampling: rounds of step_spp samples; before each round k_adaptive_mask decides which pixels go on (stopping rule
+// at adaptive_active) and lists the tiles that have any, and the round is an ordinary megakernel launch over those tiles.
+int dmt_render_adaptive(dmt_ctx* ctx, uint32_t min_spp, uint32_t max_spp, uint32_t step_spp, float threshold, int x0, int y0,
+                        int x1, int y1, uint32_t* rounds, uint64_t* samples) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (rounds) *rounds = 0;
+  if (samples) *samples = 0;
+  if (step_spp == 0 || max_spp == 0) return fail(ctx, DMT_ERR_INVALID, "dmt_render_adaptive: step_spp and max_spp must be positive");
+  if (max_spp > (1u << 24)) return fail(ctx, DMT_ERR_INVALID, "dmt_render_adaptive: max_spp above 2^24 (the sample count must stay exact in fp32)");
+  if (!std::isfinite(threshold) || threshold < 0.f) return fail(ctx, DMT_ERR_INVALID, "dmt_render_adaptive: threshold must be finite and >= 0");
+  if (!(ctx->haveTris && ctx->haveBsdfs && ctx->haveLights && ctx->haveCamera))
+    return fail(ctx, DMT_ERR_STATE, "dmt_render_adaptive: upload triangles, bsdfs, lights and set the camera first");
+  if (x0 < 0) x0 = 0;
+  if (y0 < 0) y0 = 0;
+  if (x1 > ctx->filmW) x1 = ctx->filmW;
+  if (y1 > ctx->filmH) y1 = ctx->filmH;
+  if (x1 <= x0 || y1 <= y0) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  AdaptiveArgs A{};
+  A.mean = ctx->d_mean, A.m2 = ctx->d_m2, A.width = ctx->filmW;
+  A.x0 = x0, A.y0 = y0, A.x1 = x1, A.y1 = y1;
+  A.tx0 = x0 / 8, A.ty0 = y0 / 8, A.rtx = (x1 + 7) / 8 - A.tx0;  // the tile grid of renderImpl
+  uint32_t const tiles = uint32_t(A.rtx) * uint32_t((y1 + 7) / 8 - A.ty0);
+  A.rank = ctx->rank, A.world = ctx->world;
+  A.owned = tiles > uint32_t(ctx->rank) ? (tiles - uint32_t(ctx->rank) + uint32_t(ctx->world) - 1) / uint32_t(ctx->world) : 0;
+  if (A.owned == 0) return DMT_OK;
+  A.minSpp = min_spp, A.maxSpp = max_spp, A.threshold = threshold;
+  size_t const filmTiles = size_t((ctx->filmW + 7) / 8) * size_t((ctx->filmH + 7) / 8);  // >= tiles of any region
+  HIP_TRY(ctx, ctx->d_adMask.reserve(filmTiles));
+  HIP_TRY(ctx, ctx->d_adList.reserve(filmTiles));
+  HIP_TRY(ctx, ctx->d_adCount.reserve(2));
+  A.mask = ctx->d_adMask.get(), A.list = ctx->d_adList.get(), A.counters = ctx->d_adCount.get();
+  for (uint32_t offset = 0; offset < max_spp;) {
+    A.offset = offset;
+    HIP_TRY(ctx, hipMemsetAsync(A.counters, 0, 2 * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(k_adaptive_mask, dim3((A.owned + 3u) / 4u), dim3(256), 0, ctx->stream, A);
+    HIP_TRY(ctx, hipGetLastError());
+    uint32_t h[2] = {0, 0};  // listed tiles, active pixels
+    HIP_TRY(ctx, hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int const rc = checkErrorFlag(ctx)) return rc;  // the previous round lost or duplicated a fold
+    if (h[0] == 0) break;
+    uint32_t const n = std::min(step_spp, max_spp - offset);
+    TileSelection const sel{A.list, A.mask, h[0]};
+    if (int const rc = renderImpl(ctx, offset, n, x0, y0, x1, y1, nullptr, 0, &sel)) return rc;
+    if (rounds) ++*rounds;
+    if (samples) *samples += uint64_t(h[1]) * n;
+    offset += n;
+  }
+  return DMT_OK;
 }
 
 int dmt_render_stats(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1,

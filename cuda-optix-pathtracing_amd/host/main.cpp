@@ -4,7 +4,8 @@
 //   * dmt-tracer (cli/CLIManager.cpp:11-36): --device|-d cpu|gpu, --scene|-s <file>, --out|-o <path>, --time|-t,
 //       --help|-h.  `--device cpu` is refused: this build has no CPU renderer (the CPU restatement used by the tests is test
 //       infrastructure and is never linked into the product).
-// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --light-tree, --light-tree-reference, --texture-filter, and --gpus <N>: N contexts, one per GPU
+// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --light-tree, --light-tree-reference, --texture-filter,
+// --adaptive <threshold> / --min-spp <N> (dmt_render_adaptive: --spp is the cap, --kspp the round), and --gpus <N>: N contexts, one per GPU
 // (ordinals 0..N-1), each rendering the interleaved 8x8 tiles j mod N == rank (dmt_set_partition) concurrently; the N
 // films are disjoint and summed on the host (x + 0: an exact gather).  bench.py's N-process RCCL path is the scalable
 // form of the same partition; --gpus is the single-process form for the CLI.
@@ -12,8 +13,10 @@
 // output-<spp>.png and output-<spp>_sqrt_mse.png next to the executable (or into --out).
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -38,6 +41,20 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   bool textureFilter = false; // --texture-filter: first-hit MIP / EWA filtering of image textures (DMT_TEXFILTER_REFERENCE)
   bool lightTreeRef = false; // --light-tree-reference: the reference's tree semantics, up to four lights per bounce (csrc/light_tree_ref.hpp)
   bool widthSet = false, heightSet = false, sppSet = false, depthSet = false;
+  bool adaptive = false;      // --adaptive <threshold>: adaptive sampling, --spp samples at most, rounds of --kspp
+  std::string adaptiveArg;
+  float threshold = 0.f;      // parsed from adaptiveArg by validate()
+  int minSpp = 0;             // --min-spp <N>: samples every pixel gets before the stopping rule applies
+  bool minSppSet = false;
+
+  // --adaptive's value: a finite, non-negative number and nothing else
+  static bool parseThreshold(std::string const& a, float& out) {
+    char* end = nullptr;
+    float const v = std::strtof(a.c_str(), &end);
+    if (a.empty() || end != a.c_str() + a.size() || !std::isfinite(v) || v < 0.f) return false;
+    out = v;
+    return true;
+  }
 
   std::string validate() const {  // host_utils.cuh:35-62
     if (width <= 0) return "invalid width: should be bigger than zero. got " + std::to_string(width);
@@ -51,6 +68,15 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (deviceKind != "cpu" && deviceKind != "gpu") return "--device: wrong argument is not allowed. (cpu or gpu, got " + deviceKind + ")";
     if (gpus < 1 || gpus > 64) return "invalid --gpus: expected 1..64, got " + std::to_string(gpus);
     if (device < 0) return "invalid --gpu-ordinal";
+    if (minSppSet && !adaptive) return "--min-spp needs --adaptive";
+    if (adaptive) {
+      float t = 0.f;
+      if (!parseThreshold(adaptiveArg, t)) return "invalid --adaptive: expected a finite threshold >= 0, got '" + adaptiveArg + "'";
+      if (minSpp < 0) return "invalid --min-spp: should not be negative. got " + std::to_string(minSpp);
+      if (minSpp > spp) return "invalid --min-spp: should not exceed spp. got " + std::to_string(minSpp) + " and spp " + std::to_string(spp);
+      if (spp > (1 << 24)) return "invalid spp: --adaptive allows at most 2^24 samples per pixel";
+      if (savePartial) return "--save-partial is not available with --adaptive";
+    }
     return "";
   }
 };
@@ -78,7 +104,11 @@ void printHelp() {
       "  --light-tree      -- pick the NEE light through a light BVH (flux x cosine / distance^2) instead of uniformly\n"
       "  --light-tree-reference -- the reference's light tree semantics: cones, adaptive cuts, up to four lights per bounce\n"
       "  --texture-filter  -- filter image textures at the camera ray's first hit (MIP levels / EWA by the pixel footprint)\n"
-      "                       instead of the level-0 bilinear lookup");
+      "                       instead of the level-0 bilinear lookup\n"
+      "  --adaptive <T>    -- Adaptive sampling: rounds of --kspp samples; a pixel stops at --spp samples, or once it has\n"
+      "                       --min-spp and the relative standard error of its mean is <= T.  Also writes\n"
+      "                       output-<spp>_spp.png, the samples each pixel received / spp\n"
+      "  --min-spp <N>     -- Samples every pixel receives before --adaptive may stop it (default 0)");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -95,6 +125,8 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--light-tree-reference") c.lightTreeRef = true;
     else if (a == "--texture-filter") c.textureFilter = true;
     else if (a == "--kspp" && more) c.kspp = std::atoi(argv[++i]);
+    else if (a == "--adaptive" && more) c.adaptive = true, c.adaptiveArg = argv[++i];
+    else if (a == "--min-spp" && more) c.minSpp = std::atoi(argv[++i]), c.minSppSet = true;
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -173,6 +205,7 @@ int main(int argc, char** argv) {
     printHelp();
     return 1;
   }
+  if (cfg.adaptive) Config::parseThreshold(cfg.adaptiveArg, cfg.threshold);
   std::printf("Parsed Configuration:\n - Width:     %d\n - Height:    %d\n - SPP:       %d\n - KSPP:      %d\n - Log Level: %s\n",
               cfg.width, cfg.height, cfg.spp, cfg.kspp, cfg.logLevel.c_str());
   bool const verbose = cfg.logLevel == "verbose";
@@ -229,7 +262,21 @@ int main(int argc, char** argv) {
   std::puts("Running HIP Kernel");
   double totalMs = 0.0;  // wall time of launch + sync, file writes excluded (main.cu:179-192)
   int launches = 0;
-  for (int sTot = 0; sTot < cfg.spp; sTot += cfg.kspp) {
+  uint64_t adaptiveSamples = 0;  // --adaptive: path samples traced over all GPUs
+  if (cfg.adaptive) {  // synchronous per context (one read-back per round), so the GPUs run their shares one after another
+    auto const t0 = std::chrono::steady_clock::now();
+    for (dmt_ctx* ctx : C.v) {
+      uint32_t rounds = 0;
+      uint64_t traced = 0;
+      if (dmt_render_adaptive(ctx, uint32_t(cfg.minSpp), uint32_t(cfg.spp), uint32_t(cfg.kspp), cfg.threshold, 0, 0, cfg.width,
+                              cfg.height, &rounds, &traced) != DMT_OK)
+        return fail(ctx, "dmt_render_adaptive");
+      if (dmt_sync(ctx) != DMT_OK) return fail(ctx, "dmt_sync");
+      launches = std::max(launches, int(rounds)), adaptiveSamples += traced;
+    }
+    totalMs += msSince(t0);
+  }
+  for (int sTot = 0; !cfg.adaptive && sTot < cfg.spp; sTot += cfg.kspp) {
     if (verbose) std::printf("Running HIP Kernel (%d)\n", sTot);
     auto const t0 = std::chrono::steady_clock::now();
     for (dmt_ctx* ctx : C.v)  // asynchronous: all GPUs run their share of this batch concurrently
@@ -241,9 +288,22 @@ int main(int argc, char** argv) {
     if (cfg.savePartial && !writeOut(sTot + cfg.kspp)) return 1;
   }
   if (!cfg.savePartial && !writeOut(cfg.spp)) return 1;
-  double const samples = double(pixels) * double(launches) * double(cfg.kspp);
+  if (cfg.adaptive) {  // grey map of the samples each pixel received, N / spp
+    auto const t1 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> grey(3 * pixels);
+    for (size_t i = 0; i < pixels; ++i)
+      grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = uint8_t(std::lround(255.0 * std::min(1.0, double(m2[4 * i + 3]) / double(cfg.spp))));
+    std::string err;
+    if (!dmt_host::writePngRgb8(dir + "/output-" + std::to_string(cfg.spp) + "_spp.png", grey.data(), uint32_t(cfg.width),
+                                uint32_t(cfg.height), &err)) {
+      std::fprintf(stderr, "%s\n", err.c_str());
+      return 1;
+    }
+    writeMs += msSince(t1);
+  }
+  double const samples = cfg.adaptive ? double(adaptiveSamples) : double(pixels) * double(launches) * double(cfg.kspp);
   std::printf("Done! Total Execution Time(excl write file): %llu ms | Average Execution per Kernel launch (%d spp): %llu ms | %.2f Msamples/s\n",
-              static_cast<unsigned long long>(totalMs), cfg.kspp, static_cast<unsigned long long>(totalMs / launches),
+              static_cast<unsigned long long>(totalMs), cfg.kspp, static_cast<unsigned long long>(totalMs / std::max(launches, 1)),
               samples / (totalMs * 1e3));
   if (cfg.timeReport) {  // --time: execution times of the key operations (cli/CLIManager.cpp:27-31)
     double kernelMs = 0.0;
@@ -259,6 +319,9 @@ int main(int argc, char** argv) {
                 " - film download%s:   %10.3f ms\n - PNG encode + write:       %10.3f ms\n",
                 loadMs, cfg.bvh ? " + BVH build" : "            ", uploadMs, cfg.gpus, cfg.gpus > 1 ? "s" : "", totalMs, launches, cfg.kspp,
                 kernelMs, static_cast<unsigned long long>(n), cfg.gpus > 1 ? " + gather" : "         ", downloadMs, writeMs);
+    if (cfg.adaptive)
+      std::printf(" - adaptive sampling:         %d round(s), %llu samples traced (%.2f spp on average, cap %d)\n", launches,
+                  static_cast<unsigned long long>(adaptiveSamples), double(adaptiveSamples) / double(pixels), cfg.spp);
   }
   std::puts("Cleanup...");
   return 0;

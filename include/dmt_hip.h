@@ -193,6 +193,18 @@ int dmt_download_film(dmt_ctx* ctx, float* mean4, float* m24);
  * [x0,x1) x [y0,y1) are traced and folded into the film (Welford, in sample order).
  * Asynchronous on the context's stream. */
 int dmt_render(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1);
+/* Adaptive sampling: rounds of step_spp samples from sample 0; before each round the film decides which pixels of
+ * [x0,x1) x [y0,y1) owned by this partition go on.  Rule (fp32 on the device): with N = M2.w,
+ *   err = sqrt((M2.x + M2.y + M2.z) / (N (N - 1))) / max(mean.x + mean.y + mean.z, 1e-3)   (+inf for N < 2)
+ * and a pixel takes part in the round starting at sample `offset` iff
+ *   N == offset && N < max_spp && (N < min_spp || err > threshold).
+ * A pixel that stopped at N samples is bit-identical to the same pixel of a uniform N-spp film.  Every round runs the
+ * megakernel (also under dmt_set_bvh_strategy 2) and counts in dmt_kernel_time.  Synchronous (one 8-byte read-back per
+ * round).  *rounds = rounds launched, *samples = path samples traced (either may be NULL).  DMT_ERR_INVALID for
+ * step_spp == 0, max_spp == 0, max_spp > 2^24 or a negative or non-finite threshold.  Call dmt_film_clear first for a
+ * fresh image. */
+int dmt_render_adaptive(dmt_ctx* ctx, uint32_t min_spp, uint32_t max_spp, uint32_t step_spp, float threshold,
+                        int x0, int y0, int x1, int y1, uint32_t* rounds, uint64_t* samples);
 /* Same pass through the counting build of the BVH kernel (synchronous, not for timing): stats6 =
  * {samples, closest-hit rays, shadow rays, BVH node visits, triangle tests, bounces}.  The film is
  * updated exactly as by dmt_render. */
