@@ -58,7 +58,22 @@ EXPORTED_SYMBOLS = [
     "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_light", "dmt_test_half",
     "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
     "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
+    "dmt_render_aovs", "dmt_upload_aovs", "dmt_download_aovs", "dmt_denoise_defaults", "dmt_denoise",
 ]
+
+
+class DenoiseParams(C.Structure):
+    """dmt_denoise_params (include/dmt_hip.h)"""
+    _fields_ = [("iterations", C.c_int32), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_luminance", C.c_float)]
+
+
+def denoise_defaults():
+    """dmt_denoise_defaults() as a dict: iterations, sigma_normal, sigma_position, sigma_albedo, sigma_luminance."""
+    lib = load_library()
+    lib.dmt_denoise_defaults.restype = DenoiseParams
+    p = lib.dmt_denoise_defaults()
+    return {name: getattr(p, name) for name, _ in DenoiseParams._fields_}
 
 # dmt_set_texture_filter modes (include/dmt_hip.h)
 TEXFILTER_LEVEL0 = 0
@@ -213,6 +228,8 @@ class Renderer:
             msg = self._lib.dmt_last_error(None)
             raise DmtError(f"dmt_ctx_create failed ({rc}): {msg.decode() if msg else ''}")
         self.width = self.height = 0
+        self._aov_shape = None      # (height, width) of the AOVs on the device
+        self.denoise_ms = 0.0       # HIP-event time of the last denoise()
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -399,6 +416,49 @@ class Renderer:
         keys = ["samples", "closest_rays", "shadow_rays", "node_visits", "tri_tests", "bounces", "it_node", "it_leaf",
                 "it_shade", "it_outer", "it_prep", "lanes_leaf", "lanes_shade", "lanes_prep", "dead_nodes", "overflow_pushes"]
         return dict(zip(keys, (int(v) for v in out)))
+
+    # ---- denoiser -----------------------------------------------------------
+    def render_aovs(self, aov_spp=4):
+        """Feature pass (dmt_render_aovs): albedo / normal / position planes from camera samples 0 .. aov_spp-1 of every
+        pixel, kept on the device for denoise().  Asynchronous."""
+        self._check(self._lib.dmt_render_aovs(self._ctx, C.c_uint32(aov_spp)), "dmt_render_aovs")
+        self._aov_shape = (self.height, self.width)
+
+    def upload_aovs(self, albedo, normal, position):
+        """Host planes (H x W x 4 each, layout of dmt_render_aovs) as the context's AOVs."""
+        a, n, p = _f32(albedo), _f32(normal), _f32(position)
+        assert a.ndim == 3 and a.shape[2] == 4 and a.shape == n.shape == p.shape
+        h, w = a.shape[:2]
+        self._check(self._lib.dmt_upload_aovs(self._ctx, _p(a), _p(n), _p(p), int(w), int(h)), "dmt_upload_aovs")
+        self._aov_shape = (h, w)
+
+    def download_aovs(self):
+        """(albedo, normal, position), each H x W x 4 float32."""
+        h, w = self._aov_shape or (self.height, self.width)
+        out = [np.zeros((h, w, 4), np.float32) for _ in range(3)]
+        self._check(self._lib.dmt_download_aovs(self._ctx, *[_p(x) for x in out]), "dmt_download_aovs")
+        return tuple(out)
+
+    def denoise(self, params=None, film=None):
+        """dmt_denoise: the film (the context's own, or `film` = (mean, m2) host arrays of the camera's size) denoised with
+        the context's AOVs -> H x W x 4 float32 (w = 1).  `params`: a dict overriding denoise_defaults().  Synchronous;
+        the kernels' HIP-event time lands in self.denoise_ms."""
+        p = denoise_defaults()
+        unknown = set(params or {}) - set(p)
+        if unknown:
+            raise ValueError(f"unknown denoise parameters {sorted(unknown)}")
+        p.update(params or {})
+        cp = DenoiseParams(int(p["iterations"]), float(p["sigma_normal"]), float(p["sigma_position"]), float(p["sigma_albedo"]),
+                           float(p["sigma_luminance"]))
+        mean = m2 = None
+        if film is not None:
+            mean, m2 = _f32(film[0]), _f32(film[1])
+            assert mean.shape == m2.shape == (self.height, self.width, 4)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        ms = C.c_float()
+        self._check(self._lib.dmt_denoise(self._ctx, C.byref(cp), _p(mean), _p(m2), _p(out), C.byref(ms)), "dmt_denoise")
+        self.denoise_ms = ms.value
+        return out
 
     def sync(self):
         self._check(self._lib.dmt_sync(self._ctx), "dmt_sync")

@@ -2310,6 +2310,219 @@ __global__ void k_test_closest(RenderParams P, bool useBvh, int n, float const* 
   if (alive) tri[i] = best, tOut[i] = bt;
 }
 
+// ---------------------------------------------------------------------------------------------
+// denoiser (dmt_render_aovs, dmt_denoise)
+// ---------------------------------------------------------------------------------------------
+// Feature pass: camera samples 0 .. aovSpp-1 of every pixel of the frame, the film's own camera rays, closest hit as
+// k_test_closest finds it.  Per pixel, summed in sample order over the samples whose ray hit a triangle ("hits"):
+//   albedo   = (sum W / aovSpp, hits / aovSpp)     W = the record's fp16 weight after the level-0 texture patch;
+//                                                   BS_GGX_BLEND: (1 - mix) W_diel + mix W_cond, mix clamped to [0, 1]
+//   normal   = (normalize(sum ns) or 0 when |sum| < 1e-6, 0)   ns = hit_finish's face-forwarded or the normal-mapped normal
+//   position = (sum pos / hits, sum t / hits), 0 without hits
+struct AovArgs {
+  float4* albedo;
+  float4* normal;
+  float4* position;
+  int width;
+  uint32_t pixels, aovSpp;
+  bool useBvh;
+};
+DMT_DEV f3 rec_weight(Rec32 const& r) { return mk3(h2f(lo16(r.w[0])), h2f(hi16(r.w[0])), h2f(lo16(r.w[1]))); }
+// The part of apply_material_textures (level 0) that W and the shading normal depend on: the albedo patch of Oren-Nayar
+// records and the normal map, same expressions.  Its roughness patch is left out: nothing here reads it, and patching a
+// word chosen by the record's type kept the record in scratch memory.
+DMT_DEV f3 aov_textures(KArgs k, Rec32& rec, uint32_t matId, int tri, float bu, float bv, f3 ng) {
+  KArgs const ka = kargs(k);
+  uint32_t const* const m = ka->matTex + 4 * matId;
+  int32_t const texD = int32_t(m[0]), texN = int32_t(m[2]);
+  if (texD < 0 && texN < 0) return ng;
+  float const* const uv = ka->triUv + 6 * size_t(tri);
+  float const w0 = 1.f - bu - bv;
+  float const s = w0 * uv[0] + bu * uv[2] + bv * uv[4], t = w0 * uv[1] + bu * uv[3] + bv * uv[5];
+  if (texD >= 0 && hi16(rec.w[1]) == BS_OREN) {
+    f3 const c = tex_lookup<false>(k, texD, s, t, false, TexDiff{});
+    rec.w[0] = f2h(fmaxf(0.f, fminf(c.x, 1.f))) | (f2h(fmaxf(0.f, fminf(c.y, 1.f))) << 16);
+    rec.w[1] = (rec.w[1] & 0xFFFF0000u) | f2h(fmaxf(0.f, fminf(c.z, 1.f)));
+  }
+  if (texN < 0) return ng;
+  f3 n = tex_lookup<false>(k, texN, s, t, true, TexDiff{});
+  auto quant = [](float v) { return float(int(v * 1023.f + 0.5f)) / 1023.f; };
+  n = normalize(mk3(quant(n.x), quant(n.y), quant(n.z)));
+  f3 tx, ty;
+  gram_schmidt(ng, tx, ty);
+  f3 const ns = tx * n.x + ty * n.y + ng * n.z;
+  float const l2 = dot(ns, ns);
+  return (l2 > 0.f && l2 < kInf) ? ns / sqrtf(l2) : ng;
+}
+// W and the shading normal at a camera ray's hit, as path_shade sees them at depth 0 (level-0 texture lookups)
+DMT_DEV void aov_material(KArgs k, Hit const& hit, int tri, float bu, float bv, f3& W, f3& ns) {
+  SceneView const sc = load_scene(k);
+  bool const tex = kargs(k)->matTex != nullptr;
+  Rec32 rec = sc.bsdfs[hit.matId];
+  ns = hit.normal;
+  if (tex) ns = aov_textures(k, rec, hit.matId, tri, bu, bv, hit.normal);
+  if (hi16(rec.w[1]) == BS_GGX_BLEND) {  // GGX: the albedo patch never applies, to either record
+    float const mix = fminf(fmaxf(blend_metallic(k, rec, hit.matId, tri, bu, bv), 0.f), 1.f);
+    f3 Wd = rec_weight(rec);
+    Wd.x = 1.f;  // the dielectric half keeps the metallic fraction where its W.x would be (makeGGXBlendDielectric)
+    W = Wd * (1.f - mix) + rec_weight(sc.bsdfs[hit.matId + 1u]) * mix;
+    return;
+  }
+  W = rec_weight(rec);
+}
+// one lane per pixel, row-major; whole waves stride over the frame (the BVH overflow stack is sized by the launch)
+__global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
+  KArgs const k = kargs_base();
+  if (!A.useBvh) cull_stage(k);
+  uint32_t const lane = threadIdx.x & 63u, gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t const waves = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t w = gtid >> 6; w * 64u < A.pixels; w += waves) {  // wave-uniform trip count
+    uint32_t const i = w * 64u + lane;
+    bool const alive = i < A.pixels;
+    int const px = alive ? int(i % uint32_t(A.width)) : 0, py = alive ? int(i / uint32_t(A.width)) : 0;
+    int32_t const base = halton_pixel_base(load_cold_args(k).sp, px, py);
+    f3 sumW = mk3(0, 0, 0), sumN = mk3(0, 0, 0), sumP = mk3(0, 0, 0);
+    float sumT = 0.f;
+    uint32_t hits = 0;
+    for (uint32_t s = 0; s < A.aovSpp; ++s) {
+      PathState st{};
+      // camera and sampler re-read from the kernel arguments at the point of use: held in SGPRs across the triangle pass
+      // they would spill (see kargs)
+      ColdArgs const c = load_cold_args(k);
+      Ray const r = camera_ray(c.cam, c.sp, px, py, base + int32_t(s) * (c.sp.scale0 * c.sp.scale1));
+      set_ray(st, r.o, r.d);
+      st.active = alive;
+      int best;
+      float bu, bv;
+      bool occluded;
+      if (A.useBvh)
+        trace_pair_bvh(k, st, alive, false, gtid, best, bu, bv, occluded);
+      else
+        trace_pair_brute(k, st, alive, false, best, bu, bv, occluded);
+      if (alive && best >= 0) {
+        TriS const T = load_tri(to_const_as(load_scene(k).tris), uint32_t(best));
+        float const t = mt_pair(T, st.rp).t.x;  // as k_test_closest reports it
+        Hit const hit = hit_finish(load_scene(k).post[best], bu, bv, r.d);
+        f3 W, ns;
+        aov_material(k, hit, best, bu, bv, W, ns);
+        sumW = sumW + W, sumN = sumN + ns, sumP = sumP + hit.pos, sumT += t;
+        ++hits;
+      }
+    }
+    if (alive) {
+      float const inv = 1.f / float(A.aovSpp);
+      A.albedo[i] = make_float4(sumW.x * inv, sumW.y * inv, sumW.z * inv, float(hits) * inv);
+      float const len = sqrtf(dot(sumN, sumN));
+      f3 const n = len >= 1e-6f ? sumN / len : mk3(0, 0, 0);
+      A.normal[i] = make_float4(n.x, n.y, n.z, 0.f);
+      float const h = float(hits);
+      A.position[i] = hits ? make_float4(sumP.x / h, sumP.y / h, sumP.z / h, sumT / h) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+}
+
+// A-trous passes (spatial SVGF).  Colour and variance travel together as one float4 (rgb, v) per pixel, ping-ponged
+// between passes; the AOVs stay fp32 (no packing), so tests/denoise_ref.py restates the filter on the same numbers.
+struct DenoiseArgs {
+  float4 const* mean;      // k_denoise_init: the source film
+  float4 const* m2;
+  float4 const* albedo;    // k_atrous: the AOVs
+  float4 const* normal;
+  float4 const* position;
+  float4 const* src;       // (rgb, variance) of pass i
+  float4* dst;             // of pass i + 1 (k_denoise_init: pass 0)
+  uint32_t* bad;           // k_denoise_init: pixels with N < 2 or a non-finite mean / M2
+  int width, height;
+  float theta;             // sensor height / (focal length * image height): one pixel's angle
+  float sigmaN, sigmaX, sigmaA, sigmaL;
+  float tapDist[25];       // s * sqrt(dx^2 + dy^2) of tap (dx, dy) at [5 (dy + 2) + dx + 2]
+  int step;                // s = 2^i
+};
+// c0 = mean.xyz, v0 = (M2.x + M2.y + M2.z) / (3 N (N - 1)); counts the pixels the filter refuses
+__global__ void __launch_bounds__(256) k_denoise_init(DenoiseArgs A) {
+#pragma clang fp contract(off)
+  uint32_t const i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t const pixels = uint32_t(A.width) * uint32_t(A.height);
+  bool badPx = false;
+  if (i < pixels) {
+    float4 const m = A.mean[i], v = A.m2[i];
+    float const N = v.w;
+    badPx = !(N >= 2.f) || !__builtin_isfinite(N) || !__builtin_isfinite(m.x) || !__builtin_isfinite(m.y) ||
+            !__builtin_isfinite(m.z) || !__builtin_isfinite(v.x) || !__builtin_isfinite(v.y) || !__builtin_isfinite(v.z);
+    float const var = ((v.x + v.y) + v.z) / ((3.f * N) * (N - 1.f));
+    A.dst[i] = make_float4(m.x, m.y, m.z, var);
+  }
+  unsigned long long const b = __ballot(badPx);
+  if ((threadIdx.x & 63u) == 0u && b != 0ull) atomicAdd(A.bad, uint32_t(__popcll(b)));
+}
+DMT_DEV float luminance(float4 c) {
+#pragma clang fp contract(off)
+  return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+}
+// one pass at step s: block = 64 x 4 pixels, a wave = 64 pixels of one row (tap loads coalesce); centre AOVs loaded once
+__global__ void __launch_bounds__(256) k_atrous(DenoiseArgs A) {
+#pragma clang fp contract(off)
+  int const px = int(blockIdx.x) * 64 + int(threadIdx.x & 63u), py = int(blockIdx.y) * 4 + int(threadIdx.x >> 6);
+  if (px >= A.width || py >= A.height) return;
+  size_t const W = size_t(A.width);
+  size_t const p = size_t(py) * W + size_t(px);
+  float4 const cp = A.src[p];
+  float4 const ap = A.albedo[p];
+  if (!(ap.w > 0.f)) {  // background only: passes through and feeds no one
+    A.dst[p] = cp;
+    return;
+  }
+  float4 const np = A.normal[p], xp = A.position[p];
+  float gs = 0.f, gw = 0.f;  // 3x3 [1/4, 1/2, 1/4] blur of the variance, normalised over the in-image taps
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      int const qx = px + dx, qy = py + dy;
+      if (qx < 0 || qx >= A.width || qy < 0 || qy >= A.height) continue;
+      float const kk = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+      gs = gs + kk * A.src[size_t(qy) * W + size_t(qx)].w;
+      gw = gw + kk;
+    }
+  }
+  float const lp = luminance(cp);
+  float const lden = A.sigmaL * sqrtf(gs / gw) + 1e-10f;
+  float const xden = (A.sigmaX * xp.w) * A.theta;
+  float const a2 = A.sigmaA * A.sigmaA;
+  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      int const qx = px + dx * A.step, qy = py + dy * A.step;
+      if (qx < 0 || qx >= A.width || qy < 0 || qy >= A.height) continue;
+      float const hx = dx == 0 ? 0.375f : (dx == 1 || dx == -1) ? 0.25f : 0.0625f;
+      float const hy = dy == 0 ? 0.375f : (dy == 1 || dy == -1) ? 0.25f : 0.0625f;
+      float w = hx * hy;
+      float4 cq = cp;
+      if (dx != 0 || dy != 0) {
+        size_t const q = size_t(qy) * W + size_t(qx);
+        float4 const aq = A.albedo[q];
+        if (!(aq.w > 0.f)) continue;
+        float4 const nq = A.normal[q], xq = A.position[q];
+        cq = A.src[q];
+        float const nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+        float const wn = powf(fmaxf(0.f, nd), A.sigmaN);
+        float const pd = fabsf((np.x * (xq.x - xp.x) + np.y * (xq.y - xp.y)) + np.z * (xq.z - xp.z));
+        float const wx = expf(-pd / (xden * A.tapDist[5 * (dy + 2) + dx + 2]));
+        float const ar = ap.x - aq.x, ag = ap.y - aq.y, ab = ap.z - aq.z;
+        float const wa = expf(-((ar * ar + ag * ag) + ab * ab) / a2);
+        float const wl = expf(-fabsf(lp - luminance(cq)) / lden);
+        w = (((w * wn) * wx) * wa) * wl;
+      }
+      sw = sw + w;
+      sr = sr + w * cq.x, sg = sg + w * cq.y, sb = sb + w * cq.z;
+      sv = sv + (w * w) * cq.w;
+    }
+  }
+  A.dst[p] = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -2444,7 +2657,13 @@ struct dmt_ctx {
   DevBuf<unsigned long long> d_adMask;
   DevBuf<uint32_t> d_adList;
   DevBuf<uint32_t> d_adCount;
-  uint32_t chunkSpp = 0;           // samples per work item, 0 = automatic
+  // denoiser (dmt_render_aovs / dmt_upload_aovs, dmt_denoise): the three feature planes and their size (0 x 0: none); the
+  // filter's scratch: a copy of a host film (mean, then M2), two (rgb, variance) planes, the count of refused pixels
+  DevBuf<float4> d_aovAlbedo, d_aovNormal, d_aovPos;
+  int aovW = 0, aovH = 0;
+  DevBuf<float4> d_dnFilm, d_dnCv;
+  DevBuf<uint32_t> d_dnBad;
+  uint32_t chunkSpp = 0;          // samples per work item, 0 = automatic
   int subShift = -1;               // row bands per tile (log2); -1 = choose per launch
   int maxDepth = 32;
   int accel = DMT_ACCEL_BRUTE_FORCE;
@@ -3027,6 +3246,14 @@ int finishTest(dmt_ctx* ctx) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return DMT_OK;
 }
+
+struct EventPair {  // two HIP events, destroyed on every exit path (dmt_denoise)
+  hipEvent_t e[2] = {nullptr, nullptr};
+  ~EventPair() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
 
 }  // namespace
 
@@ -4277,6 +4504,145 @@ int dmt_test_closest_hit(dmt_ctx* ctx, int nrays, const float* o3, const float* 
   if (int const rc = finishTest(ctx)) return rc;
   HIP_TRY(ctx, hipMemcpy(tri_index, di.get(), size_t(nrays) * 4, hipMemcpyDeviceToHost));
   HIP_TRY(ctx, hipMemcpy(t, dt.get(), size_t(nrays) * 4, hipMemcpyDeviceToHost));
+  return DMT_OK;
+}
+
+// ---- denoiser ------------------------------------------------------------------
+dmt_denoise_params dmt_denoise_defaults(void) {
+  dmt_denoise_params p;
+  p.iterations = 4, p.sigma_normal = 128.f, p.sigma_position = 1.f, p.sigma_albedo = 0.1f, p.sigma_luminance = 32.f;
+  return p;
+}
+
+int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (aov_spp == 0 || aov_spp > 65536u) return fail(ctx, DMT_ERR_INVALID, "dmt_render_aovs: aov_spp must be 1 .. 65536");
+  if (!(ctx->haveTris && ctx->haveBsdfs && ctx->haveCamera))
+    return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: upload triangles, bsdfs and set the camera first");
+  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
+    return fail(ctx, DMT_ERR_INVALID, "dmt_render_aovs: material index outside the BSDF array");
+  if (ctx->texCount > 0 && (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount))
+    return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
+  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
+  if (useBvh && !ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: BVH not built");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
+  ctx->aovW = ctx->aovH = 0;  // no AOVs unless this call succeeds
+  HIP_TRY(ctx, ctx->d_aovAlbedo.reserve(pixels));
+  HIP_TRY(ctx, ctx->d_aovNormal.reserve(pixels));
+  HIP_TRY(ctx, ctx->d_aovPos.reserve(pixels));
+  // a grid of a few 256-lane blocks per CU strides over the frame: the BVH overflow stack is sized by the launch's lanes
+  size_t const blocks = std::min((pixels + 255) / 256, size_t(std::max(ctx->cuCount, 1)) * 8);
+  size_t const threads = blocks * 256;
+  if (useBvh) HIP_TRY(ctx, reserveOverflow(ctx, threads));
+  AovArgs A{};
+  A.albedo = ctx->d_aovAlbedo.get(), A.normal = ctx->d_aovNormal.get(), A.position = ctx->d_aovPos.get();
+  A.width = ctx->filmW, A.pixels = uint32_t(pixels), A.aovSpp = aov_spp, A.useBvh = useBvh;
+  hipLaunchKernelGGL(k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, baseParams(ctx, threads), A);
+  HIP_TRY(ctx, hipGetLastError());
+  ctx->aovW = ctx->filmW, ctx->aovH = ctx->filmH;
+  return DMT_OK;
+}
+
+int dmt_upload_aovs(dmt_ctx* ctx, const float* albedo4, const float* normal4, const float* position4, int width, int height) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!albedo4 || !normal4 || !position4 || width <= 0 || height <= 0)
+    return fail(ctx, DMT_ERR_INVALID, "dmt_upload_aovs: three planes of a positive size");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a feature pass in flight writes the same planes
+  size_t const pixels = size_t(width) * size_t(height);
+  ctx->aovW = ctx->aovH = 0;
+  HIP_TRY(ctx, ctx->d_aovAlbedo.assign(albedo4, pixels));
+  HIP_TRY(ctx, ctx->d_aovNormal.assign(normal4, pixels));
+  HIP_TRY(ctx, ctx->d_aovPos.assign(position4, pixels));
+  ctx->aovW = width, ctx->aovH = height;
+  return DMT_OK;
+}
+
+int dmt_download_aovs(dmt_ctx* ctx, float* albedo4, float* normal4, float* position4) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (ctx->aovW == 0) return fail(ctx, DMT_ERR_STATE, "dmt_download_aovs: no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  size_t const bytes = size_t(ctx->aovW) * size_t(ctx->aovH) * sizeof(float4);
+  if (albedo4) HIP_TRY(ctx, hipMemcpy(albedo4, ctx->d_aovAlbedo.get(), bytes, hipMemcpyDeviceToHost));
+  if (normal4) HIP_TRY(ctx, hipMemcpy(normal4, ctx->d_aovNormal.get(), bytes, hipMemcpyDeviceToHost));
+  if (position4) HIP_TRY(ctx, hipMemcpy(position4, ctx->d_aovPos.get(), bytes, hipMemcpyDeviceToHost));
+  return DMT_OK;
+}
+
+// k_denoise_init (validation + pass-0 planes), then `iterations` k_atrous passes ping-ponging between two planes
+int dmt_denoise(dmt_ctx* ctx, const dmt_denoise_params* params, const float* mean4, const float* m24, float* out4, float* kernel_ms) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (kernel_ms) *kernel_ms = 0.f;
+  dmt_denoise_params const p = params ? *params : dmt_denoise_defaults();
+  if (!out4 || (mean4 == nullptr) != (m24 == nullptr))
+    return fail(ctx, DMT_ERR_INVALID, "dmt_denoise: out4 is required, and mean4 / m24 come both or not at all");
+  if (p.iterations < 0 || p.iterations > 10) return fail(ctx, DMT_ERR_INVALID, "dmt_denoise: iterations must be 0 .. 10");
+  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+  if (!positive(p.sigma_normal) || !positive(p.sigma_position) || !positive(p.sigma_albedo) || !positive(p.sigma_luminance))
+    return fail(ctx, DMT_ERR_INVALID, "dmt_denoise: every sigma must be finite and > 0");
+  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_denoise: set the camera first");
+  if (ctx->aovW == 0) return fail(ctx, DMT_ERR_STATE, "dmt_denoise: no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
+  if (ctx->aovW != ctx->filmW || ctx->aovH != ctx->filmH) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "dmt_denoise: the AOVs are %d x %d, the film %d x %d", ctx->aovW, ctx->aovH, ctx->filmW, ctx->filmH);
+    return fail(ctx, DMT_ERR_STATE, msg);
+  }
+  if (!mean4 && !ctx->d_mean) return fail(ctx, DMT_ERR_STATE, "dmt_denoise: no film");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
+  float4 const* mean = ctx->d_mean;
+  float4 const* m2 = ctx->d_m2;
+  if (mean4) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, ctx->d_dnFilm.reserve(2 * pixels));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_dnFilm.get(), mean4, pixels * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_dnFilm.get() + pixels, m24, pixels * sizeof(float4), hipMemcpyHostToDevice));
+    mean = ctx->d_dnFilm.get(), m2 = ctx->d_dnFilm.get() + pixels;
+  }
+  HIP_TRY(ctx, ctx->d_dnCv.reserve(2 * pixels));
+  HIP_TRY(ctx, ctx->d_dnBad.reserve(1));
+  float4* const cv[2] = {ctx->d_dnCv.get(), ctx->d_dnCv.get() + pixels};
+  DenoiseArgs A{};
+  A.mean = mean, A.m2 = m2, A.albedo = ctx->d_aovAlbedo.get(), A.normal = ctx->d_aovNormal.get(), A.position = ctx->d_aovPos.get();
+  A.bad = ctx->d_dnBad.get(), A.width = ctx->filmW, A.height = ctx->filmH;
+  A.theta = ctx->cam.sensor_size / (ctx->cam.focal_length * float(ctx->cam.height));
+  A.sigmaN = p.sigma_normal, A.sigmaX = p.sigma_position, A.sigmaA = p.sigma_albedo, A.sigmaL = p.sigma_luminance;
+  EventPair ev;
+  HIP_TRY(ctx, hipEventCreate(&ev.e[0]));
+  HIP_TRY(ctx, hipEventCreate(&ev.e[1]));
+  HIP_TRY(ctx, hipMemsetAsync(A.bad, 0, sizeof(uint32_t), ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
+  A.dst = cv[0];
+  hipLaunchKernelGGL(k_denoise_init, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, ctx->stream, A);
+  HIP_TRY(ctx, hipGetLastError());
+  dim3 const grid(uint32_t((ctx->filmW + 63) / 64), uint32_t((ctx->filmH + 3) / 4));
+  for (int i = 0; i < p.iterations; ++i) {
+    A.src = cv[i & 1], A.dst = cv[(i + 1) & 1], A.step = 1 << i;
+    for (int dy = -2; dy <= 2; ++dy)
+      for (int dx = -2; dx <= 2; ++dx) A.tapDist[5 * (dy + 2) + dx + 2] = float(A.step) * std::sqrt(float(dx * dx + dy * dy));
+    hipLaunchKernelGGL(k_atrous, grid, dim3(256), 0, ctx->stream, A);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
+  uint32_t bad = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&bad, A.bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (!mean4)
+    if (int const rc = checkErrorFlag(ctx)) return rc;
+  if (bad) {
+    char msg[400];
+    snprintf(msg, sizeof(msg), "dmt_denoise: %u pixel(s) have fewer than 2 samples or a non-finite mean / M2%s", bad,
+             !mean4 && ctx->world > 1 ? " (this context renders only the tiles of its dmt_set_partition rank: combine the ranks' "
+                                        "films and pass the combined film as mean4 / m24)" : "");
+    return fail(ctx, DMT_ERR_STATE, msg);
+  }
+  float ms = 0.f;
+  HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  if (kernel_ms) *kernel_ms = ms;
+  HIP_TRY(ctx, hipMemcpy(out4, cv[p.iterations & 1], pixels * sizeof(float4), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < pixels; ++i) out4[4 * i + 3] = 1.f;
   return DMT_OK;
 }
 

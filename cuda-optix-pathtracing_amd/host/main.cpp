@@ -46,6 +46,9 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   float threshold = 0.f;      // parsed from adaptiveArg by validate()
   int minSpp = 0;             // --min-spp <N>: samples every pixel gets before the stopping rule applies
   bool minSppSet = false;
+  bool denoise = false;       // --denoise: also write output-<spp>_denoised.png (dmt_render_aovs + dmt_denoise)
+  int aovSpp = 4;             // --aov-spp <N>: camera samples per pixel of the feature buffers
+  bool aovSppSet = false;
 
   // --adaptive's value: a finite, non-negative number and nothing else
   static bool parseThreshold(std::string const& a, float& out) {
@@ -77,6 +80,8 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
       if (spp > (1 << 24)) return "invalid spp: --adaptive allows at most 2^24 samples per pixel";
       if (savePartial) return "--save-partial is not available with --adaptive";
     }
+    if (aovSppSet && !denoise) return "--aov-spp needs --denoise";
+    if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
   }
 };
@@ -108,7 +113,10 @@ void printHelp() {
       "  --adaptive <T>    -- Adaptive sampling: rounds of --kspp samples; a pixel stops at --spp samples, or once it has\n"
       "                       --min-spp and the relative standard error of its mean is <= T.  Also writes\n"
       "                       output-<spp>_spp.png, the samples each pixel received / spp\n"
-      "  --min-spp <N>     -- Samples every pixel receives before --adaptive may stop it (default 0)");
+      "  --min-spp <N>     -- Samples every pixel receives before --adaptive may stop it (default 0)\n"
+      "  --denoise         -- Also write output-<spp>_denoised.png: the film through an a-trous filter guided by its variance\n"
+      "                       and first-hit albedo / normal / position buffers (every other output stays as without it)\n"
+      "  --aov-spp <N>     -- Camera samples per pixel of those buffers (default 4)");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -127,6 +135,8 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--kspp" && more) c.kspp = std::atoi(argv[++i]);
     else if (a == "--adaptive" && more) c.adaptive = true, c.adaptiveArg = argv[++i];
     else if (a == "--min-spp" && more) c.minSpp = std::atoi(argv[++i]), c.minSppSet = true;
+    else if (a == "--denoise") c.denoise = true;
+    else if (a == "--aov-spp" && more) c.aovSpp = std::atoi(argv[++i]), c.aovSppSet = true;
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -236,7 +246,9 @@ int main(int argc, char** argv) {
   size_t const pixels = size_t(cfg.width) * size_t(cfg.height);
   std::vector<float> mean(4 * pixels), m2(4 * pixels), pm, pm2;
   double downloadMs = 0.0, writeMs = 0.0;
+  int lastSamples = 0;  // the <spp> of the last output-<spp>.png
   auto writeOut = [&](int samples) {
+    lastSamples = samples;
     auto const t0 = std::chrono::steady_clock::now();
     if (dmt_download_film(C.v[0], mean.data(), m2.data()) != DMT_OK) return fail(C.v[0], "dmt_download_film"), false;
     if (cfg.gpus > 1) {  // disjoint tile sets over zero-initialised frames: the sum is an exact gather
@@ -301,6 +313,28 @@ int main(int argc, char** argv) {
     }
     writeMs += msSince(t1);
   }
+  double aovMs = 0.0, denoiseMs = 0.0;
+  float denoiseKernelMs = 0.f;
+  if (cfg.denoise) {  // feature buffers on the first context (they cover the whole frame), filter on the combined host film
+    auto const t0 = std::chrono::steady_clock::now();
+    if (dmt_render_aovs(C.v[0], uint32_t(cfg.aovSpp)) != DMT_OK) return fail(C.v[0], "dmt_render_aovs");
+    if (dmt_sync(C.v[0]) != DMT_OK) return fail(C.v[0], "dmt_sync");
+    aovMs = msSince(t0);
+    auto const t1 = std::chrono::steady_clock::now();
+    std::vector<float> den(4 * pixels);
+    if (dmt_denoise(C.v[0], nullptr, mean.data(), m2.data(), den.data(), &denoiseKernelMs) != DMT_OK) return fail(C.v[0], "dmt_denoise");
+    denoiseMs = msSince(t1);
+    auto const t2 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> rgb(3 * pixels);
+    dmt_host::filmToRgb8(den.data(), m2.data(), pixels, rgb.data(), nullptr);  // the quantisation of output-<spp>.png
+    std::string err;
+    if (!dmt_host::writePngRgb8(dir + "/output-" + std::to_string(lastSamples) + "_denoised.png", rgb.data(), uint32_t(cfg.width),
+                                uint32_t(cfg.height), &err)) {
+      std::fprintf(stderr, "%s\n", err.c_str());
+      return 1;
+    }
+    writeMs += msSince(t2);
+  }
   double const samples = cfg.adaptive ? double(adaptiveSamples) : double(pixels) * double(launches) * double(cfg.kspp);
   std::printf("Done! Total Execution Time(excl write file): %llu ms | Average Execution per Kernel launch (%d spp): %llu ms | %.2f Msamples/s\n",
               static_cast<unsigned long long>(totalMs), cfg.kspp, static_cast<unsigned long long>(totalMs / std::max(launches, 1)),
@@ -322,6 +356,9 @@ int main(int argc, char** argv) {
     if (cfg.adaptive)
       std::printf(" - adaptive sampling:         %d round(s), %llu samples traced (%.2f spp on average, cap %d)\n", launches,
                   static_cast<unsigned long long>(adaptiveSamples), double(adaptiveSamples) / double(pixels), cfg.spp);
+    if (cfg.denoise)
+      std::printf(" - denoise:                   AOVs %.3f ms (%d spp, launch + sync), filter %.3f ms (kernels, HIP events; %.3f ms with copies)\n",
+                  aovMs, cfg.aovSpp, double(denoiseKernelMs), denoiseMs);
   }
   std::puts("Cleanup...");
   return 0;

@@ -253,6 +253,45 @@ int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const
 int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count,
                             int enable, uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box);
 
+/* ---- denoiser (an explicit post-process; beyond the reference) ----------------------------- */
+/* Feature pass: camera samples 0 .. aov_spp-1 of EVERY pixel of the frame (the film's own camera rays; dmt_set_partition
+ * and regions do not apply), closest hit under the current accel mode (brute force and BVH give bit-identical planes).
+ * Three row-major float4 planes that the context owns, summed in sample order in fp32 over the samples whose ray hit a
+ * triangle ("hits"):
+ *   albedo   = (sum W / aov_spp, hits / aov_spp): W = the material record's fp16 weight after the level-0 texture patch;
+ *              BS_GGX_BLEND pairs: (1 - metallic) W_dielectric + metallic W_conductor
+ *   normal   = (normalize(sum of shading normals), 0): face-forwarded or normal-mapped; 0 without hits or if |sum| < 1e-6
+ *   position = (sum hit point / hits, sum t / hits); 0 without hits
+ * Asynchronous on the context's stream.  DMT_ERR_INVALID for aov_spp outside 1 .. 65536. */
+int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp);
+/* host -> device: three width x height planes in the layout above (e.g. synthetic input for dmt_denoise) */
+int dmt_upload_aovs(dmt_ctx* ctx, const float* albedo4, const float* normal4, const float* position4, int width, int height);
+/* device -> host copy of the planes (any pointer may be NULL); synchronises the stream */
+int dmt_download_aovs(dmt_ctx* ctx, float* albedo4, float* normal4, float* position4);
+/* Spatial SVGF: edge-avoiding a-trous passes (Dammertz et al. 2010) with the variance-guided luminance term of Schied et al.
+ * 2017.  Pass i = 0 .. iterations-1 has step s = 2^i and taps q = p + s (dx, dy), dx, dy in -2 .. 2, kernel h(dx) h(dy) with
+ * h = [1/16, 1/4, 3/8, 1/4, 1/16]; taps outside the image are skipped.  A tap q != p counts only if both p and q have
+ * coverage (albedo.w > 0), with edge weight
+ *   max(0, n_p . n_q)^sigma_normal
+ *   x exp(-|n_p . (x_q - x_p)| / (sigma_position t_p theta s sqrt(dx^2 + dy^2)))     theta = sensor_size / (focal_length height)
+ *   x exp(-|a_p - a_q|^2 / sigma_albedo^2)
+ *   x exp(-|l_p - l_q| / (sigma_luminance sqrt(g_p) + 1e-10))      l = Rec. 709 luminance, g_p = 3x3 [1/4 1/2 1/4] blur of v
+ * c' = sum w c / sum w, v' = sum w^2 v / (sum w)^2; c0 = mean.xyz, v0 = (M2.x + M2.y + M2.z) / (3 N (N - 1)). */
+typedef struct dmt_denoise_params {
+  int32_t iterations;    /* 0 .. 10; 0 returns mean.xyz bit for bit */
+  float sigma_normal;    /* every sigma: finite and > 0 */
+  float sigma_position;
+  float sigma_albedo;
+  float sigma_luminance;
+} dmt_denoise_params;
+dmt_denoise_params dmt_denoise_defaults(void);
+/* Denoises a film with the AOVs of the context into out4 (width x height float4, w = 1).  mean4 / m24 NULL: the context's
+ * film (own or bound); otherwise host planes of the camera's size (e.g. the combined film of several partitions).  params
+ * NULL: dmt_denoise_defaults().  Synchronous; *kernel_ms (may be NULL) = HIP-event time of its kernels.  Never modifies the
+ * film or the AOVs.  DMT_ERR_STATE without AOVs, for AOVs of another size than the film, or when a pixel has N < 2 or a
+ * non-finite mean / M2 (e.g. a partitioned film that was not combined); DMT_ERR_INVALID for bad parameters. */
+int dmt_denoise(dmt_ctx* ctx, const dmt_denoise_params* params, const float* mean4, const float* m24, float* out4, float* kernel_ms);
+
 /* ---- device unit-test entry points (GPU twins of the reference's T/tests kernels) ---------- */
 int dmt_test_triangle_intersect(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs,
                                 size_t count, const float* o3, const float* d3, int32_t* hit,
