@@ -12,6 +12,13 @@ from .binding import (  # noqa: F401
     DmtError,
     Renderer,
     bvh_validate,
+    bvh_check,
+    lbvh_reference,
+    BVH_BUILD_HOST,
+    BVH_BUILD_DEVICE,
+    BVH_BUILT_BY_HOST,
+    BVH_BUILT_BY_DEVICE,
+    BVH_BUILT_BY_HOST_AFTER_DEVICE,
     light_tree_pmfs,
     light_tree_ref_select,
     envmap_tables,

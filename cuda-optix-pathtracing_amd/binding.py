@@ -11,6 +11,12 @@ _LIB = None
 
 DMT_ACCEL_BRUTE_FORCE = 0
 DMT_ACCEL_BVH = 1
+# dmt_set_accel_build modes and dmt_accel_build_record.builder values (include/dmt_hip.h)
+BVH_BUILD_HOST = 0
+BVH_BUILD_DEVICE = 1
+BVH_BUILT_BY_HOST = 0
+BVH_BUILT_BY_DEVICE = 1
+BVH_BUILT_BY_HOST_AFTER_DEVICE = 2
 
 
 class DmtError(RuntimeError):
@@ -59,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
     "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
     "dmt_render_aovs", "dmt_upload_aovs", "dmt_download_aovs", "dmt_denoise_defaults", "dmt_denoise",
+    "dmt_set_accel_build", "dmt_accel_build_info", "dmt_accel_download", "dmt_lbvh_reference", "dmt_bvh_check",
 ]
 
 
@@ -171,6 +178,42 @@ def bvh_validate(xs, ys, zs):
     nc, d, ml = C.c_int(), C.c_int(), C.c_int()
     rc = lib.dmt_bvh_validate(_p(xs), _p(ys), _p(zs), C.c_size_t(n), C.byref(nc), C.byref(d), C.byref(ml))
     return {"ok": rc == 0, "node_count": nc.value, "depth": d.value, "max_leaf": ml.value}
+
+
+class AccelBuildRecord(C.Structure):
+    """dmt_accel_build_record (include/dmt_hip.h)"""
+    _fields_ = [("builder", C.c_int32), ("depth", C.c_int32), ("triangles", C.c_uint32), ("nodes", C.c_uint32),
+                ("pairs", C.c_uint32), ("reserved", C.c_uint32), ("build_ms", C.c_double), ("temp_bytes", C.c_uint64)]
+
+
+def lbvh_reference(xs, ys, zs, max_depth=48):
+    """Host-only: the serial restatement of the device BVH builder.  Returns dict(abandoned, nodes = [node_count, 64] uint8,
+    pairs = [pair_count, 2] uint32 original indices, depth); abandoned (the depth guard fired) comes with empty arrays."""
+    lib = load_library()
+    xs, ys, zs = _f32(xs), _f32(ys), _f32(zs)
+    n = xs.size // 4
+    cap = max(n, 1)
+    nodes, pairs = np.zeros((cap, 64), np.uint8), np.zeros((cap, 2), np.uint32)
+    nn, npairs, d, ab = C.c_uint32(), C.c_uint32(), C.c_int(), C.c_int()
+    rc = lib.dmt_lbvh_reference(_p(xs), _p(ys), _p(zs), C.c_size_t(n), C.c_int(max_depth), _p(nodes), C.c_size_t(cap), _p(pairs),
+                                C.c_size_t(cap), C.byref(nn), C.byref(npairs), C.byref(d), C.byref(ab))
+    if rc != 0:
+        raise DmtError(f"dmt_lbvh_reference failed ({rc})")
+    return {"abandoned": bool(ab.value), "nodes": nodes[:nn.value].copy(), "pairs": pairs[:npairs.value].copy(), "depth": d.value}
+
+
+def bvh_check(nodes, pairs, xs, ys, zs):
+    """Host-only: dmt_bvh_validate's walk on any tree (nodes [k, 64] uint8, pairs [m, 2] uint32) over a soup; returns
+    dict(ok, depth, max_leaf, sah_cost, node_count, pair_count)."""
+    lib = load_library()
+    xs, ys, zs = _f32(xs), _f32(ys), _f32(zs)
+    nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, 64)
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    d, ml, sah = C.c_int(), C.c_int(), C.c_double()
+    rc = lib.dmt_bvh_check(_p(nodes), C.c_size_t(nodes.shape[0]), _p(pairs), C.c_size_t(pairs.shape[0]), _p(xs), _p(ys), _p(zs),
+                           C.c_size_t(xs.size // 4), C.byref(d), C.byref(ml), C.byref(sah))
+    return {"ok": rc == 0, "depth": d.value, "max_leaf": ml.value, "sah_cost": sah.value, "node_count": nodes.shape[0],
+            "pair_count": pairs.shape[0]}
 
 
 def brute_cull_plan(xs, ys, zs, mat_id, enable=True):
@@ -343,6 +386,25 @@ class Renderer:
 
     def set_accel(self, mode):
         self._check(self._lib.dmt_set_accel(self._ctx, int(mode)), "dmt_set_accel")
+
+    def set_accel_build(self, mode):
+        """Who builds the tree of DMT_ACCEL_BVH: BVH_BUILD_HOST (0, default) or BVH_BUILD_DEVICE (1)."""
+        self._check(self._lib.dmt_set_accel_build(self._ctx, int(mode)), "dmt_set_accel_build")
+
+    def accel_build_info(self):
+        """The build record of the current tree: dict(builder, depth, triangles, nodes, pairs, build_ms, temp_bytes)."""
+        rec = AccelBuildRecord()
+        self._check(self._lib.dmt_accel_build_info(self._ctx, C.byref(rec)), "dmt_accel_build_info")
+        return {name: getattr(rec, name) for name, _ in AccelBuildRecord._fields_ if name != "reserved"}
+
+    def download_accel(self):
+        """The current tree: (nodes [node_count, 64] uint8, pairs [pair_count, 2] uint32 original indices)."""
+        info = self.accel_build_info()
+        nodes = np.zeros((max(info["nodes"], 1), 64), np.uint8)
+        pairs = np.zeros((max(info["pairs"], 1), 2), np.uint32)
+        self._check(self._lib.dmt_accel_download(self._ctx, _p(nodes), C.c_size_t(nodes.shape[0]), _p(pairs), C.c_size_t(pairs.shape[0])),
+                    "dmt_accel_download")
+        return nodes[:info["nodes"]].copy(), pairs[:info["pairs"]].copy()
 
     def set_light_sampling(self, mode):
         """0 = uniform pick (reference, parity mode), 1 = light tree (csrc/light_tree.hpp)."""

@@ -32,6 +32,8 @@
 #include <limits>
 #include <vector>
 
+#include "lbvh.hpp"
+
 namespace dmt {
 
 constexpr uint32_t kBvhLeafFlag = 0x80000000u;
@@ -92,23 +94,7 @@ inline void bvhChildBox(Bvh4Node const& n, int k, float lo[3], float hi[3]) {
 
 namespace bvh_build {
 
-struct Box {
-  float lo[3], hi[3];
-  void reset() {
-    for (int a = 0; a < 3; ++a) lo[a] = std::numeric_limits<float>::infinity(), hi[a] = -std::numeric_limits<float>::infinity();
-  }
-  void grow(float const p[3]) {
-    for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], p[a]), hi[a] = std::max(hi[a], p[a]);
-  }
-  void grow(Box const& b) {
-    for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], b.lo[a]), hi[a] = std::max(hi[a], b.hi[a]);
-  }
-  float area() const {
-    float const dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-    if (!(dx >= 0.f)) return 0.f;
-    return 2.f * (dx * dy + dy * dz + dz * dx);
-  }
-};
+using Box = lbvh::Box;  // lbvh.hpp: the same reset / grow / area, usable in kernels
 
 struct Node2 {  // binary build node
   Box box;
@@ -223,9 +209,10 @@ struct Result {
 };
 
 // Quantise the boxes of `nk` children (inner children first) into node `nd`.  Exact-arithmetic guarantee: the decoded
-// box encloses the given one.
-inline void encodeNode(Bvh4Node& nd, Box const* kid, int nk, int nInner) {
-  std::memset(&nd, 0, sizeof(nd));
+// box encloses the given one.  __host__ __device__: the device builder (bvh_gpu_build.hip) encodes with the same
+// arithmetic; every operation is exact or a correctly rounded fp64 division, so host and device give the same bytes.
+DMT_HD inline void encodeNode(Bvh4Node& nd, Box const* kid, int nk, int nInner) {
+  memset(&nd, 0, sizeof(nd));
   Box all;
   all.reset();
   for (int k = 0; k < nk; ++k) all.grow(kid[k]);
@@ -238,13 +225,13 @@ inline void encodeNode(Bvh4Node& nd, Box const* kid, int nk, int nInner) {
     int e = -60;  // floor of the scale: the traversal's slope a = scale * (1 / d) must never flush to zero (bvh_device.hpp)
     if (ext > 0.0) {
       int fe;
-      (void)std::frexp(ext / 255.0, &fe);  // ext / 255 = m * 2^fe, m in [0.5, 1)  ->  2^fe >= ext / 255
+      (void)::frexp(ext / 255.0, &fe);  // ext / 255 = m * 2^fe, m in [0.5, 1)  ->  2^fe >= ext / 255
       e = fe;
     }
-    e = std::min(std::max(e, -60), 127);
-    while (e < 127 && std::ldexp(255.0, e) < ext) ++e;
+    e = e < -60 ? -60 : (e > 127 ? 127 : e);
+    while (e < 127 && ::ldexp(255.0, e) < ext) ++e;
     ebytes[a] = uint32_t(e + 127);
-    scale[a] = std::ldexp(1.0, e);
+    scale[a] = ::ldexp(1.0, e);
   }
   nd.ox = org[0], nd.oy = org[1], nd.oz = org[2];
   nd.meta = ebytes[0] | (ebytes[1] << 8) | (ebytes[2] << 16) | (uint32_t(nInner) << 24) | (uint32_t(nk) << 28);
@@ -254,10 +241,11 @@ inline void encodeNode(Bvh4Node& nd, Box const* kid, int nk, int nInner) {
     for (int a = 0; a < 3; ++a) {
       uint32_t l = 255, h = 0;  // empty slot: inverted box; NOT masked by count on the device -- see buildBvh's guard pairs
       if (k < nk) {
-        double const fl = std::floor((double(kid[k].lo[a]) - double(org[a])) / scale[a]);
-        double const fh = std::ceil((double(kid[k].hi[a]) - double(org[a])) / scale[a]);
-        l = uint32_t(std::min(std::max(fl, 0.0), 255.0));
-        h = uint32_t(std::min(std::max(fh, 0.0), 255.0));
+        double const fl = ::floor((double(kid[k].lo[a]) - double(org[a])) / scale[a]);
+        double const fh = ::ceil((double(kid[k].hi[a]) - double(org[a])) / scale[a]);
+        // clamp as min(max(f, 0), 255) does (a NaN gives 0)
+        l = uint32_t(!(fl > 0.0) ? 0.0 : (fl > 255.0 ? 255.0 : fl));
+        h = uint32_t(!(fh > 0.0) ? 0.0 : (fh > 255.0 ? 255.0 : fh));
       }
       *qlo[a] |= l << (8 * k), *qhi[a] |= h << (8 * k);
     }
@@ -279,7 +267,7 @@ inline Result build(float const* xs, float const* ys, float const* zs, uint32_t 
     if ((k & 3) == 3) continue;  // the SoA's pad lane
     sceneMaxAbs = std::max(sceneMaxAbs, std::max(std::fabs(xs[k]), std::max(std::fabs(ys[k]), std::fabs(zs[k]))));
   }
-  float const slabPad = 2.5e-7f * 9.f * sceneMaxAbs;
+  float const slabPad = lbvh::slabPadOf(sceneMaxAbs);
   for (uint32_t i = 0; i < n; ++i) {
     Box bx;
     bx.reset();
@@ -287,13 +275,7 @@ inline Result build(float const* xs, float const* ys, float const* zs, uint32_t 
       float const p[3] = {xs[4 * size_t(i) + v], ys[4 * size_t(i) + v], zs[4 * size_t(i) + v]};
       bx.grow(p);
     }
-    // padding: far above the rounding of the triangle test (~1e-7 relative to the triangle) and of the slab tests (slabPad),
-    // far below anything that costs traversal work
-    for (int a = 0; a < 3; ++a) {
-      float const m = std::max(std::fabs(bx.lo[a]), std::fabs(bx.hi[a]));
-      float const pad = 1e-5f * (bx.hi[a] - bx.lo[a]) + 4e-6f * m + 1e-7f + slabPad;
-      bx.lo[a] -= pad, bx.hi[a] += pad;
-    }
+    lbvh::padBox(bx, slabPad);  // the padding terms live in lbvh.hpp: the device builder pads the same way
     b.triBox[i] = bx;
     for (int a = 0; a < 3; ++a) b.centroid[3 * size_t(i) + a] = 0.5f * (bx.lo[a] + bx.hi[a]);
     b.order[i] = i;
@@ -378,7 +360,213 @@ inline Result build(float const* xs, float const* ys, float const* zs, uint32_t 
   return out;
 }
 
+// Walks any tree in this layout over the soup xs / ys / zs (dmt_bvh_validate, dmt_bvh_check): every triangle in exactly one
+// leaf, every node reached exactly once, decoded child boxes contain their vertices and nest within a quantisation step of
+// the parent's, counts in range, leaves of at most kBvhMaxLeafTris triangles, depth within kBvhMaxDepth.  pairTris: the two
+// ORIGINAL indices of each pair.  *depth = 4-wide levels (0 for a root without children); *sahCost = sum over all child
+// slots of the decoded child box's area, a leaf slot weighted by its triangle count, over the area of the union of the
+// root's child boxes.
+inline bool check(Bvh4Node const* nodes, size_t nNodes, uint32_t const* pairTris, size_t npairs, float const* xs, float const* ys,
+                  float const* zs, size_t count, int* depth, int* maxLeafOut, double* sahCost) {
+  std::vector<uint8_t> seen(count, 0);
+  std::vector<uint8_t> nodeSeen(nNodes, 0);
+  int maxLeaf = 0, maxDepth = 0;
+  bool ok = nNodes > 0;
+  struct Item {
+    uint32_t node;
+    int depth;
+    float lo[3], hi[3];  // decoded box of the slot this node hangs in
+  };
+  std::vector<Item> stack;
+  float const inf = std::numeric_limits<float>::infinity();
+  double areaSum = 0.0;
+  Box rootBox;
+  rootBox.reset();
+  if (ok) stack.push_back({0u, 1, {-inf, -inf, -inf}, {inf, inf, inf}});
+  while (!stack.empty() && ok) {
+    Item const it = stack.back();
+    stack.pop_back();
+    if (it.node >= nNodes || nodeSeen[it.node]++) { ok = false; break; }
+    Bvh4Node const& n = nodes[it.node];
+    int const inner = bvhNodeInner(n), cnt = bvhNodeCount(n);
+    if (inner > cnt || cnt > 4 || (cnt == 0 && count > 0)) { ok = false; break; }
+    if (cnt > 0) maxDepth = std::max(maxDepth, it.depth);
+    for (int k = 0; k < cnt && ok; ++k) {
+      Item c{};
+      bvhChildBox(n, k, c.lo, c.hi);
+      for (int a = 0; a < 3; ++a) {  // nested up to the parent's quantisation step (the child is re-quantised on a finer grid)
+        float const step = bvhNodeScale(n, a);
+        ok = ok && c.lo[a] <= c.hi[a] && c.lo[a] >= it.lo[a] - step && c.hi[a] <= it.hi[a] + step;
+      }
+      double const dx = double(c.hi[0]) - double(c.lo[0]), dy = double(c.hi[1]) - double(c.lo[1]), dz = double(c.hi[2]) - double(c.lo[2]);
+      double const area = 2.0 * (dx * dy + dy * dz + dz * dx);
+      if (it.node == 0) rootBox.grow(c.lo), rootBox.grow(c.hi);
+      if (k < inner) {
+        areaSum += area;
+        c.node = n.childBase + uint32_t(k);
+        c.depth = it.depth + 1;
+        stack.push_back(c);
+        continue;
+      }
+      size_t const pair = size_t(uint32_t(n.leafRef + uint32_t(k) - kBvhLeafFlag));  // the slot's reference without its flag
+      if (pair >= npairs) { ok = false; break; }
+      uint32_t const t0 = pairTris[2 * pair], t1 = pairTris[2 * pair + 1];
+      maxLeaf = std::max(maxLeaf, t0 == t1 ? 1 : 2);
+      areaSum += area * (t0 == t1 ? 1.0 : 2.0);
+      for (int half = 0; half < (t0 == t1 ? 1 : 2) && ok; ++half) {  // a one-triangle leaf repeats its triangle
+        uint32_t const t = half ? t1 : t0;
+        if (t >= count || seen[t]++) { ok = false; break; }
+        for (int v = 0; v < 3 && ok; ++v) {
+          float const p[3] = {xs[4 * size_t(t) + v], ys[4 * size_t(t) + v], zs[4 * size_t(t) + v]};
+          for (int a = 0; a < 3; ++a) ok = ok && p[a] >= c.lo[a] && p[a] <= c.hi[a];
+        }
+      }
+    }
+  }
+  for (size_t i = 0; i < count && ok; ++i) ok = seen[i] == 1;
+  for (size_t i = 0; i < nNodes && ok; ++i) ok = nodeSeen[i] == 1;
+  if (depth) *depth = maxDepth;
+  if (maxLeafOut) *maxLeafOut = maxLeaf;
+  if (sahCost) {
+    double const dx = double(rootBox.hi[0]) - double(rootBox.lo[0]), dy = double(rootBox.hi[1]) - double(rootBox.lo[1]),
+                 dz = double(rootBox.hi[2]) - double(rootBox.lo[2]);
+    double const rootArea = dx >= 0.0 ? 2.0 * (dx * dy + dy * dz + dz * dx) : 0.0;
+    *sahCost = rootArea > 0.0 ? areaSum / rootArea : 0.0;
+  }
+  return ok && maxLeaf <= kBvhMaxLeafTris && maxDepth <= kBvhMaxDepth;
+}
+
 }  // namespace bvh_build
 
+// ---- LBVH: what needs the node layout (the rest is lbvh.hpp) ----------------------------------------------------------------
+namespace lbvh {
+
+static_assert(kLeafFlag == kBvhLeafFlag, "lbvh.hpp restates the leaf flag");
+
+// One 4-wide node made from binary ref `ref`, given where its inner children (childBase) and its leaves (firstPair) go
+struct Entry {
+  Bvh4Node node;
+  uint32_t kids[4];      // binary refs, inner children first
+  uint32_t pairTris[8];  // two ORIGINAL triangle indices per leaf, in slot order
+  int nInner, nLeaf;
+};
+DMT_HD inline void layoutEntry(Tree2 const& T, uint32_t ref, uint32_t childBase, uint32_t firstPair, Entry& E) {
+  int nk = 0;
+  selectChildren(T, ref, E.kids, nk, E.nInner);
+  E.nLeaf = nk - E.nInner;
+  Box kb[4];
+  for (int k = 0; k < nk; ++k) kb[k] = T.boxOf(E.kids[k]);
+  bvh_build::encodeNode(E.node, kb, nk, E.nInner);
+  E.node.childBase = childBase;
+  E.node.leafRef = firstPair - uint32_t(E.nInner) + kBvhLeafFlag;
+  for (int k = E.nInner; k < nk; ++k) leafTris(T, E.kids[k], E.pairTris[2 * (k - E.nInner)], E.pairTris[2 * (k - E.nInner) + 1]);
+}
+
+struct Reference {
+  std::vector<Bvh4Node> nodes;
+  std::vector<uint32_t> pairTris;
+  int depth = 0;
+  bool abandoned = false;  // the level loop would have passed maxDepth: no tree
+};
+
+// The serial restatement of the device builder: same functions, same order of levels, entries and slots.
+// xs/ys/zs: the reference's SoA (4 floats per triangle: c0, c1, c2, pad)
+inline Reference reference(float const* xs, float const* ys, float const* zs, uint32_t n, int maxDepth) {
+  Reference out;
+  if (n == 0) {  // a root without children
+    Bvh4Node root;
+    bvh_build::encodeNode(root, nullptr, 0, 0);
+    out.nodes.push_back(root);
+    return out;
+  }
+  auto verts = [&](uint32_t i, float v[9]) {
+    for (int c = 0; c < 3; ++c) v[3 * c] = xs[4 * size_t(i) + c], v[3 * c + 1] = ys[4 * size_t(i) + c], v[3 * c + 2] = zs[4 * size_t(i) + c];
+  };
+  // 1. padding scale, centroid bounds
+  uint32_t maxAbsBits = 0;  // non-negative floats order as their bit patterns
+  for (uint32_t i = 0; i < n; ++i) {
+    float v[9];
+    verts(i, v);
+    for (float f : v) {
+      float const a = fabsf(f);
+      uint32_t b;
+      memcpy(&b, &a, 4);
+      maxAbsBits = std::max(maxAbsBits, b);
+    }
+  }
+  float sceneMaxAbs;
+  memcpy(&sceneMaxAbs, &maxAbsBits, 4);
+  float const slabPad = slabPadOf(sceneMaxAbs);
+  uint32_t cbLoO[3] = {kNone, kNone, kNone}, cbHiO[3] = {0, 0, 0};
+  for (uint32_t i = 0; i < n; ++i) {
+    float v[9], c[3];
+    verts(i, v);
+    centroidOf(primBox(v, slabPad), c);
+    for (int a = 0; a < 3; ++a) cbLoO[a] = std::min(cbLoO[a], orderedOfFloat(c[a])), cbHiO[a] = std::max(cbHiO[a], orderedOfFloat(c[a]));
+  }
+  float cbLo[3], cbHi[3];
+  for (int a = 0; a < 3; ++a) cbLo[a] = floatOfOrdered(cbLoO[a]), cbHi[a] = floatOfOrdered(cbHiO[a]);
+  // 2. keys, sorted (unique: a total order)
+  std::vector<uint64_t> keys(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    float v[9], c[3];
+    verts(i, v);
+    centroidOf(primBox(v, slabPad), c);
+    keys[i] = keyOf(mortonOf(c, cbLo, cbHi), i);
+  }
+  std::sort(keys.begin(), keys.end());
+  // 3. binary radix tree
+  std::vector<uint32_t> left(n - 1), right(n - 1), parent(2 * size_t(n) - 1, kNone);
+  for (uint32_t i = 0; i + 1 < n; ++i) {
+    radixNode(keys.data(), n, i, left[i], right[i]);
+    parent[left[i]] = i, parent[right[i]] = i;
+  }
+  // 4. boxes bottom-up: the first to arrive at a parent leaves, the second combines and goes on
+  std::vector<float> box(6 * (2 * size_t(n) - 1));
+  std::vector<uint8_t> arrived(n - 1, 0);
+  auto storeBox = [&](uint32_t ref, Box const& b) {
+    for (int a = 0; a < 3; ++a) box[6 * size_t(ref) + a] = b.lo[a], box[6 * size_t(ref) + 3 + a] = b.hi[a];
+  };
+  Tree2 const T{n, left.data(), right.data(), box.data(), keys.data()};
+  for (uint32_t j = 0; j < n; ++j) {
+    float v[9];
+    verts(uint32_t(keys[j]), v);
+    Box b = primBox(v, slabPad);
+    uint32_t ref = n - 1 + j;
+    storeBox(ref, b);
+    for (uint32_t p = parent[ref]; p != kNone; p = parent[p]) {
+      if (!arrived[p]++) break;
+      b.grow(T.boxOf(left[p] == ref ? right[p] : left[p]));
+      storeBox(p, b);
+      ref = p;
+    }
+  }
+  // 5. collapse, level by level
+  std::vector<uint32_t> cur{0u}, next;
+  uint32_t levelBase = 0, pairBase = 0;
+  while (!cur.empty()) {
+    if (out.depth + 1 > maxDepth) {  // 6. depth guard
+      out.nodes.clear(), out.pairTris.clear(), out.depth = 0, out.abandoned = true;
+      return out;
+    }
+    ++out.depth;
+    uint32_t const nextBase = levelBase + uint32_t(cur.size());
+    uint32_t innerOff = 0, leafOff = 0;
+    next.clear();
+    for (uint32_t ref : cur) {
+      Entry E;
+      layoutEntry(T, ref, nextBase + innerOff, pairBase + leafOff, E);
+      out.nodes.push_back(E.node);
+      out.pairTris.insert(out.pairTris.end(), E.pairTris, E.pairTris + 2 * E.nLeaf);
+      next.insert(next.end(), E.kids, E.kids + E.nInner);
+      innerOff += uint32_t(E.nInner), leafOff += uint32_t(E.nLeaf);
+    }
+    levelBase = nextBase, pairBase += leafOff;
+    cur.swap(next);
+  }
+  return out;
+}
+
+}  // namespace lbvh
 
 }  // namespace dmt

@@ -19,7 +19,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +34,8 @@
 #include "../../include/dmt_hip.h"
 #include "pt_device.hpp"
 #include "bvh_device.hpp"
+#include "bvh_gpu_build.hpp"
+#include "devbuf.hpp"
 #include "envmap.hpp"
 #include "light_tree.hpp"
 #include "light_tree_ref.hpp"
@@ -2528,48 +2532,6 @@ __global__ void __launch_bounds__(256) k_atrous(DenoiseArgs A) {
 // =============================================================================================
 // host side of the C ABI
 // =============================================================================================
-// Owner of one device array of T: hipFree on destruction, movable, not copyable.  Every device allocation of the
-// host side goes through this type.
-template <class T>
-class DevBuf {
- public:
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) reset(), p_ = o.p_, n_ = o.n_, o.p_ = nullptr, o.n_ = 0;
-    return *this;
-  }
-  DevBuf(DevBuf const&) = delete;
-  DevBuf& operator=(DevBuf const&) = delete;
-  ~DevBuf() { reset(); }
-  T* get() const { return p_; }
-  size_t size() const { return n_; }  // elements allocated
-  void reset() {
-    if (p_) (void)hipFree(p_);
-    p_ = nullptr, n_ = 0;
-  }
-  // room for at least n elements, contents not kept.  The old array is freed before the new one is allocated, so a
-  // large scratch buffer never exists twice; on failure the buffer is empty.
-  hipError_t reserve(size_t n) {
-    if (n_ >= n) return hipSuccess;
-    reset();
-    hipError_t const e = hipMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T));
-    if (e != hipSuccess) p_ = nullptr;
-    else n_ = n;
-    return e;
-  }
-  // max(n, 1) elements holding the n elements of T at `host`
-  hipError_t assign(void const* host, size_t n) {
-    hipError_t e = reserve(n ? n : 1);
-    if (e == hipSuccess && n) e = hipMemcpy(p_, host, n * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-  }
-
- private:
-  T* p_ = nullptr;
-  size_t n_ = 0;
-};
-
 struct dmt_ctx {
   int device = 0;
   hipStream_t ownStream = nullptr;
@@ -2599,6 +2561,9 @@ struct dmt_ctx {
   int bvhDepth = 0;
   uint32_t bvhNodeCount = 0, bvhPairCount = 0;
   int blocksPerCUBvh = 0;
+  int accelBuild = DMT_BVH_BUILD_HOST;   // dmt_set_accel_build: who builds the tree
+  dmt_accel_build_record buildRecord{};  // of the current tree (dmt_accel_build_info)
+  lbvh_gpu::Scratch lbvhScratch;         // temporaries of the device builder, reused across builds
   // light tree (light_tree.hpp): built from the uploaded lights when dmt_set_light_sampling asks for it
   int lightSampling = DMT_LIGHTS_UNIFORM;
   std::vector<uint8_t> h_lights;  // host copy of the packed light records
@@ -3126,9 +3091,10 @@ int blocksPerCuOf(dmt_ctx* c, MegakernelFn kernel) {
 // BVH traversal-stack overflow area for `threads` threads
 hipError_t reserveOverflow(dmt_ctx* ctx, size_t threads) { return ctx->d_overflow.reserve(threads * size_t(kBvhOverflowStack)); }
 
-// (re)build the 4-wide BVH of the uploaded soup and upload nodes + triangle pairs
-int buildBvh(dmt_ctx* ctx) {
+// (re)build the 4-wide BVH of the uploaded soup on the host and upload nodes + triangle pairs
+int buildBvhHost(dmt_ctx* ctx, int builder) {
   uint32_t const n = ctx->triCount;
+  auto const t0 = std::chrono::steady_clock::now();
   bvh_build::Result r = bvh_build::build(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), n);
   // leaf storage: triangle pairs (bvh.hpp TriPair).  Edges are the reference's own subtractions
   // (CC/private/shapes.cu:10-11) in IEEE fp32.
@@ -3163,6 +3129,42 @@ int buildBvh(dmt_ctx* ctx) {
   ctx->bvhNodeCount = uint32_t(r.nodes.size());
   ctx->bvhPairCount = uint32_t(npairs);
   ctx->haveBvh = true;
+  dmt_accel_build_record& R = ctx->buildRecord;
+  R = dmt_accel_build_record{};
+  R.builder = builder;
+  R.triangles = n, R.nodes = ctx->bvhNodeCount, R.pairs = ctx->bvhPairCount, R.depth = r.depth;
+  R.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();  // build, pair packing, copies
+  return DMT_OK;
+}
+
+// the tree of the uploaded soup, by the builder dmt_set_accel_build chose
+int buildBvh(dmt_ctx* ctx) {
+  if (ctx->accelBuild != DMT_BVH_BUILD_DEVICE) return buildBvhHost(ctx, DMT_BVH_BUILT_BY_HOST);
+  static_assert(sizeof(TriPost) == 64 && offsetof(TriPost, p2z) == 32, "the device builder reads p0, p1, p2 as nine consecutive floats");
+  lbvh_gpu::Result r;
+  std::string what;
+  hipError_t const e = lbvh_gpu::build(reinterpret_cast<float const*>(ctx->d_post.get()), uint32_t(sizeof(TriPost) / sizeof(float)),
+                                       ctx->triCount, kBvhMaxDepth, ctx->stream, ctx->lbvhScratch, r, what);
+  if (e != hipSuccess) {  // an error, not a silent host build
+    ctx->err = "device BVH build: " + what + ": " + hipGetErrorName(e) + " - " + hipGetErrorString(e);
+    return DMT_ERR_HIP;
+  }
+  if (r.abandoned) {  // the depth guard: the traversal stack is sized by kBvhMaxDepth
+    float const lostMs = r.ms;
+    int const rc = buildBvhHost(ctx, DMT_BVH_BUILT_BY_HOST_AFTER_DEVICE);
+    if (rc == DMT_OK) ctx->buildRecord.build_ms += double(lostMs), ctx->buildRecord.temp_bytes = r.tempBytes;
+    return rc;
+  }
+  if (r.pairCount > 0x7FFFFFFFull || r.nodeCount > 0x7FFFFFFFull) return fail(ctx, DMT_ERR_INVALID, "BVH: too many nodes / triangle pairs");
+  ctx->d_bvhNodes = std::move(r.nodes), ctx->d_trisBvh = std::move(r.pairs);
+  ctx->bvhDepth = r.depth;
+  ctx->bvhNodeCount = r.nodeCount, ctx->bvhPairCount = r.pairCount;
+  ctx->haveBvh = true;
+  dmt_accel_build_record& R = ctx->buildRecord;
+  R = dmt_accel_build_record{};
+  R.builder = DMT_BVH_BUILT_BY_DEVICE;
+  R.triangles = ctx->triCount, R.nodes = r.nodeCount, R.pairs = r.pairCount, R.depth = r.depth;
+  R.build_ms = double(r.ms), R.temp_bytes = r.tempBytes;
   return DMT_OK;
 }
 
@@ -3515,6 +3517,45 @@ int dmt_set_accel(dmt_ctx* ctx, int mode) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return buildBvh(ctx);
   }
+  return DMT_OK;
+}
+
+int dmt_set_accel_build(dmt_ctx* ctx, int mode) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (mode != DMT_BVH_BUILD_HOST && mode != DMT_BVH_BUILD_DEVICE) return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel_build: unknown mode");
+  if (mode == ctx->accelBuild) return DMT_OK;
+  ctx->accelBuild = mode;
+  ctx->haveBvh = false;  // the current tree is the other builder's
+  if (ctx->accel == DMT_ACCEL_BVH && ctx->haveTris) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight still read the old tree
+    return buildBvh(ctx);
+  }
+  return DMT_OK;
+}
+
+int dmt_accel_build_info(dmt_ctx* ctx, dmt_accel_build_record* out) {
+  if (!ctx || !out) return DMT_ERR_INVALID;
+  if (!ctx->haveBvh) {  // no tree: the builder the next build will use, zero counts
+    *out = dmt_accel_build_record{};
+    out->builder = ctx->accelBuild == DMT_BVH_BUILD_DEVICE ? DMT_BVH_BUILT_BY_DEVICE : DMT_BVH_BUILT_BY_HOST;
+    return DMT_OK;
+  }
+  *out = ctx->buildRecord;
+  return DMT_OK;
+}
+
+int dmt_accel_download(dmt_ctx* ctx, void* nodes64, size_t node_cap, uint32_t* pair_orig2, size_t pair_cap) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_accel_download: no tree (set DMT_ACCEL_BVH and upload triangles first)");
+  if (node_cap < ctx->bvhNodeCount || pair_cap < ctx->bvhPairCount || (ctx->bvhNodeCount && !nodes64) || (ctx->bvhPairCount && !pair_orig2))
+    return fail(ctx, DMT_ERR_INVALID, "dmt_accel_download: arrays too small (see dmt_accel_build_info)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(nodes64, ctx->d_bvhNodes.get(), size_t(ctx->bvhNodeCount) * sizeof(Bvh4Node), hipMemcpyDeviceToHost));
+  std::vector<TriPair> pairs(ctx->bvhPairCount);
+  if (!pairs.empty()) HIP_TRY(ctx, hipMemcpy(pairs.data(), ctx->d_trisBvh.get(), pairs.size() * sizeof(TriPair), hipMemcpyDeviceToHost));
+  for (size_t p = 0; p < pairs.size(); ++p) pair_orig2[2 * p] = pairs[p].orig[0], pair_orig2[2 * p + 1] = pairs[p].orig[1];
   return DMT_OK;
 }
 
@@ -3893,55 +3934,9 @@ int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t c
   bvh_build::Result const r = bvh_build::build(xs, ys, zs, uint32_t(count));
   if (node_count) *node_count = int(r.nodes.size());
   if (depth) *depth = r.depth;
-  std::vector<uint8_t> seen(count, 0);
-  std::vector<uint8_t> nodeSeen(r.nodes.size(), 0);
-  int maxLeaf = 0;
-  bool ok = r.depth <= kBvhMaxDepth && !r.nodes.empty();
-  size_t const npairs = r.pairTris.size() / 2;
-  struct Item {
-    uint32_t node;
-    float lo[3], hi[3];  // decoded box of the slot this node hangs in
-  };
-  std::vector<Item> stack;
-  float const inf = std::numeric_limits<float>::infinity();
-  stack.push_back({0u, {-inf, -inf, -inf}, {inf, inf, inf}});
-  while (!stack.empty() && ok) {
-    Item const it = stack.back();
-    stack.pop_back();
-    if (it.node >= r.nodes.size() || nodeSeen[it.node]++) { ok = false; break; }
-    Bvh4Node const& n = r.nodes[it.node];
-    int const inner = bvhNodeInner(n), cnt = bvhNodeCount(n);
-    if (inner > cnt || cnt > 4 || (cnt == 0 && count > 0)) { ok = false; break; }
-    for (int k = 0; k < cnt && ok; ++k) {
-      Item c{};
-      bvhChildBox(n, k, c.lo, c.hi);
-      for (int a = 0; a < 3; ++a) {  // nested up to the parent's quantisation step (the child is re-quantised on a finer grid)
-        float const step = bvhNodeScale(n, a);
-        ok = ok && c.lo[a] <= c.hi[a] && c.lo[a] >= it.lo[a] - step && c.hi[a] <= it.hi[a] + step;
-      }
-      if (k < inner) {
-        c.node = n.childBase + uint32_t(k);
-        stack.push_back(c);
-        continue;
-      }
-      size_t const pair = size_t(uint32_t(n.leafRef + uint32_t(k) - kBvhLeafFlag));  // the slot's reference without its flag
-      if (pair >= npairs) { ok = false; break; }
-      uint32_t const t0 = r.pairTris[2 * pair], t1 = r.pairTris[2 * pair + 1];
-      maxLeaf = std::max(maxLeaf, t0 == t1 ? 1 : 2);
-      for (int half = 0; half < (t0 == t1 ? 1 : 2) && ok; ++half) {  // a one-triangle leaf repeats its triangle
-        uint32_t const t = half ? t1 : t0;
-        if (t >= count || seen[t]++) { ok = false; break; }
-        for (int v = 0; v < 3 && ok; ++v) {
-          float const p[3] = {xs[4 * size_t(t) + v], ys[4 * size_t(t) + v], zs[4 * size_t(t) + v]};
-          for (int a = 0; a < 3; ++a) ok = ok && p[a] >= c.lo[a] && p[a] <= c.hi[a];
-        }
-      }
-    }
-  }
-  for (size_t i = 0; i < count && ok; ++i) ok = seen[i] == 1;
-  for (size_t i = 0; i < r.nodes.size() && ok; ++i) ok = nodeSeen[i] == 1;
-  if (max_leaf) *max_leaf = maxLeaf;
-  return ok && maxLeaf <= kBvhMaxLeafTris ? DMT_OK : DMT_ERR_STATE;
+  bool const ok = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs, ys, zs, count, nullptr,
+                                   max_leaf, nullptr);
+  return ok && r.depth <= kBvhMaxDepth ? DMT_OK : DMT_ERR_STATE;
 }
 
 static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats,

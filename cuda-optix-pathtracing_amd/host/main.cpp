@@ -4,7 +4,7 @@
 //   * dmt-tracer (cli/CLIManager.cpp:11-36): --device|-d cpu|gpu, --scene|-s <file>, --out|-o <path>, --time|-t,
 //       --help|-h.  `--device cpu` is refused: this build has no CPU renderer (the CPU restatement used by the tests is test
 //       infrastructure and is never linked into the product).
-// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --light-tree, --light-tree-reference, --texture-filter,
+// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --bvh-build host|gpu, --light-tree, --light-tree-reference, --texture-filter,
 // --adaptive <threshold> / --min-spp <N> (dmt_render_adaptive: --spp is the cap, --kspp the round), and --gpus <N>: N contexts, one per GPU
 // (ordinals 0..N-1), each rendering the interleaved 8x8 tiles j mod N == rank (dmt_set_partition) concurrently; the N
 // films are disjoint and summed on the host (x + 0: an exact gather).  bench.py's N-process RCCL path is the scalable
@@ -49,6 +49,8 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   bool denoise = false;       // --denoise: also write output-<spp>_denoised.png (dmt_render_aovs + dmt_denoise)
   int aovSpp = 4;             // --aov-spp <N>: camera samples per pixel of the feature buffers
   bool aovSppSet = false;
+  bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
+  std::string bvhBuildArg;
 
   // --adaptive's value: a finite, non-negative number and nothing else
   static bool parseThreshold(std::string const& a, float& out) {
@@ -81,6 +83,8 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
       if (savePartial) return "--save-partial is not available with --adaptive";
     }
     if (aovSppSet && !denoise) return "--aov-spp needs --denoise";
+    if (bvhBuildSet && bvhBuildArg != "host" && bvhBuildArg != "gpu") return "invalid --bvh-build: expected host or gpu, got '" + bvhBuildArg + "'";
+    if (bvhBuildSet && !bvh) return "--bvh-build needs --bvh";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
   }
@@ -106,6 +110,8 @@ void printHelp() {
       "                       (PBRT-v4 subset: diffuse materials, triangle meshes, diffuse area lights);\n"
       "                       its resolution, samples and max-depth apply unless given on the command line\n"
       "  --bvh             -- BVH traversal instead of the brute-force triangle loop\n"
+      "  --bvh-build <host|gpu> -- who builds the tree of --bvh: one host core (binned SAH, the default) or the GPU (LBVH:\n"
+      "                       a much faster build of a slightly looser tree; same image bit for bit)\n"
       "  --light-tree      -- pick the NEE light through a light BVH (flux x cosine / distance^2) instead of uniformly\n"
       "  --light-tree-reference -- the reference's light tree semantics: cones, adaptive cuts, up to four lights per bounce\n"
       "  --texture-filter  -- filter image textures at the camera ray's first hit (MIP levels / EWA by the pixel footprint)\n"
@@ -129,6 +135,7 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--spp" && more) c.spp = std::atoi(argv[++i]), c.sppSet = true;
     else if ((a == "--scene" || a == "-s") && more) c.scenePath = argv[++i];
     else if (a == "--bvh") c.bvh = true;
+    else if (a == "--bvh-build" && more) c.bvhBuildSet = true, c.bvhBuildArg = argv[++i];
     else if (a == "--light-tree") c.lightTree = true;
     else if (a == "--light-tree-reference") c.lightTreeRef = true;
     else if (a == "--texture-filter") c.textureFilter = true;
@@ -234,6 +241,8 @@ int main(int argc, char** argv) {
     dmt_ctx* ctx = C.v[size_t(r)];
     if (dmt_host::uploadScene(ctx, scene) != DMT_OK) return fail(ctx, "uploadScene");
     if (dmt_set_limits(ctx, cfg.maxDepth) != DMT_OK) return fail(ctx, "dmt_set_limits");
+    if (cfg.bvhBuildSet && dmt_set_accel_build(ctx, cfg.bvhBuildArg == "gpu" ? DMT_BVH_BUILD_DEVICE : DMT_BVH_BUILD_HOST) != DMT_OK)
+      return fail(ctx, "dmt_set_accel_build");
     if (cfg.bvh && dmt_set_accel(ctx, DMT_ACCEL_BVH) != DMT_OK) return fail(ctx, "dmt_set_accel");
     if (dmt_set_partition(ctx, r, cfg.gpus) != DMT_OK) return fail(ctx, "dmt_set_partition");
     if (cfg.lightTree && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
@@ -353,6 +362,13 @@ int main(int argc, char** argv) {
                 " - film download%s:   %10.3f ms\n - PNG encode + write:       %10.3f ms\n",
                 loadMs, cfg.bvh ? " + BVH build" : "            ", uploadMs, cfg.gpus, cfg.gpus > 1 ? "s" : "", totalMs, launches, cfg.kspp,
                 kernelMs, static_cast<unsigned long long>(n), cfg.gpus > 1 ? " + gather" : "         ", downloadMs, writeMs);
+    if (cfg.bvhBuildSet) {  // the build record of the first context's tree
+      dmt_accel_build_record rec{};
+      if (dmt_accel_build_info(C.v[0], &rec) != DMT_OK) return fail(C.v[0], "dmt_accel_build_info");
+      char const* const who = rec.builder == DMT_BVH_BUILT_BY_DEVICE ? "gpu" : rec.builder == DMT_BVH_BUILT_BY_HOST ? "host" : "host, after the gpu build was abandoned as too deep";
+      std::printf(" - BVH build:                 %10.3f ms (%s): %u triangles -> %u nodes, %u pairs, depth %d, %.1f MB of device temporaries\n",
+                  rec.build_ms, who, rec.triangles, rec.nodes, rec.pairs, int(rec.depth), double(rec.temp_bytes) / 1e6);
+    }
     if (cfg.adaptive)
       std::printf(" - adaptive sampling:         %d round(s), %llu samples traced (%.2f spp on average, cap %d)\n", launches,
                   static_cast<unsigned long long>(adaptiveSamples), double(adaptiveSamples) / double(pixels), cfg.spp);

@@ -239,6 +239,62 @@ int dmt_kernel_info(dmt_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* b
 int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t count, int* node_count,
                      int* depth, int* max_leaf);
 
+/* ---- who builds the tree of DMT_ACCEL_BVH (beyond the reference) ---------------------------- */
+/* DMT_BVH_BUILD_HOST (default): binned SAH on one host core (csrc/bvh.hpp), pairs packed on the host, both arrays
+ * copied over.  DMT_BVH_BUILD_DEVICE: an LBVH built on the context's stream from the vertices the context already holds
+ * on the device (csrc/bvh_gpu_build.hip: Morton keys, radix sort, binary radix tree, bottom-up boxes, level-by-level
+ * collapse into the same 4-wide nodes and triangle pairs).  Boxes only cull and the triangle test alone decides hits,
+ * so closest hits and films are bit-identical under either tree; what differs is the build time and the tree's quality.
+ * The trade, measured on one MI355X: 1 M random triangles build in 4.5 ms instead of 760 ms, 16 M in
+ * 67 ms instead of 19.9 s (end to end either way); the device tree's SAH cost is 1.05x the host tree's on those soups
+ * and it renders at 0.97x the host tree's rate (1 M triangles, 1024^2 x 64 spp: 501 against 516 Msamples/s); on the
+ * 26-triangle Cornell box it renders at 1.045x.  The build holds 260 bytes of temporary device memory per triangle,
+ * which the context keeps for the next build.  Unknown mode -> DMT_ERR_INVALID.  A change of mode drops the current tree; it is rebuilt
+ * at once when the accel mode is DMT_ACCEL_BVH and triangles are present (as dmt_set_accel does), and
+ * dmt_upload_triangles builds with the mode in force.  A soup whose Morton-order tree would be deeper than the
+ * traversal stack allows (only possible with > 2^18 triangles in one Morton cell) is built by the host builder
+ * instead; the build record says so.  A failed device allocation is an error (DMT_ERR_HIP), never a silent host build. */
+enum {
+  DMT_BVH_BUILD_HOST = 0,
+  DMT_BVH_BUILD_DEVICE = 1,
+};
+enum { /* dmt_accel_build_record.builder */
+  DMT_BVH_BUILT_BY_HOST = 0,
+  DMT_BVH_BUILT_BY_DEVICE = 1,
+  DMT_BVH_BUILT_BY_HOST_AFTER_DEVICE = 2, /* the device build was abandoned by its depth guard */
+};
+int dmt_set_accel_build(dmt_ctx* ctx, int mode);
+typedef struct dmt_accel_build_record {
+  int32_t builder;     /* DMT_BVH_BUILT_BY_* */
+  int32_t depth;       /* 4-wide levels */
+  uint32_t triangles;
+  uint32_t nodes;
+  uint32_t pairs;      /* triangle pairs, without the three guard pairs */
+  uint32_t reserved;
+  double build_ms;     /* device: HIP events around the build on the stream; host: wall clock around build, pair
+                        * packing and the copies to the device -- end to end either way */
+  uint64_t temp_bytes; /* temporary device memory the build held (kept by the context for the next build) */
+} dmt_accel_build_record;
+/* the record of the current tree; without a tree: zero counts and the builder the next build will use */
+int dmt_accel_build_info(dmt_ctx* ctx, dmt_accel_build_record* out);
+/* the current tree for checks (synchronises the stream): its 64-byte nodes and the two ORIGINAL triangle indices of
+ * each pair.  DMT_ERR_STATE without a tree, DMT_ERR_INVALID when a capacity (in nodes / pairs) is below the record's count. */
+int dmt_accel_download(dmt_ctx* ctx, void* nodes64, size_t node_cap, uint32_t* pair_orig2, size_t pair_cap);
+/* host only (no GPU): the serial restatement of the device builder (csrc/bvh.hpp lbvh::reference), bit for bit the
+ * tree DMT_BVH_BUILD_DEVICE builds for the same soup.  max_depth: the depth guard's bound (the device uses 48);
+ * *abandoned = 1 and zero counts when the level loop would pass it.  Capacities as for dmt_accel_download:
+ * max(count, 1) nodes and pairs always suffice; DMT_ERR_INVALID when one is too small. */
+int dmt_lbvh_reference(const float* xs, const float* ys, const float* zs, size_t count, int max_depth, void* nodes64,
+                       size_t node_cap, uint32_t* pair_orig2, size_t pair_cap, uint32_t* node_count, uint32_t* pair_count,
+                       int* depth, int* abandoned);
+/* host only (no GPU): the walk of dmt_bvh_validate on ANY tree in this layout over the soup: every triangle in exactly
+ * one leaf, every node reached once, decoded boxes contain their vertices and nest within a quantisation step, counts in
+ * range, leaves <= 2 triangles, depth <= 48.  DMT_OK or DMT_ERR_STATE.  *depth = 4-wide levels, *max_leaf = triangles in
+ * the largest leaf, *sah_cost = sum over all child slots of the decoded child box's area, a leaf slot weighted by its
+ * triangle count, divided by the area of the union of the root's child boxes (any of the three may be NULL). */
+int dmt_bvh_check(const void* nodes64, size_t node_count, const uint32_t* pair_orig2, size_t pair_count, const float* xs,
+                  const float* ys, const float* zs, size_t count, int* depth, int* max_leaf, double* sah_cost);
+
 /* host-only (no GPU needed): how the brute-force pass splits a soup.  Up to 4 culled clusters, runs of
  * >= 4 consecutive triangles of one material whose bounding sphere is small next to the scene; every other triangle is
  * tested for every ray.  Cluster k: cluster_first_count[2k], [2k + 1] = first original index, triangle count;
