@@ -19,6 +19,14 @@ from .binding import (  # noqa: F401
     BVH_BUILT_BY_HOST,
     BVH_BUILT_BY_DEVICE,
     BVH_BUILT_BY_HOST_AFTER_DEVICE,
+    bvh_refit_reference,
+    BVH_UPDATE_REBUILD,
+    BVH_UPDATE_REFIT,
+    BVH_UPDATE_AUTO,
+    BVH_UPDATED_NONE,
+    BVH_UPDATED_REFIT,
+    BVH_UPDATED_REBUILD,
+    BVH_UPDATED_REBUILD_AFTER_REFIT,
     light_tree_pmfs,
     light_tree_ref_select,
     envmap_tables,

@@ -17,6 +17,14 @@ BVH_BUILD_DEVICE = 1
 BVH_BUILT_BY_HOST = 0
 BVH_BUILT_BY_DEVICE = 1
 BVH_BUILT_BY_HOST_AFTER_DEVICE = 2
+# dmt_set_accel_update modes and dmt_accel_update_record.action values
+BVH_UPDATE_REBUILD = 0
+BVH_UPDATE_REFIT = 1
+BVH_UPDATE_AUTO = 2
+BVH_UPDATED_NONE = 0
+BVH_UPDATED_REFIT = 1
+BVH_UPDATED_REBUILD = 2
+BVH_UPDATED_REBUILD_AFTER_REFIT = 3
 
 
 class DmtError(RuntimeError):
@@ -66,6 +74,7 @@ EXPORTED_SYMBOLS = [
     "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
     "dmt_render_aovs", "dmt_upload_aovs", "dmt_download_aovs", "dmt_denoise_defaults", "dmt_denoise",
     "dmt_set_accel_build", "dmt_accel_build_info", "dmt_accel_download", "dmt_lbvh_reference", "dmt_bvh_check",
+    "dmt_update_vertices", "dmt_update_vertices_device", "dmt_set_accel_update", "dmt_accel_update_info", "dmt_bvh_refit_reference",
 ]
 
 
@@ -202,6 +211,27 @@ def lbvh_reference(xs, ys, zs, max_depth=48):
     return {"abandoned": bool(ab.value), "nodes": nodes[:nn.value].copy(), "pairs": pairs[:npairs.value].copy(), "depth": d.value}
 
 
+class AccelUpdateRecord(C.Structure):
+    """dmt_accel_update_record (include/dmt_hip.h)"""
+    _fields_ = [("action", C.c_int32), ("updates_since_build", C.c_uint32), ("update_ms", C.c_double), ("sah_cost", C.c_double),
+                ("sah_cost_at_build", C.c_double), ("temp_bytes", C.c_uint64)]
+
+
+def bvh_refit_reference(nodes, pairs, xs, ys, zs):
+    """Host-only: the serial restatement of the device refit.  A tree (nodes [k, 64] uint8, pairs [m, 2] uint32 original
+    indices) and the NEW soup -> the refitted nodes [k, 64] uint8.  Raises DmtError on an inconsistent tree (DMT_ERR_STATE)."""
+    lib = load_library()
+    xs, ys, zs = _f32(xs), _f32(ys), _f32(zs)
+    nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, 64)
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    out = np.zeros_like(nodes)
+    rc = lib.dmt_bvh_refit_reference(_p(nodes), C.c_size_t(nodes.shape[0]), _p(pairs), C.c_size_t(pairs.shape[0]), _p(xs), _p(ys), _p(zs),
+                                     C.c_size_t(xs.size // 4), _p(out))
+    if rc != 0:
+        raise DmtError(f"dmt_bvh_refit_reference failed ({rc})")
+    return out
+
+
 def bvh_check(nodes, pairs, xs, ys, zs):
     """Host-only: dmt_bvh_validate's walk on any tree (nodes [k, 64] uint8, pairs [m, 2] uint32) over a soup; returns
     dict(ok, depth, max_leaf, sah_cost, node_count, pair_count)."""
@@ -304,6 +334,31 @@ class Renderer:
         assert xs.size == 4 * n and ys.size == 4 * n and zs.size == 4 * n
         self._check(self._lib.dmt_upload_triangles(self._ctx, _p(xs), _p(ys), _p(zs), _p(mat_id), C.c_size_t(n)),
                     "dmt_upload_triangles")
+
+    def update_vertices(self, xs, ys, zs):
+        """Same triangles, new positions (dmt_update_vertices): layout as upload_triangles; materials, emissive triangles,
+        textures, lights, camera and film are kept; the tree follows set_accel_update."""
+        xs, ys, zs = _f32(xs), _f32(ys), _f32(zs)
+        n = xs.size // 4
+        assert xs.size == 4 * n and ys.size == 4 * n and zs.size == 4 * n
+        self._check(self._lib.dmt_update_vertices(self._ctx, _p(xs), _p(ys), _p(zs), C.c_size_t(n)), "dmt_update_vertices")
+
+    def update_vertices_device(self, ptr, count):
+        """dmt_update_vertices_device: `ptr` = device address of count x 9 floats (p0, p1, p2 of every triangle) on this
+        context's device, e.g. a contiguous float32 torch tensor's data_ptr(); read on the context's stream."""
+        self._check(self._lib.dmt_update_vertices_device(self._ctx, C.c_void_p(int(ptr)), C.c_size_t(int(count))),
+                    "dmt_update_vertices_device")
+
+    def set_accel_update(self, mode, max_cost_ratio=0.0):
+        """What an update does to the tree: BVH_UPDATE_REBUILD (0, default), BVH_UPDATE_REFIT (1) or BVH_UPDATE_AUTO (2: refit,
+        then rebuild when the cost passes max_cost_ratio x the cost the builder left)."""
+        self._check(self._lib.dmt_set_accel_update(self._ctx, int(mode), C.c_double(max_cost_ratio)), "dmt_set_accel_update")
+
+    def accel_update_info(self):
+        """The record of the last update: dict(action, updates_since_build, update_ms, sah_cost, sah_cost_at_build, temp_bytes)."""
+        rec = AccelUpdateRecord()
+        self._check(self._lib.dmt_accel_update_info(self._ctx, C.byref(rec)), "dmt_accel_update_info")
+        return {name: getattr(rec, name) for name, _ in AccelUpdateRecord._fields_}
 
     def upload_bsdfs(self, bsdfs):
         b = np.ascontiguousarray(bsdfs, np.uint8).reshape(-1, 32)

@@ -438,6 +438,188 @@ inline bool check(Bvh4Node const* nodes, size_t nNodes, uint32_t const* pairTris
 
 }  // namespace bvh_build
 
+// ---- refit: same topology and pair order, every box recomputed from new positions ---------------------------------------------
+// A pure function of (topology, new positions): nothing of the old boxes is read, only meta's inner | count nibbles,
+// childBase and leafRef.  The kernels of bvh_gpu_build.hip (dmt_update_vertices under DMT_BVH_UPDATE_REFIT) and the serial
+// restatement reference() below (dmt_bvh_refit_reference) run the same functions, so their nodes agree in all 64 bytes.
+//   * padding: slabPadOf(largest |coordinate| of the NEW soup), as both builders take it
+//   * pair box: primBox(t0), grown by primBox(t1) when the pair holds two triangles
+//   * a node's exact box: the union of its children's exact fp32 boxes (never a decoded quantised box); children have
+//     higher indices than their parent in both builders' output (childBase = 1 + the inner children of all nodes before),
+//     so indices are walked downwards -- on the device one launch per 4-wide level, deepest first
+//   * a node: encodeNode on the <= 4 gathered boxes, childBase and leafRef written back
+// Refitting a tree with the soup it was built from reproduces it: min / max are exact and associative, so the union of the
+// children's boxes IS the box the builder took (the union of the padded triangle boxes below), and encodeNode is the
+// builders' own.
+namespace refit {
+
+using Box = lbvh::Box;
+
+DMT_HD inline Box loadBox(float const* boxes, size_t i) {
+  Box b;
+  for (int a = 0; a < 3; ++a) b.lo[a] = boxes[6 * i + a], b.hi[a] = boxes[6 * i + 3 + a];
+  return b;
+}
+DMT_HD inline void storeBox(float* boxes, size_t i, Box const& b) {
+  for (int a = 0; a < 3; ++a) boxes[6 * i + a] = b.lo[a], boxes[6 * i + 3 + a] = b.hi[a];
+}
+
+// box of the pair with vertices v0 (and v1 when it holds two triangles)
+DMT_HD inline Box pairBox(float const v0[9], float const v1[9], bool two, float slabPad) {
+  Box b = lbvh::primBox(v0, slabPad);
+  if (two) b.grow(lbvh::primBox(v1, slabPad));
+  return b;
+}
+
+// one half of a pair record from a triangle's vertices: the builders' own subtractions
+DMT_HD inline void packPairHalf(TriPair& P, int half, float const v[9], uint32_t orig) {
+  P.p0x[half] = v[0], P.p0y[half] = v[1], P.p0z[half] = v[2];
+  P.e0x[half] = v[3] - v[0], P.e0y[half] = v[4] - v[1], P.e0z[half] = v[5] - v[2];
+  P.e1x[half] = v[6] - v[0], P.e1y[half] = v[7] - v[1], P.e1z[half] = v[8] - v[2];
+  P.orig[half] = orig;
+}
+
+// the topology words of a node
+DMT_HD inline int innerOf(uint32_t meta) { return int((meta >> 24) & 0xFu); }
+DMT_HD inline int countOf(uint32_t meta) { return int((meta >> 28) & 0xFu); }
+DMT_HD inline uint32_t pairOfSlot(uint32_t leafRef, int k) { return leafRef + uint32_t(k) - kBvhLeafFlag; }
+
+// Refits node `self`: false (and nothing written) when its counts are out of range, a child index is not above its own or a
+// reference leaves the arrays.  nodeBox / pairBox: 6 floats per node / pair, the children's already final.
+DMT_HD inline bool refitNode(uint32_t self, uint32_t meta, uint32_t childBase, uint32_t leafRef, size_t nNodes, size_t nPairs, float* nodeBox,
+                             float const* pairBoxes, Bvh4Node& out) {
+  int const inner = innerOf(meta), cnt = countOf(meta);
+  if (cnt > 4 || inner > cnt) return false;
+  Box kb[4];
+  for (int k = 0; k < cnt; ++k) {
+    if (k < inner) {
+      size_t const c = size_t(childBase) + size_t(k);
+      if (c <= self || c >= nNodes) return false;
+      kb[k] = loadBox(nodeBox, c);
+    } else {
+      size_t const p = pairOfSlot(leafRef, k);
+      if (p >= nPairs) return false;
+      kb[k] = loadBox(pairBoxes, p);
+    }
+  }
+  bvh_build::encodeNode(out, kb, cnt, inner);
+  out.childBase = childBase, out.leafRef = leafRef;
+  Box all;
+  all.reset();
+  for (int k = 0; k < cnt; ++k) all.grow(kb[k]);
+  storeBox(nodeBox, self, all);
+  return true;
+}
+
+// decoded box of child k, as bvhChildBox (usable in kernels)
+DMT_HD inline void childBox(Bvh4Node const& n, int k, float lo[3], float hi[3]) {
+  uint32_t const ql[3] = {n.qlox, n.qloy, n.qloz}, qh[3] = {n.qhix, n.qhiy, n.qhiz};
+  float const o[3] = {n.ox, n.oy, n.oz};
+  for (int a = 0; a < 3; ++a) {
+    uint32_t const bits = ((n.meta >> (8 * a)) & 0xFFu) << 23;
+    float s;
+    memcpy(&s, &bits, 4);
+    lo[a] = o[a] + float((ql[a] >> (8 * k)) & 0xFFu) * s;
+    hi[a] = o[a] + float((qh[a] >> (8 * k)) & 0xFFu) * s;
+  }
+}
+
+// A node's term of bvh_build::check's SAH cost, in its fp64 arithmetic on the decoded boxes: the area of every child slot,
+// a leaf slot weighted by its triangle count.  orig: the pairs' original indices, `stride` words from pair to pair.
+DMT_HD inline double costTerm(Bvh4Node const& n, uint32_t const* orig, size_t stride, size_t nPairs) {
+  int const inner = innerOf(n.meta), cnt = countOf(n.meta);
+  double sum = 0.0;
+  for (int k = 0; k < cnt && k < 4; ++k) {
+    float lo[3], hi[3];
+    childBox(n, k, lo, hi);
+    double const dx = double(hi[0]) - double(lo[0]), dy = double(hi[1]) - double(lo[1]), dz = double(hi[2]) - double(lo[2]);
+    double const area = 2.0 * (dx * dy + dy * dz + dz * dx);
+    if (k < inner) {
+      sum += area;
+    } else {
+      size_t const p = pairOfSlot(n.leafRef, k);
+      bool const one = p >= nPairs || orig[p * stride] == orig[p * stride + 1];
+      sum += area * (one ? 1.0 : 2.0);
+    }
+  }
+  return sum;
+}
+
+// area of the union of the root's decoded child boxes: what check() divides the sum of the terms by (0: no cost)
+inline double rootArea(Bvh4Node const& root) {
+  Box rb;
+  rb.reset();
+  for (int k = 0; k < countOf(root.meta) && k < 4; ++k) {
+    float lo[3], hi[3];
+    childBox(root, k, lo, hi);
+    rb.grow(lo), rb.grow(hi);
+  }
+  double const dx = double(rb.hi[0]) - double(rb.lo[0]), dy = double(rb.hi[1]) - double(rb.lo[1]), dz = double(rb.hi[2]) - double(rb.lo[2]);
+  return dx >= 0.0 ? 2.0 * (dx * dy + dy * dz + dz * dx) : 0.0;
+}
+
+// first node of every 4-wide level of a tree laid out level by level (both builders'), then the node count: level l is
+// [out[l], out[l + 1]).  Empty when the inner counts do not add up to the array.
+inline std::vector<uint32_t> levelBounds(Bvh4Node const* nodes, size_t nNodes) {
+  std::vector<uint32_t> out;
+  size_t first = 0, count = nNodes ? 1 : 0;
+  while (count > 0) {
+    if (first + count > nNodes) return {};
+    out.push_back(uint32_t(first));
+    size_t inner = 0;
+    for (size_t i = first; i < first + count; ++i) inner += size_t(innerOf(nodes[i].meta));
+    first += count, count = inner;
+  }
+  if (first != nNodes) return {};
+  out.push_back(uint32_t(nNodes));
+  return out;
+}
+
+// The serial restatement: any tree in this layout and the NEW soup (the reference's SoA, 4 floats per triangle) -> the
+// refitted nodes.  *sahCost (may be null): the sum of the nodes' terms over the root's area.  False: a child index not above
+// its parent's, or a reference outside the arrays.
+inline bool reference(Bvh4Node const* nodes, size_t nNodes, uint32_t const* pairTris, size_t npairs, float const* xs, float const* ys,
+                      float const* zs, size_t count, Bvh4Node* out, double* sahCost) {
+  if (nNodes == 0) return false;
+  auto verts = [&](uint32_t i, float v[9]) {
+    for (int c = 0; c < 3; ++c) v[3 * c] = xs[4 * size_t(i) + c], v[3 * c + 1] = ys[4 * size_t(i) + c], v[3 * c + 2] = zs[4 * size_t(i) + c];
+  };
+  uint32_t maxAbsBits = 0;  // non-negative floats order as their bit patterns
+  for (size_t i = 0; i < count; ++i) {
+    float v[9];
+    verts(uint32_t(i), v);
+    for (float f : v) {
+      float const a = fabsf(f);
+      uint32_t b;
+      memcpy(&b, &a, 4);
+      maxAbsBits = std::max(maxAbsBits, b);
+    }
+  }
+  float sceneMaxAbs;
+  memcpy(&sceneMaxAbs, &maxAbsBits, 4);
+  float const slabPad = lbvh::slabPadOf(sceneMaxAbs);
+  std::vector<float> pairBoxes(6 * npairs), nodeBox(6 * nNodes);
+  for (size_t p = 0; p < npairs; ++p) {
+    uint32_t const t0 = pairTris[2 * p], t1 = pairTris[2 * p + 1];
+    if (t0 >= count || t1 >= count) return false;
+    float v0[9], v1[9];
+    verts(t0, v0), verts(t1, v1);
+    storeBox(pairBoxes.data(), p, pairBox(v0, v1, t0 != t1, slabPad));
+  }
+  for (size_t i = nNodes; i-- > 0;)
+    if (!refitNode(uint32_t(i), nodes[i].meta, nodes[i].childBase, nodes[i].leafRef, nNodes, npairs, nodeBox.data(), pairBoxes.data(), out[i]))
+      return false;
+  if (sahCost) {
+    double sum = 0.0;
+    for (size_t i = 0; i < nNodes; ++i) sum += costTerm(out[i], pairTris, 2, npairs);
+    double const ra = rootArea(out[0]);
+    *sahCost = ra > 0.0 ? sum / ra : 0.0;
+  }
+  return true;
+}
+
+}  // namespace refit
+
 // ---- LBVH: what needs the node layout (the rest is lbvh.hpp) ----------------------------------------------------------------
 namespace lbvh {
 

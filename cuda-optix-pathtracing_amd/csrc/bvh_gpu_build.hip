@@ -12,8 +12,18 @@
 //   k_fit                            boxes bottom-up by arrival counting (the visibility protocol: at the kernel)
 //   per 4-wide level: k_level_count, rocprim::exclusive_scan, k_level_emit; the host reads the level's totals
 //   k_guard_pairs                    three copies of the last pair
+//
+// The second half, the refit (bvh.hpp namespace refit; dmt_update_vertices): same topology and pair order, new positions.
+//   k_pack_records                   TriIsect / TriPost from 9 floats per triangle (dmt_update_vertices_device only)
+//   k_scene_max                      the padding scale of the NEW soup
+//   k_refit_pairs                    every pair rewritten from the new vertices, its box; the three guard pairs in the tail
+//   k_refit_level                    one launch per 4-wide level, deepest first, one thread per node: gathers the <= 4
+//                                    child boxes the launches before left, encodes, stores its own box.  Nothing crosses
+//                                    workgroups inside a launch; kernel boundaries are the only ordering.
+//   k_refit_cost, rocprim::reduce    one fp64 term per node (bvh_build::check's arithmetic), summed
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>  // before rocPRIM: its headers use memcpy without including it
 
 #include <rocprim/rocprim.hpp>
@@ -234,6 +244,65 @@ __global__ void k_guard_pairs(TriPair* pairs, uint32_t npairs) {
   if (threadIdx.x < 3 && npairs > 0) pairs[npairs + threadIdx.x] = pairs[npairs - 1];
 }
 
+// ---- refit ---------------------------------------------------------------------------------------------------------------
+enum : uint32_t { W_REFIT_BAD = 1, W_REFIT_WORDS = 4 };  // RefitScratch::words: W_MAX_ABS, then "a reference left the arrays"
+
+__global__ void __launch_bounds__(kBlock) k_pack_records(float const* verts9, uint32_t n, TriIsect* tris, TriPost* post) {
+  uint32_t const i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  float v[9];
+  loadVerts(verts9, 9, i, v);
+  TriIsect t;
+  TriPost q;
+  packTriangle(v, tris[i].matId, t, q);  // the material id: from the record already there
+  tris[i] = t, post[i] = q;
+}
+
+// One thread per pair, and three more for the guard pairs (copies of the last pair, made from its indices: no thread reads
+// what another writes -- orig[] of a real pair is never written).
+__global__ void __launch_bounds__(kBlock) k_refit_pairs(float const* verts, uint32_t stride, uint32_t n, TriPair* pairs, uint32_t npairs,
+                                                        uint32_t* words, float* pairBox) {
+  uint32_t const p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= npairs + 3) return;
+  uint32_t const src = p < npairs ? p : npairs - 1;
+  uint32_t const t0 = pairs[src].orig[0], t1 = pairs[src].orig[1];
+  if (t0 >= n || t1 >= n) {
+    words[W_REFIT_BAD] = 1;
+    return;
+  }
+  float v0[9], v1[9];
+  loadVerts(verts, stride, t0, v0), loadVerts(verts, stride, t1, v1);
+  TriPair P;
+  refit::packPairHalf(P, 0, v0, t0), refit::packPairHalf(P, 1, v1, t1);
+  static_assert(offsetof(TriPair, orig) == 72, "the 18 floats of a pair come first");
+  memcpy(static_cast<void*>(pairs + p), &P, offsetof(TriPair, orig));
+  if (p >= npairs) {
+    pairs[p].orig[0] = t0, pairs[p].orig[1] = t1;
+    return;
+  }
+  refit::storeBox(pairBox, p, refit::pairBox(v0, v1, t0 != t1, slabPadFrom(words)));
+}
+
+__global__ void __launch_bounds__(kBlock) k_refit_level(Bvh4Node* nodes, uint32_t first, uint32_t count, uint32_t nNodes, uint32_t nPairs,
+                                                        float* nodeBox, float const* pairBox, uint32_t* words) {
+  uint32_t const i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= count) return;
+  uint32_t const self = first + i;
+  Bvh4Node const* const old = nodes + self;  // only meta, childBase and leafRef are read
+  Bvh4Node nd;
+  if (!refit::refitNode(self, old->meta, old->childBase, old->leafRef, nNodes, nPairs, nodeBox, pairBox, nd)) {
+    words[W_REFIT_BAD] = 1;
+    return;
+  }
+  nodes[self] = nd;
+}
+
+__global__ void __launch_bounds__(kBlock) k_refit_cost(Bvh4Node const* nodes, uint32_t nNodes, TriPair const* pairs, uint32_t nPairs, double* terms) {
+  uint32_t const i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= nNodes) return;
+  terms[i] = refit::costTerm(nodes[i], pairs[0].orig, sizeof(TriPair) / sizeof(uint32_t), nPairs);
+}
+
 unsigned blocksFor(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 }  // namespace
@@ -272,6 +341,7 @@ hipError_t build(float const* verts, uint32_t strideFloats, uint32_t n, int maxD
     LBVH_TRY("uploading the empty root", out.nodes.assign(&root, 1));
     LBVH_TRY("allocating the pair array", out.pairs.assign(nullptr, 0));
     out.nodeCount = 1;
+    out.levels = {0u, 1u};
     return hipSuccess;
   }
   // temporaries
@@ -349,12 +419,14 @@ hipError_t build(float const* verts, uint32_t strideFloats, uint32_t n, int maxD
       what = "a level overran its arrays (inconsistent tree)";
       return hipErrorUnknown;
     }
+    out.levels.push_back(A.levelBase);
     A.levelBase += count, A.pairBase += h[1];
     count = h[0];
     std::swap(cur, next);
   }
   if (!out.abandoned) {
     out.nodeCount = A.levelBase, out.pairCount = A.pairBase;
+    out.levels.push_back(out.nodeCount);
     hipLaunchKernelGGL(k_guard_pairs, dim3(1), dim3(64), 0, stream, S.pairs.get(), out.pairCount);
     LBVH_TRY("launching the guard pairs", hipGetLastError());
     LBVH_TRY("allocating the node array", out.nodes.reserve(out.nodeCount));
@@ -363,10 +435,86 @@ hipError_t build(float const* verts, uint32_t strideFloats, uint32_t n, int maxD
     LBVH_TRY("copying the pairs", hipMemcpyAsync(out.pairs.get(), S.pairs.get(), (size_t(out.pairCount) + 3) * sizeof(TriPair), hipMemcpyDeviceToDevice, stream));
   } else {
     out.depth = 0;
+    out.levels.clear();
   }
   LBVH_TRY("recording the end", hipEventRecord(ev.b, stream));
   LBVH_TRY("waiting for the build", hipEventSynchronize(ev.b));
   LBVH_TRY("reading the build time", hipEventElapsedTime(&out.ms, ev.a, ev.b));
+  return hipSuccess;
+}
+
+// ---- refit, host side --------------------------------------------------------------------------------------------------
+size_t RefitScratch::bytes() const {
+  return (nodeBox.size() + pairBox.size()) * sizeof(float) + (terms.size() + sum.size()) * sizeof(double) + reduceTemp.size() +
+         words.size() * sizeof(uint32_t);
+}
+
+hipError_t packRecords(float const* verts9, uint32_t n, TriIsect* tris, TriPost* post, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pack_records, dim3(blocksFor(n)), dim3(kBlock), 0, stream, verts9, n, tris, post);
+  return hipGetLastError();
+}
+
+hipError_t refit(float const* verts, uint32_t strideFloats, uint32_t n, Bvh4Node* nodes, TriPair* pairs, uint32_t nodeCount, uint32_t pairCount,
+                 std::vector<uint32_t> const& levels, hipStream_t stream, RefitScratch& S, std::string& what) {
+  if (n == 0 || pairCount == 0 || nodeCount == 0 || levels.size() < 2 || levels.front() != 0 || levels.back() != nodeCount) {
+    what = "no tree with level bounds to refit";
+    return hipErrorInvalidValue;
+  }
+  for (size_t l = 0; l + 1 < levels.size(); ++l)
+    if (levels[l] >= levels[l + 1]) {
+      what = "level bounds out of order";
+      return hipErrorInvalidValue;
+    }
+  char const* const allocStep = "allocating refit scratch";
+  LBVH_TRY(allocStep, S.nodeBox.reserve(6 * size_t(nodeCount)));
+  LBVH_TRY(allocStep, S.pairBox.reserve(6 * size_t(pairCount)));
+  LBVH_TRY(allocStep, S.words.reserve(W_REFIT_WORDS));
+  uint32_t* const words = S.words.get();
+  LBVH_TRY("zeroing the refit words", hipMemsetAsync(words, 0, W_REFIT_WORDS * sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(k_scene_max, dim3(std::min(blocksFor(n), 4096u)), dim3(kBlock), 0, stream, verts, strideFloats, n, words);
+  hipLaunchKernelGGL(k_refit_pairs, dim3(blocksFor(pairCount + 3)), dim3(kBlock), 0, stream, verts, strideFloats, n, pairs, pairCount, words,
+                     S.pairBox.get());
+  LBVH_TRY("launching the pair kernels", hipGetLastError());
+  for (size_t l = levels.size() - 1; l-- > 0;) {  // deepest level first
+    uint32_t const first = levels[l], count = levels[l + 1] - first;
+    hipLaunchKernelGGL(k_refit_level, dim3(blocksFor(count)), dim3(kBlock), 0, stream, nodes, first, count, nodeCount, pairCount, S.nodeBox.get(),
+                       S.pairBox.get(), words);
+  }
+  LBVH_TRY("launching the level kernels", hipGetLastError());
+  uint32_t bad = 0;
+  LBVH_TRY("reading the refit flag", hipMemcpyAsync(&bad, words + W_REFIT_BAD, sizeof(bad), hipMemcpyDeviceToHost, stream));
+  LBVH_TRY("waiting for the refit", hipStreamSynchronize(stream));
+  if (bad) {
+    what = "a reference of the tree left its arrays (inconsistent tree)";
+    return hipErrorUnknown;
+  }
+  return hipSuccess;
+}
+
+hipError_t sahCost(Bvh4Node const* nodes, TriPair const* pairs, uint32_t nodeCount, uint32_t pairCount, hipStream_t stream, RefitScratch& S,
+                   double& cost, std::string& what) {
+  cost = 0.0;
+  if (nodeCount == 0 || pairCount == 0) return hipSuccess;
+  size_t reduceBytes = 0;
+  LBVH_TRY("sizing the reduction", rocprim::reduce(nullptr, reduceBytes, static_cast<double*>(nullptr), static_cast<double*>(nullptr), 0.0,
+                                                    size_t(nodeCount), rocprim::plus<double>(), stream));
+  char const* const allocStep = "allocating cost scratch";
+  LBVH_TRY(allocStep, S.terms.reserve(nodeCount));
+  LBVH_TRY(allocStep, S.sum.reserve(1));
+  LBVH_TRY(allocStep, S.reduceTemp.reserve(std::max<size_t>(reduceBytes, 16)));
+  hipLaunchKernelGGL(k_refit_cost, dim3(blocksFor(nodeCount)), dim3(kBlock), 0, stream, nodes, nodeCount, pairs, pairCount, S.terms.get());
+  LBVH_TRY("launching the cost kernel", hipGetLastError());
+  size_t tempBytes = S.reduceTemp.size();
+  LBVH_TRY("summing the cost terms", rocprim::reduce(S.reduceTemp.get(), tempBytes, S.terms.get(), S.sum.get(), 0.0, size_t(nodeCount),
+                                                      rocprim::plus<double>(), stream));
+  double sum = 0.0;
+  Bvh4Node root;
+  LBVH_TRY("reading the cost", hipMemcpyAsync(&sum, S.sum.get(), sizeof(sum), hipMemcpyDeviceToHost, stream));
+  LBVH_TRY("reading the root", hipMemcpyAsync(&root, nodes, sizeof(root), hipMemcpyDeviceToHost, stream));
+  LBVH_TRY("waiting for the cost", hipStreamSynchronize(stream));
+  double const ra = refit::rootArea(root);
+  cost = ra > 0.0 ? sum / ra : 0.0;
   return hipSuccess;
 }
 
@@ -399,6 +547,17 @@ int dmt_bvh_check(const void* nodes64, size_t node_count, const uint32_t* pair_o
   bool const ok = bvh_build::check(static_cast<Bvh4Node const*>(nodes64), node_count, pair_orig2, pair_count, xs, ys, zs, count, depth, max_leaf,
                                    sah_cost);
   return ok ? DMT_OK : DMT_ERR_STATE;
+}
+
+int dmt_bvh_refit_reference(const void* nodes64, size_t node_count, const uint32_t* pair_orig2, size_t pair_count, const float* xs,
+                            const float* ys, const float* zs, size_t count, void* nodes64_out) {
+  if ((count && (!xs || !ys || !zs)) || count > 0x0FFFFFFFu || !node_count || !nodes64 || !nodes64_out || (pair_count && !pair_orig2))
+    return DMT_ERR_INVALID;
+  std::vector<Bvh4Node> out(node_count);  // the caller's array is written only on success
+  if (!refit::reference(static_cast<Bvh4Node const*>(nodes64), node_count, pair_orig2, pair_count, xs, ys, zs, count, out.data(), nullptr))
+    return DMT_ERR_STATE;
+  memcpy(nodes64_out, out.data(), node_count * sizeof(Bvh4Node));
+  return DMT_OK;
 }
 
 }  // extern "C"

@@ -6,9 +6,11 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "bvh.hpp"
 #include "devbuf.hpp"
+#include "tri_records.hpp"
 
 namespace dmt {
 namespace lbvh_gpu {
@@ -36,12 +38,33 @@ struct Result {
   bool abandoned = false;  // the depth guard fired: no tree
   float ms = 0.f;          // HIP events around the build
   size_t tempBytes = 0;
+  std::vector<uint32_t> levels;  // first node of every 4-wide level, then nodeCount (refit::levelBounds' form)
 };
 
 // Builds the tree of the n triangles at verts[i * strideFloats + 0 .. 8] (p0, p1, p2; device memory) on `stream` and
 // waits for it.  Anything but hipSuccess: `what` names the step that failed.
 hipError_t build(float const* verts, uint32_t strideFloats, uint32_t n, int maxDepth, hipStream_t stream, Scratch& S, Result& out,
                  std::string& what);
+
+// ---- the refit (bvh.hpp namespace refit) ----
+// scratch of a refit; the context owns one and reuses it (arrays only ever grow)
+struct RefitScratch {
+  DevBuf<float> nodeBox, pairBox;  // 6 floats (24 bytes) per node / per pair: the exact fp32 boxes
+  DevBuf<double> terms, sum;       // one cost term per node; their sum
+  DevBuf<uint8_t> reduceTemp;      // rocPRIM's temporary storage
+  DevBuf<uint32_t> words;          // zeroed per refit: the padding scale, the inconsistency flag
+  size_t bytes() const;
+};
+
+// TriIsect / TriPost of the n triangles at verts9[9 i .. 9 i + 8] (device memory), material ids kept; enqueued on `stream`
+hipError_t packRecords(float const* verts9, uint32_t n, TriIsect* tris, TriPost* post, hipStream_t stream);
+// Refits the tree in place to the vertices at verts[i * strideFloats + 0 .. 8]: pairs (and the three guard pairs) rewritten,
+// every node re-encoded, level by level from the deepest.  levels: first node of every level, then nodeCount.  Waits for it.
+hipError_t refit(float const* verts, uint32_t strideFloats, uint32_t n, Bvh4Node* nodes, TriPair* pairs, uint32_t nodeCount, uint32_t pairCount,
+                 std::vector<uint32_t> const& levels, hipStream_t stream, RefitScratch& S, std::string& what);
+// SAH cost of a tree on the device by bvh_build::check's definition (waits for it)
+hipError_t sahCost(Bvh4Node const* nodes, TriPair const* pairs, uint32_t nodeCount, uint32_t pairCount, hipStream_t stream, RefitScratch& S,
+                   double& cost, std::string& what);
 
 }  // namespace lbvh_gpu
 }  // namespace dmt

@@ -2564,6 +2564,13 @@ struct dmt_ctx {
   int accelBuild = DMT_BVH_BUILD_HOST;   // dmt_set_accel_build: who builds the tree
   dmt_accel_build_record buildRecord{};  // of the current tree (dmt_accel_build_info)
   lbvh_gpu::Scratch lbvhScratch;         // temporaries of the device builder, reused across builds
+  // dmt_update_vertices: what an update does to the tree (dmt_set_accel_update), the record of the last one
+  std::vector<uint32_t> bvhLevels;       // first node of every 4-wide level of the current tree, then its node count
+  int accelUpdate = DMT_BVH_UPDATE_REBUILD;
+  double maxCostRatio = 0.0;             // DMT_BVH_UPDATE_AUTO's bound
+  dmt_accel_update_record updateRecord{};
+  bool costAtBuildKnown = false;         // updateRecord.sah_cost_at_build is of the current topology
+  lbvh_gpu::RefitScratch refitScratch;   // boxes and cost terms of a refit, reused across updates
   // light tree (light_tree.hpp): built from the uploaded lights when dmt_set_light_sampling asks for it
   int lightSampling = DMT_LIGHTS_UNIFORM;
   std::vector<uint8_t> h_lights;  // host copy of the packed light records
@@ -3091,6 +3098,13 @@ int blocksPerCuOf(dmt_ctx* c, MegakernelFn kernel) {
 // BVH traversal-stack overflow area for `threads` threads
 hipError_t reserveOverflow(dmt_ctx* ctx, size_t threads) { return ctx->d_overflow.reserve(threads * size_t(kBvhOverflowStack)); }
 
+// a builder made a new topology: the update record counts refits from here, costs are of the tree before
+void treeBuilt(dmt_ctx* ctx) {
+  ctx->updateRecord.updates_since_build = 0;
+  ctx->updateRecord.sah_cost = ctx->updateRecord.sah_cost_at_build = 0.0;
+  ctx->costAtBuildKnown = false;
+}
+
 // (re)build the 4-wide BVH of the uploaded soup on the host and upload nodes + triangle pairs
 int buildBvhHost(dmt_ctx* ctx, int builder) {
   uint32_t const n = ctx->triCount;
@@ -3129,6 +3143,8 @@ int buildBvhHost(dmt_ctx* ctx, int builder) {
   ctx->bvhNodeCount = uint32_t(r.nodes.size());
   ctx->bvhPairCount = uint32_t(npairs);
   ctx->haveBvh = true;
+  ctx->bvhLevels = refit::levelBounds(r.nodes.data(), r.nodes.size());
+  treeBuilt(ctx);
   dmt_accel_build_record& R = ctx->buildRecord;
   R = dmt_accel_build_record{};
   R.builder = builder;
@@ -3160,11 +3176,141 @@ int buildBvh(dmt_ctx* ctx) {
   ctx->bvhDepth = r.depth;
   ctx->bvhNodeCount = r.nodeCount, ctx->bvhPairCount = r.pairCount;
   ctx->haveBvh = true;
+  ctx->bvhLevels = std::move(r.levels);
+  treeBuilt(ctx);
   dmt_accel_build_record& R = ctx->buildRecord;
   R = dmt_accel_build_record{};
   R.builder = DMT_BVH_BUILT_BY_DEVICE;
   R.triangles = ctx->triCount, R.nodes = r.nodeCount, R.pairs = r.pairCount, R.depth = r.depth;
   R.build_ms = double(r.ms), R.temp_bytes = r.tempBytes;
+  return DMT_OK;
+}
+
+// ---- what dmt_upload_triangles and dmt_update_vertices share ----
+// both records of every triangle of a soup (tri_records.hpp; the record kernel of dmt_update_vertices_device runs the same function)
+void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count, std::vector<TriIsect>& a,
+              std::vector<TriPost>& b) {
+  a.resize(count), b.resize(count);
+  for (size_t i = 0; i < count; ++i) {
+    float const v[9] = {xs[4 * i], ys[4 * i], zs[4 * i], xs[4 * i + 1], ys[4 * i + 1], zs[4 * i + 1], xs[4 * i + 2], ys[4 * i + 2], zs[4 * i + 2]};
+    packTriangle(v, mat[i], a[i], b[i]);
+  }
+}
+
+// the culled clusters of the brute-force pass for a soup, by the context's DMT_BRUTE_CULL setting
+std::vector<CullCluster> planCullClusters(dmt_ctx const* ctx, float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
+  // a closest-hit key holds the original index in 26 bits: no culling for larger soups
+  std::vector<CullCluster> clusters = planBruteCull(xs, ys, zs, mat, uint32_t(count), ctx->bruteCull >= 1 && count < kCullMaxIndex, nullptr);
+  if (ctx->bruteCull >= 2 && count < kCullMaxIndex) {
+    std::vector<CullCluster> const boxes = planBruteCullBox(xs, ys, zs, mat, uint32_t(count), clusters);
+    clusters.insert(clusters.end(), boxes.begin(), boxes.end());
+  }
+  return clusters;
+}
+
+// device tables of a cluster plan; a = the soup's TriIsect records (read only when there are clusters)
+struct CullTables {
+  DevBuf<TriIsect> always;
+  DevBuf<uint32_t> idx;
+  DevBuf<CullCluster> clusters;
+  DevBuf<float> tri9;
+  uint32_t alwaysCount = 0, clusterCount = 0;
+};
+int uploadCullTables(dmt_ctx* ctx, std::vector<CullCluster> const& clusters, TriIsect const* a, size_t count, CullTables& T) {
+  T.alwaysCount = uint32_t(count), T.clusterCount = uint32_t(clusters.size());
+  if (clusters.empty()) return DMT_OK;
+  std::vector<uint8_t> culled(count, 0);
+  std::vector<float> tri9(9 * kCullMaxTris, 0.f);
+  for (CullCluster const& cl : clusters)
+    for (uint32_t j = 0; j < cl.count; ++j) {
+      TriIsect const& t = a[cl.first + j];
+      float const f[9] = {t.p0x, t.p0y, t.p0z, t.e0x, t.e0y, t.e0z, t.e1x, t.e1y, t.e1z};
+      for (int q = 0; q < 9; ++q) tri9[q * kCullMaxTris + cl.slot + j] = f[q];
+      culled[cl.first + j] = 1;
+    }
+  std::vector<TriIsect> always;
+  std::vector<uint32_t> idx;
+  for (size_t i = 0; i < count; ++i)
+    if (!culled[i]) always.push_back(a[i]), idx.push_back(uint32_t(i));
+  std::vector<CullCluster> table(kCullMaxClusters, CullCluster{});
+  std::copy(clusters.begin(), clusters.end(), table.begin());
+  T.alwaysCount = uint32_t(always.size());
+  HIP_TRY(ctx, T.always.assign(always.data(), always.size()));
+  HIP_TRY(ctx, T.idx.assign(idx.data(), idx.size()));
+  HIP_TRY(ctx, T.clusters.assign(table.data(), table.size()));
+  HIP_TRY(ctx, T.tri9.assign(tri9.data(), tri9.size()));
+  return DMT_OK;
+}
+void adoptCullTables(dmt_ctx* ctx, CullTables& T) {
+  ctx->d_cullAlways = std::move(T.always), ctx->d_cullIdx = std::move(T.idx);
+  ctx->d_cullClusters = std::move(T.clusters), ctx->d_cullTri9 = std::move(T.tri9);
+  ctx->cullAlwaysCount = T.alwaysCount, ctx->cullClusterCount = T.clusterCount;
+}
+
+// ---- dmt_update_vertices: timing and the update policy ----
+struct UpdateTimer {  // HIP events on the context's stream, destroyed on every exit path
+  hipEvent_t a = nullptr, b = nullptr;
+  ~UpdateTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+int lbvhError(dmt_ctx* ctx, char const* stage, std::string const& what, hipError_t e) {
+  ctx->err = std::string(stage) + ": " + what + ": " + hipGetErrorName(e) + " - " + hipGetErrorString(e);
+  return DMT_ERR_HIP;
+}
+int treeCost(dmt_ctx* ctx, double& cost) {
+  std::string what;
+  hipError_t const e = lbvh_gpu::sahCost(ctx->d_bvhNodes.get(), ctx->d_trisBvh.get(), ctx->bvhNodeCount, ctx->bvhPairCount, ctx->stream,
+                                         ctx->refitScratch, cost, what);
+  return e == hipSuccess ? DMT_OK : lbvhError(ctx, "BVH cost", what, e);
+}
+
+// The records, cull tables and host mirrors hold the new positions; T.a is recorded on the idle stream.  Applies
+// dmt_set_accel_update's policy to the tree and fills the update record.
+int finishUpdate(dmt_ctx* ctx, UpdateTimer& T) {
+  dmt_accel_update_record& U = ctx->updateRecord;
+  bool const bvh = ctx->accel == DMT_ACCEL_BVH;
+  bool const refitting = bvh && ctx->haveBvh && ctx->accelUpdate != DMT_BVH_UPDATE_REBUILD && ctx->bvhLevels.size() >= 2;
+  bool rebuild = bvh && !refitting;
+  if (!bvh) ctx->haveBvh = false;  // as an upload does
+  U.action = DMT_BVH_UPDATED_NONE;
+  if (refitting) {
+    if (!ctx->costAtBuildKnown) {  // the nodes still are the builder's: the refit has not run yet
+      if (int const rc = treeCost(ctx, U.sah_cost_at_build)) return rc;
+      ctx->costAtBuildKnown = true;
+    }
+    static_assert(sizeof(TriPost) == 64 && offsetof(TriPost, p2z) == 32, "the refit reads p0, p1, p2 as nine consecutive floats");
+    std::string what;
+    hipError_t const e = lbvh_gpu::refit(reinterpret_cast<float const*>(ctx->d_post.get()), uint32_t(sizeof(TriPost) / sizeof(float)), ctx->triCount,
+                                         ctx->d_bvhNodes.get(), ctx->d_trisBvh.get(), ctx->bvhNodeCount, ctx->bvhPairCount, ctx->bvhLevels,
+                                         ctx->stream, ctx->refitScratch, what);
+    if (e != hipSuccess) {
+      ctx->haveBvh = false;  // the tree may be half refitted
+      return lbvhError(ctx, "BVH refit", what, e);
+    }
+    if (int const rc = treeCost(ctx, U.sah_cost)) return rc;
+    U.action = DMT_BVH_UPDATED_REFIT;
+    ++U.updates_since_build;
+    rebuild = ctx->accelUpdate == DMT_BVH_UPDATE_AUTO && U.sah_cost > ctx->maxCostRatio * U.sah_cost_at_build;
+  }
+  HIP_TRY(ctx, hipEventRecord(T.b, ctx->stream));
+  HIP_TRY(ctx, hipEventSynchronize(T.b));
+  float ms = 0.f;
+  HIP_TRY(ctx, hipEventElapsedTime(&ms, T.a, T.b));
+  U.update_ms = double(ms);
+  if (rebuild) {
+    ctx->haveBvh = false;
+    if (int const rc = buildBvh(ctx)) return rc;  // resets updates_since_build and the costs
+    U.action = refitting ? DMT_BVH_UPDATED_REBUILD_AFTER_REFIT : DMT_BVH_UPDATED_REBUILD;
+    U.update_ms += ctx->buildRecord.build_ms;
+    if (ctx->accelUpdate != DMT_BVH_UPDATE_REBUILD) {
+      if (int const rc = treeCost(ctx, U.sah_cost)) return rc;
+      U.sah_cost_at_build = U.sah_cost;
+      ctx->costAtBuildKnown = true;
+    }
+  }
+  U.temp_bytes = ctx->refitScratch.bytes();
   return DMT_OK;
 }
 
@@ -3346,71 +3492,20 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu)
     return fail(ctx, DMT_ERR_INVALID, "dmt_upload_triangles: null array or count out of range");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<TriIsect> a(count);
-  std::vector<TriPost> b(count);
+  std::vector<TriIsect> a;
+  std::vector<TriPost> b;
+  packSoup(xs, ys, zs, mat_id, count, a, b);
   uint32_t maxMat = 0;
-  for (size_t i = 0; i < count; ++i) {
+  for (size_t i = 0; i < count; ++i)
     if (mat_id[i] > maxMat) maxMat = mat_id[i];
-    H3 const p0{xs[4 * i], ys[4 * i], zs[4 * i]};
-    H3 const p1{xs[4 * i + 1], ys[4 * i + 1], zs[4 * i + 1]};
-    H3 const p2{xs[4 * i + 2], ys[4 * i + 2], zs[4 * i + 2]};
-    H3 const e0{p1.x - p0.x, p1.y - p0.y, p1.z - p0.z};
-    H3 const e1{p2.x - p0.x, p2.y - p0.y, p2.z - p0.z};
-    H3 const n = hnormalize(hcross(e1, e0));
-    TriIsect& t = a[i];
-    t.p0x = p0.x, t.p0y = p0.y, t.p0z = p0.z;
-    t.e0x = e0.x, t.e0y = e0.y, t.e0z = e0.z;
-    t.e1x = e1.x, t.e1y = e1.y, t.e1z = e1.z;
-    t.matId = mat_id[i], t.pad0 = 0, t.pad1 = 0;
-    TriPost& q = b[i];
-    q.p0x = p0.x, q.p0y = p0.y, q.p0z = p0.z;
-    q.p1x = p1.x, q.p1y = p1.y, q.p1z = p1.z;
-    q.p2x = p2.x, q.p2y = p2.y, q.p2z = p2.z;
-    q.nx = n.x, q.ny = n.y, q.nz = n.z;
-    q.matId = mat_id[i], q.pad0 = q.pad1 = q.pad2 = 0;
-  }
   DevBuf<TriIsect> tris;
   DevBuf<TriPost> post;
   HIP_TRY(ctx, tris.assign(a.data(), count));
   HIP_TRY(ctx, post.assign(b.data(), count));
-  // a closest-hit key holds the original index in 26 bits: no culling for larger soups
-  std::vector<CullCluster> clusters =
-      planBruteCull(xs, ys, zs, mat_id, uint32_t(count), ctx->bruteCull >= 1 && count < kCullMaxIndex, nullptr);
-  if (ctx->bruteCull >= 2 && count < kCullMaxIndex) {
-    std::vector<CullCluster> const boxes = planBruteCullBox(xs, ys, zs, mat_id, uint32_t(count), clusters);
-    clusters.insert(clusters.end(), boxes.begin(), boxes.end());
-  }
-  DevBuf<TriIsect> cullAlways;
-  DevBuf<uint32_t> cullIdx;
-  DevBuf<CullCluster> cullClusters;
-  DevBuf<float> cullTri9;
-  uint32_t alwaysCount = uint32_t(count);
-  if (!clusters.empty()) {
-    std::vector<uint8_t> culled(count, 0);
-    std::vector<float> tri9(9 * kCullMaxTris, 0.f);
-    for (CullCluster const& cl : clusters)
-      for (uint32_t j = 0; j < cl.count; ++j) {
-        TriIsect const& t = a[cl.first + j];
-        float const f[9] = {t.p0x, t.p0y, t.p0z, t.e0x, t.e0y, t.e0z, t.e1x, t.e1y, t.e1z};
-        for (int q = 0; q < 9; ++q) tri9[q * kCullMaxTris + cl.slot + j] = f[q];
-        culled[cl.first + j] = 1;
-      }
-    std::vector<TriIsect> always;
-    std::vector<uint32_t> idx;
-    for (size_t i = 0; i < count; ++i)
-      if (!culled[i]) always.push_back(a[i]), idx.push_back(uint32_t(i));
-    std::vector<CullCluster> table(kCullMaxClusters, CullCluster{});
-    std::copy(clusters.begin(), clusters.end(), table.begin());
-    alwaysCount = uint32_t(always.size());
-    HIP_TRY(ctx, cullAlways.assign(always.data(), always.size()));
-    HIP_TRY(ctx, cullIdx.assign(idx.data(), idx.size()));
-    HIP_TRY(ctx, cullClusters.assign(table.data(), table.size()));
-    HIP_TRY(ctx, cullTri9.assign(tri9.data(), tri9.size()));
-  }
+  CullTables cull;
+  if (int const rcC = uploadCullTables(ctx, planCullClusters(ctx, xs, ys, zs, mat_id, count), a.data(), count, cull)) return rcC;
   ctx->d_tris = std::move(tris), ctx->d_post = std::move(post);
-  ctx->d_cullAlways = std::move(cullAlways), ctx->d_cullIdx = std::move(cullIdx);
-  ctx->d_cullClusters = std::move(cullClusters), ctx->d_cullTri9 = std::move(cullTri9);
-  ctx->cullAlwaysCount = alwaysCount, ctx->cullClusterCount = uint32_t(clusters.size());
+  adoptCullTables(ctx, cull);
   ctx->triCount = uint32_t(count);
   ctx->maxMatId = maxMat;
   ctx->haveTris = true;
@@ -3420,6 +3515,92 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->h_areaTri.clear(), ctx->h_areaLe.clear();  // emissive triangles are indices into the soup just replaced
   if (int const rcA = rebuildAreaLights(ctx)) return rcA;
   if (ctx->accel == DMT_ACCEL_BVH) return buildBvh(ctx);
+  return DMT_OK;
+}
+
+namespace {
+// common entry of the two updates: argument and state checks, the stream drained, the timer started.  *done: nothing to do
+int beginUpdate(dmt_ctx* ctx, char const* name, bool nullArray, size_t count, UpdateTimer& T, bool* done) {
+  *done = false;
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "update of vertices before any dmt_upload_triangles");
+  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "update of vertices: count differs from the uploaded triangle count");
+  if (count && nullArray) {
+    ctx->err = std::string(name) + ": null array";
+    return DMT_ERR_INVALID;
+  }
+  if (count == 0) {
+    *done = true;
+    return DMT_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old records
+  HIP_TRY(ctx, hipEventCreate(&T.a));
+  HIP_TRY(ctx, hipEventCreate(&T.b));
+  HIP_TRY(ctx, hipEventRecord(T.a, ctx->stream));
+  return DMT_OK;
+}
+}  // namespace
+
+int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs, size_t count) {
+  UpdateTimer T;
+  bool done = false;
+  if (int const rc = beginUpdate(ctx, "dmt_update_vertices", !xs || !ys || !zs, count, T, &done)) return rc;
+  if (done) return DMT_OK;
+  std::vector<TriIsect> a;
+  std::vector<TriPost> b;
+  packSoup(xs, ys, zs, ctx->h_mat.data(), count, a, b);
+  CullTables cull;
+  if (int const rcC = uploadCullTables(ctx, planCullClusters(ctx, xs, ys, zs, ctx->h_mat.data(), count), a.data(), count, cull)) return rcC;
+  HIP_TRY(ctx, hipMemcpy(ctx->d_tris.get(), a.data(), count * sizeof(TriIsect), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->d_post.get(), b.data(), count * sizeof(TriPost), hipMemcpyHostToDevice));
+  adoptCullTables(ctx, cull);
+  ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
+  return finishUpdate(ctx, T);
+}
+
+int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count) {
+  UpdateTimer T;
+  bool done = false;
+  if (int const rc = beginUpdate(ctx, "dmt_update_vertices_device", !d_verts9, count, T, &done)) return rc;
+  if (done) return DMT_OK;
+  HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->d_tris.get(), ctx->d_post.get(), ctx->stream));
+  // the host mirrors (the host builder's, the cull plan's and a later rebuild's input) from the records just made
+  std::vector<TriPost> b(count);
+  HIP_TRY(ctx, hipMemcpyAsync(b.data(), ctx->d_post.get(), count * sizeof(TriPost), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < count; ++i) {
+    TriPost const& q = b[i];
+    ctx->h_xs[4 * i] = q.p0x, ctx->h_xs[4 * i + 1] = q.p1x, ctx->h_xs[4 * i + 2] = q.p2x;
+    ctx->h_ys[4 * i] = q.p0y, ctx->h_ys[4 * i + 1] = q.p1y, ctx->h_ys[4 * i + 2] = q.p2y;
+    ctx->h_zs[4 * i] = q.p0z, ctx->h_zs[4 * i + 1] = q.p1z, ctx->h_zs[4 * i + 2] = q.p2z;
+  }
+  std::vector<CullCluster> const clusters = planCullClusters(ctx, ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->h_mat.data(), count);
+  std::vector<TriIsect> a;
+  if (!clusters.empty()) {  // the cluster tables copy TriIsect records: the kernel's own
+    a.resize(count);
+    HIP_TRY(ctx, hipMemcpy(a.data(), ctx->d_tris.get(), count * sizeof(TriIsect), hipMemcpyDeviceToHost));
+  }
+  CullTables cull;
+  if (int const rcC = uploadCullTables(ctx, clusters, a.data(), count, cull)) return rcC;
+  adoptCullTables(ctx, cull);
+  return finishUpdate(ctx, T);
+}
+
+int dmt_set_accel_update(dmt_ctx* ctx, int mode, double max_cost_ratio) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (mode != DMT_BVH_UPDATE_REBUILD && mode != DMT_BVH_UPDATE_REFIT && mode != DMT_BVH_UPDATE_AUTO)
+    return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel_update: unknown mode");
+  if (mode == DMT_BVH_UPDATE_AUTO && !(std::isfinite(max_cost_ratio) && max_cost_ratio > 1.0))
+    return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel_update: DMT_BVH_UPDATE_AUTO needs a finite max_cost_ratio > 1");
+  ctx->accelUpdate = mode;
+  if (mode == DMT_BVH_UPDATE_AUTO) ctx->maxCostRatio = max_cost_ratio;
+  return DMT_OK;
+}
+
+int dmt_accel_update_info(dmt_ctx* ctx, dmt_accel_update_record* out) {
+  if (!ctx || !out) return DMT_ERR_INVALID;
+  *out = ctx->updateRecord;
   return DMT_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/dmt_ggx_tables.inc"
+#include "tri_records.hpp"
 
 #define DMT_DEV __device__ __forceinline__
 
@@ -167,23 +168,7 @@ struct Rec32 {  // packed BSDF / Light record, 8 dwords
 DMT_DEV uint32_t lo16(uint32_t w) { return w & 0xFFFFu; }
 DMT_DEV uint32_t hi16(uint32_t w) { return w >> 16; }
 
-// hot-loop triangle record, built on the host at upload: p0, e0 = p1-p0, e1 = p2-p0 (same float
-// subtractions the reference does per test, CC/private/shapes.cu:10-11)
-struct TriIsect {  // 48 B, three 16-byte loads
-  float p0x, p0y, p0z, e0x;
-  float e0y, e0z, e1x, e1y;
-  float e1z;
-  uint32_t matId;
-  uint32_t pad0, pad1;
-};
-// post-hit record: original vertices (error bound needs them) + unit geometric normal
-// normalize(cross(e1,e0)) precomputed on the host with the same IEEE expression (shapes.cu:48)
-struct TriPost {  // 64 B
-  float p0x, p0y, p0z, p1x;
-  float p1y, p1z, p2x, p2y;
-  float p2z, nx, ny, nz;
-  uint32_t matId, pad0, pad1, pad2;
-};
+// TriIsect (hot-loop triangle record) and TriPost (post-hit record): tri_records.hpp, with the function that packs them
 
 struct CameraXf {  // the matrix entries the perspective path needs (column-major m[16])
   float cfr[16];   // cameraFromRaster

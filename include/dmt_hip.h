@@ -295,6 +295,54 @@ int dmt_lbvh_reference(const float* xs, const float* ys, const float* zs, size_t
 int dmt_bvh_check(const void* nodes64, size_t node_count, const uint32_t* pair_orig2, size_t pair_count, const float* xs,
                   const float* ys, const float* zs, size_t count, int* depth, int* max_leaf, double* sah_cost);
 
+/* ---- moving geometry: same triangles, new positions (beyond the reference) ------------------- */
+/* Same triangles, new positions.  count must equal the current triangle count (DMT_ERR_INVALID otherwise; DMT_ERR_STATE
+ * before any dmt_upload_triangles).  Layout of xs / ys / zs as in dmt_upload_triangles.  Material ids, the emissive-triangle
+ * list, texture tables and UVs, lights, camera and film are kept.  Synchronises the stream first (launches in flight read
+ * the old records), then leaves the context as dmt_upload_triangles + the same dmt_upload_area_lights +
+ * dmt_upload_textures would -- except for the tree, which follows dmt_set_accel_update.  The film is not cleared and
+ * AOVs are not recomputed.  An empty soup (count 0 on a 0-triangle context) is a no-op. */
+int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs, size_t count);
+/* The same from device memory of the context's device: count x 9 floats (p0 xyz, p1 xyz, p2 xyz), read on the context's
+ * stream; the caller orders its own writes before that (same stream via dmt_set_stream, or a synchronise).  A kernel makes
+ * the records (byte for byte the host packer's for triangles of non-zero area); the context's host copy of the soup is
+ * refreshed by device-to-host copies. */
+int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count);
+/* What an update does to the tree of DMT_ACCEL_BVH (under brute force an update drops any tree, as an upload does).  A refit
+ * (csrc/bvh.hpp namespace refit, kernels in csrc/bvh_gpu_build.hip) is a pure function of the topology and the new
+ * positions: pairs rewritten, every box recomputed bottom-up from exact fp32 boxes, one launch per 4-wide level; refitting
+ * back to the positions a tree was built from gives the builder's bytes again.  It keeps the topology of either builder;
+ * closest hits and films stay bit-identical to brute force, what degrades with the deformation is the tree's quality
+ * (sah_cost against sah_cost_at_build).  The library ships no default ratio. */
+enum {
+  DMT_BVH_UPDATE_REBUILD = 0, /* default: rebuild with the builder in force -- what a re-upload does */
+  DMT_BVH_UPDATE_REFIT = 1,   /* keep topology and pair order, recompute every box on the device */
+  DMT_BVH_UPDATE_AUTO = 2,    /* refit, then rebuild if cost > max_cost_ratio x the cost the builder left */
+};
+/* AUTO: max_cost_ratio finite and > 1, else DMT_ERR_INVALID; ignored otherwise.  Unknown mode -> DMT_ERR_INVALID. */
+int dmt_set_accel_update(dmt_ctx* ctx, int mode, double max_cost_ratio);
+enum { /* dmt_accel_update_record.action */
+  DMT_BVH_UPDATED_NONE = 0, /* no update yet, or no tree to update (brute force) */
+  DMT_BVH_UPDATED_REFIT = 1,
+  DMT_BVH_UPDATED_REBUILD = 2,
+  DMT_BVH_UPDATED_REBUILD_AFTER_REFIT = 3, /* AUTO: the refitted tree's cost passed the ratio */
+};
+typedef struct dmt_accel_update_record {
+  int32_t action;               /* DMT_BVH_UPDATED_*, of the last update */
+  uint32_t updates_since_build; /* refits since a builder made the topology; every build (upload, dmt_set_accel_build, rebuild) resets it */
+  double update_ms;             /* HIP events on the stream around record making + refit (+ cost); a rebuild adds its build_ms */
+  double sah_cost;              /* dmt_bvh_check's definition, of the current tree; 0 when not computed (REBUILD mode) */
+  double sah_cost_at_build;     /* the same of the tree as its builder left it; 0 when not computed */
+  uint64_t temp_bytes;          /* refit scratch the context keeps (boxes per node and per pair, cost terms) */
+} dmt_accel_update_record;
+/* the record of the last update; dmt_accel_build_info keeps describing the build that made the topology */
+int dmt_accel_update_info(dmt_ctx* ctx, dmt_accel_update_record* out);
+/* host only (no GPU): the serial restatement of the refit.  In: any tree in this layout (as from dmt_accel_download,
+ * dmt_lbvh_reference) and the NEW soup.  Out: the refitted nodes (node_count x 64 bytes), bit for bit what the device
+ * refit leaves.  DMT_ERR_STATE if a child index is not above its parent's or a reference leaves the arrays. */
+int dmt_bvh_refit_reference(const void* nodes64, size_t node_count, const uint32_t* pair_orig2, size_t pair_count,
+                            const float* xs, const float* ys, const float* zs, size_t count, void* nodes64_out);
+
 /* host-only (no GPU needed): how the brute-force pass splits a soup.  Up to 4 culled clusters, runs of
  * >= 4 consecutive triangles of one material whose bounding sphere is small next to the scene; every other triangle is
  * tested for every ray.  Cluster k: cluster_first_count[2k], [2k + 1] = first original index, triangle count;
