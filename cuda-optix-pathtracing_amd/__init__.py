@@ -32,6 +32,8 @@ from .binding import (  # noqa: F401
     envmap_tables,
     texture_mip_chain,
     texture_footprint,
+    temporal_defaults,
+    camera_project,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = [
     "dmt_render_aovs", "dmt_upload_aovs", "dmt_download_aovs", "dmt_denoise_defaults", "dmt_denoise",
     "dmt_set_accel_build", "dmt_accel_build_info", "dmt_accel_download", "dmt_lbvh_reference", "dmt_bvh_check",
     "dmt_update_vertices", "dmt_update_vertices_device", "dmt_set_accel_update", "dmt_accel_update_info", "dmt_bvh_refit_reference",
+    "dmt_download_aov_surface", "dmt_upload_aov_surface", "dmt_camera_project", "dmt_test_camera_project", "dmt_temporal_defaults",
+    "dmt_denoise_temporal", "dmt_temporal_reset", "dmt_temporal_info", "dmt_temporal_download",
 ]
 
 
@@ -90,6 +92,40 @@ def denoise_defaults():
     lib.dmt_denoise_defaults.restype = DenoiseParams
     p = lib.dmt_denoise_defaults()
     return {name: getattr(p, name) for name, _ in DenoiseParams._fields_}
+
+
+
+class TemporalParams(C.Structure):
+    """dmt_temporal_params (include/dmt_hip.h)"""
+    _fields_ = [("alpha", C.c_float), ("normal_threshold", C.c_float), ("plane_threshold", C.c_float)]
+
+
+class TemporalRecord(C.Structure):
+    """dmt_temporal_record (include/dmt_hip.h)"""
+    _fields_ = [("frames", C.c_uint32), ("reprojected", C.c_uint32), ("reset", C.c_uint32), ("temporal_ms", C.c_float),
+                ("history_bytes", C.c_uint64)]
+
+
+def temporal_defaults():
+    """dmt_temporal_defaults() as a dict: alpha, normal_threshold, plane_threshold."""
+    lib = load_library()
+    lib.dmt_temporal_defaults.restype = TemporalParams
+    p = lib.dmt_temporal_defaults()
+    return {name: getattr(p, name) for name, _ in TemporalParams._fields_}
+
+
+def camera_project(camera44, points):
+    """Host only (dmt_camera_project): render-space points [n, 3] -> (film coordinates [n, 2], camera-space depth [n])."""
+    lib = load_library()
+    cam = np.ascontiguousarray(camera44, np.uint8).reshape(44)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    xy, depth = np.zeros((p.shape[0], 2), np.float32), np.zeros(p.shape[0], np.float32)
+    rc = lib.dmt_camera_project(cam.ctypes.data_as(C.c_void_p), int(p.shape[0]), p.ctypes.data_as(C.c_void_p),
+                                xy.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise DmtError(f"dmt_camera_project failed ({rc})")
+    return xy, depth
+
 
 # dmt_set_texture_filter modes (include/dmt_hip.h)
 TEXFILTER_LEVEL0 = 0
@@ -576,6 +612,69 @@ class Renderer:
         self._check(self._lib.dmt_denoise(self._ctx, C.byref(cp), _p(mean), _p(m2), _p(out), C.byref(ms)), "dmt_denoise")
         self.denoise_ms = ms.value
         return out
+
+    # ---- temporal accumulation ------------------------------------------------
+    def download_aov_surface(self):
+        """The surface plane of the AOVs, H x W x 4 float32: (triangle, bu, bv, 1) of the first camera sample that hit."""
+        h, w = self._aov_shape or (self.height, self.width)
+        out = np.zeros((h, w, 4), np.float32)
+        self._check(self._lib.dmt_download_aov_surface(self._ctx, _p(out)), "dmt_download_aov_surface")
+        return out
+
+    def upload_aov_surface(self, surface):
+        """A host surface plane (H x W x 4) of the size of the context's AOVs; upload_aovs() drops it, so it comes after."""
+        s = _f32(surface)
+        assert s.ndim == 3 and s.shape[2] == 4
+        self._check(self._lib.dmt_upload_aov_surface(self._ctx, _p(s), int(s.shape[1]), int(s.shape[0])), "dmt_upload_aov_surface")
+
+    def denoise_temporal(self, params=None, temporal=None, film=None):
+        """dmt_denoise_temporal: denoise() with the previous call's accumulated plane reprojected into this frame.
+        `temporal`: a dict overriding temporal_defaults().  The a-trous passes' and the reprojection's HIP-event time lands in
+        self.denoise_ms; temporal_info() has the reprojection's own."""
+        p = denoise_defaults()
+        t = temporal_defaults()
+        unknown = (set(params or {}) - set(p)) | (set(temporal or {}) - set(t))
+        if unknown:
+            raise ValueError(f"unknown denoise parameters {sorted(unknown)}")
+        p.update(params or {})
+        t.update(temporal or {})
+        cp = DenoiseParams(int(p["iterations"]), float(p["sigma_normal"]), float(p["sigma_position"]), float(p["sigma_albedo"]),
+                           float(p["sigma_luminance"]))
+        ct = TemporalParams(float(t["alpha"]), float(t["normal_threshold"]), float(t["plane_threshold"]))
+        mean = m2 = None
+        if film is not None:
+            mean, m2 = _f32(film[0]), _f32(film[1])
+            assert mean.shape == m2.shape == (self.height, self.width, 4)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        ms = C.c_float()
+        self._check(self._lib.dmt_denoise_temporal(self._ctx, C.byref(cp), C.byref(ct), _p(mean), _p(m2), _p(out), C.byref(ms)),
+                    "dmt_denoise_temporal")
+        self.denoise_ms = ms.value
+        return out
+
+    def temporal_reset(self):
+        """Forget the history: the next denoise_temporal() starts at h = 1."""
+        self._check(self._lib.dmt_temporal_reset(self._ctx), "dmt_temporal_reset")
+
+    def temporal_info(self):
+        """dict(frames, reprojected, reset, temporal_ms, history_bytes) of the history and the last temporal call."""
+        rec = TemporalRecord()
+        self._check(self._lib.dmt_temporal_info(self._ctx, C.byref(rec)), "dmt_temporal_info")
+        return {name: getattr(rec, name) for name, _ in TemporalRecord._fields_}
+
+    def download_history(self):
+        """The history: (accumulated (rgb, variance of the mean) H x W x 4, length H x W), float32."""
+        cv = np.zeros((self.height, self.width, 4), np.float32)
+        ln = np.zeros((self.height, self.width), np.float32)
+        self._check(self._lib.dmt_temporal_download(self._ctx, _p(cv), _p(ln)), "dmt_temporal_download")
+        return cv, ln
+
+    def test_camera_project(self, points):
+        """dmt_test_camera_project: camera_project() on the device under the context's camera."""
+        p = _f32(points).reshape(-1, 3)
+        xy, depth = np.zeros((p.shape[0], 2), np.float32), np.zeros(p.shape[0], np.float32)
+        self._check(self._lib.dmt_test_camera_project(self._ctx, int(p.shape[0]), _p(p), _p(xy), _p(depth)), "dmt_test_camera_project")
+        return xy, depth
 
     def sync(self):
         self._check(self._lib.dmt_sync(self._ctx), "dmt_sync")

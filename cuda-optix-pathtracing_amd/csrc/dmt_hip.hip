@@ -2323,10 +2323,12 @@ __global__ void k_test_closest(RenderParams P, bool useBvh, int n, float const* 
 //                                                   BS_GGX_BLEND: (1 - mix) W_diel + mix W_cond, mix clamped to [0, 1]
 //   normal   = (normalize(sum ns) or 0 when |sum| < 1e-6, 0)   ns = hit_finish's face-forwarded or the normal-mapped normal
 //   position = (sum pos / hits, sum t / hits), 0 without hits
+//   surface  = (tri, bu, bv, 1) of the first sample that hit, tri the original index as a float; (-1, 0, 0, 0) without hits
 struct AovArgs {
   float4* albedo;
   float4* normal;
   float4* position;
+  float4* surface;
   int width;
   uint32_t pixels, aovSpp;
   bool useBvh;
@@ -2410,6 +2412,7 @@ __global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
         f3 W, ns;
         aov_material(k, hit, best, bu, bv, W, ns);
         sumW = sumW + W, sumN = sumN + ns, sumP = sumP + hit.pos, sumT += t;
+        if (hits == 0) A.surface[i] = make_float4(float(best), bu, bv, 1.f);  // stored here: nothing more to keep across the loop
         ++hits;
       }
     }
@@ -2421,6 +2424,7 @@ __global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
       A.normal[i] = make_float4(n.x, n.y, n.z, 0.f);
       float const h = float(hits);
       A.position[i] = hits ? make_float4(sumP.x / h, sumP.y / h, sumP.z / h, sumT / h) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!hits) A.surface[i] = make_float4(-1.f, 0.f, 0.f, 0.f);
     }
   }
 }
@@ -2525,6 +2529,147 @@ __global__ void __launch_bounds__(256) k_atrous(DenoiseArgs A) {
     }
   }
   A.dst[p] = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+}
+
+// Temporal accumulation (dmt_denoise_temporal).
+// World-to-film projection, the inverse of camera_ray's film-to-ray map: render-space point -> the continuous film
+// coordinates camera_ray calls (fx, fy), and the camera-space depth.  fp32, no contraction, one order of operations for the
+// host (dmt_camera_project) and the device; tests/temporal_ref.py restates it.
+struct ProjXf {
+  float right[3], up[3], fwd[3];  // rows of camera-from-render's rotation (the columns of CameraXf::rfc)
+  float pos[3];
+  float focal, tx, ty;            // cameraFromRaster: x_cam = fx / ipx + tx, y_cam = fy / ipy + ty at z_cam = focal
+  float ipx, ipy;                 // 1 / psx, 1 / -psy
+};
+struct Proj {
+  float fx, fy, depth;
+};
+// a / b: IEEE on the host; on the device v_rcp_f32 plus one residual step, which rounds as the host does except in rare
+// half-way cases (the library's device `/` is the 2.5-ulp one, see the Makefile)
+__host__ __device__ inline float proj_div(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  float const r = __builtin_amdgcn_rcpf(b);
+  float const q = a * r;
+  return __builtin_fmaf(__builtin_fmaf(-q, b, a), r, q);
+#else
+  return a / b;
+#endif
+}
+__host__ __device__ inline Proj project_point(ProjXf const& c, float x, float y, float z) {
+#pragma clang fp contract(off)
+  float const dx = x - c.pos[0], dy = y - c.pos[1], dz = z - c.pos[2];
+  float const cx = (c.right[0] * dx + c.right[1] * dy) + c.right[2] * dz;
+  float const cy = (c.up[0] * dx + c.up[1] * dy) + c.up[2] * dz;
+  float const cz = (c.fwd[0] * dx + c.fwd[1] * dy) + c.fwd[2] * dz;
+  float const s = proj_div(c.focal, cz);
+  Proj o;
+  o.fx = (cx * s - c.tx) * c.ipx;
+  o.fy = (cy * s - c.ty) * c.ipy;
+  o.depth = cz;
+  return o;
+}
+__global__ void k_test_project(ProjXf c, int n, float const* p3, float* xy2, float* depth) {
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  Proj const o = project_point(c, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]);
+  xy2[2 * i] = o.fx, xy2[2 * i + 1] = o.fy, depth[i] = o.depth;
+}
+// X = w0 p0 + bu p1 + bv p2, w0 = (1 - bu) - bv, left to right per component; v = the triangle's 9 raw floats
+DMT_DEV f3 surface_point(float const* v, float bu, float bv) {
+#pragma clang fp contract(off)
+  float const w0 = (1.f - bu) - bv;
+  return mk3((w0 * v[0] + bu * v[3]) + bv * v[6], (w0 * v[1] + bu * v[4]) + bv * v[7], (w0 * v[2] + bu * v[5]) + bv * v[8]);
+}
+struct TemporalArgs {
+  float4 const* cur;        // (rgb, v0) of the current film: k_denoise_init's plane
+  float4 const* albedo;     // the current AOVs
+  float4 const* normal;
+  float4 const* surface;
+  float const* vertsCur;    // 9 floats per triangle: the current frame's, the history frame's (may be the same array)
+  float const* vertsPrev;
+  float4 const* histCv;     // the history: accumulated (rgb, v), length, and the normal / position planes of its frame
+  float const* histLen;
+  float4 const* histNormal;
+  float4 const* histPos;
+  float4* outCv;            // the new history (the other half of the ping-pong)
+  float* outLen;
+  uint32_t* counts;         // [0] pixels reprojected, [1] pixels reset
+  ProjXf camCur, camPrev;
+  int width, height;
+  uint32_t triCount;
+  int haveHistory;          // 0: every pixel is reset
+  float alpha, normalThreshold, planeThreshold;
+  float thetaPrev;          // one pixel's angle under the history frame's camera
+};
+// one lane per pixel; block = 64 x 4 pixels, a wave = 64 pixels of one row, as k_atrous
+__global__ void __launch_bounds__(256) k_temporal(TemporalArgs A) {
+#pragma clang fp contract(off)
+  int const px = int(blockIdx.x) * 64 + int(threadIdx.x & 63u), py = int(blockIdx.y) * 4 + int(threadIdx.x >> 6);
+  bool const inside = px < A.width && py < A.height;
+  bool reproj = false, reset = false;
+  if (inside) {
+    size_t const W = size_t(A.width);
+    size_t const p = size_t(py) * W + size_t(px);
+    float4 const cc = A.cur[p];
+    bool const covered = A.albedo[p].w > 0.f;
+    float4 out = cc;
+    float hOut = covered ? 1.f : 0.f;
+    float4 const sf = A.surface[p];
+    // the index test also turns away a NaN and anything outside the vertex arrays
+    if (covered && A.haveHistory && sf.x >= 0.f && sf.x < float(A.triCount)) {
+      size_t const tri = size_t(uint32_t(sf.x));
+      f3 const Xc = surface_point(A.vertsCur + 9 * tri, sf.y, sf.z), Xp = surface_point(A.vertsPrev + 9 * tri, sf.y, sf.z);
+      Proj const qc = project_point(A.camCur, Xc.x, Xc.y, Xc.z), qp = project_point(A.camPrev, Xp.x, Xp.y, Xp.z);
+      float const u = float(px) + (qp.fx - qc.fx), v = float(py) + (qp.fy - qc.fy);
+      // inside (-1, width) x (-1, height): some tap of the 2 x 2 footprint can be in the image; false for a NaN
+      if (qp.depth > 0.f && u > -1.f && u < float(A.width) && v > -1.f && v < float(A.height)) {
+        float const fu0 = floorf(u), fv0 = floorf(v);
+        int const iu = int(fu0), iv = int(fv0);
+        float const fu = u - fu0, fv = v - fv0;
+        float4 const np = A.normal[p];
+        float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f, sh = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          int const qx = iu + (t & 1), qy = iv + (t >> 1);
+          float const w = ((t & 1) ? fu : 1.f - fu) * ((t >> 1) ? fv : 1.f - fv);
+          if (!(w > 0.f) || qx < 0 || qx >= A.width || qy < 0 || qy >= A.height) continue;
+          size_t const q = size_t(qy) * W + size_t(qx);
+          float const hq = A.histLen[q];
+          if (!(hq >= 1.f)) continue;
+          float4 const nq = A.histNormal[q];
+          float const nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+          if (!(nd >= A.normalThreshold)) continue;
+          float4 const xq = A.histPos[q];
+          float const pd = fabsf((nq.x * (Xp.x - xq.x) + nq.y * (Xp.y - xq.y)) + nq.z * (Xp.z - xq.z));
+          if (!(pd <= (A.planeThreshold * xq.w) * A.thetaPrev)) continue;
+          float4 const cq = A.histCv[q];
+          sw = sw + w;
+          sr = sr + w * cq.x, sg = sg + w * cq.y, sb = sb + w * cq.z;
+          sv = sv + (w * w) * cq.w;
+          sh = sh + w * hq;
+        }
+        if (sw > 0.f) {
+          reproj = true;
+          float const h = fminf(sh / sw + 1.f, 65536.f);
+          float const a = fmaxf(A.alpha, 1.f / h);
+          hOut = h;
+          if (a < 1.f) {  // a = 1 is the current frame itself, bit for bit
+            float const pr = sr / sw, pg = sg / sw, pb = sb / sw, pv = sv / (sw * sw);
+            float const b = 1.f - a;
+            out = make_float4(pr + a * (cc.x - pr), pg + a * (cc.y - pg), pb + a * (cc.z - pb), (b * b) * pv + (a * a) * cc.w);
+          }
+        }
+      }
+    }
+    reset = covered && !reproj;
+    A.outCv[p] = out;
+    A.outLen[p] = hOut;
+  }
+  unsigned long long const br = __ballot(reproj), bs = __ballot(reset);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (br != 0ull) atomicAdd(A.counts, uint32_t(__popcll(br)));
+    if (bs != 0ull) atomicAdd(A.counts + 1, uint32_t(__popcll(bs)));
+  }
 }
 
 }  // namespace
@@ -2635,6 +2780,23 @@ struct dmt_ctx {
   int aovW = 0, aovH = 0;
   DevBuf<float4> d_dnFilm, d_dnCv;
   DevBuf<uint32_t> d_dnBad;
+  // temporal accumulation (dmt_denoise_temporal).  The surface plane belongs to the AOVs; everything else is
+  // allocated by the first temporal call (temporalOn), never before
+  DevBuf<float4> d_aovSurface;
+  bool aovSurface = false;          // the surface plane matches the three AOV planes
+  bool temporalOn = false;          // a temporal call was made: the updates keep d_tvCur current
+  DevBuf<float4> d_thCv[2];         // accumulated (rgb, v), ping-pong; thSlot is the history
+  DevBuf<float> d_thLen[2];
+  DevBuf<float4> d_thNormal, d_thPos;  // the planes of the history's frame
+  DevBuf<uint32_t> d_thCounts;      // [0] reprojected, [1] reset
+  DevBuf<float> d_tvCur, d_tvPrev;  // raw vertices, 9 per triangle: current, and the history frame's once they differ
+  bool tvValid = false;             // d_tvCur holds the uploaded soup
+  bool tvPrevIsCur = true;          // no update since the history's frame: d_tvCur serves as both
+  int thSlot = 0, thW = 0, thH = 0;
+  bool thValid = false;             // false: the next call resets every pixel
+  ProjXf thCam{};                   // the camera of the history's frame, and its pixel angle
+  float thTheta = 0.f;
+  dmt_temporal_record thRecord{};
   uint32_t chunkSpp = 0;          // samples per work item, 0 = automatic
   int subShift = -1;               // row bands per tile (log2); -1 = choose per launch
   int maxDepth = 32;
@@ -3512,6 +3674,8 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
   ctx->h_mat.assign(mat_id, mat_id + count);
   ctx->haveBvh = false;
+  ctx->thValid = false, ctx->tvValid = false;  // temporal history: its triangle indices are of the soup just replaced
+  ctx->thRecord.frames = 0;
   ctx->h_areaTri.clear(), ctx->h_areaLe.clear();  // emissive triangles are indices into the soup just replaced
   if (int const rcA = rebuildAreaLights(ctx)) return rcA;
   if (ctx->accel == DMT_ACCEL_BVH) return buildBvh(ctx);
@@ -3519,6 +3683,30 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
 }
 
 namespace {
+// temporal accumulation: the raw vertices of the current soup, 9 floats per triangle, from the host copy.  The caller has
+// drained the stream (a kernel in flight may read the array)
+int uploadRawVertices(dmt_ctx* ctx) {
+  size_t const n = ctx->triCount;
+  std::vector<float> v(9 * n);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < 3; ++k)
+      v[9 * i + 3 * k] = ctx->h_xs[4 * i + k], v[9 * i + 3 * k + 1] = ctx->h_ys[4 * i + k], v[9 * i + 3 * k + 2] = ctx->h_zs[4 * i + k];
+  HIP_TRY(ctx, ctx->d_tvCur.assign(v.data(), v.size()));
+  ctx->tvValid = true;
+  return DMT_OK;
+}
+// before an update overwrites d_tvCur: the first update after the history's frame moves that frame's vertices to d_tvPrev
+// (beginUpdate has drained the stream).  wait: the overwrite is a host copy, not a launch on the stream.  Without a history
+// there is no such frame
+int keepHistoryVertices(dmt_ctx* ctx, bool wait) {
+  if (!ctx->tvPrevIsCur || !ctx->thValid) return DMT_OK;
+  size_t const n = 9 * size_t(ctx->triCount);
+  HIP_TRY(ctx, ctx->d_tvPrev.reserve(n ? n : 1));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tvPrev.get(), ctx->d_tvCur.get(), n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  if (wait) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->tvPrevIsCur = false;
+  return DMT_OK;
+}
 // common entry of the two updates: argument and state checks, the stream drained, the timer started.  *done: nothing to do
 int beginUpdate(dmt_ctx* ctx, char const* name, bool nullArray, size_t count, UpdateTimer& T, bool* done) {
   *done = false;
@@ -3556,6 +3744,10 @@ int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const fl
   HIP_TRY(ctx, hipMemcpy(ctx->d_post.get(), b.data(), count * sizeof(TriPost), hipMemcpyHostToDevice));
   adoptCullTables(ctx, cull);
   ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
+  if (ctx->temporalOn && ctx->tvValid) {
+    if (int const rcT = keepHistoryVertices(ctx, true)) return rcT;
+    if (int const rcT = uploadRawVertices(ctx)) return rcT;
+  }
   return finishUpdate(ctx, T);
 }
 
@@ -3565,6 +3757,10 @@ int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count)
   if (int const rc = beginUpdate(ctx, "dmt_update_vertices_device", !d_verts9, count, T, &done)) return rc;
   if (done) return DMT_OK;
   HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->d_tris.get(), ctx->d_post.get(), ctx->stream));
+  if (ctx->temporalOn && ctx->tvValid) {  // the caller's array has the layout of d_tvCur
+    if (int const rcT = keepHistoryVertices(ctx, false)) return rcT;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tvCur.get(), d_verts9, count * 9 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  }
   // the host mirrors (the host builder's, the cull plan's and a later rebuild's input) from the records just made
   std::vector<TriPost> b(count);
   HIP_TRY(ctx, hipMemcpyAsync(b.data(), ctx->d_post.get(), count * sizeof(TriPost), hipMemcpyDeviceToHost, ctx->stream));
@@ -3670,6 +3866,7 @@ int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam) {
     ctx->ownMean = std::move(mean), ctx->ownM2 = std::move(m2);
     ctx->d_mean = ctx->ownMean.get(), ctx->d_m2 = ctx->ownM2.get();
     ctx->filmW = cam->width, ctx->filmH = cam->height;
+    ctx->thValid = false, ctx->thRecord.frames = 0;  // temporal history: it is of the old resolution
   }
   ctx->cam = *cam;
   float m[16];
@@ -4704,19 +4901,23 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
   ctx->aovW = ctx->aovH = 0;  // no AOVs unless this call succeeds
+  ctx->aovSurface = false;
   HIP_TRY(ctx, ctx->d_aovAlbedo.reserve(pixels));
   HIP_TRY(ctx, ctx->d_aovNormal.reserve(pixels));
   HIP_TRY(ctx, ctx->d_aovPos.reserve(pixels));
+  HIP_TRY(ctx, ctx->d_aovSurface.reserve(pixels));
   // a grid of a few 256-lane blocks per CU strides over the frame: the BVH overflow stack is sized by the launch's lanes
   size_t const blocks = std::min((pixels + 255) / 256, size_t(std::max(ctx->cuCount, 1)) * 8);
   size_t const threads = blocks * 256;
   if (useBvh) HIP_TRY(ctx, reserveOverflow(ctx, threads));
   AovArgs A{};
   A.albedo = ctx->d_aovAlbedo.get(), A.normal = ctx->d_aovNormal.get(), A.position = ctx->d_aovPos.get();
+  A.surface = ctx->d_aovSurface.get();
   A.width = ctx->filmW, A.pixels = uint32_t(pixels), A.aovSpp = aov_spp, A.useBvh = useBvh;
   hipLaunchKernelGGL(k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, baseParams(ctx, threads), A);
   HIP_TRY(ctx, hipGetLastError());
   ctx->aovW = ctx->filmW, ctx->aovH = ctx->filmH;
+  ctx->aovSurface = true;
   return DMT_OK;
 }
 
@@ -4728,6 +4929,7 @@ int dmt_upload_aovs(dmt_ctx* ctx, const float* albedo4, const float* normal4, co
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a feature pass in flight writes the same planes
   size_t const pixels = size_t(width) * size_t(height);
   ctx->aovW = ctx->aovH = 0;
+  ctx->aovSurface = false;  // the surface plane is uploaded after these (dmt_upload_aov_surface)
   HIP_TRY(ctx, ctx->d_aovAlbedo.assign(albedo4, pixels));
   HIP_TRY(ctx, ctx->d_aovNormal.assign(normal4, pixels));
   HIP_TRY(ctx, ctx->d_aovPos.assign(position4, pixels));
@@ -4747,25 +4949,71 @@ int dmt_download_aovs(dmt_ctx* ctx, float* albedo4, float* normal4, float* posit
   return DMT_OK;
 }
 
-// k_denoise_init (validation + pass-0 planes), then `iterations` k_atrous passes ping-ponging between two planes
-int dmt_denoise(dmt_ctx* ctx, const dmt_denoise_params* params, const float* mean4, const float* m24, float* out4, float* kernel_ms) {
+namespace {
+ProjXf makeProjXf(dmt_camera const& cam) {
+  float cf[16], rf[16];
+  cameraFromRaster(cam.focal_length, cam.sensor_size, uint32_t(cam.width), uint32_t(cam.height), cf);
+  worldFromCamera(cam.dir, cam.pos, rf);
+  ProjXf c{};
+  for (int a = 0; a < 3; ++a) c.right[a] = rf[a], c.up[a] = rf[4 + a], c.fwd[a] = rf[8 + a], c.pos[a] = rf[12 + a];
+  c.focal = cf[14], c.tx = cf[12], c.ty = cf[13];
+  c.ipx = 1.0f / cf[0], c.ipy = 1.0f / cf[5];
+  return c;
+}
+size_t temporalBytes(dmt_ctx const* ctx) {
+  return (ctx->d_thCv[0].size() + ctx->d_thCv[1].size() + ctx->d_thNormal.size() + ctx->d_thPos.size()) * sizeof(float4) +
+         (ctx->d_thLen[0].size() + ctx->d_thLen[1].size() + ctx->d_tvCur.size() + ctx->d_tvPrev.size()) * sizeof(float) +
+         ctx->d_thCounts.size() * sizeof(uint32_t);
+}
+// the first temporal call, a new resolution, a new soup: the history's planes and the current raw vertices
+int prepareHistory(dmt_ctx* ctx, size_t pixels) {
+  if (ctx->thW != ctx->filmW || ctx->thH != ctx->filmH) ctx->thValid = false;
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(ctx, ctx->d_thCv[i].reserve(pixels));
+    HIP_TRY(ctx, ctx->d_thLen[i].reserve(pixels));
+  }
+  HIP_TRY(ctx, ctx->d_thNormal.reserve(pixels));
+  HIP_TRY(ctx, ctx->d_thPos.reserve(pixels));
+  HIP_TRY(ctx, ctx->d_thCounts.reserve(2));
+  ctx->thW = ctx->filmW, ctx->thH = ctx->filmH;
+  if (!ctx->tvValid) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int const rc = uploadRawVertices(ctx)) return rc;
+    ctx->tvPrevIsCur = true;
+  }
+  if (!ctx->thValid) ctx->tvPrevIsCur = true, ctx->thRecord.frames = 0;  // no history frame whose vertices matter
+  ctx->temporalOn = true;
+  return DMT_OK;
+}
+
+// k_denoise_init (validation + pass-0 planes), then `iterations` k_atrous passes ping-ponging between two planes.  tp (the
+// temporal form): k_temporal between the two blends the pass-0 plane with the reprojected history into the new history,
+// which pass 0 then reads in place
+int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params, const dmt_temporal_params* tp, const float* mean4,
+               const float* m24, float* out4, float* kernel_ms) {
   if (!ctx) return DMT_ERR_INVALID;
   if (kernel_ms) *kernel_ms = 0.f;
   dmt_denoise_params const p = params ? *params : dmt_denoise_defaults();
-  if (!out4 || (mean4 == nullptr) != (m24 == nullptr))
-    return fail(ctx, DMT_ERR_INVALID, "dmt_denoise: out4 is required, and mean4 / m24 come both or not at all");
-  if (p.iterations < 0 || p.iterations > 10) return fail(ctx, DMT_ERR_INVALID, "dmt_denoise: iterations must be 0 .. 10");
+  std::string const pre = std::string(name) + ": ";
+  auto failn = [&](int code, char const* msg) { return fail(ctx, code, (pre + msg).c_str()); };
+  if (!out4 || (mean4 == nullptr) != (m24 == nullptr)) return failn(DMT_ERR_INVALID, "out4 is required, and mean4 / m24 come both or not at all");
+  if (p.iterations < 0 || p.iterations > 10) return failn(DMT_ERR_INVALID, "iterations must be 0 .. 10");
   auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
   if (!positive(p.sigma_normal) || !positive(p.sigma_position) || !positive(p.sigma_albedo) || !positive(p.sigma_luminance))
-    return fail(ctx, DMT_ERR_INVALID, "dmt_denoise: every sigma must be finite and > 0");
-  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_denoise: set the camera first");
-  if (ctx->aovW == 0) return fail(ctx, DMT_ERR_STATE, "dmt_denoise: no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
+    return failn(DMT_ERR_INVALID, "every sigma must be finite and > 0");
+  if (tp && (!(tp->alpha >= 0.f && tp->alpha <= 1.f) || !std::isfinite(tp->normal_threshold) || !positive(tp->plane_threshold)))
+    return failn(DMT_ERR_INVALID, "alpha must be 0 .. 1, normal_threshold finite, plane_threshold finite and > 0");
+  if (!ctx->haveCamera) return failn(DMT_ERR_STATE, "set the camera first");
+  if (ctx->aovW == 0) return failn(DMT_ERR_STATE, "no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
   if (ctx->aovW != ctx->filmW || ctx->aovH != ctx->filmH) {
     char msg[160];
-    snprintf(msg, sizeof(msg), "dmt_denoise: the AOVs are %d x %d, the film %d x %d", ctx->aovW, ctx->aovH, ctx->filmW, ctx->filmH);
-    return fail(ctx, DMT_ERR_STATE, msg);
+    snprintf(msg, sizeof(msg), "the AOVs are %d x %d, the film %d x %d", ctx->aovW, ctx->aovH, ctx->filmW, ctx->filmH);
+    return failn(DMT_ERR_STATE, msg);
   }
-  if (!mean4 && !ctx->d_mean) return fail(ctx, DMT_ERR_STATE, "dmt_denoise: no film");
+  if (tp && !ctx->aovSurface) return failn(DMT_ERR_STATE, "no surface plane (call dmt_render_aovs, or dmt_upload_aov_surface after dmt_upload_aovs)");
+  if (tp && !ctx->haveTris) return failn(DMT_ERR_STATE, "upload triangles first");
+  if (tp && ctx->triCount > (1u << 24)) return failn(DMT_ERR_STATE, "more than 2^24 triangles: the surface plane's float index is not exact");
+  if (!mean4 && !ctx->d_mean) return failn(DMT_ERR_STATE, "no film");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
   float4 const* mean = ctx->d_mean;
@@ -4779,46 +5027,175 @@ int dmt_denoise(dmt_ctx* ctx, const dmt_denoise_params* params, const float* mea
   }
   HIP_TRY(ctx, ctx->d_dnCv.reserve(2 * pixels));
   HIP_TRY(ctx, ctx->d_dnBad.reserve(1));
+  if (tp)
+    if (int const rc = prepareHistory(ctx, pixels)) return rc;
   float4* const cv[2] = {ctx->d_dnCv.get(), ctx->d_dnCv.get() + pixels};
   DenoiseArgs A{};
   A.mean = mean, A.m2 = m2, A.albedo = ctx->d_aovAlbedo.get(), A.normal = ctx->d_aovNormal.get(), A.position = ctx->d_aovPos.get();
   A.bad = ctx->d_dnBad.get(), A.width = ctx->filmW, A.height = ctx->filmH;
   A.theta = ctx->cam.sensor_size / (ctx->cam.focal_length * float(ctx->cam.height));
   A.sigmaN = p.sigma_normal, A.sigmaX = p.sigma_position, A.sigmaA = p.sigma_albedo, A.sigmaL = p.sigma_luminance;
-  EventPair ev;
+  EventPair ev, evT;
   HIP_TRY(ctx, hipEventCreate(&ev.e[0]));
   HIP_TRY(ctx, hipEventCreate(&ev.e[1]));
   HIP_TRY(ctx, hipMemsetAsync(A.bad, 0, sizeof(uint32_t), ctx->stream));
+  if (tp) {
+    HIP_TRY(ctx, hipEventCreate(&evT.e[0]));
+    HIP_TRY(ctx, hipEventCreate(&evT.e[1]));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_thCounts.get(), 0, 2 * sizeof(uint32_t), ctx->stream));
+  }
   HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
   A.dst = cv[0];
   hipLaunchKernelGGL(k_denoise_init, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, ctx->stream, A);
   HIP_TRY(ctx, hipGetLastError());
   dim3 const grid(uint32_t((ctx->filmW + 63) / 64), uint32_t((ctx->filmH + 3) / 4));
+  int const slotNew = ctx->thSlot ^ 1;
+  ProjXf const camCur = tp ? makeProjXf(ctx->cam) : ProjXf{};
+  if (tp) {
+    TemporalArgs T{};
+    T.cur = cv[0], T.albedo = A.albedo, T.normal = A.normal, T.surface = ctx->d_aovSurface.get();
+    T.vertsCur = ctx->d_tvCur.get(), T.vertsPrev = ctx->tvPrevIsCur ? ctx->d_tvCur.get() : ctx->d_tvPrev.get();
+    T.histCv = ctx->d_thCv[ctx->thSlot].get(), T.histLen = ctx->d_thLen[ctx->thSlot].get();
+    T.histNormal = ctx->d_thNormal.get(), T.histPos = ctx->d_thPos.get();
+    T.outCv = ctx->d_thCv[slotNew].get(), T.outLen = ctx->d_thLen[slotNew].get();
+    T.counts = ctx->d_thCounts.get();
+    T.camCur = camCur, T.camPrev = ctx->thValid ? ctx->thCam : camCur;
+    T.width = ctx->filmW, T.height = ctx->filmH, T.triCount = ctx->triCount, T.haveHistory = ctx->thValid ? 1 : 0;
+    T.alpha = tp->alpha, T.normalThreshold = tp->normal_threshold, T.planeThreshold = tp->plane_threshold;
+    T.thetaPrev = ctx->thValid ? ctx->thTheta : A.theta;
+    HIP_TRY(ctx, hipEventRecord(evT.e[0], ctx->stream));
+    hipLaunchKernelGGL(k_temporal, grid, dim3(256), 0, ctx->stream, T);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(evT.e[1], ctx->stream));
+  }
+  float4 const* result = tp ? ctx->d_thCv[slotNew].get() : cv[0];
   for (int i = 0; i < p.iterations; ++i) {
-    A.src = cv[i & 1], A.dst = cv[(i + 1) & 1], A.step = 1 << i;
+    A.src = result, A.dst = cv[(i + 1) & 1], A.step = 1 << i;
     for (int dy = -2; dy <= 2; ++dy)
       for (int dx = -2; dx <= 2; ++dx) A.tapDist[5 * (dy + 2) + dx + 2] = float(A.step) * std::sqrt(float(dx * dx + dy * dy));
     hipLaunchKernelGGL(k_atrous, grid, dim3(256), 0, ctx->stream, A);
     HIP_TRY(ctx, hipGetLastError());
+    result = A.dst;
   }
   HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
-  uint32_t bad = 0;
+  uint32_t bad = 0, counts[2] = {0, 0};
   HIP_TRY(ctx, hipMemcpyAsync(&bad, A.bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+  if (tp) HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->d_thCounts.get(), sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (!mean4)
     if (int const rc = checkErrorFlag(ctx)) return rc;
   if (bad) {
     char msg[400];
-    snprintf(msg, sizeof(msg), "dmt_denoise: %u pixel(s) have fewer than 2 samples or a non-finite mean / M2%s", bad,
+    snprintf(msg, sizeof(msg), "%u pixel(s) have fewer than 2 samples or a non-finite mean / M2%s", bad,
              !mean4 && ctx->world > 1 ? " (this context renders only the tiles of its dmt_set_partition rank: combine the ranks' "
                                         "films and pass the combined film as mean4 / m24)" : "");
-    return fail(ctx, DMT_ERR_STATE, msg);
+    return failn(DMT_ERR_STATE, msg);
   }
   float ms = 0.f;
   HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
   if (kernel_ms) *kernel_ms = ms;
-  HIP_TRY(ctx, hipMemcpy(out4, cv[p.iterations & 1], pixels * sizeof(float4), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(out4, result, pixels * sizeof(float4), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < pixels; ++i) out4[4 * i + 3] = 1.f;
+  if (tp) {  // the call succeeded: its plane, its AOVs, its camera and its vertices become the history
+    float msT = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&msT, evT.e[0], evT.e[1]));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_thNormal.get(), ctx->d_aovNormal.get(), pixels * sizeof(float4), hipMemcpyDeviceToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_thPos.get(), ctx->d_aovPos.get(), pixels * sizeof(float4), hipMemcpyDeviceToDevice));
+    ctx->thSlot = slotNew, ctx->thValid = true, ctx->tvPrevIsCur = true;
+    ctx->thCam = camCur, ctx->thTheta = A.theta;
+    ctx->thRecord.frames += 1, ctx->thRecord.reprojected = counts[0], ctx->thRecord.reset = counts[1], ctx->thRecord.temporal_ms = msT;
+  }
+  return DMT_OK;
+}
+}  // namespace
+
+int dmt_denoise(dmt_ctx* ctx, const dmt_denoise_params* params, const float* mean4, const float* m24, float* out4, float* kernel_ms) {
+  return denoiseRun(ctx, "dmt_denoise", params, nullptr, mean4, m24, out4, kernel_ms);
+}
+
+// ---- temporal accumulation ---------------------------------------------------------
+dmt_temporal_params dmt_temporal_defaults(void) {
+  dmt_temporal_params p;
+  p.alpha = 0.2f, p.normal_threshold = 0.9f, p.plane_threshold = 2.f;
+  return p;
+}
+
+int dmt_denoise_temporal(dmt_ctx* ctx, const dmt_denoise_params* params, const dmt_temporal_params* tparams, const float* mean4,
+                         const float* m24, float* out4, float* kernel_ms) {
+  dmt_temporal_params const tp = tparams ? *tparams : dmt_temporal_defaults();
+  return denoiseRun(ctx, "dmt_denoise_temporal", params, &tp, mean4, m24, out4, kernel_ms);
+}
+
+int dmt_temporal_reset(dmt_ctx* ctx) {
+  if (!ctx) return DMT_ERR_INVALID;
+  ctx->thValid = false;
+  ctx->thRecord.frames = 0;
+  return DMT_OK;
+}
+
+int dmt_temporal_info(dmt_ctx* ctx, dmt_temporal_record* out) {
+  if (!ctx || !out) return DMT_ERR_INVALID;
+  *out = ctx->thRecord;
+  out->history_bytes = temporalBytes(ctx);
+  return DMT_OK;
+}
+
+int dmt_temporal_download(dmt_ctx* ctx, float* color_var4, float* length1) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->thValid) return fail(ctx, DMT_ERR_STATE, "dmt_temporal_download: no history (call dmt_denoise_temporal first)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  size_t const pixels = size_t(ctx->thW) * size_t(ctx->thH);
+  if (color_var4) HIP_TRY(ctx, hipMemcpy(color_var4, ctx->d_thCv[ctx->thSlot].get(), pixels * sizeof(float4), hipMemcpyDeviceToHost));
+  if (length1) HIP_TRY(ctx, hipMemcpy(length1, ctx->d_thLen[ctx->thSlot].get(), pixels * sizeof(float), hipMemcpyDeviceToHost));
+  return DMT_OK;
+}
+
+int dmt_download_aov_surface(dmt_ctx* ctx, float* surface4) {
+  if (!ctx || !surface4) return DMT_ERR_INVALID;
+  if (ctx->aovW == 0 || !ctx->aovSurface) return fail(ctx, DMT_ERR_STATE, "dmt_download_aov_surface: no surface plane (call dmt_render_aovs or dmt_upload_aov_surface first)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(surface4, ctx->d_aovSurface.get(), size_t(ctx->aovW) * size_t(ctx->aovH) * sizeof(float4), hipMemcpyDeviceToHost));
+  return DMT_OK;
+}
+
+int dmt_upload_aov_surface(dmt_ctx* ctx, const float* surface4, int width, int height) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!surface4 || width <= 0 || height <= 0) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_aov_surface: a plane of a positive size");
+  if (width != ctx->aovW || height != ctx->aovH)
+    return fail(ctx, DMT_ERR_STATE, "dmt_upload_aov_surface: the plane must have the size of the context's AOVs (upload or render those first)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->aovSurface = false;
+  HIP_TRY(ctx, ctx->d_aovSurface.assign(surface4, size_t(width) * size_t(height)));
+  ctx->aovSurface = true;
+  return DMT_OK;
+}
+
+int dmt_camera_project(const dmt_camera* cam, int n, const float* p3, float* xy2, float* depth) {
+  if (!cam || n < 0 || (n && (!p3 || !xy2 || !depth)) || cam->width <= 0 || cam->height <= 0) return DMT_ERR_INVALID;
+  ProjXf const c = makeProjXf(*cam);
+  for (int i = 0; i < n; ++i) {
+    Proj const o = project_point(c, p3[3 * size_t(i)], p3[3 * size_t(i) + 1], p3[3 * size_t(i) + 2]);
+    xy2[2 * size_t(i)] = o.fx, xy2[2 * size_t(i) + 1] = o.fy, depth[i] = o.depth;
+  }
+  return DMT_OK;
+}
+
+int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, float* depth) {
+  if (!ctx || n < 0 || !p3 || !xy2 || !depth) return DMT_ERR_INVALID;
+  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_camera_project: set the camera first");
+  if (n == 0) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevBuf<float> dP, dXy, dD;
+  HIP_TRY(ctx, dP.assign(p3, 3 * size_t(n)));
+  HIP_TRY(ctx, dXy.reserve(2 * size_t(n)));
+  HIP_TRY(ctx, dD.reserve(size_t(n)));
+  hipLaunchKernelGGL(k_test_project, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, makeProjXf(ctx->cam), n, dP.get(), dXy.get(), dD.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(xy2, dXy.get(), size_t(n) * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(depth, dD.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 

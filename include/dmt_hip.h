@@ -396,6 +396,55 @@ dmt_denoise_params dmt_denoise_defaults(void);
  * non-finite mean / M2 (e.g. a partitioned film that was not combined); DMT_ERR_INVALID for bad parameters. */
 int dmt_denoise(dmt_ctx* ctx, const dmt_denoise_params* params, const float* mean4, const float* m24, float* out4, float* kernel_ms);
 
+/* ---- temporal accumulation (opt-in; the "T" of SVGF with motion vectors from geometry) ------ */
+/* dmt_render_aovs also writes a fourth plane, surface = (tri, bu, bv, 1) of the first camera sample, in sample order, whose
+ * ray hit a triangle: tri = the original triangle index as a float, (bu, bv) the barycentrics of p1 and p2; (-1, 0, 0, 0)
+ * without a hit.  dmt_upload_aovs drops it: upload it after the three planes, in their size (DMT_ERR_STATE otherwise). */
+int dmt_download_aov_surface(dmt_ctx* ctx, float* surface4);
+int dmt_upload_aov_surface(dmt_ctx* ctx, const float* surface4, int width, int height);
+/* host only (no GPU): render-space points p3 (n x 3) -> xy2 (n x 2) = the continuous film coordinates (fx, fy) at which the
+ * camera's ray passes through the point (sample s of pixel (px, py) has fx = px + its pixel offset in [0, 1)), and depth (n)
+ * = the distance along the viewing direction (<= 0: behind the camera, xy2 is then meaningless).  fp32 without contraction:
+ *   d = p - pos; c = (right . d, up . d, fwd . d), each (a + b) + c; s = focal / c.z; fx = (c.x s - tx) ipx; fy = (c.y s - ty) ipy
+ * with right / up / fwd / pos of dmt_set_camera's render-from-camera matrix and focal, tx, ty, ipx = 1 / psx, ipy = -1 / psy
+ * of its camera-from-raster matrix.  dmt_test_camera_project is the device twin under the context's camera. */
+int dmt_camera_project(const dmt_camera* cam, int n, const float* p3, float* xy2, float* depth);
+typedef struct dmt_temporal_params {
+  float alpha;            /* 0 .. 1: the current frame's least share; 0 = the plain mean of the frames, 1 = no history */
+  float normal_threshold; /* finite: a history tap counts if n_p . n_prev(q) >= normal_threshold */
+  float plane_threshold;  /* finite and > 0: and if |n_prev(q) . (X_prev - x_prev(q))| <= plane_threshold t_prev(q) theta_prev */
+} dmt_temporal_params;
+dmt_temporal_params dmt_temporal_defaults(void);
+/* dmt_denoise with a history.  The current (rgb, v0) plane is blended with the previous call's accumulated plane,
+ * reprojected: for a pixel p with coverage and surface (tri, bu, bv), X = w0 p0 + bu p1 + bv p2 (w0 = (1 - bu) - bv) under
+ * the current and under the history frame's raw vertices, (u, v) = p + project_prev(X_prev) - project_cur(X_cur), the 2 x 2
+ * bilinear taps at floor(u, v).  A tap q counts if it lies in the image, h_prev(q) >= 1 and it passes the two tests above.
+ * With W = sum w > 0: c_prev = sum w c / W, v_prev = sum w^2 v / W^2, h = min(sum w h / W + 1, 65536), a = max(alpha, 1 / h),
+ * c = c_prev + a (c_cur - c_prev), v = (1 - a)^2 v_prev + a^2 v_cur (a = 1: c_cur, v_cur themselves).  Otherwise (no counted
+ * tap, no surface, depth <= 0 under the history's camera; there is no wider search): c_cur, v_cur, h = 1; without
+ * coverage h = 0.  This plane is the new history; `iterations` a-trous passes of dmt_denoise then filter it into out4.
+ * The history (allocated by the first call) also keeps the normal / position planes, the camera and the raw vertices of
+ * its frame; dmt_update_vertices[_device] keep the current vertices.  It is reset (every pixel h = 1) by
+ * dmt_upload_triangles, a change of resolution and dmt_temporal_reset.  params / tparams NULL: the defaults.  Refusals as
+ * dmt_denoise (the history is then left as it was), and DMT_ERR_STATE without a surface plane or for more than 2^24
+ * triangles, DMT_ERR_INVALID for alpha outside [0, 1], a non-finite threshold or plane_threshold <= 0.  Never modifies the
+ * film or the AOVs.  Synchronous. */
+int dmt_denoise_temporal(dmt_ctx* ctx, const dmt_denoise_params* params, const dmt_temporal_params* tparams, const float* mean4,
+                         const float* m24, float* out4, float* kernel_ms);
+/* forgets the history (its memory is kept): the next temporal call starts at h = 1 */
+int dmt_temporal_reset(dmt_ctx* ctx);
+typedef struct dmt_temporal_record {
+  uint32_t frames;        /* temporal calls accumulated since the last reset */
+  uint32_t reprojected;   /* last call: pixels that took history (at least one counted tap) */
+  uint32_t reset;         /* last call: covered pixels that took none (h = 1) */
+  float temporal_ms;      /* last call: HIP-event time of the reprojection kernel alone */
+  uint64_t history_bytes; /* device memory of the history and the vertex snapshots; 0 before the first temporal call */
+} dmt_temporal_record;
+int dmt_temporal_info(dmt_ctx* ctx, dmt_temporal_record* out);
+/* the history: color_var4 (width x height float4: accumulated rgb, variance of the mean) and length1 (width x height
+ * float), either may be NULL; DMT_ERR_STATE without a history */
+int dmt_temporal_download(dmt_ctx* ctx, float* color_var4, float* length1);
+
 /* ---- device unit-test entry points (GPU twins of the reference's T/tests kernels) ---------- */
 int dmt_test_triangle_intersect(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs,
                                 size_t count, const float* o3, const float* d3, int32_t* hit,
@@ -405,6 +454,8 @@ int dmt_test_sampler(dmt_ctx* ctx, int width, int height, int n, const int32_t* 
                      float* pixel2d, float* dims);
 int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys,
                          const int32_t* ss, float* o3, float* d3);
+/* dmt_camera_project on the device, under the camera of dmt_set_camera */
+int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, float* depth);
 int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* wo3,
                   const float* u2, const float* uc, const float* wi_eval3, float* prepared12,
                   float* sample10, float* eval4);
