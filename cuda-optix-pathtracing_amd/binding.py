@@ -77,7 +77,39 @@ EXPORTED_SYMBOLS = [
     "dmt_update_vertices", "dmt_update_vertices_device", "dmt_set_accel_update", "dmt_accel_update_info", "dmt_bvh_refit_reference",
     "dmt_download_aov_surface", "dmt_upload_aov_surface", "dmt_camera_project", "dmt_test_camera_project", "dmt_temporal_defaults",
     "dmt_denoise_temporal", "dmt_temporal_reset", "dmt_temporal_info", "dmt_temporal_download",
+    "dmt_set_sampler_table", "dmt_sampler_table_plan", "dmt_test_sampler_table",
 ]
+
+# dmt_set_sampler_table modes (include/dmt_hip.h)
+SAMPLER_TABLE_OFF = 0
+SAMPLER_TABLE_AUTO = 1
+SAMPLER_TABLE_FORCE = 2
+
+
+class SamplerTablePlanRecord(C.Structure):
+    """dmt_sampler_table_plan_record (include/dmt_hip.h)"""
+    _fields_ = [("use", C.c_uint32), ("period_width", C.c_uint32), ("period_height", C.c_uint32), ("entry_bytes", C.c_uint32),
+                ("slices", C.c_uint32), ("reserved", C.c_uint32), ("slice_bytes", C.c_uint64)]
+
+
+def sampler_table_plan(width, height, owned_pixels, spp, chunk_spp, budget_bytes=0, mode=SAMPLER_TABLE_AUTO):
+    """Host only (dmt_sampler_table_plan): what a render call does with its sampler table.  Returns a dict: use,
+    period_width, period_height, entry_bytes, slices, slice_bytes, slice_spp (list of the slices' sample counts)."""
+    lib = load_library()
+    rec = SamplerTablePlanRecord()
+    args = [int(width), int(height), C.c_uint64(int(owned_pixels)), C.c_uint32(int(spp)), C.c_uint32(int(chunk_spp)),
+            C.c_uint64(int(budget_bytes)), int(mode)]
+    rc = lib.dmt_sampler_table_plan(*args, C.byref(rec), None, C.c_uint32(0))
+    if rc != 0:
+        raise DmtError(f"dmt_sampler_table_plan failed ({rc})")
+    lens = (C.c_uint32 * max(int(rec.slices), 1))()
+    rc = lib.dmt_sampler_table_plan(*args, C.byref(rec), lens, C.c_uint32(int(rec.slices)))
+    if rc != 0:
+        raise DmtError(f"dmt_sampler_table_plan failed ({rc})")
+    out = {name: int(getattr(rec, name)) for name, _ in SamplerTablePlanRecord._fields_ if name != "reserved"}
+    out["use"] = bool(rec.use)
+    out["slice_spp"] = [int(x) for x in lens[:int(rec.slices)]]
+    return out
 
 
 class DenoiseParams(C.Structure):
@@ -515,6 +547,11 @@ class Renderer:
     def set_chunk(self, samples_per_item):
         self._check(self._lib.dmt_set_chunk(self._ctx, C.c_uint32(samples_per_item)), "dmt_set_chunk")
 
+    def set_sampler_table(self, mode, budget_bytes=0):
+        """SAMPLER_TABLE_OFF / _AUTO (default) / _FORCE; budget_bytes bounds the table's device memory (0 = 512 MiB).
+        Films are bit-identical in every mode."""
+        self._check(self._lib.dmt_set_sampler_table(self._ctx, int(mode), C.c_uint64(int(budget_bytes))), "dmt_set_sampler_table")
+
     def set_stream(self, stream_ptr):
         self._check(self._lib.dmt_set_stream(self._ctx, C.c_void_p(stream_ptr)), "dmt_set_stream")
 
@@ -722,6 +759,15 @@ class Renderer:
         self._check(self._lib.dmt_test_sampler(self._ctx, int(w), int(h), n, _p(pxs), _p(pys), _p(ss), int(ndims),
                                                _p(hi), _p(p2), _p(d)), "dmt_test_sampler")
         return hi, p2, d
+
+    def test_sampler_table(self, w, h, s0, n):
+        """The sampler table of samples [s0, s0 + n) of a w x h frame: (values [n, ph, pw, 8], jitter [n, ph, pw, 2])."""
+        pw, ph = min(int(w), 128), min(int(h), 128)
+        vals = np.zeros((n, ph, pw, 8), np.float32)
+        jit = np.zeros((n, ph, pw, 2), np.float32)
+        self._check(self._lib.dmt_test_sampler_table(self._ctx, int(w), int(h), C.c_uint32(int(s0)), C.c_uint32(int(n)), _p(vals), _p(jit)),
+                    "dmt_test_sampler_table")
+        return vals, jit
 
     def test_camera_rays(self, pxs, pys, ss):
         pxs, pys, ss = _i32(pxs), _i32(pys), _i32(ss)

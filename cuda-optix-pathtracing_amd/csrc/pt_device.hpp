@@ -455,9 +455,8 @@ DMT_DEV f3 xf_dir(float const* m, f3 v) {
   return mk3(m[0] * v.x + m[4] * v.y + m[8] * v.z, m[1] * v.x + m[5] * v.y + m[9] * v.z,
              m[2] * v.x + m[6] * v.y + m[10] * v.z);
 }
-DMT_DEV Ray camera_ray(CameraXf const& cam, SamplerParams const& sp, int px, int py,
-                       int32_t haltonIndex) {
-  f2 const r = pixel2d(sp, haltonIndex);
+// the camera ray of pixel (px, py) for the film jitter r = pixel2d(sp, haltonIndex)
+DMT_DEV Ray camera_ray_jittered(CameraXf const& cam, int px, int py, f2 r) {
   // (getPixel2D - 0.5) + 0.5 + pixel, left to right (extra_math.cu:10-12)
   float const fx = ((r.x - 0.5f) + 0.5f) + float(px);
   float const fy = ((r.y - 0.5f) + 0.5f) + float(py);
@@ -466,6 +465,10 @@ DMT_DEV Ray camera_ray(CameraXf const& cam, SamplerParams const& sp, int px, int
   ray.o = xf_point(cam.rfc, mk3(0.f, 0.f, 0.f));
   ray.d = normalize(xf_dir(cam.rfc, pCamera));
   return ray;
+}
+DMT_DEV Ray camera_ray(CameraXf const& cam, SamplerParams const& sp, int px, int py,
+                       int32_t haltonIndex) {
+  return camera_ray_jittered(cam, px, py, pixel2d(sp, haltonIndex));
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -177,6 +177,32 @@ int dmt_test_envmap(dmt_ctx* ctx, int n, const float* u2, const float* wi_in3, f
 /* samples per work item inside one dmt_render pass (0 = automatic, the default: 1 024 path samples per item; at most 512).  Purely a
  * scheduling knob: a pixel's samples are folded in index order for any value, the film is bit-identical. */
 int dmt_set_chunk(dmt_ctx* ctx, uint32_t samples_per_item);
+/* Sampler table.  The sampler's 8 values and the film jitter of sample s depend on (px % 128, py % 128, s) only, so a
+ * dmt_render call may tabulate them once over the frame's period min(width,128) x min(height,128) (a fill kernel inside
+ * the call's timed span, refilled by every call) and have every pixel load them instead of computing them.  The film
+ * is bit-identical either way.  Modes: OFF; AUTO (the default) uses the table when the call's owned pixels cover at
+ * least 4 periods; FORCE uses it whenever the launch kind allows.  dmt_render_stats / _profile, dmt_render_adaptive and
+ * the wavefront form always compute.  budget_bytes bounds the table's device memory (0 = the default, 512 MiB): a call
+ * whose table is larger runs as consecutive sample slices of whole chunks, each a fill and a launch, still one entry of
+ * dmt_kernel_time; if not even one chunk fits, the call computes.  DMT_SAMPLER_TABLE=0|1|2 in the environment sets
+ * the mode at context creation. */
+#define DMT_SAMPLER_TABLE_OFF 0
+#define DMT_SAMPLER_TABLE_AUTO 1
+#define DMT_SAMPLER_TABLE_FORCE 2
+int dmt_set_sampler_table(dmt_ctx* ctx, int mode, uint64_t budget_bytes);
+typedef struct dmt_sampler_table_plan_record {
+  uint32_t use;                          /* 1: the call fills and reads a table */
+  uint32_t period_width, period_height;  /* min(width,128), min(height,128) */
+  uint32_t entry_bytes;                  /* per (sample, period pixel): 32 bytes of values + 8 of jitter */
+  uint32_t slices;                       /* fill + launch pairs of the call (0 without a table) */
+  uint32_t reserved;
+  uint64_t slice_bytes;                  /* table bytes of the largest slice */
+} dmt_sampler_table_plan_record;
+/* host only (no GPU needed): what a dmt_render call of spp samples in chunks of chunk_spp does with owned_pixels owned
+ * pixels (whole tiles x 64) of a width x height frame.  slice_spp[0 .. min(slices, slice_cap)) receives the slices'
+ * sample counts: consecutive, every one but the last a multiple of chunk_spp, together spp. */
+int dmt_sampler_table_plan(int width, int height, uint64_t owned_pixels, uint32_t spp, uint32_t chunk_spp, uint64_t budget_bytes,
+                           int mode, dmt_sampler_table_plan_record* out, uint32_t* slice_spp, uint32_t slice_cap);
 /* borrow an external hipStream_t (e.g. the caller's); NULL restores the context's own stream */
 int dmt_set_stream(dmt_ctx* ctx, void* hip_stream);
 
@@ -452,6 +478,9 @@ int dmt_test_triangle_intersect(dmt_ctx* ctx, const float* xs, const float* ys, 
 int dmt_test_sampler(dmt_ctx* ctx, int width, int height, int n, const int32_t* pxs,
                      const int32_t* pys, const int32_t* ss, int ndims, int32_t* halton_index,
                      float* pixel2d, float* dims);
+/* fills the sampler table of samples [s0, s0 + n) of a width x height frame as a dmt_render call would and downloads
+ * it: out_vals [n][ph][pw][8], out_jitter [n][ph][pw][2] with pw = min(width,128), ph = min(height,128) */
+int dmt_test_sampler_table(dmt_ctx* ctx, int width, int height, uint32_t s0, uint32_t n, float* out_vals, float* out_jitter);
 int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys,
                          const int32_t* ss, float* o3, float* d3);
 /* dmt_camera_project on the device, under the camera of dmt_set_camera */

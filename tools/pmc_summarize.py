@@ -34,7 +34,9 @@ for f in out.rglob("*counter_collection.csv"):
             if not re.search(rf"\b{kernel}\(", name) and name.split("(")[0].split("::")[-1].strip() != kernel:
                 continue            # skips k_megakernel_bvh_stats and torch's fill kernels
             vals[row["Counter_Name"]].append(float(row["Counter_Value"]))
-d = {k: sum(v) / len(v) for k, v in sorted(vals.items())}
+# per dmt_render call of the pass: a call with a sliced sampler table is several dispatches of the kernel, whose counters add up
+launches = first["steps"] + first["warmup"]
+d = {k: sum(v) / launches for k, v in sorted(vals.items())}
 for k, v in d.items():
     print(f"{k:28s} {v:.6g}")
 
