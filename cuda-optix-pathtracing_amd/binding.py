@@ -69,7 +69,7 @@ EXPORTED_SYMBOLS = [
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
     "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_test_triangle_intersect",
-    "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_light", "dmt_test_half",
+    "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_bsdf_ng", "dmt_test_material", "dmt_test_light", "dmt_test_half",
     "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
     "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
     "dmt_render_aovs", "dmt_upload_aovs", "dmt_download_aovs", "dmt_denoise_defaults", "dmt_denoise",
@@ -789,6 +789,33 @@ class Renderer:
         self._check(self._lib.dmt_test_bsdf(self._ctx, _p(b), n, _p(ns), _p(wo), _p(u2), _p(uc), _p(wi_eval),
                                             _p(prep), _p(samp), _p(ev)), "dmt_test_bsdf")
         return prep, samp, ev
+
+    def test_bsdf_ng(self, bsdf32, ns, ng, wo, u2, uc, wi_eval):
+        """test_bsdf with a geometric normal `ng` of its own for the sampling and evaluation routines."""
+        b = np.ascontiguousarray(bsdf32, np.uint8).reshape(32)
+        ns, ng, wo, wi_eval = _f32(ns, (-1, 3)), _f32(ng, (-1, 3)), _f32(wo, (-1, 3)), _f32(wi_eval, (-1, 3))
+        u2, uc = _f32(u2, (-1, 2)), _f32(uc, (-1,))
+        n = ns.shape[0]
+        assert ng.shape[0] == n and wo.shape[0] == n and wi_eval.shape[0] == n and u2.shape[0] == n and uc.shape[0] == n
+        prep = np.zeros((n, 12), np.float32)
+        samp = np.zeros((n, 10), np.float32)
+        ev = np.zeros((n, 4), np.float32)
+        self._check(self._lib.dmt_test_bsdf_ng(self._ctx, _p(b), n, _p(ns), _p(ng), _p(wo), _p(u2), _p(uc), _p(wi_eval),
+                                               _p(prep), _p(samp), _p(ev)), "dmt_test_bsdf_ng")
+        return prep, samp, ev
+
+    def test_material(self, tri, bu, bv, ng):
+        """The uploaded scene's material at hits (tri, bu, bv) with geometric normals `ng` after the texture patch:
+        (records (n, 32) uint8, ns (n, 3), second records of fractional-metallic pairs (n, 32), metallic fraction (n,))."""
+        tri, bu, bv, ng = _i32(tri), _f32(bu, (-1,)), _f32(bv, (-1,)), _f32(ng, (-1, 3))
+        n = tri.shape[0]
+        assert bu.shape[0] == n and bv.shape[0] == n and ng.shape[0] == n
+        rec, rec2 = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8)
+        ns = np.zeros((n, 3), np.float32)
+        mix = np.zeros(n, np.float32)
+        self._check(self._lib.dmt_test_material(self._ctx, n, _p(tri), _p(bu), _p(bv), _p(ng), _p(rec), _p(ns), _p(rec2),
+                                                _p(mix)), "dmt_test_material")
+        return rec, ns, rec2, mix
 
     def test_light(self, light32, pos, nrm, u2, had_t):
         l = np.ascontiguousarray(light32, np.uint8).reshape(32)

@@ -2313,6 +2313,63 @@ __global__ void k_test_bsdf(Rec32 rec, int n, float const* ns3, float const* wo3
   e[0] = f.x, e[1] = f.y, e[2] = f.z, e[3] = pdf;
 }
 
+// k_test_bsdf with a geometric normal of its own: the render kernels hand a normal-mapped ns and hit.normal as ng to
+// sample_bsdf / eval_bsdf, wo . ns <= 0 < wo . ng included
+__global__ void k_test_bsdf_ng(Rec32 rec, int n, float const* ns3, float const* ng3, float const* wo3, float const* u2,
+                               float const* uc, float const* wi3, float* prep12, float* samp10, float* eval4) {
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  f3 const ns = mk3(ns3[3 * i], ns3[3 * i + 1], ns3[3 * i + 2]);
+  f3 const ng = mk3(ng3[3 * i], ng3[3 * i + 1], ng3[3 * i + 2]);
+  f3 const wo = mk3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]);
+  Bsdf const b = bsdf_prepare(rec, ns, wo);
+  float* p = prep12 + 12 * size_t(i);
+  p[0] = b.weight.x, p[1] = b.weight.y, p[2] = b.weight.z;
+  bool const oren = b.type == BS_OREN, ggx = b.type == BS_GGX_DIEL || b.type == BS_GGX_COND;
+  p[3] = oren ? b.ms.x : 0.f, p[4] = oren ? b.ms.y : 0.f, p[5] = oren ? b.ms.z : 0.f;
+  p[6] = ggx ? b.escale : 0.f, p[7] = float(b.type), p[8] = ggx ? b.ax : 0.f, p[9] = ggx ? b.ay : 0.f, p[10] = ggx ? b.phi0 : 0.f;
+  p[11] = b.type == BS_GGX_DIEL ? b.eta : 0.f;
+  BsdfSample const s = sample_bsdf(b, wo, ns, ng, mk2(u2[2 * i], u2[2 * i + 1]), uc[i]);
+  float* o = samp10 + 10 * size_t(i);
+  o[0] = s.wi.x, o[1] = s.wi.y, o[2] = s.wi.z, o[3] = s.f.x, o[4] = s.f.y, o[5] = s.f.z;
+  o[6] = s.pdf, o[7] = s.eta, o[8] = s.delta ? 1.f : 0.f, o[9] = s.refract ? 1.f : 0.f;
+  float pdf = 0.f;
+  f3 const f = eval_bsdf(b, wo, mk3(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]), ns, ng, pdf) * b.weight;
+  float* e = eval4 + 4 * size_t(i);
+  e[0] = f.x, e[1] = f.y, e[2] = f.z, e[3] = pdf;
+}
+
+// The material of triangle tri[i] at (bu, bv) as path_shade patches it before bsdf_prepare (level-0 lookups): the record
+// after apply_material_textures and the shading normal it returns for the geometric normal ng3[i].  A BS_GGX_BLEND
+// material also gives its conductor record, patched the same way, and the metallic fraction; the dielectric record keeps
+// the blend tag.  Other materials leave rec2 zero and mix 0.
+__global__ void k_test_material(RenderParams P, int n, int32_t const* tri, float const* bu, float const* bv, float const* ng3,
+                                uint32_t* rec8, float* ns3, uint32_t* rec2_8, float* mixOut) {
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  SceneView const sc = load_scene(k);
+  uint32_t const matId = sc.post[tri[i]].matId;
+  f3 const ng = mk3(ng3[3 * i], ng3[3 * i + 1], ng3[3 * i + 2]);
+  Rec32 rec = sc.bsdfs[matId], rec2{};
+  float mix = 0.f;
+  bool const blend = hi16(rec.w[1]) == BS_GGX_BLEND && matId + 1u < sc.bsdfCount;  // a pair: its conductor follows
+  if (blend) {
+    mix = blend_metallic<false>(k, rec, matId, tri[i], bu[i], bv[i]);
+    rec.w[1] = (rec.w[1] & 0x0000FFFFu) | (uint32_t(BS_GGX_DIEL) << 16);  // patched as the dielectric it is shaded as
+    rec2 = sc.bsdfs[matId + 1u];
+  }
+  f3 ns = ng;
+  if (kargs(k)->matTex != nullptr) {
+    ns = apply_material_textures<false>(k, rec, matId, tri[i], bu[i], bv[i], ng);
+    if (blend) (void)apply_material_textures<false>(k, rec2, matId + 1u, tri[i], bu[i], bv[i], ng);
+  }
+  if (blend) rec.w[1] = (rec.w[1] & 0x0000FFFFu) | (uint32_t(BS_GGX_BLEND) << 16);
+  for (int w = 0; w < 8; ++w) rec8[8 * size_t(i) + w] = rec.w[w], rec2_8[8 * size_t(i) + w] = rec2.w[w];
+  ns3[3 * i] = ns.x, ns3[3 * i + 1] = ns.y, ns3[3 * i + 2] = ns.z;
+  mixOut[i] = mix;
+}
+
 __global__ void k_test_light(Rec32 rec, int n, float const* pos3, float const* nrm3, float const* u2,
                              int32_t const* hadT, float* out14) {
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
@@ -4882,6 +4939,67 @@ int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, con
   HIP_TRY(ctx, hipMemcpy(prepared12, dp.get(), size_t(n) * 48, hipMemcpyDeviceToHost));
   HIP_TRY(ctx, hipMemcpy(sample10, ds.get(), size_t(n) * 40, hipMemcpyDeviceToHost));
   HIP_TRY(ctx, hipMemcpy(eval4, de.get(), size_t(n) * 16, hipMemcpyDeviceToHost));
+  return DMT_OK;
+}
+
+int dmt_test_bsdf_ng(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* ng3, const float* wo3,
+                     const float* u2, const float* uc, const float* wi_eval3, float* prepared12, float* sample10,
+                     float* eval4) {
+  if (!ctx || n < 0 || !bsdf32 || !ns3 || !ng3 || !wo3 || !u2 || !uc || !wi_eval3 || !prepared12 || !sample10 || !eval4)
+    return DMT_ERR_INVALID;
+  if (n == 0) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevBuf<float> dns, dng, dwo, du2, duc, dwi, dp, ds, de;
+  HIP_TRY(ctx, dns.assign(ns3, 3 * size_t(n)));
+  HIP_TRY(ctx, dng.assign(ng3, 3 * size_t(n)));
+  HIP_TRY(ctx, dwo.assign(wo3, 3 * size_t(n)));
+  HIP_TRY(ctx, du2.assign(u2, 2 * size_t(n)));
+  HIP_TRY(ctx, duc.assign(uc, size_t(n)));
+  HIP_TRY(ctx, dwi.assign(wi_eval3, 3 * size_t(n)));
+  HIP_TRY(ctx, dp.reserve(12 * size_t(n)));
+  HIP_TRY(ctx, ds.reserve(10 * size_t(n)));
+  HIP_TRY(ctx, de.reserve(4 * size_t(n)));
+  Rec32 rec;
+  memcpy(&rec, bsdf32, 32);
+  hipLaunchKernelGGL(k_test_bsdf_ng, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, rec, n, dns.get(), dng.get(), dwo.get(),
+                     du2.get(), duc.get(), dwi.get(), dp.get(), ds.get(), de.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(prepared12, dp.get(), size_t(n) * 48, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(sample10, ds.get(), size_t(n) * 40, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(eval4, de.get(), size_t(n) * 16, hipMemcpyDeviceToHost));
+  return DMT_OK;
+}
+
+int dmt_test_material(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* ng3, void* rec32,
+                      float* ns3, void* rec2_32, float* mix) {
+  if (!ctx || n < 0 || !tri || !bu || !bv || !ng3 || !rec32 || !ns3 || !rec2_32 || !mix) return DMT_ERR_INVALID;
+  if (!(ctx->haveTris && ctx->haveBsdfs)) return fail(ctx, DMT_ERR_STATE, "dmt_test_material: triangles and BSDFs first");
+  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
+    return fail(ctx, DMT_ERR_INVALID, "dmt_test_material: material index outside the BSDF array");
+  if (ctx->texCount > 0 && (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount))
+    return fail(ctx, DMT_ERR_STATE, "dmt_test_material: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
+  for (int i = 0; i < n; ++i)
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_material: triangle index out of range");
+  if (n == 0) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevBuf<int32_t> dTri;
+  DevBuf<float> dBu, dBv, dNg, dNs, dMix;
+  DevBuf<uint32_t> dRec, dRec2;
+  HIP_TRY(ctx, dTri.assign(tri, size_t(n)));
+  HIP_TRY(ctx, dBu.assign(bu, size_t(n)));
+  HIP_TRY(ctx, dBv.assign(bv, size_t(n)));
+  HIP_TRY(ctx, dNg.assign(ng3, 3 * size_t(n)));
+  HIP_TRY(ctx, dRec.reserve(8 * size_t(n)));
+  HIP_TRY(ctx, dRec2.reserve(8 * size_t(n)));
+  HIP_TRY(ctx, dNs.reserve(3 * size_t(n)));
+  HIP_TRY(ctx, dMix.reserve(size_t(n)));
+  hipLaunchKernelGGL(k_test_material, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, baseParams(ctx, size_t((n + 63) / 64) * 64), n,
+                     dTri.get(), dBu.get(), dBv.get(), dNg.get(), dRec.get(), dNs.get(), dRec2.get(), dMix.get());
+  if (int const rc = finishTest(ctx)) return rc;
+  HIP_TRY(ctx, hipMemcpy(rec32, dRec.get(), 32 * size_t(n), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(rec2_32, dRec2.get(), 32 * size_t(n), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(ns3, dNs.get(), 12 * size_t(n), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(mix, dMix.get(), 4 * size_t(n), hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 

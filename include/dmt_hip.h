@@ -488,6 +488,16 @@ int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, fl
 int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* wo3,
                   const float* u2, const float* uc, const float* wi_eval3, float* prepared12,
                   float* sample10, float* eval4);
+/* dmt_test_bsdf with a geometric normal of its own (ng3) handed to the sampling and evaluation routines, as the render
+ * kernels do under a normal map; same output layouts */
+int dmt_test_bsdf_ng(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* ng3, const float* wo3,
+                     const float* u2, const float* uc, const float* wi_eval3, float* prepared12, float* sample10,
+                     float* eval4);
+/* the material of triangle tri[i] of the uploaded scene at barycentrics (bu, bv), as the shading code patches it from the
+ * level-0 texture lookups: the 32-byte record (rec32) and the shading normal (ns3) for the geometric normal ng3[i].  A
+ * fractional-metallic pair also returns its second record (rec2_32) and the metallic fraction (mix); zero otherwise. */
+int dmt_test_material(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* ng3, void* rec32,
+                      float* ns3, void* rec2_32, float* mix);
 int dmt_test_light(dmt_ctx* ctx, const void* light32, int n, const float* pos3, const float* nrm3,
                    const float* u2, const int32_t* had_transmission, float* out14);
 int dmt_test_half(dmt_ctx* ctx, int n, const float* f_in, uint16_t* h_out, const uint16_t* h_in,

@@ -1073,6 +1073,16 @@ inline V3 faceForward(V3 n, V3 v) { return dot(n, v) < 0.0f ? -n : n; }
 inline float ggxPhi0(Rec32 const& b) {  // bsdf.cuh:52-55
   return float(rd16(b, G_PHI0)) / 65535 * 2.f * kPi;
 }
+// Probes only (oracle_set_cos_nh_ulps; 0 everywhere else): cos_NH moves by this many fp32 ulps on its way into the
+// distribution term D of sampleGGX / evalGGX, which is as far as a differently rounded half vector lands from this one.
+// sampleGGX_VNDF's Nh.z, a sum of O(1) terms that it clamps at 0 and renormalises, moves by as many ulps of 1 (2^-24).
+// The shading sweep's conditioning filter uses it to find the cases that this rounding decides.
+static int g_cosNhUlps = 0;
+inline float nudgeCosNH(float c) {
+  float const to = g_cosNhUlps > 0 ? std::numeric_limits<float>::infinity() : -std::numeric_limits<float>::infinity();
+  for (int k = 0; k < std::abs(g_cosNhUlps); ++k) c = nextafterf(c, to);
+  return c;
+}
 V3 sampleGGX_VNDF(V3 wo, V2 u, float ax, float ay) {  // :303-329
   V3 const V = normalize(v3(ax * wo.x, ay * wo.y, wo.z));
   V3 T1, T2;
@@ -1088,6 +1098,7 @@ V3 sampleGGX_VNDF(V3 wo, V2 u, float ax, float ay) {  // :303-329
   V2 t = sampleUniformDisk(u);
   t.y = lerpf(safeSqrt(1.f - t.x * t.x), t.y, 0.5f * (1.f + V.z));
   V3 Nh = t.x * T1 + t.y * T2 + safeSqrt(1.f - dot(t, t)) * V;
+  Nh.z += float(g_cosNhUlps) * 5.9604645e-8f;  // (probes only; + 0 otherwise)
   Nh = normalize(v3(ax * Nh.x, ay * Nh.y, fmaxf(0.f, Nh.z)));
   return Nh;
 }
@@ -1165,14 +1176,14 @@ BSDFSample sampleGGX(Rec32 const& b, V3 wo, V3 ns, V3 ng, V2 u, float uc) {  // 
     float D{}, lamI{}, lamO{};
     if (isotropic || s.refract) {
       float const alpha2 = ax * ay;
-      float const cos_NH = lH.z;
+      float const cos_NH = nudgeCosNH(lH.z);
       float const cos_NI = dot(ns, s.wi);
       D = ggx_D(alpha2, cos_NH);
       lamI = ggx_lambda(alpha2, cos_NI);
       lamO = ggx_lambda(alpha2, cos_NO);
     } else {
       V3 const lI = 2.f * cos_HO * lH - lO;
-      D = ggx_aniso_D(ax, ay, lH);
+      D = ggx_aniso_D(ax, ay, v3(lH.x, lH.y, nudgeCosNH(lH.z)));
       lamI = ggx_aniso_lambda(ax, ay, lI);
       lamO = ggx_aniso_lambda(ax, ay, lO);
     }
@@ -1213,7 +1224,7 @@ V3 evalGGX(Rec32 const& b, V3 wo, V3 wi, V3 ns, V3 ng, float* pdf) {  // :571-66
     *pdf = 0.f;
     return v3(0, 0, 0);
   }
-  float const cos_NH = dot(ns, H);
+  float const cos_NH = nudgeCosNH(dot(ns, H));
   float D{}, lamI{}, lamO{};
   if (isotropic || isTransmission) {
     float const alpha2 = ax * ay;
@@ -1224,7 +1235,7 @@ V3 evalGGX(Rec32 const& b, V3 wo, V3 wi, V3 ns, V3 ng, float* pdf) {  // :571-66
     V3 const tangent = tangentFromPhi(ns, ggxPhi0(b));
     V3 X{}, Y{};
     orthonormalTangent(ns, tangent, &X, &Y);
-    V3 const lH = v3(dot(X, H), dot(Y, H), dot(ns, H));
+    V3 const lH = v3(dot(X, H), dot(Y, H), cos_NH);
     V3 const lO = v3(dot(X, wo), dot(Y, wo), cos_NO);
     V3 const lI = v3(dot(X, wi), dot(Y, wi), cos_NI);
     D = ggx_aniso_D(ax, ay, lH);
@@ -2145,8 +2156,16 @@ inline float blendMetallic(Scene const& sc, Rec32 const& rec, uint32_t matId, in
   }
   return m;
 }
-inline V3 applyMaterialTextures(Scene const& sc, Rec32& rec, uint32_t matId, int tri, float bu, float bv, V3 ng) {
+// lookupUlps (probes only): every texture lookup is moved by that many fp32 ulps before it is quantised, which is how far a
+// differently rounded bilinear filter lands from this one -- oracle_material_at_hit finds the hits on a quantisation boundary with it
+inline V3 applyMaterialTextures(Scene const& sc, Rec32& rec, uint32_t matId, int tri, float bu, float bv, V3 ng, int lookupUlps = 0) {
   if (!sc.matTex || !sc.triUv) return ng;
+  auto textureBilinear = [lookupUlps](Scene const& scn, int32_t tex, float ss, float tt, bool isNormal) {
+    V3 c = ::textureBilinear(scn, tex, ss, tt, isNormal);
+    float const to = lookupUlps > 0 ? std::numeric_limits<float>::infinity() : -std::numeric_limits<float>::infinity();
+    for (int k = 0; k < std::abs(lookupUlps); ++k) c = v3(nextafterf(c.x, to), nextafterf(c.y, to), nextafterf(c.z, to));
+    return c;
+  };
   uint32_t const* m = sc.matTex + 4 * matId;
   int32_t const texD = int32_t(m[0]), texR = int32_t(m[1]), texN = int32_t(m[2]);
   if (texD < 0 && texR < 0 && texN < 0) return ng;
@@ -2889,6 +2908,65 @@ void oracle_bsdf_cases(const void* bsdf32, int n, const float* ns3, const float*
     float* e = eval4 + 4 * size_t(i);
     e[0] = f.x, e[1] = f.y, e[2] = f.z, e[3] = pdf;
   }
+}
+
+void oracle_set_cos_nh_ulps(int ulps) { g_cosNhUlps = ulps; }
+
+// oracle_bsdf_cases with a geometric normal of its own per case (ng3): what the path tracer hands sampleBsdf / evalBsdf
+// under a normal map, where ns != hit.normal
+void oracle_bsdf_cases_ng(const void* bsdf32, int n, const float* ns3, const float* ng3, const float* wo3, const float* u2,
+                          const float* uc, const float* wiEval3, void* prepared32, float* sample10, float* eval4) {
+  for (int i = 0; i < n; ++i) {
+    Rec32 b;
+    memcpy(&b, bsdf32, 32);
+    V3 const ns = v3(ns3[3 * i], ns3[3 * i + 1], ns3[3 * i + 2]);
+    V3 const ng = v3(ng3[3 * i], ng3[3 * i + 1], ng3[3 * i + 2]);
+    V3 const wo = v3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]);
+    prepareBSDF(&b, ns, wo, 0);
+    memcpy(static_cast<char*>(prepared32) + 32 * size_t(i), &b, 32);
+    BSDFSample const s = sampleBsdf(b, wo, ns, ng, v2(u2[2 * i], u2[2 * i + 1]), uc[i]);
+    float* o = sample10 + 10 * size_t(i);
+    o[0] = s.wi.x, o[1] = s.wi.y, o[2] = s.wi.z, o[3] = s.f.x, o[4] = s.f.y, o[5] = s.f.z;
+    o[6] = s.pdf, o[7] = s.eta, o[8] = s.delta ? 1.f : 0.f, o[9] = s.refract ? 1.f : 0.f;
+    float pdf = 0;
+    V3 const wi = v3(wiEval3[3 * i], wiEval3[3 * i + 1], wiEval3[3 * i + 2]);
+    V3 const f = evalBsdf(b, wo, wi, ns, ng, &pdf) * bsdfWeight(b);
+    float* e = eval4 + 4 * size_t(i);
+    e[0] = f.x, e[1] = f.y, e[2] = f.z, e[3] = pdf;
+  }
+}
+
+// The material of triangle tri[i] at (bu, bv) as tracePath patches it before prepareBSDF: the record after
+// applyMaterialTextures and the shading normal it returns for the geometric normal ng3[i].  A BS_GGX_BLEND material also
+// gives its conductor record, patched the same way, and the metallic fraction; its dielectric record keeps the blend tag.
+int oracle_material_at_hit(const OracleScene* s, int n, const int32_t* tri, const float* bu, const float* bv, const float* ng3,
+                           int lookupUlps, void* rec32, float* ns3, void* rec2_32, float* mixOut) {
+  Scene const sc = toScene(s);
+  for (int i = 0; i < n; ++i) {
+    if (tri[i] < 0 || uint64_t(tri[i]) >= sc.triCount) return 1;
+    uint32_t const matId = sc.matId[tri[i]];
+    if (matId >= sc.bsdfCount) return 1;
+    V3 const ng = v3(ng3[3 * i], ng3[3 * i + 1], ng3[3 * i + 2]);
+    Rec32 bsdf = sc.bsdfs[matId], bsdf2{};
+    float mix = 0.f;
+    bool const blend = bsdfType(bsdf) == BS_GGX_BLEND;
+    if (blend) {
+      if (matId + 1 >= sc.bsdfCount) return 1;
+      mix = blendMetallic(sc, bsdf, matId, tri[i], bu[i], bv[i]);
+      wr16(bsdf, B_TYPE, BS_GGX_DIEL);
+      bsdf2 = sc.bsdfs[matId + 1];
+    }
+    V3 const ns = applyMaterialTextures(sc, bsdf, matId, tri[i], bu[i], bv[i], ng, lookupUlps);
+    if (blend) {
+      (void)applyMaterialTextures(sc, bsdf2, matId + 1, tri[i], bu[i], bv[i], ng, lookupUlps);
+      wr16(bsdf, B_TYPE, BS_GGX_BLEND);
+    }
+    memcpy(static_cast<char*>(rec32) + 32 * size_t(i), &bsdf, 32);
+    memcpy(static_cast<char*>(rec2_32) + 32 * size_t(i), &bsdf2, 32);
+    ns3[3 * i] = ns.x, ns3[3 * i + 1] = ns.y, ns3[3 * i + 2] = ns.z;
+    mixOut[i] = mix;
+  }
+  return 0;
 }
 
 // --- lights: sample + eval ---------------------------------------------------------------

@@ -12,6 +12,7 @@ import numpy as np
 
 _HERE = Path(__file__).resolve().parent
 _LIB = None
+_LIB_FMA = None
 
 f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -41,6 +42,18 @@ def build(force=False):
     if force or not so.exists() or so.stat().st_mtime < src.stat().st_mtime:
         subprocess.check_call(["make", "-C", str(_HERE), "-B" if force else "-s"])
     return so
+
+
+def lib_contracted():
+    """libdmt_oracle_fma.so: the same source with a*b+c contracted into FMAs (another legal rounding of the reference).
+    A target of its own (`make -C oracle fma`), built on first use: only the shading sweep needs it."""
+    global _LIB_FMA
+    if _LIB_FMA is None:
+        so = _HERE / "libdmt_oracle_fma.so"
+        if not so.exists() or so.stat().st_mtime < (_HERE / "dmt_oracle.cpp").stat().st_mtime:
+            subprocess.check_call(["make", "-C", str(_HERE), "-s", "fma"])
+        _LIB_FMA = C.CDLL(str(so))
+    return _LIB_FMA
 
 
 def lib():
@@ -288,7 +301,53 @@ def bsdf_cases(bsdf32, ns, wo, u2, uc, wi_eval):
     return prepared, sample, ev
 
 
-def light_cases(light32, pos, nrm, u2, had_transmission):
+def bsdf_cases_ng(bsdf32, ns, ng, wo, u2, uc, wi_eval, contracted=False, cos_nh_ulps=0):
+    """bsdf_cases with a geometric normal `ng` of its own for sampleBsdf / evalBsdf (normal-mapped hits: ns != ng).
+    `contracted`: by the FMA-contracted build.  `cos_nh_ulps` moves cos_NH by that many fp32 ulps on its way into the
+    distribution term D (sampleGGX and evalGGX)."""
+    bsdf32 = np.ascontiguousarray(bsdf32, np.uint8).reshape(32)
+    ns = np.ascontiguousarray(ns, np.float32).reshape(-1, 3)
+    ng = np.ascontiguousarray(ng, np.float32).reshape(-1, 3)
+    wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+    u2 = np.ascontiguousarray(u2, np.float32).reshape(-1, 2)
+    uc = np.ascontiguousarray(uc, np.float32).reshape(-1)
+    wi_eval = np.ascontiguousarray(wi_eval, np.float32).reshape(-1, 3)
+    n = ns.shape[0]
+    assert ng.shape[0] == n and wo.shape[0] == n and u2.shape[0] == n and uc.shape[0] == n and wi_eval.shape[0] == n
+    prepared = np.zeros((n, 32), np.uint8)
+    sample = np.zeros((n, 10), np.float32)
+    ev = np.zeros((n, 4), np.float32)
+    L = lib_contracted() if contracted else lib()
+    L.oracle_set_cos_nh_ulps(int(cos_nh_ulps))
+    try:
+        L.oracle_bsdf_cases_ng(_p(bsdf32), n, _p(ns), _p(ng), _p(wo), _p(u2), _p(uc), _p(wi_eval), _p(prepared), _p(sample),
+                               _p(ev))
+    finally:
+        L.oracle_set_cos_nh_ulps(0)
+    return prepared, sample, ev
+
+
+def material_at_hit(scene, tri, bu, bv, ng, lookup_ulps=0):
+    """The scene's material at hits (tri, bu, bv) with geometric normals `ng` after the texture patch: (records (n, 32)
+    uint8, ns (n, 3), second records of fractional-metallic pairs (n, 32), metallic fraction (n,)).  `lookup_ulps` moves
+    every albedo / roughness / normal lookup by that many fp32 ulps before it is quantised."""
+    tri = np.ascontiguousarray(tri, np.int32).reshape(-1)
+    bu = np.ascontiguousarray(bu, np.float32).reshape(-1)
+    bv = np.ascontiguousarray(bv, np.float32).reshape(-1)
+    ng = np.ascontiguousarray(ng, np.float32).reshape(-1, 3)
+    n = tri.shape[0]
+    assert bu.shape[0] == n and bv.shape[0] == n and ng.shape[0] == n
+    rec, rec2 = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8)
+    ns = np.zeros((n, 3), np.float32)
+    mix = np.zeros(n, np.float32)
+    cs = scene.c_struct()
+    rc = lib().oracle_material_at_hit(C.byref(cs), n, _p(tri), _p(bu), _p(bv), _p(ng), int(lookup_ulps), _p(rec), _p(ns), _p(rec2), _p(mix))
+    if rc != 0:
+        raise ValueError("oracle_material_at_hit: triangle or material index out of range")
+    return rec, ns, rec2, mix
+
+
+def light_cases(light32, pos, nrm, u2, had_transmission, contracted=False):
     light32 = np.ascontiguousarray(light32, np.uint8).reshape(32)
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
     nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
@@ -296,7 +355,8 @@ def light_cases(light32, pos, nrm, u2, had_transmission):
     ht = np.ascontiguousarray(had_transmission, np.int32).reshape(-1)
     n = pos.shape[0]
     out = np.zeros((n, 14), np.float32)
-    lib().oracle_light_cases(_p(light32), n, _p(pos), _p(nrm), _p(u2), _p(ht), _p(out))
+    L = lib_contracted() if contracted else lib()
+    L.oracle_light_cases(_p(light32), n, _p(pos), _p(nrm), _p(u2), _p(ht), _p(out))
     return out
 
 
