@@ -1,4 +1,4 @@
-// devbuf.hpp -- the one owner type of device memory on the host side of the library.
+// devbuf.hpp -- the owner types of the host side of the library: device memory (DevBuf) and a pair of events (EventPair).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,6 +47,18 @@ class DevBuf {
  private:
   T* p_ = nullptr;
   size_t n_ = 0;
+};
+
+// Two HIP events around a span of a stream, destroyed on every exit path.  The user creates them (hipEventCreate(&p.a)).
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  EventPair() = default;
+  EventPair(EventPair const&) = delete;
+  EventPair& operator=(EventPair const&) = delete;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
 };
 
 }  // namespace dmt

@@ -2136,358 +2136,7 @@ __global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
 }
 
 #include "wavefront.hpp"
-
-// ---------------------------------------------------------------------------------------------
-// denoiser (dmt_render_aovs, dmt_denoise)
-// ---------------------------------------------------------------------------------------------
-// Feature pass: camera samples 0 .. aovSpp-1 of every pixel of the frame, the film's own camera rays, closest hit as
-// k_test_closest finds it.  Per pixel, summed in sample order over the samples whose ray hit a triangle ("hits"):
-//   albedo   = (sum W / aovSpp, hits / aovSpp)     W = the record's fp16 weight after the level-0 texture patch;
-//                                                   BS_GGX_BLEND: (1 - mix) W_diel + mix W_cond, mix clamped to [0, 1]
-//   normal   = (normalize(sum ns) or 0 when |sum| < 1e-6, 0)   ns = hit_finish's face-forwarded or the normal-mapped normal
-//   position = (sum pos / hits, sum t / hits), 0 without hits
-//   surface  = (tri, bu, bv, 1) of the first sample that hit, tri the original index as a float; (-1, 0, 0, 0) without hits
-struct AovArgs {
-  float4* albedo;
-  float4* normal;
-  float4* position;
-  float4* surface;
-  int width;
-  uint32_t pixels, aovSpp;
-  bool useBvh;
-};
-DMT_DEV f3 rec_weight(Rec32 const& r) { return mk3(h2f(lo16(r.w[0])), h2f(hi16(r.w[0])), h2f(lo16(r.w[1]))); }
-// The part of apply_material_textures (level 0) that W and the shading normal depend on: the albedo patch of Oren-Nayar
-// records and the normal map, same expressions.  Its roughness patch is left out: nothing here reads it, and patching a
-// word chosen by the record's type kept the record in scratch memory.
-DMT_DEV f3 aov_textures(KArgs k, Rec32& rec, uint32_t matId, int tri, float bu, float bv, f3 ng) {
-  KArgs const ka = kargs(k);
-  uint32_t const* const m = ka->matTex + 4 * matId;
-  int32_t const texD = int32_t(m[0]), texN = int32_t(m[2]);
-  if (texD < 0 && texN < 0) return ng;
-  float const* const uv = ka->triUv + 6 * size_t(tri);
-  float const w0 = 1.f - bu - bv;
-  float const s = w0 * uv[0] + bu * uv[2] + bv * uv[4], t = w0 * uv[1] + bu * uv[3] + bv * uv[5];
-  if (texD >= 0 && hi16(rec.w[1]) == BS_OREN) {
-    f3 const c = tex_lookup<false>(k, texD, s, t, false, TexDiff{});
-    rec.w[0] = f2h(fmaxf(0.f, fminf(c.x, 1.f))) | (f2h(fmaxf(0.f, fminf(c.y, 1.f))) << 16);
-    rec.w[1] = (rec.w[1] & 0xFFFF0000u) | f2h(fmaxf(0.f, fminf(c.z, 1.f)));
-  }
-  if (texN < 0) return ng;
-  f3 n = tex_lookup<false>(k, texN, s, t, true, TexDiff{});
-  auto quant = [](float v) { return float(int(v * 1023.f + 0.5f)) / 1023.f; };
-  n = normalize(mk3(quant(n.x), quant(n.y), quant(n.z)));
-  f3 tx, ty;
-  gram_schmidt(ng, tx, ty);
-  f3 const ns = tx * n.x + ty * n.y + ng * n.z;
-  float const l2 = dot(ns, ns);
-  return (l2 > 0.f && l2 < kInf) ? ns / sqrtf(l2) : ng;
-}
-// W and the shading normal at a camera ray's hit, as path_shade sees them at depth 0 (level-0 texture lookups)
-DMT_DEV void aov_material(KArgs k, Hit const& hit, int tri, float bu, float bv, f3& W, f3& ns) {
-  SceneView const sc = load_scene(k);
-  bool const tex = kargs(k)->matTex != nullptr;
-  Rec32 rec = sc.bsdfs[hit.matId];
-  ns = hit.normal;
-  if (tex) ns = aov_textures(k, rec, hit.matId, tri, bu, bv, hit.normal);
-  if (hi16(rec.w[1]) == BS_GGX_BLEND) {  // GGX: the albedo patch never applies, to either record
-    float const mix = fminf(fmaxf(blend_metallic(k, rec, hit.matId, tri, bu, bv), 0.f), 1.f);
-    f3 Wd = rec_weight(rec);
-    Wd.x = 1.f;  // the dielectric half keeps the metallic fraction where its W.x would be (makeGGXBlendDielectric)
-    W = Wd * (1.f - mix) + rec_weight(sc.bsdfs[hit.matId + 1u]) * mix;
-    return;
-  }
-  W = rec_weight(rec);
-}
-// one lane per pixel, row-major; whole waves stride over the frame (the BVH overflow stack is sized by the launch)
-__global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
-  KArgs const k = kargs_base();
-  if (!A.useBvh) cull_stage(k);
-  uint32_t const lane = threadIdx.x & 63u, gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t const waves = gridDim.x * (blockDim.x >> 6);
-  for (uint32_t w = gtid >> 6; w * 64u < A.pixels; w += waves) {  // wave-uniform trip count
-    uint32_t const i = w * 64u + lane;
-    bool const alive = i < A.pixels;
-    int const px = alive ? int(i % uint32_t(A.width)) : 0, py = alive ? int(i / uint32_t(A.width)) : 0;
-    int32_t const base = halton_pixel_base(load_cold_args(k).sp, px, py);
-    f3 sumW = mk3(0, 0, 0), sumN = mk3(0, 0, 0), sumP = mk3(0, 0, 0);
-    float sumT = 0.f;
-    uint32_t hits = 0;
-    for (uint32_t s = 0; s < A.aovSpp; ++s) {
-      PathState st{};
-      // camera and sampler re-read from the kernel arguments at the point of use: held in SGPRs across the triangle pass
-      // they would spill (see kargs)
-      ColdArgs const c = load_cold_args(k);
-      Ray const r = camera_ray(c.cam, c.sp, px, py, base + int32_t(s) * (c.sp.scale0 * c.sp.scale1));
-      set_ray(st, r.o, r.d);
-      st.active = alive;
-      int best;
-      float bu, bv;
-      bool occluded;
-      if (A.useBvh)
-        trace_pair_bvh(k, st, alive, false, gtid, best, bu, bv, occluded);
-      else
-        trace_pair_brute(k, st, alive, false, best, bu, bv, occluded);
-      if (alive && best >= 0) {
-        TriS const T = load_tri(to_const_as(load_scene(k).tris), uint32_t(best));
-        float const t = mt_pair(T, st.rp).t.x;  // as k_test_closest reports it
-        Hit const hit = hit_finish(load_scene(k).post[best], bu, bv, r.d);
-        f3 W, ns;
-        aov_material(k, hit, best, bu, bv, W, ns);
-        sumW = sumW + W, sumN = sumN + ns, sumP = sumP + hit.pos, sumT += t;
-        if (hits == 0) A.surface[i] = make_float4(float(best), bu, bv, 1.f);  // stored here: nothing more to keep across the loop
-        ++hits;
-      }
-    }
-    if (alive) {
-      float const inv = 1.f / float(A.aovSpp);
-      A.albedo[i] = make_float4(sumW.x * inv, sumW.y * inv, sumW.z * inv, float(hits) * inv);
-      float const len = sqrtf(dot(sumN, sumN));
-      f3 const n = len >= 1e-6f ? sumN / len : mk3(0, 0, 0);
-      A.normal[i] = make_float4(n.x, n.y, n.z, 0.f);
-      float const h = float(hits);
-      A.position[i] = hits ? make_float4(sumP.x / h, sumP.y / h, sumP.z / h, sumT / h) : make_float4(0.f, 0.f, 0.f, 0.f);
-      if (!hits) A.surface[i] = make_float4(-1.f, 0.f, 0.f, 0.f);
-    }
-  }
-}
-
-// A-trous passes (spatial SVGF).  Colour and variance travel together as one float4 (rgb, v) per pixel, ping-ponged
-// between passes; the AOVs stay fp32 (no packing), so tests/denoise_ref.py restates the filter on the same numbers.
-struct DenoiseArgs {
-  float4 const* mean;      // k_denoise_init: the source film
-  float4 const* m2;
-  float4 const* albedo;    // k_atrous: the AOVs
-  float4 const* normal;
-  float4 const* position;
-  float4 const* src;       // (rgb, variance) of pass i
-  float4* dst;             // of pass i + 1 (k_denoise_init: pass 0)
-  uint32_t* bad;           // k_denoise_init: pixels with N < 2 or a non-finite mean / M2
-  int width, height;
-  float theta;             // sensor height / (focal length * image height): one pixel's angle
-  float sigmaN, sigmaX, sigmaA, sigmaL;
-  float tapDist[25];       // s * sqrt(dx^2 + dy^2) of tap (dx, dy) at [5 (dy + 2) + dx + 2]
-  int step;                // s = 2^i
-};
-// c0 = mean.xyz, v0 = (M2.x + M2.y + M2.z) / (3 N (N - 1)); counts the pixels the filter refuses
-__global__ void __launch_bounds__(256) k_denoise_init(DenoiseArgs A) {
-#pragma clang fp contract(off)
-  uint32_t const i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t const pixels = uint32_t(A.width) * uint32_t(A.height);
-  bool badPx = false;
-  if (i < pixels) {
-    float4 const m = A.mean[i], v = A.m2[i];
-    float const N = v.w;
-    badPx = !(N >= 2.f) || !__builtin_isfinite(N) || !__builtin_isfinite(m.x) || !__builtin_isfinite(m.y) ||
-            !__builtin_isfinite(m.z) || !__builtin_isfinite(v.x) || !__builtin_isfinite(v.y) || !__builtin_isfinite(v.z);
-    float const var = ((v.x + v.y) + v.z) / ((3.f * N) * (N - 1.f));
-    A.dst[i] = make_float4(m.x, m.y, m.z, var);
-  }
-  unsigned long long const b = __ballot(badPx);
-  if ((threadIdx.x & 63u) == 0u && b != 0ull) atomicAdd(A.bad, uint32_t(__popcll(b)));
-}
-DMT_DEV float luminance(float4 c) {
-#pragma clang fp contract(off)
-  return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
-}
-// one pass at step s: block = 64 x 4 pixels, a wave = 64 pixels of one row (tap loads coalesce); centre AOVs loaded once
-__global__ void __launch_bounds__(256) k_atrous(DenoiseArgs A) {
-#pragma clang fp contract(off)
-  int const px = int(blockIdx.x) * 64 + int(threadIdx.x & 63u), py = int(blockIdx.y) * 4 + int(threadIdx.x >> 6);
-  if (px >= A.width || py >= A.height) return;
-  size_t const W = size_t(A.width);
-  size_t const p = size_t(py) * W + size_t(px);
-  float4 const cp = A.src[p];
-  float4 const ap = A.albedo[p];
-  if (!(ap.w > 0.f)) {  // background only: passes through and feeds no one
-    A.dst[p] = cp;
-    return;
-  }
-  float4 const np = A.normal[p], xp = A.position[p];
-  float gs = 0.f, gw = 0.f;  // 3x3 [1/4, 1/2, 1/4] blur of the variance, normalised over the in-image taps
-#pragma unroll
-  for (int dy = -1; dy <= 1; ++dy) {
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-      int const qx = px + dx, qy = py + dy;
-      if (qx < 0 || qx >= A.width || qy < 0 || qy >= A.height) continue;
-      float const kk = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
-      gs = gs + kk * A.src[size_t(qy) * W + size_t(qx)].w;
-      gw = gw + kk;
-    }
-  }
-  float const lp = luminance(cp);
-  float const lden = A.sigmaL * sqrtf(gs / gw) + 1e-10f;
-  float const xden = (A.sigmaX * xp.w) * A.theta;
-  float const a2 = A.sigmaA * A.sigmaA;
-  float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
-#pragma unroll
-  for (int dy = -2; dy <= 2; ++dy) {
-#pragma unroll
-    for (int dx = -2; dx <= 2; ++dx) {
-      int const qx = px + dx * A.step, qy = py + dy * A.step;
-      if (qx < 0 || qx >= A.width || qy < 0 || qy >= A.height) continue;
-      float const hx = dx == 0 ? 0.375f : (dx == 1 || dx == -1) ? 0.25f : 0.0625f;
-      float const hy = dy == 0 ? 0.375f : (dy == 1 || dy == -1) ? 0.25f : 0.0625f;
-      float w = hx * hy;
-      float4 cq = cp;
-      if (dx != 0 || dy != 0) {
-        size_t const q = size_t(qy) * W + size_t(qx);
-        float4 const aq = A.albedo[q];
-        if (!(aq.w > 0.f)) continue;
-        float4 const nq = A.normal[q], xq = A.position[q];
-        cq = A.src[q];
-        float const nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
-        float const wn = powf(fmaxf(0.f, nd), A.sigmaN);
-        float const pd = fabsf((np.x * (xq.x - xp.x) + np.y * (xq.y - xp.y)) + np.z * (xq.z - xp.z));
-        float const wx = expf(-pd / (xden * A.tapDist[5 * (dy + 2) + dx + 2]));
-        float const ar = ap.x - aq.x, ag = ap.y - aq.y, ab = ap.z - aq.z;
-        float const wa = expf(-((ar * ar + ag * ag) + ab * ab) / a2);
-        float const wl = expf(-fabsf(lp - luminance(cq)) / lden);
-        w = (((w * wn) * wx) * wa) * wl;
-      }
-      sw = sw + w;
-      sr = sr + w * cq.x, sg = sg + w * cq.y, sb = sb + w * cq.z;
-      sv = sv + (w * w) * cq.w;
-    }
-  }
-  A.dst[p] = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
-}
-
-// Temporal accumulation (dmt_denoise_temporal).
-// World-to-film projection, the inverse of camera_ray's film-to-ray map: render-space point -> the continuous film
-// coordinates camera_ray calls (fx, fy), and the camera-space depth.  fp32, no contraction, one order of operations for the
-// host (dmt_camera_project) and the device; tests/temporal_ref.py restates it.
-struct ProjXf {
-  float right[3], up[3], fwd[3];  // rows of camera-from-render's rotation (the columns of CameraXf::rfc)
-  float pos[3];
-  float focal, tx, ty;            // cameraFromRaster: x_cam = fx / ipx + tx, y_cam = fy / ipy + ty at z_cam = focal
-  float ipx, ipy;                 // 1 / psx, 1 / -psy
-};
-struct Proj {
-  float fx, fy, depth;
-};
-// a / b: IEEE on the host; on the device v_rcp_f32 plus one residual step, which rounds as the host does except in rare
-// half-way cases (the library's device `/` is the 2.5-ulp one, see the Makefile)
-__host__ __device__ inline float proj_div(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  float const r = __builtin_amdgcn_rcpf(b);
-  float const q = a * r;
-  return __builtin_fmaf(__builtin_fmaf(-q, b, a), r, q);
-#else
-  return a / b;
-#endif
-}
-__host__ __device__ inline Proj project_point(ProjXf const& c, float x, float y, float z) {
-#pragma clang fp contract(off)
-  float const dx = x - c.pos[0], dy = y - c.pos[1], dz = z - c.pos[2];
-  float const cx = (c.right[0] * dx + c.right[1] * dy) + c.right[2] * dz;
-  float const cy = (c.up[0] * dx + c.up[1] * dy) + c.up[2] * dz;
-  float const cz = (c.fwd[0] * dx + c.fwd[1] * dy) + c.fwd[2] * dz;
-  float const s = proj_div(c.focal, cz);
-  Proj o;
-  o.fx = (cx * s - c.tx) * c.ipx;
-  o.fy = (cy * s - c.ty) * c.ipy;
-  o.depth = cz;
-  return o;
-}
-// X = w0 p0 + bu p1 + bv p2, w0 = (1 - bu) - bv, left to right per component; v = the triangle's 9 raw floats
-DMT_DEV f3 surface_point(float const* v, float bu, float bv) {
-#pragma clang fp contract(off)
-  float const w0 = (1.f - bu) - bv;
-  return mk3((w0 * v[0] + bu * v[3]) + bv * v[6], (w0 * v[1] + bu * v[4]) + bv * v[7], (w0 * v[2] + bu * v[5]) + bv * v[8]);
-}
-struct TemporalArgs {
-  float4 const* cur;        // (rgb, v0) of the current film: k_denoise_init's plane
-  float4 const* albedo;     // the current AOVs
-  float4 const* normal;
-  float4 const* surface;
-  float const* vertsCur;    // 9 floats per triangle: the current frame's, the history frame's (may be the same array)
-  float const* vertsPrev;
-  float4 const* histCv;     // the history: accumulated (rgb, v), length, and the normal / position planes of its frame
-  float const* histLen;
-  float4 const* histNormal;
-  float4 const* histPos;
-  float4* outCv;            // the new history (the other half of the ping-pong)
-  float* outLen;
-  uint32_t* counts;         // [0] pixels reprojected, [1] pixels reset
-  ProjXf camCur, camPrev;
-  int width, height;
-  uint32_t triCount;
-  int haveHistory;          // 0: every pixel is reset
-  float alpha, normalThreshold, planeThreshold;
-  float thetaPrev;          // one pixel's angle under the history frame's camera
-};
-// one lane per pixel; block = 64 x 4 pixels, a wave = 64 pixels of one row, as k_atrous
-__global__ void __launch_bounds__(256) k_temporal(TemporalArgs A) {
-#pragma clang fp contract(off)
-  int const px = int(blockIdx.x) * 64 + int(threadIdx.x & 63u), py = int(blockIdx.y) * 4 + int(threadIdx.x >> 6);
-  bool const inside = px < A.width && py < A.height;
-  bool reproj = false, reset = false;
-  if (inside) {
-    size_t const W = size_t(A.width);
-    size_t const p = size_t(py) * W + size_t(px);
-    float4 const cc = A.cur[p];
-    bool const covered = A.albedo[p].w > 0.f;
-    float4 out = cc;
-    float hOut = covered ? 1.f : 0.f;
-    float4 const sf = A.surface[p];
-    // the index test also turns away a NaN and anything outside the vertex arrays
-    if (covered && A.haveHistory && sf.x >= 0.f && sf.x < float(A.triCount)) {
-      size_t const tri = size_t(uint32_t(sf.x));
-      f3 const Xc = surface_point(A.vertsCur + 9 * tri, sf.y, sf.z), Xp = surface_point(A.vertsPrev + 9 * tri, sf.y, sf.z);
-      Proj const qc = project_point(A.camCur, Xc.x, Xc.y, Xc.z), qp = project_point(A.camPrev, Xp.x, Xp.y, Xp.z);
-      float const u = float(px) + (qp.fx - qc.fx), v = float(py) + (qp.fy - qc.fy);
-      // inside (-1, width) x (-1, height): some tap of the 2 x 2 footprint can be in the image; false for a NaN
-      if (qp.depth > 0.f && u > -1.f && u < float(A.width) && v > -1.f && v < float(A.height)) {
-        float const fu0 = floorf(u), fv0 = floorf(v);
-        int const iu = int(fu0), iv = int(fv0);
-        float const fu = u - fu0, fv = v - fv0;
-        float4 const np = A.normal[p];
-        float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f, sh = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          int const qx = iu + (t & 1), qy = iv + (t >> 1);
-          float const w = ((t & 1) ? fu : 1.f - fu) * ((t >> 1) ? fv : 1.f - fv);
-          if (!(w > 0.f) || qx < 0 || qx >= A.width || qy < 0 || qy >= A.height) continue;
-          size_t const q = size_t(qy) * W + size_t(qx);
-          float const hq = A.histLen[q];
-          if (!(hq >= 1.f)) continue;
-          float4 const nq = A.histNormal[q];
-          float const nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
-          if (!(nd >= A.normalThreshold)) continue;
-          float4 const xq = A.histPos[q];
-          float const pd = fabsf((nq.x * (Xp.x - xq.x) + nq.y * (Xp.y - xq.y)) + nq.z * (Xp.z - xq.z));
-          if (!(pd <= (A.planeThreshold * xq.w) * A.thetaPrev)) continue;
-          float4 const cq = A.histCv[q];
-          sw = sw + w;
-          sr = sr + w * cq.x, sg = sg + w * cq.y, sb = sb + w * cq.z;
-          sv = sv + (w * w) * cq.w;
-          sh = sh + w * hq;
-        }
-        if (sw > 0.f) {
-          reproj = true;
-          float const h = fminf(sh / sw + 1.f, 65536.f);
-          float const a = fmaxf(A.alpha, 1.f / h);
-          hOut = h;
-          if (a < 1.f) {  // a = 1 is the current frame itself, bit for bit
-            float const pr = sr / sw, pg = sg / sw, pb = sb / sw, pv = sv / (sw * sw);
-            float const b = 1.f - a;
-            out = make_float4(pr + a * (cc.x - pr), pg + a * (cc.y - pg), pb + a * (cc.z - pb), (b * b) * pv + (a * a) * cc.w);
-          }
-        }
-      }
-    }
-    reset = covered && !reproj;
-    A.outCv[p] = out;
-    A.outLen[p] = hOut;
-  }
-  unsigned long long const br = __ballot(reproj), bs = __ballot(reset);
-  if ((threadIdx.x & 63u) == 0u) {
-    if (br != 0ull) atomicAdd(A.counts, uint32_t(__popcll(br)));
-    if (bs != 0ull) atomicAdd(A.counts + 1, uint32_t(__popcll(bs)));
-  }
-}
+#include "denoise.hpp"
 
 }  // namespace
 
@@ -2634,29 +2283,8 @@ struct dmt_ctx {
   DevBuf<unsigned long long> d_adMask;
   DevBuf<uint32_t> d_adList;
   DevBuf<uint32_t> d_adCount;
-  // denoiser (dmt_render_aovs / dmt_upload_aovs, dmt_denoise): the three feature planes and their size (0 x 0: none); the
-  // filter's scratch: a copy of a host film (mean, then M2), two (rgb, variance) planes, the count of refused pixels
-  DevBuf<float4> d_aovAlbedo, d_aovNormal, d_aovPos;
-  int aovW = 0, aovH = 0;
-  DevBuf<float4> d_dnFilm, d_dnCv;
-  DevBuf<uint32_t> d_dnBad;
-  // temporal accumulation (dmt_denoise_temporal).  The surface plane belongs to the AOVs; everything else is
-  // allocated by the first temporal call (temporalOn), never before
-  DevBuf<float4> d_aovSurface;
-  bool aovSurface = false;          // the surface plane matches the three AOV planes
-  bool temporalOn = false;          // a temporal call was made: the updates keep d_tvCur current
-  DevBuf<float4> d_thCv[2];         // accumulated (rgb, v), ping-pong; thSlot is the history
-  DevBuf<float> d_thLen[2];
-  DevBuf<float4> d_thNormal, d_thPos;  // the planes of the history's frame
-  DevBuf<uint32_t> d_thCounts;      // [0] reprojected, [1] reset
-  DevBuf<float> d_tvCur, d_tvPrev;  // raw vertices, 9 per triangle: current, and the history frame's once they differ
-  bool tvValid = false;             // d_tvCur holds the uploaded soup
-  bool tvPrevIsCur = true;          // no update since the history's frame: d_tvCur serves as both
-  int thSlot = 0, thW = 0, thH = 0;
-  bool thValid = false;             // false: the next call resets every pixel
-  ProjXf thCam{};                   // the camera of the history's frame, and its pixel angle
-  float thTheta = 0.f;
-  dmt_temporal_record thRecord{};
+  // the image-space layer: feature planes, the filter's scratch, the temporal history (denoise.hpp, denoise_host.hpp)
+  DenoiseState dn;
   uint32_t chunkSpp = 0;          // samples per work item, 0 = automatic
   int subShift = -1;               // row bands per tile (log2); -1 = choose per launch
   int maxDepth = 32;
@@ -3267,13 +2895,6 @@ void adoptCullTables(dmt_ctx* ctx, CullTables& T) {
 }
 
 // ---- dmt_update_vertices: timing and the update policy ----
-struct UpdateTimer {  // HIP events on the context's stream, destroyed on every exit path
-  hipEvent_t a = nullptr, b = nullptr;
-  ~UpdateTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
 int lbvhError(dmt_ctx* ctx, char const* stage, std::string const& what, hipError_t e) {
   ctx->err = std::string(stage) + ": " + what + ": " + hipGetErrorName(e) + " - " + hipGetErrorString(e);
   return DMT_ERR_HIP;
@@ -3287,7 +2908,7 @@ int treeCost(dmt_ctx* ctx, double& cost) {
 
 // The records, cull tables and host mirrors hold the new positions; T.a is recorded on the idle stream.  Applies
 // dmt_set_accel_update's policy to the tree and fills the update record.
-int finishUpdate(dmt_ctx* ctx, UpdateTimer& T) {
+int finishUpdate(dmt_ctx* ctx, EventPair& T) {
   dmt_accel_update_record& U = ctx->updateRecord;
   bool const bvh = ctx->accel == DMT_ACCEL_BVH;
   bool const refitting = bvh && ctx->haveBvh && ctx->accelUpdate != DMT_BVH_UPDATE_REBUILD && ctx->bvhLevels.size() >= 2;
@@ -3414,15 +3035,10 @@ int finishTest(dmt_ctx* ctx) {
   return DMT_OK;
 }
 
-struct EventPair {  // two HIP events, destroyed on every exit path (dmt_denoise)
-  hipEvent_t e[2] = {nullptr, nullptr};
-  ~EventPair() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
 }  // namespace
+
+// the image-space layer's entry points and the rules of its state; it uses the helpers above
+#include "denoise_host.hpp"
 
 static int rebuildAreaLights(dmt_ctx* ctx);
 
@@ -3535,8 +3151,7 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
   ctx->h_mat.assign(mat_id, mat_id + count);
   ctx->haveBvh = false;
-  ctx->thValid = false, ctx->tvValid = false;  // temporal history: its triangle indices are of the soup just replaced
-  ctx->thRecord.frames = 0;
+  ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
   ctx->h_areaTri.clear(), ctx->h_areaLe.clear();  // emissive triangles are indices into the soup just replaced
   if (int const rcA = rebuildAreaLights(ctx)) return rcA;
   if (ctx->accel == DMT_ACCEL_BVH) return buildBvh(ctx);
@@ -3544,32 +3159,8 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
 }
 
 namespace {
-// temporal accumulation: the raw vertices of the current soup, 9 floats per triangle, from the host copy.  The caller has
-// drained the stream (a kernel in flight may read the array)
-int uploadRawVertices(dmt_ctx* ctx) {
-  size_t const n = ctx->triCount;
-  std::vector<float> v(9 * n);
-  for (size_t i = 0; i < n; ++i)
-    for (size_t k = 0; k < 3; ++k)
-      v[9 * i + 3 * k] = ctx->h_xs[4 * i + k], v[9 * i + 3 * k + 1] = ctx->h_ys[4 * i + k], v[9 * i + 3 * k + 2] = ctx->h_zs[4 * i + k];
-  HIP_TRY(ctx, ctx->d_tvCur.assign(v.data(), v.size()));
-  ctx->tvValid = true;
-  return DMT_OK;
-}
-// before an update overwrites d_tvCur: the first update after the history's frame moves that frame's vertices to d_tvPrev
-// (beginUpdate has drained the stream).  wait: the overwrite is a host copy, not a launch on the stream.  Without a history
-// there is no such frame
-int keepHistoryVertices(dmt_ctx* ctx, bool wait) {
-  if (!ctx->tvPrevIsCur || !ctx->thValid) return DMT_OK;
-  size_t const n = 9 * size_t(ctx->triCount);
-  HIP_TRY(ctx, ctx->d_tvPrev.reserve(n ? n : 1));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tvPrev.get(), ctx->d_tvCur.get(), n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-  if (wait) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->tvPrevIsCur = false;
-  return DMT_OK;
-}
 // common entry of the two updates: argument and state checks, the stream drained, the timer started.  *done: nothing to do
-int beginUpdate(dmt_ctx* ctx, char const* name, bool nullArray, size_t count, UpdateTimer& T, bool* done) {
+int beginUpdate(dmt_ctx* ctx, char const* name, bool nullArray, size_t count, EventPair& T, bool* done) {
   *done = false;
   if (!ctx) return DMT_ERR_INVALID;
   if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "update of vertices before any dmt_upload_triangles");
@@ -3592,7 +3183,7 @@ int beginUpdate(dmt_ctx* ctx, char const* name, bool nullArray, size_t count, Up
 }  // namespace
 
 int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs, size_t count) {
-  UpdateTimer T;
+  EventPair T;
   bool done = false;
   if (int const rc = beginUpdate(ctx, "dmt_update_vertices", !xs || !ys || !zs, count, T, &done)) return rc;
   if (done) return DMT_OK;
@@ -3605,23 +3196,17 @@ int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const fl
   HIP_TRY(ctx, hipMemcpy(ctx->d_post.get(), b.data(), count * sizeof(TriPost), hipMemcpyHostToDevice));
   adoptCullTables(ctx, cull);
   ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
-  if (ctx->temporalOn && ctx->tvValid) {
-    if (int const rcT = keepHistoryVertices(ctx, true)) return rcT;
-    if (int const rcT = uploadRawVertices(ctx)) return rcT;
-  }
+  if (int const rcT = mirrorHostUpdate(ctx)) return rcT;
   return finishUpdate(ctx, T);
 }
 
 int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count) {
-  UpdateTimer T;
+  EventPair T;
   bool done = false;
   if (int const rc = beginUpdate(ctx, "dmt_update_vertices_device", !d_verts9, count, T, &done)) return rc;
   if (done) return DMT_OK;
   HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->d_tris.get(), ctx->d_post.get(), ctx->stream));
-  if (ctx->temporalOn && ctx->tvValid) {  // the caller's array has the layout of d_tvCur
-    if (int const rcT = keepHistoryVertices(ctx, false)) return rcT;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tvCur.get(), d_verts9, count * 9 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-  }
+  if (int const rcT = mirrorDeviceUpdate(ctx, d_verts9, count)) return rcT;
   // the host mirrors (the host builder's, the cull plan's and a later rebuild's input) from the records just made
   std::vector<TriPost> b(count);
   HIP_TRY(ctx, hipMemcpyAsync(b.data(), ctx->d_post.get(), count * sizeof(TriPost), hipMemcpyDeviceToHost, ctx->stream));
@@ -3727,7 +3312,7 @@ int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam) {
     ctx->ownMean = std::move(mean), ctx->ownM2 = std::move(m2);
     ctx->d_mean = ctx->ownMean.get(), ctx->d_m2 = ctx->ownM2.get();
     ctx->filmW = cam->width, ctx->filmH = cam->height;
-    ctx->thValid = false, ctx->thRecord.frames = 0;  // temporal history: it is of the old resolution
+    ctx->dn.dropHistory();  // temporal history: it is of the old resolution
   }
   ctx->cam = *cam;
   float m[16];
@@ -4523,309 +4108,6 @@ int dmt_texture_mip_chain(const uint8_t* rgba8, int width, int height, uint8_t* 
 int dmt_texture_footprint(const dmt_camera* cam, float* out) {
   if (!cam || !out || cam->width <= 0 || cam->height <= 0) return DMT_ERR_INVALID;
   textureFootprint(*cam, out);
-  return DMT_OK;
-}
-
-// ---- denoiser ------------------------------------------------------------------
-dmt_denoise_params dmt_denoise_defaults(void) {
-  dmt_denoise_params p;
-  p.iterations = 4, p.sigma_normal = 128.f, p.sigma_position = 1.f, p.sigma_albedo = 0.1f, p.sigma_luminance = 32.f;
-  return p;
-}
-
-int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (aov_spp == 0 || aov_spp > 65536u) return fail(ctx, DMT_ERR_INVALID, "dmt_render_aovs: aov_spp must be 1 .. 65536");
-  if (!(ctx->haveTris && ctx->haveBsdfs && ctx->haveCamera))
-    return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: upload triangles, bsdfs and set the camera first");
-  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_render_aovs: material index outside the BSDF array");
-  if (ctx->texCount > 0 && (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount))
-    return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
-  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
-  if (useBvh && !ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: BVH not built");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
-  ctx->aovW = ctx->aovH = 0;  // no AOVs unless this call succeeds
-  ctx->aovSurface = false;
-  HIP_TRY(ctx, ctx->d_aovAlbedo.reserve(pixels));
-  HIP_TRY(ctx, ctx->d_aovNormal.reserve(pixels));
-  HIP_TRY(ctx, ctx->d_aovPos.reserve(pixels));
-  HIP_TRY(ctx, ctx->d_aovSurface.reserve(pixels));
-  // a grid of a few 256-lane blocks per CU strides over the frame: the BVH overflow stack is sized by the launch's lanes
-  size_t const blocks = std::min((pixels + 255) / 256, size_t(std::max(ctx->cuCount, 1)) * 8);
-  size_t const threads = blocks * 256;
-  if (useBvh) HIP_TRY(ctx, reserveOverflow(ctx, threads));
-  AovArgs A{};
-  A.albedo = ctx->d_aovAlbedo.get(), A.normal = ctx->d_aovNormal.get(), A.position = ctx->d_aovPos.get();
-  A.surface = ctx->d_aovSurface.get();
-  A.width = ctx->filmW, A.pixels = uint32_t(pixels), A.aovSpp = aov_spp, A.useBvh = useBvh;
-  hipLaunchKernelGGL(k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, baseParams(ctx, threads), A);
-  HIP_TRY(ctx, hipGetLastError());
-  ctx->aovW = ctx->filmW, ctx->aovH = ctx->filmH;
-  ctx->aovSurface = true;
-  return DMT_OK;
-}
-
-int dmt_upload_aovs(dmt_ctx* ctx, const float* albedo4, const float* normal4, const float* position4, int width, int height) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!albedo4 || !normal4 || !position4 || width <= 0 || height <= 0)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_upload_aovs: three planes of a positive size");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a feature pass in flight writes the same planes
-  size_t const pixels = size_t(width) * size_t(height);
-  ctx->aovW = ctx->aovH = 0;
-  ctx->aovSurface = false;  // the surface plane is uploaded after these (dmt_upload_aov_surface)
-  HIP_TRY(ctx, ctx->d_aovAlbedo.assign(albedo4, pixels));
-  HIP_TRY(ctx, ctx->d_aovNormal.assign(normal4, pixels));
-  HIP_TRY(ctx, ctx->d_aovPos.assign(position4, pixels));
-  ctx->aovW = width, ctx->aovH = height;
-  return DMT_OK;
-}
-
-int dmt_download_aovs(dmt_ctx* ctx, float* albedo4, float* normal4, float* position4) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (ctx->aovW == 0) return fail(ctx, DMT_ERR_STATE, "dmt_download_aovs: no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  size_t const bytes = size_t(ctx->aovW) * size_t(ctx->aovH) * sizeof(float4);
-  if (albedo4) HIP_TRY(ctx, hipMemcpy(albedo4, ctx->d_aovAlbedo.get(), bytes, hipMemcpyDeviceToHost));
-  if (normal4) HIP_TRY(ctx, hipMemcpy(normal4, ctx->d_aovNormal.get(), bytes, hipMemcpyDeviceToHost));
-  if (position4) HIP_TRY(ctx, hipMemcpy(position4, ctx->d_aovPos.get(), bytes, hipMemcpyDeviceToHost));
-  return DMT_OK;
-}
-
-namespace {
-ProjXf makeProjXf(dmt_camera const& cam) {
-  float cf[16], rf[16];
-  cameraFromRaster(cam.focal_length, cam.sensor_size, uint32_t(cam.width), uint32_t(cam.height), cf);
-  worldFromCamera(cam.dir, cam.pos, rf);
-  ProjXf c{};
-  for (int a = 0; a < 3; ++a) c.right[a] = rf[a], c.up[a] = rf[4 + a], c.fwd[a] = rf[8 + a], c.pos[a] = rf[12 + a];
-  c.focal = cf[14], c.tx = cf[12], c.ty = cf[13];
-  c.ipx = 1.0f / cf[0], c.ipy = 1.0f / cf[5];
-  return c;
-}
-size_t temporalBytes(dmt_ctx const* ctx) {
-  return (ctx->d_thCv[0].size() + ctx->d_thCv[1].size() + ctx->d_thNormal.size() + ctx->d_thPos.size()) * sizeof(float4) +
-         (ctx->d_thLen[0].size() + ctx->d_thLen[1].size() + ctx->d_tvCur.size() + ctx->d_tvPrev.size()) * sizeof(float) +
-         ctx->d_thCounts.size() * sizeof(uint32_t);
-}
-// the first temporal call, a new resolution, a new soup: the history's planes and the current raw vertices
-int prepareHistory(dmt_ctx* ctx, size_t pixels) {
-  if (ctx->thW != ctx->filmW || ctx->thH != ctx->filmH) ctx->thValid = false;
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(ctx, ctx->d_thCv[i].reserve(pixels));
-    HIP_TRY(ctx, ctx->d_thLen[i].reserve(pixels));
-  }
-  HIP_TRY(ctx, ctx->d_thNormal.reserve(pixels));
-  HIP_TRY(ctx, ctx->d_thPos.reserve(pixels));
-  HIP_TRY(ctx, ctx->d_thCounts.reserve(2));
-  ctx->thW = ctx->filmW, ctx->thH = ctx->filmH;
-  if (!ctx->tvValid) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int const rc = uploadRawVertices(ctx)) return rc;
-    ctx->tvPrevIsCur = true;
-  }
-  if (!ctx->thValid) ctx->tvPrevIsCur = true, ctx->thRecord.frames = 0;  // no history frame whose vertices matter
-  ctx->temporalOn = true;
-  return DMT_OK;
-}
-
-// k_denoise_init (validation + pass-0 planes), then `iterations` k_atrous passes ping-ponging between two planes.  tp (the
-// temporal form): k_temporal between the two blends the pass-0 plane with the reprojected history into the new history,
-// which pass 0 then reads in place
-int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params, const dmt_temporal_params* tp, const float* mean4,
-               const float* m24, float* out4, float* kernel_ms) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (kernel_ms) *kernel_ms = 0.f;
-  dmt_denoise_params const p = params ? *params : dmt_denoise_defaults();
-  std::string const pre = std::string(name) + ": ";
-  auto failn = [&](int code, char const* msg) { return fail(ctx, code, (pre + msg).c_str()); };
-  if (!out4 || (mean4 == nullptr) != (m24 == nullptr)) return failn(DMT_ERR_INVALID, "out4 is required, and mean4 / m24 come both or not at all");
-  if (p.iterations < 0 || p.iterations > 10) return failn(DMT_ERR_INVALID, "iterations must be 0 .. 10");
-  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
-  if (!positive(p.sigma_normal) || !positive(p.sigma_position) || !positive(p.sigma_albedo) || !positive(p.sigma_luminance))
-    return failn(DMT_ERR_INVALID, "every sigma must be finite and > 0");
-  if (tp && (!(tp->alpha >= 0.f && tp->alpha <= 1.f) || !std::isfinite(tp->normal_threshold) || !positive(tp->plane_threshold)))
-    return failn(DMT_ERR_INVALID, "alpha must be 0 .. 1, normal_threshold finite, plane_threshold finite and > 0");
-  if (!ctx->haveCamera) return failn(DMT_ERR_STATE, "set the camera first");
-  if (ctx->aovW == 0) return failn(DMT_ERR_STATE, "no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
-  if (ctx->aovW != ctx->filmW || ctx->aovH != ctx->filmH) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "the AOVs are %d x %d, the film %d x %d", ctx->aovW, ctx->aovH, ctx->filmW, ctx->filmH);
-    return failn(DMT_ERR_STATE, msg);
-  }
-  if (tp && !ctx->aovSurface) return failn(DMT_ERR_STATE, "no surface plane (call dmt_render_aovs, or dmt_upload_aov_surface after dmt_upload_aovs)");
-  if (tp && !ctx->haveTris) return failn(DMT_ERR_STATE, "upload triangles first");
-  if (tp && ctx->triCount > (1u << 24)) return failn(DMT_ERR_STATE, "more than 2^24 triangles: the surface plane's float index is not exact");
-  if (!mean4 && !ctx->d_mean) return failn(DMT_ERR_STATE, "no film");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
-  float4 const* mean = ctx->d_mean;
-  float4 const* m2 = ctx->d_m2;
-  if (mean4) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, ctx->d_dnFilm.reserve(2 * pixels));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_dnFilm.get(), mean4, pixels * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_dnFilm.get() + pixels, m24, pixels * sizeof(float4), hipMemcpyHostToDevice));
-    mean = ctx->d_dnFilm.get(), m2 = ctx->d_dnFilm.get() + pixels;
-  }
-  HIP_TRY(ctx, ctx->d_dnCv.reserve(2 * pixels));
-  HIP_TRY(ctx, ctx->d_dnBad.reserve(1));
-  if (tp)
-    if (int const rc = prepareHistory(ctx, pixels)) return rc;
-  float4* const cv[2] = {ctx->d_dnCv.get(), ctx->d_dnCv.get() + pixels};
-  DenoiseArgs A{};
-  A.mean = mean, A.m2 = m2, A.albedo = ctx->d_aovAlbedo.get(), A.normal = ctx->d_aovNormal.get(), A.position = ctx->d_aovPos.get();
-  A.bad = ctx->d_dnBad.get(), A.width = ctx->filmW, A.height = ctx->filmH;
-  A.theta = ctx->cam.sensor_size / (ctx->cam.focal_length * float(ctx->cam.height));
-  A.sigmaN = p.sigma_normal, A.sigmaX = p.sigma_position, A.sigmaA = p.sigma_albedo, A.sigmaL = p.sigma_luminance;
-  EventPair ev, evT;
-  HIP_TRY(ctx, hipEventCreate(&ev.e[0]));
-  HIP_TRY(ctx, hipEventCreate(&ev.e[1]));
-  HIP_TRY(ctx, hipMemsetAsync(A.bad, 0, sizeof(uint32_t), ctx->stream));
-  if (tp) {
-    HIP_TRY(ctx, hipEventCreate(&evT.e[0]));
-    HIP_TRY(ctx, hipEventCreate(&evT.e[1]));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_thCounts.get(), 0, 2 * sizeof(uint32_t), ctx->stream));
-  }
-  HIP_TRY(ctx, hipEventRecord(ev.e[0], ctx->stream));
-  A.dst = cv[0];
-  hipLaunchKernelGGL(k_denoise_init, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, ctx->stream, A);
-  HIP_TRY(ctx, hipGetLastError());
-  dim3 const grid(uint32_t((ctx->filmW + 63) / 64), uint32_t((ctx->filmH + 3) / 4));
-  int const slotNew = ctx->thSlot ^ 1;
-  ProjXf const camCur = tp ? makeProjXf(ctx->cam) : ProjXf{};
-  if (tp) {
-    TemporalArgs T{};
-    T.cur = cv[0], T.albedo = A.albedo, T.normal = A.normal, T.surface = ctx->d_aovSurface.get();
-    T.vertsCur = ctx->d_tvCur.get(), T.vertsPrev = ctx->tvPrevIsCur ? ctx->d_tvCur.get() : ctx->d_tvPrev.get();
-    T.histCv = ctx->d_thCv[ctx->thSlot].get(), T.histLen = ctx->d_thLen[ctx->thSlot].get();
-    T.histNormal = ctx->d_thNormal.get(), T.histPos = ctx->d_thPos.get();
-    T.outCv = ctx->d_thCv[slotNew].get(), T.outLen = ctx->d_thLen[slotNew].get();
-    T.counts = ctx->d_thCounts.get();
-    T.camCur = camCur, T.camPrev = ctx->thValid ? ctx->thCam : camCur;
-    T.width = ctx->filmW, T.height = ctx->filmH, T.triCount = ctx->triCount, T.haveHistory = ctx->thValid ? 1 : 0;
-    T.alpha = tp->alpha, T.normalThreshold = tp->normal_threshold, T.planeThreshold = tp->plane_threshold;
-    T.thetaPrev = ctx->thValid ? ctx->thTheta : A.theta;
-    HIP_TRY(ctx, hipEventRecord(evT.e[0], ctx->stream));
-    hipLaunchKernelGGL(k_temporal, grid, dim3(256), 0, ctx->stream, T);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(evT.e[1], ctx->stream));
-  }
-  float4 const* result = tp ? ctx->d_thCv[slotNew].get() : cv[0];
-  for (int i = 0; i < p.iterations; ++i) {
-    A.src = result, A.dst = cv[(i + 1) & 1], A.step = 1 << i;
-    for (int dy = -2; dy <= 2; ++dy)
-      for (int dx = -2; dx <= 2; ++dx) A.tapDist[5 * (dy + 2) + dx + 2] = float(A.step) * std::sqrt(float(dx * dx + dy * dy));
-    hipLaunchKernelGGL(k_atrous, grid, dim3(256), 0, ctx->stream, A);
-    HIP_TRY(ctx, hipGetLastError());
-    result = A.dst;
-  }
-  HIP_TRY(ctx, hipEventRecord(ev.e[1], ctx->stream));
-  uint32_t bad = 0, counts[2] = {0, 0};
-  HIP_TRY(ctx, hipMemcpyAsync(&bad, A.bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
-  if (tp) HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->d_thCounts.get(), sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (!mean4)
-    if (int const rc = checkErrorFlag(ctx)) return rc;
-  if (bad) {
-    char msg[400];
-    snprintf(msg, sizeof(msg), "%u pixel(s) have fewer than 2 samples or a non-finite mean / M2%s", bad,
-             !mean4 && ctx->world > 1 ? " (this context renders only the tiles of its dmt_set_partition rank: combine the ranks' "
-                                        "films and pass the combined film as mean4 / m24)" : "");
-    return failn(DMT_ERR_STATE, msg);
-  }
-  float ms = 0.f;
-  HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  if (kernel_ms) *kernel_ms = ms;
-  HIP_TRY(ctx, hipMemcpy(out4, result, pixels * sizeof(float4), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < pixels; ++i) out4[4 * i + 3] = 1.f;
-  if (tp) {  // the call succeeded: its plane, its AOVs, its camera and its vertices become the history
-    float msT = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&msT, evT.e[0], evT.e[1]));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_thNormal.get(), ctx->d_aovNormal.get(), pixels * sizeof(float4), hipMemcpyDeviceToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_thPos.get(), ctx->d_aovPos.get(), pixels * sizeof(float4), hipMemcpyDeviceToDevice));
-    ctx->thSlot = slotNew, ctx->thValid = true, ctx->tvPrevIsCur = true;
-    ctx->thCam = camCur, ctx->thTheta = A.theta;
-    ctx->thRecord.frames += 1, ctx->thRecord.reprojected = counts[0], ctx->thRecord.reset = counts[1], ctx->thRecord.temporal_ms = msT;
-  }
-  return DMT_OK;
-}
-}  // namespace
-
-int dmt_denoise(dmt_ctx* ctx, const dmt_denoise_params* params, const float* mean4, const float* m24, float* out4, float* kernel_ms) {
-  return denoiseRun(ctx, "dmt_denoise", params, nullptr, mean4, m24, out4, kernel_ms);
-}
-
-// ---- temporal accumulation ---------------------------------------------------------
-dmt_temporal_params dmt_temporal_defaults(void) {
-  dmt_temporal_params p;
-  p.alpha = 0.2f, p.normal_threshold = 0.9f, p.plane_threshold = 2.f;
-  return p;
-}
-
-int dmt_denoise_temporal(dmt_ctx* ctx, const dmt_denoise_params* params, const dmt_temporal_params* tparams, const float* mean4,
-                         const float* m24, float* out4, float* kernel_ms) {
-  dmt_temporal_params const tp = tparams ? *tparams : dmt_temporal_defaults();
-  return denoiseRun(ctx, "dmt_denoise_temporal", params, &tp, mean4, m24, out4, kernel_ms);
-}
-
-int dmt_temporal_reset(dmt_ctx* ctx) {
-  if (!ctx) return DMT_ERR_INVALID;
-  ctx->thValid = false;
-  ctx->thRecord.frames = 0;
-  return DMT_OK;
-}
-
-int dmt_temporal_info(dmt_ctx* ctx, dmt_temporal_record* out) {
-  if (!ctx || !out) return DMT_ERR_INVALID;
-  *out = ctx->thRecord;
-  out->history_bytes = temporalBytes(ctx);
-  return DMT_OK;
-}
-
-int dmt_temporal_download(dmt_ctx* ctx, float* color_var4, float* length1) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->thValid) return fail(ctx, DMT_ERR_STATE, "dmt_temporal_download: no history (call dmt_denoise_temporal first)");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  size_t const pixels = size_t(ctx->thW) * size_t(ctx->thH);
-  if (color_var4) HIP_TRY(ctx, hipMemcpy(color_var4, ctx->d_thCv[ctx->thSlot].get(), pixels * sizeof(float4), hipMemcpyDeviceToHost));
-  if (length1) HIP_TRY(ctx, hipMemcpy(length1, ctx->d_thLen[ctx->thSlot].get(), pixels * sizeof(float), hipMemcpyDeviceToHost));
-  return DMT_OK;
-}
-
-int dmt_download_aov_surface(dmt_ctx* ctx, float* surface4) {
-  if (!ctx || !surface4) return DMT_ERR_INVALID;
-  if (ctx->aovW == 0 || !ctx->aovSurface) return fail(ctx, DMT_ERR_STATE, "dmt_download_aov_surface: no surface plane (call dmt_render_aovs or dmt_upload_aov_surface first)");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipMemcpy(surface4, ctx->d_aovSurface.get(), size_t(ctx->aovW) * size_t(ctx->aovH) * sizeof(float4), hipMemcpyDeviceToHost));
-  return DMT_OK;
-}
-
-int dmt_upload_aov_surface(dmt_ctx* ctx, const float* surface4, int width, int height) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!surface4 || width <= 0 || height <= 0) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_aov_surface: a plane of a positive size");
-  if (width != ctx->aovW || height != ctx->aovH)
-    return fail(ctx, DMT_ERR_STATE, "dmt_upload_aov_surface: the plane must have the size of the context's AOVs (upload or render those first)");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->aovSurface = false;
-  HIP_TRY(ctx, ctx->d_aovSurface.assign(surface4, size_t(width) * size_t(height)));
-  ctx->aovSurface = true;
-  return DMT_OK;
-}
-
-int dmt_camera_project(const dmt_camera* cam, int n, const float* p3, float* xy2, float* depth) {
-  if (!cam || n < 0 || (n && (!p3 || !xy2 || !depth)) || cam->width <= 0 || cam->height <= 0) return DMT_ERR_INVALID;
-  ProjXf const c = makeProjXf(*cam);
-  for (int i = 0; i < n; ++i) {
-    Proj const o = project_point(c, p3[3 * size_t(i)], p3[3 * size_t(i) + 1], p3[3 * size_t(i) + 2]);
-    xy2[2 * size_t(i)] = o.fx, xy2[2 * size_t(i) + 1] = o.fy, depth[i] = o.depth;
-  }
   return DMT_OK;
 }
 

@@ -2,7 +2,7 @@
 // device function over arrays of cases, which is how the tests compare the device code with the oracle function by function.
 //
 // Part of dmt_hip.hip's translation unit, included once at its end: it uses the device code, dmt_ctx, HIP_TRY, fail,
-// baseParams, reserveOverflow, resolveFeatures / kernelOf, finishTest and makeProjXf defined there.  A probe is a kernel with
+// baseParams, reserveOverflow, resolveFeatures / kernelOf and finishTest defined there, and denoise_host.hpp's makeProjXf.  A probe is a kernel with
 // one lane per case and an entry point that stages its arrays through probe_stage.hpp.
 #pragma once
 

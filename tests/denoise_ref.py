@@ -3,7 +3,7 @@ Dammertz et al. 2010 with the variance-guided luminance term of Schied et al. 20
 dmt_render_aovs.
 
 Every quantity is float32 and every expression is evaluated in the order the device kernels (k_denoise_init, k_atrous in
-csrc/dmt_hip.hip) evaluate it, so the GPU's output matches this module to the rounding of exp / pow / sqrt / division.
+csrc/denoise.hpp) evaluate it, so the GPU's output matches this module to the rounding of exp / pow / sqrt / division.
 The AOVs are not packed (fp32 planes), so nothing here has to mirror a quantisation.
 """
 import numpy as np

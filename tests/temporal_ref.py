@@ -1,6 +1,6 @@
 """numpy restatement of dmt_denoise_temporal's reprojection: the world-to-film projection
 (dmt_camera_project), the surface point under two vertex sets, the 2 x 2 history taps with their tests, the blend and its
-variance.  Every quantity is float32 and every expression is evaluated in the order k_temporal (csrc/dmt_hip.hip) evaluates
+variance.  Every quantity is float32 and every expression is evaluated in the order k_temporal (csrc/denoise.hpp) evaluates
 it, so the device matches this module to the rounding of its divisions.
 
 Next to its outputs `accumulate` returns a near-threshold mask: the pixels where one of its own tap tests lies within a

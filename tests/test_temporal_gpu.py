@@ -1,11 +1,16 @@
 """Temporal accumulation on the GPU (dmt_denoise_temporal).  The reprojection kernel is checked against
 the numpy restatement (tests/temporal_ref.py) on synthetic inputs with real motion and on the Cornell box with a moved box;
 the accumulation against the plain mean of the frames; alpha = 1 against dmt_denoise; its invariance under a common
-translation of scene and camera; the surface plane against the camera-ray and closest-hit probes; the C ABI's invariants;
-and the quality on two scenes against dmt_denoise of the last frame alone.
+translation of scene and camera; the history across update_vertices against update_vertices_device; the surface plane
+against the camera-ray and closest-hit probes; the C ABI's invariants; and the quality on two scenes against dmt_denoise of
+the last frame alone.
 
 Where a device result is compared with the restatement, only the restatement's near-threshold mask is left out, and a mask
 over temporal_ref.MASK_CAP of the pixels fails the test."""
+import subprocess
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 
@@ -124,6 +129,28 @@ def test_a_reprojection_matches_the_restatement(pkg, seed):
         mean_b, m2_b = b["film"](5)
         out0 = r.denoise_temporal({"iterations": 0}, film=(mean_b, m2_b))
         assert np.array_equal(out0[..., :3].view(np.uint32), mean_b[..., :3].view(np.uint32))  # after a reset: the film itself
+
+
+def test_a_device_pointer_updates_keep_the_history_frames_vertices(tmp_path):
+    """Frame A, an update to B's vertices, frame B (the synthetic pair of the test above, seed 1), four ways in one child
+    process (tests/_temporal_device_worker.py: torch must open the GPU before the HIP library does): update_vertices,
+    update_vertices_device from a torch tensor, and each with an update to the midpoint first.  k_temporal reads only the
+    planes, the two cameras and the two raw-vertex arrays; after B those hold the same floats whichever way they arrived,
+    and the history frame's vertices are A's in all four runs, so everything agrees bit for bit.  Were the history frame's
+    vertices snapshotted again by the second update, they would be the midpoint's and `reprojected` would move."""
+    out = tmp_path / "out.npz"
+    p = subprocess.run([sys.executable, str(Path(__file__).resolve().parent / "_temporal_device_worker.py"), str(out)], capture_output=True,
+                       text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    d = dict(np.load(out))
+    frames, reprojected, reset = (int(x) for x in d["host_info"])
+    print(f"host: frames {frames}, reprojected {reprojected}, reset {reset}")
+    assert frames == 2 and reprojected > 0
+    for tag in ("device", "host_twice", "device_twice"):
+        print(f"{tag}: (frames, reprojected, reset) {tuple(int(x) for x in d[tag + '_info'])}")
+        assert np.array_equal(d[tag + "_info"], d["host_info"]), tag
+        for plane in ("out", "cv", "len"):
+            assert np.array_equal(d[f"{tag}_{plane}"].view(np.uint32), d[f"host_{plane}"].view(np.uint32)), (tag, plane)
 
 
 def test_a_camera_projection_probe_matches_the_host(cb, pkg):
