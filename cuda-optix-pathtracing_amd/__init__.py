@@ -34,6 +34,7 @@ from .binding import (  # noqa: F401
     texture_footprint,
     temporal_defaults,
     camera_project,
+    lens_rays,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "dmt_download_aov_surface", "dmt_upload_aov_surface", "dmt_camera_project", "dmt_test_camera_project", "dmt_temporal_defaults",
     "dmt_denoise_temporal", "dmt_temporal_reset", "dmt_temporal_info", "dmt_temporal_download",
     "dmt_set_sampler_table", "dmt_sampler_table_plan", "dmt_test_sampler_table",
+    "dmt_set_lens", "dmt_lens_info", "dmt_lens_rays", "dmt_focus_distance_at", "dmt_test_lens_values",
 ]
 
 # dmt_set_sampler_table modes (include/dmt_hip.h)
@@ -157,6 +158,23 @@ def camera_project(camera44, points):
     if rc != 0:
         raise DmtError(f"dmt_camera_project failed ({rc})")
     return xy, depth
+
+
+def lens_rays(camera44, lens_radius, focus_distance, pxs, pys, ss):
+    """Host only (dmt_lens_rays): the camera rays of samples ss of pixels (pxs, pys) under a thin lens (radius 0: the pinhole
+    rays) -> (origins [n, 3], directions [n, 3], lens values (u10, u11) [n, 2]).  The serial twin of the device code."""
+    lib = load_library()
+    cam = np.ascontiguousarray(camera44, np.uint8).reshape(44)
+    pxs, pys, ss = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (pxs, pys, ss))
+    n = pxs.shape[0]
+    assert pys.shape[0] == n and ss.shape[0] == n
+    o, d, u = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 2), np.float32)
+    as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = lib.dmt_lens_rays(as_p(cam), C.c_float(lens_radius), C.c_float(focus_distance), int(n), as_p(pxs), as_p(pys), as_p(ss),
+                           as_p(o), as_p(d), as_p(u))
+    if rc != 0:
+        raise DmtError(f"dmt_lens_rays failed ({rc})")
+    return o, d, u
 
 
 # dmt_set_texture_filter modes (include/dmt_hip.h)
@@ -445,12 +463,33 @@ class Renderer:
         self.width = int(cam[24:28].view(np.int32)[0])
         self.height = int(cam[28:32].view(np.int32)[0])
 
+    def set_lens(self, lens_radius, focus_distance=1.0):
+        """Thin lens (dmt_set_lens): radius >= 0 (0 = pinhole, the default) and focus distance > 0 along the viewing
+        direction, in scene units.  The lens survives set_camera and scene uploads."""
+        self._check(self._lib.dmt_set_lens(self._ctx, C.c_float(lens_radius), C.c_float(focus_distance)), "dmt_set_lens")
+
+    def lens_info(self):
+        """(lens_radius, focus_distance) of the context."""
+        r, d = C.c_float(), C.c_float()
+        self._check(self._lib.dmt_lens_info(self._ctx, C.byref(r), C.byref(d)), "dmt_lens_info")
+        return r.value, d.value
+
+    def focus_distance_at(self, fx, fy):
+        """Autofocus (dmt_focus_distance_at): the depth along the viewing direction of what the pinhole ray through the
+        continuous film coordinates (fx, fy) hits; DmtError when it leaves the scene."""
+        d = C.c_float()
+        self._check(self._lib.dmt_focus_distance_at(self._ctx, C.c_float(fx), C.c_float(fy), C.byref(d)), "dmt_focus_distance_at")
+        return d.value
+
     def upload_scene(self, scene):
-        """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays."""
+        """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays; a scene with a `lens`
+        (lens_radius, focus_distance), as the loaders report one, sets the context's lens too."""
         self.upload_triangles(scene.xs, scene.ys, scene.zs, scene.mat_id)
         self.upload_bsdfs(scene.bsdfs)
         self.upload_lights(scene.lights, scene.inf_lights)
         self.set_camera(scene.camera)
+        if getattr(scene, "lens", None) is not None:
+            self.set_lens(float(scene.lens[0]), float(scene.lens[1]))
         if getattr(scene, "area_tri", None) is not None and len(scene.area_tri):
             self.upload_area_lights(scene.area_tri, scene.area_le)
         if getattr(scene, "env_rgb", None) is not None:
@@ -777,6 +816,14 @@ class Renderer:
         self._check(self._lib.dmt_test_camera_rays(self._ctx, n, _p(pxs), _p(pys), _p(ss), _p(o), _p(d)),
                     "dmt_test_camera_rays")
         return o, d
+
+    def test_lens_values(self, pxs, pys, ss):
+        """dmt_test_lens_values: (u10, u11) [n, 2] of the samples, as the device computes them."""
+        pxs, pys, ss = _i32(pxs), _i32(pys), _i32(ss)
+        n = pxs.shape[0]
+        u = np.zeros((n, 2), np.float32)
+        self._check(self._lib.dmt_test_lens_values(self._ctx, n, _p(pxs), _p(pys), _p(ss), _p(u)), "dmt_test_lens_values")
+        return u
 
     def test_bsdf(self, bsdf32, ns, wo, u2, uc, wi_eval):
         b = np.ascontiguousarray(bsdf32, np.uint8).reshape(32)

@@ -9,7 +9,8 @@
 // ---------------------------------------------------------------------------------------------
 // denoiser (dmt_render_aovs, dmt_denoise)
 // ---------------------------------------------------------------------------------------------
-// Feature pass: camera samples 0 .. aovSpp-1 of every pixel of the frame, the film's own camera rays, closest hit as
+// Feature pass: camera samples 0 .. aovSpp-1 of every pixel of the frame, the film's own camera rays (lens rays under
+// dmt_set_lens, so the features blur where the image blurs), closest hit as
 // k_test_closest finds it.  Per pixel, summed in sample order over the samples whose ray hit a triangle ("hits"):
 //   albedo   = (sum W / aovSpp, hits / aovSpp)     W = the record's fp16 weight after the level-0 texture patch;
 //                                                   BS_GGX_BLEND: (1 - mix) W_diel + mix W_cond, mix clamped to [0, 1]
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
       // camera and sampler re-read from the kernel arguments at the point of use: held in SGPRs across the triangle pass
       // they would spill (see kargs)
       ColdArgs const c = load_cold_args(k);
-      Ray const r = camera_ray(c.cam, c.sp, px, py, base + int32_t(s) * (c.sp.scale0 * c.sp.scale1));
+      Ray const r = camera_ray_any(c.cam, c.sp, px, py, base + int32_t(s) * (c.sp.scale0 * c.sp.scale1), kargs(k)->lensR, kargs(k)->lensD);  // the film's rays: lens rays under a lens
       set_ray(st, r.o, r.d);
       st.active = alive;
       int best;

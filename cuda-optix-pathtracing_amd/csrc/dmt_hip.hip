@@ -103,7 +103,9 @@ struct RenderParams {
   // samples from samTabS0 on and shared by every pixel congruent modulo 128.  Key [sample - samTabS0][py & 127][px & 127].
   float4 const* samTab;      // two float4 per entry: the 8 dimension values
   float2 const* samTabJit;   // one float2 per entry: pixel2d, the film jitter
+  float2 const* samTabLens;  // launches with a lens only: one float2 per entry, lens_values (u10, u11)
   uint32_t samTabS0, samTabPw, samTabPh;
+  float lensR, lensD;        // thin lens (dmt_set_lens): radius (0: pinhole) and focus distance; read where a camera ray is made
   int maxDepth;
   int shadeThreshold;         // BVH megakernel: shade when this many lanes of the wave have finished their rays (bvhShadeThreshold)
   EnvView env;                // A18 env map (w == 0: none); read by the *_env kernels only
@@ -243,10 +245,10 @@ DMT_DEV void set_shadow_ray(PathState& st, f3 o, f3 d) {
 }
 
 DMT_DEV void path_begin(PathState& st, CameraXf const& cam, SamplerParams const& sp, int px, int py,
-                        int32_t pixBase, uint32_t s) {
+                        int32_t pixBase, uint32_t s, float lensR, float lensD) {
   int32_t const hidx = pixBase + int32_t(s) * (sp.scale0 * sp.scale1);
   st.rng.start(uint32_t(hidx));
-  Ray const r = camera_ray(cam, sp, px, py, hidx);
+  Ray const r = camera_ray_any(cam, sp, px, py, hidx, lensR, lensD);
   set_ray(st, r.o, r.d);
   st.beta = mk3(1, 1, 1);
   st.L = mk3(0, 0, 0);
@@ -1367,7 +1369,38 @@ DMT_DEV ColdArgs load_cold_args(KArgs Pk) {
 // aligned vector loads per sample -- instead of computed: ~60 scrambled digits, a run-time division and a base-3 radical
 // inverse per lane, repeated for every pixel congruent modulo 128.  The table holds what the code below computes, written by
 // the same functions (k_sampler_table), so both paths prepare bit-identical samples.  The table's pointers and geometry are
-// read from the kernel arguments here, like the cold arguments.
+// read from the kernel arguments here, like the cold arguments, and so is the lens (dmt_set_lens): a second wave-uniform
+// branch, which makes the sample's ray a lens ray (prepare_lens_ray) and changes nothing else about the sample.
+// The lens ray of a prepared sample, over the pinhole ray in s_prep[8..13].  It runs after the lens-free code instead of
+// branching inside it, and reads everything it needs from the kernel arguments again, so that the code and the live ranges
+// of a launch without a lens stay the parent's.  Measured with -Rpass-analysis=kernel-resource-usage: a
+// branch inside the lens-free code, or this tail laid out in line, cost k_megakernel_bvh_env a spilled VGPR (8 bytes of
+// scratch), and a noinline function gave eight rows a stack frame (and cannot take the opaque kernarg pointer); as an
+// unlikely tail no row gains scratch.
+DMT_DEV void prepare_lens_ray(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
+  float* const prep = s_prep + threadIdx.x;
+  f2 jit;
+  LensU lu;
+  if (float2 const* const tab = kargs(Pk)->samTabLens) {  // launches with a table: its jitter and lens planes
+    KArgs const k = kargs(Pk);
+    uint32_t const e = ((s - k->samTabS0) * k->samTabPh + (uint32_t(py) & 127u)) * k->samTabPw + (uint32_t(px) & 127u);
+    float2 const j = k->samTabJit[e], u = tab[e];
+    jit = mk2(j.x, j.y), lu = LensU{u.x, u.y};
+  } else {
+    KArgs const k = kargs(Pk);
+    SamplerParams sp;
+    sp.scale0 = k->sp.scale0, sp.scale1 = k->sp.scale1, sp.exp0 = k->sp.exp0, sp.exp1 = k->sp.exp1, sp.inv0 = k->sp.inv0, sp.inv1 = k->sp.inv1;
+    int32_t const hidx = pixBase + int32_t(s) * (sp.scale0 * sp.scale1);
+    jit = pixel2d(sp, hidx), lu = lens_values(uint32_t(hidx));
+  }
+  CameraXf cam;
+  KArgs const kc = kargs(Pk);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) cam.cfr[i] = kc->cam.cfr[i], cam.rfc[i] = kc->cam.rfc[i];
+  Ray const r = camera_ray_lens(cam, px, py, jit, kc->lensR, kc->lensD, lu);
+  prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
+  prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
+}
 DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
   float* const prep = s_prep + threadIdx.x;
   Ray r;
@@ -1393,6 +1426,7 @@ DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t 
   }
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
+  if (__builtin_expect(kargs(Pk)->lensR > 0.f, 0)) prepare_lens_ray(Pk, px, py, pixBase, s);  // wave-uniform, laid out of line
 }
 DMT_DEV void path_begin_prepared(PathState& st) {
   float const* const prep = s_prep + threadIdx.x;
@@ -2073,8 +2107,9 @@ DMT_STATS_MEGAKERNELS(DMT_DEFINE_MEGAKERNEL)
 
 // Fills the sampler table of a launch (RenderParams::samTab): one thread per entry (sample s0 + k, period pixel (x, y)),
 // with the functions prepare_sample's compute path calls, so that a loaded sample is the computed one bit for bit.
+// `lens` (null without a lens): the third plane, lens_values of the entry's Halton index.
 __global__ void __launch_bounds__(256) k_sampler_table(SamplerParams sp, uint32_t s0, uint32_t n, uint32_t pw, uint32_t ph,
-                                                       float4* vals, float2* jit) {
+                                                       float4* vals, float2* jit, float2* lens) {
   uint32_t const e = blockIdx.x * 256u + threadIdx.x;  // (entries < 2^31: samplerTablePlan)
   if (e >= n * pw * ph) return;
   uint32_t const x = e % pw, row = e / pw, y = row % ph, k = row / ph;
@@ -2085,6 +2120,10 @@ __global__ void __launch_bounds__(256) k_sampler_table(SamplerParams sp, uint32_
   vals[2 * size_t(e) + 1] = make_float4(u[4 * kLdsThreads], u[5 * kLdsThreads], u[6 * kLdsThreads], u[7 * kLdsThreads]);
   f2 const p = pixel2d(sp, hidx);
   jit[e] = make_float2(p.x, p.y);
+  if (lens) {
+    LensU const u = lens_values(uint32_t(hidx));
+    lens[e] = make_float2(u.x, u.y);
+  }
 }
 
 // ---- adaptive sampling (dmt_render_adaptive) --------------------------------------------------------
@@ -2145,6 +2184,7 @@ __global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
 // =============================================================================================
 // ---- sampler table: the host's plan ----------------------------------------------------------------
 constexpr uint32_t kSamTabEntryBytes = 40;                  // 8 dimension values (two float4) + the film jitter (one float2)
+constexpr uint32_t kSamTabLensEntryBytes = 48;              // launches with a lens: + the lens values (one float2)
 constexpr uint64_t kSamTabDefaultBudget = 512ull << 20;
 // Automatic mode uses the table when the launch's owned pixels are at least this many periods: the fill costs one
 // period's worth of sampler arithmetic per sample, the compute path `ratio` periods' worth, so the table saves
@@ -2160,7 +2200,8 @@ struct SamplerTablePlan {
   uint32_t sliceChunks = 0;     // sample chunks per slice (the last slice has what is left)
 };
 // Pure host arithmetic (dmt_sampler_table_plan exposes it).  chunkSpp: samples per work item of the launch, <= spp.
-static SamplerTablePlan samplerTablePlan(int width, int height, uint64_t ownedPixels, uint32_t spp, uint32_t chunkSpp, uint64_t budget, int mode) {
+static SamplerTablePlan samplerTablePlan(int width, int height, uint64_t ownedPixels, uint32_t spp, uint32_t chunkSpp, uint64_t budget, int mode,
+                                         uint32_t entryBytes = kSamTabEntryBytes) {
   SamplerTablePlan p;
   if (width <= 0 || height <= 0) return p;
   p.pw = uint32_t(width < 128 ? width : 128), p.ph = uint32_t(height < 128 ? height : 128);
@@ -2169,7 +2210,7 @@ static SamplerTablePlan samplerTablePlan(int width, int height, uint64_t ownedPi
   uint64_t const period = uint64_t(p.pw) * p.ph;
   if (mode != DMT_SAMPLER_TABLE_FORCE && ownedPixels < kSamTabMinRatio * period) return p;
   uint64_t const chunkEntries = uint64_t(chunkSpp) * period;
-  uint64_t maxChunks = budget / (chunkEntries * kSamTabEntryBytes);
+  uint64_t maxChunks = budget / (chunkEntries * entryBytes);
   uint64_t const maxChunksByIndex = 0x7FFFFFFFull / chunkEntries;  // entry indices are 32-bit on the device
   if (maxChunks > maxChunksByIndex) maxChunks = maxChunksByIndex;
   if (maxChunks == 0) return p;  // not even one chunk fits: the launch computes its samples
@@ -2263,6 +2304,7 @@ struct dmt_ctx {
   dmt_camera cam{};
   CameraXf xf{};
   SamplerParams sp{};
+  float lensR = 0.f, lensD = 1.f;  // thin lens (dmt_set_lens): radius 0 = pinhole; survives dmt_set_camera and scene uploads
   // film: the context's own, or the caller's after dmt_film_bind (which frees the own one)
   DevBuf<float4> ownMean, ownM2;
   float4* d_mean = nullptr;
@@ -2277,6 +2319,7 @@ struct dmt_ctx {
   // sampler table of a launch (samplerTablePlan, k_sampler_table): refilled by every dmt_render call that uses it, grown on demand
   DevBuf<float4> d_samTab;
   DevBuf<float2> d_samTabJit;
+  DevBuf<float2> d_samTabLens;                   // launches with a lens only
   int samTabMode = DMT_SAMPLER_TABLE_AUTO;       // dmt_set_sampler_table, DMT_SAMPLER_TABLE at context creation
   uint64_t samTabBudget = kSamTabDefaultBudget;  // bytes of table memory a launch may use; larger tables are filled in sample slices
   // dmt_render_adaptive: per tile of the film's tile grid a mask word, the list of tiles with active pixels, two counters
@@ -2693,6 +2736,7 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.bvh = bvhView(c, threads);
   P.cam = c->xf;
   P.sp = c->sp;
+  P.lensR = c->lensR, P.lensD = c->lensD;
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = bvhShadeThreshold(c);
   P.env = c->env;
@@ -3638,7 +3682,8 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   // samples per pass, and an adaptive round's live pixel count is on the device.  The owned pixels are counted in whole tiles.
   SamplerTablePlan tab;
   if (!stats6 && !wavefront && !sel)
-    tab = samplerTablePlan(ctx->filmW, ctx->filmH, uint64_t(ownedTiles) * 64u, spp, P.chunkSpp, ctx->samTabBudget, ctx->samTabMode);
+    tab = samplerTablePlan(ctx->filmW, ctx->filmH, uint64_t(ownedTiles) * 64u, spp, P.chunkSpp, ctx->samTabBudget, ctx->samTabMode,
+                           ctx->lensR > 0.f ? kSamTabLensEntryBytes : kSamTabEntryBytes);
 
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   uint32_t const wavesWanted = P.numItems * P.numChunks < P.numItems ? P.numItems : P.numItems * P.numChunks;
@@ -3676,6 +3721,10 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
     HIP_TRY(ctx, ctx->d_samTab.reserve(2 * sliceEntries));
     HIP_TRY(ctx, ctx->d_samTabJit.reserve(sliceEntries));
     P.samTab = ctx->d_samTab.get(), P.samTabJit = ctx->d_samTabJit.get(), P.samTabPw = tab.pw, P.samTabPh = tab.ph;
+    if (ctx->lensR > 0.f) {
+      HIP_TRY(ctx, ctx->d_samTabLens.reserve(sliceEntries));
+      P.samTabLens = ctx->d_samTabLens.get();
+    }
   }
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_counter.get(), 0, sizeof(uint32_t), ctx->stream));
   HIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream));
@@ -3714,7 +3763,7 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
         P.samTabS0 = P.sampleOffset;
         uint32_t const entries = n * tab.pw * tab.ph;
         hipLaunchKernelGGL(k_sampler_table, dim3((entries + 255u) / 256u), dim3(256), 0, ctx->stream, P.sp, P.samTabS0, n, tab.pw, tab.ph,
-                           ctx->d_samTab.get(), ctx->d_samTabJit.get());
+                           ctx->d_samTab.get(), ctx->d_samTabJit.get(), const_cast<float2*>(P.samTabLens));
         HIP_TRY(ctx, hipGetLastError());
       }
       hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, ctx->stream, P);
@@ -4052,6 +4101,104 @@ int dmt_sampler_table_plan(int width, int height, uint64_t owned_pixels, uint32_
   out->slice_bytes = std::min<uint64_t>(sliceSamples, spp) * p.pw * p.ph * kSamTabEntryBytes;
   for (uint32_t k = 0; k < p.slices && k < slice_cap; ++k)
     slice_spp[k] = uint32_t(std::min<uint64_t>(sliceSamples, spp - k * sliceSamples));
+  return DMT_OK;
+}
+
+// ---- thin lens ------------------------------------------------------------------------
+int dmt_set_lens(dmt_ctx* ctx, float lens_radius, float focus_distance) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!std::isfinite(lens_radius) || lens_radius < 0.f) return fail(ctx, DMT_ERR_INVALID, "dmt_set_lens: the radius must be finite and >= 0");
+  if (lens_radius > 0.f && !(std::isfinite(focus_distance) && focus_distance > 0.f))
+    return fail(ctx, DMT_ERR_INVALID, "dmt_set_lens: the focus distance must be finite and > 0");
+  ctx->lensR = lens_radius;
+  if (lens_radius > 0.f) ctx->lensD = focus_distance;  // radius 0: the distance is ignored
+  return DMT_OK;
+}
+
+int dmt_lens_info(dmt_ctx* ctx, float* lens_radius, float* focus_distance) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (lens_radius) *lens_radius = ctx->lensR;
+  if (focus_distance) *focus_distance = ctx->lensD;
+  return DMT_OK;
+}
+
+// The host's camera ray through the continuous film position (fx, fy): camera_ray_jittered and camera_ray_lens in plain
+// fp32 without contraction, with the host's division, square root, sine and cosine where the device has its own.
+static void hostCameraRay(CameraXf const& xf, float fx, float fy, float lensR, float focusD, LensU u, float* o3, float* d3) {
+#pragma clang fp contract(off)
+  float d[3];
+  if (lensR > 0.f) {
+    // sample_uniform_disk (pt_device.hpp), the reference's branches
+    float const a = 2.f * u.x - 1.f, b = 2.f * u.y - 1.f;
+    float lx = 0.f, ly = 0.f;
+    if (!(a == 0.f && b == 0.f)) {
+      float rho, phi;
+      if (std::fabs(a) > std::fabs(b))
+        rho = a, phi = (kPi / 4) * (b / a);
+      else
+        rho = b, phi = (3 * kPi / 4) * (a / b);
+      lx = rho * std::cos(phi), ly = rho * std::sin(phi);
+    }
+    lens_ray_parts(xf.cfr, xf.rfc, fx, fy, focusD, lensR * lx, lensR * ly, o3, d);
+  } else {  // xf_point / xf_dir of camera_ray_jittered (both matrices affine: w == 1)
+    float const* const c = xf.cfr;
+    float const* const m = xf.rfc;
+    float const cx = c[0] * fx + c[4] * fy + c[8] * 0.0f + c[12];
+    float const cy = c[1] * fx + c[5] * fy + c[9] * 0.0f + c[13];
+    float const cz = c[2] * fx + c[6] * fy + c[10] * 0.0f + c[14];
+    for (int i = 0; i < 3; ++i) {
+      o3[i] = m[i] * 0.f + m[4 + i] * 0.f + m[8 + i] * 0.f + m[12 + i];
+      d[i] = m[i] * cx + m[4 + i] * cy + m[8 + i] * cz;
+    }
+  }
+  float const inv = 1.0f / std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  d3[0] = d[0] * inv, d3[1] = d[1] * inv, d3[2] = d[2] * inv;
+}
+static CameraXf hostCameraXf(dmt_camera const& cam) {
+  CameraXf xf{};
+  cameraFromRaster(cam.focal_length, cam.sensor_size, uint32_t(cam.width), uint32_t(cam.height), xf.cfr);
+  worldFromCamera(cam.dir, cam.pos, xf.rfc);
+  return xf;
+}
+
+int dmt_lens_rays(const dmt_camera* cam, float lens_radius, float focus_distance, int n, const int32_t* pxs, const int32_t* pys,
+                  const int32_t* ss, float* o3, float* d3, float* lens2) {
+  if (!cam || n < 0 || cam->width <= 0 || cam->height <= 0 || cam->width > 65536 || cam->height > 65536) return DMT_ERR_INVALID;
+  if (n && (!pxs || !pys || !ss || !o3 || !d3 || !lens2)) return DMT_ERR_INVALID;
+  if (!std::isfinite(lens_radius) || lens_radius < 0.f) return DMT_ERR_INVALID;
+  if (lens_radius > 0.f && !(std::isfinite(focus_distance) && focus_distance > 0.f)) return DMT_ERR_INVALID;
+  CameraXf const xf = hostCameraXf(*cam);
+  SamplerParams const sp = computeSamplerParams(cam->width, cam->height);
+  int64_t const stride = int64_t(sp.scale0) * sp.scale1;
+  for (int i = 0; i < n; ++i) {
+    if (pxs[i] < 0 || pys[i] < 0 || pxs[i] >= cam->width || pys[i] >= cam->height || ss[i] < 0 ||
+        (int64_t(ss[i]) + 1) * stride > 0x7FFFFFFFll)
+      return DMT_ERR_INVALID;  // outside the frame, or the sample overflows the 32-bit Halton index
+  }
+  for (int i = 0; i < n; ++i) {
+    int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * int32_t(stride);
+    LensU const u = lens_values(uint32_t(h));
+    lens2[2 * size_t(i)] = u.x, lens2[2 * size_t(i) + 1] = u.y;
+    f2 const r = pixel2d(sp, h);
+    float const fx = ((r.x - 0.5f) + 0.5f) + float(pxs[i]);  // as camera_ray_jittered
+    float const fy = ((r.y - 0.5f) + 0.5f) + float(pys[i]);
+    hostCameraRay(xf, fx, fy, lens_radius, focus_distance, u, o3 + 3 * size_t(i), d3 + 3 * size_t(i));
+  }
+  return DMT_OK;
+}
+
+int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
+#pragma clang fp contract(off)
+  if (!ctx || !distance || !std::isfinite(fx) || !std::isfinite(fy)) return DMT_ERR_INVALID;
+  if (!(ctx->haveTris && ctx->haveCamera)) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: upload triangles and set the camera first");
+  float o[3], d[3];
+  hostCameraRay(ctx->xf, fx, fy, 0.f, 1.f, LensU{0.f, 0.f}, o, d);
+  int32_t tri = -1;
+  float t = 0.f;
+  if (int const rc = dmt_test_closest_hit(ctx, 1, o, d, &tri, &t)) return rc;  // the context's accel mode; synchronous
+  if (tri < 0) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: the ray leaves the scene");
+  float const* const m = ctx->xf.rfc;  // column 2 = the viewing direction
+  *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
   return DMT_OK;
 }
 

@@ -23,7 +23,7 @@ __global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t 
   PathState st{};
   if (i < n) {
     ColdArgs const c = load_cold_args(k);
-    path_begin(st, c.cam, c.sp, pxs[i], pys[i], halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i]));
+    path_begin(st, c.cam, c.sp, pxs[i], pys[i], halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i]), kargs(k)->lensR, kargs(k)->lensD);
   }
   auto store = [&](f3 L, uint32_t) { L3[3 * i] = L.x, L3[3 * i + 1] = L.y, L3[3 * i + 2] = L.z; };
   uint32_t const gtid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,7 +78,7 @@ __global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float*
   PathState st{};
   {
     ColdArgs const c = load_cold_args(k);
-    path_begin(st, c.cam, c.sp, px, py, halton_pixel_base(c.sp, px, py), uint32_t(smp));
+    path_begin(st, c.cam, c.sp, px, py, halton_pixel_base(c.sp, px, py), uint32_t(smp), kargs(k)->lensR, kargs(k)->lensD);
   }
   int n = 0;
   for (;;) {
@@ -153,12 +153,18 @@ __global__ void k_test_sampler(SamplerParams sp, int n, int32_t const* pxs, int3
   for (int d = 0; d < ndims; ++d) dims[size_t(i) * ndims + d] = r.get1D();
 }
 
-__global__ void k_test_camera(CameraXf cam, SamplerParams sp, int n, int32_t const* pxs,
-                              int32_t const* pys, int32_t const* ss, float* o3, float* d3) {
+// the rays the render kernels trace (lens rays for lensR > 0), or with lens2 the sample's lens values alone
+__global__ void k_test_camera(CameraXf cam, SamplerParams sp, float lensR, float lensD, int n, int32_t const* pxs,
+                              int32_t const* pys, int32_t const* ss, float* o3, float* d3, float* lens2) {
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= n) return;
   int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * (sp.scale0 * sp.scale1);
-  Ray const r = camera_ray(cam, sp, pxs[i], pys[i], h);
+  if (lens2) {
+    LensU const u = lens_values(uint32_t(h));
+    lens2[2 * i] = u.x, lens2[2 * i + 1] = u.y;
+    return;
+  }
+  Ray const r = camera_ray_any(cam, sp, pxs[i], pys[i], h, lensR, lensD);
   o3[3 * i] = r.o.x, o3[3 * i + 1] = r.o.y, o3[3 * i + 2] = r.o.z;
   d3[3 * i] = r.d.x, d3[3 * i + 1] = r.d.y, d3[3 * i + 2] = r.d.z;
 }
@@ -373,7 +379,8 @@ int dmt_test_sampler_table(dmt_ctx* ctx, int width, int height, uint32_t s0, uin
   ProbeOut<float4> dv(p, out_vals, 2);
   ProbeOut<float2> dj(p, out_jitter, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_sampler_table, dim3(p.blocks(256)), dim3(256), 0, ctx->stream, sp, s0, n, pw, ph, dv.get(), dj.get());
+  hipLaunchKernelGGL(k_sampler_table, dim3(p.blocks(256)), dim3(256), 0, ctx->stream, sp, s0, n, pw, ph, dv.get(), dj.get(),
+                     static_cast<float2*>(nullptr));  // the lens-free table
   return finishProbe(ctx, p);
 }
 
@@ -415,8 +422,21 @@ int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t*
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dO(p, o3, 3), dD(p, d3, 3);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, n, dpx.get(), dpy.get(), dss.get(),
-                     dO.get(), dD.get());
+  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, ctx->lensR, ctx->lensD, n, dpx.get(),
+                     dpy.get(), dss.get(), dO.get(), dD.get(), static_cast<float*>(nullptr));
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_lens_values(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* lens2) {
+  if (!ctx || n < 0 || !pxs || !pys || !ss || !lens2) return DMT_ERR_INVALID;
+  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_lens_values: set the camera first");
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
+  ProbeOut<float> dL(p, lens2, 2);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, ctx->lensR, ctx->lensD, n, dpx.get(),
+                     dpy.get(), dss.get(), static_cast<float*>(nullptr), static_cast<float*>(nullptr), dL.get());
   return finishProbe(ctx, p);
 }
 

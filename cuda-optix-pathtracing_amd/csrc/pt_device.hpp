@@ -16,6 +16,7 @@
 #include "tri_records.hpp"
 
 #define DMT_DEV __device__ __forceinline__
+#define DMT_HD __host__ __device__ __forceinline__  // also the host's (the host-only twins of include/dmt_hip.h)
 
 namespace dmt {
 
@@ -340,7 +341,7 @@ DMT_DEV float sample_dim(uint32_t index) {  // owenScrambledRadicalInverse, rng.
   return fminf(result, 0.99999994f);
 }
 template <uint32_t BASE>
-DMT_DEV float radical_inverse(uint32_t index) {  // rng.cu:70-94
+DMT_HD float radical_inverse(uint32_t index) {  // rng.cu:70-94
   float const invBase = 1.0f / float(BASE);
   float result = 0.0f;
   float invBasePow = invBase;
@@ -355,7 +356,7 @@ DMT_DEV float radical_inverse(uint32_t index) {  // rng.cu:70-94
 }
 
 // Halton index of sample 0 of a pixel (rng.cu:216-228); add s * stride for sample s
-DMT_DEV int32_t halton_pixel_base(SamplerParams const& p, int px, int py) {
+DMT_HD int32_t halton_pixel_base(SamplerParams const& p, int px, int py) {
   int const stride = p.scale0 * p.scale1;
   int const pmx = px % 128, pmy = py % 128;
   // inverseRadicalInverse(pm, base, nDigits), rng.cu:48-59
@@ -427,11 +428,16 @@ struct Sampler {
 };
 // getPixel2D, rng.cu:254-262.  Base 2: every partial sum of distinct powers of two with <= 24
 // significant bits is exact, so the fmaf chain equals bit reversal.
-DMT_DEV f2 pixel2d(SamplerParams const& p, int32_t haltonIndex) {
+DMT_HD f2 pixel2d(SamplerParams const& p, int32_t haltonIndex) {
   uint32_t const a = uint32_t(haltonIndex >> p.exp0);
-  float const rx = fminf(float(__brev(a)) * 2.3283064365386963e-10f, 0.99999994f);
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t const rev = __brev(a);
+#else
+  uint32_t const rev = __builtin_bitreverse32(a);
+#endif
+  float const rx = fminf(float(rev) * 2.3283064365386963e-10f, 0.99999994f);
   float const ry = radical_inverse<3>(uint32_t(haltonIndex / p.scale1));
-  return mk2(rx, ry);
+  return f2{rx, ry};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -469,6 +475,80 @@ DMT_DEV Ray camera_ray_jittered(CameraXf const& cam, int px, int py, f2 r) {
 DMT_DEV Ray camera_ray(CameraXf const& cam, SamplerParams const& sp, int px, int py,
                        int32_t haltonIndex) {
   return camera_ray_jittered(cam, px, py, pixel2d(sp, haltonIndex));
+}
+
+// ---- thin lens (dmt_set_lens) -------------------------------------------------------------
+// Beyond the reference (its generateRay carries "TODO add lens?").  A lens of radius R > 0 focused at depth D along the
+// viewing direction: the sample's ray starts at a point l of the lens disk and passes through the point pf where the
+// pinhole ray of the same film position meets the plane of focus.  R == 0 is the pinhole and never reaches this code.
+//
+// The lens point comes from Halton dimensions 10 and 11 of the sample's own index (bases 31 and 37), the reference's
+// scrambled radical inverse as its loop is written -- no permutation tables: two dimensions more would cost 2.4 KB of
+// constant cache for digits a lens render draws once per sample.  The path's dimensions 2..9 do not move.
+// One body for the device and the host (dmt_lens_rays): integer arithmetic, an explicit fmaf and one plain product per digit.
+template <uint32_t BASE>
+__host__ __device__ inline float owen_radical_inverse_plain(uint32_t seed, uint32_t index) {  // rng.cu:96-135
+  float const invBase = 1.0f / float(BASE);  // a constant: correctly rounded at compile time
+  float result = 0.0f, invBasePow = invBase;
+  uint32_t revHash = 0;
+  while (index > 0) {
+    uint32_t const next = index / BASE;
+    uint32_t const digit = index - next * BASE;
+    uint32_t const sum = digit + mix_bits32_c(seed ^ revHash);  // 32-bit wraparound, as the reference
+    result = __builtin_fmaf(float(sum % BASE), invBasePow, result);
+    revHash = revHash * BASE + digit;
+    invBasePow *= invBase;
+    index = next;
+  }
+  return __builtin_fminf(result, 0.99999994f);
+}
+struct LensU {
+  float x, y;
+};
+__host__ __device__ inline LensU lens_values(uint32_t haltonIndex) {  // (u10, u11)
+  return LensU{owen_radical_inverse_plain<31>(owen_seed(10), haltonIndex), owen_radical_inverse_plain<37>(owen_seed(11), haltonIndex)};
+}
+// The arithmetic of a lens ray between the disk map and the normalisation, fp32 without contraction in one order of
+// operations for the device and the host; include/dmt_hip.h (dmt_lens_rays) states it.  cfr / rfc: CameraXf's matrices
+// (both affine: w == 1).  (lx, ly) = R * the disk point.  o3 = the origin, d3 = the direction before it is normalised.
+__host__ __device__ inline void lens_ray_parts(float const* cfr, float const* rfc, float fx, float fy, float D, float lx, float ly,
+                                               float* o3, float* d3) {
+#pragma clang fp contract(off)
+  float const cx = ((cfr[0] * fx + cfr[4] * fy) + cfr[8] * 0.0f) + cfr[12];  // pCamera = cameraFromRaster * (fx, fy, 0), as xf_point
+  float const cy = ((cfr[1] * fx + cfr[5] * fy) + cfr[9] * 0.0f) + cfr[13];
+  float const cz = ((cfr[2] * fx + cfr[6] * fy) + cfr[10] * 0.0f) + cfr[14];
+#if defined(__HIP_DEVICE_COMPILE__)
+  // D / cz: v_rcp_f32 and one residual step, which rounds as the host's division except in rare half-way cases (the
+  // library's device `/` is the 2.5-ulp one, see the Makefile)
+  float const rc = __builtin_amdgcn_rcpf(cz);
+  float const q = D * rc;
+  float const ft = __builtin_fmaf(__builtin_fmaf(-q, cz, D), rc, q);
+#else
+  float const ft = D / cz;
+#endif
+  float const vx = cx * ft - lx, vy = cy * ft - ly, vz = D;  // pf - l
+  for (int i = 0; i < 3; ++i) {
+    o3[i] = ((rfc[i] * lx + rfc[4 + i] * ly) + rfc[8 + i] * 0.0f) + rfc[12 + i];
+    d3[i] = (rfc[i] * vx + rfc[4 + i] * vy) + rfc[8 + i] * vz;
+  }
+}
+DMT_DEV f2 sample_uniform_disk(f2 u);  // below
+// the lens ray of pixel (px, py) for the film jitter r = pixel2d and the lens values u = lens_values of the same Halton index
+DMT_DEV Ray camera_ray_lens(CameraXf const& cam, int px, int py, f2 r, float lensR, float focusD, LensU u) {
+  float const fx = ((r.x - 0.5f) + 0.5f) + float(px);  // as camera_ray_jittered
+  float const fy = ((r.y - 0.5f) + 0.5f) + float(py);
+  f2 const l = sample_uniform_disk(mk2(u.x, u.y));
+  float o[3], d[3];
+  lens_ray_parts(cam.cfr, cam.rfc, fx, fy, focusD, lensR * l.x, lensR * l.y, o, d);
+  Ray ray;
+  ray.o = mk3(o[0], o[1], o[2]);
+  ray.d = normalize(mk3(d[0], d[1], d[2]));
+  return ray;
+}
+// what the render kernels trace: the lens ray for lensR > 0 (wave-uniform), else the pinhole ray
+DMT_DEV Ray camera_ray_any(CameraXf const& cam, SamplerParams const& sp, int px, int py, int32_t haltonIndex, float lensR, float focusD) {
+  if (lensR > 0.f) return camera_ray_lens(cam, px, py, pixel2d(sp, haltonIndex), lensR, focusD, lens_values(uint32_t(haltonIndex)));
+  return camera_ray(cam, sp, px, py, haltonIndex);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -117,6 +117,9 @@ const void* dmt_host_scene_bsdfs(const dmt_host_scene* h) { return h->s.bsdfs.da
 const void* dmt_host_scene_lights(const dmt_host_scene* h) { return h->s.lights.data(); }
 const void* dmt_host_scene_infinite_lights(const dmt_host_scene* h) { return h->s.infiniteLights.data(); }
 dmt_camera* dmt_host_scene_camera(dmt_host_scene* h) { return &h->s.camera; }
+void dmt_host_scene_lens(const dmt_host_scene* h, float* lens_radius, float* focus_distance) {
+  *lens_radius = h->s.lensRadius, *focus_distance = h->s.focusDistance;
+}
 void dmt_host_scene_set_resolution(dmt_host_scene* h, int width, int height) {
   h->s.camera.width = width, h->s.camera.height = height;
 }

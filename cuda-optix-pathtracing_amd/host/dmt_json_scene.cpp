@@ -199,7 +199,9 @@ struct State {
 };
 
 void parseCamera(Value const& cam, JsonScene& out, Vec3& dir, Vec3& pos) {
-  if (!cam.isObject() || cam.size() > 4) fail("'camera' should be an object with at most 4 members");  // :741
+  // beyond the reference's parser: an optional thin lens, 'lensRadius' and 'focusDistance' in scene units (absent: pinhole)
+  size_t const lensKeys = size_t(cam.isObject() && cam.contains("lensRadius")) + size_t(cam.isObject() && cam.contains("focusDistance"));
+  if (!cam.isObject() || cam.size() > 4 + lensKeys) fail("'camera' should be an object with at most 4 members and the lens keys");  // :741
   if (!cam.contains("focalLength") || !cam.contains("sensorSize") || !cam.contains("direction"))
     fail("'camera' needs 'focalLength', 'sensorSize' and 'direction'");
   if (!cam.at("sensorSize").isNumber() || float(cam.at("sensorSize").number) <= 0.f) fail("camera 'sensorSize' should be a positive number");
@@ -209,6 +211,15 @@ void parseCamera(Value const& cam, JsonScene& out, Vec3& dir, Vec3& pos) {
   out.scene.camera.sensor_size = float(cam.at("sensorSize").number);
   pos = Vec3{0, 0, 0};
   if (cam.contains("position") && !extractVec3(cam.at("position"), pos)) fail("camera 'position' should be an array of three numbers");
+  if (cam.contains("lensRadius")) {
+    if (!cam.at("lensRadius").isNumber() || !(float(cam.at("lensRadius").number) >= 0.f)) fail("camera 'lensRadius' should be a number >= 0");
+    out.scene.lensRadius = float(cam.at("lensRadius").number);
+  }
+  if (cam.contains("focusDistance")) {
+    if (!cam.at("focusDistance").isNumber() || !(float(cam.at("focusDistance").number) > 0.f)) fail("camera 'focusDistance' should be a positive number");
+    out.scene.focusDistance = float(cam.at("focusDistance").number);
+  }
+  if (out.scene.lensRadius > 0.f && !cam.contains("focusDistance")) fail("camera 'lensRadius' > 0 needs a 'focusDistance'");
   if (cam.contains("max-depth")) {
     if (!cam.at("max-depth").isInteger() || int(cam.at("max-depth").number) <= 0) fail("camera 'max-depth' should be a positive integer");
     out.maxDepth = int(cam.at("max-depth").number);

@@ -258,6 +258,11 @@ bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error) 
         if (type != "perspective") fail("Camera \"" + type + "\": only \"perspective\" is supported");
         Params const ps = params();
         if (Param const* p = find(ps, "float", "fov")) fov = p->nums.empty() ? 90 : p->nums[0];
+        // pbrt-v4's thin lens: "lensradius" (default 0, the pinhole) and "focaldistance" (default 1e6), in scene units
+        out.scene.lensRadius = 0.f, out.scene.focusDistance = 1e6f;
+        if (Param const* p = find(ps, "float", "lensradius")) out.scene.lensRadius = p->nums.empty() ? 0.f : float(p->nums[0]);
+        if (Param const* p = find(ps, "float", "focaldistance")) out.scene.focusDistance = p->nums.empty() ? 1e6f : float(p->nums[0]);
+        if (!(out.scene.lensRadius >= 0.f) || !(out.scene.focusDistance > 0.f)) fail("Camera: lensradius must be >= 0 and focaldistance > 0");
         haveCamera = true;
         gs.ctm = identity();  // pbrt: the CTM at Camera defines the camera; world space restarts at WorldBegin
       } else if (d == "WorldBegin") {

@@ -61,6 +61,8 @@ struct Scene {
   std::vector<uint32_t> matId;
   std::vector<Packed32> bsdfs, lights, infiniteLights;
   dmt_camera camera{};
+  // optional thin lens (dmt_set_lens), reported beside the camera record: radius 0 = pinhole; both in scene units
+  float lensRadius = 0.f, focusDistance = 1.f;
   // optional env-map light (A18; the JSON front-end's "envlight"): RGB floats, envHeight x envWidth x 3
   std::vector<float> envRgb;
   int envWidth = 0, envHeight = 0;

@@ -49,6 +49,8 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   bool denoise = false;       // --denoise: also write output-<spp>_denoised.png (dmt_render_aovs + dmt_denoise)
   int aovSpp = 4;             // --aov-spp <N>: camera samples per pixel of the feature buffers
   bool aovSppSet = false;
+  bool lensRadiusSet = false, focusDistanceSet = false, focusPixelSet = false;  // --lens-radius R, --focus-distance D, --focus-pixel X Y
+  float lensRadius = 0.f, focusDistance = 1.f, focusX = 0.f, focusY = 0.f;
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
 
@@ -85,6 +87,10 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (aovSppSet && !denoise) return "--aov-spp needs --denoise";
     if (bvhBuildSet && bvhBuildArg != "host" && bvhBuildArg != "gpu") return "invalid --bvh-build: expected host or gpu, got '" + bvhBuildArg + "'";
     if (bvhBuildSet && !bvh) return "--bvh-build needs --bvh";
+    if (lensRadiusSet && !(std::isfinite(lensRadius) && lensRadius >= 0.f)) return "invalid --lens-radius: expected a finite radius >= 0";
+    if (focusDistanceSet && !(std::isfinite(focusDistance) && focusDistance > 0.f)) return "invalid --focus-distance: expected a finite distance > 0";
+    if (focusDistanceSet && focusPixelSet) return "--focus-distance and --focus-pixel exclude each other";
+    if (focusPixelSet && !(focusX >= 0.f && focusX < float(width) && focusY >= 0.f && focusY < float(height))) return "invalid --focus-pixel: outside the frame";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
   }
@@ -122,7 +128,11 @@ void printHelp() {
       "  --min-spp <N>     -- Samples every pixel receives before --adaptive may stop it (default 0)\n"
       "  --denoise         -- Also write output-<spp>_denoised.png: the film through an a-trous filter guided by its variance\n"
       "                       and first-hit albedo / normal / position buffers (every other output stays as without it)\n"
-      "  --aov-spp <N>     -- Camera samples per pixel of those buffers (default 4)");
+      "  --aov-spp <N>     -- Camera samples per pixel of those buffers (default 4)\n"
+      "  --lens-radius <R> -- Thin lens of radius R in scene units: depth of field (0, the default, is the pinhole; a scene\n"
+      "                       file's own lens applies unless given here)\n"
+      "  --focus-distance <D> -- Depth along the viewing direction, in scene units, that the lens renders sharp\n"
+      "  --focus-pixel <X> <Y> -- Autofocus: focus on what the centre of pixel (X, Y) shows, and print the distance chosen");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -144,6 +154,9 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--min-spp" && more) c.minSpp = std::atoi(argv[++i]), c.minSppSet = true;
     else if (a == "--denoise") c.denoise = true;
     else if (a == "--aov-spp" && more) c.aovSpp = std::atoi(argv[++i]), c.aovSppSet = true;
+    else if (a == "--lens-radius" && more) c.lensRadius = std::strtof(argv[++i], nullptr), c.lensRadiusSet = true;
+    else if (a == "--focus-distance" && more) c.focusDistance = std::strtof(argv[++i], nullptr), c.focusDistanceSet = true;
+    else if (a == "--focus-pixel" && i + 2 < argc) c.focusX = std::strtof(argv[++i], nullptr), c.focusY = std::strtof(argv[++i], nullptr), c.focusPixelSet = true;
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -229,6 +242,8 @@ int main(int argc, char** argv) {
   dmt_host::Scene scene = cfg.scenePath.empty() ? dmt_host::cornellBox() : std::move(json.scene);
   scene.camera.width = cfg.width, scene.camera.height = cfg.height, scene.camera.spp = cfg.kspp;
   if (cfg.textureFilter) scene.camera.spp = cfg.spp;  // the filter's footprint scale follows the frame's samples per pixel
+  if (cfg.lensRadiusSet) scene.lensRadius = cfg.lensRadius;
+  if (cfg.focusDistanceSet) scene.focusDistance = cfg.focusDistance;
   double const loadMs = msSince(tLoad);
 
   // one context per GPU; DMT_CLI_SHARE_DEVICE=1 (tests on a one-GPU box) maps all ranks onto --gpu-ordinal
@@ -248,6 +263,14 @@ int main(int argc, char** argv) {
     if (cfg.lightTree && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
     if (cfg.lightTreeRef && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
     if (cfg.textureFilter && dmt_set_texture_filter(ctx, DMT_TEXFILTER_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_texture_filter");
+  }
+  if (cfg.focusPixelSet) {  // autofocus on the first context (every context holds the whole scene), then the lens of all
+    float d = 0.f;
+    if (dmt_focus_distance_at(C.v[0], std::floor(cfg.focusX) + 0.5f, std::floor(cfg.focusY) + 0.5f, &d) != DMT_OK)
+      return fail(C.v[0], "dmt_focus_distance_at");
+    std::printf("Autofocus: pixel (%d, %d) -> focus distance %.6g\n", int(cfg.focusX), int(cfg.focusY), double(d));
+    for (dmt_ctx* ctx : C.v)
+      if (dmt_set_lens(ctx, scene.lensRadius, d) != DMT_OK) return fail(ctx, "dmt_set_lens");
   }
   double const uploadMs = msSince(tUpload);
 

@@ -59,6 +59,9 @@ class HostScene:
         self.inf_lights = _copy(L.dmt_host_scene_infinite_lights(h), np.uint8,
                                 32 * L.dmt_host_scene_infinite_light_count(h)).reshape(-1, 32)
         self.camera = _copy(L.dmt_host_scene_camera(h), np.uint8, 44)
+        lr, fd = C.c_float(), C.c_float()
+        L.dmt_host_scene_lens(h, C.byref(lr), C.byref(fd))
+        self.lens = (lr.value, fd.value)  # thin lens beside the camera record: (radius, focus distance); radius 0 = pinhole
         ew, eh = C.c_int(), C.c_int()
         env = L.dmt_host_scene_env_rgb(h, C.byref(ew), C.byref(eh))
         self.env_rgb = _copy(env, np.float32, 3 * ew.value * eh.value).reshape(eh.value, ew.value, 3) if env else None
@@ -112,7 +115,8 @@ def read_fbx(path):
 
 
 def load_json(path):
-    """The reference's JSON scene description (core-parser.cpp) -> HostScene (+ .max_depth, .spp, .env_rgb).
+    """The reference's JSON scene description (core-parser.cpp) -> HostScene (+ .max_depth, .spp, .env_rgb; .lens from the
+    optional camera keys lensRadius / focusDistance).
     Raises ValueError with the loader's message when the file is rejected."""
     L = load_host_library()
     md, spp = C.c_int(), C.c_int()
@@ -126,7 +130,8 @@ def load_json(path):
 
 
 def load_pbrt(path):
-    """PBRT-v4 subset (scenes/cornell-box.pbrt's directives) -> HostScene (+ .max_depth, .spp, .area_tri, .area_le)."""
+    """PBRT-v4 subset (scenes/cornell-box.pbrt's directives) -> HostScene (+ .max_depth, .spp, .area_tri, .area_le; .lens from
+    the camera's lensradius / focaldistance)."""
     L = load_host_library()
     md, spp = C.c_int(), C.c_int()
     err = C.create_string_buffer(1024)
@@ -189,6 +194,7 @@ class ArrayScene:
         self.camera = np.ascontiguousarray(camera, np.uint8).reshape(44).copy()
         self.env_rgb = None if env_rgb is None else np.ascontiguousarray(env_rgb, np.float32)
         self.env_quat, self.env_scale = np.array([0, 0, 0, 1], np.float32), 1.0
+        self.lens = None  # (lens_radius, focus_distance) to have upload_scene set the lens; None leaves the context's
 
     tri_count = HostScene.tri_count
     width = HostScene.width

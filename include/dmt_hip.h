@@ -87,6 +87,38 @@ int dmt_upload_lights(dmt_ctx* ctx, const void* lights32, uint32_t count, const 
 /* (re)computes camera transforms and sampler parameters; (re)allocates and zeroes the film when
  * the resolution changes */
 int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam);
+
+/* ---- thin lens: depth of field (opt-in, beyond the reference) ------------------------ */
+/* Context state, not part of dmt_camera: a lens of radius lens_radius >= 0 focused at focus_distance > 0, both in scene
+ * units; the distance is measured along the viewing direction (the depth dmt_camera_project reports).  Radius 0, the
+ * default, is the pinhole: every film is then bit-identical to one rendered without this call, and the distance is ignored.
+ * The lens survives dmt_set_camera and scene uploads.  DMT_ERR_INVALID for a radius that is negative or not finite, and
+ * with a radius > 0 for a distance that is not finite or not positive.
+ *
+ * Sample s of pixel (px, py), Halton index h, in fp32 without contraction:
+ *   pCamera = cameraFromRaster (fx, fy, 0)               (fx, fy) the sample's film position, as for the pinhole
+ *   ft = D / pCamera.z;  pf = (pCamera.x ft, pCamera.y ft, D)            the point in focus
+ *   l  = R sample_uniform_disk(u10, u11)
+ *   o  = renderFromCamera point(l.x, l.y, 0);  d = normalize(renderFromCamera vector(pf.x - l.x, pf.y - l.y, pf.z))
+ * with (u10, u11) = Halton dimensions 10 and 11 of h: Owen-scrambled radical inverses in bases 31 and 37.  The path's own
+ * dimensions 2..9 do not move: a lens changes which ray a sample traces and nothing else about the sample.  Every render
+ * path traces these rays (dmt_render, its sampler table, the wavefront form, dmt_render_adaptive), and so does the
+ * feature pass dmt_render_aovs, whose planes therefore blur where the image blurs.
+ * Two things keep the pinhole: dmt_denoise_temporal's motion vectors, the projection of a surface point under both
+ * frames' cameras, which is the projection through the lens centre and stays correct (a change of lens does not reset
+ * the history); and the ray differentials of dmt_texture_footprint and of the first-hit texture filter. */
+int dmt_set_lens(dmt_ctx* ctx, float lens_radius, float focus_distance);
+int dmt_lens_info(dmt_ctx* ctx, float* lens_radius, float* focus_distance);
+/* host only (no GPU): the serial twin of the device's camera rays.  Rays (o3, d3: n x 3) of samples ss of pixels
+ * (pxs, pys) of the camera under the given lens (radius 0: the pinhole rays), and lens2 (n x 2) = (u10, u11).  The lens
+ * values are the device's bit for bit; the rays use the host's division, square root, sine and cosine.
+ * DMT_ERR_INVALID for a pixel outside the frame, a negative sample, or lens arguments dmt_set_lens would refuse. */
+int dmt_lens_rays(const dmt_camera* cam, float lens_radius, float focus_distance, int n, const int32_t* pxs, const int32_t* pys,
+                  const int32_t* ss, float* o3, float* d3, float* lens2);
+/* autofocus: traces the pinhole ray through the continuous film coordinates (fx, fy) (dmt_camera_project's) under the
+ * current accel mode; *distance = the hit's depth along the viewing direction, what dmt_set_lens takes as focus_distance.
+ * DMT_ERR_STATE when the ray leaves the scene.  Synchronous. */
+int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance);
 /* depth cap of the bounce loop; the reference hard-codes 32 (megakernel.cu:154) */
 int dmt_set_limits(dmt_ctx* ctx, int max_depth);
 int dmt_set_accel(dmt_ctx* ctx, int mode);
@@ -481,8 +513,11 @@ int dmt_test_sampler(dmt_ctx* ctx, int width, int height, int n, const int32_t* 
 /* fills the sampler table of samples [s0, s0 + n) of a width x height frame as a dmt_render call would and downloads
  * it: out_vals [n][ph][pw][8], out_jitter [n][ph][pw][2] with pw = min(width,128), ph = min(height,128) */
 int dmt_test_sampler_table(dmt_ctx* ctx, int width, int height, uint32_t s0, uint32_t n, float* out_vals, float* out_jitter);
+/* the camera rays the render kernels trace: lens rays when a lens is set (dmt_set_lens) */
 int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys,
                          const int32_t* ss, float* o3, float* d3);
+/* the lens values (u10, u11) of the samples, lens2 (n x 2), as the device computes them */
+int dmt_test_lens_values(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* lens2);
 /* dmt_camera_project on the device, under the camera of dmt_set_camera */
 int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, float* depth);
 int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* wo3,
