@@ -35,6 +35,9 @@ from .binding import (  # noqa: F401
     temporal_defaults,
     camera_project,
     lens_rays,
+    shutter_times,
+    motion_positions,
+    motion_bvh_validate,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = [
     "dmt_denoise_temporal", "dmt_temporal_reset", "dmt_temporal_info", "dmt_temporal_download",
     "dmt_set_sampler_table", "dmt_sampler_table_plan", "dmt_test_sampler_table",
     "dmt_set_lens", "dmt_lens_info", "dmt_lens_rays", "dmt_focus_distance_at", "dmt_test_lens_values",
+    "dmt_set_motion", "dmt_clear_motion", "dmt_set_shutter", "dmt_motion_info", "dmt_shutter_times", "dmt_motion_positions",
+    "dmt_motion_bvh_validate", "dmt_test_shutter_times", "dmt_test_closest_hit_at",
 ]
 
 # dmt_set_sampler_table modes (include/dmt_hip.h)
@@ -175,6 +177,46 @@ def lens_rays(camera44, lens_radius, focus_distance, pxs, pys, ss):
     if rc != 0:
         raise DmtError(f"dmt_lens_rays failed ({rc})")
     return o, d, u
+
+
+def shutter_times(width, height, open, close, pxs, pys, ss):
+    """Host only (dmt_shutter_times): the times [n] of samples ss of pixels (pxs, pys) of a width x height frame under the
+    shutter [open, close], the device's bit for bit."""
+    lib = load_library()
+    pxs, pys, ss = _i32(pxs), _i32(pys), _i32(ss)
+    n = pxs.shape[0]
+    assert pys.shape[0] == n and ss.shape[0] == n
+    t = np.zeros(n, np.float32)
+    rc = lib.dmt_shutter_times(int(width), int(height), C.c_float(open), C.c_float(close), int(n), _p(pxs), _p(pys), _p(ss), _p(t))
+    if rc != 0:
+        raise DmtError(f"dmt_shutter_times failed ({rc})")
+    return t
+
+
+def motion_positions(xs0, ys0, zs0, xs1, ys1, zs1, t):
+    """Host only (dmt_motion_positions): the vertices at time t between key 0 and key 1, fmaf(t, p1 - p0, p0) in fp32, the
+    device's bit for bit.  Layout as upload_triangles; returns (xs, ys, zs)."""
+    lib = load_library()
+    a = [_f32(v).reshape(-1) for v in (xs0, ys0, zs0, xs1, ys1, zs1)]
+    n = a[0].size // 4
+    assert all(v.size == 4 * n for v in a)
+    out = [np.zeros(4 * n, np.float32) for _ in range(3)]
+    rc = lib.dmt_motion_positions(*[_p(v) for v in a], C.c_size_t(n), C.c_float(t), *[_p(v) for v in out])
+    if rc != 0:
+        raise DmtError(f"dmt_motion_positions failed ({rc})")
+    return tuple(out)
+
+
+def motion_bvh_validate(xs0, ys0, zs0, xs1, ys1, zs1):
+    """Host only (dmt_motion_bvh_validate): builds the motion tree of the two keys and checks it against both; returns
+    dict(ok, node_count, pair_count, depth)."""
+    lib = load_library()
+    a = [_f32(v).reshape(-1) for v in (xs0, ys0, zs0, xs1, ys1, zs1)]
+    n = a[0].size // 4
+    assert all(v.size == 4 * n for v in a)
+    nc, pc, d = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.dmt_motion_bvh_validate(*[_p(v) for v in a], C.c_size_t(n), C.byref(nc), C.byref(pc), C.byref(d))
+    return {"ok": rc == 0, "node_count": nc.value, "pair_count": pc.value, "depth": d.value}
 
 
 # dmt_set_texture_filter modes (include/dmt_hip.h)
@@ -473,6 +515,31 @@ class Renderer:
         r, d = C.c_float(), C.c_float()
         self._check(self._lib.dmt_lens_info(self._ctx, C.byref(r), C.byref(d)), "dmt_lens_info")
         return r.value, d.value
+
+    def set_motion(self, xs1, ys1, zs1):
+        """Key 1 (dmt_set_motion): a second position set for the uploaded triangles, layout as upload_triangles.  Samples
+        then see the scene at their own time within the shutter.  Dropped by upload_triangles and update_vertices*."""
+        xs1, ys1, zs1 = _f32(xs1), _f32(ys1), _f32(zs1)
+        n = xs1.size // 4
+        assert xs1.size == 4 * n and ys1.size == 4 * n and zs1.size == 4 * n
+        self._check(self._lib.dmt_set_motion(self._ctx, _p(xs1), _p(ys1), _p(zs1), C.c_size_t(n)), "dmt_set_motion")
+
+    def clear_motion(self):
+        """Drops key 1 (dmt_clear_motion): every film is again what it was before set_motion."""
+        self._check(self._lib.dmt_clear_motion(self._ctx), "dmt_clear_motion")
+
+    def set_shutter(self, open=0.0, close=1.0):
+        """The shutter interval (dmt_set_shutter), 0 <= open <= close <= 1; survives set_camera and scene uploads."""
+        self._check(self._lib.dmt_set_shutter(self._ctx, C.c_float(open), C.c_float(close)), "dmt_set_shutter")
+
+    def motion_info(self):
+        """dmt_motion_info as a dict: keys (0, 1 or 2), open, close, tree_nodes, tree_pairs, tree_build_ms."""
+        k, o, c = C.c_int(), C.c_float(), C.c_float()
+        nn, npairs, ms = C.c_uint32(), C.c_uint32(), C.c_double()
+        self._check(self._lib.dmt_motion_info(self._ctx, C.byref(k), C.byref(o), C.byref(c), C.byref(nn), C.byref(npairs), C.byref(ms)),
+                    "dmt_motion_info")
+        return {"keys": k.value, "open": o.value, "close": c.value, "tree_nodes": nn.value, "tree_pairs": npairs.value,
+                "tree_build_ms": ms.value}
 
     def focus_distance_at(self, fx, fy):
         """Autofocus (dmt_focus_distance_at): the depth along the viewing direction of what the pinhole ray through the
@@ -922,6 +989,25 @@ class Renderer:
         self._check(self._lib.dmt_test_trace_log(self._ctx, int(px), int(py), int(s), _p(rec), int(cap), C.byref(n),
                                                  _p(L)), "dmt_test_trace_log")
         return rec[:n.value], L
+
+    def test_shutter_times(self, pxs, pys, ss):
+        """dmt_test_shutter_times: the times [n] of the samples under the context's shutter, as the device computes them."""
+        pxs, pys, ss = _i32(pxs), _i32(pys), _i32(ss)
+        n = pxs.shape[0]
+        t = np.zeros(n, np.float32)
+        self._check(self._lib.dmt_test_shutter_times(self._ctx, n, _p(pxs), _p(pys), _p(ss), _p(t)), "dmt_test_shutter_times")
+        return t
+
+    def test_closest_hit_at(self, o, d, time):
+        """dmt_test_closest_hit_at: closest hit of ray i against the scene at time[i] under the current accel mode ->
+        (tri [n], t [n], uv [n, 2])."""
+        o, d = _f32(o, (-1, 3)), _f32(d, (-1, 3))
+        n = o.shape[0]
+        time = np.ascontiguousarray(np.broadcast_to(np.asarray(time, np.float32), (n,)))
+        idx, t, uv = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 2), np.float32)
+        self._check(self._lib.dmt_test_closest_hit_at(self._ctx, n, _p(o), _p(d), _p(time), _p(idx), _p(t), _p(uv)),
+                    "dmt_test_closest_hit_at")
+        return idx, t, uv
 
     def test_closest_hit(self, o, d):
         o, d = _f32(o, (-1, 3)), _f32(d, (-1, 3))

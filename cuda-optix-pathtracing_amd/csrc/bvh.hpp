@@ -57,6 +57,14 @@ struct TriPair {  // 80 B = five 16-byte loads
   uint32_t orig[2];  // ORIGINAL triangle indices (brute-force tie-break, shading)
 };
 static_assert(sizeof(TriPair) == 80, "pair size");
+// Motion blur (dmt_set_motion): D = B - A of a pair's nine float fields, A the key-0 pair and B the pair
+// packed from the key-1 positions, in the same interleaving.  A leaf of the motion tree loads both records and tests
+// fmaf(t, D, A).  Like the pair array it carries three guard records behind its end (buildBvhHost).
+struct TriPairDelta {  // 80 B = five 16-byte loads
+  float p0x[2], p0y[2], p0z[2], e0x[2], e0y[2], e0z[2], e1x[2], e1y[2], e1z[2];
+  uint32_t pad[2];
+};
+static_assert(sizeof(TriPairDelta) == 80, "pair delta size");
 
 // Inner node.  Child k (k < count) has the box  [origin + qlo_k * scale, origin + qhi_k * scale]  per axis, with
 // scale_axis = 2^(exp_axis - 127) and the q's the k-th BYTES of the six plane words.  Children 0 .. inner-1 are the inner
@@ -251,8 +259,16 @@ DMT_HD inline void encodeNode(Bvh4Node& nd, Box const* kid, int nk, int nInner) 
     }
 }
 
-// xs/ys/zs: the reference's SoA (4 floats per triangle: c0, c1, c2, pad)
-inline Result build(float const* xs, float const* ys, float const* zs, uint32_t n) {
+// xs/ys/zs: the reference's SoA (4 floats per triangle: c0, c1, c2, pad).
+// xs1/ys1/zs1 (all or none): a second key of the same triangles (motion blur).  Every triangle's box is then
+// the UNION of its boxes at both keys, padded as one box, and the padding scale is taken over both keys.  A vertex moves on
+// the segment between its keys, so the exact triangle at any t in [0, 1] lies inside the union box.  What the device tests
+// is fmaf(t, D, A) with D = fl(B - A): D is off by <= 2^-24 |B - A| <= 2^-23 m (m = the box's largest |coordinate|), the
+// fmaf rounds once more (2^-24 m), and the edge records add their own subtraction (2^-24 of the triangle's extent) and the
+// same two steps on extents: every tested vertex p0 + e is within ~6 * 2^-24 (extent + m) = 3.6e-7 (extent + m) of the exact
+// one.  padBox adds 1e-5 extent + 4e-6 m: ten times that, on top of the terms the static tree needs.
+inline Result build(float const* xs, float const* ys, float const* zs, uint32_t n, float const* xs1 = nullptr, float const* ys1 = nullptr,
+                    float const* zs1 = nullptr) {
   static_assert(kBvhMaxLeafTris == 2, "a leaf is one triangle pair");
   Result out;
   Builder b;
@@ -266,6 +282,7 @@ inline Result build(float const* xs, float const* ys, float const* zs, uint32_t 
   for (size_t k = 0; k < size_t(n) * 4; ++k) {
     if ((k & 3) == 3) continue;  // the SoA's pad lane
     sceneMaxAbs = std::max(sceneMaxAbs, std::max(std::fabs(xs[k]), std::max(std::fabs(ys[k]), std::fabs(zs[k]))));
+    if (xs1) sceneMaxAbs = std::max(sceneMaxAbs, std::max(std::fabs(xs1[k]), std::max(std::fabs(ys1[k]), std::fabs(zs1[k]))));
   }
   float const slabPad = lbvh::slabPadOf(sceneMaxAbs);
   for (uint32_t i = 0; i < n; ++i) {
@@ -274,6 +291,10 @@ inline Result build(float const* xs, float const* ys, float const* zs, uint32_t 
     for (int v = 0; v < 3; ++v) {
       float const p[3] = {xs[4 * size_t(i) + v], ys[4 * size_t(i) + v], zs[4 * size_t(i) + v]};
       bx.grow(p);
+      if (xs1) {
+        float const q[3] = {xs1[4 * size_t(i) + v], ys1[4 * size_t(i) + v], zs1[4 * size_t(i) + v]};
+        bx.grow(q);
+      }
     }
     lbvh::padBox(bx, slabPad);  // the padding terms live in lbvh.hpp: the device builder pads the same way
     b.triBox[i] = bx;

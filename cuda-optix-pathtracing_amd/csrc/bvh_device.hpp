@@ -24,6 +24,15 @@ struct BvhView {
   uint32_t overflowStride;            // total threads of the launch
 };
 
+// Motion blur (dmt_set_motion): what the motion rows read beside the scene.  In a motion launch BvhView's
+// nodes / pairs are the MOTION tree's (built over both keys' boxes) and its key-0 pairs; pairDelta lines up with those pairs.
+struct MotionView {
+  TriIsect const* __restrict__ dtris;          // [triCount] D = B - A of the TriIsect fields (matId unused): the brute-force pass
+  TriKey1 const* __restrict__ post1;           // [triCount] key-1 vertices: the post-hit record
+  TriPairDelta const* __restrict__ pairDelta;  // [pairs + 3 guards] D of the motion tree's pairs
+  float open, close;                           // the shutter
+};
+
 __shared__ uint32_t s_bvh_stack[kBvhLdsStack * kLdsThreads];
 
 // The stack pointer is all a lane keeps.  The overflow column (entries beyond the LDS part, rare) is addressed from the
@@ -90,6 +99,35 @@ DMT_DEV PairHit pair_test(TriPair const* P, f3 o, f3 d) {
   h.valid1 = mt_valid(det.y, h.t.y, h.u.y, h.v.y);
   h.orig0 = __float_as_uint(f.z), h.orig1 = __float_as_uint(f.w);
   return h;
+}
+
+// A leaf of the motion tree at time `time`: five more 16-byte loads (the pair's delta record), nine v_pk_fma_f32 that make
+// both triangles fmaf(time, D, A) -- the numbers the brute-force pass makes from the same two records -- and the same test.
+struct NoMotion {};
+struct LeafMotion {
+  TriPairDelta const* delta;
+  float time;
+};
+DMT_DEV PairHit pair_test_motion(TriPair const* P, TriPairDelta const* D, float time, f3 o, f3 d) {
+  float4 const* const q = reinterpret_cast<float4 const*>(P);
+  float4 const* const g = reinterpret_cast<float4 const*>(D);
+  float4 const a = q[0], b = q[1], c = q[2], e = q[3], f = q[4];
+  float4 const ga = g[0], gb = g[1], gc = g[2], ge = g[3], gf = g[4];
+  auto at = [&](float dx, float dy, float ax, float ay) { return fma_(time, v2f{dx, dy}, v2f{ax, ay}); };
+  PairHit h;
+  v2f det;
+  mt_core9_tri2(at(ga.x, ga.y, a.x, a.y), at(ga.z, ga.w, a.z, a.w), at(gb.x, gb.y, b.x, b.y), at(gb.z, gb.w, b.z, b.w),
+                at(gc.x, gc.y, c.x, c.y), at(gc.z, gc.w, c.z, c.w), at(ge.x, ge.y, e.x, e.y), at(ge.z, ge.w, e.z, e.w),
+                at(gf.x, gf.y, f.x, f.y), o.x, o.y, o.z, d.x, d.y, d.z, det, h.t, h.u, h.v);
+  h.valid0 = mt_valid(det.x, h.t.x, h.u.x, h.v.x);
+  h.valid1 = mt_valid(det.y, h.t.y, h.u.y, h.v.y);
+  h.orig0 = __float_as_uint(f.z), h.orig1 = __float_as_uint(f.w);
+  return h;
+}
+// the pair `idx` of the view for a static leaf (NoMotion) or a leaf of the motion tree
+DMT_DEV PairHit pair_test_at(BvhView const& bv, uint32_t idx, f3 o, f3 d, NoMotion) { return pair_test(bv.pairs + idx, o, d); }
+DMT_DEV PairHit pair_test_at(BvhView const& bv, uint32_t idx, f3 o, f3 d, LeafMotion m) {
+  return pair_test_motion(bv.pairs + idx, m.delta + idx, m.time, o, d);
 }
 
 struct TraversalCounters {  // per-lane work counters (stats build of the kernel only)
@@ -248,9 +286,9 @@ DMT_DEV void trav_node(BvhView const& bv, Traversal& tv, TraversalCounters* tc =
   trav_node<STATS>(bv, tv, node_fetch(bv, tv.cur), tc);
 }
 // leaf test: `ref` is a leaf reference (one triangle pair) of the ray (o, d); updates the best hit / the occlusion flag only
-template <bool STATS = false>
-DMT_DEV void trav_leaf_ref(BvhView const& bv, Traversal& tv, f3 o, f3 d, uint32_t ref, TraversalCounters* tc = nullptr) {
-  PairHit const h = pair_test(bv.pairs + (ref & ~kBvhLeafFlag), o, d);
+template <bool STATS = false, class M = NoMotion>
+DMT_DEV void trav_leaf_ref(BvhView const& bv, Traversal& tv, f3 o, f3 d, uint32_t ref, TraversalCounters* tc = nullptr, M m = M{}) {
+  PairHit const h = pair_test_at(bv, ref & ~kBvhLeafFlag, o, d, m);
   if constexpr (STATS) tc->tris += h.orig0 != h.orig1 ? 2u : 1u;  // a one-triangle leaf repeats its triangle
   if (tv.phase == TR_CLOSEST) {  // brute force keeps the lowest index among equal t (strict < in index order; -1 = none is the largest)
     if (h.valid0 && (h.t.x < tv.tlim || (h.t.x == tv.tlim && h.orig0 < uint32_t(tv.bestTri))))
@@ -262,46 +300,46 @@ DMT_DEV void trav_leaf_ref(BvhView const& bv, Traversal& tv, f3 o, f3 d, uint32_
   }
 }
 // leaf step of the synchronous traversal: cur is a leaf reference
-template <bool STATS = false>
-DMT_DEV void trav_leaf(BvhView const& bv, Traversal& tv, f3 o, f3 d, TraversalCounters* tc = nullptr) {
-  trav_leaf_ref<STATS>(bv, tv, o, d, tv.cur, tc);
+template <bool STATS = false, class M = NoMotion>
+DMT_DEV void trav_leaf(BvhView const& bv, Traversal& tv, f3 o, f3 d, TraversalCounters* tc = nullptr, M m = M{}) {
+  trav_leaf_ref<STATS>(bv, tv, o, d, tv.cur, tc, m);
   tv.cur = tv.tlim < 0.f ? kBvhEmpty : tv.stack.pop(bv);  // (a closest-hit limit is never negative)
 }
 // ---- whole traversals of one ray per lane (test kernels, lane_step with kFeatBvh): the same step functions in a loop ----
-template <bool STATS>
-DMT_DEV void trav_run(BvhView const& bv, Traversal& tv, f3 o, f3 d, TraversalCounters* tc) {
+template <bool STATS, class M = NoMotion>
+DMT_DEV void trav_run(BvhView const& bv, Traversal& tv, f3 o, f3 d, TraversalCounters* tc, M m = M{}) {
   for (;;) {
     bool const live = tv.cur != kBvhEmpty;
     if (!__any(live)) break;
     bool const onLeaf = live && (tv.cur & kBvhLeafFlag) != 0u;
     if (live && !onLeaf) trav_node<STATS>(bv, tv, tc);
-    if (onLeaf) trav_leaf<STATS>(bv, tv, o, d, tc);
+    if (onLeaf) trav_leaf<STATS>(bv, tv, o, d, tc, m);
   }
 }
 // closest hit: bestTri = ORIGINAL triangle index or -1
-template <bool STATS = false>
+template <bool STATS = false, class M = NoMotion>
 DMT_DEV void bvh_closest(BvhView const& bv, bool active, f3 o, f3 d, uint32_t gtid, int& bestTri, float& bt,
-                         float& bu, float& bvv, TraversalCounters* tc = nullptr) {
+                         float& bu, float& bvv, TraversalCounters* tc = nullptr, M m = M{}) {
   Traversal tv{};
   if constexpr (STATS) tv.stack.ovfCount = &tc->overflowPushes;
   tv.phase = TR_CLOSEST;
   tv.bestTri = -1, tv.bu = 0.f, tv.bv = 0.f;
   trav_set_ray(tv, o, d, kInf);
   if (!active) tv.cur = kBvhEmpty;
-  trav_run<STATS>(bv, tv, o, d, tc);
+  trav_run<STATS>(bv, tv, o, d, tc, m);
   bestTri = tv.bestTri, bt = tv.tlim, bu = tv.bu, bvv = tv.bv;
 }
 // any hit with t < tmax
-template <bool STATS = false>
+template <bool STATS = false, class M = NoMotion>
 DMT_DEV bool bvh_any(BvhView const& bv, bool active, f3 o, f3 d, float tmax, uint32_t gtid,
-                     TraversalCounters* tc = nullptr) {
+                     TraversalCounters* tc = nullptr, M m = M{}) {
   Traversal tv{};
   if constexpr (STATS) tv.stack.ovfCount = &tc->overflowPushes;
   tv.phase = TR_SHADOW;
   tv.bestTri = -1;
   trav_set_ray(tv, o, d, tmax);
   if (!active) tv.cur = kBvhEmpty;
-  trav_run<STATS>(bv, tv, o, d, tc);
+  trav_run<STATS>(bv, tv, o, d, tc, m);
   return tv.occluded();
 }
 

@@ -70,9 +70,14 @@ DMT_DEV void aov_material(KArgs k, Hit const& hit, int tri, float bu, float bv, 
   W = rec_weight(rec);
 }
 // one lane per pixel, row-major; whole waves stride over the frame (the BVH overflow stack is sized by the launch)
-__global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
+// MOTION (k_aov_motion, launched while key 1 is present): every sample is traced at its own time, as the film's is, so the
+// planes blur where the film blurs; the post-hit record is the triangle's at that time.
+template <bool MOTION>
+DMT_DEV void aov_body(AovArgs const& A) {
   KArgs const k = kargs_base();
-  if (!A.useBvh) cull_stage(k);
+  if constexpr (!MOTION) {
+    if (!A.useBvh) cull_stage(k);
+  }
   uint32_t const lane = threadIdx.x & 63u, gtid = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t const waves = gridDim.x * (blockDim.x >> 6);
   for (uint32_t w = gtid >> 6; w * 64u < A.pixels; w += waves) {  // wave-uniform trip count
@@ -94,14 +99,29 @@ __global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
       int best;
       float bu, bv;
       bool occluded;
-      if (A.useBvh)
-        trace_pair_bvh(k, st, alive, false, gtid, best, bu, bv, occluded);
-      else
-        trace_pair_brute(k, st, alive, false, best, bu, bv, occluded);
+      float bt = kInf;
+      if constexpr (MOTION) {
+        float const tm = motion_sample_time(k, base, s);
+        motion_set_time(tm);
+        if (A.useBvh)
+          trace_pair_bvh_motion(k, st, alive, false, v2f{tm, tm}, gtid, best, bu, bv, occluded, &bt);
+        else
+          trace_pair_brute_motion(k, st, alive, false, v2f{tm, tm}, best, bu, bv, occluded, &bt);
+      } else {
+        if (A.useBvh)
+          trace_pair_bvh(k, st, alive, false, gtid, best, bu, bv, occluded);
+        else
+          trace_pair_brute(k, st, alive, false, best, bu, bv, occluded);
+      }
       if (alive && best >= 0) {
-        TriS const T = load_tri(to_const_as(load_scene(k).tris), uint32_t(best));
-        float const t = mt_pair(T, st.rp).t.x;  // as k_test_closest reports it
-        Hit const hit = hit_finish(load_scene(k).post[best], bu, bv, r.d);
+        float t;
+        if constexpr (MOTION) {
+          t = bt;  // the trace's own
+        } else {
+          TriS const T = load_tri(to_const_as(load_scene(k).tris), uint32_t(best));
+          t = mt_pair(T, st.rp).t.x;  // as k_test_closest reports it
+        }
+        Hit const hit = shade_hit<MOTION ? kFeatMotion : 0u>(k, load_scene(k), best, bu, bv, r.d);
         f3 W, ns;
         aov_material(k, hit, best, bu, bv, W, ns);
         sumW = sumW + W, sumN = sumN + ns, sumP = sumP + hit.pos, sumT += t;
@@ -121,6 +141,8 @@ __global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) {
     }
   }
 }
+__global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) { aov_body<false>(A); }
+__global__ void __launch_bounds__(256) k_aov_motion(RenderParams P, AovArgs A) { aov_body<true>(A); }
 
 // A-trous passes (spatial SVGF).  Colour and variance travel together as one float4 (rgb, v) per pixel, ping-ponged
 // between passes; the AOVs stay fp32 (no packing), so tests/denoise_ref.py restates the filter on the same numbers.

@@ -235,7 +235,10 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   A.albedo = ctx->dn.albedo.get(), A.normal = ctx->dn.normal.get(), A.position = ctx->dn.pos.get();
   A.surface = ctx->dn.surface.get();
   A.width = ctx->filmW, A.pixels = uint32_t(pixels), A.aovSpp = aov_spp, A.useBvh = useBvh;
-  hipLaunchKernelGGL(k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, baseParams(ctx, threads), A);
+  RenderParams P = baseParams(ctx, threads);
+  uint32_t const motionMask = ctx->haveMotion ? kFeatMotion | (useBvh ? kFeatBvh : 0u) : 0u;  // the samples' times, as the film's rows
+  if (int const rcM = motionParams(ctx, motionMask, P)) return rcM;
+  hipLaunchKernelGGL(ctx->haveMotion ? k_aov_motion : k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
   HIP_TRY(ctx, hipGetLastError());
   ctx->dn.aovW = ctx->filmW, ctx->dn.aovH = ctx->filmH;
   ctx->dn.aovSurface = true;

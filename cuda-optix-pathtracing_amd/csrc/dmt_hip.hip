@@ -129,6 +129,9 @@ struct RenderParams {
   float texSppScale;          // max(1/8, 1/sqrt(frame spp))
   uint32_t const* texMip;     // RGBA8 texels of levels 1.. of every texture, back to back
   int32_t const* texMipDesc;  // [texture] {levels, first texel of level 1 in texMip}
+  // motion blur (dmt_set_motion); read by the *_motion kernels only, which also get the motion tree in `bvh`.  Last, so that
+  // no other field moves
+  MotionView motion;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -718,6 +721,8 @@ DMT_DEV f3 apply_material_textures(KArgs k, Rec32& rec, uint32_t matId, int tri,
 template <bool CULL = true>
 DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, int& bestTri, float& bu, float& bv, bool& occluded);
 
+#include "motion.hpp"
+
 // Optional parts of the path-tracing code, one bit each: the template argument F of path_shade, lane_finish, lane_step,
 // megakernel_body(_bvh) and wf_shade_body.  featuresOf (host) computes a context's mask; DMT_MEGAKERNELS and
 // DMT_WF_SHADE_KERNELS list the masks that have a kernel.
@@ -730,12 +735,21 @@ constexpr uint32_t kFeatBlend = 1u << 5;         // image textures + fractional 
 constexpr uint32_t kFeatLightTree = 1u << 6;     // SURVEY 8f-4 light tree (light_tree.hpp)
 constexpr uint32_t kFeatLightTreeRef = 1u << 7;  // the reference-semantics light tree (light_tree_ref.hpp)
 constexpr uint32_t kFeatTexFilter = 1u << 8;     // first-hit MIP / EWA texture filtering; with kFeatTex or kFeatBlend only
+constexpr uint32_t kFeatMotion = 1u << 9;        // motion blur: triangles at the sample's time (motion.hpp); plain and env-map rows only
+
+// the post-hit record path_shade works on: the uploaded one, or under kFeatMotion the triangle at the sample's time
+template <uint32_t F>
+DMT_DEV Hit shade_hit(KArgs k, SceneView const& sc, int tri, float bu, float bv, f3 rd) {
+  if constexpr (F & kFeatMotion) return hit_finish(motion_post(k, sc.post[tri], tri, motion_time()), bu, bv, rd);
+  else return hit_finish(sc.post[tri], bu, bv, rd);
+}
 
 template <uint32_t F>
 DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv) {
   static_assert(!((F & kFeatLightTree) && (F & kFeatLightTreeRef)), "one light tree at a time");
   static_assert(!((F & kFeatTex) && (F & kFeatBlend)), "kFeatBlend carries the texture code itself");
   static_assert(!(F & kFeatTexFilter) || (F & (kFeatTex | kFeatBlend)), "the texture filter needs the texture code");
+  static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
   if constexpr (F & kFeatEnv) {
@@ -761,7 +775,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
     return true;
   }
   f3 const rd = ray_dir(st);
-  Hit const hit = hit_finish(sc.post[bestTri], bu, bv, rd);
+  Hit const hit = shade_hit<F>(k, sc, bestTri, bu, bv, rd);
   uint32_t nAll = sc.lightCount;  // lights the NEE chooses among
   if constexpr (F & kFeatArea) {
     KArgs const ka = kargs(k);
@@ -1284,6 +1298,19 @@ DMT_DEV void trace_pair_bvh(KArgs k, PathState const& st, bool doC, bool doS, ui
   occluded = bvh_any<STATS>(bvh, doS, mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y),
                             mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y), st.smax, gtid, STATS ? &ls->tc : nullptr);
 }
+// the same two traversals through the motion tree (`bvh` of a motion launch), each ray at its own time.  bt (optional): the
+// closest hit's t
+DMT_DEV void trace_pair_bvh_motion(KArgs k, PathState const& st, bool doC, bool doS, v2f time, uint32_t gtid, int& bestTri, float& bu,
+                                   float& bv, bool& occluded, float* btOut = nullptr) {
+  BvhView const bvh = load_bvh(k);
+  TriPairDelta const* const delta = kargs(k)->motion.pairDelta;
+  float bt;
+  bvh_closest<false>(bvh, doC, mk3(st.rp.ox.x, st.rp.oy.x, st.rp.oz.x), mk3(st.rp.dx.x, st.rp.dy.x, st.rp.dz.x), gtid, bestTri, bt, bu, bv,
+                     nullptr, LeafMotion{delta, time.x});
+  occluded = bvh_any<false>(bvh, doS, mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y), st.smax, gtid,
+                            nullptr, LeafMotion{delta, time.y});
+  if (btOut) *btOut = bt;
+}
 
 // One "ray pass" of a lane: trace (closest + pending shadow), resolve the shadow ray, shade.
 // sink(L, sidx) is called once per completed sample with the index the sample was started with.
@@ -1298,7 +1325,11 @@ DMT_DEV void lane_step(KArgs k, uint32_t gtid, PathState& st, Sink&& sink, LaneS
   int bestTri;
   float bu, bv;
   bool occluded;
-  if constexpr (F & kFeatBvh)
+  if constexpr ((F & kFeatMotion) && (F & kFeatBvh))
+    trace_pair_bvh_motion(k, st, doC, doS, v2f{motion_time(), motion_time_shadow()}, gtid, bestTri, bu, bv, occluded);
+  else if constexpr (F & kFeatMotion)
+    trace_pair_brute_motion(k, st, doC, doS, v2f{motion_time(), motion_time_shadow()}, bestTri, bu, bv, occluded);
+  else if constexpr (F & kFeatBvh)
     trace_pair_bvh<(F & kFeatStats) != 0>(k, st, doC, doS, gtid, bestTri, bu, bv, occluded, ls);
   else
     trace_pair_brute(k, st, doC, doS, bestTri, bu, bv, occluded);
@@ -1334,6 +1365,9 @@ DMT_DEV void lane_finish(KArgs k, PathState& st, bool doC, bool doS, int bestTri
         sink(st.L, st.sidx);
       }
     }
+  }
+  if constexpr (F & kFeatMotion) {
+    if (st.hasShadow) motion_park_shadow();  // made by the bounce just shaded (an older one was resolved above): the current sample's
   }
   sect_mark(10);
 }
@@ -1401,6 +1435,7 @@ DMT_DEV void prepare_lens_ray(KArgs Pk, int px, int py, int32_t pixBase, uint32_
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
 }
+template <bool MOTION = false>  // MOTION: the sample's time is prepared with it (motion.hpp)
 DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
   float* const prep = s_prep + threadIdx.x;
   Ray r;
@@ -1427,7 +1462,9 @@ DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t 
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
   if (__builtin_expect(kargs(Pk)->lensR > 0.f, 0)) prepare_lens_ray(Pk, px, py, pixBase, s);  // wave-uniform, laid out of line
+  if constexpr (MOTION) motion_set_prepared(motion_sample_time(Pk, pixBase, s));
 }
+template <bool MOTION = false>
 DMT_DEV void path_begin_prepared(PathState& st) {
   float const* const prep = s_prep + threadIdx.x;
   float* const u = s_sampler_u + threadIdx.x;
@@ -1442,6 +1479,7 @@ DMT_DEV void path_begin_prepared(PathState& st) {
   st.lastT = false;
   st.active = true;
   st.sidx = __float_as_uint(prep[14 * kLdsThreads]);
+  if constexpr (MOTION) motion_begin_prepared();
 }
 
 #ifndef DMT_MIN_WAVES_PER_SIMD
@@ -1651,6 +1689,7 @@ DMT_DEV void slab_publish(TileArgs const& T, int lane, uint32_t slab, uint32_t n
 }
 
 // prepare unit u of item `seq` in this lane's s_prep
+template <bool MOTION = false>
 DMT_DEV void prepare_unit(KArgs Pk, uint32_t seq, uint32_t u, LaneSched& Ls) {
   uint32_t const slot = seq & 1u;
   uint32_t const* const d = s_desc[threadIdx.x >> 6][slot];
@@ -1660,7 +1699,7 @@ DMT_DEV void prepare_unit(KArgs Pk, uint32_t seq, uint32_t u, LaneSched& Ls) {
   else k = u / nInside, j = u - k * nInside;
   uint32_t const wbase = slot * kLdsThreads + (threadIdx.x & ~63u);
   uint32_t const pixel = s_pixmap[wbase + j];
-  prepare_sample(Pk, int(d[2]) + int(pixel & 7u), int(d[3]) + int(pixel >> 3), s_pixbase[wbase + pixel], d[4] + k);
+  prepare_sample<MOTION>(Pk, int(d[2]) + int(pixel & 7u), int(d[3]) + int(pixel >> 3), s_pixbase[wbase + pixel], d[4] + k);
   s_prep[14 * kLdsThreads + threadIdx.x] = __uint_as_float((slot << 31) | (k * 64u + pixel));
   Ls.prepared = true, Ls.prepSlot = slot != 0u;
 }
@@ -1788,6 +1827,7 @@ DMT_DEV void item_complete(KArgs Pk, uint32_t gtid, int lane, uint32_t seq, Wave
 // Hand the next units of the wave's items to the lanes that ask for one (`want`) and prepare them.  This is the ONE place
 // where work items are fetched (item_fetch is large, and the kernel already fills most of the instruction cache): a wave
 // starts with no item, and a wave whose last live item was retired comes here because all its lanes are starving.
+template <bool MOTION = false>
 DMT_DEV void sched_draw(KArgs Pk, uint32_t gtid, int lane, WaveSched& W, LaneSched& Ls, bool want) {
   if (__builtin_expect(W.nextUnit == W.totalUnits, 0)) {  // the item units are drawn from is used up (or there is none yet): fetch the next if there is room
     if (!W.exhausted && W.fetched - W.cur < 2u && W.slabFree != 0u) {
@@ -1801,7 +1841,7 @@ DMT_DEV void sched_draw(KArgs Pk, uint32_t gtid, int lane, WaveSched& W, LaneSch
   unsigned long long const m = __ballot(want);
   uint32_t const rank = uint32_t(__popcll(m & ((1ull << lane) - 1ull)));
   uint32_t const cnt = uint32_t(__popcll(m));
-  if (want && rank < avail) prepare_unit(Pk, W.alloc, W.nextUnit + rank, Ls);
+  if (want && rank < avail) prepare_unit<MOTION>(Pk, W.alloc, W.nextUnit + rank, Ls);
   W.nextUnit += cnt < avail ? cnt : avail;
 }
 
@@ -1868,6 +1908,7 @@ template <uint32_t F>
 DMT_DEV void megakernel_body() {
   static_assert(!(F & kFeatBvh), "BVH kernels run megakernel_body_bvh");
   constexpr bool STATS = (F & kFeatStats) != 0;
+  constexpr bool MOTION = (F & kFeatMotion) != 0;
   KArgs const Pk = kargs_base();
   LaneStats ls;
   int const lane = int(threadIdx.x) & 63;
@@ -1879,7 +1920,7 @@ DMT_DEV void megakernel_body() {
 #if DMT_SECTION_TIMING
   if (lane == 0) s_sectLast[threadIdx.x >> 6] = __builtin_readcyclecounter();  // (LDS is not zeroed: without this, start-up holds what the block before left there)
 #endif
-  cull_stage(Pk);
+  if constexpr (!MOTION) cull_stage(Pk);  // (the motion pass is the plain loop: the clusters' bounds are of key 0)
 #if DMT_SECTION_TIMING
   if (lane < 16) s_sectAcc[threadIdx.x >> 6][lane] = 0;
   sect_mark(15);
@@ -1888,10 +1929,10 @@ DMT_DEV void megakernel_body() {
     for (;;) {
       bool const needPrep = !Ls.prepared;
       bool const starving = !st.active && needPrep;
-      if (__any(starving) || __popcll(__ballot(needPrep)) >= DMT_PREP_THRESHOLD) sched_draw(Pk, gtid, lane, W, Ls, needPrep);
+      if (__any(starving) || __popcll(__ballot(needPrep)) >= DMT_PREP_THRESHOLD) sched_draw<MOTION>(Pk, gtid, lane, W, Ls, needPrep);
       if (W.cur == W.fetched) break;  // nothing live and nothing fetched: the launch has no more items
       if (!st.active && Ls.prepared) {
-        path_begin_prepared(st);
+        path_begin_prepared<MOTION>(st);
         Ls.prepared = false;
         if constexpr (STATS) ++ls.samples;
       }
@@ -1934,6 +1975,7 @@ template <uint32_t F>
 DMT_DEV void megakernel_body_bvh() {
   static_assert((F & kFeatBvh) != 0, "brute-force kernels run megakernel_body");
   constexpr bool STATS = (F & kFeatStats) != 0;
+  constexpr bool MOTION = (F & kFeatMotion) != 0;
   KArgs const Pk = kargs_base();
 #if DMT_BVH_DUMMY_LDS > 0
   __shared__ volatile char s_dummy[DMT_BVH_DUMMY_LDS];
@@ -1957,12 +1999,12 @@ DMT_DEV void megakernel_body_bvh() {
       bool const starving = idle && !st.active && needPrep;
       if (__any(starving) || __popcll(__ballot(needPrep)) >= DMT_PREP_THRESHOLD) {
         if constexpr (STATS) ++ls.itPrep, ls.lanesPrep += needPrep ? 1u : 0u;
-        sched_draw(Pk, gtid, lane, W, Ls, needPrep);
+        sched_draw<MOTION>(Pk, gtid, lane, W, Ls, needPrep);
       }
       if (W.cur == W.fetched) break;  // nothing live and nothing fetched: the launch has no more items
       if constexpr (STATS) ++ls.itOuter;
       if (idle && !st.active && Ls.prepared) {
-        path_begin_prepared(st);
+        path_begin_prepared<MOTION>(st);
         Ls.prepared = false;
         if constexpr (STATS) ++ls.samples;
       }
@@ -1994,6 +2036,12 @@ DMT_DEV void megakernel_body_bvh() {
       //    that were still descending: 11 % lane utilisation in node steps).  The loop ends when enough lanes
       //    wait for shading.
       BvhView const bvh = load_bvh(Pk);
+      // motion rows: a leaf is tested at the time of the ray being traversed -- the pending shadow ray's own while the lane is
+      // in its shadow phase -- read from LDS at the leaf step; nothing of it is live across node steps or shading
+      auto const leafMotion = [&]() {
+        if constexpr (MOTION) return LeafMotion{kargs(Pk)->motion.pairDelta, tv.phase == TR_SHADOW ? motion_time_shadow() : motion_time()};
+        else return NoMotion{};
+      };
       int const shadeThreshold = kargs(Pk)->shadeThreshold > 1 ? kargs(Pk)->shadeThreshold : 1;  // (0 would never let the wave traverse)
       // The words of the node a lane stands on are fetched AHEAD: when a step leaves the lane on an inner node, its loads are
       // issued right there, and the step selection, the other kind of step for the other lanes and the loop overhead run
@@ -2028,7 +2076,7 @@ DMT_DEV void megakernel_body_bvh() {
 #ifdef DMT_BVH_BOTH_STEPS  // experiment: every traversing lane advances every iteration (node and leaf code both run)
         if constexpr (STATS) ++ls.itNode, ++ls.itLeaf, ls.lanesLeaf += onLeaf ? 1u : 0u;
         if (onNode) trav_node<STATS>(bvh, tv, STATS ? &ls.tc : nullptr);
-        if (onLeaf) trav_leaf<STATS>(bvh, tv, ray_org(st), ray_dir(st), STATS ? &ls.tc : nullptr);
+        if (onLeaf) trav_leaf<STATS>(bvh, tv, ray_org(st), ray_dir(st), STATS ? &ls.tc : nullptr, leafMotion());
 #else
         if (nNode * DMT_BVH_NODE_WEIGHT >= nLeaf * DMT_BVH_LEAF_WEIGHT) {
           if constexpr (STATS) ++ls.itNode;
@@ -2039,7 +2087,7 @@ DMT_DEV void megakernel_body_bvh() {
         } else {
           if constexpr (STATS) ++ls.itLeaf, ls.lanesLeaf += onLeaf ? 1u : 0u;
           if (onLeaf) {
-            trav_leaf<STATS>(bvh, tv, ray_org(st), ray_dir(st), STATS ? &ls.tc : nullptr);
+            trav_leaf<STATS>(bvh, tv, ray_org(st), ray_dir(st), STATS ? &ls.tc : nullptr, leafMotion());
             if (!(tv.cur & kBvhLeafFlag)) nd = node_fetch(bvh, tv.cur);
           }
         }
@@ -2093,7 +2141,11 @@ DMT_DEV void megakernel_body_bvh() {
   X(_blendf, kFeatBlend | kFeatTexFilter, 2, megakernel_body)                       \
   X(_bvh_blendf, kFeatBvh | kFeatBlend | kFeatTexFilter, 2, megakernel_body_bvh)    \
   X(_env_blendf, kFeatEnv | kFeatBlend | kFeatTexFilter, 2, megakernel_body)        \
-  X(_bvh_env_blendf, kFeatBvh | kFeatEnv | kFeatBlend | kFeatTexFilter, 2, megakernel_body_bvh)
+  X(_bvh_env_blendf, kFeatBvh | kFeatEnv | kFeatBlend | kFeatTexFilter, 2, megakernel_body_bvh) \
+  X(_motion, kFeatMotion, 4, megakernel_body)                                       \
+  X(_bvh_motion, kFeatBvh | kFeatMotion, 3, megakernel_body_bvh)                    \
+  X(_env_motion, kFeatEnv | kFeatMotion, 4, megakernel_body)                        \
+  X(_bvh_env_motion, kFeatBvh | kFeatEnv | kFeatMotion, 3, megakernel_body_bvh)
 // the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
 // algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
 #define DMT_STATS_MEGAKERNELS(X)                                                    \
@@ -2305,6 +2357,21 @@ struct dmt_ctx {
   CameraXf xf{};
   SamplerParams sp{};
   float lensR = 0.f, lensD = 1.f;  // thin lens (dmt_set_lens): radius 0 = pinhole; survives dmt_set_camera and scene uploads
+  // motion blur (dmt_set_motion).  Key 0 is the soup above; key 1 lives here and is dropped with it.  The
+  // motion tree is a second tree beside the static one (which stays as it is: dmt_clear_motion restores every film byte
+  // for byte), built by the host SAH builder over both keys' boxes when a BVH launch first needs it.
+  bool haveMotion = false;
+  float shutterOpen = 0.f, shutterClose = 1.f;  // dmt_set_shutter: survives scene uploads and dmt_set_camera, like the lens
+  std::vector<float> h_xs1, h_ys1, h_zs1;       // key 1 (the motion tree's input)
+  DevBuf<TriIsect> d_dtris;                     // D = B - A per triangle
+  DevBuf<TriKey1> d_post1;                      // key-1 vertices
+  DevBuf<Bvh4Node> d_mNodes;                    // the motion tree, its key-0 pairs and their deltas
+  DevBuf<TriPair> d_mPairs;
+  DevBuf<TriPairDelta> d_mDelta;
+  bool haveMotionTree = false;
+  uint32_t mNodeCount = 0, mPairCount = 0;
+  int mDepth = 0;
+  double mBuildMs = 0.0;
   // film: the context's own, or the caller's after dmt_film_bind (which frees the own one)
   DevBuf<float4> ownMean, ownM2;
   float4* d_mean = nullptr;
@@ -2667,6 +2734,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (treeable && c->lightSampling == DMT_LIGHTS_TREE) F |= kFeatLightTree;
   if (treeable && c->lightSampling == DMT_LIGHTS_TREE_REFERENCE) F |= kFeatLightTreeRef;
   if (c->texFilter == DMT_TEXFILTER_REFERENCE && (F & (kFeatTex | kFeatBlend))) F |= kFeatTexFilter;
+  if (c->haveMotion) F |= kFeatMotion;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2681,6 +2749,14 @@ int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
 }
 // the combinations dmt_render refuses (mask | kFeatStats for dmt_render_stats / dmt_render_profile)
 int checkFeatures(dmt_ctx* ctx, uint32_t F) {
+  if (F & kFeatMotion) {  // motion blur has the plain and env-map megakernel rows
+    if (F & kFeatStats) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: motion blur (dmt_set_motion) has no counting kernels");
+    if (F & kFeatTexFilter) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with the first-hit texture filter is not supported");
+    if (F & (kFeatTex | kFeatBlend)) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with image textures or blend materials is not supported");
+    if (F & kFeatArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with emissive triangles is not supported");
+    if (F & (kFeatLightTree | kFeatLightTreeRef)) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with a light tree is not supported");
+    if ((F & kFeatBvh) && ctx->bvhStrategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with the wavefront BVH strategy is not supported");
+  }
   if ((F & kFeatStats) && (F & (kFeatTex | kFeatBlend | kFeatArea | kFeatLightTree | kFeatLightTreeRef)))
     return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: the counting kernels exist for the plain and env-map BVH kernels only; "
                                     "with textures, blended materials, emissive triangles or a light tree they would describe a different kernel");
@@ -2874,6 +2950,75 @@ int buildBvh(dmt_ctx* ctx) {
   R.builder = DMT_BVH_BUILT_BY_DEVICE;
   R.triangles = ctx->triCount, R.nodes = r.nodeCount, R.pairs = r.pairCount, R.depth = r.depth;
   R.build_ms = double(r.ms), R.temp_bytes = r.tempBytes;
+  return DMT_OK;
+}
+
+// ---- motion blur: key 1 on the host side ----
+void dropMotion(dmt_ctx* ctx) {  // the positions key 1 was a motion FROM are going away
+  ctx->haveMotion = false, ctx->haveMotionTree = false;
+  ctx->h_xs1.clear(), ctx->h_ys1.clear(), ctx->h_zs1.clear();
+  ctx->d_dtris.reset(), ctx->d_post1.reset(), ctx->d_mNodes.reset(), ctx->d_mPairs.reset(), ctx->d_mDelta.reset();
+  ctx->mNodeCount = ctx->mPairCount = 0, ctx->mDepth = 0, ctx->mBuildMs = 0.0;
+}
+// The motion tree: the host SAH builder over every triangle's union box of both keys, whatever dmt_set_accel_build says (the
+// device builder and the refit know one key).  Leaves: the key-0 pair and D = (key-1 pair) - (key-0 pair) field by field, the
+// numbers of d_tris / d_dtris in the pairs' interleaving, each array with the three guard records of buildBvhHost.
+int ensureMotionTree(dmt_ctx* ctx) {
+  if (ctx->haveMotionTree) return DMT_OK;
+  uint32_t const n = ctx->triCount;
+  auto const t0 = std::chrono::steady_clock::now();
+  bvh_build::Result r = bvh_build::build(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), n, ctx->h_xs1.data(), ctx->h_ys1.data(), ctx->h_zs1.data());
+  size_t const npairs = r.pairTris.size() / 2;
+  if (npairs > 0x7FFFFFFFull || r.nodes.size() > 0x7FFFFFFFull) return fail(ctx, DMT_ERR_INVALID, "motion BVH: too many nodes / triangle pairs");
+  std::vector<TriPair> pairs(npairs ? npairs + 3 : 0);
+  std::vector<TriPairDelta> deltas(pairs.size());
+  auto verts = [](std::vector<float> const& xs, std::vector<float> const& ys, std::vector<float> const& zs, uint32_t i, float v[9]) {
+    for (int c = 0; c < 3; ++c) v[3 * c] = xs[4 * size_t(i) + c], v[3 * c + 1] = ys[4 * size_t(i) + c], v[3 * c + 2] = zs[4 * size_t(i) + c];
+  };
+  for (size_t p = 0; p < npairs; ++p) {
+    TriPair B{};
+    for (int half = 0; half < 2; ++half) {
+      uint32_t const i = r.pairTris[2 * p + size_t(half)];
+      float v0[9], v1[9];
+      verts(ctx->h_xs, ctx->h_ys, ctx->h_zs, i, v0), verts(ctx->h_xs1, ctx->h_ys1, ctx->h_zs1, i, v1);
+      refit::packPairHalf(pairs[p], half, v0, i), refit::packPairHalf(B, half, v1, i);
+    }
+    TriPair const& A = pairs[p];
+    TriPairDelta& D = deltas[p];
+    for (int h = 0; h < 2; ++h) {
+      D.p0x[h] = B.p0x[h] - A.p0x[h], D.p0y[h] = B.p0y[h] - A.p0y[h], D.p0z[h] = B.p0z[h] - A.p0z[h];
+      D.e0x[h] = B.e0x[h] - A.e0x[h], D.e0y[h] = B.e0y[h] - A.e0y[h], D.e0z[h] = B.e0z[h] - A.e0z[h];
+      D.e1x[h] = B.e1x[h] - A.e1x[h], D.e1y[h] = B.e1y[h] - A.e1y[h], D.e1z[h] = B.e1z[h] - A.e1z[h];
+    }
+    D.pad[0] = D.pad[1] = 0;
+  }
+  for (size_t p = npairs; p < pairs.size(); ++p) pairs[p] = pairs[npairs - 1], deltas[p] = deltas[npairs - 1];
+  DevBuf<Bvh4Node> nodes;
+  DevBuf<TriPair> leaves;
+  DevBuf<TriPairDelta> dl;
+  HIP_TRY(ctx, nodes.assign(r.nodes.data(), r.nodes.size()));
+  HIP_TRY(ctx, leaves.assign(pairs.data(), pairs.size()));
+  HIP_TRY(ctx, dl.assign(deltas.data(), deltas.size()));
+  ctx->d_mNodes = std::move(nodes), ctx->d_mPairs = std::move(leaves), ctx->d_mDelta = std::move(dl);
+  ctx->mNodeCount = uint32_t(r.nodes.size()), ctx->mPairCount = uint32_t(npairs), ctx->mDepth = r.depth;
+  ctx->mBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ctx->haveMotionTree = true;
+  return DMT_OK;
+}
+// What a launch of a *_motion kernel reads beside baseParams: the delta records, key 1, the shutter, and for a BVH mask the
+// motion tree in place of the static one (after the caller has set P.bvh's overflow stack for its launch).
+int motionParams(dmt_ctx* ctx, uint32_t F, RenderParams& P) {
+  if (!(F & kFeatMotion)) return DMT_OK;
+  P.motion.dtris = ctx->d_dtris.get(), P.motion.post1 = ctx->d_post1.get();
+  P.motion.open = ctx->shutterOpen, P.motion.close = ctx->shutterClose;
+  if (F & kFeatBvh) {
+    if (int const rc = ensureMotionTree(ctx)) return rc;
+    P.bvh.nodes = ctx->d_mNodes.get(), P.bvh.pairs = ctx->d_mPairs.get(), P.motion.pairDelta = ctx->d_mDelta.get();
+    if (ctx->shadeThresholdEnv <= 0) {  // bvhShadeThreshold's steps, by the motion tree's size
+      uint32_t const n = ctx->mNodeCount;
+      P.shadeThreshold = n <= 1024u ? 56 : n <= 16384u ? 52 : n <= 131072u ? 40 : DMT_BVH_SHADE_THRESHOLD;
+    }
+  }
   return DMT_OK;
 }
 
@@ -3195,6 +3340,7 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
   ctx->h_mat.assign(mat_id, mat_id + count);
   ctx->haveBvh = false;
+  dropMotion(ctx);             // key 1 was a motion from the soup just replaced
   ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
   ctx->h_areaTri.clear(), ctx->h_areaLe.clear();  // emissive triangles are indices into the soup just replaced
   if (int const rcA = rebuildAreaLights(ctx)) return rcA;
@@ -3231,6 +3377,7 @@ int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const fl
   bool done = false;
   if (int const rc = beginUpdate(ctx, "dmt_update_vertices", !xs || !ys || !zs, count, T, &done)) return rc;
   if (done) return DMT_OK;
+  dropMotion(ctx);  // key 1 was a motion from the positions being replaced
   std::vector<TriIsect> a;
   std::vector<TriPost> b;
   packSoup(xs, ys, zs, ctx->h_mat.data(), count, a, b);
@@ -3249,6 +3396,7 @@ int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count)
   bool done = false;
   if (int const rc = beginUpdate(ctx, "dmt_update_vertices_device", !d_verts9, count, T, &done)) return rc;
   if (done) return DMT_OK;
+  dropMotion(ctx);  // key 1 was a motion from the positions being replaced
   HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->d_tris.get(), ctx->d_post.get(), ctx->stream));
   if (int const rcT = mirrorDeviceUpdate(ctx, d_verts9, count)) return rcT;
   // the host mirrors (the host builder's, the cull plan's and a later rebuild's input) from the records just made
@@ -3383,7 +3531,11 @@ int dmt_set_accel(dmt_ctx* ctx, int mode) {
   ctx->accel = mode;
   if (mode == DMT_ACCEL_BVH && ctx->haveTris && !ctx->haveBvh) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return buildBvh(ctx);
+    if (int const rc = buildBvh(ctx)) return rc;
+  }
+  if (mode == DMT_ACCEL_BVH && ctx->haveMotion) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ensureMotionTree(ctx);
   }
   return DMT_OK;
 }
@@ -3681,7 +3833,7 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   // Sampler table: for plain megakernel launches only.  Counting launches are not timed, the wavefront form prepares its
   // samples per pass, and an adaptive round's live pixel count is on the device.  The owned pixels are counted in whole tiles.
   SamplerTablePlan tab;
-  if (!stats6 && !wavefront && !sel)
+  if (!stats6 && !wavefront && !sel && !(F & kFeatMotion))  // (motion launches compute their samples: the table has no time plane)
     tab = samplerTablePlan(ctx->filmW, ctx->filmH, uint64_t(ownedTiles) * 64u, spp, P.chunkSpp, ctx->samTabBudget, ctx->samTabMode,
                            ctx->lensR > 0.f ? kSamTabLensEntryBytes : kSamTabEntryBytes);
 
@@ -3750,6 +3902,7 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
       return DMT_OK;
     }
   }
+  if (int const rcM = motionParams(ctx, F, P)) return rcM;
   if (!wavefront) {
     for (uint32_t c0 = 0; c0 < callChunks; c0 += sliceChunks) {
       uint32_t const first = c0 * P.chunkSpp;  // of the call's samples
@@ -4200,6 +4353,112 @@ int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
   float const* const m = ctx->xf.rfc;  // column 2 = the viewing direction
   *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
   return DMT_OK;
+}
+
+// ---- motion blur -------------------------------------------------------------------------
+static bool shutterOk(float open, float close) { return std::isfinite(open) && std::isfinite(close) && 0.f <= open && open <= close && close <= 1.f; }
+
+int dmt_set_motion(dmt_ctx* ctx, const float* xs1, const float* ys1, const float* zs1, size_t count) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_set_motion: before any dmt_upload_triangles");
+  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: count differs from the uploaded triangle count");
+  if (count && (!xs1 || !ys1 || !zs1)) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: null array");
+  for (size_t k = 0; k < 4 * count; ++k) {
+    if ((k & 3) == 3) continue;  // the SoA's pad lane
+    if (!std::isfinite(xs1[k]) || !std::isfinite(ys1[k]) || !std::isfinite(zs1[k])) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: a position is not finite");
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old key 1
+  std::vector<TriIsect> a, b;
+  std::vector<TriPost> pa, pb;
+  packSoup(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->h_mat.data(), count, a, pa);  // A: the records the context holds
+  packSoup(xs1, ys1, zs1, ctx->h_mat.data(), count, b, pb);
+  std::vector<TriIsect> d(count);
+  std::vector<TriKey1> q(count);
+  for (size_t i = 0; i < count; ++i) {  // D = B - A, component by component in fp32
+    TriIsect const &A = a[i], &B = b[i];
+    TriIsect& D = d[i];
+    D.p0x = B.p0x - A.p0x, D.p0y = B.p0y - A.p0y, D.p0z = B.p0z - A.p0z;
+    D.e0x = B.e0x - A.e0x, D.e0y = B.e0y - A.e0y, D.e0z = B.e0z - A.e0z;
+    D.e1x = B.e1x - A.e1x, D.e1y = B.e1y - A.e1y, D.e1z = B.e1z - A.e1z;
+    D.matId = 0, D.pad0 = D.pad1 = 0;
+    TriPost const& P = pb[i];
+    q[i] = TriKey1{P.p0x, P.p0y, P.p0z, P.p1x, P.p1y, P.p1z, P.p2x, P.p2y, P.p2z, 0.f, 0.f, 0.f};
+  }
+  DevBuf<TriIsect> dd;
+  DevBuf<TriKey1> dq;
+  HIP_TRY(ctx, dd.assign(d.data(), count));
+  HIP_TRY(ctx, dq.assign(q.data(), count));
+  dropMotion(ctx);
+  ctx->d_dtris = std::move(dd), ctx->d_post1 = std::move(dq);
+  ctx->h_xs1.assign(xs1, xs1 + 4 * count), ctx->h_ys1.assign(ys1, ys1 + 4 * count), ctx->h_zs1.assign(zs1, zs1 + 4 * count);
+  ctx->haveMotion = true;
+  if (ctx->accel == DMT_ACCEL_BVH) return ensureMotionTree(ctx);
+  return DMT_OK;
+}
+
+int dmt_clear_motion(dmt_ctx* ctx) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveMotion) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read key 1
+  dropMotion(ctx);
+  return DMT_OK;
+}
+
+int dmt_set_shutter(dmt_ctx* ctx, float open, float close) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!shutterOk(open, close)) return fail(ctx, DMT_ERR_INVALID, "dmt_set_shutter: needs finite 0 <= open <= close <= 1");
+  ctx->shutterOpen = open, ctx->shutterClose = close;
+  return DMT_OK;
+}
+
+int dmt_motion_info(dmt_ctx* ctx, int* keys, float* open, float* close, uint32_t* tree_nodes, uint32_t* tree_pairs, double* tree_build_ms) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (keys) *keys = ctx->haveTris ? (ctx->haveMotion ? 2 : 1) : 0;
+  if (open) *open = ctx->shutterOpen;
+  if (close) *close = ctx->shutterClose;
+  if (tree_nodes) *tree_nodes = ctx->haveMotionTree ? ctx->mNodeCount : 0u;
+  if (tree_pairs) *tree_pairs = ctx->haveMotionTree ? ctx->mPairCount : 0u;
+  if (tree_build_ms) *tree_build_ms = ctx->haveMotionTree ? ctx->mBuildMs : 0.0;
+  return DMT_OK;
+}
+
+int dmt_shutter_times(int width, int height, float open, float close, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t) {
+  if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || n < 0 || !shutterOk(open, close)) return DMT_ERR_INVALID;
+  if (n && (!pxs || !pys || !ss || !t)) return DMT_ERR_INVALID;
+  SamplerParams const sp = computeSamplerParams(width, height);
+  int64_t const stride = int64_t(sp.scale0) * sp.scale1;
+  for (int i = 0; i < n; ++i)
+    if (pxs[i] < 0 || pys[i] < 0 || pxs[i] >= width || pys[i] >= height || ss[i] < 0 || (int64_t(ss[i]) + 1) * stride > 0x7FFFFFFFll)
+      return DMT_ERR_INVALID;  // outside the frame, or the sample overflows the 32-bit Halton index
+  for (int i = 0; i < n; ++i) t[i] = shutter_time(uint32_t(halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * int32_t(stride)), open, close);
+  return DMT_OK;
+}
+
+int dmt_motion_positions(const float* xs0, const float* ys0, const float* zs0, const float* xs1, const float* ys1, const float* zs1, size_t count,
+                         float t, float* xs, float* ys, float* zs) {
+  if (!std::isfinite(t) || (count && (!xs0 || !ys0 || !zs0 || !xs1 || !ys1 || !zs1 || !xs || !ys || !zs))) return DMT_ERR_INVALID;
+  for (size_t k = 0; k < 4 * count; ++k) {
+    bool const pad = (k & 3) == 3;  // the SoA's pad lane: key 0's
+    xs[k] = pad ? xs0[k] : motion_lerp(t, xs0[k], xs1[k]);
+    ys[k] = pad ? ys0[k] : motion_lerp(t, ys0[k], ys1[k]);
+    zs[k] = pad ? zs0[k] : motion_lerp(t, zs0[k], zs1[k]);
+  }
+  return DMT_OK;
+}
+
+int dmt_motion_bvh_validate(const float* xs0, const float* ys0, const float* zs0, const float* xs1, const float* ys1, const float* zs1,
+                            size_t count, int* node_count, int* pair_count, int* depth) {
+  if ((count && (!xs0 || !ys0 || !zs0 || !xs1 || !ys1 || !zs1)) || count > 0x0FFFFFFFu) return DMT_ERR_INVALID;
+  bvh_build::Result const r = bvh_build::build(xs0, ys0, zs0, uint32_t(count), xs1, ys1, zs1);
+  if (node_count) *node_count = int(r.nodes.size());
+  if (pair_count) *pair_count = int(r.pairTris.size() / 2);
+  if (depth) *depth = r.depth;
+  // every decoded child box holds the vertices below it at key 0 and at key 1 (and every other invariant of a tree, twice)
+  bool const ok0 = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs0, ys0, zs0, count, nullptr, nullptr, nullptr);
+  bool const ok1 = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs1, ys1, zs1, count, nullptr, nullptr, nullptr);
+  return ok0 && ok1 && r.depth <= kBvhMaxDepth ? DMT_OK : DMT_ERR_STATE;
 }
 
 int dmt_kernel_time(dmt_ctx* ctx, double* total_ms, uint64_t* launches, int reset) {

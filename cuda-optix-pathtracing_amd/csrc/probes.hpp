@@ -18,12 +18,13 @@ namespace {
 template <uint32_t F>
 __global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t const* pys, int32_t const* ss, float* L3) {
   KArgs const k = kargs_base();
-  if constexpr (!(F & kFeatBvh)) cull_stage(k);
+  if constexpr (!(F & (kFeatBvh | kFeatMotion))) cull_stage(k);
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
   PathState st{};
   if (i < n) {
     ColdArgs const c = load_cold_args(k);
     path_begin(st, c.cam, c.sp, pxs[i], pys[i], halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i]), kargs(k)->lensR, kargs(k)->lensD);
+    if constexpr (F & kFeatMotion) motion_set_time(motion_sample_time(k, halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i])));
   }
   auto store = [&](f3 L, uint32_t) { L3[3 * i] = L.x, L3[3 * i + 1] = L.y, L3[3 * i + 2] = L.z; };
   uint32_t const gtid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,8 +71,8 @@ __global__ void k_test_envmap(EnvView env, int n, float const* u2, float const* 
 
 // single path with a per-bounce log, one record per closest-hit ray (at most cap, *nOut written):
 //   rec12 = {tri (-1: miss), pos3, beta3, L3 before the bounce is shaded, depth, sampler dimension}
-__global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float* rec12, int cap, int* nOut,
-                                 float* L3) {
+template <bool MOTION>
+DMT_DEV void test_trace_log_body(int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   KArgs const k = kargs_base();
   SceneView const sc = load_scene(k);
@@ -79,6 +80,7 @@ __global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float*
   {
     ColdArgs const c = load_cold_args(k);
     path_begin(st, c.cam, c.sp, px, py, halton_pixel_base(c.sp, px, py), uint32_t(smp), kargs(k)->lensR, kargs(k)->lensD);
+    if constexpr (MOTION) motion_set_time(motion_sample_time(k, halton_pixel_base(c.sp, px, py), uint32_t(smp)));
   }
   int n = 0;
   for (;;) {
@@ -86,7 +88,10 @@ __global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float*
     int bestTri;
     float bu, bv;
     bool occluded;
-    trace_pair_brute<false>(k, st, doC, doS, bestTri, bu, bv, occluded);  // one thread: the plain loop
+    if constexpr (MOTION)  // one sample: its shadow rays share its time
+      trace_pair_brute_motion(k, st, doC, doS, v2f{motion_time(), motion_time()}, bestTri, bu, bv, occluded);
+    else
+      trace_pair_brute<false>(k, st, doC, doS, bestTri, bu, bv, occluded);  // one thread: the plain loop
     if (doS) {
       if (!occluded) st.L = st.L + get_C();
       st.hasShadow = false;
@@ -96,18 +101,25 @@ __global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float*
       if (n < cap) {
         float* r = rec12 + 12 * n++;
         f3 pos = mk3(0, 0, 0);
-        if (bestTri >= 0) pos = hit_finish(sc.post[bestTri], bu, bv, ray_dir(st)).pos;
+        if (bestTri >= 0) pos = shade_hit<MOTION ? kFeatMotion : 0u>(k, sc, bestTri, bu, bv, ray_dir(st)).pos;
         r[0] = float(bestTri), r[1] = pos.x, r[2] = pos.y, r[3] = pos.z;
         r[4] = st.beta.x, r[5] = st.beta.y, r[6] = st.beta.z, r[7] = st.L.x, r[8] = st.L.y, r[9] = st.L.z;
         r[10] = float(st.depth), r[11] = float(st.rng.dim);
       }
-      ended = path_shade<0>(k, st, bestTri, bu, bv);
+      ended = path_shade<MOTION ? kFeatMotion : 0u>(k, st, bestTri, bu, bv);
       if (ended) st.active = false;
     }
     if (ended && !st.hasShadow) break;
   }
   *nOut = n;
   L3[0] = st.L.x, L3[1] = st.L.y, L3[2] = st.L.z;
+}
+__global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float* rec12, int cap, int* nOut,
+                                 float* L3) {
+  test_trace_log_body<false>(px, py, smp, rec12, cap, nOut, L3);
+}
+__global__ void k_test_trace_log_motion(RenderParams P, int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
+  test_trace_log_body<true>(px, py, smp, rec12, cap, nOut, L3);
 }
 
 __global__ void k_test_tri(float const* xs, float const* ys, float const* zs, uint32_t n, f3 o, f3 d,
@@ -290,6 +302,39 @@ __global__ void k_test_closest(RenderParams P, bool useBvh, int n, float const* 
     bt = mt_pair(T, st.rp).t.x;
   }
   if (alive) tri[i] = best, tOut[i] = bt;
+}
+
+// dmt_test_closest_hit_at: the closest hit of ray i against the scene at time[i], by the motion rows' trace of the accel mode
+__global__ void k_test_closest_at(RenderParams P, bool useBvh, int n, float const* o3, float const* d3, float const* time, int32_t* tri,
+                                  float* tOut, float* uv2) {
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  bool const alive = i < n;
+  PathState st{};
+  if (alive)
+    set_ray(st, mk3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), mk3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]));
+  st.active = alive;
+  float const tm = alive ? time[i] : 0.f;
+  int best;
+  float bu, bv, bt = kInf;
+  bool occluded;
+  if (useBvh)
+    trace_pair_bvh_motion(k, st, alive, false, v2f{tm, tm}, blockIdx.x * blockDim.x + threadIdx.x, best, bu, bv, occluded, &bt);
+  else
+    trace_pair_brute_motion(k, st, alive, false, v2f{tm, tm}, best, bu, bv, occluded, &bt);
+  if (alive) {
+    tri[i] = best, tOut[i] = best >= 0 ? bt : kInf;
+    if (uv2) uv2[2 * i] = best >= 0 ? bu : 0.f, uv2[2 * i + 1] = best >= 0 ? bv : 0.f;
+  }
+}
+
+// dmt_test_shutter_times: shutter_time of the samples, as the motion rows compute it
+__global__ void k_test_shutter(SamplerParams sp, float open, float close, int n, int32_t const* pxs, int32_t const* pys, int32_t const* ss,
+                               float* t) {
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * (sp.scale0 * sp.scale1);
+  t[i] = shutter_time(uint32_t(h), open, close);
 }
 
 // dmt_camera_project (project_point) on the device
@@ -531,7 +576,9 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
     if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_samples: BVH not built");
     HIP_TRY(ctx, reserveOverflow(ctx, p.threads(64)));
   }
-  hipLaunchKernelGGL(kernel, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), n, dpx.get(), dpy.get(),
+  RenderParams P = baseParams(ctx, p.threads(64));
+  if (int const rc = motionParams(ctx, F, P)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, n, dpx.get(), dpy.get(),
                      dss.get(), dL.get());
   return finishProbe(ctx, p);
 }
@@ -563,8 +610,10 @@ int dmt_test_trace_log(dmt_ctx* ctx, int px, int py, int s, float* rec12, int ca
   ProbeOut<float> dr(p, rec12, 12 * size_t(cap)), dL(p, L3, 3);
   ProbeOut<int> dn(p, n_out, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), px, py, s, dr.get(),
-                     cap, dn.get(), dL.get());
+  RenderParams P = baseParams(ctx, p.threads(64));
+  if (int const rc = motionParams(ctx, ctx->haveMotion ? kFeatMotion : 0u, P)) return rc;  // (brute force: no tree)
+  hipLaunchKernelGGL(ctx->haveMotion ? k_test_trace_log_motion : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
+                     dr.get(), cap, dn.get(), dL.get());
   return finishProbe(ctx, p);
 }
 
@@ -584,6 +633,41 @@ int dmt_test_closest_hit(dmt_ctx* ctx, int nrays, const float* o3, const float* 
   }
   hipLaunchKernelGGL(k_test_closest, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), useBvh, nrays,
                      dO.get(), dD.get(), di.get(), dt.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* time, int32_t* tri_index, float* t,
+                            float* uv2) {
+  if (!ctx || nrays < 0 || !o3 || !d3 || !time || !tri_index || !t) return DMT_ERR_INVALID;
+  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: upload triangles first");
+  if (!ctx->haveMotion) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: no key 1 (dmt_set_motion first)");
+  for (int i = 0; i < nrays; ++i)
+    if (!std::isfinite(time[i])) return fail(ctx, DMT_ERR_INVALID, "dmt_test_closest_hit_at: a time is not finite");
+  if (nrays == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(nrays));
+  ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3), dT(p, time, 1);
+  ProbeOut<int32_t> di(p, tri_index, 1);
+  ProbeOut<float> dt(p, t, 1), duv(p, uv2, 2);  // uv2 optional: null is not copied back
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
+  if (useBvh) HIP_TRY(ctx, reserveOverflow(ctx, p.threads(64)));
+  RenderParams P = baseParams(ctx, p.threads(64));
+  if (int const rc = motionParams(ctx, kFeatMotion | (useBvh ? kFeatBvh : 0u), P)) return rc;
+  hipLaunchKernelGGL(k_test_closest_at, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, useBvh, nrays, dO.get(), dD.get(), dT.get(), di.get(),
+                     dt.get(), duv.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t) {
+  if (!ctx || n < 0 || !pxs || !pys || !ss || !t) return DMT_ERR_INVALID;
+  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_shutter_times: set the camera first");
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
+  ProbeOut<float> dT(p, t, 1);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  hipLaunchKernelGGL(k_test_shutter, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->sp, ctx->shutterOpen, ctx->shutterClose, n, dpx.get(),
+                     dpy.get(), dss.get(), dT.get());
   return finishProbe(ctx, p);
 }
 

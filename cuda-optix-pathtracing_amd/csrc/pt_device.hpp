@@ -502,6 +502,15 @@ __host__ __device__ inline float owen_radical_inverse_plain(uint32_t seed, uint3
   }
   return __builtin_fminf(result, 0.99999994f);
 }
+// ---- motion blur (dmt_set_motion): what the device and the host twins share --------------------------------
+// The time of the sample with Halton index h under the shutter [open, close]: Halton dimension 12 (base 41, the next prime
+// after the lens's 31 and 37) through one explicit fmaf.  In [open, close]: u12 <= 1 - 2^-24 and fl(close - open) <=
+// (close - open)(1 + 2^-24), so the exact sum stays below close and the rounding is monotone.
+__host__ __device__ inline float shutter_time(uint32_t haltonIndex, float open, float close) {
+  return __builtin_fmaf(close - open, owen_radical_inverse_plain<41>(owen_seed(12), haltonIndex), open);
+}
+// a coordinate at time t between its key-0 value a and its key-1 value b: the fp32 difference, then one fmaf
+__host__ __device__ inline float motion_lerp(float t, float a, float b) { return __builtin_fmaf(t, b - a, a); }
 struct LensU {
   float x, y;
 };
@@ -605,6 +614,24 @@ DMT_DEV void mt_core9(float p0x, float p0y, float p0z, float e0x, float e0y, flo
 // in the same order as mt_core9, element by element, so each half is bit-identical to the scalar test.
 DMT_DEV void mt_core9_tri2(v2f p0x, v2f p0y, v2f p0z, v2f e0x, v2f e0y, v2f e0z, v2f e1x, v2f e1y, v2f e1z, float ox,
                            float oy, float oz, float dx, float dy, float dz, v2f& det, v2f& tt, v2f& u, v2f& v) {
+  v2f const cx = fma_(dy, e1z, -(dz * e1y));
+  v2f const cy = fma_(dz, e1x, -(dx * e1z));
+  v2f const cz = fma_(dx, e1y, -(dy * e1x));
+  det = fma_(cz, e0z, fma_(cy, e0y, cx * e0x));
+  v2f const inv = rcp_(det);
+  v2f const ovx = ox - p0x, ovy = oy - p0y, ovz = oz - p0z;
+  v2f const qx = fma_(ovy, e0z, -(ovz * e0y));
+  v2f const qy = fma_(ovz, e0x, -(ovx * e0z));
+  v2f const qz = fma_(ovx, e0y, -(ovy * e0x));
+  u = inv * fma_(cz, ovz, fma_(cy, ovy, cx * ovx));
+  v = inv * fma_(qz, dz, fma_(qy, dy, qx * dx));
+  tt = inv * fma_(qz, e1z, fma_(qy, e1y, qx * e1x));
+}
+// Two rays against a triangle of their OWN each (.x / .y: the motion rows' brute-force pass, where the lane's closest-hit
+// ray and its pending shadow ray may belong to different samples and so see the triangle at different times): again the
+// operations of mt_core9 in its order, element by element.
+DMT_DEV void mt_core9_vv(v2f p0x, v2f p0y, v2f p0z, v2f e0x, v2f e0y, v2f e0z, v2f e1x, v2f e1y, v2f e1z, v2f ox, v2f oy,
+                         v2f oz, v2f dx, v2f dy, v2f dz, v2f& det, v2f& tt, v2f& u, v2f& v) {
   v2f const cx = fma_(dy, e1z, -(dz * e1y));
   v2f const cy = fma_(dz, e1x, -(dx * e1z));
   v2f const cz = fma_(dx, e1y, -(dy * e1x));

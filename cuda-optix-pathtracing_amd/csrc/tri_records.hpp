@@ -35,6 +35,14 @@ struct TriPost {  // 64 B
   uint32_t matId, pad0, pad1, pad2;
 };
 
+// motion blur (dmt_set_motion): the key-1 vertices of a triangle, what the post-hit record of a moving
+// triangle is rebuilt from.  (The intersection side keeps a second TriIsect array: D = B - A, field by field.)
+struct TriKey1 {  // 48 B
+  float p0x, p0y, p0z, p1x;
+  float p1y, p1z, p2x, p2y;
+  float p2z, pad0, pad1, pad2;
+};
+
 // both records of the triangle with vertices v[0..2], v[3..5], v[6..8]
 DMT_HD inline void packTriangle(float const v[9], uint32_t matId, TriIsect& t, TriPost& q) {
   float const e0x = v[3] - v[0], e0y = v[4] - v[1], e0z = v[5] - v[2];

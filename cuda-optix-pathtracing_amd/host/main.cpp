@@ -51,6 +51,9 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   bool aovSppSet = false;
   bool lensRadiusSet = false, focusDistanceSet = false, focusPixelSet = false;  // --lens-radius R, --focus-distance D, --focus-pixel X Y
   float lensRadius = 0.f, focusDistance = 1.f, focusX = 0.f, focusY = 0.f;
+  bool shutterSet = false;    // --shutter OPEN CLOSE: the shutter interval of --motion-scene (dmt_set_shutter)
+  float shutterOpen = 0.f, shutterClose = 1.f;
+  std::string motionScenePath;  // --motion-scene <file>: the same scene at the end of the frame; its triangle positions become key 1
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
 
@@ -91,6 +94,8 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (focusDistanceSet && !(std::isfinite(focusDistance) && focusDistance > 0.f)) return "invalid --focus-distance: expected a finite distance > 0";
     if (focusDistanceSet && focusPixelSet) return "--focus-distance and --focus-pixel exclude each other";
     if (focusPixelSet && !(focusX >= 0.f && focusX < float(width) && focusY >= 0.f && focusY < float(height))) return "invalid --focus-pixel: outside the frame";
+    if (shutterSet && !(std::isfinite(shutterOpen) && std::isfinite(shutterClose) && 0.f <= shutterOpen && shutterOpen <= shutterClose && shutterClose <= 1.f))
+      return "invalid --shutter: expected 0 <= OPEN <= CLOSE <= 1";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
   }
@@ -132,7 +137,11 @@ void printHelp() {
       "  --lens-radius <R> -- Thin lens of radius R in scene units: depth of field (0, the default, is the pinhole; a scene\n"
       "                       file's own lens applies unless given here)\n"
       "  --focus-distance <D> -- Depth along the viewing direction, in scene units, that the lens renders sharp\n"
-      "  --focus-pixel <X> <Y> -- Autofocus: focus on what the centre of pixel (X, Y) shows, and print the distance chosen");
+      "  --focus-pixel <X> <Y> -- Autofocus: focus on what the centre of pixel (X, Y) shows, and print the distance chosen\n"
+      "  --motion-scene <file> -- Motion blur: a second scene file of the same kind as --scene whose triangle positions are\n"
+      "                       where the triangles are at the end of the frame (same triangles, same order); every sample\n"
+      "                       sees the scene at its own time in between\n"
+      "  --shutter <OPEN> <CLOSE> -- The part of the frame the shutter is open, 0 <= OPEN <= CLOSE <= 1 (default 0 1)");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -157,6 +166,8 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--lens-radius" && more) c.lensRadius = std::strtof(argv[++i], nullptr), c.lensRadiusSet = true;
     else if (a == "--focus-distance" && more) c.focusDistance = std::strtof(argv[++i], nullptr), c.focusDistanceSet = true;
     else if (a == "--focus-pixel" && i + 2 < argc) c.focusX = std::strtof(argv[++i], nullptr), c.focusY = std::strtof(argv[++i], nullptr), c.focusPixelSet = true;
+    else if (a == "--shutter" && i + 2 < argc) c.shutterOpen = std::strtof(argv[++i], nullptr), c.shutterClose = std::strtof(argv[++i], nullptr), c.shutterSet = true;
+    else if (a == "--motion-scene" && more) c.motionScenePath = argv[++i];
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -230,6 +241,31 @@ int main(int argc, char** argv) {
     if (!cfg.depthSet) cfg.maxDepth = json.maxDepth;
     if (cfg.kspp > cfg.spp) cfg.kspp = cfg.spp;
   }
+  dmt_host::Scene key1;  // --motion-scene: only its triangle positions are used
+  if (!cfg.motionScenePath.empty()) {
+    std::string err;
+    std::string const& path = cfg.motionScenePath;
+    bool ok;
+    if (path.size() > 5 && path.compare(path.size() - 5, 5, ".pbrt") == 0) {
+      dmt_host::PbrtScene ps;
+      ok = dmt_host::loadPbrtScene(path, ps, &err);
+      key1 = std::move(ps.scene);
+    } else {
+      dmt_host::JsonScene js;
+      ok = dmt_host::loadJsonScene(path, js, &err);
+      key1 = std::move(js.scene);
+    }
+    if (!ok) {
+      std::fprintf(stderr, "motion scene '%s': %s\n", path.c_str(), err.c_str());
+      return 1;
+    }
+    size_t const want = cfg.scenePath.empty() ? dmt_host::cornellBox().triangleCount() : json.scene.triangleCount();
+    if (key1.triangleCount() != want) {
+      std::fprintf(stderr, "motion scene '%s': %zu triangles, the scene has %zu: key 1 must move the same triangles\n", path.c_str(),
+                   key1.triangleCount(), want);
+      return 1;
+    }
+  }
   if (std::string const err = cfg.validate(); !err.empty()) {
     std::fprintf(stderr, "%s\n", err.c_str());
     printHelp();
@@ -263,6 +299,9 @@ int main(int argc, char** argv) {
     if (cfg.lightTree && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
     if (cfg.lightTreeRef && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
     if (cfg.textureFilter && dmt_set_texture_filter(ctx, DMT_TEXFILTER_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_texture_filter");
+    if (cfg.shutterSet && dmt_set_shutter(ctx, cfg.shutterOpen, cfg.shutterClose) != DMT_OK) return fail(ctx, "dmt_set_shutter");
+    if (!cfg.motionScenePath.empty() && dmt_set_motion(ctx, key1.xs.data(), key1.ys.data(), key1.zs.data(), key1.triangleCount()) != DMT_OK)
+      return fail(ctx, "dmt_set_motion");
   }
   if (cfg.focusPixelSet) {  // autofocus on the first context (every context holds the whole scene), then the lens of all
     float d = 0.f;

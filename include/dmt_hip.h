@@ -119,6 +119,63 @@ int dmt_lens_rays(const dmt_camera* cam, float lens_radius, float focus_distance
  * current accel mode; *distance = the hit's depth along the viewing direction, what dmt_set_lens takes as focus_distance.
  * DMT_ERR_STATE when the ray leaves the scene.  Synchronous. */
 int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance);
+
+/* ---- motion blur: linear vertex motion over a shutter interval (opt-in, beyond the reference) ---- */
+/* Keys.  Key 0 is the positions the context holds (dmt_upload_triangles, dmt_update_vertices*).  Key 1 is a second position
+ * set for the same triangles (dmt_set_motion).  Motion is active exactly when key 1 is present; without it every film is
+ * byte for byte what it was before these calls existed, whatever the shutter.
+ *
+ * Time of a sample.  Sample s of pixel (px, py) has Halton index h.  It draws u12 = the Owen-scrambled radical inverse of h
+ * in base 41 (Halton dimension 12; the lens holds 10 and 11, the path 2..9, none of which moves) and its time is
+ *   t = fmaf(close - open, u12, open)                          [open, close] the shutter, default [0, 1]
+ * Every ray of that sample's path sees the scene at t: the camera ray, the bounce rays and the shadow rays.  open == close
+ * pins every sample to one time.
+ *
+ * The triangle at time t, once for every path.  A = the key-0 intersection record (p0, e0 = p1 - p0, e1 = p2 - p0 in fp32),
+ * B = the same record of key 1, D = B - A component by component in fp32 (made at dmt_set_motion).  The nine floats of the
+ * tested triangle are fmaf(t, D, A).  Brute force and the BVH rebuild it from the same two records with the same fmaf, so
+ * they return bit-identical hits (tri, t, u, v), as they do for static triangles.  For the post-hit record the vertices are
+ *   p_i(t) = fmaf(t, P1_i - P0_i, P0_i)
+ * and the geometric normal is normalize(cross(e1, e0)) of those vertices, in the order of operations of the static record,
+ * with the device's arithmetic (no contraction, v_rsq_f32).  Material ids and everything else come from key 0.
+ *
+ * The BVH.  Launches with key 1 traverse a second tree, built by the host SAH builder over each triangle's UNION box of both
+ * keys -- whatever dmt_set_accel_build says; the device builder and the refit know one key -- when key 1 arrives under
+ * DMT_ACCEL_BVH or a BVH launch first needs it.  The static tree stays as it is.
+ *
+ * Scope.  Motion has the plain and the env-map megakernel rows, under both accel modes: dmt_render (partitions, chunks),
+ * dmt_render_adaptive, dmt_test_trace_samples / dmt_test_trace_log, and the feature pass dmt_render_aovs, which traces at the
+ * samples' times so its planes blur where the film does.  Motion launches compute their samples (no sampler table), so
+ * films do not depend on dmt_set_sampler_table.  The brute-force pass of a motion launch is the plain loop over every
+ * triangle (the culled clusters' bounds are of key 0).  Refused with DMT_ERR_STATE and a message that names the
+ * combination: motion with emissive triangles, with image textures or blend materials, with either light tree, with the
+ * first-hit texture filter, with dmt_render_stats / dmt_render_profile, with the wavefront BVH strategy.
+ * Left on key 0: dmt_focus_distance_at, dmt_test_closest_hit, and the temporal denoiser's motion vectors. */
+/* Key 1.  Layout as dmt_upload_triangles (4 floats per triangle and axis).  DMT_ERR_STATE before any upload, DMT_ERR_INVALID
+ * when count differs from the uploaded triangle count or a position is not finite.  Synchronises the stream first.
+ * Dropped by dmt_upload_triangles, dmt_update_vertices and dmt_update_vertices_device: the positions it was a motion from
+ * are gone. */
+int dmt_set_motion(dmt_ctx* ctx, const float* xs1, const float* ys1, const float* zs1, size_t count);
+/* drops key 1; every film is then byte for byte what it was before dmt_set_motion */
+int dmt_clear_motion(dmt_ctx* ctx);
+/* the shutter: finite 0 <= open <= close <= 1, DMT_ERR_INVALID otherwise.  Survives scene uploads and dmt_set_camera, like
+ * the lens.  No effect without key 1. */
+int dmt_set_shutter(dmt_ctx* ctx, float open, float close);
+/* *keys = 0 before an upload, 1, or 2 with key 1; the shutter; the motion tree's node and pair count and the host time of
+ * its build in ms (zeros while no BVH launch has needed it).  Any pointer may be null. */
+int dmt_motion_info(dmt_ctx* ctx, int* keys, float* open, float* close, uint32_t* tree_nodes, uint32_t* tree_pairs, double* tree_build_ms);
+/* host only (no GPU): the times of samples ss of pixels (pxs, pys) of a width x height frame under the shutter, the device's
+ * bit for bit (integer arithmetic and explicit fmaf).  DMT_ERR_INVALID for a pixel outside the frame, a negative sample or
+ * a shutter dmt_set_shutter would refuse. */
+int dmt_shutter_times(int width, int height, float open, float close, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss,
+                      float* t);
+/* host only (no GPU): the vertices at time t (finite), p_i(t) above, the device's bit for bit; layout as the inputs */
+int dmt_motion_positions(const float* xs0, const float* ys0, const float* zs0, const float* xs1, const float* ys1, const float* zs1,
+                         size_t count, float t, float* xs, float* ys, float* zs);
+/* host only (no GPU): builds the motion tree of the two keys and checks dmt_bvh_validate's invariants against BOTH: every
+ * decoded child box contains the vertices below it at key 0 and at key 1.  DMT_ERR_STATE when one fails. */
+int dmt_motion_bvh_validate(const float* xs0, const float* ys0, const float* zs0, const float* xs1, const float* ys1, const float* zs1,
+                            size_t count, int* node_count, int* pair_count, int* depth);
 /* depth cap of the bounce loop; the reference hard-codes 32 (megakernel.cu:154) */
 int dmt_set_limits(dmt_ctx* ctx, int max_depth);
 int dmt_set_accel(dmt_ctx* ctx, int mode);
@@ -518,6 +575,13 @@ int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t*
                          const int32_t* ss, float* o3, float* d3);
 /* the lens values (u10, u11) of the samples, lens2 (n x 2), as the device computes them */
 int dmt_test_lens_values(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* lens2);
+/* the times of the samples under the context's shutter, as the motion rows compute them: the device twin of dmt_shutter_times */
+int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t);
+/* closest hit of ray i against the scene at time[i], under the current accel mode (the motion tree for DMT_ACCEL_BVH):
+ * tri_index (-1: none), t (+inf: none) and, when uv2 is not null, the barycentrics (n x 2).  DMT_ERR_STATE without key 1.
+ * dmt_test_closest_hit keeps answering for key 0. */
+int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* time, int32_t* tri_index, float* t,
+                            float* uv2);
 /* dmt_camera_project on the device, under the camera of dmt_set_camera */
 int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, float* depth);
 int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* wo3,
