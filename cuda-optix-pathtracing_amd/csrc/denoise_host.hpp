@@ -2,7 +2,8 @@
 // a-trous filter and temporal accumulation, and the rules that keep the temporal history and its raw-vertex mirror valid.
 //
 // Part of dmt_hip.hip's translation unit, included once after the host helpers it uses (dmt_ctx, HIP_TRY, fail, baseParams,
-// reserveOverflow, checkErrorFlag, cameraFromRaster, worldFromCamera) and before the first entry point that calls into it.
+// checkErrorFlag, cameraFromRaster, worldFromCamera; accel_host.hpp's requireTree, reserveOverflow, motionParams) and before
+// the first entry point that calls into it.  accel_host.hpp forward-declares the two mirror calls below for its vertex updates.
 // The rest of the library reaches DenoiseState through dropHistory / dropVertexMirror and the two mirror calls below.
 #pragma once
 
@@ -218,7 +219,7 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   if (ctx->texCount > 0 && (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount))
     return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
-  if (useBvh && !ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: BVH not built");
+  if (int const rcT = useBvh ? requireTree(ctx, "dmt_render_aovs") : DMT_OK) return rcT;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
   ctx->dn.aovW = ctx->dn.aovH = 0;  // no AOVs unless this call succeeds
@@ -236,9 +237,9 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   A.surface = ctx->dn.surface.get();
   A.width = ctx->filmW, A.pixels = uint32_t(pixels), A.aovSpp = aov_spp, A.useBvh = useBvh;
   RenderParams P = baseParams(ctx, threads);
-  uint32_t const motionMask = ctx->haveMotion ? kFeatMotion | (useBvh ? kFeatBvh : 0u) : 0u;  // the samples' times, as the film's rows
+  uint32_t const motionMask = ctx->ac.haveMotion ? kFeatMotion | (useBvh ? kFeatBvh : 0u) : 0u;  // the samples' times, as the film's rows
   if (int const rcM = motionParams(ctx, motionMask, P)) return rcM;
-  hipLaunchKernelGGL(ctx->haveMotion ? k_aov_motion : k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
+  hipLaunchKernelGGL(ctx->ac.haveMotion ? k_aov_motion : k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
   HIP_TRY(ctx, hipGetLastError());
   ctx->dn.aovW = ctx->filmW, ctx->dn.aovH = ctx->filmH;
   ctx->dn.aovSurface = true;

@@ -2274,6 +2274,8 @@ static SamplerTablePlan samplerTablePlan(int width, int height, uint64_t ownedPi
   return p;
 }
 
+#include "accel_state.hpp"
+
 struct dmt_ctx {
   int device = 0;
   hipStream_t ownStream = nullptr;
@@ -2287,32 +2289,11 @@ struct dmt_ctx {
   uint32_t maxMatId = 0;
   // the brute-force pass's culled clusters (planBruteCull, planBruteCullBox); none: the pass tests d_tris for every ray
   int bruteCull = 2;  // DMT_BRUTE_CULL at context creation (A/B runs, tests): 0 no clusters, 1 sphere clusters only, unset both
-  DevBuf<TriIsect> d_cullAlways;
-  DevBuf<uint32_t> d_cullIdx;
-  DevBuf<CullCluster> d_cullClusters;
-  DevBuf<float> d_cullTri9;
-  uint32_t cullAlwaysCount = 0, cullClusterCount = 0;
-  // BVH (built on demand for DMT_ACCEL_BVH)
-  std::vector<float> h_xs, h_ys, h_zs;  // host copy of the soup (the builder's input)
+  CullTables cull;
+  std::vector<float> h_xs, h_ys, h_zs;  // host copy of the soup (the builders' input)
   std::vector<uint32_t> h_mat;
-  DevBuf<Bvh4Node> d_bvhNodes;
-  int shadeThresholdEnv = 0;  // DMT_BVH_SHADE_THRESHOLD from the environment, 0 = choose by tree size
-  DevBuf<TriPair> d_trisBvh;   // leaf storage of the BVH
-  DevBuf<uint32_t> d_overflow;  // kBvhOverflowStack words per thread
-  bool haveBvh = false;
-  int bvhDepth = 0;
-  uint32_t bvhNodeCount = 0, bvhPairCount = 0;
-  int blocksPerCUBvh = 0;
-  int accelBuild = DMT_BVH_BUILD_HOST;   // dmt_set_accel_build: who builds the tree
-  dmt_accel_build_record buildRecord{};  // of the current tree (dmt_accel_build_info)
-  lbvh_gpu::Scratch lbvhScratch;         // temporaries of the device builder, reused across builds
-  // dmt_update_vertices: what an update does to the tree (dmt_set_accel_update), the record of the last one
-  std::vector<uint32_t> bvhLevels;       // first node of every 4-wide level of the current tree, then its node count
-  int accelUpdate = DMT_BVH_UPDATE_REBUILD;
-  double maxCostRatio = 0.0;             // DMT_BVH_UPDATE_AUTO's bound
-  dmt_accel_update_record updateRecord{};
-  bool costAtBuildKnown = false;         // updateRecord.sah_cost_at_build is of the current topology
-  lbvh_gpu::RefitScratch refitScratch;   // boxes and cost terms of a refit, reused across updates
+  // the acceleration layer: the static and the motion tree, builder and update policy, key 1 (accel_state.hpp, accel_host.hpp)
+  AccelState ac;
   // light tree (light_tree.hpp): built from the uploaded lights when dmt_set_light_sampling asks for it
   int lightSampling = DMT_LIGHTS_UNIFORM;
   std::vector<uint8_t> h_lights;  // host copy of the packed light records
@@ -2357,21 +2338,6 @@ struct dmt_ctx {
   CameraXf xf{};
   SamplerParams sp{};
   float lensR = 0.f, lensD = 1.f;  // thin lens (dmt_set_lens): radius 0 = pinhole; survives dmt_set_camera and scene uploads
-  // motion blur (dmt_set_motion).  Key 0 is the soup above; key 1 lives here and is dropped with it.  The
-  // motion tree is a second tree beside the static one (which stays as it is: dmt_clear_motion restores every film byte
-  // for byte), built by the host SAH builder over both keys' boxes when a BVH launch first needs it.
-  bool haveMotion = false;
-  float shutterOpen = 0.f, shutterClose = 1.f;  // dmt_set_shutter: survives scene uploads and dmt_set_camera, like the lens
-  std::vector<float> h_xs1, h_ys1, h_zs1;       // key 1 (the motion tree's input)
-  DevBuf<TriIsect> d_dtris;                     // D = B - A per triangle
-  DevBuf<TriKey1> d_post1;                      // key-1 vertices
-  DevBuf<Bvh4Node> d_mNodes;                    // the motion tree, its key-0 pairs and their deltas
-  DevBuf<TriPair> d_mPairs;
-  DevBuf<TriPairDelta> d_mDelta;
-  bool haveMotionTree = false;
-  uint32_t mNodeCount = 0, mPairCount = 0;
-  int mDepth = 0;
-  double mBuildMs = 0.0;
   // film: the context's own, or the caller's after dmt_film_bind (which frees the own one)
   DevBuf<float4> ownMean, ownM2;
   float4* d_mean = nullptr;
@@ -2402,7 +2368,6 @@ struct dmt_ctx {
   int rank = 0, world = 1;
   // launch geometry
   int cuCount = 0;
-  int blocksPerCU = 0;
   // timing
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t eventsUsed = 0;
@@ -2734,7 +2699,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (treeable && c->lightSampling == DMT_LIGHTS_TREE) F |= kFeatLightTree;
   if (treeable && c->lightSampling == DMT_LIGHTS_TREE_REFERENCE) F |= kFeatLightTreeRef;
   if (c->texFilter == DMT_TEXFILTER_REFERENCE && (F & (kFeatTex | kFeatBlend))) F |= kFeatTexFilter;
-  if (c->haveMotion) F |= kFeatMotion;
+  if (c->ac.haveMotion) F |= kFeatMotion;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2767,6 +2732,25 @@ int checkFeatures(dmt_ctx* ctx, uint32_t F) {
   return DMT_OK;
 }
 
+// ---- what dmt_upload_triangles and dmt_update_vertices share ----
+// both records of every triangle of a soup (tri_records.hpp; the record kernel of dmt_update_vertices_device runs the same function)
+void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count, std::vector<TriIsect>& a,
+              std::vector<TriPost>& b) {
+  a.resize(count), b.resize(count);
+  for (size_t i = 0; i < count; ++i) {
+    float const v[9] = {xs[4 * i], ys[4 * i], zs[4 * i], xs[4 * i + 1], ys[4 * i + 1], zs[4 * i + 1], xs[4 * i + 2], ys[4 * i + 2], zs[4 * i + 2]};
+    packTriangle(v, mat[i], a[i], b[i]);
+  }
+}
+
+}  // namespace
+
+// the acceleration layer: the trees, their builders and updates, key 1 of the motion, the cull tables; the helpers below,
+// denoise_host.hpp and probes.hpp call into it
+#include "accel_host.hpp"
+
+namespace {
+
 SceneView sceneView(dmt_ctx const* c) {
   SceneView s;
   s.tris = c->d_tris.get(), s.post = c->d_post.get(), s.bsdfs = c->d_bsdfs.get(), s.lights = c->d_lights.get();
@@ -2776,45 +2760,17 @@ SceneView sceneView(dmt_ctx const* c) {
   return s;
 }
 
-BvhView bvhView(dmt_ctx const* c, size_t threads) {
-  BvhView b;
-  b.nodes = c->d_bvhNodes.get(), b.pairs = c->d_trisBvh.get(), b.overflow = c->d_overflow.get();
-  b.overflowStride = uint32_t(threads);
-  return b;
-}
-
-// BVH megakernel: how many lanes of a wave must have finished their rays before the wave stops traversing and shades
-// (megakernel_body_bvh, step C).  Traversing lanes idle while the wave shades and finished lanes idle while it traverses, so
-// the best value follows the cost ratio of the two -- low where rays take hundreds of steps, high where the tree is shallow
-// and shading dominates.  Measured on MI355X, Msamples/s by threshold (profiles/r03/shade_threshold_sweep.txt):
-//   Cornell box, 6 nodes, depth 3             32: 1 923   48: 2 184   56: 2 266   60: 2 244   64: 2 053
-//   sphere.fbx + veranda, 123 nodes, depth 5  32: 6 867   48: 7 416   56: 7 683   64: 7 800
-//   tessellated sphere, 4 588 nodes, depth 10 32: 3 043   48: 3 381   52: 3 399   56: 3 365   64: 2 748
-//   1 M random triangles, 300 k nodes         28: 490     32: 489     36: 485     40: 473     48: 452
-//   16 M random triangles                     24: 435     28: 439     32: 437     36: 436
-// The step between 16 k and 128 k nodes is interpolated, not measured.  DMT_BVH_SHADE_THRESHOLD in the environment overrides
-// the choice (tuning runs).  Results do not depend on it.
-int bvhShadeThreshold(dmt_ctx const* c) {
-  if (c->shadeThresholdEnv > 0) return c->shadeThresholdEnv;
-  uint32_t const n = c->bvhNodeCount;
-  return n <= 1024u ? 56 : n <= 16384u ? 52 : n <= 131072u ? 40 : DMT_BVH_SHADE_THRESHOLD;
-}
 // scene / camera / limits part of the argument struct (what the path-tracing device code reads)
 RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   RenderParams P{};
   P.scene = sceneView(c);
-  if (c->cullClusterCount > 0) {
-    P.cull.always = c->d_cullAlways.get(), P.cull.alwaysIdx = c->d_cullIdx.get(), P.cull.clusters = c->d_cullClusters.get();
-    P.cull.tri9 = c->d_cullTri9.get(), P.cull.alwaysCount = c->cullAlwaysCount, P.cull.clusterCount = c->cullClusterCount;
-  } else {
-    P.cull.always = c->d_tris.get(), P.cull.alwaysCount = c->triCount;
-  }
+  P.cull = cullView(c);
   P.bvh = bvhView(c, threads);
   P.cam = c->xf;
   P.sp = c->sp;
   P.lensR = c->lensR, P.lensD = c->lensD;
   P.maxDepth = c->maxDepth;
-  P.shadeThreshold = bvhShadeThreshold(c);
+  P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   P.env = c->env;
   P.areaOf = c->d_areaOf.get(), P.areaTri = c->d_areaTri.get(), P.areaLe = c->d_areaLe.get(), P.areaCount = c->areaCount;
   if (c->texCount > 0) {
@@ -2860,287 +2816,6 @@ int blocksPerCuOf(dmt_ctx* c, MegakernelFn kernel) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, 0) != hipSuccess || n <= 0) n = 1;
   c->occupancy.emplace_back(fn, n);
   return n;
-}
-
-// BVH traversal-stack overflow area for `threads` threads
-hipError_t reserveOverflow(dmt_ctx* ctx, size_t threads) { return ctx->d_overflow.reserve(threads * size_t(kBvhOverflowStack)); }
-
-// a builder made a new topology: the update record counts refits from here, costs are of the tree before
-void treeBuilt(dmt_ctx* ctx) {
-  ctx->updateRecord.updates_since_build = 0;
-  ctx->updateRecord.sah_cost = ctx->updateRecord.sah_cost_at_build = 0.0;
-  ctx->costAtBuildKnown = false;
-}
-
-// (re)build the 4-wide BVH of the uploaded soup on the host and upload nodes + triangle pairs
-int buildBvhHost(dmt_ctx* ctx, int builder) {
-  uint32_t const n = ctx->triCount;
-  auto const t0 = std::chrono::steady_clock::now();
-  bvh_build::Result r = bvh_build::build(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), n);
-  // leaf storage: triangle pairs (bvh.hpp TriPair).  Edges are the reference's own subtractions
-  // (CC/private/shapes.cu:10-11) in IEEE fp32.
-  size_t const npairs = r.pairTris.size() / 2;
-  if (npairs > 0x7FFFFFFFull || r.nodes.size() > 0x7FFFFFFFull) return fail(ctx, DMT_ERR_INVALID, "BVH: too many nodes / triangle pairs");
-  // + 3 guard pairs (copies of the last one).  An EMPTY child slot holds an inverted quantised box and no reference of its
-  // own; its slab test misses by itself except in one corner: a ray exactly parallel to an axis through a node that is flat
-  // on the remaining axes (255 quantisation steps below half an ulp of the plane distance), where near == far.  The slot's
-  // implicit reference is then leafRef + slot, i.e. a pair of the NEXT node -- or, for the last node, up to three
-  // pairs past the array.  Testing some real triangle of the scene once more changes no result (the triangle test decides
-  // hits, and a scene triangle is a scene triangle); reading past the array would, hence the guards.
-  std::vector<TriPair> pairs(npairs ? npairs + 3 : 0);
-  for (size_t p = 0; p < npairs; ++p)
-    for (int half = 0; half < 2; ++half) {
-      uint32_t const i = r.pairTris[2 * p + size_t(half)];
-      float const* xs = &ctx->h_xs[4 * size_t(i)];
-      float const* ys = &ctx->h_ys[4 * size_t(i)];
-      float const* zs = &ctx->h_zs[4 * size_t(i)];
-      TriPair& P = pairs[p];
-      P.p0x[half] = xs[0], P.p0y[half] = ys[0], P.p0z[half] = zs[0];
-      P.e0x[half] = xs[1] - xs[0], P.e0y[half] = ys[1] - ys[0], P.e0z[half] = zs[1] - zs[0];
-      P.e1x[half] = xs[2] - xs[0], P.e1y[half] = ys[2] - ys[0], P.e1z[half] = zs[2] - zs[0];
-      P.orig[half] = i;
-    }
-  for (size_t p = npairs; p < pairs.size(); ++p) pairs[p] = pairs[npairs - 1];
-  DevBuf<Bvh4Node> nodes;
-  DevBuf<TriPair> leaves;
-  HIP_TRY(ctx, nodes.assign(r.nodes.data(), r.nodes.size()));
-  HIP_TRY(ctx, leaves.assign(pairs.data(), pairs.size()));
-  ctx->d_bvhNodes = std::move(nodes), ctx->d_trisBvh = std::move(leaves);
-  ctx->bvhDepth = r.depth;
-  ctx->bvhNodeCount = uint32_t(r.nodes.size());
-  ctx->bvhPairCount = uint32_t(npairs);
-  ctx->haveBvh = true;
-  ctx->bvhLevels = refit::levelBounds(r.nodes.data(), r.nodes.size());
-  treeBuilt(ctx);
-  dmt_accel_build_record& R = ctx->buildRecord;
-  R = dmt_accel_build_record{};
-  R.builder = builder;
-  R.triangles = n, R.nodes = ctx->bvhNodeCount, R.pairs = ctx->bvhPairCount, R.depth = r.depth;
-  R.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();  // build, pair packing, copies
-  return DMT_OK;
-}
-
-// the tree of the uploaded soup, by the builder dmt_set_accel_build chose
-int buildBvh(dmt_ctx* ctx) {
-  if (ctx->accelBuild != DMT_BVH_BUILD_DEVICE) return buildBvhHost(ctx, DMT_BVH_BUILT_BY_HOST);
-  static_assert(sizeof(TriPost) == 64 && offsetof(TriPost, p2z) == 32, "the device builder reads p0, p1, p2 as nine consecutive floats");
-  lbvh_gpu::Result r;
-  std::string what;
-  hipError_t const e = lbvh_gpu::build(reinterpret_cast<float const*>(ctx->d_post.get()), uint32_t(sizeof(TriPost) / sizeof(float)),
-                                       ctx->triCount, kBvhMaxDepth, ctx->stream, ctx->lbvhScratch, r, what);
-  if (e != hipSuccess) {  // an error, not a silent host build
-    ctx->err = "device BVH build: " + what + ": " + hipGetErrorName(e) + " - " + hipGetErrorString(e);
-    return DMT_ERR_HIP;
-  }
-  if (r.abandoned) {  // the depth guard: the traversal stack is sized by kBvhMaxDepth
-    float const lostMs = r.ms;
-    int const rc = buildBvhHost(ctx, DMT_BVH_BUILT_BY_HOST_AFTER_DEVICE);
-    if (rc == DMT_OK) ctx->buildRecord.build_ms += double(lostMs), ctx->buildRecord.temp_bytes = r.tempBytes;
-    return rc;
-  }
-  if (r.pairCount > 0x7FFFFFFFull || r.nodeCount > 0x7FFFFFFFull) return fail(ctx, DMT_ERR_INVALID, "BVH: too many nodes / triangle pairs");
-  ctx->d_bvhNodes = std::move(r.nodes), ctx->d_trisBvh = std::move(r.pairs);
-  ctx->bvhDepth = r.depth;
-  ctx->bvhNodeCount = r.nodeCount, ctx->bvhPairCount = r.pairCount;
-  ctx->haveBvh = true;
-  ctx->bvhLevels = std::move(r.levels);
-  treeBuilt(ctx);
-  dmt_accel_build_record& R = ctx->buildRecord;
-  R = dmt_accel_build_record{};
-  R.builder = DMT_BVH_BUILT_BY_DEVICE;
-  R.triangles = ctx->triCount, R.nodes = r.nodeCount, R.pairs = r.pairCount, R.depth = r.depth;
-  R.build_ms = double(r.ms), R.temp_bytes = r.tempBytes;
-  return DMT_OK;
-}
-
-// ---- motion blur: key 1 on the host side ----
-void dropMotion(dmt_ctx* ctx) {  // the positions key 1 was a motion FROM are going away
-  ctx->haveMotion = false, ctx->haveMotionTree = false;
-  ctx->h_xs1.clear(), ctx->h_ys1.clear(), ctx->h_zs1.clear();
-  ctx->d_dtris.reset(), ctx->d_post1.reset(), ctx->d_mNodes.reset(), ctx->d_mPairs.reset(), ctx->d_mDelta.reset();
-  ctx->mNodeCount = ctx->mPairCount = 0, ctx->mDepth = 0, ctx->mBuildMs = 0.0;
-}
-// The motion tree: the host SAH builder over every triangle's union box of both keys, whatever dmt_set_accel_build says (the
-// device builder and the refit know one key).  Leaves: the key-0 pair and D = (key-1 pair) - (key-0 pair) field by field, the
-// numbers of d_tris / d_dtris in the pairs' interleaving, each array with the three guard records of buildBvhHost.
-int ensureMotionTree(dmt_ctx* ctx) {
-  if (ctx->haveMotionTree) return DMT_OK;
-  uint32_t const n = ctx->triCount;
-  auto const t0 = std::chrono::steady_clock::now();
-  bvh_build::Result r = bvh_build::build(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), n, ctx->h_xs1.data(), ctx->h_ys1.data(), ctx->h_zs1.data());
-  size_t const npairs = r.pairTris.size() / 2;
-  if (npairs > 0x7FFFFFFFull || r.nodes.size() > 0x7FFFFFFFull) return fail(ctx, DMT_ERR_INVALID, "motion BVH: too many nodes / triangle pairs");
-  std::vector<TriPair> pairs(npairs ? npairs + 3 : 0);
-  std::vector<TriPairDelta> deltas(pairs.size());
-  auto verts = [](std::vector<float> const& xs, std::vector<float> const& ys, std::vector<float> const& zs, uint32_t i, float v[9]) {
-    for (int c = 0; c < 3; ++c) v[3 * c] = xs[4 * size_t(i) + c], v[3 * c + 1] = ys[4 * size_t(i) + c], v[3 * c + 2] = zs[4 * size_t(i) + c];
-  };
-  for (size_t p = 0; p < npairs; ++p) {
-    TriPair B{};
-    for (int half = 0; half < 2; ++half) {
-      uint32_t const i = r.pairTris[2 * p + size_t(half)];
-      float v0[9], v1[9];
-      verts(ctx->h_xs, ctx->h_ys, ctx->h_zs, i, v0), verts(ctx->h_xs1, ctx->h_ys1, ctx->h_zs1, i, v1);
-      refit::packPairHalf(pairs[p], half, v0, i), refit::packPairHalf(B, half, v1, i);
-    }
-    TriPair const& A = pairs[p];
-    TriPairDelta& D = deltas[p];
-    for (int h = 0; h < 2; ++h) {
-      D.p0x[h] = B.p0x[h] - A.p0x[h], D.p0y[h] = B.p0y[h] - A.p0y[h], D.p0z[h] = B.p0z[h] - A.p0z[h];
-      D.e0x[h] = B.e0x[h] - A.e0x[h], D.e0y[h] = B.e0y[h] - A.e0y[h], D.e0z[h] = B.e0z[h] - A.e0z[h];
-      D.e1x[h] = B.e1x[h] - A.e1x[h], D.e1y[h] = B.e1y[h] - A.e1y[h], D.e1z[h] = B.e1z[h] - A.e1z[h];
-    }
-    D.pad[0] = D.pad[1] = 0;
-  }
-  for (size_t p = npairs; p < pairs.size(); ++p) pairs[p] = pairs[npairs - 1], deltas[p] = deltas[npairs - 1];
-  DevBuf<Bvh4Node> nodes;
-  DevBuf<TriPair> leaves;
-  DevBuf<TriPairDelta> dl;
-  HIP_TRY(ctx, nodes.assign(r.nodes.data(), r.nodes.size()));
-  HIP_TRY(ctx, leaves.assign(pairs.data(), pairs.size()));
-  HIP_TRY(ctx, dl.assign(deltas.data(), deltas.size()));
-  ctx->d_mNodes = std::move(nodes), ctx->d_mPairs = std::move(leaves), ctx->d_mDelta = std::move(dl);
-  ctx->mNodeCount = uint32_t(r.nodes.size()), ctx->mPairCount = uint32_t(npairs), ctx->mDepth = r.depth;
-  ctx->mBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ctx->haveMotionTree = true;
-  return DMT_OK;
-}
-// What a launch of a *_motion kernel reads beside baseParams: the delta records, key 1, the shutter, and for a BVH mask the
-// motion tree in place of the static one (after the caller has set P.bvh's overflow stack for its launch).
-int motionParams(dmt_ctx* ctx, uint32_t F, RenderParams& P) {
-  if (!(F & kFeatMotion)) return DMT_OK;
-  P.motion.dtris = ctx->d_dtris.get(), P.motion.post1 = ctx->d_post1.get();
-  P.motion.open = ctx->shutterOpen, P.motion.close = ctx->shutterClose;
-  if (F & kFeatBvh) {
-    if (int const rc = ensureMotionTree(ctx)) return rc;
-    P.bvh.nodes = ctx->d_mNodes.get(), P.bvh.pairs = ctx->d_mPairs.get(), P.motion.pairDelta = ctx->d_mDelta.get();
-    if (ctx->shadeThresholdEnv <= 0) {  // bvhShadeThreshold's steps, by the motion tree's size
-      uint32_t const n = ctx->mNodeCount;
-      P.shadeThreshold = n <= 1024u ? 56 : n <= 16384u ? 52 : n <= 131072u ? 40 : DMT_BVH_SHADE_THRESHOLD;
-    }
-  }
-  return DMT_OK;
-}
-
-// ---- what dmt_upload_triangles and dmt_update_vertices share ----
-// both records of every triangle of a soup (tri_records.hpp; the record kernel of dmt_update_vertices_device runs the same function)
-void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count, std::vector<TriIsect>& a,
-              std::vector<TriPost>& b) {
-  a.resize(count), b.resize(count);
-  for (size_t i = 0; i < count; ++i) {
-    float const v[9] = {xs[4 * i], ys[4 * i], zs[4 * i], xs[4 * i + 1], ys[4 * i + 1], zs[4 * i + 1], xs[4 * i + 2], ys[4 * i + 2], zs[4 * i + 2]};
-    packTriangle(v, mat[i], a[i], b[i]);
-  }
-}
-
-// the culled clusters of the brute-force pass for a soup, by the context's DMT_BRUTE_CULL setting
-std::vector<CullCluster> planCullClusters(dmt_ctx const* ctx, float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
-  // a closest-hit key holds the original index in 26 bits: no culling for larger soups
-  std::vector<CullCluster> clusters = planBruteCull(xs, ys, zs, mat, uint32_t(count), ctx->bruteCull >= 1 && count < kCullMaxIndex, nullptr);
-  if (ctx->bruteCull >= 2 && count < kCullMaxIndex) {
-    std::vector<CullCluster> const boxes = planBruteCullBox(xs, ys, zs, mat, uint32_t(count), clusters);
-    clusters.insert(clusters.end(), boxes.begin(), boxes.end());
-  }
-  return clusters;
-}
-
-// device tables of a cluster plan; a = the soup's TriIsect records (read only when there are clusters)
-struct CullTables {
-  DevBuf<TriIsect> always;
-  DevBuf<uint32_t> idx;
-  DevBuf<CullCluster> clusters;
-  DevBuf<float> tri9;
-  uint32_t alwaysCount = 0, clusterCount = 0;
-};
-int uploadCullTables(dmt_ctx* ctx, std::vector<CullCluster> const& clusters, TriIsect const* a, size_t count, CullTables& T) {
-  T.alwaysCount = uint32_t(count), T.clusterCount = uint32_t(clusters.size());
-  if (clusters.empty()) return DMT_OK;
-  std::vector<uint8_t> culled(count, 0);
-  std::vector<float> tri9(9 * kCullMaxTris, 0.f);
-  for (CullCluster const& cl : clusters)
-    for (uint32_t j = 0; j < cl.count; ++j) {
-      TriIsect const& t = a[cl.first + j];
-      float const f[9] = {t.p0x, t.p0y, t.p0z, t.e0x, t.e0y, t.e0z, t.e1x, t.e1y, t.e1z};
-      for (int q = 0; q < 9; ++q) tri9[q * kCullMaxTris + cl.slot + j] = f[q];
-      culled[cl.first + j] = 1;
-    }
-  std::vector<TriIsect> always;
-  std::vector<uint32_t> idx;
-  for (size_t i = 0; i < count; ++i)
-    if (!culled[i]) always.push_back(a[i]), idx.push_back(uint32_t(i));
-  std::vector<CullCluster> table(kCullMaxClusters, CullCluster{});
-  std::copy(clusters.begin(), clusters.end(), table.begin());
-  T.alwaysCount = uint32_t(always.size());
-  HIP_TRY(ctx, T.always.assign(always.data(), always.size()));
-  HIP_TRY(ctx, T.idx.assign(idx.data(), idx.size()));
-  HIP_TRY(ctx, T.clusters.assign(table.data(), table.size()));
-  HIP_TRY(ctx, T.tri9.assign(tri9.data(), tri9.size()));
-  return DMT_OK;
-}
-void adoptCullTables(dmt_ctx* ctx, CullTables& T) {
-  ctx->d_cullAlways = std::move(T.always), ctx->d_cullIdx = std::move(T.idx);
-  ctx->d_cullClusters = std::move(T.clusters), ctx->d_cullTri9 = std::move(T.tri9);
-  ctx->cullAlwaysCount = T.alwaysCount, ctx->cullClusterCount = T.clusterCount;
-}
-
-// ---- dmt_update_vertices: timing and the update policy ----
-int lbvhError(dmt_ctx* ctx, char const* stage, std::string const& what, hipError_t e) {
-  ctx->err = std::string(stage) + ": " + what + ": " + hipGetErrorName(e) + " - " + hipGetErrorString(e);
-  return DMT_ERR_HIP;
-}
-int treeCost(dmt_ctx* ctx, double& cost) {
-  std::string what;
-  hipError_t const e = lbvh_gpu::sahCost(ctx->d_bvhNodes.get(), ctx->d_trisBvh.get(), ctx->bvhNodeCount, ctx->bvhPairCount, ctx->stream,
-                                         ctx->refitScratch, cost, what);
-  return e == hipSuccess ? DMT_OK : lbvhError(ctx, "BVH cost", what, e);
-}
-
-// The records, cull tables and host mirrors hold the new positions; T.a is recorded on the idle stream.  Applies
-// dmt_set_accel_update's policy to the tree and fills the update record.
-int finishUpdate(dmt_ctx* ctx, EventPair& T) {
-  dmt_accel_update_record& U = ctx->updateRecord;
-  bool const bvh = ctx->accel == DMT_ACCEL_BVH;
-  bool const refitting = bvh && ctx->haveBvh && ctx->accelUpdate != DMT_BVH_UPDATE_REBUILD && ctx->bvhLevels.size() >= 2;
-  bool rebuild = bvh && !refitting;
-  if (!bvh) ctx->haveBvh = false;  // as an upload does
-  U.action = DMT_BVH_UPDATED_NONE;
-  if (refitting) {
-    if (!ctx->costAtBuildKnown) {  // the nodes still are the builder's: the refit has not run yet
-      if (int const rc = treeCost(ctx, U.sah_cost_at_build)) return rc;
-      ctx->costAtBuildKnown = true;
-    }
-    static_assert(sizeof(TriPost) == 64 && offsetof(TriPost, p2z) == 32, "the refit reads p0, p1, p2 as nine consecutive floats");
-    std::string what;
-    hipError_t const e = lbvh_gpu::refit(reinterpret_cast<float const*>(ctx->d_post.get()), uint32_t(sizeof(TriPost) / sizeof(float)), ctx->triCount,
-                                         ctx->d_bvhNodes.get(), ctx->d_trisBvh.get(), ctx->bvhNodeCount, ctx->bvhPairCount, ctx->bvhLevels,
-                                         ctx->stream, ctx->refitScratch, what);
-    if (e != hipSuccess) {
-      ctx->haveBvh = false;  // the tree may be half refitted
-      return lbvhError(ctx, "BVH refit", what, e);
-    }
-    if (int const rc = treeCost(ctx, U.sah_cost)) return rc;
-    U.action = DMT_BVH_UPDATED_REFIT;
-    ++U.updates_since_build;
-    rebuild = ctx->accelUpdate == DMT_BVH_UPDATE_AUTO && U.sah_cost > ctx->maxCostRatio * U.sah_cost_at_build;
-  }
-  HIP_TRY(ctx, hipEventRecord(T.b, ctx->stream));
-  HIP_TRY(ctx, hipEventSynchronize(T.b));
-  float ms = 0.f;
-  HIP_TRY(ctx, hipEventElapsedTime(&ms, T.a, T.b));
-  U.update_ms = double(ms);
-  if (rebuild) {
-    ctx->haveBvh = false;
-    if (int const rc = buildBvh(ctx)) return rc;  // resets updates_since_build and the costs
-    U.action = refitting ? DMT_BVH_UPDATED_REBUILD_AFTER_REFIT : DMT_BVH_UPDATED_REBUILD;
-    U.update_ms += ctx->buildRecord.build_ms;
-    if (ctx->accelUpdate != DMT_BVH_UPDATE_REBUILD) {
-      if (int const rc = treeCost(ctx, U.sah_cost)) return rc;
-      U.sah_cost_at_build = U.sah_cost;
-      ctx->costAtBuildKnown = true;
-    }
-  }
-  U.temp_bytes = ctx->refitScratch.bytes();
-  return DMT_OK;
 }
 
 // octahedral decode on the host (CC/private/encoding.cu:39-60), as pt_device.hpp's dir_from_octa
@@ -3256,9 +2931,6 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
   if (e == hipSuccess) e = hipMemset(ctx->d_counter.get(), 0, 2 * sizeof(uint32_t));
   if (e == hipSuccess) e = ctx->d_schedDiag.reserve(kSchedDiagWords);
   if (e == hipSuccess) e = hipMemset(ctx->d_schedDiag.get(), 0, kSchedDiagWords * sizeof(unsigned long long));
-  int bpc = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, reinterpret_cast<void const*>(k_megakernel), 256, 0);
   int bpcBvh = 0;
   if (e == hipSuccess)
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpcBvh, reinterpret_cast<void const*>(k_megakernel_bvh), 256, 0);
@@ -3269,15 +2941,14 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
   }
   ctx->stream = ctx->ownStream;
   ctx->cuCount = prop.multiProcessorCount;
-  ctx->blocksPerCU = bpc > 0 ? bpc : 1;
-  ctx->blocksPerCUBvh = bpcBvh > 0 ? bpcBvh : 1;
+  ctx->ac.blocksPerCUBvh = bpcBvh > 0 ? bpcBvh : 1;
   if (char const* e3 = std::getenv("DMT_BVH_STRATEGY")) {  // experiments: 0 auto, 1 megakernel, 2 wavefront
     int const v = std::atoi(e3);
     ctx->bvhStrategy = v < 0 || v > 2 ? 0 : v;
   }
-  if (char const* e5 = std::getenv("DMT_BVH_SHADE_THRESHOLD")) {  // tuning runs (bvhShadeThreshold)
+  if (char const* e5 = std::getenv("DMT_BVH_SHADE_THRESHOLD")) {  // tuning runs (shadeThresholdFor)
     int const v = std::atoi(e5);
-    ctx->shadeThresholdEnv = v < 1 ? 0 : (v > 64 ? 64 : v);
+    ctx->ac.shadeThresholdEnv = v < 1 ? 0 : (v > 64 ? 64 : v);
   }
   if (char const* e4 = std::getenv("DMT_WF_PATHS")) {
     long long const v = std::atoll(e4);
@@ -3333,108 +3004,18 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   CullTables cull;
   if (int const rcC = uploadCullTables(ctx, planCullClusters(ctx, xs, ys, zs, mat_id, count), a.data(), count, cull)) return rcC;
   ctx->d_tris = std::move(tris), ctx->d_post = std::move(post);
-  adoptCullTables(ctx, cull);
+  ctx->cull = std::move(cull);
   ctx->triCount = uint32_t(count);
   ctx->maxMatId = maxMat;
   ctx->haveTris = true;
   ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
   ctx->h_mat.assign(mat_id, mat_id + count);
-  ctx->haveBvh = false;
+  ctx->ac.tree.drop();         // it is of the soup just replaced
   dropMotion(ctx);             // key 1 was a motion from the soup just replaced
   ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
   ctx->h_areaTri.clear(), ctx->h_areaLe.clear();  // emissive triangles are indices into the soup just replaced
   if (int const rcA = rebuildAreaLights(ctx)) return rcA;
   if (ctx->accel == DMT_ACCEL_BVH) return buildBvh(ctx);
-  return DMT_OK;
-}
-
-namespace {
-// common entry of the two updates: argument and state checks, the stream drained, the timer started.  *done: nothing to do
-int beginUpdate(dmt_ctx* ctx, char const* name, bool nullArray, size_t count, EventPair& T, bool* done) {
-  *done = false;
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "update of vertices before any dmt_upload_triangles");
-  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "update of vertices: count differs from the uploaded triangle count");
-  if (count && nullArray) {
-    ctx->err = std::string(name) + ": null array";
-    return DMT_ERR_INVALID;
-  }
-  if (count == 0) {
-    *done = true;
-    return DMT_OK;
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old records
-  HIP_TRY(ctx, hipEventCreate(&T.a));
-  HIP_TRY(ctx, hipEventCreate(&T.b));
-  HIP_TRY(ctx, hipEventRecord(T.a, ctx->stream));
-  return DMT_OK;
-}
-}  // namespace
-
-int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs, size_t count) {
-  EventPair T;
-  bool done = false;
-  if (int const rc = beginUpdate(ctx, "dmt_update_vertices", !xs || !ys || !zs, count, T, &done)) return rc;
-  if (done) return DMT_OK;
-  dropMotion(ctx);  // key 1 was a motion from the positions being replaced
-  std::vector<TriIsect> a;
-  std::vector<TriPost> b;
-  packSoup(xs, ys, zs, ctx->h_mat.data(), count, a, b);
-  CullTables cull;
-  if (int const rcC = uploadCullTables(ctx, planCullClusters(ctx, xs, ys, zs, ctx->h_mat.data(), count), a.data(), count, cull)) return rcC;
-  HIP_TRY(ctx, hipMemcpy(ctx->d_tris.get(), a.data(), count * sizeof(TriIsect), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_post.get(), b.data(), count * sizeof(TriPost), hipMemcpyHostToDevice));
-  adoptCullTables(ctx, cull);
-  ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
-  if (int const rcT = mirrorHostUpdate(ctx)) return rcT;
-  return finishUpdate(ctx, T);
-}
-
-int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count) {
-  EventPair T;
-  bool done = false;
-  if (int const rc = beginUpdate(ctx, "dmt_update_vertices_device", !d_verts9, count, T, &done)) return rc;
-  if (done) return DMT_OK;
-  dropMotion(ctx);  // key 1 was a motion from the positions being replaced
-  HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->d_tris.get(), ctx->d_post.get(), ctx->stream));
-  if (int const rcT = mirrorDeviceUpdate(ctx, d_verts9, count)) return rcT;
-  // the host mirrors (the host builder's, the cull plan's and a later rebuild's input) from the records just made
-  std::vector<TriPost> b(count);
-  HIP_TRY(ctx, hipMemcpyAsync(b.data(), ctx->d_post.get(), count * sizeof(TriPost), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < count; ++i) {
-    TriPost const& q = b[i];
-    ctx->h_xs[4 * i] = q.p0x, ctx->h_xs[4 * i + 1] = q.p1x, ctx->h_xs[4 * i + 2] = q.p2x;
-    ctx->h_ys[4 * i] = q.p0y, ctx->h_ys[4 * i + 1] = q.p1y, ctx->h_ys[4 * i + 2] = q.p2y;
-    ctx->h_zs[4 * i] = q.p0z, ctx->h_zs[4 * i + 1] = q.p1z, ctx->h_zs[4 * i + 2] = q.p2z;
-  }
-  std::vector<CullCluster> const clusters = planCullClusters(ctx, ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->h_mat.data(), count);
-  std::vector<TriIsect> a;
-  if (!clusters.empty()) {  // the cluster tables copy TriIsect records: the kernel's own
-    a.resize(count);
-    HIP_TRY(ctx, hipMemcpy(a.data(), ctx->d_tris.get(), count * sizeof(TriIsect), hipMemcpyDeviceToHost));
-  }
-  CullTables cull;
-  if (int const rcC = uploadCullTables(ctx, clusters, a.data(), count, cull)) return rcC;
-  adoptCullTables(ctx, cull);
-  return finishUpdate(ctx, T);
-}
-
-int dmt_set_accel_update(dmt_ctx* ctx, int mode, double max_cost_ratio) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (mode != DMT_BVH_UPDATE_REBUILD && mode != DMT_BVH_UPDATE_REFIT && mode != DMT_BVH_UPDATE_AUTO)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel_update: unknown mode");
-  if (mode == DMT_BVH_UPDATE_AUTO && !(std::isfinite(max_cost_ratio) && max_cost_ratio > 1.0))
-    return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel_update: DMT_BVH_UPDATE_AUTO needs a finite max_cost_ratio > 1");
-  ctx->accelUpdate = mode;
-  if (mode == DMT_BVH_UPDATE_AUTO) ctx->maxCostRatio = max_cost_ratio;
-  return DMT_OK;
-}
-
-int dmt_accel_update_info(dmt_ctx* ctx, dmt_accel_update_record* out) {
-  if (!ctx || !out) return DMT_ERR_INVALID;
-  *out = ctx->updateRecord;
   return DMT_OK;
 }
 
@@ -3522,60 +3103,6 @@ int dmt_set_limits(dmt_ctx* ctx, int max_depth) {
   if (!ctx) return DMT_ERR_INVALID;
   if (max_depth < 0) return fail(ctx, DMT_ERR_INVALID, "dmt_set_limits: max_depth < 0");
   ctx->maxDepth = max_depth;
-  return DMT_OK;
-}
-
-int dmt_set_accel(dmt_ctx* ctx, int mode) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (mode != DMT_ACCEL_BRUTE_FORCE && mode != DMT_ACCEL_BVH) return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel: unknown mode");
-  ctx->accel = mode;
-  if (mode == DMT_ACCEL_BVH && ctx->haveTris && !ctx->haveBvh) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int const rc = buildBvh(ctx)) return rc;
-  }
-  if (mode == DMT_ACCEL_BVH && ctx->haveMotion) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ensureMotionTree(ctx);
-  }
-  return DMT_OK;
-}
-
-int dmt_set_accel_build(dmt_ctx* ctx, int mode) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (mode != DMT_BVH_BUILD_HOST && mode != DMT_BVH_BUILD_DEVICE) return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel_build: unknown mode");
-  if (mode == ctx->accelBuild) return DMT_OK;
-  ctx->accelBuild = mode;
-  ctx->haveBvh = false;  // the current tree is the other builder's
-  if (ctx->accel == DMT_ACCEL_BVH && ctx->haveTris) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight still read the old tree
-    return buildBvh(ctx);
-  }
-  return DMT_OK;
-}
-
-int dmt_accel_build_info(dmt_ctx* ctx, dmt_accel_build_record* out) {
-  if (!ctx || !out) return DMT_ERR_INVALID;
-  if (!ctx->haveBvh) {  // no tree: the builder the next build will use, zero counts
-    *out = dmt_accel_build_record{};
-    out->builder = ctx->accelBuild == DMT_BVH_BUILD_DEVICE ? DMT_BVH_BUILT_BY_DEVICE : DMT_BVH_BUILT_BY_HOST;
-    return DMT_OK;
-  }
-  *out = ctx->buildRecord;
-  return DMT_OK;
-}
-
-int dmt_accel_download(dmt_ctx* ctx, void* nodes64, size_t node_cap, uint32_t* pair_orig2, size_t pair_cap) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_accel_download: no tree (set DMT_ACCEL_BVH and upload triangles first)");
-  if (node_cap < ctx->bvhNodeCount || pair_cap < ctx->bvhPairCount || (ctx->bvhNodeCount && !nodes64) || (ctx->bvhPairCount && !pair_orig2))
-    return fail(ctx, DMT_ERR_INVALID, "dmt_accel_download: arrays too small (see dmt_accel_build_info)");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipMemcpy(nodes64, ctx->d_bvhNodes.get(), size_t(ctx->bvhNodeCount) * sizeof(Bvh4Node), hipMemcpyDeviceToHost));
-  std::vector<TriPair> pairs(ctx->bvhPairCount);
-  if (!pairs.empty()) HIP_TRY(ctx, hipMemcpy(pairs.data(), ctx->d_trisBvh.get(), pairs.size() * sizeof(TriPair), hipMemcpyDeviceToHost));
-  for (size_t p = 0; p < pairs.size(); ++p) pair_orig2[2 * p] = pairs[p].orig[0], pair_orig2[2 * p + 1] = pairs[p].orig[1];
   return DMT_OK;
 }
 
@@ -3882,13 +3409,13 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
   HIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream));
   uint64_t const launchFolds = uint64_t(P.numItems) * P.numChunks;  // every item is folded exactly once (checkErrorFlag)
   if (wavefront) {
-    if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render: BVH not built");
+    if (int const rcT = requireTree(ctx, "dmt_render")) return rcT;
     int const rcW = launchWavefront(ctx, P, ownedTiles, sample_offset, spp, wfShade, stats6, nstats);
     if (rcW) return rcW;
     if (stats6) return DMT_OK;
   } else if (useBvh) {
-    if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_render: BVH not built");
-    HIP_TRY(ctx, reserveOverflow(ctx, size_t(ctx->cuCount) * size_t(std::max(blocksPerCu, ctx->blocksPerCUBvh)) * 256));
+    if (int const rcT = requireTree(ctx, "dmt_render")) return rcT;
+    HIP_TRY(ctx, reserveOverflow(ctx, size_t(ctx->cuCount) * size_t(std::max(blocksPerCu, ctx->ac.blocksPerCUBvh)) * 256));
     P.bvh = bvhView(ctx, size_t(blocks) * 256);
     if (stats6) {
       HIP_TRY(ctx, ctx->d_stats.reserve(16));
@@ -3985,17 +3512,6 @@ int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, c
       for (int a = 0; a < 6; ++a) cluster_box[6 * k + size_t(a)] = cl[k].b[a];
   }
   return DMT_OK;
-}
-
-int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t count, int* node_count, int* depth,
-                     int* max_leaf) {
-  if ((count && (!xs || !ys || !zs)) || count > 0x0FFFFFFFu) return DMT_ERR_INVALID;
-  bvh_build::Result const r = bvh_build::build(xs, ys, zs, uint32_t(count));
-  if (node_count) *node_count = int(r.nodes.size());
-  if (depth) *depth = r.depth;
-  bool const ok = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs, ys, zs, count, nullptr,
-                                   max_leaf, nullptr);
-  return ok && r.depth <= kBvhMaxDepth ? DMT_OK : DMT_ERR_STATE;
 }
 
 static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats,
@@ -4353,112 +3869,6 @@ int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
   float const* const m = ctx->xf.rfc;  // column 2 = the viewing direction
   *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
   return DMT_OK;
-}
-
-// ---- motion blur -------------------------------------------------------------------------
-static bool shutterOk(float open, float close) { return std::isfinite(open) && std::isfinite(close) && 0.f <= open && open <= close && close <= 1.f; }
-
-int dmt_set_motion(dmt_ctx* ctx, const float* xs1, const float* ys1, const float* zs1, size_t count) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_set_motion: before any dmt_upload_triangles");
-  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: count differs from the uploaded triangle count");
-  if (count && (!xs1 || !ys1 || !zs1)) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: null array");
-  for (size_t k = 0; k < 4 * count; ++k) {
-    if ((k & 3) == 3) continue;  // the SoA's pad lane
-    if (!std::isfinite(xs1[k]) || !std::isfinite(ys1[k]) || !std::isfinite(zs1[k])) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: a position is not finite");
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old key 1
-  std::vector<TriIsect> a, b;
-  std::vector<TriPost> pa, pb;
-  packSoup(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->h_mat.data(), count, a, pa);  // A: the records the context holds
-  packSoup(xs1, ys1, zs1, ctx->h_mat.data(), count, b, pb);
-  std::vector<TriIsect> d(count);
-  std::vector<TriKey1> q(count);
-  for (size_t i = 0; i < count; ++i) {  // D = B - A, component by component in fp32
-    TriIsect const &A = a[i], &B = b[i];
-    TriIsect& D = d[i];
-    D.p0x = B.p0x - A.p0x, D.p0y = B.p0y - A.p0y, D.p0z = B.p0z - A.p0z;
-    D.e0x = B.e0x - A.e0x, D.e0y = B.e0y - A.e0y, D.e0z = B.e0z - A.e0z;
-    D.e1x = B.e1x - A.e1x, D.e1y = B.e1y - A.e1y, D.e1z = B.e1z - A.e1z;
-    D.matId = 0, D.pad0 = D.pad1 = 0;
-    TriPost const& P = pb[i];
-    q[i] = TriKey1{P.p0x, P.p0y, P.p0z, P.p1x, P.p1y, P.p1z, P.p2x, P.p2y, P.p2z, 0.f, 0.f, 0.f};
-  }
-  DevBuf<TriIsect> dd;
-  DevBuf<TriKey1> dq;
-  HIP_TRY(ctx, dd.assign(d.data(), count));
-  HIP_TRY(ctx, dq.assign(q.data(), count));
-  dropMotion(ctx);
-  ctx->d_dtris = std::move(dd), ctx->d_post1 = std::move(dq);
-  ctx->h_xs1.assign(xs1, xs1 + 4 * count), ctx->h_ys1.assign(ys1, ys1 + 4 * count), ctx->h_zs1.assign(zs1, zs1 + 4 * count);
-  ctx->haveMotion = true;
-  if (ctx->accel == DMT_ACCEL_BVH) return ensureMotionTree(ctx);
-  return DMT_OK;
-}
-
-int dmt_clear_motion(dmt_ctx* ctx) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveMotion) return DMT_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read key 1
-  dropMotion(ctx);
-  return DMT_OK;
-}
-
-int dmt_set_shutter(dmt_ctx* ctx, float open, float close) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!shutterOk(open, close)) return fail(ctx, DMT_ERR_INVALID, "dmt_set_shutter: needs finite 0 <= open <= close <= 1");
-  ctx->shutterOpen = open, ctx->shutterClose = close;
-  return DMT_OK;
-}
-
-int dmt_motion_info(dmt_ctx* ctx, int* keys, float* open, float* close, uint32_t* tree_nodes, uint32_t* tree_pairs, double* tree_build_ms) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (keys) *keys = ctx->haveTris ? (ctx->haveMotion ? 2 : 1) : 0;
-  if (open) *open = ctx->shutterOpen;
-  if (close) *close = ctx->shutterClose;
-  if (tree_nodes) *tree_nodes = ctx->haveMotionTree ? ctx->mNodeCount : 0u;
-  if (tree_pairs) *tree_pairs = ctx->haveMotionTree ? ctx->mPairCount : 0u;
-  if (tree_build_ms) *tree_build_ms = ctx->haveMotionTree ? ctx->mBuildMs : 0.0;
-  return DMT_OK;
-}
-
-int dmt_shutter_times(int width, int height, float open, float close, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t) {
-  if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || n < 0 || !shutterOk(open, close)) return DMT_ERR_INVALID;
-  if (n && (!pxs || !pys || !ss || !t)) return DMT_ERR_INVALID;
-  SamplerParams const sp = computeSamplerParams(width, height);
-  int64_t const stride = int64_t(sp.scale0) * sp.scale1;
-  for (int i = 0; i < n; ++i)
-    if (pxs[i] < 0 || pys[i] < 0 || pxs[i] >= width || pys[i] >= height || ss[i] < 0 || (int64_t(ss[i]) + 1) * stride > 0x7FFFFFFFll)
-      return DMT_ERR_INVALID;  // outside the frame, or the sample overflows the 32-bit Halton index
-  for (int i = 0; i < n; ++i) t[i] = shutter_time(uint32_t(halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * int32_t(stride)), open, close);
-  return DMT_OK;
-}
-
-int dmt_motion_positions(const float* xs0, const float* ys0, const float* zs0, const float* xs1, const float* ys1, const float* zs1, size_t count,
-                         float t, float* xs, float* ys, float* zs) {
-  if (!std::isfinite(t) || (count && (!xs0 || !ys0 || !zs0 || !xs1 || !ys1 || !zs1 || !xs || !ys || !zs))) return DMT_ERR_INVALID;
-  for (size_t k = 0; k < 4 * count; ++k) {
-    bool const pad = (k & 3) == 3;  // the SoA's pad lane: key 0's
-    xs[k] = pad ? xs0[k] : motion_lerp(t, xs0[k], xs1[k]);
-    ys[k] = pad ? ys0[k] : motion_lerp(t, ys0[k], ys1[k]);
-    zs[k] = pad ? zs0[k] : motion_lerp(t, zs0[k], zs1[k]);
-  }
-  return DMT_OK;
-}
-
-int dmt_motion_bvh_validate(const float* xs0, const float* ys0, const float* zs0, const float* xs1, const float* ys1, const float* zs1,
-                            size_t count, int* node_count, int* pair_count, int* depth) {
-  if ((count && (!xs0 || !ys0 || !zs0 || !xs1 || !ys1 || !zs1)) || count > 0x0FFFFFFFu) return DMT_ERR_INVALID;
-  bvh_build::Result const r = bvh_build::build(xs0, ys0, zs0, uint32_t(count), xs1, ys1, zs1);
-  if (node_count) *node_count = int(r.nodes.size());
-  if (pair_count) *pair_count = int(r.pairTris.size() / 2);
-  if (depth) *depth = r.depth;
-  // every decoded child box holds the vertices below it at key 0 and at key 1 (and every other invariant of a tree, twice)
-  bool const ok0 = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs0, ys0, zs0, count, nullptr, nullptr, nullptr);
-  bool const ok1 = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs1, ys1, zs1, count, nullptr, nullptr, nullptr);
-  return ok0 && ok1 && r.depth <= kBvhMaxDepth ? DMT_OK : DMT_ERR_STATE;
 }
 
 int dmt_kernel_time(dmt_ctx* ctx, double* total_ms, uint64_t* launches, int reset) {

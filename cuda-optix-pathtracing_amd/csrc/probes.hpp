@@ -2,8 +2,8 @@
 // device function over arrays of cases, which is how the tests compare the device code with the oracle function by function.
 //
 // Part of dmt_hip.hip's translation unit, included once at its end: it uses the device code, dmt_ctx, HIP_TRY, fail,
-// baseParams, reserveOverflow, resolveFeatures / kernelOf and finishTest defined there, and denoise_host.hpp's makeProjXf.  A probe is a kernel with
-// one lane per case and an entry point that stages its arrays through probe_stage.hpp.
+// baseParams, resolveFeatures / kernelOf and finishTest defined there, accel_host.hpp's requireTree, reserveOverflow and
+// motionParams, and denoise_host.hpp's makeProjXf.  A probe: a kernel with one lane per case, an entry point staging its arrays (probe_stage.hpp).
 #pragma once
 
 #include "probe_stage.hpp"
@@ -573,7 +573,7 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
   TestTraceFn const kernel = kernelOf(kTestTraceKernels, F);
   if (!kernel) return noKernel(ctx, "dmt_test_trace_samples", F);
   if (F & kFeatBvh) {
-    if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_samples: BVH not built");
+    if (int const rcT = requireTree(ctx, "dmt_test_trace_samples")) return rcT;
     HIP_TRY(ctx, reserveOverflow(ctx, p.threads(64)));
   }
   RenderParams P = baseParams(ctx, p.threads(64));
@@ -611,8 +611,8 @@ int dmt_test_trace_log(dmt_ctx* ctx, int px, int py, int s, float* rec12, int ca
   ProbeOut<int> dn(p, n_out, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
   RenderParams P = baseParams(ctx, p.threads(64));
-  if (int const rc = motionParams(ctx, ctx->haveMotion ? kFeatMotion : 0u, P)) return rc;  // (brute force: no tree)
-  hipLaunchKernelGGL(ctx->haveMotion ? k_test_trace_log_motion : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
+  if (int const rc = motionParams(ctx, ctx->ac.haveMotion ? kFeatMotion : 0u, P)) return rc;  // (brute force: no tree)
+  hipLaunchKernelGGL(ctx->ac.haveMotion ? k_test_trace_log_motion : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
                      dr.get(), cap, dn.get(), dL.get());
   return finishProbe(ctx, p);
 }
@@ -628,7 +628,7 @@ int dmt_test_closest_hit(dmt_ctx* ctx, int nrays, const float* o3, const float* 
   if (p.err != hipSuccess) return probeError(ctx, p);
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   if (useBvh) {
-    if (!ctx->haveBvh) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit: BVH not built");
+    if (int const rcT = requireTree(ctx, "dmt_test_closest_hit")) return rcT;
     HIP_TRY(ctx, reserveOverflow(ctx, p.threads(64)));
   }
   hipLaunchKernelGGL(k_test_closest, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), useBvh, nrays,
@@ -640,7 +640,7 @@ int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const floa
                             float* uv2) {
   if (!ctx || nrays < 0 || !o3 || !d3 || !time || !tri_index || !t) return DMT_ERR_INVALID;
   if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: upload triangles first");
-  if (!ctx->haveMotion) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: no key 1 (dmt_set_motion first)");
+  if (!ctx->ac.haveMotion) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: no key 1 (dmt_set_motion first)");
   for (int i = 0; i < nrays; ++i)
     if (!std::isfinite(time[i])) return fail(ctx, DMT_ERR_INVALID, "dmt_test_closest_hit_at: a time is not finite");
   if (nrays == 0) return DMT_OK;
@@ -666,7 +666,7 @@ int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dT(p, t, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_shutter, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->sp, ctx->shutterOpen, ctx->shutterClose, n, dpx.get(),
+  hipLaunchKernelGGL(k_test_shutter, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->sp, ctx->ac.shutterOpen, ctx->ac.shutterClose, n, dpx.get(),
                      dpy.get(), dss.get(), dT.get());
   return finishProbe(ctx, p);
 }
