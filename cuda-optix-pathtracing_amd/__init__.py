@@ -38,6 +38,7 @@ from .binding import (  # noqa: F401
     shutter_times,
     motion_positions,
     motion_bvh_validate,
+    smooth_normals,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

@@ -81,6 +81,8 @@ EXPORTED_SYMBOLS = [
     "dmt_set_lens", "dmt_lens_info", "dmt_lens_rays", "dmt_focus_distance_at", "dmt_test_lens_values",
     "dmt_set_motion", "dmt_clear_motion", "dmt_set_shutter", "dmt_motion_info", "dmt_shutter_times", "dmt_motion_positions",
     "dmt_motion_bvh_validate", "dmt_test_shutter_times", "dmt_test_closest_hit_at",
+    "dmt_upload_vertex_normals", "dmt_clear_vertex_normals", "dmt_vertex_normals_info", "dmt_smooth_normals",
+    "dmt_test_shading_normal", "dmt_test_shading_normal_mapped",
 ]
 
 # dmt_set_sampler_table modes (include/dmt_hip.h)
@@ -217,6 +219,21 @@ def motion_bvh_validate(xs0, ys0, zs0, xs1, ys1, zs1):
     nc, pc, d = C.c_int(), C.c_int(), C.c_int()
     rc = lib.dmt_motion_bvh_validate(*[_p(v) for v in a], C.c_size_t(n), C.byref(nc), C.byref(pc), C.byref(d))
     return {"ok": rc == 0, "node_count": nc.value, "pair_count": pc.value, "depth": d.value}
+
+
+def smooth_normals(xs, ys, zs, crease_degrees=180.0):
+    """Host only (dmt_smooth_normals): angle-weighted vertex normals [n, 9] for a soup laid out as upload_triangles; corners
+    with bit-equal positions are welded, faces beyond crease_degrees of a corner's own face do not contribute, zero-area
+    triangles come out flat (zeros)."""
+    lib = load_library()
+    xs, ys, zs = _f32(xs).reshape(-1), _f32(ys).reshape(-1), _f32(zs).reshape(-1)
+    n = xs.size // 4
+    assert xs.size == 4 * n and ys.size == 4 * n and zs.size == 4 * n
+    out = np.zeros((n, 9), np.float32)
+    rc = lib.dmt_smooth_normals(_p(xs), _p(ys), _p(zs), C.c_size_t(n), C.c_float(crease_degrees), _p(out))
+    if rc != 0:
+        raise DmtError(f"dmt_smooth_normals failed ({rc})")
+    return out
 
 
 # dmt_set_texture_filter modes (include/dmt_hip.h)
@@ -541,6 +558,34 @@ class Renderer:
         return {"keys": k.value, "open": o.value, "close": c.value, "tree_nodes": nn.value, "tree_pairs": npairs.value,
                 "tree_build_ms": ms.value}
 
+    def upload_vertex_normals(self, n9):
+        """Smooth shading (dmt_upload_vertex_normals): [n, 9] the normals at vertices 0, 1, 2 of every uploaded triangle; a
+        row of zeros keeps that triangle flat.  Dropped by upload_triangles, kept by update_vertices*."""
+        n9 = _f32(n9).reshape(-1, 9)
+        self._check(self._lib.dmt_upload_vertex_normals(self._ctx, _p(n9), C.c_size_t(n9.shape[0])), "dmt_upload_vertex_normals")
+
+    def clear_vertex_normals(self):
+        """Drops the vertex normals (dmt_clear_vertex_normals): every film is again what it was before the upload."""
+        self._check(self._lib.dmt_clear_vertex_normals(self._ctx), "dmt_clear_vertex_normals")
+
+    def vertex_normals_info(self):
+        """dmt_vertex_normals_info as a dict: triangles (0 without normals), smooth_triangles."""
+        t, sm = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dmt_vertex_normals_info(self._ctx, C.byref(t), C.byref(sm)), "dmt_vertex_normals_info")
+        return {"triangles": t.value, "smooth_triangles": sm.value}
+
+    def test_shading_normal(self, tri, bu, bv, rd, mapped=False):
+        """The shading normal [n, 3] the vertex-normal rows compute for triangle tri[i] at (bu, bv) under a ray of direction
+        rd[i] (dmt_test_shading_normal); mapped: with the material's normal map applied around it."""
+        tri, bu, bv = _i32(tri).reshape(-1), _f32(bu).reshape(-1), _f32(bv).reshape(-1)
+        rd = _f32(rd).reshape(-1, 3)
+        n = tri.shape[0]
+        assert bu.shape[0] == n and bv.shape[0] == n and rd.shape[0] == n
+        ns = np.zeros((n, 3), np.float32)
+        fn = self._lib.dmt_test_shading_normal_mapped if mapped else self._lib.dmt_test_shading_normal
+        self._check(fn(self._ctx, int(n), _p(tri), _p(bu), _p(bv), _p(rd), _p(ns)), "dmt_test_shading_normal")
+        return ns
+
     def focus_distance_at(self, fx, fy):
         """Autofocus (dmt_focus_distance_at): the depth along the viewing direction of what the pinhole ray through the
         continuous film coordinates (fx, fy) hits; DmtError when it leaves the scene."""
@@ -548,10 +593,16 @@ class Renderer:
         self._check(self._lib.dmt_focus_distance_at(self._ctx, C.c_float(fx), C.c_float(fy), C.byref(d)), "dmt_focus_distance_at")
         return d.value
 
-    def upload_scene(self, scene):
+    def upload_scene(self, scene, vertex_normals=False):
         """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays; a scene with a `lens`
-        (lens_radius, focus_distance), as the loaders report one, sets the context's lens too."""
+        (lens_radius, focus_distance), as the loaders report one, sets the context's lens too.  vertex_normals: also
+        upload the scene's `tri_normals` (smooth shading); off by default, the files' normals are not used unasked."""
         self.upload_triangles(scene.xs, scene.ys, scene.zs, scene.mat_id)
+        if vertex_normals:
+            tn = getattr(scene, "tri_normals", None)
+            if tn is None or len(tn) != len(scene.mat_id):
+                raise DmtError("upload_scene(vertex_normals=True): the scene carries no tri_normals")
+            self.upload_vertex_normals(tn)
         self.upload_bsdfs(scene.bsdfs)
         self.upload_lights(scene.lights, scene.inf_lights)
         self.set_camera(scene.camera)

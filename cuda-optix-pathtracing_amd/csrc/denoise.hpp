@@ -53,13 +53,16 @@ DMT_DEV f3 aov_textures(KArgs k, Rec32& rec, uint32_t matId, int tri, float bu, 
   float const l2 = dot(ns, ns);
   return (l2 > 0.f && l2 < kInf) ? ns / sqrtf(l2) : ng;
 }
-// W and the shading normal at a camera ray's hit, as path_shade sees them at depth 0 (level-0 texture lookups)
+// W and the shading normal at a camera ray's hit, as path_shade sees them at depth 0 (level-0 texture lookups).  VN: the
+// smooth normal of the vertex-normal rows, under the normal map where there is one
+template <bool VN = false>
 DMT_DEV void aov_material(KArgs k, Hit const& hit, int tri, float bu, float bv, f3& W, f3& ns) {
   SceneView const sc = load_scene(k);
   bool const tex = kargs(k)->matTex != nullptr;
   Rec32 rec = sc.bsdfs[hit.matId];
   ns = hit.normal;
-  if (tex) ns = aov_textures(k, rec, hit.matId, tri, bu, bv, hit.normal);
+  if constexpr (VN) ns = shading_normal_at(k, tri, bu, bv, hit.normal);
+  if (tex) ns = aov_textures(k, rec, hit.matId, tri, bu, bv, ns);
   if (hi16(rec.w[1]) == BS_GGX_BLEND) {  // GGX: the albedo patch never applies, to either record
     float const mix = fminf(fmaxf(blend_metallic(k, rec, hit.matId, tri, bu, bv), 0.f), 1.f);
     f3 Wd = rec_weight(rec);
@@ -72,7 +75,8 @@ DMT_DEV void aov_material(KArgs k, Hit const& hit, int tri, float bu, float bv, 
 // one lane per pixel, row-major; whole waves stride over the frame (the BVH overflow stack is sized by the launch)
 // MOTION (k_aov_motion, launched while key 1 is present): every sample is traced at its own time, as the film's is, so the
 // planes blur where the film blurs; the post-hit record is the triangle's at that time.
-template <bool MOTION>
+// VN (k_aov_vn, launched while vertex normals are present): the normal plane accumulates the smooth shading normal.
+template <bool MOTION, bool VN = false>
 DMT_DEV void aov_body(AovArgs const& A) {
   KArgs const k = kargs_base();
   if constexpr (!MOTION) {
@@ -123,7 +127,7 @@ DMT_DEV void aov_body(AovArgs const& A) {
         }
         Hit const hit = shade_hit<MOTION ? kFeatMotion : 0u>(k, load_scene(k), best, bu, bv, r.d);
         f3 W, ns;
-        aov_material(k, hit, best, bu, bv, W, ns);
+        aov_material<VN>(k, hit, best, bu, bv, W, ns);
         sumW = sumW + W, sumN = sumN + ns, sumP = sumP + hit.pos, sumT += t;
         if (hits == 0) A.surface[i] = make_float4(float(best), bu, bv, 1.f);  // stored here: nothing more to keep across the loop
         ++hits;
@@ -143,6 +147,7 @@ DMT_DEV void aov_body(AovArgs const& A) {
 }
 __global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) { aov_body<false>(A); }
 __global__ void __launch_bounds__(256) k_aov_motion(RenderParams P, AovArgs A) { aov_body<true>(A); }
+__global__ void __launch_bounds__(256) k_aov_vn(RenderParams P, AovArgs A) { aov_body<false, true>(A); }
 
 // A-trous passes (spatial SVGF).  Colour and variance travel together as one float4 (rgb, v) per pixel, ping-ponged
 // between passes; the AOVs stay fp32 (no packing), so tests/denoise_ref.py restates the filter on the same numbers.

@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
 #include <memory>
 #include <new>
 #include <string>
@@ -71,6 +72,8 @@ struct CullView {
   float const* tri9;              // [9][kCullMaxTris] p0, e0, e1 of the culled triangles, field-major
   uint32_t alwaysCount, clusterCount;
 };
+
+struct VtxNormalRec;  // vnormals.hpp
 
 struct RenderParams {
   SceneView scene;
@@ -132,6 +135,9 @@ struct RenderParams {
   // motion blur (dmt_set_motion); read by the *_motion kernels only, which also get the motion tree in `bvh`.  Last, so that
   // no other field moves
   MotionView motion;
+  // smooth shading (dmt_upload_vertex_normals): [triangle] three octahedral normals and a flags word; read by the *_vn
+  // kernels only, at the hit.  After `motion`, so that no other field moves
+  VtxNormalRec const* vtxNormals;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -722,6 +728,7 @@ template <bool CULL = true>
 DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, int& bestTri, float& bu, float& bv, bool& occluded);
 
 #include "motion.hpp"
+#include "vnormals.hpp"
 
 // Optional parts of the path-tracing code, one bit each: the template argument F of path_shade, lane_finish, lane_step,
 // megakernel_body(_bvh) and wf_shade_body.  featuresOf (host) computes a context's mask; DMT_MEGAKERNELS and
@@ -736,6 +743,7 @@ constexpr uint32_t kFeatLightTree = 1u << 6;     // SURVEY 8f-4 light tree (ligh
 constexpr uint32_t kFeatLightTreeRef = 1u << 7;  // the reference-semantics light tree (light_tree_ref.hpp)
 constexpr uint32_t kFeatTexFilter = 1u << 8;     // first-hit MIP / EWA texture filtering; with kFeatTex or kFeatBlend only
 constexpr uint32_t kFeatMotion = 1u << 9;        // motion blur: triangles at the sample's time (motion.hpp); plain and env-map rows only
+constexpr uint32_t kFeatVtxNormals = 1u << 10;   // smooth shading: ns interpolated from per-vertex normals (vnormals.hpp); plain, env, tex rows
 
 // the post-hit record path_shade works on: the uploaded one, or under kFeatMotion the triangle at the sample's time
 template <uint32_t F>
@@ -750,6 +758,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   static_assert(!((F & kFeatTex) && (F & kFeatBlend)), "kFeatBlend carries the texture code itself");
   static_assert(!(F & kFeatTexFilter) || (F & (kFeatTex | kFeatBlend)), "the texture filter needs the texture code");
   static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
+  static_assert(!(F & kFeatVtxNormals) || !(F & ~(kFeatVtxNormals | kFeatBvh | kFeatEnv | kFeatTex)), "vertex normals: the plain, env-map and texture rows only");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
   if constexpr (F & kFeatEnv) {
@@ -800,7 +809,8 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
 
   f3 const wo = -rd;
   Rec32 rec = sc.bsdfs[hit.matId];
-  f3 ns = hit.normal;  // shading normal: the geometric one unless a normal map says otherwise
+  f3 ns = hit.normal;  // shading normal: the geometric one unless vertex normals or a normal map say otherwise
+  if constexpr (F & kFeatVtxNormals) ns = shading_normal_at(k, bestTri, bu, bv, hit.normal);
   // fractional "metallic" (BS_GGX_BLEND, JSON scenes): both lobes of the material are prepared, evaluated and sampled and the
   // results blended as the reference's CPU renderer does (core-material.cpp:275-286, :383-394).  kFeatBlend instantiations only.
   Rec32 rec2{};
@@ -822,7 +832,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   }
   if constexpr (F & (kFeatTex | kFeatBlend)) {
     if (!(F & kFeatBlend) || kargs(k)->matTex != nullptr) {
-      ns = apply_material_textures<FILT>(k, rec, hit.matId, bestTri, bu, bv, hit.normal, td);
+      ns = apply_material_textures<FILT>(k, rec, hit.matId, bestTri, bu, bv, ns, td);  // (ns: hit.normal, or the smooth normal the map perturbs)
       if (blend) (void)apply_material_textures<FILT>(k, rec2, hit.matId + 1u, bestTri, bu, bv, hit.normal, td);  // same roughness map
     }
   }
@@ -2109,6 +2119,9 @@ DMT_DEV void megakernel_body_bvh() {
 // calls its body directly (one more inlined level in between changes the generated code).  Separate kernels, so that one
 // combination's register allocation never touches another's.  No suffix: brute force, the reference's semantics; _bvh: 16 KB
 // more LDS per block for the traversal stacks; _blend: a second prepared BSDF per lane, one wave per SIMD fewer than _tex.
+// _vn: the parent row's body and bounds with a shading normal of its own (three more live VGPRs through path_shade, as the
+// _tex rows already carry); _env_vn and _bvh_env_vn run one wave per SIMD fewer than _env / _bvh_env, which is what keeps
+// them within their parents' scratch.
 #define DMT_MEGAKERNELS(X)                                                          \
   X(, 0, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                                   \
   X(_bvh, kFeatBvh, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh)                \
@@ -2145,7 +2158,15 @@ DMT_DEV void megakernel_body_bvh() {
   X(_motion, kFeatMotion, 4, megakernel_body)                                       \
   X(_bvh_motion, kFeatBvh | kFeatMotion, 3, megakernel_body_bvh)                    \
   X(_env_motion, kFeatEnv | kFeatMotion, 4, megakernel_body)                        \
-  X(_bvh_env_motion, kFeatBvh | kFeatEnv | kFeatMotion, 3, megakernel_body_bvh)
+  X(_bvh_env_motion, kFeatBvh | kFeatEnv | kFeatMotion, 3, megakernel_body_bvh)      \
+  X(_vn, kFeatVtxNormals, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                  \
+  X(_bvh_vn, kFeatBvh | kFeatVtxNormals, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh) \
+  X(_env_vn, kFeatEnv | kFeatVtxNormals, 3, megakernel_body)                        \
+  X(_bvh_env_vn, kFeatBvh | kFeatEnv | kFeatVtxNormals, 2, megakernel_body_bvh)     \
+  X(_tex_vn, kFeatTex | kFeatVtxNormals, 4, megakernel_body)                        \
+  X(_bvh_tex_vn, kFeatBvh | kFeatTex | kFeatVtxNormals, 3, megakernel_body_bvh)     \
+  X(_env_tex_vn, kFeatEnv | kFeatTex | kFeatVtxNormals, 4, megakernel_body)         \
+  X(_bvh_env_tex_vn, kFeatBvh | kFeatEnv | kFeatTex | kFeatVtxNormals, 3, megakernel_body_bvh)
 // the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
 // algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
 #define DMT_STATS_MEGAKERNELS(X)                                                    \
@@ -2317,6 +2338,10 @@ struct dmt_ctx {
   float texFoot[19] = {};         // dmt_texture_footprint of the current camera
   bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_blend kernels carry that code
   size_t triUvCount = 0;
+  // smooth shading (dmt_upload_vertex_normals; vnormals.hpp): one record per triangle of the soup, dropped with it
+  DevBuf<VtxNormalRec> d_vtxNormals;
+  bool haveVtxNormals = false;
+  uint64_t vtxSmoothCount = 0;
   // wavefront form of the BVH path (wavefront.hpp)
   int bvhStrategy = 0;             // 0 = automatic (by launch size), 1 = megakernel, 2 = wavefront
   size_t wfTargetPaths = size_t(1) << 22;  // path slots per pass
@@ -2700,6 +2725,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (treeable && c->lightSampling == DMT_LIGHTS_TREE_REFERENCE) F |= kFeatLightTreeRef;
   if (c->texFilter == DMT_TEXFILTER_REFERENCE && (F & (kFeatTex | kFeatBlend))) F |= kFeatTexFilter;
   if (c->ac.haveMotion) F |= kFeatMotion;
+  if (c->haveVtxNormals) F |= kFeatVtxNormals;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2714,6 +2740,15 @@ int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
 }
 // the combinations dmt_render refuses (mask | kFeatStats for dmt_render_stats / dmt_render_profile)
 int checkFeatures(dmt_ctx* ctx, uint32_t F) {
+  if (F & kFeatVtxNormals) {  // smooth shading has the plain, env-map and texture megakernel rows
+    if (F & kFeatStats) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: vertex normals (dmt_upload_vertex_normals) have no counting kernels");
+    if (F & kFeatMotion) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with motion blur are not supported");
+    if (F & kFeatTexFilter) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with the first-hit texture filter are not supported");
+    if (F & kFeatBlend) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with blend materials are not supported");
+    if (F & kFeatArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with emissive triangles are not supported");
+    if (F & (kFeatLightTree | kFeatLightTreeRef)) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with a light tree are not supported");
+    if ((F & kFeatBvh) && ctx->bvhStrategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with the wavefront BVH strategy are not supported");
+  }
   if (F & kFeatMotion) {  // motion blur has the plain and env-map megakernel rows
     if (F & kFeatStats) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: motion blur (dmt_set_motion) has no counting kernels");
     if (F & kFeatTexFilter) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with the first-hit texture filter is not supported");
@@ -2751,6 +2786,11 @@ void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const*
 
 namespace {
 
+void dropVertexNormals(dmt_ctx* ctx) {
+  ctx->d_vtxNormals.reset();
+  ctx->haveVtxNormals = false, ctx->vtxSmoothCount = 0;
+}
+
 SceneView sceneView(dmt_ctx const* c) {
   SceneView s;
   s.tris = c->d_tris.get(), s.post = c->d_post.get(), s.bsdfs = c->d_bsdfs.get(), s.lights = c->d_lights.get();
@@ -2773,6 +2813,7 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   P.env = c->env;
   P.areaOf = c->d_areaOf.get(), P.areaTri = c->d_areaTri.get(), P.areaLe = c->d_areaLe.get(), P.areaCount = c->areaCount;
+  if (c->haveVtxNormals) P.vtxNormals = c->d_vtxNormals.get();
   if (c->texCount > 0) {
     P.texRgba = c->d_texRgba.get(), P.texDesc = c->d_texDesc.get(), P.matTex = c->d_matTex.get(), P.triUv = c->d_triUv.get();
     P.texMip = c->d_texMip.get(), P.texMipDesc = c->d_texMipDesc.get();
@@ -3012,6 +3053,7 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->h_mat.assign(mat_id, mat_id + count);
   ctx->ac.tree.drop();         // it is of the soup just replaced
   dropMotion(ctx);             // key 1 was a motion from the soup just replaced
+  dropVertexNormals(ctx);      // they were the normals of the soup just replaced
   ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
   ctx->h_areaTri.clear(), ctx->h_areaLe.clear();  // emissive triangles are indices into the soup just replaced
   if (int const rcA = rebuildAreaLights(ctx)) return rcA;
@@ -3868,6 +3910,49 @@ int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
   if (tri < 0) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: the ray leaves the scene");
   float const* const m = ctx->xf.rfc;  // column 2 = the viewing direction
   *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
+  return DMT_OK;
+}
+
+// ---- smooth shading -----------------------------------------------------------------------
+int dmt_upload_vertex_normals(dmt_ctx* ctx, const float* n9, size_t count) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_upload_vertex_normals: before any dmt_upload_triangles");
+  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_vertex_normals: count differs from the uploaded triangle count");
+  if (count && !n9) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_vertex_normals: null array");
+  std::vector<VtxNormalRec> recs;
+  uint64_t smooth = 0;
+  long long const bad = vnormals::packRecords(n9, count, recs, &smooth);
+  if (bad >= 0)
+    return fail(ctx, DMT_ERR_INVALID, ("dmt_upload_vertex_normals: triangle " + std::to_string(bad) +
+                                       " has a normal that is not finite or shorter than 1e-6 (all nine zeros mark a flat triangle)").c_str());
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old records
+  DevBuf<VtxNormalRec> d;
+  HIP_TRY(ctx, d.assign(recs.data(), count));
+  ctx->d_vtxNormals = std::move(d);
+  ctx->haveVtxNormals = true, ctx->vtxSmoothCount = smooth;
+  return DMT_OK;
+}
+
+int dmt_clear_vertex_normals(dmt_ctx* ctx) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveVtxNormals) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the records
+  dropVertexNormals(ctx);
+  return DMT_OK;
+}
+
+int dmt_vertex_normals_info(dmt_ctx* ctx, uint64_t* triangles, uint64_t* smooth_triangles) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (triangles) *triangles = ctx->haveVtxNormals ? ctx->triCount : 0u;
+  if (smooth_triangles) *smooth_triangles = ctx->haveVtxNormals ? ctx->vtxSmoothCount : 0u;
+  return DMT_OK;
+}
+
+int dmt_smooth_normals(const float* xs, const float* ys, const float* zs, size_t count, float crease_degrees, float* n9_out) {
+  if (!std::isfinite(crease_degrees) || (count && (!xs || !ys || !zs || !n9_out))) return DMT_ERR_INVALID;
+  vnormals::smoothNormals(xs, ys, zs, count, crease_degrees, n9_out);
   return DMT_OK;
 }
 

@@ -71,7 +71,7 @@ __global__ void k_test_envmap(EnvView env, int n, float const* u2, float const* 
 
 // single path with a per-bounce log, one record per closest-hit ray (at most cap, *nOut written):
 //   rec12 = {tri (-1: miss), pos3, beta3, L3 before the bounce is shaded, depth, sampler dimension}
-template <bool MOTION>
+template <bool MOTION, bool VN = false>
 DMT_DEV void test_trace_log_body(int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   KArgs const k = kargs_base();
@@ -106,7 +106,7 @@ DMT_DEV void test_trace_log_body(int px, int py, int smp, float* rec12, int cap,
         r[4] = st.beta.x, r[5] = st.beta.y, r[6] = st.beta.z, r[7] = st.L.x, r[8] = st.L.y, r[9] = st.L.z;
         r[10] = float(st.depth), r[11] = float(st.rng.dim);
       }
-      ended = path_shade<MOTION ? kFeatMotion : 0u>(k, st, bestTri, bu, bv);
+      ended = path_shade<MOTION ? kFeatMotion : VN ? kFeatVtxNormals : 0u>(k, st, bestTri, bu, bv);
       if (ended) st.active = false;
     }
     if (ended && !st.hasShadow) break;
@@ -120,6 +120,30 @@ __global__ void k_test_trace_log(RenderParams P, int px, int py, int smp, float*
 }
 __global__ void k_test_trace_log_motion(RenderParams P, int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
   test_trace_log_body<true>(px, py, smp, rec12, cap, nOut, L3);
+}
+
+__global__ void k_test_trace_log_vn(RenderParams P, int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
+  test_trace_log_body<false, true>(px, py, smp, rec12, cap, nOut, L3);
+}
+
+// dmt_test_shading_normal: shading_normal_at of triangle tri[i] at (bu, bv) for a ray of direction rd3[i]; ngFacing is
+// the stored normal flipped against the ray as hit_finish flips it
+// MAPPED (dmt_test_shading_normal_mapped): then the material's normal map around it, as path_shade's *_tex_vn rows apply it
+template <bool MAPPED>
+__global__ void k_test_shading_normal(RenderParams P, int n, int32_t const* tri, float const* bu, float const* bv, float const* rd3, float* ns3) {
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  SceneView const sc = load_scene(k);
+  TriPost const T = sc.post[tri[i]];
+  f3 ng = mk3(T.nx, T.ny, T.nz);
+  if (dot(mk3(rd3[3 * i], rd3[3 * i + 1], rd3[3 * i + 2]), ng) > 0) ng = -ng;
+  f3 ns = shading_normal_at(k, tri[i], bu[i], bv[i], ng);
+  if constexpr (MAPPED) {
+    Rec32 rec = sc.bsdfs[T.matId];
+    ns = apply_material_textures<false>(k, rec, T.matId, tri[i], bu[i], bv[i], ns);
+  }
+  ns3[3 * i] = ns.x, ns3[3 * i + 1] = ns.y, ns3[3 * i + 2] = ns.z;
 }
 
 __global__ void k_test_tri(float const* xs, float const* ys, float const* zs, uint32_t n, f3 o, f3 d,
@@ -606,13 +630,15 @@ int dmt_test_texture_filter(dmt_ctx* ctx, int n, const int32_t* tri, const float
 int dmt_test_trace_log(dmt_ctx* ctx, int px, int py, int s, float* rec12, int cap, int* n_out, float* L3) {
   if (!ctx || !rec12 || cap <= 0 || !n_out || !L3) return DMT_ERR_INVALID;
   if (int const rc = sceneReady(ctx, "dmt_test_trace_log", true)) return rc;
+  if (ctx->ac.haveMotion && ctx->haveVtxNormals)
+    return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_log: vertex normals (dmt_upload_vertex_normals) together with motion blur are not supported");
   Probe p(ctx->device, 1);  // one path, walked by one lane
   ProbeOut<float> dr(p, rec12, 12 * size_t(cap)), dL(p, L3, 3);
   ProbeOut<int> dn(p, n_out, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
   RenderParams P = baseParams(ctx, p.threads(64));
   if (int const rc = motionParams(ctx, ctx->ac.haveMotion ? kFeatMotion : 0u, P)) return rc;  // (brute force: no tree)
-  hipLaunchKernelGGL(ctx->ac.haveMotion ? k_test_trace_log_motion : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
+  hipLaunchKernelGGL(ctx->ac.haveMotion ? k_test_trace_log_motion : ctx->haveVtxNormals ? k_test_trace_log_vn : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
                      dr.get(), cap, dn.get(), dL.get());
   return finishProbe(ctx, p);
 }
@@ -656,6 +682,34 @@ int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const floa
   hipLaunchKernelGGL(k_test_closest_at, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, useBvh, nrays, dO.get(), dD.get(), dT.get(), di.get(),
                      dt.get(), duv.get());
   return finishProbe(ctx, p);
+}
+
+static int probeShadingNormal(dmt_ctx* ctx, bool mapped, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3, float* ns3) {
+  if (!ctx || n < 0 || !tri || !bu || !bv || !rd3 || !ns3) return DMT_ERR_INVALID;
+  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: upload triangles first");
+  if (!ctx->haveVtxNormals) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: no vertex normals (dmt_upload_vertex_normals first)");
+  if (mapped) {
+    if (int const rc = sceneReady(ctx, "dmt_test_shading_normal_mapped", false)) return rc;
+    if (!ctx->haveBsdfs || ctx->texCount == 0 || ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount)
+      return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal_mapped: BSDFs and textures (matching the uploaded BSDFs / triangles) first");
+  }
+  for (int i = 0; i < n; ++i)
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_shading_normal: triangle index out of range");
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<int32_t> dTri(p, tri, 1);
+  ProbeIn<float> dBu(p, bu, 1), dBv(p, bv, 1), dRd(p, rd3, 3);
+  ProbeOut<float> dNs(p, ns3, 3);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  hipLaunchKernelGGL(mapped ? k_test_shading_normal<true> : k_test_shading_normal<false>, dim3(p.blocks(64)), dim3(64), 0, ctx->stream,
+                     baseParams(ctx, p.threads(64)), n, dTri.get(), dBu.get(), dBv.get(), dRd.get(), dNs.get());
+  return finishProbe(ctx, p);
+}
+int dmt_test_shading_normal(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3, float* ns3) {
+  return probeShadingNormal(ctx, false, n, tri, bu, bv, rd3, ns3);
+}
+int dmt_test_shading_normal_mapped(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3, float* ns3) {
+  return probeShadingNormal(ctx, true, n, tri, bu, bv, rd3, ns3);
 }
 
 int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t) {

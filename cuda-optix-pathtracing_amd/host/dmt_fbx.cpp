@@ -187,7 +187,8 @@ bool prop70(Node const& owner, char const* name, double* out, int n) {
 
 }  // namespace
 
-static bool readFbxMeshImpl(std::string const& path, std::vector<Triangle>& out, std::string* error, std::vector<float>* uv6) {
+static bool readFbxMeshImpl(std::string const& path, std::vector<Triangle>& out, std::string* error, std::vector<float>* uv6,
+                            std::vector<float>* n9) {
   auto bad = [&](std::string const& m) {
     if (error) *error = path + ": " + m;
     return false;
@@ -296,8 +297,45 @@ static bool readFbxMeshImpl(std::string const& path, std::vector<Triangle>& out,
     if (idx < 0 || size_t(2 * idx + 1) >= UV->size()) return;
     uv[0] = float((*UV)[size_t(2 * idx)]), uv[1] = float((*UV)[size_t(2 * idx + 1)]);
   };
+  // first LayerElementNormal (the reference's importer insists on one, core-mesh-parser.cpp:448-470): per polygon vertex or
+  // by control point, direct or through NormalsIndex, resolved as cornerUv resolves UVs.  A normal transforms by the inverse
+  // transpose of the 3x3 that transforms positions, A M S without the translation and the unit scale: A (a signed
+  // permutation) and M (a rotation) are their own inverse transposes, so it is A M S^-1; then normalised.
+  std::vector<double> const* NR = nullptr;
+  std::vector<double> const* NRI = nullptr;
+  bool nrByPolygonVertex = true, nrMappingKnown = true;
+  if (Node const* le = geom->child("LayerElementNormal")) {
+    if (Node const* a = le->child("Normals"))
+      if (!a->props.empty()) NR = &a->props[0].arr;
+    if (Node const* a = le->child("NormalsIndex"))
+      if (!a->props.empty() && !a->props[0].arr.empty()) NRI = &a->props[0].arr;
+    if (Node const* a = le->child("MappingInformationType"))
+      if (!a->props.empty()) {  // by polygon vertex or by control point; any other mapping (ByPolygon, AllSame, ...) is not read: flat
+        std::string const& mt = a->props[0].str;
+        nrByPolygonVertex = mt == "ByPolygonVertex";
+        nrMappingKnown = nrByPolygonVertex || mt == "ByVertice" || mt == "ByVertex";
+      }
+    if (Node const* a = le->child("ReferenceInformationType"))
+      if (!a->props.empty() && a->props[0].str == "Direct") NRI = nullptr;
+  }
+  bool const haveNormals = n9 && NR && !NR->empty() && nrMappingKnown;
+  auto cornerNormal = [&](size_t corner, uint32_t vertex, float* n) {
+    n[0] = n[1] = n[2] = 0.f;
+    size_t const k = nrByPolygonVertex ? corner : size_t(vertex);
+    int64_t const idx = NRI ? (k < NRI->size() ? int64_t((*NRI)[k]) : -1) : int64_t(k);
+    if (idx < 0 || size_t(3 * idx + 2) >= NR->size()) return;
+    double const x = S[0] != 0 ? (*NR)[size_t(3 * idx)] / S[0] : 0, y = S[1] != 0 ? (*NR)[size_t(3 * idx + 1)] / S[1] : 0,
+                 z = S[2] != 0 ? (*NR)[size_t(3 * idx + 2)] / S[2] : 0;
+    double const g[3] = {M[0][0] * x + M[0][1] * y + M[0][2] * z, M[1][0] * x + M[1][1] * y + M[1][2] * z, M[2][0] * x + M[2][1] * y + M[2][2] * z};
+    double const w[3] = {A[0][0] * g[0] + A[0][1] * g[1] + A[0][2] * g[2], A[1][0] * g[0] + A[1][1] * g[1] + A[1][2] * g[2],
+                         A[2][0] * g[0] + A[2][1] * g[1] + A[2][2] * g[2]};
+    double const len = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    if (!(len > 0) || !std::isfinite(len)) return;
+    n[0] = float(w[0] / len), n[1] = float(w[1] / len), n[2] = float(w[2] / len);
+  };
   out.clear();
   if (uv6) uv6->clear();
+  if (n9) n9->clear();
   std::vector<uint32_t> poly;
   std::vector<size_t> polyCorner;
   size_t corner = 0;
@@ -317,6 +355,13 @@ static bool readFbxMeshImpl(std::string const& path, std::vector<Triangle>& out,
           cornerUv(polyCorner[0], poly[0], uv), cornerUv(polyCorner[b], poly[b], uv + 2), cornerUv(polyCorner[c], poly[c], uv + 4);
           uv6->insert(uv6->end(), uv, uv + 6);
         }
+        if (haveNormals) {  // the corners the triangle was made of, in its (possibly reversed) order
+          float nn[9];
+          cornerNormal(polyCorner[0], poly[0], nn), cornerNormal(polyCorner[b], poly[b], nn + 3), cornerNormal(polyCorner[c], poly[c], nn + 6);
+          for (int v = 0; v < 3; ++v)  // a corner without a usable normal: the whole triangle stays flat (nine zeros)
+            if (nn[3 * v] == 0.f && nn[3 * v + 1] == 0.f && nn[3 * v + 2] == 0.f) std::fill(nn, nn + 9, 0.f);
+          n9->insert(n9->end(), nn, nn + 9);
+        }
       }
       poly.clear(), polyCorner.clear();
     }
@@ -326,15 +371,16 @@ static bool readFbxMeshImpl(std::string const& path, std::vector<Triangle>& out,
 }
 
 // Files are untrusted input: nothing escapes as an exception (allocation failure on a forged size, ...).
-bool readFbxMesh(std::string const& path, std::vector<Triangle>& out, std::string* error, std::vector<float>* uv6) {
+bool readFbxMesh(std::string const& path, std::vector<Triangle>& out, std::string* error, std::vector<float>* uv6, std::vector<float>* n9) {
   try {
-    return readFbxMeshImpl(path, out, error, uv6);
+    return readFbxMeshImpl(path, out, error, uv6, n9);
   } catch (std::exception const& e) {
     if (error) *error = path + ": " + e.what();
   } catch (...) {
     if (error) *error = path + ": unknown error";
   }
   out.clear();
+  if (n9) n9->clear();
   return false;
 }
 

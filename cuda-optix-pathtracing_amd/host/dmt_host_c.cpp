@@ -68,6 +68,24 @@ int64_t dmt_host_read_fbx(const char* path, float* out9, uint64_t cap_triangles,
     }
   return int64_t(tris.size());
 }
+// the vertex normals of the same mesh (9 floats per triangle, the triangles and corners of dmt_host_read_fbx); returns the
+// number of triangles that carry normals -- 0 for a file without a normal layer -- or -1 on failure.  Same protocol.
+int64_t dmt_host_read_fbx_normals(const char* path, float* out9, uint64_t cap_triangles, char* err, uint64_t err_cap) {
+  std::vector<Triangle> tris;
+  std::vector<float> n9;
+  std::string msg;
+  if (!path || !readFbxMesh(path, tris, &msg, nullptr, &n9)) {
+    if (err && err_cap) {
+      size_t const n = msg.size() < err_cap - 1 ? msg.size() : size_t(err_cap - 1);
+      memcpy(err, msg.data(), n);
+      err[n] = 0;
+    }
+    return -1;
+  }
+  size_t const count = n9.size() / 9;
+  if (out9 && count) memcpy(out9, n9.data(), 9 * sizeof(float) * (count < cap_triangles ? count : size_t(cap_triangles)));
+  return int64_t(count);
+}
 // PBRT-v4 subset front-end; same protocol as dmt_host_scene_load_json
 dmt_host_scene* dmt_host_scene_load_pbrt(const char* path, int* max_depth, int* samples_per_pixel, char* err, uint64_t err_cap) {
   auto* h = new (std::nothrow) dmt_host_scene();
@@ -103,6 +121,8 @@ const uint8_t* dmt_host_scene_tex_rgba(const dmt_host_scene* h) { return h->s.te
 const int32_t* dmt_host_scene_tex_desc(const dmt_host_scene* h) { return h->s.texDesc.data(); }
 const uint32_t* dmt_host_scene_mat_tex(const dmt_host_scene* h) { return h->s.matTex.data(); }
 const float* dmt_host_scene_tri_uv(const dmt_host_scene* h) { return h->s.triUv.data(); }
+// vertex normals (smooth shading): 9 floats per triangle, or null when no mesh of the scene carries any
+const float* dmt_host_scene_tri_normals(const dmt_host_scene* h) { return h->s.triNormals.empty() ? nullptr : h->s.triNormals.data(); }
 void dmt_host_scene_destroy(dmt_host_scene* h) { delete h; }
 
 uint64_t dmt_host_scene_triangle_count(const dmt_host_scene* h) { return h->s.triangleCount(); }

@@ -21,6 +21,7 @@
 // (dmt_upload_textures); a fractional or textured 'metallic' makes a record PAIR blended per hit (packMaterial).  FBX objects go through this build's own binary reader (dmt_fbx.cpp).
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -87,6 +88,12 @@ Vec3 xformVector(Mat4 const& M, Vec3 v) {
               M.m[2] * v.x + M.m[6] * v.y + M.m[10] * v.z};
 }
 
+// a unit normal through the inverse transpose of M's upper 3x3 (column-major m[16])
+Vec3 xformNormal(Mat4 const& M, Vec3 n) {
+  double const m[3][3] = {{M.m[0], M.m[4], M.m[8]}, {M.m[1], M.m[5], M.m[9]}, {M.m[2], M.m[6], M.m[10]}};
+  return normalThrough(m, n.x, n.y, n.z);
+}
+
 std::string directoryOf(std::string const& path) {
   size_t const p = path.find_last_of('/');
   return p == std::string::npos ? std::string(".") : path.substr(0, p);
@@ -131,6 +138,7 @@ struct LightProto {
 struct Mesh {
   std::vector<Triangle> tris;
   std::vector<float> uv;  // six per triangle
+  std::vector<float> normals;  // nine per triangle, or empty (FBX meshes with a normal layer)
   uint32_t material = 0;
 };
 struct Texture {
@@ -380,7 +388,7 @@ void parseObject(Value const& o, State& st, std::string const& baseDir) {
     onlyKeys(o, {"name", "type", "material", "path"}, "object '" + name + "'");
     if (!o.contains("path") || !o.at("path").isString()) fail("object '" + name + "' should have a 'path' string");
     std::string ferr;
-    if (!readFbxMesh(baseDir + "/" + o.at("path").string, mesh.tris, &ferr, &mesh.uv)) fail("object '" + name + "': " + ferr);
+    if (!readFbxMesh(baseDir + "/" + o.at("path").string, mesh.tris, &ferr, &mesh.uv, &mesh.normals)) fail("object '" + name + "': " + ferr);
   } else if (type == "primitive") {
     onlyKeys(o, {"name", "type", "material", "shape"}, "object '" + name + "'");
     if (!o.contains("shape") || !o.at("shape").isString()) fail("object '" + name + "' should have a 'shape' string");
@@ -490,6 +498,18 @@ void walkWorld(Value const& node, State& st, Scene& sc) {  // parseWorldTranform
           Triangle const& t = mesh.tris[k];
           emitTriangle(sc, Triangle{xformPoint(cur, t.v0), xformPoint(cur, t.v1), xformPoint(cur, t.v2)}, mesh.material);
           for (int j = 0; j < 6; ++j) sc.triUv.push_back(6 * k + size_t(j) < mesh.uv.size() ? mesh.uv[6 * k + size_t(j)] : 0.f);
+          float nn[9] = {};  // vertex normals through the instance transform; meshes without any stay flat (zeros)
+          if (9 * k + 8 < mesh.normals.size()) {
+            bool ok = true;
+            for (int v = 0; v < 3; ++v) {
+              float const* const q = &mesh.normals[9 * k + size_t(3 * v)];
+              Vec3 const w = xformNormal(cur, Vec3{q[0], q[1], q[2]});
+              nn[3 * v] = w.x, nn[3 * v + 1] = w.y, nn[3 * v + 2] = w.z;
+              ok = ok && (w.x != 0.f || w.y != 0.f || w.z != 0.f);
+            }
+            if (!ok) std::fill(nn, nn + 9, 0.f);
+          }
+          sc.triNormals.insert(sc.triNormals.end(), nn, nn + 9);
         }
       }
     } else if (key == "lights") {
@@ -656,6 +676,7 @@ bool loadJsonScene(std::string const& path, JsonScene& out, std::string* error) 
     } else {
       out.scene.triUv.clear();
     }
+    if (std::all_of(out.scene.triNormals.begin(), out.scene.triNormals.end(), [](float v) { return v == 0.f; })) out.scene.triNormals.clear();
     return true;
   } catch (Fail const& e) {
     if (error) *error = e.msg;

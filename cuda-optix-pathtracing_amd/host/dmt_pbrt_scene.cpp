@@ -16,6 +16,7 @@
 // on the side of the pbrt normal).  pbrt's raster x axis runs against the megakernel camera's (for LookAt's handedness),
 // so the scene is mirrored in the camera's right axis and every triangle rewound: the film then shows pbrt's picture.
 // The camera must be the megakernel's kind: perspective, up = +z.  fov maps exactly for square films.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -131,6 +132,11 @@ Vec3 apply(M4 const& M, double x, double y, double z) {
   return Vec3{float(M.m[0][0] * x + M.m[0][1] * y + M.m[0][2] * z + M.m[0][3]), float(M.m[1][0] * x + M.m[1][1] * y + M.m[1][2] * z + M.m[1][3]),
               float(M.m[2][0] * x + M.m[2][1] * y + M.m[2][2] * z + M.m[2][3])};
 }
+// a normal through the inverse transpose of M's upper 3x3, normalised; zero when that is not possible
+Vec3 applyNormal(M4 const& M, double x, double y, double z) {
+  double const m[3][3] = {{M.m[0][0], M.m[0][1], M.m[0][2]}, {M.m[1][0], M.m[1][1], M.m[1][2]}, {M.m[2][0], M.m[2][1], M.m[2][2]}};
+  return normalThrough(m, x, y, z);
+}
 
 struct GState {
   M4 ctm = identity();
@@ -218,6 +224,7 @@ bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error) 
     Vec3 eye{0, 0, 0}, look{0, 1, 0}, up{0, 0, 1};
     struct PendingTri {
       Vec3 v[3];
+      Vec3 n[3];  // "normal N" through the CTM; zeros without it
       int material;
       bool emissive;
       float L[3];
@@ -378,6 +385,9 @@ bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error) 
           fail("Shape \"trianglemesh\": \"integer indices\" is required for more than three points");
         }
         if (idx.size() % 3) fail("Shape \"trianglemesh\": the number of indices is not a multiple of 3");
+        Param const* N = find(ps, "normal", "N");
+        if (!N) N = find(ps, "normal3", "N");
+        if (N && N->nums.size() != P->nums.size()) fail("Shape \"trianglemesh\": \"normal N\" needs one normal per point");
         if (gs.material < 0) {
           if (defaultMaterial < 0) defaultMaterial = addMaterial(Params{}, "default material");
         }
@@ -387,7 +397,10 @@ bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error) 
             int const j = idx[i + size_t(k)];
             if (j < 0 || size_t(j) >= nv) fail("Shape \"trianglemesh\": index out of range");
             t.v[k] = apply(gs.ctm, P->nums[3 * size_t(j)], P->nums[3 * size_t(j) + 1], P->nums[3 * size_t(j) + 2]);
+            t.n[k] = N ? applyNormal(gs.ctm, N->nums[3 * size_t(j)], N->nums[3 * size_t(j) + 1], N->nums[3 * size_t(j) + 2]) : Vec3{0, 0, 0};
           }
+          for (int k = 0; k < 3; ++k)  // a corner without a usable normal: the triangle stays flat
+            if (t.n[k].x == 0.f && t.n[k].y == 0.f && t.n[k].z == 0.f) t.n[0] = t.n[1] = t.n[2] = Vec3{0, 0, 0};
           t.material = gs.material < 0 ? defaultMaterial : gs.material;
           t.emissive = gs.emissive;
           memcpy(t.L, gs.L, sizeof(t.L));
@@ -425,6 +438,11 @@ bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error) 
       out.scene.ys.insert(out.scene.ys.end(), {a.y, b.y, c.y, 0.f});
       out.scene.zs.insert(out.scene.zs.end(), {a.z, b.z, c.z, 0.f});
       out.scene.matId.push_back(uint32_t(t.material));
+      for (int k : {0, 2, 1}) {  // the corners' order above; a reflection is its own inverse transpose
+        Vec3 const n = t.n[k];
+        float const dn = n.x * rx + n.y * ry + n.z * rz;
+        out.scene.triNormals.insert(out.scene.triNormals.end(), {n.x - 2.f * dn * rx, n.y - 2.f * dn * ry, n.z - 2.f * dn * rz});
+      }
       if (t.emissive) {
         out.scene.areaTri.push_back(uint32_t(out.scene.matId.size() - 1));
         out.scene.areaLe.insert(out.scene.areaLe.end(), {t.L[0], t.L[1], t.L[2]});
@@ -445,6 +463,7 @@ bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error) 
     }
     for (Vec3 const& r : materials) out.scene.bsdfs.push_back(makeOrenNayar(r, 0.f));
     if (out.scene.bsdfs.empty()) out.scene.bsdfs.push_back(makeOrenNayar(Vec3{0.5f, 0.5f, 0.5f}, 0.f));
+    if (std::all_of(out.scene.triNormals.begin(), out.scene.triNormals.end(), [](float v) { return v == 0.f; })) out.scene.triNormals.clear();
     return true;
   } catch (Fail const& e) {
     if (error) *error = e.msg;

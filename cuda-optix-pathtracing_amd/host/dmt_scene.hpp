@@ -7,6 +7,7 @@
 // names, argument meaning and byte-identical packed records.  IEEE fp32 throughout.
 #pragma once
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -79,6 +80,10 @@ struct Scene {
   std::vector<int32_t> texDesc;
   std::vector<uint32_t> matTex;
   std::vector<float> triUv;
+  // optional vertex normals (smooth shading, dmt_upload_vertex_normals): empty, or 9 floats per triangle, the unit normals at
+  // vertices 0, 1, 2; triangles of meshes without normals are nine zeros (= flat).  uploadScene does NOT upload them
+  // (the files' normals are used only where the caller asks: main.cpp --shading-normals).
+  std::vector<float> triNormals;
 
   size_t triangleCount() const { return matId.size(); }
   // addModel + the material walk of triSoupFromTriangles: the FIRST mesh always gets material 0
@@ -119,7 +124,25 @@ struct PbrtScene {
 bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error = nullptr);
 // binary FBX (Kaydara 7100+): first mesh, fan-triangulated, Model TRS and unit scale applied (host/dmt_fbx.cpp); uv6: optional,
 // six floats per triangle from the mesh's first LayerElementUV (zeros when the file has none)
-bool readFbxMesh(std::string const& path, std::vector<Triangle>& out, std::string* error = nullptr, std::vector<float>* uv6 = nullptr);
+// n9: optional, nine floats per triangle from the mesh's first LayerElementNormal (by polygon vertex or by control point,
+// direct or indexed), pushed through the inverse transpose of the positions' 3x3 and normalised, in the triangles' corner
+// order; EMPTY when the file has no normal layer
+bool readFbxMesh(std::string const& path, std::vector<Triangle>& out, std::string* error = nullptr, std::vector<float>* uv6 = nullptr,
+                 std::vector<float>* n9 = nullptr);
+// A normal through the inverse transpose of the 3x3 m (row-major, acting on column vectors): the cofactor matrix over the
+// determinant's sign, normalised.  Zero when m is singular or the result is not finite.  What both scene loaders carry
+// vertex normals through their transforms with.
+inline Vec3 normalThrough(double const m[3][3], double x, double y, double z) {
+  double const C[3][3] = {{m[1][1] * m[2][2] - m[1][2] * m[2][1], m[1][2] * m[2][0] - m[1][0] * m[2][2], m[1][0] * m[2][1] - m[1][1] * m[2][0]},
+                          {m[0][2] * m[2][1] - m[0][1] * m[2][2], m[0][0] * m[2][2] - m[0][2] * m[2][0], m[0][1] * m[2][0] - m[0][0] * m[2][1]},
+                          {m[0][1] * m[1][2] - m[0][2] * m[1][1], m[0][2] * m[1][0] - m[0][0] * m[1][2], m[0][0] * m[1][1] - m[0][1] * m[1][0]}};
+  double const det = m[0][0] * C[0][0] + m[0][1] * C[0][1] + m[0][2] * C[0][2], sgn = det < 0 ? -1.0 : 1.0;
+  double const w[3] = {sgn * (C[0][0] * x + C[0][1] * y + C[0][2] * z), sgn * (C[1][0] * x + C[1][1] * y + C[1][2] * z),
+                       sgn * (C[2][0] * x + C[2][1] * y + C[2][2] * z)};
+  double const len = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  if (!(len > 0) || !std::isfinite(len)) return Vec3{};
+  return Vec3{float(w[0] / len), float(w[1] / len), float(w[2] / len)};
+}
 // 8-bit grey / RGB / RGBA non-interlaced PNG -> RGB floats, byte / 255 as the reference's loadImageAsRGB
 // (core-parser.cpp:156-167)
 bool readPngRgb(std::string const& path, std::vector<float>& rgb, int& width, int& height, std::string* error = nullptr);

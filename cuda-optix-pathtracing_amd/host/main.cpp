@@ -54,9 +54,21 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   bool shutterSet = false;    // --shutter OPEN CLOSE: the shutter interval of --motion-scene (dmt_set_shutter)
   float shutterOpen = 0.f, shutterClose = 1.f;
   std::string motionScenePath;  // --motion-scene <file>: the same scene at the end of the frame; its triangle positions become key 1
+  std::string shadingNormals = "off";  // --shading-normals off|file|smooth[:DEG] (dmt_upload_vertex_normals)
+  float creaseDegrees = 180.f;         // parsed from shadingNormals by validate()
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
 
+  // --shading-normals' value: off, file, smooth or smooth:DEG with 0 <= DEG <= 180
+  static bool parseShadingNormals(std::string const& a, float& crease) {
+    if (a == "off" || a == "file" || a == "smooth") return true;
+    if (a.compare(0, 7, "smooth:") != 0) return false;
+    char* end = nullptr;
+    float const v = std::strtof(a.c_str() + 7, &end);
+    if (a.size() == 7 || end != a.c_str() + a.size() || !std::isfinite(v) || v < 0.f || v > 180.f) return false;
+    crease = v;
+    return true;
+  }
   // --adaptive's value: a finite, non-negative number and nothing else
   static bool parseThreshold(std::string const& a, float& out) {
     char* end = nullptr;
@@ -96,6 +108,9 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (focusPixelSet && !(focusX >= 0.f && focusX < float(width) && focusY >= 0.f && focusY < float(height))) return "invalid --focus-pixel: outside the frame";
     if (shutterSet && !(std::isfinite(shutterOpen) && std::isfinite(shutterClose) && 0.f <= shutterOpen && shutterOpen <= shutterClose && shutterClose <= 1.f))
       return "invalid --shutter: expected 0 <= OPEN <= CLOSE <= 1";
+    if (float c = 180.f; !parseShadingNormals(shadingNormals, c))
+      return "invalid --shading-normals: expected off, file, smooth or smooth:DEG (0 <= DEG <= 180), got '" + shadingNormals + "'";
+    if (shadingNormals != "off" && !motionScenePath.empty()) return "--shading-normals and --motion-scene exclude each other";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
   }
@@ -141,7 +156,12 @@ void printHelp() {
       "  --motion-scene <file> -- Motion blur: a second scene file of the same kind as --scene whose triangle positions are\n"
       "                       where the triangles are at the end of the frame (same triangles, same order); every sample\n"
       "                       sees the scene at its own time in between\n"
-      "  --shutter <OPEN> <CLOSE> -- The part of the frame the shutter is open, 0 <= OPEN <= CLOSE <= 1 (default 0 1)");
+      "  --shutter <OPEN> <CLOSE> -- The part of the frame the shutter is open, 0 <= OPEN <= CLOSE <= 1 (default 0 1)\n"
+      "  --shading-normals <off|file|smooth[:DEG]> -- Smooth shading: interpolate per-vertex normals at every hit.  off (the\n"
+      "                       default): faceted, as the reference renders.  file: the normals of the scene's meshes (FBX normal\n"
+      "                       layers, PBRT \"normal N\"); meshes without any stay faceted.  smooth: normals computed from the\n"
+      "                       geometry, angle-weighted over the faces that meet at a vertex within DEG degrees of each\n"
+      "                       other (default 180: no crease)");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -168,6 +188,7 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--focus-pixel" && i + 2 < argc) c.focusX = std::strtof(argv[++i], nullptr), c.focusY = std::strtof(argv[++i], nullptr), c.focusPixelSet = true;
     else if (a == "--shutter" && i + 2 < argc) c.shutterOpen = std::strtof(argv[++i], nullptr), c.shutterClose = std::strtof(argv[++i], nullptr), c.shutterSet = true;
     else if (a == "--motion-scene" && more) c.motionScenePath = argv[++i];
+    else if (a == "--shading-normals" && more) c.shadingNormals = argv[++i];
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -272,6 +293,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (cfg.adaptive) Config::parseThreshold(cfg.adaptiveArg, cfg.threshold);
+  Config::parseShadingNormals(cfg.shadingNormals, cfg.creaseDegrees);
   std::printf("Parsed Configuration:\n - Width:     %d\n - Height:    %d\n - SPP:       %d\n - KSPP:      %d\n - Log Level: %s\n",
               cfg.width, cfg.height, cfg.spp, cfg.kspp, cfg.logLevel.c_str());
   bool const verbose = cfg.logLevel == "verbose";
@@ -280,6 +302,20 @@ int main(int argc, char** argv) {
   if (cfg.textureFilter) scene.camera.spp = cfg.spp;  // the filter's footprint scale follows the frame's samples per pixel
   if (cfg.lensRadiusSet) scene.lensRadius = cfg.lensRadius;
   if (cfg.focusDistanceSet) scene.focusDistance = cfg.focusDistance;
+  std::vector<float> vertexNormals;  // --shading-normals: 9 floats per triangle for dmt_upload_vertex_normals
+  if (cfg.shadingNormals == "file") {
+    if (scene.triNormals.size() != 9 * scene.triangleCount()) {
+      std::fprintf(stderr, "--shading-normals file: the scene's meshes carry no vertex normals (try --shading-normals smooth)\n");
+      return 1;
+    }
+    vertexNormals = scene.triNormals;
+  } else if (cfg.shadingNormals != "off") {
+    vertexNormals.resize(9 * scene.triangleCount());
+    if (dmt_smooth_normals(scene.xs.data(), scene.ys.data(), scene.zs.data(), scene.triangleCount(), cfg.creaseDegrees, vertexNormals.data()) != DMT_OK) {
+      std::fprintf(stderr, "--shading-normals smooth: dmt_smooth_normals failed\n");
+      return 1;
+    }
+  }
   double const loadMs = msSince(tLoad);
 
   // one context per GPU; DMT_CLI_SHARE_DEVICE=1 (tests on a one-GPU box) maps all ranks onto --gpu-ordinal
@@ -302,6 +338,8 @@ int main(int argc, char** argv) {
     if (cfg.shutterSet && dmt_set_shutter(ctx, cfg.shutterOpen, cfg.shutterClose) != DMT_OK) return fail(ctx, "dmt_set_shutter");
     if (!cfg.motionScenePath.empty() && dmt_set_motion(ctx, key1.xs.data(), key1.ys.data(), key1.zs.data(), key1.triangleCount()) != DMT_OK)
       return fail(ctx, "dmt_set_motion");
+    if (!vertexNormals.empty() && dmt_upload_vertex_normals(ctx, vertexNormals.data(), scene.triangleCount()) != DMT_OK)
+      return fail(ctx, "dmt_upload_vertex_normals");
   }
   if (cfg.focusPixelSet) {  // autofocus on the first context (every context holds the whole scene), then the lens of all
     float d = 0.f;

@@ -20,7 +20,7 @@ def load_host_library():
                      "dmt_host_scene_ys", "dmt_host_scene_zs", "dmt_host_scene_mat_ids", "dmt_host_scene_bsdfs",
                      "dmt_host_scene_lights", "dmt_host_scene_infinite_lights", "dmt_host_scene_camera",
                      "dmt_host_scene_load_json", "dmt_host_scene_env_rgb", "dmt_host_scene_load_pbrt",
-                     "dmt_host_scene_area_tri", "dmt_host_scene_area_le"):
+                     "dmt_host_scene_area_tri", "dmt_host_scene_area_le", "dmt_host_scene_tri_normals"):
             getattr(lib, name).restype = C.c_void_p
         lib.dmt_host_scene_random_triangles.argtypes = [C.c_uint64, C.c_uint64]
         lib.dmt_host_scene_random_triangles_ex.argtypes = [C.c_uint64, C.c_uint64, C.c_float]
@@ -82,6 +82,10 @@ class HostScene:
             self.tex_desc = _copy(L.dmt_host_scene_tex_desc(h), np.int32, 3 * nt).reshape(-1, 3)
             self.mat_tex = _copy(L.dmt_host_scene_mat_tex(h), np.uint32, 4 * self.bsdfs.shape[0]).reshape(-1, 4)
             self.tri_uv = _copy(L.dmt_host_scene_tri_uv(h), np.float32, 6 * n).reshape(-1, 6)
+        # vertex normals (smooth shading): [n, 9], rows of zeros for triangles of meshes without normals; None when no mesh
+        # carries any.  upload_scene uploads them only when asked (vertex_normals=True).
+        tn = L.dmt_host_scene_tri_normals(h)
+        self.tri_normals = _copy(tn, np.float32, 9 * n).reshape(-1, 9) if tn else None
         L.dmt_host_scene_destroy(h)
 
     @property
@@ -111,6 +115,21 @@ def read_fbx(path):
         raise ValueError(err.value.decode())
     out = np.zeros((n, 3, 3), np.float32)
     L.dmt_host_read_fbx(str(path).encode(), out.ctypes.data_as(C.c_void_p), C.c_uint64(n), err, C.c_uint64(len(err)))
+    return out
+
+
+def read_fbx_normals(path):
+    """Vertex normals of the same mesh -> float32 [n, 3, 3] (triangle, corner, xyz), unit length, through the inverse
+    transpose of the transform read_fbx applies; an empty [0, 3, 3] array for a file without a normal layer."""
+    L = load_host_library()
+    L.dmt_host_read_fbx_normals.restype = C.c_int64
+    err = C.create_string_buffer(1024)
+    n = L.dmt_host_read_fbx_normals(str(path).encode(), None, C.c_uint64(0), err, C.c_uint64(len(err)))
+    if n < 0:
+        raise ValueError(err.value.decode())
+    out = np.zeros((n, 3, 3), np.float32)
+    if n:
+        L.dmt_host_read_fbx_normals(str(path).encode(), out.ctypes.data_as(C.c_void_p), C.c_uint64(n), err, C.c_uint64(len(err)))
     return out
 
 
@@ -195,6 +214,7 @@ class ArrayScene:
         self.env_rgb = None if env_rgb is None else np.ascontiguousarray(env_rgb, np.float32)
         self.env_quat, self.env_scale = np.array([0, 0, 0, 1], np.float32), 1.0
         self.lens = None  # (lens_radius, focus_distance) to have upload_scene set the lens; None leaves the context's
+        self.tri_normals = None  # [n, 9] vertex normals for upload_scene(vertex_normals=True)
 
     tri_count = HostScene.tri_count
     width = HostScene.width

@@ -176,6 +176,47 @@ int dmt_motion_positions(const float* xs0, const float* ys0, const float* zs0, c
  * decoded child box contains the vertices below it at key 0 and at key 1.  DMT_ERR_STATE when one fails. */
 int dmt_motion_bvh_validate(const float* xs0, const float* ys0, const float* zs0, const float* xs1, const float* ys1, const float* zs1,
                             size_t count, int* node_count, int* pair_count, int* depth);
+/* ---- smooth shading: per-vertex normals interpolated at every hit (opt-in, beyond the reference) ---- */
+/* Without vertex normals every surface is faceted: the shading normal ns is the triangle's geometric normal unless a normal
+ * map moves it.  With them ns is interpolated at the hit; the geometric normal ng keeps every role it has (ray offsets, the
+ * ng argument of the BSDF routines, light sampling, texture footprints).  Without an upload every film is byte for byte
+ * what it was before these calls existed.
+ *
+ * The record.  16 bytes per triangle, read by one 16-byte load per hit: the three normals in the 2 x 16 bit octahedral
+ * mapping of the light records (what the device's decoder inverts; the reference's encoder clamps a component to [0, 1]
+ * before rounding and so cannot carry a normal: the record is written with the clamp at 65535) and a flags word, bit 0 =
+ * smooth.  The round trip moves a normal by less than 1e-4 rad.
+ *
+ * The shading normal at a hit with barycentrics (bu, bv) of vertices 1 and 2, for the geometric normal ngFacing already
+ * flipped against the ray:  n = (1 - bu - bv) n0 + bu n1 + bv n2, normalised, and negated if dot(n, ngFacing) < 0 -- it
+ * lives in the hemisphere of the ray-facing geometric normal whichever way the file's normals and winding point.  A flat
+ * triangle, and a sum whose squared length is not finite or below 1e-12, give ngFacing bit for bit.  A normal map perturbs
+ * the smooth normal: its tangent frame is taken around it.  No terminator softening.
+ *
+ * Scope.  Vertex normals have the plain, env-map and texture megakernel rows with and without the env map (_vn, _env_vn,
+ * _tex_vn, _env_tex_vn and their _bvh twins): dmt_render with the sampler table as before, dmt_render_adaptive,
+ * dmt_test_trace_samples / dmt_test_trace_log, and dmt_render_aovs, whose normal plane then holds the smooth normal.
+ * Refused with DMT_ERR_STATE and a message that names the combination: vertex normals with emissive triangles, with blend
+ * materials, with either light tree, with the first-hit texture filter, with motion blur, with the wavefront BVH strategy,
+ * with dmt_render_stats / dmt_render_profile. */
+/* n9: 9 floats per triangle, the normals at vertices 0, 1, 2 in the vertex order of dmt_upload_triangles; any length, they
+ * are normalised here.  A triangle whose nine floats are all exactly zero is flat and keeps its geometric normal, so one
+ * scene can mix flat walls and smooth meshes.  DMT_ERR_STATE before any upload of triangles; DMT_ERR_INVALID when count
+ * differs from the uploaded triangle count, or when any other normal is not finite or shorter than 1e-6 (the message names
+ * the triangle).  Synchronises the stream first.
+ * Dropped by dmt_upload_triangles.  KEPT by dmt_update_vertices and dmt_update_vertices_device, like UVs, materials and
+ * emissive triangles: a caller who deforms the mesh uploads the normals of the new shape. */
+int dmt_upload_vertex_normals(dmt_ctx* ctx, const float* n9, size_t count);
+/* drops the normals; every film is then byte for byte what it was before dmt_upload_vertex_normals */
+int dmt_clear_vertex_normals(dmt_ctx* ctx);
+/* *triangles = the number of records (0 without normals), *smooth_triangles = those not flat.  Either pointer may be null. */
+int dmt_vertex_normals_info(dmt_ctx* ctx, uint64_t* triangles, uint64_t* smooth_triangles);
+/* host only (no GPU): vertex normals for a soup that comes without any (layout of dmt_upload_triangles in, of
+ * dmt_upload_vertex_normals out).  Corners with bit-equal positions are welded.  A corner's normal is the normalised sum of
+ * the stored face normals, normalize(cross(e1, e0)) in fp32, of the triangles around that position, each weighted by its
+ * interior angle at that corner; only faces whose normal lies within crease_degrees (finite; clamped to [0, 180]) of the
+ * corner's own face contribute.  Zero-area triangles contribute nothing and come out flat (nine zeros). */
+int dmt_smooth_normals(const float* xs, const float* ys, const float* zs, size_t count, float crease_degrees, float* n9_out);
 /* depth cap of the bounce loop; the reference hard-codes 32 (megakernel.cu:154) */
 int dmt_set_limits(dmt_ctx* ctx, int max_depth);
 int dmt_set_accel(dmt_ctx* ctx, int mode);
@@ -582,6 +623,14 @@ int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
  * dmt_test_closest_hit keeps answering for key 0. */
 int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* time, int32_t* tri_index, float* t,
                             float* uv2);
+/* shading_normal_at of the uploaded vertex normals: the shading normal ns3 (n x 3) of triangle tri[i] at barycentrics
+ * (bu, bv) for a ray of direction rd3[i]; ngFacing is the stored geometric normal flipped against rd as at a hit.
+ * DMT_ERR_STATE without vertex normals. */
+int dmt_test_shading_normal(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3, float* ns3);
+/* the same, then the material's normal map (level 0) applied around it as the *_tex_vn rows apply it; needs BSDFs and
+ * textures uploaded */
+int dmt_test_shading_normal_mapped(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3,
+                                   float* ns3);
 /* dmt_camera_project on the device, under the camera of dmt_set_camera */
 int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, float* depth);
 int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* wo3,

@@ -73,9 +73,11 @@ def _pint(name, v):
     return N('P', [('S', name), ('S', 'int'), ('S', 'Integer'), ('S', ''), ('I', int(v))])
 
 
-def write(path, verts, polys, T=(0, 0, 0), R=(0, 0, 0), S=(1, 1, 1), unit=1.0, axes=None):
+def write(path, verts, polys, T=(0, 0, 0), R=(0, 0, 0), S=(1, 1, 1), unit=1.0, axes=None, normals=None, normals_mapping='ByPolygonVertex'):
     """axes: None (no axis properties: the file counts as already in the importer's target system) or
-    dict(up=(axis, sign), front=(axis, sign), coord=(axis, sign)) -> GlobalSettings UpAxis/.../CoordAxisSign."""
+    dict(up=(axis, sign), front=(axis, sign), coord=(axis, sign)) -> GlobalSettings UpAxis/.../CoordAxisSign.
+    normals: None, or object-space normals -> a LayerElementNormal (Direct) under normals_mapping: one per polygon vertex
+    for 'ByPolygonVertex', one per control point for 'ByVertice'."""
     idx = []
     for p in polys:
         idx += p[:-1] + [~p[-1]]
@@ -88,7 +90,10 @@ def write(path, verts, polys, T=(0, 0, 0), R=(0, 0, 0), S=(1, 1, 1), unit=1.0, a
         N('GlobalSettings', [], [N('Properties70', [], gprops)]),
         N('Objects', [], [
             N('Geometry', [('L', gid), ('S', b'MESH_Fixture\x00\x01Geometry'), ('S', 'Mesh')],
-              [N('Vertices', [('d', verts.reshape(-1))]), N('PolygonVertexIndex', [('i', idx)])]),
+              [N('Vertices', [('d', verts.reshape(-1))]), N('PolygonVertexIndex', [('i', idx)])] +
+              ([] if normals is None else [N('LayerElementNormal', [('I', 0)], [
+                  N('Version', [('I', 101)]), N('Name', [('S', '')]), N('MappingInformationType', [('S', normals_mapping)]),
+                  N('ReferenceInformationType', [('S', 'Direct')]), N('Normals', [('d', np.asarray(normals, np.float64).reshape(-1))])])])),
             N('Model', [('L', mid), ('S', b'Fixture\x00\x01Model'), ('S', 'Mesh')],
               [N('Properties70', [], [P70('Lcl Translation', 'Lcl Translation', *T), P70('Lcl Rotation', 'Lcl Rotation', *R),
                                       P70('Lcl Scaling', 'Lcl Scaling', *S)])]),
@@ -132,6 +137,34 @@ def expected_triangles(verts, polys, T, R, S, unit, axes=None):
     return np.array(tris, np.float32)
 
 
+def radial_normals(verts, polys):
+    """Object-space normals of a sphere about the origin, one per polygon vertex in PolygonVertexIndex order."""
+    n = np.array([verts[i] for p in polys for i in p], np.float64)
+    return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+def expected_normals(verts, polys, R, S, axes=None):
+    """The normals a correct reader returns for radial_normals, [triangle, corner, 3] float64: each pushed through the
+    inverse transpose of the positions' 3x3 (A M S; no translation, no unit scale) and normalised, the corners permuted as
+    expected_triangles permutes them."""
+    rx, ry, rz = np.radians(R)
+    Rx = np.array([[1, 0, 0], [0, np.cos(rx), -np.sin(rx)], [0, np.sin(rx), np.cos(rx)]])
+    Ry = np.array([[np.cos(ry), 0, np.sin(ry)], [0, 1, 0], [-np.sin(ry), 0, np.cos(ry)]])
+    Rz = np.array([[np.cos(rz), -np.sin(rz), 0], [np.sin(rz), np.cos(rz), 0], [0, 0, 1]])
+    A = np.eye(3) if axes is None else axis_matrix(axes)
+    L = A @ (Rz @ Ry @ Rx) @ np.diag(np.array(S, np.float64))
+    G = np.linalg.inv(L).T
+    mirrored = np.linalg.det(A) < 0
+    out = []
+    for p in polys:
+        nn = [G @ (verts[i] / np.linalg.norm(verts[i])) for i in p]
+        nn = [v / np.linalg.norm(v) for v in nn]
+        for k in range(1, len(p) - 1):
+            b, c = (k + 1, k) if mirrored else (k, k + 1)
+            out.append([nn[0], nn[b], nn[c]])
+    return np.array(out, np.float64)
+
+
 FIXTURE = dict(T=(0.5, -0.25, 1.0), R=(20.0, -35.0, 50.0), S=(1.5, 1.0, 0.75), unit=2.0)
 # three axis systems a file may declare (GlobalSettings), each on the same transformed sphere
 AXIS_FIXTURES = {
@@ -150,4 +183,7 @@ if __name__ == "__main__":
     write(out / "ball.fbx", v2, p2)
     for name, axes in AXIS_FIXTURES.items():
         write(out / f"uv_sphere_{name}.fbx", v, p, axes=axes, **FIXTURE)
+    # the same sphere with radial normals, Y-up right-handed (a reflection: the winding reverses) under the non-uniform
+    # Lcl Scaling of FIXTURE (the inverse transpose matters)
+    write(out / "uv_sphere_normals_maya_yup_rh.fbx", v, p, axes=AXIS_FIXTURES["maya_yup_rh"], normals=radial_normals(v, p), **FIXTURE)
     print("wrote", sorted(x.name for x in out.iterdir()))
