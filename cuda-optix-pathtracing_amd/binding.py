@@ -68,7 +68,7 @@ EXPORTED_SYMBOLS = [
     "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
-    "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_test_triangle_intersect",
+    "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_brute_cull_box_records", "dmt_cull_box_test", "dmt_test_triangle_intersect",
     "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_bsdf_ng", "dmt_test_material", "dmt_test_light", "dmt_test_half",
     "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
     "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
@@ -417,6 +417,37 @@ def brute_cull_box_plan(xs, ys, zs, mat_id, enable=True):
         raise DmtError(f"dmt_brute_cull_box_plan failed ({rc})")
     return [(int(fc[2 * k]), int(fc[2 * k + 1]), tuple(float(x) for x in box[6 * k:6 * k + 3]),
              tuple(float(x) for x in box[6 * k + 3:6 * k + 6])) for k in range(nc.value)]
+
+
+def brute_cull_box_records(xs, ys, zs, mat_id, enable=True):
+    """Host-only: the box clusters as planned and as the device reads them, a list of (box [6] = lo xyz, hi xyz as
+    brute_cull_box_plan gives them, record [6] = centre xyz, half-width xyz), float32 arrays."""
+    lib = load_library()
+    xs, ys, zs = _f32(xs), _f32(ys), _f32(zs)
+    mat = np.ascontiguousarray(mat_id, np.uint32)
+    n = xs.size // 4
+    nc, box, rec = C.c_uint32(), np.zeros(72, np.float32), np.zeros(72, np.float32)
+    rc = lib.dmt_brute_cull_box_records(_p(xs), _p(ys), _p(zs), _p(mat), C.c_size_t(n), int(bool(enable)), C.byref(nc), _p(box), _p(rec))
+    if rc != 0:
+        raise DmtError(f"dmt_brute_cull_box_records failed ({rc})")
+    return [(box[6 * k:6 * k + 6].copy(), rec[6 * k:6 * k + 6].copy()) for k in range(nc.value)]
+
+
+def cull_box_test(record, origins, dirs, tmax):
+    """Host-only: the device's box bound test (brute_clusters) for rays [n, 3] / [n, 3] / tmax [n] against one box record
+    (centre xyz, half-width xyz); returns a bool array, True = the cluster's triangles would be tested for the ray."""
+    lib = load_library()
+    rec = np.ascontiguousarray(record, np.float32).reshape(6)
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tmax, np.float32).reshape(-1)
+    if not (o.shape[0] == d.shape[0] == t.shape[0]):
+        raise ValueError("cull_box_test: origins, dirs and tmax differ in length")
+    out = np.zeros(o.shape[0], np.uint8)
+    rc = lib.dmt_cull_box_test(_p(rec), _p(o), _p(d), _p(t), C.c_size_t(o.shape[0]), _p(out))
+    if rc != 0:
+        raise DmtError(f"dmt_cull_box_test failed ({rc})")
+    return out.astype(bool)
 
 
 def envmap_tables(rgb):

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
@@ -56,7 +57,7 @@ constexpr uint32_t kCullMaxTris = 44;      // LDS copy of the culled triangles, 
 constexpr uint32_t kCullSlotBits = 6;      // a closest-hit key holds (original index << 6 | LDS slot): kCullMaxTris <= 64
 constexpr uint32_t kCullMaxIndex = 1u << (32 - kCullSlotBits);  // no culling for soups of more triangles
 struct CullCluster {                       // 48 B, read by scalar loads in the bound tests
-  float b[6];                              // sphere: centre xyz and squared inflated radius; box: inflated lo xyz, hi xyz
+  float b[6];                              // sphere: centre xyz and squared inflated radius; box: centre xyz, half-width xyz
   uint32_t box;                            // 0: sphere bound, 1: box bound
   uint32_t first, count;                   // original triangle indices [first, first + count)
   uint32_t slot, magic;                    // first slot of its triangles in the LDS copy; ceil(2^32 / count)
@@ -1110,10 +1111,73 @@ DMT_DEV void cull_stage(KArgs k) {
   __syncthreads();
 }
 
-// 1 / d for the slab test, with |d| raised to FLT_MIN first: the reciprocal is finite, so (plane - o) * inv is never
-// 0 * inf = NaN.  A zero component becomes a tiny one of the same sign: the ray leans into the slab it lies in, and an
-// origin on a face gives t = 0 on that face -- a hit, never a miss.  (1 / FLT_MIN = 2^126 is a normal float.)
-DMT_DEV float slab_rcp(float d) { return rcp_(copysignf(fmaxf(fabsf(d), 0x1p-126f), d)); }
+// ---- the box bound (device: brute_clusters; host: dmt_cull_box_test runs the same functions) ----
+// A box record holds centre c and half-width h per axis.  With A = 1 / d and B = -(o A), the ray meets the axis' two planes
+// at mid -+ h |A|, mid = c A + B: no compare orders the two.  Per ray (cull_ray): A, B, E2 (|A| the compiler forms again
+// at every box, 6 v_and: packed fmas take no abs).  Per box and axis (cull_box_axis): three fmas.  Per ray and box
+// (cull_box_accept): max3, min3, two clamps, one fma and max(near_xyz, kCullTLo) <= min(far_xyz, tmax) * kCullTSlack + E2.
+//
+// |d| is raised to kCullDirFloor = 2^-60 before the reciprocal, so A, B and E2 stay finite for coordinates below 2^60 (with
+// a floor of FLT_MIN, o A overflows for |o| >= 4 and c A + B is inf - inf).  A smaller component becomes one of that size
+// and the same sign: the ray leans into the slab it lies in, and an origin on a face gives mid -+ h |A| = 0 on that face up
+// to E2 -- a hit, never a miss.  Raising |d| shrinks the axis' interval towards t = 0; a ray that meets the vertex box with
+// such a component starts within 2^-60 t of its slab and at least m inside the record's, whose far plane then lies beyond
+// 2^60 m, past every t the other axes allow.
+//
+// Conservativeness.  Let R = [c - h, c + h] in exact arithmetic; the planner makes R hold its inflated box.
+// u = 2^-24.  The three roundings of an axis bound, near' = fl(fl(c A - fl(o A)) -+ h |A|):
+//   fl(o A):        at most u |B|;
+//   the mid fma:    at most u |mid'| <= u (|c| |A| + |B|);
+//   the bound fma:  at most u (|mid'| + h |A|) <= u ((|c| + h) |A| + |B|);
+// in all at most 3 u |B| + u (2 |c| + h) |A| (second-order terms are 2^-22 of that).  The second term is the plane moved by
+// at most u (2 |c| + h) <= 2^-23 (extent + |coordinate|_max) = m / 16 in space: the computed bounds are those of a box R-
+// that still holds the vertex box inflated by 15/16 m, which is what remains for what m was sized for (mt_valid's slack,
+// the float edges, Moeller-Trumbore's rounding across the ray: a margin of about 7.5 instead of 8).  The first term has no
+// bound relative to a small t -- an origin near a plane, a camera far from the scene -- and is covered by
+// E = kCullErrK max(|Bx|, |By|, |Bz|) per ray, kCullErrK = 2^-21 = 8 u: every bound is within 3/8 E of R-'s, so
+// max near' <= max near + 3/8 E <= min far + 3/8 E <= min far' + 3/4 E, and the two clamps are exact.  The test adds
+// E2 = 2 E: of the 5/4 E to spare, 2^-8 (3/8 E) goes to the slack factor multiplying a far' that is 3/8 E low, the rest is
+// margin (a factor 8/3 on the rounding terms).  A is the reciprocal instruction's, within 1 ulp of 1 / d: a relative error
+// of every t of the axis, which kCullTSlack covers with room, as it covers the rounding of the t that mt_core9 computes.
+// Flushed denormals move a bound by at most 2^-126, far below 2^-8 kCullTLo.
+constexpr float kCullDirFloor = 0x1p-60f;
+constexpr float kCullErrK = 0x1p-21f;
+DMT_HD float cull_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+DMT_HD v2f cull_fma(float a, v2f b, v2f c) { return __builtin_elementwise_fma(v2f{a, a}, b, c); }
+DMT_HD float cull_abs(float a) { return __builtin_fabsf(a); }
+DMT_HD v2f cull_abs(v2f a) { return __builtin_elementwise_abs(a); }
+DMT_HD float cull_max(float a, float b) { return __builtin_fmaxf(a, b); }
+DMT_HD v2f cull_max(v2f a, v2f b) { return __builtin_elementwise_max(a, b); }
+// the direction component whose reciprocal the caller takes (device: v_rcp_f32, host: a division)
+DMT_HD float cull_dir(float d) { return __builtin_copysignf(__builtin_fmaxf(__builtin_fabsf(d), kCullDirFloor), d); }
+template <class T>
+struct CullRay {
+  T ax, ay, az;  // A
+  T rx, ry, rz;  // |A|
+  T bx, by, bz;  // B
+  T e2;          // 2 E
+};
+template <class T>
+DMT_HD CullRay<T> cull_ray(T ox, T oy, T oz, T ax, T ay, T az) {
+  CullRay<T> r;
+  r.ax = ax, r.ay = ay, r.az = az;
+  r.rx = cull_abs(ax), r.ry = cull_abs(ay), r.rz = cull_abs(az);
+  r.bx = -(ox * ax), r.by = -(oy * ay), r.bz = -(oz * az);
+  r.e2 = (2.0f * kCullErrK) * cull_max(cull_max(cull_abs(r.bx), cull_abs(r.by)), cull_abs(r.bz));
+  return r;
+}
+template <class T>
+DMT_HD void cull_box_axis(float c, float h, T a, T r, T b, T& near, T& far) {
+  T const mid = cull_fma(c, a, b);
+  near = cull_fma(-h, r, mid), far = cull_fma(h, r, mid);
+}
+// tmax: the segment's end times kCullTSlack
+DMT_HD bool cull_box_accept(float nx, float ny, float nz, float fx, float fy, float fz, float tmax, float e2) {
+  float const n = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(nx, ny), nz), kCullTLo);
+  float const f = __builtin_fminf(__builtin_fminf(__builtin_fminf(fx, fy), fz), tmax);
+  return n <= cull_fma(f, kCullTSlack, e2);
+}
+DMT_DEV float slab_rcp(float d) { return rcp_(cull_dir(d)); }
 
 // The culled clusters for the lane's ray pair, after the packed loop has run over the always list (h holds its result,
 // with the always list's position in h.tri).  The clusters are taken kCullGroup at a time, which bounds the owner lists.  For
@@ -1138,9 +1202,13 @@ DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, Br
   s_cullOcc[w] = 0;
   float tmaxC = h.bt * kCullTSlack;
   float const tmaxS = st.smax * kCullTSlack;
-  v2f const ix = {slab_rcp(st.rp.dx.x), slab_rcp(st.rp.dx.y)};
-  v2f const iy = {slab_rcp(st.rp.dy.x), slab_rcp(st.rp.dy.y)};
-  v2f const iz = {slab_rcp(st.rp.dz.x), slab_rcp(st.rp.dz.y)};
+  // the rays' constants of the two bound tests, once per call.  Unconditional: a uniform branch on the kinds of cluster
+  // the plan has would cost a select per register, and the optimiser had hoisted the sphere test's pair out of the
+  // loop for every plan before.
+  CullRay<v2f> const cr = cull_ray(st.rp.ox, st.rp.oy, st.rp.oz, v2f{slab_rcp(st.rp.dx.x), slab_rcp(st.rp.dx.y)},
+                                   v2f{slab_rcp(st.rp.dy.x), slab_rcp(st.rp.dy.y)}, v2f{slab_rcp(st.rp.dz.x), slab_rcp(st.rp.dz.y)});
+  v2f const dd = st.rp.dx * st.rp.dx + st.rp.dy * st.rp.dy + st.rp.dz * st.rp.dz;
+  v2f const idd = rcp_(dd);
 #if DMT_CULL_COUNTS
   unsigned long long cnt[16] = {};
   cnt[0] = 1, cnt[1] = __popcll(__ballot(doC)), cnt[2] = __popcll(__ballot(doS));
@@ -1158,22 +1226,21 @@ DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, Br
         cl.box = r.box, cl.count = r.count;
         bool hitC, hitS;
         if (cl.box) {
-          // slabs: per axis the t of the two faces, near = max over the axes' entries and the segment start, far = min over
-          // the exits and the segment end.  Each t is within a few ulps (relative) of the exact one, near > 0, so
-          // near <= far * kCullTSlack keeps every segment that meets the box.
-          v2f const x0 = (cl.b[0] - st.rp.ox) * ix, x1 = (cl.b[3] - st.rp.ox) * ix;
-          v2f const y0 = (cl.b[1] - st.rp.oy) * iy, y1 = (cl.b[4] - st.rp.oy) * iy;
-          v2f const z0 = (cl.b[2] - st.rp.oz) * iz, z1 = (cl.b[5] - st.rp.oz) * iz;
-          float const nC = fmaxf(fmaxf(fminf(x0.x, x1.x), fminf(y0.x, y1.x)), fmaxf(fminf(z0.x, z1.x), kCullTLo));
-          float const fC = fminf(fminf(fmaxf(x0.x, x1.x), fmaxf(y0.x, y1.x)), fminf(fmaxf(z0.x, z1.x), tmaxC));
-          float const nS = fmaxf(fmaxf(fminf(x0.y, x1.y), fminf(y0.y, y1.y)), fmaxf(fminf(z0.y, z1.y), kCullTLo));
-          float const fS = fminf(fminf(fmaxf(x0.y, x1.y), fmaxf(y0.y, y1.y)), fminf(fmaxf(z0.y, z1.y), tmaxS));
-          hitC = doC && nC <= fC * kCullTSlack, hitS = doS && nS <= fS * kCullTSlack;
+          // slabs: per axis the entry and the exit, near = max over the entries and the segment start, far = min over the
+          // exits and the segment end (see cull_ray for the arithmetic and what keeps it conservative)
+          v2f nx, ny, nz, fx, fy, fz;
+          cull_box_axis(cl.b[0], cl.b[3], cr.ax, cr.rx, cr.bx, nx, fx);
+          cull_box_axis(cl.b[1], cl.b[4], cr.ay, cr.ry, cr.by, ny, fy);
+          cull_box_axis(cl.b[2], cl.b[5], cr.az, cr.rz, cr.bz, nz, fz);
+          // (both verdicts first, then the masks: behind a short-circuit && the test sits in a branch of its own, where
+          // the compiler quiets every min / max input again)
+          bool const aC = cull_box_accept(nx.x, ny.x, nz.x, fx.x, fy.x, fz.x, tmaxC, cr.e2.x);
+          bool const aS = cull_box_accept(nx.y, ny.y, nz.y, fx.y, fy.y, fz.y, tmaxS, cr.e2.y);
+          hitC = doC & aC, hitS = doS & aS;
         } else {
           v2f const wx = cl.b[0] - st.rp.ox, wy = cl.b[1] - st.rp.oy, wz = cl.b[2] - st.rp.oz;
-          v2f const dd = st.rp.dx * st.rp.dx + st.rp.dy * st.rp.dy + st.rp.dz * st.rp.dz;
           v2f const ww = wx * wx + wy * wy + wz * wz;
-          v2f tc = (wx * st.rp.dx + wy * st.rp.dy + wz * st.rp.dz) * rcp_(dd);
+          v2f tc = (wx * st.rp.dx + wy * st.rp.dy + wz * st.rp.dz) * idd;
           tc.x = fminf(fmaxf(tc.x, 0.f), tmaxC);
           tc.y = fminf(fmaxf(tc.y, 0.f), tmaxS);
           v2f const ex = wx - tc * st.rp.dx, ey = wy - tc * st.rp.dy, ez = wz - tc * st.rp.dz;
@@ -2513,10 +2580,10 @@ std::vector<CullCluster> planBruteCull(float const* xs, float const* ys, float c
 //  * e0 / e1 are stored as floats: the tested triangle's vertices are up to 2^-24 |e| <= 1.1e-7 extent off the soup's;
 //  * the rounding of the Moeller-Trumbore arithmetic across the ray: a few ulps of the coordinates, 2^-22 |coordinate|_max.
 // Along the ray the device allows for its own rounding: the segment runs from kCullTLo = (1 - 2^-8) 1e-4 to the end t
-// times kCullTSlack = 1 + 2^-8, and the slab test keeps near <= far * kCullTSlack; every t it or mt_core9 computes is
-// within a few ulps of the exact one (relative), far below 2^-8.  An axis-aligned wall has zero thickness and 2m after
-// inflation; m stays well below kCullTLo, so a ray that leaves a wall at more than ~m / 1e-4 radians to its plane (Cornell:
-// 0.057) is not handed that wall again.
+// times kCullTSlack = 1 + 2^-8, and the slab test keeps near <= far * kCullTSlack + 2 E (cull_ray: the error term of its
+// centre / half-width arithmetic, which also takes m / 16 of the inflation).  A wall is 2m thick after inflation, m well
+// below kCullTLo: a ray leaving it at more than ~m / 1e-4 rad to its plane (Cornell: 0.057) gets it again only through E.
+// The record stores the box as centre and half-width, the half-width rounded up until [c - hw, c + hw] holds the box.
 // A run becomes a cluster when its box (before inflation) has a surface area of at most kCullBoxMaxAreaFrac of the scene
 // box's: a random line that meets the scene box meets a convex body inside it with probability S_body / S_scene (Cauchy),
 // and a compacted test costs about 2.7 packed ones.  Cornell's walls are exactly 1/3.  Clusters are taken in
@@ -2524,7 +2591,7 @@ std::vector<CullCluster> planBruteCull(float const* xs, float const* ys, float c
 constexpr uint32_t kCullBoxMinTris = 2;  // the task decode needs count >= 2; a lone triangle costs about one bound test anyway
 constexpr double kCullBoxMaxAreaFrac = 0.35;
 std::vector<CullCluster> planBruteCullBox(float const* xs, float const* ys, float const* zs, uint32_t const* mat, uint32_t n,
-                                          std::vector<CullCluster> const& spheres) {
+                                          std::vector<CullCluster> const& spheres, std::vector<float>* planBox = nullptr) {
   std::vector<CullCluster> out;
   if (n == 0) return out;
   auto vtx = [&](uint32_t t, int k, int a) { return double((a == 0 ? xs : a == 1 ? ys : zs)[4 * size_t(t) + k]); };
@@ -2556,12 +2623,27 @@ std::vector<CullCluster> planBruteCullBox(float const* xs, float const* ys, floa
       ext = std::fmax(ext, bhi[a] - blo[a]), cmax = std::fmax(cmax, std::fmax(std::fabs(blo[a]), std::fabs(bhi[a])));
     double const m = 0x1p-19 * (ext + cmax);
     CullCluster cl{};
+    float pl[3], ph[3];
+    bool holds = true;
     for (int a = 0; a < 3; ++a) {
       float l = float(blo[a] - m), h = float(bhi[a] + m);
       if (double(l) > blo[a] - m) l = std::nextafter(l, -HUGE_VALF);
       if (double(h) < bhi[a] + m) h = std::nextafter(h, HUGE_VALF);
-      cl.b[a] = l, cl.b[3 + a] = h;
+      pl[a] = l, ph[a] = h;
+      // the record: centre and half-width with [c - hw, c + hw] holding [l, h] in exact arithmetic.  The doubles below
+      // are within 2^-53 of the exact values, the float above them plus one more step is 2^-24 beyond.
+      float const c = float(0.5 * (double(l) + double(h)));
+      double const hd = std::fmax(double(c) - double(l), double(h) - double(c));
+      float hw = float(hd);
+      if (double(hw) < hd) hw = std::nextafter(hw, HUGE_VALF);
+      hw = std::nextafter(hw, HUGE_VALF);
+      holds = holds && std::isfinite(c) && std::isfinite(hw) && (long double)c - (long double)hw <= (long double)l &&
+              (long double)c + (long double)hw >= (long double)h;
+      cl.b[a] = c, cl.b[3 + a] = hw;
     }
+    assert(holds);
+    if (!holds) continue;  // (NDEBUG builds) the run stays in the always list
+    if (planBox) planBox->insert(planBox->end(), {pl[0], pl[1], pl[2], ph[0], ph[1], ph[2]});
     cl.box = 1;
     cl.first = first, cl.count = count, cl.slot = culled;
     cl.magic = uint32_t(((uint64_t(1) << 32) + count - 1) / count);
@@ -3539,19 +3621,50 @@ int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const
   return DMT_OK;
 }
 
-int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
-                            uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box) {
+// cluster_box: the planner's inflated boxes (lo xyz, hi xyz); cluster_record: what the device reads (centre xyz, half-width xyz)
+static int cullBoxPlan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                       uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box, float* cluster_record) {
   if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
   std::vector<CullCluster> cl;
+  std::vector<float> planBox;
   if (enable && count < kCullMaxIndex) {
     std::vector<CullCluster> const spheres = planBruteCull(xs, ys, zs, mat_id, uint32_t(count), true, nullptr);
-    cl = planBruteCullBox(xs, ys, zs, mat_id, uint32_t(count), spheres);
+    cl = planBruteCullBox(xs, ys, zs, mat_id, uint32_t(count), spheres, &planBox);
   }
   *cluster_count = uint32_t(cl.size());
   for (size_t k = 0; k < cl.size(); ++k) {
     if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
-    if (cluster_box)
-      for (int a = 0; a < 6; ++a) cluster_box[6 * k + size_t(a)] = cl[k].b[a];
+    for (int a = 0; a < 6; ++a) {
+      if (cluster_box) cluster_box[6 * k + size_t(a)] = planBox[6 * k + size_t(a)];
+      if (cluster_record) cluster_record[6 * k + size_t(a)] = cl[k].b[a];
+    }
+  }
+  return DMT_OK;
+}
+
+int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                            uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box) {
+  return cullBoxPlan(xs, ys, zs, mat_id, count, enable, cluster_count, cluster_first_count, cluster_box, nullptr);
+}
+
+int dmt_brute_cull_box_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                               uint32_t* cluster_count, float* cluster_box, float* cluster_record) {
+  return cullBoxPlan(xs, ys, zs, mat_id, count, enable, cluster_count, nullptr, cluster_box, cluster_record);
+}
+
+// The device's box bound test on the host, ray by ray: cull_ray, cull_box_axis and cull_box_accept as brute_clusters calls
+// them, with a division where the device has v_rcp_f32 (within 1 ulp of it) and denormals kept.
+int dmt_cull_box_test(const float* record6, const float* origins, const float* dirs, const float* tmax, size_t count, uint8_t* accept) {
+  if (!record6 || (count && (!origins || !dirs || !tmax || !accept))) return DMT_ERR_INVALID;
+  for (size_t i = 0; i < count; ++i) {
+    float const* const o = origins + 3 * i;
+    float const* const d = dirs + 3 * i;
+    CullRay<float> const cr = cull_ray(o[0], o[1], o[2], 1.0f / cull_dir(d[0]), 1.0f / cull_dir(d[1]), 1.0f / cull_dir(d[2]));
+    float nx, ny, nz, fx, fy, fz;
+    cull_box_axis(record6[0], record6[3], cr.ax, cr.rx, cr.bx, nx, fx);
+    cull_box_axis(record6[1], record6[4], cr.ay, cr.ry, cr.by, ny, fy);
+    cull_box_axis(record6[2], record6[5], cr.az, cr.rz, cr.bz, nz, fz);
+    accept[i] = cull_box_accept(nx, ny, nz, fx, fy, fz, tmax[i] * kCullTSlack, cr.e2) ? 1 : 0;
   }
   return DMT_OK;
 }

@@ -513,6 +513,18 @@ int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const
 int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count,
                             int enable, uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box);
 
+/* host-only: the same box clusters in both forms, cluster_box[6k .. 6k + 5] as above and cluster_record[6k .. 6k + 5] =
+ * centre xyz, half-width xyz: what the device's bound test reads.  [centre - half-width, centre + half-width] holds the
+ * inflated box in exact arithmetic.  Either array may be null. */
+int dmt_brute_cull_box_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count,
+                               int enable, uint32_t* cluster_count, float* cluster_box, float* cluster_record);
+
+/* host-only: the device's box bound test, the same inline functions compiled for the host (a division stands for the
+ * device's reciprocal instruction).  record6 = one cluster_record; ray i: origins[3i .. 3i + 2], dirs[3i .. 3i + 2] and the
+ * segment end tmax[i] (inf allowed); accept[i] = 1 when the brute-force pass would test the cluster's triangles for it. */
+int dmt_cull_box_test(const float* record6, const float* origins, const float* dirs, const float* tmax, size_t count,
+                      uint8_t* accept);
+
 /* ---- denoiser (an explicit post-process; beyond the reference) ----------------------------- */
 /* Feature pass: camera samples 0 .. aov_spp-1 of EVERY pixel of the frame (the film's own camera rays; dmt_set_partition
  * and regions do not apply), closest hit under the current accel mode (brute force and BVH give bit-identical planes).
