@@ -39,6 +39,8 @@ from .binding import (  # noqa: F401
     motion_positions,
     motion_bvh_validate,
     smooth_normals,
+    opacity_eval,
+    OPACITY_NONE,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

@@ -83,6 +83,7 @@ EXPORTED_SYMBOLS = [
     "dmt_motion_bvh_validate", "dmt_test_shutter_times", "dmt_test_closest_hit_at",
     "dmt_upload_vertex_normals", "dmt_clear_vertex_normals", "dmt_vertex_normals_info", "dmt_smooth_normals",
     "dmt_test_shading_normal", "dmt_test_shading_normal_mapped",
+    "dmt_upload_opacity", "dmt_clear_opacity", "dmt_opacity_info", "dmt_opacity_eval", "dmt_test_opacity", "dmt_test_closest_hit_opacity",
 ]
 
 # dmt_set_sampler_table modes (include/dmt_hip.h)
@@ -234,6 +235,28 @@ def smooth_normals(xs, ys, zs, crease_degrees=180.0):
     if rc != 0:
         raise DmtError(f"dmt_smooth_normals failed ({rc})")
     return out
+
+
+OPACITY_NONE = 0xFFFFFFFF  # dmt_upload_opacity: the material is opaque
+
+
+def opacity_eval(tex_rgba, tex_desc, tex, uv6, bu, bv, cutoff=0.5):
+    """Host only (dmt_opacity_eval): the cutout lookup of texture tex[i] (textures as upload_textures takes them) for a
+    triangle with UVs uv6[i] at barycentrics (bu[i], bv[i]), the device's bit for bit.  Returns (alpha8 [n] float32,
+    passes [n] bool), passes = alpha8 >= cutoff * 255."""
+    lib = load_library()
+    rgba = np.ascontiguousarray(tex_rgba, np.uint8).reshape(-1, 4)
+    desc = np.ascontiguousarray(tex_desc, np.int32).reshape(-1, 3)
+    tex, uv6 = _i32(tex).reshape(-1), _f32(uv6).reshape(-1, 6)
+    bu, bv = _f32(bu).reshape(-1), _f32(bv).reshape(-1)
+    n = tex.shape[0]
+    assert uv6.shape[0] == n and bu.shape[0] == n and bv.shape[0] == n
+    a, ok = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    rc = lib.dmt_opacity_eval(_p(rgba), C.c_uint64(rgba.shape[0]), _p(desc), C.c_uint32(desc.shape[0]), int(n), _p(tex), _p(uv6), _p(bu),
+                              _p(bv), C.c_float(cutoff), _p(a), _p(ok))
+    if rc != 0:
+        raise DmtError(f"dmt_opacity_eval failed ({rc})")
+    return a, ok.astype(bool)
 
 
 # dmt_set_texture_filter modes (include/dmt_hip.h)
@@ -605,6 +628,43 @@ class Renderer:
         self._check(self._lib.dmt_vertex_normals_info(self._ctx, C.byref(t), C.byref(sm)), "dmt_vertex_normals_info")
         return {"triangles": t.value, "smooth_triangles": sm.value}
 
+    def upload_opacity(self, mat_opacity_tex, cutoff=0.5):
+        """Alpha cutouts (dmt_upload_opacity): per BSDF the index of the uploaded texture whose A channel is its opacity,
+        OPACITY_NONE = opaque.  A hit counts iff the A channel there is at least cutoff * 255.  After upload_textures;
+        dropped by upload_triangles, upload_bsdfs and upload_textures, kept by update_vertices*."""
+        m = np.ascontiguousarray(mat_opacity_tex, np.uint32).reshape(-1)
+        self._check(self._lib.dmt_upload_opacity(self._ctx, _p(m), C.c_uint32(m.shape[0]), C.c_float(cutoff)), "dmt_upload_opacity")
+
+    def clear_opacity(self):
+        """Drops the opacity (dmt_clear_opacity): every film is again what it was before the upload."""
+        self._check(self._lib.dmt_clear_opacity(self._ctx), "dmt_clear_opacity")
+
+    def opacity_info(self):
+        """dmt_opacity_info as a dict: cutout_triangles, cutout_materials, cutoff (zeros without opacity)."""
+        t, m, c = C.c_uint64(), C.c_uint32(), C.c_float()
+        self._check(self._lib.dmt_opacity_info(self._ctx, C.byref(t), C.byref(m), C.byref(c)), "dmt_opacity_info")
+        return {"cutout_triangles": t.value, "cutout_materials": m.value, "cutoff": c.value}
+
+    def test_opacity(self, tri, bu, bv):
+        """dmt_test_opacity: (alpha8 [n], passes [n] bool) of triangle tri[i] at (bu, bv), as the cutout rows compute them."""
+        tri, bu, bv = _i32(tri).reshape(-1), _f32(bu).reshape(-1), _f32(bv).reshape(-1)
+        n = tri.shape[0]
+        assert bu.shape[0] == n and bv.shape[0] == n
+        a, ok = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+        self._check(self._lib.dmt_test_opacity(self._ctx, int(n), _p(tri), _p(bu), _p(bv), _p(a), _p(ok)), "dmt_test_opacity")
+        return a, ok.astype(bool)
+
+    def test_closest_hit_opacity(self, o, d, tmax):
+        """dmt_test_closest_hit_opacity: ray i under the cutout rule and the current accel mode -> (tri [n], t [n], uv [n, 2],
+        occluded [n] bool); occluded = some passing hit has t < tmax[i]."""
+        o, d = _f32(o, (-1, 3)), _f32(d, (-1, 3))
+        n = o.shape[0]
+        tmax = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        idx, t, uv, occ = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+        self._check(self._lib.dmt_test_closest_hit_opacity(self._ctx, n, _p(o), _p(d), _p(tmax), _p(idx), _p(t), _p(uv), _p(occ)),
+                    "dmt_test_closest_hit_opacity")
+        return idx, t, uv, occ.astype(bool)
+
     def test_shading_normal(self, tri, bu, bv, rd, mapped=False):
         """The shading normal [n, 3] the vertex-normal rows compute for triangle tri[i] at (bu, bv) under a ray of direction
         rd[i] (dmt_test_shading_normal); mapped: with the material's normal map applied around it."""
@@ -624,10 +684,11 @@ class Renderer:
         self._check(self._lib.dmt_focus_distance_at(self._ctx, C.c_float(fx), C.c_float(fy), C.byref(d)), "dmt_focus_distance_at")
         return d.value
 
-    def upload_scene(self, scene, vertex_normals=False):
+    def upload_scene(self, scene, vertex_normals=False, opacity=True):
         """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays; a scene with a `lens`
         (lens_radius, focus_distance), as the loaders report one, sets the context's lens too.  vertex_normals: also
-        upload the scene's `tri_normals` (smooth shading); off by default, the files' normals are not used unasked."""
+        upload the scene's `tri_normals` (smooth shading); off by default, the files' normals are not used unasked.
+        opacity: upload the scene's `mat_opacity` / `opacity_cutoff` (alpha cutouts) when it carries them."""
         self.upload_triangles(scene.xs, scene.ys, scene.zs, scene.mat_id)
         if vertex_normals:
             tn = getattr(scene, "tri_normals", None)
@@ -649,6 +710,9 @@ class Renderer:
             self.upload_textures(scene.tex_rgba, scene.tex_desc, scene.mat_tex, scene.tri_uv)
         else:
             self.upload_textures(None, None, None, None)
+        mo = getattr(scene, "mat_opacity", None)
+        if opacity and mo is not None and len(mo):
+            self.upload_opacity(mo, float(getattr(scene, "opacity_cutoff", 0.5)))
 
     def upload_textures(self, tex_rgba, tex_desc, mat_tex, tri_uv):
         """SURVEY 8f-1 image textures (layout: include/dmt_hip.h dmt_upload_textures); all None clears."""

@@ -129,6 +129,11 @@ DMT_DEV PairHit pair_test_at(BvhView const& bv, uint32_t idx, f3 o, f3 d, NoMoti
 DMT_DEV PairHit pair_test_at(BvhView const& bv, uint32_t idx, f3 o, f3 d, LeafMotion m) {
   return pair_test_motion(bv.pairs + idx, m.delta + idx, m.time, o, d);
 }
+// Any-hit rule of a leaf policy: does the valid hit (bu, bv) on ORIGINAL triangle `orig` count?  Static and motion leaves accept
+// every valid hit (the call folds away); the cutout policy (opacity.hpp, found by argument-dependent lookup) asks the
+// triangle's opacity texture.  Called only for a half the step would otherwise accept.
+DMT_DEV bool leaf_accept(NoMotion, uint32_t, float, float) { return true; }
+DMT_DEV bool leaf_accept(LeafMotion const&, uint32_t, float, float) { return true; }
 
 struct TraversalCounters {  // per-lane work counters (stats build of the kernel only)
   uint32_t nodes = 0, tris = 0;
@@ -291,11 +296,12 @@ DMT_DEV void trav_leaf_ref(BvhView const& bv, Traversal& tv, f3 o, f3 d, uint32_
   PairHit const h = pair_test_at(bv, ref & ~kBvhLeafFlag, o, d, m);
   if constexpr (STATS) tc->tris += h.orig0 != h.orig1 ? 2u : 1u;  // a one-triangle leaf repeats its triangle
   if (tv.phase == TR_CLOSEST) {  // brute force keeps the lowest index among equal t (strict < in index order; -1 = none is the largest)
-    if (h.valid0 && (h.t.x < tv.tlim || (h.t.x == tv.tlim && h.orig0 < uint32_t(tv.bestTri))))
+    if (h.valid0 && (h.t.x < tv.tlim || (h.t.x == tv.tlim && h.orig0 < uint32_t(tv.bestTri))) && leaf_accept(m, h.orig0, h.u.x, h.v.x))
       tv.tlim = h.t.x, tv.bu = h.u.x, tv.bv = h.v.x, tv.bestTri = int(h.orig0);
-    if (h.valid1 && (h.t.y < tv.tlim || (h.t.y == tv.tlim && h.orig1 < uint32_t(tv.bestTri))))
+    if (h.valid1 && (h.t.y < tv.tlim || (h.t.y == tv.tlim && h.orig1 < uint32_t(tv.bestTri))) && leaf_accept(m, h.orig1, h.u.y, h.v.y))
       tv.tlim = h.t.y, tv.bu = h.u.y, tv.bv = h.v.y, tv.bestTri = int(h.orig1);
-  } else if ((h.valid0 && h.t.x < tv.tlim) || (h.valid1 && h.t.y < tv.tlim)) {
+  } else if ((h.valid0 && h.t.x < tv.tlim && leaf_accept(m, h.orig0, h.u.x, h.v.x)) ||
+             (h.valid1 && h.t.y < tv.tlim && leaf_accept(m, h.orig1, h.u.y, h.v.y))) {
     tv.tlim = -1.f;
   }
 }

@@ -76,10 +76,12 @@ DMT_DEV void aov_material(KArgs k, Hit const& hit, int tri, float bu, float bv, 
 // MOTION (k_aov_motion, launched while key 1 is present): every sample is traced at its own time, as the film's is, so the
 // planes blur where the film blurs; the post-hit record is the triangle's at that time.
 // VN (k_aov_vn, launched while vertex normals are present): the normal plane accumulates the smooth shading normal.
-template <bool MOTION, bool VN = false>
+// CUT (k_aov_cut, launched while opacity is present): the camera rays see through the holes, as the film's do, so the planes
+// show what lies behind a cutout.
+template <bool MOTION, bool VN = false, bool CUT = false>
 DMT_DEV void aov_body(AovArgs const& A) {
   KArgs const k = kargs_base();
-  if constexpr (!MOTION) {
+  if constexpr (!MOTION && !CUT) {
     if (!A.useBvh) cull_stage(k);
   }
   uint32_t const lane = threadIdx.x & 63u, gtid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -111,6 +113,11 @@ DMT_DEV void aov_body(AovArgs const& A) {
           trace_pair_bvh_motion(k, st, alive, false, v2f{tm, tm}, gtid, best, bu, bv, occluded, &bt);
         else
           trace_pair_brute_motion(k, st, alive, false, v2f{tm, tm}, best, bu, bv, occluded, &bt);
+      } else if constexpr (CUT) {
+        if (A.useBvh)
+          trace_pair_bvh_cut(k, st, alive, false, gtid, best, bu, bv, occluded);
+        else
+          trace_pair_brute_cut(k, st, alive, false, best, bu, bv, occluded);
       } else {
         if (A.useBvh)
           trace_pair_bvh(k, st, alive, false, gtid, best, bu, bv, occluded);
@@ -148,6 +155,7 @@ DMT_DEV void aov_body(AovArgs const& A) {
 __global__ void __launch_bounds__(256) k_aov(RenderParams P, AovArgs A) { aov_body<false>(A); }
 __global__ void __launch_bounds__(256) k_aov_motion(RenderParams P, AovArgs A) { aov_body<true>(A); }
 __global__ void __launch_bounds__(256) k_aov_vn(RenderParams P, AovArgs A) { aov_body<false, true>(A); }
+__global__ void __launch_bounds__(256) k_aov_cut(RenderParams P, AovArgs A) { aov_body<false, false, true>(A); }
 
 // A-trous passes (spatial SVGF).  Colour and variance travel together as one float4 (rgb, v) per pixel, ping-ponged
 // between passes; the AOVs stay fp32 (no packing), so tests/denoise_ref.py restates the filter on the same numbers.

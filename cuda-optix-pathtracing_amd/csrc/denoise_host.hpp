@@ -220,6 +220,8 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
     return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
   if (ctx->haveVtxNormals && ctx->ac.haveMotion)
     return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: vertex normals (dmt_upload_vertex_normals) together with motion blur are not supported");
+  if (ctx->haveOpacity && (ctx->ac.haveMotion || ctx->haveVtxNormals))
+    return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: opacity textures (dmt_upload_opacity) together with motion blur or vertex normals are not supported");
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   if (int const rcT = useBvh ? requireTree(ctx, "dmt_render_aovs") : DMT_OK) return rcT;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -241,7 +243,7 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   RenderParams P = baseParams(ctx, threads);
   uint32_t const motionMask = ctx->ac.haveMotion ? kFeatMotion | (useBvh ? kFeatBvh : 0u) : 0u;  // the samples' times, as the film's rows
   if (int const rcM = motionParams(ctx, motionMask, P)) return rcM;
-  hipLaunchKernelGGL(ctx->ac.haveMotion ? k_aov_motion : ctx->haveVtxNormals ? k_aov_vn : k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
+  hipLaunchKernelGGL(ctx->haveOpacity ? k_aov_cut : ctx->ac.haveMotion ? k_aov_motion : ctx->haveVtxNormals ? k_aov_vn : k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
   HIP_TRY(ctx, hipGetLastError());
   ctx->dn.aovW = ctx->filmW, ctx->dn.aovH = ctx->filmH;
   ctx->dn.aovSurface = true;

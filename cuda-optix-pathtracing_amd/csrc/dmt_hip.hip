@@ -75,6 +75,7 @@ struct CullView {
 };
 
 struct VtxNormalRec;  // vnormals.hpp
+struct OpacityRec;    // opacity.hpp
 
 struct RenderParams {
   SceneView scene;
@@ -139,6 +140,10 @@ struct RenderParams {
   // smooth shading (dmt_upload_vertex_normals): [triangle] three octahedral normals and a flags word; read by the *_vn
   // kernels only, at the hit.  After `motion`, so that no other field moves
   VtxNormalRec const* vtxNormals;
+  // alpha cutouts (dmt_upload_opacity): [triangle] the cutout record and the cutoff in byte units; read by the *_cut kernels
+  // only, at candidate hits.  After `vtxNormals`, so that no other field moves
+  OpacityRec const* opacity;
+  float opacityCutoff8;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -744,6 +749,7 @@ constexpr uint32_t kFeatLightTree = 1u << 6;     // SURVEY 8f-4 light tree (ligh
 constexpr uint32_t kFeatLightTreeRef = 1u << 7;  // the reference-semantics light tree (light_tree_ref.hpp)
 constexpr uint32_t kFeatTexFilter = 1u << 8;     // first-hit MIP / EWA texture filtering; with kFeatTex or kFeatBlend only
 constexpr uint32_t kFeatMotion = 1u << 9;        // motion blur: triangles at the sample's time (motion.hpp); plain and env-map rows only
+constexpr uint32_t kFeatCutout = 1u << 11;       // alpha cutouts: candidate hits filtered by an opacity texture (opacity.hpp); the texture rows only
 constexpr uint32_t kFeatVtxNormals = 1u << 10;   // smooth shading: ns interpolated from per-vertex normals (vnormals.hpp); plain, env, tex rows
 
 // the post-hit record path_shade works on: the uploaded one, or under kFeatMotion the triangle at the sample's time
@@ -759,6 +765,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   static_assert(!((F & kFeatTex) && (F & kFeatBlend)), "kFeatBlend carries the texture code itself");
   static_assert(!(F & kFeatTexFilter) || (F & (kFeatTex | kFeatBlend)), "the texture filter needs the texture code");
   static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
+  static_assert(!(F & kFeatCutout) || ((F & kFeatTex) && !(F & ~(kFeatCutout | kFeatBvh | kFeatEnv | kFeatTex))), "cutouts: the texture rows only");
   static_assert(!(F & kFeatVtxNormals) || !(F & ~(kFeatVtxNormals | kFeatBvh | kFeatEnv | kFeatTex)), "vertex normals: the plain, env-map and texture rows only");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
@@ -1357,6 +1364,8 @@ DMT_DEV void trace_pair_brute(KArgs k, PathState const& st, bool doC, bool doS, 
   bestTri = h.tri, bu = h.bu, bv = h.bv, occluded = h.occluded;
 }
 
+#include "opacity.hpp"
+
 struct LaneStats {  // stats build only
   uint32_t samples = 0, closest = 0, shadow = 0, bounces = 0;
   TraversalCounters tc;
@@ -1402,7 +1411,11 @@ DMT_DEV void lane_step(KArgs k, uint32_t gtid, PathState& st, Sink&& sink, LaneS
   int bestTri;
   float bu, bv;
   bool occluded;
-  if constexpr ((F & kFeatMotion) && (F & kFeatBvh))
+  if constexpr ((F & kFeatCutout) && (F & kFeatBvh))
+    trace_pair_bvh_cut(k, st, doC, doS, gtid, bestTri, bu, bv, occluded);
+  else if constexpr (F & kFeatCutout)
+    trace_pair_brute_cut(k, st, doC, doS, bestTri, bu, bv, occluded);
+  else if constexpr ((F & kFeatMotion) && (F & kFeatBvh))
     trace_pair_bvh_motion(k, st, doC, doS, v2f{motion_time(), motion_time_shadow()}, gtid, bestTri, bu, bv, occluded);
   else if constexpr (F & kFeatMotion)
     trace_pair_brute_motion(k, st, doC, doS, v2f{motion_time(), motion_time_shadow()}, bestTri, bu, bv, occluded);
@@ -1997,7 +2010,7 @@ DMT_DEV void megakernel_body() {
 #if DMT_SECTION_TIMING
   if (lane == 0) s_sectLast[threadIdx.x >> 6] = __builtin_readcyclecounter();  // (LDS is not zeroed: without this, start-up holds what the block before left there)
 #endif
-  if constexpr (!MOTION) cull_stage(Pk);  // (the motion pass is the plain loop: the clusters' bounds are of key 0)
+  if constexpr (!MOTION && !(F & kFeatCutout)) cull_stage(Pk);  // (the motion pass is the plain loop: the clusters' bounds are of key 0; so is the cutout pass)
 #if DMT_SECTION_TIMING
   if (lane < 16) s_sectAcc[threadIdx.x >> 6][lane] = 0;
   sect_mark(15);
@@ -2117,6 +2130,7 @@ DMT_DEV void megakernel_body_bvh() {
       // in its shadow phase -- read from LDS at the leaf step; nothing of it is live across node steps or shading
       auto const leafMotion = [&]() {
         if constexpr (MOTION) return LeafMotion{kargs(Pk)->motion.pairDelta, tv.phase == TR_SHADOW ? motion_time_shadow() : motion_time()};
+        else if constexpr (F & kFeatCutout) return LeafCutout{load_cutout(Pk)};  // cutout rows: fetched at the leaf step, live nowhere else
         else return NoMotion{};
       };
       int const shadeThreshold = kargs(Pk)->shadeThreshold > 1 ? kargs(Pk)->shadeThreshold : 1;  // (0 would never let the wave traverse)
@@ -2189,6 +2203,8 @@ DMT_DEV void megakernel_body_bvh() {
 // _vn: the parent row's body and bounds with a shading normal of its own (three more live VGPRs through path_shade, as the
 // _tex rows already carry); _env_vn and _bvh_env_vn run one wave per SIMD fewer than _env / _bvh_env, which is what keeps
 // them within their parents' scratch.
+// _cut: the parent _tex row's body with the cutout trace, one wave per SIMD fewer than the parent: at the parents' bounds
+// (where the parents themselves spill) the rows would spill VGPRs; at these they do not.
 #define DMT_MEGAKERNELS(X)                                                          \
   X(, 0, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                                   \
   X(_bvh, kFeatBvh, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh)                \
@@ -2233,7 +2249,11 @@ DMT_DEV void megakernel_body_bvh() {
   X(_tex_vn, kFeatTex | kFeatVtxNormals, 4, megakernel_body)                        \
   X(_bvh_tex_vn, kFeatBvh | kFeatTex | kFeatVtxNormals, 3, megakernel_body_bvh)     \
   X(_env_tex_vn, kFeatEnv | kFeatTex | kFeatVtxNormals, 4, megakernel_body)         \
-  X(_bvh_env_tex_vn, kFeatBvh | kFeatEnv | kFeatTex | kFeatVtxNormals, 3, megakernel_body_bvh)
+  X(_bvh_env_tex_vn, kFeatBvh | kFeatEnv | kFeatTex | kFeatVtxNormals, 3, megakernel_body_bvh) \
+  X(_tex_cut, kFeatTex | kFeatCutout, 3, megakernel_body)                           \
+  X(_bvh_tex_cut, kFeatBvh | kFeatTex | kFeatCutout, 2, megakernel_body_bvh)        \
+  X(_env_tex_cut, kFeatEnv | kFeatTex | kFeatCutout, 3, megakernel_body)            \
+  X(_bvh_env_tex_cut, kFeatBvh | kFeatEnv | kFeatTex | kFeatCutout, 2, megakernel_body_bvh)
 // the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
 // algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
 #define DMT_STATS_MEGAKERNELS(X)                                                    \
@@ -2409,6 +2429,12 @@ struct dmt_ctx {
   DevBuf<VtxNormalRec> d_vtxNormals;
   bool haveVtxNormals = false;
   uint64_t vtxSmoothCount = 0;
+  // alpha cutouts (dmt_upload_opacity; opacity.hpp): one record per triangle; dropped with the soup, the BSDFs or the textures
+  DevBuf<OpacityRec> d_opacity;
+  bool haveOpacity = false;
+  float opacityCutoff = 0.f;
+  uint64_t cutoutTris = 0;
+  uint32_t cutoutMats = 0;
   // wavefront form of the BVH path (wavefront.hpp)
   int bvhStrategy = 0;             // 0 = automatic (by launch size), 1 = megakernel, 2 = wavefront
   size_t wfTargetPaths = size_t(1) << 22;  // path slots per pass
@@ -2808,6 +2834,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (c->texFilter == DMT_TEXFILTER_REFERENCE && (F & (kFeatTex | kFeatBlend))) F |= kFeatTexFilter;
   if (c->ac.haveMotion) F |= kFeatMotion;
   if (c->haveVtxNormals) F |= kFeatVtxNormals;
+  if (c->haveOpacity) F |= kFeatCutout;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2822,6 +2849,11 @@ int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
 }
 // the combinations dmt_render refuses (mask | kFeatStats for dmt_render_stats / dmt_render_profile)
 int checkFeatures(dmt_ctx* ctx, uint32_t F) {
+  if (F & kFeatCutout) {  // alpha cutouts have the four texture megakernel rows; the rest is refused as for those rows
+    if (F & kFeatBlend) return fail(ctx, DMT_ERR_STATE, "dmt_render: opacity textures (dmt_upload_opacity) together with blend materials are not supported");
+    if (F & kFeatTexFilter) return fail(ctx, DMT_ERR_STATE, "dmt_render: opacity textures (dmt_upload_opacity) together with the first-hit texture filter are not supported");
+    if (F & kFeatVtxNormals) return fail(ctx, DMT_ERR_STATE, "dmt_render: opacity textures (dmt_upload_opacity) together with vertex normals are not supported");
+  }
   if (F & kFeatVtxNormals) {  // smooth shading has the plain, env-map and texture megakernel rows
     if (F & kFeatStats) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: vertex normals (dmt_upload_vertex_normals) have no counting kernels");
     if (F & kFeatMotion) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with motion blur are not supported");
@@ -2868,6 +2900,11 @@ void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const*
 
 namespace {
 
+void dropOpacity(dmt_ctx* ctx) {  // what the records were made from (soup, materials or textures) is going away
+  ctx->d_opacity.reset();
+  ctx->haveOpacity = false, ctx->opacityCutoff = 0.f, ctx->cutoutTris = 0, ctx->cutoutMats = 0;
+}
+
 void dropVertexNormals(dmt_ctx* ctx) {
   ctx->d_vtxNormals.reset();
   ctx->haveVtxNormals = false, ctx->vtxSmoothCount = 0;
@@ -2896,6 +2933,7 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.env = c->env;
   P.areaOf = c->d_areaOf.get(), P.areaTri = c->d_areaTri.get(), P.areaLe = c->d_areaLe.get(), P.areaCount = c->areaCount;
   if (c->haveVtxNormals) P.vtxNormals = c->d_vtxNormals.get();
+  if (c->haveOpacity) P.opacity = c->d_opacity.get(), P.opacityCutoff8 = c->opacityCutoff * 255.f;
   if (c->texCount > 0) {
     P.texRgba = c->d_texRgba.get(), P.texDesc = c->d_texDesc.get(), P.matTex = c->d_matTex.get(), P.triUv = c->d_triUv.get();
     P.texMip = c->d_texMip.get(), P.texMipDesc = c->d_texMipDesc.get();
@@ -3136,6 +3174,7 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->ac.tree.drop();         // it is of the soup just replaced
   dropMotion(ctx);             // key 1 was a motion from the soup just replaced
   dropVertexNormals(ctx);      // they were the normals of the soup just replaced
+  dropOpacity(ctx);            // one record per triangle of the soup just replaced
   ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
   ctx->h_areaTri.clear(), ctx->h_areaLe.clear();  // emissive triangles are indices into the soup just replaced
   if (int const rcA = rebuildAreaLights(ctx)) return rcA;
@@ -3162,6 +3201,8 @@ int dmt_upload_bsdfs(dmt_ctx* ctx, const void* bsdf32, uint32_t count) {
       blend = true;
     }
   }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (a launch in flight may read the cutout records dropped below)
+  dropOpacity(ctx);  // the records name the materials just replaced
   ctx->d_bsdfs = std::move(bsdfs);
   ctx->hasBlend = blend;
   ctx->bsdfCount = count;
@@ -3802,6 +3843,7 @@ int dmt_upload_textures(dmt_ctx* ctx, const uint8_t* rgba8, uint64_t texel_count
   ctx->d_texRgba.reset(), ctx->d_texDesc.reset(), ctx->d_matTex.reset(), ctx->d_triUv.reset();
   ctx->d_texMip.reset(), ctx->d_texMipDesc.reset();
   ctx->texCount = 0, ctx->matTexCount = 0, ctx->triUvCount = 0;
+  dropOpacity(ctx);  // the records point into the texel store just replaced
   if (texture_count == 0) return DMT_OK;  // cleared
   if (!rgba8 || !desc3 || !mat_tex4 || !tri_uv6 || texel_count == 0 || bsdf_count == 0 || triangle_count == 0)
     return fail(ctx, DMT_ERR_INVALID, "dmt_upload_textures: null array or zero count");
@@ -4066,6 +4108,96 @@ int dmt_vertex_normals_info(dmt_ctx* ctx, uint64_t* triangles, uint64_t* smooth_
 int dmt_smooth_normals(const float* xs, const float* ys, const float* zs, size_t count, float crease_degrees, float* n9_out) {
   if (!std::isfinite(crease_degrees) || (count && (!xs || !ys || !zs || !n9_out))) return DMT_ERR_INVALID;
   vnormals::smoothNormals(xs, ys, zs, count, crease_degrees, n9_out);
+  return DMT_OK;
+}
+
+// ---- alpha cutouts ------------------------------------------------------------------------
+int dmt_upload_opacity(dmt_ctx* ctx, const uint32_t* mat_opacity_tex, uint32_t bsdf_count, float cutoff) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveTris || !ctx->haveBsdfs || ctx->texCount == 0)
+    return fail(ctx, DMT_ERR_STATE, "dmt_upload_opacity: upload triangles, BSDFs and textures first");
+  if (ctx->triUvCount != ctx->triCount)
+    return fail(ctx, DMT_ERR_STATE, "dmt_upload_opacity: the uploaded textures carry no UV triple per uploaded triangle (upload textures last)");
+  if (!mat_opacity_tex || bsdf_count != ctx->bsdfCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: null array, or count differs from the uploaded BSDF count");
+  if (!std::isfinite(cutoff) || cutoff < 0.f || cutoff > 1.f) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: the cutoff must be finite and in [0, 1]");
+  for (uint32_t b = 0; b < bsdf_count; ++b)
+    if (mat_opacity_tex[b] != 0xFFFFFFFFu && mat_opacity_tex[b] >= ctx->texCount)
+      return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: a material refers to a texture that does not exist");
+  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: material index outside the BSDF array");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old records
+  std::vector<int32_t> desc(3 * size_t(ctx->texCount));
+  std::vector<float> uv(6 * size_t(ctx->triCount));
+  HIP_TRY(ctx, hipMemcpy(desc.data(), ctx->d_texDesc.get(), desc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (!uv.empty()) HIP_TRY(ctx, hipMemcpy(uv.data(), ctx->d_triUv.get(), uv.size() * sizeof(float), hipMemcpyDeviceToHost));
+  uint32_t mats = 0;
+  for (uint32_t b = 0; b < bsdf_count; ++b) {
+    uint32_t const t = mat_opacity_tex[b];
+    if (t == 0xFFFFFFFFu) continue;
+    ++mats;
+    if (desc[3 * size_t(t) + 1] > 65535 || desc[3 * size_t(t) + 2] > 65535)
+      return fail(ctx, DMT_ERR_INVALID, ("dmt_upload_opacity: opacity texture " + std::to_string(t) + " is wider or taller than 65535 texels").c_str());
+  }
+  std::vector<OpacityRec> recs(ctx->triCount);
+  uint64_t cut = 0;
+  for (size_t i = 0; i < ctx->triCount; ++i) {
+    OpacityRec& R = recs[i];
+    float const* const q = &uv[6 * i];
+    R = OpacityRec{q[0], q[1], q[2], q[3], q[4], q[5], 0u, 0u};
+    uint32_t const t = mat_opacity_tex[ctx->h_mat[i]];
+    if (t == 0xFFFFFFFFu) continue;
+    for (int j = 0; j < 6; ++j)
+      if (!std::isfinite(q[j]) || std::fabs(q[j]) > 1048576.f)
+        return fail(ctx, DMT_ERR_INVALID, ("dmt_upload_opacity: triangle " + std::to_string(i) + " of a cutout material has a UV that is not finite or beyond 2^20").c_str());
+    R.first = uint32_t(desc[3 * size_t(t)]), R.wh = uint32_t(desc[3 * size_t(t) + 1]) | (uint32_t(desc[3 * size_t(t) + 2]) << 16);
+    ++cut;
+  }
+  DevBuf<OpacityRec> d;
+  HIP_TRY(ctx, d.assign(recs.data(), recs.size()));
+  ctx->d_opacity = std::move(d);
+  ctx->haveOpacity = true, ctx->opacityCutoff = cutoff, ctx->cutoutTris = cut, ctx->cutoutMats = mats;
+  return DMT_OK;
+}
+
+int dmt_clear_opacity(dmt_ctx* ctx) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!ctx->haveOpacity) return DMT_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the records
+  dropOpacity(ctx);
+  return DMT_OK;
+}
+
+int dmt_opacity_info(dmt_ctx* ctx, uint64_t* cutout_triangles, uint32_t* cutout_materials, float* cutoff) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (cutout_triangles) *cutout_triangles = ctx->haveOpacity ? ctx->cutoutTris : 0u;
+  if (cutout_materials) *cutout_materials = ctx->haveOpacity ? ctx->cutoutMats : 0u;
+  if (cutoff) *cutoff = ctx->haveOpacity ? ctx->opacityCutoff : 0.f;
+  return DMT_OK;
+}
+
+int dmt_opacity_eval(const uint8_t* rgba8, uint64_t texel_count, const int32_t* desc3, uint32_t texture_count, int n, const int32_t* tex,
+                     const float* uv6, const float* bu, const float* bv, float cutoff, float* alpha8_out, uint8_t* pass_out) {
+  if (n < 0 || !rgba8 || !desc3 || texture_count == 0 || !std::isfinite(cutoff) || cutoff < 0.f || cutoff > 1.f) return DMT_ERR_INVALID;
+  if (n && (!tex || !uv6 || !bu || !bv || !alpha8_out || !pass_out)) return DMT_ERR_INVALID;
+  for (uint32_t k = 0; k < texture_count; ++k) {
+    int64_t const first = desc3[3 * k], w = desc3[3 * k + 1], h = desc3[3 * k + 2];
+    if (first < 0 || w <= 0 || h <= 0 || w > 65535 || h > 65535 || uint64_t(first) + uint64_t(w) * uint64_t(h) > texel_count) return DMT_ERR_INVALID;
+  }
+  for (int i = 0; i < n; ++i)
+    if (tex[i] < 0 || uint32_t(tex[i]) >= texture_count) return DMT_ERR_INVALID;
+  float const cutoff8 = cutoff * 255.f;
+  struct Texels {  // the RGBA8 store as the device's little-endian words
+    uint8_t const* p;
+    uint32_t operator[](size_t i) const { return uint32_t(p[4 * i]) | uint32_t(p[4 * i + 1]) << 8 | uint32_t(p[4 * i + 2]) << 16 | uint32_t(p[4 * i + 3]) << 24; }
+  };
+  for (int i = 0; i < n; ++i) {
+    int32_t const* const d = desc3 + 3 * size_t(tex[i]);
+    float const* const q = uv6 + 6 * size_t(i);
+    OpacityRec const R{q[0], q[1], q[2], q[3], q[4], q[5], uint32_t(d[0]), uint32_t(d[1]) | (uint32_t(d[2]) << 16)};
+    alpha8_out[i] = opacity_alpha8_at(Texels{rgba8}, R, bu[i], bv[i]);
+    pass_out[i] = alpha8_out[i] >= cutoff8 ? 1 : 0;
+  }
   return DMT_OK;
 }
 

@@ -18,7 +18,7 @@ namespace {
 template <uint32_t F>
 __global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t const* pys, int32_t const* ss, float* L3) {
   KArgs const k = kargs_base();
-  if constexpr (!(F & (kFeatBvh | kFeatMotion))) cull_stage(k);
+  if constexpr (!(F & (kFeatBvh | kFeatMotion | kFeatCutout))) cull_stage(k);
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
   PathState st{};
   if (i < n) {
@@ -71,7 +71,7 @@ __global__ void k_test_envmap(EnvView env, int n, float const* u2, float const* 
 
 // single path with a per-bounce log, one record per closest-hit ray (at most cap, *nOut written):
 //   rec12 = {tri (-1: miss), pos3, beta3, L3 before the bounce is shaded, depth, sampler dimension}
-template <bool MOTION, bool VN = false>
+template <bool MOTION, bool VN = false, bool CUT = false>
 DMT_DEV void test_trace_log_body(int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   KArgs const k = kargs_base();
@@ -90,6 +90,8 @@ DMT_DEV void test_trace_log_body(int px, int py, int smp, float* rec12, int cap,
     bool occluded;
     if constexpr (MOTION)  // one sample: its shadow rays share its time
       trace_pair_brute_motion(k, st, doC, doS, v2f{motion_time(), motion_time()}, bestTri, bu, bv, occluded);
+    else if constexpr (CUT)  // every ray of the path sees the cutouts
+      trace_pair_brute_cut(k, st, doC, doS, bestTri, bu, bv, occluded);
     else
       trace_pair_brute<false>(k, st, doC, doS, bestTri, bu, bv, occluded);  // one thread: the plain loop
     if (doS) {
@@ -124,6 +126,10 @@ __global__ void k_test_trace_log_motion(RenderParams P, int px, int py, int smp,
 
 __global__ void k_test_trace_log_vn(RenderParams P, int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
   test_trace_log_body<false, true>(px, py, smp, rec12, cap, nOut, L3);
+}
+
+__global__ void k_test_trace_log_cut(RenderParams P, int px, int py, int smp, float* rec12, int cap, int* nOut, float* L3) {
+  test_trace_log_body<false, false, true>(px, py, smp, rec12, cap, nOut, L3);
 }
 
 // dmt_test_shading_normal: shading_normal_at of triangle tri[i] at (bu, bv) for a ray of direction rd3[i]; ngFacing is
@@ -349,6 +355,47 @@ __global__ void k_test_closest_at(RenderParams P, bool useBvh, int n, float cons
   if (alive) {
     tri[i] = best, tOut[i] = best >= 0 ? bt : kInf;
     if (uv2) uv2[2 * i] = best >= 0 ? bu : 0.f, uv2[2 * i + 1] = best >= 0 ? bv : 0.f;
+  }
+}
+
+// dmt_test_opacity: alpha8 and the pass decision of triangle tri[i] at (bu, bv), by the record and the lookup the cutout rows
+// use (an opaque triangle: 255, passes)
+__global__ void k_test_opacity(RenderParams P, int n, int32_t const* tri, float const* bu, float const* bv, float* alpha8, uint8_t* pass) {
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  CutoutView const cv = load_cutout(k);
+  OpacityRec const R = cv.recs[tri[i]];
+  float const a = R.wh == 0u ? 255.f : opacity_alpha8_at(cv.rgba, R, bu[i], bv[i]);
+  alpha8[i] = a;
+  pass[i] = (R.wh == 0u || a >= cv.cutoff8) ? 1 : 0;
+}
+
+// dmt_test_closest_hit_opacity: ray i as a closest-hit ray and as a shadow ray of length tmax[i] at once, by the cutout rows'
+// trace of the accel mode
+__global__ void k_test_closest_cut(RenderParams P, bool useBvh, int n, float const* o3, float const* d3, float const* tmax, int32_t* tri,
+                                   float* tOut, float* uv2, uint8_t* occ) {
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  bool const alive = i < n;
+  PathState st{};
+  if (alive) {
+    f3 const o = mk3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), d = mk3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+    set_ray(st, o, d), set_shadow_ray(st, o, d);
+    st.smax = tmax[i];
+  }
+  st.active = alive, st.hasShadow = alive;
+  int best;
+  float bu, bv, bt = kInf;
+  bool occluded;
+  if (useBvh)
+    trace_pair_bvh_cut(k, st, alive, alive, blockIdx.x * blockDim.x + threadIdx.x, best, bu, bv, occluded, &bt);
+  else
+    trace_pair_brute_cut(k, st, alive, alive, best, bu, bv, occluded, &bt);
+  if (alive) {
+    tri[i] = best, tOut[i] = best >= 0 ? bt : kInf;
+    if (uv2) uv2[2 * i] = best >= 0 ? bu : 0.f, uv2[2 * i + 1] = best >= 0 ? bv : 0.f;
+    if (occ) occ[i] = occluded ? 1 : 0;
   }
 }
 
@@ -638,7 +685,9 @@ int dmt_test_trace_log(dmt_ctx* ctx, int px, int py, int s, float* rec12, int ca
   if (p.err != hipSuccess) return probeError(ctx, p);
   RenderParams P = baseParams(ctx, p.threads(64));
   if (int const rc = motionParams(ctx, ctx->ac.haveMotion ? kFeatMotion : 0u, P)) return rc;  // (brute force: no tree)
-  hipLaunchKernelGGL(ctx->ac.haveMotion ? k_test_trace_log_motion : ctx->haveVtxNormals ? k_test_trace_log_vn : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
+  if (ctx->haveOpacity && (ctx->ac.haveMotion || ctx->haveVtxNormals))
+    return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_log: opacity textures (dmt_upload_opacity) together with motion blur or vertex normals are not supported");
+  hipLaunchKernelGGL(ctx->haveOpacity ? k_test_trace_log_cut : ctx->ac.haveMotion ? k_test_trace_log_motion : ctx->haveVtxNormals ? k_test_trace_log_vn : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
                      dr.get(), cap, dn.get(), dL.get());
   return finishProbe(ctx, p);
 }
@@ -710,6 +759,45 @@ int dmt_test_shading_normal(dmt_ctx* ctx, int n, const int32_t* tri, const float
 }
 int dmt_test_shading_normal_mapped(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3, float* ns3) {
   return probeShadingNormal(ctx, true, n, tri, bu, bv, rd3, ns3);
+}
+
+int dmt_test_opacity(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, float* alpha8, uint8_t* pass) {
+  if (!ctx || n < 0 || !tri || !bu || !bv || !alpha8 || !pass) return DMT_ERR_INVALID;
+  if (!ctx->haveOpacity) return fail(ctx, DMT_ERR_STATE, "dmt_test_opacity: no opacity (dmt_upload_opacity first)");
+  for (int i = 0; i < n; ++i)
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_opacity: triangle index out of range");
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<int32_t> dTri(p, tri, 1);
+  ProbeIn<float> dBu(p, bu, 1), dBv(p, bv, 1);
+  ProbeOut<float> dA(p, alpha8, 1);
+  ProbeOut<uint8_t> dP(p, pass, 1);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  hipLaunchKernelGGL(k_test_opacity, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), n, dTri.get(), dBu.get(),
+                     dBv.get(), dA.get(), dP.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_closest_hit_opacity(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* tmax, int32_t* tri_index, float* t,
+                                 float* uv2, uint8_t* occluded) {
+  if (!ctx || nrays < 0 || !o3 || !d3 || !tmax || !tri_index || !t) return DMT_ERR_INVALID;
+  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: upload triangles first");
+  if (!ctx->haveOpacity) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: no opacity (dmt_upload_opacity first)");
+  if (nrays == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(nrays));
+  ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3), dM(p, tmax, 1);
+  ProbeOut<int32_t> di(p, tri_index, 1);
+  ProbeOut<float> dt(p, t, 1), duv(p, uv2, 2);  // uv2, occluded optional: null is not copied back
+  ProbeOut<uint8_t> docc(p, occluded, 1);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
+  if (useBvh) {
+    if (int const rcT = requireTree(ctx, "dmt_test_closest_hit_opacity")) return rcT;
+    HIP_TRY(ctx, reserveOverflow(ctx, p.threads(64)));
+  }
+  hipLaunchKernelGGL(k_test_closest_cut, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), useBvh, nrays, dO.get(),
+                     dD.get(), dM.get(), di.get(), dt.get(), duv.get(), docc.get());
+  return finishProbe(ctx, p);
 }
 
 int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t) {

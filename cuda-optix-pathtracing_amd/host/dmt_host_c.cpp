@@ -123,6 +123,9 @@ const uint32_t* dmt_host_scene_mat_tex(const dmt_host_scene* h) { return h->s.ma
 const float* dmt_host_scene_tri_uv(const dmt_host_scene* h) { return h->s.triUv.data(); }
 // vertex normals (smooth shading): 9 floats per triangle, or null when no mesh of the scene carries any
 const float* dmt_host_scene_tri_normals(const dmt_host_scene* h) { return h->s.triNormals.empty() ? nullptr : h->s.triNormals.data(); }
+// alpha cutouts: per BSDF the opacity texture (0xFFFFFFFF = opaque), or null when no material of the scene names one; the cutoff
+const uint32_t* dmt_host_scene_mat_opacity(const dmt_host_scene* h) { return h->s.matOpacity.empty() ? nullptr : h->s.matOpacity.data(); }
+float dmt_host_scene_opacity_cutoff(const dmt_host_scene* h) { return h->s.opacityCutoff; }
 void dmt_host_scene_destroy(dmt_host_scene* h) { delete h; }
 
 uint64_t dmt_host_scene_triangle_count(const dmt_host_scene* h) { return h->s.triangleCount(); }

@@ -126,6 +126,8 @@ struct Material {
   Vec3 reflectanceTint{1, 1, 1}, transmittanceTint{1, 1, 1};
   bool orenNayar = false;
   int32_t diffuseTex = -1, roughnessTex = -1, normalTex = -1, metallicTex = -1;  // indices into State::textureList
+  int32_t opacityTex = -1;     // alpha cutouts (dmt_upload_opacity): the 'opacity' texture, -1 = opaque
+  float opacityCutoff = 0.5f;  // 'opacity-cutoff'
   // 0 < metallic < 1, or a metallic map: the material becomes TWO records (dielectric tagged BS_GGX_BLEND, then conductor)
   bool blend() const { return !orenNayar && (metallicTex >= 0 || (metallic > 0.f && metallic < 1.f)); }
   int records() const { return blend() ? 2 : 1; }
@@ -255,7 +257,7 @@ void parseTexture(Value const& t, State& st, std::string const& baseDir) {
   if (!t.contains("path") || !t.at("path").isString()) fail("Texture object should contain attribute 'path' and it should be a string");
   std::string const name = t.at("name").string, type = t.at("type").string;
   if (st.textures.count(name)) fail("texture " + name + " already exists");
-  if (type != "diffuse" && type != "normal" && type != "metallic" && type != "roughness") fail("texture: unrecognized type '" + type + "'");
+  if (type != "diffuse" && type != "normal" && type != "metallic" && type != "roughness" && type != "opacity") fail("texture: unrecognized type '" + type + "'");
   // 8-bit PNGs (what the reference's scenes ship); channel rule of core-parser.cpp:373-386: diffuse / normal are
   // 3-channel images, metallic / roughness 1-channel ones
   std::vector<uint8_t> img;
@@ -263,12 +265,21 @@ void parseTexture(Value const& t, State& st, std::string const& baseDir) {
   std::string perr;
   if (!readPng8(baseDir + "/" + t.at("path").string, img, w, h, ch, &perr)) fail("Error loading texture '" + name + "': " + perr);
   bool const rgb = type == "diffuse" || type == "normal";
-  if (rgb ? ch < 3 : (ch != 1 && ch != 2)) fail("Error loading texture '" + name + "': metallic, roughness expect 1 channel; diffuse, normal expect 3 channels");
+  // 'opacity' (alpha cutouts, beyond the reference): 1, 2 or 4 channels; A = the grey byte of a 1-channel image, the file's
+  // alpha byte otherwise, and RGB = that same byte
+  bool const opacity = type == "opacity";
+  if (opacity && ch != 1 && ch != 2 && ch != 4) fail("Error loading texture '" + name + "': opacity expects 1, 2 or 4 channels");
+  if (opacity ? false : rgb ? ch < 3 : (ch != 1 && ch != 2)) fail("Error loading texture '" + name + "': metallic, roughness expect 1 channel; diffuse, normal expect 3 channels");
   Texture tex;
   tex.type = type, tex.first = int32_t(st.texels.size() / 4), tex.width = w, tex.height = h;
   st.texels.reserve(st.texels.size() + size_t(w) * size_t(h) * 4);
   for (size_t i = 0; i < size_t(w) * size_t(h); ++i) {
     uint8_t const* p = &img[i * size_t(ch)];
+    if (opacity) {
+      uint8_t const a = p[ch - 1];
+      st.texels.insert(st.texels.end(), {a, a, a, a});
+      continue;
+    }
     uint8_t const r = p[0], g = rgb ? p[1] : p[0], b = rgb ? p[2] : p[0];
     st.texels.insert(st.texels.end(), {r, g, b, uint8_t(255)});
   }
@@ -295,7 +306,7 @@ void parseMaterial(Value const& m, State& st) {
   std::string const name = m.at("name").string;
   if (st.materials.count(name)) fail("Duplicate material name '" + name + "'");
   onlyKeys(m, {"name", "diffuse", "metallic", "normal", "roughness", "ior", "eta", "etak", "ggx-anisotropy", "ggx-dielectric",
-               "oren-nayar-dielectric"}, "material '" + name + "'");
+               "oren-nayar-dielectric", "opacity", "opacity-cutoff"}, "material '" + name + "'");
   if (!m.contains("diffuse")) fail("material should specify a 'diffuse' either as RGB or texture name");
   if (!m.contains("metallic")) fail("material should specify a 'metallic' either as float or texture name");
   if (!m.contains("roughness")) fail("material should specify a 'roughness' either as float or texture name");
@@ -318,6 +329,18 @@ void parseMaterial(Value const& m, State& st) {
     if (!st.textures.count(m.at("normal").string)) fail("'normal' texture name should be an existing named texture");
     if (st.textureList[st.textures.at(m.at("normal").string)].type != "normal") fail("'normal' material texture should point to a 'normal' texture");
     mat.normalTex = int32_t(st.textures.at(m.at("normal").string));
+  }
+  if (m.contains("opacity")) {  // alpha cutouts: the texture whose A channel decides whether a hit counts
+    if (!m.at("opacity").isString()) fail("material 'opacity' should be an opacity texture name");
+    if (!st.textures.count(m.at("opacity").string)) fail("'opacity' texture name should be an existing named texture");
+    if (st.textureList[st.textures.at(m.at("opacity").string)].type != "opacity") fail("'opacity' material texture should point to a 'opacity' texture");
+    mat.opacityTex = int32_t(st.textures.at(m.at("opacity").string));
+  }
+  if (m.contains("opacity-cutoff")) {
+    Value const& c = m.at("opacity-cutoff");
+    if (!c.isNumber() || !(c.number >= 0.0 && c.number <= 1.0)) fail("'opacity-cutoff' should be a number in [0, 1]");
+    if (mat.opacityTex < 0) fail("'opacity-cutoff' needs an 'opacity' texture");
+    mat.opacityCutoff = float(c.number);
   }
   mat.roughness = scalarOrTexture(m.at("roughness"), "roughness", st, &mat.roughnessTex);
   mat.metallic = scalarOrTexture(m.at("metallic"), "metallic", st, &mat.metallicTex);
@@ -662,7 +685,7 @@ bool loadJsonScene(std::string const& path, JsonScene& out, std::string* error) 
     // image textures: only when some material uses one (otherwise the plain kernels run and nothing is uploaded)
     bool textured = false;
     for (Material const& m : st.materialList)
-      textured = textured || m.diffuseTex >= 0 || m.roughnessTex >= 0 || m.normalTex >= 0 || m.metallicTex >= 0;
+      textured = textured || m.diffuseTex >= 0 || m.roughnessTex >= 0 || m.normalTex >= 0 || m.metallicTex >= 0 || m.opacityTex >= 0;
     if (textured) {
       out.scene.texRgba = std::move(st.texels);
       for (Texture const& t : st.textureList) out.scene.texDesc.insert(out.scene.texDesc.end(), {t.first, t.width, t.height});
@@ -676,6 +699,16 @@ bool loadJsonScene(std::string const& path, JsonScene& out, std::string* error) 
     } else {
       out.scene.triUv.clear();
     }
+    // alpha cutouts: one row per packed record, only when some material names an opacity texture; the context takes ONE cutoff
+    bool cut = false;
+    for (Material const& m : st.materialList) {
+      if (m.opacityTex < 0) continue;
+      if (cut && m.opacityCutoff != out.scene.opacityCutoff) fail("materials with an 'opacity' texture should share one 'opacity-cutoff'");
+      cut = true, out.scene.opacityCutoff = m.opacityCutoff;
+    }
+    if (cut)
+      for (Material const& m : st.materialList)
+        for (int r = 0; r < m.records(); ++r) out.scene.matOpacity.push_back(uint32_t(m.opacityTex));
     if (std::all_of(out.scene.triNormals.begin(), out.scene.triNormals.end(), [](float v) { return v == 0.f; })) out.scene.triNormals.clear();
     return true;
   } catch (Fail const& e) {

@@ -417,8 +417,10 @@ int uploadScene(dmt_ctx* ctx, Scene const& s) {
   if (rc) return rc;
   if (s.texDesc.empty())
     return dmt_upload_textures(ctx, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0);
-  return dmt_upload_textures(ctx, s.texRgba.data(), s.texRgba.size() / 4, s.texDesc.data(), uint32_t(s.texDesc.size() / 3), s.matTex.data(),
-                             uint32_t(s.matTex.size() / 4), s.triUv.data(), s.triUv.size() / 6);
+  rc = dmt_upload_textures(ctx, s.texRgba.data(), s.texRgba.size() / 4, s.texDesc.data(), uint32_t(s.texDesc.size() / 3), s.matTex.data(),
+                           uint32_t(s.matTex.size() / 4), s.triUv.data(), s.triUv.size() / 6);
+  if (rc || s.matOpacity.empty()) return rc;
+  return dmt_upload_opacity(ctx, s.matOpacity.data(), uint32_t(s.matOpacity.size()), s.opacityCutoff);  // alpha cutouts: after the textures
 }
 
 }  // namespace dmt_host

@@ -84,6 +84,11 @@ struct Scene {
   // vertices 0, 1, 2; triangles of meshes without normals are nine zeros (= flat).  uploadScene does NOT upload them
   // (the files' normals are used only where the caller asks: main.cpp --shading-normals).
   std::vector<float> triNormals;
+  // optional alpha cutouts (dmt_upload_opacity; the JSON front-end's material keys "opacity" / "opacity-cutoff"): empty, or
+  // per BSDF the texture whose A channel is its opacity (0xFFFFFFFF = opaque), and the scene's cutoff.  uploadScene
+  // uploads them after the textures.
+  std::vector<uint32_t> matOpacity;
+  float opacityCutoff = 0.5f;
 
   size_t triangleCount() const { return matId.size(); }
   // addModel + the material walk of triSoupFromTriangles: the FIRST mesh always gets material 0

@@ -56,6 +56,7 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   std::string motionScenePath;  // --motion-scene <file>: the same scene at the end of the frame; its triangle positions become key 1
   std::string shadingNormals = "off";  // --shading-normals off|file|smooth[:DEG] (dmt_upload_vertex_normals)
   float creaseDegrees = 180.f;         // parsed from shadingNormals by validate()
+  std::string cutouts = "on";  // --cutouts on|off: upload the scene's opacity textures (dmt_upload_opacity), or ignore them
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
 
@@ -111,6 +112,7 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (float c = 180.f; !parseShadingNormals(shadingNormals, c))
       return "invalid --shading-normals: expected off, file, smooth or smooth:DEG (0 <= DEG <= 180), got '" + shadingNormals + "'";
     if (shadingNormals != "off" && !motionScenePath.empty()) return "--shading-normals and --motion-scene exclude each other";
+    if (cutouts != "on" && cutouts != "off") return "invalid --cutouts: expected on or off, got '" + cutouts + "'";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
   }
@@ -161,7 +163,11 @@ void printHelp() {
       "                       default): faceted, as the reference renders.  file: the normals of the scene's meshes (FBX normal\n"
       "                       layers, PBRT \"normal N\"); meshes without any stay faceted.  smooth: normals computed from the\n"
       "                       geometry, angle-weighted over the faces that meet at a vertex within DEG degrees of each\n"
-      "                       other (default 180: no crease)");
+      "                       other (default 180: no crease)\n"
+      "  --cutouts <on|off> -- Alpha cutouts: a material's \"opacity\" texture decides at every hit whether the hit counts (A\n"
+      "                       channel >= the material's \"opacity-cutoff\", default 0.5), for camera, bounce and shadow rays.\n"
+      "                       on (the default): as the scene says; scenes without opacity textures are unaffected.  off:\n"
+      "                       ignore them, every triangle is solid");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -189,6 +195,7 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--shutter" && i + 2 < argc) c.shutterOpen = std::strtof(argv[++i], nullptr), c.shutterClose = std::strtof(argv[++i], nullptr), c.shutterSet = true;
     else if (a == "--motion-scene" && more) c.motionScenePath = argv[++i];
     else if (a == "--shading-normals" && more) c.shadingNormals = argv[++i];
+    else if (a == "--cutouts" && more) c.cutouts = argv[++i];
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -302,6 +309,7 @@ int main(int argc, char** argv) {
   if (cfg.textureFilter) scene.camera.spp = cfg.spp;  // the filter's footprint scale follows the frame's samples per pixel
   if (cfg.lensRadiusSet) scene.lensRadius = cfg.lensRadius;
   if (cfg.focusDistanceSet) scene.focusDistance = cfg.focusDistance;
+  if (cfg.cutouts == "off") scene.matOpacity.clear();  // --cutouts off: uploadScene then uploads no opacity
   std::vector<float> vertexNormals;  // --shading-normals: 9 floats per triangle for dmt_upload_vertex_normals
   if (cfg.shadingNormals == "file") {
     if (scene.triNormals.size() != 9 * scene.triangleCount()) {

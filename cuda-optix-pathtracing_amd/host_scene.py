@@ -20,13 +20,15 @@ def load_host_library():
                      "dmt_host_scene_ys", "dmt_host_scene_zs", "dmt_host_scene_mat_ids", "dmt_host_scene_bsdfs",
                      "dmt_host_scene_lights", "dmt_host_scene_infinite_lights", "dmt_host_scene_camera",
                      "dmt_host_scene_load_json", "dmt_host_scene_env_rgb", "dmt_host_scene_load_pbrt",
-                     "dmt_host_scene_area_tri", "dmt_host_scene_area_le", "dmt_host_scene_tri_normals"):
+                     "dmt_host_scene_area_tri", "dmt_host_scene_area_le", "dmt_host_scene_tri_normals", "dmt_host_scene_mat_opacity"):
             getattr(lib, name).restype = C.c_void_p
         lib.dmt_host_scene_random_triangles.argtypes = [C.c_uint64, C.c_uint64]
         lib.dmt_host_scene_random_triangles_ex.argtypes = [C.c_uint64, C.c_uint64, C.c_float]
         lib.dmt_host_scene_triangle_count.restype = C.c_uint64
         for name in ("dmt_host_scene_bsdf_count", "dmt_host_scene_light_count", "dmt_host_scene_infinite_light_count"):
             getattr(lib, name).restype = C.c_uint32
+        lib.dmt_host_scene_opacity_cutoff.restype = C.c_float
+        lib.dmt_host_scene_opacity_cutoff.argtypes = [C.c_void_p]
         lib.dmt_host_half_bits_to_float.restype = C.c_float
         lib.dmt_host_half_bits_to_float.argtypes = [C.c_uint16]
         lib.dmt_host_float_to_half_bits.restype = C.c_uint16
@@ -86,6 +88,10 @@ class HostScene:
         # carries any.  upload_scene uploads them only when asked (vertex_normals=True).
         tn = L.dmt_host_scene_tri_normals(h)
         self.tri_normals = _copy(tn, np.float32, 9 * n).reshape(-1, 9) if tn else None
+        # alpha cutouts: per BSDF the opacity texture (0xFFFFFFFF = opaque) and the cutoff; None when no material names one
+        mo = L.dmt_host_scene_mat_opacity(h)
+        self.mat_opacity = _copy(mo, np.uint32, self.bsdfs.shape[0]) if mo else None
+        self.opacity_cutoff = float(L.dmt_host_scene_opacity_cutoff(h)) if mo else None
         L.dmt_host_scene_destroy(h)
 
     @property

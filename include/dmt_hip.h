@@ -217,6 +217,54 @@ int dmt_vertex_normals_info(dmt_ctx* ctx, uint64_t* triangles, uint64_t* smooth_
  * interior angle at that corner; only faces whose normal lies within crease_degrees (finite; clamped to [0, 180]) of the
  * corner's own face contribute.  Zero-area triangles contribute nothing and come out flat (nine zeros). */
 int dmt_smooth_normals(const float* xs, const float* ys, const float* zs, size_t count, float crease_degrees, float* n9_out);
+
+/* ---- alpha cutouts: opacity textures tested at every ray-triangle hit (opt-in, beyond the reference) ---- */
+/* Binary cutout.  A material may name one of the uploaded textures as its opacity texture.  A hit on a triangle of such a
+ * material counts only if the texture's A channel at the hit passes a cutoff; otherwise the ray goes on as if the triangle
+ * were not there.  Fractional or stochastic transparency and coloured transmission are out of scope.  Without the upload
+ * every film, tree and probe result is byte for byte what it was before these calls existed.
+ *
+ * The lookup.  With (bu, bv) the hit's barycentrics and (u_i, v_i) the triangle's UVs of dmt_upload_textures, in fp32 with
+ * every operation rounded (nothing contracted):
+ *   w0 = (1 - bu) - bv;   s = (w0*u0 + bu*u1) + bv*u2;   t = (w0*v0 + bu*v1) + bv*v2
+ *   x = s*w - 0.5, y = t*h - 0.5 (each clamped to +-2^30), x0 = floorf(x), tx = x - x0 (y alike), texels mirror-wrapped
+ *   ax0 = a00*(1 - tx) + a10*tx;  ax1 = a01*(1 - tx) + a11*tx;  alpha8 = ax0*(1 - ty) + ax1*ty
+ * -- the arithmetic of the level-0 bilinear colour lookup, on the raw A bytes a_xy as floats in [0, 255], with no division.
+ * The test: the hit passes iff alpha8 >= cutoff8, cutoff8 = cutoff * 255.f computed once on the host.  No reciprocal and no
+ * contraction: dmt_opacity_eval (host) and a plain float32 restatement equal the device bit for bit.
+ *
+ * Rays.  Closest hit = the minimum t over valid AND passing hits, the lowest original index on equal t, as for solid
+ * triangles.  A shadow ray is occluded iff some valid and passing hit has t < its length.  Every ray of a path sees
+ * cutouts: camera, bounce and shadow rays.  The pass decision is a function of (triangle, bu, bv) alone, which brute force
+ * and the BVH produce bit for bit, so their hits and films stay bit-identical.  The trees do not change (boxes only
+ * cull): dmt_accel_download, the refit and the device builder are byte-identical with and without opacity.
+ *
+ * Scope.  Cutouts run on the four texture megakernel rows (plain / env map, brute force / BVH): dmt_render (partitions,
+ * chunks), dmt_render_adaptive, dmt_test_trace_samples / dmt_test_trace_log and dmt_render_aovs, whose planes see through
+ * holes.  The brute-force pass of a cutout launch is the plain loop over every triangle.  Refused with DMT_ERR_STATE and a
+ * message that names opacity and the other side: blend materials, the first-hit texture filter, vertex normals.  Refused as
+ * for any textured scene, with those messages: emissive triangles, motion blur, dmt_render_stats / dmt_render_profile.  The
+ * wavefront strategy and the light trees behave as for a textured scene (the megakernel runs; the uniform light pick).
+ * Left on solid geometry: dmt_focus_distance_at, dmt_test_closest_hit, and the temporal denoiser's motion vectors. */
+/* Per BSDF the index of an uploaded texture whose A channel is the material's opacity, 0xFFFFFFFF = opaque.
+ * DMT_ERR_STATE before triangles, BSDFs and textures (with one UV triple per triangle) are uploaded.  DMT_ERR_INVALID for a
+ * count that differs from the uploaded BSDF count, a texture index out of range, an opacity texture wider or taller than
+ * 65535 texels, a cutoff that is not finite or outside [0, 1], or a triangle of a cutout material with a UV that is not
+ * finite or has |uv| > 2^20 (texel coordinates then stay inside int on host and device alike; the message names the
+ * triangle).  A refused upload leaves the context as it was.  Synchronises the stream first.  Dropped by
+ * dmt_upload_triangles, dmt_upload_bsdfs and dmt_upload_textures; kept by dmt_update_vertices[_device], like the UVs. */
+int dmt_upload_opacity(dmt_ctx* ctx, const uint32_t* mat_opacity_tex, uint32_t bsdf_count, float cutoff);
+/* drops the opacity; every film is then byte for byte what it was before dmt_upload_opacity */
+int dmt_clear_opacity(dmt_ctx* ctx);
+/* triangles and materials that carry an opacity texture, and the cutoff; all zero without opacity.  Any pointer may be null. */
+int dmt_opacity_info(dmt_ctx* ctx, uint64_t* cutout_triangles, uint32_t* cutout_materials, float* cutoff);
+/* host only (no GPU): the serial twin of the device lookup, bit for bit.  Textures as dmt_upload_textures takes them (rgba8,
+ * desc3 = {first texel, width, height} per texture); case i looks texture tex[i] up for a triangle with UVs uv6[6i..] at
+ * barycentrics (bu[i], bv[i]): alpha8_out[i], and pass_out[i] = alpha8 >= cutoff * 255.f ? 1 : 0.  DMT_ERR_INVALID for a
+ * descriptor outside the texel array or beyond 65535 texels a side, a texture index out of range, or a cutoff
+ * dmt_upload_opacity would refuse. */
+int dmt_opacity_eval(const uint8_t* rgba8, uint64_t texel_count, const int32_t* desc3, uint32_t texture_count, int n, const int32_t* tex,
+                     const float* uv6, const float* bu, const float* bv, float cutoff, float* alpha8_out, uint8_t* pass_out);
 /* depth cap of the bounce loop; the reference hard-codes 32 (megakernel.cu:154) */
 int dmt_set_limits(dmt_ctx* ctx, int max_depth);
 int dmt_set_accel(dmt_ctx* ctx, int mode);
@@ -643,6 +691,14 @@ int dmt_test_shading_normal(dmt_ctx* ctx, int n, const int32_t* tri, const float
  * textures uploaded */
 int dmt_test_shading_normal_mapped(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3,
                                    float* ns3);
+/* the cutout lookup on the uploaded scene, by the device function the cutout rows run: alpha8[i] and pass[i] of triangle tri[i]
+ * at barycentrics (bu, bv); a triangle of an opaque material answers 255 and passes.  DMT_ERR_STATE without opacity. */
+int dmt_test_opacity(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, float* alpha8, uint8_t* pass);
+/* ray i under the cutout rule and the current accel mode, through the trace the cutout rows run: the closest PASSING hit --
+ * tri_index (-1: none), t (+inf: none), uv2 (n x 2, may be null) -- and occluded[i] (may be null) = some valid and passing
+ * hit has t < tmax[i].  DMT_ERR_STATE without opacity.  dmt_test_closest_hit keeps answering for solid geometry. */
+int dmt_test_closest_hit_opacity(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* tmax, int32_t* tri_index, float* t,
+                                 float* uv2, uint8_t* occluded);
 /* dmt_camera_project on the device, under the camera of dmt_set_camera */
 int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, float* depth);
 int dmt_test_bsdf(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, const float* wo3,
