@@ -83,6 +83,7 @@ EXPORTED_SYMBOLS = [
     "dmt_motion_bvh_validate", "dmt_test_shutter_times", "dmt_test_closest_hit_at",
     "dmt_upload_vertex_normals", "dmt_clear_vertex_normals", "dmt_vertex_normals_info", "dmt_smooth_normals",
     "dmt_test_shading_normal", "dmt_test_shading_normal_mapped",
+    "dmt_set_ggx_batch", "dmt_ggx_batch_diag",
     "dmt_upload_opacity", "dmt_clear_opacity", "dmt_opacity_info", "dmt_opacity_eval", "dmt_test_opacity", "dmt_test_closest_hit_opacity",
 ]
 
@@ -804,6 +805,17 @@ class Renderer:
         Films are bit-identical in every mode."""
         self._check(self._lib.dmt_set_sampler_table(self._ctx, int(mode), C.c_uint64(int(budget_bytes))), "dmt_set_sampler_table")
 
+    def set_ggx_batch(self, batch):
+        """GGX hits of the plain brute-force launches (k_megakernel) are shaded `batch` at a time (0: in the pass that
+        finds them).  Films are bit-identical for every value."""
+        self._check(self._lib.dmt_set_ggx_batch(self._ctx, C.c_uint32(int(batch))), "dmt_set_ggx_batch")
+
+    def ggx_batch(self):
+        """The context's batch size (dmt_ggx_batch_diag; synchronises)."""
+        out = (C.c_uint64 * 5)()
+        self._check(self._lib.dmt_ggx_batch_diag(self._ctx, out), "dmt_ggx_batch_diag")
+        return int(out[4])
+
     def set_stream(self, stream_ptr):
         self._check(self._lib.dmt_set_stream(self._ctx, C.c_void_p(stream_ptr)), "dmt_set_stream")
 
@@ -969,14 +981,20 @@ class Renderer:
         self._check(self._lib.dmt_sync(self._ctx), "dmt_sync")
 
     def sched_diag(self, reset=False):
-        """Counters of the in-launch fold hand-over (dmt_sched_diag); synchronises the stream."""
+        """Counters of the in-launch fold hand-over (dmt_sched_diag) and, under ggx_*, of the GGX batching
+        (dmt_ggx_batch_diag, read first: the reset clears both); synchronises the stream."""
         out = (C.c_uint64 * 8)()
         if not hasattr(self._lib, "dmt_sched_diag"):   # an older build loaded through DMT_HIP_LIB for an A/B run
             return dict.fromkeys(["folds", "handed_over", "folded_for_others", "slab_stalls", "early_exits",
                                   "max_stall_ticks_10ns", "launched", "slabs_per_wave"], 0)
+        ggx = (C.c_uint64 * 5)()
+        if hasattr(self._lib, "dmt_ggx_batch_diag"):   # (read before dmt_sched_diag resets the counters)
+            self._check(self._lib.dmt_ggx_batch_diag(self._ctx, ggx), "dmt_ggx_batch_diag")
         self._check(self._lib.dmt_sched_diag(self._ctx, out, int(bool(reset))), "dmt_sched_diag")
         keys = ["folds", "handed_over", "folded_for_others", "slab_stalls", "early_exits", "max_stall_ticks_10ns", "launched", "slabs_per_wave"]
-        return dict(zip(keys, [int(x) for x in out]))
+        d = dict(zip(keys, [int(x) for x in out]))
+        d.update(ggx_parked=int(ggx[0]), ggx_resumed=int(ggx[1]), ggx_shade_passes=int(ggx[2]), ggx_shaded_full=int(ggx[3]))
+        return d
 
     def kernel_time(self, reset=True):
         ms, n = C.c_double(), C.c_uint64()

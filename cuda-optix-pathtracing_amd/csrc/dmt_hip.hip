@@ -144,6 +144,11 @@ struct RenderParams {
   // only, at candidate hits.  After `vtxNormals`, so that no other field moves
   OpacityRec const* opacity;
   float opacityCutoff8;
+  // GGX batching (dmt_set_ggx_batch; ggx_park / ggx_resume): the waves' queues of parked hits, [wave][kGgxFields][kGgxQueueCap],
+  // and the batch size T (0: off, the queue is then not read).  Read by k_megakernel only.  After
+  // `opacityCutoff8`, so that no other field moves
+  uint32_t ggxBatchT;
+  float* ggxQueue;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -223,6 +228,11 @@ struct PathState {
   float lastPdf;    // env-map kernels only: pdf / delta flag of the bounce that produced the current ray
   bool lastSpecular;
 };
+// GGX batching (k_megakernel): a lane that has just taken a parked hit back (ggx_resume) carries the
+// path's depth as its complement, i.e. negative, until it shades (ggx_park puts it back).  Such a lane traces no closest
+// ray in that pass: rp.d*.x is the hit's ray direction and rp.o*.x hold tri, bu, bv as bits.  No state of its own: a
+// flag per lane cost the kernel a register.
+DMT_DEV bool ggx_resumed(PathState const& st) { return st.depth < 0; }
 // cold per-lane values in LDS, [field][thread]: pending NEE contribution C (0..2) and the parked
 // radiance Lfin of a finished sample (3..5) with its staging index (6); each is touched once per ray pass at most
 __shared__ float s_cold[7 * kLdsThreads];
@@ -1400,17 +1410,31 @@ DMT_DEV void trace_pair_bvh_motion(KArgs k, PathState const& st, bool doC, bool 
 
 // One "ray pass" of a lane: trace (closest + pending shadow), resolve the shadow ray, shade.
 // sink(L, sidx) is called once per completed sample with the index the sample was started with.
-template <uint32_t F, class Sink>
+// park(doC, bestTri, bu, bv) (GGX batching, megakernel_body): called by every lane of the pass between the shadow resolve and
+// the shading; returns whether the lane still shades in this pass.  NoPark: every lane with a closest ray does.
+struct NoPark {};
+template <uint32_t F, class Sink, class Park = NoPark>
 DMT_DEV void lane_finish(KArgs k, PathState& st, bool doC, bool doS, int bestTri, float bu, float bv, bool occluded,
-                         Sink&& sink);
+                         Sink&& sink, Park&& park = Park{});
 
-template <uint32_t F, class Sink>
-DMT_DEV void lane_step(KArgs k, uint32_t gtid, PathState& st, Sink&& sink, LaneStats* ls = nullptr) {
+template <uint32_t F, class Sink, class Park = NoPark>
+DMT_DEV void lane_step(KArgs k, uint32_t gtid, PathState& st, Sink&& sink, LaneStats* ls = nullptr, Park&& park = Park{}) {
+  constexpr bool PARK = !std::is_same<typename std::decay<Park>::type, NoPark>::value;
   bool const doC = st.active;
   bool const doS = st.hasShadow;
   int bestTri;
   float bu, bv;
   bool occluded;
+  if constexpr (PARK) {
+    // a lane that has taken a parked hit back shades it in this pass and traces no closest ray (its shadow ray, if it has
+    // one, is traced as usual): the hit comes from the closest-ray half of rp, which such a lane does not need (ggx_resume)
+    static_assert(F == 0, "GGX batching: the plain brute-force row only");
+    trace_pair_brute(k, st, doC && !ggx_resumed(st), doS, bestTri, bu, bv, occluded);
+    if (ggx_resumed(st)) bestTri = __float_as_int(st.rp.ox.x), bu = st.rp.oy.x, bv = st.rp.oz.x;
+    sect_mark(2);
+    lane_finish<F>(k, st, doC, doS, bestTri, bu, bv, occluded, sink, park);
+    return;
+  }
   if constexpr ((F & kFeatCutout) && (F & kFeatBvh))
     trace_pair_bvh_cut(k, st, doC, doS, gtid, bestTri, bu, bv, occluded);
   else if constexpr (F & kFeatCutout)
@@ -1429,9 +1453,9 @@ DMT_DEV void lane_step(KArgs k, uint32_t gtid, PathState& st, Sink&& sink, LaneS
 }
 
 // Second half of a ray pass: resolve the shadow ray (in the reference's accumulation order), then shade.
-template <uint32_t F, class Sink>
+template <uint32_t F, class Sink, class Park>
 DMT_DEV void lane_finish(KArgs k, PathState& st, bool doC, bool doS, int bestTri, float bu, float bv, bool occluded,
-                         Sink&& sink) {
+                         Sink&& sink, Park&& park) {
   if (doS) {
     st.hasShadow = false;
     if (st.finPending) {  // the shadow ray of an already finished sample
@@ -1444,6 +1468,8 @@ DMT_DEV void lane_finish(KArgs k, PathState& st, bool doC, bool doS, int bestTri
     }
   }
   sect_mark(3);
+  // (the path's own shadow ray is resolved: a hit that parks here parks no shadow state)
+  if constexpr (!std::is_same<typename std::decay<Park>::type, NoPark>::value) doC = park(doC, bestTri, bu, bv);
   if (doC) {
     if (path_shade<F>(k, st, bestTri, bu, bv)) {
       st.active = false;
@@ -1651,7 +1677,7 @@ constexpr uint32_t kFoldReady = 0xFFFFFFFFu;  // link word: the tile's previous 
 #ifndef DMT_SLAB_WAIT_MS
 #define DMT_SLAB_WAIT_MS 250  // a wave without a live item and without a free slab polls this long, then exits
 #endif
-constexpr int kSchedDiagWords = 8;  // folds, handed over, folded for another wave, stalls, early exits, max stall ticks
+constexpr int kSchedDiagWords = 12;  // folds, handed over, folded for another wave, stalls, early exits, max stall ticks; 8-11: GGX batching
 
 // wave-level bookkeeping (all wave-uniform)
 struct WaveSched {
@@ -1664,7 +1690,8 @@ struct WaveSched {
 };
 // launch diagnostics (dmt_sched_diag; the host checks folds == items): one atomic per EVENT, from lane 0 -- an event is at
 // most once per work item (~10^3 path samples), and counters kept in the wave's registers cost spills in the hot loop
-enum { SD_FOLDS = 0, SD_HANDED = 1, SD_CHAINED = 2, SD_STALLS = 3, SD_EXITS = 4, SD_MAXSTALL = 5 };
+enum { SD_FOLDS = 0, SD_HANDED = 1, SD_CHAINED = 2, SD_STALLS = 3, SD_EXITS = 4, SD_MAXSTALL = 5,
+       SD_GGX_PARKED = 8, SD_GGX_RESUMED = 9, SD_GGX_PASSES = 10, SD_GGX_FULL = 11 };
 DMT_DEV void sched_count(unsigned long long* D, int lane, int what, unsigned long long n = 1ull) {
   if (lane == 0) atomicAdd(&D[what], n);
 }
@@ -1971,6 +1998,112 @@ DMT_DEV bool lane_holds(PathState const& st, LaneSched const& Ls, bool curSlot) 
          (st.finPending && ((get_finIdx() >> 31) != 0u) == curSlot);
 }
 
+// ---- GGX batching (k_megakernel; dmt_set_ggx_batch) ---------------------------------------------------------------
+// The GGX branches of bsdf_prepare, eval_bsdf and sample_bsdf run for the whole wave whenever one lane of a pass has hit
+// a GGX material: on Cornell in more than half of the passes, for one or two lanes.  With a batch size T > 0 such a hit
+// is PARKED instead of shaded: the lane writes the path into the wave's queue in global memory and is free, so it starts
+// its next prepared sample in the next pass like a lane whose path has ended -- a parked path keeps no lane idle.  When the
+// queue holds T records, lanes that are free take them back and shade them together, in one pass, through the same
+// path_shade call as every other lane.  Entering path_shade for a hit is a pure function of what the record holds (no
+// emission is added at a hit in these rows), every sample draws the same sampler dimensions, and the film is folded per
+// chunk in sample-index order from the staging slab: films do not depend on T.
+// Queue: a LIFO per wave, [field][slot] floats, written and read with plain accesses by its own wave only (one wave's
+// vector memory operations on an address complete in order).  Invariants, all wave-uniform:
+//   (1) records in the queue == parked0 + parked1 <= kGgxQueueCap; a hit that finds the queue full is shaded at once;
+//   (2) a parked path belongs to its item: item `cur` is not retired while the parked count of its slot is non-zero
+//       (megakernel_body), so a slot's descriptor and slab outlive every record that names them;
+//   (3) when item cur has no units left and has parked paths, free lanes take records back whatever T is, before they
+//       start a sample of the next item (megakernel_body): paths end, so lanes fall free and the count reaches zero;
+//   (4) hence a wave leaves the loop only with an empty queue: it leaves with no live item, and (2) held for each.
+#ifndef DMT_GGX_BATCH_T
+#define DMT_GGX_BATCH_T 32  // a context's batch size until dmt_set_ggx_batch / DMT_GGX_BATCH say otherwise (DESIGN.md 4.1 has the sweep)
+#endif
+constexpr uint32_t kGgxQueueCap = 64;  // records per wave
+constexpr uint32_t kGgxFields = 24;    // beta, L, ray direction, tri, bu, bv, depth, staging index, (14 unused), dim | lastT, 8 sampler values
+// Wave-uniform state, four scalars.  The hits taken back are not counted on their own: a record leaves the queue only by
+// being taken back, so a wave has taken back what it parked minus what its queue holds when it leaves -- which is what
+// dmt_sync checks (a wave that left with records in its queue).
+struct GgxBatch {
+  uint32_t parked = 0;                             // parked paths of the items in slot 0 (low half) and slot 1 (high half)
+  uint32_t nParked = 0, nPasses = 0, nFull = 0;    // dmt_ggx_batch_diag: flushed once, when the wave leaves
+  DMT_DEV uint32_t queued() const { return (parked & 0xFFFFu) + (parked >> 16); }
+  DMT_DEV uint32_t of_slot(uint32_t slot) const { return (parked >> (slot * 16u)) & 0xFFFFu; }
+};
+DMT_DEV float* ggx_queue(KArgs Pk, uint32_t gtid, uint32_t slot) {
+  return kargs(Pk)->ggxQueue + (size_t(wave_index(gtid)) * (kGgxFields * kGgxQueueCap) + slot);
+}
+DMT_DEV uint32_t lane_rank(unsigned long long m) {  // set bits of m below this lane
+  return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+}
+// Called by every lane of a pass after the shadow resolve (lane_finish): parks the lane's hit if it is a GGX hit below the
+// bounce cap and the queue has room.  Returns whether the lane shades in this pass.
+DMT_DEV bool ggx_park(KArgs Pk, uint32_t gtid, PathState& st, GgxBatch& G, bool doC, int bestTri, float bu, float bv) {
+  if (kargs(Pk)->ggxBatchT == 0u) return doC;  // wave-uniform: off (nothing was ever parked, no lane has resumed)
+  bool const resumed = ggx_resumed(st);
+  if (resumed) st.depth = ~st.depth;
+  bool ggx = false;
+  if (doC && !resumed && bestTri >= 0 && st.depth < kargs(Pk)->maxDepth) {
+    KArgs const k = kargs(Pk);
+    uint32_t const type = hi16(k->scene.bsdfs[k->scene.post[bestTri].matId].w[1]);
+    ggx = type == BS_GGX_DIEL || type == BS_GGX_COND;
+  }
+  unsigned long long const m = __ballot(ggx);
+  bool park = false;
+  if (m != 0ull) {
+    uint32_t const q = G.queued();
+    uint32_t const room = kGgxQueueCap - q;  // invariant (1): q <= kGgxQueueCap
+    uint32_t const want = uint32_t(__popcll(m));
+    uint32_t const n = want < room ? want : room;
+    uint32_t const rank = lane_rank(m);
+    park = ggx && rank < room;  // queue full: shade now
+    if (park) {
+      float* const r = ggx_queue(Pk, gtid, q + rank);  // slot q + rank < q + room == kGgxQueueCap
+      float const* const u = s_sampler_u + threadIdx.x;
+      r[0 * kGgxQueueCap] = st.beta.x, r[1 * kGgxQueueCap] = st.beta.y, r[2 * kGgxQueueCap] = st.beta.z;
+      r[3 * kGgxQueueCap] = st.L.x, r[4 * kGgxQueueCap] = st.L.y, r[5 * kGgxQueueCap] = st.L.z;
+      r[6 * kGgxQueueCap] = st.rp.dx.x, r[7 * kGgxQueueCap] = st.rp.dy.x, r[8 * kGgxQueueCap] = st.rp.dz.x;
+      r[9 * kGgxQueueCap] = __int_as_float(bestTri), r[10 * kGgxQueueCap] = bu, r[11 * kGgxQueueCap] = bv;
+      r[12 * kGgxQueueCap] = __int_as_float(st.depth), r[13 * kGgxQueueCap] = __uint_as_float(st.sidx);
+      r[15 * kGgxQueueCap] = __uint_as_float(uint32_t(st.rng.dim) | (st.lastT ? 0x100u : 0u));
+#pragma unroll
+      for (uint32_t d = 0; d < 8; ++d) r[(16 + d) * kGgxQueueCap] = u[d * kLdsThreads];
+      st.active = false;  // the lane is free: it starts its prepared sample in the next pass
+    }
+    uint32_t const n1 = uint32_t(__popcll(__ballot(park && (st.sidx >> 31) != 0u)));
+    G.parked += (n - n1) + (n1 << 16), G.nParked += n, G.nFull += want - n;  // want - n hits found the queue full
+  }
+  if (__any(doC && (resumed || (ggx && !park)))) ++G.nPasses;  // a pass that runs the GGX branches
+  return doC && !park;
+}
+// Free lanes take the newest records of the queue back (the caller has decided that they should): a lane restores the
+// path and shades the hit in this pass without tracing a closest ray (lane_step).
+DMT_DEV void ggx_resume(KArgs Pk, uint32_t gtid, PathState& st, GgxBatch& G) {
+  uint32_t const q = G.queued();
+  unsigned long long const m = __ballot(!st.active);
+  if (m == 0ull) return;
+  uint32_t const have = uint32_t(__popcll(m));
+  uint32_t const n = have < q ? have : q;
+  uint32_t const rank = lane_rank(m);
+  bool const pop = !st.active && rank < q;
+  if (pop) {
+    float const* const r = ggx_queue(Pk, gtid, q - 1u - rank);  // slot in [q - n, q), q <= kGgxQueueCap
+    float* const u = s_sampler_u + threadIdx.x;
+    st.beta = mk3(r[0 * kGgxQueueCap], r[1 * kGgxQueueCap], r[2 * kGgxQueueCap]);
+    st.L = mk3(r[3 * kGgxQueueCap], r[4 * kGgxQueueCap], r[5 * kGgxQueueCap]);
+    st.rp.dx.x = r[6 * kGgxQueueCap], st.rp.dy.x = r[7 * kGgxQueueCap], st.rp.dz.x = r[8 * kGgxQueueCap];
+    st.rp.ox.x = r[9 * kGgxQueueCap], st.rp.oy.x = r[10 * kGgxQueueCap], st.rp.oz.x = r[11 * kGgxQueueCap];  // tri (as bits), bu, bv
+    st.depth = ~__float_as_int(r[12 * kGgxQueueCap]);  // the mark of a lane that has resumed
+    st.sidx = __float_as_uint(r[13 * kGgxQueueCap]);
+    uint32_t const flags = __float_as_uint(r[15 * kGgxQueueCap]);
+    st.rng.dim = int(flags & 0xFFu), st.lastT = (flags & 0x100u) != 0u;
+#pragma unroll
+    for (uint32_t d = 0; d < 8; ++d) u[d * kLdsThreads] = r[(16 + d) * kGgxQueueCap];
+    st.active = true;
+  }
+  uint32_t const n1 = uint32_t(__popcll(__ballot(pop && (st.sidx >> 31) != 0u)));
+  G.parked -= (n - n1) + (n1 << 16);
+}
+
 template <bool STATS>
 DMT_DEV void flush_stats(KArgs Pk, LaneStats const& ls) {
   if constexpr (STATS) {
@@ -2015,12 +2148,39 @@ DMT_DEV void megakernel_body() {
   if (lane < 16) s_sectAcc[threadIdx.x >> 6][lane] = 0;
   sect_mark(15);
 #endif
+  // GGX batching: the plain row only.  (k_megakernel_env could park its hits as well -- lastPdf and lastSpecular would ride in
+  // the record -- but with the code it needs 44 bytes of scratch instead of 16, so it is compiled as it was)
+  constexpr bool BATCH = F == 0;
+  GgxBatch G;
   {
     for (;;) {
+      if constexpr (BATCH) {
+        // Free lanes take parked hits back BEFORE they start a sample: when the queue holds a batch, or (invariant 3)
+        // when item cur has no units left and still has parked paths -- those are drained whatever T is, so that cur
+        // can be retired; records of item cur + 1 that lie above them in the LIFO come back with them.  The same when
+        // the item units are drawn from has none left: a free lane would have nothing else to start.
+        uint32_t const q = G.queued();
+        if (q != 0u) {  // (never with T == 0)
+          uint32_t const ofCur = G.of_slot(W.cur & 1u);
+          bool const drain = W.nextUnit == W.totalUnits || (W.alloc != W.cur && ofCur != 0u);
+          if (drain || q >= kargs(Pk)->ggxBatchT) ggx_resume(Pk, gtid, st, G);
+        }
+      }
       bool const needPrep = !Ls.prepared;
       bool const starving = !st.active && needPrep;
-      if (__any(starving) || __popcll(__ballot(needPrep)) >= DMT_PREP_THRESHOLD) sched_draw<MOTION>(Pk, gtid, lane, W, Ls, needPrep);
-      if (W.cur == W.fetched) break;  // nothing live and nothing fetched: the launch has no more items
+      if (__any(starving) || __popcll(__ballot(needPrep)) >= DMT_PREP_THRESHOLD) {
+        if constexpr (BATCH) {
+          // The lane index goes through an opaque copy: item_fetch forms an LDS address from it (s_pixbase + lane) that is
+          // otherwise hoisted out of this loop and kept in a VGPR across it, the one register the kernel does not have
+          // (make asm: 8 bytes of scratch, that address spilled at kernel start).  The copy is one move per call.
+          int l = lane;
+          asm volatile("" : "+v"(l));
+          sched_draw<MOTION>(Pk, gtid, l, W, Ls, needPrep);
+        } else {
+          sched_draw<MOTION>(Pk, gtid, lane, W, Ls, needPrep);
+        }
+      }
+      if (W.cur == W.fetched) break;  // nothing live and nothing fetched: the launch has no more items (invariant 4: nothing parked)
       if (!st.active && Ls.prepared) {
         path_begin_prepared<MOTION>(st);
         Ls.prepared = false;
@@ -2028,7 +2188,19 @@ DMT_DEV void megakernel_body() {
       }
       sect_mark(0);
       if (W.alloc != W.cur || W.nextUnit == W.totalUnits) {  // item cur has no units left: is it complete?
-        if (!__any(lane_holds(st, Ls, (W.cur & 1u) != 0u))) {
+        // (invariant 2: not while one of its paths is parked -- that path's sample is not staged yet)
+        // Spelled twice on purpose.  With one statement and the parked term in its condition -- as `!held && !__any(..)` or as
+        // `!__any(held || ..)`, `held` a constant false in the other rows -- every brute-force row that does not batch changed
+        // its register allocation (make asm: k_megakernel_tex 40 -> 84 bytes of scratch, k_megakernel_area 4 -> 12 spilled
+        // SGPRs); with the parent's statement kept as it is they compile as before.  An edit to one copy belongs in the other.
+        if constexpr (BATCH) {
+          if (G.of_slot(W.cur & 1u) == 0u && !__any(lane_holds(st, Ls, (W.cur & 1u) != 0u))) {
+            bool const more = sched_retire(Pk, gtid, lane, W);
+            sect_mark(1);
+            if (!more) break;
+            continue;
+          }
+        } else if (!__any(lane_holds(st, Ls, (W.cur & 1u) != 0u))) {
           bool const more = sched_retire(Pk, gtid, lane, W);  // fold it, or hand it over (never waits for another wave's item)
           sect_mark(1);
           if (!more) break;
@@ -2036,8 +2208,20 @@ DMT_DEV void megakernel_body() {
         }
       }
       sect_mark(1);
-      lane_step<F>(Pk, gtid, st, sink, STATS ? &ls : nullptr);
+      if constexpr (BATCH)
+        lane_step<F>(Pk, gtid, st, sink, nullptr, [&](bool doC, int tri, float bu, float bv) {
+          return ggx_park(Pk, gtid, st, G, doC, tri, bu, bv);
+        });
+      else
+        lane_step<F>(Pk, gtid, st, sink, STATS ? &ls : nullptr);
     }
+  }
+  if constexpr (BATCH) {  // (both exits of the loop are taken with no live item: the queue is empty)
+    unsigned long long* const D = kargs(Pk)->schedDiag;
+    int const first = int(lane_rank(~0ull));  // 0 in lane 0; formed here, so that nothing of it is live across the loop
+    if (G.nParked != 0u) sched_count(D, first, SD_GGX_PARKED, G.nParked), sched_count(D, first, SD_GGX_RESUMED, G.nParked - G.queued());
+    if (G.nPasses != 0u) sched_count(D, first, SD_GGX_PASSES, G.nPasses);
+    if (G.nFull != 0u) sched_count(D, first, SD_GGX_FULL, G.nFull);
   }
 #if DMT_SECTION_TIMING
   if (lane < 16) atomicAdd(&g_sect[lane], s_sectAcc[threadIdx.x >> 6][lane]);
@@ -2467,6 +2651,10 @@ struct dmt_ctx {
   unsigned long long expectedFolds = 0;    // work items launched so far: what d_schedDiag[0] must read once the stream has drained
   DevBuf<unsigned long long> d_stats;      // 16 device counters of dmt_render_stats / dmt_render_profile
   DevBuf<float> d_stage;        // staging slabs of finished samples, [wave][kSlabsPerWave][chunkSpp][64] float3
+  // GGX batching (ggx_park / ggx_resume): the queues of parked hits, [wave][kGgxFields][kGgxQueueCap], grown on demand
+  DevBuf<float> d_ggxQueue;
+  uint32_t ggxBatchT = DMT_GGX_BATCH_T;  // dmt_set_ggx_batch, DMT_GGX_BATCH at context creation; 0 = off
+  unsigned long long ggxLostReported = 0;  // parked - taken back that checkErrorFlag has reported already (0 in a healthy context)
   // sampler table of a launch (samplerTablePlan, k_sampler_table): refilled by every dmt_render call that uses it, grown on demand
   DevBuf<float4> d_samTab;
   DevBuf<float2> d_samTabJit;
@@ -3042,8 +3230,18 @@ int ensureLightTree(dmt_ctx* ctx) {
 // (item_complete / fold_chain count their folds).  Anything else means the hand-over protocol lost or duplicated a sample
 // chunk and the film is not the ordered fold the contract promises.
 int checkErrorFlag(dmt_ctx* ctx) {
-  unsigned long long folds = 0;
-  HIP_TRY(ctx, hipMemcpy(&folds, ctx->d_schedDiag.get(), sizeof(folds), hipMemcpyDeviceToHost));
+  unsigned long long d[kSchedDiagWords] = {};
+  HIP_TRY(ctx, hipMemcpy(d, ctx->d_schedDiag.get(), sizeof(d), hipMemcpyDeviceToHost));
+  unsigned long long const folds = d[SD_FOLDS];
+  // a wave left a launch with parked hits in its queue: their samples are missing.  Reported once per difference; the
+  // device counters stay as they are for dmt_ggx_batch_diag
+  if (d[SD_GGX_PARKED] - d[SD_GGX_RESUMED] != ctx->ggxLostReported) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "GGX batching: %llu hits were parked, %llu were taken back: the film is invalid", d[SD_GGX_PARKED],
+             d[SD_GGX_RESUMED]);
+    ctx->ggxLostReported = d[SD_GGX_PARKED] - d[SD_GGX_RESUMED];
+    return fail(ctx, DMT_ERR_HIP, msg);
+  }
   if (folds != ctx->expectedFolds) {
     char msg[200];
     snprintf(msg, sizeof(msg), "in-launch ordering: %llu sample chunks were folded into the film, %llu were launched: the film is invalid",
@@ -3122,6 +3320,10 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
   if (char const* e7 = std::getenv("DMT_SAMPLER_TABLE")) {  // A/B runs and tests: 0 off, 1 automatic (the default), 2 force
     int const v = std::atoi(e7);
     ctx->samTabMode = v == 0 ? DMT_SAMPLER_TABLE_OFF : v == 2 ? DMT_SAMPLER_TABLE_FORCE : DMT_SAMPLER_TABLE_AUTO;
+  }
+  if (char const* e8 = std::getenv("DMT_GGX_BATCH")) {  // A/B runs and tests: 0 off, T = batch size (at most the queue's capacity)
+    int const v = std::atoi(e8);
+    ctx->ggxBatchT = v <= 0 ? 0u : std::min<uint32_t>(uint32_t(v), kGgxQueueCap);
   }
   if (char const* e2 = std::getenv("DMT_SUB_SHIFT")) {  // scheduling experiments only: results do not depend on it
     int const v = std::atoi(e2);
@@ -3548,6 +3750,10 @@ static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0
     HIP_TRY(ctx, ctx->d_stage.reserve(floats));
     P.stage = ctx->d_stage.get();
   }
+  if (ctx->ggxBatchT != 0u && F == 0u && !stats6 && !wavefront) {  // the row that parks GGX hits: one queue per wave
+    HIP_TRY(ctx, ctx->d_ggxQueue.reserve(size_t(blocks) * size_t(kLdsThreads / 64) * size_t(kGgxFields) * size_t(kGgxQueueCap)));  // (wave_index)
+    P.ggxQueue = ctx->d_ggxQueue.get(), P.ggxBatchT = ctx->ggxBatchT;
+  }
   // A call with a sampler table runs as tab.slices consecutive sample slices, each a table fill and a megakernel launch
   // over a whole number of chunks, all inside the one event pair; the film is bit-identical under any split of the
   // sample range.  Without a table the call is one slice.
@@ -3800,9 +4006,26 @@ int dmt_sched_diag(dmt_ctx* ctx, uint64_t* out8, int reset) {
   out8[6] = ctx->expectedFolds;
   out8[7] = uint64_t(kSlabsPerWave);
   if (reset) {
-    HIP_TRY(ctx, hipMemset(ctx->d_schedDiag.get(), 0, sizeof(d)));
-    ctx->expectedFolds = 0;
+    HIP_TRY(ctx, hipMemset(ctx->d_schedDiag.get(), 0, sizeof(d)));  // (the GGX batching words too: read dmt_ggx_batch_diag first)
+    ctx->expectedFolds = 0, ctx->ggxLostReported = 0;
   }
+  return DMT_OK;
+}
+
+int dmt_set_ggx_batch(dmt_ctx* ctx, uint32_t batch) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (batch > kGgxQueueCap) return fail(ctx, DMT_ERR_INVALID, "dmt_set_ggx_batch: a batch is at most 64 hits (the queue's capacity)");
+  ctx->ggxBatchT = batch;
+  return DMT_OK;
+}
+
+int dmt_ggx_batch_diag(dmt_ctx* ctx, uint64_t* out5) {
+  if (!ctx || !out5) return DMT_ERR_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  unsigned long long d[kSchedDiagWords] = {};
+  HIP_TRY(ctx, hipMemcpy(d, ctx->d_schedDiag.get(), sizeof(d), hipMemcpyDeviceToHost));
+  out5[0] = d[SD_GGX_PARKED], out5[1] = d[SD_GGX_RESUMED], out5[2] = d[SD_GGX_PASSES], out5[3] = d[SD_GGX_FULL], out5[4] = ctx->ggxBatchT;
   return DMT_OK;
 }
 

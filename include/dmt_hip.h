@@ -429,6 +429,20 @@ int dmt_sync(dmt_ctx* ctx);
  * wave, times a wave found all its staging slabs handed over, waves that left the launch early because of that,
  * longest such stall in 10 ns ticks, sample chunks launched (must equal [0]), staging slabs per wave}. */
 int dmt_sched_diag(dmt_ctx* ctx, uint64_t* out8, int reset);
+/* GGX batching (brute-force launches without an env map, textures, area lights, motion, cutouts, vertex normals or a light
+ * tree, i.e. k_megakernel; every other launch ignores the setting).  A hit on a GGX material below the bounce cap is not shaded in the pass that found it:
+ * the lane writes the path into its wave's queue in device memory and starts its next sample; when `batch` hits wait
+ * (or their work item has no other work left), lanes that fall free take them back and shade them together.  The film is
+ * bit-identical for every batch, 0 (off) included.  batch <= 64; DMT_GGX_BATCH=0|T in the environment sets it at context
+ * creation.  Off is not free: the kernel carries the code either way, and with batch 0 the 1024^2 Cornell frame runs
+ * about 1 % slower than it did before the kernel had it; so does a scene without a GGX material.
+ * dmt_sync (and what reports like it) fails if a launch took back fewer hits than it parked. */
+int dmt_set_ggx_batch(dmt_ctx* ctx, uint32_t batch);
+/* Its counters since the last dmt_sched_diag reset (synchronises): out5 = {hits parked, hits taken back, shading passes that
+ * ran the GGX code, GGX hits shaded at once because the queue was full, the context's batch size}.  The first four are
+ * counted while batching is on only.  dmt_sched_diag itself reports none of them (its eight words are taken), and its
+ * reset clears them: read these first. */
+int dmt_ggx_batch_diag(dmt_ctx* ctx, uint64_t* out5);
 /* HIP-event time of the megakernel launches since the last reset (synchronises the stream):
  * total milliseconds and launch count. */
 int dmt_kernel_time(dmt_ctx* ctx, double* total_ms, uint64_t* launches, int reset);
