@@ -2,8 +2,9 @@
 // a-trous filter and temporal accumulation, and the rules that keep the temporal history and its raw-vertex mirror valid.
 //
 // Part of dmt_hip.hip's translation unit, included once after the host helpers it uses (dmt_ctx, HIP_TRY, fail, baseParams,
-// checkErrorFlag, cameraFromRaster, worldFromCamera; accel_host.hpp's requireTree, reserveOverflow, motionParams) and before
-// the first entry point that calls into it.  accel_host.hpp forward-declares the two mirror calls below for its vertex updates.
+// checkErrorFlag, cameraFromRaster, worldFromCamera; accel_host.hpp's requireTree, reserveOverflow, motionParams;
+// surface_host.hpp's firstHitVariant) and before the first entry point that calls into it.  accel_host.hpp forward-declares
+// the two mirror calls below for its vertex updates.
 // The rest of the library reaches DenoiseState through dropHistory / dropVertexMirror and the two mirror calls below.
 #pragma once
 
@@ -216,12 +217,10 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
     return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: upload triangles, bsdfs and set the camera first");
   if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
     return fail(ctx, DMT_ERR_INVALID, "dmt_render_aovs: material index outside the BSDF array");
-  if (ctx->texCount > 0 && (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount))
+  if (!ctx->surf.texturesMatch(ctx->bsdfCount, ctx->triCount))
     return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
-  if (ctx->haveVtxNormals && ctx->ac.haveMotion)
-    return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: vertex normals (dmt_upload_vertex_normals) together with motion blur are not supported");
-  if (ctx->haveOpacity && (ctx->ac.haveMotion || ctx->haveVtxNormals))
-    return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: opacity textures (dmt_upload_opacity) together with motion blur or vertex normals are not supported");
+  int variant = 0;
+  if (int const rcV = firstHitVariant(ctx, "dmt_render_aovs", &variant)) return rcV;
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   if (int const rcT = useBvh ? requireTree(ctx, "dmt_render_aovs") : DMT_OK) return rcT;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -243,7 +242,8 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   RenderParams P = baseParams(ctx, threads);
   uint32_t const motionMask = ctx->ac.haveMotion ? kFeatMotion | (useBvh ? kFeatBvh : 0u) : 0u;  // the samples' times, as the film's rows
   if (int const rcM = motionParams(ctx, motionMask, P)) return rcM;
-  hipLaunchKernelGGL(ctx->haveOpacity ? k_aov_cut : ctx->ac.haveMotion ? k_aov_motion : ctx->haveVtxNormals ? k_aov_vn : k_aov, dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
+  decltype(&k_aov) const kernels[4] = {k_aov, k_aov_vn, k_aov_motion, k_aov_cut};  // by firstHitVariant
+  hipLaunchKernelGGL(kernels[variant], dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
   HIP_TRY(ctx, hipGetLastError());
   ctx->dn.aovW = ctx->filmW, ctx->dn.aovH = ctx->filmH;
   ctx->dn.aovSurface = true;

@@ -3,7 +3,7 @@
 //
 // Part of dmt_hip.hip's translation unit, included once at its end: it uses the device code, dmt_ctx, HIP_TRY, fail,
 // baseParams, resolveFeatures / kernelOf and finishTest defined there, accel_host.hpp's requireTree, reserveOverflow and
-// motionParams, and denoise_host.hpp's makeProjXf.  A probe: a kernel with one lane per case, an entry point staging its arrays (probe_stage.hpp).
+// motionParams, surface_host.hpp's firstHitVariant, and denoise_host.hpp's makeProjXf.  A probe: a kernel with one lane per case, an entry point staging its arrays (probe_stage.hpp).
 #pragma once
 
 #include "probe_stage.hpp"
@@ -586,7 +586,7 @@ int dmt_test_material(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, 
   if (!ctx || n < 0 || !tri || !bu || !bv || !ng3 || !rec32 || !ns3 || !rec2_32 || !mix) return DMT_ERR_INVALID;
   if (!(ctx->haveTris && ctx->haveBsdfs)) return fail(ctx, DMT_ERR_STATE, "dmt_test_material: triangles and BSDFs first");
   if (int const rc = sceneReady(ctx, "dmt_test_material", false)) return rc;
-  if (ctx->texCount > 0 && (ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount))
+  if (!ctx->surf.texturesMatch(ctx->bsdfCount, ctx->triCount))
     return fail(ctx, DMT_ERR_STATE, "dmt_test_material: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
   for (int i = 0; i < n; ++i)
     if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_material: triangle index out of range");
@@ -657,10 +657,10 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
 int dmt_test_texture_filter(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const int32_t* tex,
                             const int32_t* depth, float* rgb3, int32_t* branch, float* lod) {
   if (!ctx || n < 0 || !tri || !bu || !bv || !tex || !depth || !rgb3 || !branch || !lod) return DMT_ERR_INVALID;
-  if (!(ctx->haveTris && ctx->haveCamera) || ctx->texCount == 0 || ctx->triUvCount != ctx->triCount)
+  if (!(ctx->haveTris && ctx->haveCamera) || ctx->surf.tex.count == 0 || ctx->surf.tex.triUvCount != ctx->triCount)
     return fail(ctx, DMT_ERR_STATE, "dmt_test_texture_filter: triangles, camera and textures (with one UV triple per triangle) first");
   for (int i = 0; i < n; ++i)
-    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount || tex[i] < 0 || uint32_t(tex[i]) >= ctx->texCount)
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount || tex[i] < 0 || uint32_t(tex[i]) >= ctx->surf.tex.count)
       return fail(ctx, DMT_ERR_INVALID, "dmt_test_texture_filter: triangle or texture index out of range");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
@@ -677,17 +677,16 @@ int dmt_test_texture_filter(dmt_ctx* ctx, int n, const int32_t* tri, const float
 int dmt_test_trace_log(dmt_ctx* ctx, int px, int py, int s, float* rec12, int cap, int* n_out, float* L3) {
   if (!ctx || !rec12 || cap <= 0 || !n_out || !L3) return DMT_ERR_INVALID;
   if (int const rc = sceneReady(ctx, "dmt_test_trace_log", true)) return rc;
-  if (ctx->ac.haveMotion && ctx->haveVtxNormals)
-    return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_log: vertex normals (dmt_upload_vertex_normals) together with motion blur are not supported");
+  int variant = 0;
+  if (int const rc = firstHitVariant(ctx, "dmt_test_trace_log", &variant)) return rc;
   Probe p(ctx->device, 1);  // one path, walked by one lane
   ProbeOut<float> dr(p, rec12, 12 * size_t(cap)), dL(p, L3, 3);
   ProbeOut<int> dn(p, n_out, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
   RenderParams P = baseParams(ctx, p.threads(64));
   if (int const rc = motionParams(ctx, ctx->ac.haveMotion ? kFeatMotion : 0u, P)) return rc;  // (brute force: no tree)
-  if (ctx->haveOpacity && (ctx->ac.haveMotion || ctx->haveVtxNormals))
-    return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_log: opacity textures (dmt_upload_opacity) together with motion blur or vertex normals are not supported");
-  hipLaunchKernelGGL(ctx->haveOpacity ? k_test_trace_log_cut : ctx->ac.haveMotion ? k_test_trace_log_motion : ctx->haveVtxNormals ? k_test_trace_log_vn : k_test_trace_log, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
+  decltype(&k_test_trace_log) const kernels[4] = {k_test_trace_log, k_test_trace_log_vn, k_test_trace_log_motion, k_test_trace_log_cut};  // by firstHitVariant
+  hipLaunchKernelGGL(kernels[variant], dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, px, py, s,
                      dr.get(), cap, dn.get(), dL.get());
   return finishProbe(ctx, p);
 }
@@ -736,10 +735,10 @@ int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const floa
 static int probeShadingNormal(dmt_ctx* ctx, bool mapped, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3, float* ns3) {
   if (!ctx || n < 0 || !tri || !bu || !bv || !rd3 || !ns3) return DMT_ERR_INVALID;
   if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: upload triangles first");
-  if (!ctx->haveVtxNormals) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: no vertex normals (dmt_upload_vertex_normals first)");
+  if (!ctx->surf.vn.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: no vertex normals (dmt_upload_vertex_normals first)");
   if (mapped) {
     if (int const rc = sceneReady(ctx, "dmt_test_shading_normal_mapped", false)) return rc;
-    if (!ctx->haveBsdfs || ctx->texCount == 0 || ctx->matTexCount != ctx->bsdfCount || ctx->triUvCount != ctx->triCount)
+    if (!ctx->haveBsdfs || ctx->surf.tex.count == 0 || !ctx->surf.texturesMatch(ctx->bsdfCount, ctx->triCount))
       return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal_mapped: BSDFs and textures (matching the uploaded BSDFs / triangles) first");
   }
   for (int i = 0; i < n; ++i)
@@ -763,7 +762,7 @@ int dmt_test_shading_normal_mapped(dmt_ctx* ctx, int n, const int32_t* tri, cons
 
 int dmt_test_opacity(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, float* alpha8, uint8_t* pass) {
   if (!ctx || n < 0 || !tri || !bu || !bv || !alpha8 || !pass) return DMT_ERR_INVALID;
-  if (!ctx->haveOpacity) return fail(ctx, DMT_ERR_STATE, "dmt_test_opacity: no opacity (dmt_upload_opacity first)");
+  if (!ctx->surf.op.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_opacity: no opacity (dmt_upload_opacity first)");
   for (int i = 0; i < n; ++i)
     if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_opacity: triangle index out of range");
   if (n == 0) return DMT_OK;
@@ -782,7 +781,7 @@ int dmt_test_closest_hit_opacity(dmt_ctx* ctx, int nrays, const float* o3, const
                                  float* uv2, uint8_t* occluded) {
   if (!ctx || nrays < 0 || !o3 || !d3 || !tmax || !tri_index || !t) return DMT_ERR_INVALID;
   if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: upload triangles first");
-  if (!ctx->haveOpacity) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: no opacity (dmt_upload_opacity first)");
+  if (!ctx->surf.op.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: no opacity (dmt_upload_opacity first)");
   if (nrays == 0) return DMT_OK;
   Probe p(ctx->device, size_t(nrays));
   ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3), dM(p, tmax, 1);

@@ -1,0 +1,85 @@
+// surface_state.hpp -- what a context keeps for the surface-attribute layer: image textures with their MIP chains and UVs,
+// the first-hit texture filter and its camera footprint, per-vertex normals, opacity records and emissive triangles.  The
+// layer's device code is in surface_device.hpp (vnormals.hpp, opacity.hpp), its helpers and entry points in surface_host.hpp.
+//
+// Part of dmt_hip.hip's translation unit, included once before dmt_ctx: it uses DevBuf, RenderParams, VtxNormalRec and
+// OpacityRec.
+//
+// What invalidates what.  "drop" frees a record's arrays and zeroes its counts, so its *_info call answers zeros and fill()
+// leaves its RenderParams fields null.  The caller has drained the stream where a launch in flight may read the arrays.
+//
+//   event            member function     vertex normals   opacity   emissive triangles   textures and UVs
+//   soup replaced    soupReplaced        drop             drop      drop                 kept (checked at launch: texturesMatch)
+//   BSDFs replaced   bsdfsReplaced       kept             drop      kept                 kept (checked at launch: texturesMatch)
+//   textures         texturesReplaced    kept             drop      kept                 the old tables are dropped first: a refused
+//   replaced or                                                                          upload leaves the context without textures
+//   cleared
+//   vertices updated (none)              kept             kept      kept                 kept
+//   (dmt_update_vertices*)
+//
+// Opacity records are made from the soup's materials, the texture descriptors and the UVs, so each of the three takes them
+// along.  The texture filter mode and the camera footprint survive everything (dmt_set_texture_filter, dmt_set_camera).
+#pragma once
+
+namespace {
+
+struct SurfaceState {
+  // SURVEY 8f-1 image textures (dmt_upload_textures)
+  struct Textures {
+    DevBuf<uint32_t> rgba;
+    DevBuf<int32_t> desc;      // 3 words per texture
+    DevBuf<uint32_t> matTex;   // 4 words per BSDF
+    DevBuf<float> triUv;       // 6 floats per triangle
+    DevBuf<uint32_t> mip;      // MIP levels 1.. of every texture (buildMipChain)
+    DevBuf<int32_t> mipDesc;   // 2 words per texture: {levels, first texel of level 1}
+    uint32_t count = 0, matTexCount = 0;
+    size_t triUvCount = 0;
+  } tex;
+  int texFilter = DMT_TEXFILTER_LEVEL0;
+  float texFoot[19] = {};      // dmt_texture_footprint of the current camera
+  // smooth shading (dmt_upload_vertex_normals; vnormals.hpp): one record per triangle of the soup
+  struct VertexNormals {
+    DevBuf<VtxNormalRec> recs;
+    bool have = false;
+    uint64_t smooth = 0;       // triangles with a smooth record
+  } vn;
+  // alpha cutouts (dmt_upload_opacity; opacity.hpp): one record per triangle of the soup
+  struct Opacity {
+    DevBuf<OpacityRec> recs;
+    bool have = false;
+    float cutoff = 0.f;
+    uint64_t cutoutTris = 0;
+    uint32_t cutoutMats = 0;
+  } op;
+  // SURVEY 8f-3 emissive triangles (dmt_upload_area_lights)
+  struct Emissive {
+    DevBuf<uint32_t> of, tri;  // [triangle] index into the list, 0xFFFFFFFF: not emissive; [count] triangle index
+    DevBuf<float> le;          // [count] rgb radiance
+    uint32_t count = 0;
+  } area;
+
+  // the events of the table above
+  void soupReplaced() { vn = VertexNormals{}, op = Opacity{}, area = Emissive{}; }
+  void bsdfsReplaced() { op = Opacity{}; }
+  void texturesReplaced() { tex = Textures{}, op = Opacity{}; }
+
+  // the texture tables, if any, are of the uploaded BSDFs and triangles: what every launch that reads them asks first
+  bool texturesMatch(uint32_t bsdfCount, size_t triCount) const { return tex.count == 0 || (tex.matTexCount == bsdfCount && tex.triUvCount == triCount); }
+
+  // the layer's part of the argument struct (baseParams)
+  void fill(RenderParams& P) const {
+    P.areaOf = area.of.get(), P.areaTri = area.tri.get(), P.areaLe = area.le.get(), P.areaCount = area.count;
+    if (vn.have) P.vtxNormals = vn.recs.get();
+    if (op.have) P.opacity = op.recs.get(), P.opacityCutoff8 = op.cutoff * 255.f;
+    if (tex.count > 0) {
+      P.texRgba = tex.rgba.get(), P.texDesc = tex.desc.get(), P.matTex = tex.matTex.get(), P.triUv = tex.triUv.get();
+      P.texMip = tex.mip.get(), P.texMipDesc = tex.mipDesc.get();
+      memcpy(P.texCfr, texFoot, 12 * sizeof(float));
+      memcpy(P.texMinDx, texFoot + 12, 3 * sizeof(float));
+      memcpy(P.texMinDy, texFoot + 15, 3 * sizeof(float));
+      P.texSppScale = texFoot[18];
+    }
+  }
+};
+
+}  // namespace
