@@ -463,6 +463,9 @@ int dmt_accel_download(dmt_ctx* ctx, void* nodes64, size_t node_cap, uint32_t* p
   return DMT_OK;
 }
 
+// Host-only: build the BVH of a soup and check its invariants (every triangle in exactly one leaf, every DECODED
+// (quantised) child box encloses all vertices below it and lies inside its parent's decoded box up to one quantisation
+// step, inner children first with consecutive indices, depth within the traversal-stack bound).
 int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t count, int* node_count, int* depth,
                      int* max_leaf) {
   if ((count && (!xs || !ys || !zs)) || count > 0x0FFFFFFFu) return DMT_ERR_INVALID;

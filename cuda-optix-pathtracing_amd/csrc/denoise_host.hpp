@@ -179,7 +179,7 @@ int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params,
   if (bad) {
     char msg[400];
     snprintf(msg, sizeof(msg), "%u pixel(s) have fewer than 2 samples or a non-finite mean / M2%s", bad,
-             !mean4 && ctx->world > 1 ? " (this context renders only the tiles of its dmt_set_partition rank: combine the ranks' "
+             !mean4 && ctx->launch.world > 1 ? " (this context renders only the tiles of its dmt_set_partition rank: combine the ranks' "
                                         "films and pass the combined film as mean4 / m24)" : "");
     return failn(DMT_ERR_STATE, msg);
   }
@@ -232,7 +232,7 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   HIP_TRY(ctx, ctx->dn.pos.reserve(pixels));
   HIP_TRY(ctx, ctx->dn.surface.reserve(pixels));
   // a grid of a few 256-lane blocks per CU strides over the frame: the BVH overflow stack is sized by the launch's lanes
-  size_t const blocks = std::min((pixels + 255) / 256, size_t(std::max(ctx->cuCount, 1)) * 8);
+  size_t const blocks = std::min((pixels + 255) / 256, size_t(std::max(ctx->launch.cuCount, 1)) * 8);
   size_t const threads = blocks * 256;
   if (useBvh) HIP_TRY(ctx, reserveOverflow(ctx, threads));
   AovArgs A{};

@@ -1145,405 +1145,7 @@ DMT_DEV void path_begin_prepared(PathState& st) {
   if constexpr (MOTION) motion_begin_prepared();
 }
 
-#ifndef DMT_MIN_WAVES_PER_SIMD
-#define DMT_MIN_WAVES_PER_SIMD 4
-#endif
-#ifndef DMT_MIN_WAVES_PER_SIMD_BVH
-#define DMT_MIN_WAVES_PER_SIMD_BVH 3
-#endif
-constexpr uint32_t kMaxChunkSpp = 512;  // staging: 384 KB per slab at most
-#ifndef DMT_SLABS_PER_WAVE
-#define DMT_SLABS_PER_WAVE 4
-#endif
-constexpr int kSlabsPerWave = DMT_SLABS_PER_WAVE;  // staging slabs per wave: two live items + two handed over
-#ifndef DMT_PREP_THRESHOLD
-#define DMT_PREP_THRESHOLD 64
-#endif
-struct TileArgs {  // what a wave needs when it picks up a new work item
-  float4* mean;
-  float4* m2;
-  uint32_t* counter;
-  int width, x0, y0, x1, y1, tx0, ty0, rtx;
-  uint32_t numItems, subShift, sampleOffset, spp, chunkSpp, numChunks;
-  uint32_t* link;
-  uint32_t* slabBusy;
-  float* stage;
-  int rank, world;
-};
-DMT_DEV TileArgs load_tile_args(KArgs k) {
-  k = kargs(k);
-  TileArgs t;
-  t.mean = k->mean, t.m2 = k->m2, t.counter = k->counter, t.width = k->width;
-  t.x0 = k->x0, t.y0 = k->y0, t.x1 = k->x1, t.y1 = k->y1, t.tx0 = k->tx0, t.ty0 = k->ty0, t.rtx = k->rtx;
-  t.numItems = k->numItems, t.subShift = k->subShift, t.sampleOffset = k->sampleOffset, t.spp = k->spp, t.rank = k->rank, t.world = k->world;
-  t.chunkSpp = k->chunkSpp, t.numChunks = k->numChunks, t.link = k->link, t.slabBusy = k->slabBusy, t.stage = k->stage;
-  return t;
-}
-
-// ---- work items ------------------------------------------------------------------------------------
-// Work item = (sample chunk c, owned tile t), handed out chunk-major from one atomic counter: all tiles
-// of chunk 0, then chunk 1, ...  An item is n samples x 64 pixels = up to 64 n UNITS (pixel, sample).
-//
-// * Lanes are not tied to pixels.  A lane that needs work takes the item's next unit (wave-wide ballot +
-//   prefix count on a wave-uniform cursor; unit u -> pixel u mod 64, sample u div 64, so a batch of 64
-//   requests is one sample of every pixel).  Path lengths differ between pixels (glass vs wall) and between
-//   samples; with lane == pixel every item ran at the pace of its slowest pixel, now the wave stays full
-//   until the item runs out of units.
-// * A finished sample's radiance goes to one of the wave's kSlabsPerWave staging SLABS in global memory
-//   ([sample][pixel] float3, written through so that any wave can read it back).  The film is the reference's
-//   Welford update (SMEMLayout::updateSample, T/megakernel/megakernel.cuh:59-79) applied to a pixel's samples
-//   IN INDEX ORDER, so chunk c of a tile must be folded after chunk c-1 -- while chunks c and c+1 are traced
-//   CONCURRENTLY by different waves (a small frame, or one GPU's share of a frame split eight ways, still fills
-//   the machine).  Nobody waits for that order; the fold is HANDED OVER instead (item_complete):
-//     - every (chunk, tile) has one hand-over word `link`, zero at launch.  Exactly two parties touch it, each
-//       with ONE atomic exchange: the wave that finishes tracing chunk c writes "slab + 1", the wave that has
-//       put chunk c-1 into the film writes kFoldReady.  Exchanges on one word are totally ordered, so exactly
-//       one of the two sees the other's value, and that one folds chunk c: the finisher if the predecessor was
-//       already in the film, else the predecessor's folder, which then goes on to chunk c+1 the same way
-//       (fold_chain).  Chunk 0 is folded by its finisher.
-//     - a slab that was handed over stays busy until its folder clears `slabBusy`; its owner meanwhile uses
-//       another of its slabs.
-//   The film is therefore bit-identical for every chunk size and schedule, and no wave ever spins on another
-//   wave's progress while it holds work: the only wait left is a wave with NO live item whose slabs are all
-//   handed over and not folded yet (sched_retire) -- it holds nothing anybody needs, polls for a bounded wall
-//   clock time and then EXITS (the remaining items are fetched by the other waves; counted in schedDiag).
-//   Round 2's protocol had the finisher spin on a per-tile completion counter instead.  That is deadlock-free
-//   only if every wave that has fetched an item keeps running; it gave up (error flag, 71 s per step) when four
-//   processes' persistent kernels shared one GPU (DESIGN.md 7 has the record).
-// * A wave holds up to TWO live items (sequence numbers cur and cur+1, LDS slots seq & 1): when item cur has
-//   no units left, free lanes draw from item cur+1 (fetched at that moment) while the last paths of cur drain;
-//   when cur's last sample is staged the wave completes it (lane i folds pixel i; whatever lane i is tracing
-//   meanwhile stays in its registers).  Small items are therefore cheap, which keeps the end-of-launch tail
-//   short when a frame is split over 8 GPUs.
-__shared__ uint32_t s_desc[kLdsThreads / 64][2][8];  // per wave, per slot: chunk, tile item, px0, py0, s0, first float of the slab, nInside, slab
-__shared__ int32_t s_pixbase[2 * kLdsThreads];       // per slot, per pixel: Halton pixel base, -1 = outside the region
-__shared__ uint32_t s_pixmap[2 * kLdsThreads];       // per slot: j-th pixel inside the region
-
-constexpr uint32_t kSlotBit = 0x80000000u;  // staging index = slot bit | (sample * 64 + pixel)
-constexpr uint32_t kFoldReady = 0xFFFFFFFFu;  // link word: the tile's previous chunk is in the film
-#ifndef DMT_SLAB_WAIT_MS
-#define DMT_SLAB_WAIT_MS 250  // a wave without a live item and without a free slab polls this long, then exits
-#endif
-constexpr int kSchedDiagWords = 12;  // folds, handed over, folded for another wave, stalls, early exits, max stall ticks; 8-11: GGX batching
-
-// wave-level bookkeeping (all wave-uniform)
-struct WaveSched {
-  uint32_t cur = 0, fetched = 0;          // live items are [cur, fetched), at most two
-  uint32_t alloc = 0;                     // item units are drawn from
-  uint32_t nextUnit = 0, totalUnits = 0;  // cursor / size of item `alloc`
-  bool exhausted = false;                 // the launch has no more items
-  uint32_t slabFree = (1u << kSlabsPerWave) - 1u;  // own slabs that are free
-  uint32_t slabPend = 0;                           // own slabs handed over, not known to be folded yet
-};
-// launch diagnostics (dmt_sched_diag; the host checks folds == items): one atomic per EVENT, from lane 0 -- an event is at
-// most once per work item (~10^3 path samples), and counters kept in the wave's registers cost spills in the hot loop
-enum { SD_FOLDS = 0, SD_HANDED = 1, SD_CHAINED = 2, SD_STALLS = 3, SD_EXITS = 4, SD_MAXSTALL = 5,
-       SD_GGX_PARKED = 8, SD_GGX_RESUMED = 9, SD_GGX_PASSES = 10, SD_GGX_FULL = 11 };
-DMT_DEV void sched_count(unsigned long long* D, int lane, int what, unsigned long long n = 1ull) {
-  if (lane == 0) atomicAdd(&D[what], n);
-}
-// per-lane bookkeeping
-struct LaneSched {
-  bool prepared = false;  // a unit is waiting in s_prep
-  bool prepSlot = false;  // ... of the item in this slot
-};
-
-// pixel origin and row count of a tile item (an owned tile is scheduled as 1 << subShift bands of 8 >> subShift
-// rows: more, smaller items when this GPU has fewer tiles than resident waves; lanes beyond the band are "outside").
-// Adaptive launches (tileList set; wave-uniform) take the tile from the list and keep only the lanes whose pixel bit is
-// set in the tile's mask word: pixel (x, y) of the tile is bit y * 8 + x, so lane i of band b is bit b * rows * 8 + i.
-// The two pointers are read from the kernel arguments here, not kept in TileArgs (SGPRs held across the hot loop).
-struct ItemGeom {
-  int px0, py0;
-  uint32_t rows;
-  unsigned long long live;  // bit i: lane i's pixel is traced (all ones without a tile list)
-};
-DMT_DEV ItemGeom item_geom(TileArgs const& T, uint32_t item) {
-  uint32_t const band = item & ((1u << T.subShift) - 1u);
-  uint32_t const rows = 8u >> T.subShift;
-  uint32_t j;
-  unsigned long long live = ~0ull;
-  KArgs const k = kargs(kargs_base());
-  if (uint32_t const* const list = k->tileList) {
-    j = list[item >> T.subShift];
-    live = kargs(k)->tileMask[j] >> (band * rows * 8u);
-  } else {
-    j = uint32_t(T.rank) + (item >> T.subShift) * uint32_t(T.world);
-  }
-  return {(T.tx0 + int(j % uint32_t(T.rtx))) * 8, (T.ty0 + int(j / uint32_t(T.rtx))) * 8 + int(band * rows), rows, live};
-}
-DMT_DEV bool item_lane_inside(TileArgs const& T, ItemGeom const& g, int lane) {
-  int const px = g.px0 + (lane & 7), py = g.py0 + (lane >> 3);
-  // (g.live is wave-uniform and bit i belongs to lane i: it IS the lane mask -- no per-lane shift, no VGPRs)
-  return uint32_t(lane >> 3) < g.rows && px >= T.x0 && px < T.x1 && py >= T.y0 && py < T.y1 &&
-         __builtin_amdgcn_inverse_ballot_w64(g.live);
-}
-DMT_DEV uint32_t chunk_samples(TileArgs const& T, uint32_t chunk) {
-  uint32_t const s0 = chunk * T.chunkSpp;
-  return s0 + T.chunkSpp < T.spp ? T.chunkSpp : T.spp - s0;
-}
-
-// index of this wave in the launch, as a value the compiler knows to be wave-uniform (gtid >> 6 lives in a VGPR; slab
-// bookkeeping derived from it would be treated as divergent: VALU bit scans, exec-masked branches around item_fetch)
-DMT_DEV uint32_t wave_index(uint32_t) { return blockIdx.x * (kLdsThreads / 64) + uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6))); }
-
-// which of the wave's handed-over slabs have been folded meanwhile?
-DMT_DEV void slab_refresh(TileArgs const& T, uint32_t gtid, int lane, WaveSched& W) {
-  if (W.slabPend == 0u) return;
-  bool const mine = lane < kSlabsPerWave && ((W.slabPend >> lane) & 1u) != 0u;
-  uint32_t busy = 1u;
-  if (mine) busy = __hip_atomic_load(&T.slabBusy[wave_index(gtid) * kSlabsPerWave + uint32_t(lane)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  uint32_t const freed = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(__ballot(mine && busy == 0u)))));
-  W.slabFree |= freed, W.slabPend &= ~freed;
-}
-
-// fetch the next work item into slot seq & 1; false = the launch has no more items.  The caller has checked that the
-// wave has a free slab (W.slabFree != 0; slab_refresh runs in sched_retire only, to keep it out of the hot loop).
-DMT_DEV bool item_fetch(KArgs Pk, uint32_t gtid, int lane, uint32_t seq, WaveSched& W, uint32_t& units) {
-  TileArgs const T = load_tile_args(Pk);
-  uint32_t work = 0;
-  if (lane == 0) work = atomicAdd(T.counter, 1u);
-  work = uint32_t(__builtin_amdgcn_readfirstlane(int(work)));
-  if (work >= T.numItems * T.numChunks) return false;
-  uint32_t const slabK = uint32_t(__builtin_ctz(W.slabFree));
-  W.slabFree &= ~(1u << slabK);
-  uint32_t const chunk = work / T.numItems;
-  uint32_t const item = work - chunk * T.numItems;
-  ItemGeom const g = item_geom(T, item);
-  int const px = g.px0 + (lane & 7), py = g.py0 + (lane >> 3);
-  bool const inside = item_lane_inside(T, g, lane);
-  uint32_t const s0 = T.sampleOffset + chunk * T.chunkSpp;
-  uint32_t const n = chunk_samples(T, chunk);
-  uint32_t const slot = seq & 1u;
-  unsigned long long const insideMask = __ballot(inside);
-  uint32_t const nInside = uint32_t(__popcll(insideMask));
-  uint32_t* const d = s_desc[threadIdx.x >> 6][slot];  // wave-uniform values: every lane stores the same words
-  d[0] = chunk, d[1] = item, d[2] = uint32_t(g.px0), d[3] = uint32_t(g.py0), d[4] = s0, d[6] = nInside;
-  d[7] = wave_index(gtid) * kSlabsPerWave + slabK;
-  d[5] = d[7] * T.chunkSpp * 192u;  // first float of the slab (< 2^32: at most 16 384 slabs of kMaxChunkSpp * 192 floats)
-  uint32_t const wbase = slot * kLdsThreads + (threadIdx.x & ~63u);
-  s_pixbase[wbase + lane] = inside ? halton_pixel_base(load_cold_args(Pk).sp, px, py) : -1;
-  if (inside) s_pixmap[wbase + uint32_t(__popcll(insideMask & ((1ull << lane) - 1ull)))] = uint32_t(lane);
-  units = nInside * n;
-  return true;
-}
-
-// Staged radiance goes to the wave's slab with PLAIN stores (they merge in this XCD's L2; the owner folds its own slab
-// from there).  Only when a slab is handed over is it made visible to the other XCDs (slab_publish).
-DMT_DEV void stage_sample(KArgs Pk, uint32_t sidx, f3 L) {
-  uint32_t const first = s_desc[threadIdx.x >> 6][sidx >> 31][5];
-  float* const p = kargs(Pk)->stage + (first + (sidx & ~kSlotBit) * 3u);
-  p[0] = L.x, p[1] = L.y, p[2] = L.z;
-}
-// Hand-over: the folder may run on another XCD, whose L2 is a different one, and this XCD's L2 holds the slab as dirty
-// lines.  Writing back the whole L2 (release fence = buffer_wbl2) would cost far more than the slab is worth, so the
-// owner re-stores its n x 64 x 3 floats with agent-scope stores (global_store ... sc1: written through to memory), lane i
-// the samples of pixel i; the folder reads them with agent-scope loads.  48 loads + 48 stores per lane for 16 samples,
-// paid only by chunks that finish before their predecessor (none on a frame with more tiles than resident waves).
-DMT_DEV void slab_publish(TileArgs const& T, int lane, uint32_t slab, uint32_t n) {
-  float* p = T.stage + size_t(slab) * size_t(T.chunkSpp) * 192u + uint32_t(lane) * 3u;
-#pragma unroll 4
-  for (uint32_t k = 0; k < n; ++k, p += 192) {
-    float const x = p[0], y = p[1], z = p[2];
-    uint32_t* const q = reinterpret_cast<uint32_t*>(p);
-    __hip_atomic_store(q + 0, __float_as_uint(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(q + 1, __float_as_uint(y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(q + 2, __float_as_uint(z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// prepare unit u of item `seq` in this lane's s_prep
-template <bool MOTION = false>
-DMT_DEV void prepare_unit(KArgs Pk, uint32_t seq, uint32_t u, LaneSched& Ls) {
-  uint32_t const slot = seq & 1u;
-  uint32_t const* const d = s_desc[threadIdx.x >> 6][slot];
-  uint32_t const nInside = d[6];
-  uint32_t k, j;
-  if (nInside == 64u) k = u >> 6, j = u & 63u;
-  else k = u / nInside, j = u - k * nInside;
-  uint32_t const wbase = slot * kLdsThreads + (threadIdx.x & ~63u);
-  uint32_t const pixel = s_pixmap[wbase + j];
-  prepare_sample<MOTION>(Pk, int(d[2]) + int(pixel & 7u), int(d[3]) + int(pixel >> 3), s_pixbase[wbase + pixel], d[4] + k);
-  s_prep[14 * kLdsThreads + threadIdx.x] = __uint_as_float((slot << 31) | (k * 64u + pixel));
-  Ls.prepared = true, Ls.prepSlot = slot != 0u;
-}
-
-// Film words that another wave of this launch may read or have written (the tile's previous / next chunk) are
-// moved with agent-scope relaxed atomics (global_load/store ... sc1: coherent across the XCDs' L2s) and
-// ordered against the hand-over word by s_waitcnt.  The obvious alternative, plain accesses between
-// acquire/release FENCES, costs a buffer_inv / buffer_wbl2 of the XCD's whole L2 per item.
-DMT_DEV float4 film_load(float4 const* p) {
-  unsigned long long const* const q = reinterpret_cast<unsigned long long const*>(p);
-  unsigned long long const a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  unsigned long long const b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return make_float4(__uint_as_float(uint32_t(a)), __uint_as_float(uint32_t(a >> 32)), __uint_as_float(uint32_t(b)),
-                     __uint_as_float(uint32_t(b >> 32)));
-}
-DMT_DEV void film_store(float4* p, float4 v) {
-  unsigned long long* const q = reinterpret_cast<unsigned long long*>(p);
-  __hip_atomic_store(q, (unsigned long long)__float_as_uint(v.x) | ((unsigned long long)__float_as_uint(v.y) << 32),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(q + 1, (unsigned long long)__float_as_uint(v.z) | ((unsigned long long)__float_as_uint(v.w) << 32),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One sample into a pixel's running statistics: SMEMLayout::updateSample, T/megakernel/megakernel.cuh:59-79.  ONE function
-// for every fold in this library (megakernel items, wavefront passes), so that every path to the film rounds alike.
-DMT_DEV void welford_update(f3& mean, f3& M2, float& N, f3 L) {
-  N = N + 1.0f;
-  f3 const delta = L - mean;
-  mean = mean + delta / N;
-  f3 const delta2 = L - mean;
-  M2 = M2 + delta * delta2;
-}
-
-// Put chunk `chunk` of tile item `item` (staged in `slab`) into the film -- the caller knows that chunk - 1 is there --
-// and then every directly following chunk that has already been handed over.  Lane i folds pixel i of the tile.
-DMT_DEV void fold_chain(TileArgs const& T, unsigned long long* D, uint32_t gtid, int lane, uint32_t item, uint32_t chunk, uint32_t slab) {
-  ItemGeom const g = item_geom(T, item);
-  bool const inside = item_lane_inside(T, g, lane);
-  size_t const pidx = size_t(g.px0 + (lane & 7)) + size_t(g.py0 + (lane >> 3)) * size_t(T.width);
-  f3 mean = mk3(0, 0, 0), M2 = mk3(0, 0, 0);
-  float N = 0.f;
-  uint32_t folded = 0;
-  if (inside) {
-    float4 const m = film_load(T.mean + pidx);  // SMEMLayout::startSample, megakernel.cuh:45-57
-    float4 const v = film_load(T.m2 + pidx);
-    mean = mk3(m.x, m.y, m.z), M2 = mk3(v.x, v.y, v.z), N = v.w;
-  }
-  for (;;) {
-    uint32_t const n = chunk_samples(T, chunk);
-    bool const own = slab / kSlabsPerWave == wave_index(gtid);  // wave-uniform
-    float const* p = T.stage + size_t(slab) * size_t(T.chunkSpp) * 192u + uint32_t(lane) * 3u;
-    if (inside) {
-      if (own) {
-#pragma unroll 4
-        for (uint32_t k = 0; k < n; ++k, p += 192) welford_update(mean, M2, N, mk3(p[0], p[1], p[2]));
-      } else {  // another wave's slab: read it where it was written through to
-#pragma unroll 2
-        for (uint32_t k = 0; k < n; ++k, p += 192) {
-          uint32_t const* const q = reinterpret_cast<uint32_t const*>(p);
-          uint32_t const x = __hip_atomic_load(q + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          uint32_t const y = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          uint32_t const z = __hip_atomic_load(q + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          welford_update(mean, M2, N, mk3(__uint_as_float(x), __uint_as_float(y), __uint_as_float(z)));
-        }
-      }
-      film_store(T.mean + pidx, make_float4(mean.x, mean.y, mean.z, 0.f));  // endSample, megakernel.cuh:81-85
-      film_store(T.m2 + pidx, make_float4(M2.x, M2.y, M2.z, N));
-    }
-    ++folded;
-    if (++chunk == T.numChunks) {  // (a foreign slab of the last chunk still has to be released)
-      if (!own) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_store(&T.slabBusy[slab], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      break;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // slab read, film stores written through -> release the slab, publish
-    uint32_t next = 0;
-    if (lane == 0) {
-      if (!own) __hip_atomic_store(&T.slabBusy[slab], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      next = __hip_atomic_exchange(&T.link[size_t(chunk) * T.numItems + item], kFoldReady, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    next = uint32_t(__builtin_amdgcn_readfirstlane(int(next)));
-    if (next == 0u) break;  // chunk not finished yet: its finisher will find kFoldReady and fold it
-    slab = next - 1u;       // finished and handed over: this wave folds it (the running statistics are in registers)
-  }
-  sched_count(D, lane, SD_FOLDS, folded);
-  if (folded > 1u) sched_count(D, lane, SD_CHAINED, folded - 1u);
-}
-
-// Item `seq` of this wave is completely staged: fold it, or hand it over to the folder of the tile's previous chunk.
-DMT_DEV void item_complete(KArgs Pk, uint32_t gtid, int lane, uint32_t seq, WaveSched& W) {
-  TileArgs const T = load_tile_args(Pk);
-  uint32_t const* const d = s_desc[threadIdx.x >> 6][seq & 1u];
-  uint32_t const chunk = uint32_t(__builtin_amdgcn_readfirstlane(int(d[0])));
-  uint32_t const item = uint32_t(__builtin_amdgcn_readfirstlane(int(d[1])));
-  uint32_t const slab = uint32_t(__builtin_amdgcn_readfirstlane(int(d[7])));
-  uint32_t const slabBit = 1u << (slab - wave_index(gtid) * kSlabsPerWave);
-  if (chunk > 0u) {
-    // Is the previous chunk in the film already (the usual case when the frame has more tiles than resident waves)?
-    // Then this wave folds, and nothing has to be published.  A stale "no" only costs an unnecessary publish.
-    uint32_t seen = 0;
-    if (lane == 0) seen = __hip_atomic_load(&T.link[size_t(chunk) * T.numItems + item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    seen = uint32_t(__builtin_amdgcn_readfirstlane(int(seen)));
-    if (seen != kFoldReady) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own staging stores have landed (in this XCD's L2)
-      slab_publish(T, lane, slab, chunk_samples(T, chunk));
-      if (lane == 0) __hip_atomic_store(&T.slabBusy[slab], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the slab is in memory and marked busy -> offer it
-      uint32_t old = 0;
-      if (lane == 0) old = __hip_atomic_exchange(&T.link[size_t(chunk) * T.numItems + item], slab + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      old = uint32_t(__builtin_amdgcn_readfirstlane(int(old)));
-      if (old != kFoldReady) {  // the previous chunk is not in the film yet: its folder takes this slab
-        W.slabPend |= slabBit;
-        sched_count(kargs(Pk)->schedDiag, lane, SD_HANDED);
-        return;
-      }
-    }  // (kFoldReady seen or received: nobody else touches this word any more)
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own staging stores have landed
-  fold_chain(T, kargs(Pk)->schedDiag, gtid, lane, item, chunk, slab);
-  W.slabFree |= slabBit;
-}
-
-// Hand the next units of the wave's items to the lanes that ask for one (`want`) and prepare them.  This is the ONE place
-// where work items are fetched (item_fetch is large, and the kernel already fills most of the instruction cache): a wave
-// starts with no item, and a wave whose last live item was retired comes here because all its lanes are starving.
-template <bool MOTION = false>
-DMT_DEV void sched_draw(KArgs Pk, uint32_t gtid, int lane, WaveSched& W, LaneSched& Ls, bool want) {
-  if (__builtin_expect(W.nextUnit == W.totalUnits, 0)) {  // the item units are drawn from is used up (or there is none yet): fetch the next if there is room
-    if (!W.exhausted && W.fetched - W.cur < 2u && W.slabFree != 0u) {
-      uint32_t units = 0;
-      if (item_fetch(Pk, gtid, lane, W.fetched, W, units)) W.alloc = W.fetched, ++W.fetched, W.nextUnit = 0, W.totalUnits = units;
-      else W.exhausted = true;
-    }
-  }
-  uint32_t const avail = W.totalUnits - W.nextUnit;
-  if (avail == 0u) return;
-  unsigned long long const m = __ballot(want);
-  uint32_t const rank = uint32_t(__popcll(m & ((1ull << lane) - 1ull)));
-  uint32_t const cnt = uint32_t(__popcll(m));
-  if (want && rank < avail) prepare_unit<MOTION>(Pk, W.alloc, W.nextUnit + rank, Ls);
-  W.nextUnit += cnt < avail ? cnt : avail;
-}
-
-// item cur: all units drawn and none of them still in a lane -> complete it; false = the wave leaves the launch
-DMT_DEV bool sched_retire(KArgs Pk, uint32_t gtid, int lane, WaveSched& W) {
-  item_complete(Pk, gtid, lane, W.cur, W);
-  ++W.cur;
-  if (W.slabPend != 0u) slab_refresh(load_tile_args(Pk), gtid, lane, W);  // once per completed item: which handed-over slabs are back?
-  if (W.cur == W.fetched) {  // no live item: the next sched_draw fetches one
-    if (W.exhausted) return false;
-    if (W.slabFree == 0u) {
-      // Every slab of this wave is handed over and waits for a folder.  The wave holds nothing anybody needs; in a
-      // healthy launch a slab comes back within one item's tracing time.  Poll for a bounded WALL CLOCK time, then leave:
-      // the other waves fetch the remaining items, and a free wave slot lets a switched-out wave run again.
-      TileArgs const T = load_tile_args(Pk);
-      unsigned long long* const D = kargs(Pk)->schedDiag;
-      sched_count(D, lane, SD_STALLS);
-      unsigned long long const t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz
-      unsigned long long waited = 0;
-      do {
-        __builtin_amdgcn_s_sleep(64);
-        slab_refresh(T, gtid, lane, W);
-        waited = __builtin_amdgcn_s_memrealtime() - t0;
-      } while (W.slabFree == 0u && waited <= (unsigned long long)(DMT_SLAB_WAIT_MS) * 100000ull);
-      if (lane == 0) atomicMax(&D[SD_MAXSTALL], waited);
-      if (W.slabFree == 0u) {
-        sched_count(D, lane, SD_EXITS);
-        return false;
-      }
-    }
-  }
-  return true;
-}
-// does this lane still hold a sample of the item in slot `curSlot`?
-DMT_DEV bool lane_holds(PathState const& st, LaneSched const& Ls, bool curSlot) {
-  return (st.active && ((st.sidx >> 31) != 0u) == curSlot) || (Ls.prepared && Ls.prepSlot == curSlot) ||
-         (st.finPending && ((get_finIdx() >> 31) != 0u) == curSlot);
-}
+#include "launch_device.hpp"
 
 // ---- GGX batching (k_megakernel; dmt_set_ggx_batch) ---------------------------------------------------------------
 // The GGX branches of bsdf_prepare, eval_bsdf and sample_bsdf run for the whole wave whenever one lane of a pass has hit
@@ -2073,48 +1675,9 @@ __global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
 // =============================================================================================
 // host side of the C ABI
 // =============================================================================================
-// ---- sampler table: the host's plan ----------------------------------------------------------------
-constexpr uint32_t kSamTabEntryBytes = 40;                  // 8 dimension values (two float4) + the film jitter (one float2)
-constexpr uint32_t kSamTabLensEntryBytes = 48;              // launches with a lens: + the lens values (one float2)
-constexpr uint64_t kSamTabDefaultBudget = 512ull << 20;
-// Automatic mode uses the table when the launch's owned pixels are at least this many periods: the fill costs one
-// period's worth of sampler arithmetic per sample, the compute path `ratio` periods' worth, so the table saves
-// (1 - 1/ratio) of it and pays three loads per prepared sample.  Measured on Cornell frames of 2 048 spp, table forced
-// against off: ratio 1 (128 x 128) +10.7 %, 1.56 +3.1 %, 2.25 -2.7 %, 4 (256 x 256) -9.5 %, 9 -15.7 %, 16 -16.7 %
-// ("Sampler table").  The break-even is near 2; 4 keeps a margin for launches that own only part of their
-// tiles' pixels (regions off the tile grid) and for every committed workload it is a gain.
-constexpr uint64_t kSamTabMinRatio = 4;
-struct SamplerTablePlan {
-  bool use = false;
-  uint32_t pw = 0, ph = 0;      // the frame's Halton period in pixels: min(width, 128) x min(height, 128)
-  uint32_t slices = 0;          // fill + megakernel pairs of the call
-  uint32_t sliceChunks = 0;     // sample chunks per slice (the last slice has what is left)
-};
-// Pure host arithmetic (dmt_sampler_table_plan exposes it).  chunkSpp: samples per work item of the launch, <= spp.
-static SamplerTablePlan samplerTablePlan(int width, int height, uint64_t ownedPixels, uint32_t spp, uint32_t chunkSpp, uint64_t budget, int mode,
-                                         uint32_t entryBytes = kSamTabEntryBytes) {
-  SamplerTablePlan p;
-  if (width <= 0 || height <= 0) return p;
-  p.pw = uint32_t(width < 128 ? width : 128), p.ph = uint32_t(height < 128 ? height : 128);
-  if (mode == DMT_SAMPLER_TABLE_OFF || spp == 0 || chunkSpp == 0) return p;
-  if (chunkSpp > spp) chunkSpp = spp;
-  uint64_t const period = uint64_t(p.pw) * p.ph;
-  if (mode != DMT_SAMPLER_TABLE_FORCE && ownedPixels < kSamTabMinRatio * period) return p;
-  uint64_t const chunkEntries = uint64_t(chunkSpp) * period;
-  uint64_t maxChunks = budget / (chunkEntries * entryBytes);
-  uint64_t const maxChunksByIndex = 0x7FFFFFFFull / chunkEntries;  // entry indices are 32-bit on the device
-  if (maxChunks > maxChunksByIndex) maxChunks = maxChunksByIndex;
-  if (maxChunks == 0) return p;  // not even one chunk fits: the launch computes its samples
-  uint64_t const numChunks = (uint64_t(spp) + chunkSpp - 1) / chunkSpp;
-  uint64_t const k = (numChunks + maxChunks - 1) / maxChunks;
-  p.sliceChunks = uint32_t((numChunks + k - 1) / k);  // equal chunk counts, <= maxChunks
-  p.slices = uint32_t((numChunks + p.sliceChunks - 1) / p.sliceChunks);
-  p.use = true;
-  return p;
-}
-
 #include "accel_state.hpp"
 #include "surface_state.hpp"
+#include "launch_state.hpp"
 
 struct dmt_ctx {
   int device = 0;
@@ -2144,18 +1707,10 @@ struct dmt_ctx {
   bool lightTreeValid = false;
   bool lightTreeTooDeep = false;   // the last build exceeded the walk's depth guard: the uniform pick is used instead (dmt_last_error says so)
   bool lightsTreeable = false;     // every record of the light list is a point or spot light
-  std::vector<std::pair<void const*, int>> occupancy;  // megakernel variant -> resident 256-thread blocks per CU
   // the surface-attribute layer: textures and UVs, the texture filter, vertex normals, opacity records, emissive triangles
   // (surface_state.hpp, surface_host.hpp)
   SurfaceState surf;
   bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_blend kernels carry that code
-  // wavefront form of the BVH path (wavefront.hpp)
-  int bvhStrategy = 0;             // 0 = automatic (by launch size), 1 = megakernel, 2 = wavefront
-  size_t wfTargetPaths = size_t(1) << 22;  // path slots per pass
-  DevBuf<float> d_wfState;
-  DevBuf<uint32_t> d_wfQueue;   // two queues
-  DevBuf<uint32_t> d_wfCounts;  // counts + cursors
-  int wfBlocksTrace = 0, wfBlocksShade = 0;
   DevBuf<float> d_env;     // A18: one allocation holding the five tables and the image
   EnvView env{};           // env.w == 0: no env map
   bool haveTris = false, haveBsdfs = false, haveLights = false, haveCamera = false;
@@ -2169,40 +1724,13 @@ struct dmt_ctx {
   float4* d_mean = nullptr;
   float4* d_m2 = nullptr;
   int filmW = 0, filmH = 0;
-  DevBuf<uint32_t> d_counter;   // work counter
-  DevBuf<uint32_t> d_sched;     // [waves * kSlabsPerWave] slab-busy marks, then [numChunks][numItems] hand-over words; zeroed per launch
-  DevBuf<unsigned long long> d_schedDiag;  // kSchedDiagWords counters over all launches (dmt_sched_diag)
-  unsigned long long expectedFolds = 0;    // work items launched so far: what d_schedDiag[0] must read once the stream has drained
-  DevBuf<unsigned long long> d_stats;      // 16 device counters of dmt_render_stats / dmt_render_profile
-  DevBuf<float> d_stage;        // staging slabs of finished samples, [wave][kSlabsPerWave][chunkSpp][64] float3
-  // GGX batching (ggx_park / ggx_resume): the queues of parked hits, [wave][kGgxFields][kGgxQueueCap], grown on demand
-  DevBuf<float> d_ggxQueue;
-  uint32_t ggxBatchT = DMT_GGX_BATCH_T;  // dmt_set_ggx_batch, DMT_GGX_BATCH at context creation; 0 = off
-  unsigned long long ggxLostReported = 0;  // parked - taken back that checkErrorFlag has reported already (0 in a healthy context)
-  // sampler table of a launch (samplerTablePlan, k_sampler_table): refilled by every dmt_render call that uses it, grown on demand
-  DevBuf<float4> d_samTab;
-  DevBuf<float2> d_samTabJit;
-  DevBuf<float2> d_samTabLens;                   // launches with a lens only
-  int samTabMode = DMT_SAMPLER_TABLE_AUTO;       // dmt_set_sampler_table, DMT_SAMPLER_TABLE at context creation
-  uint64_t samTabBudget = kSamTabDefaultBudget;  // bytes of table memory a launch may use; larger tables are filled in sample slices
-  // dmt_render_adaptive: per tile of the film's tile grid a mask word, the list of tiles with active pixels, two counters
-  DevBuf<unsigned long long> d_adMask;
-  DevBuf<uint32_t> d_adList;
-  DevBuf<uint32_t> d_adCount;
+  // the launch layer: the scheduler's buffers and fold accounting, GGX batching, the sampler table, adaptive rounds, the
+  // wavefront form, timing, and the settings that shape a launch (launch_state.hpp, launch_host.hpp)
+  LaunchState launch;
   // the image-space layer: feature planes, the filter's scratch, the temporal history (denoise.hpp, denoise_host.hpp)
   DenoiseState dn;
-  uint32_t chunkSpp = 0;          // samples per work item, 0 = automatic
-  int subShift = -1;               // row bands per tile (log2); -1 = choose per launch
   int maxDepth = 32;
   int accel = DMT_ACCEL_BRUTE_FORCE;
-  int rank = 0, world = 1;
-  // launch geometry
-  int cuCount = 0;
-  // timing
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  size_t eventsUsed = 0;
-  double accumMs = 0.0;
-  uint64_t accumLaunches = 0;
 };
 
 namespace {
@@ -2479,7 +2007,7 @@ int checkFeatures(dmt_ctx* ctx, uint32_t F) {
     if (F & kFeatBlend) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with blend materials are not supported");
     if (F & kFeatArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with emissive triangles are not supported");
     if (F & (kFeatLightTree | kFeatLightTreeRef)) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with a light tree are not supported");
-    if ((F & kFeatBvh) && ctx->bvhStrategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with the wavefront BVH strategy are not supported");
+    if ((F & kFeatBvh) && ctx->launch.wf.strategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: vertex normals (dmt_upload_vertex_normals) together with the wavefront BVH strategy are not supported");
   }
   if (F & kFeatMotion) {  // motion blur has the plain and env-map megakernel rows
     if (F & kFeatStats) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: motion blur (dmt_set_motion) has no counting kernels");
@@ -2487,7 +2015,7 @@ int checkFeatures(dmt_ctx* ctx, uint32_t F) {
     if (F & (kFeatTex | kFeatBlend)) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with image textures or blend materials is not supported");
     if (F & kFeatArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with emissive triangles is not supported");
     if (F & (kFeatLightTree | kFeatLightTreeRef)) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with a light tree is not supported");
-    if ((F & kFeatBvh) && ctx->bvhStrategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with the wavefront BVH strategy is not supported");
+    if ((F & kFeatBvh) && ctx->launch.wf.strategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with the wavefront BVH strategy is not supported");
   }
   if ((F & kFeatStats) && (F & (kFeatTex | kFeatBlend | kFeatArea | kFeatLightTree | kFeatLightTreeRef)))
     return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: the counting kernels exist for the plain and env-map BVH kernels only; "
@@ -2550,37 +2078,6 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   return P;
 }
 
-// kernel tables: {mask, kernel} per row of the device-side lists; a mask without a row has no kernel (nullptr)
-template <class Fn>
-struct KernelRow { uint32_t mask; Fn fn; };
-template <class Fn, size_t N>
-Fn kernelOf(KernelRow<Fn> const (&rows)[N], uint32_t mask) {
-  for (KernelRow<Fn> const& r : rows) if (r.mask == mask) return r.fn;
-  return nullptr;
-}
-int noKernel(dmt_ctx* ctx, char const* what, uint32_t mask) {
-  ctx->err = std::string(what) + ": no kernel is compiled for this combination of scene features (mask " + std::to_string(mask) + ")";
-  return DMT_ERR_STATE;
-}
-typedef void (*MegakernelFn)(RenderParams);
-typedef void (*WfKernelFn)(RenderParams, WfParams);
-#define DMT_MEGAKERNEL_ROW(suffix, mask, waves, body) {mask, k_megakernel##suffix},
-#define DMT_WF_SHADE_ROW(suffix, mask, waves) {mask, k_wf_shade##suffix},
-KernelRow<MegakernelFn> const kMegakernels[] = {DMT_MEGAKERNELS(DMT_MEGAKERNEL_ROW) DMT_STATS_MEGAKERNELS(DMT_MEGAKERNEL_ROW)};
-KernelRow<WfKernelFn> const kWfShadeKernels[] = {DMT_WF_SHADE_KERNELS(DMT_WF_SHADE_ROW)};
-
-MegakernelFn megakernelOf(uint32_t mask) { return kernelOf(kMegakernels, mask); }
-// resident 256-thread blocks per CU of a kernel (cached per context)
-int blocksPerCuOf(dmt_ctx* c, MegakernelFn kernel) {
-  void const* const fn = reinterpret_cast<void const*>(kernel);
-  for (auto const& e : c->occupancy)
-    if (e.first == fn) return e.second;
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, 0) != hipSuccess || n <= 0) n = 1;
-  c->occupancy.emplace_back(fn, n);
-  return n;
-}
-
 // octahedral decode on the host (CC/private/encoding.cu:39-60), as pt_device.hpp's dir_from_octa
 void octa_host(uint32_t octa, float out[3]) {
   float const mx = 65535.f;
@@ -2640,32 +2137,6 @@ int ensureLightTree(dmt_ctx* ctx) {
   return DMT_OK;
 }
 
-// After the stream has drained: every work item of every past launch must have been folded into the film exactly once
-// (item_complete / fold_chain count their folds).  Anything else means the hand-over protocol lost or duplicated a sample
-// chunk and the film is not the ordered fold the contract promises.
-int checkErrorFlag(dmt_ctx* ctx) {
-  unsigned long long d[kSchedDiagWords] = {};
-  HIP_TRY(ctx, hipMemcpy(d, ctx->d_schedDiag.get(), sizeof(d), hipMemcpyDeviceToHost));
-  unsigned long long const folds = d[SD_FOLDS];
-  // a wave left a launch with parked hits in its queue: their samples are missing.  Reported once per difference; the
-  // device counters stay as they are for dmt_ggx_batch_diag
-  if (d[SD_GGX_PARKED] - d[SD_GGX_RESUMED] != ctx->ggxLostReported) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "GGX batching: %llu hits were parked, %llu were taken back: the film is invalid", d[SD_GGX_PARKED],
-             d[SD_GGX_RESUMED]);
-    ctx->ggxLostReported = d[SD_GGX_PARKED] - d[SD_GGX_RESUMED];
-    return fail(ctx, DMT_ERR_HIP, msg);
-  }
-  if (folds != ctx->expectedFolds) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "in-launch ordering: %llu sample chunks were folded into the film, %llu were launched: the film is invalid",
-             folds, ctx->expectedFolds);
-    ctx->expectedFolds = folds;  // report once
-    return fail(ctx, DMT_ERR_HIP, msg);
-  }
-  return DMT_OK;
-}
-
 int finishTest(dmt_ctx* ctx) {
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2673,6 +2144,10 @@ int finishTest(dmt_ctx* ctx) {
 }
 
 }  // namespace
+
+// the launch layer's helpers and entry points: the kernel tables, the plan and the enqueue of a dmt_render* call, the fold
+// check (checkErrorFlag) that denoise_host.hpp and probes.hpp use, timing
+#include "launch_host.hpp"
 
 // the image-space layer's entry points and the rules of its state; it uses the helpers above
 #include "denoise_host.hpp"
@@ -2698,10 +2173,7 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->ownStream, hipStreamNonBlocking);
   hipDeviceProp_t prop{};
   if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device_ordinal);
-  if (e == hipSuccess) e = ctx->d_counter.reserve(2);
-  if (e == hipSuccess) e = hipMemset(ctx->d_counter.get(), 0, 2 * sizeof(uint32_t));
-  if (e == hipSuccess) e = ctx->d_schedDiag.reserve(kSchedDiagWords);
-  if (e == hipSuccess) e = hipMemset(ctx->d_schedDiag.get(), 0, kSchedDiagWords * sizeof(unsigned long long));
+  if (e == hipSuccess) e = ctx->launch.allocate();
   int bpcBvh = 0;
   if (e == hipSuccess)
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpcBvh, reinterpret_cast<void const*>(k_megakernel_bvh), 256, 0);
@@ -2711,35 +2183,16 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
     return DMT_ERR_HIP;
   }
   ctx->stream = ctx->ownStream;
-  ctx->cuCount = prop.multiProcessorCount;
+  ctx->launch.cuCount = prop.multiProcessorCount;
   ctx->ac.blocksPerCUBvh = bpcBvh > 0 ? bpcBvh : 1;
-  if (char const* e3 = std::getenv("DMT_BVH_STRATEGY")) {  // experiments: 0 auto, 1 megakernel, 2 wavefront
-    int const v = std::atoi(e3);
-    ctx->bvhStrategy = v < 0 || v > 2 ? 0 : v;
-  }
+  ctx->launch.fromEnv();
   if (char const* e5 = std::getenv("DMT_BVH_SHADE_THRESHOLD")) {  // tuning runs (shadeThresholdFor)
     int const v = std::atoi(e5);
     ctx->ac.shadeThresholdEnv = v < 1 ? 0 : (v > 64 ? 64 : v);
   }
-  if (char const* e4 = std::getenv("DMT_WF_PATHS")) {
-    long long const v = std::atoll(e4);
-    if (v >= 4096) ctx->wfTargetPaths = size_t(v);
-  }
   if (char const* e6 = std::getenv("DMT_BRUTE_CULL")) {  // A/B runs and tests
     int const v = std::atoi(e6);
     ctx->bruteCull = v == 0 ? 0 : v == 1 ? 1 : 2;
-  }
-  if (char const* e7 = std::getenv("DMT_SAMPLER_TABLE")) {  // A/B runs and tests: 0 off, 1 automatic (the default), 2 force
-    int const v = std::atoi(e7);
-    ctx->samTabMode = v == 0 ? DMT_SAMPLER_TABLE_OFF : v == 2 ? DMT_SAMPLER_TABLE_FORCE : DMT_SAMPLER_TABLE_AUTO;
-  }
-  if (char const* e8 = std::getenv("DMT_GGX_BATCH")) {  // A/B runs and tests: 0 off, T = batch size (at most the queue's capacity)
-    int const v = std::atoi(e8);
-    ctx->ggxBatchT = v <= 0 ? 0u : std::min<uint32_t>(uint32_t(v), kGgxQueueCap);
-  }
-  if (char const* e2 = std::getenv("DMT_SUB_SHIFT")) {  // scheduling experiments only: results do not depend on it
-    int const v = std::atoi(e2);
-    ctx->subShift = v < 0 ? -1 : (v > 2 ? 2 : v);
   }
   *out = ctx.release();
   return DMT_OK;
@@ -2749,7 +2202,7 @@ int dmt_ctx_destroy(dmt_ctx* ctx) {
   if (!ctx) return DMT_ERR_INVALID;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  for (auto& ev : ctx->events) {
+  for (auto& ev : ctx->launch.timing.events) {
     (void)hipEventDestroy(ev.first);
     (void)hipEventDestroy(ev.second);
   }
@@ -2929,21 +2382,6 @@ int dmt_light_tree_ref_select(const void* lights32, uint32_t count, int n, const
   return DMT_OK;
 }
 
-int dmt_set_bvh_strategy(dmt_ctx* ctx, int strategy, uint64_t paths_per_pass) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (strategy < 0 || strategy > 2) return fail(ctx, DMT_ERR_INVALID, "dmt_set_bvh_strategy: 0 = automatic, 1 = megakernel, 2 = wavefront");
-  ctx->bvhStrategy = strategy;
-  if (paths_per_pass) ctx->wfTargetPaths = size_t(paths_per_pass);
-  return DMT_OK;
-}
-
-int dmt_set_partition(dmt_ctx* ctx, int rank, int world) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (world < 1 || rank < 0 || rank >= world) return fail(ctx, DMT_ERR_INVALID, "dmt_set_partition: bad rank/world");
-  ctx->rank = rank, ctx->world = world;
-  return DMT_OK;
-}
-
 int dmt_set_stream(dmt_ctx* ctx, void* hip_stream) {
   if (!ctx) return DMT_ERR_INVALID;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2990,253 +2428,6 @@ int dmt_download_film(dmt_ctx* ctx, float* mean4, float* m24) {
   return DMT_OK;
 }
 
-// Wavefront form of a BVH launch (wavefront.hpp): passes over (owned tiles, sample range), each pass a fixed sequence of
-// kernels on the context's stream.  `ownedTiles` = tiles this rank renders; P carries region / partition / film.
-// `shade` = the k_wf_shade* row of the launch's mask.
-static int launchWavefront(dmt_ctx* ctx, RenderParams P, uint32_t ownedTiles, uint32_t sample_offset, uint32_t spp, WfKernelFn shade,
-                           uint64_t* stats, int nstats) {
-  uint32_t const iters = uint32_t(ctx->maxDepth) + 2u;  // closest rays at depth 0..maxDepth, + one trailing shadow ray
-  size_t const target = ctx->wfTargetPaths < 4096 ? 4096 : ctx->wfTargetPaths;
-  uint32_t const tilesPerPass = uint32_t(std::min<size_t>(ownedTiles, std::max<size_t>(1, target / 64)));
-  uint32_t n = uint32_t(std::max<size_t>(1, target / (size_t(tilesPerPass) * 64)));
-  if (n > spp) n = spp;
-  size_t const slotsMax = size_t(tilesPerPass) * 64 * n;
-  HIP_TRY(ctx, ctx->d_wfState.reserve(size_t(WF_PLANES) * slotsMax));
-  HIP_TRY(ctx, ctx->d_wfQueue.reserve(2 * slotsMax));
-  size_t const nCounts = 2 * (size_t(iters) + 2);
-  HIP_TRY(ctx, ctx->d_wfCounts.reserve(nCounts));
-  if (ctx->wfBlocksTrace == 0) {
-    int a = 0, b = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, reinterpret_cast<void const*>(k_wf_trace), 256, 0);
-    // one shade grid for every variant: sized by the one with the most registers
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, reinterpret_cast<void const*>(k_wf_shade_env_area), 256, 0);
-    ctx->wfBlocksTrace = a > 0 ? a : 1, ctx->wfBlocksShade = b > 0 ? b : 1;
-  }
-  uint32_t const traceBlocks = uint32_t(ctx->cuCount) * uint32_t(stats ? 4 : ctx->wfBlocksTrace);
-  uint32_t const shadeBlocks = uint32_t(ctx->cuCount) * uint32_t(stats ? 2 : ctx->wfBlocksShade);
-  HIP_TRY(ctx, reserveOverflow(ctx, size_t(traceBlocks) * 256));
-  P.bvh = bvhView(ctx, size_t(traceBlocks) * 256);
-  if (stats) {
-    HIP_TRY(ctx, ctx->d_stats.reserve(16));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats.get(), 0, 16 * sizeof(unsigned long long), ctx->stream));
-    P.stats = ctx->d_stats.get();
-  }
-  WfKernelFn const trace = stats ? k_wf_trace_stats : k_wf_trace;
-  WfParams W{};
-  W.state = ctx->d_wfState.get();
-  W.queue[0] = ctx->d_wfQueue.get(), W.queue[1] = ctx->d_wfQueue.get() + slotsMax;
-  W.counts = ctx->d_wfCounts.get(), W.cursors = ctx->d_wfCounts.get() + (iters + 2);
-  for (uint32_t tile0 = 0; tile0 < ownedTiles; tile0 += tilesPerPass) {
-    uint32_t const tiles = std::min(tilesPerPass, ownedTiles - tile0);
-    for (uint32_t s = 0; s < spp; s += n) {
-      W.tile0 = tile0, W.pixelSlots = tiles * 64u, W.s0 = sample_offset + s, W.n = std::min(n, spp - s);
-      W.slots = W.pixelSlots * W.n;
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_wfCounts.get(), 0, nCounts * sizeof(uint32_t), ctx->stream));
-      uint32_t const genBlocks = std::min<uint32_t>((W.slots + 255u) / 256u, uint32_t(ctx->cuCount) * 8u);
-      W.it = 0;
-      hipLaunchKernelGGL(k_wf_generate, dim3(genBlocks), dim3(256), 0, ctx->stream, P, W);
-      for (uint32_t it = 0; it < iters; ++it) {
-        W.it = it;
-        // a persistent grid no larger than the pass: small passes do not pay for 2 048 idle blocks per launch
-        uint32_t const tb = std::min<uint32_t>(traceBlocks, (W.slots + 255u) / 256u);
-        uint32_t const sb = std::min<uint32_t>(shadeBlocks, (W.slots + 255u) / 256u);
-        hipLaunchKernelGGL(trace, dim3(tb), dim3(256), 0, ctx->stream, P, W);
-        hipLaunchKernelGGL(shade, dim3(sb), dim3(256), 0, ctx->stream, P, W);
-      }
-      if (!stats) hipLaunchKernelGGL(k_wf_fold, dim3((W.pixelSlots + 255u) / 256u), dim3(256), 0, ctx->stream, P, W);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-  }
-  if (stats) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<unsigned long long> h(16, 0);
-    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->d_stats.get(), 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    {  // samples = pixels of the owned tiles inside the region x spp (the kernels count rays, visits and bounces)
-      uint64_t pixels = 0;
-      for (uint32_t item = 0; item < ownedTiles; ++item) {
-        uint32_t const j = uint32_t(P.rank) + item * uint32_t(P.world);
-        int const px0 = (P.tx0 + int(j % uint32_t(P.rtx))) * 8, py0 = (P.ty0 + int(j / uint32_t(P.rtx))) * 8;
-        int const w = std::min(px0 + 8, P.x1) - std::max(px0, P.x0), hgt = std::min(py0 + 8, P.y1) - std::max(py0, P.y0);
-        if (w > 0 && hgt > 0) pixels += uint64_t(w) * uint64_t(hgt);
-      }
-      h[0] = pixels * spp;
-    }
-    for (int k = 0; k < nstats && k < 16; ++k) stats[k] = h[size_t(k)];
-  }
-  return DMT_OK;
-}
-
-// the tiles of an adaptive round (dmt_render_adaptive): `count` region tiles in `list`, their pixel masks in `mask`
-struct TileSelection {
-  uint32_t const* list;
-  unsigned long long const* mask;
-  uint32_t count;
-};
-static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats,
-                      TileSelection const* sel = nullptr) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (stats6) memset(stats6, 0, size_t(nstats) * sizeof(uint64_t));
-  if (!(ctx->haveTris && ctx->haveBsdfs && ctx->haveLights && ctx->haveCamera))
-    return fail(ctx, DMT_ERR_STATE, "dmt_render: upload triangles, bsdfs, lights and set the camera first");
-  // the Halton index sample * stride must stay inside int32 (CC/private/rng.cu:229)
-  uint64_t const stride = uint64_t(ctx->sp.scale0) * uint64_t(ctx->sp.scale1);
-  if ((uint64_t(sample_offset) + spp + 1) * stride > 0x7FFFFFFFull)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_render: sample index overflows the 32-bit Halton index");
-  // every material index must address an uploaded BSDF (the kernel gathers bsdfs[matId])
-  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_render: a triangle's material index is outside the BSDF array");
-  if (x0 < 0) x0 = 0;
-  if (y0 < 0) y0 = 0;
-  if (x1 > ctx->filmW) x1 = ctx->filmW;
-  if (y1 > ctx->filmH) y1 = ctx->filmH;
-  if (spp == 0 || x1 <= x0 || y1 <= y0) return DMT_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  uint32_t F = 0;
-  if (int const rc = resolveFeatures(ctx, &F)) return rc;
-  if (int const rc = checkFeatures(ctx, stats6 ? F | kFeatStats : F)) return rc;
-  MegakernelFn const kernel = megakernelOf(F);
-  if (!kernel) return noKernel(ctx, "dmt_render", F);
-
-  RenderParams P = baseParams(ctx, 0);
-  P.mean = ctx->d_mean, P.m2 = ctx->d_m2, P.counter = ctx->d_counter.get();
-  P.width = ctx->filmW, P.height = ctx->filmH;
-  P.x0 = x0, P.y0 = y0, P.x1 = x1, P.y1 = y1;
-  P.tx0 = x0 / 8, P.ty0 = y0 / 8;
-  int const tx1 = (x1 + 7) / 8, ty1 = (y1 + 7) / 8;
-  P.rtx = tx1 - P.tx0;
-  uint32_t const tiles = uint32_t(P.rtx) * uint32_t(ty1 - P.ty0);
-  P.rank = ctx->rank, P.world = ctx->world;
-  P.numItems = tiles > uint32_t(ctx->rank) ? (tiles - uint32_t(ctx->rank) + uint32_t(ctx->world) - 1) / uint32_t(ctx->world) : 0;
-  P.sampleOffset = sample_offset, P.spp = spp;
-  if (P.numItems == 0) return DMT_OK;
-  uint32_t const ownedTiles = P.numItems;
-  if (sel) P.numItems = sel->count, P.tileList = sel->list, P.tileMask = sel->mask;  // (count > 0: checked by the caller)
-  // BVH launches run as the megakernel unless the wavefront form (wavefront.hpp) is asked for: on the measured scenes
-  // the megakernel is faster (1 M triangles: 489 vs 378 Msamples/s), so "automatic" means megakernel
-  // (BVH masks without textures, blends or a light tree have a k_wf_shade* row)
-  WfKernelFn const wfShade = kernelOf(kWfShadeKernels, stats6 ? F | kFeatStats : F);
-  bool const wavefront = ctx->bvhStrategy == 2 && wfShade != nullptr && !sel;  // (adaptive rounds: always the megakernel)
-  int const blocksPerCu = blocksPerCuOf(ctx, kernel);
-  {  // fewer owned tiles than ~4 per resident wave: schedule row bands of the tiles instead of whole tiles
-    uint32_t const waves = uint32_t(ctx->cuCount) * uint32_t(blocksPerCu) * 4u;
-    P.subShift = ctx->subShift >= 0 ? uint32_t(ctx->subShift) : 0u;
-    if (ctx->subShift < 0)
-      while (P.subShift < 2u && (uint64_t(P.numItems) << P.subShift) < 4ull * waves) ++P.subShift;
-    P.numItems <<= P.subShift;
-  }
-  // samples per work item: automatic = 16 per 64 pixels (1 024 path samples per item); bounded so the staging
-  // area (768 B per sample index per resident wave and slot) stays small
-  P.chunkSpp = ctx->chunkSpp ? ctx->chunkSpp : (16u << P.subShift);
-  if (P.chunkSpp > spp) P.chunkSpp = spp;
-  if (P.chunkSpp > kMaxChunkSpp) P.chunkSpp = kMaxChunkSpp;
-  P.numChunks = (spp + P.chunkSpp - 1) / P.chunkSpp;
-  if (uint64_t(P.numItems) * P.numChunks > 0x7FFFFFFFull)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_render: too many work items (tiles x sample chunks); raise dmt_set_chunk or split the pass");
-  P.schedDiag = ctx->d_schedDiag.get();
-  // Sampler table: for plain megakernel launches only.  Counting launches are not timed, the wavefront form prepares its
-  // samples per pass, and an adaptive round's live pixel count is on the device.  The owned pixels are counted in whole tiles.
-  SamplerTablePlan tab;
-  if (!stats6 && !wavefront && !sel && !(F & kFeatMotion))  // (motion launches compute their samples: the table has no time plane)
-    tab = samplerTablePlan(ctx->filmW, ctx->filmH, uint64_t(ownedTiles) * 64u, spp, P.chunkSpp, ctx->samTabBudget, ctx->samTabMode,
-                           ctx->lensR > 0.f ? kSamTabLensEntryBytes : kSamTabEntryBytes);
-
-  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
-  uint32_t const wavesWanted = P.numItems * P.numChunks < P.numItems ? P.numItems : P.numItems * P.numChunks;
-  uint32_t blocks = uint32_t(ctx->cuCount) * uint32_t(blocksPerCu);
-  uint32_t const blocksNeeded = (wavesWanted + 3) / 4;
-  if (blocks > blocksNeeded) blocks = blocksNeeded;
-  if (blocks == 0) blocks = 1;
-
-  if (ctx->eventsUsed == ctx->events.size()) {
-    hipEvent_t a, b;
-    HIP_TRY(ctx, hipEventCreate(&a));
-    HIP_TRY(ctx, hipEventCreate(&b));
-    ctx->events.emplace_back(a, b);
-  }
-  auto& ev = ctx->events[ctx->eventsUsed];
-  {  // staging slabs of finished samples, kSlabsPerWave per wave of the launch
-    size_t const floats = size_t(blocks) * 4u * size_t(kSlabsPerWave) * size_t(P.chunkSpp) * 192u;
-    HIP_TRY(ctx, ctx->d_stage.reserve(floats));
-    P.stage = ctx->d_stage.get();
-  }
-  if (ctx->ggxBatchT != 0u && F == 0u && !stats6 && !wavefront) {  // the row that parks GGX hits: one queue per wave
-    HIP_TRY(ctx, ctx->d_ggxQueue.reserve(size_t(blocks) * size_t(kLdsThreads / 64) * size_t(kGgxFields) * size_t(kGgxQueueCap)));  // (wave_index)
-    P.ggxQueue = ctx->d_ggxQueue.get(), P.ggxBatchT = ctx->ggxBatchT;
-  }
-  // A call with a sampler table runs as tab.slices consecutive sample slices, each a table fill and a megakernel launch
-  // over a whole number of chunks, all inside the one event pair; the film is bit-identical under any split of the
-  // sample range.  Without a table the call is one slice.
-  uint32_t const callChunks = P.numChunks;
-  uint32_t const sliceChunks = tab.use ? tab.sliceChunks : callChunks;
-  size_t const busyWords = size_t(blocks) * 4u * size_t(kSlabsPerWave);
-  size_t const linkWords = sliceChunks > 1 ? size_t(P.numItems) * size_t(sliceChunks) : 0;
-  {  // slab-busy marks + one hand-over word per (chunk, tile item), all zero at launch
-    HIP_TRY(ctx, ctx->d_sched.reserve(busyWords + linkWords));
-    P.slabBusy = ctx->d_sched.get(), P.link = ctx->d_sched.get() + busyWords;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_sched.get(), 0, (busyWords + linkWords) * sizeof(uint32_t), ctx->stream));
-  }
-  size_t const sliceEntries = size_t(std::min<uint64_t>(uint64_t(sliceChunks) * P.chunkSpp, spp)) * tab.pw * tab.ph;
-  if (tab.use) {
-    HIP_TRY(ctx, ctx->d_samTab.reserve(2 * sliceEntries));
-    HIP_TRY(ctx, ctx->d_samTabJit.reserve(sliceEntries));
-    P.samTab = ctx->d_samTab.get(), P.samTabJit = ctx->d_samTabJit.get(), P.samTabPw = tab.pw, P.samTabPh = tab.ph;
-    if (ctx->lensR > 0.f) {
-      HIP_TRY(ctx, ctx->d_samTabLens.reserve(sliceEntries));
-      P.samTabLens = ctx->d_samTabLens.get();
-    }
-  }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_counter.get(), 0, sizeof(uint32_t), ctx->stream));
-  HIP_TRY(ctx, hipEventRecord(ev.first, ctx->stream));
-  uint64_t const launchFolds = uint64_t(P.numItems) * P.numChunks;  // every item is folded exactly once (checkErrorFlag)
-  if (wavefront) {
-    if (int const rcT = requireTree(ctx, "dmt_render")) return rcT;
-    int const rcW = launchWavefront(ctx, P, ownedTiles, sample_offset, spp, wfShade, stats6, nstats);
-    if (rcW) return rcW;
-    if (stats6) return DMT_OK;
-  } else if (useBvh) {
-    if (int const rcT = requireTree(ctx, "dmt_render")) return rcT;
-    HIP_TRY(ctx, reserveOverflow(ctx, size_t(ctx->cuCount) * size_t(std::max(blocksPerCu, ctx->ac.blocksPerCUBvh)) * 256));
-    P.bvh = bvhView(ctx, size_t(blocks) * 256);
-    if (stats6) {
-      HIP_TRY(ctx, ctx->d_stats.reserve(16));
-      HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats.get(), 0, 16 * sizeof(unsigned long long), ctx->stream));
-      P.stats = ctx->d_stats.get();
-      hipLaunchKernelGGL(megakernelOf(F | kFeatStats), dim3(blocks), dim3(256), 0, ctx->stream, P);
-      HIP_TRY(ctx, hipGetLastError());
-      ctx->expectedFolds += launchFolds;
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_TRY(ctx, hipMemcpy(stats6, ctx->d_stats.get(), size_t(nstats) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      return DMT_OK;
-    }
-  }
-  if (int const rcM = motionParams(ctx, F, P)) return rcM;
-  if (!wavefront) {
-    for (uint32_t c0 = 0; c0 < callChunks; c0 += sliceChunks) {
-      uint32_t const first = c0 * P.chunkSpp;  // of the call's samples
-      uint32_t const n = std::min<uint64_t>(uint64_t(sliceChunks) * P.chunkSpp, spp - first);
-      P.sampleOffset = sample_offset + first, P.spp = n, P.numChunks = (n + P.chunkSpp - 1) / P.chunkSpp;
-      if (c0 > 0) {  // the link words and the counter start every slice at zero, as they start every launch
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_sched.get(), 0, (busyWords + linkWords) * sizeof(uint32_t), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_counter.get(), 0, sizeof(uint32_t), ctx->stream));
-      }
-      if (tab.use) {
-        P.samTabS0 = P.sampleOffset;
-        uint32_t const entries = n * tab.pw * tab.ph;
-        hipLaunchKernelGGL(k_sampler_table, dim3((entries + 255u) / 256u), dim3(256), 0, ctx->stream, P.sp, P.samTabS0, n, tab.pw, tab.ph,
-                           ctx->d_samTab.get(), ctx->d_samTabJit.get(), const_cast<float2*>(P.samTabLens));
-        HIP_TRY(ctx, hipGetLastError());
-      }
-      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, ctx->stream, P);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  if (!wavefront) ctx->expectedFolds += launchFolds;
-  HIP_TRY(ctx, hipEventRecord(ev.second, ctx->stream));
-  ++ctx->eventsUsed;
-  return DMT_OK;
-}
-
 #if DMT_CULL_COUNTS
 extern "C" int dmt_diag_cull_counts(unsigned long long* out16, int reset) {
   hipError_t e = hipDeviceSynchronize();
@@ -3260,9 +2451,6 @@ extern "C" int dmt_diag_section_cycles(unsigned long long* out16, int reset) {
 }
 #endif
 
-// Host-only: build the BVH of a soup and check its invariants (every triangle in exactly one leaf, every DECODED
-// (quantised) child box encloses all vertices below it and lies inside its parent's decoded box up to one quantisation
-// step, inner children first with consecutive indices, depth within the traversal-stack bound).
 int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
                         uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_sphere) {
   if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
@@ -3325,119 +2513,6 @@ int dmt_cull_box_test(const float* record6, const float* origins, const float* d
   return DMT_OK;
 }
 
-static int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1, uint64_t* stats6, int nstats,
-                      TileSelection const* sel);
-
-int dmt_render(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1) {
-  return renderImpl(ctx, sample_offset, spp, x0, y0, x1, y1, nullptr, 0);
-}
-
-// Adaptive sampling: rounds of step_spp samples; before each round k_adaptive_mask decides which pixels go on (stopping rule
-// at adaptive_active) and lists the tiles that have any, and the round is an ordinary megakernel launch over those tiles.
-int dmt_render_adaptive(dmt_ctx* ctx, uint32_t min_spp, uint32_t max_spp, uint32_t step_spp, float threshold, int x0, int y0,
-                        int x1, int y1, uint32_t* rounds, uint64_t* samples) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (rounds) *rounds = 0;
-  if (samples) *samples = 0;
-  if (step_spp == 0 || max_spp == 0) return fail(ctx, DMT_ERR_INVALID, "dmt_render_adaptive: step_spp and max_spp must be positive");
-  if (max_spp > (1u << 24)) return fail(ctx, DMT_ERR_INVALID, "dmt_render_adaptive: max_spp above 2^24 (the sample count must stay exact in fp32)");
-  if (!std::isfinite(threshold) || threshold < 0.f) return fail(ctx, DMT_ERR_INVALID, "dmt_render_adaptive: threshold must be finite and >= 0");
-  if (!(ctx->haveTris && ctx->haveBsdfs && ctx->haveLights && ctx->haveCamera))
-    return fail(ctx, DMT_ERR_STATE, "dmt_render_adaptive: upload triangles, bsdfs, lights and set the camera first");
-  if (x0 < 0) x0 = 0;
-  if (y0 < 0) y0 = 0;
-  if (x1 > ctx->filmW) x1 = ctx->filmW;
-  if (y1 > ctx->filmH) y1 = ctx->filmH;
-  if (x1 <= x0 || y1 <= y0) return DMT_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  AdaptiveArgs A{};
-  A.mean = ctx->d_mean, A.m2 = ctx->d_m2, A.width = ctx->filmW;
-  A.x0 = x0, A.y0 = y0, A.x1 = x1, A.y1 = y1;
-  A.tx0 = x0 / 8, A.ty0 = y0 / 8, A.rtx = (x1 + 7) / 8 - A.tx0;  // the tile grid of renderImpl
-  uint32_t const tiles = uint32_t(A.rtx) * uint32_t((y1 + 7) / 8 - A.ty0);
-  A.rank = ctx->rank, A.world = ctx->world;
-  A.owned = tiles > uint32_t(ctx->rank) ? (tiles - uint32_t(ctx->rank) + uint32_t(ctx->world) - 1) / uint32_t(ctx->world) : 0;
-  if (A.owned == 0) return DMT_OK;
-  A.minSpp = min_spp, A.maxSpp = max_spp, A.threshold = threshold;
-  size_t const filmTiles = size_t((ctx->filmW + 7) / 8) * size_t((ctx->filmH + 7) / 8);  // >= tiles of any region
-  HIP_TRY(ctx, ctx->d_adMask.reserve(filmTiles));
-  HIP_TRY(ctx, ctx->d_adList.reserve(filmTiles));
-  HIP_TRY(ctx, ctx->d_adCount.reserve(2));
-  A.mask = ctx->d_adMask.get(), A.list = ctx->d_adList.get(), A.counters = ctx->d_adCount.get();
-  for (uint32_t offset = 0; offset < max_spp;) {
-    A.offset = offset;
-    HIP_TRY(ctx, hipMemsetAsync(A.counters, 0, 2 * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_adaptive_mask, dim3((A.owned + 3u) / 4u), dim3(256), 0, ctx->stream, A);
-    HIP_TRY(ctx, hipGetLastError());
-    uint32_t h[2] = {0, 0};  // listed tiles, active pixels
-    HIP_TRY(ctx, hipMemcpyAsync(h, A.counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (int const rc = checkErrorFlag(ctx)) return rc;  // the previous round lost or duplicated a fold
-    if (h[0] == 0) break;
-    uint32_t const n = std::min(step_spp, max_spp - offset);
-    TileSelection const sel{A.list, A.mask, h[0]};
-    if (int const rc = renderImpl(ctx, offset, n, x0, y0, x1, y1, nullptr, 0, &sel)) return rc;
-    if (rounds) ++*rounds;
-    if (samples) *samples += uint64_t(h[1]) * n;
-    offset += n;
-  }
-  return DMT_OK;
-}
-
-int dmt_render_stats(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1,
-                     uint64_t* stats6) {
-  if (!ctx || !stats6) return DMT_ERR_INVALID;
-  if (ctx->accel != DMT_ACCEL_BVH) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats: only the BVH path has device counters");
-  return renderImpl(ctx, sample_offset, spp, x0, y0, x1, y1, stats6, 6);
-}
-
-int dmt_render_profile(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y0, int x1, int y1,
-                       uint64_t* stats16) {
-  if (!ctx || !stats16) return DMT_ERR_INVALID;
-  if (ctx->accel != DMT_ACCEL_BVH) return fail(ctx, DMT_ERR_STATE, "dmt_render_profile: only the BVH path has device counters");
-  return renderImpl(ctx, sample_offset, spp, x0, y0, x1, y1, stats16, 16);
-}
-
-int dmt_sync(dmt_ctx* ctx) {
-  if (!ctx) return DMT_ERR_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return checkErrorFlag(ctx);
-}
-
-int dmt_sched_diag(dmt_ctx* ctx, uint64_t* out8, int reset) {
-  if (!ctx || !out8) return DMT_ERR_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  unsigned long long d[kSchedDiagWords] = {};
-  HIP_TRY(ctx, hipMemcpy(d, ctx->d_schedDiag.get(), sizeof(d), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 8; ++i) out8[i] = i < kSchedDiagWords ? d[i] : 0;
-  out8[6] = ctx->expectedFolds;
-  out8[7] = uint64_t(kSlabsPerWave);
-  if (reset) {
-    HIP_TRY(ctx, hipMemset(ctx->d_schedDiag.get(), 0, sizeof(d)));  // (the GGX batching words too: read dmt_ggx_batch_diag first)
-    ctx->expectedFolds = 0, ctx->ggxLostReported = 0;
-  }
-  return DMT_OK;
-}
-
-int dmt_set_ggx_batch(dmt_ctx* ctx, uint32_t batch) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (batch > kGgxQueueCap) return fail(ctx, DMT_ERR_INVALID, "dmt_set_ggx_batch: a batch is at most 64 hits (the queue's capacity)");
-  ctx->ggxBatchT = batch;
-  return DMT_OK;
-}
-
-int dmt_ggx_batch_diag(dmt_ctx* ctx, uint64_t* out5) {
-  if (!ctx || !out5) return DMT_ERR_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  unsigned long long d[kSchedDiagWords] = {};
-  HIP_TRY(ctx, hipMemcpy(d, ctx->d_schedDiag.get(), sizeof(d), hipMemcpyDeviceToHost));
-  out5[0] = d[SD_GGX_PARKED], out5[1] = d[SD_GGX_RESUMED], out5[2] = d[SD_GGX_PASSES], out5[3] = d[SD_GGX_FULL], out5[4] = ctx->ggxBatchT;
-  return DMT_OK;
-}
-
 int dmt_envmap_tables(const float* rgb, int width, int height, float* func, float* cdf, float* row_integral,
                       float* marginal_func, float* marginal_cdf, float* marginal_integral) {
   if (!rgb || width < 8 || height < 8 || (width & (width - 1)) || (height & (height - 1)) || !func || !cdf ||
@@ -3491,38 +2566,6 @@ int dmt_upload_envmap(dmt_ctx* ctx, const float* rgb, int width, int height, con
   e.qx = quat_xyzw[0] / len, e.qy = quat_xyzw[1] / len, e.qz = quat_xyzw[2] / len, e.qw = quat_xyzw[3] / len;
   ctx->d_env = std::move(buf);
   ctx->env = e;
-  return DMT_OK;
-}
-
-int dmt_set_chunk(dmt_ctx* ctx, uint32_t samples_per_item) {
-  if (!ctx) return DMT_ERR_INVALID;
-  ctx->chunkSpp = samples_per_item;
-  return DMT_OK;
-}
-
-int dmt_set_sampler_table(dmt_ctx* ctx, int mode, uint64_t budget_bytes) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (mode != DMT_SAMPLER_TABLE_OFF && mode != DMT_SAMPLER_TABLE_AUTO && mode != DMT_SAMPLER_TABLE_FORCE)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_set_sampler_table: unknown mode");
-  ctx->samTabMode = mode;
-  ctx->samTabBudget = budget_bytes ? budget_bytes : kSamTabDefaultBudget;
-  return DMT_OK;
-}
-
-int dmt_sampler_table_plan(int width, int height, uint64_t owned_pixels, uint32_t spp, uint32_t chunk_spp, uint64_t budget_bytes, int mode,
-                           dmt_sampler_table_plan_record* out, uint32_t* slice_spp, uint32_t slice_cap) {
-  if (!out || width <= 0 || height <= 0 || (slice_cap && !slice_spp)) return DMT_ERR_INVALID;
-  if (mode != DMT_SAMPLER_TABLE_OFF && mode != DMT_SAMPLER_TABLE_AUTO && mode != DMT_SAMPLER_TABLE_FORCE) return DMT_ERR_INVALID;
-  if (chunk_spp > spp) chunk_spp = spp;
-  SamplerTablePlan const p = samplerTablePlan(width, height, owned_pixels, spp, chunk_spp, budget_bytes ? budget_bytes : kSamTabDefaultBudget, mode);
-  *out = dmt_sampler_table_plan_record{};
-  out->use = p.use ? 1 : 0, out->period_width = p.pw, out->period_height = p.ph, out->entry_bytes = kSamTabEntryBytes;
-  if (!p.use) return DMT_OK;
-  out->slices = p.slices;
-  uint64_t const sliceSamples = uint64_t(p.sliceChunks) * chunk_spp;
-  out->slice_bytes = std::min<uint64_t>(sliceSamples, spp) * p.pw * p.ph * kSamTabEntryBytes;
-  for (uint32_t k = 0; k < p.slices && k < slice_cap; ++k)
-    slice_spp[k] = uint32_t(std::min<uint64_t>(sliceSamples, spp - k * sliceSamples));
   return DMT_OK;
 }
 
@@ -3621,40 +2664,6 @@ int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
   if (tri < 0) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: the ray leaves the scene");
   float const* const m = ctx->xf.rfc;  // column 2 = the viewing direction
   *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
-  return DMT_OK;
-}
-
-int dmt_kernel_time(dmt_ctx* ctx, double* total_ms, uint64_t* launches, int reset) {
-  if (!ctx) return DMT_ERR_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (int const rc = checkErrorFlag(ctx)) return rc;  // a time measured on an invalid film is not reported
-  for (size_t i = 0; i < ctx->eventsUsed; ++i) {
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->events[i].first, ctx->events[i].second));
-    ctx->accumMs += double(ms);
-    ++ctx->accumLaunches;
-  }
-  ctx->eventsUsed = 0;
-  if (total_ms) *total_ms = ctx->accumMs;
-  if (launches) *launches = ctx->accumLaunches;
-  if (reset) ctx->accumMs = 0.0, ctx->accumLaunches = 0;
-  return DMT_OK;
-}
-
-int dmt_kernel_info(dmt_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* blocks_per_cu, int* cu_count) {
-  if (!ctx) return DMT_ERR_INVALID;
-  uint32_t F = 0;  // facts of the kernel dmt_render would launch now
-  if (int const rc = resolveFeatures(ctx, &F)) return rc;
-  MegakernelFn const kernel = megakernelOf(F);
-  if (!kernel) return noKernel(ctx, "dmt_kernel_info", F);
-  hipFuncAttributes attr{};
-  HIP_TRY(ctx, hipFuncGetAttributes(&attr, reinterpret_cast<void const*>(kernel)));
-  if (vgprs) *vgprs = attr.numRegs;
-  if (sgprs) *sgprs = 0;
-  if (lds_bytes) *lds_bytes = int(attr.sharedSizeBytes);
-  if (blocks_per_cu) *blocks_per_cu = blocksPerCuOf(ctx, kernel);
-  if (cu_count) *cu_count = ctx->cuCount;
   return DMT_OK;
 }
 
