@@ -83,7 +83,7 @@ EXPORTED_SYMBOLS = [
     "dmt_motion_bvh_validate", "dmt_test_shutter_times", "dmt_test_closest_hit_at",
     "dmt_upload_vertex_normals", "dmt_clear_vertex_normals", "dmt_vertex_normals_info", "dmt_smooth_normals",
     "dmt_test_shading_normal", "dmt_test_shading_normal_mapped",
-    "dmt_set_ggx_batch", "dmt_ggx_batch_diag",
+    "dmt_set_ggx_batch", "dmt_ggx_batch_diag", "dmt_tri_kind_bits",
     "dmt_upload_opacity", "dmt_clear_opacity", "dmt_opacity_info", "dmt_opacity_eval", "dmt_test_opacity", "dmt_test_closest_hit_opacity",
 ]
 
@@ -815,6 +815,13 @@ class Renderer:
         out = (C.c_uint64 * 5)()
         self._check(self._lib.dmt_ggx_batch_diag(self._ctx, out), "dmt_ggx_batch_diag")
         return int(out[4])
+
+    def tri_kind_bits(self, triangles):
+        """The per-triangle material kinds as a launch reads them (dmt_tri_kind_bits): uint32 [(triangles + 31) // 32], bit i
+        of word i // 32 set when triangle i has a GGX material."""
+        out = np.zeros((int(triangles) + 31) // 32, np.uint32)
+        self._check(self._lib.dmt_tri_kind_bits(self._ctx, out.ctypes.data_as(C.c_void_p), C.c_uint64(out.size)), "dmt_tri_kind_bits")
+        return out
 
     def set_stream(self, stream_ptr):
         self._check(self._lib.dmt_set_stream(self._ctx, C.c_void_p(stream_ptr)), "dmt_set_stream")

@@ -149,6 +149,12 @@ struct RenderParams {
   // `opacityCutoff8`, so that no other field moves
   uint32_t ggxBatchT;
   float* ggxQueue;
+  // material kind per triangle (SurfaceState::Kind): bit i of word i >> 5 is set when ORIGINAL triangle i has a GGX material,
+  // i.e. when ggx_park parks its hits.  Soups of at most 64 triangles carry the table in the arguments themselves
+  // (triKindInline; triKindBits is then null), larger ones in device memory.  Read by k_megakernel only.  After `ggxQueue`, so
+  // that no other field moves
+  uint32_t const* triKindBits;
+  uint32_t triKindInline[2];
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -773,9 +779,10 @@ DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, Br
                                    v2f{slab_rcp(st.rp.dy.x), slab_rcp(st.rp.dy.y)}, v2f{slab_rcp(st.rp.dz.x), slab_rcp(st.rp.dz.y)});
   v2f const dd = st.rp.dx * st.rp.dx + st.rp.dy * st.rp.dy + st.rp.dz * st.rp.dz;
   v2f const idd = rcp_(dd);
+  unsigned long long const mDoC = __ballot(doC), mDoS = __ballot(doS);  // the lanes with a ray of each kind, once per call
 #if DMT_CULL_COUNTS
   unsigned long long cnt[16] = {};
-  cnt[0] = 1, cnt[1] = __popcll(__ballot(doC)), cnt[2] = __popcll(__ballot(doS));
+  cnt[0] = 1, cnt[1] = __popcll(mDoC), cnt[2] = __popcll(mDoS);
 #endif
   for (uint32_t c0 = 0; c0 < nc; c0 += kCullGroup) {
     uint32_t pre[kCullGroup + 1];  // first task of each cluster of the group (uniform)
@@ -788,7 +795,11 @@ DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, Br
         CullCluster cl;
         for (int i = 0; i < 6; ++i) cl.b[i] = r.b[i];
         cl.box = r.box, cl.count = r.count;
-        bool hitC, hitS;
+        // The verdicts are balloted inside each arm, each ballot of ONE compare, and meet the rays' masks (mDoC, mDoS) in
+        // scalar registers.  A ballot of anything but a compare -- a lane boolean merged across this branch, an `and` of
+        // two -- is lowered through a VGPR: v_cndmask 0, 1 and v_cmp_ne 0, two expensive instructions per vote, four
+        // votes per cluster.  The lane's own bit comes back from the mask for free.
+        unsigned long long mC, mS;
         if (cl.box) {
           // slabs: per axis the entry and the exit, near = max over the entries and the segment start, far = min over the
           // exits and the segment end (see cull_ray for the arithmetic and what keeps it conservative)
@@ -800,7 +811,7 @@ DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, Br
           // the compiler quiets every min / max input again)
           bool const aC = cull_box_accept(nx.x, ny.x, nz.x, fx.x, fy.x, fz.x, tmaxC, cr.e2.x);
           bool const aS = cull_box_accept(nx.y, ny.y, nz.y, fx.y, fy.y, fz.y, tmaxS, cr.e2.y);
-          hitC = doC & aC, hitS = doS & aS;
+          mC = __ballot(aC) & mDoC, mS = __ballot(aS) & mDoS;
         } else {
           v2f const wx = cl.b[0] - st.rp.ox, wy = cl.b[1] - st.rp.oy, wz = cl.b[2] - st.rp.oz;
           v2f const ww = wx * wx + wy * wy + wz * wz;
@@ -810,9 +821,9 @@ DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, Br
           v2f const ex = wx - tc * st.rp.dx, ey = wy - tc * st.rp.dy, ez = wz - tc * st.rp.dz;
           v2f const ee = ex * ex + ey * ey + ez * ez;
           v2f const lim = cl.b[3] + kCullRel * (ww + tc * tc * dd);
-          hitC = doC && ee.x <= lim.x, hitS = doS && ee.y <= lim.y;
+          mC = __ballot(ee.x <= lim.x) & mDoC, mS = __ballot(ee.y <= lim.y) & mDoS;
         }
-        unsigned long long const mC = __ballot(hitC), mS = __ballot(hitS);
+        bool const hitC = __builtin_amdgcn_inverse_ballot_w64(mC), hitS = __builtin_amdgcn_inverse_ballot_w64(mS);
         uint32_t const nC = uint32_t(__popcll(mC)), nS = uint32_t(__popcll(mS));
         if (hitC) s_cullOwner[w][q][__builtin_amdgcn_mbcnt_hi(uint32_t(mC >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mC), 0u))] = uint8_t(lane);
         if (hitS)
@@ -1188,24 +1199,40 @@ DMT_DEV uint32_t lane_rank(unsigned long long m) {  // set bits of m below this 
 // bounce cap and the queue has room.  Returns whether the lane shades in this pass.
 DMT_DEV bool ggx_park(KArgs Pk, uint32_t gtid, PathState& st, GgxBatch& G, bool doC, int bestTri, float bu, float bv) {
   if (kargs(Pk)->ggxBatchT == 0u) return doC;  // wave-uniform: off (nothing was ever parked, no lane has resumed)
-  bool const resumed = ggx_resumed(st);
-  if (resumed) st.depth = ~st.depth;
-  bool ggx = false;
-  if (doC && !resumed && bestTri >= 0 && st.depth < kargs(Pk)->maxDepth) {
+  // The votes of this function are wave masks, each the ballot of ONE compare, combined in scalar registers; a lane takes its
+  // own bit back from a mask where it needs it (inverse ballot).  A ballot of anything else -- an `and` of conditions, a lane
+  // boolean merged across one of the uniform branches below -- is lowered through a VGPR: v_cndmask 0, 1 and v_cmp_ne 0.
+  unsigned long long const mDoC = __ballot(doC);
+  // (the compare intrinsic: st.depth < 0 has another use below, and a ballot folds only a compare that is its own)
+  unsigned long long const mResumed = __builtin_amdgcn_sicmp(st.depth, 0, 40 /* signed < */) & mDoC;  // (ggx_resumed)
+  if (st.depth < 0) st.depth = ~st.depth;
+  // Whether the hit's material is a GGX one is a bit of the per-triangle table made at upload (SurfaceState::Kind): from the
+  // kernel arguments for soups of at most 64 triangles -- scalar loads, no vector memory -- and one load from the array
+  // otherwise (wave-uniform branch).  Neither the triangle's record nor the material's is read before path_shade, and
+  // nothing here waits for the staging store the shadow resolve has just issued.  (tri: a lane without a hit reads
+  // triangle 0's word; the array holds >= 1 word.)
+  uint32_t const tri = uint32_t(bestTri < 0 ? 0 : bestTri);
+  unsigned long long m = mDoC & ~mResumed & __ballot(bestTri >= 0) & __ballot(st.depth < kargs(Pk)->maxDepth);
+  {
     KArgs const k = kargs(Pk);
-    uint32_t const type = hi16(k->scene.bsdfs[k->scene.post[bestTri].matId].w[1]);
-    ggx = type == BS_GGX_DIEL || type == BS_GGX_COND;
+    if (uint32_t const* const bits = k->triKindBits) {
+      m &= __ballot(((bits[tri >> 5] >> (tri & 31u)) & 1u) != 0u);
+    } else {
+      uint32_t w0 = k->triKindInline[0], w1 = k->triKindInline[1];
+      asm volatile("" : "+s"(w0), "+s"(w1));  // both words by scalar load: a select of the two addresses becomes a vector load
+      uint32_t const word = (tri & 32u) != 0u ? w1 : w0;
+      m &= __ballot(((word >> (tri & 31u)) & 1u) != 0u);
+    }
   }
-  unsigned long long const m = __ballot(ggx);
-  bool park = false;
+  unsigned long long mPark = 0ull;
   if (m != 0ull) {
     uint32_t const q = G.queued();
     uint32_t const room = kGgxQueueCap - q;  // invariant (1): q <= kGgxQueueCap
     uint32_t const want = uint32_t(__popcll(m));
     uint32_t const n = want < room ? want : room;
     uint32_t const rank = lane_rank(m);
-    park = ggx && rank < room;  // queue full: shade now
-    if (park) {
+    mPark = m & __ballot(rank < room);  // queue full: shade now
+    if (__builtin_amdgcn_inverse_ballot_w64(mPark)) {
       float* const r = ggx_queue(Pk, gtid, q + rank);  // slot q + rank < q + room == kGgxQueueCap
       float const* const u = s_sampler_u + threadIdx.x;
       r[0 * kGgxQueueCap] = st.beta.x, r[1 * kGgxQueueCap] = st.beta.y, r[2 * kGgxQueueCap] = st.beta.z;
@@ -1218,11 +1245,11 @@ DMT_DEV bool ggx_park(KArgs Pk, uint32_t gtid, PathState& st, GgxBatch& G, bool 
       for (uint32_t d = 0; d < 8; ++d) r[(16 + d) * kGgxQueueCap] = u[d * kLdsThreads];
       st.active = false;  // the lane is free: it starts its prepared sample in the next pass
     }
-    uint32_t const n1 = uint32_t(__popcll(__ballot(park && (st.sidx >> 31) != 0u)));
+    uint32_t const n1 = uint32_t(__popcll(mPark & __ballot((st.sidx >> 31) != 0u)));
     G.parked += (n - n1) + (n1 << 16), G.nParked += n, G.nFull += want - n;  // want - n hits found the queue full
   }
-  if (__any(doC && (resumed || (ggx && !park)))) ++G.nPasses;  // a pass that runs the GGX branches
-  return doC && !park;
+  if ((mResumed | (m & ~mPark)) != 0ull) ++G.nPasses;  // a pass that runs the GGX branches
+  return __builtin_amdgcn_inverse_ballot_w64(mDoC & ~mPark);  // (as `doC && !park` of lane booleans the kernel spills 17 VGPRs)
 }
 // Free lanes take the newest records of the queue back (the caller has decided that they should): a lane restores the
 // path and shades the hit in this pass without tracing a closest ray (lane_step).
@@ -1233,8 +1260,8 @@ DMT_DEV void ggx_resume(KArgs Pk, uint32_t gtid, PathState& st, GgxBatch& G) {
   uint32_t const have = uint32_t(__popcll(m));
   uint32_t const n = have < q ? have : q;
   uint32_t const rank = lane_rank(m);
-  bool const pop = !st.active && rank < q;
-  if (pop) {
+  unsigned long long const mPop = m & __ballot(rank < q);  // (a mask, like ggx_park's votes)
+  if (__builtin_amdgcn_inverse_ballot_w64(mPop)) {
     float const* const r = ggx_queue(Pk, gtid, q - 1u - rank);  // slot in [q - n, q), q <= kGgxQueueCap
     float* const u = s_sampler_u + threadIdx.x;
     st.beta = mk3(r[0 * kGgxQueueCap], r[1 * kGgxQueueCap], r[2 * kGgxQueueCap]);
@@ -1249,7 +1276,7 @@ DMT_DEV void ggx_resume(KArgs Pk, uint32_t gtid, PathState& st, GgxBatch& G) {
     for (uint32_t d = 0; d < 8; ++d) u[d * kLdsThreads] = r[(16 + d) * kGgxQueueCap];
     st.active = true;
   }
-  uint32_t const n1 = uint32_t(__popcll(__ballot(pop && (st.sidx >> 31) != 0u)));
+  uint32_t const n1 = uint32_t(__popcll(mPop & __ballot((st.sidx >> 31) != 0u)));
   G.parked -= (n - n1) + (n1 << 16);
 }
 
@@ -2194,6 +2221,7 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
     int const v = std::atoi(e6);
     ctx->bruteCull = v == 0 ? 0 : v == 1 ? 1 : 2;
   }
+  if (char const* e7 = std::getenv("DMT_TRI_KIND_INLINE")) ctx->surf.kind.allowInline = std::atoi(e7) != 0;  // tests (SurfaceState::Kind)
   *out = ctx.release();
   return DMT_OK;
 }
@@ -2240,8 +2268,9 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->h_mat.assign(mat_id, mat_id + count);
   ctx->ac.tree.drop();         // it is of the soup just replaced
   dropMotion(ctx);             // key 1 was a motion from the soup just replaced
-  ctx->surf.soupReplaced();    // vertex normals, opacity records and emissive triangles were of the soup just replaced
+  hipError_t const kindRc = ctx->surf.soupReplaced(ctx->h_mat);  // vertex normals, opacity records and emissive triangles were of the soup just replaced; the material kinds are made anew
   ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
+  HIP_TRY(ctx, kindRc);
   if (ctx->accel == DMT_ACCEL_BVH) return buildBvh(ctx);
   return DMT_OK;
 }
@@ -2266,11 +2295,12 @@ int dmt_upload_bsdfs(dmt_ctx* ctx, const void* bsdf32, uint32_t count) {
     }
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (a launch in flight may read the cutout records dropped below)
-  ctx->surf.bsdfsReplaced();  // the cutout records name the materials just replaced
+  hipError_t const kindRc = ctx->surf.bsdfsReplaced(bsdf32, count, ctx->h_mat);  // the cutout records name the materials just replaced; the material kinds are made anew
   ctx->d_bsdfs = std::move(bsdfs);
   ctx->hasBlend = blend;
   ctx->bsdfCount = count;
   ctx->haveBsdfs = true;
+  HIP_TRY(ctx, kindRc);
   return DMT_OK;
 }
 

@@ -167,6 +167,25 @@ int dmt_upload_area_lights(dmt_ctx* ctx, const uint32_t* triangle_index, const f
   return DMT_OK;
 }
 
+// ---- material kind per triangle (SurfaceState::Kind) --------------------------------------------------------
+// What a launch reads: the device array where the table travels as one, the words that go into the kernel arguments otherwise.
+int dmt_tri_kind_bits(dmt_ctx* ctx, uint32_t* out, uint64_t words) {
+  if (!ctx) return DMT_ERR_INVALID;
+  SurfaceState::Kind const& kind = ctx->surf.kind;
+  size_t const n = kind.words.size();
+  if (words < n || (n && !out)) return fail(ctx, DMT_ERR_INVALID, "dmt_tri_kind_bits: room for (triangles + 31) / 32 words is needed");
+  if (n == 0) return DMT_OK;
+  if (kind.bits.get()) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy(out, kind.bits.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  } else {
+    RenderParams P{};
+    ctx->surf.fill(P);
+    for (size_t w = 0; w < n; ++w) out[w] = w < 2 ? P.triKindInline[w] : 0u;  // (n > 2 here only after a failed upload of the table: all zeros)
+  }
+  return DMT_OK;
+}
+
 // ---- image textures and the first-hit texture filter -------------------------
 int dmt_upload_textures(dmt_ctx* ctx, const uint8_t* rgba8, uint64_t texel_count, const int32_t* desc3, uint32_t texture_count,
                         const uint32_t* mat_tex4, uint32_t bsdf_count, const float* tri_uv6, uint64_t triangle_count) {

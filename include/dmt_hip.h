@@ -443,6 +443,13 @@ int dmt_set_ggx_batch(dmt_ctx* ctx, uint32_t batch);
  * counted while batching is on only.  dmt_sched_diag itself reports none of them (its eight words are taken), and its
  * reset clears them: read these first. */
 int dmt_ggx_batch_diag(dmt_ctx* ctx, uint64_t* out5);
+/* The table that tells GGX batching which hits to park, as a launch reads it: bit i of word i / 32 is set when the
+ * material of triangle i is a GGX dielectric or conductor.  It is made on the host from the material ids of
+ * dmt_upload_triangles and the records of dmt_upload_bsdfs, anew by either call (in any order; a material id beyond the
+ * BSDF array counts as not GGX).  Soups of at most 64 triangles carry it in the kernel arguments, larger ones as a
+ * device array; DMT_TRI_KIND_INLINE=0 in the environment at context creation makes every soup use the array (tests).
+ * out: (triangles + 31) / 32 words; `words` is the room at out.  Synchronises where the table is a device array. */
+int dmt_tri_kind_bits(dmt_ctx* ctx, uint32_t* out, uint64_t words);
 /* HIP-event time of the megakernel launches since the last reset (synchronises the stream):
  * total milliseconds and launch count. */
 int dmt_kernel_time(dmt_ctx* ctx, double* total_ms, uint64_t* launches, int reset);
