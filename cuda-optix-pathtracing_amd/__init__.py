@@ -41,6 +41,9 @@ from .binding import (  # noqa: F401
     smooth_normals,
     opacity_eval,
     OPACITY_NONE,
+    medium_segment,
+    medium_values,
+    phase_hg,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

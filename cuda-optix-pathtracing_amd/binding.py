@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "dmt_test_shading_normal", "dmt_test_shading_normal_mapped",
     "dmt_set_ggx_batch", "dmt_ggx_batch_diag", "dmt_tri_kind_bits",
     "dmt_upload_opacity", "dmt_clear_opacity", "dmt_opacity_info", "dmt_opacity_eval", "dmt_test_opacity", "dmt_test_closest_hit_opacity",
+    "dmt_set_medium", "dmt_clear_medium", "dmt_medium_info", "dmt_medium_segment", "dmt_medium_values", "dmt_phase_hg", "dmt_test_medium",
 ]
 
 # dmt_set_sampler_table modes (include/dmt_hip.h)
@@ -236,6 +237,58 @@ def smooth_normals(xs, ys, zs, crease_degrees=180.0):
     if rc != 0:
         raise DmtError(f"dmt_smooth_normals failed ({rc})")
     return out
+
+
+def _u32(a):
+    return np.ascontiguousarray(a, np.uint32).reshape(-1)
+
+
+def medium_segment(box_min, box_max, o, d, t_hit):
+    """Host only (dmt_medium_segment): the clip of rays (o, d: [n, 3]) ending at t_hit [n] (may be +inf) against the box, the
+    device's bit for bit -> (seg [n, 2] = (t0, t1), hit [n] bool = t0 < t1)."""
+    lib = load_library()
+    o, d = _f32(o).reshape(-1, 3), _f32(d).reshape(-1, 3)
+    t = _f32(t_hit).reshape(-1)
+    n = o.shape[0]
+    assert d.shape[0] == n and t.shape[0] == n
+    seg, hit = np.zeros((n, 2), np.float32), np.zeros(n, np.int32)
+    rc = lib.dmt_medium_segment(_p(_f32(box_min, (3,))), _p(_f32(box_max, (3,))), int(n), _p(o), _p(d), _p(t), _p(seg), _p(hit))
+    if rc != 0:
+        raise DmtError(f"dmt_medium_segment failed ({rc})")
+    return seg, hit.astype(bool)
+
+
+def medium_values(h, depth):
+    """Host only (dmt_medium_values): the free-flight numbers medium_u(h, depth) [n] in [0, 1), the device's bit for bit."""
+    lib = load_library()
+    h, depth = _u32(h), _u32(depth)
+    assert h.shape[0] == depth.shape[0]
+    u = np.zeros(h.shape[0], np.float32)
+    rc = lib.dmt_medium_values(int(h.shape[0]), _p(h), _p(depth), _p(u))
+    if rc != 0:
+        raise DmtError(f"dmt_medium_values failed ({rc})")
+    return u
+
+
+def phase_hg(g, cosine=None, wo=None, u=None):
+    """Host only (dmt_phase_hg): Henyey-Greenstein of asymmetry g in fp32.  With cosine [n] = dot(wo, wi): eval [n].  With wo
+    [n, 3] (unit) and u [n, 2]: (wi [n, 3], pdf [n]).  With both: (eval, wi, pdf)."""
+    lib = load_library()
+    ev = wi = pdf = None
+    n = 0
+    if cosine is not None:
+        cosine = _f32(cosine).reshape(-1)
+        n, ev = cosine.shape[0], np.zeros(cosine.shape[0], np.float32)
+    if wo is not None or u is not None:
+        wo, u = _f32(wo).reshape(-1, 3), _f32(u).reshape(-1, 2)
+        assert wo.shape[0] == u.shape[0] and (cosine is None or wo.shape[0] == n)
+        n, wi, pdf = wo.shape[0], np.zeros(wo.shape, np.float32), np.zeros(wo.shape[0], np.float32)
+    rc = lib.dmt_phase_hg(C.c_float(g), int(n), _p(cosine), _p(ev), _p(wo), _p(u), _p(wi), _p(pdf))
+    if rc != 0:
+        raise DmtError(f"dmt_phase_hg failed ({rc})")
+    if wi is None:
+        return ev
+    return (wi, pdf) if ev is None else (ev, wi, pdf)
 
 
 OPACITY_NONE = 0xFFFFFFFF  # dmt_upload_opacity: the material is opaque
@@ -582,6 +635,40 @@ class Renderer:
         direction, in scene units.  The lens survives set_camera and scene uploads."""
         self._check(self._lib.dmt_set_lens(self._ctx, C.c_float(lens_radius), C.c_float(focus_distance)), "dmt_set_lens")
 
+    def set_medium(self, sigma_t, albedo=(1.0, 1.0, 1.0), g=0.0, box_min=(0.0, 0.0, 0.0), box_max=(1.0, 1.0, 1.0)):
+        """Participating medium (dmt_set_medium): homogeneous fog of grey extinction sigma_t >= 0 per scene unit, albedo in
+        [0, 1] per channel and Henyey-Greenstein asymmetry |g| < 1 inside the box [box_min, box_max].  Active exactly when
+        sigma_t > 0; survives scene uploads and set_camera."""
+        self._check(self._lib.dmt_set_medium(self._ctx, C.c_float(sigma_t), _p(_f32(albedo, (3,))), C.c_float(g), _p(_f32(box_min, (3,))),
+                                             _p(_f32(box_max, (3,)))), "dmt_set_medium")
+
+    def clear_medium(self):
+        """dmt_clear_medium: every film is then byte for byte what it was without a medium."""
+        self._check(self._lib.dmt_clear_medium(self._ctx), "dmt_clear_medium")
+
+    def medium_info(self):
+        """dmt_medium_info -> dict(active, sigma_t, albedo, g, box_min, box_max): the record as it was set."""
+        act, st, g = C.c_int(), C.c_float(), C.c_float()
+        a, lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._check(self._lib.dmt_medium_info(self._ctx, C.byref(act), C.byref(st), _p(a), C.byref(g), _p(lo), _p(hi)), "dmt_medium_info")
+        return dict(active=bool(act.value), sigma_t=st.value, albedo=a, g=g.value, box_min=lo, box_max=hi)
+
+    def test_medium(self, sigma_t, g, box_min, box_max, o, d, t_hit, h, depth, cosine, u):
+        """dmt_test_medium: the device versions of the medium's arithmetic over n cases -> dict(seg [n, 2], hit [n] bool,
+        u [n], flight [n], transmittance [n], eval [n], wi [n, 3], pdf [n]); wi is sampled around wo = -d."""
+        o, d, u = _f32(o).reshape(-1, 3), _f32(d).reshape(-1, 3), _f32(u).reshape(-1, 2)
+        t, cosine, h, depth = _f32(t_hit).reshape(-1), _f32(cosine).reshape(-1), _u32(h), _u32(depth)
+        n = o.shape[0]
+        assert all(a.shape[0] == n for a in (d, u, t, cosine, h, depth))
+        seg, hit, val = np.zeros((n, 2), np.float32), np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+        ev, wi, pdf = np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        medium8 = np.concatenate([[sigma_t, g], _f32(box_min, (3,)), _f32(box_max, (3,))]).astype(np.float32)
+        self._check(self._lib.dmt_test_medium(self._ctx, _p(medium8), int(n),
+                                              _p(o), _p(d), _p(t), _p(h), _p(depth), _p(cosine), _p(u), _p(seg), _p(hit), _p(val), _p(ev),
+                                              _p(wi), _p(pdf)), "dmt_test_medium")
+        return dict(seg=seg, hit=hit.astype(bool), u=val[:, 0].copy(), flight=val[:, 1].copy(), transmittance=val[:, 2].copy(), eval=ev,
+                    wi=wi, pdf=pdf)
+
     def lens_info(self):
         """(lens_radius, focus_distance) of the context."""
         r, d = C.c_float(), C.c_float()
@@ -687,7 +774,8 @@ class Renderer:
 
     def upload_scene(self, scene, vertex_normals=False, opacity=True):
         """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays; a scene with a `lens`
-        (lens_radius, focus_distance), as the loaders report one, sets the context's lens too.  vertex_normals: also
+        (lens_radius, focus_distance), as the loaders report one, sets the context's lens too, and one with a `medium`
+        (the keyword arguments of set_medium) the context's medium.  vertex_normals: also
         upload the scene's `tri_normals` (smooth shading); off by default, the files' normals are not used unasked.
         opacity: upload the scene's `mat_opacity` / `opacity_cutoff` (alpha cutouts) when it carries them."""
         self.upload_triangles(scene.xs, scene.ys, scene.zs, scene.mat_id)
@@ -701,6 +789,8 @@ class Renderer:
         self.set_camera(scene.camera)
         if getattr(scene, "lens", None) is not None:
             self.set_lens(float(scene.lens[0]), float(scene.lens[1]))
+        if getattr(scene, "medium", None) is not None:  # a scene file's "medium"; a scene without one leaves the context's
+            self.set_medium(**scene.medium)
         if getattr(scene, "area_tri", None) is not None and len(scene.area_tri):
             self.upload_area_lights(scene.area_tri, scene.area_le)
         if getattr(scene, "env_rgb", None) is not None:

@@ -35,6 +35,7 @@
 
 #include "../../include/dmt_hip.h"
 #include "pt_device.hpp"
+#include "medium.hpp"
 #include "bvh_device.hpp"
 #include "bvh_gpu_build.hpp"
 #include "devbuf.hpp"
@@ -155,6 +156,9 @@ struct RenderParams {
   // that no other field moves
   uint32_t const* triKindBits;
   uint32_t triKindInline[2];
+  // the participating medium (dmt_set_medium; medium.hpp): sigmaT == 0 without one.  Read by the *_medium kernels only.
+  // After `triKindInline`, so that no other field moves
+  MediumParams medium;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -314,6 +318,7 @@ constexpr uint32_t kFeatTexFilter = 1u << 8;     // first-hit MIP / EWA texture 
 constexpr uint32_t kFeatMotion = 1u << 9;        // motion blur: triangles at the sample's time (motion.hpp); plain and env-map rows only
 constexpr uint32_t kFeatCutout = 1u << 11;       // alpha cutouts: candidate hits filtered by an opacity texture (opacity.hpp); the texture rows only
 constexpr uint32_t kFeatVtxNormals = 1u << 10;   // smooth shading: ns interpolated from per-vertex normals (vnormals.hpp); plain, env, tex rows
+constexpr uint32_t kFeatMedium = 1u << 12;       // participating medium: free flight and scatter vertices between two ray casts (medium_device.hpp); plain and env-map rows only
 
 // the post-hit record path_shade works on: the uploaded one, or under kFeatMotion the triangle at the sample's time
 template <uint32_t F>
@@ -321,6 +326,8 @@ DMT_DEV Hit shade_hit(KArgs k, SceneView const& sc, int tri, float bu, float bv,
   if constexpr (F & kFeatMotion) return hit_finish(motion_post(k, sc.post[tri], tri, motion_time()), bu, bv, rd);
   else return hit_finish(sc.post[tri], bu, bv, rd);
 }
+
+#include "medium_device.hpp"
 
 template <uint32_t F>
 DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv) {
@@ -330,8 +337,13 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
   static_assert(!(F & kFeatCutout) || ((F & kFeatTex) && !(F & ~(kFeatCutout | kFeatBvh | kFeatEnv | kFeatTex))), "cutouts: the texture rows only");
   static_assert(!(F & kFeatVtxNormals) || !(F & ~(kFeatVtxNormals | kFeatBvh | kFeatEnv | kFeatTex)), "vertex normals: the plain, env-map and texture rows only");
+  static_assert(!(F & kFeatMedium) || !(F & ~(kFeatMedium | kFeatBvh | kFeatEnv)), "medium: the plain and env-map rows only");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
+  if constexpr (F & kFeatMedium) {  // a collision inside the box replaces the surface hit or the miss
+    int const mv = medium_vertex<F>(k, st, sc, bestTri, bu, bv);
+    if (mv != MV_THROUGH) return mv == MV_ENDED;
+  }
   if constexpr (F & kFeatEnv) {
     if (bestTri < 0) {  // A18: the env map seen by a path ray, MIS against NEE (core-render.cpp:154-163)
       EnvView const env = load_env(k);
@@ -577,6 +589,9 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
     }
   }
 
+  if constexpr (F & kFeatMedium) {  // the NEE just left pending, times the transmittance of its shadow segment
+    if (st.hasShadow) medium_attenuate_pending(k, st);
+  }
   // bounce (:247-295); get2D before get1D = left-to-right argument evaluation
   sect_mark(7);
   f2 const u2 = st.rng.get2D();
@@ -1565,6 +1580,9 @@ DMT_DEV void megakernel_body_bvh() {
 // them within their parents' scratch.
 // _cut: the parent _tex row's body with the cutout trace, one wave per SIMD fewer than the parent: at the parents' bounds
 // (where the parents themselves spill) the rows would spill VGPRs; at these they do not.
+// _medium: the static twin's body with the medium's code in path_shade.  _bvh_medium and _bvh_env_medium keep their twins'
+// bounds; _medium and _env_medium run one wave per SIMD fewer than theirs: at four they spill 8 and 15 VGPRs (36 and 48
+// bytes of scratch, where k_megakernel has none).
 #define DMT_MEGAKERNELS(X)                                                          \
   X(, 0, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                                   \
   X(_bvh, kFeatBvh, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh)                \
@@ -1613,7 +1631,11 @@ DMT_DEV void megakernel_body_bvh() {
   X(_tex_cut, kFeatTex | kFeatCutout, 3, megakernel_body)                           \
   X(_bvh_tex_cut, kFeatBvh | kFeatTex | kFeatCutout, 2, megakernel_body_bvh)        \
   X(_env_tex_cut, kFeatEnv | kFeatTex | kFeatCutout, 3, megakernel_body)            \
-  X(_bvh_env_tex_cut, kFeatBvh | kFeatEnv | kFeatTex | kFeatCutout, 2, megakernel_body_bvh)
+  X(_bvh_env_tex_cut, kFeatBvh | kFeatEnv | kFeatTex | kFeatCutout, 2, megakernel_body_bvh) \
+  X(_medium, kFeatMedium, 3, megakernel_body)                                       \
+  X(_bvh_medium, kFeatBvh | kFeatMedium, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh) \
+  X(_env_medium, kFeatEnv | kFeatMedium, 3, megakernel_body)                        \
+  X(_bvh_env_medium, kFeatBvh | kFeatEnv | kFeatMedium, 3, megakernel_body_bvh)
 // the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
 // algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
 #define DMT_STATS_MEGAKERNELS(X)                                                    \
@@ -2008,6 +2030,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (c->ac.haveMotion) F |= kFeatMotion;
   if (c->surf.vn.have) F |= kFeatVtxNormals;
   if (c->surf.op.have) F |= kFeatCutout;
+  if (c->launch.medium.active()) F |= kFeatMedium;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2022,6 +2045,17 @@ int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
 }
 // the combinations dmt_render refuses (mask | kFeatStats for dmt_render_stats / dmt_render_profile)
 int checkFeatures(dmt_ctx* ctx, uint32_t F) {
+  if (F & kFeatMedium) {  // the medium has the plain and env-map megakernel rows
+    if (F & kFeatStats) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: a participating medium (dmt_set_medium) has no counting kernels");
+    if (F & kFeatArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with emissive triangles is not supported");
+    if (F & kFeatCutout) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with opacity textures is not supported");
+    if (F & kFeatTexFilter) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with the first-hit texture filter is not supported");
+    if (F & (kFeatTex | kFeatBlend)) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with image textures or blend materials is not supported");
+    if (F & (kFeatLightTree | kFeatLightTreeRef)) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with a light tree is not supported");
+    if (F & kFeatMotion) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with motion blur is not supported");
+    if (F & kFeatVtxNormals) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with vertex normals is not supported");
+    if ((F & kFeatBvh) && ctx->launch.wf.strategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with the wavefront BVH strategy is not supported");
+  }
   if (F & kFeatCutout) {  // alpha cutouts have the four texture megakernel rows; the rest is refused as for those rows
     if (F & kFeatBlend) return fail(ctx, DMT_ERR_STATE, "dmt_render: opacity textures (dmt_upload_opacity) together with blend materials are not supported");
     if (F & kFeatTexFilter) return fail(ctx, DMT_ERR_STATE, "dmt_render: opacity textures (dmt_upload_opacity) together with the first-hit texture filter are not supported");
@@ -2098,6 +2132,7 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   P.env = c->env;
+  if (c->launch.medium.active()) P.medium = c->launch.medium.p;
   c->surf.fill(P);
   uint32_t const F = featuresOf(c);
   if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree.get();

@@ -83,6 +83,16 @@ __shared__ uint32_t s_pixmap[2 * kLdsThreads];       // per slot: j-th pixel ins
 
 constexpr uint32_t kSlotBit = 0x80000000u;  // staging index = slot bit | (sample * 64 + pixel)
 constexpr uint32_t kFoldReady = 0xFFFFFFFFu;  // link word: the tile's previous chunk is in the film
+// The Halton index of the sample a lane is tracing (the *_medium rows: medium_device.hpp), from its staging index alone:
+// slot, sample k of the chunk and pixel name the chunk's first sample (s_desc word 4) and the pixel's base index
+// (s_pixbase), both of which outlive every sample of their item.  No state of its own: the brute-force rows have 32 bytes
+// of LDS left per block at four blocks per CU.
+DMT_DEV uint32_t medium_h(KArgs k, PathState const& st) {
+  uint32_t const slot = st.sidx >> 31, ks = (st.sidx & ~kSlotBit) >> 6, pixel = st.sidx & 63u;
+  k = kargs(k);
+  int32_t const base = s_pixbase[slot * kLdsThreads + (threadIdx.x & ~63u) + pixel];
+  return uint32_t(base + int32_t(s_desc[threadIdx.x >> 6][slot][4] + ks) * (k->sp.scale0 * k->sp.scale1));
+}
 #ifndef DMT_SLAB_WAIT_MS
 #define DMT_SLAB_WAIT_MS 250  // a wave without a live item and without a free slab polls this long, then exits
 #endif

@@ -543,6 +543,75 @@ int dmt_set_partition(dmt_ctx* ctx, int rank, int world) {
   return DMT_OK;
 }
 
+// ---- the participating medium (medium.hpp) ----------------------------------------
+static char const* mediumArgsError(float sigma_t, const float* albedo3, float g, const float* box_min3, const float* box_max3) {
+  if (!albedo3 || !box_min3 || !box_max3) return "null argument";
+  if (!std::isfinite(sigma_t) || sigma_t < 0.f) return "sigma_t must be finite and >= 0";
+  for (int i = 0; i < 3; ++i)
+    if (!(albedo3[i] >= 0.f && albedo3[i] <= 1.f)) return "the albedo must be in [0, 1] per channel";
+  if (!(std::fabs(g) < 1.f)) return "g must be in (-1, 1)";
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(box_min3[i]) || !std::isfinite(box_max3[i]) || !(box_min3[i] < box_max3[i])) return "the box must be finite with min < max on every axis";
+  return nullptr;
+}
+
+int dmt_set_medium(dmt_ctx* ctx, float sigma_t, const float* albedo3, float g, const float* box_min3, const float* box_max3) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (char const* const why = mediumArgsError(sigma_t, albedo3, g, box_min3, box_max3))
+    return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_set_medium: ") + why).c_str());
+  MediumParams& m = ctx->launch.medium.p;  // (a launch in flight holds its own copy in its kernel arguments)
+  m.sigmaT = sigma_t, m.g = g;
+  for (int i = 0; i < 3; ++i) m.albedo[i] = albedo3[i], m.lo[i] = box_min3[i], m.hi[i] = box_max3[i];
+  return DMT_OK;
+}
+
+int dmt_clear_medium(dmt_ctx* ctx) {
+  if (!ctx) return DMT_ERR_INVALID;
+  ctx->launch.medium.p = MediumParams{};
+  return DMT_OK;
+}
+
+int dmt_medium_info(dmt_ctx* ctx, int* active, float* sigma_t, float* albedo3, float* g, float* box_min3, float* box_max3) {
+  if (!ctx) return DMT_ERR_INVALID;
+  MediumParams const& m = ctx->launch.medium.p;
+  if (active) *active = ctx->launch.medium.active() ? 1 : 0;
+  if (sigma_t) *sigma_t = m.sigmaT;
+  if (g) *g = m.g;
+  for (int i = 0; i < 3; ++i) {
+    if (albedo3) albedo3[i] = m.albedo[i];
+    if (box_min3) box_min3[i] = m.lo[i];
+    if (box_max3) box_max3[i] = m.hi[i];
+  }
+  return DMT_OK;
+}
+
+int dmt_medium_segment(const float* box_min3, const float* box_max3, int n, const float* o3, const float* d3, const float* t_hit, float* seg2,
+                       int32_t* hit) {
+  if (!box_min3 || !box_max3 || n < 0 || !o3 || !d3 || !t_hit || !seg2 || !hit) return DMT_ERR_INVALID;
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(box_min3[i]) || !std::isfinite(box_max3[i]) || !(box_min3[i] < box_max3[i])) return DMT_ERR_INVALID;
+  for (int i = 0; i < n; ++i) hit[i] = medium_segment(o3 + 3 * i, d3 + 3 * i, t_hit[i], box_min3, box_max3, seg2 + 2 * i, seg2 + 2 * i + 1) ? 1 : 0;
+  return DMT_OK;
+}
+
+int dmt_medium_values(int n, const uint32_t* h, const uint32_t* depth, float* u) {
+  if (n < 0 || !h || !depth || !u) return DMT_ERR_INVALID;
+  for (int i = 0; i < n; ++i) u[i] = medium_u(h[i], depth[i]);
+  return DMT_OK;
+}
+
+int dmt_phase_hg(float g, int n, const float* cosine, float* eval, const float* wo3, const float* u2, float* wi3, float* pdf) {
+  if (n < 0 || !(std::fabs(g) < 1.f)) return DMT_ERR_INVALID;
+  if ((cosine != nullptr) != (eval != nullptr)) return DMT_ERR_INVALID;
+  bool const sample = wo3 || u2 || wi3 || pdf;
+  if (sample && !(wo3 && u2 && wi3 && pdf)) return DMT_ERR_INVALID;
+  for (int i = 0; i < n; ++i) {
+    if (eval) eval[i] = hg_eval(g, cosine[i]);
+    if (sample) hg_sample(g, wo3 + 3 * i, u2[2 * i], u2[2 * i + 1], wi3 + 3 * i, pdf + i);
+  }
+  return DMT_OK;
+}
+
 int dmt_kernel_time(dmt_ctx* ctx, double* total_ms, uint64_t* launches, int reset) {
   if (!ctx) return DMT_ERR_INVALID;
   HIP_TRY(ctx, hipSetDevice(ctx->device));

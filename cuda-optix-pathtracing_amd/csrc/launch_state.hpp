@@ -36,6 +36,13 @@
 //   subShift                  --                      DMT_SUB_SHIFT (< 0 automatic; at most 2)
 //   chunkSpp                  dmt_set_chunk           --
 //   rank, world               dmt_set_partition       --
+//   medium                    dmt_set_medium,         --
+//                             dmt_clear_medium
+//
+// The medium (medium.hpp) is per context and belongs to no upload: dmt_upload_triangles, dmt_update_vertices*, the other
+// scene uploads and dmt_set_camera leave it as it is, and so does a refused call.  It is active exactly when its sigmaT > 0;
+// a record with sigmaT == 0 (dmt_set_medium with 0, dmt_clear_medium, a new context) selects the kernels a context without
+// a medium launches.
 //
 // dmt_sched_diag(reset) zeroes sched.diag (the GGX batching words with it) and with it sched.expectedFolds and
 // ggx.lostReported, the host's two views of those words; nothing else.  dmt_kernel_time folds the used event pairs into
@@ -126,6 +133,11 @@ struct LaunchState {
     double ms = 0.0;
     uint64_t launches = 0;
   } timing;
+  // the participating medium of the context (dmt_set_medium): what the *_medium rows read as RenderParams::medium
+  struct Medium {
+    MediumParams p{};
+    bool active() const { return p.sigmaT > 0.f; }
+  } medium;
   // the shape of a launch
   uint32_t chunkSpp = 0;                    // samples per work item, 0 = automatic
   int subShift = -1;                        // row bands per tile (log2); -1 = choose per launch

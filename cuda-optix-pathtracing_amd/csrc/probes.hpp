@@ -25,6 +25,11 @@ __global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t 
     ColdArgs const c = load_cold_args(k);
     path_begin(st, c.cam, c.sp, pxs[i], pys[i], halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i]), kargs(k)->lensR, kargs(k)->lensD);
     if constexpr (F & kFeatMotion) motion_set_time(motion_sample_time(k, halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i])));
+    if constexpr (F & kFeatMedium) {  // medium_h: the lane's sample is sample 0 of "pixel" lane of slot 0, whose base is the sample's own index
+      st.sidx = threadIdx.x & 63u;
+      s_pixbase[threadIdx.x] = halton_pixel_base(c.sp, pxs[i], pys[i]) + ss[i] * (c.sp.scale0 * c.sp.scale1);
+      s_desc[threadIdx.x >> 6][0][4] = 0u;
+    }
   }
   auto store = [&](f3 L, uint32_t) { L3[3 * i] = L.x, L3[3 * i + 1] = L.y, L3[3 * i + 2] = L.z; };
   uint32_t const gtid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -406,6 +411,21 @@ __global__ void k_test_shutter(SamplerParams sp, float open, float close, int n,
   if (i >= n) return;
   int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * (sp.scale0 * sp.scale1);
   t[i] = shutter_time(uint32_t(h), open, close);
+}
+
+// dmt_test_medium: the device versions of what the *_medium rows compute between two ray casts
+__global__ void k_test_medium(MediumParams m, int n, float const* o3, float const* d3, float const* tHit, uint32_t const* h, uint32_t const* depth,
+                              float const* cosine, float const* u2, float* seg2, int32_t* hit, float* values3, float* eval, float* wi3, float* pdf) {
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  float t0, t1;
+  bool const ok = medium_segment(o3 + 3 * i, d3 + 3 * i, tHit[i], m.lo, m.hi, &t0, &t1);
+  seg2[2 * i] = t0, seg2[2 * i + 1] = t1, hit[i] = ok ? 1 : 0;
+  float const u = medium_u(h[i], depth[i]);
+  values3[3 * i] = u, values3[3 * i + 1] = medium_free_flight(m.sigmaT, u), values3[3 * i + 2] = medium_transmittance(m.sigmaT, ok ? t1 - t0 : 0.f);
+  eval[i] = hg_eval(m.g, cosine[i]);
+  float const wo[3] = {-d3[3 * i], -d3[3 * i + 1], -d3[3 * i + 2]};
+  hg_sample(m.g, wo, u2[2 * i], u2[2 * i + 1], wi3 + 3 * i, pdf + i);
 }
 
 // dmt_camera_project (project_point) on the device
@@ -796,6 +816,28 @@ int dmt_test_closest_hit_opacity(dmt_ctx* ctx, int nrays, const float* o3, const
   }
   hipLaunchKernelGGL(k_test_closest_cut, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), useBvh, nrays, dO.get(),
                      dD.get(), dM.get(), di.get(), dt.get(), duv.get(), docc.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_medium(dmt_ctx* ctx, const float* medium8, int n, const float* o3, const float* d3, const float* t_hit, const uint32_t* h, const uint32_t* depth, const float* cosine, const float* u2, float* seg2, int32_t* hit,
+                    float* values3, float* eval, float* wi3, float* pdf) {
+  if (!ctx || !medium8 || n < 0 || !o3 || !d3 || !t_hit || !h || !depth || !cosine || !u2 || !seg2 || !hit || !values3 || !eval || !wi3 || !pdf) return DMT_ERR_INVALID;
+  float const sigma_t = medium8[0], g = medium8[1], *const box_min3 = medium8 + 2, *const box_max3 = medium8 + 5;
+  float const white[3] = {1.f, 1.f, 1.f};
+  if (char const* const why = mediumArgsError(sigma_t, white, g, box_min3, box_max3)) return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_test_medium: ") + why).c_str());
+  if (!(sigma_t > 0.f)) return fail(ctx, DMT_ERR_INVALID, "dmt_test_medium: sigma_t must be > 0 (the free-flight distance divides by it)");
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3), dT(p, t_hit, 1), dC(p, cosine, 1), dU(p, u2, 2);
+  ProbeIn<uint32_t> dH(p, h, 1), dDepth(p, depth, 1);
+  ProbeOut<float> dSeg(p, seg2, 2), dVal(p, values3, 3), dEval(p, eval, 1), dWi(p, wi3, 3), dPdf(p, pdf, 1);
+  ProbeOut<int32_t> dHit(p, hit, 1);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  MediumParams m{};
+  m.sigmaT = sigma_t, m.g = g;
+  for (int i = 0; i < 3; ++i) m.albedo[i] = 1.f, m.lo[i] = box_min3[i], m.hi[i] = box_max3[i];
+  hipLaunchKernelGGL(k_test_medium, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, m, n, dO.get(), dD.get(), dT.get(), dH.get(), dDepth.get(), dC.get(),
+                     dU.get(), dSeg.get(), dHit.get(), dVal.get(), dEval.get(), dWi.get(), dPdf.get());
   return finishProbe(ctx, p);
 }
 

@@ -143,6 +143,13 @@ dmt_camera* dmt_host_scene_camera(dmt_host_scene* h) { return &h->s.camera; }
 void dmt_host_scene_lens(const dmt_host_scene* h, float* lens_radius, float* focus_distance) {
   *lens_radius = h->s.lensRadius, *focus_distance = h->s.focusDistance;
 }
+// the scene's participating medium: 1 and the record (sigma_t, albedo3, g, min3, max3 -> out11), or 0 without one
+int dmt_host_scene_medium(const dmt_host_scene* h, float* out11) {
+  if (!h->s.hasMedium) return 0;
+  out11[0] = h->s.mediumSigmaT, out11[4] = h->s.mediumG;
+  for (int i = 0; i < 3; ++i) out11[1 + i] = h->s.mediumAlbedo[i], out11[5 + i] = h->s.mediumMin[i], out11[8 + i] = h->s.mediumMax[i];
+  return 1;
+}
 void dmt_host_scene_set_resolution(dmt_host_scene* h, int width, int height) {
   h->s.camera.width = width, h->s.camera.height = height;
 }

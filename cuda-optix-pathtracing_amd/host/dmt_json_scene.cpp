@@ -631,6 +631,44 @@ bool readPngRgb(std::string const& path, std::vector<float>& rgb, int& width, in
   return true;
 }
 
+// beyond the reference's parser: the optional top-level "medium", homogeneous fog in an axis-aligned box (dmt_set_medium):
+// {"sigma_t": number >= 0, "albedo": [r, g, b] in [0, 1], "g": number in (-1, 1), "min": [x, y, z], "max": [x, y, z]};
+// "sigma_t", "min" and "max" are required, "albedo" defaults to white and "g" to 0
+void parseMedium(Value const& m, Scene& scene) {
+  if (!m.isObject()) fail("'medium' should be an object");
+  static char const* const keys[] = {"sigma_t", "albedo", "g", "min", "max"};
+  for (auto const& kv : m.object) {
+    bool known = false;
+    for (char const* k : keys) known = known || kv.first == k;
+    if (!known) fail("'medium' has extraneous key '" + kv.first + "'");
+  }
+  auto number = [&](char const* k, float& out) {
+    if (!m.at(k).isNumber() || !std::isfinite(float(m.at(k).number))) fail(std::string("medium '") + k + "' should be a finite number");
+    out = float(m.at(k).number);
+  };
+  auto triple = [&](char const* k, float* out) {
+    Value const& a = m.at(k);
+    if (!a.isArray() || a.array.size() != 3) fail(std::string("medium '") + k + "' should be an array of three numbers");
+    for (size_t i = 0; i < 3; ++i) {
+      if (!a.array[i].isNumber() || !std::isfinite(float(a.array[i].number))) fail(std::string("medium '") + k + "' should be an array of three numbers");
+      out[i] = float(a.array[i].number);
+    }
+  };
+  for (char const* k : {"sigma_t", "min", "max"})
+    if (!m.contains(k)) fail(std::string("'medium' is lacking '") + k + "'");
+  number("sigma_t", scene.mediumSigmaT);
+  if (scene.mediumSigmaT < 0.f) fail("medium 'sigma_t' should be >= 0");
+  if (m.contains("g")) number("g", scene.mediumG);
+  if (!(std::fabs(scene.mediumG) < 1.f)) fail("medium 'g' should be in (-1, 1)");
+  if (m.contains("albedo")) triple("albedo", scene.mediumAlbedo);
+  for (float a : scene.mediumAlbedo)
+    if (!(a >= 0.f && a <= 1.f)) fail("medium 'albedo' should be in [0, 1] per channel");
+  triple("min", scene.mediumMin), triple("max", scene.mediumMax);
+  for (int i = 0; i < 3; ++i)
+    if (!(scene.mediumMin[i] < scene.mediumMax[i])) fail("medium 'min' should be below 'max' on every axis");
+  scene.hasMedium = true;
+}
+
 bool loadJsonScene(std::string const& path, JsonScene& out, std::string* error) {
   try {
     std::ifstream f(path);
@@ -648,7 +686,7 @@ bool loadJsonScene(std::string const& path, JsonScene& out, std::string* error) 
     for (auto const& kv : data.object) {
       bool known = false;
       for (char const* k : keys) known = known || kv.first == k;
-      if (!known) fail("JSON value has extraneous key '" + kv.first + "'");
+      if (!known && kv.first != "medium") fail("JSON value has extraneous key '" + kv.first + "'");  // ("medium": optional)
     }
     out = JsonScene{};
     State st;
@@ -710,6 +748,7 @@ bool loadJsonScene(std::string const& path, JsonScene& out, std::string* error) 
       for (Material const& m : st.materialList)
         for (int r = 0; r < m.records(); ++r) out.scene.matOpacity.push_back(uint32_t(m.opacityTex));
     if (std::all_of(out.scene.triNormals.begin(), out.scene.triNormals.end(), [](float v) { return v == 0.f; })) out.scene.triNormals.clear();
+    if (data.contains("medium")) parseMedium(data.at("medium"), out.scene);
     return true;
   } catch (Fail const& e) {
     if (error) *error = e.msg;

@@ -411,6 +411,8 @@ int uploadScene(dmt_ctx* ctx, Scene const& s) {
   if (rc) return rc;
   rc = dmt_set_lens(ctx, s.lensRadius, s.focusDistance);
   if (rc) return rc;
+  rc = s.hasMedium ? dmt_set_medium(ctx, s.mediumSigmaT, s.mediumAlbedo, s.mediumG, s.mediumMin, s.mediumMax) : dmt_clear_medium(ctx);
+  if (rc) return rc;
   rc = dmt_upload_area_lights(ctx, s.areaTri.data(), s.areaLe.data(), uint32_t(s.areaTri.size()));
   if (rc) return rc;
   rc = s.envRgb.empty() ? dmt_clear_envmap(ctx) : dmt_upload_envmap(ctx, s.envRgb.data(), s.envWidth, s.envHeight, s.envQuat, s.envScale);

@@ -89,6 +89,12 @@ struct Scene {
   // uploads them after the textures.
   std::vector<uint32_t> matOpacity;
   float opacityCutoff = 0.5f;
+  // optional participating medium (dmt_set_medium; the JSON front-end's top-level "medium", main.cpp --medium): homogeneous
+  // fog of extinction mediumSigmaT > 0 inside the box.  uploadScene sets it, or clears the context's when the scene has none.
+  bool hasMedium = false;
+  float mediumSigmaT = 0.f, mediumG = 0.f;
+  float mediumAlbedo[3] = {1.f, 1.f, 1.f};
+  float mediumMin[3] = {0.f, 0.f, 0.f}, mediumMax[3] = {0.f, 0.f, 0.f};
 
   size_t triangleCount() const { return matId.size(); }
   // addModel + the material walk of triSoupFromTriangles: the FIRST mesh always gets material 0

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -57,6 +58,9 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   std::string shadingNormals = "off";  // --shading-normals off|file|smooth[:DEG] (dmt_upload_vertex_normals)
   float creaseDegrees = 180.f;         // parsed from shadingNormals by validate()
   std::string cutouts = "on";  // --cutouts on|off: upload the scene's opacity textures (dmt_upload_opacity), or ignore them
+  // --medium SIGMA_T [--medium-albedo R G B] [--medium-g G] [--medium-box X0 Y0 Z0 X1 Y1 Z1]: homogeneous fog (dmt_set_medium)
+  bool mediumSet = false, mediumAlbedoSet = false, mediumGSet = false, mediumBoxSet = false;
+  float mediumSigmaT = 0.f, mediumG = 0.f, mediumAlbedo[3] = {1.f, 1.f, 1.f}, mediumBox[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
 
@@ -113,6 +117,16 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
       return "invalid --shading-normals: expected off, file, smooth or smooth:DEG (0 <= DEG <= 180), got '" + shadingNormals + "'";
     if (shadingNormals != "off" && !motionScenePath.empty()) return "--shading-normals and --motion-scene exclude each other";
     if (cutouts != "on" && cutouts != "off") return "invalid --cutouts: expected on or off, got '" + cutouts + "'";
+    if ((mediumAlbedoSet || mediumGSet || mediumBoxSet) && !mediumSet) return "--medium-albedo, --medium-g and --medium-box need --medium";
+    if (mediumSet && !(std::isfinite(mediumSigmaT) && mediumSigmaT >= 0.f)) return "invalid --medium: expected a finite extinction coefficient >= 0";
+    if (mediumAlbedoSet && !(mediumAlbedo[0] >= 0.f && mediumAlbedo[0] <= 1.f && mediumAlbedo[1] >= 0.f && mediumAlbedo[1] <= 1.f && mediumAlbedo[2] >= 0.f && mediumAlbedo[2] <= 1.f))
+      return "invalid --medium-albedo: expected three numbers in [0, 1]";
+    if (mediumGSet && !(std::fabs(mediumG) < 1.f)) return "invalid --medium-g: expected a number in (-1, 1)";
+    if (mediumBoxSet)
+      for (int i = 0; i < 3; ++i)
+        if (!(std::isfinite(mediumBox[i]) && std::isfinite(mediumBox[3 + i]) && mediumBox[i] < mediumBox[3 + i]))
+          return "invalid --medium-box: expected finite X0 Y0 Z0 X1 Y1 Z1 with X0 < X1, Y0 < Y1, Z0 < Z1";
+    if (mediumSet && mediumSigmaT > 0.f && denoise) return "--medium and --denoise exclude each other (the feature buffers do not know the fog)";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
   }
@@ -167,7 +181,13 @@ void printHelp() {
       "  --cutouts <on|off> -- Alpha cutouts: a material's \"opacity\" texture decides at every hit whether the hit counts (A\n"
       "                       channel >= the material's \"opacity-cutoff\", default 0.5), for camera, bounce and shadow rays.\n"
       "                       on (the default): as the scene says; scenes without opacity textures are unaffected.  off:\n"
-      "                       ignore them, every triangle is solid");
+      "                       ignore them, every triangle is solid\n"
+      "  --medium <SIGMA_T> -- Participating medium: homogeneous fog of extinction SIGMA_T per scene unit (0: none), sampled\n"
+      "                       in-path: light shafts, glow and depth cueing from the scene's own lights.  Overrides the scene\n"
+      "                       file's \"medium\"\n"
+      "  --medium-albedo <R> <G> <B> -- Its single-scattering albedo per channel, in [0, 1] (default 1 1 1)\n"
+      "  --medium-g <G>    -- Its Henyey-Greenstein asymmetry, in (-1, 1): 0 isotropic (the default), > 0 forward\n"
+      "  --medium-box <X0> <Y0> <Z0> <X1> <Y1> <Z1> -- The box that holds it (default: the bounds of the scene's triangles)");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -196,6 +216,15 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--motion-scene" && more) c.motionScenePath = argv[++i];
     else if (a == "--shading-normals" && more) c.shadingNormals = argv[++i];
     else if (a == "--cutouts" && more) c.cutouts = argv[++i];
+    else if (a == "--medium" && more) c.mediumSigmaT = std::strtof(argv[++i], nullptr), c.mediumSet = true;
+    else if (a == "--medium-g" && more) c.mediumG = std::strtof(argv[++i], nullptr), c.mediumGSet = true;
+    else if (a == "--medium-albedo" && i + 3 < argc) {
+      for (float& v : c.mediumAlbedo) v = std::strtof(argv[++i], nullptr);
+      c.mediumAlbedoSet = true;
+    } else if (a == "--medium-box" && i + 6 < argc) {
+      for (float& v : c.mediumBox) v = std::strtof(argv[++i], nullptr);
+      c.mediumBoxSet = true;
+    }
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -309,6 +338,28 @@ int main(int argc, char** argv) {
   if (cfg.textureFilter) scene.camera.spp = cfg.spp;  // the filter's footprint scale follows the frame's samples per pixel
   if (cfg.lensRadiusSet) scene.lensRadius = cfg.lensRadius;
   if (cfg.focusDistanceSet) scene.focusDistance = cfg.focusDistance;
+  if (cfg.mediumSet) {  // --medium replaces the scene file's medium; the default box is the bounds of the triangles
+    scene.hasMedium = cfg.mediumSigmaT > 0.f, scene.mediumSigmaT = cfg.mediumSigmaT, scene.mediumG = cfg.mediumG;
+    for (int i = 0; i < 3; ++i) scene.mediumAlbedo[i] = cfg.mediumAlbedo[i];
+    for (int i = 0; i < 3 && cfg.mediumBoxSet; ++i) scene.mediumMin[i] = cfg.mediumBox[i], scene.mediumMax[i] = cfg.mediumBox[3 + i];
+    if (!cfg.mediumBoxSet) {
+      std::vector<float> const* const axes[3] = {&scene.xs, &scene.ys, &scene.zs};
+      for (int a = 0; a < 3; ++a) {
+        float lo = std::numeric_limits<float>::infinity(), hi = -lo;
+        for (size_t t = 0; t < scene.triangleCount(); ++t)
+          for (size_t c = 0; c < 3; ++c) lo = std::min(lo, (*axes[a])[4 * t + c]), hi = std::max(hi, (*axes[a])[4 * t + c]);
+        scene.mediumMin[a] = lo, scene.mediumMax[a] = hi;
+        if (scene.hasMedium && !(lo < hi)) {
+          std::fprintf(stderr, "--medium: the scene's triangles span no volume; give --medium-box\n");
+          return 1;
+        }
+      }
+    }
+  }
+  if (scene.hasMedium && scene.mediumSigmaT > 0.f && cfg.denoise) {
+    std::fprintf(stderr, "the scene's medium and --denoise exclude each other (the feature buffers do not know the fog)\n");
+    return 1;
+  }
   if (cfg.cutouts == "off") scene.matOpacity.clear();  // --cutouts off: uploadScene then uploads no opacity
   std::vector<float> vertexNormals;  // --shading-normals: 9 floats per triangle for dmt_upload_vertex_normals
   if (cfg.shadingNormals == "file") {

@@ -64,6 +64,11 @@ class HostScene:
         lr, fd = C.c_float(), C.c_float()
         L.dmt_host_scene_lens(h, C.byref(lr), C.byref(fd))
         self.lens = (lr.value, fd.value)  # thin lens beside the camera record: (radius, focus distance); radius 0 = pinhole
+        m11 = np.zeros(11, np.float32)
+        L.dmt_host_scene_medium.restype = C.c_int
+        # participating medium (the JSON front-end's "medium"): dict(sigma_t, albedo, g, box_min, box_max), or None
+        self.medium = (dict(sigma_t=float(m11[0]), albedo=m11[1:4].copy(), g=float(m11[4]), box_min=m11[5:8].copy(), box_max=m11[8:11].copy())
+                       if L.dmt_host_scene_medium(h, m11.ctypes.data_as(C.c_void_p)) else None)
         ew, eh = C.c_int(), C.c_int()
         env = L.dmt_host_scene_env_rgb(h, C.byref(ew), C.byref(eh))
         self.env_rgb = _copy(env, np.float32, 3 * ew.value * eh.value).reshape(eh.value, ew.value, 3) if env else None

@@ -265,6 +265,56 @@ int dmt_opacity_info(dmt_ctx* ctx, uint64_t* cutout_triangles, uint32_t* cutout_
  * dmt_upload_opacity would refuse. */
 int dmt_opacity_eval(const uint8_t* rgba8, uint64_t texel_count, const int32_t* desc3, uint32_t texture_count, int n, const int32_t* tex,
                      const float* uv6, const float* bu, const float* bv, float cutoff, float* alpha8_out, uint8_t* pass_out);
+/* ---- participating medium: homogeneous fog in a box, sampled in-path (opt-in, beyond the reference) ---- */
+/* The medium.  One per context: a grey extinction coefficient sigma_t >= 0 per scene unit, a single-scattering albedo in
+ * [0, 1] per channel, the Henyey-Greenstein asymmetry g with |g| < 1, and a finite axis-aligned box min < max.  It is active
+ * exactly when it has been set with sigma_t > 0: dmt_set_medium with sigma_t == 0 and dmt_clear_medium both leave the
+ * context on the kernels it launches without these calls, and every film is then byte for byte what it was.  The medium
+ * belongs to no upload: scene uploads, vertex updates and dmt_set_camera leave it as it is.
+ *
+ * Per path segment, origin o, unit direction d, ending at t_hit = dot(hit.pos - o, d), +inf on a miss:
+ *   [t0, t1] = the clip of the ray against the box, intersected with [0, t_hit] (dmt_medium_segment states the arithmetic);
+ *   empty (not t0 < t1): nothing changes for the segment.  Otherwise
+ *   s = -log1p(-u) / sigma_t with u = medium_u(h, depth), a hash of the sample's Halton index h and the path's depth:
+ *       x = mix_bits32(h ^ mix_bits32(0x9E3779B9 * (depth + 1))), u = (x >> 8) * 2^-24 in [0, 1)  (the sampler's mix_bits32);
+ *   t0 + s < t1: the path scatters at p = o + (t0 + s) d instead of reaching the surface or the miss; otherwise it goes on
+ *   with beta untouched and the sampler's dimensions unmoved -- the chance of getting through is the transmittance, which
+ *   is why emission seen through the fog needs no factor and the MIS weights stand as they are.
+ * A scatter vertex ends the path at depth >= max_depth or with an all-zero albedo.  Otherwise it draws what a surface
+ * bounce draws, in its order (1 + 2 numbers for the light, 2 + 1 for the bounce, the roulette number under the surface's
+ * condition).  NEE: the light is chosen as at a surface (uniform pick; half env map in the env rows), sampled as from a point
+ * without a normal, f = albedo p_HG(dot(wo, wi)) with material pdf p_HG and no cosine, combined with the light's pdf by the
+ * surface code's expressions; the shadow ray starts at p itself.  Bounce: wi by pbrt's HG inversion (isotropic below
+ * |g| = 1e-3), beta *= albedo, then roulette and depth + 1 as at a surface.  wo = -d, and
+ *   p_HG(c) = (1 - g^2) / (4 pi (1 + g^2 + 2 g c)^1.5),   c = dot(wo, wi) = -1 straight on.
+ * Every NEE contribution of a medium launch, made at a surface or at a scatter vertex, is multiplied by
+ * exp(-sigma_t len), len = the length of its shadow segment inside the box (the same clip with t_hit = the ray's length).
+ *
+ * Scope.  The medium has the plain and the env-map megakernel rows under both accel modes, whose films agree bit for bit:
+ * dmt_render (partitions, chunks, the sampler table, a lens), dmt_render_adaptive, dmt_test_trace_samples.  Refused with
+ * DMT_ERR_STATE and a message that names the combination: the medium with emissive triangles, with image textures or blend
+ * materials, with either light tree, with the first-hit texture filter, with motion blur, with vertex normals, with
+ * opacity textures, with the wavefront BVH strategy, with dmt_render_stats / dmt_render_profile, and dmt_render_aovs /
+ * dmt_test_trace_log (the feature pass and the path log know surfaces only). */
+/* DMT_ERR_INVALID for sigma_t negative or not finite, an albedo outside [0, 1], |g| >= 1, or a box that is not finite or
+ * has min >= max on an axis; a refused call leaves the medium as it was.  Takes effect with the next launch. */
+int dmt_set_medium(dmt_ctx* ctx, float sigma_t, const float* albedo3, float g, const float* box_min3, const float* box_max3);
+int dmt_clear_medium(dmt_ctx* ctx);
+/* the record as it was set (zeros after dmt_clear_medium) and *active = 1 iff sigma_t > 0.  Any pointer may be null. */
+int dmt_medium_info(dmt_ctx* ctx, int* active, float* sigma_t, float* albedo3, float* g, float* box_min3, float* box_max3);
+/* host only (no GPU): the clip, the device's bit for bit while no intermediate is subnormal (the device flushes those).
+ * fp32 without contraction.  t0 = 0, t1 = t_hit; per axis a in x, y, z order: |d[a]| < 2^-100 (parallel): the interval is
+ * emptied when o[a] < min[a] or o[a] > max[a] and left alone otherwise; else inv = fl32(1 / d[a]) correctly rounded,
+ * ta = (min[a] - o[a]) * inv, tb = (max[a] - o[a]) * inv, t0 = max(t0, min(ta, tb)), t1 = min(t1, max(ta, tb)).
+ * seg2[i] = (t0, t1) and hit[i] = t0 < t1 for ray i (o3, d3: n x 3; t_hit[i] >= 0, may be +inf). */
+int dmt_medium_segment(const float* box_min3, const float* box_max3, int n, const float* o3, const float* d3, const float* t_hit, float* seg2,
+                       int32_t* hit);
+/* host only: u[i] = medium_u(h[i], depth[i]), the device's bit for bit */
+int dmt_medium_values(int n, const uint32_t* h, const uint32_t* depth, float* u);
+/* host only: Henyey-Greenstein in fp32.  Evaluation (cosine and eval both given, or both null): eval[i] = p_HG(cosine[i]).
+ * Sampling (wo3, u2, wi3, pdf all given, or all null): wi3[i] around the unit vector wo3[i] for the numbers u2[i], and
+ * pdf[i] = p_HG at the sampled cosine.  The device's operations with the host's sine, cosine, division and square root. */
+int dmt_phase_hg(float g, int n, const float* cosine, float* eval, const float* wo3, const float* u2, float* wi3, float* pdf);
 /* depth cap of the bounce loop; the reference hard-codes 32 (megakernel.cu:154) */
 int dmt_set_limits(dmt_ctx* ctx, int max_depth);
 int dmt_set_accel(dmt_ctx* ctx, int mode);
@@ -699,6 +749,13 @@ int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t*
 int dmt_test_lens_values(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* lens2);
 /* the times of the samples under the context's shutter, as the motion rows compute them: the device twin of dmt_shutter_times */
 int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t);
+/* what the *_medium rows compute between two ray casts, by the device, for a medium given here and not the context's own:
+ * medium8 = {sigma_t > 0, g, box min x y z, box max x y z}, checked as dmt_set_medium checks them.  Case i: seg2 / hit = the clip of ray (o3, d3, t_hit) as dmt_medium_segment; values3 = (medium_u(h,
+ * depth), the free-flight distance -log1p(-u) / sigma_t for that u, the transmittance exp(-sigma_t (t1 - t0)) of the clipped
+ * segment, 1 when it is empty); eval = p_HG(cosine); wi3 / pdf = the direction sampled around wo = -d3 for the numbers u2. */
+int dmt_test_medium(dmt_ctx* ctx, const float* medium8, int n, const float* o3, const float* d3, const float* t_hit, const uint32_t* h,
+                    const uint32_t* depth, const float* cosine, const float* u2, float* seg2, int32_t* hit, float* values3, float* eval,
+                    float* wi3, float* pdf);
 /* closest hit of ray i against the scene at time[i], under the current accel mode (the motion tree for DMT_ACCEL_BVH):
  * tri_index (-1: none), t (+inf: none) and, when uv2 is not null, the barycentrics (n x 2).  DMT_ERR_STATE without key 1.
  * dmt_test_closest_hit keeps answering for key 0. */
