@@ -44,6 +44,7 @@ from .binding import (  # noqa: F401
     medium_segment,
     medium_values,
     phase_hg,
+    medium_grid_march,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

@@ -86,6 +86,7 @@ EXPORTED_SYMBOLS = [
     "dmt_set_ggx_batch", "dmt_ggx_batch_diag", "dmt_tri_kind_bits",
     "dmt_upload_opacity", "dmt_clear_opacity", "dmt_opacity_info", "dmt_opacity_eval", "dmt_test_opacity", "dmt_test_closest_hit_opacity",
     "dmt_set_medium", "dmt_clear_medium", "dmt_medium_info", "dmt_medium_segment", "dmt_medium_values", "dmt_phase_hg", "dmt_test_medium",
+    "dmt_set_medium_grid", "dmt_set_medium_grid_device", "dmt_clear_medium_grid", "dmt_medium_grid_info", "dmt_medium_grid_march", "dmt_test_medium_grid",
 ]
 
 # dmt_set_sampler_table modes (include/dmt_hip.h)
@@ -289,6 +290,33 @@ def phase_hg(g, cosine=None, wo=None, u=None):
     if wi is None:
         return ev
     return (wi, pdf) if ev is None else (ev, wi, pdf)
+
+
+def _grid_call(density, o, d, t_end, tau_target):
+    """the arrays of dmt_medium_grid_march / dmt_test_medium_grid: density [nz, ny, nx], n rays, four outputs"""
+    density = _f32(density)
+    assert density.ndim == 3, "the density grid has shape (nz, ny, nx)"
+    o, d = _f32(o).reshape(-1, 3), _f32(d).reshape(-1, 3)
+    t, target = _f32(t_end).reshape(-1), _f32(tau_target).reshape(-1)
+    n = o.shape[0]
+    assert d.shape[0] == n and t.shape[0] == n and target.shape[0] == n
+    out = dict(tau=np.zeros(n, np.float32), ts=np.zeros(n, np.float32), collided=np.zeros(n, np.int32), steps=np.zeros(n, np.int32))
+    return density, o, d, t, target, n, out
+
+
+def medium_grid_march(box_min, box_max, sigma_t, density, o, d, t_end, tau_target):
+    """Host only (dmt_medium_grid_march): the voxel march of rays (o, d: [n, 3]) over [0, t_end] up to the optical depth
+    tau_target (both [n], may be +inf) through the grid density [nz, ny, nx] in the box, the device's bit for bit ->
+    dict(tau [n], ts [n], collided [n] bool, steps [n])."""
+    lib = load_library()
+    density, o, d, t, target, n, out = _grid_call(density, o, d, t_end, tau_target)
+    nz, ny, nx = density.shape
+    rc = lib.dmt_medium_grid_march(_p(_f32(box_min, (3,))), _p(_f32(box_max, (3,))), C.c_float(sigma_t), int(nx), int(ny), int(nz), _p(density),
+                                   int(n), _p(o), _p(d), _p(t), _p(target), _p(out["tau"]), _p(out["ts"]), _p(out["collided"]), _p(out["steps"]))
+    if rc != 0:
+        raise DmtError(f"dmt_medium_grid_march failed ({rc})")
+    out["collided"] = out["collided"].astype(bool)
+    return out
 
 
 OPACITY_NONE = 0xFFFFFFFF  # dmt_upload_opacity: the material is opaque
@@ -669,6 +697,51 @@ class Renderer:
         return dict(seg=seg, hit=hit.astype(bool), u=val[:, 0].copy(), flight=val[:, 1].copy(), transmittance=val[:, 2].copy(), eval=ev,
                     wi=wi, pdf=pdf)
 
+    def set_medium_grid(self, density):
+        """The medium's density grid (dmt_set_medium_grid), shape (nz, ny, nx), every value finite and >= 0:
+        the extinction in a voxel is sigma_t * density, the grid fills the medium's box.  A numpy array (anything
+        np.asarray takes) goes through the host call; a contiguous float32 torch tensor on the context's device goes through
+        dmt_set_medium_grid_device, after the tensor's stream has been synchronised.  Kept by set_medium, scene uploads and
+        set_camera; dropped by clear_medium and clear_medium_grid."""
+        if hasattr(density, "data_ptr"):  # a torch tensor
+            import torch
+            if density.dim() != 3 or density.dtype != torch.float32 or not density.is_contiguous() or not density.is_cuda:
+                raise DmtError("set_medium_grid: a tensor must be contiguous float32 of shape (nz, ny, nx) on the context's device")
+            nz, ny, nx = (int(v) for v in density.shape)
+            torch.cuda.current_stream(density.device).synchronize()
+            self._check(self._lib.dmt_set_medium_grid_device(self._ctx, C.c_void_p(int(density.data_ptr())), nx, ny, nz), "dmt_set_medium_grid_device")
+            return
+        density = _f32(density)
+        if density.ndim != 3:
+            raise DmtError("set_medium_grid: the density grid has shape (nz, ny, nx)")
+        nz, ny, nx = density.shape
+        self._check(self._lib.dmt_set_medium_grid(self._ctx, _p(density), int(nx), int(ny), int(nz)), "dmt_set_medium_grid")
+
+    def clear_medium_grid(self):
+        """dmt_clear_medium_grid: the medium is homogeneous again."""
+        self._check(self._lib.dmt_clear_medium_grid(self._ctx), "dmt_clear_medium_grid")
+
+    def medium_grid_info(self):
+        """dmt_medium_grid_info -> dict(present, dims (nx, ny, nz), support_min, support_max (inclusive voxel indices per axis;
+        min > max without a density > 0), positive (voxels > 0), max_density, active (the grid rows would run))."""
+        present, active, positive, top = C.c_int(), C.c_int(), C.c_uint64(), C.c_float()
+        dims, lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32), np.zeros(3, np.int32)
+        self._check(self._lib.dmt_medium_grid_info(self._ctx, C.byref(present), _p(dims), _p(lo), _p(hi), C.byref(positive), C.byref(top),
+                                                   C.byref(active)), "dmt_medium_grid_info")
+        return dict(present=bool(present.value), dims=tuple(int(v) for v in dims), support_min=tuple(int(v) for v in lo),
+                    support_max=tuple(int(v) for v in hi), positive=int(positive.value), max_density=top.value, active=bool(active.value))
+
+    def test_medium_grid(self, box_min, box_max, sigma_t, density, o, d, t_end, tau_target):
+        """dmt_test_medium_grid: medium_grid_march by the device, for a grid given here -> as the module's medium_grid_march."""
+        density, o, d, t, target, n, out = _grid_call(density, o, d, t_end, tau_target)
+        nz, ny, nx = density.shape
+        medium7 = np.concatenate([[sigma_t], _f32(box_min, (3,)), _f32(box_max, (3,))]).astype(np.float32)
+        self._check(self._lib.dmt_test_medium_grid(self._ctx, _p(medium7), int(nx), int(ny), int(nz), _p(density), int(n), _p(o), _p(d), _p(t),
+                                                   _p(target), _p(out["tau"]), _p(out["ts"]), _p(out["collided"]), _p(out["steps"])),
+                    "dmt_test_medium_grid")
+        out["collided"] = out["collided"].astype(bool)
+        return out
+
     def lens_info(self):
         """(lens_radius, focus_distance) of the context."""
         r, d = C.c_float(), C.c_float()
@@ -791,6 +864,8 @@ class Renderer:
             self.set_lens(float(scene.lens[0]), float(scene.lens[1]))
         if getattr(scene, "medium", None) is not None:  # a scene file's "medium"; a scene without one leaves the context's
             self.set_medium(**scene.medium)
+        if getattr(scene, "medium_grid", None) is not None:  # its "grid"
+            self.set_medium_grid(scene.medium_grid)
         if getattr(scene, "area_tri", None) is not None and len(scene.area_tri):
             self.upload_area_lights(scene.area_tri, scene.area_le)
         if getattr(scene, "env_rgb", None) is not None:

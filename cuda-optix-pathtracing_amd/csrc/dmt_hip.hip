@@ -36,6 +36,7 @@
 #include "../../include/dmt_hip.h"
 #include "pt_device.hpp"
 #include "medium.hpp"
+#include "medium_grid.hpp"
 #include "bvh_device.hpp"
 #include "bvh_gpu_build.hpp"
 #include "devbuf.hpp"
@@ -159,6 +160,9 @@ struct RenderParams {
   // the participating medium (dmt_set_medium; medium.hpp): sigmaT == 0 without one.  Read by the *_medium kernels only.
   // After `triKindInline`, so that no other field moves
   MediumParams medium;
+  // its density grid (dmt_set_medium_grid; medium_grid.hpp): density == nullptr without one.  Read by the *_medium_grid
+  // kernels only.  After `medium`, so that no other field moves
+  MediumGridParams mediumGrid;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -319,6 +323,7 @@ constexpr uint32_t kFeatMotion = 1u << 9;        // motion blur: triangles at th
 constexpr uint32_t kFeatCutout = 1u << 11;       // alpha cutouts: candidate hits filtered by an opacity texture (opacity.hpp); the texture rows only
 constexpr uint32_t kFeatVtxNormals = 1u << 10;   // smooth shading: ns interpolated from per-vertex normals (vnormals.hpp); plain, env, tex rows
 constexpr uint32_t kFeatMedium = 1u << 12;       // participating medium: free flight and scatter vertices between two ray casts (medium_device.hpp); plain and env-map rows only
+constexpr uint32_t kFeatMediumGrid = 1u << 13;   // the medium's extinction from a density grid, marched voxel by voxel (medium_grid.hpp); set together with kFeatMedium
 
 // the post-hit record path_shade works on: the uploaded one, or under kFeatMotion the triangle at the sample's time
 template <uint32_t F>
@@ -337,7 +342,8 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
   static_assert(!(F & kFeatCutout) || ((F & kFeatTex) && !(F & ~(kFeatCutout | kFeatBvh | kFeatEnv | kFeatTex))), "cutouts: the texture rows only");
   static_assert(!(F & kFeatVtxNormals) || !(F & ~(kFeatVtxNormals | kFeatBvh | kFeatEnv | kFeatTex)), "vertex normals: the plain, env-map and texture rows only");
-  static_assert(!(F & kFeatMedium) || !(F & ~(kFeatMedium | kFeatBvh | kFeatEnv)), "medium: the plain and env-map rows only");
+  static_assert(!(F & kFeatMedium) || !(F & ~(kFeatMedium | kFeatMediumGrid | kFeatBvh | kFeatEnv)), "medium: the plain and env-map rows only");
+  static_assert(!(F & kFeatMediumGrid) || ((F & kFeatMedium) && !(F & ~(kFeatMediumGrid | kFeatMedium | kFeatBvh | kFeatEnv))), "medium grid: with the medium, on the plain and env-map rows only");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
   if constexpr (F & kFeatMedium) {  // a collision inside the box replaces the surface hit or the miss
@@ -590,7 +596,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   }
 
   if constexpr (F & kFeatMedium) {  // the NEE just left pending, times the transmittance of its shadow segment
-    if (st.hasShadow) medium_attenuate_pending(k, st);
+    if (st.hasShadow) medium_attenuate_pending<F>(k, st);
   }
   // bounce (:247-295); get2D before get1D = left-to-right argument evaluation
   sect_mark(7);
@@ -1583,6 +1589,9 @@ DMT_DEV void megakernel_body_bvh() {
 // _medium: the static twin's body with the medium's code in path_shade.  _bvh_medium and _bvh_env_medium keep their twins'
 // bounds; _medium and _env_medium run one wave per SIMD fewer than theirs: at four they spill 8 and 15 VGPRs (36 and 48
 // bytes of scratch, where k_megakernel has none).
+// _medium_grid: the _medium twin's body with the voxel march in place of the closed forms.  Three rows keep their twins'
+// bounds; _bvh_env_medium_grid runs one wave per SIMD fewer than _bvh_env_medium: at three it spills 2 VGPRs (8 bytes of
+// scratch).
 #define DMT_MEGAKERNELS(X)                                                          \
   X(, 0, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                                   \
   X(_bvh, kFeatBvh, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh)                \
@@ -1635,7 +1644,11 @@ DMT_DEV void megakernel_body_bvh() {
   X(_medium, kFeatMedium, 3, megakernel_body)                                       \
   X(_bvh_medium, kFeatBvh | kFeatMedium, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh) \
   X(_env_medium, kFeatEnv | kFeatMedium, 3, megakernel_body)                        \
-  X(_bvh_env_medium, kFeatBvh | kFeatEnv | kFeatMedium, 3, megakernel_body_bvh)
+  X(_bvh_env_medium, kFeatBvh | kFeatEnv | kFeatMedium, 3, megakernel_body_bvh) \
+  X(_medium_grid, kFeatMedium | kFeatMediumGrid, 3, megakernel_body)                \
+  X(_bvh_medium_grid, kFeatBvh | kFeatMedium | kFeatMediumGrid, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh) \
+  X(_env_medium_grid, kFeatEnv | kFeatMedium | kFeatMediumGrid, 3, megakernel_body) \
+  X(_bvh_env_medium_grid, kFeatBvh | kFeatEnv | kFeatMedium | kFeatMediumGrid, 2, megakernel_body_bvh)
 // the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
 // algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
 #define DMT_STATS_MEGAKERNELS(X)                                                    \
@@ -2031,6 +2044,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (c->surf.vn.have) F |= kFeatVtxNormals;
   if (c->surf.op.have) F |= kFeatCutout;
   if (c->launch.medium.active()) F |= kFeatMedium;
+  if (c->launch.medium.gridActive()) F |= kFeatMediumGrid;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2133,6 +2147,7 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   P.env = c->env;
   if (c->launch.medium.active()) P.medium = c->launch.medium.p;
+  if (c->launch.medium.gridActive()) P.mediumGrid = c->launch.medium.gridParams();
   c->surf.fill(P);
   uint32_t const F = featuresOf(c);
   if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree.get();

@@ -134,9 +134,27 @@ struct LaunchState {
     uint64_t launches = 0;
   } timing;
   // the participating medium of the context (dmt_set_medium): what the *_medium rows read as RenderParams::medium
+  // and its density grid (dmt_set_medium_grid; what the *_medium_grid rows read as RenderParams::mediumGrid).  The grid is
+  // kept across dmt_set_medium (its derived values are made again from the new box) and dropped by dmt_clear_medium and
+  // dmt_clear_medium_grid.  A grid without a density > 0 is an empty medium: the context then launches the plain rows.
   struct Medium {
     MediumParams p{};
-    bool active() const { return p.sigmaT > 0.f; }
+    struct Grid {
+      bool have = false;
+      DevBuf<float> density;
+      int32_t n[3] = {0, 0, 0}, imin[3] = {0, 0, 0}, imax[3] = {0, 0, 0};  // imin > imax without a density > 0
+      uint64_t positive = 0;                                                // voxels with density > 0
+      float maxDensity = 0.f;
+    } grid;
+    bool active() const { return p.sigmaT > 0.f && !(grid.have && grid.positive == 0); }
+    bool gridActive() const { return active() && grid.have; }
+    MediumGridParams gridParams() const {  // (gridActive(): the box is set and the support is not empty)
+      MediumGridParams g{};
+      g.density = grid.density.get();
+      for (int a = 0; a < 3; ++a) g.n[a] = grid.n[a], g.imin[a] = grid.imin[a], g.imax[a] = grid.imax[a];
+      medium_grid_derive(g, p.lo, p.hi);
+      return g;
+    }
   } medium;
   // the shape of a launch
   uint32_t chunkSpp = 0;                    // samples per work item, 0 = automatic

@@ -2,7 +2,8 @@
 // the free flight, the transmittance of shadow segments and the scatter vertex that path_shade's *_medium rows call.
 //
 // Part of dmt_hip.hip's translation unit, included once between shade_hit and path_shade.  Nothing here is referenced by a
-// kernel instantiated without kFeatMedium.
+// kernel instantiated without kFeatMedium.  Under kFeatMediumGrid (the *_medium_grid rows; medium_grid.hpp)
+// the extinction is sigmaT times a grid of densities: the free flight and the transmittance come from medium_grid_march.
 #pragma once
 
 // the distance to the next collision for the number u in [0, 1), and the transmittance over a length
@@ -27,8 +28,31 @@ DMT_DEV float medium_length(MediumParams const& m, f3 o, f3 d, float tEnd) {
 }
 // The NEE contribution the shading step has just left pending (st.hasShadow), times the transmittance of its shadow
 // segment: every pending contribution of a medium row, made at a surface or at a scatter vertex, passes through here.
+// the grid as the kernel arguments hold it, and the march of the segment o + t d, 0 <= t <= tEnd, up to tauTarget
+DMT_DEV MediumGridParams load_medium_grid(KArgs k) {
+  k = kargs(k);
+  MediumGridParams g;
+  g.density = k->mediumGrid.density;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    g.n[i] = k->mediumGrid.n[i], g.cell[i] = k->mediumGrid.cell[i], g.invCell[i] = k->mediumGrid.invCell[i];
+    g.imin[i] = k->mediumGrid.imin[i], g.imax[i] = k->mediumGrid.imax[i], g.slo[i] = k->mediumGrid.slo[i], g.shi[i] = k->mediumGrid.shi[i];
+  }
+  return g;
+}
+DMT_DEV MediumGridMarch medium_grid_walk(KArgs k, MediumParams const& m, f3 o, f3 d, float tEnd, float tauTarget) {
+  MediumGridParams const g = load_medium_grid(k);
+  float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
+  return medium_grid_march(o3, d3, tEnd, tauTarget, m.sigmaT, m.lo, m.hi, g);
+}
+template <uint32_t F>
 DMT_DEV void medium_attenuate_pending(KArgs k, PathState const& st) {
   MediumParams const m = load_medium(k);
+  if constexpr (F & kFeatMediumGrid) {
+    float const tau = medium_grid_walk(k, m, mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y), st.smax, kInf).tau;
+    if (tau != 0.f) put_C(get_C() * expf(-tau));
+    return;
+  }
   float const len = medium_length(m, mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y), st.smax);
   if (len > 0.f) put_C(get_C() * medium_transmittance(m.sigmaT, len));
 }
@@ -44,14 +68,22 @@ DMT_DEV int medium_vertex(KArgs k, PathState& st, SceneView const& sc, int bestT
   f3 const o = ray_org(st), d = ray_dir(st);
   float tHit = kInf;
   if (bestTri >= 0) tHit = dot(shade_hit<F>(k, sc, bestTri, bu, bv, d).pos - o, d);
-  float t0, t1;
-  {
-    float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
-    if (!medium_segment(o3, d3, tHit, m.lo, m.hi, &t0, &t1)) return MV_THROUGH;
+  float tColl;
+  if constexpr (F & kFeatMediumGrid) {  // the collision is where the optical depth along the segment reaches -log1p(-u)
+    MediumGridMarch const r = medium_grid_walk(k, m, o, d, tHit, -log1pf(-medium_u(medium_h(k, st), uint32_t(st.depth))));
+    if (!r.collided) return MV_THROUGH;
+    tColl = r.ts;
+  } else {
+    float t0, t1;
+    {
+      float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
+      if (!medium_segment(o3, d3, tHit, m.lo, m.hi, &t0, &t1)) return MV_THROUGH;
+    }
+    float const s = medium_free_flight(m.sigmaT, medium_u(medium_h(k, st), uint32_t(st.depth)));
+    if (!(t0 + s < t1)) return MV_THROUGH;  // through with probability = the transmittance: beta stays as it is
+    tColl = t0 + s;
   }
-  float const s = medium_free_flight(m.sigmaT, medium_u(medium_h(k, st), uint32_t(st.depth)));
-  if (!(t0 + s < t1)) return MV_THROUGH;  // through with probability = the transmittance: beta stays as it is
-  f3 const p = o + (t0 + s) * d;
+  f3 const p = o + tColl * d;
   if (st.depth >= kargs(k)->maxDepth) return MV_ENDED;
   f3 const albedo = mk3(m.albedo[0], m.albedo[1], m.albedo[2]);
   if (is_zero(albedo)) return MV_ENDED;
@@ -102,7 +134,7 @@ DMT_DEV int medium_vertex(KArgs k, PathState& st, SceneView const& sc, int bestT
       }
     }
   }
-  if (st.hasShadow) medium_attenuate_pending(k, st);
+  if (st.hasShadow) medium_attenuate_pending<F>(k, st);
 
   // bounce: get2D + get1D as at a surface (the last value unused); f / pdf == 1
   f2 const u2 = st.rng.get2D();

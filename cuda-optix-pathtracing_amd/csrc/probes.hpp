@@ -428,6 +428,15 @@ __global__ void k_test_medium(MediumParams m, int n, float const* o3, float cons
   hg_sample(m.g, wo, u2[2 * i], u2[2 * i + 1], wi3 + 3 * i, pdf + i);
 }
 
+// dmt_test_medium_grid: medium_grid_march on the device, one ray per thread
+__global__ void k_test_medium_grid(MediumParams m, MediumGridParams g, int n, float const* o3, float const* d3, float const* tEnd,
+                                   float const* tauTarget, float* tau, float* ts, int32_t* collided, int32_t* steps) {
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  MediumGridMarch const r = medium_grid_march(o3 + 3 * i, d3 + 3 * i, tEnd[i], tauTarget[i], m.sigmaT, m.lo, m.hi, g);
+  tau[i] = r.tau, ts[i] = r.ts, collided[i] = r.collided, steps[i] = r.steps;
+}
+
 // dmt_camera_project (project_point) on the device
 __global__ void k_test_project(ProjXf c, int n, float const* p3, float* xy2, float* depth) {
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
@@ -838,6 +847,35 @@ int dmt_test_medium(dmt_ctx* ctx, const float* medium8, int n, const float* o3, 
   for (int i = 0; i < 3; ++i) m.albedo[i] = 1.f, m.lo[i] = box_min3[i], m.hi[i] = box_max3[i];
   hipLaunchKernelGGL(k_test_medium, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, m, n, dO.get(), dD.get(), dT.get(), dH.get(), dDepth.get(), dC.get(),
                      dU.get(), dSeg.get(), dHit.get(), dVal.get(), dEval.get(), dWi.get(), dPdf.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_medium_grid(dmt_ctx* ctx, const float* medium7, int nx, int ny, int nz, const float* density, int n, const float* o3, const float* d3,
+                         const float* t_end, const float* tau_target, float* tau, float* ts, int32_t* collided, int32_t* steps) {
+  if (!ctx || !medium7 || n < 0 || !o3 || !d3 || !t_end || !tau_target || !tau || !ts || !collided || !steps) return DMT_ERR_INVALID;
+  float const sigma_t = medium7[0], *const box_min3 = medium7 + 1, *const box_max3 = medium7 + 4;
+  MediumGridParams g;
+  std::string why;
+  if (char const* const e = mediumGridCallRecord(box_min3, box_max3, sigma_t, nx, ny, nz, density, g, why))
+    return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_test_medium_grid: ") + e).c_str());
+  if (n == 0) return DMT_OK;
+  if (g.imin[0] > g.imax[0]) {  // no density > 0: nothing to march, as the host twin
+    for (int i = 0; i < n; ++i) tau[i] = 0.f, ts[i] = 0.f, collided[i] = 0, steps[i] = 0;
+    return DMT_OK;
+  }
+  Probe p(ctx->device, size_t(n));
+  DevBuf<float> dGrid;
+  p.ok(dGrid.assign(density, size_t(nx) * size_t(ny) * size_t(nz)), "hipMalloc + hipMemcpy (probe grid to device)");
+  ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3), dT(p, t_end, 1), dTarget(p, tau_target, 1);
+  ProbeOut<float> dTau(p, tau, 1), dTs(p, ts, 1);
+  ProbeOut<int32_t> dColl(p, collided, 1), dSteps(p, steps, 1);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  g.density = dGrid.get();
+  MediumParams m{};
+  m.sigmaT = sigma_t;
+  for (int i = 0; i < 3; ++i) m.albedo[i] = 1.f, m.lo[i] = box_min3[i], m.hi[i] = box_max3[i];
+  hipLaunchKernelGGL(k_test_medium_grid, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, m, g, n, dO.get(), dD.get(), dT.get(), dTarget.get(),
+                     dTau.get(), dTs.get(), dColl.get(), dSteps.get());
   return finishProbe(ctx, p);
 }
 

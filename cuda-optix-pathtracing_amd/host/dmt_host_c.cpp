@@ -150,6 +150,31 @@ int dmt_host_scene_medium(const dmt_host_scene* h, float* out11) {
   for (int i = 0; i < 3; ++i) out11[1 + i] = h->s.mediumAlbedo[i], out11[5 + i] = h->s.mediumMin[i], out11[8 + i] = h->s.mediumMax[i];
   return 1;
 }
+// its density grid: the nx * ny * nz values and dims3 = (nx, ny, nz), or null without one
+const float* dmt_host_scene_medium_grid(const dmt_host_scene* h, int* dims3) {
+  if (h->s.mediumGrid.empty()) return nullptr;
+  for (int i = 0; i < 3; ++i) dims3[i] = h->s.mediumGridDims[i];
+  return h->s.mediumGrid.data();
+}
+// readNpyGrid: the number of values and dims3 = (nx, ny, nz), the values into out when it is not null and cap holds them;
+// -1 and the message in err on failure (the protocol of dmt_host_read_fbx)
+int64_t dmt_host_read_npy_grid(const char* path, float* out, uint64_t cap, int* dims3, char* err, uint64_t err_cap) {
+  std::vector<float> grid;
+  std::string msg;
+  int dims[3] = {0, 0, 0};
+  if (!path || !readNpyGrid(path, grid, dims, &msg)) {
+    if (err && err_cap) {
+      size_t const n = msg.size() < err_cap - 1 ? msg.size() : size_t(err_cap - 1);
+      memcpy(err, msg.data(), n);
+      err[n] = 0;
+    }
+    return -1;
+  }
+  if (dims3)
+    for (int i = 0; i < 3; ++i) dims3[i] = dims[i];
+  if (out && cap >= grid.size()) memcpy(out, grid.data(), grid.size() * sizeof(float));
+  return int64_t(grid.size());
+}
 void dmt_host_scene_set_resolution(dmt_host_scene* h, int width, int height) {
   h->s.camera.width = width, h->s.camera.height = height;
 }

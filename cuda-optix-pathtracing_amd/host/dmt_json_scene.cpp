@@ -633,10 +633,11 @@ bool readPngRgb(std::string const& path, std::vector<float>& rgb, int& width, in
 
 // beyond the reference's parser: the optional top-level "medium", homogeneous fog in an axis-aligned box (dmt_set_medium):
 // {"sigma_t": number >= 0, "albedo": [r, g, b] in [0, 1], "g": number in (-1, 1), "min": [x, y, z], "max": [x, y, z]};
-// "sigma_t", "min" and "max" are required, "albedo" defaults to white and "g" to 0
-void parseMedium(Value const& m, Scene& scene) {
+// "sigma_t", "min" and "max" are required, "albedo" defaults to white and "g" to 0; the optional "grid" names a NumPy .npy
+// file of densities, shape (nz, ny, nx), relative to the scene file (dmt_set_medium_grid)
+void parseMedium(Value const& m, Scene& scene, std::string const& baseDir) {
   if (!m.isObject()) fail("'medium' should be an object");
-  static char const* const keys[] = {"sigma_t", "albedo", "g", "min", "max"};
+  static char const* const keys[] = {"sigma_t", "albedo", "g", "min", "max", "grid"};
   for (auto const& kv : m.object) {
     bool known = false;
     for (char const* k : keys) known = known || kv.first == k;
@@ -666,6 +667,11 @@ void parseMedium(Value const& m, Scene& scene) {
   triple("min", scene.mediumMin), triple("max", scene.mediumMax);
   for (int i = 0; i < 3; ++i)
     if (!(scene.mediumMin[i] < scene.mediumMax[i])) fail("medium 'min' should be below 'max' on every axis");
+  if (m.contains("grid")) {
+    if (!m.at("grid").isString()) fail("medium 'grid' should be a path string");
+    std::string err;
+    if (!readNpyGrid(baseDir + "/" + m.at("grid").string, scene.mediumGrid, scene.mediumGridDims, &err)) fail("medium 'grid': " + err);
+  }
   scene.hasMedium = true;
 }
 
@@ -748,7 +754,7 @@ bool loadJsonScene(std::string const& path, JsonScene& out, std::string* error) 
       for (Material const& m : st.materialList)
         for (int r = 0; r < m.records(); ++r) out.scene.matOpacity.push_back(uint32_t(m.opacityTex));
     if (std::all_of(out.scene.triNormals.begin(), out.scene.triNormals.end(), [](float v) { return v == 0.f; })) out.scene.triNormals.clear();
-    if (data.contains("medium")) parseMedium(data.at("medium"), out.scene);
+    if (data.contains("medium")) parseMedium(data.at("medium"), out.scene, directoryOf(path));
     return true;
   } catch (Fail const& e) {
     if (error) *error = e.msg;

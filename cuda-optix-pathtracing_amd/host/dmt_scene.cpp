@@ -399,6 +399,72 @@ bool writeMeanAndMSERowMajor(float const* mean4, float const* m24, uint32_t widt
          writePngRgb8(baseName + "_sqrt_mse.png", b.data(), width, height, error);
 }
 
+// NumPy's .npy: "\x93NUMPY", major, minor, the header's length (u16 little-endian in version 1.0, u32 in 2.0), the header -- a
+// Python dict literal with the keys 'descr', 'fortran_order' and 'shape' -- then the data
+bool readNpyGrid(std::string const& path, std::vector<float>& density, int dims3[3], std::string* error) {
+  auto bad = [&](std::string const& why) {
+    if (error) *error = "'" + path + "': " + why;
+    return false;
+  };
+  FILE* const f = std::fopen(path.c_str(), "rb");
+  if (!f) return bad("cannot open the file");
+  std::vector<unsigned char> bytes;
+  unsigned char buf[65536];
+  for (size_t got; (got = std::fread(buf, 1, sizeof buf, f)) > 0;) bytes.insert(bytes.end(), buf, buf + got);
+  std::fclose(f);
+  if (bytes.size() < 10 || std::memcmp(bytes.data(), "\x93NUMPY", 6) != 0) return bad("not a NumPy .npy file (no \\x93NUMPY magic)");
+  int const major = bytes[6], minor = bytes[7];
+  if (!((major == 1 || major == 2) && minor == 0)) return bad("unsupported .npy format version " + std::to_string(major) + "." + std::to_string(minor) + " (1.0 or 2.0 expected)");
+  size_t const lenBytes = major == 1 ? 2 : 4;
+  if (bytes.size() < 8 + lenBytes) return bad("truncated .npy header");
+  size_t headerLen = 0;
+  for (size_t i = 0; i < lenBytes; ++i) headerLen |= size_t(bytes[8 + i]) << (8 * i);
+  size_t const dataAt = 8 + lenBytes + headerLen;
+  if (bytes.size() < dataAt) return bad("truncated .npy header");
+  std::string const header(reinterpret_cast<char const*>(bytes.data()) + 8 + lenBytes, headerLen);
+  // the value text after 'key':
+  auto valueOf = [&](char const* key, std::string& out) {
+    size_t p = header.find(std::string("'") + key + "'");
+    if (p == std::string::npos) return false;
+    p = header.find(':', p);
+    if (p == std::string::npos) return false;
+    ++p;
+    while (p < header.size() && header[p] == ' ') ++p;
+    out = header.substr(p);
+    return true;
+  };
+  std::string descr, order, shape;
+  if (!valueOf("descr", descr) || !valueOf("fortran_order", order) || !valueOf("shape", shape)) return bad("the .npy header lacks 'descr', 'fortran_order' or 'shape'");
+  if (descr.empty() || (descr[0] != '\'' && descr[0] != '"') || descr.find(descr[0], 1) == std::string::npos) return bad("the .npy header's 'descr' is not a plain type string (structured arrays are not supported)");
+  descr = descr.substr(1, descr.find(descr[0], 1) - 1);
+  if (descr != "<f4") return bad("dtype '" + descr + "' found, little-endian float32 ('<f4') expected");
+  if (order.compare(0, 5, "False") != 0) return bad(order.compare(0, 4, "True") == 0 ? "Fortran order found, C order expected" : "the .npy header's 'fortran_order' is neither True nor False");
+  if (shape.empty() || shape[0] != '(' || shape.find(')') == std::string::npos) return bad("the .npy header's 'shape' is not a tuple");
+  std::vector<long long> dims;
+  {
+    std::string const inner = shape.substr(1, shape.find(')') - 1);
+    size_t p = 0;
+    while (p < inner.size()) {
+      while (p < inner.size() && (inner[p] == ' ' || inner[p] == ',')) ++p;
+      if (p >= inner.size()) break;
+      if (inner[p] < '0' || inner[p] > '9') return bad("the .npy header's 'shape' is not a tuple of numbers");
+      long long v = 0;
+      while (p < inner.size() && inner[p] >= '0' && inner[p] <= '9') v = v < (1ll << 40) ? v * 10 + (inner[p] - '0') : v, ++p;
+      dims.push_back(v);
+    }
+  }
+  if (dims.size() != 3) return bad("an array of " + std::to_string(dims.size()) + " dimensions found, shape (nz, ny, nx) expected");
+  for (long long v : dims)
+    if (v < 1 || v > 512) return bad("shape (" + std::to_string(dims[0]) + ", " + std::to_string(dims[1]) + ", " + std::to_string(dims[2]) + ") found, 1 .. 512 voxels per axis expected");
+  size_t const count = size_t(dims[0]) * size_t(dims[1]) * size_t(dims[2]);
+  if (bytes.size() - dataAt < count * sizeof(float))
+    return bad("truncated: " + std::to_string(count * sizeof(float)) + " bytes of data expected, " + std::to_string(bytes.size() - dataAt) + " found");
+  density.resize(count);
+  std::memcpy(density.data(), bytes.data() + dataAt, count * sizeof(float));  // (little-endian hosts only, as the rest of the loaders)
+  dims3[0] = int(dims[2]), dims3[1] = int(dims[1]), dims3[2] = int(dims[0]);
+  return true;
+}
+
 int uploadScene(dmt_ctx* ctx, Scene const& s) {
   int rc = dmt_upload_triangles(ctx, s.xs.data(), s.ys.data(), s.zs.data(), s.matId.data(), s.triangleCount());
   if (rc) return rc;
@@ -413,6 +479,11 @@ int uploadScene(dmt_ctx* ctx, Scene const& s) {
   if (rc) return rc;
   rc = s.hasMedium ? dmt_set_medium(ctx, s.mediumSigmaT, s.mediumAlbedo, s.mediumG, s.mediumMin, s.mediumMax) : dmt_clear_medium(ctx);
   if (rc) return rc;
+  if (s.hasMedium) {  // (dmt_clear_medium has dropped the grid with the medium)
+    rc = s.mediumGrid.empty() ? dmt_clear_medium_grid(ctx)
+                              : dmt_set_medium_grid(ctx, s.mediumGrid.data(), s.mediumGridDims[0], s.mediumGridDims[1], s.mediumGridDims[2]);
+    if (rc) return rc;
+  }
   rc = dmt_upload_area_lights(ctx, s.areaTri.data(), s.areaLe.data(), uint32_t(s.areaTri.size()));
   if (rc) return rc;
   rc = s.envRgb.empty() ? dmt_clear_envmap(ctx) : dmt_upload_envmap(ctx, s.envRgb.data(), s.envWidth, s.envHeight, s.envQuat, s.envScale);

@@ -95,6 +95,10 @@ struct Scene {
   float mediumSigmaT = 0.f, mediumG = 0.f;
   float mediumAlbedo[3] = {1.f, 1.f, 1.f};
   float mediumMin[3] = {0.f, 0.f, 0.f}, mediumMax[3] = {0.f, 0.f, 0.f};
+  // its optional density grid (dmt_set_medium_grid; "grid" inside the JSON "medium", main.cpp --medium-grid): nx * ny * nz
+  // values, x fastest, filling the box; empty = homogeneous.  uploadScene sets it after the medium, or clears the context's.
+  std::vector<float> mediumGrid;
+  int mediumGridDims[3] = {0, 0, 0};
 
   size_t triangleCount() const { return matId.size(); }
   // addModel + the material walk of triSoupFromTriangles: the FIRST mesh always gets material 0
@@ -159,6 +163,10 @@ inline Vec3 normalThrough(double const m[3][3], double x, double y, double z) {
 bool readPngRgb(std::string const& path, std::vector<float>& rgb, int& width, int& height, std::string* error = nullptr);
 // the same decoder, bytes as stored: channels = 1 (grey), 2, 3 or 4 per pixel
 bool readPng8(std::string const& path, std::vector<uint8_t>& pixels, int& width, int& height, int& channels, std::string* error = nullptr);
+// a density grid from a NumPy .npy file: format version 1.0 or 2.0, little-endian float32 ('<f4'), C order, shape
+// (nz, ny, nx) -> nx * ny * nz values, x fastest, and dims3 = (nx, ny, nz).  Anything else is refused with a message that
+// says what was found.  Values and sizes are left to dmt_set_medium_grid to check.
+bool readNpyGrid(std::string const& path, std::vector<float>& density, int dims3[3], std::string* error = nullptr);
 
 // 8-bit images of the film, exactly as the reference's writers quantise them
 // (CC/private/host_utils.cu:475-497): u8 = (uint8)min(max(v,0)*255, 255), linear, truncating;

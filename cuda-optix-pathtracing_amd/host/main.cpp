@@ -61,6 +61,7 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   // --medium SIGMA_T [--medium-albedo R G B] [--medium-g G] [--medium-box X0 Y0 Z0 X1 Y1 Z1]: homogeneous fog (dmt_set_medium)
   bool mediumSet = false, mediumAlbedoSet = false, mediumGSet = false, mediumBoxSet = false;
   float mediumSigmaT = 0.f, mediumG = 0.f, mediumAlbedo[3] = {1.f, 1.f, 1.f}, mediumBox[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  std::string mediumGridPath;  // --medium-grid FILE: a density grid for the medium (dmt_set_medium_grid), a NumPy .npy file
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
 
@@ -126,6 +127,7 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
       for (int i = 0; i < 3; ++i)
         if (!(std::isfinite(mediumBox[i]) && std::isfinite(mediumBox[3 + i]) && mediumBox[i] < mediumBox[3 + i]))
           return "invalid --medium-box: expected finite X0 Y0 Z0 X1 Y1 Z1 with X0 < X1, Y0 < Y1, Z0 < Z1";
+    if (!mediumGridPath.empty() && mediumSet && !(mediumSigmaT > 0.f)) return "--medium-grid needs a medium: --medium 0 switches it off";
     if (mediumSet && mediumSigmaT > 0.f && denoise) return "--medium and --denoise exclude each other (the feature buffers do not know the fog)";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
     return "";
@@ -187,7 +189,11 @@ void printHelp() {
       "                       file's \"medium\"\n"
       "  --medium-albedo <R> <G> <B> -- Its single-scattering albedo per channel, in [0, 1] (default 1 1 1)\n"
       "  --medium-g <G>    -- Its Henyey-Greenstein asymmetry, in (-1, 1): 0 isotropic (the default), > 0 forward\n"
-      "  --medium-box <X0> <Y0> <Z0> <X1> <Y1> <Z1> -- The box that holds it (default: the bounds of the scene's triangles)");
+      "  --medium-box <X0> <Y0> <Z0> <X1> <Y1> <Z1> -- The box that holds it (default: the bounds of the scene's triangles)\n"
+      "  --medium-grid <FILE> -- A density grid that fills the medium's box: the extinction in a voxel is SIGMA_T times its\n"
+      "                       density, marched exactly.  A NumPy .npy file (version 1.0 or 2.0, little-endian float32, C order,\n"
+      "                       shape (nz, ny, nx), values finite and >= 0).  Needs a medium, from --medium or the scene file;\n"
+      "                       replaces the scene file's \"grid\"");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -217,6 +223,7 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--shading-normals" && more) c.shadingNormals = argv[++i];
     else if (a == "--cutouts" && more) c.cutouts = argv[++i];
     else if (a == "--medium" && more) c.mediumSigmaT = std::strtof(argv[++i], nullptr), c.mediumSet = true;
+    else if (a == "--medium-grid" && more) c.mediumGridPath = argv[++i];
     else if (a == "--medium-g" && more) c.mediumG = std::strtof(argv[++i], nullptr), c.mediumGSet = true;
     else if (a == "--medium-albedo" && i + 3 < argc) {
       for (float& v : c.mediumAlbedo) v = std::strtof(argv[++i], nullptr);
@@ -354,6 +361,17 @@ int main(int argc, char** argv) {
           return 1;
         }
       }
+    }
+  }
+  if (!cfg.mediumGridPath.empty()) {  // --medium-grid replaces the scene file's grid; checked before any GPU is touched
+    if (!scene.hasMedium) {
+      std::fprintf(stderr, "--medium-grid needs a medium, from --medium or the scene file\n");
+      return 1;
+    }
+    std::string err;
+    if (!dmt_host::readNpyGrid(cfg.mediumGridPath, scene.mediumGrid, scene.mediumGridDims, &err)) {
+      std::fprintf(stderr, "--medium-grid: %s\n", err.c_str());
+      return 1;
     }
   }
   if (scene.hasMedium && scene.mediumSigmaT > 0.f && cfg.denoise) {

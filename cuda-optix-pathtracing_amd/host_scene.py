@@ -69,6 +69,11 @@ class HostScene:
         # participating medium (the JSON front-end's "medium"): dict(sigma_t, albedo, g, box_min, box_max), or None
         self.medium = (dict(sigma_t=float(m11[0]), albedo=m11[1:4].copy(), g=float(m11[4]), box_min=m11[5:8].copy(), box_max=m11[8:11].copy())
                        if L.dmt_host_scene_medium(h, m11.ctypes.data_as(C.c_void_p)) else None)
+        gd = (C.c_int * 3)()
+        L.dmt_host_scene_medium_grid.restype = C.c_void_p
+        grid = L.dmt_host_scene_medium_grid(h, gd)
+        # its density grid (the "grid" inside "medium"): float32 [nz, ny, nx], or None
+        self.medium_grid = _copy(grid, np.float32, gd[0] * gd[1] * gd[2]).reshape(gd[2], gd[1], gd[0]) if grid else None
         ew, eh = C.c_int(), C.c_int()
         env = L.dmt_host_scene_env_rgb(h, C.byref(ew), C.byref(eh))
         self.env_rgb = _copy(env, np.float32, 3 * ew.value * eh.value).reshape(eh.value, ew.value, 3) if env else None
@@ -141,6 +146,21 @@ def read_fbx_normals(path):
     out = np.zeros((n, 3, 3), np.float32)
     if n:
         L.dmt_host_read_fbx_normals(str(path).encode(), out.ctypes.data_as(C.c_void_p), C.c_uint64(n), err, C.c_uint64(len(err)))
+    return out
+
+
+def read_npy_grid(path):
+    """A density grid from a NumPy .npy file as the host reads it (readNpyGrid: version 1.0 / 2.0, '<f4', C order, three
+    dimensions) -> float32 [nz, ny, nx].  Raises ValueError with the reader's message when the file is refused."""
+    L = load_host_library()
+    L.dmt_host_read_npy_grid.restype = C.c_int64
+    err = C.create_string_buffer(1024)
+    dims = (C.c_int * 3)()
+    n = L.dmt_host_read_npy_grid(str(path).encode(), None, C.c_uint64(0), dims, err, C.c_uint64(len(err)))
+    if n < 0:
+        raise ValueError(err.value.decode())
+    out = np.zeros((dims[2], dims[1], dims[0]), np.float32)
+    L.dmt_host_read_npy_grid(str(path).encode(), out.ctypes.data_as(C.c_void_p), C.c_uint64(n), dims, err, C.c_uint64(len(err)))
     return out
 
 

@@ -315,6 +315,59 @@ int dmt_medium_values(int n, const uint32_t* h, const uint32_t* depth, float* u)
  * Sampling (wo3, u2, wi3, pdf all given, or all null): wi3[i] around the unit vector wo3[i] for the numbers u2[i], and
  * pdf[i] = p_HG at the sampled cosine.  The device's operations with the host's sine, cosine, division and square root. */
 int dmt_phase_hg(float g, int n, const float* cosine, float* eval, const float* wo3, const float* u2, float* wi3, float* pdf);
+/* ---- heterogeneous medium: a density grid in the medium's box, marched exactly (opt-in) ---- */
+/* The grid.  nx * ny * nz float32 densities, x fastest, then y, then z, attached to the context's medium and filling its box
+ * [min, max].  The extinction in voxel v is sigma_t * density[v], looked up nearest-neighbour (piecewise constant); albedo, g
+ * and the box stay those of dmt_set_medium.  Limits: every density finite and >= 0, 1 <= n <= 512 per axis, at most 2^26
+ * voxels.
+ *
+ * Active.  The grid rows (*_medium_grid) run exactly when the medium is active (sigma_t > 0) and a grid is present with at
+ * least one density > 0.  Medium active, no grid: the *_medium rows, byte for byte.  A grid without a density > 0 is an empty
+ * medium: the plain rows, as for sigma_t = 0, and dmt_medium_info reports the medium as not active.  The grid belongs to no
+ * scene upload: uploads, vertex updates and dmt_set_camera keep it, dmt_set_medium keeps it (the same grid under a new box
+ * or sigma_t), dmt_clear_medium and dmt_clear_medium_grid drop it.  It may be set before dmt_set_medium.
+ *
+ * Derived (host, fp32, no contraction; made again from the box of every launch): cell[a] = (max[a] - min[a]) / n[a],
+ * invCell[a] = fl32(1 / cell[a]) correctly rounded, plane(a, i) = i == n[a] ? max[a] : min[a] + float(i) * cell[a] (multiply,
+ * then add), and the support box: per axis the inclusive index range [imin, imax] of the voxels with density > 0 and its
+ * planes plane(a, imin), plane(a, imax + 1).
+ *
+ * The march of the ray o + t d over [0, t_end] up to the optical depth tau_target (dmt_medium_grid_march is the host twin;
+ * fp32, no contraction, one order of operations):
+ *   1. [t0, t1] = the clip of dmt_medium_segment against the SUPPORT box, intersected with [0, t_end].  Empty: tau = 0, no
+ *      collision, steps = 0.
+ *   2. Per axis i = clamp(floorf((o + t0 * d - min) * invCell), imin, imax).  |d| < 2^-100: the axis never steps; otherwise
+ *      inv = fl32(1 / d) correctly rounded and step = d > 0 ? +1 : -1.
+ *   3. tc = t0, tau = 0; per iteration: tn[a] = (plane(a, i[a] + (step > 0)) - o[a]) * inv[a], +inf on a parallel axis (from the
+ *      plane index every time, never accumulated); ax = the axis of the smallest tn, the lowest axis on a tie;
+ *      te = tn[ax] < t1 ? tn[ax] : t1; seg = te - tc, 0 unless seg > 0; s = sigma_t * density[voxel]; dtau = s * seg.
+ *      s > 0 and tau + dtau >= tau_target: collision at ts = min(tc + float(double(tau_target - tau) / double(s)), te), done.
+ *      Otherwise tau += dtau, tc = max(tc, te); stop unless tn[ax] < t1; i[ax] += step, stop when that leaves [imin, imax].
+ *   tau = the segment's optical depth when no collision happened; steps = iterations, at most nx + ny + nz.
+ * In the grid rows a path segment ending at t_hit collides where the march with tau_target = -log1p(-medium_u(h, depth))
+ * does, at p = o + ts d; everything after that point is dmt_set_medium's scatter vertex.  No collision: the path goes on
+ * untouched.  Every NEE contribution is multiplied by exp(-tau) of its shadow segment (tau_target = +inf), unless tau == 0.
+ * u == 0 gives target 0: the first voxel with s > 0 collides at its entry.
+ *
+ * Scope: as the medium's, and refused with the medium's messages. */
+/* DMT_ERR_INVALID for sizes outside the limits or a density that is negative or not finite (the message names the voxel); a
+ * refused call leaves the context as it was.  Synchronises the context's stream, then copies. */
+int dmt_set_medium_grid(dmt_ctx* ctx, const float* density, int nx, int ny, int nz);
+/* the same from device memory on the context's device (a torch tensor's data_ptr()): a device-to-device copy on the context's
+ * stream, one kernel that reduces the support ranges and the invalid-value flag, one synchronous read-back.  Same errors,
+ * same resulting state and films as dmt_set_medium_grid. */
+int dmt_set_medium_grid_device(dmt_ctx* ctx, const void* d_density, int nx, int ny, int nz);
+int dmt_clear_medium_grid(dmt_ctx* ctx);
+/* *present = 1 with a grid; dims3 = (nx, ny, nz); the support index ranges (min > max without a density > 0); the number of
+ * voxels > 0; the largest density; *active = 1 iff the grid rows would run.  Any pointer may be null. */
+int dmt_medium_grid_info(dmt_ctx* ctx, int* present, int* dims3, int* support_min3, int* support_max3, uint64_t* positive, float* max_density,
+                         int* active);
+/* host only (no GPU): the march above for n rays through a grid given here, the device's bit for bit while no intermediate
+ * is subnormal.  sigma_t, the box and the grid are checked as dmt_set_medium / dmt_set_medium_grid check them.  t_end[i] >= 0
+ * and tau_target[i] >= 0, both may be +inf.  ts[i] is 0 without a collision. */
+int dmt_medium_grid_march(const float* box_min3, const float* box_max3, float sigma_t, int nx, int ny, int nz, const float* density, int n,
+                          const float* o3, const float* d3, const float* t_end, const float* tau_target, float* tau, float* ts, int32_t* collided,
+                          int32_t* steps);
 /* depth cap of the bounce loop; the reference hard-codes 32 (megakernel.cu:154) */
 int dmt_set_limits(dmt_ctx* ctx, int max_depth);
 int dmt_set_accel(dmt_ctx* ctx, int mode);
@@ -756,6 +809,11 @@ int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
 int dmt_test_medium(dmt_ctx* ctx, const float* medium8, int n, const float* o3, const float* d3, const float* t_hit, const uint32_t* h,
                     const uint32_t* depth, const float* cosine, const float* u2, float* seg2, int32_t* hit, float* values3, float* eval,
                     float* wi3, float* pdf);
+/* dmt_medium_grid_march by the device, the body the *_medium_grid rows run, for a grid given here and not the context's own:
+ * medium7 = {sigma_t, box min x y z, box max x y z}, the rest as dmt_medium_grid_march */
+int dmt_test_medium_grid(dmt_ctx* ctx, const float* medium7, int nx, int ny, int nz, const float* density, int n, const float* o3,
+                         const float* d3, const float* t_end, const float* tau_target, float* tau, float* ts, int32_t* collided,
+                         int32_t* steps);
 /* closest hit of ray i against the scene at time[i], under the current accel mode (the motion tree for DMT_ACCEL_BVH):
  * tri_index (-1: none), t (+inf: none) and, when uv2 is not null, the barycentrics (n x 2).  DMT_ERR_STATE without key 1.
  * dmt_test_closest_hit keeps answering for key 0. */
