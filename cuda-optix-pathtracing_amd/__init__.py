@@ -45,6 +45,7 @@ from .binding import (  # noqa: F401
     medium_values,
     phase_hg,
     medium_grid_march,
+    medium_spectrum_event,
     mip_level_count,
     TEXFILTER_LEVEL0,
     TEXFILTER_REFERENCE,

@@ -87,6 +87,7 @@ EXPORTED_SYMBOLS = [
     "dmt_upload_opacity", "dmt_clear_opacity", "dmt_opacity_info", "dmt_opacity_eval", "dmt_test_opacity", "dmt_test_closest_hit_opacity",
     "dmt_set_medium", "dmt_clear_medium", "dmt_medium_info", "dmt_medium_segment", "dmt_medium_values", "dmt_phase_hg", "dmt_test_medium",
     "dmt_set_medium_grid", "dmt_set_medium_grid_device", "dmt_clear_medium_grid", "dmt_medium_grid_info", "dmt_medium_grid_march", "dmt_test_medium_grid",
+    "dmt_set_medium_spectrum", "dmt_clear_medium_spectrum", "dmt_medium_spectrum_info", "dmt_medium_spectrum_event", "dmt_test_medium_spectrum",
 ]
 
 # dmt_set_sampler_table modes (include/dmt_hip.h)
@@ -315,6 +316,31 @@ def medium_grid_march(box_min, box_max, sigma_t, density, o, d, t_end, tau_targe
                                    int(n), _p(o), _p(d), _p(t), _p(target), _p(out["tau"]), _p(out["ts"]), _p(out["collided"]), _p(out["steps"]))
     if rc != 0:
         raise DmtError(f"dmt_medium_grid_march failed ({rc})")
+    out["collided"] = out["collided"].astype(bool)
+    return out
+
+
+def _spectrum_call(beta, h, depth, tau_seg):
+    """the arrays of dmt_medium_spectrum_event / dmt_test_medium_spectrum: n cases, four outputs"""
+    beta, tau = _f32(beta).reshape(-1, 3), _f32(tau_seg).reshape(-1)
+    h, depth = _u32(h), _u32(depth)
+    n = beta.shape[0]
+    assert h.shape[0] == n and depth.shape[0] == n and tau.shape[0] == n
+    out = dict(channel=np.zeros(n, np.int32), collided=np.zeros(n, np.int32), tau_at=np.zeros(n, np.float32), weight=np.zeros((n, 3), np.float32))
+    return beta, h, depth, tau, n, out
+
+
+def medium_spectrum_event(k, beta, h, depth, tau_seg):
+    """Host only (dmt_medium_spectrum_event): the event of n path segments in a medium of channel extinctions k (3): the
+    throughputs beta [n, 3], Halton indices h [n], depths [n] and channel-m optical depths tau_seg [n] (may be +inf) ->
+    dict(channel [n] (-1 without an event), collided [n] bool, tau_at [n], weight [n, 3]); the decisions are the device's
+    bit for bit."""
+    lib = load_library()
+    beta, h, depth, tau, n, out = _spectrum_call(beta, h, depth, tau_seg)
+    rc = lib.dmt_medium_spectrum_event(_p(_f32(k, (3,))), int(n), _p(beta), _p(h), _p(depth), _p(tau), _p(out["channel"]), _p(out["collided"]),
+                                       _p(out["tau_at"]), _p(out["weight"]))
+    if rc != 0:
+        raise DmtError(f"dmt_medium_spectrum_event failed ({rc})")
     out["collided"] = out["collided"].astype(bool)
     return out
 
@@ -742,6 +768,33 @@ class Renderer:
         out["collided"] = out["collided"].astype(bool)
         return out
 
+    def set_medium_spectrum(self, extinction=(1.0, 1.0, 1.0), emission=(0.0, 0.0, 0.0)):
+        """The medium's spectrum (dmt_set_medium_spectrum): an extinction colour (the channel extinctions are
+        sigma_t * extinction; finite, >= 0, not all zero) and an emitted radiance (finite, >= 0) per channel.  Kept by
+        set_medium, scene uploads and set_camera; dropped by clear_medium and clear_medium_spectrum."""
+        self._check(self._lib.dmt_set_medium_spectrum(self._ctx, _p(_f32(extinction, (3,))), _p(_f32(emission, (3,)))), "dmt_set_medium_spectrum")
+
+    def clear_medium_spectrum(self):
+        """dmt_clear_medium_spectrum: the medium is grey and dark again."""
+        self._check(self._lib.dmt_clear_medium_spectrum(self._ctx), "dmt_clear_medium_spectrum")
+
+    def medium_spectrum_info(self):
+        """dmt_medium_spectrum_info -> dict(present, extinction, emission, k (the channel extinctions from the medium's
+        sigma_t), ref_channel, active (the spectrum rows would run))."""
+        present, ref, active = C.c_int(), C.c_int(), C.c_int()
+        e, le, k = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32)
+        self._check(self._lib.dmt_medium_spectrum_info(self._ctx, C.byref(present), _p(e), _p(le), _p(k), C.byref(ref), C.byref(active)),
+                    "dmt_medium_spectrum_info")
+        return dict(present=bool(present.value), extinction=e, emission=le, k=k, ref_channel=int(ref.value), active=bool(active.value))
+
+    def test_medium_spectrum(self, k, beta, h, depth, tau_seg):
+        """dmt_test_medium_spectrum: medium_spectrum_event by the device -> as the module's medium_spectrum_event."""
+        beta, h, depth, tau, n, out = _spectrum_call(beta, h, depth, tau_seg)
+        self._check(self._lib.dmt_test_medium_spectrum(self._ctx, _p(_f32(k, (3,))), int(n), _p(beta), _p(h), _p(depth), _p(tau), _p(out["channel"]),
+                                                       _p(out["collided"]), _p(out["tau_at"]), _p(out["weight"])), "dmt_test_medium_spectrum")
+        out["collided"] = out["collided"].astype(bool)
+        return out
+
     def lens_info(self):
         """(lens_radius, focus_distance) of the context."""
         r, d = C.c_float(), C.c_float()
@@ -848,7 +901,7 @@ class Renderer:
     def upload_scene(self, scene, vertex_normals=False, opacity=True):
         """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays; a scene with a `lens`
         (lens_radius, focus_distance), as the loaders report one, sets the context's lens too, and one with a `medium`
-        (the keyword arguments of set_medium) the context's medium.  vertex_normals: also
+        (the keyword arguments of set_medium, and the "extinction" and "emission" of set_medium_spectrum) the context's medium.  vertex_normals: also
         upload the scene's `tri_normals` (smooth shading); off by default, the files' normals are not used unasked.
         opacity: upload the scene's `mat_opacity` / `opacity_cutoff` (alpha cutouts) when it carries them."""
         self.upload_triangles(scene.xs, scene.ys, scene.zs, scene.mat_id)
@@ -863,7 +916,13 @@ class Renderer:
         if getattr(scene, "lens", None) is not None:
             self.set_lens(float(scene.lens[0]), float(scene.lens[1]))
         if getattr(scene, "medium", None) is not None:  # a scene file's "medium"; a scene without one leaves the context's
-            self.set_medium(**scene.medium)
+            m = dict(scene.medium)
+            e, le = m.pop("extinction", (1.0, 1.0, 1.0)), m.pop("emission", (0.0, 0.0, 0.0))  # its "extinction" and "emission"
+            self.set_medium(**m)
+            if tuple(float(v) for v in e) == (1.0, 1.0, 1.0) and not any(float(v) for v in le):
+                self.clear_medium_spectrum()  # the file's medium is grey and dark
+            else:
+                self.set_medium_spectrum(e, le)
         if getattr(scene, "medium_grid", None) is not None:  # its "grid"
             self.set_medium_grid(scene.medium_grid)
         if getattr(scene, "area_tri", None) is not None and len(scene.area_tri):

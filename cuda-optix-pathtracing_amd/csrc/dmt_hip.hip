@@ -163,6 +163,9 @@ struct RenderParams {
   // its density grid (dmt_set_medium_grid; medium_grid.hpp): density == nullptr without one.  Read by the *_medium_grid
   // kernels only.  After `medium`, so that no other field moves
   MediumGridParams mediumGrid;
+  // its spectrum (dmt_set_medium_spectrum; medium.hpp): read by the *_rgb kernels only, whose `medium.sigmaT` is the
+  // reference channel's extinction.  After `mediumGrid`, so that no other field moves
+  MediumSpectrumParams mediumSpectrum;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -324,6 +327,7 @@ constexpr uint32_t kFeatCutout = 1u << 11;       // alpha cutouts: candidate hit
 constexpr uint32_t kFeatVtxNormals = 1u << 10;   // smooth shading: ns interpolated from per-vertex normals (vnormals.hpp); plain, env, tex rows
 constexpr uint32_t kFeatMedium = 1u << 12;       // participating medium: free flight and scatter vertices between two ray casts (medium_device.hpp); plain and env-map rows only
 constexpr uint32_t kFeatMediumGrid = 1u << 13;   // the medium's extinction from a density grid, marched voxel by voxel (medium_grid.hpp); set together with kFeatMedium
+constexpr uint32_t kFeatMediumSpectrum = 1u << 14;  // per-channel extinction and emission: one-sample MIS over the channels' free flights (medium.hpp); set together with kFeatMedium
 
 // the post-hit record path_shade works on: the uploaded one, or under kFeatMotion the triangle at the sample's time
 template <uint32_t F>
@@ -342,8 +346,9 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
   static_assert(!(F & kFeatCutout) || ((F & kFeatTex) && !(F & ~(kFeatCutout | kFeatBvh | kFeatEnv | kFeatTex))), "cutouts: the texture rows only");
   static_assert(!(F & kFeatVtxNormals) || !(F & ~(kFeatVtxNormals | kFeatBvh | kFeatEnv | kFeatTex)), "vertex normals: the plain, env-map and texture rows only");
-  static_assert(!(F & kFeatMedium) || !(F & ~(kFeatMedium | kFeatMediumGrid | kFeatBvh | kFeatEnv)), "medium: the plain and env-map rows only");
-  static_assert(!(F & kFeatMediumGrid) || ((F & kFeatMedium) && !(F & ~(kFeatMediumGrid | kFeatMedium | kFeatBvh | kFeatEnv))), "medium grid: with the medium, on the plain and env-map rows only");
+  static_assert(!(F & kFeatMedium) || !(F & ~(kFeatMedium | kFeatMediumGrid | kFeatMediumSpectrum | kFeatBvh | kFeatEnv)), "medium: the plain and env-map rows only");
+  static_assert(!(F & kFeatMediumGrid) || ((F & kFeatMedium) && !(F & ~(kFeatMediumGrid | kFeatMediumSpectrum | kFeatMedium | kFeatBvh | kFeatEnv))), "medium grid: with the medium, on the plain and env-map rows only");
+  static_assert(!(F & kFeatMediumSpectrum) || ((F & kFeatMedium) && !(F & ~(kFeatMediumSpectrum | kFeatMediumGrid | kFeatMedium | kFeatBvh | kFeatEnv))), "medium spectrum: with the medium, on the plain and env-map rows only");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
   if constexpr (F & kFeatMedium) {  // a collision inside the box replaces the surface hit or the miss
@@ -1592,6 +1597,9 @@ DMT_DEV void megakernel_body_bvh() {
 // _medium_grid: the _medium twin's body with the voxel march in place of the closed forms.  Three rows keep their twins'
 // bounds; _bvh_env_medium_grid runs one wave per SIMD fewer than _bvh_env_medium: at three it spills 2 VGPRs (8 bytes of
 // scratch).
+// _rgb: the grey twin's body with the spectrum's event and per-channel transmittances (medium.hpp).  Seven rows keep their
+// twins' bounds; _bvh_env_medium_rgb runs one wave per SIMD fewer than _bvh_env_medium: at three it spills 1 VGPR (8 bytes
+// of scratch).
 #define DMT_MEGAKERNELS(X)                                                          \
   X(, 0, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                                   \
   X(_bvh, kFeatBvh, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh)                \
@@ -1648,7 +1656,15 @@ DMT_DEV void megakernel_body_bvh() {
   X(_medium_grid, kFeatMedium | kFeatMediumGrid, 3, megakernel_body)                \
   X(_bvh_medium_grid, kFeatBvh | kFeatMedium | kFeatMediumGrid, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh) \
   X(_env_medium_grid, kFeatEnv | kFeatMedium | kFeatMediumGrid, 3, megakernel_body) \
-  X(_bvh_env_medium_grid, kFeatBvh | kFeatEnv | kFeatMedium | kFeatMediumGrid, 2, megakernel_body_bvh)
+  X(_bvh_env_medium_grid, kFeatBvh | kFeatEnv | kFeatMedium | kFeatMediumGrid, 2, megakernel_body_bvh) \
+  X(_medium_rgb, kFeatMedium | kFeatMediumSpectrum, 3, megakernel_body)             \
+  X(_bvh_medium_rgb, kFeatBvh | kFeatMedium | kFeatMediumSpectrum, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh) \
+  X(_env_medium_rgb, kFeatEnv | kFeatMedium | kFeatMediumSpectrum, 3, megakernel_body) \
+  X(_bvh_env_medium_rgb, kFeatBvh | kFeatEnv | kFeatMedium | kFeatMediumSpectrum, 2, megakernel_body_bvh) \
+  X(_medium_grid_rgb, kFeatMedium | kFeatMediumGrid | kFeatMediumSpectrum, 3, megakernel_body) \
+  X(_bvh_medium_grid_rgb, kFeatBvh | kFeatMedium | kFeatMediumGrid | kFeatMediumSpectrum, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh) \
+  X(_env_medium_grid_rgb, kFeatEnv | kFeatMedium | kFeatMediumGrid | kFeatMediumSpectrum, 3, megakernel_body) \
+  X(_bvh_env_medium_grid_rgb, kFeatBvh | kFeatEnv | kFeatMedium | kFeatMediumGrid | kFeatMediumSpectrum, 2, megakernel_body_bvh)
 // the same bodies with per-lane work counters (node visits, triangle tests, rays, bounces): they feed the
 // algorithmic-bytes model of the BVH path (dmt_render_stats) and are never on the timed path
 #define DMT_STATS_MEGAKERNELS(X)                                                    \
@@ -2045,6 +2061,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (c->surf.op.have) F |= kFeatCutout;
   if (c->launch.medium.active()) F |= kFeatMedium;
   if (c->launch.medium.gridActive()) F |= kFeatMediumGrid;
+  if (c->launch.medium.spectrumActive()) F |= kFeatMediumSpectrum;
   return F;
 }
 int ensureLightTree(dmt_ctx* ctx);
@@ -2146,8 +2163,9 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   P.env = c->env;
-  if (c->launch.medium.active()) P.medium = c->launch.medium.p;
+  if (c->launch.medium.active()) P.medium = c->launch.medium.p, P.medium.sigmaT = c->launch.medium.sigmaT();  // (with a spectrum: the reference channel's)
   if (c->launch.medium.gridActive()) P.mediumGrid = c->launch.medium.gridParams();
+  if (c->launch.medium.spectrumActive()) P.mediumSpectrum = c->launch.medium.spectrumParams();
   c->surf.fill(P);
   uint32_t const F = featuresOf(c);
   if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree.get();

@@ -569,6 +569,77 @@ int dmt_clear_medium(dmt_ctx* ctx) {
   if (!ctx) return DMT_ERR_INVALID;
   if (int const rc = dmt_clear_medium_grid(ctx)) return rc;  // the grid goes with its medium
   ctx->launch.medium.p = MediumParams{};
+  ctx->launch.medium.spectrum = LaunchState::Medium::Spectrum{};  // and so does the spectrum
+  return DMT_OK;
+}
+
+// ---- the medium's spectrum (medium.hpp) -------------------------------------------
+static char const* mediumSpectrumArgsError(const float* extinction3, const float* emission3) {
+  if (!extinction3 || !emission3) return "null argument";
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(extinction3[i]) || extinction3[i] < 0.f) return "the extinction colour must be finite and >= 0 per channel";
+  if (extinction3[0] == 0.f && extinction3[1] == 0.f && extinction3[2] == 0.f) return "the extinction colour must not be all zero";
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(emission3[i]) || emission3[i] < 0.f) return "the emission must be finite and >= 0 per channel";
+  return nullptr;
+}
+
+int dmt_set_medium_spectrum(dmt_ctx* ctx, const float* extinction3, const float* emission3) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (char const* const why = mediumSpectrumArgsError(extinction3, emission3))
+    return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_set_medium_spectrum: ") + why).c_str());
+  LaunchState::Medium::Spectrum& s = ctx->launch.medium.spectrum;
+  s.have = true;
+  for (int i = 0; i < 3; ++i) s.e[i] = extinction3[i], s.le[i] = emission3[i];
+  return DMT_OK;
+}
+
+int dmt_clear_medium_spectrum(dmt_ctx* ctx) {
+  if (!ctx) return DMT_ERR_INVALID;
+  ctx->launch.medium.spectrum = LaunchState::Medium::Spectrum{};
+  return DMT_OK;
+}
+
+int dmt_medium_spectrum_info(dmt_ctx* ctx, int* present, float* extinction3, float* emission3, float* k3, int* ref_channel, int* active) {
+  if (!ctx) return DMT_ERR_INVALID;
+  LaunchState::Medium const& m = ctx->launch.medium;
+  float k[3];
+  int const ref = m.channelK(k);
+  if (present) *present = m.spectrum.have ? 1 : 0;
+  for (int i = 0; i < 3; ++i) {
+    if (extinction3) extinction3[i] = m.spectrum.e[i];
+    if (emission3) emission3[i] = m.spectrum.le[i];
+    if (k3) k3[i] = k[i];
+  }
+  if (ref_channel) *ref_channel = ref;
+  if (active) *active = m.spectrumActive() ? 1 : 0;
+  return DMT_OK;
+}
+
+// channel extinctions given in a call (dmt_medium_spectrum_event, dmt_test_medium_spectrum): finite, >= 0, not all zero;
+// q3 = k / the largest
+static char const* mediumSpectrumCallRecord(const float* k3, float* q3) {
+  if (!k3) return "null argument";
+  int m = 0;
+  for (int i = 0; i < 3; ++i) {
+    if (!std::isfinite(k3[i]) || k3[i] < 0.f) return "the channel extinctions must be finite and >= 0";
+    if (k3[i] > k3[m]) m = i;
+  }
+  if (!(k3[m] > 0.f)) return "the channel extinctions must not be all zero";
+  for (int i = 0; i < 3; ++i) q3[i] = medium_spectrum_q(k3[i], k3[m]);
+  return nullptr;
+}
+
+int dmt_medium_spectrum_event(const float* k3, int n, const float* beta3, const uint32_t* h, const uint32_t* depth, const float* tau_seg,
+                              int32_t* channel, int32_t* collided, float* tau_at, float* weight3) {
+  if (n < 0 || !beta3 || !h || !depth || !tau_seg || !channel || !collided || !tau_at || !weight3) return DMT_ERR_INVALID;
+  float q[3];
+  if (mediumSpectrumCallRecord(k3, q)) return DMT_ERR_INVALID;
+  for (int i = 0; i < n; ++i) {
+    MediumSpectrumEvent const ev = medium_spectrum_event(q, beta3 + 3 * i, h[i], depth[i], tau_seg[i]);
+    channel[i] = ev.channel, collided[i] = ev.collided, tau_at[i] = ev.tauAt;
+    for (int c = 0; c < 3; ++c) weight3[3 * i + c] = ev.w[c];
+  }
   return DMT_OK;
 }
 

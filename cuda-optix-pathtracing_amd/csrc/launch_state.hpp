@@ -38,6 +38,8 @@
 //   rank, world               dmt_set_partition       --
 //   medium                    dmt_set_medium,         --
 //                             dmt_clear_medium
+//   medium.spectrum           dmt_set_medium_spectrum, --
+//                             dmt_clear_medium_spectrum
 //
 // The medium (medium.hpp) is per context and belongs to no upload: dmt_upload_triangles, dmt_update_vertices*, the other
 // scene uploads and dmt_set_camera leave it as it is, and so does a refused call.  It is active exactly when its sigmaT > 0;
@@ -146,8 +148,44 @@ struct LaunchState {
       uint64_t positive = 0;                                                // voxels with density > 0
       float maxDensity = 0.f;
     } grid;
-    bool active() const { return p.sigmaT > 0.f && !(grid.have && grid.positive == 0); }
+    // its spectrum (dmt_set_medium_spectrum; what the *_rgb rows read as RenderParams::mediumSpectrum): kept across
+    // dmt_set_medium, dropped by dmt_clear_medium and dmt_clear_medium_spectrum.  The channel extinctions are made from
+    // p.sigmaT whenever they are asked for, so the spectrum may be set first.
+    struct Spectrum {
+      bool have = false;
+      float e[3] = {1.f, 1.f, 1.f}, le[3] = {0.f, 0.f, 0.f};
+    } spectrum;
+    // k_c = fl32(sigma_t * e_c) (a product beyond the floats' range counts as the largest float), and the reference channel
+    int channelK(float* k) const {
+      int m = 0;
+      for (int c = 0; c < 3; ++c) {
+        float const x = p.sigmaT * spectrum.e[c];
+        k[c] = x < 3.402823466e+38f ? x : 3.402823466e+38f;
+        if (k[c] > k[m]) m = c;
+      }
+      return m;
+    }
+    // the extinction the launch marches with: sigma_t, or with a spectrum the reference channel's
+    float sigmaT() const {
+      float k[3];
+      int const m = channelK(k);
+      return spectrum.have ? k[m] : p.sigmaT;
+    }
+    bool active() const { return sigmaT() > 0.f && !(grid.have && grid.positive == 0); }
     bool gridActive() const { return active() && grid.have; }
+    bool spectrumActive() const {
+      if (!active() || !spectrum.have) return false;
+      float k[3];
+      channelK(k);
+      return k[0] != k[1] || k[1] != k[2] || spectrum.le[0] != 0.f || spectrum.le[1] != 0.f || spectrum.le[2] != 0.f;
+    }
+    MediumSpectrumParams spectrumParams() const {  // (spectrumActive(): k_m > 0)
+      float k[3];
+      int const m = channelK(k);
+      MediumSpectrumParams s{};
+      for (int c = 0; c < 3; ++c) s.q[c] = medium_spectrum_q(k[c], k[m]), s.le[c] = spectrum.le[c];
+      return s;
+    }
     MediumGridParams gridParams() const {  // (gridActive(): the box is set and the support is not empty)
       MediumGridParams g{};
       g.density = grid.density.get();

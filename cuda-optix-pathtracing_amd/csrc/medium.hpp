@@ -60,6 +60,103 @@ __host__ __device__ inline float medium_u(uint32_t h, uint32_t depth) {
   return float(x >> 8) * 0x1p-24f;
 }
 
+// ---- the medium's spectrum (dmt_set_medium_spectrum) ------------------------------------------------
+// Channel extinctions k_c = sigma_t e_c and an emission.  Every clip and march runs once, in the reference channel m (the
+// largest k; MediumParams::sigmaT holds k_m in a spectrum launch); the other channels' optical depths are q_c tau_m.
+struct MediumSpectrumParams {  // the tail of RenderParams after MediumGridParams; read by the *_rgb rows only
+  float q[3];   // k_c / k_m, correctly rounded on the host; q[m] == 1
+  float le[3];  // emitted radiance
+};
+// the stream of the channel choice: medium_u(h, depth + kMediumChoiceStream).  dmt_set_limits admits every depth an int
+// holds, so the offset is 2^31 and not 65536: depth + 1 and depth + 1 + 2^31 never meet below 2^31
+constexpr uint32_t kMediumChoiceStream = 0x80000000u;
+// q_c = k_c / k_m, correctly rounded (host): the quotient in double, rounded once more to float, as medium_rcp
+inline float medium_spectrum_q(float k, float km) { return float(double(k) / double(km)); }
+
+// -log(y) for y = 1 - u, u = medium_u(..): a multiple of 2^-24 in [2^-24, 1], so y is exact.  In double, by operations that
+// are IEEE on both sides (no contraction, one division), rounded once to float: the device and the host get the same
+// bits, which the library's log1pf does not promise.  y = 2^e m with m in (sqrt(1/2), sqrt(2)]; log m = 2 atanh(s),
+// s = (m - 1) / (m + 1), |s| <= 0.1716, the series to s^13 (the next term is below 3e-12 of the sum).
+__host__ __device__ inline double medium_neg_log(float y) {
+#pragma clang fp contract(off)
+  uint32_t bits;
+  __builtin_memcpy(&bits, &y, 4);
+  int e = int(bits >> 23) - 127;
+  uint32_t const mant = (bits & 0x7FFFFFu) | 0x3F800000u;
+  float mf;
+  __builtin_memcpy(&mf, &mant, 4);
+  if (mf > 1.41421356f) mf *= 0.5f, ++e;
+  double const m = double(mf);
+  double s = (m - 1.0) / (m + 1.0);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(s));  // (as in medium_rcp: keeps the quotient in double)
+#endif
+  double const z = s * s;
+  double const poly = 1.0 + z * (1.0 / 3.0 + z * (1.0 / 5.0 + z * (1.0 / 7.0 + z * (1.0 / 9.0 + z * (1.0 / 11.0 + z * (1.0 / 13.0))))));
+  return 0.0 - (double(e) * 0.693147180559945309417 + (2.0 * s) * poly);
+}
+
+struct MediumSpectrumChoice {
+  int channel;  // j; -1 when beta is all zero (the event is then a pass with weights 1)
+  float T;      // the target optical depth in channel m, +inf when q_j == 0
+  float p[3];   // the choice probabilities beta_c / (beta_0 + beta_1 + beta_2)
+};
+struct MediumSpectrumEvent {
+  int channel, collided;
+  float tauAt;  // channel-m optical depth at the event: T on a collision, tauSeg on a pass
+  float w[3];   // the factors of beta
+};
+// Steps 1 and 2 of the event: the channel j with probability p_j by the second hash stream, and the target in channel m.
+// The cumulative sums are compared without a division, so the choice is exact on both sides; a channel with beta == 0 is
+// never chosen, whatever the last sum rounds to.  Nothing here indexes an array by j.
+__host__ __device__ inline MediumSpectrumChoice medium_spectrum_choose(float const* q, float const* beta, uint32_t h, uint32_t depth) {
+#pragma clang fp contract(off)
+  MediumSpectrumChoice c;
+  float const b0 = beta[0], b1 = beta[1], b2 = beta[2];
+  float const s01 = b0 + b1, sum = s01 + b2;
+  c.channel = -1, c.T = __builtin_huge_valf(), c.p[0] = c.p[1] = c.p[2] = 0.0f;
+  if (!(sum > 0.0f) || !(sum < __builtin_huge_valf())) return c;
+  float const x = medium_u(h, depth + kMediumChoiceStream) * sum;
+  int j = x < b0 ? 0 : (x < s01 ? 1 : 2);
+  if (j == 2 && !(b2 > 0.0f)) j = b1 > 0.0f ? 1 : 0;
+  if (j == 1 && !(b1 > 0.0f)) j = 0;
+  c.channel = j;
+  c.p[0] = b0 / sum, c.p[1] = b1 / sum, c.p[2] = b2 / sum;
+  float const qj = j == 0 ? q[0] : (j == 1 ? q[1] : q[2]);
+  if (qj > 0.0f) {
+    double t = medium_neg_log(1.0f - medium_u(h, depth)) / double(qj);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(t));
+#endif
+    c.T = float(t);
+  }
+  return c;
+}
+// Steps 3 and 4: the one-sample balance heuristic over the three free-flight densities, at channel-m optical depth tauAt.
+// Collision: w_c = q_c e^(-q_c T) / sum_i p_i q_i e^(-q_i T).  Pass: w_c = e^(-q_c tau) / sum_i p_i e^(-q_i tau).  A channel
+// with q_c == 0 has optical depth 0 whatever tauAt is (+inf included).  The chosen channel's own term keeps the sum > 0.
+__host__ __device__ inline MediumSpectrumEvent medium_spectrum_weights(float const* q, MediumSpectrumChoice const& c, bool collided, float tauAt) {
+#pragma clang fp contract(off)
+  MediumSpectrumEvent ev;
+  ev.channel = c.channel, ev.collided = collided ? 1 : 0, ev.tauAt = tauAt;
+  float n[3], sum = 0.0f;
+  for (int i = 0; i < 3; ++i) {
+    float const t = q[i] > 0.0f ? expf(-(q[i] * tauAt)) : 1.0f;
+    n[i] = collided ? q[i] * t : t;
+    sum += c.p[i] * n[i];
+  }
+  for (int i = 0; i < 3; ++i) ev.w[i] = c.channel < 0 ? 1.0f : n[i] / sum;
+  return ev;
+}
+// The event of a path segment whose channel-m optical depth is tauSeg > 0 (+inf allowed): steps 1 to 4 in one body, which
+// the homogeneous *_rgb rows, the probe dmt_test_medium_spectrum and the host twin dmt_medium_spectrum_event share.  The
+// grid rows call its two halves around their march, which decides the collision (tau_target = T) and gives tauSeg.
+__host__ __device__ inline MediumSpectrumEvent medium_spectrum_event(float const* q, float const* beta, uint32_t h, uint32_t depth, float tauSeg) {
+  MediumSpectrumChoice const c = medium_spectrum_choose(q, beta, h, depth);
+  bool const collided = c.channel >= 0 && c.T < tauSeg;
+  return medium_spectrum_weights(q, c, collided, collided ? c.T : tauSeg);
+}
+
 // Henyey-Greenstein, pbrt's convention: c = dot(wo, wi) with wo pointing back along the arriving ray, so c = -1 is straight
 // on.  1 + g^2 + 2 g c is formed as (1 - |g|)^2 + 2 |g| (1 + sign(g) c): every term is non-negative, so the peak of a
 // strongly forward (or backward) lobe does not cancel.

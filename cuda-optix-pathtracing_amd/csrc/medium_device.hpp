@@ -4,6 +4,8 @@
 // Part of dmt_hip.hip's translation unit, included once between shade_hit and path_shade.  Nothing here is referenced by a
 // kernel instantiated without kFeatMedium.  Under kFeatMediumGrid (the *_medium_grid rows; medium_grid.hpp)
 // the extinction is sigmaT times a grid of densities: the free flight and the transmittance come from medium_grid_march.
+// Under kFeatMediumSpectrum (the *_rgb rows) sigmaT is the reference channel's extinction, the event at the
+// end of a segment is medium_spectrum_event's, and transmittances are taken per channel.
 #pragma once
 
 // the distance to the next collision for the number u in [0, 1), and the transmittance over a length
@@ -45,9 +47,28 @@ DMT_DEV MediumGridMarch medium_grid_walk(KArgs k, MediumParams const& m, f3 o, f
   float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
   return medium_grid_march(o3, d3, tEnd, tauTarget, m.sigmaT, m.lo, m.hi, g);
 }
+DMT_DEV MediumSpectrumParams load_medium_spectrum(KArgs k) {
+  k = kargs(k);
+  MediumSpectrumParams s;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) s.q[i] = k->mediumSpectrum.q[i], s.le[i] = k->mediumSpectrum.le[i];
+  return s;
+}
+// exp(-q_c tau) per channel; a channel with q_c == 0 passes untouched
+DMT_DEV f3 medium_spectrum_transmittance(MediumSpectrumParams const& s, float tau) {
+  return mk3(s.q[0] > 0.f ? expf(-(s.q[0] * tau)) : 1.f, s.q[1] > 0.f ? expf(-(s.q[1] * tau)) : 1.f, s.q[2] > 0.f ? expf(-(s.q[2] * tau)) : 1.f);
+}
 template <uint32_t F>
 DMT_DEV void medium_attenuate_pending(KArgs k, PathState const& st) {
   MediumParams const m = load_medium(k);
+  if constexpr (F & kFeatMediumSpectrum) {  // the segment's optical depth in the reference channel, once; then per channel
+    f3 const so = mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), sd = mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y);
+    float tau;
+    if constexpr (F & kFeatMediumGrid) tau = medium_grid_walk(k, m, so, sd, st.smax, kInf).tau;
+    else tau = m.sigmaT * medium_length(m, so, sd, st.smax);
+    if (tau > 0.f) put_C(get_C() * medium_spectrum_transmittance(load_medium_spectrum(k), tau));
+    return;
+  }
   if constexpr (F & kFeatMediumGrid) {
     float const tau = medium_grid_walk(k, m, mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y), st.smax, kInf).tau;
     if (tau != 0.f) put_C(get_C() * expf(-tau));
@@ -59,7 +80,8 @@ DMT_DEV void medium_attenuate_pending(KArgs k, PathState const& st) {
 
 enum : int { MV_THROUGH = 0, MV_ENDED = 1, MV_SCATTERED = 2 };
 // The path segment that has just been traced (st's ray, ending at the hit bestTri or nowhere) against the medium.
-// MV_THROUGH: no collision, path_shade goes on to the surface or the miss with st untouched (st.rng included).
+// MV_THROUGH: no collision, path_shade goes on to the surface or the miss with st untouched (st.rng included); in the
+// *_rgb rows st.beta carries the pass weights.
 // MV_SCATTERED: the path scattered inside the box; NEE and the bounce are done, st holds the next ray.  MV_ENDED: the path
 // ends at the scatter vertex (bounce cap, all-zero albedo, roulette).
 template <uint32_t F>
@@ -69,7 +91,37 @@ DMT_DEV int medium_vertex(KArgs k, PathState& st, SceneView const& sc, int bestT
   float tHit = kInf;
   if (bestTri >= 0) tHit = dot(shade_hit<F>(k, sc, bestTri, bu, bv, d).pos - o, d);
   float tColl;
-  if constexpr (F & kFeatMediumGrid) {  // the collision is where the optical depth along the segment reaches -log1p(-u)
+  if constexpr (F & kFeatMediumSpectrum) {
+    MediumSpectrumParams const sp = load_medium_spectrum(k);
+    float const beta3[3] = {st.beta.x, st.beta.y, st.beta.z};
+    uint32_t const h = medium_h(k, st);
+    MediumSpectrumEvent ev;
+    if constexpr (F & kFeatMediumGrid) {  // the march decides: it collides where the channel-m optical depth reaches T
+      MediumSpectrumChoice const ch = medium_spectrum_choose(sp.q, beta3, h, uint32_t(st.depth));
+      MediumGridMarch const r = medium_grid_walk(k, m, o, d, tHit, ch.T);
+      if (!r.collided && !(r.tau > 0.f)) return MV_THROUGH;
+      ev = medium_spectrum_weights(sp.q, ch, r.collided != 0, r.collided ? ch.T : r.tau);
+      tColl = r.ts;
+    } else {
+      float t0, t1;
+      {
+        float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
+        if (!medium_segment(o3, d3, tHit, m.lo, m.hi, &t0, &t1)) return MV_THROUGH;
+      }
+      float const tauSeg = m.sigmaT * (t1 - t0);
+      if (!(tauSeg > 0.f)) return MV_THROUGH;
+      ev = medium_spectrum_event(sp.q, beta3, h, uint32_t(st.depth), tauSeg);
+      tColl = fminf(t0 + ev.tauAt / m.sigmaT, t1);
+    }
+    f3 const w = mk3(ev.w[0], ev.w[1], ev.w[2]);
+    if (!ev.collided) {
+      st.beta = st.beta * w;
+      return MV_THROUGH;
+    }
+    // emission at the collision, before the depth cap, as a surface adds its own before it; then the weights
+    st.L = st.L + st.beta * w * (mk3(1.f - m.albedo[0], 1.f - m.albedo[1], 1.f - m.albedo[2]) * mk3(sp.le[0], sp.le[1], sp.le[2]));
+    st.beta = st.beta * w;
+  } else if constexpr (F & kFeatMediumGrid) {  // the collision is where the optical depth along the segment reaches -log1p(-u)
     MediumGridMarch const r = medium_grid_walk(k, m, o, d, tHit, -log1pf(-medium_u(medium_h(k, st), uint32_t(st.depth))));
     if (!r.collided) return MV_THROUGH;
     tColl = r.ts;

@@ -437,6 +437,17 @@ __global__ void k_test_medium_grid(MediumParams m, MediumGridParams g, int n, fl
   tau[i] = r.tau, ts[i] = r.ts, collided[i] = r.collided, steps[i] = r.steps;
 }
 
+// dmt_test_medium_spectrum: medium_spectrum_event on the device, one case per thread
+__global__ void k_test_medium_spectrum(MediumSpectrumParams sp, int n, float const* beta3, uint32_t const* h, uint32_t const* depth,
+                                       float const* tauSeg, int32_t* channel, int32_t* collided, float* tauAt, float* weight3) {
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  float const beta[3] = {beta3[3 * i], beta3[3 * i + 1], beta3[3 * i + 2]};
+  MediumSpectrumEvent const ev = medium_spectrum_event(sp.q, beta, h[i], depth[i], tauSeg[i]);
+  channel[i] = ev.channel, collided[i] = ev.collided, tauAt[i] = ev.tauAt;
+  weight3[3 * i] = ev.w[0], weight3[3 * i + 1] = ev.w[1], weight3[3 * i + 2] = ev.w[2];
+}
+
 // dmt_camera_project (project_point) on the device
 __global__ void k_test_project(ProjXf c, int n, float const* p3, float* xy2, float* depth) {
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
@@ -876,6 +887,23 @@ int dmt_test_medium_grid(dmt_ctx* ctx, const float* medium7, int nx, int ny, int
   for (int i = 0; i < 3; ++i) m.albedo[i] = 1.f, m.lo[i] = box_min3[i], m.hi[i] = box_max3[i];
   hipLaunchKernelGGL(k_test_medium_grid, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, m, g, n, dO.get(), dD.get(), dT.get(), dTarget.get(),
                      dTau.get(), dTs.get(), dColl.get(), dSteps.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_medium_spectrum(dmt_ctx* ctx, const float* k3, int n, const float* beta3, const uint32_t* h, const uint32_t* depth, const float* tau_seg,
+                             int32_t* channel, int32_t* collided, float* tau_at, float* weight3) {
+  if (!ctx || n < 0 || !beta3 || !h || !depth || !tau_seg || !channel || !collided || !tau_at || !weight3) return DMT_ERR_INVALID;
+  MediumSpectrumParams sp{};
+  if (char const* const why = mediumSpectrumCallRecord(k3, sp.q)) return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_test_medium_spectrum: ") + why).c_str());
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<float> dBeta(p, beta3, 3), dTau(p, tau_seg, 1);
+  ProbeIn<uint32_t> dH(p, h, 1), dDepth(p, depth, 1);
+  ProbeOut<int32_t> dCh(p, channel, 1), dColl(p, collided, 1);
+  ProbeOut<float> dAt(p, tau_at, 1), dW(p, weight3, 3);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  hipLaunchKernelGGL(k_test_medium_spectrum, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, sp, n, dBeta.get(), dH.get(), dDepth.get(), dTau.get(),
+                     dCh.get(), dColl.get(), dAt.get(), dW.get());
   return finishProbe(ctx, p);
 }
 

@@ -150,6 +150,10 @@ int dmt_host_scene_medium(const dmt_host_scene* h, float* out11) {
   for (int i = 0; i < 3; ++i) out11[1 + i] = h->s.mediumAlbedo[i], out11[5 + i] = h->s.mediumMin[i], out11[8 + i] = h->s.mediumMax[i];
   return 1;
 }
+// its spectrum: the extinction colour and the emission (out6); the defaults (1, 1, 1, 0, 0, 0) for a grey, dark medium
+void dmt_host_scene_medium_spectrum(const dmt_host_scene* h, float* out6) {
+  for (int i = 0; i < 3; ++i) out6[i] = h->s.mediumExtinction[i], out6[3 + i] = h->s.mediumEmission[i];
+}
 // its density grid: the nx * ny * nz values and dims3 = (nx, ny, nz), or null without one
 const float* dmt_host_scene_medium_grid(const dmt_host_scene* h, int* dims3) {
   if (h->s.mediumGrid.empty()) return nullptr;

@@ -634,10 +634,11 @@ bool readPngRgb(std::string const& path, std::vector<float>& rgb, int& width, in
 // beyond the reference's parser: the optional top-level "medium", homogeneous fog in an axis-aligned box (dmt_set_medium):
 // {"sigma_t": number >= 0, "albedo": [r, g, b] in [0, 1], "g": number in (-1, 1), "min": [x, y, z], "max": [x, y, z]};
 // "sigma_t", "min" and "max" are required, "albedo" defaults to white and "g" to 0; the optional "grid" names a NumPy .npy
-// file of densities, shape (nz, ny, nx), relative to the scene file (dmt_set_medium_grid)
+// file of densities, shape (nz, ny, nx), relative to the scene file (dmt_set_medium_grid); the optional "extinction" and
+// "emission", arrays of three numbers >= 0, are the medium's spectrum (dmt_set_medium_spectrum; "sigma_t" stays a scalar)
 void parseMedium(Value const& m, Scene& scene, std::string const& baseDir) {
   if (!m.isObject()) fail("'medium' should be an object");
-  static char const* const keys[] = {"sigma_t", "albedo", "g", "min", "max", "grid"};
+  static char const* const keys[] = {"sigma_t", "albedo", "g", "min", "max", "grid", "extinction", "emission"};
   for (auto const& kv : m.object) {
     bool known = false;
     for (char const* k : keys) known = known || kv.first == k;
@@ -667,6 +668,14 @@ void parseMedium(Value const& m, Scene& scene, std::string const& baseDir) {
   triple("min", scene.mediumMin), triple("max", scene.mediumMax);
   for (int i = 0; i < 3; ++i)
     if (!(scene.mediumMin[i] < scene.mediumMax[i])) fail("medium 'min' should be below 'max' on every axis");
+  if (m.contains("extinction")) triple("extinction", scene.mediumExtinction);
+  if (m.contains("emission")) triple("emission", scene.mediumEmission);
+  for (int i = 0; i < 3; ++i) {
+    if (scene.mediumExtinction[i] < 0.f) fail("medium 'extinction' should be >= 0 per channel");
+    if (scene.mediumEmission[i] < 0.f) fail("medium 'emission' should be >= 0 per channel");
+  }
+  if (scene.mediumExtinction[0] == 0.f && scene.mediumExtinction[1] == 0.f && scene.mediumExtinction[2] == 0.f)
+    fail("medium 'extinction' should not be all zero");
   if (m.contains("grid")) {
     if (!m.at("grid").isString()) fail("medium 'grid' should be a path string");
     std::string err;

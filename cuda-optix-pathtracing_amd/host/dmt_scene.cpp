@@ -479,7 +479,11 @@ int uploadScene(dmt_ctx* ctx, Scene const& s) {
   if (rc) return rc;
   rc = s.hasMedium ? dmt_set_medium(ctx, s.mediumSigmaT, s.mediumAlbedo, s.mediumG, s.mediumMin, s.mediumMax) : dmt_clear_medium(ctx);
   if (rc) return rc;
-  if (s.hasMedium) {  // (dmt_clear_medium has dropped the grid with the medium)
+  if (s.hasMedium) {  // (dmt_clear_medium has dropped the grid and the spectrum with the medium)
+    bool const grey = s.mediumExtinction[0] == 1.f && s.mediumExtinction[1] == 1.f && s.mediumExtinction[2] == 1.f && s.mediumEmission[0] == 0.f &&
+                      s.mediumEmission[1] == 0.f && s.mediumEmission[2] == 0.f;
+    rc = grey ? dmt_clear_medium_spectrum(ctx) : dmt_set_medium_spectrum(ctx, s.mediumExtinction, s.mediumEmission);
+    if (rc) return rc;
     rc = s.mediumGrid.empty() ? dmt_clear_medium_grid(ctx)
                               : dmt_set_medium_grid(ctx, s.mediumGrid.data(), s.mediumGridDims[0], s.mediumGridDims[1], s.mediumGridDims[2]);
     if (rc) return rc;

@@ -95,6 +95,10 @@ struct Scene {
   float mediumSigmaT = 0.f, mediumG = 0.f;
   float mediumAlbedo[3] = {1.f, 1.f, 1.f};
   float mediumMin[3] = {0.f, 0.f, 0.f}, mediumMax[3] = {0.f, 0.f, 0.f};
+  // its optional spectrum (dmt_set_medium_spectrum; "extinction" and "emission" inside the JSON "medium", main.cpp
+  // --medium-extinction / --medium-emission): the extinction colour and the emitted radiance.  uploadScene sets it with the
+  // medium, or clears the context's when both are the defaults (a grey, dark medium).
+  float mediumExtinction[3] = {1.f, 1.f, 1.f}, mediumEmission[3] = {0.f, 0.f, 0.f};
   // its optional density grid (dmt_set_medium_grid; "grid" inside the JSON "medium", main.cpp --medium-grid): nx * ny * nz
   // values, x fastest, filling the box; empty = homogeneous.  uploadScene sets it after the medium, or clears the context's.
   std::vector<float> mediumGrid;

@@ -61,6 +61,9 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   // --medium SIGMA_T [--medium-albedo R G B] [--medium-g G] [--medium-box X0 Y0 Z0 X1 Y1 Z1]: homogeneous fog (dmt_set_medium)
   bool mediumSet = false, mediumAlbedoSet = false, mediumGSet = false, mediumBoxSet = false;
   float mediumSigmaT = 0.f, mediumG = 0.f, mediumAlbedo[3] = {1.f, 1.f, 1.f}, mediumBox[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // --medium-extinction R G B, --medium-emission R G B: its spectrum (dmt_set_medium_spectrum)
+  bool mediumExtinctionSet = false, mediumEmissionSet = false;
+  float mediumExtinction[3] = {1.f, 1.f, 1.f}, mediumEmission[3] = {0.f, 0.f, 0.f};
   std::string mediumGridPath;  // --medium-grid FILE: a density grid for the medium (dmt_set_medium_grid), a NumPy .npy file
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
@@ -119,6 +122,16 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (shadingNormals != "off" && !motionScenePath.empty()) return "--shading-normals and --motion-scene exclude each other";
     if (cutouts != "on" && cutouts != "off") return "invalid --cutouts: expected on or off, got '" + cutouts + "'";
     if ((mediumAlbedoSet || mediumGSet || mediumBoxSet) && !mediumSet) return "--medium-albedo, --medium-g and --medium-box need --medium";
+    if ((mediumExtinctionSet || mediumEmissionSet) && !mediumSet) return "--medium-extinction and --medium-emission need --medium";
+    if (mediumExtinctionSet) {
+      for (float v : mediumExtinction)
+        if (!(std::isfinite(v) && v >= 0.f)) return "invalid --medium-extinction: expected three finite numbers >= 0, not all zero";
+      if (mediumExtinction[0] == 0.f && mediumExtinction[1] == 0.f && mediumExtinction[2] == 0.f)
+        return "invalid --medium-extinction: expected three finite numbers >= 0, not all zero";
+    }
+    if (mediumEmissionSet)
+      for (float v : mediumEmission)
+        if (!(std::isfinite(v) && v >= 0.f)) return "invalid --medium-emission: expected three finite numbers >= 0";
     if (mediumSet && !(std::isfinite(mediumSigmaT) && mediumSigmaT >= 0.f)) return "invalid --medium: expected a finite extinction coefficient >= 0";
     if (mediumAlbedoSet && !(mediumAlbedo[0] >= 0.f && mediumAlbedo[0] <= 1.f && mediumAlbedo[1] >= 0.f && mediumAlbedo[1] <= 1.f && mediumAlbedo[2] >= 0.f && mediumAlbedo[2] <= 1.f))
       return "invalid --medium-albedo: expected three numbers in [0, 1]";
@@ -190,6 +203,9 @@ void printHelp() {
       "  --medium-albedo <R> <G> <B> -- Its single-scattering albedo per channel, in [0, 1] (default 1 1 1)\n"
       "  --medium-g <G>    -- Its Henyey-Greenstein asymmetry, in (-1, 1): 0 isotropic (the default), > 0 forward\n"
       "  --medium-box <X0> <Y0> <Z0> <X1> <Y1> <Z1> -- The box that holds it (default: the bounds of the scene's triangles)\n"
+      "  --medium-extinction <R> <G> <B> -- Its extinction colour: the channel extinctions are SIGMA_T times these (default\n"
+      "                       1 1 1, grey); three numbers >= 0, not all zero.  Unequal channels are sampled by one-sample MIS\n"
+      "  --medium-emission <R> <G> <B> -- The radiance it emits per channel, >= 0 (default 0 0 0): a glowing gas\n"
       "  --medium-grid <FILE> -- A density grid that fills the medium's box: the extinction in a voxel is SIGMA_T times its\n"
       "                       density, marched exactly.  A NumPy .npy file (version 1.0 or 2.0, little-endian float32, C order,\n"
       "                       shape (nz, ny, nx), values finite and >= 0).  Needs a medium, from --medium or the scene file;\n"
@@ -228,6 +244,12 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--medium-albedo" && i + 3 < argc) {
       for (float& v : c.mediumAlbedo) v = std::strtof(argv[++i], nullptr);
       c.mediumAlbedoSet = true;
+    } else if (a == "--medium-extinction" && i + 3 < argc) {
+      for (float& v : c.mediumExtinction) v = std::strtof(argv[++i], nullptr);
+      c.mediumExtinctionSet = true;
+    } else if (a == "--medium-emission" && i + 3 < argc) {
+      for (float& v : c.mediumEmission) v = std::strtof(argv[++i], nullptr);
+      c.mediumEmissionSet = true;
     } else if (a == "--medium-box" && i + 6 < argc) {
       for (float& v : c.mediumBox) v = std::strtof(argv[++i], nullptr);
       c.mediumBoxSet = true;
@@ -348,6 +370,7 @@ int main(int argc, char** argv) {
   if (cfg.mediumSet) {  // --medium replaces the scene file's medium; the default box is the bounds of the triangles
     scene.hasMedium = cfg.mediumSigmaT > 0.f, scene.mediumSigmaT = cfg.mediumSigmaT, scene.mediumG = cfg.mediumG;
     for (int i = 0; i < 3; ++i) scene.mediumAlbedo[i] = cfg.mediumAlbedo[i];
+    for (int i = 0; i < 3; ++i) scene.mediumExtinction[i] = cfg.mediumExtinction[i], scene.mediumEmission[i] = cfg.mediumEmission[i];
     for (int i = 0; i < 3 && cfg.mediumBoxSet; ++i) scene.mediumMin[i] = cfg.mediumBox[i], scene.mediumMax[i] = cfg.mediumBox[3 + i];
     if (!cfg.mediumBoxSet) {
       std::vector<float> const* const axes[3] = {&scene.xs, &scene.ys, &scene.zs};

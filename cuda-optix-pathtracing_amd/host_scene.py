@@ -66,8 +66,13 @@ class HostScene:
         self.lens = (lr.value, fd.value)  # thin lens beside the camera record: (radius, focus distance); radius 0 = pinhole
         m11 = np.zeros(11, np.float32)
         L.dmt_host_scene_medium.restype = C.c_int
-        # participating medium (the JSON front-end's "medium"): dict(sigma_t, albedo, g, box_min, box_max), or None
-        self.medium = (dict(sigma_t=float(m11[0]), albedo=m11[1:4].copy(), g=float(m11[4]), box_min=m11[5:8].copy(), box_max=m11[8:11].copy())
+        s6 = np.zeros(6, np.float32)
+        L.dmt_host_scene_medium_spectrum.restype = None
+        L.dmt_host_scene_medium_spectrum(h, s6.ctypes.data_as(C.c_void_p))
+        # participating medium (the JSON front-end's "medium"): dict(sigma_t, albedo, g, box_min, box_max, and its spectrum:
+        # extinction, emission), or None
+        self.medium = (dict(sigma_t=float(m11[0]), albedo=m11[1:4].copy(), g=float(m11[4]), box_min=m11[5:8].copy(), box_max=m11[8:11].copy(),
+                            extinction=s6[0:3].copy(), emission=s6[3:6].copy())
                        if L.dmt_host_scene_medium(h, m11.ctypes.data_as(C.c_void_p)) else None)
         gd = (C.c_int * 3)()
         L.dmt_host_scene_medium_grid.restype = C.c_void_p

@@ -266,7 +266,7 @@ int dmt_opacity_info(dmt_ctx* ctx, uint64_t* cutout_triangles, uint32_t* cutout_
 int dmt_opacity_eval(const uint8_t* rgba8, uint64_t texel_count, const int32_t* desc3, uint32_t texture_count, int n, const int32_t* tex,
                      const float* uv6, const float* bu, const float* bv, float cutoff, float* alpha8_out, uint8_t* pass_out);
 /* ---- participating medium: homogeneous fog in a box, sampled in-path (opt-in, beyond the reference) ---- */
-/* The medium.  One per context: a grey extinction coefficient sigma_t >= 0 per scene unit, a single-scattering albedo in
+/* The medium.  One per context: an extinction coefficient sigma_t >= 0 per scene unit (grey unless dmt_set_medium_spectrum colours it), a single-scattering albedo in
  * [0, 1] per channel, the Henyey-Greenstein asymmetry g with |g| < 1, and a finite axis-aligned box min < max.  It is active
  * exactly when it has been set with sigma_t > 0: dmt_set_medium with sigma_t == 0 and dmt_clear_medium both leave the
  * context on the kernels it launches without these calls, and every film is then byte for byte what it was.  The medium
@@ -368,6 +368,57 @@ int dmt_medium_grid_info(dmt_ctx* ctx, int* present, int* dims3, int* support_mi
 int dmt_medium_grid_march(const float* box_min3, const float* box_max3, float sigma_t, int nx, int ny, int nz, const float* density, int n,
                           const float* o3, const float* d3, const float* t_end, const float* tau_target, float* tau, float* ts, int32_t* collided,
                           int32_t* steps);
+/* ---- chromatic and emissive media: RGB extinction by one-sample MIS (opt-in) ---- */
+/* The spectrum.  Attached to the context's medium, the way the grid is: an extinction colour e[3] >= 0 (finite, not all zero)
+ * and an emission radiance Le[3] >= 0 (finite).  The channel extinctions are k_c = fl32(sigma_t * e_c); with a grid the
+ * extinction in voxel v is k_c * density[v].  Defaults: e = (1, 1, 1), Le = (0, 0, 0).  The spectrum belongs to no upload: it
+ * survives dmt_set_medium, scene uploads and dmt_set_camera; dmt_clear_medium and dmt_clear_medium_spectrum drop it.  It may
+ * be set before dmt_set_medium.
+ *
+ * Active.  The spectrum rows (*_medium_rgb, *_medium_grid_rgb) run exactly when the medium is active and either the three k_c
+ * are not all equal or Le != 0.  With three equal k_c and Le == 0 the context launches the grey rows with sigma_t = k_0, and
+ * films are byte for byte those of dmt_set_medium(k_0, ..); without a spectrum every film of every row is what it was.  With
+ * a spectrum the medium is active iff its largest k_c is > 0 (and its grid, if any, has a density > 0).
+ *
+ * Reference channel.  m = the channel with the largest k (the lowest index on a tie); q_c = fl32(k_c / k_m), correctly
+ * rounded on the host.  All clipping and marching is done once, in channel m: tau_m = k_m * len in the homogeneous rows,
+ * the march of dmt_medium_grid_march with sigma_t = k_m in the grid rows.  Every other optical depth is tau_c = q_c tau_m.
+ *
+ * Per path segment whose channel-m optical depth is tau_seg > 0 (tau_seg == 0 or a miss of the box: nothing changes):
+ *   1. j = the channel chosen with probability p_j = beta_j / (beta_0 + beta_1 + beta_2) by v = medium_u(h, depth + 2^31), the
+ *      free-flight hash's second stream (2^31 and not a smaller offset: dmt_set_limits admits every depth below 2^31):
+ *      x = v * ((beta_0 + beta_1) + beta_2); j = 0 if x < beta_0, else 1 if x < beta_0 + beta_1, else 2; a channel with
+ *      beta_j == 0 is never chosen (a j that rounding let through falls back to the last channel before it with beta > 0).
+ *      An all-zero (or non-finite) beta has no event: the segment is a pass with weights 1.
+ *   2. T = fl32(-log(1 - medium_u(h, depth)) / q_j), the logarithm and the quotient in double by the same IEEE operations on
+ *      both sides (so T is the device's bit for bit); +inf when q_j == 0.
+ *   3. Collision (T < tau_seg; in the grid rows: the march with tau_target = T collides): at the point where the channel-m
+ *      optical depth reaches T, i.e. t0 + T / k_m, or the march's ts.  tau_c = q_c T,
+ *        w_c = q_c e^(-tau_c) / sum_i p_i q_i e^(-tau_i).
+ *      First L += beta_c w_c (1 - albedo_c) Le_c (before the depth cap, as a surface adds its emission before it), then
+ *      beta_c *= w_c, then dmt_set_medium's scatter vertex unchanged.
+ *   4. Pass (otherwise): tau_c = q_c tau_seg, beta_c *= e^(-tau_c) / sum_i p_i e^(-tau_i); the sampler's dimensions stay
+ *      unmoved and the path goes on to the surface or the miss.
+ *   5. Every pending NEE contribution, made at a surface or at a scatter vertex, is multiplied per channel by
+ *      e^(-q_c tau_m(shadow segment)).
+ * A channel with q_c == 0 has optical depth 0 (e^0 = 1) whatever tau_m is.  This is the one-sample balance heuristic over
+ * the three free-flight densities: unbiased for any positive p, and with throughput-proportional p the sum
+ * beta_0 + beta_1 + beta_2 is conserved exactly by both weights (sum_c p_c w_c = 1).  fp32 range: the chosen channel's term
+ * p_j q_j e^(-tau_j) must stay a normal float (p_j q_j above about 2^-100).
+ *
+ * Scope: as the medium's, and refused with the medium's messages. */
+/* DMT_ERR_INVALID for a negative or non-finite value or an all-zero extinction; a refused call changes nothing. */
+int dmt_set_medium_spectrum(dmt_ctx* ctx, const float* extinction3, const float* emission3);
+int dmt_clear_medium_spectrum(dmt_ctx* ctx);
+/* *present = 1 with a spectrum; the colour and the emission as set (the defaults without one); k3 = fl32(sigma_t * e_c) from
+ * the medium's current sigma_t; the reference channel; *active = 1 iff the spectrum rows would run.  Any pointer may be null. */
+int dmt_medium_spectrum_info(dmt_ctx* ctx, int* present, float* extinction3, float* emission3, float* k3, int* ref_channel, int* active);
+/* host only (no GPU): steps 1 to 4 for n cases in a medium of channel extinctions k3 (finite, >= 0, not all zero): beta3
+ * [n x 3] >= 0, the Halton index h, the depth, tau_seg > 0 (may be +inf).  channel = j (-1 without an event), collided,
+ * tau_at = T on a collision and tau_seg on a pass, weight3 = the factors of beta.  The decisions are the device's bit for
+ * bit; the weights differ by the two sides' expf and division. */
+int dmt_medium_spectrum_event(const float* k3, int n, const float* beta3, const uint32_t* h, const uint32_t* depth, const float* tau_seg,
+                              int32_t* channel, int32_t* collided, float* tau_at, float* weight3);
 /* depth cap of the bounce loop; the reference hard-codes 32 (megakernel.cu:154) */
 int dmt_set_limits(dmt_ctx* ctx, int max_depth);
 int dmt_set_accel(dmt_ctx* ctx, int mode);
@@ -809,6 +860,9 @@ int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
 int dmt_test_medium(dmt_ctx* ctx, const float* medium8, int n, const float* o3, const float* d3, const float* t_hit, const uint32_t* h,
                     const uint32_t* depth, const float* cosine, const float* u2, float* seg2, int32_t* hit, float* values3, float* eval,
                     float* wi3, float* pdf);
+/* dmt_medium_spectrum_event by the device, the body the *_rgb rows run: the same arguments and results */
+int dmt_test_medium_spectrum(dmt_ctx* ctx, const float* k3, int n, const float* beta3, const uint32_t* h, const uint32_t* depth, const float* tau_seg,
+                             int32_t* channel, int32_t* collided, float* tau_at, float* weight3);
 /* dmt_medium_grid_march by the device, the body the *_medium_grid rows run, for a grid given here and not the context's own:
  * medium7 = {sigma_t, box min x y z, box max x y z}, the rest as dmt_medium_grid_march */
 int dmt_test_medium_grid(dmt_ctx* ctx, const float* medium7, int nx, int ny, int nz, const float* density, int n, const float* o3,
