@@ -273,6 +273,8 @@ DMT_DEV void put_finIdx(uint32_t i) { s_cold[6 * kLdsThreads + threadIdx.x] = __
 DMT_DEV uint32_t get_finIdx() { return __float_as_uint(s_cold[6 * kLdsThreads + threadIdx.x]); }
 DMT_DEV f3 ray_dir(PathState const& st) { return mk3(st.rp.dx.x, st.rp.dy.x, st.rp.dz.x); }
 DMT_DEV f3 ray_org(PathState const& st) { return mk3(st.rp.ox.x, st.rp.oy.x, st.rp.oz.x); }
+DMT_DEV f3 shadow_dir(PathState const& st) { return mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y); }  // the pending shadow ray (set_shadow_ray)
+DMT_DEV f3 shadow_org(PathState const& st) { return mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y); }
 DMT_DEV void swap_rays(PathState& st) {  // path ray <-> pending shadow ray (megakernel_body_bvh)
   auto sw = [](v2f& p) { float const t = p.x; p.x = p.y, p.y = t; };
   sw(st.rp.ox), sw(st.rp.oy), sw(st.rp.oz), sw(st.rp.dx), sw(st.rp.dy), sw(st.rp.dz);
@@ -346,9 +348,12 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
   static_assert(!(F & kFeatCutout) || ((F & kFeatTex) && !(F & ~(kFeatCutout | kFeatBvh | kFeatEnv | kFeatTex))), "cutouts: the texture rows only");
   static_assert(!(F & kFeatVtxNormals) || !(F & ~(kFeatVtxNormals | kFeatBvh | kFeatEnv | kFeatTex)), "vertex normals: the plain, env-map and texture rows only");
-  static_assert(!(F & kFeatMedium) || !(F & ~(kFeatMedium | kFeatMediumGrid | kFeatMediumSpectrum | kFeatBvh | kFeatEnv)), "medium: the plain and env-map rows only");
-  static_assert(!(F & kFeatMediumGrid) || ((F & kFeatMedium) && !(F & ~(kFeatMediumGrid | kFeatMediumSpectrum | kFeatMedium | kFeatBvh | kFeatEnv))), "medium grid: with the medium, on the plain and env-map rows only");
-  static_assert(!(F & kFeatMediumSpectrum) || ((F & kFeatMedium) && !(F & ~(kFeatMediumSpectrum | kFeatMediumGrid | kFeatMedium | kFeatBvh | kFeatEnv))), "medium spectrum: with the medium, on the plain and env-map rows only");
+  // the medium has the plain and env-map rows only: each of its bits implies kFeatMedium and nothing outside kMediumRow
+  constexpr uint32_t kMediumRow = kFeatBvh | kFeatEnv | kFeatMedium | kFeatMediumGrid | kFeatMediumSpectrum;
+  constexpr bool mediumRowOk = (F & kFeatMedium) && !(F & ~kMediumRow);
+  static_assert(!(F & kFeatMedium) || mediumRowOk, "medium: the plain and env-map rows only");
+  static_assert(!(F & kFeatMediumGrid) || mediumRowOk, "medium grid: with the medium, on the plain and env-map rows only");
+  static_assert(!(F & kFeatMediumSpectrum) || mediumRowOk, "medium spectrum: with the medium, on the plain and env-map rows only");
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
   if constexpr (F & kFeatMedium) {  // a collision inside the box replaces the surface hit or the miss
@@ -1755,6 +1760,7 @@ __global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
 // =============================================================================================
 #include "accel_state.hpp"
 #include "surface_state.hpp"
+#include "medium_state.hpp"
 #include "launch_state.hpp"
 
 struct dmt_ctx {
@@ -1802,6 +1808,8 @@ struct dmt_ctx {
   float4* d_mean = nullptr;
   float4* d_m2 = nullptr;
   int filmW = 0, filmH = 0;
+  // the medium layer: the participating medium, its density grid and its spectrum (medium_state.hpp, medium_host.hpp)
+  MediumState medium;
   // the launch layer: the scheduler's buffers and fold accounting, GGX batching, the sampler table, adaptive rounds, the
   // wavefront form, timing, and the settings that shape a launch (launch_state.hpp, launch_host.hpp)
   LaunchState launch;
@@ -2059,10 +2067,7 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (c->ac.haveMotion) F |= kFeatMotion;
   if (c->surf.vn.have) F |= kFeatVtxNormals;
   if (c->surf.op.have) F |= kFeatCutout;
-  if (c->launch.medium.active()) F |= kFeatMedium;
-  if (c->launch.medium.gridActive()) F |= kFeatMediumGrid;
-  if (c->launch.medium.spectrumActive()) F |= kFeatMediumSpectrum;
-  return F;
+  return F | c->medium.features();
 }
 int ensureLightTree(dmt_ctx* ctx);
 // featuresOf once the light tree it asks for is built: a tree deeper than the walk's guard switches the context back to the
@@ -2140,6 +2145,10 @@ void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const*
 // emissive triangles, and the first-hit variant chooser that denoise_host.hpp and probes.hpp use
 #include "surface_host.hpp"
 
+// the medium layer's helpers and entry points: the medium, its density grid and its spectrum, and the checks and call
+// records that probes.hpp uses
+#include "medium_host.hpp"
+
 namespace {
 
 SceneView sceneView(dmt_ctx const* c) {
@@ -2163,9 +2172,7 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   P.env = c->env;
-  if (c->launch.medium.active()) P.medium = c->launch.medium.p, P.medium.sigmaT = c->launch.medium.sigmaT();  // (with a spectrum: the reference channel's)
-  if (c->launch.medium.gridActive()) P.mediumGrid = c->launch.medium.gridParams();
-  if (c->launch.medium.spectrumActive()) P.mediumSpectrum = c->launch.medium.spectrumParams();
+  c->medium.fill(P);
   c->surf.fill(P);
   uint32_t const F = featuresOf(c);
   if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree.get();

@@ -36,15 +36,6 @@
 //   subShift                  --                      DMT_SUB_SHIFT (< 0 automatic; at most 2)
 //   chunkSpp                  dmt_set_chunk           --
 //   rank, world               dmt_set_partition       --
-//   medium                    dmt_set_medium,         --
-//                             dmt_clear_medium
-//   medium.spectrum           dmt_set_medium_spectrum, --
-//                             dmt_clear_medium_spectrum
-//
-// The medium (medium.hpp) is per context and belongs to no upload: dmt_upload_triangles, dmt_update_vertices*, the other
-// scene uploads and dmt_set_camera leave it as it is, and so does a refused call.  It is active exactly when its sigmaT > 0;
-// a record with sigmaT == 0 (dmt_set_medium with 0, dmt_clear_medium, a new context) selects the kernels a context without
-// a medium launches.
 //
 // dmt_sched_diag(reset) zeroes sched.diag (the GGX batching words with it) and with it sched.expectedFolds and
 // ggx.lostReported, the host's two views of those words; nothing else.  dmt_kernel_time folds the used event pairs into
@@ -135,65 +126,6 @@ struct LaunchState {
     double ms = 0.0;
     uint64_t launches = 0;
   } timing;
-  // the participating medium of the context (dmt_set_medium): what the *_medium rows read as RenderParams::medium
-  // and its density grid (dmt_set_medium_grid; what the *_medium_grid rows read as RenderParams::mediumGrid).  The grid is
-  // kept across dmt_set_medium (its derived values are made again from the new box) and dropped by dmt_clear_medium and
-  // dmt_clear_medium_grid.  A grid without a density > 0 is an empty medium: the context then launches the plain rows.
-  struct Medium {
-    MediumParams p{};
-    struct Grid {
-      bool have = false;
-      DevBuf<float> density;
-      int32_t n[3] = {0, 0, 0}, imin[3] = {0, 0, 0}, imax[3] = {0, 0, 0};  // imin > imax without a density > 0
-      uint64_t positive = 0;                                                // voxels with density > 0
-      float maxDensity = 0.f;
-    } grid;
-    // its spectrum (dmt_set_medium_spectrum; what the *_rgb rows read as RenderParams::mediumSpectrum): kept across
-    // dmt_set_medium, dropped by dmt_clear_medium and dmt_clear_medium_spectrum.  The channel extinctions are made from
-    // p.sigmaT whenever they are asked for, so the spectrum may be set first.
-    struct Spectrum {
-      bool have = false;
-      float e[3] = {1.f, 1.f, 1.f}, le[3] = {0.f, 0.f, 0.f};
-    } spectrum;
-    // k_c = fl32(sigma_t * e_c) (a product beyond the floats' range counts as the largest float), and the reference channel
-    int channelK(float* k) const {
-      int m = 0;
-      for (int c = 0; c < 3; ++c) {
-        float const x = p.sigmaT * spectrum.e[c];
-        k[c] = x < 3.402823466e+38f ? x : 3.402823466e+38f;
-        if (k[c] > k[m]) m = c;
-      }
-      return m;
-    }
-    // the extinction the launch marches with: sigma_t, or with a spectrum the reference channel's
-    float sigmaT() const {
-      float k[3];
-      int const m = channelK(k);
-      return spectrum.have ? k[m] : p.sigmaT;
-    }
-    bool active() const { return sigmaT() > 0.f && !(grid.have && grid.positive == 0); }
-    bool gridActive() const { return active() && grid.have; }
-    bool spectrumActive() const {
-      if (!active() || !spectrum.have) return false;
-      float k[3];
-      channelK(k);
-      return k[0] != k[1] || k[1] != k[2] || spectrum.le[0] != 0.f || spectrum.le[1] != 0.f || spectrum.le[2] != 0.f;
-    }
-    MediumSpectrumParams spectrumParams() const {  // (spectrumActive(): k_m > 0)
-      float k[3];
-      int const m = channelK(k);
-      MediumSpectrumParams s{};
-      for (int c = 0; c < 3; ++c) s.q[c] = medium_spectrum_q(k[c], k[m]), s.le[c] = spectrum.le[c];
-      return s;
-    }
-    MediumGridParams gridParams() const {  // (gridActive(): the box is set and the support is not empty)
-      MediumGridParams g{};
-      g.density = grid.density.get();
-      for (int a = 0; a < 3; ++a) g.n[a] = grid.n[a], g.imin[a] = grid.imin[a], g.imax[a] = grid.imax[a];
-      medium_grid_derive(g, p.lo, p.hi);
-      return g;
-    }
-  } medium;
   // the shape of a launch
   uint32_t chunkSpp = 0;                    // samples per work item, 0 = automatic
   int subShift = -1;                        // row bands per tile (log2); -1 = choose per launch

@@ -22,14 +22,15 @@ DMT_DEV MediumParams load_medium(KArgs k) {
   for (int i = 0; i < 3; ++i) m.albedo[i] = k->medium.albedo[i], m.lo[i] = k->medium.lo[i], m.hi[i] = k->medium.hi[i];
   return m;
 }
-// the length inside the box of the segment o + t d, 0 <= t <= tEnd
-DMT_DEV float medium_length(MediumParams const& m, f3 o, f3 d, float tEnd) {
+// the part of the segment o + t d, 0 <= t <= tEnd, inside the box, and its length
+DMT_DEV bool medium_box_segment(MediumParams const& m, f3 o, f3 d, float tEnd, float* t0, float* t1) {
   float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
-  float t0, t1;
-  return medium_segment(o3, d3, tEnd, m.lo, m.hi, &t0, &t1) ? t1 - t0 : 0.f;
+  return medium_segment(o3, d3, tEnd, m.lo, m.hi, t0, t1);
 }
-// The NEE contribution the shading step has just left pending (st.hasShadow), times the transmittance of its shadow
-// segment: every pending contribution of a medium row, made at a surface or at a scatter vertex, passes through here.
+DMT_DEV float medium_length(MediumParams const& m, f3 o, f3 d, float tEnd) {
+  float t0, t1;
+  return medium_box_segment(m, o, d, tEnd, &t0, &t1) ? t1 - t0 : 0.f;
+}
 // the grid as the kernel arguments hold it, and the march of the segment o + t d, 0 <= t <= tEnd, up to tauTarget
 DMT_DEV MediumGridParams load_medium_grid(KArgs k) {
   k = kargs(k);
@@ -47,6 +48,12 @@ DMT_DEV MediumGridMarch medium_grid_walk(KArgs k, MediumParams const& m, f3 o, f
   float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
   return medium_grid_march(o3, d3, tEnd, tauTarget, m.sigmaT, m.lo, m.hi, g);
 }
+// the optical depth of the whole segment: the march's under a grid, sigmaT times the length inside the box without one
+template <uint32_t F>
+DMT_DEV float medium_segment_tau(KArgs k, MediumParams const& m, f3 o, f3 d, float tEnd) {
+  if constexpr (F & kFeatMediumGrid) return medium_grid_walk(k, m, o, d, tEnd, kInf).tau;
+  else return m.sigmaT * medium_length(m, o, d, tEnd);
+}
 DMT_DEV MediumSpectrumParams load_medium_spectrum(KArgs k) {
   k = kargs(k);
   MediumSpectrumParams s;
@@ -58,24 +65,25 @@ DMT_DEV MediumSpectrumParams load_medium_spectrum(KArgs k) {
 DMT_DEV f3 medium_spectrum_transmittance(MediumSpectrumParams const& s, float tau) {
   return mk3(s.q[0] > 0.f ? expf(-(s.q[0] * tau)) : 1.f, s.q[1] > 0.f ? expf(-(s.q[1] * tau)) : 1.f, s.q[2] > 0.f ? expf(-(s.q[2] * tau)) : 1.f);
 }
+// The NEE contribution the shading step has just left pending (st.hasShadow), times the transmittance of its shadow
+// segment: every pending contribution of a medium row, made at a surface or at a scatter vertex, passes through here.
+// The *_rgb rows take the segment's optical depth in the reference channel once, then the factor per channel.  The grey
+// rows keep the skip tests they have had: the closed form asks the length, which can be > 0 where sigmaT times it is not.
 template <uint32_t F>
 DMT_DEV void medium_attenuate_pending(KArgs k, PathState const& st) {
   MediumParams const m = load_medium(k);
-  if constexpr (F & kFeatMediumSpectrum) {  // the segment's optical depth in the reference channel, once; then per channel
-    f3 const so = mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), sd = mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y);
-    float tau;
-    if constexpr (F & kFeatMediumGrid) tau = medium_grid_walk(k, m, so, sd, st.smax, kInf).tau;
-    else tau = m.sigmaT * medium_length(m, so, sd, st.smax);
-    if (tau > 0.f) put_C(get_C() * medium_spectrum_transmittance(load_medium_spectrum(k), tau));
-    return;
+  f3 const o = shadow_org(st), d = shadow_dir(st);
+  if constexpr (F & (kFeatMediumGrid | kFeatMediumSpectrum)) {
+    float const tau = medium_segment_tau<F>(k, m, o, d, st.smax);
+    if constexpr (F & kFeatMediumSpectrum) {
+      if (tau > 0.f) put_C(get_C() * medium_spectrum_transmittance(load_medium_spectrum(k), tau));
+    } else {
+      if (tau != 0.f) put_C(get_C() * expf(-tau));
+    }
+  } else {
+    float const len = medium_length(m, o, d, st.smax);
+    if (len > 0.f) put_C(get_C() * medium_transmittance(m.sigmaT, len));
   }
-  if constexpr (F & kFeatMediumGrid) {
-    float const tau = medium_grid_walk(k, m, mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y), st.smax, kInf).tau;
-    if (tau != 0.f) put_C(get_C() * expf(-tau));
-    return;
-  }
-  float const len = medium_length(m, mk3(st.rp.ox.y, st.rp.oy.y, st.rp.oz.y), mk3(st.rp.dx.y, st.rp.dy.y, st.rp.dz.y), st.smax);
-  if (len > 0.f) put_C(get_C() * medium_transmittance(m.sigmaT, len));
 }
 
 enum : int { MV_THROUGH = 0, MV_ENDED = 1, MV_SCATTERED = 2 };
@@ -104,10 +112,7 @@ DMT_DEV int medium_vertex(KArgs k, PathState& st, SceneView const& sc, int bestT
       tColl = r.ts;
     } else {
       float t0, t1;
-      {
-        float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
-        if (!medium_segment(o3, d3, tHit, m.lo, m.hi, &t0, &t1)) return MV_THROUGH;
-      }
+      if (!medium_box_segment(m, o, d, tHit, &t0, &t1)) return MV_THROUGH;
       float const tauSeg = m.sigmaT * (t1 - t0);
       if (!(tauSeg > 0.f)) return MV_THROUGH;
       ev = medium_spectrum_event(sp.q, beta3, h, uint32_t(st.depth), tauSeg);
@@ -127,10 +132,7 @@ DMT_DEV int medium_vertex(KArgs k, PathState& st, SceneView const& sc, int bestT
     tColl = r.ts;
   } else {
     float t0, t1;
-    {
-      float const o3[3] = {o.x, o.y, o.z}, d3[3] = {d.x, d.y, d.z};
-      if (!medium_segment(o3, d3, tHit, m.lo, m.hi, &t0, &t1)) return MV_THROUGH;
-    }
+    if (!medium_box_segment(m, o, d, tHit, &t0, &t1)) return MV_THROUGH;
     float const s = medium_free_flight(m.sigmaT, medium_u(medium_h(k, st), uint32_t(st.depth)));
     if (!(t0 + s < t1)) return MV_THROUGH;  // through with probability = the transmittance: beta stays as it is
     tColl = t0 + s;

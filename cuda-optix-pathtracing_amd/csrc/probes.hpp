@@ -844,7 +844,7 @@ int dmt_test_medium(dmt_ctx* ctx, const float* medium8, int n, const float* o3, 
   if (!ctx || !medium8 || n < 0 || !o3 || !d3 || !t_hit || !h || !depth || !cosine || !u2 || !seg2 || !hit || !values3 || !eval || !wi3 || !pdf) return DMT_ERR_INVALID;
   float const sigma_t = medium8[0], g = medium8[1], *const box_min3 = medium8 + 2, *const box_max3 = medium8 + 5;
   float const white[3] = {1.f, 1.f, 1.f};
-  if (char const* const why = mediumArgsError(sigma_t, white, g, box_min3, box_max3)) return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_test_medium: ") + why).c_str());
+  if (char const* const why = mediumArgsError(sigma_t, white, g, box_min3, box_max3)) return mediumRefused(ctx, "dmt_test_medium", why);
   if (!(sigma_t > 0.f)) return fail(ctx, DMT_ERR_INVALID, "dmt_test_medium: sigma_t must be > 0 (the free-flight distance divides by it)");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
@@ -867,8 +867,7 @@ int dmt_test_medium_grid(dmt_ctx* ctx, const float* medium7, int nx, int ny, int
   float const sigma_t = medium7[0], *const box_min3 = medium7 + 1, *const box_max3 = medium7 + 4;
   MediumGridParams g;
   std::string why;
-  if (char const* const e = mediumGridCallRecord(box_min3, box_max3, sigma_t, nx, ny, nz, density, g, why))
-    return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_test_medium_grid: ") + e).c_str());
+  if (char const* const e = mediumGridCallRecord(box_min3, box_max3, sigma_t, nx, ny, nz, density, g, why)) return mediumRefused(ctx, "dmt_test_medium_grid", e);
   if (n == 0) return DMT_OK;
   if (g.imin[0] > g.imax[0]) {  // no density > 0: nothing to march, as the host twin
     for (int i = 0; i < n; ++i) tau[i] = 0.f, ts[i] = 0.f, collided[i] = 0, steps[i] = 0;
@@ -894,7 +893,7 @@ int dmt_test_medium_spectrum(dmt_ctx* ctx, const float* k3, int n, const float* 
                              int32_t* channel, int32_t* collided, float* tau_at, float* weight3) {
   if (!ctx || n < 0 || !beta3 || !h || !depth || !tau_seg || !channel || !collided || !tau_at || !weight3) return DMT_ERR_INVALID;
   MediumSpectrumParams sp{};
-  if (char const* const why = mediumSpectrumCallRecord(k3, sp.q)) return fail(ctx, DMT_ERR_INVALID, (std::string("dmt_test_medium_spectrum: ") + why).c_str());
+  if (char const* const why = mediumSpectrumCallRecord(k3, sp.q)) return mediumRefused(ctx, "dmt_test_medium_spectrum", why);
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<float> dBeta(p, beta3, 3), dTau(p, tau_seg, 1);

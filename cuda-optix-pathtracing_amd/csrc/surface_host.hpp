@@ -124,7 +124,7 @@ OpacityRec makeOpacityRec(float const* uv6, int32_t const* desc3) {
 // normal it is shaded with: 0 plain, 1 vertex normals, 2 motion, 3 cutout.  No kernel combines two of them.
 int firstHitVariant(dmt_ctx* ctx, char const* who, int* variant) {
   bool const normals = ctx->surf.vn.have, motion = ctx->ac.haveMotion, cutout = ctx->surf.op.have;
-  if (ctx->launch.medium.active())  // the feature pass and the path log know surfaces only
+  if (ctx->medium.active())  // the feature pass and the path log know surfaces only
     return fail(ctx, DMT_ERR_STATE, (std::string(who) + ": a participating medium (dmt_set_medium) is not supported here").c_str());
   if (normals && motion)
     return fail(ctx, DMT_ERR_STATE, (std::string(who) + ": vertex normals (dmt_upload_vertex_normals) together with motion blur are not supported").c_str());
