@@ -68,9 +68,9 @@ EXPORTED_SYMBOLS = [
     "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
-    "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_brute_cull_box_records", "dmt_cull_box_test", "dmt_test_triangle_intersect",
+    "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_brute_cull_box_records", "dmt_cull_records", "dmt_cull_box_test", "dmt_test_triangle_intersect",
     "dmt_test_sampler", "dmt_test_camera_rays", "dmt_test_bsdf", "dmt_test_bsdf_ng", "dmt_test_material", "dmt_test_light", "dmt_test_half",
-    "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit",
+    "dmt_test_trace_samples", "dmt_test_trace_log", "dmt_test_closest_hit", "dmt_test_trace_pair",
     "dmt_set_texture_filter", "dmt_texture_mip_chain", "dmt_texture_footprint", "dmt_test_texture_filter",
     "dmt_render_aovs", "dmt_upload_aovs", "dmt_download_aovs", "dmt_denoise_defaults", "dmt_denoise",
     "dmt_set_accel_build", "dmt_accel_build_info", "dmt_accel_download", "dmt_lbvh_reference", "dmt_bvh_check",
@@ -562,6 +562,27 @@ def brute_cull_box_records(xs, ys, zs, mat_id, enable=True):
     if rc != 0:
         raise DmtError(f"dmt_brute_cull_box_records failed ({rc})")
     return [(box[6 * k:6 * k + 6].copy(), rec[6 * k:6 * k + 6].copy()) for k in range(nc.value)]
+
+
+CULL_RECORD_DTYPE = np.dtype([("b", "<f4", 6), ("box", "<u4"), ("count", "<u4"), ("first", "<u4"), ("slot", "<u4"),
+                              ("magic", "<u4"), ("pad", "<u4", 5)])
+
+
+def cull_records(xs, ys, zs, mat_id, level=2):
+    """Host-only: the cluster table the brute-force pass uploads for a soup at DMT_BRUTE_CULL = level, as
+    (records, record_bytes, record_align): a CULL_RECORD_DTYPE array of the clusters, sphere clusters first."""
+    lib = load_library()
+    xs, ys, zs = _f32(xs), _f32(ys), _f32(zs)
+    mat = np.ascontiguousarray(mat_id, np.uint32)
+    n = xs.size // 4
+    nc, nb, na = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    raw = np.zeros(12 * 64, np.uint8)
+    rc = lib.dmt_cull_records(_p(xs), _p(ys), _p(zs), _p(mat), C.c_size_t(n), int(level), C.byref(nc), C.byref(nb), C.byref(na), _p(raw))
+    if rc != 0:
+        raise DmtError(f"dmt_cull_records failed ({rc})")
+    if nb.value != CULL_RECORD_DTYPE.itemsize:
+        raise DmtError(f"dmt_cull_records: record of {nb.value} bytes, expected {CULL_RECORD_DTYPE.itemsize}")
+    return raw[:nc.value * nb.value].view(CULL_RECORD_DTYPE).copy(), nb.value, na.value
 
 
 def cull_box_test(record, origins, dirs, tmax):
@@ -1403,6 +1424,18 @@ class Renderer:
         self._check(self._lib.dmt_test_closest_hit_at(self._ctx, n, _p(o), _p(d), _p(time), _p(idx), _p(t), _p(uv)),
                     "dmt_test_closest_hit_at")
         return idx, t, uv
+
+    def test_trace_pair(self, o, d, so, sd, smax):
+        """dmt_test_trace_pair: pair i = (closest ray o, d; shadow ray so, sd up to smax) through one trace call of the
+        render kernels under the current accel mode -> (tri [n], uv [n, 2], occluded [n] bool)."""
+        o, d, so, sd = _f32(o, (-1, 3)), _f32(d, (-1, 3)), _f32(so, (-1, 3)), _f32(sd, (-1, 3))
+        n = o.shape[0]
+        assert d.shape[0] == n and so.shape[0] == n and sd.shape[0] == n
+        smax = np.ascontiguousarray(np.broadcast_to(np.asarray(smax, np.float32), (n,)))
+        idx, uv, occ = np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+        self._check(self._lib.dmt_test_trace_pair(self._ctx, n, _p(o), _p(d), _p(so), _p(sd), _p(smax), _p(idx), _p(uv), _p(occ)),
+                    "dmt_test_trace_pair")
+        return idx, uv, occ.astype(bool)
 
     def test_closest_hit(self, o, d):
         o, d = _f32(o, (-1, 3)), _f32(d, (-1, 3))

@@ -215,14 +215,17 @@ int motionParams(dmt_ctx* ctx, uint32_t F, RenderParams& P) {
 
 // ---- the brute-force pass's cluster tables ----
 // the culled clusters of the brute-force pass for a soup, by the context's DMT_BRUTE_CULL setting
-std::vector<CullCluster> planCullClusters(dmt_ctx const* ctx, float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
+std::vector<CullCluster> planCullClusters(int level, float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
   // a closest-hit key holds the original index in 26 bits: no culling for larger soups
-  std::vector<CullCluster> clusters = planBruteCull(xs, ys, zs, mat, uint32_t(count), ctx->bruteCull >= 1 && count < kCullMaxIndex, nullptr);
-  if (ctx->bruteCull >= 2 && count < kCullMaxIndex) {
+  std::vector<CullCluster> clusters = planBruteCull(xs, ys, zs, mat, uint32_t(count), level >= 1 && count < kCullMaxIndex, nullptr);
+  if (level >= 2 && count < kCullMaxIndex) {
     std::vector<CullCluster> const boxes = planBruteCullBox(xs, ys, zs, mat, uint32_t(count), clusters);
     clusters.insert(clusters.end(), boxes.begin(), boxes.end());
   }
   return clusters;
+}
+std::vector<CullCluster> planCullClusters(dmt_ctx const* ctx, float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
+  return planCullClusters(ctx->bruteCull, xs, ys, zs, mat, count);
 }
 
 // device tables of a cluster plan; a = the soup's TriIsect records (read only when there are clusters).  The caller adopts

@@ -58,13 +58,17 @@ constexpr uint32_t kCullGroup = 4;
 constexpr uint32_t kCullMaxTris = 44;      // LDS copy of the culled triangles, 36 B each (see the LDS budget in DESIGN.md 4.1)
 constexpr uint32_t kCullSlotBits = 6;      // a closest-hit key holds (original index << 6 | LDS slot): kCullMaxTris <= 64
 constexpr uint32_t kCullMaxIndex = 1u << (32 - kCullSlotBits);  // no culling for soups of more triangles
-struct CullCluster {                       // 48 B, read by scalar loads in the bound tests
+struct alignas(64) CullCluster {           // 64 B: the first 32 are what a bound test reads, in one aligned s_load_dwordx8
   float b[6];                              // sphere: centre xyz and squared inflated radius; box: centre xyz, half-width xyz
   uint32_t box;                            // 0: sphere bound, 1: box bound
-  uint32_t first, count;                   // original triangle indices [first, first + count)
+  uint32_t count;                          // original triangle indices [first, first + count)
+  uint32_t first;
   uint32_t slot, magic;                    // first slot of its triangles in the LDS copy; ceil(2^32 / count)
-  uint32_t pad;
+  uint32_t pad[5];
 };
+typedef uint32_t CullWords __attribute__((ext_vector_type(8)));  // b[0..5], box, count
+static_assert(offsetof(CullCluster, box) == 24 && offsetof(CullCluster, count) == 28, "CullWords: the record's first eight words");
+static_assert(sizeof(CullCluster) == 64 && alignof(CullCluster) == 64 && offsetof(CullCluster, first) == 32, "CullCluster layout");
 struct CullRec {                           // 12 B, the block's LDS copy of what a compacted task needs
   uint32_t first, countSlot, magic;        // countSlot = count | slot << 16
 };
@@ -822,10 +826,12 @@ DMT_DEV void brute_clusters(KArgs k, PathState const& st, bool doC, bool doS, Br
     for (uint32_t q = 0; q < kCullGroup; ++q) {
       uint32_t tasks = 0;
       if (c0 + q < nc) {
-        auto const& r = cls[c0 + q];  // scalar loads: c0 + q is uniform
+        // the record's first eight words in one scalar load (c0 + q is uniform): the bound, its kind and the count.  Volatile
+        // keeps it one load at this place: a plain one is sunk into the two arms below, behind their arithmetic
+        CullWords const rw = *reinterpret_cast<CullWords const volatile DMT_CONST_AS*>(cls + (c0 + q));
         CullCluster cl;
-        for (int i = 0; i < 6; ++i) cl.b[i] = r.b[i];
-        cl.box = r.box, cl.count = r.count;
+        for (int i = 0; i < 6; ++i) cl.b[i] = __uint_as_float(rw[i]);
+        cl.box = rw[6], cl.count = rw[7];
         // The verdicts are balloted inside each arm, each ballot of ONE compare, and meet the rays' masks (mDoC, mDoS) in
         // scalar registers.  A ballot of anything but a compare -- a lane boolean merged across this branch, an `and` of
         // two -- is lowered through a VGPR: v_cndmask 0, 1 and v_cmp_ne 0, two expensive instructions per vote, four
@@ -1140,10 +1146,16 @@ DMT_DEV void prepare_lens_ray(KArgs Pk, int px, int py, int32_t pixBase, uint32_
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
 }
+#ifndef DMT_LENS_EARLY
+#define DMT_LENS_EARLY 1  // variant builds for A/B runs: 0 reads the lens radius after the sample's LDS stores
+#endif
 template <bool MOTION = false>  // MOTION: the sample's time is prepared with it (motion.hpp)
 DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
   float* const prep = s_prep + threadIdx.x;
   Ray r;
+#if DMT_LENS_EARLY
+  float const lensR = kargs(Pk)->lensR;  // with the table pointer, so that the compare below finds it ready
+#endif
   if (float4 const* const tab = kargs(Pk)->samTab) {
     KArgs const k = kargs(Pk);
     uint32_t const e = ((s - k->samTabS0) * k->samTabPh + (uint32_t(py) & 127u)) * k->samTabPw + (uint32_t(px) & 127u);
@@ -1166,7 +1178,10 @@ DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t 
   }
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
-  if (__builtin_expect(kargs(Pk)->lensR > 0.f, 0)) prepare_lens_ray(Pk, px, py, pixBase, s);  // wave-uniform, laid out of line
+#if !DMT_LENS_EARLY
+  float const lensR = kargs(Pk)->lensR;
+#endif
+  if (__builtin_expect(lensR > 0.f, 0)) prepare_lens_ray(Pk, px, py, pixBase, s);  // wave-uniform, laid out of line
   if constexpr (MOTION) motion_set_prepared(motion_sample_time(Pk, pixBase, s));
 }
 template <bool MOTION = false>
@@ -2599,6 +2614,17 @@ int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, c
 int dmt_brute_cull_box_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
                                uint32_t* cluster_count, float* cluster_box, float* cluster_record) {
   return cullBoxPlan(xs, ys, zs, mat_id, count, enable, cluster_count, nullptr, cluster_box, cluster_record);
+}
+
+int dmt_cull_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int level,
+                     uint32_t* cluster_count, uint32_t* record_bytes, uint32_t* record_align, void* records) {
+  if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
+  std::vector<CullCluster> const cl = planCullClusters(level, xs, ys, zs, mat_id, count);
+  *cluster_count = uint32_t(cl.size());
+  if (record_bytes) *record_bytes = uint32_t(sizeof(CullCluster));
+  if (record_align) *record_align = uint32_t(alignof(CullCluster));
+  if (records && !cl.empty()) memcpy(records, cl.data(), cl.size() * sizeof(CullCluster));
+  return DMT_OK;
 }
 
 // The device's box bound test on the host, ray by ray: cull_ray, cull_box_axis and cull_box_accept as brute_clusters calls

@@ -339,6 +339,34 @@ __global__ void k_test_closest(RenderParams P, bool useBvh, int n, float const* 
   if (alive) tri[i] = best, tOut[i] = bt;
 }
 
+// dmt_test_trace_pair: one call of the render kernels' trace for the pair (closest ray i, shadow ray i) of every lane, full
+// waves of pairs as the megakernel traces them: what the brute-force pass's culled clusters see of both kinds of ray
+__global__ void k_test_trace_pair(RenderParams P, bool useBvh, int n, float const* o3, float const* d3, float const* so3, float const* sd3,
+                                  float const* smax, int32_t* tri, float* uv2, uint8_t* occ) {
+  KArgs const k = kargs_base();
+  if (!useBvh) cull_stage(k);
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  bool const alive = i < n;
+  PathState st{};
+  if (alive) {
+    set_ray(st, mk3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), mk3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]));
+    set_shadow_ray(st, mk3(so3[3 * i], so3[3 * i + 1], so3[3 * i + 2]), mk3(sd3[3 * i], sd3[3 * i + 1], sd3[3 * i + 2]));
+    st.smax = smax[i];
+  }
+  st.active = alive, st.hasShadow = alive;
+  int best;
+  float bu, bv;
+  bool occluded;
+  if (useBvh)
+    trace_pair_bvh(k, st, alive, alive, blockIdx.x * blockDim.x + threadIdx.x, best, bu, bv, occluded);
+  else
+    trace_pair_brute(k, st, alive, alive, best, bu, bv, occluded);
+  if (alive) {
+    tri[i] = best, occ[i] = occluded ? 1 : 0;
+    uv2[2 * i] = best >= 0 ? bu : 0.f, uv2[2 * i + 1] = best >= 0 ? bv : 0.f;
+  }
+}
+
 // dmt_test_closest_hit_at: the closest hit of ray i against the scene at time[i], by the motion rows' trace of the accel mode
 __global__ void k_test_closest_at(RenderParams P, bool useBvh, int n, float const* o3, float const* d3, float const* time, int32_t* tri,
                                   float* tOut, float* uv2) {
@@ -747,6 +775,27 @@ int dmt_test_closest_hit(dmt_ctx* ctx, int nrays, const float* o3, const float* 
   }
   hipLaunchKernelGGL(k_test_closest, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), useBvh, nrays,
                      dO.get(), dD.get(), di.get(), dt.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_trace_pair(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* so3, const float* sd3, const float* smax,
+                        int32_t* tri_index, float* uv2, uint8_t* occluded) {
+  if (!ctx || nrays < 0 || !o3 || !d3 || !so3 || !sd3 || !smax || !tri_index || !uv2 || !occluded) return DMT_ERR_INVALID;
+  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_pair: upload triangles first");
+  if (nrays == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(nrays));
+  ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3), dSO(p, so3, 3), dSD(p, sd3, 3), dM(p, smax, 1);
+  ProbeOut<int32_t> di(p, tri_index, 1);
+  ProbeOut<float> duv(p, uv2, 2);
+  ProbeOut<uint8_t> docc(p, occluded, 1);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
+  if (useBvh) {
+    if (int const rcT = requireTree(ctx, "dmt_test_trace_pair")) return rcT;
+    HIP_TRY(ctx, reserveOverflow(ctx, p.threads(64)));
+  }
+  hipLaunchKernelGGL(k_test_trace_pair, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, baseParams(ctx, p.threads(64)), useBvh, nrays,
+                     dO.get(), dD.get(), dSO.get(), dSD.get(), dM.get(), di.get(), duv.get(), docc.get());
   return finishProbe(ctx, p);
 }
 

@@ -742,6 +742,15 @@ int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, c
 int dmt_brute_cull_box_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count,
                                int enable, uint32_t* cluster_count, float* cluster_box, float* cluster_record);
 
+/* host-only: the whole cluster table of a soup as the device reads it, sphere clusters first, then box clusters, for
+ * level = what DMT_BRUTE_CULL selects (0 none, 1 spheres, 2 spheres and boxes).  records (may be null) takes cluster_count
+ * <= 12 records of *record_bytes = 64 bytes each, little-endian 32-bit words: [0..5] the bound as float (sphere: centre xyz,
+ * squared inflated radius, 0, 0; box: centre xyz, half-width xyz), [6] 1 for a box bound, [7] triangle count, [8] first
+ * original index, [9] first slot in the block's LDS copy, [10] ceil(2^32 / count), [11..15] zero.  Words 0..7 are what a
+ * bound test loads, in one 32-byte scalar load; *record_align = 64 is the alignment of a record in the device table. */
+int dmt_cull_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int level,
+                     uint32_t* cluster_count, uint32_t* record_bytes, uint32_t* record_align, void* records);
+
 /* host-only: the device's box bound test, the same inline functions compiled for the host (a division stands for the
  * device's reciprocal instruction).  record6 = one cluster_record; ray i: origins[3i .. 3i + 2], dirs[3i .. 3i + 2] and the
  * segment end tmax[i] (inf allowed); accept[i] = 1 when the brute-force pass would test the cluster's triangles for it. */
@@ -868,6 +877,12 @@ int dmt_test_medium_spectrum(dmt_ctx* ctx, const float* k3, int n, const float* 
 int dmt_test_medium_grid(dmt_ctx* ctx, const float* medium7, int nx, int ny, int nz, const float* density, int n, const float* o3,
                          const float* d3, const float* t_end, const float* tau_target, float* tau, float* ts, int32_t* collided,
                          int32_t* steps);
+/* one trace call of the render kernels for the ray pairs (closest ray o3 / d3, shadow ray so3 / sd3 up to smax) under the
+ * current accel mode, a wave of 64 pairs at a time as the megakernel traces them (brute force: the always list, then the
+ * culled clusters): tri_index (-1: none) and barycentrics uv2 (n x 2) of the closest ray's hit, occluded[i] = the shadow
+ * ray meets a triangle before smax[i].  Key 0, solid geometry. */
+int dmt_test_trace_pair(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* so3, const float* sd3, const float* smax,
+                        int32_t* tri_index, float* uv2, uint8_t* occluded);
 /* closest hit of ray i against the scene at time[i], under the current accel mode (the motion tree for DMT_ACCEL_BVH):
  * tri_index (-1: none), t (+inf: none) and, when uv2 is not null, the barycentrics (n x 2).  DMT_ERR_STATE without key 1.
  * dmt_test_closest_hit keeps answering for key 0. */
