@@ -29,6 +29,10 @@ from .binding import (  # noqa: F401
     BVH_UPDATED_REBUILD_AFTER_REFIT,
     light_tree_pmfs,
     light_tree_ref_select,
+    light_tree_nodes,
+    LIGHT_TREE_NODE,
+    LIGHT_TREE_REF_NODE,
+    LIGHT_TREE_LEAF,
     envmap_tables,
     texture_mip_chain,
     texture_footprint,

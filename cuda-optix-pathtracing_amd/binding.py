@@ -65,7 +65,7 @@ def load_library():
 # every symbol include/dmt_hip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED_SYMBOLS = [
     "dmt_ctx_create", "dmt_ctx_destroy", "dmt_last_error", "dmt_upload_triangles", "dmt_upload_bsdfs",
-    "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
+    "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_light_tree_nodes", "dmt_test_light_tree", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
     "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_brute_cull_box_records", "dmt_cull_records", "dmt_cull_box_test", "dmt_test_triangle_intersect",
@@ -455,6 +455,30 @@ def light_tree_ref_select(lights32, p, n, u, start_pmf=1.0):
     return idx, pmf, cnt, nc.value, d.value
 
 
+# one node of the trees dmt_light_tree_nodes returns (csrc/light_tree.hpp LightTreeNode, csrc/light_tree_ref.hpp LightTreeRefNode)
+LIGHT_TREE_NODE = np.dtype([("lo", "<f4", 3), ("phi", "<f4"), ("hi", "<f4", 3), ("ref", "<u4")])
+LIGHT_TREE_REF_NODE = np.dtype([("lo", "<f4", 3), ("phi", "<f4"), ("hi", "<f4", 3), ("varPhi", "<f4"), ("w", "<f4", 3), ("cosTheta_o", "<f4"),
+                                ("cosTheta_e", "<f4"), ("numEmitters", "<u4"), ("left", "<u4"), ("light", "<u4")])
+LIGHT_TREE_LEAF = 0x80000000
+
+
+def light_tree_nodes(lights32, mode, cap=None):
+    """Host-only (dmt_light_tree_nodes): the node array a context uploads for the packed lights under light sampling `mode`
+    (1: LIGHT_TREE_NODE records, 2: LIGHT_TREE_REF_NODE records), root first -> (nodes, depth).  cap: room offered, in nodes
+    (default: what the tree needs); too little is refused."""
+    lib = load_library()
+    L = np.ascontiguousarray(lights32, np.uint8).reshape(-1, 32)
+    nc, d = C.c_int(), C.c_int()
+    if cap is None:
+        lib.dmt_light_tree_nodes(_p(L), C.c_uint32(L.shape[0]), int(mode), None, C.c_uint32(0), C.byref(nc), C.byref(d))
+        cap = nc.value
+    out = np.zeros(max(int(cap), 1), LIGHT_TREE_NODE if int(mode) == 1 else LIGHT_TREE_REF_NODE)
+    rc = lib.dmt_light_tree_nodes(_p(L), C.c_uint32(L.shape[0]), int(mode), _p(out), C.c_uint32(int(cap)), C.byref(nc), C.byref(d))
+    if rc != 0:
+        raise DmtError(f"dmt_light_tree_nodes failed ({rc}): {nc.value} nodes, room for {int(cap)}")
+    return out[:nc.value], d.value
+
+
 def bvh_validate(xs, ys, zs):
     """Host-only BVH build + invariant check; returns dict(node_count, depth, max_leaf, ok)."""
     lib = load_library()
@@ -653,6 +677,12 @@ class Renderer:
         if rc != 0:
             msg = self._lib.dmt_last_error(self._ctx)
             raise DmtError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+    def last_error(self):
+        """dmt_last_error: the context's latest message -- a refused call's reason, or a note such as the light tree's
+        fall-back to the uniform pick."""
+        msg = self._lib.dmt_last_error(self._ctx)
+        return msg.decode() if msg else ""
 
     # ---- uploads ---------------------------------------------------------------------------
     def upload_triangles(self, xs, ys, zs, mat_id):
@@ -1356,6 +1386,17 @@ class Renderer:
         self._check(self._lib.dmt_test_light(self._ctx, _p(l), n, _p(pos), _p(nrm), _p(u2), _p(ht), _p(out)),
                     "dmt_test_light")
         return out
+
+    def test_light_tree(self, pos, nrm, u, start_pmf=1.0):
+        """dmt_test_light_tree: the device's light choice at shading points pos [k,3] with normals nrm [k,3] and one random
+        number each, under the context's light sampling mode -> (indices [k,4] (-1 = none), pmfs [k,4], counts [k])."""
+        pos, nrm, u = _f32(pos, (-1, 3)), _f32(nrm, (-1, 3)), _f32(u, (-1,))
+        k = pos.shape[0]
+        assert nrm.shape[0] == k and u.shape[0] == k
+        idx, pmf, cnt = np.zeros((k, 4), np.int32), np.zeros((k, 4), np.float32), np.zeros(k, np.int32)
+        self._check(self._lib.dmt_test_light_tree(self._ctx, k, _p(pos), _p(nrm), _p(u), C.c_float(start_pmf), _p(idx), _p(pmf), _p(cnt)),
+                    "dmt_test_light_tree")
+        return idx, pmf, cnt
 
     def test_half(self, floats=None, halves=None):
         h_out = f_out = None

@@ -2220,34 +2220,44 @@ std::vector<LightTreeRefNode> buildLightTreeRef(uint8_t const* lights32, uint32_
   }
   return light_tree_ref::build(items, depth);
 }
+// the DMT_LIGHTS_TREE tree of a packed light list, as buildLightTreeRef is DMT_LIGHTS_TREE_REFERENCE's
+std::vector<LightTreeNode> buildLightTree(uint8_t const* lights32, uint32_t count, int* depth, bool* ok) {
+  std::vector<light_tree::Item> items;
+  *ok = true;
+  for (uint32_t i = 0; i < count; ++i) {
+    light_tree::Item it{};
+    if (!light_tree::itemOf(lights32 + 32 * size_t(i), i, [](uint16_t h) { return h2f_host(h); }, it)) {
+      *ok = false;
+      return {};
+    }
+    items.push_back(it);
+  }
+  return light_tree::build(items, depth);
+}
+// a tree deeper than the walks' guard (lights at geometrically growing spacing) would cut paths short: the context keeps the
+// uniform pick and says so through dmt_last_error; the call that found out goes on
+int keepUniformPick(dmt_ctx* ctx, int guard) {
+  ctx->lightTreeTooDeep = true;
+  ctx->err = "light tree: its depth of " + std::to_string(ctx->lightTreeDepth) + " exceeds the walk's guard of " + std::to_string(guard) +
+             " levels; the uniform pick is used instead";
+  return DMT_OK;
+}
 // (re)build the light tree from the host copy of the light records and upload it
 int ensureLightTree(dmt_ctx* ctx) {
   if (ctx->lightTreeValid) return DMT_OK;
+  bool ok = true;
   if (ctx->lightSampling == DMT_LIGHTS_TREE_REFERENCE) {
-    bool ok = true;
     std::vector<LightTreeRefNode> const nodes = buildLightTreeRef(ctx->h_lights.data(), ctx->lightCount, &ctx->lightTreeDepth, &ok);
     if (!ok) return fail(ctx, DMT_ERR_STATE, "light tree: only point and spot lights can be in the light list");
-    if (ctx->lightTreeDepth > kLightTreeRefMaxDepth) {
-      ctx->lightTreeTooDeep = true;
-      return DMT_OK;
-    }
+    if (ctx->lightTreeDepth > kLightTreeRefMaxDepth) return keepUniformPick(ctx, kLightTreeRefMaxDepth);
     HIP_TRY(ctx, ctx->d_lightTreeRef.assign(nodes.data(), nodes.size()));
     ctx->lightTreeNodes = uint32_t(nodes.size());
     ctx->lightTreeValid = true;
     return DMT_OK;
   }
-  std::vector<light_tree::Item> items;
-  for (uint32_t i = 0; i < ctx->lightCount; ++i) {
-    light_tree::Item it{};
-    if (!light_tree::itemOf(ctx->h_lights.data() + 32 * size_t(i), i, [](uint16_t h) { return h2f_host(h); }, it))
-      return fail(ctx, DMT_ERR_STATE, "light tree: only point and spot lights can be in the light list");
-    items.push_back(it);
-  }
-  std::vector<LightTreeNode> const nodes = light_tree::build(items, &ctx->lightTreeDepth);
-  if (ctx->lightTreeDepth > 60) {  // lights at geometrically growing spacing: the walk's guard would cut paths short -> uniform pick
-    ctx->lightTreeTooDeep = true;
-    return DMT_OK;
-  }
+  std::vector<LightTreeNode> const nodes = buildLightTree(ctx->h_lights.data(), ctx->lightCount, &ctx->lightTreeDepth, &ok);
+  if (!ok) return fail(ctx, DMT_ERR_STATE, "light tree: only point and spot lights can be in the light list");
+  if (ctx->lightTreeDepth > 60) return keepUniformPick(ctx, 60);
   HIP_TRY(ctx, ctx->d_lightTree.assign(nodes.data(), nodes.size()));
   ctx->lightTreeNodes = uint32_t(nodes.size());
   ctx->lightTreeValid = true;
@@ -2468,14 +2478,10 @@ int dmt_set_light_sampling(dmt_ctx* ctx, int mode) {
 int dmt_light_tree_pmfs(const void* lights32, uint32_t count, const float* p3, const float* n3, float* pmf_out, int* node_count,
                         int* depth) {
   if ((count && !lights32) || !p3 || !n3 || !pmf_out) return DMT_ERR_INVALID;
-  std::vector<light_tree::Item> items;
-  for (uint32_t i = 0; i < count; ++i) {
-    light_tree::Item it{};
-    if (!light_tree::itemOf(static_cast<uint8_t const*>(lights32) + 32 * size_t(i), i, [](uint16_t h) { return h2f_host(h); }, it)) return DMT_ERR_INVALID;
-    items.push_back(it);
-  }
+  bool ok = true;
   int d = 0;
-  std::vector<LightTreeNode> const nodes = light_tree::build(items, &d);
+  std::vector<LightTreeNode> const nodes = buildLightTree(static_cast<uint8_t const*>(lights32), count, &d, &ok);
+  if (!ok) return DMT_ERR_INVALID;
   light_tree::pmfs(nodes, p3, n3, pmf_out, count);
   if (node_count) *node_count = int(nodes.size());
   if (depth) *depth = d;
@@ -2499,6 +2505,25 @@ int dmt_light_tree_ref_select(const void* lights32, uint32_t count, int n, const
     for (int k = 0; k < kLightTreeMaxSplitSize; ++k)
       indices4[4 * i + k] = k < int(sel.count) ? int32_t(sel.indices[k]) : -1, pmfs4[4 * i + k] = k < int(sel.count) ? sel.pmfs[k] : 0.f;
   }
+  return DMT_OK;
+}
+
+// host only: the node array ensureLightTree uploads for `mode`, by the same builder call
+int dmt_light_tree_nodes(const void* lights32, uint32_t count, int mode, void* nodes_out, uint32_t cap, int* node_count, int* depth) {
+  if ((count && !lights32) || (cap && !nodes_out) || (mode != DMT_LIGHTS_TREE && mode != DMT_LIGHTS_TREE_REFERENCE)) return DMT_ERR_INVALID;
+  bool ok = true;
+  int d = 0;
+  std::vector<LightTreeNode> nodes;
+  std::vector<LightTreeRefNode> refNodes;
+  if (mode == DMT_LIGHTS_TREE) nodes = buildLightTree(static_cast<uint8_t const*>(lights32), count, &d, &ok);
+  else refNodes = buildLightTreeRef(static_cast<uint8_t const*>(lights32), count, &d, &ok);
+  if (!ok) return DMT_ERR_INVALID;
+  size_t const n = mode == DMT_LIGHTS_TREE ? nodes.size() : refNodes.size();
+  if (node_count) *node_count = int(n);
+  if (depth) *depth = d;
+  if (n > cap) return DMT_ERR_INVALID;  // the counts are reported: ask again with room for them
+  if (n) memcpy(nodes_out, mode == DMT_LIGHTS_TREE ? static_cast<void const*>(nodes.data()) : static_cast<void const*>(refNodes.data()),
+                n * (mode == DMT_LIGHTS_TREE ? sizeof(LightTreeNode) : sizeof(LightTreeRefNode)));
   return DMT_OK;
 }
 

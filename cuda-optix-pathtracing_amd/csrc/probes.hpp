@@ -484,6 +484,30 @@ __global__ void k_test_project(ProjXf c, int n, float const* p3, float* xy2, flo
   xy2[2 * i] = o.fx, xy2[2 * i + 1] = o.fy, depth[i] = o.depth;
 }
 
+// dmt_test_light_tree: the light choice of a bounce at (pos3, nrm3) with the random number u, by the function the rows of the
+// context's tree call on the tree they read.  REF: ltr_select's cut of up to four lights (*_ltree2); otherwise lt_select's one
+// light, its probability formed as path_shade forms it (*_ltree).  Slots past counts[i] hold -1 / 0.
+template <bool REF>
+__global__ void k_test_light_tree(RenderParams P, int n, float const* pos3, float const* nrm3, float const* u, float startPmf,
+                                  int32_t* idx4, float* pmf4, int32_t* counts) {
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  LightTreeRefSelection sel{};
+  if constexpr (REF) {
+    sel = ltr_select(kargs(k)->lightTreeRef, pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2], nrm3[3 * i], nrm3[3 * i + 1], nrm3[3 * i + 2],
+                     u[i], startPmf);
+  } else {
+    float treePmf = 0.f;
+    int const li = lt_select(kargs(k)->lightTree, pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2], nrm3[3 * i], nrm3[3 * i + 1],
+                             nrm3[3 * i + 2], u[i], treePmf);
+    if (li >= 0) sel.indices[0] = uint32_t(li), sel.pmfs[0] = startPmf * treePmf, sel.count = 1u;
+  }
+  counts[i] = int32_t(sel.count);
+  for (uint32_t s = 0; s < uint32_t(kLightTreeMaxSplitSize); ++s)
+    idx4[4 * i + s] = s < sel.count ? int32_t(sel.indices[s]) : -1, pmf4[4 * i + s] = s < sel.count ? sel.pmfs[s] : 0.f;
+}
+
 typedef void (*TestTraceFn)(RenderParams, int, int32_t const*, int32_t const*, int32_t const*, float*);
 #define DMT_TEST_TRACE_ROW(suffix, mask, waves, body) {mask, k_test_trace<mask>},
 KernelRow<TestTraceFn> const kTestTraceKernels[] = {DMT_MEGAKERNELS(DMT_TEST_TRACE_ROW)};
@@ -683,6 +707,36 @@ int dmt_test_light(dmt_ctx* ctx, const void* light32, int n, const float* pos3, 
   memcpy(&rec, light32, 32);
   hipLaunchKernelGGL(k_test_light, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, rec, n, dp.get(), dn.get(), du.get(), dh.get(),
                      dout.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_light_tree(dmt_ctx* ctx, int n, const float* pos3, const float* nrm3, const float* u, float start_pmf, int32_t* indices4,
+                        float* pmfs4, int32_t* counts) {
+  if (!ctx || n < 0 || !pos3 || !nrm3 || !u || !indices4 || !pmfs4 || !counts) return DMT_ERR_INVALID;
+  if (!ctx->haveLights) return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: upload lights first");
+  if (ctx->lightSampling == DMT_LIGHTS_UNIFORM)
+    return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: the context picks its lights uniformly (dmt_set_light_sampling first)");
+  if (ctx->lightCount <= 1) return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: a tree needs more than one light; the uniform pick is used");
+  uint32_t F = 0;  // the tree dmt_render would read, built first
+  if (int const rc = resolveFeatures(ctx, &F)) return rc;
+  if (ctx->lightTreeTooDeep)
+    return fail(ctx, DMT_ERR_STATE, ("dmt_test_light_tree: the light tree is too deep for the walk's guard (" + std::to_string(ctx->lightTreeDepth) +
+                                     " levels); the uniform pick is used instead").c_str());
+  if (!(F & (kFeatLightTree | kFeatLightTreeRef)))
+    return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: this scene keeps the uniform pick (a light tree takes point and spot lights, "
+                                    "without emissive triangles, image textures or blend materials)");
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<float> dP(p, pos3, 3), dN(p, nrm3, 3), dU(p, u, 1);
+  ProbeOut<int32_t> dI(p, indices4, 4), dC(p, counts, 1);
+  ProbeOut<float> dPmf(p, pmfs4, 4);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  RenderParams const P = baseParams(ctx, p.threads(64));
+  bool const ref = (F & kFeatLightTreeRef) != 0;
+  if (!(ref ? static_cast<void const*>(P.lightTreeRef) : static_cast<void const*>(P.lightTree)))
+    return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: no light tree on the device");
+  hipLaunchKernelGGL(ref ? k_test_light_tree<true> : k_test_light_tree<false>, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, n, dP.get(),
+                     dN.get(), dU.get(), start_pmf, dI.get(), dPmf.get(), dC.get());
   return finishProbe(ctx, p);
 }
 

@@ -445,6 +445,11 @@ int dmt_light_tree_ref_select(const void* lights32, uint32_t count, int n, const
 /* host only (no GPU): probability of each of the `count` packed lights at point p3 with normal n3 under the tree */
 int dmt_light_tree_pmfs(const void* lights32, uint32_t count, const float* p3, const float* n3, float* pmf_out, int* node_count,
                         int* depth);
+/* host only (no GPU): the node array a context uploads for the `count` packed lights under `mode`, root first -- 32-byte
+ * records for DMT_LIGHTS_TREE (csrc/light_tree.hpp LightTreeNode), 64-byte records for DMT_LIGHTS_TREE_REFERENCE
+ * (csrc/light_tree_ref.hpp LightTreeRefNode).  nodes_out has room for `cap` records; node_count and depth are always
+ * reported, and a cap below node_count is refused (DMT_ERR_INVALID) with nothing written to nodes_out. */
+int dmt_light_tree_nodes(const void* lights32, uint32_t count, int mode, void* nodes_out, uint32_t cap, int* node_count, int* depth);
 /* How DMT_ACCEL_BVH launches are executed (results are bit-identical either way): 0 = automatic = 1 = the megakernel
  * (fastest on every measured scene); 2 = the device-side wavefront -- generate / trace / shade / fold kernels over
  * path-state arrays in HBM, csrc/wavefront.hpp -- kept as a measured alternative.  paths_per_pass: path
@@ -921,6 +926,14 @@ int dmt_test_material(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, 
                       float* ns3, void* rec2_32, float* mix);
 int dmt_test_light(dmt_ctx* ctx, const void* light32, int n, const float* pos3, const float* nrm3,
                    const float* u2, const int32_t* had_transmission, float* out14);
+/* the light choice of a bounce at n shading points (pos3, nrm3) with one random number u each, on the device: the selection
+ * function of the context's light sampling mode on the tree it built from the uploaded lights.  DMT_LIGHTS_TREE: counts[i] is
+ * 0 or 1, indices4[4 i] the light and pmfs4[4 i] = start_pmf x the tree's probability; DMT_LIGHTS_TREE_REFERENCE: the cut's
+ * up to four (light, pmf) pairs as dmt_light_tree_ref_select returns them.  Slots past counts[i] hold -1 / 0.  DMT_ERR_STATE
+ * where the context would not use a tree: uniform mode, fewer than two lights, a list that cannot be put in a tree, a tree
+ * deeper than the walk's guard. */
+int dmt_test_light_tree(dmt_ctx* ctx, int n, const float* pos3, const float* nrm3, const float* u, float start_pmf, int32_t* indices4,
+                        float* pmfs4, int32_t* counts);
 int dmt_test_half(dmt_ctx* ctx, int n, const float* f_in, uint16_t* h_out, const uint16_t* h_in,
                   float* f_out);
 /* radiance of individual (pixel, sample) paths of the uploaded scene */

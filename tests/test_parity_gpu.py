@@ -1278,14 +1278,14 @@ def test_texture_upload_is_validated(renderer, pkg, O):
 # ---------------------------------------------------------------------------------------------
 # light tree (opt-in; the uniform pick stays the parity mode).  Parity unpinned: oracle <-> HIP only.
 # ---------------------------------------------------------------------------------------------
-def _many_lights_cornell(O, pkg, res, nlights=48, env=False):
+def _many_lights_cornell(O, pkg, res, nlights=48, env=False, radius=2e-4):
     from test_light_tree import _lights
     sc = O.cornell_box(res, res)
     # radius 2e-4: "effectively delta" lights (radius / distance < 1e-3, light.cu:29,131), the kind the JSON front-end
     # makes.  For those NEE is Le f / pmf and any selection probability gives the same expected image.  For larger
     # lights the reference weights NEE by a power heuristic that is NOT divided by the light pdf (megakernel.cu:233-238,
     # kept for parity): its expectation depends on the selection probabilities, so there the tree changes the picture.
-    L = _lights(pkg, nlights, 11, spread=0.9, radius=2e-4)
+    L = _lights(pkg, nlights, 11, spread=0.9, radius=radius)
     pos = L[:, 8:20].copy().view(np.float32).reshape(-1, 3)
     pos[:] = pos * [1.0, 0.25, 0.9] + [0.0, 0.5, 0.6]             # inside the box (y 1..3, z -0.3..1.5), near the ceiling
     L[:, 8:20] = pos.view(np.uint8).reshape(-1, 12)
@@ -1364,6 +1364,37 @@ def test_reference_light_tree_film_vs_oracle(renderer, pkg, O, accel, env):
     assert film_rmse(mean, om) < RMSE_TOL * max(1.0, scale), film_rmse(mean, om)
     # several lights per bounce: less variance than the single-light tree on the same scene
     assert float(m2[..., :3].mean()) < float(sm2[..., :3].mean()), (float(m2[..., :3].mean()), float(sm2[..., :3].mean()))
+
+
+@pytest.mark.parametrize("mode, accel", [(1, 0), (1, 1), (2, 0), (2, 1)])
+def test_light_tree_film_with_lights_of_visible_size_vs_oracle(renderer, pkg, O, mode, accel):
+    """Lights of radius 0.05 are not "effectively delta": NEE takes the power-heuristic branch, w = (pmf pdf)^2 / (pmf pdf +
+    bsdfPdf)^2, the one where the tree's selection probability changes the expected image.  Both trees, both traces, against
+    the oracle."""
+    sc = _many_lights_cornell(O, pkg, 32, radius=0.05)
+    sc.light_sampling = mode
+    walls = [np.stack([sc.xs[t, :3], sc.ys[t, :3], sc.zs[t, :3]], -1).mean(0) for t in (0, 3, 6, 9)]
+    for rec in sc.lights[:6]:                                           # spot (radius 0.025) and point lights (0.05) alike
+        out = renderer.test_light(rec, walls, np.tile([0.0, 0.0, 1.0], (len(walls), 1)), np.full((len(walls), 2), 0.5), np.zeros(len(walls)))
+        assert (out[:, 7] == 0).all()                                   # delta == 0 at the walls
+    renderer.upload_scene(sc)
+    renderer.set_limits(4)
+    renderer.set_accel(accel)
+    renderer.set_partition(0, 1)
+    try:
+        renderer.set_light_sampling(mode)
+        renderer.film_clear()
+        renderer.render(16)
+        renderer.sync()
+        mean, m2 = renderer.download_film()
+    finally:
+        renderer.set_light_sampling(0)
+        renderer.set_accel(0)
+    om, om2 = O.render(sc, 16, max_depth=4, threads=8)[:2]
+    assert np.array_equal(m2[..., 3], om2[..., 3]) and np.isfinite(mean).all()
+    scale = float(om[..., :3].mean())
+    assert scale > 0.01
+    assert film_rmse(mean, om) < RMSE_TOL * max(1.0, scale), film_rmse(mean, om)
 
 
 def test_light_tree_converges_to_the_uniform_image(renderer, pkg, O):

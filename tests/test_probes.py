@@ -18,7 +18,7 @@ def probe_declarations():
 def null_argument(param):
     if "*" in param:
         return C.c_void_p(None)
-    ctype = {"int": C.c_int, "size_t": C.c_size_t, "uint32_t": C.c_uint32}[param.split()[0]]
+    ctype = {"int": C.c_int, "size_t": C.c_size_t, "uint32_t": C.c_uint32, "float": C.c_float}[param.split()[0]]
     return ctype(0)
 
 

@@ -145,6 +145,19 @@ def test_envmap_staging(renderer, scene, cases):
         renderer.clear_envmap()
 
 
+@pytest.mark.parametrize("mode", [1, 2])
+def test_light_tree_staging(renderer, pkg, scene, cases, mode):
+    from test_light_tree_select import light_set
+    renderer.upload_lights(light_set(pkg, "n17"), [])
+    renderer.set_light_sampling(mode)
+    try:
+        pos = cases.points * 3.0 + np.array([0.0, 6.0, 0.0], np.float32)
+        full = same_at_every_size(lambda n: renderer.test_light_tree(pos[:n], cases.dir[:n], cases.u2[:n, 0]), SIZES)
+        assert full[2].max() >= 1
+    finally:
+        renderer.set_light_sampling(0)
+
+
 def test_camera_staging(renderer, scene, cases):
     c = cases
     same_at_every_size(lambda n: renderer.test_camera_rays(c.px[:n], c.py[:n], c.s[:n]), SIZES)
