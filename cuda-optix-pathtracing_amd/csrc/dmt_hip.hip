@@ -1776,6 +1776,7 @@ __global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
 #include "accel_state.hpp"
 #include "surface_state.hpp"
 #include "medium_state.hpp"
+#include "light_state.hpp"
 #include "launch_state.hpp"
 
 struct dmt_ctx {
@@ -1786,8 +1787,8 @@ struct dmt_ctx {
   // scene
   DevBuf<TriIsect> d_tris;
   DevBuf<TriPost> d_post;
-  DevBuf<Rec32> d_bsdfs, d_lights, d_inf;
-  uint32_t triCount = 0, bsdfCount = 0, lightCount = 0, infCount = 0;
+  DevBuf<Rec32> d_bsdfs;
+  uint32_t triCount = 0, bsdfCount = 0;
   uint32_t maxMatId = 0;
   // the brute-force pass's culled clusters (planBruteCull, planBruteCullBox); none: the pass tests d_tris for every ray
   int bruteCull = 2;  // DMT_BRUTE_CULL at context creation (A/B runs, tests): 0 no clusters, 1 sphere clusters only, unset both
@@ -1796,23 +1797,13 @@ struct dmt_ctx {
   std::vector<uint32_t> h_mat;
   // the acceleration layer: the static and the motion tree, builder and update policy, key 1 (accel_state.hpp, accel_host.hpp)
   AccelState ac;
-  // light tree (light_tree.hpp): built from the uploaded lights when dmt_set_light_sampling asks for it
-  int lightSampling = DMT_LIGHTS_UNIFORM;
-  std::vector<uint8_t> h_lights;  // host copy of the packed light records
-  DevBuf<LightTreeNode> d_lightTree;
-  DevBuf<LightTreeRefNode> d_lightTreeRef;  // DMT_LIGHTS_TREE_REFERENCE
-  uint32_t lightTreeNodes = 0;
-  int lightTreeDepth = 0;
-  bool lightTreeValid = false;
-  bool lightTreeTooDeep = false;   // the last build exceeded the walk's depth guard: the uniform pick is used instead (dmt_last_error says so)
-  bool lightsTreeable = false;     // every record of the light list is a point or spot light
+  // the light layer: the light list, the light tree over it and the env map (light_state.hpp, light_host.hpp)
+  LightState lights;
   // the surface-attribute layer: textures and UVs, the texture filter, vertex normals, opacity records, emissive triangles
   // (surface_state.hpp, surface_host.hpp)
   SurfaceState surf;
   bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_blend kernels carry that code
-  DevBuf<float> d_env;     // A18: one allocation holding the five tables and the image
-  EnvView env{};           // env.w == 0: no env map
-  bool haveTris = false, haveBsdfs = false, haveLights = false, haveCamera = false;
+  bool haveTris = false, haveBsdfs = false, haveCamera = false;
   // camera
   dmt_camera cam{};
   CameraXf xf{};
@@ -1837,27 +1828,6 @@ struct dmt_ctx {
 namespace {
 
 std::string g_createError;
-
-float h2f_host(uint16_t h) {  // exact fp16 -> fp32 (CC/private/encoding.cu:124-155)
-  uint32_t const sgn = uint32_t(h & 0x8000u) << 16;
-  uint32_t e = (h >> 10) & 0x1Fu, m = h & 0x3FFu, out;
-  if (e == 0) {
-    if (m == 0) {
-      out = sgn;
-    } else {
-      e = 113;
-      while (!(m & 0x400u)) m <<= 1, --e;
-      out = sgn | (e << 23) | ((m & 0x3FFu) << 13);
-    }
-  } else if (e == 31) {
-    out = sgn | 0x7F800000u | (m << 13);
-  } else {
-    out = sgn | ((e + 112) << 23) | (m << 13);
-  }
-  float f;
-  memcpy(&f, &out, 4);
-  return f;
-}
 
 #define HIP_TRY(ctx, call)                                                                 \
   do {                                                                                     \
@@ -2065,30 +2035,26 @@ SamplerParams computeSamplerParams(int width, int height) {
   return p;
 }
 
-// The feature mask (kFeat*) of what a launch of this context needs.  The light tree applies to plain point / spot light
-// lists; textured or emissive-triangle scenes keep the uniform pick.  A light tree not built yet counts as applying:
-// resolveFeatures builds it first.
+// The feature mask (kFeat*) of what a launch of this context needs.  The light and the medium layer give their own bits; the
+// light tree applies to plain surfaces only: textured or emissive-triangle scenes keep the uniform pick.
+bool plainSurfaces(dmt_ctx const* c) { return c->surf.area.count == 0 && c->surf.tex.count == 0 && !c->hasBlend; }
 uint32_t featuresOf(dmt_ctx const* c) {
-  bool const treeable = !c->lightTreeTooDeep && c->lightCount > 1 && c->lightsTreeable && c->surf.area.count == 0 && c->surf.tex.count == 0 && !c->hasBlend;
   uint32_t F = 0;
   if (c->accel == DMT_ACCEL_BVH) F |= kFeatBvh;
-  if (c->env.w > 0) F |= kFeatEnv;
   if (c->surf.area.count > 0) F |= kFeatArea;
   if (c->hasBlend) F |= kFeatBlend;  // the blend kernels carry the texture code too
   else if (c->surf.tex.count > 0) F |= kFeatTex;
-  if (treeable && c->lightSampling == DMT_LIGHTS_TREE) F |= kFeatLightTree;
-  if (treeable && c->lightSampling == DMT_LIGHTS_TREE_REFERENCE) F |= kFeatLightTreeRef;
   if (c->surf.texFilter == DMT_TEXFILTER_REFERENCE && (F & (kFeatTex | kFeatBlend))) F |= kFeatTexFilter;
   if (c->ac.haveMotion) F |= kFeatMotion;
   if (c->surf.vn.have) F |= kFeatVtxNormals;
   if (c->surf.op.have) F |= kFeatCutout;
-  return F | c->medium.features();
+  return F | c->lights.features(plainSurfaces(c)) | c->medium.features();
 }
 int ensureLightTree(dmt_ctx* ctx);
 // featuresOf once the light tree it asks for is built: a tree deeper than the walk's guard switches the context back to the
-// uniform pick (lightTreeTooDeep), which changes the kernel, its occupancy and the launch shape
+// uniform pick (LightState::Tree::tooDeep), which changes the kernel, its occupancy and the launch shape
 int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
-  if ((featuresOf(ctx) & (kFeatLightTree | kFeatLightTreeRef)) && !ctx->lightTreeValid) {
+  if (featuresOf(ctx) & (kFeatLightTree | kFeatLightTreeRef)) {
     if (int const rc = ensureLightTree(ctx)) return rc;
   }
   *mask = featuresOf(ctx);
@@ -2164,21 +2130,17 @@ void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const*
 // records that probes.hpp uses
 #include "medium_host.hpp"
 
-namespace {
+// the light layer's helpers and entry points: the light list, the sampling mode, the one builder of the two light trees
+// and the lazy build that resolveFeatures calls, the env map
+#include "light_host.hpp"
 
-SceneView sceneView(dmt_ctx const* c) {
-  SceneView s;
-  s.tris = c->d_tris.get(), s.post = c->d_post.get(), s.bsdfs = c->d_bsdfs.get(), s.lights = c->d_lights.get();
-  s.infLights = c->d_inf.get();
-  s.triCount = c->triCount, s.bsdfCount = c->bsdfCount, s.lightCount = c->lightCount;
-  s.infLightCount = c->infCount;
-  return s;
-}
+namespace {
 
 // scene / camera / limits part of the argument struct (what the path-tracing device code reads)
 RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   RenderParams P{};
-  P.scene = sceneView(c);
+  P.scene.tris = c->d_tris.get(), P.scene.post = c->d_post.get(), P.scene.bsdfs = c->d_bsdfs.get();
+  P.scene.triCount = c->triCount, P.scene.bsdfCount = c->bsdfCount;
   P.cull = cullView(c);
   P.bvh = bvhView(c, threads);
   P.cam = c->xf;
@@ -2186,82 +2148,10 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.lensR = c->lensR, P.lensD = c->lensD;
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
-  P.env = c->env;
+  c->lights.fill(P, plainSurfaces(c));
   c->medium.fill(P);
   c->surf.fill(P);
-  uint32_t const F = featuresOf(c);
-  if ((F & kFeatLightTree) && c->lightTreeValid) P.lightTree = c->d_lightTree.get();
-  if ((F & kFeatLightTreeRef) && c->lightTreeValid) P.lightTreeRef = c->d_lightTreeRef.get();
   return P;
-}
-
-// octahedral decode on the host (CC/private/encoding.cu:39-60), as pt_device.hpp's dir_from_octa
-void octa_host(uint32_t octa, float out[3]) {
-  float const mx = 65535.f;
-  float const fx = float(octa & 0xFFFFu) / mx * 2.f - 1.f, fy = float((octa >> 16) & 0xFFFFu) / mx * 2.f - 1.f;
-  float n[3] = {fx, fy, 1.f - fabsf(fx) - fabsf(fy)};
-  if (n[2] < 0.f) {
-    n[0] = (1.f - fabsf(fy)) * (std::signbit(fx) ? -1.f : 1.f);
-    n[1] = (1.f - fabsf(fx)) * (std::signbit(fy) ? -1.f : 1.f);
-  }
-  float const inv = 1.f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-  out[0] = n[0] * inv, out[1] = n[1] * inv, out[2] = n[2] * inv;
-}
-std::vector<LightTreeRefNode> buildLightTreeRef(uint8_t const* lights32, uint32_t count, int* depth, bool* ok) {
-  std::vector<light_tree_ref::Item> items;
-  *ok = true;
-  for (uint32_t i = 0; i < count; ++i) {
-    light_tree_ref::Item it{};
-    if (!light_tree_ref::itemOf(lights32 + 32 * size_t(i), i, [](uint16_t h) { return h2f_host(h); }, [](uint32_t o, float* d) { octa_host(o, d); }, it)) {
-      *ok = false;
-      return {};
-    }
-    items.push_back(it);
-  }
-  return light_tree_ref::build(items, depth);
-}
-// the DMT_LIGHTS_TREE tree of a packed light list, as buildLightTreeRef is DMT_LIGHTS_TREE_REFERENCE's
-std::vector<LightTreeNode> buildLightTree(uint8_t const* lights32, uint32_t count, int* depth, bool* ok) {
-  std::vector<light_tree::Item> items;
-  *ok = true;
-  for (uint32_t i = 0; i < count; ++i) {
-    light_tree::Item it{};
-    if (!light_tree::itemOf(lights32 + 32 * size_t(i), i, [](uint16_t h) { return h2f_host(h); }, it)) {
-      *ok = false;
-      return {};
-    }
-    items.push_back(it);
-  }
-  return light_tree::build(items, depth);
-}
-// a tree deeper than the walks' guard (lights at geometrically growing spacing) would cut paths short: the context keeps the
-// uniform pick and says so through dmt_last_error; the call that found out goes on
-int keepUniformPick(dmt_ctx* ctx, int guard) {
-  ctx->lightTreeTooDeep = true;
-  ctx->err = "light tree: its depth of " + std::to_string(ctx->lightTreeDepth) + " exceeds the walk's guard of " + std::to_string(guard) +
-             " levels; the uniform pick is used instead";
-  return DMT_OK;
-}
-// (re)build the light tree from the host copy of the light records and upload it
-int ensureLightTree(dmt_ctx* ctx) {
-  if (ctx->lightTreeValid) return DMT_OK;
-  bool ok = true;
-  if (ctx->lightSampling == DMT_LIGHTS_TREE_REFERENCE) {
-    std::vector<LightTreeRefNode> const nodes = buildLightTreeRef(ctx->h_lights.data(), ctx->lightCount, &ctx->lightTreeDepth, &ok);
-    if (!ok) return fail(ctx, DMT_ERR_STATE, "light tree: only point and spot lights can be in the light list");
-    if (ctx->lightTreeDepth > kLightTreeRefMaxDepth) return keepUniformPick(ctx, kLightTreeRefMaxDepth);
-    HIP_TRY(ctx, ctx->d_lightTreeRef.assign(nodes.data(), nodes.size()));
-    ctx->lightTreeNodes = uint32_t(nodes.size());
-    ctx->lightTreeValid = true;
-    return DMT_OK;
-  }
-  std::vector<LightTreeNode> const nodes = buildLightTree(ctx->h_lights.data(), ctx->lightCount, &ctx->lightTreeDepth, &ok);
-  if (!ok) return fail(ctx, DMT_ERR_STATE, "light tree: only point and spot lights can be in the light list");
-  if (ctx->lightTreeDepth > 60) return keepUniformPick(ctx, 60);
-  HIP_TRY(ctx, ctx->d_lightTree.assign(nodes.data(), nodes.size()));
-  ctx->lightTreeNodes = uint32_t(nodes.size());
-  ctx->lightTreeValid = true;
-  return DMT_OK;
 }
 
 int finishTest(dmt_ctx* ctx) {
@@ -2404,31 +2294,6 @@ int dmt_upload_bsdfs(dmt_ctx* ctx, const void* bsdf32, uint32_t count) {
   return DMT_OK;
 }
 
-int dmt_upload_lights(dmt_ctx* ctx, const void* lights32, uint32_t count, const void* infinite32,
-                      uint32_t infinite_count) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if ((count && !lights32) || (infinite_count && !infinite32))
-    return fail(ctx, DMT_ERR_INVALID, "dmt_upload_lights: null array");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DevBuf<Rec32> lights, inf;
-  HIP_TRY(ctx, lights.assign(lights32, count));
-  HIP_TRY(ctx, inf.assign(infinite32, infinite_count));
-  ctx->d_lights = std::move(lights), ctx->d_inf = std::move(inf);
-  ctx->lightCount = count;
-  ctx->infCount = infinite_count;
-  ctx->haveLights = true;
-  ctx->h_lights.assign(static_cast<uint8_t const*>(lights32), static_cast<uint8_t const*>(lights32) + size_t(count) * 32);
-  ctx->lightTreeValid = false;
-  ctx->lightTreeTooDeep = false;
-  ctx->lightsTreeable = count > 0;
-  for (uint32_t i = 0; i < count; ++i) {  // a directional light in the list (PBRT "distant") has no position: such lists keep the uniform pick
-    uint16_t type;
-    memcpy(&type, ctx->h_lights.data() + 32 * size_t(i) + 6, 2);
-    if (type != 0 && type != 1) ctx->lightsTreeable = false;
-  }
-  return DMT_OK;
-}
-
 int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam) {
   if (!ctx) return DMT_ERR_INVALID;
   if (!cam || cam->width <= 0 || cam->height <= 0 || cam->width > 65536 || cam->height > 65536)
@@ -2462,68 +2327,6 @@ int dmt_set_limits(dmt_ctx* ctx, int max_depth) {
   if (!ctx) return DMT_ERR_INVALID;
   if (max_depth < 0) return fail(ctx, DMT_ERR_INVALID, "dmt_set_limits: max_depth < 0");
   ctx->maxDepth = max_depth;
-  return DMT_OK;
-}
-
-int dmt_set_light_sampling(dmt_ctx* ctx, int mode) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (mode != DMT_LIGHTS_UNIFORM && mode != DMT_LIGHTS_TREE && mode != DMT_LIGHTS_TREE_REFERENCE)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_set_light_sampling: unknown mode");
-  if (mode != ctx->lightSampling) ctx->lightTreeValid = false, ctx->lightTreeTooDeep = false;  // the two trees are different structures
-  ctx->lightSampling = mode;
-  return DMT_OK;
-}
-
-// host only: the probability with which the light tree built from `lights32` picks each light at (p, n)
-int dmt_light_tree_pmfs(const void* lights32, uint32_t count, const float* p3, const float* n3, float* pmf_out, int* node_count,
-                        int* depth) {
-  if ((count && !lights32) || !p3 || !n3 || !pmf_out) return DMT_ERR_INVALID;
-  bool ok = true;
-  int d = 0;
-  std::vector<LightTreeNode> const nodes = buildLightTree(static_cast<uint8_t const*>(lights32), count, &d, &ok);
-  if (!ok) return DMT_ERR_INVALID;
-  light_tree::pmfs(nodes, p3, n3, pmf_out, count);
-  if (node_count) *node_count = int(nodes.size());
-  if (depth) *depth = d;
-  return DMT_OK;
-}
-
-// host only: cut + selection of the reference-semantics tree at n shading points (light_tree_ref.hpp's ltr_select, the
-// function the *_ltree2 kernels call)
-int dmt_light_tree_ref_select(const void* lights32, uint32_t count, int n, const float* p3, const float* n3, const float* u, float start_pmf,
-                              int32_t* indices4, float* pmfs4, int32_t* counts, int* node_count, int* depth) {
-  if ((count && !lights32) || n < 0 || (n && (!p3 || !n3 || !u || !indices4 || !pmfs4 || !counts))) return DMT_ERR_INVALID;
-  bool ok = true;
-  int d = 0;
-  std::vector<LightTreeRefNode> const nodes = buildLightTreeRef(static_cast<uint8_t const*>(lights32), count, &d, &ok);
-  if (!ok || nodes.empty()) return DMT_ERR_INVALID;
-  if (node_count) *node_count = int(nodes.size());
-  if (depth) *depth = d;
-  for (int i = 0; i < n; ++i) {
-    LightTreeRefSelection const sel = ltr_select(nodes.data(), p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], n3[3 * i], n3[3 * i + 1], n3[3 * i + 2], u[i], start_pmf);
-    counts[i] = int32_t(sel.count);
-    for (int k = 0; k < kLightTreeMaxSplitSize; ++k)
-      indices4[4 * i + k] = k < int(sel.count) ? int32_t(sel.indices[k]) : -1, pmfs4[4 * i + k] = k < int(sel.count) ? sel.pmfs[k] : 0.f;
-  }
-  return DMT_OK;
-}
-
-// host only: the node array ensureLightTree uploads for `mode`, by the same builder call
-int dmt_light_tree_nodes(const void* lights32, uint32_t count, int mode, void* nodes_out, uint32_t cap, int* node_count, int* depth) {
-  if ((count && !lights32) || (cap && !nodes_out) || (mode != DMT_LIGHTS_TREE && mode != DMT_LIGHTS_TREE_REFERENCE)) return DMT_ERR_INVALID;
-  bool ok = true;
-  int d = 0;
-  std::vector<LightTreeNode> nodes;
-  std::vector<LightTreeRefNode> refNodes;
-  if (mode == DMT_LIGHTS_TREE) nodes = buildLightTree(static_cast<uint8_t const*>(lights32), count, &d, &ok);
-  else refNodes = buildLightTreeRef(static_cast<uint8_t const*>(lights32), count, &d, &ok);
-  if (!ok) return DMT_ERR_INVALID;
-  size_t const n = mode == DMT_LIGHTS_TREE ? nodes.size() : refNodes.size();
-  if (node_count) *node_count = int(n);
-  if (depth) *depth = d;
-  if (n > cap) return DMT_ERR_INVALID;  // the counts are reported: ask again with room for them
-  if (n) memcpy(nodes_out, mode == DMT_LIGHTS_TREE ? static_cast<void const*>(nodes.data()) : static_cast<void const*>(refNodes.data()),
-                n * (mode == DMT_LIGHTS_TREE ? sizeof(LightTreeNode) : sizeof(LightTreeRefNode)));
   return DMT_OK;
 }
 
@@ -2666,62 +2469,6 @@ int dmt_cull_box_test(const float* record6, const float* origins, const float* d
     cull_box_axis(record6[2], record6[5], cr.az, cr.rz, cr.bz, nz, fz);
     accept[i] = cull_box_accept(nx, ny, nz, fx, fy, fz, tmax[i] * kCullTSlack, cr.e2) ? 1 : 0;
   }
-  return DMT_OK;
-}
-
-int dmt_envmap_tables(const float* rgb, int width, int height, float* func, float* cdf, float* row_integral,
-                      float* marginal_func, float* marginal_cdf, float* marginal_integral) {
-  if (!rgb || width < 8 || height < 8 || (width & (width - 1)) || (height & (height - 1)) || !func || !cdf ||
-      !row_integral || !marginal_func || !marginal_cdf || !marginal_integral)
-    return DMT_ERR_INVALID;
-  envmap::Tables const t = envmap::build(rgb, width, height);
-  memcpy(func, t.func.data(), t.func.size() * 4), memcpy(cdf, t.cdf.data(), t.cdf.size() * 4);
-  memcpy(row_integral, t.rowInt.data(), t.rowInt.size() * 4);
-  memcpy(marginal_func, t.mFunc.data(), t.mFunc.size() * 4), memcpy(marginal_cdf, t.mCdf.data(), t.mCdf.size() * 4);
-  *marginal_integral = t.mInt;
-  return DMT_OK;
-}
-
-int dmt_clear_envmap(dmt_ctx* ctx) {
-  if (!ctx) return DMT_ERR_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->d_env.reset();
-  ctx->env = EnvView{};
-  return DMT_OK;
-}
-
-int dmt_upload_envmap(dmt_ctx* ctx, const float* rgb, int width, int height, const float* quat_xyzw, float scale) {
-  if (!ctx || !rgb || !quat_xyzw) return DMT_ERR_INVALID;
-  // the reference asserts powers of two and width == 2 * height (core-light.cpp:116); 8 = one AVX2 block of its CDF
-  if (width < 8 || height < 8 || (width & (width - 1)) || (height & (height - 1)) || width != 2 * height)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_upload_envmap: resolution must be powers of two >= 8 with width == 2 * height");
-  float const len = std::sqrt(quat_xyzw[0] * quat_xyzw[0] + quat_xyzw[1] * quat_xyzw[1] + quat_xyzw[2] * quat_xyzw[2] +
-                              quat_xyzw[3] * quat_xyzw[3]);
-  if (!(len > 0.f)) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_envmap: zero quaternion");
-  (void)scale;  // stored by the reference and never applied (core-light.cpp:115, :444-452)
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  envmap::Tables const t = envmap::build(rgb, width, height);
-  size_t const wh = size_t(width) * size_t(height), h = size_t(height);
-  DevBuf<float> buf;
-  HIP_TRY(ctx, buf.reserve(2 * wh + 3 * h + 3 * wh));
-  float* p = buf.get();
-  EnvView e{};
-  hipError_t err = hipSuccess;
-  auto put = [&](float const* src, size_t n) -> float const* {
-    float* dst = p;
-    p += n;
-    if (err == hipSuccess) err = hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice);
-    return dst;
-  };
-  e.func = put(t.func.data(), wh), e.cdf = put(t.cdf.data(), wh), e.rowInt = put(t.rowInt.data(), h);
-  e.mFunc = put(t.mFunc.data(), h), e.mCdf = put(t.mCdf.data(), h), e.rgb = put(rgb, 3 * wh);
-  if (err != hipSuccess) return fail(ctx, DMT_ERR_HIP, "dmt_upload_envmap: copy failed");
-  e.mInt = t.mInt, e.w = width, e.h = height;
-  e.qx = quat_xyzw[0] / len, e.qy = quat_xyzw[1] / len, e.qz = quat_xyzw[2] / len, e.qw = quat_xyzw[3] / len;
-  ctx->d_env = std::move(buf);
-  ctx->env = e;
   return DMT_OK;
 }
 

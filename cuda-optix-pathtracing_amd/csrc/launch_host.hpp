@@ -76,7 +76,7 @@ int checkErrorFlag(dmt_ctx* ctx) {
 
 // ---- what renderImpl and dmt_render_adaptive ask first, each under its own name --------------------
 int requireScene(dmt_ctx* ctx, char const* caller) {
-  if (ctx->haveTris && ctx->haveBsdfs && ctx->haveLights && ctx->haveCamera) return DMT_OK;
+  if (ctx->haveTris && ctx->haveBsdfs && ctx->lights.list.have && ctx->haveCamera) return DMT_OK;
   ctx->err = std::string(caller) + ": upload triangles, bsdfs, lights and set the camera first";
   return DMT_ERR_STATE;
 }

@@ -1,0 +1,245 @@
+// light_host.hpp -- the host side of the light layer: the one builder over the two kinds of light tree, the lazy build of a
+// context's tree, and the dmt_* entry points of the light list, the sampling mode, the host-only tree calls and the env map.
+// The layer's state and its rules -- what each call keeps and invalidates, when a feature bit is set, the too-deep
+// fall-back, which calls drain the stream -- are in light_state.hpp; the trees themselves in light_tree.hpp and
+// light_tree_ref.hpp, the env map's tables and device code in envmap.hpp.
+//
+// Part of dmt_hip.hip's translation unit, included once after the host helpers it uses (dmt_ctx, HIP_TRY, fail) and before
+// launch_host.hpp and probes.hpp: resolveFeatures (dmt_hip.hip) calls ensureLightTree ahead of every launch and of
+// dmt_test_light_tree.
+#pragma once
+
+namespace {
+
+float h2f_host(uint16_t h) {  // exact fp16 -> fp32 (CC/private/encoding.cu:124-155)
+  uint32_t const sgn = uint32_t(h & 0x8000u) << 16;
+  uint32_t e = (h >> 10) & 0x1Fu, m = h & 0x3FFu, out;
+  if (e == 0) {
+    if (m == 0) {
+      out = sgn;
+    } else {
+      e = 113;
+      while (!(m & 0x400u)) m <<= 1, --e;
+      out = sgn | (e << 23) | ((m & 0x3FFu) << 13);
+    }
+  } else if (e == 31) {
+    out = sgn | 0x7F800000u | (m << 13);
+  } else {
+    out = sgn | ((e + 112) << 23) | (m << 13);
+  }
+  float f;
+  memcpy(&f, &out, 4);
+  return f;
+}
+// octahedral decode on the host (CC/private/encoding.cu:39-60), as pt_device.hpp's dir_from_octa
+void octa_host(uint32_t octa, float out[3]) {
+  float const mx = 65535.f;
+  float const fx = float(octa & 0xFFFFu) / mx * 2.f - 1.f, fy = float((octa >> 16) & 0xFFFFu) / mx * 2.f - 1.f;
+  float n[3] = {fx, fy, 1.f - fabsf(fx) - fabsf(fy)};
+  if (n[2] < 0.f) {
+    n[0] = (1.f - fabsf(fy)) * (std::signbit(fx) ? -1.f : 1.f);
+    n[1] = (1.f - fabsf(fx)) * (std::signbit(fy) ? -1.f : 1.f);
+  }
+  float const inv = 1.f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  out[0] = n[0] * inv, out[1] = n[1] * inv, out[2] = n[2] * inv;
+}
+
+// ---- the two kinds of light tree ---------------------------------------------------
+// A kind: its node and item types, the item of a packed record, its builder, its walk's depth guard, its buffer in the state.
+struct LightTreeKind {  // DMT_LIGHTS_TREE (light_tree.hpp)
+  using Node = LightTreeNode;
+  using Item = light_tree::Item;
+  static constexpr int maxDepth = kLightTreeMaxDepth;
+  static bool itemOf(uint8_t const* rec32, uint32_t i, Item& it) { return light_tree::itemOf(rec32, i, h2f_host, it); }
+  static std::vector<Node> build(std::vector<Item> const& items, int* depth) { return light_tree::build(items, depth); }
+  static DevBuf<Node>& buffer(LightState::Tree& t) { return t.nodes; }
+};
+struct LightTreeRefKind {  // DMT_LIGHTS_TREE_REFERENCE (light_tree_ref.hpp)
+  using Node = LightTreeRefNode;
+  using Item = light_tree_ref::Item;
+  static constexpr int maxDepth = kLightTreeRefMaxDepth;
+  static bool itemOf(uint8_t const* rec32, uint32_t i, Item& it) { return light_tree_ref::itemOf(rec32, i, h2f_host, octa_host, it); }
+  static std::vector<Node> build(std::vector<Item> const& items, int* depth) { return light_tree_ref::build(items, depth); }
+  static DevBuf<Node>& buffer(LightState::Tree& t) { return t.refNodes; }
+};
+
+// The tree of kind K over a packed light list: what a context uploads and what the host-only calls return.  False, and
+// nothing written, when a record is neither a point nor a spot light.  depth (may be null) = levels.
+template <class K>
+bool buildLightTree(void const* lights32, uint32_t count, std::vector<typename K::Node>& nodes, int* depth) {
+  std::vector<typename K::Item> items(count);
+  for (uint32_t i = 0; i < count; ++i)
+    if (!K::itemOf(static_cast<uint8_t const*>(lights32) + 32 * size_t(i), i, items[i])) return false;
+  nodes = K::build(items, depth);
+  return true;
+}
+
+// a tree deeper than the walks' guard (lights at geometrically growing spacing) would cut paths short: the context keeps the
+// uniform pick and says so through dmt_last_error; the call that found out goes on
+int keepUniformPick(dmt_ctx* ctx, int guard) {
+  ctx->lights.tree.tooDeep = true;
+  ctx->err = "light tree: its depth of " + std::to_string(ctx->lights.tree.depth) + " exceeds the walk's guard of " + std::to_string(guard) +
+             " levels; the uniform pick is used instead";
+  return DMT_OK;
+}
+// (re)build the tree of kind K from the host copy of the light records and upload it
+template <class K>
+int uploadLightTree(dmt_ctx* ctx) {
+  LightState& L = ctx->lights;
+  std::vector<typename K::Node> nodes;
+  if (!buildLightTree<K>(L.list.host.data(), L.list.count, nodes, &L.tree.depth))
+    return fail(ctx, DMT_ERR_STATE, "light tree: only point and spot lights can be in the light list");
+  if (L.tree.depth > K::maxDepth) return keepUniformPick(ctx, K::maxDepth);
+  HIP_TRY(ctx, K::buffer(L.tree).assign(nodes.data(), nodes.size()));
+  L.tree.valid = true;
+  return DMT_OK;
+}
+int ensureLightTree(dmt_ctx* ctx) {
+  if (ctx->lights.tree.valid) return DMT_OK;
+  return ctx->lights.tree.mode == DMT_LIGHTS_TREE_REFERENCE ? uploadLightTree<LightTreeRefKind>(ctx) : uploadLightTree<LightTreeKind>(ctx);
+}
+
+// dmt_light_tree_nodes for one kind
+template <class K>
+int lightTreeNodes(void const* lights32, uint32_t count, void* nodes_out, uint32_t cap, int* node_count, int* depth) {
+  std::vector<typename K::Node> nodes;
+  if (!buildLightTree<K>(lights32, count, nodes, depth)) return DMT_ERR_INVALID;
+  if (node_count) *node_count = int(nodes.size());
+  if (nodes.size() > cap) return DMT_ERR_INVALID;  // the counts are reported: ask again with room for them
+  if (!nodes.empty()) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(typename K::Node));
+  return DMT_OK;
+}
+
+// ---- the env map (envmap.hpp) -------------------------------------------------------
+// what the tables take: powers of two, at least 8 (one AVX2 block of the reference's CDF)
+bool envResolutionOk(int width, int height) { return width >= 8 && height >= 8 && !(width & (width - 1)) && !(height & (height - 1)); }
+
+}  // namespace
+
+extern "C" {
+
+int dmt_upload_lights(dmt_ctx* ctx, const void* lights32, uint32_t count, const void* infinite32, uint32_t infinite_count) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if ((count && !lights32) || (infinite_count && !infinite32))
+    return fail(ctx, DMT_ERR_INVALID, "dmt_upload_lights: null array");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevBuf<Rec32> lights, inf;
+  HIP_TRY(ctx, lights.assign(lights32, count));
+  HIP_TRY(ctx, inf.assign(infinite32, infinite_count));
+  LightState::List& l = ctx->lights.list;
+  l.recs = std::move(lights), l.inf = std::move(inf);
+  l.count = count, l.infCount = infinite_count, l.have = true;
+  l.host.assign(static_cast<uint8_t const*>(lights32), static_cast<uint8_t const*>(lights32) + size_t(count) * 32);
+  ctx->lights.invalidateTree();
+  l.treeable = count > 0;
+  for (uint32_t i = 0; i < count; ++i) {  // a directional light in the list (PBRT "distant") has no position: such lists keep the uniform pick
+    uint16_t type;
+    memcpy(&type, l.host.data() + 32 * size_t(i) + 6, 2);
+    if (type != 0 && type != 1) l.treeable = false;
+  }
+  return DMT_OK;
+}
+
+int dmt_set_light_sampling(dmt_ctx* ctx, int mode) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (mode != DMT_LIGHTS_UNIFORM && mode != DMT_LIGHTS_TREE && mode != DMT_LIGHTS_TREE_REFERENCE)
+    return fail(ctx, DMT_ERR_INVALID, "dmt_set_light_sampling: unknown mode");
+  if (mode != ctx->lights.tree.mode) ctx->lights.invalidateTree();  // the two trees are different structures
+  ctx->lights.tree.mode = mode;
+  return DMT_OK;
+}
+
+// host only: the probability with which the light tree built from `lights32` picks each light at (p, n)
+int dmt_light_tree_pmfs(const void* lights32, uint32_t count, const float* p3, const float* n3, float* pmf_out, int* node_count,
+                        int* depth) {
+  if ((count && !lights32) || !p3 || !n3 || !pmf_out) return DMT_ERR_INVALID;
+  std::vector<LightTreeNode> nodes;
+  if (!buildLightTree<LightTreeKind>(lights32, count, nodes, depth)) return DMT_ERR_INVALID;
+  light_tree::pmfs(nodes, p3, n3, pmf_out, count);
+  if (node_count) *node_count = int(nodes.size());
+  return DMT_OK;
+}
+
+// host only: cut + selection of the reference-semantics tree at n shading points (light_tree_ref.hpp's ltr_select, the
+// function the *_ltree2 kernels call)
+int dmt_light_tree_ref_select(const void* lights32, uint32_t count, int n, const float* p3, const float* n3, const float* u, float start_pmf,
+                              int32_t* indices4, float* pmfs4, int32_t* counts, int* node_count, int* depth) {
+  if ((count && !lights32) || n < 0 || (n && (!p3 || !n3 || !u || !indices4 || !pmfs4 || !counts))) return DMT_ERR_INVALID;
+  std::vector<LightTreeRefNode> nodes;
+  int d = 0;
+  if (!buildLightTree<LightTreeRefKind>(lights32, count, nodes, &d) || nodes.empty()) return DMT_ERR_INVALID;
+  if (node_count) *node_count = int(nodes.size());
+  if (depth) *depth = d;
+  for (int i = 0; i < n; ++i) {
+    LightTreeRefSelection const sel = ltr_select(nodes.data(), p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], n3[3 * i], n3[3 * i + 1], n3[3 * i + 2], u[i], start_pmf);
+    counts[i] = int32_t(sel.count);
+    for (int k = 0; k < kLightTreeMaxSplitSize; ++k)
+      indices4[4 * i + k] = k < int(sel.count) ? int32_t(sel.indices[k]) : -1, pmfs4[4 * i + k] = k < int(sel.count) ? sel.pmfs[k] : 0.f;
+  }
+  return DMT_OK;
+}
+
+// host only: the node array ensureLightTree uploads for `mode`: both go through buildLightTree<K>
+int dmt_light_tree_nodes(const void* lights32, uint32_t count, int mode, void* nodes_out, uint32_t cap, int* node_count, int* depth) {
+  if ((count && !lights32) || (cap && !nodes_out) || (mode != DMT_LIGHTS_TREE && mode != DMT_LIGHTS_TREE_REFERENCE)) return DMT_ERR_INVALID;
+  return mode == DMT_LIGHTS_TREE ? lightTreeNodes<LightTreeKind>(lights32, count, nodes_out, cap, node_count, depth)
+                                 : lightTreeNodes<LightTreeRefKind>(lights32, count, nodes_out, cap, node_count, depth);
+}
+
+// host only: any power-of-two pair >= 8
+int dmt_envmap_tables(const float* rgb, int width, int height, float* func, float* cdf, float* row_integral,
+                      float* marginal_func, float* marginal_cdf, float* marginal_integral) {
+  if (!rgb || !envResolutionOk(width, height) || !func || !cdf || !row_integral || !marginal_func || !marginal_cdf || !marginal_integral)
+    return DMT_ERR_INVALID;
+  envmap::Tables const t = envmap::build(rgb, width, height);
+  memcpy(func, t.func.data(), t.func.size() * 4), memcpy(cdf, t.cdf.data(), t.cdf.size() * 4);
+  memcpy(row_integral, t.rowInt.data(), t.rowInt.size() * 4);
+  memcpy(marginal_func, t.mFunc.data(), t.mFunc.size() * 4), memcpy(marginal_cdf, t.mCdf.data(), t.mCdf.size() * 4);
+  *marginal_integral = t.mInt;
+  return DMT_OK;
+}
+
+int dmt_clear_envmap(dmt_ctx* ctx) {
+  if (!ctx) return DMT_ERR_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->lights.env.buf.reset();
+  ctx->lights.env.view = EnvView{};
+  return DMT_OK;
+}
+
+int dmt_upload_envmap(dmt_ctx* ctx, const float* rgb, int width, int height, const float* quat_xyzw, float scale) {
+  if (!ctx || !rgb || !quat_xyzw) return DMT_ERR_INVALID;
+  // the reference asserts powers of two and width == 2 * height (core-light.cpp:116)
+  if (!envResolutionOk(width, height) || width != 2 * height)
+    return fail(ctx, DMT_ERR_INVALID, "dmt_upload_envmap: resolution must be powers of two >= 8 with width == 2 * height");
+  float const len = std::sqrt(quat_xyzw[0] * quat_xyzw[0] + quat_xyzw[1] * quat_xyzw[1] + quat_xyzw[2] * quat_xyzw[2] +
+                              quat_xyzw[3] * quat_xyzw[3]);
+  if (!(len > 0.f)) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_envmap: zero quaternion");
+  (void)scale;  // stored by the reference and never applied (core-light.cpp:115, :444-452)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  envmap::Tables const t = envmap::build(rgb, width, height);
+  size_t const wh = size_t(width) * size_t(height), h = size_t(height);
+  DevBuf<float> buf;
+  HIP_TRY(ctx, buf.reserve(2 * wh + 3 * h + 3 * wh));
+  float* p = buf.get();
+  EnvView e{};
+  hipError_t err = hipSuccess;
+  auto put = [&](float const* src, size_t n) -> float const* {
+    float* dst = p;
+    p += n;
+    if (err == hipSuccess) err = hipMemcpy(dst, src, n * sizeof(float), hipMemcpyHostToDevice);
+    return dst;
+  };
+  e.func = put(t.func.data(), wh), e.cdf = put(t.cdf.data(), wh), e.rowInt = put(t.rowInt.data(), h);
+  e.mFunc = put(t.mFunc.data(), h), e.mCdf = put(t.mCdf.data(), h), e.rgb = put(rgb, 3 * wh);
+  if (err != hipSuccess) return fail(ctx, DMT_ERR_HIP, "dmt_upload_envmap: copy failed");
+  e.mInt = t.mInt, e.w = width, e.h = height;
+  e.qx = quat_xyzw[0] / len, e.qy = quat_xyzw[1] / len, e.qz = quat_xyzw[2] / len, e.qw = quat_xyzw[3] / len;
+  ctx->lights.env.buf = std::move(buf);
+  ctx->lights.env.view = e;
+  return DMT_OK;
+}
+
+}  // extern "C"

@@ -72,6 +72,11 @@ DMT_LT_HD float lt_importance(LightTreeNode const& nd, float px, float py, float
   return fmaxf(nd.phi * cosIB / distSqr, 0.f);
 }
 
+// The deepest tree (in levels, a lone leaf = 1) a context uploads; a deeper one keeps the uniform pick (light_state.hpp).  A
+// walk over d levels takes d iterations of lt_select's loop, the last of which returns at the leaf: its guard of 64 iterations
+// leaves four to spare, as ltr_select's guard of kLightTreeRefMaxDepth + 4 does.
+constexpr int kLightTreeMaxDepth = 60;
+
 // Walk from the root to one light, choosing a child in proportion to its importance (sampleDiscrete with remapped u).
 // Returns the light index and its probability, or -1 when both children of some node have importance 0.
 DMT_LT_HD int lt_select(LightTreeNode const* nodes, float px, float py, float pz, float nx, float ny, float nz, float u, float& pmf) {

@@ -529,7 +529,7 @@ int finishProbe(dmt_ctx* ctx, Probe& p) {
 // What the probes that walk the uploaded scene check first, reported under the entry point's name `who`: the whole scene
 // and the camera set (wholeScene), and every material index inside the BSDF array.
 int sceneReady(dmt_ctx* ctx, char const* who, bool wholeScene) {
-  if (wholeScene && !(ctx->haveTris && ctx->haveBsdfs && ctx->haveLights && ctx->haveCamera))
+  if (wholeScene && !(ctx->haveTris && ctx->haveBsdfs && ctx->lights.list.have && ctx->haveCamera))
     return fail(ctx, DMT_ERR_STATE, (std::string(who) + ": scene/camera not set").c_str());
   if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
     return fail(ctx, DMT_ERR_INVALID, (std::string(who) + ": material index outside the BSDF array").c_str());
@@ -565,13 +565,13 @@ extern "C" {
 int dmt_test_envmap(dmt_ctx* ctx, int n, const float* u2, const float* wi_in3, float* wi3, float* pdf, float* uv2, float* Le3,
                     int32_t* ok, float* Le_dir3, float* pdf_dir) {
   if (!ctx || n <= 0 || !u2 || !wi_in3 || !wi3 || !pdf || !uv2 || !Le3 || !ok || !Le_dir3 || !pdf_dir) return DMT_ERR_INVALID;
-  if (ctx->env.w <= 0) return fail(ctx, DMT_ERR_STATE, "dmt_test_envmap: no env map uploaded");
+  if (ctx->lights.env.view.w <= 0) return fail(ctx, DMT_ERR_STATE, "dmt_test_envmap: no env map uploaded");
   Probe p(ctx->device, size_t(n));
   ProbeIn<float> du(p, u2, 2), dwin(p, wi_in3, 3);
   ProbeOut<float> dwi(p, wi3, 3), dpdf(p, pdf, 1), duv(p, uv2, 2), dLe(p, Le3, 3), dLd(p, Le_dir3, 3), dpd(p, pdf_dir, 1);
   ProbeOut<int32_t> dok(p, ok, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_envmap, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->env, n, du.get(), dwin.get(), dwi.get(),
+  hipLaunchKernelGGL(k_test_envmap, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->lights.env.view, n, du.get(), dwin.get(), dwi.get(),
                      dpdf.get(), duv.get(), dLe.get(), dok.get(), dLd.get(), dpd.get());
   return finishProbe(ctx, p);
 }
@@ -713,18 +713,18 @@ int dmt_test_light(dmt_ctx* ctx, const void* light32, int n, const float* pos3, 
 int dmt_test_light_tree(dmt_ctx* ctx, int n, const float* pos3, const float* nrm3, const float* u, float start_pmf, int32_t* indices4,
                         float* pmfs4, int32_t* counts) {
   if (!ctx || n < 0 || !pos3 || !nrm3 || !u || !indices4 || !pmfs4 || !counts) return DMT_ERR_INVALID;
-  if (!ctx->haveLights) return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: upload lights first");
-  if (ctx->lightSampling == DMT_LIGHTS_UNIFORM)
-    return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: the context picks its lights uniformly (dmt_set_light_sampling first)");
-  if (ctx->lightCount <= 1) return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: a tree needs more than one light; the uniform pick is used");
   uint32_t F = 0;  // the tree dmt_render would read, built first
   if (int const rc = resolveFeatures(ctx, &F)) return rc;
-  if (ctx->lightTreeTooDeep)
-    return fail(ctx, DMT_ERR_STATE, ("dmt_test_light_tree: the light tree is too deep for the walk's guard (" + std::to_string(ctx->lightTreeDepth) +
-                                     " levels); the uniform pick is used instead").c_str());
-  if (!(F & (kFeatLightTree | kFeatLightTreeRef)))
-    return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: this scene keeps the uniform pick (a light tree takes point and spot lights, "
-                                    "without emissive triangles, image textures or blend materials)");
+  switch (ctx->lights.why(plainSurfaces(ctx))) {  // where a launch runs the uniform rows there is no tree to walk
+    case LightState::Pick::NoList: return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: upload lights first");
+    case LightState::Pick::UniformMode: return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: the context picks its lights uniformly (dmt_set_light_sampling first)");
+    case LightState::Pick::OneLight: return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: a tree needs more than one light; the uniform pick is used");
+    case LightState::Pick::TooDeep: return fail(ctx, DMT_ERR_STATE, ("dmt_test_light_tree: the light tree is too deep for the walk's guard (" +
+                                                std::to_string(ctx->lights.tree.depth) + " levels); the uniform pick is used instead").c_str());
+    case LightState::Pick::NotTreeable: return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: this scene keeps the uniform pick (a light tree takes point and spot lights, "
+                                                                        "without emissive triangles, image textures or blend materials)");
+    case LightState::Pick::Tree: break;
+  }
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<float> dP(p, pos3, 3), dN(p, nrm3, 3), dU(p, u, 1);
