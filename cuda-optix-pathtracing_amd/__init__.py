@@ -33,6 +33,13 @@ from .binding import (  # noqa: F401
     LIGHT_TREE_NODE,
     LIGHT_TREE_REF_NODE,
     LIGHT_TREE_LEAF,
+    emitter_tree_nodes,
+    emitter_tree_select,
+    emitter_tree_pmfs,
+    EMITTER_TREE_NODE,
+    EMITTER_TREE_LEAF,
+    EMITTERS_UNIFORM,
+    EMITTERS_TREE,
     envmap_tables,
     texture_mip_chain,
     texture_footprint,

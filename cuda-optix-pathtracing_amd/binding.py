@@ -65,7 +65,7 @@ def load_library():
 # every symbol include/dmt_hip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED_SYMBOLS = [
     "dmt_ctx_create", "dmt_ctx_destroy", "dmt_last_error", "dmt_upload_triangles", "dmt_upload_bsdfs",
-    "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_light_tree_nodes", "dmt_test_light_tree", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
+    "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_light_tree_nodes", "dmt_test_light_tree", "dmt_set_emitter_sampling", "dmt_emitter_tree_info", "dmt_emitter_tree_nodes", "dmt_emitter_tree_select", "dmt_emitter_tree_pmfs", "dmt_test_emitter_tree", "dmt_kernel_scratch", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
     "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_brute_cull_box_records", "dmt_cull_records", "dmt_cull_box_test", "dmt_test_triangle_intersect",
@@ -477,6 +477,71 @@ def light_tree_nodes(lights32, mode, cap=None):
     if rc != 0:
         raise DmtError(f"dmt_light_tree_nodes failed ({rc}): {nc.value} nodes, room for {int(cap)}")
     return out[:nc.value], d.value
+
+
+# one node of the tree dmt_emitter_tree_nodes returns (csrc/emitter_tree.hpp EmitterNode, 48 bytes)
+EMITTER_TREE_NODE = np.dtype([("lo", "<f4", 3), ("phi", "<f4"), ("hi", "<f4", 3), ("ref", "<u4"), ("axis", "<f4", 3), ("cosO", "<f4")])
+EMITTER_TREE_LEAF = 0x80000000
+EMITTERS_UNIFORM, EMITTERS_TREE = 0, 1
+
+
+def _emitter_scene(lights32, xs, ys, zs, area_tri, area_le):
+    """The arguments the host-only emitter-tree calls share: packed lights [k,32] (may be empty), the soup as
+    dmt_upload_triangles takes it (4 floats per triangle and axis), the emissive list (triangle indices, rgb radiance)."""
+    L = np.ascontiguousarray(lights32, np.uint8).reshape(-1, 32)
+    xs, ys, zs = _f32(xs).reshape(-1), _f32(ys).reshape(-1), _f32(zs).reshape(-1)
+    tri = np.ascontiguousarray(area_tri, np.uint32).reshape(-1)
+    le = _f32(area_le).reshape(-1, 3)
+    assert xs.size % 4 == 0 and ys.size == xs.size and zs.size == xs.size and le.shape[0] == tri.size
+    keep = (L, xs, ys, zs, tri, le)
+    args = (_p(L) if L.size else None, C.c_uint32(L.shape[0]), _p(xs), _p(ys), _p(zs), C.c_uint64(xs.size // 4), _p(tri) if tri.size else None,
+            _p(le) if tri.size else None, C.c_uint32(tri.size))
+    return keep, args, L.shape[0] + tri.size
+
+
+def emitter_tree_nodes(lights32, xs, ys, zs, area_tri, area_le, cap=None):
+    """Host-only (dmt_emitter_tree_nodes): the emitter tree a context uploads for this scene -> (nodes [EMITTER_TREE_NODE],
+    trails [emitters] uint64, lengths [emitters] int32, depth).  cap: room offered, in nodes; too little is refused."""
+    lib = load_library()
+    keep, args, count = _emitter_scene(lights32, xs, ys, zs, area_tri, area_le)
+    nc, d = C.c_int(), C.c_int()
+    if cap is None:
+        rc = lib.dmt_emitter_tree_nodes(*args, None, C.c_uint32(0), None, None, C.byref(nc), C.byref(d))
+        if rc != 0:
+            raise DmtError(f"dmt_emitter_tree_nodes failed ({rc})")
+        cap = nc.value
+    out = np.zeros(max(int(cap), 1), EMITTER_TREE_NODE)
+    trails, lengths = np.zeros(max(count, 1), np.uint64), np.zeros(max(count, 1), np.int32)
+    rc = lib.dmt_emitter_tree_nodes(*args, _p(out), C.c_uint32(int(cap)), _p(trails), _p(lengths), C.byref(nc), C.byref(d))
+    if rc != 0:
+        raise DmtError(f"dmt_emitter_tree_nodes failed ({rc}): {nc.value} nodes, room for {int(cap)}")
+    return out[:nc.value], trails[:count], lengths[:count], d.value
+
+
+def emitter_tree_select(lights32, xs, ys, zs, area_tri, area_le, p, n, u, start_pmf=1.0):
+    """Host-only (dmt_emitter_tree_select): et_select at cases (p [k,3], n [k,3], u [k]) -> (index [k] (-1 = none), pmf [k],
+    pmf_by_trail [k]), both probabilities times start_pmf."""
+    lib = load_library()
+    keep, args, _ = _emitter_scene(lights32, xs, ys, zs, area_tri, area_le)
+    p, n, u = _f32(p).reshape(-1, 3), _f32(n).reshape(-1, 3), _f32(u).reshape(-1)
+    k = p.shape[0]
+    assert n.shape[0] == k and u.shape[0] == k
+    idx, pmf, trail = np.zeros(k, np.int32), np.zeros(k, np.float32), np.zeros(k, np.float32)
+    rc = lib.dmt_emitter_tree_select(*args, C.c_int(k), _p(p), _p(n), _p(u), C.c_float(start_pmf), _p(idx), _p(pmf), _p(trail))
+    if rc != 0:
+        raise DmtError(f"dmt_emitter_tree_select failed ({rc})")
+    return idx, pmf, trail
+
+
+def emitter_tree_pmfs(lights32, xs, ys, zs, area_tri, area_le, p, n):
+    """Host-only (dmt_emitter_tree_pmfs): et_pmf of every emitter at point p with normal n."""
+    lib = load_library()
+    keep, args, count = _emitter_scene(lights32, xs, ys, zs, area_tri, area_le)
+    out = np.zeros(max(count, 1), np.float32)
+    rc = lib.dmt_emitter_tree_pmfs(*args, _p(_f32(p, (3,))), _p(_f32(n, (3,))), _p(out))
+    if rc != 0:
+        raise DmtError(f"dmt_emitter_tree_pmfs failed ({rc})")
+    return out[:count]
 
 
 def bvh_validate(xs, ys, zs):
@@ -1283,6 +1348,24 @@ class Renderer:
         self._check(self._lib.dmt_kernel_time(self._ctx, C.byref(ms), C.byref(n), int(bool(reset))), "dmt_kernel_time")
         return ms.value, n.value
 
+    def set_emitter_sampling(self, mode):
+        """0 = uniform pick among lights and emissive triangles (default), 1 = the emitter tree (csrc/emitter_tree.hpp)."""
+        self._check(self._lib.dmt_set_emitter_sampling(self._ctx, int(mode)), "dmt_set_emitter_sampling")
+
+    def emitter_tree_info(self):
+        """dict(mode, active, emitters, nodes, depth, build_ms) of dmt_emitter_tree_info."""
+        mode, active, depth = C.c_int(), C.c_int(), C.c_int()
+        emitters, nodes, ms = C.c_uint32(), C.c_uint32(), C.c_double()
+        self._check(self._lib.dmt_emitter_tree_info(self._ctx, C.byref(mode), C.byref(active), C.byref(emitters), C.byref(nodes), C.byref(depth),
+                                                    C.byref(ms)), "dmt_emitter_tree_info")
+        return dict(mode=mode.value, active=bool(active.value), emitters=emitters.value, nodes=nodes.value, depth=depth.value, build_ms=ms.value)
+
+    def kernel_scratch(self):
+        """Scratch bytes per lane of the kernel a render would launch now (dmt_kernel_scratch)."""
+        v = C.c_int()
+        self._check(self._lib.dmt_kernel_scratch(self._ctx, C.byref(v)), "dmt_kernel_scratch")
+        return v.value
+
     def kernel_info(self):
         v = [C.c_int() for _ in range(5)]
         self._check(self._lib.dmt_kernel_info(self._ctx, *[C.byref(x) for x in v]), "dmt_kernel_info")
@@ -1397,6 +1480,17 @@ class Renderer:
         self._check(self._lib.dmt_test_light_tree(self._ctx, k, _p(pos), _p(nrm), _p(u), C.c_float(start_pmf), _p(idx), _p(pmf), _p(cnt)),
                     "dmt_test_light_tree")
         return idx, pmf, cnt
+
+    def test_emitter_tree(self, pos, nrm, u, start_pmf=1.0):
+        """dmt_test_emitter_tree: the device's emitter choice at shading points pos [k,3] with normals nrm [k,3] and one random
+        number each -> (index [k] (-1 = none), pmf [k], pmf_by_trail [k])."""
+        pos, nrm, u = _f32(pos, (-1, 3)), _f32(nrm, (-1, 3)), _f32(u, (-1,))
+        k = pos.shape[0]
+        assert nrm.shape[0] == k and u.shape[0] == k
+        idx, pmf, trail = np.zeros(k, np.int32), np.zeros(k, np.float32), np.zeros(k, np.float32)
+        self._check(self._lib.dmt_test_emitter_tree(self._ctx, k, _p(pos), _p(nrm), _p(u), C.c_float(start_pmf), _p(idx), _p(pmf), _p(trail)),
+                    "dmt_test_emitter_tree")
+        return idx, pmf, trail
 
     def test_half(self, floats=None, halves=None):
         h_out = f_out = None

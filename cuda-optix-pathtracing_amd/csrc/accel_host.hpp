@@ -351,6 +351,7 @@ int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const fl
   if (int const rc = beginUpdate(ctx, "dmt_update_vertices", !xs || !ys || !zs, count, T, &done)) return rc;
   if (done) return DMT_OK;
   dropMotion(ctx);  // key 1 was a motion from the positions being replaced
+  ctx->lights.invalidateEmitters();  // and the emitter tree was built over them
   std::vector<TriIsect> a;
   std::vector<TriPost> b;
   packSoup(xs, ys, zs, ctx->h_mat.data(), count, a, b);
@@ -370,6 +371,7 @@ int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count)
   if (int const rc = beginUpdate(ctx, "dmt_update_vertices_device", !d_verts9, count, T, &done)) return rc;
   if (done) return DMT_OK;
   dropMotion(ctx);  // key 1 was a motion from the positions being replaced
+  ctx->lights.invalidateEmitters();  // and the emitter tree was built over them
   HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->d_tris.get(), ctx->d_post.get(), ctx->stream));
   if (int const rcT = mirrorDeviceUpdate(ctx, d_verts9, count)) return rcT;
   // the host mirrors (the host builder's, the cull plan's and a later rebuild's input) from the records just made

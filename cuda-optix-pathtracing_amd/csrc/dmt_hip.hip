@@ -43,6 +43,7 @@
 #include "envmap.hpp"
 #include "light_tree.hpp"
 #include "light_tree_ref.hpp"
+#include "emitter_tree.hpp"
 
 using namespace dmt;
 
@@ -170,6 +171,10 @@ struct RenderParams {
   // its spectrum (dmt_set_medium_spectrum; medium.hpp): read by the *_rgb kernels only, whose `medium.sigmaT` is the
   // reference channel's extinction.  After `mediumGrid`, so that no other field moves
   MediumSpectrumParams mediumSpectrum;
+  // the emitter tree (dmt_set_emitter_sampling; emitter_tree.hpp) over `lights` and the emissive triangles: its nodes and, per
+  // emitter, the bit trail of its leaf.  Read by the *_etree kernels only.  After `mediumSpectrum`, so that no other field moves
+  EmitterNode const* emitterTree;
+  EmitterTrail const* emitterTrails;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -273,6 +278,20 @@ DMT_DEV f3 get_Lfin() {
   float const* const c = s_cold + threadIdx.x;
   return mk3(c[3 * kLdsThreads], c[4 * kLdsThreads], c[5 * kLdsThreads]);
 }
+// emitter-tree kernels only (kFeatEmitterTree): the surface vertex the current path ray left, position (0..2) and geometric
+// normal (3..5) exactly as et_select saw them, for et_pmf when the ray hits an emissive triangle.  Written once per bounce,
+// read once per emitter hit; an array of its own, so that only the kernels that use it allocate it
+__shared__ float s_prev[6 * kLdsThreads];
+DMT_DEV void put_prev_vertex(f3 p, f3 n) {
+  float* const c = s_prev + threadIdx.x;
+  c[0 * kLdsThreads] = p.x, c[1 * kLdsThreads] = p.y, c[2 * kLdsThreads] = p.z;
+  c[3 * kLdsThreads] = n.x, c[4 * kLdsThreads] = n.y, c[5 * kLdsThreads] = n.z;
+}
+DMT_DEV void get_prev_vertex(f3& p, f3& n) {
+  float const* const c = s_prev + threadIdx.x;
+  p = mk3(c[0 * kLdsThreads], c[1 * kLdsThreads], c[2 * kLdsThreads]);
+  n = mk3(c[3 * kLdsThreads], c[4 * kLdsThreads], c[5 * kLdsThreads]);
+}
 DMT_DEV void put_finIdx(uint32_t i) { s_cold[6 * kLdsThreads + threadIdx.x] = __uint_as_float(i); }
 DMT_DEV uint32_t get_finIdx() { return __float_as_uint(s_cold[6 * kLdsThreads + threadIdx.x]); }
 DMT_DEV f3 ray_dir(PathState const& st) { return mk3(st.rp.dx.x, st.rp.dy.x, st.rp.dz.x); }
@@ -333,6 +352,7 @@ constexpr uint32_t kFeatCutout = 1u << 11;       // alpha cutouts: candidate hit
 constexpr uint32_t kFeatVtxNormals = 1u << 10;   // smooth shading: ns interpolated from per-vertex normals (vnormals.hpp); plain, env, tex rows
 constexpr uint32_t kFeatMedium = 1u << 12;       // participating medium: free flight and scatter vertices between two ray casts (medium_device.hpp); plain and env-map rows only
 constexpr uint32_t kFeatMediumGrid = 1u << 13;   // the medium's extinction from a density grid, marched voxel by voxel (medium_grid.hpp); set together with kFeatMedium
+constexpr uint32_t kFeatEmitterTree = 1u << 15;  // NEE picks among lights and emissive triangles by the emitter tree (emitter_tree.hpp); with kFeatArea, the four *_area rows only
 constexpr uint32_t kFeatMediumSpectrum = 1u << 14;  // per-channel extinction and emission: one-sample MIS over the channels' free flights (medium.hpp); set together with kFeatMedium
 
 // the post-hit record path_shade works on: the uploaded one, or under kFeatMotion the triangle at the sample's time
@@ -347,6 +367,7 @@ DMT_DEV Hit shade_hit(KArgs k, SceneView const& sc, int tri, float bu, float bv,
 template <uint32_t F>
 DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv) {
   static_assert(!((F & kFeatLightTree) && (F & kFeatLightTreeRef)), "one light tree at a time");
+  static_assert(!(F & kFeatEmitterTree) || ((F & kFeatArea) && !(F & ~(kFeatEmitterTree | kFeatArea | kFeatBvh | kFeatEnv))), "emitter tree: the emissive-triangle rows only");
   static_assert(!((F & kFeatTex) && (F & kFeatBlend)), "kFeatBlend carries the texture code itself");
   static_assert(!(F & kFeatTexFilter) || (F & (kFeatTex | kFeatBlend)), "the texture filter needs the texture code");
   static_assert(!(F & kFeatMotion) || !(F & ~(kFeatMotion | kFeatBvh | kFeatEnv)), "motion: the plain and env-map rows only");
@@ -401,7 +422,16 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
         if (st.depth == 0 || st.lastSpecular) {
           st.L = st.L + st.beta * Le;
         } else {
-          float const a = st.lastPdf, b = pl * ((F & kFeatEnv) ? 0.5f : 1.f) / float(nAll);
+          float const a = st.lastPdf;
+          float b;  // pl x the probability with which NEE at the vertex the ray left picks this triangle
+          if constexpr (F & kFeatEmitterTree) {
+            f3 pp, pn;
+            get_prev_vertex(pp, pn);
+            b = pl * ((F & kFeatEnv) ? 0.5f : 1.f) *
+                et_pmf(ka->emitterTree, ka->emitterTrails[sc.lightCount + ai], pp.x, pp.y, pp.z, pn.x, pn.y, pn.z);
+          } else {
+            b = pl * ((F & kFeatEnv) ? 0.5f : 1.f) / float(nAll);
+          }
           st.L = st.L + st.beta * Le * ((a * a) / (a * a + b * b));
         }
       }
@@ -497,9 +527,23 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
     }
   }
   bool areaNee = false;
+  [[maybe_unused]] int etSel = -1;  // kFeatEmitterTree: the emitter the tree picked at this vertex (-1: none) and its probability
+  [[maybe_unused]] float etPmf = 0.f;
   if constexpr (F & kFeatArea) {
-    uint32_t const li = pick_index(uLight, nAll);
-    areaNee = !envNee && li >= sc.lightCount;
+    uint32_t li;
+    if constexpr (F & kFeatEmitterTree) {
+      // one walk at (hit.pos, hit.normal), the vertex a later emitter hit evaluates et_pmf at: kept bit for bit (put_prev_vertex)
+      put_prev_vertex(hit.pos, hit.normal);
+      if (!envNee) {
+        KArgs const ka = kargs(k);
+        etSel = et_select(ka->emitterTree, hit.pos.x, hit.pos.y, hit.pos.z, hit.normal.x, hit.normal.y, hit.normal.z, uLight, etPmf);
+      }
+      li = etSel >= 0 ? uint32_t(etSel) : 0u;
+      areaNee = etSel >= 0 && li >= sc.lightCount;
+    } else {
+      li = pick_index(uLight, nAll);
+      areaNee = !envNee && li >= sc.lightCount;
+    }
     if (areaNee) {
       KArgs const ka = kargs(k);
       uint32_t const ai = li - sc.lightCount;
@@ -509,7 +553,10 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
         f3 const f = eval_material(as.wi, bsdfPdf);
         if (!is_zero(f)) {
           f3 const Le = mk3(ka->areaLe[3 * ai], ka->areaLe[3 * ai + 1], ka->areaLe[3 * ai + 2]);
-          float const a = as.pdf * ((F & kFeatEnv) ? 0.5f : 1.f) / float(nAll), bb = bsdfPdf;
+          float a;
+          if constexpr (F & kFeatEmitterTree) a = as.pdf * ((F & kFeatEnv) ? 0.5f : 1.f) * etPmf;
+          else a = as.pdf * ((F & kFeatEnv) ? 0.5f : 1.f) / float(nAll);
+          float const bb = bsdfPdf;
           put_C(st.beta * (Le * f * (((a * a) / (a * a + bb * bb)) / a)));
           set_shadow_ray(st, offset_ray_origin(hit.pos, hit.error, hit.normal, as.wi), as.wi);
           st.smax = as.dist * 0.999f;
@@ -583,6 +630,10 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
       picked = sel >= 0;
       li = picked ? uint32_t(sel) : 0u;
       pmf = ((F & kFeatEnv) ? 0.5f : 1.f) * treePmf;
+    } else if constexpr (F & kFeatEmitterTree) {  // the walk above returned a record of the light list, or nothing
+      picked = etSel >= 0;
+      li = picked ? uint32_t(etSel) : 0u;
+      pmf = ((F & kFeatEnv) ? 0.5f : 1.f) * etPmf;
     } else {
       li = pick_index(uLight, (F & kFeatArea) ? nAll : sc.lightCount);
       pmf = ((F & kFeatEnv) ? 0.5f : 1.f) / float((F & kFeatArea) ? nAll : sc.lightCount);
@@ -1620,6 +1671,11 @@ DMT_DEV void megakernel_body_bvh() {
 // _rgb: the grey twin's body with the spectrum's event and per-channel transmittances (medium.hpp).  Seven rows keep their
 // twins' bounds; _bvh_env_medium_rgb runs one wave per SIMD fewer than _bvh_env_medium: at three it spills 1 VGPR (8 bytes
 // of scratch).
+// _etree: the _area twin's body with the emitter tree's walk in path_shade (et_select at the hit, et_pmf at an emitter hit)
+// and the previous vertex in 6 KB more LDS per block (s_prev).  The walk holds both children of a level, six quads, in
+// flight: 13 to 28 more VGPRs than the twin (149 / 181 / 156 / 188 against 128 / 168 / 128 / 168).  At the twins' bounds
+// (4 / 3) the compiler cannot fit that without spilling and misses the bound instead; each row runs one wave per SIMD
+// fewer (3 / 2), where it uses no scratch.
 #define DMT_MEGAKERNELS(X)                                                          \
   X(, 0, DMT_MIN_WAVES_PER_SIMD, megakernel_body)                                   \
   X(_bvh, kFeatBvh, DMT_MIN_WAVES_PER_SIMD_BVH, megakernel_body_bvh)                \
@@ -1637,6 +1693,10 @@ DMT_DEV void megakernel_body_bvh() {
   X(_bvh_blend, kFeatBvh | kFeatBlend, 2, megakernel_body_bvh)                      \
   X(_env_blend, kFeatEnv | kFeatBlend, 3, megakernel_body)                          \
   X(_bvh_env_blend, kFeatBvh | kFeatEnv | kFeatBlend, 2, megakernel_body_bvh)       \
+  X(_area_etree, kFeatArea | kFeatEmitterTree, 3, megakernel_body)                  \
+  X(_bvh_area_etree, kFeatBvh | kFeatArea | kFeatEmitterTree, 2, megakernel_body_bvh) \
+  X(_env_area_etree, kFeatEnv | kFeatArea | kFeatEmitterTree, 3, megakernel_body)   \
+  X(_bvh_env_area_etree, kFeatBvh | kFeatEnv | kFeatArea | kFeatEmitterTree, 2, megakernel_body_bvh) \
   X(_ltree, kFeatLightTree, 4, megakernel_body)                                     \
   X(_bvh_ltree, kFeatBvh | kFeatLightTree, 3, megakernel_body_bvh)                  \
   X(_env_ltree, kFeatEnv | kFeatLightTree, 4, megakernel_body)                      \
@@ -2048,14 +2108,18 @@ uint32_t featuresOf(dmt_ctx const* c) {
   if (c->ac.haveMotion) F |= kFeatMotion;
   if (c->surf.vn.have) F |= kFeatVtxNormals;
   if (c->surf.op.have) F |= kFeatCutout;
-  return F | c->lights.features(plainSurfaces(c)) | c->medium.features();
+  return F | c->lights.features(plainSurfaces(c)) | c->lights.emitterFeatures(c->surf.area.count) | c->medium.features();
 }
 int ensureLightTree(dmt_ctx* ctx);
+int ensureEmitterTree(dmt_ctx* ctx);
 // featuresOf once the light tree it asks for is built: a tree deeper than the walk's guard switches the context back to the
 // uniform pick (LightState::Tree::tooDeep), which changes the kernel, its occupancy and the launch shape
 int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
   if (featuresOf(ctx) & (kFeatLightTree | kFeatLightTreeRef)) {
     if (int const rc = ensureLightTree(ctx)) return rc;
+  }
+  if (featuresOf(ctx) & kFeatEmitterTree) {  // too deep: the bit goes and the *_area rows run
+    if (int const rc = ensureEmitterTree(ctx)) return rc;
   }
   *mask = featuresOf(ctx);
   return DMT_OK;
@@ -2095,6 +2159,10 @@ int checkFeatures(dmt_ctx* ctx, uint32_t F) {
     if (F & (kFeatLightTree | kFeatLightTreeRef)) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with a light tree is not supported");
     if ((F & kFeatBvh) && ctx->launch.wf.strategy == 2) return fail(ctx, DMT_ERR_STATE, "dmt_render: motion blur (dmt_set_motion) together with the wavefront BVH strategy is not supported");
   }
+  if ((F & kFeatEmitterTree) && (F & kFeatBvh) && ctx->launch.wf.strategy == 2)
+    return fail(ctx, DMT_ERR_STATE, "dmt_render: the emitter tree (dmt_set_emitter_sampling) together with the wavefront BVH strategy is not supported");
+  if ((F & kFeatEmitterTree) && (F & kFeatStats))
+    return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: the emitter tree (dmt_set_emitter_sampling) has no counting kernels");
   if ((F & kFeatStats) && (F & (kFeatTex | kFeatBlend | kFeatArea | kFeatLightTree | kFeatLightTreeRef)))
     return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: the counting kernels exist for the plain and env-map BVH kernels only; "
                                     "with textures, blended materials, emissive triangles or a light tree they would describe a different kernel");
@@ -2149,6 +2217,7 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   c->lights.fill(P, plainSurfaces(c));
+  c->lights.fillEmitters(P, c->surf.area.count);
   c->medium.fill(P);
   c->surf.fill(P);
   return P;
@@ -2258,6 +2327,7 @@ int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const f
   ctx->h_mat.assign(mat_id, mat_id + count);
   ctx->ac.tree.drop();         // it is of the soup just replaced
   dropMotion(ctx);             // key 1 was a motion from the soup just replaced
+  ctx->lights.invalidateEmitters();  // the emitter tree was over triangles of the soup just replaced
   hipError_t const kindRc = ctx->surf.soupReplaced(ctx->h_mat);  // vertex normals, opacity records and emissive triangles were of the soup just replaced; the material kinds are made anew
   ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
   HIP_TRY(ctx, kindRc);

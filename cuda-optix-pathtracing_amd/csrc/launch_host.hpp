@@ -578,4 +578,17 @@ int dmt_kernel_info(dmt_ctx* ctx, int* vgprs, int* sgprs, int* lds_bytes, int* b
   return DMT_OK;
 }
 
+// scratch (private segment) bytes per lane of the kernel dmt_render would launch now: 0 = no register spills, no stack
+int dmt_kernel_scratch(dmt_ctx* ctx, int* scratch_bytes) {
+  if (!ctx || !scratch_bytes) return DMT_ERR_INVALID;
+  uint32_t F = 0;
+  if (int const rc = resolveFeatures(ctx, &F)) return rc;
+  MegakernelFn const kernel = megakernelOf(F);
+  if (!kernel) return noKernel(ctx, "dmt_kernel_scratch", F);
+  hipFuncAttributes attr{};
+  HIP_TRY(ctx, hipFuncGetAttributes(&attr, reinterpret_cast<void const*>(kernel)));
+  *scratch_bytes = int(attr.localSizeBytes);
+  return DMT_OK;
+}
+
 }  // extern "C"

@@ -110,6 +110,55 @@ int lightTreeNodes(void const* lights32, uint32_t count, void* nodes_out, uint32
   return DMT_OK;
 }
 
+// ---- the emitter tree (emitter_tree.hpp) -------------------------------------------
+// The one builder call: what a context uploads and what the host-only calls return.  Emitters are the packed lights and
+// then the triangles area_tri of the soup xs / ys / zs (4 floats per triangle and axis).  False, and nothing written, when a
+// record is neither a point nor a spot light or a triangle index lies outside the soup.
+bool buildEmitterTree(void const* lights32, uint32_t count, float const* xs, float const* ys, float const* zs, uint64_t triCount,
+                      uint32_t const* areaTri, float const* areaLe, uint32_t areaCount, emitter_tree::Tree& tree) {
+  std::vector<emitter_tree::Item> items(size_t(count) + areaCount);
+  for (uint32_t i = 0; i < count; ++i)
+    if (!emitter_tree::lightItem(static_cast<uint8_t const*>(lights32) + 32 * size_t(i), i, h2f_host, items[i])) return false;
+  for (uint32_t k = 0; k < areaCount; ++k) {
+    size_t const t = areaTri[k];
+    if (t >= triCount) return false;
+    float const p0[3] = {xs[4 * t], ys[4 * t], zs[4 * t]}, p1[3] = {xs[4 * t + 1], ys[4 * t + 1], zs[4 * t + 1]};
+    float const p2[3] = {xs[4 * t + 2], ys[4 * t + 2], zs[4 * t + 2]};
+    emitter_tree::triangleItem(p0, p1, p2, areaLe + 3 * size_t(k), count + k, items[size_t(count) + k]);
+  }
+  tree = emitter_tree::build(std::move(items));
+  return true;
+}
+// (re)build the emitter tree from the host copies of the light records, the emissive list and the soup, and upload it.  Too
+// deep: the same kind of note as keepUniformPick's, and the call that found out goes on with the uniform rows
+int ensureEmitterTree(dmt_ctx* ctx) {
+  LightState::Emitters& E = ctx->lights.emitters;
+  if (E.valid || E.tooDeep) return DMT_OK;
+  SurfaceState::Emissive const& area = ctx->surf.area;
+  emitter_tree::Tree tree;
+  auto const t0 = std::chrono::steady_clock::now();
+  if (!buildEmitterTree(ctx->lights.list.host.data(), ctx->lights.list.count, ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->triCount,
+                        area.hostTri.data(), area.hostLe.data(), area.count, tree))
+    return fail(ctx, DMT_ERR_STATE, "emitter tree: only point and spot lights can be in the light list");
+  E.buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  E.depth = tree.depth, E.emitters = uint32_t(tree.trails.size()), E.nodeCount = uint32_t(tree.nodes.size());
+  if (tree.depth > kEmitterTreeMaxDepth) {
+    E.tooDeep = true;
+    ctx->err = "emitter tree: its depth of " + std::to_string(tree.depth) + " exceeds the walk's guard of " + std::to_string(kEmitterTreeMaxDepth) +
+               " levels; the uniform pick is used instead";
+    return DMT_OK;
+  }
+  HIP_TRY(ctx, E.nodes.assign(tree.nodes.data(), tree.nodes.size()));
+  HIP_TRY(ctx, E.trails.assign(tree.trails.data(), tree.trails.size()));
+  E.valid = true;
+  return DMT_OK;
+}
+// the arguments the three host-only emitter-tree calls share
+bool emitterSceneOk(void const* lights32, uint32_t count, float const* xs, float const* ys, float const* zs, uint64_t triCount,
+                    uint32_t const* areaTri, float const* areaLe, uint32_t areaCount) {
+  return !(count && !lights32) && !(triCount && (!xs || !ys || !zs)) && !(areaCount && (!areaTri || !areaLe));
+}
+
 // ---- the env map (envmap.hpp) -------------------------------------------------------
 // what the tables take: powers of two, at least 8 (one AVX2 block of the reference's CDF)
 bool envResolutionOk(int width, int height) { return width >= 8 && height >= 8 && !(width & (width - 1)) && !(height & (height - 1)); }
@@ -130,7 +179,7 @@ int dmt_upload_lights(dmt_ctx* ctx, const void* lights32, uint32_t count, const 
   l.recs = std::move(lights), l.inf = std::move(inf);
   l.count = count, l.infCount = infinite_count, l.have = true;
   l.host.assign(static_cast<uint8_t const*>(lights32), static_cast<uint8_t const*>(lights32) + size_t(count) * 32);
-  ctx->lights.invalidateTree();
+  ctx->lights.invalidateTree(), ctx->lights.invalidateEmitters();
   l.treeable = count > 0;
   for (uint32_t i = 0; i < count; ++i) {  // a directional light in the list (PBRT "distant") has no position: such lists keep the uniform pick
     uint16_t type;
@@ -146,6 +195,86 @@ int dmt_set_light_sampling(dmt_ctx* ctx, int mode) {
     return fail(ctx, DMT_ERR_INVALID, "dmt_set_light_sampling: unknown mode");
   if (mode != ctx->lights.tree.mode) ctx->lights.invalidateTree();  // the two trees are different structures
   ctx->lights.tree.mode = mode;
+  return DMT_OK;
+}
+
+int dmt_set_emitter_sampling(dmt_ctx* ctx, int mode) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (mode != DMT_EMITTERS_UNIFORM && mode != DMT_EMITTERS_TREE) return fail(ctx, DMT_ERR_INVALID, "dmt_set_emitter_sampling: unknown mode");
+  if (mode != ctx->lights.emitters.mode) ctx->lights.invalidateEmitters();
+  ctx->lights.emitters.mode = mode;
+  return DMT_OK;
+}
+
+int dmt_emitter_tree_info(dmt_ctx* ctx, int* mode, int* active, uint32_t* emitters, uint32_t* nodes, int* depth, double* build_ms) {
+  if (!ctx) return DMT_ERR_INVALID;
+  LightState& L = ctx->lights;
+  uint32_t const areaCount = ctx->surf.area.count;
+  if (L.emitterFeatures(areaCount)) {  // as a launch would: build it, which may find it too deep
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int const rc = ensureEmitterTree(ctx)) return rc;
+  }
+  bool const on = L.emitterFeatures(areaCount) != 0u && L.emitters.valid;
+  bool const built = on || L.whyEmitters(areaCount) == LightState::EmitterPick::TooDeep;  // a too-deep build still reports what it found
+  if (mode) *mode = L.emitters.mode;
+  if (active) *active = on ? 1 : 0;
+  if (emitters) *emitters = built ? L.emitters.emitters : 0u;
+  if (nodes) *nodes = built ? L.emitters.nodeCount : 0u;
+  if (depth) *depth = built ? L.emitters.depth : 0;
+  if (build_ms) *build_ms = built ? L.emitters.buildMs : 0.0;
+  return DMT_OK;
+}
+
+// host only: the emitter tree ensureEmitterTree uploads for this scene
+int dmt_emitter_tree_nodes(const void* lights32, uint32_t count, const float* xs, const float* ys, const float* zs, uint64_t tri_count,
+                           const uint32_t* area_tri, const float* area_le, uint32_t area_count, void* nodes_out, uint32_t cap,
+                           uint64_t* trails_out, int32_t* lengths_out, int* node_count, int* depth) {
+  if (!emitterSceneOk(lights32, count, xs, ys, zs, tri_count, area_tri, area_le, area_count)) return DMT_ERR_INVALID;
+  emitter_tree::Tree T;
+  if (!buildEmitterTree(lights32, count, xs, ys, zs, tri_count, area_tri, area_le, area_count, T)) return DMT_ERR_INVALID;
+  if (node_count) *node_count = int(T.nodes.size());
+  if (depth) *depth = T.depth;
+  if (nodes_out) {
+    if (T.nodes.size() > cap) return DMT_ERR_INVALID;  // the counts are reported: ask again with room for them
+    if (!T.nodes.empty()) memcpy(nodes_out, T.nodes.data(), T.nodes.size() * sizeof(EmitterNode));
+  }
+  for (size_t i = 0; i < T.trails.size(); ++i) {
+    if (trails_out) trails_out[i] = uint64_t(T.trails[i].lo) | (uint64_t(T.trails[i].hi) << 32);
+    if (lengths_out) lengths_out[i] = int32_t(T.trails[i].length);
+  }
+  return DMT_OK;
+}
+
+// host only: et_select and et_pmf, the functions the *_etree kernels call, at n cases
+int dmt_emitter_tree_select(const void* lights32, uint32_t count, const float* xs, const float* ys, const float* zs, uint64_t tri_count,
+                            const uint32_t* area_tri, const float* area_le, uint32_t area_count, int n, const float* p3, const float* n3,
+                            const float* u, float start_pmf, int32_t* index_out, float* pmf_out, float* pmf_by_trail_out) {
+  if (!emitterSceneOk(lights32, count, xs, ys, zs, tri_count, area_tri, area_le, area_count) || n < 0 ||
+      (n && (!p3 || !n3 || !u || !index_out || !pmf_out || !pmf_by_trail_out)))
+    return DMT_ERR_INVALID;
+  emitter_tree::Tree T;
+  if (!buildEmitterTree(lights32, count, xs, ys, zs, tri_count, area_tri, area_le, area_count, T) || T.nodes.empty()) return DMT_ERR_INVALID;
+  if (T.depth > kEmitterTreeMaxDepth) return DMT_ERR_STATE;  // its trails do not fit: a context keeps the uniform pick
+  for (int i = 0; i < n; ++i) {
+    float pmf = 0.f;
+    int const e = et_select(T.nodes.data(), p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], n3[3 * i], n3[3 * i + 1], n3[3 * i + 2], u[i], pmf);
+    index_out[i] = e, pmf_out[i] = e >= 0 ? start_pmf * pmf : 0.f;
+    pmf_by_trail_out[i] = e >= 0 ? start_pmf * et_pmf(T.nodes.data(), T.trails[size_t(e)], p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], n3[3 * i],
+                                                      n3[3 * i + 1], n3[3 * i + 2])
+                                 : 0.f;
+  }
+  return DMT_OK;
+}
+
+// host only: et_pmf of every emitter at (p, n)
+int dmt_emitter_tree_pmfs(const void* lights32, uint32_t count, const float* xs, const float* ys, const float* zs, uint64_t tri_count,
+                          const uint32_t* area_tri, const float* area_le, uint32_t area_count, const float* p3, const float* n3,
+                          float* pmf_out) {
+  if (!emitterSceneOk(lights32, count, xs, ys, zs, tri_count, area_tri, area_le, area_count) || !p3 || !n3 || !pmf_out) return DMT_ERR_INVALID;
+  emitter_tree::Tree T;
+  if (!buildEmitterTree(lights32, count, xs, ys, zs, tri_count, area_tri, area_le, area_count, T)) return DMT_ERR_INVALID;
+  if (T.depth > kEmitterTreeMaxDepth) return DMT_ERR_STATE;
+  emitter_tree::pmfs(T, p3, n3, pmf_out);
   return DMT_OK;
 }
 

@@ -3,9 +3,9 @@
 // envmap.hpp and the two tree headers, its helpers and entry points in light_host.hpp.
 //
 // Part of dmt_hip.hip's translation unit, included once before dmt_ctx: it uses DevBuf, Rec32, EnvView, RenderParams, the
-// node types of the two trees and the kFeatEnv / kFeatLightTree / kFeatLightTreeRef bits.
+// node types of the trees and the kFeatEnv / kFeatLightTree / kFeatLightTreeRef / kFeatEmitterTree bits.
 //
-// Three records.  A new context holds the default values below.
+// Four records.  A new context holds the default values below.
 //
 //   record   setter                   cleared by                       survives
 //   list     dmt_upload_lights        the next dmt_upload_lights       every other upload (dmt_upload_triangles, _bsdfs,
@@ -18,6 +18,10 @@
 //   env      dmt_upload_envmap        dmt_clear_envmap, the next       the same, and dmt_upload_lights and
 //                                     dmt_upload_envmap                dmt_set_light_sampling
 //
+//   emitters mode:                    mode: the next                   the same as the tree's mode.  nodes, trails, counts,
+//            dmt_set_emitter_sampling dmt_set_emitter_sampling         depth, valid and tooDeep are derived (below) and go
+//                                                                      with an invalidation
+//
 // Derived lazily: the tree's nodes, by the first launch or dmt_test_light_tree that wants them (resolveFeatures ->
 // ensureLightTree), from the host copy of the list, for the mode the context has then.  Two things invalidate the tree
 // (invalidateTree): dmt_upload_lights, and a dmt_set_light_sampling that CHANGES the mode -- through DMT_LIGHTS_UNIFORM too,
@@ -26,6 +30,16 @@
 // when they go.  An invalidation frees nothing: both node buffers may hold an earlier tree, and only the one of the current
 // mode, and only while valid, reaches a launch (fill).
 //
+// The emitter tree (emitter_tree.hpp) is derived lazily in the same place (resolveFeatures ->
+// ensureEmitterTree), from the host copy of the list, the host copy of the emissive-triangle list (SurfaceState::Emissive) and
+// the host mirrors of the soup's positions, which the vertex updates keep current.  invalidateEmitters is called by
+// dmt_upload_lights, dmt_upload_area_lights, a new soup (dmt_upload_triangles), dmt_update_vertices and
+// dmt_update_vertices_device, and a dmt_set_emitter_sampling that CHANGES the mode.  dmt_set_motion and dmt_clear_motion do
+// not apply: they leave key 0 and its mirrors alone, and a launch with motion and emissive triangles is refused.  It
+// survives everything else, dmt_set_light_sampling included.  Commit-last, the too-deep fall-back and draining are the
+// tree's (below): its two DevBufs are assigned like the tree's, and every call that invalidates it with new positions or a
+// new list has drained the stream or waited in hipFree before the next build.
+//
 // Feature bits (features), one list of conditions:
 //   kFeatEnv            an env map is present (env.view.w > 0); nothing else matters to it
 //   kFeatLightTree      all of: a list was uploaded; the mode is DMT_LIGHTS_TREE; the list has more than one record (infinite
@@ -33,6 +47,9 @@
 //                       (list.treeable: a directional record has no position); and the surfaces are plain -- no emissive
 //                       triangles, no image textures, no blend materials, which featuresOf knows and passes in
 //   kFeatLightTreeRef   the same with DMT_LIGHTS_TREE_REFERENCE
+//   kFeatEmitterTree    all of: the emitter mode is DMT_EMITTERS_TREE; emissive triangles are present; every list record is a
+//                       point or spot light, or the list is empty (a directional record keeps the uniform pick, as
+//                       `treeable` does); the last build was not too deep.  whyEmitters() names the first that fails
 // So a context with mode 1 set still runs the uniform rows when: no list was uploaded or it has fewer than two records, a
 // record is directional, the tree came out too deep, or emissive triangles, image textures or blend materials are present.
 // why() names the first of these that holds, in that order; dmt_test_light_tree refuses with it.
@@ -80,6 +97,17 @@ struct LightState {
     bool valid = false;                 // the buffer of `mode` holds the tree of `list`
     bool tooDeep = false;               // the last build exceeded its walk's guard: the uniform pick is used instead
   } tree;
+  // what the *_etree rows read as RenderParams::emitterTree / emitterTrails
+  struct Emitters {
+    int mode = DMT_EMITTERS_UNIFORM;
+    DevBuf<EmitterNode> nodes;
+    DevBuf<EmitterTrail> trails;        // [emitter]
+    uint32_t emitters = 0, nodeCount = 0;  // of the last build
+    int depth = 0;
+    double buildMs = 0.0;               // host time of the last build
+    bool valid = false;                 // the buffers hold the tree of the list, the emissive triangles and the positions
+    bool tooDeep = false;               // the last build exceeded kEmitterTreeMaxDepth: the uniform pick is used instead
+  } emitters;
   // what the *_env rows read as RenderParams::env
   struct Env {
     DevBuf<float> buf;  // A18: one allocation holding the five tables and the image
@@ -92,6 +120,18 @@ struct LightState {
     return !list.have ? Pick::NoList : tree.mode == DMT_LIGHTS_UNIFORM ? Pick::UniformMode : list.count <= 1 ? Pick::OneLight
            : tree.tooDeep ? Pick::TooDeep : !(list.treeable && plainSurfaces) ? Pick::NotTreeable : Pick::Tree;
   }
+
+  // the emitter tree's turn: which pick the *_area rows' scenes run
+  enum class EmitterPick { Tree, UniformMode, NoTriangles, NotTreeable, TooDeep };
+  EmitterPick whyEmitters(uint32_t areaCount) const {
+    return emitters.mode != DMT_EMITTERS_TREE ? EmitterPick::UniformMode : areaCount == 0 ? EmitterPick::NoTriangles
+           : !(list.count == 0 || list.treeable) ? EmitterPick::NotTreeable : emitters.tooDeep ? EmitterPick::TooDeep : EmitterPick::Tree;
+  }
+  uint32_t emitterFeatures(uint32_t areaCount) const { return whyEmitters(areaCount) == EmitterPick::Tree ? kFeatEmitterTree : 0u; }
+  void fillEmitters(RenderParams& P, uint32_t areaCount) const {
+    if (emitters.valid && emitterFeatures(areaCount)) P.emitterTree = emitters.nodes.get(), P.emitterTrails = emitters.trails.get();
+  }
+  void invalidateEmitters() { emitters.valid = false, emitters.tooDeep = false; }
 
   // the layer's part of the feature mask (featuresOf).  A tree not built yet counts as applying: resolveFeatures builds it
   uint32_t features(bool plainSurfaces) const {

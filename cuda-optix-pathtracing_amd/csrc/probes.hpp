@@ -508,6 +508,22 @@ __global__ void k_test_light_tree(RenderParams P, int n, float const* pos3, floa
     idx4[4 * i + s] = s < sel.count ? int32_t(sel.indices[s]) : -1, pmf4[4 * i + s] = s < sel.count ? sel.pmfs[s] : 0.f;
 }
 
+// dmt_test_emitter_tree: the emitter choice of a bounce at (pos3, nrm3) with the random number u, one lane per case: et_select
+// on the tree the *_etree rows read, its probability formed as path_shade forms it, and et_pmf along the selected emitter's
+// trail as an emitter hit forms it
+__global__ void k_test_emitter_tree(RenderParams P, int n, float const* pos3, float const* nrm3, float const* u, float startPmf,
+                                    int32_t* idx, float* pmf, float* pmfTrail) {
+  KArgs const k = kargs_base();
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  EmitterNode const* const nodes = kargs(k)->emitterTree;
+  float const px = pos3[3 * i], py = pos3[3 * i + 1], pz = pos3[3 * i + 2], nx = nrm3[3 * i], ny = nrm3[3 * i + 1], nz = nrm3[3 * i + 2];
+  float treePmf = 0.f;
+  int const e = et_select(nodes, px, py, pz, nx, ny, nz, u[i], treePmf);
+  idx[i] = e, pmf[i] = e >= 0 ? startPmf * treePmf : 0.f;
+  pmfTrail[i] = e >= 0 ? startPmf * et_pmf(nodes, kargs(k)->emitterTrails[e], px, py, pz, nx, ny, nz) : 0.f;
+}
+
 typedef void (*TestTraceFn)(RenderParams, int, int32_t const*, int32_t const*, int32_t const*, float*);
 #define DMT_TEST_TRACE_ROW(suffix, mask, waves, body) {mask, k_test_trace<mask>},
 KernelRow<TestTraceFn> const kTestTraceKernels[] = {DMT_MEGAKERNELS(DMT_TEST_TRACE_ROW)};
@@ -737,6 +753,33 @@ int dmt_test_light_tree(dmt_ctx* ctx, int n, const float* pos3, const float* nrm
     return fail(ctx, DMT_ERR_STATE, "dmt_test_light_tree: no light tree on the device");
   hipLaunchKernelGGL(ref ? k_test_light_tree<true> : k_test_light_tree<false>, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, n, dP.get(),
                      dN.get(), dU.get(), start_pmf, dI.get(), dPmf.get(), dC.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_emitter_tree(dmt_ctx* ctx, int n, const float* pos3, const float* nrm3, const float* u, float start_pmf, int32_t* index_out,
+                          float* pmf_out, float* pmf_by_trail_out) {
+  if (!ctx || n < 0 || !pos3 || !nrm3 || !u || !index_out || !pmf_out || !pmf_by_trail_out) return DMT_ERR_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint32_t F = 0;  // the tree dmt_render would read, built first
+  if (int const rc = resolveFeatures(ctx, &F)) return rc;
+  switch (ctx->lights.whyEmitters(ctx->surf.area.count)) {  // where a launch runs the uniform rows there is no tree to walk
+    case LightState::EmitterPick::UniformMode: return fail(ctx, DMT_ERR_STATE, "dmt_test_emitter_tree: the context picks its emitters uniformly (dmt_set_emitter_sampling first)");
+    case LightState::EmitterPick::NoTriangles: return fail(ctx, DMT_ERR_STATE, "dmt_test_emitter_tree: no emissive triangles (dmt_upload_area_lights); the emitter tree is not used");
+    case LightState::EmitterPick::NotTreeable: return fail(ctx, DMT_ERR_STATE, "dmt_test_emitter_tree: the light list holds a directional light; the uniform pick is used");
+    case LightState::EmitterPick::TooDeep: return fail(ctx, DMT_ERR_STATE, ("dmt_test_emitter_tree: the emitter tree is too deep for the walk's guard (" +
+                                                       std::to_string(ctx->lights.emitters.depth) + " levels); the uniform pick is used instead").c_str());
+    case LightState::EmitterPick::Tree: break;
+  }
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<float> dP(p, pos3, 3), dN(p, nrm3, 3), dU(p, u, 1);
+  ProbeOut<int32_t> dI(p, index_out, 1);
+  ProbeOut<float> dPmf(p, pmf_out, 1), dTrail(p, pmf_by_trail_out, 1);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  RenderParams const P = baseParams(ctx, p.threads(64));
+  if (!P.emitterTree || !P.emitterTrails) return fail(ctx, DMT_ERR_STATE, "dmt_test_emitter_tree: no emitter tree on the device");
+  hipLaunchKernelGGL(k_test_emitter_tree, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, P, n, dP.get(), dN.get(), dU.get(), start_pmf,
+                     dI.get(), dPmf.get(), dTrail.get());
   return finishProbe(ctx, p);
 }
 

@@ -156,6 +156,7 @@ int dmt_upload_area_lights(dmt_ctx* ctx, const uint32_t* triangle_index, const f
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   SurfaceState::Emissive& area = ctx->surf.area = SurfaceState::Emissive{};
+  ctx->lights.invalidateEmitters();  // the emitter tree was of the old list
   if (count == 0 || !ctx->haveTris) return DMT_OK;
   std::vector<uint32_t> of(ctx->triCount, 0xFFFFFFFFu);
   for (uint32_t k = 0; k < count; ++k) {
@@ -165,6 +166,7 @@ int dmt_upload_area_lights(dmt_ctx* ctx, const uint32_t* triangle_index, const f
   HIP_TRY(ctx, area.of.assign(of.data(), of.size()));
   HIP_TRY(ctx, area.tri.assign(triangle_index, count));
   HIP_TRY(ctx, area.le.assign(radiance_rgb, 3 * size_t(count)));
+  area.hostTri.assign(triangle_index, triangle_index + count), area.hostLe.assign(radiance_rgb, radiance_rgb + 3 * size_t(count));
   area.count = count;
   return DMT_OK;
 }

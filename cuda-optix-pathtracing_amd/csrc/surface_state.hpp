@@ -61,6 +61,8 @@ struct SurfaceState {
     DevBuf<uint32_t> of, tri;  // [triangle] index into the list, 0xFFFFFFFF: not emissive; [count] triangle index
     DevBuf<float> le;          // [count] rgb radiance
     uint32_t count = 0;
+    std::vector<uint32_t> hostTri;  // host copies of tri and le: what the emitter tree is built from (light_host.hpp)
+    std::vector<float> hostLe;
   } area;
   // material kind per triangle (k_megakernel's ggx_park; dmt_tri_kind_bits): bit i of word i >> 5 is set when the material
   // of ORIGINAL triangle i is a GGX one.  Host arithmetic over the soup's material ids and the BSDF records' type words,

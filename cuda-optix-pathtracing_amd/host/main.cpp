@@ -4,7 +4,7 @@
 //   * dmt-tracer (cli/CLIManager.cpp:11-36): --device|-d cpu|gpu, --scene|-s <file>, --out|-o <path>, --time|-t,
 //       --help|-h.  `--device cpu` is refused: this build has no CPU renderer (the CPU restatement used by the tests is test
 //       infrastructure and is never linked into the product).
-// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --bvh-build host|gpu, --light-tree, --light-tree-reference, --texture-filter,
+// plus --max-depth <N> (reference constant 32), --gpu-ordinal <N>, --bvh, --bvh-build host|gpu, --light-tree, --light-tree-reference, --emitter-tree, --texture-filter,
 // --adaptive <threshold> / --min-spp <N> (dmt_render_adaptive: --spp is the cap, --kspp the round), and --gpus <N>: N contexts, one per GPU
 // (ordinals 0..N-1), each rendering the interleaved 8x8 tiles j mod N == rank (dmt_set_partition) concurrently; the N
 // films are disjoint and summed on the host (x + 0: an exact gather).  bench.py's N-process RCCL path is the scalable
@@ -40,6 +40,7 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   bool bvh = false;       // --bvh: traverse the 4-wide BVH instead of testing every triangle
   bool lightTree = false; // --light-tree: importance-driven light choice (csrc/light_tree.hpp) instead of the uniform pick
   bool textureFilter = false; // --texture-filter: first-hit MIP / EWA filtering of image textures (DMT_TEXFILTER_REFERENCE)
+  bool emitterTree = false; // --emitter-tree: emissive triangles and lights picked through the emitter tree (csrc/emitter_tree.hpp)
   bool lightTreeRef = false; // --light-tree-reference: the reference's tree semantics, up to four lights per bounce (csrc/light_tree_ref.hpp)
   bool widthSet = false, heightSet = false, sppSet = false, depthSet = false;
   bool adaptive = false;      // --adaptive <threshold>: adaptive sampling, --spp samples at most, rounds of --kspp
@@ -170,6 +171,8 @@ void printHelp() {
       "  --bvh-build <host|gpu> -- who builds the tree of --bvh: one host core (binned SAH, the default) or the GPU (LBVH:\n"
       "                       a much faster build of a slightly looser tree; same image bit for bit)\n"
       "  --light-tree      -- pick the NEE light through a light BVH (flux x cosine / distance^2) instead of uniformly\n"
+      "  --emitter-tree    -- with emissive triangles: pick the NEE emitter (triangle or light) through a light BVH with normal\n"
+      "                       cones instead of uniformly; without emissive triangles it changes nothing\n"
       "  --light-tree-reference -- the reference's light tree semantics: cones, adaptive cuts, up to four lights per bounce\n"
       "  --texture-filter  -- filter image textures at the camera ray's first hit (MIP levels / EWA by the pixel footprint)\n"
       "                       instead of the level-0 bilinear lookup\n"
@@ -225,6 +228,7 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--bvh-build" && more) c.bvhBuildSet = true, c.bvhBuildArg = argv[++i];
     else if (a == "--light-tree") c.lightTree = true;
     else if (a == "--light-tree-reference") c.lightTreeRef = true;
+    else if (a == "--emitter-tree") c.emitterTree = true;
     else if (a == "--texture-filter") c.textureFilter = true;
     else if (a == "--kspp" && more) c.kspp = std::atoi(argv[++i]);
     else if (a == "--adaptive" && more) c.adaptive = true, c.adaptiveArg = argv[++i];
@@ -433,6 +437,7 @@ int main(int argc, char** argv) {
     if (cfg.bvh && dmt_set_accel(ctx, DMT_ACCEL_BVH) != DMT_OK) return fail(ctx, "dmt_set_accel");
     if (dmt_set_partition(ctx, r, cfg.gpus) != DMT_OK) return fail(ctx, "dmt_set_partition");
     if (cfg.lightTree && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
+    if (cfg.emitterTree && dmt_set_emitter_sampling(ctx, DMT_EMITTERS_TREE) != DMT_OK) return fail(ctx, "dmt_set_emitter_sampling");
     if (cfg.lightTreeRef && dmt_set_light_sampling(ctx, DMT_LIGHTS_TREE_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_light_sampling");
     if (cfg.textureFilter && dmt_set_texture_filter(ctx, DMT_TEXFILTER_REFERENCE) != DMT_OK) return fail(ctx, "dmt_set_texture_filter");
     if (cfg.shutterSet && dmt_set_shutter(ctx, cfg.shutterOpen, cfg.shutterClose) != DMT_OK) return fail(ctx, "dmt_set_shutter");

@@ -450,6 +450,38 @@ int dmt_light_tree_pmfs(const void* lights32, uint32_t count, const float* p3, c
  * (csrc/light_tree_ref.hpp LightTreeRefNode).  nodes_out has room for `cap` records; node_count and depth are always
  * reported, and a cap below node_count is refused (DMT_ERR_INVALID) with nothing written to nodes_out. */
 int dmt_light_tree_nodes(const void* lights32, uint32_t count, int mode, void* nodes_out, uint32_t cap, int* node_count, int* depth);
+/* How next-event estimation picks among [uploaded lights..., emissive triangles...] when emissive triangles
+ * (dmt_upload_area_lights) are present.  DMT_EMITTERS_UNIFORM (default): the uniform pick.  DMT_EMITTERS_TREE: a light BVH
+ * with normal cones over the point / spot lights and the emissive triangles together (csrc/emitter_tree.hpp, after the light
+ * BVH of pbrt-v4), walked once per bounce; a path ray that hits an emissive triangle weighs it with the
+ * tree's probability of that triangle at the vertex the ray left.  Same expected image, less noise with many emitters.
+ * Without emissive triangles, with a directional light in the list, or where the tree comes out deeper than its walk's
+ * guard (a note in dmt_last_error), the uniform rows run as if the mode were not set.  Independent of
+ * dmt_set_light_sampling.  An unknown mode is refused. */
+#define DMT_EMITTERS_UNIFORM 0
+#define DMT_EMITTERS_TREE 1
+int dmt_set_emitter_sampling(dmt_ctx* ctx, int mode);
+/* mode; active = a launch now runs the *_etree rows (builds the tree if it has to); emitters, nodes, depth (levels, a lone
+ * leaf = 1) and the host build time of the last build (zeros while not active).  Any pointer may be null. */
+int dmt_emitter_tree_info(dmt_ctx* ctx, int* mode, int* active, uint32_t* emitters, uint32_t* nodes, int* depth, double* build_ms);
+/* host only (no GPU): the emitter tree a context builds for `count` packed lights (point / spot only), a soup xs / ys / zs
+ * (4 floats per triangle and axis, as dmt_upload_triangles) of tri_count triangles and the emissive list area_tri / area_le
+ * (3 floats each) of area_count entries.  Emitter i < count is light i, otherwise triangle area_tri[i - count].  nodes_out:
+ * room for `cap` 48-byte records (csrc/emitter_tree.hpp EmitterNode), root first; trails_out / lengths_out: one bit trail
+ * (bit k = the choice at level k below the root, 1 = right) and its length per emitter; any of the three may be null.
+ * node_count and depth are always reported; a cap below node_count is refused with nothing written. */
+int dmt_emitter_tree_nodes(const void* lights32, uint32_t count, const float* xs, const float* ys, const float* zs, uint64_t tri_count,
+                           const uint32_t* area_tri, const float* area_le, uint32_t area_count, void* nodes_out, uint32_t cap,
+                           uint64_t* trails_out, int32_t* lengths_out, int* node_count, int* depth);
+/* host only: et_select at n cases (p3, n3, u) on that tree: index_out (-1: none), pmf_out = start_pmf x the walk's
+ * probability, pmf_by_trail_out = start_pmf x et_pmf along the selected emitter's trail (0 where none was selected) */
+int dmt_emitter_tree_select(const void* lights32, uint32_t count, const float* xs, const float* ys, const float* zs, uint64_t tri_count,
+                            const uint32_t* area_tri, const float* area_le, uint32_t area_count, int n, const float* p3, const float* n3,
+                            const float* u, float start_pmf, int32_t* index_out, float* pmf_out, float* pmf_by_trail_out);
+/* host only: et_pmf of every emitter (count + area_count values) at point p3 with normal n3 */
+int dmt_emitter_tree_pmfs(const void* lights32, uint32_t count, const float* xs, const float* ys, const float* zs, uint64_t tri_count,
+                          const uint32_t* area_tri, const float* area_le, uint32_t area_count, const float* p3, const float* n3,
+                          float* pmf_out);
 /* How DMT_ACCEL_BVH launches are executed (results are bit-identical either way): 0 = automatic = 1 = the megakernel
  * (fastest on every measured scene); 2 = the device-side wavefront -- generate / trace / shade / fold kernels over
  * path-state arrays in HBM, csrc/wavefront.hpp -- kept as a measured alternative.  paths_per_pass: path
@@ -934,6 +966,14 @@ int dmt_test_light(dmt_ctx* ctx, const void* light32, int n, const float* pos3, 
  * deeper than the walk's guard. */
 int dmt_test_light_tree(dmt_ctx* ctx, int n, const float* pos3, const float* nrm3, const float* u, float start_pmf, int32_t* indices4,
                         float* pmfs4, int32_t* counts);
+/* the emitter choice of a bounce at n shading points (pos3, nrm3) with one random number u each, on the device: et_select and
+ * et_pmf themselves, one lane per case, on the tree the context uploaded.  index_out: the emitter or -1; pmf_out = start_pmf x
+ * the walk's probability; pmf_by_trail_out = start_pmf x et_pmf along the selected emitter's trail (0 where none).
+ * DMT_ERR_STATE, with the reason, where the emitter tree is not active (dmt_emitter_tree_info). */
+/* scratch (private segment) bytes per lane of the kernel dmt_render would launch now; 0: no spills, no stack */
+int dmt_kernel_scratch(dmt_ctx* ctx, int* scratch_bytes);
+int dmt_test_emitter_tree(dmt_ctx* ctx, int n, const float* pos3, const float* nrm3, const float* u, float start_pmf, int32_t* index_out,
+                          float* pmf_out, float* pmf_by_trail_out);
 int dmt_test_half(dmt_ctx* ctx, int n, const float* f_in, uint16_t* h_out, const uint16_t* h_in,
                   float* f_out);
 /* radiance of individual (pixel, sample) paths of the uploaded scene */
