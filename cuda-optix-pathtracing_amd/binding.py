@@ -79,6 +79,7 @@ EXPORTED_SYMBOLS = [
     "dmt_denoise_temporal", "dmt_temporal_reset", "dmt_temporal_info", "dmt_temporal_download",
     "dmt_set_sampler_table", "dmt_sampler_table_plan", "dmt_test_sampler_table",
     "dmt_set_lens", "dmt_lens_info", "dmt_lens_rays", "dmt_focus_distance_at", "dmt_test_lens_values",
+    "dmt_set_pixel_filter", "dmt_pixel_filter_info", "dmt_pixel_filter_table", "dmt_pixel_filter_positions", "dmt_test_film_positions",
     "dmt_set_motion", "dmt_clear_motion", "dmt_set_shutter", "dmt_motion_info", "dmt_shutter_times", "dmt_motion_positions",
     "dmt_motion_bvh_validate", "dmt_test_shutter_times", "dmt_test_closest_hit_at",
     "dmt_upload_vertex_normals", "dmt_clear_vertex_normals", "dmt_vertex_normals_info", "dmt_smooth_normals",
@@ -184,6 +185,41 @@ def lens_rays(camera44, lens_radius, focus_distance, pxs, pys, ss):
     if rc != 0:
         raise DmtError(f"dmt_lens_rays failed ({rc})")
     return o, d, u
+
+
+# dmt_set_pixel_filter kinds (include/dmt_hip.h)
+FILTER_BOX = 0
+FILTER_TENT = 1
+FILTER_GAUSSIAN = 2
+FILTER_BLACKMAN_HARRIS = 3
+PIXEL_FILTER_KINDS = {"box": FILTER_BOX, "tent": FILTER_TENT, "triangle": FILTER_TENT, "gaussian": FILTER_GAUSSIAN,
+                      "blackman-harris": FILTER_BLACKMAN_HARRIS}
+
+
+def pixel_filter_table(kind, radius, param=0.0):
+    """Host only (dmt_pixel_filter_table): the 257 float32 knots W(i / 256) of the filter's inverse CDF over [-1, 1]."""
+    lib = load_library()
+    knots = np.zeros(257, np.float32)
+    rc = lib.dmt_pixel_filter_table(int(kind), C.c_float(radius), C.c_float(param), knots.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise DmtError(f"dmt_pixel_filter_table failed ({rc})")
+    return knots
+
+
+def pixel_filter_positions(width, height, kind, radius, param, pxs, pys, ss):
+    """Host only (dmt_pixel_filter_positions): the film positions [n, 2] of samples ss of pixels (pxs, pys) of a
+    width x height frame under the filter (box with radius 0.5: the unfiltered positions), the device's bit for bit."""
+    lib = load_library()
+    pxs, pys, ss = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (pxs, pys, ss))
+    n = pxs.shape[0]
+    assert pys.shape[0] == n and ss.shape[0] == n
+    xy = np.zeros((n, 2), np.float32)
+    as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = lib.dmt_pixel_filter_positions(int(width), int(height), int(kind), C.c_float(radius), C.c_float(param), int(n), as_p(pxs),
+                                        as_p(pys), as_p(ss), as_p(xy))
+    if rc != 0:
+        raise DmtError(f"dmt_pixel_filter_positions failed ({rc})")
+    return xy
 
 
 def shutter_times(width, height, open, close, pxs, pys, ss):
@@ -1007,6 +1043,23 @@ class Renderer:
         self._check(fn(self._ctx, int(n), _p(tri), _p(bu), _p(bv), _p(rd), _p(ns)), "dmt_test_shading_normal")
         return ns
 
+    def set_pixel_filter(self, kind, radius, param=0.0):
+        """Pixel reconstruction filter, importance-sampled per sample (dmt_set_pixel_filter).  kind: FILTER_BOX, FILTER_TENT,
+        FILTER_GAUSSIAN (param = sigma) or FILTER_BLACKMAN_HARRIS, or its name ("box", "tent", "gaussian",
+        "blackman-harris"); radius in pixels, in (0, 8].  Box with radius 0.5, the default, is inactive.  The filter
+        survives set_camera and scene uploads."""
+        if isinstance(kind, str):
+            if kind not in PIXEL_FILTER_KINDS:
+                raise DmtError(f"set_pixel_filter: unsupported kind '{kind}'")
+            kind = PIXEL_FILTER_KINDS[kind]
+        self._check(self._lib.dmt_set_pixel_filter(self._ctx, int(kind), C.c_float(radius), C.c_float(param)), "dmt_set_pixel_filter")
+
+    def pixel_filter_info(self):
+        """The context's pixel filter as a dict: kind, radius, param, active."""
+        k, a, r, p = C.c_int(), C.c_int(), C.c_float(), C.c_float()
+        self._check(self._lib.dmt_pixel_filter_info(self._ctx, C.byref(k), C.byref(r), C.byref(p), C.byref(a)), "dmt_pixel_filter_info")
+        return {"kind": k.value, "radius": r.value, "param": p.value, "active": bool(a.value)}
+
     def focus_distance_at(self, fx, fy):
         """Autofocus (dmt_focus_distance_at): the depth along the viewing direction of what the pinhole ray through the
         continuous film coordinates (fx, fy) hits; DmtError when it leaves the scene."""
@@ -1014,12 +1067,29 @@ class Renderer:
         self._check(self._lib.dmt_focus_distance_at(self._ctx, C.c_float(fx), C.c_float(fy), C.byref(d)), "dmt_focus_distance_at")
         return d.value
 
-    def upload_scene(self, scene, vertex_normals=False, opacity=True):
+    @staticmethod
+    def scene_pixel_filter(scene):
+        """(kind, radius, sigma) of the pixel filter a scene records, for set_pixel_filter; None for a scene without one;
+        DmtError for a kind the library does not offer."""
+        pf = getattr(scene, "pixel_filter", None)
+        if pf is None:
+            return None
+        if pf.get("kind") is None:
+            raise DmtError(f"the scene's pixel filter '{pf.get('type')}' is an unsupported kind (signed filters need a per-sample weight)")
+        return int(pf["kind"]), float(pf["radius"]), float(pf["sigma"])
+
+    def upload_scene(self, scene, vertex_normals=False, opacity=True, pixel_filter=False):
         """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays; a scene with a `lens`
         (lens_radius, focus_distance), as the loaders report one, sets the context's lens too, and one with a `medium`
         (the keyword arguments of set_medium, and the "extinction" and "emission" of set_medium_spectrum) the context's medium.  vertex_normals: also
         upload the scene's `tri_normals` (smooth shading); off by default, the files' normals are not used unasked.
-        opacity: upload the scene's `mat_opacity` / `opacity_cutoff` (alpha cutouts) when it carries them."""
+        opacity: upload the scene's `mat_opacity` / `opacity_cutoff` (alpha cutouts) when it carries them.
+        pixel_filter: also set the pixel filter the scene records (`pixel_filter`: PBRT PixelFilter, JSON film.filter); off by
+        default, so that every load renders as before.  DmtError, before anything is uploaded, for a recorded kind the library
+        does not offer (mitchell, sinc)."""
+        wanted_filter = self.scene_pixel_filter(scene) if pixel_filter else None
+        if wanted_filter is not None:
+            self.set_pixel_filter(*wanted_filter)
         self.upload_triangles(scene.xs, scene.ys, scene.zs, scene.mat_id)
         if vertex_normals:
             tn = getattr(scene, "tri_normals", None)
@@ -1412,6 +1482,15 @@ class Renderer:
         self._check(self._lib.dmt_test_camera_rays(self._ctx, n, _p(pxs), _p(pys), _p(ss), _p(o), _p(d)),
                     "dmt_test_camera_rays")
         return o, d
+
+    def test_film_positions(self, pxs, pys, ss):
+        """dmt_test_film_positions: the film positions [n, 2] of the samples as the device forms them under the context's
+        pixel filter (the device twin of pixel_filter_positions)."""
+        pxs, pys, ss = _i32(pxs), _i32(pys), _i32(ss)
+        n = pxs.shape[0]
+        xy = np.zeros((n, 2), np.float32)
+        self._check(self._lib.dmt_test_film_positions(self._ctx, n, _p(pxs), _p(pys), _p(ss), _p(xy)), "dmt_test_film_positions")
+        return xy
 
     def test_lens_values(self, pxs, pys, ss):
         """dmt_test_lens_values: (u10, u11) [n, 2] of the samples, as the device computes them."""

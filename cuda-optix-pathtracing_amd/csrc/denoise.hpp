@@ -99,7 +99,7 @@ DMT_DEV void aov_body(AovArgs const& A) {
       // camera and sampler re-read from the kernel arguments at the point of use: held in SGPRs across the triangle pass
       // they would spill (see kargs)
       ColdArgs const c = load_cold_args(k);
-      Ray const r = camera_ray_any(c.cam, c.sp, px, py, base + int32_t(s) * (c.sp.scale0 * c.sp.scale1), kargs(k)->lensR, kargs(k)->lensD);  // the film's rays: lens rays under a lens
+      Ray const r = camera_ray_any(c.cam, c.sp, px, py, base + int32_t(s) * (c.sp.scale0 * c.sp.scale1), load_camera_extra(k));  // the film's rays: lens rays under a lens, filtered positions under a pixel filter
       set_ray(st, r.o, r.d);
       st.active = alive;
       int best;

@@ -117,7 +117,8 @@ struct RenderParams {
   float2 const* samTabJit;   // one float2 per entry: pixel2d, the film jitter
   float2 const* samTabLens;  // launches with a lens only: one float2 per entry, lens_values (u10, u11)
   uint32_t samTabS0, samTabPw, samTabPh;
-  float lensR, lensD;        // thin lens (dmt_set_lens): radius (0: pinhole) and focus distance; read where a camera ray is made
+  float camTail, lensD;      // camTail: non-zero when prepare_sample's cold tail has work (a lens, or a pixel filter the sampler table
+                             // does not already carry); the lens radius itself is lensRad, below.  lensD: the focus distance
   int maxDepth;
   int shadeThreshold;         // BVH megakernel: shade when this many lanes of the wave have finished their rays (bvhShadeThreshold)
   EnvView env;                // A18 env map (w == 0: none); read by the *_env kernels only
@@ -175,6 +176,10 @@ struct RenderParams {
   // emitter, the bit trail of its leaf.  Read by the *_etree kernels only.  After `mediumSpectrum`, so that no other field moves
   EmitterNode const* emitterTree;
   EmitterTrail const* emitterTrails;
+  // camera-side state read where a camera ray is made: the thin lens's radius (dmt_set_lens; 0: pinhole) and the pixel filter
+  // (dmt_set_pixel_filter; filtKnots null: box 0.5, no warp).  After `emitterTrails`, so that no other field moves
+  float lensRad, filtR;
+  FilterBin const* filtKnots;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -194,6 +199,10 @@ DMT_DEV KArgs kargs_base() { return (KArgs)__builtin_amdgcn_kernarg_segment_ptr(
 DMT_DEV KArgs kargs(KArgs p) {
   asm volatile("" : "+s"(p));
   return p;
+}
+DMT_DEV CameraExtra load_camera_extra(KArgs k) {  // at the point of use, like the cold arguments
+  k = kargs(k);
+  return CameraExtra{k->lensRad, k->lensD, k->filtKnots, k->filtR};
 }
 DMT_DEV SceneView load_scene(KArgs k) {
   k = kargs(k);
@@ -312,10 +321,10 @@ DMT_DEV void set_shadow_ray(PathState& st, f3 o, f3 d) {
 }
 
 DMT_DEV void path_begin(PathState& st, CameraXf const& cam, SamplerParams const& sp, int px, int py,
-                        int32_t pixBase, uint32_t s, float lensR, float lensD) {
+                        int32_t pixBase, uint32_t s, CameraExtra const& extra) {
   int32_t const hidx = pixBase + int32_t(s) * (sp.scale0 * sp.scale1);
   st.rng.start(uint32_t(hidx));
-  Ray const r = camera_ray_any(cam, sp, px, py, hidx, lensR, lensD);
+  Ray const r = camera_ray_any(cam, sp, px, py, hidx, extra);
   set_ray(st, r.o, r.d);
   st.beta = mk3(1, 1, 1);
   st.L = mk3(0, 0, 0);
@@ -1173,27 +1182,45 @@ DMT_DEV ColdArgs load_cold_args(KArgs Pk) {
 // branch inside the lens-free code, or this tail laid out in line, cost k_megakernel_bvh_env a spilled VGPR (8 bytes of
 // scratch), and a noinline function gave eight rows a stack frame (and cannot take the opaque kernarg pointer); as an
 // unlikely tail no row gains scratch.
+// Under a pixel filter (dmt_set_pixel_filter) this is also where the jitter is warped: the one cold tail for
+// lens and filter.  A table's jitter plane already holds the warped jitter, so a tabulated launch gets here only for a lens.
+// Without a lens the tail forms the pinhole ray through camera_ray_jittered, the function the tabulated main path calls.
+// Its form is the measured one again: jitter, then lens values, then one choice between the two ray
+// functions.  A tail split into a lens branch and a filter branch cost k_megakernel_env_tex 4 bytes of scratch, and a lower
+// clamp on filter_warp's bin index, or two 4-byte loads per axis from the knots themselves, cost forty rows a VGPR.
+// The sample's film jitter as the tail needs it when no table supplies it: pixel2d, warped under a pixel filter.
+DMT_DEV f2 tail_jitter(KArgs Pk, int32_t hidx) {
+  KArgs const k = kargs(Pk);
+  SamplerParams sp;
+  sp.scale0 = k->sp.scale0, sp.scale1 = k->sp.scale1, sp.exp0 = k->sp.exp0, sp.exp1 = k->sp.exp1, sp.inv0 = k->sp.inv0, sp.inv1 = k->sp.inv1;
+  f2 jit = pixel2d(sp, hidx);
+  if (FilterBin const* const knots = kargs(Pk)->filtKnots) {
+    float const fr = kargs(Pk)->filtR;
+    jit.x = filter_warp(knots, fr, jit.x);
+    jit.y = filter_warp(knots, fr, jit.y);
+  }
+  return jit;
+}
 DMT_DEV void prepare_lens_ray(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
   float* const prep = s_prep + threadIdx.x;
   f2 jit;
-  LensU lu;
-  if (float2 const* const tab = kargs(Pk)->samTabLens) {  // launches with a table: its jitter and lens planes
+  LensU lu{0.f, 0.f};
+  float const lensR = kargs(Pk)->lensRad;
+  if (float2 const* const tab = kargs(Pk)->samTabLens) {  // launches with a table and a lens: its jitter (warped already) and lens planes
     KArgs const k = kargs(Pk);
     uint32_t const e = ((s - k->samTabS0) * k->samTabPh + (uint32_t(py) & 127u)) * k->samTabPw + (uint32_t(px) & 127u);
     float2 const j = k->samTabJit[e], u = tab[e];
     jit = mk2(j.x, j.y), lu = LensU{u.x, u.y};
-  } else {
-    KArgs const k = kargs(Pk);
-    SamplerParams sp;
-    sp.scale0 = k->sp.scale0, sp.scale1 = k->sp.scale1, sp.exp0 = k->sp.exp0, sp.exp1 = k->sp.exp1, sp.inv0 = k->sp.inv0, sp.inv1 = k->sp.inv1;
-    int32_t const hidx = pixBase + int32_t(s) * (sp.scale0 * sp.scale1);
-    jit = pixel2d(sp, hidx), lu = lens_values(uint32_t(hidx));
+  } else {  // computed: a lens, a pixel filter, or both
+    int32_t const hidx = pixBase + int32_t(s) * (kargs(Pk)->sp.scale0 * kargs(Pk)->sp.scale1);
+    jit = tail_jitter(Pk, hidx);
+    if (lensR > 0.f) lu = lens_values(uint32_t(hidx));
   }
   CameraXf cam;
   KArgs const kc = kargs(Pk);
 #pragma unroll
   for (int i = 0; i < 16; ++i) cam.cfr[i] = kc->cam.cfr[i], cam.rfc[i] = kc->cam.rfc[i];
-  Ray const r = camera_ray_lens(cam, px, py, jit, kc->lensR, kc->lensD, lu);
+  Ray const r = lensR > 0.f ? camera_ray_lens(cam, px, py, jit, lensR, kc->lensD, lu) : camera_ray_jittered(cam, px, py, jit);
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
 }
@@ -1205,7 +1232,7 @@ DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t 
   float* const prep = s_prep + threadIdx.x;
   Ray r;
 #if DMT_LENS_EARLY
-  float const lensR = kargs(Pk)->lensR;  // with the table pointer, so that the compare below finds it ready
+  float const lensR = kargs(Pk)->camTail;  // lens or filter; with the table pointer, so that the compare below finds it ready
 #endif
   if (float4 const* const tab = kargs(Pk)->samTab) {
     KArgs const k = kargs(Pk);
@@ -1230,9 +1257,9 @@ DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t 
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
 #if !DMT_LENS_EARLY
-  float const lensR = kargs(Pk)->lensR;
+  float const lensR = kargs(Pk)->camTail;
 #endif
-  if (__builtin_expect(lensR > 0.f, 0)) prepare_lens_ray(Pk, px, py, pixBase, s);  // wave-uniform, laid out of line
+  if (__builtin_expect(lensR > 0.f, 0)) prepare_lens_ray(Pk, px, py, pixBase, s);  // lens or filter: wave-uniform, laid out of line
   if constexpr (MOTION) motion_set_prepared(motion_sample_time(Pk, pixBase, s));
 }
 template <bool MOTION = false>
@@ -1758,9 +1785,10 @@ DMT_STATS_MEGAKERNELS(DMT_DEFINE_MEGAKERNEL)
 
 // Fills the sampler table of a launch (RenderParams::samTab): one thread per entry (sample s0 + k, period pixel (x, y)),
 // with the functions prepare_sample's compute path calls, so that a loaded sample is the computed one bit for bit.
-// `lens` (null without a lens): the third plane, lens_values of the entry's Halton index.
+// `lens` (null without a lens): the third plane, lens_values of the entry's Halton index.  `knots` (null without a pixel
+// filter): the jitter is warped by the filter before it is stored.
 __global__ void __launch_bounds__(256) k_sampler_table(SamplerParams sp, uint32_t s0, uint32_t n, uint32_t pw, uint32_t ph,
-                                                       float4* vals, float2* jit, float2* lens) {
+                                                       float4* vals, float2* jit, float2* lens, FilterBin const* knots, float filtR) {
   uint32_t const e = blockIdx.x * 256u + threadIdx.x;  // (entries < 2^31: samplerTablePlan)
   if (e >= n * pw * ph) return;
   uint32_t const x = e % pw, row = e / pw, y = row % ph, k = row / ph;
@@ -1769,7 +1797,8 @@ __global__ void __launch_bounds__(256) k_sampler_table(SamplerParams sp, uint32_
   sampler_values(uint32_t(hidx), u);
   vals[2 * size_t(e)] = make_float4(u[0 * kLdsThreads], u[1 * kLdsThreads], u[2 * kLdsThreads], u[3 * kLdsThreads]);
   vals[2 * size_t(e) + 1] = make_float4(u[4 * kLdsThreads], u[5 * kLdsThreads], u[6 * kLdsThreads], u[7 * kLdsThreads]);
-  f2 const p = pixel2d(sp, hidx);
+  f2 p = pixel2d(sp, hidx);
+  if (knots) p = f2{filter_warp(knots, filtR, p.x), filter_warp(knots, filtR, p.y)};  // the jitter plane holds the warped jitter
   jit[e] = make_float2(p.x, p.y);
   if (lens) {
     LensU const u = lens_values(uint32_t(hidx));
@@ -1869,6 +1898,14 @@ struct dmt_ctx {
   CameraXf xf{};
   SamplerParams sp{};
   float lensR = 0.f, lensD = 1.f;  // thin lens (dmt_set_lens): radius 0 = pinhole; survives dmt_set_camera and scene uploads
+  // pixel filter (dmt_set_pixel_filter): box 0.5, the default, is inactive (no table, no warp); survives like the lens
+  struct PixelFilter {
+    int kind = DMT_FILTER_BOX;
+    float radius = 0.5f, param = 0.f;
+    bool active = false;
+    DevBuf<FilterBin> knots;  // kFilterBins pairs while active (kept, unread, after a return to the default)
+    FilterBin const* view() const { return active ? knots.get() : nullptr; }
+  } filt;
   // film: the context's own, or the caller's after dmt_film_bind (which frees the own one)
   DevBuf<float4> ownMean, ownM2;
   float4* d_mean = nullptr;
@@ -2213,7 +2250,9 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   P.bvh = bvhView(c, threads);
   P.cam = c->xf;
   P.sp = c->sp;
-  P.lensR = c->lensR, P.lensD = c->lensD;
+  P.lensRad = c->lensR, P.lensD = c->lensD;
+  P.filtKnots = c->filt.view(), P.filtR = c->filt.radius;
+  P.camTail = (c->lensR > 0.f || c->filt.active) ? 1.f : 0.f;  // (a tabulated launch without a lens clears it: growLaunchBuffers)
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   c->lights.fill(P, plainSurfaces(c));
@@ -2222,6 +2261,8 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   c->surf.fill(P);
   return P;
 }
+
+CameraExtra cameraExtraOf(dmt_ctx const* c) { return CameraExtra{c->lensR, c->lensD, c->filt.view(), c->filt.radius}; }
 
 int finishTest(dmt_ctx* ctx) {
   HIP_TRY(ctx, hipGetLastError());
@@ -2637,6 +2678,117 @@ int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
   if (tri < 0) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: the ray leaves the scene");
   float const* const m = ctx->xf.rfc;  // column 2 = the viewing direction
   *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
+  return DMT_OK;
+}
+
+// ---- pixel filter ---------------------------------------------------------------------
+// The filter's 1-D profile over w = x / radius in [-1, 1], integrated in float64 (each kind has a closed-form integral) and
+// normalised to F(-1) = 0, F(1) = 1.  False for arguments dmt_set_pixel_filter refuses.
+static bool pixelFilterArgsOk(int kind, float radius, float param) {
+  if (kind < DMT_FILTER_BOX || kind > DMT_FILTER_BLACKMAN_HARRIS) return false;
+  if (!std::isfinite(radius) || !(radius > 0.f) || radius > 8.f) return false;
+  if (kind == DMT_FILTER_GAUSSIAN && !(std::isfinite(param) && param > 0.f)) return false;
+  return true;
+}
+static double pixelFilterIntegral(int kind, double sigmaW, double w) {  // unnormalised, from -1 to w
+  double const pi = 3.14159265358979323846;
+  switch (kind) {
+    case DMT_FILTER_TENT: return w <= 0.0 ? 0.5 * (1.0 + w) * (1.0 + w) : 1.0 - 0.5 * (1.0 - w) * (1.0 - w);
+    case DMT_FILTER_GAUSSIAN: {  // max(0, G(w) - G(1)), pbrt-v4's; sigmaW = sigma / radius
+      double const a = 1.0 / (sigmaW * std::sqrt(2.0));
+      return sigmaW * std::sqrt(pi / 2.0) * (std::erf(a * w) + std::erf(a)) - std::exp(-0.5 / (sigmaW * sigmaW)) * (w + 1.0);
+    }
+    case DMT_FILTER_BLACKMAN_HARRIS: {  // the four-term window over t = (w + 1) / 2
+      double const t = 0.5 * (w + 1.0);
+      return 2.0 * (0.35875 * t - 0.48829 * std::sin(2.0 * pi * t) / (2.0 * pi) + 0.14128 * std::sin(4.0 * pi * t) / (4.0 * pi) -
+                    0.01168 * std::sin(6.0 * pi * t) / (6.0 * pi));
+    }
+    default: return w + 1.0;  // box
+  }
+}
+// The kFilterKnots knots W(i / 256) of the inverse CDF: bisection on the float64 integral for the lower half, mirrored for
+// the upper one (the profiles are even), rounded to float32 once.  False when the profile has no mass in float64 (a Gaussian
+// whose sigma is so far above the radius that G(w) - G(1) cancels).
+static bool pixelFilterKnots(int kind, float radius, float param, float* knots) {
+  double const sigmaW = kind == DMT_FILTER_GAUSSIAN ? double(param) / double(radius) : 1.0;
+  double const total = pixelFilterIntegral(kind, sigmaW, 1.0);
+  if (!(total > 1e-12) || !std::isfinite(total)) return false;
+  knots[0] = -1.f, knots[128] = 0.f, knots[256] = 1.f;
+  for (int i = 1; i < 128; ++i) {
+    double const target = total * (double(i) / 256.0);
+    double lo = -1.0, hi = 0.0;
+    for (int it = 0; it < 64; ++it) {
+      double const mid = 0.5 * (lo + hi);
+      (pixelFilterIntegral(kind, sigmaW, mid) < target ? lo : hi) = mid;
+    }
+    float k = float(0.5 * (lo + hi));
+    if (k < knots[i - 1]) k = knots[i - 1];  // monotone after the rounding to float32
+    knots[i] = k, knots[256 - i] = -k;
+  }
+  return true;
+}
+static bool pixelFilterIsDefault(int kind, float radius) { return kind == DMT_FILTER_BOX && radius == 0.5f; }
+// what filter_warp reads: per bin the knot and the fp32 difference to the next one
+static void pixelFilterBins(float const* knots, FilterBin* bins) {
+#pragma clang fp contract(off)
+  for (int i = 0; i < kFilterBins; ++i) bins[i] = FilterBin{knots[i], knots[i + 1] - knots[i]};
+}
+
+int dmt_pixel_filter_table(int kind, float radius, float param, float* knots257) {
+  if (!knots257 || !pixelFilterArgsOk(kind, radius, param)) return DMT_ERR_INVALID;
+  return pixelFilterKnots(kind, radius, param, knots257) ? DMT_OK : DMT_ERR_INVALID;
+}
+
+int dmt_set_pixel_filter(dmt_ctx* ctx, int kind, float radius, float param) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (!pixelFilterArgsOk(kind, radius, param))
+    return fail(ctx, DMT_ERR_INVALID,
+                "dmt_set_pixel_filter: a kind DMT_FILTER_BOX .. DMT_FILTER_BLACKMAN_HARRIS, a finite radius in (0, 8], and for the Gaussian a finite sigma > 0");
+  if (!pixelFilterIsDefault(kind, radius)) {
+    float knots[kFilterKnots];
+    if (!pixelFilterKnots(kind, radius, param, knots))
+      return fail(ctx, DMT_ERR_INVALID, "dmt_set_pixel_filter: the Gaussian's sigma is too large for its radius (the profile has no mass)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a launch in flight may still read the old table
+    FilterBin bins[kFilterBins];
+    pixelFilterBins(knots, bins);
+    HIP_TRY(ctx, ctx->filt.knots.assign(bins, kFilterBins));
+  }
+  ctx->filt.kind = kind, ctx->filt.radius = radius, ctx->filt.param = kind == DMT_FILTER_GAUSSIAN ? param : 0.f;
+  ctx->filt.active = !pixelFilterIsDefault(kind, radius);
+  return DMT_OK;
+}
+
+int dmt_pixel_filter_info(dmt_ctx* ctx, int* kind, float* radius, float* param, int* active) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (kind) *kind = ctx->filt.kind;
+  if (radius) *radius = ctx->filt.radius;
+  if (param) *param = ctx->filt.param;
+  if (active) *active = ctx->filt.active ? 1 : 0;
+  return DMT_OK;
+}
+
+int dmt_pixel_filter_positions(int width, int height, int kind, float radius, float param, int n, const int32_t* pxs, const int32_t* pys,
+                               const int32_t* ss, float* xy2) {
+  if (n < 0 || width <= 0 || height <= 0 || width > 65536 || height > 65536 || !pixelFilterArgsOk(kind, radius, param)) return DMT_ERR_INVALID;
+  if (n && (!pxs || !pys || !ss || !xy2)) return DMT_ERR_INVALID;
+  float knots[kFilterKnots];
+  bool const active = !pixelFilterIsDefault(kind, radius);
+  if (active && !pixelFilterKnots(kind, radius, param, knots)) return DMT_ERR_INVALID;
+  FilterBin bins[kFilterBins];
+  if (active) pixelFilterBins(knots, bins);
+  SamplerParams const sp = computeSamplerParams(width, height);
+  int64_t const stride = int64_t(sp.scale0) * sp.scale1;
+  for (int i = 0; i < n; ++i) {
+    if (pxs[i] < 0 || pys[i] < 0 || pxs[i] >= width || pys[i] >= height || ss[i] < 0 || (int64_t(ss[i]) + 1) * stride > 0x7FFFFFFFll)
+      return DMT_ERR_INVALID;  // outside the frame, or the sample overflows the 32-bit Halton index
+  }
+  for (int i = 0; i < n; ++i) {
+    int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * int32_t(stride);
+    f2 r = pixel2d(sp, h);
+    if (active) r = f2{filter_warp(bins, radius, r.x), filter_warp(bins, radius, r.y)};
+    xy2[2 * size_t(i)] = film_coord(r.x, pxs[i]), xy2[2 * size_t(i) + 1] = film_coord(r.y, pys[i]);
+  }
   return DMT_OK;
 }
 

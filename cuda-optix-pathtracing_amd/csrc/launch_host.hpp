@@ -283,6 +283,8 @@ int growLaunchBuffers(dmt_ctx* ctx, LaunchPlan const& L, uint32_t spp, RenderPar
     if (ctx->lensR > 0.f) {
       HIP_TRY(ctx, S.tab.lens.reserve(sliceEntries));
       P.samTabLens = S.tab.lens.get();
+    } else {
+      P.camTail = 0.f;  // a pixel filter alone: the jitter plane holds the warped jitter, the main path needs no tail
     }
   }
   return DMT_OK;
@@ -303,7 +305,7 @@ int enqueueSlices(dmt_ctx* ctx, LaunchPlan const& L, RenderParams& P, uint32_t s
       P.samTabS0 = P.sampleOffset;
       uint32_t const entries = n * L.tab.pw * L.tab.ph;
       hipLaunchKernelGGL(k_sampler_table, dim3((entries + 255u) / 256u), dim3(256), 0, ctx->stream, P.sp, P.samTabS0, n, L.tab.pw, L.tab.ph,
-                         S.tab.vals.get(), S.tab.jit.get(), const_cast<float2*>(P.samTabLens));
+                         S.tab.vals.get(), S.tab.jit.get(), const_cast<float2*>(P.samTabLens), P.filtKnots, P.filtR);
       HIP_TRY(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(L.kernel, dim3(L.blocks), dim3(256), 0, ctx->stream, P);

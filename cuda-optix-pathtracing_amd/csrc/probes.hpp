@@ -23,7 +23,7 @@ __global__ void k_test_trace(RenderParams P, int n, int32_t const* pxs, int32_t 
   PathState st{};
   if (i < n) {
     ColdArgs const c = load_cold_args(k);
-    path_begin(st, c.cam, c.sp, pxs[i], pys[i], halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i]), kargs(k)->lensR, kargs(k)->lensD);
+    path_begin(st, c.cam, c.sp, pxs[i], pys[i], halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i]), load_camera_extra(k));
     if constexpr (F & kFeatMotion) motion_set_time(motion_sample_time(k, halton_pixel_base(c.sp, pxs[i], pys[i]), uint32_t(ss[i])));
     if constexpr (F & kFeatMedium) {  // medium_h: the lane's sample is sample 0 of "pixel" lane of slot 0, whose base is the sample's own index
       st.sidx = threadIdx.x & 63u;
@@ -84,7 +84,7 @@ DMT_DEV void test_trace_log_body(int px, int py, int smp, float* rec12, int cap,
   PathState st{};
   {
     ColdArgs const c = load_cold_args(k);
-    path_begin(st, c.cam, c.sp, px, py, halton_pixel_base(c.sp, px, py), uint32_t(smp), kargs(k)->lensR, kargs(k)->lensD);
+    path_begin(st, c.cam, c.sp, px, py, halton_pixel_base(c.sp, px, py), uint32_t(smp), load_camera_extra(k));
     if constexpr (MOTION) motion_set_time(motion_sample_time(k, halton_pixel_base(c.sp, px, py), uint32_t(smp)));
   }
   int n = 0;
@@ -201,7 +201,7 @@ __global__ void k_test_sampler(SamplerParams sp, int n, int32_t const* pxs, int3
 }
 
 // the rays the render kernels trace (lens rays for lensR > 0), or with lens2 the sample's lens values alone
-__global__ void k_test_camera(CameraXf cam, SamplerParams sp, float lensR, float lensD, int n, int32_t const* pxs,
+__global__ void k_test_camera(CameraXf cam, SamplerParams sp, CameraExtra extra, int n, int32_t const* pxs,
                               int32_t const* pys, int32_t const* ss, float* o3, float* d3, float* lens2) {
   int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= n) return;
@@ -211,9 +211,20 @@ __global__ void k_test_camera(CameraXf cam, SamplerParams sp, float lensR, float
     lens2[2 * i] = u.x, lens2[2 * i + 1] = u.y;
     return;
   }
-  Ray const r = camera_ray_any(cam, sp, pxs[i], pys[i], h, lensR, lensD);
+  Ray const r = camera_ray_any(cam, sp, pxs[i], pys[i], h, extra);
   o3[3 * i] = r.o.x, o3[3 * i + 1] = r.o.y, o3[3 * i + 2] = r.o.z;
   d3[3 * i] = r.d.x, d3[3 * i + 1] = r.d.y, d3[3 * i + 2] = r.d.z;
+}
+
+// the film positions the camera-ray code forms: the jitter, warped under a pixel filter (knots non-null), plus the pixel
+__global__ void k_test_film_positions(SamplerParams sp, FilterBin const* knots, float filtR, int n, int32_t const* pxs, int32_t const* pys,
+                                      int32_t const* ss, float* xy2) {
+  int const i = int(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * (sp.scale0 * sp.scale1);
+  f2 r = pixel2d(sp, h);
+  if (knots) r = f2{filter_warp(knots, filtR, r.x), filter_warp(knots, filtR, r.y)};
+  xy2[2 * i] = film_coord(r.x, pxs[i]), xy2[2 * i + 1] = film_coord(r.y, pys[i]);
 }
 
 // The BSDF probes' body: one lane per case of record `rec`, shading normal ns3[i], geometric normal ng3[i] (kOwnNg) or the
@@ -604,7 +615,7 @@ int dmt_test_sampler_table(dmt_ctx* ctx, int width, int height, uint32_t s0, uin
   ProbeOut<float2> dj(p, out_jitter, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
   hipLaunchKernelGGL(k_sampler_table, dim3(p.blocks(256)), dim3(256), 0, ctx->stream, sp, s0, n, pw, ph, dv.get(), dj.get(),
-                     static_cast<float2*>(nullptr));  // the lens-free table
+                     static_cast<float2*>(nullptr), ctx->filt.view(), ctx->filt.radius);  // the lens-free table; the jitter warped under a pixel filter
   return finishProbe(ctx, p);
 }
 
@@ -646,7 +657,7 @@ int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t*
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dO(p, o3, 3), dD(p, d3, 3);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, ctx->lensR, ctx->lensD, n, dpx.get(),
+  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, cameraExtraOf(ctx), n, dpx.get(),
                      dpy.get(), dss.get(), dO.get(), dD.get(), static_cast<float*>(nullptr));
   return finishProbe(ctx, p);
 }
@@ -659,8 +670,21 @@ int dmt_test_lens_values(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t*
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dL(p, lens2, 2);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, ctx->lensR, ctx->lensD, n, dpx.get(),
+  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, cameraExtraOf(ctx), n, dpx.get(),
                      dpy.get(), dss.get(), static_cast<float*>(nullptr), static_cast<float*>(nullptr), dL.get());
+  return finishProbe(ctx, p);
+}
+
+int dmt_test_film_positions(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* xy2) {
+  if (!ctx || n < 0 || !pxs || !pys || !ss || !xy2) return DMT_ERR_INVALID;
+  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_film_positions: set the camera first");
+  if (n == 0) return DMT_OK;
+  Probe p(ctx->device, size_t(n));
+  ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
+  ProbeOut<float> dXy(p, xy2, 2);
+  if (p.err != hipSuccess) return probeError(ctx, p);
+  hipLaunchKernelGGL(k_test_film_positions, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->sp, ctx->filt.view(), ctx->filt.radius, n,
+                     dpx.get(), dpy.get(), dss.get(), dXy.get());
   return finishProbe(ctx, p);
 }
 

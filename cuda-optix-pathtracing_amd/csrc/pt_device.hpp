@@ -554,9 +554,49 @@ DMT_DEV Ray camera_ray_lens(CameraXf const& cam, int px, int py, f2 r, float len
   ray.d = normalize(mk3(d[0], d[1], d[2]));
   return ray;
 }
-// what the render kernels trace: the lens ray for lensR > 0 (wave-uniform), else the pinhole ray
-DMT_DEV Ray camera_ray_any(CameraXf const& cam, SamplerParams const& sp, int px, int py, int32_t haltonIndex, float lensR, float focusD) {
-  if (lensR > 0.f) return camera_ray_lens(cam, px, py, pixel2d(sp, haltonIndex), lensR, focusD, lens_values(uint32_t(haltonIndex)));
+// ---- pixel filter (dmt_set_pixel_filter) ---------------------------------------------------------
+// Filter importance sampling: the sample's film jitter r = pixel2d becomes r' = 0.5 + radius * W(r) per axis, W the
+// inverse CDF of the filter's 1-D profile over [-1, 1], tabulated by the host as kFilterKnots float32 knots at u = i / 256
+// and interpolated linearly: W = fmaf(t, knot[i+1] - knot[i], knot[i]).  Every sample's weight is 1.
+// What the device and the host twin (dmt_pixel_filter_positions) read is the table of kFilterBins pairs
+// (knot[i], knot[i+1] - knot[i]), the difference formed once on the host by the same fp32 subtraction: one 8-byte load
+// per axis.  (Two 4-byte loads per axis from the knots themselves cost forty megakernel rows a VGPR)
+// One body for both: 256 u and its fraction are exact, then one explicit fmaf, one product and one sum.
+constexpr int kFilterKnots = 257, kFilterBins = 256;
+struct alignas(8) FilterBin {
+  float knot, step;  // W(i / 256) and fl32(W((i + 1) / 256) - W(i / 256))
+};
+__host__ __device__ inline float filter_warp(FilterBin const* bins, float radius, float u) {
+#pragma clang fp contract(off)
+  float const s = u * 256.0f;
+  int i = int(s);
+  // u = pixel2d's value is in [0, 1 - 2^-24], so 0 <= i <= 255 already; the upper clamp is free, a lower one is not (it
+  // cost forty megakernel rows a VGPR) and is left out
+  if (i > kFilterBins - 1) i = kFilterBins - 1;
+  FilterBin const b = bins[i];
+  float const w = __builtin_fmaf(s - float(i), b.step, b.knot);
+  return 0.5f + radius * w;
+}
+// a sample's film coordinate from its (warped) jitter, as camera_ray_jittered and camera_ray_lens form it
+__host__ __device__ inline float film_coord(float r, int p) {
+#pragma clang fp contract(off)
+  return ((r - 0.5f) + 0.5f) + float(p);
+}
+// the camera-side state beside the camera record: the thin lens and the pixel filter (knots null: box 0.5, no warp)
+struct CameraExtra {
+  float lensR, lensD;
+  FilterBin const* knots;
+  float filtR;
+};
+// what the render kernels trace: the lens ray for lensR > 0, the jitter warped under a pixel filter (both wave-uniform),
+// else the pinhole ray
+DMT_DEV Ray camera_ray_any(CameraXf const& cam, SamplerParams const& sp, int px, int py, int32_t haltonIndex, CameraExtra const& x) {
+  if (x.lensR > 0.f || x.knots) {
+    f2 r = pixel2d(sp, haltonIndex);
+    if (x.knots) r = f2{filter_warp(x.knots, x.filtR, r.x), filter_warp(x.knots, x.filtR, r.y)};
+    if (x.lensR > 0.f) return camera_ray_lens(cam, px, py, r, x.lensR, x.lensD, lens_values(uint32_t(haltonIndex)));
+    return camera_ray_jittered(cam, px, py, r);
+  }
   return camera_ray(cam, sp, px, py, haltonIndex);
 }
 

@@ -1,4 +1,5 @@
 // dmt_host_c.cpp -- flat C view of the host-side scene library (for ctypes / other FFIs).
+#include <cstdio>
 #include <cstring>
 #include <new>
 
@@ -142,6 +143,16 @@ const void* dmt_host_scene_infinite_lights(const dmt_host_scene* h) { return h->
 dmt_camera* dmt_host_scene_camera(dmt_host_scene* h) { return &h->s.camera; }
 void dmt_host_scene_lens(const dmt_host_scene* h, float* lens_radius, float* focus_distance) {
   *lens_radius = h->s.lensRadius, *focus_distance = h->s.focusDistance;
+}
+// the pixel filter the scene file records (not applied by an upload unless asked): 0 without one, 1 for a kind the library
+// offers (*kind = its DMT_FILTER_* value), 2 for an unsupported kind (mitchell, sinc); radius, sigma, and the file's name
+// for the kind (up to name_cap - 1 characters)
+int dmt_host_scene_pixel_filter(const dmt_host_scene* h, int* kind, float* radius, float* sigma, char* name, int name_cap) {
+  dmt_host::Scene const& s = h->s;
+  if (s.pixelFilterKind == dmt_host::Scene::kNoPixelFilter) return 0;
+  *kind = s.pixelFilterKind, *radius = s.pixelFilterRadius, *sigma = s.pixelFilterSigma;
+  if (name && name_cap > 0) std::snprintf(name, size_t(name_cap), "%s", s.pixelFilterName.c_str());
+  return s.pixelFilterKind == dmt_host::Scene::kUnsupportedPixelFilter ? 2 : 1;
 }
 // the scene's participating medium: 1 and the record (sigma_t, albedo3, g, min3, max3 -> out11), or 0 without one
 int dmt_host_scene_medium(const dmt_host_scene* h, float* out11) {

@@ -237,7 +237,26 @@ void parseCamera(Value const& cam, JsonScene& out, Vec3& dir, Vec3& pos) {
 }
 
 void parseFilm(Value const& film, JsonScene& out) {
-  if (!film.isObject() || film.size() > 3) fail("'film' should be an object with at most 3 members");
+  // beyond the reference's parser: an optional pixel filter, 'filter': {type, radius, sigma}, recorded in the scene and applied
+  // on request only (Scene::pixelFilterKind)
+  size_t const filterKeys = size_t(film.isObject() && film.contains("filter"));
+  if (!film.isObject() || film.size() > 3 + filterKeys) fail("'film' should be an object with at most 3 members and 'filter'");
+  if (filterKeys) {
+    Value const& f = film.at("filter");
+    if (!f.isObject()) fail("film 'filter' should be an object");
+    onlyKeys(f, {"type", "radius", "sigma"}, "film 'filter'");
+    if (!f.contains("type") || !f.at("type").isString()) fail("film 'filter' needs a string 'type'");
+    float radius = -1.f, sigma = -1.f;
+    if (f.contains("radius")) {
+      if (!f.at("radius").isNumber() || !(float(f.at("radius").number) > 0.f)) fail("film filter 'radius' should be a positive number");
+      radius = float(f.at("radius").number);
+    }
+    if (f.contains("sigma")) {
+      if (!f.at("sigma").isNumber() || !(float(f.at("sigma").number) > 0.f)) fail("film filter 'sigma' should be a positive number");
+      sigma = float(f.at("sigma").number);
+    }
+    if (!dmt_host::recordPixelFilter(out.scene, f.at("type").string, radius, sigma)) fail("film filter 'type' '" + f.at("type").string + "' is unknown");
+  }
   if (!film.contains("resolutionX") || !film.contains("resolutionY")) fail("'film' needs 'resolutionX' and 'resolutionY'");
   if (!film.at("resolutionX").isNumber() || !film.at("resolutionY").isNumber()) fail("film resolution should be numeric");
   if (film.contains("samples")) {

@@ -8,7 +8,9 @@
 //   AreaLightSource "diffuse" "rgb L" [, "float scale"]                   Shape "trianglemesh" "point3 P" "integer indices"
 //   LightSource "point" (I, from) | "spot" (I, from, to, coneangle, conedeltaangle) | "distant" (L, from, to) |
 //               "infinite" (constant L): packed into the reference's own Light records (CC/private/light.cu:271-307)
-//   Option / ColorSpace / Integrator / PixelFilter / Accelerator: accepted and ignored ("integer maxdepth" is read)
+//   Option / ColorSpace / Integrator / Accelerator: accepted and ignored ("integer maxdepth" is read)
+//   PixelFilter "box" | "triangle" | "gaussian" ("float radius", "float sigma"): recorded in the scene, applied on request only;
+//               "mitchell" | "sinc": recorded as an unsupported kind
 // Everything else is an error that names the directive.
 //
 // Mappings of this build: a pbrt "diffuse" material is Lambertian R/pi, which the reference's packed
@@ -254,7 +256,17 @@ bool loadPbrtScene(std::string const& path, PbrtScene& out, std::string* error) 
         stringArg("Integrator");
         Params const ps = params();
         if (Param const* p = find(ps, "integer", "maxdepth")) out.maxDepth = p->nums.empty() ? 5 : int(p->nums[0]);
-      } else if (d == "Option" || d == "ColorSpace" || d == "PixelFilter" || d == "Accelerator") {
+      } else if (d == "PixelFilter") {
+        // recorded in the scene, applied only where the caller asks (Scene::pixelFilterKind); pbrt-v4's names and defaults
+        std::string const type = stringArg("PixelFilter");
+        Params const ps = params();
+        float radius = -1.f, sigma = -1.f;
+        if (Param const* p = find(ps, "float", "radius")) radius = p->nums.empty() ? -1.f : float(p->nums[0]);
+        if (Param const* p = find(ps, "float", "sigma")) sigma = p->nums.empty() ? -1.f : float(p->nums[0]);
+        if ((find(ps, "float", "radius") && !(radius > 0.f)) || (find(ps, "float", "sigma") && !(sigma > 0.f)))
+          fail("PixelFilter: radius and sigma must be > 0");
+        if (!dmt_host::recordPixelFilter(out.scene, type, radius, sigma)) fail("PixelFilter \"" + type + "\": unknown filter");
+      } else if (d == "Option" || d == "ColorSpace" || d == "Accelerator") {
         if (d != "Option") stringArg(d.c_str());
         (void)params();
       } else if (d == "LookAt") {

@@ -500,4 +500,38 @@ int uploadScene(dmt_ctx* ctx, Scene const& s) {
   return dmt_upload_opacity(ctx, s.matOpacity.data(), uint32_t(s.matOpacity.size()), s.opacityCutoff);  // alpha cutouts: after the textures
 }
 
+bool recordPixelFilter(Scene& s, std::string const& type, float radius, float sigma) {
+  struct Known {
+    char const* name;
+    int kind;
+    float radius;  // pbrt-v4's default
+  };
+  static Known const known[] = {{"box", DMT_FILTER_BOX, 0.5f},
+                                {"triangle", DMT_FILTER_TENT, 2.f},
+                                {"tent", DMT_FILTER_TENT, 2.f},
+                                {"gaussian", DMT_FILTER_GAUSSIAN, 1.5f},
+                                {"blackman-harris", DMT_FILTER_BLACKMAN_HARRIS, 2.f},
+                                {"mitchell", Scene::kUnsupportedPixelFilter, 2.f},
+                                {"sinc", Scene::kUnsupportedPixelFilter, 4.f}};
+  for (Known const& k : known) {
+    if (type != k.name) continue;
+    s.pixelFilterKind = k.kind, s.pixelFilterName = type;
+    s.pixelFilterRadius = radius < 0.f ? k.radius : radius;
+    s.pixelFilterSigma = sigma < 0.f ? 0.5f : sigma;
+    return true;
+  }
+  return false;
+}
+
+int applyPixelFilter(dmt_ctx* ctx, Scene const& s, std::string& error) {
+  if (s.pixelFilterKind == Scene::kNoPixelFilter) return DMT_OK;
+  if (s.pixelFilterKind == Scene::kUnsupportedPixelFilter) {
+    error = "the scene's pixel filter '" + s.pixelFilterName + "' is an unsupported kind (signed filters need a per-sample weight)";
+    return DMT_ERR_INVALID;
+  }
+  int const rc = dmt_set_pixel_filter(ctx, s.pixelFilterKind, s.pixelFilterRadius, s.pixelFilterSigma);
+  if (rc) error = dmt_last_error(ctx);
+  return rc;
+}
+
 }  // namespace dmt_host

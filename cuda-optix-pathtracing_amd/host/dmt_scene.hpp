@@ -64,6 +64,14 @@ struct Scene {
   dmt_camera camera{};
   // optional thin lens (dmt_set_lens), reported beside the camera record: radius 0 = pinhole; both in scene units
   float lensRadius = 0.f, focusDistance = 1.f;
+  // optional pixel filter (dmt_set_pixel_filter; the PBRT front-end's PixelFilter, the JSON front-end's film.filter): recorded
+  // here and NOT applied by uploadScene -- only where the caller asks (applyPixelFilter; main.cpp --pixel-filter scene).
+  // Kind: kNoPixelFilter, a DMT_FILTER_* value, or kUnsupportedPixelFilter for a kind the library does not offer (signed
+  // filters: mitchell, sinc), whose name pixelFilterName keeps for the message.
+  static constexpr int kNoPixelFilter = -1, kUnsupportedPixelFilter = -2;
+  int pixelFilterKind = kNoPixelFilter;
+  float pixelFilterRadius = 0.5f, pixelFilterSigma = 0.5f;
+  std::string pixelFilterName;
   // optional env-map light (A18; the JSON front-end's "envlight"): RGB floats, envHeight x envWidth x 3
   std::vector<float> envRgb;
   int envWidth = 0, envHeight = 0;
@@ -186,5 +194,12 @@ bool writePngRgb8(std::string const& path, uint8_t const* rgb, uint32_t width, u
 // upload a Scene through the C ABI (triSoupFromTriangles + deviceBSDF + deviceLights +
 // deviceCamera + allocateDeviceConstantMemory in the reference, megakernel/main.cu:110-117)
 int uploadScene(dmt_ctx* ctx, Scene const& scene);
+
+// Records a scene file's pixel filter in `scene` (the PBRT names "box" | "triangle" | "gaussian"; "mitchell" | "sinc" as an
+// unsupported kind; radius / sigma < 0: pbrt-v4's default of the kind).  False for a name that is no filter at all.
+bool recordPixelFilter(Scene& scene, std::string const& type, float radius, float sigma);
+// The opt-in: hands the scene's recorded pixel filter to the context (a scene without one: DMT_OK, the context's filter stays).
+// DMT_ERR_INVALID and a message in `error` for a recorded kind the library does not offer.
+int applyPixelFilter(dmt_ctx* ctx, Scene const& scene, std::string& error);
 
 }  // namespace dmt_host

@@ -53,6 +53,10 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   bool aovSppSet = false;
   bool lensRadiusSet = false, focusDistanceSet = false, focusPixelSet = false;  // --lens-radius R, --focus-distance D, --focus-pixel X Y
   float lensRadius = 0.f, focusDistance = 1.f, focusX = 0.f, focusY = 0.f;
+  // --pixel-filter box|tent|gaussian|blackman-harris|scene, --filter-radius R, --filter-sigma S (dmt_set_pixel_filter)
+  std::string pixelFilter;
+  bool filterRadiusSet = false, filterSigmaSet = false;
+  float filterRadius = 0.f, filterSigma = 0.5f;
   bool shutterSet = false;    // --shutter OPEN CLOSE: the shutter interval of --motion-scene (dmt_set_shutter)
   float shutterOpen = 0.f, shutterClose = 1.f;
   std::string motionScenePath;  // --motion-scene <file>: the same scene at the end of the frame; its triangle positions become key 1
@@ -116,6 +120,13 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (focusDistanceSet && !(std::isfinite(focusDistance) && focusDistance > 0.f)) return "invalid --focus-distance: expected a finite distance > 0";
     if (focusDistanceSet && focusPixelSet) return "--focus-distance and --focus-pixel exclude each other";
     if (focusPixelSet && !(focusX >= 0.f && focusX < float(width) && focusY >= 0.f && focusY < float(height))) return "invalid --focus-pixel: outside the frame";
+    if (!pixelFilter.empty() && pixelFilter != "box" && pixelFilter != "tent" && pixelFilter != "gaussian" && pixelFilter != "blackman-harris" &&
+        pixelFilter != "scene")
+      return "invalid --pixel-filter: expected box, tent, gaussian, blackman-harris or scene, got '" + pixelFilter + "'";
+    if ((filterRadiusSet || filterSigmaSet) && (pixelFilter.empty() || pixelFilter == "scene")) return "--filter-radius and --filter-sigma need --pixel-filter with a kind";
+    if (filterRadiusSet && !(std::isfinite(filterRadius) && filterRadius > 0.f && filterRadius <= 8.f)) return "invalid --filter-radius: expected a radius in (0, 8] pixels";
+    if (filterSigmaSet && pixelFilter != "gaussian") return "--filter-sigma needs --pixel-filter gaussian";
+    if (filterSigmaSet && !(std::isfinite(filterSigma) && filterSigma > 0.f)) return "invalid --filter-sigma: expected a finite sigma > 0";
     if (shutterSet && !(std::isfinite(shutterOpen) && std::isfinite(shutterClose) && 0.f <= shutterOpen && shutterOpen <= shutterClose && shutterClose <= 1.f))
       return "invalid --shutter: expected 0 <= OPEN <= CLOSE <= 1";
     if (float c = 180.f; !parseShadingNormals(shadingNormals, c))
@@ -187,6 +198,11 @@ void printHelp() {
       "                       file's own lens applies unless given here)\n"
       "  --focus-distance <D> -- Depth along the viewing direction, in scene units, that the lens renders sharp\n"
       "  --focus-pixel <X> <Y> -- Autofocus: focus on what the centre of pixel (X, Y) shows, and print the distance chosen\n"
+      "  --pixel-filter <box|tent|gaussian|blackman-harris|scene> -- Pixel reconstruction filter, importance-sampled per sample\n"
+      "                       (every sample keeps weight 1).  Default: the box of radius 0.5, as the reference renders.  scene:\n"
+      "                       the filter the scene file records (PBRT PixelFilter, JSON film.filter), which is ignored otherwise\n"
+      "  --filter-radius <R> -- Its radius in pixels, in (0, 8] (defaults: box 0.5, tent 2, gaussian 1.5, blackman-harris 2)\n"
+      "  --filter-sigma <S> -- The Gaussian's sigma in pixels (default 0.5)\n"
       "  --motion-scene <file> -- Motion blur: a second scene file of the same kind as --scene whose triangle positions are\n"
       "                       where the triangles are at the end of the frame (same triangles, same order); every sample\n"
       "                       sees the scene at its own time in between\n"
@@ -242,6 +258,9 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--motion-scene" && more) c.motionScenePath = argv[++i];
     else if (a == "--shading-normals" && more) c.shadingNormals = argv[++i];
     else if (a == "--cutouts" && more) c.cutouts = argv[++i];
+    else if (a == "--pixel-filter" && more) c.pixelFilter = argv[++i];
+    else if (a == "--filter-radius" && more) c.filterRadius = std::strtof(argv[++i], nullptr), c.filterRadiusSet = true;
+    else if (a == "--filter-sigma" && more) c.filterSigma = std::strtof(argv[++i], nullptr), c.filterSigmaSet = true;
     else if (a == "--medium" && more) c.mediumSigmaT = std::strtof(argv[++i], nullptr), c.mediumSet = true;
     else if (a == "--medium-grid" && more) c.mediumGridPath = argv[++i];
     else if (a == "--medium-g" && more) c.mediumG = std::strtof(argv[++i], nullptr), c.mediumGSet = true;
@@ -405,6 +424,21 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "the scene's medium and --denoise exclude each other (the feature buffers do not know the fog)\n");
     return 1;
   }
+  // --pixel-filter: the scene file's filter applies only with "scene"; a kind given here replaces it; without the option none is set
+  if (cfg.pixelFilter.empty()) {
+    scene.pixelFilterKind = dmt_host::Scene::kNoPixelFilter;
+  } else if (cfg.pixelFilter == "scene") {
+    if (scene.pixelFilterKind == dmt_host::Scene::kNoPixelFilter) {
+      std::fprintf(stderr, "--pixel-filter scene: the scene records no pixel filter\n");
+      return 1;
+    }
+    if (scene.pixelFilterKind == dmt_host::Scene::kUnsupportedPixelFilter) {
+      std::fprintf(stderr, "--pixel-filter scene: the scene's pixel filter '%s' is an unsupported kind\n", scene.pixelFilterName.c_str());
+      return 1;
+    }
+  } else {
+    dmt_host::recordPixelFilter(scene, cfg.pixelFilter, cfg.filterRadiusSet ? cfg.filterRadius : -1.f, cfg.filterSigmaSet ? cfg.filterSigma : -1.f);
+  }
   if (cfg.cutouts == "off") scene.matOpacity.clear();  // --cutouts off: uploadScene then uploads no opacity
   std::vector<float> vertexNormals;  // --shading-normals: 9 floats per triangle for dmt_upload_vertex_normals
   if (cfg.shadingNormals == "file") {
@@ -431,6 +465,10 @@ int main(int argc, char** argv) {
     if (dmt_ctx_create(share ? cfg.device : cfg.device + r, &C.v[size_t(r)]) != DMT_OK) return fail(nullptr, "dmt_ctx_create");
     dmt_ctx* ctx = C.v[size_t(r)];
     if (dmt_host::uploadScene(ctx, scene) != DMT_OK) return fail(ctx, "uploadScene");
+    if (std::string err; dmt_host::applyPixelFilter(ctx, scene, err) != DMT_OK) {  // every rank sets it on its own context, as the lens
+      std::fprintf(stderr, "pixel filter: %s\n", err.c_str());
+      return 1;
+    }
     if (dmt_set_limits(ctx, cfg.maxDepth) != DMT_OK) return fail(ctx, "dmt_set_limits");
     if (cfg.bvhBuildSet && dmt_set_accel_build(ctx, cfg.bvhBuildArg == "gpu" ? DMT_BVH_BUILD_DEVICE : DMT_BVH_BUILD_HOST) != DMT_OK)
       return fail(ctx, "dmt_set_accel_build");

@@ -64,6 +64,14 @@ class HostScene:
         lr, fd = C.c_float(), C.c_float()
         L.dmt_host_scene_lens(h, C.byref(lr), C.byref(fd))
         self.lens = (lr.value, fd.value)  # thin lens beside the camera record: (radius, focus distance); radius 0 = pinhole
+        # the pixel filter the file records (PBRT PixelFilter, JSON film.filter): dict(type, kind, radius, sigma) or None; kind is
+        # the library's FILTER_* value, or None for a kind it does not offer (mitchell, sinc).  Applied only by
+        # upload_scene(scene, pixel_filter=True).
+        fk, fr, fs, fname = C.c_int(), C.c_float(), C.c_float(), C.create_string_buffer(32)
+        L.dmt_host_scene_pixel_filter.restype = C.c_int
+        have = L.dmt_host_scene_pixel_filter(h, C.byref(fk), C.byref(fr), C.byref(fs), fname, C.c_int(len(fname)))
+        self.pixel_filter = (dict(type=fname.value.decode(), kind=fk.value if have == 1 else None, radius=fr.value, sigma=fs.value)
+                             if have else None)
         m11 = np.zeros(11, np.float32)
         L.dmt_host_scene_medium.restype = C.c_int
         s6 = np.zeros(6, np.float32)
@@ -250,6 +258,7 @@ class ArrayScene:
         self.env_rgb = None if env_rgb is None else np.ascontiguousarray(env_rgb, np.float32)
         self.env_quat, self.env_scale = np.array([0, 0, 0, 1], np.float32), 1.0
         self.lens = None  # (lens_radius, focus_distance) to have upload_scene set the lens; None leaves the context's
+        self.pixel_filter = None  # dict(type, kind, radius, sigma) for upload_scene(pixel_filter=True); None leaves the context's
         self.tri_normals = None  # [n, 9] vertex normals for upload_scene(vertex_normals=True)
 
     tri_count = HostScene.tri_count

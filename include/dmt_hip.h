@@ -120,6 +120,49 @@ int dmt_lens_rays(const dmt_camera* cam, float lens_radius, float focus_distance
  * DMT_ERR_STATE when the ray leaves the scene.  Synchronous. */
 int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance);
 
+/* ---- pixel reconstruction filter, importance-sampled per sample (opt-in, beyond the reference) ---- */
+/* Context state beside the camera, like the lens: it survives dmt_set_camera and scene uploads.  The filter is separable,
+ * f(x, y) = f1(x) f1(y), with a radius in pixels.  Kinds: box; tent (triangle); Gaussian, pbrt-v4's max(0, G(x) - G(radius))
+ * with param = sigma; the four-term Blackman-Harris window.  param is ignored by the other kinds.
+ * DMT_ERR_INVALID, and the state untouched, for an unknown kind, a radius that is not finite, not > 0 or above 8, and for a
+ * Gaussian a sigma that is not finite or not > 0 (or so far above the radius that the profile has no mass in float64).
+ * The default, box with radius 0.5, is inactive: the same kernels run, nothing is allocated, and every film is
+ * byte-identical to one of a context that never saw this call.
+ *
+ * Filter importance sampling.  The filter moves where a sample's camera ray goes and nothing else: no splatting, every
+ * sample's weight is exactly 1, every pixel is still owned by one tile.  The sample's film jitter r = pixel2d in [0,1)^2
+ * becomes, per axis,   r' = 0.5 + radius * W(r),   and the film position is formed from r' as from r:
+ * ((r' - 0.5) + 0.5) + pixel.  Positions outside the film are ordinary rays.  W: [0,1) -> [-1,1] is the inverse CDF of f1
+ * over x / radius, tabulated on the host (f1 integrated in float64) as 257 float32 knots at u = i / 256 with W(0) = -1,
+ * W(1) = 1, antisymmetric about u = 1/2, and evaluated in fp32 without contraction as
+ *   i = floor(256 u);  t = 256 u - i;  W = fmaf(t, knot[i+1] - knot[i], knot[i])
+ * by the device and by dmt_pixel_filter_positions alike, from the same bytes: they agree bit for bit.
+ * THE RENDERED FILTER IS THE TABULATED ONE: 256 bins of equal mass with constant density inside each bin.  Its CDF equals
+ * the analytic CDF at every knot and deviates from it between knots (DESIGN.md 4.21 records by how much, about 1e-3).
+ * W is monotone, so the Halton stratification of a pixel's samples survives.  Sampler dimensions 2..9, the lens's 10 and 11
+ * and the shutter's 12 do not move.  Every render path traces the filtered positions (dmt_render, its sampler table, whose
+ * jitter plane then holds r', the wavefront form, dmt_render_adaptive, the motion rows), and so do the feature pass
+ * dmt_render_aovs and the trace probes.  What keeps the pixel centre or the pinhole reading, as under the lens:
+ * dmt_denoise_temporal's reprojection (a change of filter does not reset the history), dmt_camera_project,
+ * dmt_texture_footprint and the first-hit texture filter, dmt_focus_distance_at.  Signed filters (Mitchell, sinc) are
+ * not offered: they need a per-sample weight in the film's fold. */
+enum {
+  DMT_FILTER_BOX = 0,
+  DMT_FILTER_TENT = 1,
+  DMT_FILTER_GAUSSIAN = 2, /* param = sigma, in pixels */
+  DMT_FILTER_BLACKMAN_HARRIS = 3,
+};
+int dmt_set_pixel_filter(dmt_ctx* ctx, int kind, float radius, float param);
+/* any output may be null; *active = 0 for the default (box, radius 0.5) */
+int dmt_pixel_filter_info(dmt_ctx* ctx, int* kind, float* radius, float* param, int* active);
+/* host only (no GPU): the 257 knots W(i / 256) of a filter dmt_set_pixel_filter would accept (the box's are 2u - 1) */
+int dmt_pixel_filter_table(int kind, float radius, float param, float* knots257);
+/* host only (no GPU): the film positions (xy2: n x 2) of samples ss of pixels (pxs, pys) of a width x height frame under the
+ * filter; box with radius 0.5 gives the unfiltered positions.  The device's bit for bit (dmt_test_film_positions).
+ * DMT_ERR_INVALID for a pixel outside the frame, a negative sample, or filter arguments dmt_set_pixel_filter would refuse. */
+int dmt_pixel_filter_positions(int width, int height, int kind, float radius, float param, int n, const int32_t* pxs, const int32_t* pys,
+                               const int32_t* ss, float* xy2);
+
 /* ---- motion blur: linear vertex motion over a shutter interval (opt-in, beyond the reference) ---- */
 /* Keys.  Key 0 is the positions the context holds (dmt_upload_triangles, dmt_update_vertices*).  Key 1 is a second position
  * set for the same triangles (dmt_set_motion).  Motion is active exactly when key 1 is present; without it every film is
@@ -890,9 +933,14 @@ int dmt_test_sampler(dmt_ctx* ctx, int width, int height, int n, const int32_t* 
                      const int32_t* pys, const int32_t* ss, int ndims, int32_t* halton_index,
                      float* pixel2d, float* dims);
 /* fills the sampler table of samples [s0, s0 + n) of a width x height frame as a dmt_render call would and downloads
- * it: out_vals [n][ph][pw][8], out_jitter [n][ph][pw][2] with pw = min(width,128), ph = min(height,128) */
+ * it: out_vals [n][ph][pw][8], out_jitter [n][ph][pw][2] with pw = min(width,128), ph = min(height,128).  Under a pixel
+ * filter (dmt_set_pixel_filter) out_jitter is the warped jitter r', which is what the table then holds */
 int dmt_test_sampler_table(dmt_ctx* ctx, int width, int height, uint32_t s0, uint32_t n, float* out_vals, float* out_jitter);
-/* the camera rays the render kernels trace: lens rays when a lens is set (dmt_set_lens) */
+/* the film positions (xy2: n x 2) of the samples as the device forms them under the context's pixel filter: the device twin
+ * of dmt_pixel_filter_positions */
+int dmt_test_film_positions(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* xy2);
+/* the camera rays the render kernels trace: lens rays when a lens is set (dmt_set_lens), through the filtered film
+ * positions when a pixel filter is set (dmt_set_pixel_filter) */
 int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys,
                          const int32_t* ss, float* o3, float* d3);
 /* the lens values (u10, u11) of the samples, lens2 (n x 2), as the device computes them */
