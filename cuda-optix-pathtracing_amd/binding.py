@@ -65,7 +65,7 @@ def load_library():
 # every symbol include/dmt_hip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTED_SYMBOLS = [
     "dmt_ctx_create", "dmt_ctx_destroy", "dmt_last_error", "dmt_upload_triangles", "dmt_upload_bsdfs",
-    "dmt_upload_lights", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_light_tree_nodes", "dmt_test_light_tree", "dmt_set_emitter_sampling", "dmt_emitter_tree_info", "dmt_emitter_tree_nodes", "dmt_emitter_tree_select", "dmt_emitter_tree_pmfs", "dmt_test_emitter_tree", "dmt_kernel_scratch", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
+    "dmt_upload_lights", "dmt_uniform_lights_info", "dmt_set_camera", "dmt_set_limits", "dmt_set_accel", "dmt_set_light_sampling", "dmt_light_tree_pmfs", "dmt_light_tree_ref_select", "dmt_light_tree_nodes", "dmt_test_light_tree", "dmt_set_emitter_sampling", "dmt_emitter_tree_info", "dmt_emitter_tree_nodes", "dmt_emitter_tree_select", "dmt_emitter_tree_pmfs", "dmt_test_emitter_tree", "dmt_kernel_scratch", "dmt_set_bvh_strategy", "dmt_set_partition", "dmt_set_chunk", "dmt_render_profile",
     "dmt_upload_area_lights", "dmt_upload_textures", "dmt_upload_envmap", "dmt_clear_envmap", "dmt_envmap_tables", "dmt_test_envmap",
     "dmt_set_stream", "dmt_film_clear", "dmt_film_bind", "dmt_film_device_ptrs", "dmt_download_film",
     "dmt_render", "dmt_render_adaptive", "dmt_render_stats", "dmt_sync", "dmt_sched_diag", "dmt_kernel_time", "dmt_kernel_info", "dmt_bvh_validate", "dmt_brute_cull_plan", "dmt_brute_cull_box_plan", "dmt_brute_cull_box_records", "dmt_cull_records", "dmt_cull_box_test", "dmt_test_triangle_intersect",
@@ -829,6 +829,12 @@ class Renderer:
         self._check(self._lib.dmt_upload_lights(self._ctx, _p(l) if l.shape[0] else None, C.c_uint32(l.shape[0]),
                                                 _p(i) if i.shape[0] else None, C.c_uint32(i.shape[0])),
                     "dmt_upload_lights")
+
+    def uniform_lights_info(self):
+        """True when launches pass the scalar path's switch for one-record light lists (dmt_uniform_lights_info)."""
+        v = C.c_int()
+        self._check(self._lib.dmt_uniform_lights_info(self._ctx, C.byref(v)), "dmt_uniform_lights_info")
+        return bool(v.value)
 
     def set_camera(self, camera44):
         cam = np.ascontiguousarray(camera44, np.uint8).reshape(44)

@@ -180,6 +180,10 @@ struct RenderParams {
   // (dmt_set_pixel_filter; filtKnots null: box 0.5, no warp).  After `emitterTrails`, so that no other field moves
   float lensRad, filtR;
   FilterBin const* filtKnots;
+  // one-record light lists through the scalar path (LightState::uniformPath; DMT_UNIFORM_LIGHTS=0 at context creation clears
+  // it): non-zero lets path_shade read lights[0] / infLights[0] by s_load where the pick runs over one record.  After
+  // `filtKnots`, so that no other field moves
+  uint32_t uniformLights;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -373,6 +377,24 @@ DMT_DEV Hit shade_hit(KArgs k, SceneView const& sc, int tri, float bu, float bv,
 
 #include "medium_device.hpp"
 
+// One-record light lists through the scalar path (RenderParams::uniformLights): the rows of path_shade that carry the two
+// scalar arms.  Every row whose pick is the uniform one does, but for the nine masks under which a kernel gains scratch from the
+// arms and the plain BVH row, which measured slower with them ("Shading: scalar light records"; profiles/shade_loads/kernel_resources_*.txt); those keep the parent's
+// code, and run the lane's pick for every list.  The tree rows pick by their trees and are left alone in the hit arm.
+// The list is read off one compiler's register allocation and nothing re-derives it by itself: after a change to path_shade
+// or a new compiler, return true here, run `make asm` on that and on the commit before, and diff the two tables of
+// tools/kernel_resources.py over EVERY line -- the megakernel rows and the `void k_test_trace<F>` probes, which instantiate
+// the same masks, alike (first column: everything before the last seven fields).  A mask any of whose kernels gains scratch
+// bytes or loses a wave goes on the list; then build again and diff again, since the masks taken out return to the parent's
+// figures.
+constexpr bool uniform_lights_row(uint32_t F) {
+  uint32_t const row = F & ~kFeatStats;
+  return row != (kFeatBvh | kFeatEnv) && row != (kFeatBvh | kFeatEnv | kFeatMedium) && row != (kFeatBvh | kFeatEnv | kFeatTex) &&
+         row != (kFeatBvh | kFeatEnv | kFeatTex | kFeatVtxNormals) && row != (kFeatBvh | kFeatTex) && row != (kFeatEnv | kFeatArea) &&
+         row != (kFeatEnv | kFeatMotion) && row != (kFeatBvh | kFeatBlend) && row != (kFeatEnv | kFeatTex | kFeatTexFilter) &&
+         row != kFeatBvh;  // (no scratch, one more VGPR: measured 0.3 % slower on 1 M triangles with the arms, six runs each)
+}
+
 template <uint32_t F>
 DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv) {
   static_assert(!((F & kFeatLightTree) && (F & kFeatLightTreeRef)), "one light tree at a time");
@@ -388,6 +410,7 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   static_assert(!(F & kFeatMedium) || mediumRowOk, "medium: the plain and env-map rows only");
   static_assert(!(F & kFeatMediumGrid) || mediumRowOk, "medium grid: with the medium, on the plain and env-map rows only");
   static_assert(!(F & kFeatMediumSpectrum) || mediumRowOk, "medium spectrum: with the medium, on the plain and env-map rows only");
+  constexpr bool kUniformRow = uniform_lights_row(F);
   SceneView const sc = load_scene(k);
   int const maxDepth = kargs(k)->maxDepth;
   if constexpr (F & kFeatMedium) {  // a collision inside the box replaces the surface hit or the miss
@@ -408,10 +431,24 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
   }
   if (bestTri < 0) {  // miss: constant environment, no MIS (megakernel.cu:135-151)
     if (sc.infLightCount > 0) {
-      uint32_t const li = pick_index(st.rng.get1D(), sc.infLightCount);
-      Rec32 const light = sc.infLights[li];
-      float const pmf = 1.f / float(sc.infLightCount);
-      if (light_type(light) == LT_ENV) st.L = st.L + st.beta * light_intensity(light) / pmf;
+      if constexpr (kUniformRow) {
+        // one infinite light: pick_index(u, 1) is 0 for every u, so the record is wave-uniform and comes by s_load; its type
+        // test is a scalar branch and the arm has no vector load.  The draw stays: the dimension counter advances as before
+        float const uInf = st.rng.get1D();
+        float const pmf = 1.f / float(sc.infLightCount);
+        if (sc.infLightCount == 1u && kargs(k)->uniformLights) {
+          Rec32 const light = load_rec0_uniform(sc.infLights);
+          if (light_type(light) == LT_ENV) st.L = st.L + st.beta * light_intensity(light) / pmf;
+        } else {
+          Rec32 const light = sc.infLights[pick_index(uInf, sc.infLightCount)];
+          if (light_type(light) == LT_ENV) st.L = st.L + st.beta * light_intensity(light) / pmf;
+        }
+      } else {
+        uint32_t const li = pick_index(st.rng.get1D(), sc.infLightCount);
+        Rec32 const light = sc.infLights[li];
+        float const pmf = 1.f / float(sc.infLightCount);
+        if (light_type(light) == LT_ENV) st.L = st.L + st.beta * light_intensity(light) / pmf;
+      }
     }
     sect_mark(4);
     return true;
@@ -647,14 +684,32 @@ DMT_DEV bool path_shade(KArgs k, PathState& st, int bestTri, float bu, float bv)
       li = pick_index(uLight, (F & kFeatArea) ? nAll : sc.lightCount);
       pmf = ((F & kFeatEnv) ? 0.5f : 1.f) / float((F & kFeatArea) ? nAll : sc.lightCount);
     }
-    Rec32 const light = sc.lights[li];
-    LightSample const ls = sample_light(light, hit.pos, uLight2, st.lastT, hit.normal);
+    // The uniform pick over ONE record returns 0 for every draw, so the record is wave-uniform: it comes by s_load, and the
+    // type switches and the decoding of sample_light and eval_light run on scalar registers, each in a copy of its own so
+    // that no word of the record merges with a lane's.  Only the sample meets the lane's path again.  Any other count, and
+    // the tree rows, run the lane's pick
+    constexpr bool kUniformArm = kUniformRow && !(F & (kFeatLightTree | kFeatEmitterTree | kFeatLightTreeRef));
+    [[maybe_unused]] bool uniformRec = false;
+    [[maybe_unused]] Rec32 light{};
+    LightSample ls;
+    if constexpr (kUniformArm) {
+      uniformRec = ((F & kFeatArea) ? nAll : sc.lightCount) == 1u && kargs(k)->uniformLights;
+      if (uniformRec) ls = sample_light(load_rec0_uniform(sc.lights), hit.pos, uLight2, st.lastT, hit.normal);
+      else ls = sample_light(sc.lights[li], hit.pos, uLight2, st.lastT, hit.normal);
+    } else {
+      light = sc.lights[li];
+      ls = sample_light(light, hit.pos, uLight2, st.lastT, hit.normal);
+    }
     sect_mark(6);
     if (picked && ls.valid()) {
       float bsdfPdf = 0.f;
       f3 const f = eval_material(ls.direction, bsdfPdf);
       if (!is_zero(f)) {
-        f3 const Le = eval_light(light, ls);
+        f3 Le;
+        if constexpr (kUniformArm)  // (the record again, where it is used: its words are not held across the material's evaluation)
+          Le = uniformRec ? eval_light(load_rec0_uniform(sc.lights), ls) : eval_light(sc.lights[li], ls);
+        else
+          Le = eval_light(light, ls);
         if (ls.delta) {
           put_C(st.beta * Le * f / pmf);
         } else {  // power heuristic, no division by the light pdf (:233-238)
@@ -2322,6 +2377,7 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
     ctx->bruteCull = v == 0 ? 0 : v == 1 ? 1 : 2;
   }
   if (char const* e7 = std::getenv("DMT_TRI_KIND_INLINE")) ctx->surf.kind.allowInline = std::atoi(e7) != 0;  // tests (SurfaceState::Kind)
+  if (char const* e8 = std::getenv("DMT_UNIFORM_LIGHTS")) ctx->lights.uniformPath = std::atoi(e8) != 0;  // A/B runs and tests (LightState)
   *out = ctx.release();
   return DMT_OK;
 }

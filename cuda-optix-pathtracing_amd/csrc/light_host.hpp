@@ -198,6 +198,14 @@ int dmt_set_light_sampling(dmt_ctx* ctx, int mode) {
   return DMT_OK;
 }
 
+int dmt_uniform_lights_info(dmt_ctx* ctx, int* enabled) {
+  if (!ctx || !enabled) return DMT_ERR_INVALID;
+  RenderParams P{};
+  ctx->lights.fill(P, true);  // what a launch passes: the switch as it reaches the kernels
+  *enabled = P.uniformLights != 0u;
+  return DMT_OK;
+}
+
 int dmt_set_emitter_sampling(dmt_ctx* ctx, int mode) {
   if (!ctx) return DMT_ERR_INVALID;
   if (mode != DMT_EMITTERS_UNIFORM && mode != DMT_EMITTERS_TREE) return fail(ctx, DMT_ERR_INVALID, "dmt_set_emitter_sampling: unknown mode");

@@ -22,6 +22,9 @@
 //            dmt_set_emitter_sampling dmt_set_emitter_sampling         depth, valid and tooDeep are derived (below) and go
 //                                                                      with an invalidation
 //
+//   uniformPath  DMT_UNIFORM_LIGHTS at    --                              everything: set once, when the context is created
+//            context creation (0 clears it)
+//
 // Derived lazily: the tree's nodes, by the first launch or dmt_test_light_tree that wants them (resolveFeatures ->
 // ensureLightTree), from the host copy of the list, for the mode the context has then.  Two things invalidate the tree
 // (invalidateTree): dmt_upload_lights, and a dmt_set_light_sampling that CHANGES the mode -- through DMT_LIGHTS_UNIFORM too,
@@ -114,6 +117,10 @@ struct LightState {
     EnvView view{};     // w == 0: no env map
   } env;
 
+  // one-record lists through the scalar path (RenderParams::uniformLights).  DMT_UNIFORM_LIGHTS=0 at context creation clears
+  // it: every pick then loads the lane's record, as lists of other sizes always do (A/B runs, tests)
+  bool uniformPath = true;
+
   // which light pick a launch runs, and if the uniform one although a tree is asked for, the first reason why
   enum class Pick { Tree, NoList, UniformMode, OneLight, TooDeep, NotTreeable };
   Pick why(bool plainSurfaces) const {
@@ -143,6 +150,7 @@ struct LightState {
   void fill(RenderParams& P, bool plainSurfaces) const {
     P.scene.lights = list.recs.get(), P.scene.infLights = list.inf.get(), P.scene.lightCount = list.count, P.scene.infLightCount = list.infCount;
     P.env = env.view;
+    P.uniformLights = uniformPath ? 1u : 0u;
     uint32_t const F = tree.valid ? features(plainSurfaces) : 0u;
     if (F & kFeatLightTree) P.lightTree = tree.nodes.get();
     if (F & kFeatLightTreeRef) P.lightTreeRef = tree.refNodes.get();

@@ -194,6 +194,18 @@ __host__ __device__ inline T const DMT_CONST_AS* to_const_as(T const* p) {
 #pragma clang diagnostic pop
 }
 
+// Record 0 of a light list through the scalar path: the list's address is wave-uniform (a kernel argument), so the eight
+// words arrive by one s_load_dwordx8 and the callers' decoding and type switches run on scalar registers.  For lists of
+// ONE record, where pick_index(u, 1) == 0 for every u (path_shade; tests/test_uniform_lights.py).  The lists are device
+// allocations, hence 32-byte aligned, and are never written by a kernel.
+typedef uint32_t RecWords __attribute__((ext_vector_type(8)));
+DMT_DEV Rec32 load_rec0_uniform(Rec32 const* list) {
+  RecWords const w = *reinterpret_cast<RecWords const DMT_CONST_AS*>(to_const_as(list));
+  Rec32 r;
+  for (int i = 0; i < 8; ++i) r.w[i] = w[i];
+  return r;
+}
+
 struct SceneView {
   TriIsect const* __restrict__ tris;
   TriPost const* __restrict__ post;

@@ -82,8 +82,14 @@ const char* dmt_last_error(const dmt_ctx* ctx);
 int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs,
                          const uint32_t* mat_id, size_t count);
 int dmt_upload_bsdfs(dmt_ctx* ctx, const void* bsdf32, uint32_t count);
+/* A list of ONE record (either list) is read by the kernels through the scalar path: the uniform pick over one record is
+ * record 0 for every draw, so the record is wave-uniform.  Films do not depend on it; DMT_UNIFORM_LIGHTS=0 in the environment
+ * at context creation makes every list use the lane's pick and vector loads (A/B runs, tests). */
 int dmt_upload_lights(dmt_ctx* ctx, const void* lights32, uint32_t count, const void* infinite32,
                       uint32_t infinite_count);
+/* enabled = 1 when launches of this context pass the scalar path's switch to the kernels (RenderParams::uniformLights), 0 under
+ * DMT_UNIFORM_LIGHTS=0.  Which lists take the path is the kernels' matter (one record; path_shade). */
+int dmt_uniform_lights_info(dmt_ctx* ctx, int* enabled);
 /* (re)computes camera transforms and sampler parameters; (re)allocates and zeroes the film when
  * the resolution changes */
 int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam);
