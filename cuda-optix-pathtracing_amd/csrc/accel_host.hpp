@@ -1,14 +1,17 @@
 // accel_host.hpp -- the host side of the acceleration layer (accel_state.hpp): building, adopting, updating and dropping the
-// two trees, key 1 of the motion, the cull tables of the brute-force pass, and the dmt_* entry points of all of these.
+// two trees, key 1 of the motion, the cull tables of the brute-force pass, and the dmt_* entry points of all of these, the
+// host-only ones that show a cull plan (cull_plan.hpp) among them.
 //
-// Part of dmt_hip.hip's translation unit, included once: after the host helpers it uses (dmt_ctx, HIP_TRY, fail, packSoup,
-// planBruteCull, planBruteCullBox, computeSamplerParams) and before baseParams, denoise_host.hpp and probes.hpp, which call
-// into it (bvhView, cullView, shadeThresholdFor, reserveOverflow, requireTree, motionParams).  The two calls the other way,
-// the vertex updates into denoise_host.hpp's mirror, are the two forward declarations below.
+// Part of dmt_hip.hip's translation unit, included once: after the host helpers it uses (dmt_ctx, HIP_TRY, fail, cull_plan.hpp's
+// planners, camera_host.hpp's computeSamplerParams, resolutionOk and haltonIndices) and before scene_host.hpp, baseParams,
+// denoise_host.hpp and probes.hpp, which call into it (soupArgsOk, uploadCullTables, dropMotion, buildBvh, bvhView, cullView,
+// shadeThresholdFor, reserveOverflow, requireTree, motionParams).  The three calls the other way, packSoup of scene_host.hpp and
+// the vertex updates into denoise_host.hpp's mirror, are the forward declarations below.
 #pragma once
 
 namespace {
 
+void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count, std::vector<TriIsect>& a, std::vector<TriPost>& b);  // scene_host.hpp
 int mirrorHostUpdate(dmt_ctx* ctx);                                         // denoise_host.hpp
 int mirrorDeviceUpdate(dmt_ctx* ctx, void const* d_verts9, size_t count);  // denoise_host.hpp
 
@@ -19,14 +22,14 @@ BvhView bvhView(dmt_ctx const* c, size_t threads) {
   return b;
 }
 
-// the brute-force pass's tables; without clusters the pass tests d_tris for every ray
+// the brute-force pass's tables; without clusters the pass tests the soup's records for every ray
 CullView cullView(dmt_ctx const* c) {
   CullView v{};
-  if (c->cull.clusterCount > 0) {
-    v.always = c->cull.always.get(), v.alwaysIdx = c->cull.idx.get(), v.clusters = c->cull.clusters.get();
-    v.tri9 = c->cull.tri9.get(), v.alwaysCount = c->cull.alwaysCount, v.clusterCount = c->cull.clusterCount;
+  if (c->ac.cull.clusterCount > 0) {
+    v.always = c->ac.cull.always.get(), v.alwaysIdx = c->ac.cull.idx.get(), v.clusters = c->ac.cull.clusters.get();
+    v.tri9 = c->ac.cull.tri9.get(), v.alwaysCount = c->ac.cull.alwaysCount, v.clusterCount = c->ac.cull.clusterCount;
   } else {
-    v.always = c->d_tris.get(), v.alwaysCount = c->triCount;
+    v.always = c->scene.tris.get(), v.alwaysCount = c->scene.triCount;
   }
   return v;
 }
@@ -73,7 +76,7 @@ void adopt(dmt_ctx* ctx, BvhTree&& t, int builder, size_t tempBytes) {
   dmt_accel_build_record& R = A.buildRecord;
   R = dmt_accel_build_record{};
   R.builder = builder;
-  R.triangles = ctx->triCount, R.nodes = A.tree.nodeCount, R.pairs = A.tree.pairCount, R.depth = A.tree.depth;
+  R.triangles = ctx->scene.triCount, R.nodes = A.tree.nodeCount, R.pairs = A.tree.pairCount, R.depth = A.tree.depth;
   R.build_ms = A.tree.buildMs, R.temp_bytes = tempBytes;
 }
 
@@ -137,8 +140,8 @@ int uploadHostTree(dmt_ctx* ctx, bvh_build::Result const& r, float const* const 
 // (re)build the 4-wide BVH of the uploaded soup on the host and upload nodes + triangle pairs
 int buildBvhHost(dmt_ctx* ctx, int builder) {
   auto const t0 = std::chrono::steady_clock::now();
-  bvh_build::Result r = bvh_build::build(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->triCount);
-  float const* const key0[3] = {ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data()};
+  bvh_build::Result r = bvh_build::build(ctx->scene.h_xs.data(), ctx->scene.h_ys.data(), ctx->scene.h_zs.data(), ctx->scene.triCount);
+  float const* const key0[3] = {ctx->scene.h_xs.data(), ctx->scene.h_ys.data(), ctx->scene.h_zs.data()};
   BvhTree t;
   if (int const rc = uploadHostTree(ctx, r, key0, nullptr, "BVH: too many nodes / triangle pairs", t)) return rc;
   t.levels = refit::levelBounds(r.nodes.data(), r.nodes.size());
@@ -154,8 +157,8 @@ int buildBvh(dmt_ctx* ctx) {
   static_assert(sizeof(TriPost) == 64 && offsetof(TriPost, p2z) == 32, "the device builder reads p0, p1, p2 as nine consecutive floats");
   lbvh_gpu::Result r;
   std::string what;
-  hipError_t const e = lbvh_gpu::build(reinterpret_cast<float const*>(ctx->d_post.get()), uint32_t(sizeof(TriPost) / sizeof(float)),
-                                       ctx->triCount, kBvhMaxDepth, ctx->stream, A.lbvhScratch, r, what);
+  hipError_t const e = lbvh_gpu::build(reinterpret_cast<float const*>(ctx->scene.post.get()), uint32_t(sizeof(TriPost) / sizeof(float)),
+                                       ctx->scene.triCount, kBvhMaxDepth, ctx->stream, A.lbvhScratch, r, what);
   if (e != hipSuccess) {  // an error, not a silent host build
     ctx->err = "device BVH build: " + what + ": " + hipGetErrorName(e) + " - " + hipGetErrorString(e);
     return DMT_ERR_HIP;
@@ -188,9 +191,9 @@ int ensureMotionTree(dmt_ctx* ctx) {
   AccelState& A = ctx->ac;
   if (A.motionTree.valid) return DMT_OK;
   auto const t0 = std::chrono::steady_clock::now();
-  float const* const key0[3] = {ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data()};
+  float const* const key0[3] = {ctx->scene.h_xs.data(), ctx->scene.h_ys.data(), ctx->scene.h_zs.data()};
   float const* const key1[3] = {A.h_xs1.data(), A.h_ys1.data(), A.h_zs1.data()};
-  bvh_build::Result r = bvh_build::build(key0[0], key0[1], key0[2], ctx->triCount, key1[0], key1[1], key1[2]);
+  bvh_build::Result r = bvh_build::build(key0[0], key0[1], key0[2], ctx->scene.triCount, key1[0], key1[1], key1[2]);
   BvhTree t;
   if (int const rc = uploadHostTree(ctx, r, key0, key1, "motion BVH: too many nodes / triangle pairs", t)) return rc;
   t.buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -214,22 +217,13 @@ int motionParams(dmt_ctx* ctx, uint32_t F, RenderParams& P) {
 }
 
 // ---- the brute-force pass's cluster tables ----
-// the culled clusters of the brute-force pass for a soup, by the context's DMT_BRUTE_CULL setting
-std::vector<CullCluster> planCullClusters(int level, float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
-  // a closest-hit key holds the original index in 26 bits: no culling for larger soups
-  std::vector<CullCluster> clusters = planBruteCull(xs, ys, zs, mat, uint32_t(count), level >= 1 && count < kCullMaxIndex, nullptr);
-  if (level >= 2 && count < kCullMaxIndex) {
-    std::vector<CullCluster> const boxes = planBruteCullBox(xs, ys, zs, mat, uint32_t(count), clusters);
-    clusters.insert(clusters.end(), boxes.begin(), boxes.end());
-  }
-  return clusters;
-}
-std::vector<CullCluster> planCullClusters(dmt_ctx const* ctx, float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
-  return planCullClusters(ctx->bruteCull, xs, ys, zs, mat, count);
+// what every call that takes a soup with its material ids checks first
+bool soupArgsOk(float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count) {
+  return !((count && (!xs || !ys || !zs || !mat)) || count > 0x7FFFFFFFu);
 }
 
 // device tables of a cluster plan; a = the soup's TriIsect records (read only when there are clusters).  The caller adopts
-// them when everything else of its call has succeeded: ctx->cull = std::move(T)
+// them when everything else of its call has succeeded: ctx->ac.cull = std::move(T)
 int uploadCullTables(dmt_ctx* ctx, std::vector<CullCluster> const& clusters, TriIsect const* a, size_t count, CullTables& T) {
   T.alwaysCount = uint32_t(count), T.clusterCount = uint32_t(clusters.size());
   if (clusters.empty()) return DMT_OK;
@@ -285,7 +279,7 @@ int finishUpdate(dmt_ctx* ctx, EventPair& T) {
     }
     static_assert(sizeof(TriPost) == 64 && offsetof(TriPost, p2z) == 32, "the refit reads p0, p1, p2 as nine consecutive floats");
     std::string what;
-    hipError_t const e = lbvh_gpu::refit(reinterpret_cast<float const*>(ctx->d_post.get()), uint32_t(sizeof(TriPost) / sizeof(float)), ctx->triCount,
+    hipError_t const e = lbvh_gpu::refit(reinterpret_cast<float const*>(ctx->scene.post.get()), uint32_t(sizeof(TriPost) / sizeof(float)), ctx->scene.triCount,
                                          A.tree.nodes.get(), A.tree.pairs.get(), A.tree.nodeCount, A.tree.pairCount, A.tree.levels, ctx->stream,
                                          A.refitScratch, what);
     if (e != hipSuccess) {
@@ -321,8 +315,8 @@ int finishUpdate(dmt_ctx* ctx, EventPair& T) {
 int beginUpdate(dmt_ctx* ctx, char const* name, bool nullArray, size_t count, EventPair& T, bool* done) {
   *done = false;
   if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "update of vertices before any dmt_upload_triangles");
-  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "update of vertices: count differs from the uploaded triangle count");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "update of vertices before any dmt_upload_triangles");
+  if (count != ctx->scene.triCount) return fail(ctx, DMT_ERR_INVALID, "update of vertices: count differs from the uploaded triangle count");
   if (count && nullArray) {
     ctx->err = std::string(name) + ": null array";
     return DMT_ERR_INVALID;
@@ -354,13 +348,13 @@ int dmt_update_vertices(dmt_ctx* ctx, const float* xs, const float* ys, const fl
   ctx->lights.invalidateEmitters();  // and the emitter tree was built over them
   std::vector<TriIsect> a;
   std::vector<TriPost> b;
-  packSoup(xs, ys, zs, ctx->h_mat.data(), count, a, b);
+  packSoup(xs, ys, zs, ctx->scene.h_mat.data(), count, a, b);
   CullTables cull;
-  if (int const rcC = uploadCullTables(ctx, planCullClusters(ctx, xs, ys, zs, ctx->h_mat.data(), count), a.data(), count, cull)) return rcC;
-  HIP_TRY(ctx, hipMemcpy(ctx->d_tris.get(), a.data(), count * sizeof(TriIsect), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_post.get(), b.data(), count * sizeof(TriPost), hipMemcpyHostToDevice));
-  ctx->cull = std::move(cull);
-  ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
+  if (int const rcC = uploadCullTables(ctx, planCullClusters(ctx->ac.bruteCull, CullSoup{xs, ys, zs, ctx->scene.h_mat.data(), uint32_t(count)}), a.data(), count, cull)) return rcC;
+  HIP_TRY(ctx, hipMemcpy(ctx->scene.tris.get(), a.data(), count * sizeof(TriIsect), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->scene.post.get(), b.data(), count * sizeof(TriPost), hipMemcpyHostToDevice));
+  ctx->ac.cull = std::move(cull);
+  ctx->scene.h_xs.assign(xs, xs + 4 * count), ctx->scene.h_ys.assign(ys, ys + 4 * count), ctx->scene.h_zs.assign(zs, zs + 4 * count);
   if (int const rcT = mirrorHostUpdate(ctx)) return rcT;
   return finishUpdate(ctx, T);
 }
@@ -372,27 +366,27 @@ int dmt_update_vertices_device(dmt_ctx* ctx, const void* d_verts9, size_t count)
   if (done) return DMT_OK;
   dropMotion(ctx);  // key 1 was a motion from the positions being replaced
   ctx->lights.invalidateEmitters();  // and the emitter tree was built over them
-  HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->d_tris.get(), ctx->d_post.get(), ctx->stream));
+  HIP_TRY(ctx, lbvh_gpu::packRecords(static_cast<float const*>(d_verts9), uint32_t(count), ctx->scene.tris.get(), ctx->scene.post.get(), ctx->stream));
   if (int const rcT = mirrorDeviceUpdate(ctx, d_verts9, count)) return rcT;
   // the host mirrors (the host builder's, the cull plan's and a later rebuild's input) from the records just made
   std::vector<TriPost> b(count);
-  HIP_TRY(ctx, hipMemcpyAsync(b.data(), ctx->d_post.get(), count * sizeof(TriPost), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(b.data(), ctx->scene.post.get(), count * sizeof(TriPost), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < count; ++i) {
     TriPost const& q = b[i];
-    ctx->h_xs[4 * i] = q.p0x, ctx->h_xs[4 * i + 1] = q.p1x, ctx->h_xs[4 * i + 2] = q.p2x;
-    ctx->h_ys[4 * i] = q.p0y, ctx->h_ys[4 * i + 1] = q.p1y, ctx->h_ys[4 * i + 2] = q.p2y;
-    ctx->h_zs[4 * i] = q.p0z, ctx->h_zs[4 * i + 1] = q.p1z, ctx->h_zs[4 * i + 2] = q.p2z;
+    ctx->scene.h_xs[4 * i] = q.p0x, ctx->scene.h_xs[4 * i + 1] = q.p1x, ctx->scene.h_xs[4 * i + 2] = q.p2x;
+    ctx->scene.h_ys[4 * i] = q.p0y, ctx->scene.h_ys[4 * i + 1] = q.p1y, ctx->scene.h_ys[4 * i + 2] = q.p2y;
+    ctx->scene.h_zs[4 * i] = q.p0z, ctx->scene.h_zs[4 * i + 1] = q.p1z, ctx->scene.h_zs[4 * i + 2] = q.p2z;
   }
-  std::vector<CullCluster> const clusters = planCullClusters(ctx, ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->h_mat.data(), count);
+  std::vector<CullCluster> const clusters = planCullClusters(ctx->ac.bruteCull, CullSoup{ctx->scene.h_xs.data(), ctx->scene.h_ys.data(), ctx->scene.h_zs.data(), ctx->scene.h_mat.data(), uint32_t(count)});
   std::vector<TriIsect> a;
   if (!clusters.empty()) {  // the cluster tables copy TriIsect records: the kernel's own
     a.resize(count);
-    HIP_TRY(ctx, hipMemcpy(a.data(), ctx->d_tris.get(), count * sizeof(TriIsect), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(a.data(), ctx->scene.tris.get(), count * sizeof(TriIsect), hipMemcpyDeviceToHost));
   }
   CullTables cull;
   if (int const rcC = uploadCullTables(ctx, clusters, a.data(), count, cull)) return rcC;
-  ctx->cull = std::move(cull);
+  ctx->ac.cull = std::move(cull);
   return finishUpdate(ctx, T);
 }
 
@@ -417,7 +411,7 @@ int dmt_set_accel(dmt_ctx* ctx, int mode) {
   if (!ctx) return DMT_ERR_INVALID;
   if (mode != DMT_ACCEL_BRUTE_FORCE && mode != DMT_ACCEL_BVH) return fail(ctx, DMT_ERR_INVALID, "dmt_set_accel: unknown mode");
   ctx->accel = mode;
-  if (mode == DMT_ACCEL_BVH && ctx->haveTris && !ctx->ac.tree.valid) {
+  if (mode == DMT_ACCEL_BVH && ctx->scene.haveTris && !ctx->ac.tree.valid) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int const rc = buildBvh(ctx)) return rc;
   }
@@ -434,7 +428,7 @@ int dmt_set_accel_build(dmt_ctx* ctx, int mode) {
   if (mode == ctx->ac.accelBuild) return DMT_OK;
   ctx->ac.accelBuild = mode;
   ctx->ac.tree.drop();  // the current tree is the other builder's
-  if (ctx->accel == DMT_ACCEL_BVH && ctx->haveTris) {
+  if (ctx->accel == DMT_ACCEL_BVH && ctx->scene.haveTris) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight still read the old tree
     return buildBvh(ctx);
@@ -485,8 +479,8 @@ int dmt_bvh_validate(const float* xs, const float* ys, const float* zs, size_t c
 // ---- motion blur -------------------------------------------------------------------------
 int dmt_set_motion(dmt_ctx* ctx, const float* xs1, const float* ys1, const float* zs1, size_t count) {
   if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_set_motion: before any dmt_upload_triangles");
-  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: count differs from the uploaded triangle count");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_set_motion: before any dmt_upload_triangles");
+  if (count != ctx->scene.triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: count differs from the uploaded triangle count");
   if (count && (!xs1 || !ys1 || !zs1)) return fail(ctx, DMT_ERR_INVALID, "dmt_set_motion: null array");
   for (size_t k = 0; k < 4 * count; ++k) {
     if ((k & 3) == 3) continue;  // the SoA's pad lane
@@ -496,8 +490,8 @@ int dmt_set_motion(dmt_ctx* ctx, const float* xs1, const float* ys1, const float
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old key 1
   std::vector<TriIsect> a, b;
   std::vector<TriPost> pa, pb;
-  packSoup(ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->h_mat.data(), count, a, pa);  // A: the records the context holds
-  packSoup(xs1, ys1, zs1, ctx->h_mat.data(), count, b, pb);
+  packSoup(ctx->scene.h_xs.data(), ctx->scene.h_ys.data(), ctx->scene.h_zs.data(), ctx->scene.h_mat.data(), count, a, pa);  // A: the records the context holds
+  packSoup(xs1, ys1, zs1, ctx->scene.h_mat.data(), count, b, pb);
   std::vector<TriIsect> d(count);  // zeroed: the material id and the pads of a delta record
   std::vector<TriKey1> q(count);
   for (size_t i = 0; i < count; ++i) {  // D = B - A, component by component in fp32
@@ -537,7 +531,7 @@ int dmt_set_shutter(dmt_ctx* ctx, float open, float close) {
 int dmt_motion_info(dmt_ctx* ctx, int* keys, float* open, float* close, uint32_t* tree_nodes, uint32_t* tree_pairs, double* tree_build_ms) {
   if (!ctx) return DMT_ERR_INVALID;
   AccelState const& A = ctx->ac;  // a dropped motion tree has zero counts and time
-  if (keys) *keys = ctx->haveTris ? (A.haveMotion ? 2 : 1) : 0;
+  if (keys) *keys = ctx->scene.haveTris ? (A.haveMotion ? 2 : 1) : 0;
   if (open) *open = A.shutterOpen;
   if (close) *close = A.shutterClose;
   if (tree_nodes) *tree_nodes = A.motionTree.nodeCount;
@@ -547,14 +541,11 @@ int dmt_motion_info(dmt_ctx* ctx, int* keys, float* open, float* close, uint32_t
 }
 
 int dmt_shutter_times(int width, int height, float open, float close, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t) {
-  if (width <= 0 || height <= 0 || width > 65536 || height > 65536 || n < 0 || !shutterOk(open, close)) return DMT_ERR_INVALID;
+  if (!resolutionOk(width, height) || n < 0 || !shutterOk(open, close)) return DMT_ERR_INVALID;
   if (n && (!pxs || !pys || !ss || !t)) return DMT_ERR_INVALID;
-  SamplerParams const sp = computeSamplerParams(width, height);
-  int64_t const stride = int64_t(sp.scale0) * sp.scale1;
-  for (int i = 0; i < n; ++i)
-    if (pxs[i] < 0 || pys[i] < 0 || pxs[i] >= width || pys[i] >= height || ss[i] < 0 || (int64_t(ss[i]) + 1) * stride > 0x7FFFFFFFll)
-      return DMT_ERR_INVALID;  // outside the frame, or the sample overflows the 32-bit Halton index
-  for (int i = 0; i < n; ++i) t[i] = shutter_time(uint32_t(halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * int32_t(stride)), open, close);
+  std::vector<int32_t> hs;
+  if (!haltonIndices(computeSamplerParams(width, height), width, height, n, pxs, pys, ss, hs)) return DMT_ERR_INVALID;
+  for (int i = 0; i < n; ++i) t[i] = shutter_time(uint32_t(hs[size_t(i)]), open, close);
   return DMT_OK;
 }
 
@@ -581,6 +572,80 @@ int dmt_motion_bvh_validate(const float* xs0, const float* ys0, const float* zs0
   bool const ok0 = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs0, ys0, zs0, count, nullptr, nullptr, nullptr);
   bool const ok1 = bvh_build::check(r.nodes.data(), r.nodes.size(), r.pairTris.data(), r.pairTris.size() / 2, xs1, ys1, zs1, count, nullptr, nullptr, nullptr);
   return ok0 && ok1 && r.depth <= kBvhMaxDepth ? DMT_OK : DMT_ERR_STATE;
+}
+
+// ---- the brute-force pass's cluster plan, host-only (cull_plan.hpp) ------------------------------
+int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                        uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_sphere) {
+  if (!soupArgsOk(xs, ys, zs, mat_id, count) || !cluster_count) return DMT_ERR_INVALID;
+  std::vector<float> radii;
+  std::vector<CullCluster> const cl = planBruteCull(CullSoup{xs, ys, zs, mat_id, uint32_t(count)}, enable != 0, &radii);
+  *cluster_count = uint32_t(cl.size());
+  for (size_t k = 0; k < cl.size(); ++k) {
+    if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
+    if (cluster_sphere) cluster_sphere[4 * k] = cl[k].b[0], cluster_sphere[4 * k + 1] = cl[k].b[1], cluster_sphere[4 * k + 2] = cl[k].b[2],
+                        cluster_sphere[4 * k + 3] = radii[k];
+  }
+  return DMT_OK;
+}
+
+// cluster_box: the planner's inflated boxes (lo xyz, hi xyz); cluster_record: what the device reads (centre xyz, half-width xyz)
+static int cullBoxPlan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                       uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box, float* cluster_record) {
+  if (!soupArgsOk(xs, ys, zs, mat_id, count) || !cluster_count) return DMT_ERR_INVALID;
+  std::vector<CullCluster> cl;
+  std::vector<float> planBox;
+  if (enable && count < kCullMaxIndex) {
+    CullSoup const soup{xs, ys, zs, mat_id, uint32_t(count)};
+    cl = planBruteCullBox(soup, planBruteCull(soup, true, nullptr), &planBox);
+  }
+  *cluster_count = uint32_t(cl.size());
+  for (size_t k = 0; k < cl.size(); ++k) {
+    if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
+    for (int a = 0; a < 6; ++a) {
+      if (cluster_box) cluster_box[6 * k + size_t(a)] = planBox[6 * k + size_t(a)];
+      if (cluster_record) cluster_record[6 * k + size_t(a)] = cl[k].b[a];
+    }
+  }
+  return DMT_OK;
+}
+
+int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                            uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box) {
+  return cullBoxPlan(xs, ys, zs, mat_id, count, enable, cluster_count, cluster_first_count, cluster_box, nullptr);
+}
+
+int dmt_brute_cull_box_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
+                               uint32_t* cluster_count, float* cluster_box, float* cluster_record) {
+  return cullBoxPlan(xs, ys, zs, mat_id, count, enable, cluster_count, nullptr, cluster_box, cluster_record);
+}
+
+int dmt_cull_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int level,
+                     uint32_t* cluster_count, uint32_t* record_bytes, uint32_t* record_align, void* records) {
+  if (!soupArgsOk(xs, ys, zs, mat_id, count) || !cluster_count) return DMT_ERR_INVALID;
+  std::vector<CullCluster> const cl = planCullClusters(level, CullSoup{xs, ys, zs, mat_id, uint32_t(count)});
+  *cluster_count = uint32_t(cl.size());
+  if (record_bytes) *record_bytes = uint32_t(sizeof(CullCluster));
+  if (record_align) *record_align = uint32_t(alignof(CullCluster));
+  if (records && !cl.empty()) memcpy(records, cl.data(), cl.size() * sizeof(CullCluster));
+  return DMT_OK;
+}
+
+// The device's box bound test on the host, ray by ray: cull_ray, cull_box_axis and cull_box_accept as brute_clusters calls
+// them, with a division where the device has v_rcp_f32 (within 1 ulp of it) and denormals kept.
+int dmt_cull_box_test(const float* record6, const float* origins, const float* dirs, const float* tmax, size_t count, uint8_t* accept) {
+  if (!record6 || (count && (!origins || !dirs || !tmax || !accept))) return DMT_ERR_INVALID;
+  for (size_t i = 0; i < count; ++i) {
+    float const* const o = origins + 3 * i;
+    float const* const d = dirs + 3 * i;
+    CullRay<float> const cr = cull_ray(o[0], o[1], o[2], 1.0f / cull_dir(d[0]), 1.0f / cull_dir(d[1]), 1.0f / cull_dir(d[2]));
+    float nx, ny, nz, fx, fy, fz;
+    cull_box_axis(record6[0], record6[3], cr.ax, cr.rx, cr.bx, nx, fx);
+    cull_box_axis(record6[1], record6[4], cr.ay, cr.ry, cr.by, ny, fy);
+    cull_box_axis(record6[2], record6[5], cr.az, cr.rz, cr.bz, nz, fz);
+    accept[i] = cull_box_accept(nx, ny, nz, fx, fy, fz, tmax[i] * kCullTSlack, cr.e2) ? 1 : 0;
+  }
+  return DMT_OK;
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // accel_host.hpp.
 //
 // Part of dmt_hip.hip's translation unit, included once before dmt_ctx: it uses DevBuf, the node and pair records of
-// bvh.hpp, the record types of tri_records.hpp, CullCluster, the builder's scratch types and the two records of dmt_hip.h.
+// bvh.hpp, the record types of tri_records.hpp, CullCluster (cull_plan.hpp), the builder's scratch types and the two records
+// of dmt_hip.h.
 //
 // What invalidates what.  "drop" frees a tree's arrays and zeroes its counts; nothing reads a dropped tree (requireTree,
 // ensureMotionTree).  Under DMT_ACCEL_BVH a dropped tree is rebuilt before the call returns: the static tree by buildBvh,
@@ -23,6 +24,10 @@
 //
 // The build record is of the static tree only and is rewritten by every build of it (adopt); without a static tree
 // dmt_accel_build_info reports zero counts.  dmt_set_shutter, shadeThresholdEnv and the scratch buffers survive everything.
+//
+// The cull tables are of the soup's current positions: dmt_upload_triangles and both vertex updates plan them anew
+// (planCullClusters, by bruteCull) and commit them with the records they were planned from; nothing else touches them.
+// bruteCull is set once, from DMT_BRUTE_CULL when the context is created.
 #pragma once
 
 namespace {
@@ -50,6 +55,9 @@ struct CullTables {
 };
 
 struct AccelState {
+  // the brute-force pass's culled clusters (cull_plan.hpp); none: the pass tests the soup's records for every ray
+  int bruteCull = 2;  // DMT_BRUTE_CULL at context creation (A/B runs, tests): 0 no clusters, 1 sphere clusters only, unset both
+  CullTables cull;
   BvhTree tree;                          // of the uploaded soup (key 0), built for DMT_ACCEL_BVH
   // motion blur (dmt_set_motion).  Key 0 is the context's soup; key 1 lives here and is dropped with it.  The
   // motion tree is a second tree beside the static one (which stays as it is: dmt_clear_motion restores every film byte

@@ -2,9 +2,9 @@
 // a-trous filter and temporal accumulation, and the rules that keep the temporal history and its raw-vertex mirror valid.
 //
 // Part of dmt_hip.hip's translation unit, included once after the host helpers it uses (dmt_ctx, HIP_TRY, fail, baseParams,
-// checkErrorFlag, cameraFromRaster, worldFromCamera; accel_host.hpp's requireTree, reserveOverflow, motionParams;
-// surface_host.hpp's firstHitVariant) and before the first entry point that calls into it.  accel_host.hpp forward-declares
-// the two mirror calls below for its vertex updates.
+// checkErrorFlag; camera_host.hpp's cameraFromRaster and worldFromCamera; accel_host.hpp's requireTree, reserveOverflow,
+// motionParams; surface_host.hpp's firstHitVariant; SceneState::matIdOutside) and before the first entry point that calls
+// into it.  accel_host.hpp forward-declares the two mirror calls below for its vertex updates.
 // The rest of the library reaches DenoiseState through dropHistory / dropVertexMirror and the two mirror calls below.
 #pragma once
 
@@ -12,11 +12,11 @@ namespace {
 // temporal accumulation: the raw vertices of the current soup, 9 floats per triangle, from the host copy.  The caller has
 // drained the stream (a kernel in flight may read the array)
 int uploadRawVertices(dmt_ctx* ctx) {
-  size_t const n = ctx->triCount;
+  size_t const n = ctx->scene.triCount;
   std::vector<float> v(9 * n);
   for (size_t i = 0; i < n; ++i)
     for (size_t k = 0; k < 3; ++k)
-      v[9 * i + 3 * k] = ctx->h_xs[4 * i + k], v[9 * i + 3 * k + 1] = ctx->h_ys[4 * i + k], v[9 * i + 3 * k + 2] = ctx->h_zs[4 * i + k];
+      v[9 * i + 3 * k] = ctx->scene.h_xs[4 * i + k], v[9 * i + 3 * k + 1] = ctx->scene.h_ys[4 * i + k], v[9 * i + 3 * k + 2] = ctx->scene.h_zs[4 * i + k];
   HIP_TRY(ctx, ctx->dn.tvCur.assign(v.data(), v.size()));
   ctx->dn.tvValid = true;
   return DMT_OK;
@@ -26,7 +26,7 @@ int uploadRawVertices(dmt_ctx* ctx) {
 // there is no such frame
 int keepHistoryVertices(dmt_ctx* ctx, bool wait) {
   if (!ctx->dn.tvPrevIsCur || !ctx->dn.thValid) return DMT_OK;
-  size_t const n = 9 * size_t(ctx->triCount);
+  size_t const n = 9 * size_t(ctx->scene.triCount);
   HIP_TRY(ctx, ctx->dn.tvPrev.reserve(n ? n : 1));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->dn.tvPrev.get(), ctx->dn.tvCur.get(), n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   if (wait) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -61,7 +61,7 @@ ProjXf makeProjXf(dmt_camera const& cam) {
 }
 // the first temporal call, a new resolution, a new soup: the history's planes and the current raw vertices
 int prepareHistory(dmt_ctx* ctx, size_t pixels) {
-  if (ctx->dn.thW != ctx->filmW || ctx->dn.thH != ctx->filmH) ctx->dn.dropHistory();
+  if (ctx->dn.thW != ctx->film.w || ctx->dn.thH != ctx->film.h) ctx->dn.dropHistory();
   for (int i = 0; i < 2; ++i) {
     HIP_TRY(ctx, ctx->dn.histCv[i].reserve(pixels));
     HIP_TRY(ctx, ctx->dn.histLen[i].reserve(pixels));
@@ -69,7 +69,7 @@ int prepareHistory(dmt_ctx* ctx, size_t pixels) {
   HIP_TRY(ctx, ctx->dn.histNormal.reserve(pixels));
   HIP_TRY(ctx, ctx->dn.histPos.reserve(pixels));
   HIP_TRY(ctx, ctx->dn.counts.reserve(2));
-  ctx->dn.thW = ctx->filmW, ctx->dn.thH = ctx->filmH;
+  ctx->dn.thW = ctx->film.w, ctx->dn.thH = ctx->film.h;
   if (!ctx->dn.tvValid) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (int const rc = uploadRawVertices(ctx)) return rc;  // the soup is new: dropVertexMirror has dropped the history
@@ -95,21 +95,21 @@ int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params,
     return failn(DMT_ERR_INVALID, "every sigma must be finite and > 0");
   if (tp && (!(tp->alpha >= 0.f && tp->alpha <= 1.f) || !std::isfinite(tp->normal_threshold) || !positive(tp->plane_threshold)))
     return failn(DMT_ERR_INVALID, "alpha must be 0 .. 1, normal_threshold finite, plane_threshold finite and > 0");
-  if (!ctx->haveCamera) return failn(DMT_ERR_STATE, "set the camera first");
+  if (!ctx->camera.have) return failn(DMT_ERR_STATE, "set the camera first");
   if (ctx->dn.aovW == 0) return failn(DMT_ERR_STATE, "no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
-  if (ctx->dn.aovW != ctx->filmW || ctx->dn.aovH != ctx->filmH) {
+  if (ctx->dn.aovW != ctx->film.w || ctx->dn.aovH != ctx->film.h) {
     char msg[160];
-    snprintf(msg, sizeof(msg), "the AOVs are %d x %d, the film %d x %d", ctx->dn.aovW, ctx->dn.aovH, ctx->filmW, ctx->filmH);
+    snprintf(msg, sizeof(msg), "the AOVs are %d x %d, the film %d x %d", ctx->dn.aovW, ctx->dn.aovH, ctx->film.w, ctx->film.h);
     return failn(DMT_ERR_STATE, msg);
   }
   if (tp && !ctx->dn.aovSurface) return failn(DMT_ERR_STATE, "no surface plane (call dmt_render_aovs, or dmt_upload_aov_surface after dmt_upload_aovs)");
-  if (tp && !ctx->haveTris) return failn(DMT_ERR_STATE, "upload triangles first");
-  if (tp && ctx->triCount > (1u << 24)) return failn(DMT_ERR_STATE, "more than 2^24 triangles: the surface plane's float index is not exact");
-  if (!mean4 && !ctx->d_mean) return failn(DMT_ERR_STATE, "no film");
+  if (tp && !ctx->scene.haveTris) return failn(DMT_ERR_STATE, "upload triangles first");
+  if (tp && ctx->scene.triCount > (1u << 24)) return failn(DMT_ERR_STATE, "more than 2^24 triangles: the surface plane's float index is not exact");
+  if (!mean4 && !ctx->film.mean) return failn(DMT_ERR_STATE, "no film");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
-  float4 const* mean = ctx->d_mean;
-  float4 const* m2 = ctx->d_m2;
+  size_t const pixels = size_t(ctx->film.w) * size_t(ctx->film.h);
+  float4 const* mean = ctx->film.mean;
+  float4 const* m2 = ctx->film.m2;
   if (mean4) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, ctx->dn.film.reserve(2 * pixels));
@@ -124,8 +124,8 @@ int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params,
   float4* const cv[2] = {ctx->dn.cv.get(), ctx->dn.cv.get() + pixels};
   DenoiseArgs A{};
   A.mean = mean, A.m2 = m2, A.albedo = ctx->dn.albedo.get(), A.normal = ctx->dn.normal.get(), A.position = ctx->dn.pos.get();
-  A.bad = ctx->dn.bad.get(), A.width = ctx->filmW, A.height = ctx->filmH;
-  A.theta = ctx->cam.sensor_size / (ctx->cam.focal_length * float(ctx->cam.height));
+  A.bad = ctx->dn.bad.get(), A.width = ctx->film.w, A.height = ctx->film.h;
+  A.theta = ctx->camera.cam.sensor_size / (ctx->camera.cam.focal_length * float(ctx->camera.cam.height));
   A.sigmaN = p.sigma_normal, A.sigmaX = p.sigma_position, A.sigmaA = p.sigma_albedo, A.sigmaL = p.sigma_luminance;
   EventPair ev, evT;
   HIP_TRY(ctx, hipEventCreate(&ev.a));
@@ -140,9 +140,9 @@ int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params,
   A.dst = cv[0];
   hipLaunchKernelGGL(k_denoise_init, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, ctx->stream, A);
   HIP_TRY(ctx, hipGetLastError());
-  dim3 const grid(uint32_t((ctx->filmW + 63) / 64), uint32_t((ctx->filmH + 3) / 4));
+  dim3 const grid(uint32_t((ctx->film.w + 63) / 64), uint32_t((ctx->film.h + 3) / 4));
   int const slotNew = ctx->dn.thSlot ^ 1;
-  ProjXf const camCur = tp ? makeProjXf(ctx->cam) : ProjXf{};
+  ProjXf const camCur = tp ? makeProjXf(ctx->camera.cam) : ProjXf{};
   if (tp) {
     TemporalArgs T{};
     T.cur = cv[0], T.albedo = A.albedo, T.normal = A.normal, T.surface = ctx->dn.surface.get();
@@ -152,7 +152,7 @@ int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params,
     T.outCv = ctx->dn.histCv[slotNew].get(), T.outLen = ctx->dn.histLen[slotNew].get();
     T.counts = ctx->dn.counts.get();
     T.camCur = camCur, T.camPrev = ctx->dn.thValid ? ctx->dn.thCam : camCur;
-    T.width = ctx->filmW, T.height = ctx->filmH, T.triCount = ctx->triCount, T.haveHistory = ctx->dn.thValid ? 1 : 0;
+    T.width = ctx->film.w, T.height = ctx->film.h, T.triCount = ctx->scene.triCount, T.haveHistory = ctx->dn.thValid ? 1 : 0;
     T.alpha = tp->alpha, T.normalThreshold = tp->normal_threshold, T.planeThreshold = tp->plane_threshold;
     T.thetaPrev = ctx->dn.thValid ? ctx->dn.thTheta : A.theta;
     HIP_TRY(ctx, hipEventRecord(evT.a, ctx->stream));
@@ -213,18 +213,18 @@ dmt_denoise_params dmt_denoise_defaults(void) {
 int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   if (!ctx) return DMT_ERR_INVALID;
   if (aov_spp == 0 || aov_spp > 65536u) return fail(ctx, DMT_ERR_INVALID, "dmt_render_aovs: aov_spp must be 1 .. 65536");
-  if (!(ctx->haveTris && ctx->haveBsdfs && ctx->haveCamera))
+  if (!(ctx->scene.haveTris && ctx->scene.haveBsdfs && ctx->camera.have))
     return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: upload triangles, bsdfs and set the camera first");
-  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
+  if (ctx->scene.matIdOutside())
     return fail(ctx, DMT_ERR_INVALID, "dmt_render_aovs: material index outside the BSDF array");
-  if (!ctx->surf.texturesMatch(ctx->bsdfCount, ctx->triCount))
+  if (!ctx->surf.texturesMatch(ctx->scene.bsdfCount, ctx->scene.triCount))
     return fail(ctx, DMT_ERR_STATE, "dmt_render_aovs: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
   int variant = 0;
   if (int const rcV = firstHitVariant(ctx, "dmt_render_aovs", &variant)) return rcV;
   bool const useBvh = ctx->accel == DMT_ACCEL_BVH;
   if (int const rcT = useBvh ? requireTree(ctx, "dmt_render_aovs") : DMT_OK) return rcT;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t const pixels = size_t(ctx->filmW) * size_t(ctx->filmH);
+  size_t const pixels = size_t(ctx->film.w) * size_t(ctx->film.h);
   ctx->dn.aovW = ctx->dn.aovH = 0;  // no AOVs unless this call succeeds
   ctx->dn.aovSurface = false;
   HIP_TRY(ctx, ctx->dn.albedo.reserve(pixels));
@@ -238,14 +238,14 @@ int dmt_render_aovs(dmt_ctx* ctx, uint32_t aov_spp) {
   AovArgs A{};
   A.albedo = ctx->dn.albedo.get(), A.normal = ctx->dn.normal.get(), A.position = ctx->dn.pos.get();
   A.surface = ctx->dn.surface.get();
-  A.width = ctx->filmW, A.pixels = uint32_t(pixels), A.aovSpp = aov_spp, A.useBvh = useBvh;
+  A.width = ctx->film.w, A.pixels = uint32_t(pixels), A.aovSpp = aov_spp, A.useBvh = useBvh;
   RenderParams P = baseParams(ctx, threads);
   uint32_t const motionMask = ctx->ac.haveMotion ? kFeatMotion | (useBvh ? kFeatBvh : 0u) : 0u;  // the samples' times, as the film's rows
   if (int const rcM = motionParams(ctx, motionMask, P)) return rcM;
   decltype(&k_aov) const kernels[4] = {k_aov, k_aov_vn, k_aov_motion, k_aov_cut};  // by firstHitVariant
   hipLaunchKernelGGL(kernels[variant], dim3(uint32_t(blocks)), dim3(256), 0, ctx->stream, P, A);
   HIP_TRY(ctx, hipGetLastError());
-  ctx->dn.aovW = ctx->filmW, ctx->dn.aovH = ctx->filmH;
+  ctx->dn.aovW = ctx->film.w, ctx->dn.aovH = ctx->film.h;
   ctx->dn.aovSurface = true;
   return DMT_OK;
 }

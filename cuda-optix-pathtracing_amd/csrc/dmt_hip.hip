@@ -44,32 +44,16 @@
 #include "light_tree.hpp"
 #include "light_tree_ref.hpp"
 #include "emitter_tree.hpp"
+#include "cull_plan.hpp"
 
 using namespace dmt;
 
 namespace {
 
-// Culled clusters of the brute-force pass (planBruteCull / planBruteCullBox on the host, brute_clusters on the device).  A
-// cluster is a run of consecutive triangles of one material -- one mesh of the scene front-ends -- with a cheap bound: a small
-// sphere (compact meshes) or a thin box (flat meshes such as walls); the pass tests its triangles only for the rays that touch
-// the bound, compacted over the wave's lanes.  Everything else stays in the "always" list, which the packed SGPR loop tests
-// for every ray as before.
-constexpr uint32_t kCullMaxClusters = 12;  // sphere clusters first, then box clusters; the device takes them kCullGroup at a time
-constexpr uint32_t kCullGroup = 4;
-constexpr uint32_t kCullMaxTris = 44;      // LDS copy of the culled triangles, 36 B each (see the LDS budget in DESIGN.md 4.1)
-constexpr uint32_t kCullSlotBits = 6;      // a closest-hit key holds (original index << 6 | LDS slot): kCullMaxTris <= 64
-constexpr uint32_t kCullMaxIndex = 1u << (32 - kCullSlotBits);  // no culling for soups of more triangles
-struct alignas(64) CullCluster {           // 64 B: the first 32 are what a bound test reads, in one aligned s_load_dwordx8
-  float b[6];                              // sphere: centre xyz and squared inflated radius; box: centre xyz, half-width xyz
-  uint32_t box;                            // 0: sphere bound, 1: box bound
-  uint32_t count;                          // original triangle indices [first, first + count)
-  uint32_t first;
-  uint32_t slot, magic;                    // first slot of its triangles in the LDS copy; ceil(2^32 / count)
-  uint32_t pad[5];
-};
-typedef uint32_t CullWords __attribute__((ext_vector_type(8)));  // b[0..5], box, count
-static_assert(offsetof(CullCluster, box) == 24 && offsetof(CullCluster, count) == 28, "CullWords: the record's first eight words");
-static_assert(sizeof(CullCluster) == 64 && alignof(CullCluster) == 64 && offsetof(CullCluster, first) == 32, "CullCluster layout");
+// Culled clusters of the brute-force pass: the record (CullCluster), the plan's limits and the host planners are in
+// cull_plan.hpp; what follows is the device's view of a plan (brute_clusters).
+constexpr uint32_t kCullGroup = 4;         // the device takes the clusters kCullGroup at a time
+typedef uint32_t CullWords __attribute__((ext_vector_type(8)));  // a CullCluster's first eight words: b[0..5], box, count
 struct CullRec {                           // 12 B, the block's LDS copy of what a compacted task needs
   uint32_t first, countSlot, magic;        // countSlot = count | slot << 16
 };
@@ -1917,6 +1901,8 @@ __global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
 // =============================================================================================
 // host side of the C ABI
 // =============================================================================================
+#include "scene_state.hpp"
+#include "camera_state.hpp"
 #include "accel_state.hpp"
 #include "surface_state.hpp"
 #include "medium_state.hpp"
@@ -1928,44 +1914,20 @@ struct dmt_ctx {
   hipStream_t ownStream = nullptr;
   hipStream_t stream = nullptr;
   std::string err;
-  // scene
-  DevBuf<TriIsect> d_tris;
-  DevBuf<TriPost> d_post;
-  DevBuf<Rec32> d_bsdfs;
-  uint32_t triCount = 0, bsdfCount = 0;
-  uint32_t maxMatId = 0;
-  // the brute-force pass's culled clusters (planBruteCull, planBruteCullBox); none: the pass tests d_tris for every ray
-  int bruteCull = 2;  // DMT_BRUTE_CULL at context creation (A/B runs, tests): 0 no clusters, 1 sphere clusters only, unset both
-  CullTables cull;
-  std::vector<float> h_xs, h_ys, h_zs;  // host copy of the soup (the builders' input)
-  std::vector<uint32_t> h_mat;
-  // the acceleration layer: the static and the motion tree, builder and update policy, key 1 (accel_state.hpp, accel_host.hpp)
+  // the scene layer: the triangle soup with its host copy, the BSDF records (scene_state.hpp, scene_host.hpp)
+  SceneState scene;
+  // the camera layer: the camera and the sampler set-up, the thin lens, the pixel filter; and the film, the context's own or
+  // the caller's after dmt_film_bind (camera_state.hpp, camera_host.hpp)
+  CameraState camera;
+  FilmState film;
+  // the acceleration layer: the static and the motion tree, builder and update policy, key 1, the cull tables of the
+  // brute-force pass (accel_state.hpp, accel_host.hpp, cull_plan.hpp)
   AccelState ac;
   // the light layer: the light list, the light tree over it and the env map (light_state.hpp, light_host.hpp)
   LightState lights;
   // the surface-attribute layer: textures and UVs, the texture filter, vertex normals, opacity records, emissive triangles
   // (surface_state.hpp, surface_host.hpp)
   SurfaceState surf;
-  bool hasBlend = false;  // some uploaded BSDF record is a BS_GGX_BLEND pair: the *_blend kernels carry that code
-  bool haveTris = false, haveBsdfs = false, haveCamera = false;
-  // camera
-  dmt_camera cam{};
-  CameraXf xf{};
-  SamplerParams sp{};
-  float lensR = 0.f, lensD = 1.f;  // thin lens (dmt_set_lens): radius 0 = pinhole; survives dmt_set_camera and scene uploads
-  // pixel filter (dmt_set_pixel_filter): box 0.5, the default, is inactive (no table, no warp); survives like the lens
-  struct PixelFilter {
-    int kind = DMT_FILTER_BOX;
-    float radius = 0.5f, param = 0.f;
-    bool active = false;
-    DevBuf<FilterBin> knots;  // kFilterBins pairs while active (kept, unread, after a return to the default)
-    FilterBin const* view() const { return active ? knots.get() : nullptr; }
-  } filt;
-  // film: the context's own, or the caller's after dmt_film_bind (which frees the own one)
-  DevBuf<float4> ownMean, ownM2;
-  float4* d_mean = nullptr;
-  float4* d_m2 = nullptr;
-  int filmW = 0, filmH = 0;
   // the medium layer: the participating medium, its density grid and its spectrum (medium_state.hpp, medium_host.hpp)
   MediumState medium;
   // the launch layer: the scheduler's buffers and fold accounting, GGX batching, the sampler table, adaptive rounds, the
@@ -1996,205 +1958,14 @@ int fail(dmt_ctx* ctx, int code, char const* msg) {
   return code;
 }
 
-// ---- host math for the one-off camera / sampler setup (IEEE fp32, same expressions as the
-// reference host code: CC/private/extra_math.cu:43-90, CC/private/common_math.cu:16-78,
-// CC/private/rng.cu:21-46,182-208)
-struct H3 {
-  float x, y, z;
-};
-H3 hcross(H3 a, H3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-H3 hnormalize(H3 a) {
-  float const inv = 1.0f / sqrtf(a.x * a.x + a.y * a.y + a.z * a.z);
-  return {a.x * inv, a.y * inv, a.z * inv};
-}
-
-// ---- the brute-force pass's culled clusters ----
-// A candidate is a maximal run of consecutive triangles with one material id (one mesh of the scene front-ends) of at least
-// kCullMinTris triangles.  Its bound is the sphere around the centre of its vertex box through the farthest vertex, inflated
-// by 1/1024 of the radius plus 1e-6 of (|centre|_max + radius): far more than mt_valid's 1e-7 barycentric slack (1e-7 of an
-// edge), the float rounding of the centre and of e0 / e1, and the squared radius is rounded up.  It is culled when that
-// radius is at most kCullMaxRadiusFrac of the scene's bounding-box diagonal; in index order while at most kCullMaxSphereClusters
-// clusters and kCullMaxSphereTris triangles are taken.  The device test adds a relative margin of its own
-// (kCullRel) for the rounding of the segment-sphere test and of the Moeller-Trumbore hit point.
-constexpr uint32_t kCullMinTris = 4;
-constexpr double kCullMaxRadiusFrac = 0.125;
-constexpr uint32_t kCullMaxSphereClusters = 4, kCullMaxSphereTris = 32;
-std::vector<CullCluster> planBruteCull(float const* xs, float const* ys, float const* zs, uint32_t const* mat, uint32_t n, bool enable,
-                                       std::vector<float>* radii) {
-  std::vector<CullCluster> out;
-  if (!enable || n == 0) return out;
-  auto vtx = [&](uint32_t t, int k, int a) { return double((a == 0 ? xs : a == 1 ? ys : zs)[4 * size_t(t) + k]); };
-  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-  for (uint32_t t = 0; t < n; ++t)
-    for (int k = 0; k < 3; ++k)
-      for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], vtx(t, k, a)), hi[a] = std::fmax(hi[a], vtx(t, k, a));
-  double const diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
-  if (!std::isfinite(diag)) return out;
-  uint32_t culled = 0;
-  for (uint32_t first = 0, end = 0; first < n && out.size() < kCullMaxSphereClusters; first = end) {
-    for (end = first + 1; end < n && mat[end] == mat[first];) ++end;
-    uint32_t const count = end - first;
-    if (count < kCullMinTris || culled + count > kCullMaxSphereTris) continue;
-    double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (uint32_t t = first; t < end; ++t)
-      for (int k = 0; k < 3; ++k)
-        for (int a = 0; a < 3; ++a) blo[a] = std::fmin(blo[a], vtx(t, k, a)), bhi[a] = std::fmax(bhi[a], vtx(t, k, a));
-    float const c[3] = {float(0.5 * (blo[0] + bhi[0])), float(0.5 * (blo[1] + bhi[1])), float(0.5 * (blo[2] + bhi[2]))};
-    double r2 = 0.0;
-    for (uint32_t t = first; t < end; ++t)
-      for (int k = 0; k < 3; ++k) {
-        double const dx = vtx(t, k, 0) - c[0], dy = vtx(t, k, 1) - c[1], dz = vtx(t, k, 2) - c[2];
-        r2 = std::fmax(r2, dx * dx + dy * dy + dz * dz);
-      }
-    double const cmax = std::fmax(std::fabs(double(c[0])), std::fmax(std::fabs(double(c[1])), std::fabs(double(c[2]))));
-    double const r = std::sqrt(r2) * (1.0 + 1.0 / 1024) + 1e-6 * (cmax + std::sqrt(r2));
-    if (!(r <= kCullMaxRadiusFrac * diag)) continue;
-    CullCluster cl{};
-    cl.b[0] = c[0], cl.b[1] = c[1], cl.b[2] = c[2];
-    cl.b[3] = std::nextafter(float(r * r), HUGE_VALF);
-    cl.first = first, cl.count = count, cl.slot = culled;
-    cl.magic = uint32_t(((uint64_t(1) << 32) + count - 1) / count);
-    out.push_back(cl);
-    if (radii) radii->push_back(float(r));
-    culled += count;
-  }
-  return out;
-}
-// Box clusters: a maximal one-material run of at least kCullBoxMinTris triangles that planBruteCull did not take -- the sphere
-// rule rejects flat meshes such as walls, whose sphere holds most of the scene.  Its bound is its vertex box with every face
-// moved out by m = 2^-19 (extent + |coordinate|_max of the box), then rounded outward to float.  m covers, with a margin of
-// about 8:
-//  * mt_valid's slack: it accepts u, v >= -1e-7 and u + v <= 1 + 1e-7, i.e. points up to 1e-7 (|e0| + |e1|) <= 3.5e-7 extent
-//    outside the triangle;
-//  * e0 / e1 are stored as floats: the tested triangle's vertices are up to 2^-24 |e| <= 1.1e-7 extent off the soup's;
-//  * the rounding of the Moeller-Trumbore arithmetic across the ray: a few ulps of the coordinates, 2^-22 |coordinate|_max.
-// Along the ray the device allows for its own rounding: the segment runs from kCullTLo = (1 - 2^-8) 1e-4 to the end t
-// times kCullTSlack = 1 + 2^-8, and the slab test keeps near <= far * kCullTSlack + 2 E (cull_ray: the error term of its
-// centre / half-width arithmetic, which also takes m / 16 of the inflation).  A wall is 2m thick after inflation, m well
-// below kCullTLo: a ray leaving it at more than ~m / 1e-4 rad to its plane (Cornell: 0.057) gets it again only through E.
-// The record stores the box as centre and half-width, the half-width rounded up until [c - hw, c + hw] holds the box.
-// A run becomes a cluster when its box (before inflation) has a surface area of at most kCullBoxMaxAreaFrac of the scene
-// box's: a random line that meets the scene box meets a convex body inside it with probability S_body / S_scene (Cauchy),
-// and a compacted test costs about 2.7 packed ones.  Cornell's walls are exactly 1/3.  Clusters are taken in
-// index order while the total stays within kCullMaxClusters clusters and kCullMaxTris triangles (the LDS copy).
-constexpr uint32_t kCullBoxMinTris = 2;  // the task decode needs count >= 2; a lone triangle costs about one bound test anyway
-constexpr double kCullBoxMaxAreaFrac = 0.35;
-std::vector<CullCluster> planBruteCullBox(float const* xs, float const* ys, float const* zs, uint32_t const* mat, uint32_t n,
-                                          std::vector<CullCluster> const& spheres, std::vector<float>* planBox = nullptr) {
-  std::vector<CullCluster> out;
-  if (n == 0) return out;
-  auto vtx = [&](uint32_t t, int k, int a) { return double((a == 0 ? xs : a == 1 ? ys : zs)[4 * size_t(t) + k]); };
-  auto area = [](double const lo[3], double const hi[3]) {
-    double const x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
-    return 2.0 * (x * y + y * z + z * x);
-  };
-  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-  for (uint32_t t = 0; t < n; ++t)
-    for (int k = 0; k < 3; ++k)
-      for (int a = 0; a < 3; ++a) lo[a] = std::fmin(lo[a], vtx(t, k, a)), hi[a] = std::fmax(hi[a], vtx(t, k, a));
-  double const sceneArea = area(lo, hi);
-  if (!std::isfinite(sceneArea) || !(sceneArea > 0.0)) return out;
-  uint32_t culled = 0;
-  for (CullCluster const& c : spheres) culled += c.count;
-  size_t const taken = spheres.size();
-  for (uint32_t first = 0, end = 0; first < n && taken + out.size() < kCullMaxClusters; first = end) {
-    for (end = first + 1; end < n && mat[end] == mat[first];) ++end;
-    uint32_t const count = end - first;
-    if (count < kCullBoxMinTris || culled + count > kCullMaxTris) continue;
-    if (std::any_of(spheres.begin(), spheres.end(), [&](CullCluster const& c) { return c.first == first; })) continue;
-    double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (uint32_t t = first; t < end; ++t)
-      for (int k = 0; k < 3; ++k)
-        for (int a = 0; a < 3; ++a) blo[a] = std::fmin(blo[a], vtx(t, k, a)), bhi[a] = std::fmax(bhi[a], vtx(t, k, a));
-    if (!(area(blo, bhi) <= kCullBoxMaxAreaFrac * sceneArea)) continue;
-    double ext = 0.0, cmax = 0.0;
-    for (int a = 0; a < 3; ++a)
-      ext = std::fmax(ext, bhi[a] - blo[a]), cmax = std::fmax(cmax, std::fmax(std::fabs(blo[a]), std::fabs(bhi[a])));
-    double const m = 0x1p-19 * (ext + cmax);
-    CullCluster cl{};
-    float pl[3], ph[3];
-    bool holds = true;
-    for (int a = 0; a < 3; ++a) {
-      float l = float(blo[a] - m), h = float(bhi[a] + m);
-      if (double(l) > blo[a] - m) l = std::nextafter(l, -HUGE_VALF);
-      if (double(h) < bhi[a] + m) h = std::nextafter(h, HUGE_VALF);
-      pl[a] = l, ph[a] = h;
-      // the record: centre and half-width with [c - hw, c + hw] holding [l, h] in exact arithmetic.  The doubles below
-      // are within 2^-53 of the exact values, the float above them plus one more step is 2^-24 beyond.
-      float const c = float(0.5 * (double(l) + double(h)));
-      double const hd = std::fmax(double(c) - double(l), double(h) - double(c));
-      float hw = float(hd);
-      if (double(hw) < hd) hw = std::nextafter(hw, HUGE_VALF);
-      hw = std::nextafter(hw, HUGE_VALF);
-      holds = holds && std::isfinite(c) && std::isfinite(hw) && (long double)c - (long double)hw <= (long double)l &&
-              (long double)c + (long double)hw >= (long double)h;
-      cl.b[a] = c, cl.b[3 + a] = hw;
-    }
-    assert(holds);
-    if (!holds) continue;  // (NDEBUG builds) the run stays in the always list
-    if (planBox) planBox->insert(planBox->end(), {pl[0], pl[1], pl[2], ph[0], ph[1], ph[2]});
-    cl.box = 1;
-    cl.first = first, cl.count = count, cl.slot = culled;
-    cl.magic = uint32_t(((uint64_t(1) << 32) + count - 1) / count);
-    out.push_back(cl);
-    culled += count;
-  }
-  return out;
-}
-void worldFromCamera(float const dir[3], float const pos[3], float m[16]) {
-  H3 const fwd = hnormalize({dir[0], dir[1], dir[2]});
-  H3 const right = hnormalize(hcross(fwd, {0, 0, 1}));
-  H3 const up = hcross(right, fwd);
-  m[0] = right.x, m[4] = up.x, m[8] = fwd.x, m[12] = pos[0];
-  m[1] = right.y, m[5] = up.y, m[9] = fwd.y, m[13] = pos[1];
-  m[2] = right.z, m[6] = up.z, m[10] = fwd.z, m[14] = pos[2];
-  m[3] = 0.f, m[7] = 0.f, m[11] = 0.f, m[15] = 1.f;
-}
-void cameraFromRaster(float focal_mm, float sensorH_mm, uint32_t xRes, uint32_t yRes, float m[16]) {
-  float const sensorW_mm = sensorH_mm * float(xRes) / float(yRes);
-  float const MM = 0.001f;
-  float const focal = focal_mm * MM, sh = sensorH_mm * MM, sw = sensorW_mm * MM;
-  float const psx = sw / float(xRes), psy = sh / float(yRes);
-  float const tx = -0.5f * sw + 0.5f * psx;
-  float const ty = 0.5f * sh - 0.5f * psy;
-  for (int i = 0; i < 16; ++i) m[i] = 0.f;
-  m[0] = psx, m[5] = -psy, m[10] = 1.f, m[12] = tx, m[13] = ty, m[14] = focal, m[15] = 1.f;
-}
-int64_t multInverse(int64_t a, int64_t n) {
-  int64_t t = 0, nt = 1, r = n, nr = a;
-  while (nr != 0) {
-    int64_t const q = r / nr;
-    int64_t tmp = t - q * nt;
-    t = nt, nt = tmp;
-    tmp = r - q * nr;
-    r = nr, nr = tmp;
-  }
-  return t < 0 ? t + n : t;
-}
-SamplerParams computeSamplerParams(int width, int height) {
-  SamplerParams p{};
-  int const res[2] = {width, height};
-  int32_t scale[2], ex[2];
-  int const base[2] = {2, 3};
-  for (int i = 0; i < 2; ++i) {
-    scale[i] = 1, ex[i] = 0;
-    int const lim = res[i] < 128 ? res[i] : 128;
-    while (scale[i] < lim) scale[i] *= base[i], ++ex[i];
-  }
-  p.scale0 = scale[0], p.scale1 = scale[1], p.exp0 = ex[0], p.exp1 = ex[1];
-  p.inv0 = int32_t(multInverse(scale[1], scale[0]));
-  p.inv1 = int32_t(multInverse(scale[0], scale[1]));
-  return p;
-}
-
 // The feature mask (kFeat*) of what a launch of this context needs.  The light and the medium layer give their own bits; the
 // light tree applies to plain surfaces only: textured or emissive-triangle scenes keep the uniform pick.
-bool plainSurfaces(dmt_ctx const* c) { return c->surf.area.count == 0 && c->surf.tex.count == 0 && !c->hasBlend; }
+bool plainSurfaces(dmt_ctx const* c) { return c->surf.area.count == 0 && c->surf.tex.count == 0 && !c->scene.hasBlend; }
 uint32_t featuresOf(dmt_ctx const* c) {
   uint32_t F = 0;
   if (c->accel == DMT_ACCEL_BVH) F |= kFeatBvh;
   if (c->surf.area.count > 0) F |= kFeatArea;
-  if (c->hasBlend) F |= kFeatBlend;  // the blend kernels carry the texture code too
+  if (c->scene.hasBlend) F |= kFeatBlend;  // the blend kernels carry the texture code too
   else if (c->surf.tex.count > 0) F |= kFeatTex;
   if (c->surf.texFilter == DMT_TEXFILTER_REFERENCE && (F & (kFeatTex | kFeatBlend))) F |= kFeatTexFilter;
   if (c->ac.haveMotion) F |= kFeatMotion;
@@ -2260,27 +2031,23 @@ int checkFeatures(dmt_ctx* ctx, uint32_t F) {
                                     "with textures, blended materials, emissive triangles or a light tree they would describe a different kernel");
   if ((F & kFeatBlend) && (F & kFeatArea)) return fail(ctx, DMT_ERR_STATE, "dmt_render: fractional-metallic materials together with emissive triangles are not supported");
   if ((F & kFeatTex) && (F & kFeatArea)) return fail(ctx, DMT_ERR_STATE, "dmt_render: image textures together with emissive triangles are not supported");
-  if (!ctx->surf.texturesMatch(ctx->bsdfCount, ctx->triCount))
+  if (!ctx->surf.texturesMatch(ctx->scene.bsdfCount, ctx->scene.triCount))
     return fail(ctx, DMT_ERR_STATE, "dmt_render: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
   return DMT_OK;
 }
 
-// ---- what dmt_upload_triangles and dmt_update_vertices share ----
-// both records of every triangle of a soup (tri_records.hpp; the record kernel of dmt_update_vertices_device runs the same function)
-void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const* mat, size_t count, std::vector<TriIsect>& a,
-              std::vector<TriPost>& b) {
-  a.resize(count), b.resize(count);
-  for (size_t i = 0; i < count; ++i) {
-    float const v[9] = {xs[4 * i], ys[4 * i], zs[4 * i], xs[4 * i + 1], ys[4 * i + 1], zs[4 * i + 1], xs[4 * i + 2], ys[4 * i + 2], zs[4 * i + 2]};
-    packTriangle(v, mat[i], a[i], b[i]);
-  }
-}
-
 }  // namespace
 
-// the acceleration layer: the trees, their builders and updates, key 1 of the motion, the cull tables; the helpers below,
-// denoise_host.hpp and probes.hpp call into it
+// the camera layer's helpers and entry points: the camera and sampler set-up math that the headers below use, the film, the
+// thin lens, the pixel filter
+#include "camera_host.hpp"
+
+// the acceleration layer: the trees, their builders and updates, key 1 of the motion, the cull tables and the entry points
+// that show a cull plan; the helpers below, scene_host.hpp, denoise_host.hpp and probes.hpp call into it
 #include "accel_host.hpp"
+
+// the scene layer's helpers and entry points: the records of a soup, dmt_upload_triangles, dmt_upload_bsdfs
+#include "scene_host.hpp"
 
 // the surface-attribute layer's helpers and entry points: textures, the texture filter, vertex normals, opacity records,
 // emissive triangles, and the first-hit variant chooser that denoise_host.hpp and probes.hpp use
@@ -2296,18 +2063,13 @@ void packSoup(float const* xs, float const* ys, float const* zs, uint32_t const*
 
 namespace {
 
-// scene / camera / limits part of the argument struct (what the path-tracing device code reads)
+// the layers' parts of the argument struct and the limits (what the path-tracing device code reads)
 RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   RenderParams P{};
-  P.scene.tris = c->d_tris.get(), P.scene.post = c->d_post.get(), P.scene.bsdfs = c->d_bsdfs.get();
-  P.scene.triCount = c->triCount, P.scene.bsdfCount = c->bsdfCount;
+  c->scene.fill(P);
   P.cull = cullView(c);
   P.bvh = bvhView(c, threads);
-  P.cam = c->xf;
-  P.sp = c->sp;
-  P.lensRad = c->lensR, P.lensD = c->lensD;
-  P.filtKnots = c->filt.view(), P.filtR = c->filt.radius;
-  P.camTail = (c->lensR > 0.f || c->filt.active) ? 1.f : 0.f;  // (a tabulated launch without a lens clears it: growLaunchBuffers)
+  c->camera.fill(P);
   P.maxDepth = c->maxDepth;
   P.shadeThreshold = shadeThresholdFor(c, c->ac.tree.nodeCount);
   c->lights.fill(P, plainSurfaces(c));
@@ -2316,8 +2078,6 @@ RenderParams baseParams(dmt_ctx const* c, size_t threads) {
   c->surf.fill(P);
   return P;
 }
-
-CameraExtra cameraExtraOf(dmt_ctx const* c) { return CameraExtra{c->lensR, c->lensD, c->filt.view(), c->filt.radius}; }
 
 int finishTest(dmt_ctx* ctx) {
   HIP_TRY(ctx, hipGetLastError());
@@ -2374,7 +2134,7 @@ int dmt_ctx_create(int device_ordinal, dmt_ctx** out) {
   }
   if (char const* e6 = std::getenv("DMT_BRUTE_CULL")) {  // A/B runs and tests
     int const v = std::atoi(e6);
-    ctx->bruteCull = v == 0 ? 0 : v == 1 ? 1 : 2;
+    ctx->ac.bruteCull = v == 0 ? 0 : v == 1 ? 1 : 2;
   }
   if (char const* e7 = std::getenv("DMT_TRI_KIND_INLINE")) ctx->surf.kind.allowInline = std::atoi(e7) != 0;  // tests (SurfaceState::Kind)
   if (char const* e8 = std::getenv("DMT_UNIFORM_LIGHTS")) ctx->lights.uniformPath = std::atoi(e8) != 0;  // A/B runs and tests (LightState)
@@ -2397,99 +2157,6 @@ int dmt_ctx_destroy(dmt_ctx* ctx) {
 
 const char* dmt_last_error(const dmt_ctx* ctx) { return ctx ? ctx->err.c_str() : g_createError.c_str(); }
 
-int dmt_upload_triangles(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs,
-                         const uint32_t* mat_id, size_t count) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_upload_triangles: null array or count out of range");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<TriIsect> a;
-  std::vector<TriPost> b;
-  packSoup(xs, ys, zs, mat_id, count, a, b);
-  uint32_t maxMat = 0;
-  for (size_t i = 0; i < count; ++i)
-    if (mat_id[i] > maxMat) maxMat = mat_id[i];
-  DevBuf<TriIsect> tris;
-  DevBuf<TriPost> post;
-  HIP_TRY(ctx, tris.assign(a.data(), count));
-  HIP_TRY(ctx, post.assign(b.data(), count));
-  CullTables cull;
-  if (int const rcC = uploadCullTables(ctx, planCullClusters(ctx, xs, ys, zs, mat_id, count), a.data(), count, cull)) return rcC;
-  ctx->d_tris = std::move(tris), ctx->d_post = std::move(post);
-  ctx->cull = std::move(cull);
-  ctx->triCount = uint32_t(count);
-  ctx->maxMatId = maxMat;
-  ctx->haveTris = true;
-  ctx->h_xs.assign(xs, xs + 4 * count), ctx->h_ys.assign(ys, ys + 4 * count), ctx->h_zs.assign(zs, zs + 4 * count);
-  ctx->h_mat.assign(mat_id, mat_id + count);
-  ctx->ac.tree.drop();         // it is of the soup just replaced
-  dropMotion(ctx);             // key 1 was a motion from the soup just replaced
-  ctx->lights.invalidateEmitters();  // the emitter tree was over triangles of the soup just replaced
-  hipError_t const kindRc = ctx->surf.soupReplaced(ctx->h_mat);  // vertex normals, opacity records and emissive triangles were of the soup just replaced; the material kinds are made anew
-  ctx->dn.dropVertexMirror();  // temporal history: its triangle indices are of the soup just replaced
-  HIP_TRY(ctx, kindRc);
-  if (ctx->accel == DMT_ACCEL_BVH) return buildBvh(ctx);
-  return DMT_OK;
-}
-
-int dmt_upload_bsdfs(dmt_ctx* ctx, const void* bsdf32, uint32_t count) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (count && !bsdf32) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_bsdfs: null array");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DevBuf<Rec32> bsdfs;
-  HIP_TRY(ctx, bsdfs.assign(bsdf32, count));
-  // fractional-metallic materials (BS_GGX_BLEND: this record + the conductor record after it) run on the *_tex kernels
-  bool blend = false;
-  for (uint32_t i = 0; i < count; ++i) {
-    uint32_t w1;
-    memcpy(&w1, static_cast<unsigned char const*>(bsdf32) + 32 * size_t(i) + 4, 4);
-    if ((w1 >> 16) == BS_GGX_BLEND) {
-      uint32_t w1next = 0;
-      if (i + 1 < count) memcpy(&w1next, static_cast<unsigned char const*>(bsdf32) + 32 * size_t(i + 1) + 4, 4);
-      if (i + 1 >= count || (w1next >> 16) != BS_GGX_COND)
-        return fail(ctx, DMT_ERR_INVALID, "dmt_upload_bsdfs: a blend record (type 4) must be followed by its GGX conductor record");
-      blend = true;
-    }
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (a launch in flight may read the cutout records dropped below)
-  hipError_t const kindRc = ctx->surf.bsdfsReplaced(bsdf32, count, ctx->h_mat);  // the cutout records name the materials just replaced; the material kinds are made anew
-  ctx->d_bsdfs = std::move(bsdfs);
-  ctx->hasBlend = blend;
-  ctx->bsdfCount = count;
-  ctx->haveBsdfs = true;
-  HIP_TRY(ctx, kindRc);
-  return DMT_OK;
-}
-
-int dmt_set_camera(dmt_ctx* ctx, const dmt_camera* cam) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!cam || cam->width <= 0 || cam->height <= 0 || cam->width > 65536 || cam->height > 65536)
-    return fail(ctx, DMT_ERR_INVALID, "dmt_set_camera: bad camera / resolution");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (cam->width != ctx->filmW || cam->height != ctx->filmH) {  // a new film, zeroed
-    size_t const pixels = size_t(cam->width) * size_t(cam->height);
-    DevBuf<float4> mean, m2;
-    HIP_TRY(ctx, mean.reserve(pixels));
-    HIP_TRY(ctx, m2.reserve(pixels));
-    HIP_TRY(ctx, hipMemsetAsync(mean.get(), 0, pixels * sizeof(float4), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(m2.get(), 0, pixels * sizeof(float4), ctx->stream));
-    ctx->ownMean = std::move(mean), ctx->ownM2 = std::move(m2);
-    ctx->d_mean = ctx->ownMean.get(), ctx->d_m2 = ctx->ownM2.get();
-    ctx->filmW = cam->width, ctx->filmH = cam->height;
-    ctx->dn.dropHistory();  // temporal history: it is of the old resolution
-  }
-  ctx->cam = *cam;
-  float m[16];
-  cameraFromRaster(cam->focal_length, cam->sensor_size, uint32_t(cam->width), uint32_t(cam->height), m);
-  memcpy(ctx->xf.cfr, m, sizeof(m));
-  worldFromCamera(cam->dir, cam->pos, m);
-  memcpy(ctx->xf.rfc, m, sizeof(m));
-  ctx->sp = computeSamplerParams(cam->width, cam->height);
-  textureFootprint(*cam, ctx->surf.texFoot);
-  ctx->haveCamera = true;
-  return DMT_OK;
-}
-
 int dmt_set_limits(dmt_ctx* ctx, int max_depth) {
   if (!ctx) return DMT_ERR_INVALID;
   if (max_depth < 0) return fail(ctx, DMT_ERR_INVALID, "dmt_set_limits: max_depth < 0");
@@ -2501,45 +2168,6 @@ int dmt_set_stream(dmt_ctx* ctx, void* hip_stream) {
   if (!ctx) return DMT_ERR_INVALID;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->ownStream;
-  return DMT_OK;
-}
-
-int dmt_film_clear(dmt_ctx* ctx) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->d_mean) return fail(ctx, DMT_ERR_STATE, "dmt_film_clear: no film (call dmt_set_camera first)");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t const bytes = size_t(ctx->filmW) * size_t(ctx->filmH) * sizeof(float4);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_mean, 0, bytes, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_m2, 0, bytes, ctx->stream));
-  return DMT_OK;
-}
-
-int dmt_film_bind(dmt_ctx* ctx, void* d_mean, void* d_m2) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_film_bind: call dmt_set_camera first");
-  if (!d_mean || !d_m2) return fail(ctx, DMT_ERR_INVALID, "dmt_film_bind: null buffer");
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->ownMean.reset(), ctx->ownM2.reset();
-  ctx->d_mean = static_cast<float4*>(d_mean);
-  ctx->d_m2 = static_cast<float4*>(d_m2);
-  return DMT_OK;
-}
-
-int dmt_film_device_ptrs(dmt_ctx* ctx, void** d_mean, void** d_m2) {
-  if (!ctx || !d_mean || !d_m2) return DMT_ERR_INVALID;
-  *d_mean = ctx->d_mean, *d_m2 = ctx->d_m2;
-  return DMT_OK;
-}
-
-int dmt_download_film(dmt_ctx* ctx, float* mean4, float* m24) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->d_mean) return fail(ctx, DMT_ERR_STATE, "dmt_download_film: no film");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t const bytes = size_t(ctx->filmW) * size_t(ctx->filmH) * sizeof(float4);
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (int const rc = checkErrorFlag(ctx)) return rc;
-  if (mean4) HIP_TRY(ctx, hipMemcpy(mean4, ctx->d_mean, bytes, hipMemcpyDeviceToHost));
-  if (m24) HIP_TRY(ctx, hipMemcpy(m24, ctx->d_m2, bytes, hipMemcpyDeviceToHost));
   return DMT_OK;
 }
 
@@ -2565,288 +2193,6 @@ extern "C" int dmt_diag_section_cycles(unsigned long long* out16, int reset) {
   return e == hipSuccess ? 0 : -1;
 }
 #endif
-
-int dmt_brute_cull_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
-                        uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_sphere) {
-  if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
-  std::vector<float> radii;
-  std::vector<CullCluster> const cl = planBruteCull(xs, ys, zs, mat_id, uint32_t(count), enable != 0, &radii);
-  *cluster_count = uint32_t(cl.size());
-  for (size_t k = 0; k < cl.size(); ++k) {
-    if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
-    if (cluster_sphere) cluster_sphere[4 * k] = cl[k].b[0], cluster_sphere[4 * k + 1] = cl[k].b[1], cluster_sphere[4 * k + 2] = cl[k].b[2],
-                        cluster_sphere[4 * k + 3] = radii[k];
-  }
-  return DMT_OK;
-}
-
-// cluster_box: the planner's inflated boxes (lo xyz, hi xyz); cluster_record: what the device reads (centre xyz, half-width xyz)
-static int cullBoxPlan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
-                       uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box, float* cluster_record) {
-  if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
-  std::vector<CullCluster> cl;
-  std::vector<float> planBox;
-  if (enable && count < kCullMaxIndex) {
-    std::vector<CullCluster> const spheres = planBruteCull(xs, ys, zs, mat_id, uint32_t(count), true, nullptr);
-    cl = planBruteCullBox(xs, ys, zs, mat_id, uint32_t(count), spheres, &planBox);
-  }
-  *cluster_count = uint32_t(cl.size());
-  for (size_t k = 0; k < cl.size(); ++k) {
-    if (cluster_first_count) cluster_first_count[2 * k] = cl[k].first, cluster_first_count[2 * k + 1] = cl[k].count;
-    for (int a = 0; a < 6; ++a) {
-      if (cluster_box) cluster_box[6 * k + size_t(a)] = planBox[6 * k + size_t(a)];
-      if (cluster_record) cluster_record[6 * k + size_t(a)] = cl[k].b[a];
-    }
-  }
-  return DMT_OK;
-}
-
-int dmt_brute_cull_box_plan(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
-                            uint32_t* cluster_count, uint32_t* cluster_first_count, float* cluster_box) {
-  return cullBoxPlan(xs, ys, zs, mat_id, count, enable, cluster_count, cluster_first_count, cluster_box, nullptr);
-}
-
-int dmt_brute_cull_box_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int enable,
-                               uint32_t* cluster_count, float* cluster_box, float* cluster_record) {
-  return cullBoxPlan(xs, ys, zs, mat_id, count, enable, cluster_count, nullptr, cluster_box, cluster_record);
-}
-
-int dmt_cull_records(const float* xs, const float* ys, const float* zs, const uint32_t* mat_id, size_t count, int level,
-                     uint32_t* cluster_count, uint32_t* record_bytes, uint32_t* record_align, void* records) {
-  if ((count && (!xs || !ys || !zs || !mat_id)) || count > 0x7FFFFFFFu || !cluster_count) return DMT_ERR_INVALID;
-  std::vector<CullCluster> const cl = planCullClusters(level, xs, ys, zs, mat_id, count);
-  *cluster_count = uint32_t(cl.size());
-  if (record_bytes) *record_bytes = uint32_t(sizeof(CullCluster));
-  if (record_align) *record_align = uint32_t(alignof(CullCluster));
-  if (records && !cl.empty()) memcpy(records, cl.data(), cl.size() * sizeof(CullCluster));
-  return DMT_OK;
-}
-
-// The device's box bound test on the host, ray by ray: cull_ray, cull_box_axis and cull_box_accept as brute_clusters calls
-// them, with a division where the device has v_rcp_f32 (within 1 ulp of it) and denormals kept.
-int dmt_cull_box_test(const float* record6, const float* origins, const float* dirs, const float* tmax, size_t count, uint8_t* accept) {
-  if (!record6 || (count && (!origins || !dirs || !tmax || !accept))) return DMT_ERR_INVALID;
-  for (size_t i = 0; i < count; ++i) {
-    float const* const o = origins + 3 * i;
-    float const* const d = dirs + 3 * i;
-    CullRay<float> const cr = cull_ray(o[0], o[1], o[2], 1.0f / cull_dir(d[0]), 1.0f / cull_dir(d[1]), 1.0f / cull_dir(d[2]));
-    float nx, ny, nz, fx, fy, fz;
-    cull_box_axis(record6[0], record6[3], cr.ax, cr.rx, cr.bx, nx, fx);
-    cull_box_axis(record6[1], record6[4], cr.ay, cr.ry, cr.by, ny, fy);
-    cull_box_axis(record6[2], record6[5], cr.az, cr.rz, cr.bz, nz, fz);
-    accept[i] = cull_box_accept(nx, ny, nz, fx, fy, fz, tmax[i] * kCullTSlack, cr.e2) ? 1 : 0;
-  }
-  return DMT_OK;
-}
-
-// ---- thin lens ------------------------------------------------------------------------
-int dmt_set_lens(dmt_ctx* ctx, float lens_radius, float focus_distance) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!std::isfinite(lens_radius) || lens_radius < 0.f) return fail(ctx, DMT_ERR_INVALID, "dmt_set_lens: the radius must be finite and >= 0");
-  if (lens_radius > 0.f && !(std::isfinite(focus_distance) && focus_distance > 0.f))
-    return fail(ctx, DMT_ERR_INVALID, "dmt_set_lens: the focus distance must be finite and > 0");
-  ctx->lensR = lens_radius;
-  if (lens_radius > 0.f) ctx->lensD = focus_distance;  // radius 0: the distance is ignored
-  return DMT_OK;
-}
-
-int dmt_lens_info(dmt_ctx* ctx, float* lens_radius, float* focus_distance) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (lens_radius) *lens_radius = ctx->lensR;
-  if (focus_distance) *focus_distance = ctx->lensD;
-  return DMT_OK;
-}
-
-// The host's camera ray through the continuous film position (fx, fy): camera_ray_jittered and camera_ray_lens in plain
-// fp32 without contraction, with the host's division, square root, sine and cosine where the device has its own.
-static void hostCameraRay(CameraXf const& xf, float fx, float fy, float lensR, float focusD, LensU u, float* o3, float* d3) {
-#pragma clang fp contract(off)
-  float d[3];
-  if (lensR > 0.f) {
-    // sample_uniform_disk (pt_device.hpp), the reference's branches
-    float const a = 2.f * u.x - 1.f, b = 2.f * u.y - 1.f;
-    float lx = 0.f, ly = 0.f;
-    if (!(a == 0.f && b == 0.f)) {
-      float rho, phi;
-      if (std::fabs(a) > std::fabs(b))
-        rho = a, phi = (kPi / 4) * (b / a);
-      else
-        rho = b, phi = (3 * kPi / 4) * (a / b);
-      lx = rho * std::cos(phi), ly = rho * std::sin(phi);
-    }
-    lens_ray_parts(xf.cfr, xf.rfc, fx, fy, focusD, lensR * lx, lensR * ly, o3, d);
-  } else {  // xf_point / xf_dir of camera_ray_jittered (both matrices affine: w == 1)
-    float const* const c = xf.cfr;
-    float const* const m = xf.rfc;
-    float const cx = c[0] * fx + c[4] * fy + c[8] * 0.0f + c[12];
-    float const cy = c[1] * fx + c[5] * fy + c[9] * 0.0f + c[13];
-    float const cz = c[2] * fx + c[6] * fy + c[10] * 0.0f + c[14];
-    for (int i = 0; i < 3; ++i) {
-      o3[i] = m[i] * 0.f + m[4 + i] * 0.f + m[8 + i] * 0.f + m[12 + i];
-      d[i] = m[i] * cx + m[4 + i] * cy + m[8 + i] * cz;
-    }
-  }
-  float const inv = 1.0f / std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  d3[0] = d[0] * inv, d3[1] = d[1] * inv, d3[2] = d[2] * inv;
-}
-static CameraXf hostCameraXf(dmt_camera const& cam) {
-  CameraXf xf{};
-  cameraFromRaster(cam.focal_length, cam.sensor_size, uint32_t(cam.width), uint32_t(cam.height), xf.cfr);
-  worldFromCamera(cam.dir, cam.pos, xf.rfc);
-  return xf;
-}
-
-int dmt_lens_rays(const dmt_camera* cam, float lens_radius, float focus_distance, int n, const int32_t* pxs, const int32_t* pys,
-                  const int32_t* ss, float* o3, float* d3, float* lens2) {
-  if (!cam || n < 0 || cam->width <= 0 || cam->height <= 0 || cam->width > 65536 || cam->height > 65536) return DMT_ERR_INVALID;
-  if (n && (!pxs || !pys || !ss || !o3 || !d3 || !lens2)) return DMT_ERR_INVALID;
-  if (!std::isfinite(lens_radius) || lens_radius < 0.f) return DMT_ERR_INVALID;
-  if (lens_radius > 0.f && !(std::isfinite(focus_distance) && focus_distance > 0.f)) return DMT_ERR_INVALID;
-  CameraXf const xf = hostCameraXf(*cam);
-  SamplerParams const sp = computeSamplerParams(cam->width, cam->height);
-  int64_t const stride = int64_t(sp.scale0) * sp.scale1;
-  for (int i = 0; i < n; ++i) {
-    if (pxs[i] < 0 || pys[i] < 0 || pxs[i] >= cam->width || pys[i] >= cam->height || ss[i] < 0 ||
-        (int64_t(ss[i]) + 1) * stride > 0x7FFFFFFFll)
-      return DMT_ERR_INVALID;  // outside the frame, or the sample overflows the 32-bit Halton index
-  }
-  for (int i = 0; i < n; ++i) {
-    int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * int32_t(stride);
-    LensU const u = lens_values(uint32_t(h));
-    lens2[2 * size_t(i)] = u.x, lens2[2 * size_t(i) + 1] = u.y;
-    f2 const r = pixel2d(sp, h);
-    float const fx = ((r.x - 0.5f) + 0.5f) + float(pxs[i]);  // as camera_ray_jittered
-    float const fy = ((r.y - 0.5f) + 0.5f) + float(pys[i]);
-    hostCameraRay(xf, fx, fy, lens_radius, focus_distance, u, o3 + 3 * size_t(i), d3 + 3 * size_t(i));
-  }
-  return DMT_OK;
-}
-
-int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
-#pragma clang fp contract(off)
-  if (!ctx || !distance || !std::isfinite(fx) || !std::isfinite(fy)) return DMT_ERR_INVALID;
-  if (!(ctx->haveTris && ctx->haveCamera)) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: upload triangles and set the camera first");
-  float o[3], d[3];
-  hostCameraRay(ctx->xf, fx, fy, 0.f, 1.f, LensU{0.f, 0.f}, o, d);
-  int32_t tri = -1;
-  float t = 0.f;
-  if (int const rc = dmt_test_closest_hit(ctx, 1, o, d, &tri, &t)) return rc;  // the context's accel mode; synchronous
-  if (tri < 0) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: the ray leaves the scene");
-  float const* const m = ctx->xf.rfc;  // column 2 = the viewing direction
-  *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
-  return DMT_OK;
-}
-
-// ---- pixel filter ---------------------------------------------------------------------
-// The filter's 1-D profile over w = x / radius in [-1, 1], integrated in float64 (each kind has a closed-form integral) and
-// normalised to F(-1) = 0, F(1) = 1.  False for arguments dmt_set_pixel_filter refuses.
-static bool pixelFilterArgsOk(int kind, float radius, float param) {
-  if (kind < DMT_FILTER_BOX || kind > DMT_FILTER_BLACKMAN_HARRIS) return false;
-  if (!std::isfinite(radius) || !(radius > 0.f) || radius > 8.f) return false;
-  if (kind == DMT_FILTER_GAUSSIAN && !(std::isfinite(param) && param > 0.f)) return false;
-  return true;
-}
-static double pixelFilterIntegral(int kind, double sigmaW, double w) {  // unnormalised, from -1 to w
-  double const pi = 3.14159265358979323846;
-  switch (kind) {
-    case DMT_FILTER_TENT: return w <= 0.0 ? 0.5 * (1.0 + w) * (1.0 + w) : 1.0 - 0.5 * (1.0 - w) * (1.0 - w);
-    case DMT_FILTER_GAUSSIAN: {  // max(0, G(w) - G(1)), pbrt-v4's; sigmaW = sigma / radius
-      double const a = 1.0 / (sigmaW * std::sqrt(2.0));
-      return sigmaW * std::sqrt(pi / 2.0) * (std::erf(a * w) + std::erf(a)) - std::exp(-0.5 / (sigmaW * sigmaW)) * (w + 1.0);
-    }
-    case DMT_FILTER_BLACKMAN_HARRIS: {  // the four-term window over t = (w + 1) / 2
-      double const t = 0.5 * (w + 1.0);
-      return 2.0 * (0.35875 * t - 0.48829 * std::sin(2.0 * pi * t) / (2.0 * pi) + 0.14128 * std::sin(4.0 * pi * t) / (4.0 * pi) -
-                    0.01168 * std::sin(6.0 * pi * t) / (6.0 * pi));
-    }
-    default: return w + 1.0;  // box
-  }
-}
-// The kFilterKnots knots W(i / 256) of the inverse CDF: bisection on the float64 integral for the lower half, mirrored for
-// the upper one (the profiles are even), rounded to float32 once.  False when the profile has no mass in float64 (a Gaussian
-// whose sigma is so far above the radius that G(w) - G(1) cancels).
-static bool pixelFilterKnots(int kind, float radius, float param, float* knots) {
-  double const sigmaW = kind == DMT_FILTER_GAUSSIAN ? double(param) / double(radius) : 1.0;
-  double const total = pixelFilterIntegral(kind, sigmaW, 1.0);
-  if (!(total > 1e-12) || !std::isfinite(total)) return false;
-  knots[0] = -1.f, knots[128] = 0.f, knots[256] = 1.f;
-  for (int i = 1; i < 128; ++i) {
-    double const target = total * (double(i) / 256.0);
-    double lo = -1.0, hi = 0.0;
-    for (int it = 0; it < 64; ++it) {
-      double const mid = 0.5 * (lo + hi);
-      (pixelFilterIntegral(kind, sigmaW, mid) < target ? lo : hi) = mid;
-    }
-    float k = float(0.5 * (lo + hi));
-    if (k < knots[i - 1]) k = knots[i - 1];  // monotone after the rounding to float32
-    knots[i] = k, knots[256 - i] = -k;
-  }
-  return true;
-}
-static bool pixelFilterIsDefault(int kind, float radius) { return kind == DMT_FILTER_BOX && radius == 0.5f; }
-// what filter_warp reads: per bin the knot and the fp32 difference to the next one
-static void pixelFilterBins(float const* knots, FilterBin* bins) {
-#pragma clang fp contract(off)
-  for (int i = 0; i < kFilterBins; ++i) bins[i] = FilterBin{knots[i], knots[i + 1] - knots[i]};
-}
-
-int dmt_pixel_filter_table(int kind, float radius, float param, float* knots257) {
-  if (!knots257 || !pixelFilterArgsOk(kind, radius, param)) return DMT_ERR_INVALID;
-  return pixelFilterKnots(kind, radius, param, knots257) ? DMT_OK : DMT_ERR_INVALID;
-}
-
-int dmt_set_pixel_filter(dmt_ctx* ctx, int kind, float radius, float param) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (!pixelFilterArgsOk(kind, radius, param))
-    return fail(ctx, DMT_ERR_INVALID,
-                "dmt_set_pixel_filter: a kind DMT_FILTER_BOX .. DMT_FILTER_BLACKMAN_HARRIS, a finite radius in (0, 8], and for the Gaussian a finite sigma > 0");
-  if (!pixelFilterIsDefault(kind, radius)) {
-    float knots[kFilterKnots];
-    if (!pixelFilterKnots(kind, radius, param, knots))
-      return fail(ctx, DMT_ERR_INVALID, "dmt_set_pixel_filter: the Gaussian's sigma is too large for its radius (the profile has no mass)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // a launch in flight may still read the old table
-    FilterBin bins[kFilterBins];
-    pixelFilterBins(knots, bins);
-    HIP_TRY(ctx, ctx->filt.knots.assign(bins, kFilterBins));
-  }
-  ctx->filt.kind = kind, ctx->filt.radius = radius, ctx->filt.param = kind == DMT_FILTER_GAUSSIAN ? param : 0.f;
-  ctx->filt.active = !pixelFilterIsDefault(kind, radius);
-  return DMT_OK;
-}
-
-int dmt_pixel_filter_info(dmt_ctx* ctx, int* kind, float* radius, float* param, int* active) {
-  if (!ctx) return DMT_ERR_INVALID;
-  if (kind) *kind = ctx->filt.kind;
-  if (radius) *radius = ctx->filt.radius;
-  if (param) *param = ctx->filt.param;
-  if (active) *active = ctx->filt.active ? 1 : 0;
-  return DMT_OK;
-}
-
-int dmt_pixel_filter_positions(int width, int height, int kind, float radius, float param, int n, const int32_t* pxs, const int32_t* pys,
-                               const int32_t* ss, float* xy2) {
-  if (n < 0 || width <= 0 || height <= 0 || width > 65536 || height > 65536 || !pixelFilterArgsOk(kind, radius, param)) return DMT_ERR_INVALID;
-  if (n && (!pxs || !pys || !ss || !xy2)) return DMT_ERR_INVALID;
-  float knots[kFilterKnots];
-  bool const active = !pixelFilterIsDefault(kind, radius);
-  if (active && !pixelFilterKnots(kind, radius, param, knots)) return DMT_ERR_INVALID;
-  FilterBin bins[kFilterBins];
-  if (active) pixelFilterBins(knots, bins);
-  SamplerParams const sp = computeSamplerParams(width, height);
-  int64_t const stride = int64_t(sp.scale0) * sp.scale1;
-  for (int i = 0; i < n; ++i) {
-    if (pxs[i] < 0 || pys[i] < 0 || pxs[i] >= width || pys[i] >= height || ss[i] < 0 || (int64_t(ss[i]) + 1) * stride > 0x7FFFFFFFll)
-      return DMT_ERR_INVALID;  // outside the frame, or the sample overflows the 32-bit Halton index
-  }
-  for (int i = 0; i < n; ++i) {
-    int32_t const h = halton_pixel_base(sp, pxs[i], pys[i]) + ss[i] * int32_t(stride);
-    f2 r = pixel2d(sp, h);
-    if (active) r = f2{filter_warp(bins, radius, r.x), filter_warp(bins, radius, r.y)};
-    xy2[2 * size_t(i)] = film_coord(r.x, pxs[i]), xy2[2 * size_t(i) + 1] = film_coord(r.y, pys[i]);
-  }
-  return DMT_OK;
-}
 
 }  // extern "C"
 

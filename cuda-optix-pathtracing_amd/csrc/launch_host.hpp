@@ -5,7 +5,8 @@
 //
 // Part of dmt_hip.hip's translation unit, included once after surface_host.hpp and baseParams and before
 // denoise_host.hpp: it uses resolveFeatures, checkFeatures, baseParams, requireTree, reserveOverflow, bvhView and
-// motionParams, and denoise_host.hpp, probes.hpp and dmt_download_film call checkErrorFlag.
+// motionParams and SceneState::matIdOutside; denoise_host.hpp and probes.hpp call checkErrorFlag, and camera_host.hpp's
+// dmt_download_film reaches it through a forward declaration.
 #pragma once
 
 namespace {
@@ -76,7 +77,7 @@ int checkErrorFlag(dmt_ctx* ctx) {
 
 // ---- what renderImpl and dmt_render_adaptive ask first, each under its own name --------------------
 int requireScene(dmt_ctx* ctx, char const* caller) {
-  if (ctx->haveTris && ctx->haveBsdfs && ctx->lights.list.have && ctx->haveCamera) return DMT_OK;
+  if (ctx->scene.haveTris && ctx->scene.haveBsdfs && ctx->lights.list.have && ctx->camera.have) return DMT_OK;
   ctx->err = std::string(caller) + ": upload triangles, bsdfs, lights and set the camera first";
   return DMT_ERR_STATE;
 }
@@ -88,7 +89,7 @@ struct TileGrid {
   int tx0 = 0, ty0 = 0, rtx = 0;   // origin (in tiles) and tiles per row
   uint32_t tiles = 0, owned = 0;
   TileGrid(dmt_ctx const* c, int ax0, int ay0, int ax1, int ay1)
-      : x0(std::max(ax0, 0)), y0(std::max(ay0, 0)), x1(std::min(ax1, c->filmW)), y1(std::min(ay1, c->filmH)), rank(c->launch.rank), world(c->launch.world) {
+      : x0(std::max(ax0, 0)), y0(std::max(ay0, 0)), x1(std::min(ax1, c->film.w)), y1(std::min(ay1, c->film.h)), rank(c->launch.rank), world(c->launch.world) {
     if (empty()) return;
     tx0 = x0 / 8, ty0 = y0 / 8, rtx = (x1 + 7) / 8 - tx0;
     tiles = uint32_t(rtx) * uint32_t((y1 + 7) / 8 - ty0);
@@ -240,8 +241,8 @@ int planLaunch(dmt_ctx* ctx, uint32_t F, TileGrid const& G, uint32_t spp, bool c
   // Sampler table: for plain megakernel launches only.  Counting launches are not timed, the wavefront form prepares its
   // samples per pass, and an adaptive round's live pixel count is on the device.  The owned pixels are counted in whole tiles.
   if (!counting && !L.wavefront && !sel && !(F & kFeatMotion))  // (motion launches compute their samples: the table has no time plane)
-    L.tab = samplerTablePlan(ctx->filmW, ctx->filmH, uint64_t(G.owned) * 64u, spp, L.chunkSpp, S.tab.budget, S.tab.mode,
-                             ctx->lensR > 0.f ? kSamTabLensEntryBytes : kSamTabEntryBytes);
+    L.tab = samplerTablePlan(ctx->film.w, ctx->film.h, uint64_t(G.owned) * 64u, spp, L.chunkSpp, S.tab.budget, S.tab.mode,
+                             ctx->camera.lensR > 0.f ? kSamTabLensEntryBytes : kSamTabEntryBytes);
   uint32_t const wavesWanted = L.numItems * L.numChunks < L.numItems ? L.numItems : L.numItems * L.numChunks;
   L.blocks = uint32_t(S.cuCount) * uint32_t(L.blocksPerCu);
   uint32_t const blocksNeeded = (wavesWanted + 3) / 4;
@@ -280,7 +281,7 @@ int growLaunchBuffers(dmt_ctx* ctx, LaunchPlan const& L, uint32_t spp, RenderPar
     HIP_TRY(ctx, S.tab.vals.reserve(2 * sliceEntries));
     HIP_TRY(ctx, S.tab.jit.reserve(sliceEntries));
     P.samTab = S.tab.vals.get(), P.samTabJit = S.tab.jit.get(), P.samTabPw = L.tab.pw, P.samTabPh = L.tab.ph;
-    if (ctx->lensR > 0.f) {
+    if (ctx->camera.lensR > 0.f) {
       HIP_TRY(ctx, S.tab.lens.reserve(sliceEntries));
       P.samTabLens = S.tab.lens.get();
     } else {
@@ -320,8 +321,8 @@ int enqueueLaunch(dmt_ctx* ctx, LaunchPlan const& L, TileGrid const& G, uint32_t
                   TileSelection const* sel) {
   LaunchState& S = ctx->launch;
   RenderParams P = baseParams(ctx, 0);
-  P.mean = ctx->d_mean, P.m2 = ctx->d_m2, P.counter = S.sched.counter.get();
-  P.width = ctx->filmW, P.height = ctx->filmH;
+  P.mean = ctx->film.mean, P.m2 = ctx->film.m2, P.counter = S.sched.counter.get();
+  P.width = ctx->film.w, P.height = ctx->film.h;
   G.put(P);
   P.numItems = L.numItems, P.subShift = L.subShift, P.chunkSpp = L.chunkSpp, P.numChunks = L.numChunks;
   P.sampleOffset = sample_offset, P.spp = spp;
@@ -372,11 +373,11 @@ int renderImpl(dmt_ctx* ctx, uint32_t sample_offset, uint32_t spp, int x0, int y
   if (stats6) memset(stats6, 0, size_t(nstats) * sizeof(uint64_t));
   if (int const rc = requireScene(ctx, "dmt_render")) return rc;
   // the Halton index sample * stride must stay inside int32 (CC/private/rng.cu:229)
-  uint64_t const stride = uint64_t(ctx->sp.scale0) * uint64_t(ctx->sp.scale1);
+  uint64_t const stride = uint64_t(ctx->camera.sp.scale0) * uint64_t(ctx->camera.sp.scale1);
   if ((uint64_t(sample_offset) + spp + 1) * stride > 0x7FFFFFFFull)
     return fail(ctx, DMT_ERR_INVALID, "dmt_render: sample index overflows the 32-bit Halton index");
   // every material index must address an uploaded BSDF (the kernel gathers bsdfs[matId])
-  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
+  if (ctx->scene.matIdOutside())
     return fail(ctx, DMT_ERR_INVALID, "dmt_render: a triangle's material index is outside the BSDF array");
   TileGrid const G(ctx, x0, y0, x1, y1);
   if (spp == 0 || G.empty()) return DMT_OK;
@@ -416,11 +417,11 @@ int dmt_render_adaptive(dmt_ctx* ctx, uint32_t min_spp, uint32_t max_spp, uint32
   if (G.owned == 0) return DMT_OK;
   LaunchState::Adaptive& ad = ctx->launch.adaptive;
   AdaptiveArgs A{};
-  A.mean = ctx->d_mean, A.m2 = ctx->d_m2, A.width = ctx->filmW;
+  A.mean = ctx->film.mean, A.m2 = ctx->film.m2, A.width = ctx->film.w;
   G.put(A);
   A.owned = G.owned;
   A.minSpp = min_spp, A.maxSpp = max_spp, A.threshold = threshold;
-  size_t const filmTiles = size_t((ctx->filmW + 7) / 8) * size_t((ctx->filmH + 7) / 8);  // >= tiles of any region
+  size_t const filmTiles = size_t((ctx->film.w + 7) / 8) * size_t((ctx->film.h + 7) / 8);  // >= tiles of any region
   HIP_TRY(ctx, ad.mask.reserve(filmTiles));
   HIP_TRY(ctx, ad.list.reserve(filmTiles));
   HIP_TRY(ctx, ad.count.reserve(2));

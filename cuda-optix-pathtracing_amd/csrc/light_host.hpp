@@ -4,7 +4,8 @@
 // fall-back, which calls drain the stream -- are in light_state.hpp; the trees themselves in light_tree.hpp and
 // light_tree_ref.hpp, the env map's tables and device code in envmap.hpp.
 //
-// Part of dmt_hip.hip's translation unit, included once after the host helpers it uses (dmt_ctx, HIP_TRY, fail) and before
+// Part of dmt_hip.hip's translation unit, included once after the host helpers it uses (dmt_ctx with SceneState's host copy
+// of the soup, HIP_TRY, fail) and before
 // launch_host.hpp and probes.hpp: resolveFeatures (dmt_hip.hip) calls ensureLightTree ahead of every launch and of
 // dmt_test_light_tree.
 #pragma once
@@ -137,7 +138,7 @@ int ensureEmitterTree(dmt_ctx* ctx) {
   SurfaceState::Emissive const& area = ctx->surf.area;
   emitter_tree::Tree tree;
   auto const t0 = std::chrono::steady_clock::now();
-  if (!buildEmitterTree(ctx->lights.list.host.data(), ctx->lights.list.count, ctx->h_xs.data(), ctx->h_ys.data(), ctx->h_zs.data(), ctx->triCount,
+  if (!buildEmitterTree(ctx->lights.list.host.data(), ctx->lights.list.count, ctx->scene.h_xs.data(), ctx->scene.h_ys.data(), ctx->scene.h_zs.data(), ctx->scene.triCount,
                         area.hostTri.data(), area.hostLe.data(), area.count, tree))
     return fail(ctx, DMT_ERR_STATE, "emitter tree: only point and spot lights can be in the light list");
   E.buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

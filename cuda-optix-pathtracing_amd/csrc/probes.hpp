@@ -3,7 +3,8 @@
 //
 // Part of dmt_hip.hip's translation unit, included once at its end: it uses the device code, dmt_ctx, HIP_TRY, fail,
 // baseParams, resolveFeatures / kernelOf and finishTest defined there, accel_host.hpp's requireTree, reserveOverflow and
-// motionParams, surface_host.hpp's firstHitVariant, and denoise_host.hpp's makeProjXf.  A probe: a kernel with one lane per case, an entry point staging its arrays (probe_stage.hpp).
+// motionParams, surface_host.hpp's firstHitVariant, camera_host.hpp's computeSamplerParams, CameraState::extra,
+// SceneState::matIdOutside, and denoise_host.hpp's makeProjXf.  A probe: a kernel with one lane per case, an entry point staging its arrays (probe_stage.hpp).
 #pragma once
 
 #include "probe_stage.hpp"
@@ -556,9 +557,9 @@ int finishProbe(dmt_ctx* ctx, Probe& p) {
 // What the probes that walk the uploaded scene check first, reported under the entry point's name `who`: the whole scene
 // and the camera set (wholeScene), and every material index inside the BSDF array.
 int sceneReady(dmt_ctx* ctx, char const* who, bool wholeScene) {
-  if (wholeScene && !(ctx->haveTris && ctx->haveBsdfs && ctx->lights.list.have && ctx->haveCamera))
+  if (wholeScene && !(ctx->scene.haveTris && ctx->scene.haveBsdfs && ctx->lights.list.have && ctx->camera.have))
     return fail(ctx, DMT_ERR_STATE, (std::string(who) + ": scene/camera not set").c_str());
-  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount)
+  if (ctx->scene.matIdOutside())
     return fail(ctx, DMT_ERR_INVALID, (std::string(who) + ": material index outside the BSDF array").c_str());
   return DMT_OK;
 }
@@ -615,7 +616,7 @@ int dmt_test_sampler_table(dmt_ctx* ctx, int width, int height, uint32_t s0, uin
   ProbeOut<float2> dj(p, out_jitter, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
   hipLaunchKernelGGL(k_sampler_table, dim3(p.blocks(256)), dim3(256), 0, ctx->stream, sp, s0, n, pw, ph, dv.get(), dj.get(),
-                     static_cast<float2*>(nullptr), ctx->filt.view(), ctx->filt.radius);  // the lens-free table; the jitter warped under a pixel filter
+                     static_cast<float2*>(nullptr), ctx->camera.filt.view(), ctx->camera.filt.radius);  // the lens-free table; the jitter warped under a pixel filter
   return finishProbe(ctx, p);
 }
 
@@ -651,52 +652,52 @@ int dmt_test_sampler(dmt_ctx* ctx, int width, int height, int n, const int32_t* 
 
 int dmt_test_camera_rays(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* o3, float* d3) {
   if (!ctx || n < 0 || !pxs || !pys || !ss || !o3 || !d3) return DMT_ERR_INVALID;
-  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_camera_rays: set the camera first");
+  if (!ctx->camera.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_camera_rays: set the camera first");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dO(p, o3, 3), dD(p, d3, 3);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, cameraExtraOf(ctx), n, dpx.get(),
+  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->camera.xf, ctx->camera.sp, ctx->camera.extra(), n, dpx.get(),
                      dpy.get(), dss.get(), dO.get(), dD.get(), static_cast<float*>(nullptr));
   return finishProbe(ctx, p);
 }
 
 int dmt_test_lens_values(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* lens2) {
   if (!ctx || n < 0 || !pxs || !pys || !ss || !lens2) return DMT_ERR_INVALID;
-  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_lens_values: set the camera first");
+  if (!ctx->camera.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_lens_values: set the camera first");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dL(p, lens2, 2);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->xf, ctx->sp, cameraExtraOf(ctx), n, dpx.get(),
+  hipLaunchKernelGGL(k_test_camera, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->camera.xf, ctx->camera.sp, ctx->camera.extra(), n, dpx.get(),
                      dpy.get(), dss.get(), static_cast<float*>(nullptr), static_cast<float*>(nullptr), dL.get());
   return finishProbe(ctx, p);
 }
 
 int dmt_test_film_positions(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* xy2) {
   if (!ctx || n < 0 || !pxs || !pys || !ss || !xy2) return DMT_ERR_INVALID;
-  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_film_positions: set the camera first");
+  if (!ctx->camera.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_film_positions: set the camera first");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dXy(p, xy2, 2);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_film_positions, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->sp, ctx->filt.view(), ctx->filt.radius, n,
+  hipLaunchKernelGGL(k_test_film_positions, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->camera.sp, ctx->camera.filt.view(), ctx->camera.filt.radius, n,
                      dpx.get(), dpy.get(), dss.get(), dXy.get());
   return finishProbe(ctx, p);
 }
 
 int dmt_test_camera_project(dmt_ctx* ctx, int n, const float* p3, float* xy2, float* depth) {
   if (!ctx || n < 0 || !p3 || !xy2 || !depth) return DMT_ERR_INVALID;
-  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_camera_project: set the camera first");
+  if (!ctx->camera.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_camera_project: set the camera first");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<float> dP(p, p3, 3);
   ProbeOut<float> dXy(p, xy2, 2), dD(p, depth, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_project, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, makeProjXf(ctx->cam), n, dP.get(), dXy.get(), dD.get());
+  hipLaunchKernelGGL(k_test_project, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, makeProjXf(ctx->camera.cam), n, dP.get(), dXy.get(), dD.get());
   return finishProbe(ctx, p);
 }
 
@@ -716,12 +717,12 @@ int dmt_test_bsdf_ng(dmt_ctx* ctx, const void* bsdf32, int n, const float* ns3, 
 int dmt_test_material(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const float* ng3, void* rec32,
                       float* ns3, void* rec2_32, float* mix) {
   if (!ctx || n < 0 || !tri || !bu || !bv || !ng3 || !rec32 || !ns3 || !rec2_32 || !mix) return DMT_ERR_INVALID;
-  if (!(ctx->haveTris && ctx->haveBsdfs)) return fail(ctx, DMT_ERR_STATE, "dmt_test_material: triangles and BSDFs first");
+  if (!(ctx->scene.haveTris && ctx->scene.haveBsdfs)) return fail(ctx, DMT_ERR_STATE, "dmt_test_material: triangles and BSDFs first");
   if (int const rc = sceneReady(ctx, "dmt_test_material", false)) return rc;
-  if (!ctx->surf.texturesMatch(ctx->bsdfCount, ctx->triCount))
+  if (!ctx->surf.texturesMatch(ctx->scene.bsdfCount, ctx->scene.triCount))
     return fail(ctx, DMT_ERR_STATE, "dmt_test_material: texture tables do not match the uploaded BSDFs / triangles (upload textures last)");
   for (int i = 0; i < n; ++i)
-    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_material: triangle index out of range");
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->scene.triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_material: triangle index out of range");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<int32_t> dTri(p, tri, 1);
@@ -846,10 +847,10 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
 int dmt_test_texture_filter(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, const float* bv, const int32_t* tex,
                             const int32_t* depth, float* rgb3, int32_t* branch, float* lod) {
   if (!ctx || n < 0 || !tri || !bu || !bv || !tex || !depth || !rgb3 || !branch || !lod) return DMT_ERR_INVALID;
-  if (!(ctx->haveTris && ctx->haveCamera) || ctx->surf.tex.count == 0 || ctx->surf.tex.triUvCount != ctx->triCount)
+  if (!(ctx->scene.haveTris && ctx->camera.have) || ctx->surf.tex.count == 0 || ctx->surf.tex.triUvCount != ctx->scene.triCount)
     return fail(ctx, DMT_ERR_STATE, "dmt_test_texture_filter: triangles, camera and textures (with one UV triple per triangle) first");
   for (int i = 0; i < n; ++i)
-    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount || tex[i] < 0 || uint32_t(tex[i]) >= ctx->surf.tex.count)
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->scene.triCount || tex[i] < 0 || uint32_t(tex[i]) >= ctx->surf.tex.count)
       return fail(ctx, DMT_ERR_INVALID, "dmt_test_texture_filter: triangle or texture index out of range");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
@@ -882,7 +883,7 @@ int dmt_test_trace_log(dmt_ctx* ctx, int px, int py, int s, float* rec12, int ca
 
 int dmt_test_closest_hit(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, int32_t* tri_index, float* t) {
   if (!ctx || nrays < 0 || !o3 || !d3 || !tri_index || !t) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit: upload triangles first");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit: upload triangles first");
   if (nrays == 0) return DMT_OK;
   Probe p(ctx->device, size_t(nrays));
   ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3);
@@ -902,7 +903,7 @@ int dmt_test_closest_hit(dmt_ctx* ctx, int nrays, const float* o3, const float* 
 int dmt_test_trace_pair(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* so3, const float* sd3, const float* smax,
                         int32_t* tri_index, float* uv2, uint8_t* occluded) {
   if (!ctx || nrays < 0 || !o3 || !d3 || !so3 || !sd3 || !smax || !tri_index || !uv2 || !occluded) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_pair: upload triangles first");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_trace_pair: upload triangles first");
   if (nrays == 0) return DMT_OK;
   Probe p(ctx->device, size_t(nrays));
   ProbeIn<float> dO(p, o3, 3), dD(p, d3, 3), dSO(p, so3, 3), dSD(p, sd3, 3), dM(p, smax, 1);
@@ -923,7 +924,7 @@ int dmt_test_trace_pair(dmt_ctx* ctx, int nrays, const float* o3, const float* d
 int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* time, int32_t* tri_index, float* t,
                             float* uv2) {
   if (!ctx || nrays < 0 || !o3 || !d3 || !time || !tri_index || !t) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: upload triangles first");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: upload triangles first");
   if (!ctx->ac.haveMotion) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_at: no key 1 (dmt_set_motion first)");
   for (int i = 0; i < nrays; ++i)
     if (!std::isfinite(time[i])) return fail(ctx, DMT_ERR_INVALID, "dmt_test_closest_hit_at: a time is not finite");
@@ -944,15 +945,15 @@ int dmt_test_closest_hit_at(dmt_ctx* ctx, int nrays, const float* o3, const floa
 
 static int probeShadingNormal(dmt_ctx* ctx, bool mapped, int n, const int32_t* tri, const float* bu, const float* bv, const float* rd3, float* ns3) {
   if (!ctx || n < 0 || !tri || !bu || !bv || !rd3 || !ns3) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: upload triangles first");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: upload triangles first");
   if (!ctx->surf.vn.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal: no vertex normals (dmt_upload_vertex_normals first)");
   if (mapped) {
     if (int const rc = sceneReady(ctx, "dmt_test_shading_normal_mapped", false)) return rc;
-    if (!ctx->haveBsdfs || ctx->surf.tex.count == 0 || !ctx->surf.texturesMatch(ctx->bsdfCount, ctx->triCount))
+    if (!ctx->scene.haveBsdfs || ctx->surf.tex.count == 0 || !ctx->surf.texturesMatch(ctx->scene.bsdfCount, ctx->scene.triCount))
       return fail(ctx, DMT_ERR_STATE, "dmt_test_shading_normal_mapped: BSDFs and textures (matching the uploaded BSDFs / triangles) first");
   }
   for (int i = 0; i < n; ++i)
-    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_shading_normal: triangle index out of range");
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->scene.triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_shading_normal: triangle index out of range");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<int32_t> dTri(p, tri, 1);
@@ -974,7 +975,7 @@ int dmt_test_opacity(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, c
   if (!ctx || n < 0 || !tri || !bu || !bv || !alpha8 || !pass) return DMT_ERR_INVALID;
   if (!ctx->surf.op.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_opacity: no opacity (dmt_upload_opacity first)");
   for (int i = 0; i < n; ++i)
-    if (tri[i] < 0 || size_t(tri[i]) >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_opacity: triangle index out of range");
+    if (tri[i] < 0 || size_t(tri[i]) >= ctx->scene.triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_test_opacity: triangle index out of range");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<int32_t> dTri(p, tri, 1);
@@ -990,7 +991,7 @@ int dmt_test_opacity(dmt_ctx* ctx, int n, const int32_t* tri, const float* bu, c
 int dmt_test_closest_hit_opacity(dmt_ctx* ctx, int nrays, const float* o3, const float* d3, const float* tmax, int32_t* tri_index, float* t,
                                  float* uv2, uint8_t* occluded) {
   if (!ctx || nrays < 0 || !o3 || !d3 || !tmax || !tri_index || !t) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: upload triangles first");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: upload triangles first");
   if (!ctx->surf.op.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_closest_hit_opacity: no opacity (dmt_upload_opacity first)");
   if (nrays == 0) return DMT_OK;
   Probe p(ctx->device, size_t(nrays));
@@ -1078,13 +1079,13 @@ int dmt_test_medium_spectrum(dmt_ctx* ctx, const float* k3, int n, const float* 
 
 int dmt_test_shutter_times(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_t* pys, const int32_t* ss, float* t) {
   if (!ctx || n < 0 || !pxs || !pys || !ss || !t) return DMT_ERR_INVALID;
-  if (!ctx->haveCamera) return fail(ctx, DMT_ERR_STATE, "dmt_test_shutter_times: set the camera first");
+  if (!ctx->camera.have) return fail(ctx, DMT_ERR_STATE, "dmt_test_shutter_times: set the camera first");
   if (n == 0) return DMT_OK;
   Probe p(ctx->device, size_t(n));
   ProbeIn<int32_t> dpx(p, pxs, 1), dpy(p, pys, 1), dss(p, ss, 1);
   ProbeOut<float> dT(p, t, 1);
   if (p.err != hipSuccess) return probeError(ctx, p);
-  hipLaunchKernelGGL(k_test_shutter, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->sp, ctx->ac.shutterOpen, ctx->ac.shutterClose, n, dpx.get(),
+  hipLaunchKernelGGL(k_test_shutter, dim3(p.blocks(64)), dim3(64), 0, ctx->stream, ctx->camera.sp, ctx->ac.shutterOpen, ctx->ac.shutterClose, n, dpx.get(),
                      dpy.get(), dss.get(), dT.get());
   return finishProbe(ctx, p);
 }

@@ -2,9 +2,10 @@
 // footprint of the first-hit texture filter, the checks and record builders the uploads share, the chooser of the first-hit
 // kernel variant, and the dmt_* entry points of textures, emissive triangles, vertex normals and opacity records.
 //
-// Part of dmt_hip.hip's translation unit, included once: after the host helpers it uses (dmt_ctx, HIP_TRY, fail,
-// cameraFromRaster, worldFromCamera; vnormals.hpp's packRecords and smoothNormals, opacity.hpp's opacity_alpha8_at) and
-// before denoise_host.hpp, probes.hpp and dmt_set_camera, which call into it (firstHitVariant, textureFootprint).  The
+// Part of dmt_hip.hip's translation unit, included once: after the host helpers it uses (dmt_ctx, HIP_TRY, fail;
+// camera_host.hpp's cameraFromRaster and worldFromCamera; vnormals.hpp's packRecords and smoothNormals, opacity.hpp's
+// opacity_alpha8_at; SceneState::matIdOutside) and before denoise_host.hpp and probes.hpp, which call into it
+// (firstHitVariant); camera_host.hpp's dmt_set_camera reaches textureFootprint through a forward declaration.  The
 // rule for what each upload invalidates is SurfaceState's table; every hipStreamSynchronize here sits in front of a drop or
 // a replace of arrays that a launch in flight may read.
 #pragma once
@@ -157,10 +158,10 @@ int dmt_upload_area_lights(dmt_ctx* ctx, const uint32_t* triangle_index, const f
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   SurfaceState::Emissive& area = ctx->surf.area = SurfaceState::Emissive{};
   ctx->lights.invalidateEmitters();  // the emitter tree was of the old list
-  if (count == 0 || !ctx->haveTris) return DMT_OK;
-  std::vector<uint32_t> of(ctx->triCount, 0xFFFFFFFFu);
+  if (count == 0 || !ctx->scene.haveTris) return DMT_OK;
+  std::vector<uint32_t> of(ctx->scene.triCount, 0xFFFFFFFFu);
   for (uint32_t k = 0; k < count; ++k) {
-    if (triangle_index[k] >= ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "area light refers to a triangle outside the uploaded soup");
+    if (triangle_index[k] >= ctx->scene.triCount) return fail(ctx, DMT_ERR_INVALID, "area light refers to a triangle outside the uploaded soup");
     of[triangle_index[k]] = k;
   }
   HIP_TRY(ctx, area.of.assign(of.data(), of.size()));
@@ -252,8 +253,8 @@ int dmt_texture_footprint(const dmt_camera* cam, float* out) {
 // ---- smooth shading -----------------------------------------------------------------------
 int dmt_upload_vertex_normals(dmt_ctx* ctx, const float* n9, size_t count) {
   if (!ctx) return DMT_ERR_INVALID;
-  if (!ctx->haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_upload_vertex_normals: before any dmt_upload_triangles");
-  if (count != ctx->triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_vertex_normals: count differs from the uploaded triangle count");
+  if (!ctx->scene.haveTris) return fail(ctx, DMT_ERR_STATE, "dmt_upload_vertex_normals: before any dmt_upload_triangles");
+  if (count != ctx->scene.triCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_vertex_normals: count differs from the uploaded triangle count");
   if (count && !n9) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_vertex_normals: null array");
   std::vector<VtxNormalRec> recs;
   SurfaceState::VertexNormals vn;  // adopted at the end
@@ -273,7 +274,7 @@ int dmt_clear_vertex_normals(dmt_ctx* ctx) { return ctx ? clearRecord(ctx, ctx->
 
 int dmt_vertex_normals_info(dmt_ctx* ctx, uint64_t* triangles, uint64_t* smooth_triangles) {
   if (!ctx) return DMT_ERR_INVALID;
-  if (triangles) *triangles = ctx->surf.vn.have ? ctx->triCount : 0u;
+  if (triangles) *triangles = ctx->surf.vn.have ? ctx->scene.triCount : 0u;
   if (smooth_triangles) *smooth_triangles = ctx->surf.vn.smooth;  // a dropped record holds zeros
   return DMT_OK;
 }
@@ -288,20 +289,20 @@ int dmt_smooth_normals(const float* xs, const float* ys, const float* zs, size_t
 int dmt_upload_opacity(dmt_ctx* ctx, const uint32_t* mat_opacity_tex, uint32_t bsdf_count, float cutoff) {
   if (!ctx) return DMT_ERR_INVALID;
   SurfaceState::Textures const& tex = ctx->surf.tex;
-  if (!ctx->haveTris || !ctx->haveBsdfs || tex.count == 0)
+  if (!ctx->scene.haveTris || !ctx->scene.haveBsdfs || tex.count == 0)
     return fail(ctx, DMT_ERR_STATE, "dmt_upload_opacity: upload triangles, BSDFs and textures first");
-  if (tex.triUvCount != ctx->triCount)
+  if (tex.triUvCount != ctx->scene.triCount)
     return fail(ctx, DMT_ERR_STATE, "dmt_upload_opacity: the uploaded textures carry no UV triple per uploaded triangle (upload textures last)");
-  if (!mat_opacity_tex || bsdf_count != ctx->bsdfCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: null array, or count differs from the uploaded BSDF count");
+  if (!mat_opacity_tex || bsdf_count != ctx->scene.bsdfCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: null array, or count differs from the uploaded BSDF count");
   if (!std::isfinite(cutoff) || cutoff < 0.f || cutoff > 1.f) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: the cutoff must be finite and in [0, 1]");
   for (uint32_t b = 0; b < bsdf_count; ++b)
     if (mat_opacity_tex[b] != 0xFFFFFFFFu && mat_opacity_tex[b] >= tex.count)
       return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: a material refers to a texture that does not exist");
-  if (ctx->triCount > 0 && ctx->maxMatId >= ctx->bsdfCount) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: material index outside the BSDF array");
+  if (ctx->scene.matIdOutside()) return fail(ctx, DMT_ERR_INVALID, "dmt_upload_opacity: material index outside the BSDF array");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // launches in flight read the old records
   std::vector<int32_t> desc(3 * size_t(tex.count));
-  std::vector<float> uv(6 * size_t(ctx->triCount));
+  std::vector<float> uv(6 * size_t(ctx->scene.triCount));
   HIP_TRY(ctx, hipMemcpy(desc.data(), tex.desc.get(), desc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (!uv.empty()) HIP_TRY(ctx, hipMemcpy(uv.data(), tex.triUv.get(), uv.size() * sizeof(float), hipMemcpyDeviceToHost));
   SurfaceState::Opacity op;  // counted into, adopted at the end
@@ -312,10 +313,10 @@ int dmt_upload_opacity(dmt_ctx* ctx, const uint32_t* mat_opacity_tex, uint32_t b
     if (desc[3 * size_t(t) + 1] > 65535 || desc[3 * size_t(t) + 2] > 65535)
       return fail(ctx, DMT_ERR_INVALID, ("dmt_upload_opacity: opacity texture " + std::to_string(t) + " is wider or taller than 65535 texels").c_str());
   }
-  std::vector<OpacityRec> recs(ctx->triCount);
-  for (size_t i = 0; i < ctx->triCount; ++i) {
+  std::vector<OpacityRec> recs(ctx->scene.triCount);
+  for (size_t i = 0; i < ctx->scene.triCount; ++i) {
     float const* const q = &uv[6 * i];
-    uint32_t const t = mat_opacity_tex[ctx->h_mat[i]];
+    uint32_t const t = mat_opacity_tex[ctx->scene.h_mat[i]];
     bool const cutout = t != 0xFFFFFFFFu;
     for (int j = 0; cutout && j < 6; ++j)
       if (!std::isfinite(q[j]) || std::fabs(q[j]) > 1048576.f)
