@@ -80,6 +80,7 @@ EXPORTED_SYMBOLS = [
     "dmt_set_sampler_table", "dmt_sampler_table_plan", "dmt_test_sampler_table",
     "dmt_set_lens", "dmt_lens_info", "dmt_lens_rays", "dmt_focus_distance_at", "dmt_test_lens_values",
     "dmt_set_pixel_filter", "dmt_pixel_filter_info", "dmt_pixel_filter_table", "dmt_pixel_filter_positions", "dmt_test_film_positions",
+    "dmt_set_projection", "dmt_projection_info", "dmt_projection_rays", "dmt_projection_project",
     "dmt_set_motion", "dmt_clear_motion", "dmt_set_shutter", "dmt_motion_info", "dmt_shutter_times", "dmt_motion_positions",
     "dmt_motion_bvh_validate", "dmt_test_shutter_times", "dmt_test_closest_hit_at",
     "dmt_upload_vertex_normals", "dmt_clear_vertex_normals", "dmt_vertex_normals_info", "dmt_smooth_normals",
@@ -185,6 +186,54 @@ def lens_rays(camera44, lens_radius, focus_distance, pxs, pys, ss):
     if rc != 0:
         raise DmtError(f"dmt_lens_rays failed ({rc})")
     return o, d, u
+
+
+# dmt_set_projection kinds (include/dmt_hip.h)
+PROJECTION_PERSPECTIVE = 0
+PROJECTION_ORTHOGRAPHIC = 1
+PROJECTION_EQUIRECT = 2
+PROJECTION_FISHEYE = 3
+PROJECTION_KINDS = {"perspective": PROJECTION_PERSPECTIVE, "orthographic": PROJECTION_ORTHOGRAPHIC, "equirect": PROJECTION_EQUIRECT,
+                    "fisheye": PROJECTION_FISHEYE}
+
+
+def _projection_kind(kind, who):
+    if isinstance(kind, str):
+        if kind not in PROJECTION_KINDS:
+            raise DmtError(f"{who}: unsupported projection '{kind}'")
+        return PROJECTION_KINDS[kind]
+    return int(kind)
+
+
+def projection_rays(camera44, kind, param, xy):
+    """Host only (dmt_projection_rays): the rays through the continuous film positions xy [n, 2] of the camera under a
+    projection (kind or its name; param: the orthographic view height or the fisheye's diagonal field of view in degrees)
+    -> (origins [n, 3], directions [n, 3]).  The serial twin of the device code."""
+    lib = load_library()
+    cam = np.ascontiguousarray(camera44, np.uint8).reshape(44)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    n = xy.shape[0]
+    o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = lib.dmt_projection_rays(as_p(cam), _projection_kind(kind, "projection_rays"), C.c_float(param), int(n), as_p(xy), as_p(o), as_p(d))
+    if rc != 0:
+        raise DmtError(f"dmt_projection_rays failed ({rc})")
+    return o, d
+
+
+def projection_project(camera44, kind, param, points):
+    """Host only (dmt_projection_project): render-space points [n, 3] -> (film coordinates [n, 2], depth [n]) under a
+    projection; the depth is the camera-space z for perspective and orthographic, the distance for equirect and fisheye."""
+    lib = load_library()
+    cam = np.ascontiguousarray(camera44, np.uint8).reshape(44)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    xy, depth = np.zeros((p.shape[0], 2), np.float32), np.zeros(p.shape[0], np.float32)
+    as_p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = lib.dmt_projection_project(as_p(cam), _projection_kind(kind, "projection_project"), C.c_float(param), int(p.shape[0]), as_p(p),
+                                    as_p(xy), as_p(depth))
+    if rc != 0:
+        raise DmtError(f"dmt_projection_project failed ({rc})")
+    return xy, depth
 
 
 # dmt_set_pixel_filter kinds (include/dmt_hip.h)
@@ -1066,6 +1115,19 @@ class Renderer:
         self._check(self._lib.dmt_pixel_filter_info(self._ctx, C.byref(k), C.byref(r), C.byref(p), C.byref(a)), "dmt_pixel_filter_info")
         return {"kind": k.value, "radius": r.value, "param": p.value, "active": bool(a.value)}
 
+    def set_projection(self, kind, param=0.0):
+        """Camera projection (dmt_set_projection).  kind: PROJECTION_PERSPECTIVE (the default), PROJECTION_ORTHOGRAPHIC
+        (param = the view height in scene units), PROJECTION_EQUIRECT or PROJECTION_FISHEYE (param = the field of view across
+        the film's diagonal, in degrees), or its name ("perspective", "orthographic", "equirect", "fisheye").  The projection
+        survives set_camera and scene uploads; it is refused while a lens is set."""
+        self._check(self._lib.dmt_set_projection(self._ctx, _projection_kind(kind, "set_projection"), C.c_float(param)), "dmt_set_projection")
+
+    def projection_info(self):
+        """The context's projection as a dict: kind, param."""
+        k, p = C.c_int(), C.c_float()
+        self._check(self._lib.dmt_projection_info(self._ctx, C.byref(k), C.byref(p)), "dmt_projection_info")
+        return {"kind": k.value, "param": p.value}
+
     def focus_distance_at(self, fx, fy):
         """Autofocus (dmt_focus_distance_at): the depth along the viewing direction of what the pinhole ray through the
         continuous film coordinates (fx, fy) hits; DmtError when it leaves the scene."""
@@ -1086,7 +1148,8 @@ class Renderer:
 
     def upload_scene(self, scene, vertex_normals=False, opacity=True, pixel_filter=False):
         """`scene`: any object with xs, ys, zs, mat_id, bsdfs, lights, inf_lights, camera arrays; a scene with a `lens`
-        (lens_radius, focus_distance), as the loaders report one, sets the context's lens too, and one with a `medium`
+        (lens_radius, focus_distance), as the loaders report one, sets the context's lens too, one with a `projection`
+        (kind, param) the context's projection, and one with a `medium`
         (the keyword arguments of set_medium, and the "extinction" and "emission" of set_medium_spectrum) the context's medium.  vertex_normals: also
         upload the scene's `tri_normals` (smooth shading); off by default, the files' normals are not used unasked.
         opacity: upload the scene's `mat_opacity` / `opacity_cutoff` (alpha cutouts) when it carries them.
@@ -1105,8 +1168,15 @@ class Renderer:
         self.upload_bsdfs(scene.bsdfs)
         self.upload_lights(scene.lights, scene.inf_lights)
         self.set_camera(scene.camera)
-        if getattr(scene, "lens", None) is not None:
-            self.set_lens(float(scene.lens[0]), float(scene.lens[1]))
+        # lens and projection exclude each other: a scene that carries both records has the one it leaves at its default set
+        # first, so that a context still holding the last scene's projection takes this scene's lens (and the other way round)
+        lens, proj = getattr(scene, "lens", None), getattr(scene, "projection", None)
+        lens_first = not (lens is not None and float(lens[0]) > 0.0)
+        for which in (("lens", "projection") if lens_first else ("projection", "lens")):
+            if which == "lens" and lens is not None:
+                self.set_lens(float(lens[0]), float(lens[1]))
+            if which == "projection" and proj is not None:
+                self.set_projection(proj[0], float(proj[1]))
         if getattr(scene, "medium", None) is not None:  # a scene file's "medium"; a scene without one leaves the context's
             m = dict(scene.medium)
             e, le = m.pop("extinction", (1.0, 1.0, 1.0)), m.pop("emission", (0.0, 0.0, 0.0))  # its "extinction" and "emission"

@@ -1,17 +1,18 @@
 // camera_host.hpp -- the host side of the camera layer (camera_state.hpp): the one-off camera and sampler set-up math, the
-// host's camera ray, the pixel filter's table, and the dmt_* entry points of the camera, the film, the thin lens and the pixel
-// filter.
+// host's camera ray, the pixel filter's table, the projections' host rays and inverses, and the dmt_* entry points of the
+// camera, the film, the thin lens, the pixel filter and the projection.
 //
 // Part of dmt_hip.hip's translation unit, included once: after dmt_ctx, HIP_TRY and fail, and before accel_host.hpp,
 // surface_host.hpp, denoise_host.hpp and probes.hpp, which use its set-up math (computeSamplerParams, cameraFromRaster,
 // worldFromCamera) and the argument checks it shares with them (resolutionOk, haltonIndices).  The calls the other way are
-// the two forward declarations below and dmt_test_closest_hit (probes.hpp), which dmt_hip.h declares.
+// the three forward declarations below and dmt_test_closest_hit (probes.hpp), which dmt_hip.h declares.
 #pragma once
 
 namespace {
 
 void textureFootprint(dmt_camera const& cam, float out[19]);  // surface_host.hpp
 int checkErrorFlag(dmt_ctx* ctx);                              // launch_host.hpp
+ProjXf makeProjXf(dmt_camera const& cam);                      // denoise_host.hpp
 
 // ---- host math for the one-off camera / sampler setup (IEEE fp32, same expressions as the
 // reference host code: CC/private/extra_math.cu:43-90, CC/private/common_math.cu:16-78,
@@ -125,6 +126,43 @@ void hostCameraRay(CameraXf const& xf, float fx, float fy, float lensR, float fo
       o3[i] = m[i] * 0.f + m[4 + i] * 0.f + m[8 + i] * 0.f + m[12 + i];
       d[i] = m[i] * cx + m[4 + i] * cy + m[8 + i] * cz;
     }
+  }
+  float const inv = 1.0f / std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  d3[0] = d[0] * inv, d3[1] = d[1] * inv, d3[2] = d[2] * inv;
+}
+
+// ---- projections ------------------------------------------------------------------------
+// what dmt_set_projection takes: null, or why it refuses
+char const* projectionArgsError(int kind, float param) {
+  if (kind < DMT_PROJECTION_PERSPECTIVE || kind > DMT_PROJECTION_FISHEYE)
+    return "dmt_set_projection: a kind DMT_PROJECTION_PERSPECTIVE .. DMT_PROJECTION_FISHEYE";
+  if (kind == DMT_PROJECTION_ORTHOGRAPHIC && !(std::isfinite(param) && param > 0.f))
+    return "dmt_set_projection: the orthographic view height must be finite and > 0";
+  if (kind == DMT_PROJECTION_FISHEYE && !(std::isfinite(param) && param > 0.f && param <= 360.f))
+    return "dmt_set_projection: the fisheye field of view must be finite, > 0 and <= 360 degrees";
+  return nullptr;
+}
+// The host's ray through the film position (fx, fy) under a projection: camera_ray_projection's bodies with the host's
+// sine, cosine, division and square root; perspective is hostCameraRay's pinhole ray.
+void hostProjectionRay(dmt_camera const& cam, CameraXf const& xf, int kind, float a, float fx, float fy, float* o3, float* d3) {
+#pragma clang fp contract(off)
+  if (kind == DMT_PROJECTION_PERSPECTIVE) return hostCameraRay(xf, fx, fy, 0.f, 1.f, LensU{0.f, 0.f}, o3, d3);
+  float const W = float(cam.width), H = float(cam.height);
+  float d[3];
+  if (kind == DMT_PROJECTION_ORTHOGRAPHIC) {
+    ortho_ray_parts(xf.cfr, xf.rfc, fx, fy, a, o3, d);
+  } else {
+    float c[3];
+    if (kind == DMT_PROJECTION_EQUIRECT) {
+      float lon, lat;
+      equirect_angles(fx, fy, W, H, lon, lat);
+      equirect_dir(std::sin(lon), std::cos(lon), std::sin(lat), std::cos(lat), c);
+    } else {
+      float ux, uy, theta;
+      fisheye_angle(fx, fy, W, H, a, ux, uy, theta);
+      fisheye_dir(ux, uy, std::sin(theta), std::cos(theta), c);
+    }
+    angular_ray_parts(xf.rfc, c, o3, d);
   }
   float const inv = 1.0f / std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
   d3[0] = d[0] * inv, d3[1] = d[1] * inv, d3[2] = d[2] * inv;
@@ -251,6 +289,8 @@ int dmt_download_film(dmt_ctx* ctx, float* mean4, float* m24) {
 int dmt_set_lens(dmt_ctx* ctx, float lens_radius, float focus_distance) {
   if (!ctx) return DMT_ERR_INVALID;
   if (char const* const why = lensArgsError(lens_radius, focus_distance)) return fail(ctx, DMT_ERR_INVALID, why);
+  if (lens_radius > 0.f && ctx->camera.projKind != DMT_PROJECTION_PERSPECTIVE)
+    return fail(ctx, DMT_ERR_STATE, "dmt_set_lens: only the perspective camera has a lens (dmt_set_projection set another projection)");
   ctx->camera.lensR = lens_radius;
   if (lens_radius > 0.f) ctx->camera.lensD = focus_distance;  // radius 0: the distance is ignored
   return DMT_OK;
@@ -288,6 +328,8 @@ int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
 #pragma clang fp contract(off)
   if (!ctx || !distance || !std::isfinite(fx) || !std::isfinite(fy)) return DMT_ERR_INVALID;
   if (!(ctx->scene.haveTris && ctx->camera.have)) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: upload triangles and set the camera first");
+  if (ctx->camera.projKind != DMT_PROJECTION_PERSPECTIVE)
+    return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: the autofocus ray is the pinhole's (dmt_set_projection set another projection)");
   float o[3], d[3];
   hostCameraRay(ctx->camera.xf, fx, fy, 0.f, 1.f, LensU{0.f, 0.f}, o, d);
   int32_t tri = -1;
@@ -296,6 +338,66 @@ int dmt_focus_distance_at(dmt_ctx* ctx, float fx, float fy, float* distance) {
   if (tri < 0) return fail(ctx, DMT_ERR_STATE, "dmt_focus_distance_at: the ray leaves the scene");
   float const* const m = ctx->camera.xf.rfc;  // column 2 = the viewing direction
   *distance = t * ((d[0] * m[8] + d[1] * m[9]) + d[2] * m[10]);
+  return DMT_OK;
+}
+
+// ---- projections ------------------------------------------------------------------------
+int dmt_set_projection(dmt_ctx* ctx, int kind, float param) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (char const* const why = projectionArgsError(kind, param)) return fail(ctx, DMT_ERR_INVALID, why);
+  if (kind != DMT_PROJECTION_PERSPECTIVE && ctx->camera.lensR > 0.f)
+    return fail(ctx, DMT_ERR_STATE, "dmt_set_projection: a thin lens (dmt_set_lens, radius > 0) is set; only the perspective camera has one");
+  ctx->camera.projKind = kind;
+  ctx->camera.projParam = (kind == DMT_PROJECTION_ORTHOGRAPHIC || kind == DMT_PROJECTION_FISHEYE) ? param : 0.f;
+  return DMT_OK;
+}
+
+int dmt_projection_info(dmt_ctx* ctx, int* kind, float* param) {
+  if (!ctx) return DMT_ERR_INVALID;
+  if (kind) *kind = ctx->camera.projKind;
+  if (param) *param = ctx->camera.projParam;
+  return DMT_OK;
+}
+
+int dmt_projection_rays(const dmt_camera* cam, int kind, float param, int n, const float* xy2, float* o3, float* d3) {
+  if (!cam || n < 0 || !resolutionOk(cam->width, cam->height) || projectionArgsError(kind, param)) return DMT_ERR_INVALID;
+  if (n && (!xy2 || !o3 || !d3)) return DMT_ERR_INVALID;
+  CameraXf const xf = hostCameraXf(*cam);
+  float const a = projectionFactor(*cam, kind, param);
+  for (int i = 0; i < n; ++i)
+    hostProjectionRay(*cam, xf, kind, a, xy2[2 * size_t(i)], xy2[2 * size_t(i) + 1], o3 + 3 * size_t(i), d3 + 3 * size_t(i));
+  return DMT_OK;
+}
+
+int dmt_projection_project(const dmt_camera* cam, int kind, float param, int n, const float* p3, float* xy2, float* depth) {
+#pragma clang fp contract(off)
+  if (!cam || n < 0 || !resolutionOk(cam->width, cam->height) || projectionArgsError(kind, param)) return DMT_ERR_INVALID;
+  if (n && (!p3 || !xy2 || !depth)) return DMT_ERR_INVALID;
+  if (kind == DMT_PROJECTION_PERSPECTIVE) return dmt_camera_project(cam, n, p3, xy2, depth);
+  ProjXf const c = makeProjXf(*cam);
+  float const a = projectionFactor(*cam, kind, param);
+  float const W = float(cam->width), H = float(cam->height);
+  for (int i = 0; i < n; ++i) {
+    float const dx = p3[3 * size_t(i)] - c.pos[0], dy = p3[3 * size_t(i) + 1] - c.pos[1], dz = p3[3 * size_t(i) + 2] - c.pos[2];
+    float const cx = (c.right[0] * dx + c.right[1] * dy) + c.right[2] * dz;  // camera space, as project_point
+    float const cy = (c.up[0] * dx + c.up[1] * dy) + c.up[2] * dz;
+    float const cz = (c.fwd[0] * dx + c.fwd[1] * dy) + c.fwd[2] * dz;
+    float fx, fy, dep;
+    if (kind == DMT_PROJECTION_ORTHOGRAPHIC) {
+      fx = (cx / a - c.tx) * c.ipx, fy = (cy / a - c.ty) * c.ipy, dep = cz;
+    } else if (kind == DMT_PROJECTION_EQUIRECT) {
+      float const lon = std::atan2(cx, cz), lat = std::atan2(cy, std::hypot(cx, cz));
+      fx = (lon / (2.0f * kPi) + 0.5f) * W, fy = (0.5f - lat / kPi) * H;
+      dep = std::sqrt((cx * cx + cy * cy) + cz * cz);
+    } else {
+      float const rho = std::hypot(cx, cy);
+      float const r = std::atan2(rho, cz) / a;  // theta / s, in pixels
+      float const ux = rho > 0.f ? cx / rho : 0.f, uy = rho > 0.f ? cy / rho : 0.f;
+      fx = 0.5f * W + r * ux, fy = 0.5f * H - r * uy;
+      dep = std::sqrt((cx * cx + cy * cy) + cz * cz);
+    }
+    xy2[2 * size_t(i)] = fx, xy2[2 * size_t(i) + 1] = fy, depth[i] = dep;
+  }
   return DMT_OK;
 }
 

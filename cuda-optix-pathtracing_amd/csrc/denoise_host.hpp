@@ -96,6 +96,8 @@ int denoiseRun(dmt_ctx* ctx, char const* name, const dmt_denoise_params* params,
   if (tp && (!(tp->alpha >= 0.f && tp->alpha <= 1.f) || !std::isfinite(tp->normal_threshold) || !positive(tp->plane_threshold)))
     return failn(DMT_ERR_INVALID, "alpha must be 0 .. 1, normal_threshold finite, plane_threshold finite and > 0");
   if (!ctx->camera.have) return failn(DMT_ERR_STATE, "set the camera first");
+  if (ctx->camera.projKind != DMT_PROJECTION_PERSPECTIVE)  // before anything is touched: the history stays as it was
+    return failn(DMT_ERR_STATE, "the depth scale and the reprojection are the perspective camera's (dmt_set_projection set another projection)");
   if (ctx->dn.aovW == 0) return failn(DMT_ERR_STATE, "no AOVs (call dmt_render_aovs or dmt_upload_aovs first)");
   if (ctx->dn.aovW != ctx->film.w || ctx->dn.aovH != ctx->film.h) {
     char msg[160];

@@ -168,6 +168,11 @@ struct RenderParams {
   // it): non-zero lets path_shade read lights[0] / infLights[0] by s_load where the pick runs over one record.  After
   // `filtKnots`, so that no other field moves
   uint32_t uniformLights;
+  // the camera's projection (dmt_set_projection): projKind 0 is the perspective camera, projA the model's
+  // host-made factor and projW x projH the film's size as floats (camera_ray_projection).  Read by prepare_sample's cold
+  // tail, the feature pass and the probes.  After `uniformLights`, so that no other field moves
+  int projKind;
+  float projA, projW, projH;
 };
 
 // Per-lane state.  A lane carries (a) the path it is currently extending and (b) at most one
@@ -190,7 +195,7 @@ DMT_DEV KArgs kargs(KArgs p) {
 }
 DMT_DEV CameraExtra load_camera_extra(KArgs k) {  // at the point of use, like the cold arguments
   k = kargs(k);
-  return CameraExtra{k->lensRad, k->lensD, k->filtKnots, k->filtR};
+  return CameraExtra{k->lensRad, k->lensD, k->filtKnots, k->filtR, k->projKind, k->projA, k->projW, k->projH};
 }
 DMT_DEV SceneView load_scene(KArgs k) {
   k = kargs(k);
@@ -1240,6 +1245,26 @@ DMT_DEV f2 tail_jitter(KArgs Pk, int32_t hidx) {
   }
   return jit;
 }
+// The ray of another projection than the perspective one (dmt_set_projection; never with a lens), over the
+// ray prepare_lens_ray has just stored: the last step of the cold tail, after the perspective code and not a branch inside
+// it.  It recomputes the jitter by tail_jitter (the bits a table's jitter plane holds) and reads the matrices from the kernel
+// arguments once more, so that nothing of the perspective tail stays live for it.  Measured: where this
+// block sits -- here, as a sibling branch in prepare_sample, merged into the choice between the two ray functions, or ahead of
+// the lens code -- changes no row's resources; what does is the literal constants of its sine and cosine, which the compiler
+// hoists out of the sample loop into registers that then live across the shading code (sincos_cold, pt_device.hpp).
+DMT_DEV void prepare_projection_ray(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
+  float* const prep = s_prep + threadIdx.x;
+  int32_t const hidx = pixBase + int32_t(s) * (kargs(Pk)->sp.scale0 * kargs(Pk)->sp.scale1);
+  f2 const jit = tail_jitter(Pk, hidx);
+  KArgs const kp = kargs(Pk);
+  CameraXf cam;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) cam.cfr[i] = kp->cam.cfr[i], cam.rfc[i] = kp->cam.rfc[i];
+  Ray const q = camera_ray_projection(cam, film_coord(jit.x, px), film_coord(jit.y, py), kp->projKind, kp->projA, kp->projW, kp->projH);
+  prep[8 * kLdsThreads] = q.o.x, prep[9 * kLdsThreads] = q.o.y, prep[10 * kLdsThreads] = q.o.z;
+  prep[11 * kLdsThreads] = q.d.x, prep[12 * kLdsThreads] = q.d.y, prep[13 * kLdsThreads] = q.d.z;
+}
+template <bool PROJ>  // PROJ: the row carries the projection's ray (projection_row)
 DMT_DEV void prepare_lens_ray(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
   float* const prep = s_prep + threadIdx.x;
   f2 jit;
@@ -1262,11 +1287,23 @@ DMT_DEV void prepare_lens_ray(KArgs Pk, int px, int py, int32_t pixBase, uint32_
   Ray const r = lensR > 0.f ? camera_ray_lens(cam, px, py, jit, lensR, kc->lensD, lu) : camera_ray_jittered(cam, px, py, jit);
   prep[8 * kLdsThreads] = r.o.x, prep[9 * kLdsThreads] = r.o.y, prep[10 * kLdsThreads] = r.o.z;
   prep[11 * kLdsThreads] = r.d.x, prep[12 * kLdsThreads] = r.d.y, prep[13 * kLdsThreads] = r.d.z;
+  if constexpr (PROJ) {
+    if (__builtin_expect(kargs(Pk)->projKind != 0, 0)) prepare_projection_ray(Pk, px, py, pixBase, s);
+  }
 }
 #ifndef DMT_LENS_EARLY
 #define DMT_LENS_EARLY 1  // variant builds for A/B runs: 0 reads the lens radius after the sample's LDS stores
 #endif
-template <bool MOTION = false>  // MOTION: the sample's time is prepared with it (motion.hpp)
+// The rows whose cold tail carries the projection's ray: all but k_megakernel_env and k_megakernel_bvh_env_ltree.  Host and
+// device read the same function (checkFeatures).
+constexpr bool projection_row(uint32_t F) {
+  uint32_t const row = F & ~kFeatStats;
+  return row != kFeatEnv && row != (kFeatBvh | kFeatEnv | kFeatLightTree);
+}
+// PROJ: the cold tail ends with the projection's ray.  Two rows are compiled without it (projection_row): with it, in every
+// shape of the tail that was measured, they spill one VGPR more than they did; without it their code is what
+// it was, and dmt_render refuses another projection than the perspective one for them.
+template <bool MOTION = false, bool PROJ = true>  // MOTION: the sample's time is prepared with it (motion.hpp)
 DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t s) {
   float* const prep = s_prep + threadIdx.x;
   Ray r;
@@ -1298,7 +1335,7 @@ DMT_DEV void prepare_sample(KArgs Pk, int px, int py, int32_t pixBase, uint32_t 
 #if !DMT_LENS_EARLY
   float const lensR = kargs(Pk)->camTail;
 #endif
-  if (__builtin_expect(lensR > 0.f, 0)) prepare_lens_ray(Pk, px, py, pixBase, s);  // lens or filter: wave-uniform, laid out of line
+  if (__builtin_expect(lensR > 0.f, 0)) prepare_lens_ray<PROJ>(Pk, px, py, pixBase, s);  // lens, filter or projection: wave-uniform, laid out of line
   if constexpr (MOTION) motion_set_prepared(motion_sample_time(Pk, pixBase, s));
 }
 template <bool MOTION = false>
@@ -1514,9 +1551,9 @@ DMT_DEV void megakernel_body() {
           // (make asm: 8 bytes of scratch, that address spilled at kernel start).  The copy is one move per call.
           int l = lane;
           asm volatile("" : "+v"(l));
-          sched_draw<MOTION>(Pk, gtid, l, W, Ls, needPrep);
+          sched_draw<MOTION, projection_row(F)>(Pk, gtid, l, W, Ls, needPrep);
         } else {
-          sched_draw<MOTION>(Pk, gtid, lane, W, Ls, needPrep);
+          sched_draw<MOTION, projection_row(F)>(Pk, gtid, lane, W, Ls, needPrep);
         }
       }
       if (W.cur == W.fetched) break;  // nothing live and nothing fetched: the launch has no more items (invariant 4: nothing parked)
@@ -1612,7 +1649,7 @@ DMT_DEV void megakernel_body_bvh() {
       bool const starving = idle && !st.active && needPrep;
       if (__any(starving) || __popcll(__ballot(needPrep)) >= DMT_PREP_THRESHOLD) {
         if constexpr (STATS) ++ls.itPrep, ls.lanesPrep += needPrep ? 1u : 0u;
-        sched_draw<MOTION>(Pk, gtid, lane, W, Ls, needPrep);
+        sched_draw<MOTION, projection_row(F)>(Pk, gtid, lane, W, Ls, needPrep);
       }
       if (W.cur == W.fetched) break;  // nothing live and nothing fetched: the launch has no more items
       if constexpr (STATS) ++ls.itOuter;
@@ -1987,8 +2024,19 @@ int resolveFeatures(dmt_ctx* ctx, uint32_t* mask) {
   *mask = featuresOf(ctx);
   return DMT_OK;
 }
+// what another projection than the perspective one (dmt_set_projection) refuses of a feature mask: dmt_render*
+// (checkFeatures) and the trace probes, which shade with the same bodies
+int checkProjection(dmt_ctx* ctx, uint32_t F) {
+  if (!projection_row(F) && ctx->camera.projKind != DMT_PROJECTION_PERSPECTIVE)  // the two rows compiled without the projection's tail
+    return fail(ctx, DMT_ERR_STATE, (F & kFeatBvh) ? "dmt_render: another projection than the perspective one (dmt_set_projection) together with an env map, the BVH and the light tree is not supported (use the uniform light pick)"
+                                                   : "dmt_render: another projection than the perspective one (dmt_set_projection) together with an env map needs the BVH (dmt_set_accel) unless the scene has textures, emissive triangles, motion, vertex normals or a medium");
+  if ((F & kFeatTexFilter) && ctx->camera.projKind != DMT_PROJECTION_PERSPECTIVE)  // its footprints are the pinhole's differentials
+    return fail(ctx, DMT_ERR_STATE, "dmt_render: the first-hit texture filter together with another projection than the perspective one (dmt_set_projection) is not supported");
+  return DMT_OK;
+}
 // the combinations dmt_render refuses (mask | kFeatStats for dmt_render_stats / dmt_render_profile)
 int checkFeatures(dmt_ctx* ctx, uint32_t F) {
+  if (int const rc = checkProjection(ctx, F)) return rc;
   if (F & kFeatMedium) {  // the medium has the plain and env-map megakernel rows
     if (F & kFeatStats) return fail(ctx, DMT_ERR_STATE, "dmt_render_stats / dmt_render_profile: a participating medium (dmt_set_medium) has no counting kernels");
     if (F & kFeatArea) return fail(ctx, DMT_ERR_STATE, "dmt_render: a participating medium (dmt_set_medium) together with emissive triangles is not supported");

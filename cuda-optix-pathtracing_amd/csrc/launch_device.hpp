@@ -225,7 +225,7 @@ DMT_DEV void slab_publish(TileArgs const& T, int lane, uint32_t slab, uint32_t n
 }
 
 // prepare unit u of item `seq` in this lane's s_prep
-template <bool MOTION = false>
+template <bool MOTION = false, bool PROJ = true>
 DMT_DEV void prepare_unit(KArgs Pk, uint32_t seq, uint32_t u, LaneSched& Ls) {
   uint32_t const slot = seq & 1u;
   uint32_t const* const d = s_desc[threadIdx.x >> 6][slot];
@@ -235,7 +235,7 @@ DMT_DEV void prepare_unit(KArgs Pk, uint32_t seq, uint32_t u, LaneSched& Ls) {
   else k = u / nInside, j = u - k * nInside;
   uint32_t const wbase = slot * kLdsThreads + (threadIdx.x & ~63u);
   uint32_t const pixel = s_pixmap[wbase + j];
-  prepare_sample<MOTION>(Pk, int(d[2]) + int(pixel & 7u), int(d[3]) + int(pixel >> 3), s_pixbase[wbase + pixel], d[4] + k);
+  prepare_sample<MOTION, PROJ>(Pk, int(d[2]) + int(pixel & 7u), int(d[3]) + int(pixel >> 3), s_pixbase[wbase + pixel], d[4] + k);
   s_prep[14 * kLdsThreads + threadIdx.x] = __uint_as_float((slot << 31) | (k * 64u + pixel));
   Ls.prepared = true, Ls.prepSlot = slot != 0u;
 }
@@ -363,7 +363,7 @@ DMT_DEV void item_complete(KArgs Pk, uint32_t gtid, int lane, uint32_t seq, Wave
 // Hand the next units of the wave's items to the lanes that ask for one (`want`) and prepare them.  This is the ONE place
 // where work items are fetched (item_fetch is large, and the kernel already fills most of the instruction cache): a wave
 // starts with no item, and a wave whose last live item was retired comes here because all its lanes are starving.
-template <bool MOTION = false>
+template <bool MOTION = false, bool PROJ = true>
 DMT_DEV void sched_draw(KArgs Pk, uint32_t gtid, int lane, WaveSched& W, LaneSched& Ls, bool want) {
   if (__builtin_expect(W.nextUnit == W.totalUnits, 0)) {  // the item units are drawn from is used up (or there is none yet): fetch the next if there is room
     if (!W.exhausted && W.fetched - W.cur < 2u && W.slabFree != 0u) {
@@ -377,7 +377,7 @@ DMT_DEV void sched_draw(KArgs Pk, uint32_t gtid, int lane, WaveSched& W, LaneSch
   unsigned long long const m = __ballot(want);
   uint32_t const rank = uint32_t(__popcll(m & ((1ull << lane) - 1ull)));
   uint32_t const cnt = uint32_t(__popcll(m));
-  if (want && rank < avail) prepare_unit<MOTION>(Pk, W.alloc, W.nextUnit + rank, Ls);
+  if (want && rank < avail) prepare_unit<MOTION, PROJ>(Pk, W.alloc, W.nextUnit + rank, Ls);
   W.nextUnit += cnt < avail ? cnt : avail;
 }
 

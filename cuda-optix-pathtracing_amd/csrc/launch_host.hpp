@@ -284,9 +284,9 @@ int growLaunchBuffers(dmt_ctx* ctx, LaunchPlan const& L, uint32_t spp, RenderPar
     if (ctx->camera.lensR > 0.f) {
       HIP_TRY(ctx, S.tab.lens.reserve(sliceEntries));
       P.samTabLens = S.tab.lens.get();
-    } else {
+    } else if (ctx->camera.projKind == DMT_PROJECTION_PERSPECTIVE) {
       P.camTail = 0.f;  // a pixel filter alone: the jitter plane holds the warped jitter, the main path needs no tail
-    }
+    }  // (another projection keeps its tail, which recomputes the jitter by tail_jitter: the jitter plane's bits)
   }
   return DMT_OK;
 }

@@ -831,6 +831,7 @@ int dmt_test_trace_samples(dmt_ctx* ctx, int n, const int32_t* pxs, const int32_
   if (p.err != hipSuccess) return probeError(ctx, p);
   uint32_t F = 0;  // the shading body dmt_render would run
   if (int const rc = resolveFeatures(ctx, &F)) return rc;
+  if (int const rc = checkProjection(ctx, F)) return rc;  // as dmt_render
   TestTraceFn const kernel = kernelOf(kTestTraceKernels, F);
   if (!kernel) return noKernel(ctx, "dmt_test_trace_samples", F);
   if (F & kFeatBvh) {

@@ -594,15 +594,124 @@ __host__ __device__ inline float film_coord(float r, int p) {
 #pragma clang fp contract(off)
   return ((r - 0.5f) + 0.5f) + float(p);
 }
-// the camera-side state beside the camera record: the thin lens and the pixel filter (knots null: box 0.5, no warp)
+// ---- camera projections (dmt_set_projection) ------------------------------------------------------
+// Beyond the reference, whose camera is the perspective pinhole.  A projection maps the sample's film position (fx, fy) to
+// another ray and changes nothing else about the sample.  The models live in camera space (x right, y up, z forward);
+// include/dmt_hip.h states them.  One body per model for the arithmetic up to the trigonometric calls, fp32 without
+// contraction in one order of operations for the device and the host twin (dmt_projection_rays); the device divides by
+// v_rcp_f32 with one residual step (as lens_ray_parts) and takes the square root by its rsqrt, the host uses `/` and sqrt.
+// kind: DMT_PROJECTION_*; 0 is the perspective camera and never reaches this code.
+constexpr int kProjOrthographic = 1, kProjEquirect = 2, kProjFisheye = 3;
+__host__ __device__ inline float proj_quot(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  float const r = __builtin_amdgcn_rcpf(b);
+  float const q = a * r;
+  return __builtin_fmaf(__builtin_fmaf(-q, b, a), r, q);
+#else
+  return a / b;
+#endif
+}
+// orthographic: o3 = renderFromCamera point(cx k, cy k, 0) with (cx, cy) of cameraFromRaster (fx, fy, 0), as lens_ray_parts
+// forms them; k = view height / sensor height, formed once on the host.  d3 = the forward column as stored (not normalised)
+__host__ __device__ inline void ortho_ray_parts(float const* cfr, float const* rfc, float fx, float fy, float k, float* o3, float* d3) {
+#pragma clang fp contract(off)
+  float const cx = ((cfr[0] * fx + cfr[4] * fy) + cfr[8] * 0.0f) + cfr[12];
+  float const cy = ((cfr[1] * fx + cfr[5] * fy) + cfr[9] * 0.0f) + cfr[13];
+  float const ox = cx * k, oy = cy * k;
+  for (int i = 0; i < 3; ++i) {
+    o3[i] = ((rfc[i] * ox + rfc[4 + i] * oy) + rfc[8 + i] * 0.0f) + rfc[12 + i];
+    d3[i] = rfc[8 + i];
+  }
+}
+// equirectangular: the longitude and the latitude of film position (fx, fy) on a W x H film
+__host__ __device__ inline void equirect_angles(float fx, float fy, float W, float H, float& lon, float& lat) {
+#pragma clang fp contract(off)
+  float const u = proj_quot(fx, W), v = proj_quot(fy, H);
+  lon = (u - 0.5f) * (2.0f * kPi);
+  lat = (0.5f - v) * kPi;
+}
+// fisheye (equidistant): the unit vector (ux, uy) from the film's centre to (fx, fy), y up, and the angle theta = r s from
+// the axis; s = (fov / 2 in radians) / (half the film's diagonal), formed once on the host.  (0, 0) and theta 0 at the centre
+__host__ __device__ inline void fisheye_angle(float fx, float fy, float W, float H, float s, float& ux, float& uy, float& theta) {
+#pragma clang fp contract(off)
+  float const x = fx - 0.5f * W, y = 0.5f * H - fy;
+  float const r2 = x * x + y * y;
+#if defined(__HIP_DEVICE_COMPILE__)
+  float const inv = r2 > 0.f ? __builtin_amdgcn_rsqf(r2) : 0.f;
+  float const r = r2 * inv;
+#else
+  float const r = std::sqrt(r2);
+  float const inv = r2 > 0.f ? 1.0f / r : 0.f;
+#endif
+  ux = x * inv, uy = y * inv;
+  theta = r * s;
+}
+// the camera-space direction of either angular model from the sines and cosines of its angles
+__host__ __device__ inline void equirect_dir(float sLon, float cLon, float sLat, float cLat, float* c3) {
+#pragma clang fp contract(off)
+  c3[0] = cLat * sLon, c3[1] = sLat, c3[2] = cLat * cLon;
+}
+__host__ __device__ inline void fisheye_dir(float ux, float uy, float sT, float cT, float* c3) {
+#pragma clang fp contract(off)
+  c3[0] = sT * ux, c3[1] = sT * uy, c3[2] = cT;
+}
+// renderFromCamera's vector transform and its translation column: the angular models' direction (before it is normalised)
+// and origin, the camera position
+__host__ __device__ inline void angular_ray_parts(float const* rfc, float const* c3, float* o3, float* d3) {
+#pragma clang fp contract(off)
+  for (int i = 0; i < 3; ++i) {
+    o3[i] = rfc[12 + i];
+    d3[i] = (rfc[i] * c3[0] + rfc[4 + i] * c3[1]) + rfc[8 + i] * c3[2];
+  }
+}
+// sincos_bounded (below) with every literal constant behind an opaque copy: one body, sincos_bounded_t, makes both.  Left
+// as literals in the projections' cold tail the constants are hoisted out of the megakernels' sample loop and held in VGPRs
+// across the shading code, which cost k_megakernel_area and k_megakernel_vn a spilled VGPR each; an opaque
+// copy is materialised where it is used.
+DMT_DEV void sincos_cold(float x, float& sn, float& cs);  // below
+// the ray of film position (fx, fy) under projection kind != 0; a: the model's host-made factor (k or s), W x H: the film
+DMT_DEV Ray camera_ray_projection(CameraXf const& cam, float fx, float fy, int kind, float a, float W, float H) {
+  float o[3], d[3];
+  if (kind == kProjOrthographic) {
+    ortho_ray_parts(cam.cfr, cam.rfc, fx, fy, a, o, d);
+  } else {
+    float c[3];
+    if (kind == kProjEquirect) {
+      float lon, lat, sLon, cLon, sLat, cLat;
+      equirect_angles(fx, fy, W, H, lon, lat);
+      sincos_cold(lon, sLon, cLon);
+      sincos_cold(lat, sLat, cLat);
+      equirect_dir(sLon, cLon, sLat, cLat, c);
+    } else {
+      float ux, uy, theta, sT, cT;
+      fisheye_angle(fx, fy, W, H, a, ux, uy, theta);
+      sincos_cold(theta, sT, cT);
+      fisheye_dir(ux, uy, sT, cT, c);
+    }
+    angular_ray_parts(cam.rfc, c, o, d);
+  }
+  Ray ray;
+  ray.o = mk3(o[0], o[1], o[2]);
+  ray.d = normalize(mk3(d[0], d[1], d[2]));
+  return ray;
+}
+// the camera-side state beside the camera record: the thin lens, the pixel filter (knots null: box 0.5, no warp) and the
+// projection (proj 0: perspective; projA: the model's factor; projW x projH: the film)
 struct CameraExtra {
   float lensR, lensD;
   FilterBin const* knots;
   float filtR;
+  int proj;
+  float projA, projW, projH;
 };
-// what the render kernels trace: the lens ray for lensR > 0, the jitter warped under a pixel filter (both wave-uniform),
-// else the pinhole ray
+// what the render kernels trace: the lens ray for lensR > 0, the jitter warped under a pixel filter, the projection's ray
+// for another model than the perspective one (all wave-uniform), else the pinhole ray
 DMT_DEV Ray camera_ray_any(CameraXf const& cam, SamplerParams const& sp, int px, int py, int32_t haltonIndex, CameraExtra const& x) {
+  if (x.proj != 0) {  // never with a lens (dmt_set_projection)
+    f2 r = pixel2d(sp, haltonIndex);
+    if (x.knots) r = f2{filter_warp(x.knots, x.filtR, r.x), filter_warp(x.knots, x.filtR, r.y)};
+    return camera_ray_projection(cam, film_coord(r.x, px), film_coord(r.y, py), x.proj, x.projA, x.projW, x.projH);
+  }
   if (x.lensR > 0.f || x.knots) {
     f2 r = pixel2d(sp, haltonIndex);
     if (x.knots) r = f2{filter_warp(x.knots, x.filtR, r.x), filter_warp(x.knots, x.filtR, r.y)};
@@ -774,20 +883,27 @@ DMT_DEV f3 offset_ray_origin(f3 p, f3 error, f3 ng, f3 w) {
 // Payne-Hanek path for huge arguments that is never taken here but was a THIRD of the megakernel's code
 // (3 300 of 9 900 instructions for three call sites): the kernel no longer fit the instruction cache it shares
 // with the neighbouring CU.
-DMT_DEV void sincos_bounded(float x, float& sn, float& cs) {
-  float const q = rintf(x * 0.636619772367581343f);  // x * 2/pi
-  float r = fma_(q, -1.5703125f, x);
-  r = fma_(q, -4.837512969970703125e-4f, r);
-  r = fma_(q, -7.54978995489188216e-8f, r);
+template <bool OPAQUE>  // OPAQUE: the literals go through an opaque register copy (sincos_cold); the arithmetic is the same
+DMT_DEV void sincos_bounded_t(float x, float& sn, float& cs) {
+  auto const k = [](float c) {
+    if constexpr (OPAQUE) asm volatile("" : "+v"(c));
+    return c;
+  };
+  float const q = rintf(x * k(0.636619772367581343f));  // x * 2/pi
+  float r = fma_(q, k(-1.5703125f), x);
+  r = fma_(q, k(-4.837512969970703125e-4f), r);
+  r = fma_(q, k(-7.54978995489188216e-8f), r);
   float const r2 = r * r;
-  float const sp = fma_(fma_(fma_(-1.9515295891e-4f, r2, 8.3321608736e-3f), r2, -1.6666654611e-1f), r2 * r, r);
-  float const cp = fma_(fma_(fma_(2.443315711809948e-5f, r2, -1.388731625493765e-3f), r2, 4.166664568298827e-2f), r2 * r2,
+  float const sp = fma_(fma_(fma_(k(-1.9515295891e-4f), r2, k(8.3321608736e-3f)), r2, k(-1.6666654611e-1f)), r2 * r, r);
+  float const cp = fma_(fma_(fma_(k(2.443315711809948e-5f), r2, k(-1.388731625493765e-3f)), r2, k(4.166664568298827e-2f)), r2 * r2,
                         fma_(-0.5f, r2, 1.0f));
   int const n = int(q) & 3;
   float const a = (n & 1) ? cp : sp, b = (n & 1) ? sp : cp;
   sn = (n & 2) ? -a : a;
   cs = ((n + 1) & 2) ? -b : b;
 }
+DMT_DEV void sincos_bounded(float x, float& sn, float& cs) { sincos_bounded_t<false>(x, sn, cs); }
+DMT_DEV void sincos_cold(float x, float& sn, float& cs) { sincos_bounded_t<true>(x, sn, cs); }
 
 // ---------------------------------------------------------------------------------------------
 // sampling helpers                                               CC/private/sampling.cu

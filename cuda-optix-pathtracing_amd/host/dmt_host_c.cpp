@@ -144,6 +144,9 @@ dmt_camera* dmt_host_scene_camera(dmt_host_scene* h) { return &h->s.camera; }
 void dmt_host_scene_lens(const dmt_host_scene* h, float* lens_radius, float* focus_distance) {
   *lens_radius = h->s.lensRadius, *focus_distance = h->s.focusDistance;
 }
+void dmt_host_scene_projection(const dmt_host_scene* h, int* kind, float* param) {
+  *kind = h->s.projection, *param = h->s.projectionParam;
+}
 // the pixel filter the scene file records (not applied by an upload unless asked): 0 without one, 1 for a kind the library
 // offers (*kind = its DMT_FILTER_* value), 2 for an unsupported kind (mitchell, sinc); radius, sigma, and the file's name
 // for the kind (up to name_cap - 1 characters)

@@ -211,7 +211,13 @@ struct State {
 void parseCamera(Value const& cam, JsonScene& out, Vec3& dir, Vec3& pos) {
   // beyond the reference's parser: an optional thin lens, 'lensRadius' and 'focusDistance' in scene units (absent: pinhole)
   size_t const lensKeys = size_t(cam.isObject() && cam.contains("lensRadius")) + size_t(cam.isObject() && cam.contains("focusDistance"));
-  if (!cam.isObject() || cam.size() > 4 + lensKeys) fail("'camera' should be an object with at most 4 members and the lens keys");  // :741
+  // and an optional projection: 'projection' ("orthographic" | "equirect" | "fisheye"; absent: perspective) with 'orthoHeight'
+  // in scene units or 'fisheyeFov' in degrees across the film's diagonal
+  size_t projKeys = 0;
+  for (char const* key : {"projection", "orthoHeight", "fisheyeFov"}) projKeys += size_t(cam.isObject() && cam.contains(key));
+  if (!cam.isObject() || cam.size() > 4 + lensKeys + projKeys)
+    fail(projKeys ? "'camera' should be an object with at most 4 members, the lens keys and the projection keys"
+                  : "'camera' should be an object with at most 4 members and the lens keys");  // :741
   if (!cam.contains("focalLength") || !cam.contains("sensorSize") || !cam.contains("direction"))
     fail("'camera' needs 'focalLength', 'sensorSize' and 'direction'");
   if (!cam.at("sensorSize").isNumber() || float(cam.at("sensorSize").number) <= 0.f) fail("camera 'sensorSize' should be a positive number");
@@ -230,6 +236,27 @@ void parseCamera(Value const& cam, JsonScene& out, Vec3& dir, Vec3& pos) {
     out.scene.focusDistance = float(cam.at("focusDistance").number);
   }
   if (out.scene.lensRadius > 0.f && !cam.contains("focusDistance")) fail("camera 'lensRadius' > 0 needs a 'focusDistance'");
+  if (projKeys) {
+    if (!cam.contains("projection") || !cam.at("projection").isString()) fail("camera 'orthoHeight' / 'fisheyeFov' need a 'projection' string");
+    std::string const& name = cam.at("projection").string;
+    int const kind = name == "orthographic" ? 1 : name == "equirect" ? 2 : name == "fisheye" ? 3 : 0;
+    if (kind == 0) fail("camera 'projection' should be \"orthographic\", \"equirect\" or \"fisheye\"");
+    if (cam.contains("orthoHeight") != (kind == 1)) fail("camera 'orthoHeight' goes with the \"orthographic\" projection, and only with it");
+    if (cam.contains("fisheyeFov") != (kind == 3)) fail("camera 'fisheyeFov' goes with the \"fisheye\" projection, and only with it");
+    float param = 0.f;
+    if (kind == 1) {
+      if (!cam.at("orthoHeight").isNumber() || !(float(cam.at("orthoHeight").number) > 0.f) || !std::isfinite(float(cam.at("orthoHeight").number)))
+        fail("camera 'orthoHeight' should be a positive number");
+      param = float(cam.at("orthoHeight").number);
+    }
+    if (kind == 3) {
+      float const fov = cam.at("fisheyeFov").isNumber() ? float(cam.at("fisheyeFov").number) : 0.f;
+      if (!(fov > 0.f && fov <= 360.f)) fail("camera 'fisheyeFov' should be a number in (0, 360]");
+      param = fov;
+    }
+    if (out.scene.lensRadius > 0.f) fail("camera 'lensRadius' > 0 goes with the perspective projection only");
+    out.scene.projection = kind, out.scene.projectionParam = param;
+  }
   if (cam.contains("max-depth")) {
     if (!cam.at("max-depth").isInteger() || int(cam.at("max-depth").number) <= 0) fail("camera 'max-depth' should be a positive integer");
     out.maxDepth = int(cam.at("max-depth").number);

@@ -475,7 +475,15 @@ int uploadScene(dmt_ctx* ctx, Scene const& s) {
   if (rc) return rc;
   rc = dmt_set_camera(ctx, &s.camera);
   if (rc) return rc;
-  rc = dmt_set_lens(ctx, s.lensRadius, s.focusDistance);
+  // The scene's lens and projection replace the context's.  The two exclude each other, so what the scene leaves at its default
+  // is set first: a context that still holds the last scene's projection (or lens) then takes this scene's lens (or projection).
+  // A scene that asks for both is refused by the second call, with the library's message.
+  bool const perspective = s.projection == DMT_PROJECTION_PERSPECTIVE;
+  if (perspective) rc = dmt_set_projection(ctx, s.projection, s.projectionParam);
+  else rc = dmt_set_lens(ctx, s.lensRadius, s.focusDistance);
+  if (rc) return rc;
+  if (perspective) rc = dmt_set_lens(ctx, s.lensRadius, s.focusDistance);
+  else rc = dmt_set_projection(ctx, s.projection, s.projectionParam);
   if (rc) return rc;
   rc = s.hasMedium ? dmt_set_medium(ctx, s.mediumSigmaT, s.mediumAlbedo, s.mediumG, s.mediumMin, s.mediumMax) : dmt_clear_medium(ctx);
   if (rc) return rc;

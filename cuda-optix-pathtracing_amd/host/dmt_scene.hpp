@@ -64,6 +64,10 @@ struct Scene {
   dmt_camera camera{};
   // optional thin lens (dmt_set_lens), reported beside the camera record: radius 0 = pinhole; both in scene units
   float lensRadius = 0.f, focusDistance = 1.f;
+  // optional projection (dmt_set_projection), reported beside the camera record: DMT_PROJECTION_* (0 = perspective) and its
+  // parameter, the orthographic view height in scene units or the fisheye's diagonal field of view in degrees
+  int projection = 0;
+  float projectionParam = 0.f;
   // optional pixel filter (dmt_set_pixel_filter; the PBRT front-end's PixelFilter, the JSON front-end's film.filter): recorded
   // here and NOT applied by uploadScene -- only where the caller asks (applyPixelFilter; main.cpp --pixel-filter scene).
   // Kind: kNoPixelFilter, a DMT_FILTER_* value, or kUnsupportedPixelFilter for a kind the library does not offer (signed

@@ -55,6 +55,9 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   float lensRadius = 0.f, focusDistance = 1.f, focusX = 0.f, focusY = 0.f;
   // --pixel-filter box|tent|gaussian|blackman-harris|scene, --filter-radius R, --filter-sigma S (dmt_set_pixel_filter)
   std::string pixelFilter;
+  std::string projection;     // --projection perspective|orthographic|equirect|fisheye (dmt_set_projection); empty: the scene file's
+  bool orthoHeightSet = false, fisheyeFovSet = false;  // --ortho-height H, --fisheye-fov DEG
+  float orthoHeight = 0.f, fisheyeFov = 0.f;
   bool filterRadiusSet = false, filterSigmaSet = false;
   float filterRadius = 0.f, filterSigma = 0.5f;
   bool shutterSet = false;    // --shutter OPEN CLOSE: the shutter interval of --motion-scene (dmt_set_shutter)
@@ -120,6 +123,12 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (focusDistanceSet && !(std::isfinite(focusDistance) && focusDistance > 0.f)) return "invalid --focus-distance: expected a finite distance > 0";
     if (focusDistanceSet && focusPixelSet) return "--focus-distance and --focus-pixel exclude each other";
     if (focusPixelSet && !(focusX >= 0.f && focusX < float(width) && focusY >= 0.f && focusY < float(height))) return "invalid --focus-pixel: outside the frame";
+    if (!projection.empty() && projection != "perspective" && projection != "orthographic" && projection != "equirect" && projection != "fisheye")
+      return "invalid --projection: expected perspective, orthographic, equirect or fisheye, got '" + projection + "'";
+    if (orthoHeightSet != (projection == "orthographic")) return "--ortho-height goes with --projection orthographic, and only with it";
+    if (fisheyeFovSet != (projection == "fisheye")) return "--fisheye-fov goes with --projection fisheye, and only with it";
+    if (orthoHeightSet && !(std::isfinite(orthoHeight) && orthoHeight > 0.f)) return "invalid --ortho-height: expected a finite height > 0";
+    if (fisheyeFovSet && !(fisheyeFov > 0.f && fisheyeFov <= 360.f)) return "invalid --fisheye-fov: expected degrees in (0, 360]";
     if (!pixelFilter.empty() && pixelFilter != "box" && pixelFilter != "tent" && pixelFilter != "gaussian" && pixelFilter != "blackman-harris" &&
         pixelFilter != "scene")
       return "invalid --pixel-filter: expected box, tent, gaussian, blackman-harris or scene, got '" + pixelFilter + "'";
@@ -196,6 +205,12 @@ void printHelp() {
       "  --aov-spp <N>     -- Camera samples per pixel of those buffers (default 4)\n"
       "  --lens-radius <R> -- Thin lens of radius R in scene units: depth of field (0, the default, is the pinhole; a scene\n"
       "                       file's own lens applies unless given here)\n"
+      "  --projection <P>  -- Camera projection: perspective (the default), orthographic (with --ortho-height), equirect (a\n"
+      "                       360-degree panorama; 2:1 frames are the natural shape) or fisheye (equidistant, with\n"
+      "                       --fisheye-fov).  A scene file's own projection applies unless given here.  Not with\n"
+      "                       --lens-radius, --denoise or --texture-filter\n"
+      "  --ortho-height <H> -- Height of the orthographic view, in scene units\n"
+      "  --fisheye-fov <DEG> -- Field of view of the fisheye across the frame's diagonal, in degrees (0, 360]\n"
       "  --focus-distance <D> -- Depth along the viewing direction, in scene units, that the lens renders sharp\n"
       "  --focus-pixel <X> <Y> -- Autofocus: focus on what the centre of pixel (X, Y) shows, and print the distance chosen\n"
       "  --pixel-filter <box|tent|gaussian|blackman-harris|scene> -- Pixel reconstruction filter, importance-sampled per sample\n"
@@ -259,6 +274,9 @@ Config parseArguments(int argc, char** argv) {
     else if (a == "--shading-normals" && more) c.shadingNormals = argv[++i];
     else if (a == "--cutouts" && more) c.cutouts = argv[++i];
     else if (a == "--pixel-filter" && more) c.pixelFilter = argv[++i];
+    else if (a == "--projection" && more) c.projection = argv[++i];
+    else if (a == "--ortho-height" && more) c.orthoHeight = std::strtof(argv[++i], nullptr), c.orthoHeightSet = true;
+    else if (a == "--fisheye-fov" && more) c.fisheyeFov = std::strtof(argv[++i], nullptr), c.fisheyeFovSet = true;
     else if (a == "--filter-radius" && more) c.filterRadius = std::strtof(argv[++i], nullptr), c.filterRadiusSet = true;
     else if (a == "--filter-sigma" && more) c.filterSigma = std::strtof(argv[++i], nullptr), c.filterSigmaSet = true;
     else if (a == "--medium" && more) c.mediumSigmaT = std::strtof(argv[++i], nullptr), c.mediumSet = true;
@@ -390,6 +408,22 @@ int main(int argc, char** argv) {
   if (cfg.textureFilter) scene.camera.spp = cfg.spp;  // the filter's footprint scale follows the frame's samples per pixel
   if (cfg.lensRadiusSet) scene.lensRadius = cfg.lensRadius;
   if (cfg.focusDistanceSet) scene.focusDistance = cfg.focusDistance;
+  if (!cfg.projection.empty()) {  // --projection replaces the scene file's
+    scene.projection = cfg.projection == "orthographic" ? DMT_PROJECTION_ORTHOGRAPHIC : cfg.projection == "equirect" ? DMT_PROJECTION_EQUIRECT
+                       : cfg.projection == "fisheye"    ? DMT_PROJECTION_FISHEYE : DMT_PROJECTION_PERSPECTIVE;
+    scene.projectionParam = cfg.orthoHeightSet ? cfg.orthoHeight : cfg.fisheyeFovSet ? cfg.fisheyeFov : 0.f;
+  }
+  if (scene.projection != DMT_PROJECTION_PERSPECTIVE) {  // what the library refuses under the projection, before anything is rendered
+    char const* why = nullptr;
+    if (scene.lensRadius > 0.f) why = "dmt_set_projection: a thin lens (dmt_set_lens, radius > 0) is set; only the perspective camera has one";
+    else if (cfg.denoise) why = "dmt_denoise: the depth scale and the reprojection are the perspective camera's (dmt_set_projection set another projection)";
+    else if (cfg.textureFilter) why = "dmt_render: the first-hit texture filter together with another projection than the perspective one (dmt_set_projection) is not supported";
+    else if (cfg.focusPixelSet) why = "dmt_focus_distance_at: the autofocus ray is the pinhole's (dmt_set_projection set another projection)";
+    if (why) {
+      std::fprintf(stderr, "--projection / the scene's projection: %s\n", why);
+      return 1;
+    }
+  }
   if (cfg.mediumSet) {  // --medium replaces the scene file's medium; the default box is the bounds of the triangles
     scene.hasMedium = cfg.mediumSigmaT > 0.f, scene.mediumSigmaT = cfg.mediumSigmaT, scene.mediumG = cfg.mediumG;
     for (int i = 0; i < 3; ++i) scene.mediumAlbedo[i] = cfg.mediumAlbedo[i];

@@ -64,6 +64,11 @@ class HostScene:
         lr, fd = C.c_float(), C.c_float()
         L.dmt_host_scene_lens(h, C.byref(lr), C.byref(fd))
         self.lens = (lr.value, fd.value)  # thin lens beside the camera record: (radius, focus distance); radius 0 = pinhole
+        pk, pp = C.c_int(), C.c_float()
+        L.dmt_host_scene_projection(h, C.byref(pk), C.byref(pp))
+        # the projection the scene records (JSON camera.projection) beside the camera record, as the lens: (kind, param);
+        # (0, 0.0) is the perspective camera, which upload_scene sets like any other
+        self.projection = (pk.value, pp.value)
         # the pixel filter the file records (PBRT PixelFilter, JSON film.filter): dict(type, kind, radius, sigma) or None; kind is
         # the library's FILTER_* value, or None for a kind it does not offer (mitchell, sinc).  Applied only by
         # upload_scene(scene, pixel_filter=True).
@@ -258,6 +263,7 @@ class ArrayScene:
         self.env_rgb = None if env_rgb is None else np.ascontiguousarray(env_rgb, np.float32)
         self.env_quat, self.env_scale = np.array([0, 0, 0, 1], np.float32), 1.0
         self.lens = None  # (lens_radius, focus_distance) to have upload_scene set the lens; None leaves the context's
+        self.projection = None  # (kind, param) to have upload_scene set the projection; None leaves the context's
         self.pixel_filter = None  # dict(type, kind, radius, sigma) for upload_scene(pixel_filter=True); None leaves the context's
         self.tri_normals = None  # [n, 9] vertex normals for upload_scene(vertex_normals=True)
 

@@ -169,6 +169,63 @@ int dmt_pixel_filter_table(int kind, float radius, float param, float* knots257)
 int dmt_pixel_filter_positions(int width, int height, int kind, float radius, float param, int n, const int32_t* pxs, const int32_t* pys,
                                const int32_t* ss, float* xy2);
 
+/* ---- camera projections: orthographic, equirectangular, fisheye (opt-in, beyond the reference) ---- */
+/* Context state beside the camera, like the lens and the filter: dmt_camera does not change, and the projection survives
+ * dmt_set_camera and scene uploads.  A projection changes which ray a sample traces and nothing else about the sample, so
+ * every kernel row runs under it (media, motion, cutouts, textures, the emitter tree, both accel modes), and every render
+ * path traces its rays: dmt_render, its sampler table, the wavefront form, dmt_render_adaptive, the feature pass
+ * dmt_render_aovs and the trace probes.  Perspective, the default, launches what it always launched: every film is
+ * byte-identical to one of a context that never saw this call.
+ *
+ * param: the view height in scene units for orthographic (finite, > 0); the field of view across the film's DIAGONAL in
+ * degrees for fisheye (finite, 0 < fov <= 360); ignored for perspective and equirect.  DMT_ERR_INVALID, and the state
+ * untouched, for an unknown kind or a bad param.
+ *
+ * The models, in camera space (x right, y up, z forward; the world is z-up), for the continuous film position (fx, fy) of
+ * a W x H film, fp32 without contraction; (cx, cy, focal) = cameraFromRaster (fx, fy, 0); every direction is normalised once.
+ *   orthographic   k = param / (sensor_size 0.001f), formed once on the host
+ *                  o = renderFromCamera point(cx k, cy k, 0);  d = the forward column of renderFromCamera
+ *                  The film's height spans param scene units; with param = sensor D / focal it frames depth D as the
+ *                  perspective camera does.  inverse: fx = (c.x / k - tx) ipx, fy = (c.y / k - ty) ipy, depth = c.z
+ *   equirect       u = fx / W, v = fy / H, lon = (u - 0.5) 2 pi, lat = (0.5 - v) pi          (the full sphere)
+ *                  d_cam = (cos lat sin lon, sin lat, cos lat cos lon);  o = the camera position
+ *                  The film's centre looks along dir, the top row up, the left and right edges meet behind the camera.
+ *                  inverse: lon = atan2(c.x, c.z), lat = atan2(c.y, hypot(c.x, c.z)), depth = |c|
+ *   fisheye        x = fx - W / 2, y = H / 2 - fy, r = sqrt(x x + y y), theta = r s          (equidistant, full frame)
+ *                  s = (fov / 2 in radians) / (sqrt(W W + H H) / 2), formed once on the host: the fov is reached at the
+ *                  film's corners, so every pixel has a ray
+ *                  d_cam = (sin theta x / r, sin theta y / r, cos theta), (0, 0, 1) at r = 0;  o = the camera position
+ *                  inverse: theta = atan2(hypot(c.x, c.y), c.z), r = theta / s, depth = |c|
+ * A wide pixel filter can push (fx, fy) slightly outside the film; the angles then leave their nominal range by a fraction
+ * of a pixel's worth.  Nothing is clamped.
+ *
+ * What another projection than the perspective one refuses, each with DMT_ERR_STATE and a message that names
+ * dmt_set_projection, and nothing else changed: a lens (dmt_set_projection while the lens radius is > 0, and dmt_set_lens
+ * with a radius > 0 under the projection); a render whose kernels use the first-hit texture filter, whose footprints are
+ * the pinhole's differentials; a render, or a trace probe, of one of the two kernel rows that are compiled without the
+ * projection's ray because they spill a register more with it: a scene under an env map with no other
+ * surface feature in brute-force mode (set DMT_ACCEL_BVH), and an env map with the BVH and the light tree (use the uniform
+ * pick); dmt_denoise and dmt_denoise_temporal, whose depth scale and reprojection are the pinhole's
+ * (the temporal history is left as it was); dmt_focus_distance_at.  Not offered: partial panoramas, circular fisheyes with
+ * dead pixels, camera motion, the PBRT front end's other cameras. */
+enum {
+  DMT_PROJECTION_PERSPECTIVE = 0,
+  DMT_PROJECTION_ORTHOGRAPHIC = 1, /* param = the view height, in scene units */
+  DMT_PROJECTION_EQUIRECT = 2,
+  DMT_PROJECTION_FISHEYE = 3,      /* param = the field of view across the film's diagonal, in degrees */
+};
+int dmt_set_projection(dmt_ctx* ctx, int kind, float param);
+/* either output may be null; *param = 0 for the kinds that ignore it */
+int dmt_projection_info(dmt_ctx* ctx, int* kind, float* param);
+/* host only (no GPU): the serial twin of the device's rays.  Rays (o3, d3: n x 3) through the continuous film positions
+ * xy2 (n x 2; (fx, fy) as dmt_camera_project defines them) of the camera under the projection; perspective gives the
+ * pinhole rays.  The device's arithmetic with the host's division, square root, sine and cosine.
+ * DMT_ERR_INVALID for arguments dmt_set_projection would refuse. */
+int dmt_projection_rays(const dmt_camera* cam, int kind, float param, int n, const float* xy2, float* o3, float* d3);
+/* host only (no GPU): the inverse, render-space points p3 (n x 3) -> film positions xy2 (n x 2) and depth (n): the
+ * camera-space z for perspective (dmt_camera_project) and orthographic, the distance from the camera for the angular models. */
+int dmt_projection_project(const dmt_camera* cam, int kind, float param, int n, const float* p3, float* xy2, float* depth);
+
 /* ---- motion blur: linear vertex motion over a shutter interval (opt-in, beyond the reference) ---- */
 /* Keys.  Key 0 is the positions the context holds (dmt_upload_triangles, dmt_update_vertices*).  Key 1 is a second position
  * set for the same triangles (dmt_set_motion).  Motion is active exactly when key 1 is present; without it every film is
