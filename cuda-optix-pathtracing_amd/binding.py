@@ -77,6 +77,8 @@ EXPORTED_SYMBOLS = [
     "dmt_update_vertices", "dmt_update_vertices_device", "dmt_set_accel_update", "dmt_accel_update_info", "dmt_bvh_refit_reference",
     "dmt_download_aov_surface", "dmt_upload_aov_surface", "dmt_camera_project", "dmt_test_camera_project", "dmt_temporal_defaults",
     "dmt_denoise_temporal", "dmt_temporal_reset", "dmt_temporal_info", "dmt_temporal_download",
+    "dmt_display_defaults", "dmt_display", "dmt_display_device", "dmt_display_info", "dmt_display_curve", "dmt_display_metering",
+    "dmt_display_bin",
     "dmt_set_sampler_table", "dmt_sampler_table_plan", "dmt_test_sampler_table",
     "dmt_set_lens", "dmt_lens_info", "dmt_lens_rays", "dmt_focus_distance_at", "dmt_test_lens_values",
     "dmt_set_pixel_filter", "dmt_pixel_filter_info", "dmt_pixel_filter_table", "dmt_pixel_filter_positions", "dmt_test_film_positions",
@@ -156,6 +158,79 @@ def temporal_defaults():
     lib.dmt_temporal_defaults.restype = TemporalParams
     p = lib.dmt_temporal_defaults()
     return {name: getattr(p, name) for name, _ in TemporalParams._fields_}
+
+
+# dmt_display_params enums (include/dmt_hip.h)
+TONE_LINEAR, TONE_REINHARD, TONE_ACES, TONE_HABLE = 0, 1, 2, 3
+OETF_LINEAR, OETF_SRGB, OETF_GAMMA22 = 0, 1, 2
+QUANT_TRUNCATE, QUANT_ROUND, QUANT_DITHER = 0, 1, 2
+
+
+class DisplayParams(C.Structure):
+    """dmt_display_params (include/dmt_hip.h)"""
+    _fields_ = [("auto_exposure", C.c_int32), ("exposure_ev", C.c_float), ("key", C.c_float), ("low_fraction", C.c_float),
+                ("high_fraction", C.c_float), ("bloom_levels", C.c_int32), ("bloom_strength", C.c_float), ("tone", C.c_int32),
+                ("white", C.c_float), ("oetf", C.c_int32), ("quantiser", C.c_int32)]
+
+
+class DisplayRecord(C.Structure):
+    """dmt_display_record (include/dmt_hip.h)"""
+    _fields_ = [("histogram", C.c_uint32 * 256), ("counted", C.c_uint32), ("skipped", C.c_uint32), ("nonfinite", C.c_uint32),
+                ("levels", C.c_int32), ("avg_log2", C.c_double), ("scale", C.c_float), ("histogram_ms", C.c_float),
+                ("bloom_ms", C.c_float), ("resolve_ms", C.c_float), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+def display_defaults():
+    """dmt_display_defaults() as a dict: auto_exposure, exposure_ev, key, low_fraction, high_fraction, bloom_levels,
+    bloom_strength, tone, white, oetf, quantiser."""
+    lib = load_library()
+    lib.dmt_display_defaults.restype = DisplayParams
+    p = lib.dmt_display_defaults()
+    return {name: getattr(p, name) for name, _ in DisplayParams._fields_}
+
+
+def _display_params(params):
+    p = display_defaults()
+    unknown = set(params or {}) - set(p)
+    if unknown:
+        raise ValueError(f"unknown display parameters {sorted(unknown)}")
+    p.update(params or {})
+    return DisplayParams(*[(int if t is C.c_int32 else float)(p[name]) for name, t in DisplayParams._fields_])
+
+
+def display_curve(rgb, params=None):
+    """Host only (dmt_display_curve): the tone curve and the transfer function of `params` on already exposed rgb triples."""
+    a = np.ascontiguousarray(rgb, np.float32)
+    assert a.shape[-1] == 3
+    out = np.zeros_like(a)
+    cp = _display_params(params)
+    rc = load_library().dmt_display_curve(C.byref(cp), int(a.size // 3), a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise DmtError(f"dmt_display_curve failed ({rc})")
+    return out
+
+
+def display_metering(histogram, params=None):
+    """Host only (dmt_display_metering): (avg_log2, scale) of a 256-bin histogram under the parameters' key, fractions and
+    exposure_ev; scale is a numpy float32."""
+    h = np.ascontiguousarray(histogram, np.uint32)
+    assert h.shape == (256,)
+    cp = _display_params(params)
+    avg, scale = C.c_double(), C.c_float()
+    rc = load_library().dmt_display_metering(C.byref(cp), h.ctypes.data_as(C.c_void_p), C.byref(avg), C.byref(scale))
+    if rc != 0:
+        raise DmtError(f"dmt_display_metering failed ({rc})")
+    return avg.value, np.float32(scale.value)
+
+
+def display_bin(y):
+    """Host only (dmt_display_bin): the histogram bin of each luminance, int32; -1 where the meter skips it."""
+    a = np.ascontiguousarray(y, np.float32)
+    out = np.zeros(a.shape, np.int32)
+    rc = load_library().dmt_display_bin(int(a.size), a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise DmtError(f"dmt_display_bin failed ({rc})")
+    return out
 
 
 def camera_project(camera44, points):
@@ -805,6 +880,7 @@ class Renderer:
         self.width = self.height = 0
         self._aov_shape = None      # (height, width) of the AOVs on the device
         self.denoise_ms = 0.0       # HIP-event time of the last denoise()
+        self.display_ms = 0.0       # HIP-event time of the last display()
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -1462,6 +1538,47 @@ class Renderer:
         ln = np.zeros((self.height, self.width), np.float32)
         self._check(self._lib.dmt_temporal_download(self._ctx, _p(cv), _p(ln)), "dmt_temporal_download")
         return cv, ln
+
+    # ---- display transform ------------------------------------------------------
+    def display(self, params=None, image=None, want=("float", "u8")):
+        """dmt_display: a linear plane (the context's film mean, or `image`, an H x W x 4 host array of the camera's size)
+        through exposure, bloom, tone curve, transfer function and quantiser.  `params`: a dict overriding
+        display_defaults().  `want` names the outputs: "float" (H x W x 4 float32, w = 1) and / or "u8" (H x W x 4 uint8,
+        A = 255).  Returns them in that order, or the one array when one is asked for.  Synchronous; the kernels' HIP-event
+        time lands in self.display_ms, display_info() has the rest."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or set(want) - {"float", "u8"}:
+            raise ValueError(f"want must name 'float' and / or 'u8', got {want!r}")
+        cp = _display_params(params)
+        src = None
+        if image is not None:
+            src = _f32(image)
+            assert src.shape == (self.height, self.width, 4)
+        out4 = np.zeros((self.height, self.width, 4), np.float32) if "float" in want else None
+        out8 = np.zeros((self.height, self.width, 4), np.uint8) if "u8" in want else None
+        ms = C.c_float()
+        self._check(self._lib.dmt_display(self._ctx, C.byref(cp), _p(src), _p(out4), _p(out8), C.byref(ms)), "dmt_display")
+        self.display_ms = ms.value
+        outs = tuple(out4 if w == "float" else out8 for w in want)
+        return outs[0] if len(outs) == 1 else outs
+
+    def display_device(self, params=None, src_ptr=None, out4_ptr=None, out8_ptr=None):
+        """dmt_display_device: display() on device pointers (e.g. torch data_ptr()): the source plane (None: the film mean),
+        the float4 output and the RGBA8 output (either None, not both).  Asynchronous on the context's stream, except that
+        auto exposure waits for its histogram."""
+        cp = _display_params(params)
+        self._check(self._lib.dmt_display_device(self._ctx, C.byref(cp), C.c_void_p(src_ptr), C.c_void_p(out4_ptr),
+                                                 C.c_void_p(out8_ptr)), "dmt_display_device")
+
+    def display_info(self):
+        """dict of the last display call: histogram (uint32[256]), counted, skipped, nonfinite, levels, avg_log2, scale,
+        histogram_ms, bloom_ms, resolve_ms, width, height.  Waits for the stream after display_device()."""
+        rec = DisplayRecord()
+        self._check(self._lib.dmt_display_info(self._ctx, C.byref(rec)), "dmt_display_info")
+        out = {name: getattr(rec, name) for name, _ in DisplayRecord._fields_ if name != "histogram"}
+        out["histogram"] = np.array(rec.histogram, np.uint32)
+        out["scale"] = np.float32(rec.scale)
+        return out
 
     def test_camera_project(self, points):
         """dmt_test_camera_project: camera_project() on the device under the context's camera."""

@@ -1932,6 +1932,7 @@ __global__ void __launch_bounds__(256) k_adaptive_mask(AdaptiveArgs A) {
 
 #include "wavefront.hpp"
 #include "denoise.hpp"
+#include "display.hpp"
 
 }  // namespace
 
@@ -1972,6 +1973,8 @@ struct dmt_ctx {
   LaunchState launch;
   // the image-space layer: feature planes, the filter's scratch, the temporal history (denoise.hpp, denoise_host.hpp)
   DenoiseState dn;
+  // the display transform: its scratch planes, the bloom pyramid, the record of the last call (display.hpp, display_host.hpp)
+  DisplayState disp;
   int maxDepth = 32;
   int accel = DMT_ACCEL_BRUTE_FORCE;
 };
@@ -2141,6 +2144,9 @@ int finishTest(dmt_ctx* ctx) {
 
 // the image-space layer's entry points and the rules of its state; it uses the helpers above
 #include "denoise_host.hpp"
+
+// the display transform's entry points and host twins; of the context they read the camera's size, the film and the stream
+#include "display_host.hpp"
 
 extern "C" {
 

@@ -226,5 +226,8 @@ void dmt_host_film_to_rgb8(const float* mean4, const float* m24, uint64_t pixels
 int dmt_host_write_mean_and_mse(const float* mean4, const float* m24, uint32_t width, uint32_t height, const char* baseName) {
   return writeMeanAndMSERowMajor(mean4, m24, width, height, baseName) ? 0 : 1;
 }
+int dmt_host_write_pfm(const float* mean4, uint32_t width, uint32_t height, const char* path) {
+  return writePfmRgb(path, mean4, width, height) ? 0 : 1;
+}
 
 }  // extern "C"

@@ -390,6 +390,29 @@ bool writePngRgb8(std::string const& path, uint8_t const* rgb, uint32_t width, u
   return ok ? true : failWith("short write");
 }
 
+bool writePfmRgb(std::string const& path, float const* mean4, uint32_t width, uint32_t height, std::string* error) {
+  auto failWith = [&](char const* m) {
+    if (error) *error = std::string(m) + ": " + path;
+    return false;
+  };
+  FILE* fp = fopen(path.c_str(), "wb");
+  if (!fp) return failWith("cannot open for writing");
+  bool ok = fprintf(fp, "PF\n%u %u\n-1.0\n", width, height) > 0;
+  std::vector<uint8_t> row(size_t(width) * 12);
+  for (uint32_t y = height; ok && y-- > 0;) {  // the format's first row is the bottom one
+    for (uint32_t x = 0; x < width; ++x)
+      for (int c = 0; c < 3; ++c) {
+        uint32_t bits;
+        memcpy(&bits, mean4 + 4 * (size_t(y) * width + x) + c, 4);
+        uint8_t* const p = row.data() + 12 * size_t(x) + 4 * c;
+        p[0] = uint8_t(bits), p[1] = uint8_t(bits >> 8), p[2] = uint8_t(bits >> 16), p[3] = uint8_t(bits >> 24);
+      }
+    ok = fwrite(row.data(), 1, row.size(), fp) == row.size();
+  }
+  ok = (fclose(fp) == 0) && ok;
+  return ok ? true : failWith("short write");
+}
+
 bool writeMeanAndMSERowMajor(float const* mean4, float const* m24, uint32_t width, uint32_t height,
                              std::string const& baseName, std::string* error) {
   size_t const n = size_t(width) * height;

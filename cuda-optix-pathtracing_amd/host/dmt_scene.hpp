@@ -194,6 +194,10 @@ bool writeMeanAndMSERowMajor(float const* mean4, float const* m24, uint32_t widt
                              std::string const& baseName, std::string* error = nullptr);
 bool writePngRgb8(std::string const& path, uint8_t const* rgb, uint32_t width, uint32_t height,
                   std::string* error = nullptr);
+// The linear film as a Portable Float Map: "PF\n<w> <h>\n-1.0\n", then the rgb of mean4 as little-endian float32, rows
+// bottom to top as the format has them.  Nothing is clamped or scrubbed.
+bool writePfmRgb(std::string const& path, float const* mean4, uint32_t width, uint32_t height,
+                 std::string* error = nullptr);
 
 // upload a Scene through the C ABI (triSoupFromTriangles + deviceBSDF + deviceLights +
 // deviceCamera + allocateDeviceConstantMemory in the reference, megakernel/main.cu:110-117)

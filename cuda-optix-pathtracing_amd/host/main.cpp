@@ -75,6 +75,14 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
   std::string mediumGridPath;  // --medium-grid FILE: a density grid for the medium (dmt_set_medium_grid), a NumPy .npy file
   bool bvhBuildSet = false;   // --bvh-build host|gpu: who builds the tree of --bvh (dmt_set_accel_build)
   std::string bvhBuildArg;
+  // the display transform (dmt_display): any of these also writes output-<spp>_display.png.  --tonemap, --exposure EV|auto,
+  // --exposure-key K, --white W, --bloom S, --bloom-levels K, --oetf, --dither
+  bool display = false;
+  std::string tonemap = "aces", exposure = "0", oetf = "srgb";
+  bool exposureKeySet = false, whiteSet = false, bloomSet = false, bloomLevelsSet = false, dither = false;
+  float exposureKey = 0.18f, white = 0.f, bloom = 0.f;
+  int bloomLevels = 5;        // the levels of --bloom unless --bloom-levels says otherwise
+  bool hdr = false;           // --hdr: also write output-<spp>.pfm, the linear mean
 
   // --shading-normals' value: off, file, smooth or smooth:DEG with 0 <= DEG <= 180
   static bool parseShadingNormals(std::string const& a, float& crease) {
@@ -164,7 +172,39 @@ struct Config {  // defaults: CC/public/cuda-core/host_utils.cuh:25-31
     if (!mediumGridPath.empty() && mediumSet && !(mediumSigmaT > 0.f)) return "--medium-grid needs a medium: --medium 0 switches it off";
     if (mediumSet && mediumSigmaT > 0.f && denoise) return "--medium and --denoise exclude each other (the feature buffers do not know the fog)";
     if (aovSpp < 1 || aovSpp > 65536) return "invalid --aov-spp: expected 1..65536, got " + std::to_string(aovSpp);
+    if (tonemap != "linear" && tonemap != "reinhard" && tonemap != "aces" && tonemap != "hable")
+      return "invalid --tonemap: expected linear, reinhard, aces or hable, got '" + tonemap + "'";
+    if (oetf != "linear" && oetf != "srgb" && oetf != "gamma22") return "invalid --oetf: expected linear, srgb or gamma22, got '" + oetf + "'";
+    if (float ev = 0.f; exposure != "auto" && !parseNumber(exposure, ev)) return "invalid --exposure: expected a finite EV or auto, got '" + exposure + "'";
+    if (exposureKeySet && exposure != "auto") return "--exposure-key needs --exposure auto";
+    if (exposureKeySet && !(std::isfinite(exposureKey) && exposureKey > 0.f)) return "invalid --exposure-key: expected a finite key > 0";
+    if (whiteSet && !(std::isfinite(white) && white > 0.f)) return "invalid --white: expected a finite white point > 0";
+    if (whiteSet && tonemap != "reinhard" && tonemap != "hable") return "--white needs --tonemap reinhard or hable";
+    if (bloomSet && !(bloom >= 0.f && bloom <= 1.f)) return "invalid --bloom: expected a strength in [0, 1]";
+    if (bloomLevelsSet && !bloomSet) return "--bloom-levels needs --bloom";
+    if (bloomLevelsSet && (bloomLevels < 0 || bloomLevels > 8)) return "invalid --bloom-levels: expected 0..8, got " + std::to_string(bloomLevels);
     return "";
+  }
+  // a finite number and nothing else
+  static bool parseNumber(std::string const& a, float& out) {
+    char* end = nullptr;
+    float const v = std::strtof(a.c_str(), &end);
+    if (a.empty() || end != a.c_str() + a.size() || !std::isfinite(v)) return false;
+    out = v;
+    return true;
+  }
+  // the parameters of the flags, over dmt_display_defaults()
+  dmt_display_params displayParams() const {
+    dmt_display_params p = dmt_display_defaults();
+    p.tone = tonemap == "linear" ? DMT_TONE_LINEAR : tonemap == "reinhard" ? DMT_TONE_REINHARD : tonemap == "hable" ? DMT_TONE_HABLE : DMT_TONE_ACES;
+    p.oetf = oetf == "linear" ? DMT_OETF_LINEAR : oetf == "gamma22" ? DMT_OETF_GAMMA22 : DMT_OETF_SRGB;
+    p.auto_exposure = exposure == "auto" ? 1 : 0;
+    if (!p.auto_exposure) parseNumber(exposure, p.exposure_ev);
+    if (exposureKeySet) p.key = exposureKey;
+    if (whiteSet) p.white = white;
+    if (bloomSet) p.bloom_strength = bloom, p.bloom_levels = bloomLevels;
+    if (dither) p.quantiser = DMT_QUANT_DITHER;
+    return p;
   }
 };
 
@@ -243,7 +283,20 @@ void printHelp() {
       "  --medium-grid <FILE> -- A density grid that fills the medium's box: the extinction in a voxel is SIGMA_T times its\n"
       "                       density, marched exactly.  A NumPy .npy file (version 1.0 or 2.0, little-endian float32, C order,\n"
       "                       shape (nz, ny, nx), values finite and >= 0).  Needs a medium, from --medium or the scene file;\n"
-      "                       replaces the scene file's \"grid\"");
+      "                       replaces the scene file's \"grid\"\n"
+      "  --tonemap <linear|reinhard|aces|hable> -- Display transform: any of this and the next seven flags also writes\n"
+      "                       output-<spp>_display.png (and output-<spp>_denoised_display.png with --denoise): the linear film\n"
+      "                       through exposure, bloom, this tone curve (default aces), a transfer function and a rounding\n"
+      "                       quantiser, on the GPU.  Every other output stays as without them\n"
+      "  --exposure <EV|auto> -- Exposure in stops (default 0), or auto: metered from a histogram of the log luminance so\n"
+      "                       that its trimmed average lands on the key\n"
+      "  --exposure-key <K> -- The key of --exposure auto (default 0.18)\n"
+      "  --white <W>       -- White point of --tonemap reinhard (default 4) or hable (default 11.2)\n"
+      "  --bloom <S>       -- Bloom strength in [0, 1] (default 0: none): the frame mixed with a blur pyramid of itself\n"
+      "  --bloom-levels <K> -- Levels of that pyramid, 0..8 (default 5)\n"
+      "  --oetf <linear|srgb|gamma22> -- Transfer function (default srgb)\n"
+      "  --dither          -- Quantise with an 8x8 ordered dither instead of rounding\n"
+      "  --hdr             -- Also write output-<spp>.pfm: the linear mean as a little-endian RGB Portable Float Map");
 }
 
 Config parseArguments(int argc, char** argv) {
@@ -295,6 +348,15 @@ Config parseArguments(int argc, char** argv) {
       for (float& v : c.mediumBox) v = std::strtof(argv[++i], nullptr);
       c.mediumBoxSet = true;
     }
+    else if (a == "--tonemap" && more) c.tonemap = argv[++i], c.display = true;
+    else if (a == "--exposure" && more) c.exposure = argv[++i], c.display = true;
+    else if (a == "--exposure-key" && more) c.exposureKey = std::strtof(argv[++i], nullptr), c.exposureKeySet = c.display = true;
+    else if (a == "--white" && more) c.white = std::strtof(argv[++i], nullptr), c.whiteSet = c.display = true;
+    else if (a == "--bloom" && more) c.bloom = std::strtof(argv[++i], nullptr), c.bloomSet = c.display = true;
+    else if (a == "--bloom-levels" && more) c.bloomLevels = std::atoi(argv[++i]), c.bloomLevelsSet = c.display = true;
+    else if (a == "--oetf" && more) c.oetf = argv[++i], c.display = true;
+    else if (a == "--dither") c.dither = c.display = true;
+    else if (a == "--hdr") c.hdr = true;
     else if (a == "--log-level" && more) c.logLevel = argv[++i];
     else if (a == "--save-partial") c.savePartial = true;
     else if (a == "--max-depth" && more) c.maxDepth = std::atoi(argv[++i]), c.depthSet = true;
@@ -601,13 +663,14 @@ int main(int argc, char** argv) {
   }
   double aovMs = 0.0, denoiseMs = 0.0;
   float denoiseKernelMs = 0.f;
+  std::vector<float> den;  // --denoise: the filtered plane, kept for the display transform
   if (cfg.denoise) {  // feature buffers on the first context (they cover the whole frame), filter on the combined host film
     auto const t0 = std::chrono::steady_clock::now();
     if (dmt_render_aovs(C.v[0], uint32_t(cfg.aovSpp)) != DMT_OK) return fail(C.v[0], "dmt_render_aovs");
     if (dmt_sync(C.v[0]) != DMT_OK) return fail(C.v[0], "dmt_sync");
     aovMs = msSince(t0);
     auto const t1 = std::chrono::steady_clock::now();
-    std::vector<float> den(4 * pixels);
+    den.resize(4 * pixels);
     if (dmt_denoise(C.v[0], nullptr, mean.data(), m2.data(), den.data(), &denoiseKernelMs) != DMT_OK) return fail(C.v[0], "dmt_denoise");
     denoiseMs = msSince(t1);
     auto const t2 = std::chrono::steady_clock::now();
@@ -620,6 +683,40 @@ int main(int argc, char** argv) {
       return 1;
     }
     writeMs += msSince(t2);
+  }
+  double displayMs = 0.0;
+  float displayKernelMs = 0.f;
+  dmt_display_record displayRec{};
+  if (cfg.display) {  // on the first context, from the combined host film, as the denoiser
+    dmt_display_params const dp = cfg.displayParams();
+    std::vector<uint8_t> rgba(4 * pixels), rgb(3 * pixels);
+    auto show = [&](float const* plane, std::string const& name) {
+      auto const t0 = std::chrono::steady_clock::now();
+      float ms = 0.f;
+      if (dmt_display(C.v[0], &dp, plane, nullptr, rgba.data(), &ms) != DMT_OK) return fail(C.v[0], "dmt_display"), false;
+      displayMs += msSince(t0), displayKernelMs += ms;
+      auto const t1 = std::chrono::steady_clock::now();
+      for (size_t i = 0; i < pixels; ++i) rgb[3 * i] = rgba[4 * i], rgb[3 * i + 1] = rgba[4 * i + 1], rgb[3 * i + 2] = rgba[4 * i + 2];
+      std::string err;
+      if (!dmt_host::writePngRgb8(dir + "/output-" + std::to_string(lastSamples) + name, rgb.data(), uint32_t(cfg.width), uint32_t(cfg.height), &err)) {
+        std::fprintf(stderr, "%s\n", err.c_str());
+        return false;
+      }
+      writeMs += msSince(t1);
+      return true;
+    };
+    if (!show(mean.data(), "_display.png")) return 1;
+    if (dmt_display_info(C.v[0], &displayRec) != DMT_OK) return fail(C.v[0], "dmt_display_info");  // the film's, not the denoised plane's
+    if (cfg.denoise && !show(den.data(), "_denoised_display.png")) return 1;
+  }
+  if (cfg.hdr) {
+    auto const t0 = std::chrono::steady_clock::now();
+    std::string err;
+    if (!dmt_host::writePfmRgb(dir + "/output-" + std::to_string(lastSamples) + ".pfm", mean.data(), uint32_t(cfg.width), uint32_t(cfg.height), &err)) {
+      std::fprintf(stderr, "%s\n", err.c_str());
+      return 1;
+    }
+    writeMs += msSince(t0);
   }
   double const samples = cfg.adaptive ? double(adaptiveSamples) : double(pixels) * double(launches) * double(cfg.kspp);
   std::printf("Done! Total Execution Time(excl write file): %llu ms | Average Execution per Kernel launch (%d spp): %llu ms | %.2f Msamples/s\n",
@@ -652,6 +749,9 @@ int main(int argc, char** argv) {
     if (cfg.denoise)
       std::printf(" - denoise:                   AOVs %.3f ms (%d spp, launch + sync), filter %.3f ms (kernels, HIP events; %.3f ms with copies)\n",
                   aovMs, cfg.aovSpp, double(denoiseKernelMs), denoiseMs);
+    if (cfg.display)
+      std::printf(" - display:                   %.3f ms (kernels, HIP events; %.3f ms with copies), exposure scale %.6g%s, %d bloom level(s)\n",
+                  double(displayKernelMs), displayMs, double(displayRec.scale), cfg.exposure == "auto" ? " (metered)" : "", int(displayRec.levels));
   }
   std::puts("Cleanup...");
   return 0;

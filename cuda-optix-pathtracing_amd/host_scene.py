@@ -250,6 +250,15 @@ def write_mean_and_mse(mean, m2, base_name):
         raise RuntimeError(f"writing {base_name}.png failed")
 
 
+def write_pfm(mean, path):
+    """The rgb of an H x W x 4 float32 plane as a little-endian Portable Float Map (the CLI's --hdr writer)."""
+    mean = np.ascontiguousarray(mean, np.float32)
+    h, w = mean.shape[:2]
+    rc = load_host_library().dmt_host_write_pfm(mean.ctypes.data_as(C.c_void_p), C.c_uint32(w), C.c_uint32(h), str(path).encode())
+    if rc != 0:
+        raise RuntimeError(f"writing {path} failed")
+
+
 class ArrayScene:
     """A scene assembled from numpy arrays (same attributes as HostScene)."""
 

@@ -988,6 +988,78 @@ int dmt_temporal_info(dmt_ctx* ctx, dmt_temporal_record* out);
  * float), either may be NULL; DMT_ERR_STATE without a history */
 int dmt_temporal_download(dmt_ctx* ctx, float* color_var4, float* length1);
 
+/* ---- display transform (an explicit post-process; beyond the reference) ----- */
+/* A linear RGB plane (the film's mean, or any plane of the camera's size) to a display-referred one, in this order:
+ *   0 scrub     a component that is not finite or is negative becomes 0 (pixels with a non-finite component are counted);
+ *   1 exposure  c = scale * rgb.  Manual: scale = 2^exposure_ev.  Auto: metered from a histogram of the log luminance
+ *               y = (0.2126 r + 0.7152 g) + 0.0722 b, eight bins per stop over [2^-16, 2^16) taken from the float's bits
+ *               (dmt_display_bin); pixels with y <= 0 are skipped.  Of the T counted pixels the mass between
+ *               low_fraction T and (1 - high_fraction) T is kept, avg is its mean log2 luminance (bin k stands for
+ *               floor(k/8) - 16 + log2(1 + (k mod 8 + 0.5) / 8)) and scale = key / 2^avg * 2^exposure_ev, in double, rounded
+ *               once (dmt_display_metering).  Nothing counted: scale = 2^exposure_ev;
+ *   2 bloom     a mean-preserving pyramid without a threshold: K' = min(bloom_levels, floor(log2(min(w, h)))) levels, each a
+ *               2x2 box average of the one below (edges clamped), summed back up through a separable (0.75, 0.25) upsample,
+ *               divided by K' + 1 and mixed in: c + bloom_strength (bloom - c).  Off at 0 levels or strength 0;
+ *   3 tone      LINEAR; REINHARD (extended, on luminance, white point `white`, default 4); ACES (Narkowicz's fit, per
+ *               channel); HABLE (Uncharted 2's curve at 2x over its value at `white`, default 11.2).  Clamped to [0, 1];
+ *   4 transfer  LINEAR; SRGB (the piecewise sRGB OETF); GAMMA22 (x^(1/2.2)).  Clamped to [0, 1]: the float output, w = 1;
+ *   5 quantise  to RGBA8, A = 255: TRUNCATE floor(min(255 v, 255)); ROUND floor(min(255 v + 0.5, 255)); DITHER
+ *               floor(min(255 v + (M[y & 7][x & 7] + 0.5) / 64, 255)), M the 8 x 8 Bayer index matrix.
+ * LINEAR / LINEAR / TRUNCATE at 0 EV without bloom is the rule of the PNG writer.  The same plane always gives the same bytes:
+ * the histogram is integer, the metering is the host's, and stages 0, 1 and 5 round once per operation.  The device flushes
+ * fp32 denormals, so a luminance below 2^-126 is skipped there where dmt_display_bin counts it. */
+enum { DMT_TONE_LINEAR = 0, DMT_TONE_REINHARD = 1, DMT_TONE_ACES = 2, DMT_TONE_HABLE = 3 };
+enum { DMT_OETF_LINEAR = 0, DMT_OETF_SRGB = 1, DMT_OETF_GAMMA22 = 2 };
+enum { DMT_QUANT_TRUNCATE = 0, DMT_QUANT_ROUND = 1, DMT_QUANT_DITHER = 2 };
+typedef struct dmt_display_params {
+  int32_t auto_exposure;  /* 0: manual, scale = 2^exposure_ev; otherwise metered, exposure_ev is a compensation on top */
+  float exposure_ev;
+  float key;              /* auto: the luminance the metered average is mapped to; > 0 */
+  float low_fraction;     /* auto: the share of the counted pixels trimmed at the dark end, and */
+  float high_fraction;    /*       at the bright end; each in [0, 1), their sum < 1 */
+  int32_t bloom_levels;   /* 0 .. 8 */
+  float bloom_strength;   /* 0 .. 1 */
+  int32_t tone;           /* DMT_TONE_* */
+  float white;            /* the curve's white point; 0: its default; >= 0 */
+  int32_t oetf;           /* DMT_OETF_* */
+  int32_t quantiser;      /* DMT_QUANT_* */
+} dmt_display_params;
+/* manual 0 EV, key 0.18, fractions 0.10 / 0.05, no bloom (0 levels, strength 0), ACES, sRGB, ROUND, white 0 */
+dmt_display_params dmt_display_defaults(void);
+/* src4: a host plane of the camera's size (width x height float4, w ignored), or NULL for the context's film mean.  out4
+ * (float4, w = 1) and out_rgba8 (4 bytes per pixel) may each be NULL, not both.  params NULL: the defaults.  Synchronous;
+ * *kernel_ms (may be NULL) = HIP-event time of its kernels.  Never modifies the film, the AOVs or the temporal history.
+ * DMT_ERR_INVALID, with a message and nothing changed, for a non-finite parameter, key <= 0, a fraction outside [0, 1) or a
+ * sum >= 1, bloom_levels outside 0 .. 8, bloom_strength outside [0, 1], an unknown enum, white < 0, or both outputs NULL;
+ * DMT_ERR_STATE before dmt_set_camera, for a frame of more than 2^31 pixels, and for a NULL source on a context whose dmt_set_partition world is above 1 (its
+ * film holds its own tiles only: combine the ranks' films and pass the plane). */
+int dmt_display(dmt_ctx* ctx, const dmt_display_params* params, const float* src4, float* out4, uint8_t* out_rgba8, float* kernel_ms);
+/* The same with device pointers (e.g. torch data_ptr()): d_src4 NULL for the film mean; d_out4 / d_out_rgba8 as above.
+ * Asynchronous on the context's stream, with one exception: auto exposure reads the histogram back, so such a call has waited
+ * for the stream up to and including its histogram kernel when it returns. */
+int dmt_display_device(dmt_ctx* ctx, const dmt_display_params* params, const void* d_src4, void* d_out4, void* d_out_rgba8);
+typedef struct dmt_display_record {
+  uint32_t histogram[256]; /* last call, auto exposure: the counts; all 0 after a manual call */
+  uint32_t counted;        /* their sum T */
+  uint32_t skipped;        /* auto: pixels with y <= 0 */
+  uint32_t nonfinite;      /* pixels with a non-finite component */
+  int32_t levels;          /* bloom levels used, K' (0: no bloom ran) */
+  double avg_log2;         /* auto: the metered average; 0 when nothing was kept */
+  float scale;             /* the exposure applied */
+  float histogram_ms, bloom_ms, resolve_ms; /* HIP-event times of the stages' kernels; 0 for a stage that did not run */
+  int32_t width, height;   /* of the plane */
+} dmt_display_record;
+/* the record of the last dmt_display / dmt_display_device call; waits for the stream when that call was asynchronous.
+ * DMT_ERR_STATE before any call */
+int dmt_display_info(dmt_ctx* ctx, dmt_display_record* out);
+/* Host only (no GPU): the twins that tests and callers can use.
+ * dmt_display_curve: stages 3 and 4 on n already exposed rgb triples.  dmt_display_metering: avg_log2 and scale of a
+ * histogram under the parameters' key, fractions and exposure_ev.  dmt_display_bin: the bin of each luminance, -1 where the
+ * meter skips it.  DMT_ERR_INVALID for parameters dmt_display would refuse or a null array. */
+int dmt_display_curve(const dmt_display_params* params, int n, const float* rgb3_in, float* rgb3_out);
+int dmt_display_metering(const dmt_display_params* params, const uint32_t* histogram256, double* avg_log2, float* scale);
+int dmt_display_bin(int n, const float* y, int32_t* bin);
+
 /* ---- device unit-test entry points (GPU twins of the reference's T/tests kernels) ---------- */
 int dmt_test_triangle_intersect(dmt_ctx* ctx, const float* xs, const float* ys, const float* zs,
                                 size_t count, const float* o3, const float* d3, int32_t* hit,
